@@ -1,16 +1,21 @@
 #!/usr/bin/env python
 """bench.py — DeeperCut part-detector forward throughput on MI355X.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A step = one forward of the hot path (ResNet-152 FCN + deconvolution heads -> prob / loc_pred /
 next_pred) over one batch of synthetic input already resident in HBM, on every rank, followed (N>1)
-by the RCCL gather of the three score maps to rank 0.  Two timed regions of exactly K steps each are
-run: one forward at a time (kernel durations for the roofline), then with `--streams` (default 4 at batch 1)
+by the RCCL gather of the three score maps to rank 0.  `value` is the throughput of `--streams` (default 4 at batch 1)
 independent batch-B forwards in flight on separate HIP streams — a batch-1 layer of this net fills
-only ~3/4 of the 256 CUs, the next request's kernels fill the rest; `value` is that throughput and the
-one-at-a-time figure is reported beside it.  The streams of the forwards in flight are the executors' own, chosen by the library
+only ~3/4 of the 256 CUs, the next request's kernels fill the rest — timed over exactly K steps after W warm-up
+steps per stream; `ms_per_step` is the wall time of one of those K steps.  A plain run does only that (set-up, the
+library's stream choice and in-flight tile tuning, warm-up, the K timed steps) and prints its line.  `--full` times
+`--regions` (default 5 there) regions of K steps instead of one, `value` = the median, and adds everything else: the
+one-forward-at-a-time region (kernel durations for the roofline), the host-path / pycaffe / cross-request / ResNet-101 /
+float16-pyramid figures beside the headline, the CPU baseline, and (N>1) the gather measured alone.  `--dump-outputs DIR` writes the maps the
+last timed step produced (all ranks' at N>1, as rank 0 receives them) as DIR/<name>.npy, float32 (see dump_outputs).
+The streams of the forwards in flight are the executors' own, chosen by the library
 (`dc_nets_choose_streams`: the real forwards timed on a pool of `--stream-candidates` streams; `config.stream_choice`).  Workload at N=1 = BASELINE.json configs[1]:
 batch=1, 1x3x544x736, fp32 (the shipped prototxt is ResNet-152 — SURVEY F1 — not the "ResNet-101"
 of the config string).  Weak scaling: every rank forwards its own image each step.
@@ -35,6 +40,23 @@ for p in (ROOT, PKG, os.path.join(PKG, "python")):
 
 PEAK_FP32_MFMA_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 dense peak
 PEAK_FP16_MFMA_TFLOPS = 2500.0  # dense f16/bf16 MFMA peak (no sparsity)
+DUMP_LIMIT_BYTES = 60 * 2 ** 20  # --dump-outputs: data bytes in all (under 64 MB with room for the .npy headers)
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """`--dump-outputs DIR`: every array as DIR/<name>.npy, float32.  When they hold more than `limit` bytes in all, each one
+    is replaced by a fixed sample of its flattened elements (seed 0, sorted positions: the same elements in every run with
+    the same arguments), its share of the limit in proportion to its size."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    for name, v in arrays.items():
+        if total > limit:
+            keep = int(v.size * limit // total)
+            v = v.reshape(-1)[np.unique(np.random.RandomState(0).randint(0, v.size, keep))]
+        np.save(os.path.join(path, name + ".npy"), v)
 
 
 def inject_weights(net, layers):
@@ -461,9 +483,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--regions", type=int, default=5,
-                    help="how many times each timed region (W warm-up + exactly K timed steps) is run; value = the median region, "
-                         "value_min / value_max the spread (one 45-ms region cannot resolve a 1 %% change)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: one-forward-at-a-time region and roofline, host-path, pycaffe, "
+                         "cross-request, ResNet-101 and float16-pyramid figures, CPU baseline, the N>1 gather alone")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the maps of the last timed step as DIR/<name>.npy (float32; a fixed sample above 60 MiB)")
+    ap.add_argument("--regions", type=int, default=None,
+                    help="how many times each timed region (W warm-up + exactly K timed steps) is run (default: 1, or 5 with --full); "
+                         "value = the median region, value_min / value_max the spread (one 45-ms region cannot resolve a 1 %% change)")
     ap.add_argument("--height", type=int, default=544)
     ap.add_argument("--width", type=int, default=736)
     ap.add_argument("--batch", type=int, default=0, help="images per rank per step (default: 1, or 8 with --config 3)")
@@ -471,11 +498,11 @@ def main():
                     help="BASELINE.json configs index: 1 = batch 1 per GPU (the headline), 3 = 8 images of 736x544 per GPU "
                          "(batch 64 sharded 8-way) with the gather of the maps to rank 0")
     ap.add_argument("--coalesce", type=int, default=4,
-                    help="also measure cross-request batching (deepcut_tools.Pipeline, opportunistic): at most k batch-1 requests per batch forward (0/1: skip)")
-    ap.add_argument("--no-f16-line", action="store_true", help="skip the configs[2] (fp16 pyramid) measurement printed beside the headline")
+                    help="--full: also measure cross-request batching (deepcut_tools.Pipeline, opportunistic): at most k batch-1 requests per batch forward (0/1: skip)")
+    ap.add_argument("--no-f16-line", action="store_true", help="--full: skip the configs[2] (fp16 pyramid) measurement printed beside the headline")
     ap.add_argument("--depth", type=int, default=152)
-    ap.add_argument("--no-resnet101", action="store_true", help="skip the ResNet-101 side figure (the depth BASELINE.json names)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-resnet101", action="store_true", help="--full: skip the ResNet-101 side figure (the depth BASELINE.json names)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--dtype", default="f32", choices=["f32", "f16"],
                     help="device element type: f32 (the headline, BASELINE configs[1]) or f16 operands with fp32 "
                          "accumulation (BASELINE configs[2])")
@@ -494,6 +521,10 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="N>1 control path only (process group, rank identities, gather of real-size payloads over gloo), no forwards, no GPU")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.regions is None:
+        args.regions = 5 if args.full else 1
     if args.batch <= 0:
         args.batch = 8 if args.config == 3 else 1
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -608,12 +639,15 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    def timed_region(nstreams, steps, warmup):
-        """W untimed + exactly `steps` timed steps, barrier + synchronize on both sides; returns
-        (max-over-ranks wall seconds, hipEvent ms on this rank's launch streams)."""
+    def warm_up(nstreams, warmup):
         for i in range(warmup * nstreams):
             step(i, nstreams)
         fence()
+
+    def timed_region(nstreams, steps, warmup):
+        """W untimed + exactly `steps` timed steps, barrier + synchronize on both sides; returns
+        (max-over-ranks wall seconds, hipEvent ms on this rank's launch streams)."""
+        warm_up(nstreams, warmup)
         e0 = torch.cuda.Event(enable_timing=True)
         e1 = torch.cuda.Event(enable_timing=True)
         t0 = time.perf_counter()
@@ -641,8 +675,13 @@ def main():
         m = rs[order[len(rs) // 2]]
         return m[0], m[1], [r[0] for r in rs]
 
-    # (1) one forward at a time: per-kernel durations are undisturbed -> the roofline figure
-    lat_dt, lat_ev_ms, lat_all = repeated(1)
+    # (1) one forward at a time: per-kernel durations are undisturbed -> the roofline figure (--full; with one stream it is the
+    # headline region).  A plain run only warms up here: net 0 lowers, tunes its tiles and captures its graph alone, as in (1)
+    lat = None
+    if args.full or S == 1:
+        lat = lat_dt, lat_ev_ms, lat_all = repeated(1)
+    else:
+        warm_up(1, max(1, args.warmup))
     # (2) the reported throughput: S independent batch-B forwards in flight (S streams, S Nets).  The tiles region (1) ran with were
     # chosen for the latency of one forward; a service that keeps S forwards in flight tunes for THAT load (untimed, like the
     # autotuning inside the warm-up): deepcut_tools.tune_in_flight, coordinate descent over the busiest GEMM signatures.
@@ -682,13 +721,23 @@ def main():
     if S > 1:
         dt, ev_ms, dt_all = repeated(S)
     else:
-        dt, ev_ms, dt_all = lat_dt, lat_ev_ms, lat_all
+        dt, ev_ms, dt_all = lat
     x = xs[0]
 
-    # N > 1: the exchange alone (no forwards): what rank 0's seven receives reach, and who the ranks are
+    if args.dump_outputs and rank == 0:
+        # the maps of the last timed step (slot (K-1) mod S), as a caller receives them: rank 0's own, or at N>1 every rank's
+        # payload as it arrived at rank 0, stacked along the batch axis in rank order
+        k_last = (args.steps - 1) % S
+        parts = [outs[k_last]] if world == 1 else [recvs[k_last][r] for r in range(world)]
+        parts = [p.float().cpu().numpy() for p in parts]
+        bounds = {"prob": (0, a), "loc_pred": (a, b), "next_pred": (b, outs[0].numel())}
+        dump_outputs(args.dump_outputs, {name: np.concatenate([p[lo:hi].reshape(shp[name]) for p in parts])
+                                         for name, (lo, hi) in bounds.items()})
+
+    # N > 1 (--full): the exchange alone (no forwards): what rank 0's seven receives reach, and who the ranks are
     gather_gbps = None
     payload_bytes = outs[0].numel() * outs[0].element_size()
-    if world > 1:
+    if world > 1 and args.full:
         fence()
         g0 = time.perf_counter()
         for _ in range(10):
@@ -707,15 +756,6 @@ def main():
     if rank == 0:
         total_images = args.steps * B * world
         launches = net.num_launches()
-        conv_launches = sum(1 for ln in net.plan_text().splitlines() if "conv_gemm<" in ln or "wino_f23<" in ln or "wino_h23<" in ln or "ws1x1<" in ln or "ws1x1f<" in ln or "ws7x7f<" in ln or "stem7x7<" in ln)
-        # roofline of the dominant kernel family (conv_gemm: every convolution/deconvolution launch):
-        # algorithmic FLOPs per launch / average launch duration over the ONE-FORWARD-AT-A-TIME timed
-        # region (launches do not overlap there, so the duration is the kernel's own and agrees with
-        # rocprofv3 --stats).  The hipEvents bracket the region on the launch stream, so gaps and the few
-        # non-GEMM kernels (max-pool, layout converts) are charged to the GEMM launches: a lower bound.
-        per_launch_flops = flops_img * B / conv_launches
-        avg_launch_s = (lat_ev_ms / 1e3) / (args.steps * conv_launches)
-        achieved = per_launch_flops / avg_launch_s / 1e12
         res = {
             "metric": "images/sec, DeeperCut ResNet-%d FCN forward (prob+loc_pred+next_pred), whole node" % args.depth,
             "value": total_images / dt,
@@ -751,48 +791,60 @@ def main():
                 "distributed": dist_report,
             },
             "tflops": total_images * flops_img / dt / 1e12,
-            "one_forward_at_a_time": {"value": total_images / lat_dt, "value_min": total_images / max(lat_all),
-                                      "value_max": total_images / min(lat_all), "unit": "images/s",
-                                      "ms_per_step": lat_dt / args.steps * 1e3,
-                                      "tflops": total_images * flops_img / lat_dt / 1e12},
-            "roofline": {
-                "bound": "mfma",
-                "kernel": "conv_gemm + wino_f23 / wino_h23 + ws1x1f / ws1x1 / stem7x7 (%s gather-GEMM, all tile variants; Winograd F(2x2,3x3) and the streaming 1x1 forms where they are faster)" % (
-                    "f16 v_mfma_f32_32x32x16_f16, fp32 accumulate" if args.dtype == "f16" else "fp32 v_mfma_f32_32x32x2_f32"),
-                "achieved": achieved,
-                "peak": PEAK_FP16_MFMA_TFLOPS if args.dtype == "f16" else PEAK_FP32_MFMA_TFLOPS,
-                "unit": "TFLOP/s",
-                "frac": achieved / (PEAK_FP16_MFMA_TFLOPS if args.dtype == "f16" else PEAK_FP32_MFMA_TFLOPS),
-                "flops_per_launch": per_launch_flops,
-                "avg_launch_us": avg_launch_s * 1e6,
-                "launches_per_image": conv_launches,
-                "traffic": hbm_traffic_from_profile((args.dtype, B, H, W))[0],
-                "traffic_source": "committed profile profiles/%s (rocprofv3 PMC passes of this workload; counters cannot be read inside the timed run)"
-                                  % hbm_traffic_from_profile((args.dtype, B, H, W))[1],
-                "traffic_unit": "HBM bytes per conv_gemm launch (PMC FETCH_SIZE x2 + WRITE_SIZE, profiles/%s); "
-                                "algorithmic minimum %.1f MB" % (hbm_traffic_from_profile((args.dtype, B, H, W))[1],
-                                                                 (2.07e9 * (H * W) / (544.0 * 736.0) * B + 0.263e9) * (0.5 if args.dtype == "f16" else 1.0) / conv_launches / 1e6),
-                "achieved_with_forwards_in_flight": total_images * flops_img / dt / 1e12,
-                # `value` is the in-flight regime, `frac` above the one-forward-at-a-time one (launches do not overlap there, so a launch
-                # duration exists): the same ratio for the regime of `value`, and what the counters say about it
-                "frac_in_flight": total_images * flops_img / dt / 1e12 / (PEAK_FP16_MFMA_TFLOPS if args.dtype == "f16" else PEAK_FP32_MFMA_TFLOPS),
-            },
         }
-        mc = mfma_counters_from_profile((args.dtype, B, H, W))
-        if mc:
-            # share of the wall time the 1024 matrix pipes are busy = busy cycles one forward issues (counted) x forwards per second
-            # (this run) / (2.4e9 x 1024): at the 2.4 GHz the loaded chip does not always hold — an upper bound on the clock, a lower
-            # bound on the share.  by_stage: raw SQ_VALU_MFMA_BUSY_CYCLES / GRBM_GUI_ACTIVE of the committed counter windows
-            res["roofline"].update({
-                "mfma_busy_cycles_per_forward": mc["busy_cycles_per_forward"],
-                "mfma_busy_frac_in_flight": mc["busy_cycles_per_forward"] * (total_images / dt / B) / (2.4e9 * 1024),
-                "mfma_busy_frac_one_at_a_time": mc["busy_cycles_per_forward"] * (total_images / lat_dt / B) / (2.4e9 * 1024),
-                "mfma_util_by_stage_in_flight_pct": mc["by_stage_in_flight"],
-                "mfma_util_by_stage_alone_pct": mc.get("by_stage_alone"),
-                "mfma_counters_source": "committed profile profiles/%s (tools/pmc_in_flight.sh)" % mc["source"],
+        if lat is not None:  # --full, or one stream: the one-forward-at-a-time region ran
+            conv_launches = sum(1 for ln in net.plan_text().splitlines() if "conv_gemm<" in ln or "wino_f23<" in ln or "wino_h23<" in ln or "ws1x1<" in ln or "ws1x1f<" in ln or "ws7x7f<" in ln or "stem7x7<" in ln)
+            # roofline of the dominant kernel family (conv_gemm: every convolution/deconvolution launch):
+            # algorithmic FLOPs per launch / average launch duration over the ONE-FORWARD-AT-A-TIME timed
+            # region (launches do not overlap there, so the duration is the kernel's own and agrees with
+            # rocprofv3 --stats).  The hipEvents bracket the region on the launch stream, so gaps and the few
+            # non-GEMM kernels (max-pool, layout converts) are charged to the GEMM launches: a lower bound.
+            per_launch_flops = flops_img * B / conv_launches
+            avg_launch_s = (lat_ev_ms / 1e3) / (args.steps * conv_launches)
+            achieved = per_launch_flops / avg_launch_s / 1e12
+            res.update({
+                "one_forward_at_a_time": {"value": total_images / lat_dt, "value_min": total_images / max(lat_all),
+                                          "value_max": total_images / min(lat_all), "unit": "images/s",
+                                          "ms_per_step": lat_dt / args.steps * 1e3,
+                                          "tflops": total_images * flops_img / lat_dt / 1e12},
+                "roofline": {
+                    "bound": "mfma",
+                    "kernel": "conv_gemm + wino_f23 / wino_h23 + ws1x1f / ws1x1 / stem7x7 (%s gather-GEMM, all tile variants; Winograd F(2x2,3x3) and the streaming 1x1 forms where they are faster)" % (
+                        "f16 v_mfma_f32_32x32x16_f16, fp32 accumulate" if args.dtype == "f16" else "fp32 v_mfma_f32_32x32x2_f32"),
+                    "achieved": achieved,
+                    "peak": PEAK_FP16_MFMA_TFLOPS if args.dtype == "f16" else PEAK_FP32_MFMA_TFLOPS,
+                    "unit": "TFLOP/s",
+                    "frac": achieved / (PEAK_FP16_MFMA_TFLOPS if args.dtype == "f16" else PEAK_FP32_MFMA_TFLOPS),
+                    "flops_per_launch": per_launch_flops,
+                    "avg_launch_us": avg_launch_s * 1e6,
+                    "launches_per_image": conv_launches,
+                    "traffic": hbm_traffic_from_profile((args.dtype, B, H, W))[0],
+                    "traffic_source": "committed profile profiles/%s (rocprofv3 PMC passes of this workload; counters cannot be read inside the timed run)"
+                                      % hbm_traffic_from_profile((args.dtype, B, H, W))[1],
+                    "traffic_unit": "HBM bytes per conv_gemm launch (PMC FETCH_SIZE x2 + WRITE_SIZE, profiles/%s); "
+                                    "algorithmic minimum %.1f MB" % (hbm_traffic_from_profile((args.dtype, B, H, W))[1],
+                                                                     (2.07e9 * (H * W) / (544.0 * 736.0) * B + 0.263e9) * (0.5 if args.dtype == "f16" else 1.0) / conv_launches / 1e6),
+                    "achieved_with_forwards_in_flight": total_images * flops_img / dt / 1e12,
+                    # `value` is the in-flight regime, `frac` above the one-forward-at-a-time one (launches do not overlap there, so a launch
+                    # duration exists): the same ratio for the regime of `value`, and what the counters say about it
+                    "frac_in_flight": total_images * flops_img / dt / 1e12 / (PEAK_FP16_MFMA_TFLOPS if args.dtype == "f16" else PEAK_FP32_MFMA_TFLOPS),
+                },
             })
-        # --- measurements reported BESIDE the headline (never as `value`).  Each one is guarded: whatever happens in them,
-        #     the line with `value`, `roofline` (and, if it ran, `cpu_baseline`) is printed.
+            mc = mfma_counters_from_profile((args.dtype, B, H, W))
+            if mc:
+                # share of the wall time the 1024 matrix pipes are busy = busy cycles one forward issues (counted) x forwards per second
+                # (this run) / (2.4e9 x 1024): at the 2.4 GHz the loaded chip does not always hold — an upper bound on the clock, a lower
+                # bound on the share.  by_stage: raw SQ_VALU_MFMA_BUSY_CYCLES / GRBM_GUI_ACTIVE of the committed counter windows
+                res["roofline"].update({
+                    "mfma_busy_cycles_per_forward": mc["busy_cycles_per_forward"],
+                    "mfma_busy_frac_in_flight": mc["busy_cycles_per_forward"] * (total_images / dt / B) / (2.4e9 * 1024),
+                    "mfma_busy_frac_one_at_a_time": mc["busy_cycles_per_forward"] * (total_images / lat_dt / B) / (2.4e9 * 1024),
+                    "mfma_util_by_stage_in_flight_pct": mc["by_stage_in_flight"],
+                    "mfma_util_by_stage_alone_pct": mc.get("by_stage_alone"),
+                    "mfma_counters_source": "committed profile profiles/%s (tools/pmc_in_flight.sh)" % mc["source"],
+                })
+        # --- measurements reported BESIDE the headline (never as `value`), --full only.  Each one is guarded: whatever happens in
+        #     them, the line with `value`, `roofline` (and, if it ran, `cpu_baseline`) is printed.
         def beside(key, fn):
             try:
                 res[key] = fn()
@@ -983,16 +1035,16 @@ def main():
             return res101
 
         n_pcie = max(3, min(20, args.steps))
-        if world == 1:
+        if args.full and world == 1:
             beside("pcie_inclusive_pipelined", pcie_inclusive_pipelined)
             beside("pcie_inclusive", pcie_inclusive)
             beside("pcie_inclusive_image_entry", image_entry)
             beside("pycaffe_forward", pycaffe_forward)
-        if world == 1 and args.config == 1 and args.coalesce > 1 and B == 1:
+        if args.full and world == 1 and args.config == 1 and args.coalesce > 1 and B == 1:
             beside("cross_request_batching", cross_request_batching)
-        if world == 1 and args.config == 1 and not args.no_resnet101 and args.depth != 101:
+        if args.full and world == 1 and args.config == 1 and not args.no_resnet101 and args.depth != 101:
             beside("resnet101", resnet101)
-        if world == 1 and args.dtype == "f32" and args.config == 1 and not args.no_f16_line:
+        if args.full and world == 1 and args.dtype == "f32" and args.config == 1 and not args.no_f16_line:
             # the other single-GPU configuration of BASELINE.json, timed by the same run
             beside("config2_f16", lambda: config2_f16_line(caffe, layers, args.depth, 10, dev, inject_weights,
                                                           int(os.environ.get("DC_BENCH_F16_EXECS", "2")), not args.no_tune_in_flight, max(1, args.regions)))
@@ -1002,7 +1054,7 @@ def main():
             with open(args.breakdown, "w") as f:
                 f.write(net.plan_text())
                 f.write(net.profile_text(20))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             beside("cpu_baseline", lambda: cpu_baseline(lambda h, w: deepercut_prototxt(args.depth, h, w), layers, flops_img, (H, W)))
             if "value" in res["cpu_baseline"]:
                 res["gpu_over_cpu"] = res["value"] / res["cpu_baseline"]["value"]

@@ -80,3 +80,28 @@ def test_self_launch_hands_back_a_failing_rank():
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=_clean_env(), cwd=ROOT)
     assert r.returncode != 0
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+
+
+def test_dump_outputs_writes_float32_maps_and_a_fixed_sample_above_the_limit(tmp_path):
+    """`--dump-outputs DIR`: <name>.npy in float32, whole while they fit; above the limit the same seeded sample in every run"""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    rs = np.random.RandomState(5)
+    maps = {"prob": rs.randn(2, 14, 6, 7).astype(np.float16), "loc_pred": rs.randn(2, 28, 6, 7)}
+    bench.dump_outputs(str(tmp_path / "whole"), maps)
+    for k, v in maps.items():
+        got = np.load(str(tmp_path / "whole" / (k + ".npy")))
+        assert got.dtype == np.float32 and got.shape == v.shape and np.array_equal(got, v.astype(np.float32))
+    limit = 4 * 500
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), maps, limit=limit)
+    total = 0
+    for k, v in maps.items():
+        a, b = np.load(str(tmp_path / "a" / (k + ".npy"))), np.load(str(tmp_path / "b" / (k + ".npy")))
+        assert a.dtype == np.float32 and a.ndim == 1 and 0 < a.size < v.size and np.array_equal(a, b)
+        assert np.isin(a, v.astype(np.float32).ravel()).all()
+        total += a.nbytes
+    assert total <= limit

@@ -1,5 +1,7 @@
 """CPU: the two independent prototxt readers (csrc/formats.cpp used by the product, oracle/oracle.py used
-by the checker) agree on the model; the generated model equals the reference file when it is present."""
+by the checker) agree on the model; the generated model equals the reference's models/deepercut/ResNet-152.prototxt
+(kept as tests/golden/ResNet-152.prototxt.gz)."""
+import gzip
 import os
 
 import pytest
@@ -8,7 +10,7 @@ import caffe
 from deepcut_tools import deepercut_layer_table, deepercut_prototxt
 from oracle import oracle as O
 
-REF = "/root/reference/models/deepercut/ResNet-152.prototxt"
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ResNet-152.prototxt.gz")
 
 
 def _layers_from_oracle_parser(text):
@@ -31,9 +33,9 @@ def test_both_parsers_agree_on_the_generated_model():
     assert [(l["name"], l["type"], l["bottoms"], l["tops"]) for l in table] == a
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference tree not present (GPU box)")
-def test_generated_model_is_equivalent_to_the_reference_prototxt():
-    ref_text = open(REF).read()
+def test_generated_model_is_equivalent_to_the_reference_prototxt(tmp_path):
+    with gzip.open(REF, "rt") as f:
+        ref_text = f.read()
     ref = O.parse_prototxt(ref_text)
     gen = O.parse_prototxt(deepercut_prototxt(152, 688, 688))
     assert O._get(ref, "name") == O._get(gen, "name")
@@ -54,7 +56,9 @@ def test_generated_model_is_equivalent_to_the_reference_prototxt():
     for a, b in zip(rl, gl):
         assert norm(a) == norm(b), (O._get(a, "name"), norm(a), norm(b))
     # and the product's parser loads the reference file itself, with the same graph
-    n_ref = caffe.Net(REF, caffe.TEST)
+    ref_path = tmp_path / "ResNet-152.prototxt"
+    ref_path.write_text(ref_text)
+    n_ref = caffe.Net(str(ref_path), caffe.TEST)
     n_gen = caffe.Net(deepercut_prototxt(152, 688, 688), caffe.TEST, from_text=True)
     assert n_ref._layer_names == n_gen._layer_names
     assert list(n_ref.blobs) == list(n_gen.blobs)

@@ -2,7 +2,7 @@
 has to get right before a scaling curve means anything.
 
 * `python bench.py --gpus 2 --backend nccl`, started the way the driver starts the N=1 line (no launcher, no WORLD_SIZE): bench.py
-  becomes the launcher, two ranks on two distinct devices, the RCCL gather to rank 0 measured;
+  becomes the launcher, two ranks on two distinct devices, the RCCL gather to rank 0 measured (`--full`);
 * dc_forward_batch over DC_COMM_RCCL with one executor per device — the grouped ncclRecv / ncclSend exchange with more than one
   executor, which no 1-GPU box can run — equals the single-executor maps; DC_COMM_AUTO ends on a transport that works (it probes the
   RCCL communicators at creation and falls back to peer copies); DC_COMM_PEER across devices (hipMemcpyPeerAsync).
@@ -25,7 +25,7 @@ pytestmark = [pytest.mark.gpu, pytest.mark.skipif(caffe.device_count() < 2, reas
 def test_bench_gpus2_over_rccl_starts_itself():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "nccl", "--steps", "5", "--warmup", "2", "--regions", "1",
-           "--no-cpu-baseline", "--no-f16-line", "--no-resnet101", "--coalesce", "0"]
+           "--full", "--no-cpu-baseline", "--no-f16-line", "--no-resnet101", "--coalesce", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

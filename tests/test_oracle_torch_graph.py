@@ -6,9 +6,9 @@ deconvolution + crop + skip-add heads, and its own prototxt reader.  The per-op 
 see a mistake there, and tests/test_fullnet_golden.py pins the oracle to itself.  Here the DeeperCut graph is written a second time,
 by hand, as a torch float64 functional graph that never reads a prototxt — wiring straight from the ResNet / DeeperCut definition
 (He et al.; models/deepercut/ResNet-152.prototxt:67-7344 read as a paper figure, not parsed) — and every Caffe-visible blob of the
-oracle is compared with it.  When the reference tree is present (build container) the oracle parses the reference's OWN
-`models/deepercut/ResNet-152.prototxt`; otherwise (the GPU box's CPU suite) the generated text, which tests/test_formats.py holds
-equivalent to it."""
+oracle is compared with it.  At depth 152 the oracle parses the reference's OWN `models/deepercut/ResNet-152.prototxt` (kept as
+tests/golden/ResNet-152.prototxt.gz); at depth 101 the generated text, which tests/test_formats.py holds equivalent to it at 152."""
+import gzip
 import os
 
 import numpy as np
@@ -18,7 +18,7 @@ import torch.nn.functional as F
 
 from oracle import oracle as O
 
-REF_PROTO = "/root/reference/models/deepercut/ResNet-152.prototxt"
+REF_PROTO = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ResNet-152.prototxt.gz")
 _BLOCKS = {152: (3, 8, 36, 3), 101: (3, 4, 23, 3)}
 
 
@@ -81,9 +81,10 @@ def test_oracle_graph_equals_independent_torch_float64_graph(depth, hw, batch):
 
     h, w = hw
     layers = synth_weights(depth, seed=3)
-    if depth == 152 and os.path.exists(REF_PROTO):
+    if depth == 152:
         # the reference's own file, its input_dim lines rewritten to this test's shape (ResNet-152.prototxt:3-9: 1x3x688x688)
-        text = open(REF_PROTO).read()
+        with gzip.open(REF_PROTO, "rt") as f:
+            text = f.read()
         import re
 
         dims = iter((batch, 3, h, w))

@@ -4,12 +4,12 @@
 TAG=${1:?tag}; N=${2:-3}
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 for i in $(seq 1 $N); do
-  timeout 600 python bench.py --no-cpu-baseline --no-f16-line --no-resnet101 --coalesce 0 > $OUT/run$i.json 2> $OUT/run$i.err
+  timeout 600 python bench.py --full --no-cpu-baseline --no-f16-line --no-resnet101 --coalesce 0 > $OUT/run$i.json 2> $OUT/run$i.err
 done
 python - $OUT $N <<'PY' | tee $OUT/bench_repeat.txt
 import json, sys
 out, n = sys.argv[1], int(sys.argv[2])
-print("# bench.py --no-cpu-baseline --no-f16-line --no-resnet101 --coalesce 0, %d fresh processes on one box" % n)
+print("# bench.py --full --no-cpu-baseline --no-f16-line --no-resnet101 --coalesce 0, %d fresh processes on one box" % n)
 for i in range(1, n + 1):
     try:
         d = json.loads(open("%s/run%d.json" % (out, i)).read().strip().splitlines()[-1])

@@ -50,15 +50,15 @@ tests)
   tail -15 $OUT/pytest.log ;;
 bench)
   TUNE=${TUNE:-none} seed_cache
-  timeout 500 python bench.py $QUIET --steps 10 --warmup 2 --breakdown $OUT/per_launch.txt "$@" > $OUT/bench.json 2> $OUT/bench.err
+  timeout 500 python bench.py --full $QUIET --steps 10 --warmup 2 --breakdown $OUT/per_launch.txt "$@" > $OUT/bench.json 2> $OUT/bench.err
   line "bench $*" $OUT/bench.json
   python tools/breakdown.py $OUT/per_launch.txt > $OUT/per_shape_summary.txt; head -${LINES_OUT:-16} $OUT/per_shape_summary.txt ;;
 check)
   export DC_TUNE_CACHE=$OUT/tune_cache.txt
   timeout 1100 python -m pytest tests -m gpu -q > $OUT/pytest.log 2>&1; echo "pytest rc=$?" >> $OUT/pytest.log; tail -5 $OUT/pytest.log
   rm -f $DC_TUNE_CACHE  # (the driver's bench starts without a cache: tiles tuned in the process, tune_in_flight with isolated timings)
-  timeout 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err; tail -c 1500 $OUT/bench.json
-  timeout 300 python bench.py $QUIET --streams 1 --breakdown $OUT/per_launch.txt > $OUT/bench_s1.json 2>> $OUT/bench.err; tail -3 $OUT/bench.err ;;
+  timeout 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; tail -c 1500 $OUT/bench.json
+  timeout 300 python bench.py --full $QUIET --streams 1 --breakdown $OUT/per_launch.txt > $OUT/bench_s1.json 2>> $OUT/bench.err; tail -3 $OUT/bench.err ;;
 probe)
   # correctness on the ragged shapes first, under a short timeout: a barrier bug must not hang the box
   timeout 60 tools/probes/bin/conv_probe --shapes tiny_3x3,tiny_d2,tiny_odd,tiny_w1,tiny_w3 --batch 3 --reps 5 "$@" > $OUT/tiny.txt 2>&1 || { echo "tiny run failed/hung"; tail -20 $OUT/tiny.txt; exit 1; }
@@ -69,13 +69,13 @@ stamps)
   seed_cache
   args=(); while [ $# -gt 0 ] && [ "$1" != "--" ]; do args+=("$1"); shift; done; shift
   for idx in "$@"; do
-    DC_DEBUG_TIMING=$idx timeout 200 python bench.py $QUIET --no-graph --streams 1 --steps 2 --warmup 1 "${args[@]}" 2>&1 >/dev/null | grep -A1 "dc timing" | tail -3
+    DC_DEBUG_TIMING=$idx timeout 200 python bench.py --full $QUIET --no-graph --streams 1 --steps 2 --warmup 1 "${args[@]}" 2>&1 >/dev/null | grep -A1 "dc timing" | tail -3
   done ;;
 ab)
   seed_cache
   VAR=$1; V0=$2; V1=$3; shift 3
   for rep in 1 2 3; do for v in $V0 $V1; do
-    env $VAR=$v timeout 300 python bench.py $QUIET --steps 100 --warmup 10 "$@" > $OUT/$VAR$v.json 2> $OUT/$VAR$v.err
+    env $VAR=$v timeout 300 python bench.py --full $QUIET --steps 100 --warmup 10 "$@" > $OUT/$VAR$v.json 2> $OUT/$VAR$v.err
     line "$VAR=$v" $OUT/$VAR$v.json
   done; done ;;
 tiles)
@@ -95,7 +95,7 @@ for l in open(src):
     out.append(l)
 open(dst, "w").writelines(out)
 PY
-    timeout 300 python bench.py $QUIET --steps 30 --warmup 4 "$@" > $OUT/t.json 2> $OUT/t.err
+    timeout 300 python bench.py --full $QUIET --steps 30 --warmup 4 "$@" > $OUT/t.json 2> $OUT/t.err
     line "$st" $OUT/t.json
   done; done ;;
 libs)
@@ -103,20 +103,20 @@ libs)
   for rep in 1 2; do for which in base "${names[@]}"; do
     if [ $which = base ]; then unset DEEPCUT_HIP_LIB; else export DEEPCUT_HIP_LIB=$PWD/tools/probes/bin/lib_$which.so; fi
     seed_cache
-    timeout 300 python bench.py $QUIET --steps 100 --warmup 10 "$@" > $OUT/$which.json 2> $OUT/$which.err
+    timeout 300 python bench.py --full $QUIET --steps 100 --warmup 10 "$@" > $OUT/$which.json 2> $OUT/$which.err
     line "$which" $OUT/$which.json
   done; done ;;
 sweep)
   seed_cache
   case ${1:-streams} in
-  streams) for s in 1 2 3 4 6 8; do timeout 300 python bench.py $QUIET --steps 30 --warmup 3 --streams $s > $OUT/s$s.json 2> $OUT/s$s.err; line "streams $s" $OUT/s$s.json; done ;;
-  coalesce) for s in 1 2 3; do for c in 2 3 4 6 8; do timeout 300 python bench.py --no-cpu-baseline --no-f16-line --coalesce $c --streams $s --steps 40 --warmup 3 > $OUT/s${s}c$c.json 2>/dev/null; line "executors $s coalesce $c" $OUT/s${s}c$c.json; done; done ;;
-  queues) for q in 2 4 8; do for s in 3 4 6 8; do GPU_MAX_HW_QUEUES=$q timeout 300 python bench.py $QUIET --steps 30 --warmup 3 --streams $s > $OUT/q${q}s$s.json 2>/dev/null; line "queues $q streams $s" $OUT/q${q}s$s.json; done; done ;;
+  streams) for s in 1 2 3 4 6 8; do timeout 300 python bench.py --full $QUIET --steps 30 --warmup 3 --streams $s > $OUT/s$s.json 2> $OUT/s$s.err; line "streams $s" $OUT/s$s.json; done ;;
+  coalesce) for s in 1 2 3; do for c in 2 3 4 6 8; do timeout 300 python bench.py --full --no-cpu-baseline --no-f16-line --coalesce $c --streams $s --steps 40 --warmup 3 > $OUT/s${s}c$c.json 2>/dev/null; line "executors $s coalesce $c" $OUT/s${s}c$c.json; done; done ;;
+  queues) for q in 2 4 8; do for s in 3 4 6 8; do GPU_MAX_HW_QUEUES=$q timeout 300 python bench.py --full $QUIET --steps 30 --warmup 3 --streams $s > $OUT/q${q}s$s.json 2>/dev/null; line "queues $q streams $s" $OUT/q${q}s$s.json; done; done ;;
   esac ;;
 pmc)
   seed_cache
   cd /tmp && export TMPDIR=/tmp
-  PMC_CMD="python $R/bench.py $QUIET --streams 1 --no-graph --steps 2 --warmup 1 $*"
+  PMC_CMD="python $R/bench.py --full $QUIET --streams 1 --no-graph --steps 2 --warmup 1 $*"
   timeout 400 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/pmc_fetch -o f -- $PMC_CMD > /dev/null 2> $OUT/pmc_fetch.err
   timeout 400 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/pmc_write -o w -- $PMC_CMD > /dev/null 2> $OUT/pmc_write.err
   cd $R

@@ -5,14 +5,14 @@
 TAG=${1:-head}; OUT=gpurun_out/$TAG; mkdir -p $OUT
 export DC_TUNE_CACHE=$OUT/tune_cache.txt
 rm -f $DC_TUNE_CACHE
-timeout 400 python bench.py --no-cpu-baseline --no-f16-line --steps 60 --warmup 5 > $OUT/tuned.json 2> $OUT/err.txt
+timeout 400 python bench.py --full --no-cpu-baseline --no-f16-line --steps 60 --warmup 5 > $OUT/tuned.json 2> $OUT/err.txt
 KEY=$(grep "+mc4" $DC_TUNE_CACHE | awk '{print $1}' | head -1); CUR=$(grep "+mc4" $DC_TUNE_CACHE | awk '{print $2}' | head -1)
 echo "head key $KEY tuned to $CUR"
 cp $DC_TUNE_CACHE $OUT/base_cache.txt
 for v in $CUR 32x32x64_w114_p4 64x64x32_w221_p3 64x64x64_w222_p3 128x64x32_w222_p2 64x128x32_w222_p2 128x128x32_w222_p2; do
   grep -v "+mc4" $OUT/base_cache.txt > $DC_TUNE_CACHE; echo "$KEY $v" >> $DC_TUNE_CACHE
   for rep in 1 2; do
-    timeout 400 python bench.py --no-cpu-baseline --no-f16-line --steps 60 --warmup 5 > $OUT/$v.json 2>> $OUT/err.txt
+    timeout 400 python bench.py --full --no-cpu-baseline --no-f16-line --steps 60 --warmup 5 > $OUT/$v.json 2>> $OUT/err.txt
     python - "$v" $OUT/$v.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
@@ -21,7 +21,7 @@ PY
   done
   if [ "${2:-}" = pmc ]; then
     R=$PWD; cd /tmp; export TMPDIR=/tmp
-    CMD="python $R/bench.py --no-cpu-baseline --no-f16-line --no-resnet101 --coalesce 0 --streams 1 --no-graph --steps 2 --warmup 1"
+    CMD="python $R/bench.py --full --no-cpu-baseline --no-f16-line --no-resnet101 --coalesce 0 --streams 1 --no-graph --steps 2 --warmup 1"
     timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $R/$OUT/f_$v -o f -- $CMD > /dev/null 2>> $R/$OUT/err.txt
     timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $R/$OUT/w_$v -o w -- $CMD > /dev/null 2>> $R/$OUT/err.txt
     cd $R

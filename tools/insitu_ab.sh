@@ -1,12 +1,12 @@
 #!/bin/bash
 # ON THE GPU BOX: tile tuning from scratch with and without the in-situ pass interleaved:
-#   gpurun -- 'bash tools/insitu_ab.sh [f16|f32|both]'
-mkdir -p gpurun_out/insitu
-W=${1:-both}
+#   bash tools/insitu_ab.sh <output dir> [f16|f32|both]
+D=${1:?output dir}; mkdir -p $D
+W=${2:-both}
 run() {  # run <label> <bench args...>  (environment of the caller)
   local label=$1; shift
-  rm -f gpurun_out/insitu/tc.txt
-  DC_TUNE_CACHE=gpurun_out/insitu/tc.txt python bench.py --no-cpu-baseline --no-f16-line --no-resnet101 --coalesce 0 "$@" 2>>gpurun_out/insitu/err.txt |
+  rm -f $D/tc.txt
+  DC_TUNE_CACHE=$D/tc.txt python bench.py --full --no-cpu-baseline --no-f16-line --no-resnet101 --coalesce 0 "$@" 2>>$D/err.txt |
     python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%-28s value %7.1f  one at a time %7.1f' % ('$label', d['value'], d['one_forward_at_a_time']['value']))"
 }
 for rep in 1 2; do

@@ -15,8 +15,8 @@ if [ $WHAT = f16 ]; then ARGS="--dtype f16 --batch 8"; NEIGH="1 150 f16 8"; NDES
 else ARGS=""; NEIGH="3 150"; NDESC="three more executors of ANOTHER, unprofiled process keep batch-1 forwards in flight"; fi
 Q="--no-cpu-baseline --no-f16-line --no-resnet101 --coalesce 0"
 # the plan (launch order -> stage) and the unprofiled duration of every launch, same tiles: a plain run first (it also warms the tune cache)
-timeout 400 python bench.py $Q --streams 1 --steps 10 --warmup 2 $ARGS --breakdown $OUT/per_launch_$WHAT.txt > $OUT/bench_s1_$WHAT.json 2> $OUT/bench_s1.err
-CMD="python $R/bench.py $Q --streams 1 --no-graph --steps 3 --warmup 1 $ARGS"
+timeout 400 python bench.py --full $Q --streams 1 --steps 10 --warmup 2 $ARGS --breakdown $OUT/per_launch_$WHAT.txt > $OUT/bench_s1_$WHAT.json 2> $OUT/bench_s1.err
+CMD="python $R/bench.py --full $Q --streams 1 --no-graph --steps 3 --warmup 1 $ARGS"
 cd /tmp && export TMPDIR=/tmp
 # (a) alone
 timeout 300 rocprofv3 --kernel-trace --pmc $MF -d $OUT/alone -o m -- $CMD > /dev/null 2> $OUT/alone.err
@@ -33,7 +33,7 @@ kill $LOAD 2>/dev/null; wait $LOAD 2>/dev/null
 cd $R
 for w in alone loaded; do
   DB=$(find $OUT/$w -name "*.db" | head -1)
-  python tools/pmc_mfma_util.py $DB "rocprofv3 --kernel-trace --pmc $MF over one executor (bench.py --streams 1 --no-graph --steps 3 $ARGS), $w$( [ $w = loaded ] && echo ": $NDESC on the same GPU")" $OUT/per_launch_$WHAT.txt > $OUT/pmc_mfma_util_${WHAT}_$w.txt 2> $OUT/post_$w.err
+  python tools/pmc_mfma_util.py $DB "rocprofv3 --kernel-trace --pmc $MF over one executor (bench.py --full --streams 1 --no-graph --steps 3 $ARGS), $w$( [ $w = loaded ] && echo ": $NDESC on the same GPU")" $OUT/per_launch_$WHAT.txt > $OUT/pmc_mfma_util_${WHAT}_$w.txt 2> $OUT/post_$w.err
   grep -A8 "^stage" $OUT/pmc_mfma_util_${WHAT}_$w.txt
 done
 cat $OUT/load_marks.txt; grep -c . $OUT/load_$WHAT.txt; head -4 $OUT/load_$WHAT.txt; tail -3 $OUT/load_$WHAT.txt

@@ -5,7 +5,7 @@ cd "$(dirname "$0")/.."
 OUT=gpurun_out/wsf_ab; mkdir -p $OUT
 for rep in $(seq 1 ${1:-2}); do for mode in on off; do
   if [ $mode = off ]; then export DC_STREAM1X1=0; else unset DC_STREAM1X1; fi
-  timeout 600 python bench.py --no-cpu-baseline --no-f16-line --no-resnet101 --coalesce 0 > $OUT/run_${mode}_$rep.json 2> $OUT/run_${mode}_$rep.err
+  timeout 600 python bench.py --full --no-cpu-baseline --no-f16-line --no-resnet101 --coalesce 0 > $OUT/run_${mode}_$rep.json 2> $OUT/run_${mode}_$rep.err
   python - $OUT/run_${mode}_$rep.json $mode <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

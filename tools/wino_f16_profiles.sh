@@ -12,9 +12,9 @@ tools/probes/bin/mfma16_probe > $OUT/mfma16_probe.txt 2>&1
 tools/probes/bin/wino16_loop_probe > $OUT/wino16_loop_probe.txt 2>&1
 # rocprofv3 --kernel-trace --stats of the float16 batch-8 bench, one forward at a time (the kernel's average duration inside the forward)
 export DC_TUNE_CACHE=$OUT/tune_cache.txt
-timeout 300 python bench.py --no-cpu-baseline --no-f16-line --no-resnet101 --coalesce 0 --dtype f16 --batch 8 --streams 1 --steps 10 --warmup 2 > $OUT/bench_f16_b8_s1.json 2> $OUT/bench.err
+timeout 300 python bench.py --full --no-cpu-baseline --no-f16-line --no-resnet101 --coalesce 0 --dtype f16 --batch 8 --streams 1 --steps 10 --warmup 2 > $OUT/bench_f16_b8_s1.json 2> $OUT/bench.err
 cd /tmp && export TMPDIR=/tmp
-timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/stats16 -o s -- python $R/bench.py --no-cpu-baseline --no-f16-line --no-resnet101 --coalesce 0 --dtype f16 --batch 8 --streams 1 --steps 20 --warmup 3 > $OUT/bench_f16_b8_under_rocprof.json 2> $OUT/rocprof16.err
+timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/stats16 -o s -- python $R/bench.py --full --no-cpu-baseline --no-f16-line --no-resnet101 --coalesce 0 --dtype f16 --batch 8 --streams 1 --steps 20 --warmup 3 > $OUT/bench_f16_b8_under_rocprof.json 2> $OUT/rocprof16.err
 cd $R
 python tools/rocprof_summary.py $(find $OUT/stats16 -name "*.db" | head -1) > $OUT/kernel_stats_f16_b8.txt 2> $OUT/post.err
 rm -rf $OUT/stats16
