@@ -567,6 +567,10 @@ int dc_net_set_tile(dc_net* net, const char* signature, const char* tile) {
 int dc_conv_variant_count(void) { return dc::conv_num_variants(); }
 const char* dc_conv_variant_name(int i) { return i >= 0 && i < dc::conv_num_variants() ? dc::conv_variant(i).name : nullptr; }
 int dc_conv_variant_esize(int i) { return i >= 0 && i < dc::conv_num_variants() ? dc::conv_variant_esize(i) : 0; }
+int dc_conv_bf16_variant_count(void) { return dc::conv_num_bf16_variants(); }
+const char* dc_conv_bf16_variant_name(int i) {
+  return i >= 0 && i < dc::conv_num_bf16_variants() ? dc::conv_variant(dc::kBf16Variant0 + i).name : nullptr;
+}
 int dc_wino_half_pack(const float* g, int cout, int cin, int rowscale, float* out, float* row_scale) {
   REQUIRE(g);
   REQUIRE(out);

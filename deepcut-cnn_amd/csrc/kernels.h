@@ -8,6 +8,12 @@ namespace dc {
 
 constexpr int kMaxTaps = 32;  // tap-validity masks are one 32-bit word per staged row
 
+// element kind of the device images (the values of DC_OPT_DTYPE): float32, float16, bfloat16.  Host tensors, the per-channel
+// affine vectors and every accumulation are float in all three.
+enum ElemKind { kElemF32 = 0, kElemF16 = 1, kElemBF16 = 2 };
+inline int elem_kind_size(int kind) { return kind == kElemF32 ? 4 : 2; }
+inline const char* elem_kind_name(int kind) { return kind == kElemF16 ? "f16" : kind == kElemBF16 ? "bf16" : "f32"; }
+
 // out[pixel][co] = act( (sum_k A[pixel][k] * W[co][k]) * scale[co] + shift[co] (+ resid[pixel][co]) )
 //   pixel = (n, oy, ox) over an NB x OH x OW grid,
 //   A[pixel][.] = concatenation over a (nty x ntx) grid of TAPS of `klen` consecutive floats of source row
@@ -64,7 +70,7 @@ struct ConvMultiTable {
 };
 
 struct ConvGemmParams {
-  int esize;          // bytes per activation / filter element: 4 (float) or 2 (_Float16); strides are in elements
+  int esize;          // bytes per activation / filter element: 4 (float) or 2 (_Float16 / __bf16); strides are in elements
   const void* x;
   long x_img_stride;  // elements between images
   int x_row_stride;   // elements between rows
@@ -118,7 +124,7 @@ struct ConvGemmParams {
   // --- multi-problem launches: nprob > 0 and the ConvMultiTable that follows the block in the kernel arguments
   //     (ConvMultiArgs) replace every per-tensor field above
   int nprob;
-  int pad2_;
+  int ekind;  // ElemKind of x / w / y / resid (esize alone does not tell float16 from bfloat16)
 };
 // kernel arguments of a multi-problem launch: the table travels IN the argument block (3.6 KB of the 4 KB a HIP kernel may
 // take), so a workgroup finds its problem with scalar loads from the same segment as everything else — with the table behind
@@ -141,6 +147,16 @@ const ConvVariant& conv_variant(int i);
 // workgroups this variant launches for the problem
 int conv_variant_bk(int i);
 int conv_variant_esize(int i);
+// The bfloat16 tiles are a table of their own (v_mfma_f32_32x32x16_bf16): tile i of it is variant kBf16Variant0 + i wherever a
+// variant number travels (Launch::variant, tune caches by name); conv_variant* above answer for those numbers too.
+constexpr int kBf16Variant0 = 2000;
+int conv_num_bf16_variants();
+inline bool is_bf16_variant(int v) { return v >= kBf16Variant0 && v < kBf16Variant0 + conv_num_bf16_variants(); }
+int conv_variant_ekind(int v);
+bool conv_variant_exists(int v);  // a gather-GEMM tile of either table
+// every tile variant of one element kind, in table order (the candidates of a launch before its K and class checks)
+const int* conv_variants_of(int ekind, int* count);
+int conv_variant_by_name(const char* name);  // -1: no gather-GEMM tile of that name
 bool conv_variant_multiclass(int i);  // has a multi-class instantiation (ConvGemmParams::ncls > 1)
 long conv_grid(const ConvGemmParams& p, int variant);
 // returns hipError_t as int
@@ -167,6 +183,7 @@ constexpr int kStreamFloat = 1005;             // ... and the float32 form of th
 constexpr int kStemFloat = 1006;               // ... and the float32 7x7 / stride-2 stem on that kernel's skeleton (stream1x1_f32.hip, "ws7x7f")
 inline bool is_wino_variant(int v) { return v == kWinoVariant || v == kWinoVariant16 || v == kWinoHalf || v == kStreamHalf || v == kStemHalf || v == kStreamFloat || v == kStemFloat; }
 inline int wino_variant_esize(int v) { return v == kWinoHalf || v == kStreamHalf || v == kStemHalf ? 2 : 4; }  // element size of the nets the form serves
+inline int wino_variant_ekind(int v) { return wino_variant_esize(v) == 2 ? kElemF16 : kElemF32; }  // ... and their kind (no form serves bfloat16)
 const char* wino_variant_name(int variant);    // the tile name of tune caches / reports / set_tile
 const char* wino_kernel_label(int variant);    // the kernel column of plan texts
 int wino_variant_by_name(const char* name);    // -1: not a Winograd tile name
@@ -216,31 +233,33 @@ int launch_stem7x7(const ConvGemmParams& p, void* stream);
 long stream1x1_prepare_multi(const ConvGemmParams& p, const ConvMultiTable& tb, int nprob);  // the grid, or -1
 int launch_stream1x1_multi(const ConvMultiArgs& a, void* stream);                              // a.p.nprob, a.t as filled by the caller
 
-// The remaining kernels take `esize` = bytes per device element (4 float / 2 _Float16); host-side tensors
+// The remaining kernels take `ekind` = the ElemKind of the device images (float / _Float16 / __bf16); host-side tensors
 // and the per-channel affine vectors are always float.
 
 // MAX pooling, NHWC, windows clipped to the image (pooling_layer.cpp:140-187).
-int launch_maxpool(const void* x, void* y, int esize, int NB, int H, int W, int C, int OH, int OW, int k, int s,
+int launch_maxpool(const void* x, void* y, int ekind, int NB, int H, int W, int C, int OH, int OW, int k, int s,
                    int pad, void* stream);
 
 // y = act(x*a[c] + b[c] + z)   (a,b,z optional) — the stand-alone BatchNorm/Scale/ReLU/Eltwise/Sigmoid
 // layers when they are not folded into a producing convolution.
-int launch_eltwise(const void* x, const void* z, const float* a, const float* b, void* y, int esize, long total, int C,
+int launch_eltwise(const void* x, const void* z, const float* a, const float* b, void* y, int ekind, long total, int C,
                    int relu, int sigmoid, void* stream);
 
 // crop the top-left (offset oh,ow) OH x OW window of an NHWC tensor (crop_layer.cpp:37-50)
-int launch_crop(const void* x, void* y, int esize, int NB, int H, int W, int C, int oh, int ow, int OH, int OW,
+int launch_crop(const void* x, void* y, int ekind, int NB, int H, int W, int C, int oh, int ow, int OH, int OW,
                 void* stream);
 
 // layout changes at the Blob boundary (host side is NCHW float, blob.hpp:153-164)
 // src NCHW [NB,C,H,W] -> dst NHWC with channel pitch CP (>= C, extra channels zeroed)
-int launch_nchw_to_nhwc(const float* src, void* dst, int esize, int NB, int C, int H, int W, int CP, void* stream);
-// src NHWC pitch CP, channels [c0, c0+C) -> dst NCHW [NB,C,H,W], float (dst_esize 4) or — from a half image only —
-// _Float16 (dst_esize 2: the gather payload of an fp16 net)
-int launch_nhwc_to_nchw(const void* src, void* dst, int esize, int NB, int C, int H, int W, int CP, int c0,
+int launch_nchw_to_nhwc(const float* src, void* dst, int ekind, int NB, int C, int H, int W, int CP, void* stream);
+// src NHWC pitch CP, channels [c0, c0+C) -> dst NCHW [NB,C,H,W], float (dst_esize 4) or — from a 16-bit image only — the
+// image's own element type (dst_esize 2: the gather payload of an fp16 net, the bf16 values of a bf16 net as they are)
+int launch_nhwc_to_nchw(const void* src, void* dst, int ekind, int NB, int C, int H, int W, int CP, int c0,
                         void* stream, int dst_esize = 4);
 // packed filter image float -> half (fp16 nets)
 int launch_f32_to_f16(const float* src, void* dst, long n, void* stream);
+// ... -> bfloat16, rounded to nearest even (bf16 nets)
+int launch_f32_to_bf16(const float* src, void* dst, long n, void* stream);
 
 // pose decode (estimate_pose.py:131-143) from NHWC score / refinement maps (channel pitch + first channel)
 // Multi-person consumers of the maps.  The reference repository stops at the maps; what these kernels
@@ -252,10 +271,10 @@ int launch_f32_to_f16(const float* src, void* dst, long n, void* stream);
 //           out[((n*J+j)*max_det + k)*5 + {0..4}] = x, y, score, row, col (x, y refined with loc_pred and divided by scale),
 //           counts[n*J+j] = how many were written.  Deterministic for every input (no arrival-order truncation).
 //           spill: NB*J*H*W keys of scratch.
-int launch_part_select(const void* prob, int pcp, int pc0, const void* loc, int lcp, int lc0, int esize, int NB, int H, int W, int J, float thr,
+int launch_part_select(const void* prob, int pcp, int pc0, const void* loc, int lcp, int lc0, int ekind, int NB, int H, int W, int J, float thr,
                        int radius, double scale, int max_det, unsigned long long* spill, int* counts, double* out, void* stream);
 // pairwise: out[(d*E + l)*2 + k] = pt_k + (next_pred[2l+k] at the detection's cell * std[l][k] + mean[l][k]) / scale
-int launch_pairwise_decode(const void* next, int ncp, int nc0, int esize, int NB, int H, int W, int E, double scale, int ndet,
+int launch_pairwise_decode(const void* next, int ncp, int nc0, int ekind, int NB, int H, int W, int E, double scale, int ndet,
                            const int* det /* [ndet][3] image, row, col */, const double* mean, const double* stdev, double* out,
                            void* stream);
 
@@ -275,13 +294,13 @@ struct ImagePrepParams {
   int y_ksize;
   unsigned char* tmp;        // [n][rows][use_w][4]: rows row0..row0+rows of the horizontally resampled padded image
   int row0, rows;
-  void* dst;                 // [n][out_h][out_w][dst_cp] float (dst_esize 4) or _Float16 (2); pad channels zeroed
-  int dst_esize, dst_cp;
+  void* dst;                 // [n][out_h][out_w][dst_cp] float, _Float16 or __bf16 (dst_ekind); pad channels zeroed
+  int dst_ekind, dst_cp;
   float mean[3];
 };
 int launch_image_prep(const ImagePrepParams& p, void* stream);
 
-int launch_pose_decode(const void* prob, int pcp, int pc0, const void* loc, int lcp, int lc0, int esize, int NB, int H,
+int launch_pose_decode(const void* prob, int pcp, int pc0, const void* loc, int lcp, int lc0, int ekind, int NB, int H,
                        int W, int J, double scale, double* out, void* stream);
 
 }  // namespace dc

@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
+#include <vector>
 
 #include "kernels.h"
 
@@ -49,6 +50,8 @@ __device__ __forceinline__ int dc_fastdiv(int n, const unsigned (&mg)[2]) {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // LDS-DMA (`buffer_load_dwordx4 ... lds`): 64 lanes x 16 bytes travel from global memory straight into LDS, no VGPRs and
@@ -149,6 +152,27 @@ struct Elem<_Float16> {
     __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, (_Float16)v), r, off, 0, 0);
   }
 };
+// bfloat16: float32's exponent range with 8 significant bits.  Widening is a 16-bit shift; a store rounds once, to nearest even
+// (v_cvt_pk_bf16_f32; NaN stays NaN)
+template <>
+struct Elem<__bf16> {
+  static constexpr int SPC = 1;  // 1 x v_mfma_f32_32x32x16_bf16 (k = 16) per 32-byte chunk
+  typedef unsigned short raw_t;
+  static __device__ __forceinline__ raw_t load_raw(__amdgpu_buffer_rsrc_t r, unsigned off) { return __builtin_amdgcn_raw_buffer_load_b16(r, off, 0, 0); }
+  static __device__ __forceinline__ float cvt(raw_t v) { return __builtin_bit_cast(float, (unsigned)v << 16); }
+  static __device__ __forceinline__ float load(__amdgpu_buffer_rsrc_t r, unsigned off) { return cvt(load_raw(r, off)); }
+  static __device__ __forceinline__ void store(float v, __amdgpu_buffer_rsrc_t r, unsigned off) {
+    __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, (__bf16)v), r, off, 0, 0);
+  }
+};
+// the 16-bit matrix step of either 16-bit type: 32x32 output fragment += 32x16 (a) x 16x32 (b), float32 accumulation
+template <typename T>
+__device__ __forceinline__ f32x16 dc_mfma16(f32x4 a, f32x4 b, f32x16 c) {
+  if constexpr (std::is_same_v<T, __bf16>)
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+  else
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+}
 
 // MC: multi-class launch (ConvGemmParams::ncls > 1): the class-dependent scalars come from p.cls[class of this block].
 // DMA: 0 = operands staged through a register ring (PF tiles) and ds_write_b128 into two padded LDS stages;
@@ -690,12 +714,8 @@ __global__ __launch_bounds__(WR* WC* WK * 64, (DMA && WR * WC * WK == 4) ? 2 : 1
             if constexpr (SWP) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(bv[cur][b][st], av[cur][a][st], acc[a][b], 0, 0, 0);
             else acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[cur][a][st], bv[cur][b][st], acc[a][b], 0, 0, 0);
           } else {
-            if constexpr (SWP)
-              acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, bv[cur][b]),
-                                                                 __builtin_bit_cast(f16x8, av[cur][a]), acc[a][b], 0, 0, 0);
-            else
-              acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, av[cur][a]),
-                                                                 __builtin_bit_cast(f16x8, bv[cur][b]), acc[a][b], 0, 0, 0);
+            if constexpr (SWP) acc[a][b] = dc_mfma16<T>(bv[cur][b], av[cur][a], acc[a][b]);
+            else acc[a][b] = dc_mfma16<T>(av[cur][a], bv[cur][b], acc[a][b]);
           }
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -803,8 +823,7 @@ __global__ __launch_bounds__(WR* WC* WK * 64, (DMA && WR * WC * WK == 4) ? 2 : 1
             if constexpr (SPC == 4)
               acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[cur][a][st], bv[cur][b][st], acc[a][b], 0, 0, 0);
             else
-              acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, av[cur][a]),
-                                                                 __builtin_bit_cast(f16x8, bv[cur][b]), acc[a][b], 0, 0, 0);
+              acc[a][b] = dc_mfma16<T>(av[cur][a], bv[cur][b], acc[a][b]);
           }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -958,14 +977,26 @@ __global__ __launch_bounds__(WR* WC* WK * 64, (DMA && WR * WC * WK == 4) ? 2 : 1
 #pragma unroll
                   for (int i = 0; i < 4; ++i) {
                     float x0 = i < 2 ? lo[2 * i] : hi[2 * i - 4], x1 = i < 2 ? lo[2 * i + 1] : hi[2 * i - 3];
-                    if (HAS_RES) {
-                      x0 = dc_add_half_lo(rz[i], x0);
-                      x1 = dc_add_half_hi(rz[i], x1);
+                    if constexpr (std::is_same_v<T, __bf16>) {
+                      // bfloat16: no mixed-precision add — the shortcut pair is widened by a shift / a mask (exact), added in float,
+                      // ReLU'd in float and the pair rounded once by v_cvt_pk_bf16_f32
+                      if (HAS_RES) {
+                        x0 += __builtin_bit_cast(float, rz[i] << 16);
+                        x1 += __builtin_bit_cast(float, rz[i] & 0xffff0000u);
+                      }
+                      if (RELU) x0 = fmaxf(x0, 0.f), x1 = fmaxf(x1, 0.f);
+                      const f32x2 xp = {x0, x1};
+                      o[i] = __builtin_bit_cast(unsigned, __builtin_convertvector(xp, bf16x2));
+                    } else {
+                      if (HAS_RES) {
+                        x0 = dc_add_half_lo(rz[i], x0);
+                        x1 = dc_add_half_hi(rz[i], x1);
+                      }
+                      const f32x2 xp = {x0, x1};
+                      f16x2 hp = __builtin_convertvector(xp, f16x2);
+                      if (RELU) hp = __builtin_elementwise_max(hp, rl2);
+                      o[i] = __builtin_bit_cast(unsigned, hp);
                     }
-                    const f32x2 xp = {x0, x1};
-                    f16x2 hp = __builtin_convertvector(xp, f16x2);
-                    if (RELU) hp = __builtin_elementwise_max(hp, rl2);
-                    o[i] = __builtin_bit_cast(unsigned, hp);
                   }
                   __builtin_amdgcn_raw_buffer_store_b128(o, yr, off[a][b][j], 0, 0);
                 }
@@ -1029,13 +1060,14 @@ __global__ __launch_bounds__(WR* WC* WK * 64, (DMA && WR * WC * WK == 4) ? 2 : 1
           const int v = t + i * NT, row = v / (BN / 8), cv = v - row * (BN / 8);
           const f32x4 lo = *reinterpret_cast<const f32x4*>(stg + row * WPS + cv * 8);
           const f32x4 hi = *reinterpret_cast<const f32x4*>(stg + row * WPS + cv * 8 + 4);
-          f16x8 rz = __builtin_bit_cast(f16x8, wres[i]);
-          f16x8 o;
+          typedef T t8 __attribute__((ext_vector_type(8)));  // 8 halves / 8 bfloat16s
+          t8 rz = __builtin_bit_cast(t8, wres[i]);
+          t8 o;
 #pragma unroll
           for (int q = 0; q < 8; ++q) {
             float x = (q < 4 ? lo[q] : hi[q - 4]) + (c_resid ? (float)rz[q] : 0.f);
             if (p.relu) x = fmaxf(x, 0.f);
-            o[q] = (_Float16)x;
+            o[q] = (T)x;
           }
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), yr, woff[i], 0, 0);
         }
@@ -1149,6 +1181,20 @@ struct VariantEntry {
   { {"d" #BM "x" #BN "x128_w" #WR #WC #WK "_s" #S, BM, BN, WR, WC, WK}, DC_K3(_Float16, BM, BN, 128, WR, WC, WK, 1, S, true, 2, false) }
 #define DC_VARIANT_FD(BM, BN, BK, WR, WC, WK, S) /* float32: BK = 32 (128-byte rows) or 64 (256-byte rows) */ \
   { {"e" #BM "x" #BN "x" #BK "_w" #WR #WC #WK "_s" #S, BM, BN, WR, WC, WK}, DC_K3(float, BM, BN, BK, WR, WC, WK, 1, S, true, 4, false) }
+// bfloat16 (v_mfma_f32_32x32x16_bf16, fp32 accumulate): the float16 tiles again, "b" / "bd" for "h" / "d" — same bytes, same
+// instruction rate, so the same shapes win; a table of its own (kBf16Variant0 + i), the float16 / float32 one keeps its indices
+#define DC_VARIANT_B(BM, BN, BK, WR, WC, WK, PF) \
+  { {"b" #BM "x" #BN "x" #BK "_w" #WR #WC #WK "_p" #PF, BM, BN, WR, WC, WK}, DC_K3(__bf16, BM, BN, BK, WR, WC, WK, PF, 0, false, 2, false) }
+#define DC_VARIANT_B_MC(BM, BN, BK, WR, WC, WK, PF) \
+  { {"b" #BM "x" #BN "x" #BK "_w" #WR #WC #WK "_p" #PF, BM, BN, WR, WC, WK}, DC_K3(__bf16, BM, BN, BK, WR, WC, WK, PF, 0, false, 2, true) }
+#define DC_VARIANT_BD(BM, BN, WR, WC, WK, S) \
+  { {"bd" #BM "x" #BN "x64_w" #WR #WC #WK "_s" #S, BM, BN, WR, WC, WK}, DC_K3(__bf16, BM, BN, 64, WR, WC, WK, 1, S, true, 2, false) }
+#define DC_VARIANT_BD_T(BM, BN, WR, WC, WK, S) \
+  { {"bd" #BM "x" #BN "x64_w" #WR #WC #WK "_s" #S "_t", BM, BN, WR, WC, WK}, DC_K3(__bf16, BM, BN, 64, WR, WC, WK, 1, S, false, 2, false) }
+#define DC_VARIANT_BD_MC(BM, BN, WR, WC, WK, S) \
+  { {"bd" #BM "x" #BN "x64_w" #WR #WC #WK "_s" #S, BM, BN, WR, WC, WK}, DC_K3(__bf16, BM, BN, 64, WR, WC, WK, 1, S, true, 2, true) }
+#define DC_VARIANT_BD2(BM, BN, WR, WC, WK, S) \
+  { {"bd" #BM "x" #BN "x128_w" #WR #WC #WK "_s" #S, BM, BN, WR, WC, WK}, DC_K3(__bf16, BM, BN, 128, WR, WC, WK, 1, S, true, 2, false) }
 const VariantEntry kVariants[] = {
     DC_VARIANT(128, 128, 32, 2, 2, 1, 2),  // 0: big-M layers (res2/res3)
     DC_VARIANT(128, 64, 32, 2, 2, 1, 2),   // 1
@@ -1218,20 +1264,79 @@ const VariantEntry kVariants[] = {
     DC_VARIANT_HD(128, 128, 2, 4, 1, 3),      // 54
 };
 constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
+const VariantEntry kVariantsBf16[] = {
+    DC_VARIANT_B_MC(128, 128, 64, 2, 2, 1, 2), // 0
+    DC_VARIANT_B_MC(128, 64, 64, 2, 2, 1, 2), // 1
+    DC_VARIANT_B(64, 128, 64, 2, 2, 1, 2),  // 2
+    DC_VARIANT_B_MC(64, 64, 64, 2, 2, 1, 3), // 3
+    DC_VARIANT_B_MC(64, 64, 128, 2, 2, 2, 2), // 4
+    DC_VARIANT_B_MC(32, 64, 128, 1, 2, 2, 3), // 5
+    DC_VARIANT_B(64, 32, 128, 2, 1, 2, 3),  // 6
+    DC_VARIANT_B_MC(32, 64, 256, 1, 2, 4, 2), // 7
+    DC_VARIANT_B_MC(128, 128, 128, 2, 2, 2, 2), // 8
+    DC_VARIANT_B_MC(32, 32, 256, 1, 1, 4, 2), // 9
+    DC_VARIANT_B(128, 128, 64, 2, 2, 1, 3), // 10
+    DC_VARIANT_B(128, 64, 64, 2, 2, 1, 3),  // 11
+    DC_VARIANT_B(64, 128, 64, 2, 2, 1, 3),  // 12
+    DC_VARIANT_B(256, 128, 64, 4, 2, 1, 2), // 13
+    DC_VARIANT_B(128, 256, 64, 2, 4, 1, 2), // 14
+    DC_VARIANT_BD_MC(128, 128, 2, 2, 1, 2), // 15
+    DC_VARIANT_BD_MC(128, 128, 2, 2, 2, 3), // 16
+    DC_VARIANT_BD(128, 128, 2, 2, 2, 4),    // 17
+    DC_VARIANT_BD(128, 64, 2, 2, 1, 3),     // 18
+    DC_VARIANT_BD(64, 128, 2, 2, 1, 3),     // 19
+    DC_VARIANT_BD(64, 64, 2, 2, 1, 4),      // 20
+    DC_VARIANT_BD_MC(256, 128, 4, 2, 1, 3), // 21
+    DC_VARIANT_BD_MC(128, 256, 2, 4, 1, 3), // 22
+    DC_VARIANT_BD(128, 64, 2, 2, 1, 2),     // 23
+    DC_VARIANT_BD(64, 128, 2, 2, 1, 2),     // 24
+    DC_VARIANT_BD(64, 64, 2, 2, 1, 2),      // 25
+    DC_VARIANT_BD2(64, 64, 2, 2, 2, 2),     // 26
+    DC_VARIANT_BD2(32, 64, 1, 2, 4, 3),     // 27
+    DC_VARIANT_BD_T(128, 128, 2, 2, 1, 2),  // 28
+    DC_VARIANT_BD_T(64, 128, 2, 2, 1, 2),   // 29
+    DC_VARIANT_BD(128, 128, 4, 2, 1, 3),    // 30
+    DC_VARIANT_BD(128, 128, 2, 4, 1, 3),    // 31
+};
+constexpr int kNumBf16Variants = sizeof(kVariantsBf16) / sizeof(kVariantsBf16[0]);
+// the table entry of a variant number (callers have checked it with dc_variant_ok)
+const VariantEntry& entry_of(int v) { return v >= kBf16Variant0 ? kVariantsBf16[v - kBf16Variant0] : kVariants[v]; }
+bool dc_variant_ok(int v) { return (v >= 0 && v < kNumVariants) || (v >= kBf16Variant0 && v < kBf16Variant0 + kNumBf16Variants); }
 }  // namespace
 
 int conv_num_variants() { return kNumVariants; }
+int conv_num_bf16_variants() { return kNumBf16Variants; }
 // (kStreamHalf — stream1x1.hip — answers these like a table entry: the group code handles it as one more multi-problem tile)
 const ConvVariant& conv_variant(int i) {
   static const ConvVariant kStream = {"ws1x1", 32, 256, 1, 8, 1};
-  return i == kStreamHalf ? kStream : kVariants[i].v;
+  return i == kStreamHalf ? kStream : entry_of(i).v;
 }
-int conv_variant_bk(int i) { return i == kStreamHalf ? 64 : kVariants[i].BK; }
-int conv_variant_esize(int i) { return i == kStreamHalf ? 2 : kVariants[i].esize; }
-bool conv_variant_multiclass(int i) { return i == kStreamHalf ? false : kVariants[i].kernel_mc != nullptr; }
+int conv_variant_bk(int i) { return i == kStreamHalf ? 64 : entry_of(i).BK; }
+int conv_variant_esize(int i) { return i == kStreamHalf ? 2 : entry_of(i).esize; }
+int conv_variant_ekind(int i) { return is_bf16_variant(i) ? kElemBF16 : conv_variant_esize(i) == 2 ? kElemF16 : kElemF32; }
+bool conv_variant_multiclass(int i) { return i == kStreamHalf ? false : entry_of(i).kernel_mc != nullptr; }
+const int* conv_variants_of(int ekind, int* count) {
+  static const std::vector<int>* lists = [] {
+    auto* l = new std::vector<int>[3];
+    for (int v = 0; v < kNumVariants; ++v) l[kVariants[v].esize == 2 ? kElemF16 : kElemF32].push_back(v);
+    for (int v = 0; v < kNumBf16Variants; ++v) l[kElemBF16].push_back(kBf16Variant0 + v);
+    return l;
+  }();
+  const std::vector<int>& l = lists[ekind == kElemBF16 ? kElemBF16 : ekind == kElemF16 ? kElemF16 : kElemF32];
+  *count = (int)l.size();
+  return l.data();
+}
+bool conv_variant_exists(int v) { return dc_variant_ok(v); }
+int conv_variant_by_name(const char* name) {
+  for (int v = 0; v < kNumVariants; ++v)
+    if (!std::strcmp(name, kVariants[v].v.name)) return v;
+  for (int v = 0; v < kNumBf16Variants; ++v)
+    if (!std::strcmp(name, kVariantsBf16[v].v.name)) return kBf16Variant0 + v;
+  return -1;
+}
 
 long conv_grid(const ConvGemmParams& p, int variant) {
-  const ConvVariant& v = kVariants[variant].v;
+  const ConvVariant& v = entry_of(variant).v;
   const long tn = (p.Cout + v.BN - 1) / v.BN;
   if (p.ncls > 1) {
     long g = 0;
@@ -1243,10 +1348,10 @@ long conv_grid(const ConvGemmParams& p, int variant) {
 }
 
 int launch_conv_gemm(const ConvGemmParams& p_in, int variant, void* stream) {
-  if (variant < 0 || variant >= kNumVariants) return (int)hipErrorInvalidValue;
-  const VariantEntry& e = kVariants[variant];
+  if (!dc_variant_ok(variant)) return (int)hipErrorInvalidValue;
+  const VariantEntry& e = entry_of(variant);
   ConvGemmParams p = p_in;
-  if (p.esize != e.esize) return (int)hipErrorInvalidValue;
+  if (p.esize != e.esize || (p.ekind == kElemBF16) != is_bf16_variant(variant)) return (int)hipErrorInvalidValue;
   static const int wide_epi = getenv("DC_WIDE_EPI") ? atoi(getenv("DC_WIDE_EPI")) : 1;
   p.wide_epi = wide_epi && p.esize == 2 && p.ncls <= 1 && p.Cout % 8 == 0 && p.y_pix_stride % 8 == 0 && p.y_row_stride % 8 == 0 &&
                p.y_img_stride % 8 == 0 && p.sigmoid_ch == 0 && ((uintptr_t)p.y & 15) == 0 && (!p.resid || ((uintptr_t)p.resid & 15) == 0);
@@ -1385,7 +1490,7 @@ int launch_conv_gemm(const ConvGemmParams& p_in, int variant, void* stream) {
   return (int)hipGetLastError();
 }
 
-bool conv_variant_multiproblem(int i) { return i == kStreamHalf ? true : kVariants[i].kernel_mp != nullptr; }
+bool conv_variant_multiproblem(int i) { return i == kStreamHalf ? true : entry_of(i).kernel_mp != nullptr; }
 
 // Multi-problem launch: host-side preparation (once per plan), see kernels.h.
 long prepare_conv_multi(ConvGemmParams& p, ConvMultiTable& tb, int nprob, int variant) {
@@ -1394,9 +1499,9 @@ long prepare_conv_multi(ConvGemmParams& p, ConvMultiTable& tb, int nprob, int va
     if (g > 0) p.nprob = nprob, p.ncls = 0;
     return g;
   }
-  if (variant < 0 || variant >= kNumVariants || nprob < 1 || nprob > kMaxProblems) return -1;
-  const VariantEntry& e = kVariants[variant];
-  if (!e.kernel_mp || p.esize != e.esize || p.klen % e.BK != 0) return -1;
+  if (!dc_variant_ok(variant) || nprob < 1 || nprob > kMaxProblems) return -1;
+  const VariantEntry& e = entry_of(variant);
+  if (!e.kernel_mp || p.esize != e.esize || (p.ekind == kElemBF16) != is_bf16_variant(variant) || p.klen % e.BK != 0) return -1;
   const long es = p.esize;
   const double lim = 2147483647.0;
   static const int dense = getenv("DC_DENSE") ? atoi(getenv("DC_DENSE")) : 1;
@@ -1489,8 +1594,8 @@ long prepare_conv_multi(ConvGemmParams& p, ConvMultiTable& tb, int nprob, int va
 
 int launch_conv_multi(const ConvMultiArgs& a, int variant, long grid, void* stream) {
   if (variant == kStreamHalf) return launch_stream1x1_multi(a, stream);
-  if (variant < 0 || variant >= kNumVariants || !kVariants[variant].kernel_mp || a.p.nprob < 1 || grid <= 0) return (int)hipErrorInvalidValue;
-  const VariantEntry& e = kVariants[variant];
+  if (!dc_variant_ok(variant) || !entry_of(variant).kernel_mp || a.p.nprob < 1 || grid <= 0) return (int)hipErrorInvalidValue;
+  const VariantEntry& e = entry_of(variant);
   const int nt = e.v.WR * e.v.WC * e.v.WK * 64;
   hipLaunchKernelGGL(e.kernel_mp, dim3((unsigned)grid), dim3(nt), 0, (hipStream_t)stream, a);
   return (int)hipGetLastError();
@@ -1771,6 +1876,7 @@ __global__ __launch_bounds__(WNTH * NG, 4) void wino_f23_kernel(const ConvGemmPa
 }
 
 bool wino_eligible(const ConvGemmParams& p) {
+  if (p.ekind == kElemBF16) return false;          // no Winograd form for bfloat16
   if (p.esize == 2) return wino_half_eligible(p);  // the float16 kernel (wino_f16.hip)
   const int d = p.ddy;  // dilation (1 or more), the same along x and y, with pad = dilation ("same" convolution)
   if (p.esize != 4 || p.nty != 3 || p.ntx != 3 || p.sy != 1 || d < 1 || d > 4 || p.dy0 != -d) return false;
@@ -1856,6 +1962,21 @@ int launch_wino_conv(const ConvGemmParams& p, void* stream, int variant) {
   return (int)hipGetLastError();
 }
 
+// the element type of an ElemKind: f(tag) with tag a null T* (float, _Float16 or __bf16)
+template <typename F>
+static int dc_by_kind(int ekind, F&& f) {
+  if (ekind == kElemF16) return f((_Float16*)nullptr);
+  if (ekind == kElemBF16) return f((__bf16*)nullptr);
+  return f((float*)nullptr);
+}
+// the most negative finite value of T (Caffe's -FLT_MAX start of a max, pooling_layer.cpp:150: rounded into the type's range)
+template <typename T>
+__device__ __forceinline__ T dc_lowest() {
+  if constexpr (std::is_same_v<T, float>) return (T)-3.402823466e+38f;
+  else if constexpr (std::is_same_v<T, _Float16>) return (T)-65504.f;
+  else return __builtin_bit_cast(T, (unsigned short)0xff7fu);  // -3.3895e38
+}
+
 // ------------------------------------------------------------------------------------------------
 // MAX pooling (NHWC, 16 bytes of channels per thread), windows clipped to the image
 // ------------------------------------------------------------------------------------------------
@@ -1880,7 +2001,7 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const T* __restrict__ x, T
   ws = max(ws, 0);
   vec_t m;
 #pragma unroll
-  for (int q = 0; q < V; ++q) m[q] = (T)(sizeof(T) == 4 ? -3.402823466e+38f : -65504.f);
+  for (int q = 0; q < V; ++q) m[q] = dc_lowest<T>();
   for (int iy = hs; iy < he; ++iy)
     for (int ix = ws; ix < we; ++ix) {
       vec_t v = *reinterpret_cast<const vec_t*>(x + (((long)n * H + iy) * W + ix) * C + cv * V);
@@ -1933,10 +2054,11 @@ static int launch_maxpool_t(const void* x, void* y, int NB, int H, int W, int C,
   return (int)hipGetLastError();
 }
 
-int launch_maxpool(const void* x, void* y, int esize, int NB, int H, int W, int C, int OH, int OW, int k, int s,
+int launch_maxpool(const void* x, void* y, int ekind, int NB, int H, int W, int C, int OH, int OW, int k, int s,
                    int pad, void* stream) {
-  return esize == 2 ? launch_maxpool_t<_Float16>(x, y, NB, H, W, C, OH, OW, k, s, pad, stream)
-                    : launch_maxpool_t<float>(x, y, NB, H, W, C, OH, OW, k, s, pad, stream);
+  return dc_by_kind(ekind, [&](auto* tag) {
+    return launch_maxpool_t<std::remove_pointer_t<decltype(tag)>>(x, y, NB, H, W, C, OH, OW, k, s, pad, stream);
+  });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2009,10 +2131,11 @@ static int launch_eltwise_t(const void* x, const void* z, const float* a, const 
   return (int)hipGetLastError();
 }
 
-int launch_eltwise(const void* x, const void* z, const float* a, const float* b, void* y, int esize, long total, int C,
+int launch_eltwise(const void* x, const void* z, const float* a, const float* b, void* y, int ekind, long total, int C,
                    int relu, int sigmoid, void* stream) {
-  return esize == 2 ? launch_eltwise_t<_Float16>(x, z, a, b, y, total, C, relu, sigmoid, stream)
-                    : launch_eltwise_t<float>(x, z, a, b, y, total, C, relu, sigmoid, stream);
+  return dc_by_kind(ekind, [&](auto* tag) {
+    return launch_eltwise_t<std::remove_pointer_t<decltype(tag)>>(x, z, a, b, y, total, C, relu, sigmoid, stream);
+  });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2034,19 +2157,18 @@ __global__ __launch_bounds__(256) void crop_kernel(const T* __restrict__ x, T* _
   }
 }
 
-int launch_crop(const void* x, void* y, int esize, int NB, int H, int W, int C, int oh, int ow, int OH, int OW,
+int launch_crop(const void* x, void* y, int ekind, int NB, int H, int W, int C, int oh, int ow, int OH, int OW,
                 void* stream) {
   long total = (long)NB * OH * OW * C;
   if (total <= 0) return 0;
   long blocks = (total + 255) / 256;
   if (blocks > 4096) blocks = 4096;
-  if (esize == 2)
-    hipLaunchKernelGGL(crop_kernel<_Float16>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
-                       (const _Float16*)x, (_Float16*)y, NB, H, W, C, oh, ow, OH, OW);
-  else
-    hipLaunchKernelGGL(crop_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)x,
-                       (float*)y, NB, H, W, C, oh, ow, OH, OW);
-  return (int)hipGetLastError();
+  return dc_by_kind(ekind, [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    hipLaunchKernelGGL(crop_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, NB, H, W, C,
+                       oh, ow, OH, OW);
+    return (int)hipGetLastError();
+  });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2092,30 +2214,31 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const T* __restrict__
   }
 }
 
-int launch_nchw_to_nhwc(const float* src, void* dst, int esize, int NB, int C, int H, int W, int CP, void* stream) {
+int launch_nchw_to_nhwc(const float* src, void* dst, int ekind, int NB, int C, int H, int W, int CP, void* stream) {
   int HW = H * W;
   if (NB <= 0 || HW <= 0) return 0;
   dim3 grid((HW + 31) / 32, (CP + 31) / 32, NB);
-  if (esize == 2)
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel<_Float16>, grid, dim3(256), 0, (hipStream_t)stream, src, (_Float16*)dst, C, HW, CP);
-  else
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, src, (float*)dst, C, HW, CP);
-  return (int)hipGetLastError();
+  return dc_by_kind(ekind, [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    hipLaunchKernelGGL(nchw_to_nhwc_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, src, (T*)dst, C, HW, CP);
+    return (int)hipGetLastError();
+  });
 }
 
-int launch_nhwc_to_nchw(const void* src, void* dst, int esize, int NB, int C, int H, int W, int CP, int c0,
+int launch_nhwc_to_nchw(const void* src, void* dst, int ekind, int NB, int C, int H, int W, int CP, int c0,
                         void* stream, int dst_esize) {
   int HW = H * W;
   if (NB <= 0 || HW <= 0) return 0;
-  if ((dst_esize != 2 && dst_esize != 4) || (dst_esize == 2 && esize != 2)) return (int)hipErrorInvalidValue;  // f32 image -> f16 copy: not offered
+  if ((dst_esize != 2 && dst_esize != 4) || (dst_esize == 2 && ekind == kElemF32)) return (int)hipErrorInvalidValue;  // f32 image -> 16-bit copy: not offered
   dim3 grid((HW + 31) / 32, (C + 31) / 32, NB);
-  if (esize == 2 && dst_esize == 2)
-    hipLaunchKernelGGL((nhwc_to_nchw_kernel<_Float16, _Float16>), grid, dim3(256), 0, (hipStream_t)stream, (const _Float16*)src, (_Float16*)dst, C, HW, CP, c0);
-  else if (esize == 2)
-    hipLaunchKernelGGL((nhwc_to_nchw_kernel<_Float16, float>), grid, dim3(256), 0, (hipStream_t)stream, (const _Float16*)src, (float*)dst, C, HW, CP, c0);
-  else
-    hipLaunchKernelGGL((nhwc_to_nchw_kernel<float, float>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)src, (float*)dst, C, HW, CP, c0);
-  return (int)hipGetLastError();
+  return dc_by_kind(ekind, [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    if (dst_esize == 2)
+      hipLaunchKernelGGL((nhwc_to_nchw_kernel<T, T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)src, (T*)dst, C, HW, CP, c0);
+    else
+      hipLaunchKernelGGL((nhwc_to_nchw_kernel<T, float>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)src, (float*)dst, C, HW, CP, c0);
+    return (int)hipGetLastError();
+  });
 }
 
 // float -> half conversion of a packed filter image (upload path of fp16 nets)
@@ -2128,6 +2251,18 @@ int launch_f32_to_f16(const float* src, void* dst, long n, void* stream) {
   long blocks = (n + 255) / 256;
   if (blocks > 8192) blocks = 8192;
   hipLaunchKernelGGL(f32_to_f16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, src, (_Float16*)dst, n);
+  return (int)hipGetLastError();
+}
+// ... and to bfloat16 (bf16 nets): round to nearest even, NaN stays NaN (v_cvt_pk_bf16_f32)
+__global__ __launch_bounds__(256) void f32_to_bf16_kernel(const float* __restrict__ src, __bf16* __restrict__ dst, long n) {
+  long stride = (long)gridDim.x * blockDim.x;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) dst[i] = (__bf16)src[i];
+}
+int launch_f32_to_bf16(const float* src, void* dst, long n, void* stream) {
+  if (n <= 0) return 0;
+  long blocks = (n + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(f32_to_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, src, (__bf16*)dst, n);
   return (int)hipGetLastError();
 }
 
@@ -2178,16 +2313,15 @@ __global__ __launch_bounds__(256) void pose_decode_kernel(const T* __restrict__ 
   }
 }
 
-int launch_pose_decode(const void* prob, int pcp, int pc0, const void* loc, int lcp, int lc0, int esize, int NB, int H,
+int launch_pose_decode(const void* prob, int pcp, int pc0, const void* loc, int lcp, int lc0, int ekind, int NB, int H,
                        int W, int J, double scale, double* out, void* stream) {
   if (NB <= 0 || J <= 0) return 0;
-  if (esize == 2)
-    hipLaunchKernelGGL(pose_decode_kernel<_Float16>, dim3(J, NB), dim3(256), 0, (hipStream_t)stream, (const _Float16*)prob,
-                       pcp, pc0, (const _Float16*)loc, lcp, lc0, H, W, J, scale, out);
-  else
-    hipLaunchKernelGGL(pose_decode_kernel<float>, dim3(J, NB), dim3(256), 0, (hipStream_t)stream, (const float*)prob, pcp,
-                       pc0, (const float*)loc, lcp, lc0, H, W, J, scale, out);
-  return (int)hipGetLastError();
+  return dc_by_kind(ekind, [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    hipLaunchKernelGGL(pose_decode_kernel<T>, dim3(J, NB), dim3(256), 0, (hipStream_t)stream, (const T*)prob, pcp, pc0, (const T*)loc, lcp,
+                       lc0, H, W, J, scale, out);
+    return (int)hipGetLastError();
+  });
 }
 
 // ---- multi-person consumers: part candidates (NMS) and pairwise regression decode ------------------------------------
@@ -2321,30 +2455,28 @@ __global__ __launch_bounds__(256) void pairwise_decode_kernel(const T* __restric
   o[1] = ((double)row * 8.0 + 4.0 + (double)(float)p[1] * s1 + m1) / scale;
 }
 
-int launch_part_select(const void* prob, int pcp, int pc0, const void* loc, int lcp, int lc0, int esize, int NB, int H, int W, int J, float thr,
+int launch_part_select(const void* prob, int pcp, int pc0, const void* loc, int lcp, int lc0, int ekind, int NB, int H, int W, int J, float thr,
                        int radius, double scale, int max_det, unsigned long long* spill, int* counts, double* out, void* stream) {
   if (NB * J <= 0) return 0;
-  if (esize == 2)
-    hipLaunchKernelGGL(part_select_kernel<_Float16>, dim3(NB * J), dim3(256), 0, (hipStream_t)stream, (const _Float16*)prob, pcp, pc0,
-                       (const _Float16*)loc, lcp, lc0, H, W, J, thr, radius, scale, max_det, spill, counts, out);
-  else
-    hipLaunchKernelGGL(part_select_kernel<float>, dim3(NB * J), dim3(256), 0, (hipStream_t)stream, (const float*)prob, pcp, pc0,
-                       (const float*)loc, lcp, lc0, H, W, J, thr, radius, scale, max_det, spill, counts, out);
-  return (int)hipGetLastError();
+  return dc_by_kind(ekind, [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    hipLaunchKernelGGL(part_select_kernel<T>, dim3(NB * J), dim3(256), 0, (hipStream_t)stream, (const T*)prob, pcp, pc0, (const T*)loc, lcp,
+                       lc0, H, W, J, thr, radius, scale, max_det, spill, counts, out);
+    return (int)hipGetLastError();
+  });
 }
 
-int launch_pairwise_decode(const void* next, int ncp, int nc0, int esize, int NB, int H, int W, int E, double scale, int ndet,
+int launch_pairwise_decode(const void* next, int ncp, int nc0, int ekind, int NB, int H, int W, int E, double scale, int ndet,
                            const int* det, const double* mean, const double* stdev, double* out, void* stream) {
   const long total = (long)ndet * E;
   if (total <= 0) return 0;
   const dim3 grid((unsigned)((total + 255) / 256));
-  if (esize == 2)
-    hipLaunchKernelGGL(pairwise_decode_kernel<_Float16>, grid, dim3(256), 0, (hipStream_t)stream, (const _Float16*)next, ncp, nc0, NB, H, W,
-                       E, scale, ndet, det, mean, stdev, out);
-  else
-    hipLaunchKernelGGL(pairwise_decode_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)next, ncp, nc0, NB, H, W, E,
-                       scale, ndet, det, mean, stdev, out);
-  return (int)hipGetLastError();
+  return dc_by_kind(ekind, [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    hipLaunchKernelGGL(pairwise_decode_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, (const T*)next, ncp, nc0, NB, H, W, E, scale, ndet,
+                       det, mean, stdev, out);
+    return (int)hipGetLastError();
+  });
 }
 
 // ---- image pre-processing -----------------------------------------------------------------------------------------
@@ -2418,7 +2550,7 @@ __global__ __launch_bounds__(256) void image_finish_kernel(ImagePrepParams p) {
 }
 
 int launch_image_prep(const ImagePrepParams& p, void* stream) {
-  if (p.dst_esize != 2 && p.dst_esize != 4) return (int)hipErrorInvalidValue;
+  if (p.dst_ekind != kElemF32 && p.dst_ekind != kElemF16 && p.dst_ekind != kElemBF16) return (int)hipErrorInvalidValue;
   if (p.dst_cp < 3 || p.use_h > p.out_h || p.use_w > p.out_w) return (int)hipErrorInvalidValue;
   if (p.x_bounds) {
     const long total = (long)p.n * p.rows * p.use_w;
@@ -2427,11 +2559,11 @@ int launch_image_prep(const ImagePrepParams& p, void* stream) {
   }
   const long total = (long)p.n * p.out_h * p.out_w;
   if (total <= 0) return 0;
-  if (p.dst_esize == 2)
-    hipLaunchKernelGGL(image_finish_kernel<_Float16>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
-  else
-    hipLaunchKernelGGL(image_finish_kernel<float>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
-  return (int)hipGetLastError();
+  return dc_by_kind(p.dst_ekind, [&](auto* tag) {
+    hipLaunchKernelGGL(image_finish_kernel<std::remove_pointer_t<decltype(tag)>>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, p);
+    return (int)hipGetLastError();
+  });
 }
 
 }  // namespace dc

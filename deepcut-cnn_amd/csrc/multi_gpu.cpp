@@ -402,7 +402,7 @@ void Comm::forward(Net* const* nets, const float* const* inputs, const int (*hw)
     // a sub-batch must stay a batch the kernels run well on: halves of at least 4 images in float32, 8 in float16 (measured on one GPU,
     // 8 executors x 8 images of 544x736: float16 halves of 4 ran 624 images/s where whole batches of 8 run 803; float32 halves of 4
     // 357 against 333) — smaller groups go as one batch, still pipelined against the executor's other groups
-    const size_t min_half = nets[k]->dtype == 1 ? 8 : 4;
+    const size_t min_half = nets[k]->dtype != kElemF32 ? 8 : 4;  // (bfloat16: the float16 bytes and matrix rate)
     for (const Group& g : whole) {
       const size_t nb = g.idx.size(), first = nb >= 2 * min_half ? (nb + 1) / 2 : nb;
       for (size_t b0 = 0; b0 < nb; b0 += (b0 == 0 ? first : nb - first)) {

@@ -42,9 +42,10 @@ struct Storage {
   float* host = nullptr;
   size_t host_cap = 0;
   bool host_pinned = false;
-  unsigned char* dev = nullptr;  // NHWC image (float or _Float16 elements, `esize` bytes each), channel pitch cp()
+  unsigned char* dev = nullptr;  // NHWC image (float, _Float16 or __bf16 elements, `esize` bytes each), channel pitch cp()
   size_t dev_cap = 0;            // capacity in bytes
-  int esize = 4;                 // bytes per device element (2 in fp16 nets)
+  int esize = 4;                 // bytes per device element (2 in fp16 and bf16 nets)
+  int ekind = kElemF32;          // ElemKind of the device image
   float* stage = nullptr;  // device NCHW staging for up/download
   size_t stage_cap = 0;
   int head = UNINITIALIZED;
@@ -116,6 +117,7 @@ struct LayerRec {
 struct DevVec {  // a packed filter / affine vector; shared between a Net and its clones
   std::vector<float> host;
   bool as_half = false;  // filter image of an fp16 net: converted to _Float16 on upload
+  bool as_bf16 = false;  // ... of a bf16 net: converted to __bf16 (round to nearest even) on upload
   // fp16 filter images: output channel c of the image was multiplied by an exact power of two 2^k(c) that brings its largest
   // weight into [2^13, 2^14) — filters of 1e-5 (a head on a trunk with large activations) would otherwise sit in float16's
   // subnormal range with a handful of significant bits —; row_scale[c] = 2^-k(c) goes into the launch's fp32 epilogue scale
@@ -159,6 +161,14 @@ void resample_coeffs(int in_size, int out_size, int& ksize, std::vector<int>& bo
 // estimate_pose.py:85-88,96: canvas (stride-8) and resized-image sizes for an h x w image at `scale`
 void image_canvas_size(int h, int w, double scale, int& out_h, int& out_w, int& new_h, int& new_w);
 
+// A tile takes K segments of `klen` elements: klen is a multiple of its K tile, and for a row-tap launch exactly one K tile.  (A row
+// tap spans several adjacent pixels of a narrow input; the kernel checks a lane's tap validity at its column of the tap's FIRST K tile,
+// so a later K tile of the same tap would read the pixels past the row end — the next row's, or past the tensor — as if they were inside.)
+inline bool tile_takes_k(int v, int klen, bool row_tap) {
+  const int bk = conv_variant_bk(v);
+  return klen % bk == 0 && (!row_tap || bk == klen);
+}
+
 struct Launch {
   enum Kind { CONV, POOL, ELT, CROP } kind = CONV;
   std::string label;    // e.g. "res4b3_branch2b+bn+scale+relu"
@@ -168,14 +178,20 @@ struct Launch {
   // CONV
   ConvGemmParams cg{};  // pointers filled at launch time
   int variant = 0;
+  bool row_tap = false;  // one tap per kernel row over several adjacent pixels (inputs narrower than a K tile): see tile_takes_k
   std::shared_ptr<DevVec> w, scale, shift;  // packed filters / folded affine (kept alive by the plan)
   std::shared_ptr<DevVec> wino_w;           // Winograd-transformed filters (eligible 3x3 layers) / the fragment-order image of the streaming
                                             // form (eligible float16 1x1 layers, stream1x1.hip), else null
   std::shared_ptr<DevVec> wino_scale;       // float16 nets: the epilogue scale of the Winograd form (folded affine x the image's row scale x 4)
   // a Winograd form this launch can run as: the image exists and the form serves the net's element type
   bool takes_wino(int v) const {
-    return is_wino_variant(v) && (bool)wino_w && wino_variant_esize(v) == cg.esize && cg.ncls <= 1 && (v == kStreamHalf || v == kStreamFloat) == (cg.nty == 1 && cg.ntx == 1) &&
+    return is_wino_variant(v) && (bool)wino_w && wino_variant_ekind(v) == cg.ekind && cg.ncls <= 1 && (v == kStreamHalf || v == kStreamFloat) == (cg.nty == 1 && cg.ntx == 1) &&
            (v == kStemHalf || v == kStemFloat) == (cg.nty == 7 && cg.ntx == 1);
+  }
+  // a tile (or form) this launch can run on: the net's element kind, the launch's K segments and deconvolution classes
+  bool takes_tile(int v) const {
+    if (is_wino_variant(v)) return takes_wino(v);
+    return conv_variant_exists(v) && conv_variant_ekind(v) == cg.ekind && tile_takes_k(v, cg.klen, row_tap) && (cg.ncls <= 1 || conv_variant_multiclass(v));
   }
   long y_off = 0;                      // element offset of this launch's first output (deconvolution classes, channel splits)
   long w_off = 0;                      // element offset of this launch's first filter row inside `w` (channel splits)
@@ -225,7 +241,7 @@ struct Net {
   std::vector<int> inputs, outputs;  // blob indices
 
   int fuse = 2;
-  int dtype = 0;  // 0: float activations/filters; 1: _Float16 activations/filters, fp32 accumulate + epilogue
+  int dtype = 0;  // ElemKind of activations / filters: 0 float; 1 _Float16, 2 __bf16 (fp32 accumulate + epilogue in both)
   int use_graph = 0;
   int outputs_mask = -1;  // DC_OPT_OUTPUTS: bit i = output i (order of `outputs`) is wanted
   std::shared_ptr<ModelShared> shared;   // joint with every clone
@@ -263,7 +279,7 @@ struct Net {
   static void choose_streams(const std::vector<Net*>& nets, int ncand, int reps, double* rate_chosen, double* rate_first);
   void adopt_stream(void* s);  // a pool stream becomes the net's own
   void* own_stream();          // the net's own stream, created on first use
-  void set_dtype(int d);  // 0 float32 / 1 float16 device images (DC_OPT_DTYPE)
+  void set_dtype(int d);  // 0 float32 / 1 float16 / 2 bfloat16 device images (DC_OPT_DTYPE)
   void set_outputs_mask(int mask);  // DC_OPT_OUTPUTS
   void copy_from(const std::string& path);
   void save(const std::string& path);
@@ -330,7 +346,7 @@ struct Net {
   std::map<std::pair<int, int>, std::shared_ptr<ResampleTable>> resample_;
   struct MapRef {
     const void* ptr;
-    int cp, c0, es, NB, C, H, W;
+    int cp, c0, es, ek, NB, C, H, W;
   };
   MapRef map_ref(const char* blob_name);  // device image of an output map (channel views of the merged heads included)
   unsigned char* scratch_dev_ = nullptr;  // candidates / detections / pairwise scratch
@@ -358,6 +374,7 @@ struct GroupLaunch {
   int index = 0;              // index into every member's plan
   int member = -1;            // !multi: the member whose launch `index` this is
   ConvGemmParams p{};         // multi: the layer's common block (not yet prepared for a variant)
+  bool row_tap = false;       // ... a row-tap layer (Launch::row_tap)
   const void* ws_w = nullptr; // ... the layer's stream1x1 filter image if every member has one (variant kStreamHalf reads it instead of p.w)
   ConvMultiTable table{};     // ... and the problems (pointers filled, not yet prepared)
   ConvMultiArgs args{};       // both, prepared for `variant`: the kernel arguments

@@ -152,14 +152,18 @@ static long group_args(const GroupLaunch& gl, int variant, ConvMultiArgs& a) {
   if (variant == kStreamHalf) {
     if (!gl.ws_w) return -1;
     a.p.w = gl.ws_w;
+  } else if (!conv_variant_exists(variant) || !tile_takes_k(variant, gl.p.klen, gl.row_tap)) {
+    return -1;
   }
   return prepare_conv_multi(a.p, a.t, gl.nprob, variant);
 }
 // the tiles a merged launch can be timed on: every multi-problem tile of its K granularity and type, and the streaming form
 static std::vector<int> group_candidates(const GroupLaunch& gl) {
   std::vector<int> c;
-  for (int v = 0; v < conv_num_variants(); ++v)
-    if (conv_variant_multiproblem(v) && gl.p.klen % conv_variant_bk(v) == 0 && conv_variant_esize(v) == gl.p.esize) c.push_back(v);
+  int n = 0;
+  const int* cand = conv_variants_of(gl.p.ekind, &n);
+  for (int i = 0; i < n; ++i)
+    if (conv_variant_multiproblem(cand[i]) && tile_takes_k(cand[i], gl.p.klen, gl.row_tap)) c.push_back(cand[i]);
   if (gl.ws_w && env_int("DC_STREAM1X1", -1) != 0) c.push_back(kStreamHalf);
   return c;
 }
@@ -228,15 +232,17 @@ void NetGroup::merge(GroupPlan& gp) {
       const bool wino_apart = is_wino_variant(l.variant) && l.variant != kWinoHalf && l.variant != kStreamHalf && l.variant != kStreamFloat && l.variant != kStemFloat;
       if (l.kind != Launch::CONV || wino_apart || l.w != l0.w || l.scale != l0.scale || l.shift != l0.shift || l.c_off != l0.c_off ||
           l.w_off != l0.w_off ||
-          (l.in2 >= 0) != (l0.in2 >= 0) || g.esize != g0.esize || g.klen != g0.klen || g.sy != g0.sy || g.sx != g0.sx || g.Cout != g0.Cout ||
+          (l.in2 >= 0) != (l0.in2 >= 0) || g.esize != g0.esize || g.ekind != g0.ekind || g.klen != g0.klen || g.sy != g0.sy || g.sx != g0.sx || g.Cout != g0.Cout ||
           g.relu != g0.relu || g.sigmoid_ch != g0.sigmoid_ch)
         mergeable = false;
     }
     if (mergeable) {
       // a multi-problem tile must exist for this K granularity
       bool have = false;
-      for (int v = 0; v < conv_num_variants(); ++v)
-        if (conv_variant_multiproblem(v) && l0.cg.klen % conv_variant_bk(v) == 0 && conv_variant_esize(v) == l0.cg.esize) have = true;
+      int n = 0;
+      const int* cand = conv_variants_of(l0.cg.ekind, &n);
+      for (int k = 0; k < n; ++k)
+        if (conv_variant_multiproblem(cand[k]) && tile_takes_k(cand[k], l0.cg.klen, l0.row_tap)) have = true;
       mergeable = have;
     }
     if (!mergeable) {
@@ -314,6 +320,7 @@ void NetGroup::merge(GroupPlan& gp) {
       gl.index = (int)i;
       gl.nprob = (int)std::min<size_t>(kMaxProblems, recs.size() - r0);
       gl.p = l0.cg;  // the layer's common fields: esize, klen, sy, sx, Cout, relu, sigmoid_ch
+      gl.row_tap = l0.row_tap;
       gl.p.ncls = 0;
       gl.p.dbg = nullptr;
       gl.p.x = nullptr, gl.p.y = nullptr, gl.p.resid = nullptr;
@@ -347,9 +354,10 @@ void NetGroup::merge(GroupPlan& gp) {
       if (!gl.multi) continue;
       auto it = nets[0]->shared->tune_cache.find(gl.key);
       int v = it != nets[0]->shared->tune_cache.end() ? it->second : -1;
-      const int forced = env_int("DC_CONV_VARIANT", -1);
-      if (forced >= 0 && forced < conv_num_variants() && conv_variant_multiproblem(forced) && gl.p.klen % conv_variant_bk(forced) == 0 &&
-          conv_variant_esize(forced) == gl.p.esize)
+      const int forced_bf16 = env_int("DC_CONV_VARIANT_BF16", -1);
+      const int forced = gl.p.ekind == kElemBF16 && forced_bf16 >= 0 ? kBf16Variant0 + forced_bf16 : env_int("DC_CONV_VARIANT", -1);
+      if (forced >= 0 && conv_variant_exists(forced) && conv_variant_multiproblem(forced) && tile_takes_k(forced, gl.p.klen, gl.row_tap) &&
+          conv_variant_ekind(forced) == gl.p.ekind)
         v = forced;
       if (forced < 0 && gl.ws_w && env_int("DC_STREAM1X1", -1) >= 1) v = kStreamHalf;  // (forced on: wherever eligible, as in Net's lowering)
       gl.variant = v;
@@ -359,7 +367,7 @@ void NetGroup::merge(GroupPlan& gp) {
     if (!gl.multi) continue;
     int v = gl.variant;
     auto usable = [&](int cand) {
-      if (cand != kStreamHalf && (cand < 0 || cand >= conv_num_variants() || is_wino_variant(cand))) return false;
+      if (cand != kStreamHalf && (!conv_variant_exists(cand) || is_wino_variant(cand))) return false;
       ConvMultiArgs a;
       return group_args(gl, cand, a) > 0;
     };
@@ -369,8 +377,10 @@ void NetGroup::merge(GroupPlan& gp) {
       for (int c : gp.lane_members[gl.lane])
         if (nets[c]->plan[gl.index].cg.M > nets[big]->plan[gl.index].cg.M) big = (size_t)c;
       if (usable(nets[big]->plan[gl.index].variant)) v = nets[big]->plan[gl.index].variant;
-      for (int cand = 0; v < 0 && cand < conv_num_variants(); ++cand)
-        if (usable(cand)) v = cand;
+      int n = 0;
+      const int* cands = conv_variants_of(gl.p.ekind, &n);
+      for (int k = 0; v < 0 && k < n; ++k)
+        if (usable(cands[k])) v = cands[k];
       if (v < 0) throw DcError(DC_EUNSUP, "group launch '" + gl.label + "': no multi-problem tile takes it");
     }
     apply_variant(gp, gl, v);
@@ -681,11 +691,11 @@ void NetGroup::forward_batch(const float* const* inputs, const int* n, const int
     Storage& in = *ins[c];
     const int C = in.dim(1);
     if (is_device) {
-      KCHECK(launch_nchw_to_nhwc(inputs[c], in.dev, in.esize, n[c], C, h[c], w[c], in.cp(), s));
+      KCHECK(launch_nchw_to_nhwc(inputs[c], in.dev, in.ekind, n[c], C, h[c], w[c], in.cp(), s));
     } else {
       in.ensure_stage(in.count());
       HIPCHECK(hipMemcpyAsync(in.stage, inputs[c], in.count() * sizeof(float), hipMemcpyHostToDevice, (hipStream_t)s));
-      KCHECK(launch_nchw_to_nhwc(in.stage, in.dev, in.esize, n[c], C, h[c], w[c], in.cp(), s));
+      KCHECK(launch_nchw_to_nhwc(in.stage, in.dev, in.ekind, n[c], C, h[c], w[c], in.cp(), s));
     }
     in.head = HEAD_AT_GPU;
   }
@@ -727,7 +737,7 @@ std::string NetGroup::plan_text() {
   if (!cur_) throw DcError(DC_EINVAL, "group: run a forward first");
   std::ostringstream os;
   os << "# group of " << nets.size() << " executors in " << cur_->nlanes << " lane" << (cur_->nlanes > 1 ? "s" : "") << ": " << cur_->launches.size() << " launches (" << num_multi_launches() << " multi-problem), "
-     << cur_->flops / 1e9 << " GFLOP algorithmic" << (nets[0]->dtype == 1 ? ", dtype=f16" : ", dtype=f32") << "\n";
+     << cur_->flops / 1e9 << " GFLOP algorithmic" << ", dtype=" << elem_kind_name(nets[0]->dtype) << "\n";
   for (size_t i = 0; i < cur_->launches.size(); ++i) {
     const GroupLaunch& gl = cur_->launches[i];
     os << i << "\t";
@@ -774,9 +784,7 @@ std::string NetGroup::tune_report_text() {
 
 void NetGroup::set_tile(const std::string& key, const std::string& tile) {
   current_plan();
-  int v = -1;
-  for (int i = 0; v < 0 && i < conv_num_variants(); ++i)
-    if (tile == conv_variant(i).name) v = i;
+  int v = conv_variant_by_name(tile.c_str());
   if (tile == conv_variant(kStreamHalf).name) v = kStreamHalf;
   if (v < 0) throw DcError(DC_EINVAL, "no tile variant named '" + tile + "'");
   bool any = false;

@@ -122,7 +122,7 @@ void Net::prep_images(const unsigned char* bgr, int n, int h, int w, double scal
   q.src = src;
   q.n = n, q.h = h, q.w = w;
   q.out_h = out_h, q.out_w = out_w, q.use_h = use_h, q.use_w = use_w;
-  q.dst = in.dev, q.dst_esize = in.esize, q.dst_cp = in.cp();
+  q.dst = in.dev, q.dst_ekind = in.ekind, q.dst_cp = in.cp();
   q.mean[0] = 104.f, q.mean[1] = 117.f, q.mean[2] = 123.f;  // _MEAN, estimate_pose.py:26
   std::shared_ptr<ResampleTable> hold_y, hold_x;  // the tables outlive a cache flush until the launches are enqueued
   if (need_y) {
@@ -179,14 +179,14 @@ void Net::decode_pose(double scale, double* out, bool is_device, void* user_stre
   };
   const void *pp, *lp;
   int pcp, pc0, lcp, lc0;
-  const int pes = P.view_of >= 0 ? storages[P.view_of]->esize : P.esize;
+  const int pek = P.view_of >= 0 ? storages[P.view_of]->ekind : P.ekind;
   img(P, pp, pcp, pc0);
   img(L, lp, lcp, lc0);
   const int NB = P.dim(0), J = P.dim(1), H = P.dim(2), W = P.dim(3);
   void* s = user_stream ? user_stream : stream;
   const size_t cnt = (size_t)NB * 5 * J;
   if (is_device) {
-    KCHECK(launch_pose_decode(pp, pcp, pc0, lp, lcp, lc0, pes, NB, H, W, J, scale, out, s));
+    KCHECK(launch_pose_decode(pp, pcp, pc0, lp, lcp, lc0, pek, NB, H, W, J, scale, out, s));
     if (!user_stream) HIPCHECK(hipStreamSynchronize((hipStream_t)s));
     return;
   }
@@ -196,7 +196,7 @@ void Net::decode_pose(double scale, double* out, bool is_device, void* user_stre
     dev_alloc((void**)&pose_dev, cnt * sizeof(double));
     pose_cap = cnt;
   }
-  KCHECK(launch_pose_decode(pp, pcp, pc0, lp, lcp, lc0, pes, NB, H, W, J, scale, pose_dev, s));
+  KCHECK(launch_pose_decode(pp, pcp, pc0, lp, lcp, lc0, pek, NB, H, W, J, scale, pose_dev, s));
   HIPCHECK(hipMemcpyAsync(out, pose_dev, cnt * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)s));
   HIPCHECK(hipStreamSynchronize((hipStream_t)s));
 }
@@ -212,10 +212,10 @@ Net::MapRef Net::map_ref(const char* blob_name) {
   MapRef r{};
   if (s.view_of >= 0) {
     Storage& b = *storages[s.view_of];
-    r.ptr = b.dev, r.cp = b.cp(), r.c0 = s.view_c0, r.es = b.esize;
+    r.ptr = b.dev, r.cp = b.cp(), r.c0 = s.view_c0, r.es = b.esize, r.ek = b.ekind;
   } else {
     if (s.head == HEAD_AT_CPU) sync_to_device(s);
-    r.ptr = s.dev, r.cp = s.cp(), r.c0 = 0, r.es = s.esize;
+    r.ptr = s.dev, r.cp = s.cp(), r.c0 = 0, r.es = s.esize, r.ek = s.ekind;
   }
   r.NB = s.dim(0), r.C = s.dim(1), r.H = s.dim(2), r.W = s.dim(3);
   return r;
@@ -248,7 +248,7 @@ void Net::detect_parts(double scale, float thr, int radius, int max_det, int* co
   int* cnt = (int*)base;
   unsigned long long* spill = (unsigned long long*)(base + cnt_b);
   double* out = (double*)(base + cnt_b + spill_b);
-  KCHECK(launch_part_select(P.ptr, P.cp, P.c0, L.ptr, L.cp, L.c0, P.es, P.NB, P.H, P.W, P.C, thr, radius, scale, max_det, spill, cnt, out,
+  KCHECK(launch_part_select(P.ptr, P.cp, P.c0, L.ptr, L.cp, L.c0, P.ek, P.NB, P.H, P.W, P.C, thr, radius, scale, max_det, spill, cnt, out,
                             stream));
   HIPCHECK(hipMemcpyAsync(counts, cnt, (size_t)lists * sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
   HIPCHECK(hipMemcpyAsync(dets, out, out_b, hipMemcpyDeviceToHost, (hipStream_t)stream));
@@ -274,7 +274,7 @@ void Net::decode_pairwise(double scale, int ndet, const int* det, const double* 
   HIPCHECK(hipMemcpyAsync(ddet, det, (size_t)ndet * 3 * sizeof(int), hipMemcpyHostToDevice, (hipStream_t)stream));
   if (mean) HIPCHECK(hipMemcpyAsync(dmean, mean, st_b, hipMemcpyHostToDevice, (hipStream_t)stream));
   if (stdev) HIPCHECK(hipMemcpyAsync(dstd, stdev, st_b, hipMemcpyHostToDevice, (hipStream_t)stream));
-  KCHECK(launch_pairwise_decode(N.ptr, N.cp, N.c0, N.es, N.NB, N.H, N.W, E, scale, ndet, ddet, mean ? dmean : nullptr,
+  KCHECK(launch_pairwise_decode(N.ptr, N.cp, N.c0, N.ek, N.NB, N.H, N.W, E, scale, ndet, ddet, mean ? dmean : nullptr,
                                 stdev ? dstd : nullptr, dout, stream));
   HIPCHECK(hipMemcpyAsync(out, dout, out_b, hipMemcpyDeviceToHost, (hipStream_t)stream));
   HIPCHECK(hipStreamSynchronize((hipStream_t)stream));
@@ -286,7 +286,7 @@ std::string Net::plan_text() {
   os << "# plan for input";
   for (int d : plan_input_shape) os << " " << d;
   os << ": " << plan.size() << " launches, " << plan_flops / 1e9 << " GFLOP algorithmic, fuse=" << fuse
-     << (dtype == 1 ? ", dtype=f16" : ", dtype=f32") << "\n";
+     << ", dtype=" << elem_kind_name(dtype) << "\n";
   for (size_t i = 0; i < plan.size(); ++i) {
     const Launch& l = plan[i];
     os << i << "\t" << l.kernel << "\t";

@@ -133,7 +133,7 @@ Net* Net::clone() {
   if (dtype != c->dtype) {
     c->dtype = dtype;
     for (auto& st : c->storages)
-      if (!st->is_param) st->esize = dtype == 1 ? 2 : 4;
+      if (!st->is_param) st->esize = elem_kind_size(dtype), st->ekind = dtype;
   }
   c->device = device;
   c->reshape();
@@ -156,7 +156,7 @@ void Net::set_outputs_mask(int mask) {
 }
 
 void Net::set_dtype(int d) {
-  if (d != 0 && d != 1) throw DcError(DC_EINVAL, "dtype must be 0 (float32) or 1 (float16)");
+  if (d != kElemF32 && d != kElemF16 && d != kElemBF16) throw DcError(DC_EINVAL, "dtype must be 0 (float32), 1 (float16) or 2 (bfloat16)");
   if (d == dtype) return;
   dtype = d;
   for (auto& st : storages) {
@@ -168,7 +168,8 @@ void Net::set_dtype(int d) {
       st->dev = nullptr;
       st->dev_cap = 0;
     }
-    st->esize = d == 1 ? 2 : 4;
+    st->esize = elem_kind_size(d);
+    st->ekind = d;
   }
   invalidate_plans();  // packed images are keyed by dtype in the shared cache: no re-pack of the other type's images
 }

@@ -310,7 +310,8 @@ void Net::build_plan() {
           auto st = std::make_shared<Storage>();
           st->id = (int)storages.size();
           st->owner = this;
-          st->esize = dtype == 1 ? 2 : 4;
+          st->esize = elem_kind_size(dtype);
+          st->ekind = dtype;
           storages.push_back(st);
           id = st->id;
           aux_index_[key] = id;
@@ -428,10 +429,15 @@ void Net::build_plan() {
     }
     return s;
   };
-  const int force_variant = env_int("DC_CONV_VARIANT", -1);
-  const int es = dtype == 1 ? 2 : 4;          // bytes per activation / filter element
-  const int kmin = dtype == 1 ? 64 : 32;      // smallest K tile of the dtype's variants (one 128-byte line)
-  const std::string dkey = dtype == 1 ? "h:" : "";
+  // DC_CONV_VARIANT=i forces tile i of the float32 / float16 table, DC_CONV_VARIANT_BF16=i tile i of the bfloat16 one (on bf16 nets;
+  // a forced tile of the other table matches no candidate there: the cost model chooses)
+  const int force_bf16 = env_int("DC_CONV_VARIANT_BF16", -1);
+  const int force_variant = dtype == kElemBF16 && force_bf16 >= 0 ? kBf16Variant0 + force_bf16 : env_int("DC_CONV_VARIANT", -1);
+  const int es = elem_kind_size(dtype);       // bytes per activation / filter element
+  const int kmin = es == 2 ? 64 : 32;         // smallest K tile of the dtype's variants (one 128-byte line)
+  const std::string dkey = dtype == kElemF16 ? "h:" : dtype == kElemBF16 ? "b:" : "";
+  int ncand = 0;
+  const int* cand = conv_variants_of(dtype, &ncand);  // the tiles of the net's element kind, in table order
 
   auto affine_vecs = [&](const LOp& op, Launch& l, int C) {
     if (op.a.empty()) return;
@@ -450,7 +456,7 @@ void Net::build_plan() {
   // a[c] * 2^-k(c) (keyed by the image, since k depends on the image's rows).
   static const bool half_rowscale = env_int("DC_HALF_ROWSCALE", 1) != 0;
   auto half_row_scale = [&](Launch& l, const LOp& op, int OC) {
-    if (dtype != 1 || !half_rowscale || !l.w) return;
+    if (dtype != kElemF16 || !half_rowscale || !l.w) return;
     DevVec& Wv = *l.w;
     if (Wv.row_scale.empty()) {
       if (Wv.host.empty()) return;  // an image uploaded before this feature existed in the process: leave it
@@ -499,15 +505,17 @@ void Net::build_plan() {
     int best = -1;
     double bc = 0;
     const bool mc = l.cg.ncls > 1;  // multi-class launches need a tile with a multi-class instantiation
-    for (int v = 0; v < conv_num_variants(); ++v) {
-      if (kgcd % conv_variant_bk(v) != 0 || conv_variant_esize(v) != es || (mc && !conv_variant_multiclass(v))) continue;
+    for (int ci = 0; ci < ncand; ++ci) {
+      const int v = cand[ci];
+      if (!tile_takes_k(v, kgcd, l.row_tap) || (mc && !conv_variant_multiclass(v))) continue;
       if (force_variant >= 0 && v != force_variant) continue;
       double c = variant_cost(l.cg, v);
       if (best < 0 || c < bc) best = v, bc = c;
     }
     if (best < 0)
-      for (int v = 0; v < conv_num_variants(); ++v) {
-        if (kgcd % conv_variant_bk(v) != 0 || conv_variant_esize(v) != es || (mc && !conv_variant_multiclass(v))) continue;
+      for (int ci = 0; ci < ncand; ++ci) {
+        const int v = cand[ci];
+        if (!tile_takes_k(v, kgcd, l.row_tap) || (mc && !conv_variant_multiclass(v))) continue;
         double c = variant_cost(l.cg, v);
         if (best < 0 || c < bc) best = v, bc = c;
       }
@@ -584,6 +592,7 @@ void Net::build_plan() {
       l.kind = Launch::CONV;
       ConvGemmParams& g = l.cg;
       g.esize = es;
+      g.ekind = dtype;
       g.x_img_stride = (long)H * W * CP;
       g.x_row_stride = W * CP;
       g.x_rows = H;
@@ -592,6 +601,7 @@ void Net::build_plan() {
       g.sx = c.sw * CP;
       int kgcd;
       const bool rowtap = (CP % kmin) != 0;
+      l.row_tap = rowtap;
       if (rowtap) {
         // small-channel input (the 3->4 channel stem): one tap per kernel ROW, the kw adjacent pixels of
         // that row being contiguous in NHWC; K per tap = kw*CP rounded up to 32 with zero weights
@@ -670,18 +680,19 @@ void Net::build_plan() {
       affine_vecs(op, l, OC);
       l.flops = 2.0 * g.M * (double)OC * C * c.kh * c.kw;
       plan_flops += l.flops;
-      l.w->as_half = dtype == 1;
+      l.w->as_half = dtype == kElemF16;
+      l.w->as_bf16 = dtype == kElemBF16;
           half_row_scale(l, op, OC);
       choose_variant(l, kgcd);
       // stride-1 3x3 layers can also run as Winograd F(2x2,3x3): keep the transformed filters next to the direct ones
       // and let the per-shape timing decide (kernels.hip, wino_f23_kernel)
-      if (!rowtap && wino_mode != 0 && op.wls.empty() && wino_eligible(g) && dtype == 0) {
+      if (!rowtap && wino_mode != 0 && op.wls.empty() && wino_eligible(g) && dtype == kElemF32) {
         l.wino_w = get_vec(dkey + "wino:" + std::to_string(op.wl), [&](std::vector<float>& h) {
           h.assign(wino_packed_floats(c.num_output, C), 0.f);
           wino_pack_filters(L.params[0]->st->host_ptr(), c.num_output, C, h.data());
         });
         if (wino_mode >= 1 && (force_variant < 0 || is_wino_variant(force_variant))) use_wino(l, wino_mode == 2 ? kWinoVariant16 : kWinoVariant);
-      } else if (!rowtap && wino_mode != 0 && op.wls.empty() && dtype == 1 && op.in2 < 0 && wino_eligible(g)) {
+      } else if (!rowtap && wino_mode != 0 && op.wls.empty() && dtype == kElemF16 && op.in2 < 0 && wino_eligible(g)) {
         // float16 (wino_f16.hip): the image is packed in MFMA fragment order with its own per-channel power-of-two row scale
         // (DevVec::row_scale: G g G^T has other maxima than g); the form's epilogue scale = folded affine x row scale x 4 (the
         // kernel stages the pixels pre-multiplied by 1/4 so that B^T d B cannot overflow float16)
@@ -701,7 +712,7 @@ void Net::build_plan() {
           for (int q = 0; q < OC; ++q) h[q] = (float)((op.a.empty() ? 1.0 : op.a[q]) * 4.0 * (double)(ws->row_scale.empty() ? 1.f : ws->row_scale[q]));
         });
         if (wino_mode >= 1 && (force_variant < 0 || is_wino_variant(force_variant))) use_wino(l, kWinoHalf);
-      } else if (!rowtap && stream_mode != 0 && op.wls.empty() && dtype == 1 && g.klen == C && g.Ktot == C && stream1x1_eligible(g)) {
+      } else if (!rowtap && stream_mode != 0 && op.wls.empty() && dtype == kElemF16 && g.klen == C && g.Ktot == C && stream1x1_eligible(g)) {
         // float16 dense 1x1 layers (stream1x1.hip): the same row-scaled filters as the direct image, in MFMA fragment order;
         // scale / shift / shortcut are the launch's own.  The per-shape timing decides (DC_STREAM1X1=1: wherever eligible, 0: never)
         std::shared_ptr<DevVec> direct = l.w;
@@ -718,7 +729,7 @@ void Net::build_plan() {
         l.wino_w->as_half = true;
         if (stream_mode >= 1 && (force_variant < 0 || is_wino_variant(force_variant))) use_wino(l, kStreamHalf);
       }
-      if (!rowtap && !l.wino_w && stream_mode != 0 && op.wls.empty() && dtype == 0 && g.klen == C && g.Ktot == C && stream1x1f_eligible(g)) {
+      if (!rowtap && !l.wino_w && stream_mode != 0 && op.wls.empty() && dtype == kElemF32 && g.klen == C && g.Ktot == C && stream1x1f_eligible(g)) {
         // float32 dense 1x1 layers with 64 / 128 / 256 / 512 input channels (stream1x1_f32.hip): the filters in the order of its 16x16x4 matrix steps
         l.wino_w = get_vec(dkey + "wsf:" + std::to_string(op.wl), [&](std::vector<float>& h) {
           h.assign(stream1x1f_packed_elems(OC, C), 0.f);
@@ -726,7 +737,7 @@ void Net::build_plan() {
         });
         if (stream_mode >= 1 && (force_variant < 0 || is_wino_variant(force_variant))) use_wino(l, kStreamFloat);
       }
-      if (rowtap && stem_mode != 0 && op.wls.empty() && dtype == 1 && C <= 4 && stem7x7_eligible(g)) {
+      if (rowtap && stem_mode != 0 && op.wls.empty() && dtype == kElemF16 && C <= 4 && stem7x7_eligible(g)) {
         // float16 stem (stem_f16.hip): the same row-scaled filters as the row-tap image, the 28 real elements of every kernel row in MFMA
         // operand order; scale / shift are the launch's own.  The per-shape timing decides (DC_STEM=1: forced, 0: never)
         std::shared_ptr<DevVec> direct = l.w;
@@ -743,7 +754,7 @@ void Net::build_plan() {
         l.wino_w->as_half = true;
         if (stem_mode >= 1 && (force_variant < 0 || is_wino_variant(force_variant))) use_wino(l, kStemHalf);
       }
-      if (rowtap && stem_mode != 0 && op.wls.empty() && dtype == 0 && C <= 4 && stem_ws_eligible(g)) {
+      if (rowtap && stem_mode != 0 && op.wls.empty() && dtype == kElemF32 && C <= 4 && stem_ws_eligible(g)) {
         // float32 stem on the streaming skeleton (stream1x1_f32.hip, "ws7x7f"): the row-tap image's 224 columns + 32 of zeros in the order of
         // its 16x16x4 matrix steps; scale / shift are the launch's own.  The per-shape timing decides (DC_STEM=1: forced, 0: never)
         std::shared_ptr<DevVec> direct = l.w;
@@ -806,6 +817,7 @@ void Net::build_plan() {
           ConvGemmParams& g = rec.g;
           g = ConvGemmParams{};
           g.esize = es;
+          g.ekind = dtype;
           g.x_img_stride = (long)H * W * CP;
           g.x_row_stride = W * CP;
           g.x_rows = H;
@@ -884,9 +896,8 @@ void Net::build_plan() {
         affine_vecs(op, l, OC);
         // a multi-class tile must exist among the candidates of this K granularity (or be the forced one)
         bool have_mc = false;
-        for (int v = 0; v < conv_num_variants(); ++v)
-          if (CP % conv_variant_bk(v) == 0 && conv_variant_esize(v) == es && conv_variant_multiclass(v) &&
-              (force_variant < 0 || force_variant == v))
+        for (int ci = 0; ci < ncand; ++ci)
+          if (CP % conv_variant_bk(cand[ci]) == 0 && conv_variant_multiclass(cand[ci]) && (force_variant < 0 || force_variant == cand[ci]))
             have_mc = true;
         if (have_mc) {
           std::string key = wkey + ":mc";
@@ -895,7 +906,8 @@ void Net::build_plan() {
             h.assign((size_t)woff, 0.f);
             for (size_t q = 0; q < recs.size(); ++q) fill_class(recs[q], h.data() + l.cg.cls[q].w_off);
           });
-          l.w->as_half = dtype == 1;
+          l.w->as_half = dtype == kElemF16;
+          l.w->as_bf16 = dtype == kElemBF16;
           half_row_scale(l, op, OC);
           choose_variant(l, CP);
           push_split(std::move(l), CP);
@@ -915,7 +927,8 @@ void Net::build_plan() {
             fill_class(rec, h.data());
           });
           l.flops = 2.0 * rec.g.M * (double)OC * C * rec.g.nty * rec.g.ntx;
-          l.w->as_half = dtype == 1;
+          l.w->as_half = dtype == kElemF16;
+          l.w->as_bf16 = dtype == kElemBF16;
           half_row_scale(l, op, OC);
           choose_variant(l, CP);
           plan.push_back(std::move(l));

@@ -27,7 +27,7 @@ void Net::upload_vecs() {
   for (DevVec* vq : todo) {
     DevVec& v = *vq;
     if (!v.dev && !v.host.empty()) {
-      if (v.as_half) {  // filter image of an fp16 net: upload as float, convert on the device, keep the half copy
+      if (v.as_half || v.as_bf16) {  // filter image of an fp16 / bf16 net: upload as float, convert on the device, keep the 16-bit copy
         float* tmp = nullptr;
         dev_alloc((void**)&tmp, v.host.size() * sizeof(float));
         struct TmpGuard {
@@ -36,7 +36,7 @@ void Net::upload_vecs() {
         } tmp_guard{tmp};
         dev_upload(tmp, v.host.data(), v.host.size() * sizeof(float), stream);
         dev_alloc((void**)&v.dev, v.host.size() * 2);
-        KCHECK(launch_f32_to_f16(tmp, v.dev, (long)v.host.size(), stream));
+        KCHECK(v.as_bf16 ? launch_f32_to_bf16(tmp, v.dev, (long)v.host.size(), stream) : launch_f32_to_f16(tmp, v.dev, (long)v.host.size(), stream));
         HIPCHECK(hipStreamSynchronize((hipStream_t)stream));
       } else {
         dev_alloc((void**)&v.dev, v.host.size() * sizeof(float));
@@ -182,15 +182,15 @@ void Net::run_launch(const Launch& l, void* s) {
       break;
     }
     case Launch::POOL:
-      KCHECK(launch_maxpool(X.dev, Y.dev, X.esize, X.dim(0), X.dim(2), X.dim(3), X.cp(), Y.dim(2), Y.dim(3), l.pk, l.ps, l.pp, s));
+      KCHECK(launch_maxpool(X.dev, Y.dev, X.ekind, X.dim(0), X.dim(2), X.dim(3), X.cp(), Y.dim(2), Y.dim(3), l.pk, l.ps, l.pp, s));
       break;
     case Launch::ELT:
       KCHECK(launch_eltwise(X.dev, l.in2 >= 0 ? storages[l.in2]->dev : nullptr, l.scale ? l.scale->dev : nullptr,
-                            l.shift ? l.shift->dev : nullptr, Y.dev, Y.esize, (long)Y.dev_count(), Y.cp(), l.relu,
+                            l.shift ? l.shift->dev : nullptr, Y.dev, Y.ekind, (long)Y.dev_count(), Y.cp(), l.relu,
                             l.sigmoid, s));
       break;
     case Launch::CROP:
-      KCHECK(launch_crop(X.dev, Y.dev, X.esize, X.dim(0), X.dim(2), X.dim(3), X.cp(), l.oh, l.ow, Y.dim(2), Y.dim(3), s));
+      KCHECK(launch_crop(X.dev, Y.dev, X.ekind, X.dim(0), X.dim(2), X.dim(3), X.cp(), l.oh, l.ow, Y.dim(2), Y.dim(3), s));
       break;
   }
 }
@@ -342,15 +342,15 @@ void Net::enqueue_plan(void* s) {
   for (int v : plan_views_) storages[v]->head = HEAD_AT_GPU;
 }
 
-// Copy the three output maps out as NCHW (host or device destination), enqueued on s: float32, or — dst_esize 2, fp16
-// nets only — the half values as they are in HBM (half the gather payload).
+// Copy the three output maps out as NCHW (host or device destination), enqueued on s: float32, or — dst_esize 2, fp16 and bf16
+// nets only — the 16-bit values as they are in HBM (half the gather payload).
 void Net::emit_maps(void* prob, void* loc, void* next, bool is_device, void* s, int dst_esize) {
   struct Out {
     const char* name;
     void* dst;
   } outs[3] = {{"prob", prob}, {"loc_pred", loc}, {"next_pred", next}};
-  if (dst_esize != 4 && !(dst_esize == 2 && dtype == 1))
-    throw DcError(DC_EINVAL, "maps are emitted as float32, or as float16 from a float16 net (DC_OPT_DTYPE 1)");
+  if (dst_esize != 4 && !(dst_esize == 2 && dtype != kElemF32))
+    throw DcError(DC_EINVAL, "maps are emitted as float32, or as the net's own 16-bit values from a float16 / bfloat16 net (DC_OPT_DTYPE 1 / 2)");
   for (auto& o : outs) {
     if (!o.dst) continue;
     auto it = blob_index.find(o.name);
@@ -358,15 +358,15 @@ void Net::emit_maps(void* prob, void* loc, void* next, bool is_device, void* s, 
     Storage& st = *blobs[it->second]->st;
     size_t m = st.count();
     const void* src = st.view_of >= 0 ? storages[st.view_of]->dev : st.dev;
-    const int ses = st.view_of >= 0 ? storages[st.view_of]->esize : st.esize;
+    const int sek = st.view_of >= 0 ? storages[st.view_of]->ekind : st.ekind;
     const int scp = st.view_of >= 0 ? storages[st.view_of]->cp() : st.cp();
     const int sc0 = st.view_of >= 0 ? st.view_c0 : 0;
     if (st.head == UNINITIALIZED) throw DcError(DC_EINVAL, std::string("'") + o.name + "': run a forward first");
     if (is_device) {
-      KCHECK(launch_nhwc_to_nchw(src, o.dst, ses, st.dim(0), st.dim(1), st.dim(2), st.dim(3), scp, sc0, s, dst_esize));
+      KCHECK(launch_nhwc_to_nchw(src, o.dst, sek, st.dim(0), st.dim(1), st.dim(2), st.dim(3), scp, sc0, s, dst_esize));
     } else {
       st.ensure_stage(m);  // sized in floats: large enough for either element type
-      KCHECK(launch_nhwc_to_nchw(src, st.stage, ses, st.dim(0), st.dim(1), st.dim(2), st.dim(3), scp, sc0, s, dst_esize));
+      KCHECK(launch_nhwc_to_nchw(src, st.stage, sek, st.dim(0), st.dim(1), st.dim(2), st.dim(3), scp, sc0, s, dst_esize));
       HIPCHECK(hipMemcpyAsync(o.dst, st.stage, m * (size_t)dst_esize, hipMemcpyDeviceToHost, (hipStream_t)s));
     }
   }
@@ -374,7 +374,7 @@ void Net::emit_maps(void* prob, void* loc, void* next, bool is_device, void* s, 
 
 void Net::emit_last_maps(void* prob, void* loc, void* next, int elem, bool is_device, void* user_stream) {
   if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "emit_maps() in CPU mode");
-  if (elem != 0 && elem != 1) throw DcError(DC_EINVAL, "element type must be 0 (float32) or 1 (float16)");
+  if (elem != 0 && elem != 1) throw DcError(DC_EINVAL, "element type must be 0 (float32) or 1 (the net's 16-bit type)");
   ensure_device();
   const bool own_async = user_stream == (void*)-1;
   if (own_async) user_stream = nullptr;
@@ -393,11 +393,11 @@ void Net::forward_batch(const float* input, int n, int h, int w, bool is_device,
   void* s = user_stream ? user_stream : stream;
   size_t cnt = in.count();
   if (is_device) {
-    KCHECK(launch_nchw_to_nhwc(input, in.dev, in.esize, n, C, h, w, in.cp(), s));
+    KCHECK(launch_nchw_to_nhwc(input, in.dev, in.ekind, n, C, h, w, in.cp(), s));
   } else {
     in.ensure_stage(cnt);
     HIPCHECK(hipMemcpyAsync(in.stage, input, cnt * sizeof(float), hipMemcpyHostToDevice, (hipStream_t)s));
-    KCHECK(launch_nchw_to_nhwc(in.stage, in.dev, in.esize, n, C, h, w, in.cp(), s));
+    KCHECK(launch_nchw_to_nhwc(in.stage, in.dev, in.ekind, n, C, h, w, in.cp(), s));
   }
   in.head = HEAD_AT_GPU;
   enqueue_plan(s);
@@ -412,7 +412,7 @@ void Net::forward_host_images(const float* const* inputs, int n, int h, int w) {
   in.ensure_stage(img * n);
   for (int i = 0; i < n; ++i)
     HIPCHECK(hipMemcpyAsync(reinterpret_cast<float*>(in.stage) + i * img, inputs[i], img * sizeof(float), hipMemcpyHostToDevice, (hipStream_t)stream));
-  KCHECK(launch_nchw_to_nhwc(reinterpret_cast<const float*>(in.stage), in.dev, in.esize, n, C, h, w, in.cp(), stream));
+  KCHECK(launch_nchw_to_nhwc(reinterpret_cast<const float*>(in.stage), in.dev, in.ekind, n, C, h, w, in.cp(), stream));
   in.head = HEAD_AT_GPU;
   enqueue_plan(stream);
 }
@@ -428,7 +428,7 @@ void Net::forward_requests(int n, const float* const* inputs, int h, int w, floa
   if (own_async) user_stream = nullptr;
   void* s = user_stream ? user_stream : stream;
   const long img = (long)h * w * in.cp();
-  for (int i = 0; i < n; ++i) KCHECK(launch_nchw_to_nhwc(inputs[i], in.dev_at(i * img), in.esize, 1, C, h, w, in.cp(), s));
+  for (int i = 0; i < n; ++i) KCHECK(launch_nchw_to_nhwc(inputs[i], in.dev_at(i * img), in.ekind, 1, C, h, w, in.cp(), s));
   in.head = HEAD_AT_GPU;
   enqueue_plan(s);
   struct Out {
@@ -441,7 +441,7 @@ void Net::forward_requests(int n, const float* const* inputs, int h, int w, floa
     const long per = (long)m.H * m.W * m.cp;
     for (int i = 0; i < n; ++i)
       if (o.dst[i])
-        KCHECK(launch_nhwc_to_nchw((const unsigned char*)m.ptr + (size_t)i * per * m.es, o.dst[i], m.es, 1, m.C, m.H, m.W, m.cp, m.c0, s));
+        KCHECK(launch_nhwc_to_nchw((const unsigned char*)m.ptr + (size_t)i * per * m.es, o.dst[i], m.ek, 1, m.C, m.H, m.W, m.cp, m.c0, s));
   }
   if (!(user_stream || own_async)) HIPCHECK(hipStreamSynchronize((hipStream_t)s));
 }

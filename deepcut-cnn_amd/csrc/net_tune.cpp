@@ -21,10 +21,8 @@ void load_tune_cache_locked(ModelShared& shared) {
     const size_t sp = line.find_last_of(' ');
     if (sp != std::string::npos && sp > 0 && sp + 1 < line.size()) {
       const std::string key = line.substr(0, sp), vname = line.substr(sp + 1);
-      int v = -1;
-      v = wino_variant_by_name(vname.c_str());
-      for (int i = 0; v < 0 && i < conv_num_variants(); ++i)
-        if (vname == conv_variant(i).name) v = i;
+      int v = wino_variant_by_name(vname.c_str());
+      if (v < 0) v = conv_variant_by_name(vname.c_str());
       if (v >= 0 && !shared.tune_cache.count(key)) shared.tune_cache[key] = v;
     }
     line.clear();
@@ -56,7 +54,7 @@ void write_tune_cache_locked(ModelShared& shared) {
 
 void Net::autotune() {
   tuned = true;
-  if (env_int("DC_AUTOTUNE", 1) == 0 || env_int("DC_CONV_VARIANT", -1) >= 0) return;
+  if (env_int("DC_AUTOTUNE", 1) == 0 || env_int("DC_CONV_VARIANT", -1) >= 0 || (dtype == kElemBF16 && env_int("DC_CONV_VARIANT_BF16", -1) >= 0)) return;
   // DC_TUNE_CACHE=<file>: tuning results persist across processes ("signature variant-name" per line), so
   // a service (or a profiling run) starts without the timing launches
   std::lock_guard<std::mutex> tune_lock(shared->mu);  // one executor times a shape, the clones reuse its choices
@@ -99,8 +97,11 @@ void Net::autotune() {
     if (tune_cache_.count(key)) continue;
     timed_any = true;
     std::vector<std::pair<float, int>>& c = timed[key];
-    for (int v = 0; v < conv_num_variants(); ++v) {
-      if (g.klen % conv_variant_bk(v) != 0 || conv_variant_esize(v) != g.esize) continue;
+    int ncand = 0;
+    const int* cand = conv_variants_of(g.ekind, &ncand);
+    for (int ci = 0; ci < ncand; ++ci) {
+      const int v = cand[ci];
+      if (!tile_takes_k(v, g.klen, l.row_tap)) continue;
       if (g.ncls > 1 && !conv_variant_multiclass(v)) continue;
       Launch trial = l;
       trial.variant = v;
@@ -256,12 +257,10 @@ void Net::autotune() {
   // (3) the choices go into the plan
   for (auto& l : plan) {
     if (l.kind != Launch::CONV) continue;
-    const ConvGemmParams& g = l.cg;
     auto it = tune_cache_.find(key_of(l));
-    // a cache line naming the Winograd form while it is switched off (or not eligible any more): keep the cost model's tile
-    if (it != tune_cache_.end() && !(is_wino_variant(it->second) && !l.takes_wino(it->second)) &&
-        !(g.ncls > 1 && (is_wino_variant(it->second) || !conv_variant_multiclass(it->second))))
-      l.variant = it->second;
+    // a cache line naming the Winograd form while it is switched off (or not eligible any more), or a tile of another element kind
+    // (a hand-edited file shared by float16 and bfloat16 nets): keep the cost model's tile
+    if (it != tune_cache_.end() && l.takes_tile(it->second)) l.variant = it->second;
     if (is_wino_variant(l.variant)) {
       l.kernel = wino_kernel_label(l.variant);
       l.grid = wino_grid(l.cg);
@@ -276,7 +275,7 @@ void Net::autotune() {
   release_graph();
 }
 
-// GEMM signature of a launch: the key of the tile choice ("h" prefix: float16; "+w": the Winograd form competes for this layer —
+// GEMM signature of a launch: the key of the tile choice ("h" prefix: float16, "b": bfloat16; "+w": the Winograd form competes for this layer —
 // a different candidate set than with DC_WINOGRAD=0 —; "+mcN:K..": a multi-class launch, N classes with these K and M)
 std::string Net::tune_key(const Launch& l) const {
   const ConvGemmParams& g = l.cg;
@@ -286,7 +285,7 @@ std::string Net::tune_key(const Launch& l) const {
     mck = "+mc" + std::to_string(g.ncls);
     for (int c = 0; c < g.ncls; ++c) mck += ":" + std::to_string(g.cls[c].Ktot) + "m" + std::to_string(g.cls[c].M);
   }
-  std::snprintf(key, sizeof key, "%s%d/%d/%d/%d/%dx%d/%d,%d/%d/%d%s%s", g.esize == 2 ? "h" : "", g.M, g.Cout, g.Ktot, g.klen, g.nty, g.ntx,
+  std::snprintf(key, sizeof key, "%s%d/%d/%d/%d/%dx%d/%d,%d/%d/%d%s%s", g.ekind == kElemBF16 ? "b" : g.esize == 2 ? "h" : "", g.M, g.Cout, g.Ktot, g.klen, g.nty, g.ntx,
                 g.sy, g.sx, l.in2 >= 0 ? 1 : 0, g.OW, l.wino_w ? "+w" : "", mck.c_str());
   return key;
 }
@@ -326,16 +325,12 @@ std::string Net::tune_report_text() {
 // set_tile on each executor to change their current plans), and the captured graph is dropped.
 void Net::set_tile(const std::string& key, const std::string& tile) {
   int v = wino_variant_by_name(tile.c_str());
-  for (int i = 0; v < 0 && i < conv_num_variants(); ++i)
-    if (tile == conv_variant(i).name) v = i;
+  if (v < 0) v = conv_variant_by_name(tile.c_str());
   if (v < 0) throw DcError(DC_EINVAL, "no tile variant named '" + tile + "'");
   bool any = false;
   for (auto& l : plan) {
     if (l.kind != Launch::CONV || tune_key(l) != key) continue;
-    const ConvGemmParams& g = l.cg;
-    const bool ok = is_wino_variant(v) ? l.takes_wino(v)
-                                      : g.klen % conv_variant_bk(v) == 0 && conv_variant_esize(v) == g.esize && (g.ncls <= 1 || conv_variant_multiclass(v));
-    if (!ok) throw DcError(DC_EUNSUP, "tile '" + tile + "' cannot take launch '" + l.label + "' (" + key + ")");
+    if (!l.takes_tile(v)) throw DcError(DC_EUNSUP, "tile '" + tile + "' cannot take launch '" + l.label + "' (" + key + ")");
     any = true;
   }
   if (!any) throw DcError(DC_EINVAL, "the current plan has no launch with signature '" + key + "'");

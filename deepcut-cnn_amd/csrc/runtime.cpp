@@ -204,7 +204,7 @@ void storage_to_device_impl(Storage& s, void* stream, bool wait) {
   if (s.shape.size() == 4) {
     s.ensure_stage(n);
     HIPCHECK(hipMemcpyAsync(s.stage, s.host_ptr(), n * sizeof(float), hipMemcpyHostToDevice, (hipStream_t)stream));
-    KCHECK(launch_nchw_to_nhwc(s.stage, s.dev, s.esize, s.dim(0), s.dim(1), s.dim(2), s.dim(3), s.cp(), stream));
+    KCHECK(launch_nchw_to_nhwc(s.stage, s.dev, s.ekind, s.dim(0), s.dim(1), s.dim(2), s.dim(3), s.cp(), stream));
   } else {
     if (s.esize != 4) throw DcError(DC_EUNSUP, "only 4-D blobs have a half-precision device image");
     HIPCHECK(hipMemcpyAsync(s.dev, s.host_ptr(), n * sizeof(float), hipMemcpyHostToDevice, (hipStream_t)stream));
@@ -237,11 +237,11 @@ void storage_download_enqueue(Storage& s, void* stream, Storage* base) {
   float* h = s.host_ptr();
   if (base) {  // channel slice of a concatenated tensor
     s.ensure_stage(n);
-    KCHECK(launch_nhwc_to_nchw(base->dev, s.stage, base->esize, s.dim(0), s.dim(1), s.dim(2), s.dim(3), base->cp(), s.view_c0, stream));
+    KCHECK(launch_nhwc_to_nchw(base->dev, s.stage, base->ekind, s.dim(0), s.dim(1), s.dim(2), s.dim(3), base->cp(), s.view_c0, stream));
     HIPCHECK(hipMemcpyAsync(h, s.stage, n * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)stream));
   } else if (s.shape.size() == 4) {
     s.ensure_stage(n);
-    KCHECK(launch_nhwc_to_nchw(s.dev, s.stage, s.esize, s.dim(0), s.dim(1), s.dim(2), s.dim(3), s.cp(), 0, stream));
+    KCHECK(launch_nhwc_to_nchw(s.dev, s.stage, s.ekind, s.dim(0), s.dim(1), s.dim(2), s.dim(3), s.cp(), 0, stream));
     HIPCHECK(hipMemcpyAsync(h, s.stage, n * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)stream));
   } else {
     if (s.esize != 4) throw DcError(DC_EUNSUP, "only 4-D blobs have a half-precision device image");
@@ -265,9 +265,9 @@ void storage_copy(Storage& dst, Storage& src, Storage* src_base, void* stream) {
       if (dst.shape != src.shape) throw DcError(DC_ESHAPE, "device copy needs equal 4-D shapes");
       dst.ensure_stage(n);
       Storage& img = src_base ? *src_base : src;
-      KCHECK(launch_nhwc_to_nchw(img.dev, dst.stage, img.esize, src.dim(0), src.dim(1), src.dim(2), src.dim(3), img.cp(),
+      KCHECK(launch_nhwc_to_nchw(img.dev, dst.stage, img.ekind, src.dim(0), src.dim(1), src.dim(2), src.dim(3), img.cp(),
                                  src_base ? src.view_c0 : 0, stream));
-      KCHECK(launch_nchw_to_nhwc(dst.stage, dst.dev, dst.esize, dst.dim(0), dst.dim(1), dst.dim(2), dst.dim(3), dst.cp(), stream));
+      KCHECK(launch_nchw_to_nhwc(dst.stage, dst.dev, dst.ekind, dst.dim(0), dst.dim(1), dst.dim(2), dst.dim(3), dst.cp(), stream));
     } else if (src.shape.size() != 4 && dst.shape.size() != 4) {
       HIPCHECK(hipMemcpyAsync(dst.dev, src.dev, n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     } else {

@@ -201,7 +201,7 @@ void t_magic(unsigned dv, unsigned (&mg)[2]) {  // dc_magic of kernels.hip
 // the launch the lowering makes of the stem: 7 row-taps of one 64-element K segment over an image of CP = 4 or 8 channels per pixel
 // (at most 4 of them real: the caller's business), stride 2, pad 3
 bool stem7x7_eligible(const ConvGemmParams& p) {
-  if (p.esize != 2 || p.ncls > 1 || p.nprob > 0 || p.sigmoid_ch != 0 || p.resid) return false;
+  if (p.esize != 2 || p.ekind == kElemBF16 || p.ncls > 1 || p.nprob > 0 || p.sigmoid_ch != 0 || p.resid) return false;
   const int CP = p.sx / 2;
   if ((CP != 4 && CP != 8) || p.sx != 2 * CP || p.x0 != -3 * CP) return false;
   if (p.nty != 7 || p.ntx != 1 || p.klen != 64 || p.Ktot != 7 * 64 || p.dy0 != -3 || p.ddy != 1 || p.sy != 2) return false;

@@ -538,7 +538,7 @@ bool ws_tensor_ok(const void* x, const void* y, const void* resid, long M, long 
 }  // namespace
 
 bool stream1x1_eligible(const ConvGemmParams& p) {
-  if (p.esize != 2 || p.ncls > 1 || p.nprob > 0 || p.nty != 1 || p.ntx != 1 || p.dy0 != 0 || p.x0 != 0 || p.sy != 1 || p.sigmoid_ch != 0) return false;
+  if (p.esize != 2 || p.ekind == kElemBF16 || p.ncls > 1 || p.nprob > 0 || p.nty != 1 || p.ntx != 1 || p.dy0 != 0 || p.x0 != 0 || p.sy != 1 || p.sigmoid_ch != 0) return false;
   const WsForm* f = form_of(p.klen);
   if (!f || p.Ktot != p.klen || p.Cout % (f->NW * f->FN * 32) != 0) return false;
   // dense NHWC on both sides: output pixel m reads the klen halves at m * sx and is written at m * y_pix_stride

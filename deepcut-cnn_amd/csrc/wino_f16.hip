@@ -404,7 +404,7 @@ __global__ __launch_bounds__(HNTH, 1) void wino_h23_kernel(const ConvGemmParams 
 // ---- host side ------------------------------------------------------------------------------------------------------------
 bool wino_half_eligible(const ConvGemmParams& p) {
   const int d = p.ddy;  // dilation (1 or more), the same along x and y, with pad = dilation ("same" convolution)
-  if (p.esize != 2 || p.nty != 3 || p.ntx != 3 || p.sy != 1 || d < 1 || d > 4 || p.dy0 != -d) return false;
+  if (p.esize != 2 || p.ekind == kElemBF16 || p.nty != 3 || p.ntx != 3 || p.sy != 1 || d < 1 || d > 4 || p.dy0 != -d) return false;
   const int C = p.klen;
   if (C <= 0 || C % HKC != 0 || p.Cout % 64 != 0 || p.sigmoid_ch != 0 || p.ncls > 1) return false;
   if (p.sx != C || p.ddx != d * C || p.x0 != -d * C) return false;        // stride 1, dilation d, pad d along x

@@ -141,6 +141,8 @@ def _load():
         "dc_conv_variant_count": (ci, []),
         "dc_conv_variant_name": (cp, [ci]),
         "dc_conv_variant_esize": (ci, [ci]),
+        "dc_conv_bf16_variant_count": (ci, []),
+        "dc_conv_bf16_variant_name": (cp, [ci]),
         "dc_wino_half_pack": (ci, [C.c_void_p, ci, ci, ci, C.c_void_p, C.c_void_p]),
         "dc_stream1x1_pack": (ci, [C.c_void_p, ci, ci, C.c_void_p]),
         "dc_stem7x7_pack": (ci, [C.c_void_p, ci, C.c_void_p]),
@@ -177,9 +179,18 @@ def device_count():
     return _lib.dc_device_count()
 
 
+# Net(..., dtype=...) -> DC_OPT_DTYPE
+_DTYPES = {"f32": 0, "float32": 0, "f16": 1, "float16": 1, "bf16": 2, "bfloat16": 2}
+
+
 def conv_variants():
     """[(name, element size)] of the gather-GEMM tile variants, in DC_CONV_VARIANT index order (diagnostics)."""
     return [((_lib.dc_conv_variant_name(i) or b"").decode(), _lib.dc_conv_variant_esize(i)) for i in range(_lib.dc_conv_variant_count())]
+
+
+def conv_variants_bf16():
+    """[name] of the bfloat16 tile variants (their own table), in DC_CONV_VARIANT_BF16 index order."""
+    return [(_lib.dc_conv_bf16_variant_name(i) or b"").decode() for i in range(_lib.dc_conv_bf16_variant_count())]
 
 
 def stream1x1_pack(g):
@@ -397,7 +408,7 @@ class Net(object):
         if "hipgraph" in kw:
             self.set_option(2, int(kw["hipgraph"]))
         if "dtype" in kw:
-            self.set_option(3, {"f32": 0, "float32": 0, "f16": 1, "float16": 1}[kw["dtype"]])
+            self.set_option(3, _DTYPES[kw["dtype"]])
         self._blobs = None
         self._params = None
         if kw.get("want") is not None:
@@ -435,8 +446,8 @@ class Net(object):
 
     @property
     def dtype(self):
-        """'f32' or 'f16': the element type of activations and filters in HBM (DC_OPT_DTYPE)."""
-        return "f16" if self.get_option(3) == 1 else "f32"
+        """'f32', 'f16' or 'bf16': the element type of activations and filters in HBM (DC_OPT_DTYPE)."""
+        return {1: "f16", 2: "bf16"}.get(self.get_option(3), "f32")
 
     # --- pycaffe.py:22-59 -----------------------------------------------------------------
     @property
@@ -692,8 +703,8 @@ class Net(object):
                                           C.c_void_p(stream or 0)))
 
     def emit_maps_device(self, prob_ptr=None, loc_ptr=None, next_ptr=None, half=False, stream=None):
-        """Copy the maps of the last forward into device buffers as NCHW float32, or (half=True, fp16 nets) float16 —
-        the gather payload in the net's own element type.  Asynchronous on `stream` ("own" = the net's)."""
+        """Copy the maps of the last forward into device buffers as NCHW float32, or (half=True, fp16 / bf16 nets) the net's
+        16-bit values as they are (float16 / bfloat16) — the gather payload in the net's own element type.  Asynchronous on `stream` ("own" = the net's)."""
         if stream == "own":
             stream = C.c_void_p(-1).value
         _check(_lib.dc_net_emit_maps(self._h, C.c_void_p(prob_ptr or 0), C.c_void_p(loc_ptr or 0), C.c_void_p(next_ptr or 0),

@@ -51,7 +51,11 @@ extern "C" {
 #define DC_OPT_HIPGRAPH 2   /* 1: replay the per-shape launch sequence as a hipGraph        */
 #define DC_OPT_DTYPE 3      /* 0 (default): float32 activations and filters in HBM, v_mfma_f32_32x32x2_f32;
                                1: float16 activations and filters, v_mfma_f32_32x32x16_f16 with float32
-                               accumulation and epilogue (BASELINE configs[2]); host blobs stay float32 */
+                               accumulation and epilogue (BASELINE configs[2]);
+                               2: bfloat16 activations and filters (float32's exponent range: no overflow where
+                               float32 has none), v_mfma_f32_32x32x16_bf16 with float32 accumulation and epilogue,
+                               the direct gather-GEMM tiles only (no Winograd / streaming / stem forms);
+                               host blobs stay float32 */
 
 #define DC_OPT_OUTPUTS 4    /* bit i set = the i-th output blob of the net (dc_net_num_outputs order: alphabetical, net.cpp:268-273) is wanted;
                                default -1 = all.  The lowering drops every launch that only feeds unwanted outputs (the demo reads `prob`
@@ -150,7 +154,9 @@ int dc_blob_mutable_cpu_data(dc_blob* b, float** out);
 /* SyncedMemory::head() (syncedmem.hpp:59): 0 UNINITIALIZED 1 HEAD_AT_CPU 2 HEAD_AT_GPU 3 SYNCED */
 int dc_blob_head(dc_blob* b);
 /* Blob::gpu_data (blob.cpp:88-92): device pointer of the channels-last (NHWC) image of the
- * blob, plus its channel pitch (>= channels; the 3-channel input is stored with pitch 4). */
+ * blob, plus its channel pitch (>= channels; the 3-channel input is stored with pitch 4).
+ * Its elements are the net's DC_OPT_DTYPE: float32, float16, or on a bf16 net (2) the bfloat16
+ * values as they are in HBM (pitch rounded to 8 elements like float16's).  Same for the mutable form. */
 int dc_blob_gpu_data(dc_blob* b, const void** dev_ptr, int* channel_pitch);
 
 /* Blob<float>() / Blob<float>(shape) (blob.hpp:26-33): a blob of its own, owned by the caller — the bottoms and tops a
@@ -218,7 +224,8 @@ int dc_net_forward_requests(dc_net* net, int n, const float* const* inputs, int 
                             float* const* loc_pred, float* const* next_pred, void* stream);
 
 /* The maps of the LAST forward copied out as NCHW, host or device destination, any pointer NULL to skip: elem 0 =
- * float32; elem 1 = float16, offered by fp16 nets (DC_OPT_DTYPE 1) only — the values as they are in HBM, i.e. half the
+ * float32; elem 1 = the net's 16-bit element type, offered by fp16 and bf16 nets (DC_OPT_DTYPE 1 / 2) only, refused on a
+ * float32 net — float16 or bfloat16 values as they are in HBM, i.e. half the
  * bytes for the gather of the maps to rank 0 (no reference counterpart; Blob::cpu_data of the three outputs).
  * stream as dc_net_forward_batch.                                                                             */
 int dc_net_emit_maps(dc_net* net, void* prob, void* loc_pred, void* next_pred, int elem, int is_device, void* stream);
@@ -313,6 +320,10 @@ int dc_net_set_tile(dc_net* net, const char* signature, const char* tile);
 int dc_conv_variant_count(void);
 const char* dc_conv_variant_name(int i);
 int dc_conv_variant_esize(int i);
+/* the bfloat16 tiles (DC_OPT_DTYPE 2), a table of their own: names for dc_net_set_tile / tune caches, index i = what
+ * DC_CONV_VARIANT_BF16=i forces on bf16 nets                                                                            */
+int dc_conv_bf16_variant_count(void);
+const char* dc_conv_bf16_variant_name(int i);
 /* the float16 Winograd form's filter image (csrc/wino_f16.hip, tile `wino_h23`), made on the host exactly as the lowering makes it:
  * g = [cout][cin][3][3] (Caffe order, convolution_param of a stride-1 3x3 layer; cin % 16 == 0, cout % 32 == 0) -> out[16 * cout * cin]
  * = U = G g G^T per (co, ci) in double, channel co multiplied by row_scale[co]^-1 — an exact power of two bringing its largest |U|
