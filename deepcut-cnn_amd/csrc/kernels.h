@@ -3,6 +3,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <string>
 
 namespace dc {
 
@@ -111,7 +112,7 @@ struct ConvGemmParams {
   long long* dbg;  // optional [grid][4 waves][6] device timestamps (DC_DEBUG_TIMING), else null
   // --- multi-class launches (the stride-2 deconvolution heads): ncls > 1 and cls[0..ncls) replace the single-problem
   //     fields nty..x_bias / Ktot / OH / OW / M above; sy, sx, klen, strides, Cout, epilogue are common to all classes
-  // --- Winograd launches (filled by launch_wino_conv): tile-grid geometry and the magic numbers of its divisions
+  // --- Winograd launches (filled by the wino_f23 launch): tile-grid geometry and the magic numbers of its divisions
   int w_TY, w_TX, w_NBY, w_NBX, w_nblk;
   unsigned w_div_nblk[2], w_div_nbyx[2], w_div_dd[2], w_div_d[2], w_div_nbx[2];
   int wide_epi;  // (filled by launch_conv_gemm) float16: 16-byte epilogue through LDS — Cout and the output strides are multiples of 8
@@ -169,31 +170,16 @@ long prepare_conv_multi(ConvGemmParams& p, ConvMultiTable& table, int nprob, int
 bool conv_variant_multiproblem(int i);
 int launch_conv_multi(const ConvMultiArgs& a, int variant, long grid, void* stream);
 
-// ---- Winograd F(2x2, 3x3) for the stride-1, dilation-1, pad-1 3x3 convolutions (float32) -------------------------
+// ---- Winograd F(2x2, 3x3) for the stride-1 3x3 convolutions of dilation d = pad (float32) --------------------------------
 // Same ConvGemmParams as the gather-GEMM (x/y/resid/scale/shift/relu, NB, OH, OW, Cout, strides; klen = input channels,
-// x_rows = H, x_rowlen = W*klen); `w` is the transformed-filter image made by wino_pack_filters().
-constexpr int kWinoVariant = 1000;             // Launch::variant value that selects this kernel: 8 waves per workgroup ("wino_f23")
-constexpr int kWinoVariant16 = 1001;           // ... its 16-wave form ("wino_f23_w16": launches of at most one workgroup per CU, kernels.hip)
-constexpr int kWinoHalf = 1002;                // the float16 kernel (wino_f16.hip, "wino_h23"): fp16 operands, fp32 accumulate
-constexpr int kStreamHalf = 1003;              // NOT Winograd: the float16 streaming form of the dense 1x1 layers (stream1x1.hip, "ws1x1") — listed
-                                               // here because it is handled like one everywhere: a form outside the tile table with a filter
-                                               // image of its own (Launch::wino_w), timed against the tiles per shape
-constexpr int kStemHalf = 1004;                // NOT Winograd either: the float16 7x7 / stride-2 stem as a kernel of its own (stem_f16.hip, "stem7x7")
-constexpr int kStreamFloat = 1005;             // ... and the float32 form of the streaming 1x1 kernel (stream1x1_f32.hip, "ws1x1f")
-constexpr int kStemFloat = 1006;               // ... and the float32 7x7 / stride-2 stem on that kernel's skeleton (stream1x1_f32.hip, "ws7x7f")
-inline bool is_wino_variant(int v) { return v == kWinoVariant || v == kWinoVariant16 || v == kWinoHalf || v == kStreamHalf || v == kStemHalf || v == kStreamFloat || v == kStemFloat; }
-inline int wino_variant_esize(int v) { return v == kWinoHalf || v == kStreamHalf || v == kStemHalf ? 2 : 4; }  // element size of the nets the form serves
-inline int wino_variant_ekind(int v) { return wino_variant_esize(v) == 2 ? kElemF16 : kElemF32; }  // ... and their kind (no form serves bfloat16)
-const char* wino_variant_name(int variant);    // the tile name of tune caches / reports / set_tile
-const char* wino_kernel_label(int variant);    // the kernel column of plan texts
-int wino_variant_by_name(const char* name);    // -1: not a Winograd tile name
+// x_rows = H, x_rowlen = W*klen); `w` is the transformed-filter image made by wino_pack_filters().  Launched as the forms
+// wino_f23 and wino_f23_w16 (conv_form below).
 bool wino_eligible(const ConvGemmParams& p);   // geometry / type the kernel takes
 long wino_grid(const ConvGemmParams& p);
 size_t wino_packed_floats(int Cout, int Cin);
 // g: [Cout][Cin][3][3] (Caffe order) -> U = G g G^T per (co, ci), laid out so that one wave's B-operand load is 1 KB
 // contiguous: [Cout/16][4 i][Cin/16][4 j][64 lanes][4]
 void wino_pack_filters(const float* g, int Cout, int Cin, float* out);
-int launch_wino_conv(const ConvGemmParams& p, void* stream, int variant = kWinoVariant);
 // ---- the same for a float16 net (wino_f16.hip): `w` is the image made by wino_half_pack_filters() uploaded as _Float16, `scale`
 // must carry the extra factors 4 (the staged pixels are pre-multiplied by 1/4) and row_scale[co]; no shortcut operand
 bool wino_half_eligible(const ConvGemmParams& p);
@@ -229,9 +215,45 @@ long stem7x7_grid(const ConvGemmParams& p);
 size_t stem7x7_packed_elems();
 void stem7x7_pack_filters(const float* g, int C, float* out);  // g: [64][C][7][7], C <= 4
 int launch_stem7x7(const ConvGemmParams& p, void* stream);
-// multi-problem (NetGroup): prepare_conv_multi / launch_conv_multi take kStreamHalf as a variant and end here; p.w must be the packed image
+// multi-problem (NetGroup): prepare_conv_multi / launch_conv_multi end here for the ws1x1 form; p.w must be the packed image
 long stream1x1_prepare_multi(const ConvGemmParams& p, const ConvMultiTable& tb, int nprob);  // the grid, or -1
 int launch_stream1x1_multi(const ConvMultiArgs& a, void* stream);                              // a.p.nprob, a.t as filled by the caller
+
+// ---- FORMS: the convolution kernels outside the tile tables.  A form has a filter image of its own (Launch::form_w) and is timed against
+// the tiles per shape.  Its variant number travels in Launch::variant and tune caches like a tile's, and DC_CONV_VARIANT takes it.
+constexpr int kWinoVariant = 1000;    // "wino_f23": Winograd F(2x2, 3x3), float32, 8 waves per workgroup (kernels.hip)
+constexpr int kWinoVariant16 = 1001;  // "wino_f23_w16": its 16-wave form (launches of at most one workgroup per CU)
+constexpr int kWinoHalf = 1002;       // "wino_h23": the float16 Winograd kernel (wino_f16.hip): fp16 operands, fp32 accumulate
+constexpr int kStreamHalf = 1003;     // "ws1x1": the float16 streaming form of the dense 1x1 layers (stream1x1.hip)
+constexpr int kStemHalf = 1004;       // "stem7x7": the float16 7x7 / stride-2 stem (stem_f16.hip)
+constexpr int kStreamFloat = 1005;    // "ws1x1f": the float32 streaming 1x1 form (stream1x1_f32.hip)
+constexpr int kStemFloat = 1006;      // "ws7x7f": the float32 stem on that kernel's skeleton (stream1x1_f32.hip)
+constexpr int kFormVariant0 = kWinoVariant, kNumForms = 7;
+enum FormGeometry { kForm3x3, kForm1x1, kFormStem };  // the layers a form takes: 3x3, dense 1x1, the 7-row-tap stem
+struct ConvForm {
+  int variant;
+  const char *name, *label;  // in tune caches, reports and set_tile; in the kernel column of plan texts
+  int ekind, geometry, waves;  // the element kind of the nets it serves, FormGeometry, waves per workgroup
+  const char* const* timing_slots;  // DC_DEBUG_TIMING: the names of its phase slots 1..7
+  bool (*eligible)(const ConvGemmParams& p);
+  long (*grid)(const ConvGemmParams& p);
+  int (*launch)(const ConvGemmParams& p, void* stream);
+  bool own_scale;      // runs on an epilogue scale of its own (Launch::form_scale) and takes no shortcut operand
+  bool merges;         // a NetGroup merges a member on it as the direct layer it also is; else the member runs apart
+  // a multi-problem candidate of NetGroup launches (on the members' shared image), else null
+  long (*prepare_multi)(const ConvGemmParams& p, const ConvMultiTable& tb, int nprob);
+  int (*launch_multi)(const ConvMultiArgs& a, void* stream);
+  int sibling;         // the form on the same image that autotuning compares it with in whole passes, else -1
+  const char* env;     // its switch: unset or -1 where measured faster, 0 never, >= 1 wherever eligible
+};
+const ConvForm* conv_form(int variant);  // null: not a form (a tile)
+
+// ---- any variant, tile or form
+const char* variant_name(int v);
+int variant_by_name(const char* name);  // -1: no tile or form of that name
+std::string variant_kernel_label(int v);  // the kernel column of plan texts
+long variant_grid(const ConvGemmParams& p, int v);
+int launch_conv(const ConvGemmParams& p, int v, void* stream);  // returns hipError_t as int
 
 // The remaining kernels take `ekind` = the ElemKind of the device images (float / _Float16 / __bf16); host-side tensors
 // and the per-channel affine vectors are always float.

@@ -1306,15 +1306,11 @@ bool dc_variant_ok(int v) { return (v >= 0 && v < kNumVariants) || (v >= kBf16Va
 
 int conv_num_variants() { return kNumVariants; }
 int conv_num_bf16_variants() { return kNumBf16Variants; }
-// (kStreamHalf — stream1x1.hip — answers these like a table entry: the group code handles it as one more multi-problem tile)
-const ConvVariant& conv_variant(int i) {
-  static const ConvVariant kStream = {"ws1x1", 32, 256, 1, 8, 1};
-  return i == kStreamHalf ? kStream : entry_of(i).v;
-}
-int conv_variant_bk(int i) { return i == kStreamHalf ? 64 : entry_of(i).BK; }
-int conv_variant_esize(int i) { return i == kStreamHalf ? 2 : entry_of(i).esize; }
+const ConvVariant& conv_variant(int i) { return entry_of(i).v; }
+int conv_variant_bk(int i) { return entry_of(i).BK; }
+int conv_variant_esize(int i) { return entry_of(i).esize; }
 int conv_variant_ekind(int i) { return is_bf16_variant(i) ? kElemBF16 : conv_variant_esize(i) == 2 ? kElemF16 : kElemF32; }
-bool conv_variant_multiclass(int i) { return i == kStreamHalf ? false : entry_of(i).kernel_mc != nullptr; }
+bool conv_variant_multiclass(int i) { return entry_of(i).kernel_mc != nullptr; }
 const int* conv_variants_of(int ekind, int* count) {
   static const std::vector<int>* lists = [] {
     auto* l = new std::vector<int>[3];
@@ -1490,12 +1486,12 @@ int launch_conv_gemm(const ConvGemmParams& p_in, int variant, void* stream) {
   return (int)hipGetLastError();
 }
 
-bool conv_variant_multiproblem(int i) { return i == kStreamHalf ? true : entry_of(i).kernel_mp != nullptr; }
+bool conv_variant_multiproblem(int i) { return entry_of(i).kernel_mp != nullptr; }
 
 // Multi-problem launch: host-side preparation (once per plan), see kernels.h.
 long prepare_conv_multi(ConvGemmParams& p, ConvMultiTable& tb, int nprob, int variant) {
-  if (variant == kStreamHalf) {
-    const long g = stream1x1_prepare_multi(p, tb, nprob);
+  if (const ConvForm* f = conv_form(variant)) {
+    const long g = f->prepare_multi ? f->prepare_multi(p, tb, nprob) : -1;
     if (g > 0) p.nprob = nprob, p.ncls = 0;
     return g;
   }
@@ -1593,7 +1589,7 @@ long prepare_conv_multi(ConvGemmParams& p, ConvMultiTable& tb, int nprob, int va
 }
 
 int launch_conv_multi(const ConvMultiArgs& a, int variant, long grid, void* stream) {
-  if (variant == kStreamHalf) return launch_stream1x1_multi(a, stream);
+  if (const ConvForm* f = conv_form(variant)) return f->launch_multi ? f->launch_multi(a, stream) : (int)hipErrorInvalidValue;
   if (!dc_variant_ok(variant) || !entry_of(variant).kernel_mp || a.p.nprob < 1 || grid <= 0) return (int)hipErrorInvalidValue;
   const VariantEntry& e = entry_of(variant);
   const int nt = e.v.WR * e.v.WC * e.v.WK * 64;
@@ -1876,8 +1872,6 @@ __global__ __launch_bounds__(WNTH * NG, 4) void wino_f23_kernel(const ConvGemmPa
 }
 
 bool wino_eligible(const ConvGemmParams& p) {
-  if (p.ekind == kElemBF16) return false;          // no Winograd form for bfloat16
-  if (p.esize == 2) return wino_half_eligible(p);  // the float16 kernel (wino_f16.hip)
   const int d = p.ddy;  // dilation (1 or more), the same along x and y, with pad = dilation ("same" convolution)
   if (p.esize != 4 || p.nty != 3 || p.ntx != 3 || p.sy != 1 || d < 1 || d > 4 || p.dy0 != -d) return false;
   const int C = p.klen;
@@ -1891,11 +1885,6 @@ bool wino_eligible(const ConvGemmParams& p) {
 }
 
 long wino_grid(const ConvGemmParams& p) {
-  if (p.esize == 2 && p.nty == 1 && p.ntx == 1) return stream1x1_grid(p);  // (a 1x1 layer on a form of its own: the streaming one)
-  if (p.esize == 4 && p.nty == 1 && p.ntx == 1) return stream1x1f_grid(p);
-  if (p.esize == 2 && p.nty == 7 && p.ntx == 1) return stem7x7_grid(p);    // (the stem)
-  if (p.esize == 4 && p.nty == 7 && p.ntx == 1) return stem_ws_grid(p);
-  if (p.esize == 2) return wino_half_grid(p);
   const int d = p.ddy;
   const int TY = ((p.OH + d - 1) / d + 1) / 2, TX = ((p.OW + d - 1) / d + 1) / 2;
   return (long)p.NB * d * d * ((TY + WBTY - 1) / WBTY) * ((TX + WBTX - 1) / WBTX) * (p.Cout / WBN);
@@ -1921,25 +1910,10 @@ void wino_pack_filters(const float* g, int Cout, int Cin, float* out) {
     }
 }
 
-const char* wino_variant_name(int variant) {
-  return variant == kStemFloat ? "ws7x7f" : variant == kStreamFloat ? "ws1x1f" : variant == kStemHalf ? "stem7x7" : variant == kStreamHalf ? "ws1x1" : variant == kWinoHalf ? "wino_h23" : variant == kWinoVariant16 ? "wino_f23_w16" : "wino_f23";
-}
-const char* wino_kernel_label(int variant) {
-  return variant == kStemFloat ? "ws7x7f<16x64>" : variant == kStreamFloat ? "ws1x1f<16xN>" : variant == kStemHalf ? "stem7x7<8x64>" : variant == kStreamHalf ? "ws1x1<32xN>" : variant == kWinoHalf ? "wino_h23<2x4x8x64>" : variant == kWinoVariant16 ? "wino_f23<4x8x16_w16>" : "wino_f23<4x8x16>";
-}
-int wino_variant_by_name(const char* name) {
-  for (int v : {kWinoVariant, kWinoVariant16, kWinoHalf, kStreamHalf, kStemHalf, kStreamFloat, kStemFloat})
-    if (name && std::strcmp(name, wino_variant_name(v)) == 0) return v;
-  return -1;
-}
-
-int launch_wino_conv(const ConvGemmParams& p, void* stream, int variant) {
-  if (variant == kStreamHalf) return launch_stream1x1(p, stream);
-  if (variant == kStemHalf) return launch_stem7x7(p, stream);
-  if (variant == kStreamFloat) return launch_stream1x1f(p, stream);
-  if (variant == kStemFloat) return launch_stem_ws(p, stream);
-  if (variant == kWinoHalf) return launch_wino_half(p, stream);
-  if (p.esize != 4 || !wino_eligible(p) || !is_wino_variant(variant)) return (int)hipErrorInvalidValue;
+// NG = 1: wino_f23 (8 waves per workgroup), 2: wino_f23_w16 (16)
+template <int NG>
+static int launch_wino_f23(const ConvGemmParams& p, void* stream) {
+  if (p.esize != 4 || !wino_eligible(p)) return (int)hipErrorInvalidValue;
   const long grid = wino_grid(p);
   if (grid <= 0) return 0;
   if (grid > 0x7fffffffL) return (int)hipErrorInvalidValue;
@@ -1957,9 +1931,66 @@ int launch_wino_conv(const ConvGemmParams& p, void* stream, int variant) {
     dc_magic((unsigned)d, q.w_div_d);
     dc_magic((unsigned)q.w_NBX, q.w_div_nbx);
   }
-  if (variant == kWinoVariant16) hipLaunchKernelGGL(wino_f23_kernel<2>, dim3((unsigned)grid), dim3(2 * WNTH), 0, (hipStream_t)stream, q);
-  else hipLaunchKernelGGL(wino_f23_kernel<1>, dim3((unsigned)grid), dim3(WNTH), 0, (hipStream_t)stream, q);
+  hipLaunchKernelGGL(wino_f23_kernel<NG>, dim3((unsigned)grid), dim3(NG * WNTH), 0, (hipStream_t)stream, q);
   return (int)hipGetLastError();
+}
+
+// DC_DEBUG_TIMING phase slots 1..7 of the forms: the Winograd kernels' (stem7x7 reports under these names too) and the streaming ones'
+// (stream1x1.hip: 0 start, 1 every prologue request issued, 2 first stage + filters + constants landed, 3 the peeled first D steps done,
+// 4 the other steps (and the late half's last epilogue) done, 5 requests drained)
+static const char* const kWinoSlots[7] = {"index setup", "first loads issued", "two stages in LDS", "K loop", "partials to LDS + barrier",
+                                          "inverse transform + epilogue constants", "shortcut + stores"};
+static const char* const kStreamSlots[7] = {"prologue requests issued", "first stage + filters landed", "the first D steps", "the other steps",
+                                            "drain", "-", "exit"};
+static constexpr ConvForm kForms[kNumForms] = {
+    // variant, name, label, ekind, geometry, waves, slots, eligible, grid, launch, own_scale, merges, prepare_multi, launch_multi, sibling, env
+    {kWinoVariant, "wino_f23", "wino_f23<4x8x16>", kElemF32, kForm3x3, 8, kWinoSlots, wino_eligible, wino_grid, launch_wino_f23<1>,
+     false, false, nullptr, nullptr, kWinoVariant16, "DC_WINOGRAD"},
+    {kWinoVariant16, "wino_f23_w16", "wino_f23<4x8x16_w16>", kElemF32, kForm3x3, 16, kWinoSlots, wino_eligible, wino_grid, launch_wino_f23<2>,
+     false, false, nullptr, nullptr, kWinoVariant, "DC_WINOGRAD"},
+    {kWinoHalf, "wino_h23", "wino_h23<2x4x8x64>", kElemF16, kForm3x3, 8, kWinoSlots, wino_half_eligible, wino_half_grid, launch_wino_half,
+     true, true, nullptr, nullptr, -1, "DC_WINOGRAD"},
+    {kStreamHalf, "ws1x1", "ws1x1<32xN>", kElemF16, kForm1x1, 4, kStreamSlots, stream1x1_eligible, stream1x1_grid, launch_stream1x1,
+     false, true, stream1x1_prepare_multi, launch_stream1x1_multi, -1, "DC_STREAM1X1"},
+    {kStemHalf, "stem7x7", "stem7x7<8x64>", kElemF16, kFormStem, 4, kWinoSlots, stem7x7_eligible, stem7x7_grid, launch_stem7x7,
+     false, false, nullptr, nullptr, -1, "DC_STEM"},
+    {kStreamFloat, "ws1x1f", "ws1x1f<16xN>", kElemF32, kForm1x1, 4, kStreamSlots, stream1x1f_eligible, stream1x1f_grid, launch_stream1x1f,
+     false, true, nullptr, nullptr, -1, "DC_STREAM1X1"},
+    {kStemFloat, "ws7x7f", "ws7x7f<16x64>", kElemF32, kFormStem, 4, kStreamSlots, stem_ws_eligible, stem_ws_grid, launch_stem_ws,
+     false, true, nullptr, nullptr, -1, "DC_STEM"},
+};
+
+static constexpr bool forms_in_variant_order() {
+  for (int i = 0; i < kNumForms; ++i)
+    if (kForms[i].variant != kFormVariant0 + i) return false;
+  return true;
+}
+static_assert(forms_in_variant_order(), "row i of kForms is variant kFormVariant0 + i");
+
+const ConvForm* conv_form(int variant) {
+  return variant >= kFormVariant0 && variant < kFormVariant0 + kNumForms ? &kForms[variant - kFormVariant0] : nullptr;
+}
+
+const char* variant_name(int v) {
+  const ConvForm* f = conv_form(v);
+  return f ? f->name : conv_variant(v).name;
+}
+int variant_by_name(const char* name) {
+  for (const ConvForm& f : kForms)
+    if (std::strcmp(name, f.name) == 0) return f.variant;
+  return conv_variant_by_name(name);
+}
+std::string variant_kernel_label(int v) {
+  const ConvForm* f = conv_form(v);
+  return f ? std::string(f->label) : std::string("conv_gemm<") + conv_variant(v).name + ">";
+}
+long variant_grid(const ConvGemmParams& p, int v) {
+  const ConvForm* f = conv_form(v);
+  return f ? f->grid(p) : conv_grid(p, v);
+}
+int launch_conv(const ConvGemmParams& p, int v, void* stream) {
+  const ConvForm* f = conv_form(v);
+  return f ? f->launch(p, stream) : launch_conv_gemm(p, v, stream);
 }
 
 // the element type of an ElemKind: f(tag) with tag a null T* (float, _Float16 or __bf16)

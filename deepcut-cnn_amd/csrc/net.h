@@ -180,19 +180,21 @@ struct Launch {
   int variant = 0;
   bool row_tap = false;  // one tap per kernel row over several adjacent pixels (inputs narrower than a K tile): see tile_takes_k
   std::shared_ptr<DevVec> w, scale, shift;  // packed filters / folded affine (kept alive by the plan)
-  std::shared_ptr<DevVec> wino_w;           // Winograd-transformed filters (eligible 3x3 layers) / the fragment-order image of the streaming
-                                            // form (eligible float16 1x1 layers, stream1x1.hip), else null
-  std::shared_ptr<DevVec> wino_scale;       // float16 nets: the epilogue scale of the Winograd form (folded affine x the image's row scale x 4)
-  // a Winograd form this launch can run as: the image exists and the form serves the net's element type
-  bool takes_wino(int v) const {
-    return is_wino_variant(v) && (bool)wino_w && wino_variant_ekind(v) == cg.ekind && cg.ncls <= 1 && (v == kStreamHalf || v == kStreamFloat) == (cg.nty == 1 && cg.ntx == 1) &&
-           (v == kStemHalf || v == kStemFloat) == (cg.nty == 7 && cg.ntx == 1);
+  std::shared_ptr<DevVec> form_w;           // the filter image of the forms this launch can run on (kernels.h ConvForm): Winograd-transformed
+                                            // filters of a 3x3 layer, the image of a streaming 1x1 layer or of the stem; else null
+  std::shared_ptr<DevVec> form_scale;       // the epilogue scale of a form with its own (ConvForm::own_scale: folded affine x the image's row scale x 4)
+  // a form this launch can run on: the image exists, and the form serves the net's element type and takes the layer
+  bool takes_form(int v) const {
+    const ConvForm* f = conv_form(v);
+    return f && form_w && f->ekind == cg.ekind && cg.ncls <= 1 && (f->geometry == kForm1x1) == (cg.nty == 1 && cg.ntx == 1) &&
+           (f->geometry == kFormStem) == (cg.nty == 7 && cg.ntx == 1) && f->eligible(cg);
   }
   // a tile (or form) this launch can run on: the net's element kind, the launch's K segments and deconvolution classes
   bool takes_tile(int v) const {
-    if (is_wino_variant(v)) return takes_wino(v);
+    if (conv_form(v)) return takes_form(v);
     return conv_variant_exists(v) && conv_variant_ekind(v) == cg.ekind && tile_takes_k(v, cg.klen, row_tap) && (cg.ncls <= 1 || conv_variant_multiclass(v));
   }
+  void set_variant(int v) { variant = v, kernel = variant_kernel_label(v), grid = variant_grid(cg, v); }  // a tile or form, its label and grid
   long y_off = 0;                      // element offset of this launch's first output (deconvolution classes, channel splits)
   long w_off = 0;                      // element offset of this launch's first filter row inside `w` (channel splits)
   int c_off = 0;                       // first output channel of this launch inside scale / shift (channel splits)
@@ -366,8 +368,8 @@ struct Net {
 // the group is launch i of every member's plan merged into a multi-problem gather-GEMM (kernels.h ConvProblem) — the
 // residue classes of the deconvolution heads become problems too —, so a 4-scale pyramid is 161 launches (one lane) or 318 (the default two
 // concurrent lanes of two scales, GroupPlan::lane_members) instead of 632.
-// Members keep their blobs, plans and tile choices: a member can still be run alone.  Launches that cannot merge (Winograd
-// form, max-pool, stand-alone element-wise layers) run member by member inside the same sequence.
+// Members keep their blobs, plans and tile choices: a member can still be run alone.  Launches that cannot merge (a member on a
+// form that does not merge, max-pool, stand-alone element-wise layers) run member by member inside the same sequence.
 struct GroupLaunch {
   bool multi = false;
   int lane = 0;               // which lane of the plan runs it (GroupPlan::lane_members)
@@ -375,7 +377,8 @@ struct GroupLaunch {
   int member = -1;            // !multi: the member whose launch `index` this is
   ConvGemmParams p{};         // multi: the layer's common block (not yet prepared for a variant)
   bool row_tap = false;       // ... a row-tap layer (Launch::row_tap)
-  const void* ws_w = nullptr; // ... the layer's stream1x1 filter image if every member has one (variant kStreamHalf reads it instead of p.w)
+  int form = -1;              // ... the multi-problem form every member can run on (ConvForm::launch_multi), else -1,
+  const void* form_w = nullptr; // ... and the members' shared image of it (read instead of p.w on that form)
   ConvMultiTable table{};     // ... and the problems (pointers filled, not yet prepared)
   ConvMultiArgs args{};       // both, prepared for `variant`: the kernel arguments
   int nprob = 0;

@@ -145,26 +145,26 @@ void NetGroup::forget_plan(GroupPlan* gp) {
     }
 }
 
-// the kernel arguments of a merged launch for a tile (common block + problem table); returns the grid, <= 0 if the tile cannot take it
+// the kernel arguments of a merged launch for a tile or form (common block + problem table); returns the grid, <= 0 if it cannot take it
 static long group_args(const GroupLaunch& gl, int variant, ConvMultiArgs& a) {
   a.p = gl.p;
   a.t = gl.table;
-  if (variant == kStreamHalf) {
-    if (!gl.ws_w) return -1;
-    a.p.w = gl.ws_w;
+  if (conv_form(variant)) {
+    if (variant != gl.form) return -1;
+    a.p.w = gl.form_w;
   } else if (!conv_variant_exists(variant) || !tile_takes_k(variant, gl.p.klen, gl.row_tap)) {
     return -1;
   }
   return prepare_conv_multi(a.p, a.t, gl.nprob, variant);
 }
-// the tiles a merged launch can be timed on: every multi-problem tile of its K granularity and type, and the streaming form
+// the tiles a merged launch can be timed on: every multi-problem tile of its K granularity and type, and its multi-problem form
 static std::vector<int> group_candidates(const GroupLaunch& gl) {
   std::vector<int> c;
   int n = 0;
   const int* cand = conv_variants_of(gl.p.ekind, &n);
   for (int i = 0; i < n; ++i)
     if (conv_variant_multiproblem(cand[i]) && tile_takes_k(cand[i], gl.p.klen, gl.row_tap)) c.push_back(cand[i]);
-  if (gl.ws_w && env_int("DC_STREAM1X1", -1) != 0) c.push_back(kStreamHalf);
+  if (gl.form >= 0 && env_int(conv_form(gl.form)->env, -1) != 0) c.push_back(gl.form);
   return c;
 }
 
@@ -224,13 +224,13 @@ void NetGroup::merge(GroupPlan& gp) {
       const size_t c = (size_t)mem[cc];
       const Launch& l = nets[c]->plan[i];
       const ConvGemmParams &g = l.cg, &g0 = l0.cg;
-      // (a member on the float16 Winograd form merges as the direct layer it also is: the form is a one-round kernel that wins alone on
-      //  a 240-workgroup grid — round 6: with the 544x736 member's conv4_x 3x3 launches kept out of the merge, the four scales of that
-      //  layer ran as 17.8 + 31.2 + 17.0 + 14.3 us where the merged direct launch takes 60.5.  The float32 forms stay member by member.)
-      //  (The float32 streaming forms, round 6 — ws1x1f and the stem on its skeleton —, merge the same way: they win by a few per cent
-      //   on a member's own grid only.)
-      const bool wino_apart = is_wino_variant(l.variant) && l.variant != kWinoHalf && l.variant != kStreamHalf && l.variant != kStreamFloat && l.variant != kStemFloat;
-      if (l.kind != Launch::CONV || wino_apart || l.w != l0.w || l.scale != l0.scale || l.shift != l0.shift || l.c_off != l0.c_off ||
+      // (a member on a form merges as the direct layer it also is where ConvForm::merges says so — wino_h23, ws1x1, ws1x1f, ws7x7f —, and
+      //  keeps the launch apart on wino_f23, wino_f23_w16 and stem7x7.  wino_h23 is a one-round kernel that wins alone on a 240-workgroup
+      //  grid — round 6: with the 544x736 member's conv4_x 3x3 launches kept out of the merge, the four scales of that layer ran as 17.8 +
+      //  31.2 + 17.0 + 14.3 us where the merged direct launch takes 60.5 —; the float32 streaming forms win by a few per cent on a
+      //  member's own grid only.)
+      const ConvForm* form = conv_form(l.variant);
+      if (l.kind != Launch::CONV || (form && !form->merges) || l.w != l0.w || l.scale != l0.scale || l.shift != l0.shift || l.c_off != l0.c_off ||
           l.w_off != l0.w_off ||
           (l.in2 >= 0) != (l0.in2 >= 0) || g.esize != g0.esize || g.ekind != g0.ekind || g.klen != g0.klen || g.sy != g0.sy || g.sx != g0.sx || g.Cout != g0.Cout ||
           g.relu != g0.relu || g.sigmoid_ch != g0.sigmoid_ch)
@@ -325,10 +325,11 @@ void NetGroup::merge(GroupPlan& gp) {
       gl.p.dbg = nullptr;
       gl.p.x = nullptr, gl.p.y = nullptr, gl.p.resid = nullptr;
       gl.p.w = l0.w->dev;
-      {  // the streaming form of a dense float16 1x1 layer (stream1x1.hip) is a candidate if every member carries the (shared) image
-        bool all = l0.takes_wino(kStreamHalf) && l0.wino_w->dev;
-        for (int c : mem) all = all && nets[c]->plan[i].wino_w == l0.wino_w && nets[c]->plan[i].takes_wino(kStreamHalf);
-        gl.ws_w = all ? l0.wino_w->dev : nullptr;
+      // a multi-problem form (ws1x1) is a candidate if every member carries its (shared) image
+      for (int v = kFormVariant0; v < kFormVariant0 + kNumForms; ++v) {
+        bool all = conv_form(v)->launch_multi && l0.takes_form(v) && l0.form_w->dev;
+        for (int c : mem) all = all && nets[c]->plan[i].form_w == l0.form_w && nets[c]->plan[i].takes_form(v);
+        if (all) gl.form = v, gl.form_w = l0.form_w->dev;
       }
       gl.p.scale = l0.scale ? l0.scale->dev + l0.c_off : nullptr;
       gl.p.shift = l0.shift ? l0.shift->dev + l0.c_off : nullptr;
@@ -359,7 +360,7 @@ void NetGroup::merge(GroupPlan& gp) {
       if (forced >= 0 && conv_variant_exists(forced) && conv_variant_multiproblem(forced) && tile_takes_k(forced, gl.p.klen, gl.row_tap) &&
           conv_variant_ekind(forced) == gl.p.ekind)
         v = forced;
-      if (forced < 0 && gl.ws_w && env_int("DC_STREAM1X1", -1) >= 1) v = kStreamHalf;  // (forced on: wherever eligible, as in Net's lowering)
+      if (forced < 0 && gl.form >= 0 && env_int(conv_form(gl.form)->env, -1) >= 1) v = gl.form;  // (forced on: wherever eligible, as in Net's lowering)
       gl.variant = v;
     }
   }
@@ -367,7 +368,7 @@ void NetGroup::merge(GroupPlan& gp) {
     if (!gl.multi) continue;
     int v = gl.variant;
     auto usable = [&](int cand) {
-      if (cand != kStreamHalf && (!conv_variant_exists(cand) || is_wino_variant(cand))) return false;
+      if (!conv_form(cand) && !conv_variant_exists(cand)) return false;
       ConvMultiArgs a;
       return group_args(gl, cand, a) > 0;
     };
@@ -391,7 +392,7 @@ void NetGroup::merge(GroupPlan& gp) {
 void NetGroup::apply_variant(GroupPlan&, GroupLaunch& gl, int variant) {
   ConvMultiArgs a;
   const long grid = group_args(gl, variant, a);
-  if (grid <= 0) throw DcError(DC_EUNSUP, "group launch '" + gl.label + "': tile " + conv_variant(variant).name + " cannot take it");
+  if (grid <= 0) throw DcError(DC_EUNSUP, "group launch '" + gl.label + "': tile " + variant_name(variant) + " cannot take it");
   gl.args = a;
   gl.variant = variant;
   gl.grid = grid;
@@ -745,7 +746,7 @@ std::string NetGroup::plan_text() {
       long M = 0;
       int kmax = 0;
       for (int k = 0; k < gl.nprob; ++k) M += gl.table.prob[k].M, kmax = std::max(kmax, gl.table.prob[k].Ktot);
-      os << "conv_gemm_mp<" << conv_variant(gl.variant).name << ">\tM=" << M << " N=" << gl.p.Cout << " K=" << kmax << " problems=" << gl.nprob
+      os << "conv_gemm_mp<" << variant_name(gl.variant) << ">\tM=" << M << " N=" << gl.p.Cout << " K=" << kmax << " problems=" << gl.nprob
          << " grid=" << gl.grid << (cur_->nlanes > 1 ? " lane=" + std::to_string(gl.lane) : std::string()) << (gl.table.prob[0].resid ? " +resid" : "")
          << (gl.p.relu ? " +relu" : "") << (gl.p.sigmoid_ch ? " +sigmoid" : "");
     } else {
@@ -769,12 +770,12 @@ std::string NetGroup::tune_report_text() {
   }
   std::string out;
   for (auto& k : order) {
-    out += k + "\t" + conv_variant(seen[k].first).name + "\t" + std::to_string(seen[k].second) + "\t";
+    out += k + "\t" + variant_name(seen[k].first) + "\t" + std::to_string(seen[k].second) + "\t";
     auto t = nets[0]->shared->tune_timings.find(k);
     if (t != nets[0]->shared->tune_timings.end())
       for (size_t i = 0; i < t->second.size(); ++i) {
         char buf[96];
-        std::snprintf(buf, sizeof buf, "%s%s:%.2f", i ? " " : "", conv_variant(t->second[i].second).name, t->second[i].first * 1000.f / 5.f);
+        std::snprintf(buf, sizeof buf, "%s%s:%.2f", i ? " " : "", variant_name(t->second[i].second), t->second[i].first * 1000.f / 5.f);
         out += buf;
       }
     out += "\n";
@@ -784,14 +785,14 @@ std::string NetGroup::tune_report_text() {
 
 void NetGroup::set_tile(const std::string& key, const std::string& tile) {
   current_plan();
-  int v = conv_variant_by_name(tile.c_str());
-  if (tile == conv_variant(kStreamHalf).name) v = kStreamHalf;
+  int v = variant_by_name(tile.c_str());
+  if (v >= 0 && conv_form(v) && !conv_form(v)->launch_multi) v = -1;  // (the forms that never run merged are not group tiles)
   if (v < 0) throw DcError(DC_EINVAL, "no tile variant named '" + tile + "'");
   bool any = false;
   for (auto& gl : cur_->launches) {
     if (!gl.multi || gl.key != key) continue;
     ConvMultiArgs a;
-    if (!conv_variant_multiproblem(v) || group_args(gl, v, a) <= 0)
+    if (group_args(gl, v, a) <= 0)
       throw DcError(DC_EUNSUP, "tile '" + tile + "' cannot take group launch '" + gl.label + "'");
     any = true;
   }
@@ -856,7 +857,7 @@ std::string NetGroup::profile_text(int iters) {
     const double us = ms * 1000.0 / iters;
     total_us += us;
     const double fl = gl.multi ? gl.flops : nets[gl.member]->plan[gl.index].flops;
-    const std::string kn = gl.multi ? std::string("conv_gemm_mp<") + conv_variant(gl.variant).name + ">" : nets[gl.member]->plan[gl.index].kernel;
+    const std::string kn = gl.multi ? std::string("conv_gemm_mp<") + variant_name(gl.variant) + ">" : nets[gl.member]->plan[gl.index].kernel;
     char buf[640];
     std::snprintf(buf, sizeof buf, "%zu\t%s\t%.2f\t%.3f\t%.2f\t%ld\t%s\n", i, kn.c_str(), us, fl / 1e9, us > 0 ? fl / us / 1e6 : 0.0,
                   gl.multi ? gl.grid : nets[gl.member]->plan[gl.index].grid, gl.label.c_str());

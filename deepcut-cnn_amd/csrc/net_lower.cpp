@@ -499,8 +499,8 @@ void Net::build_plan() {
   };
   // -1: where measured faster (autotune); 0: never; 1: wherever eligible, 8 waves per workgroup; 2: wherever eligible, the 16-wave form
   const int wino_mode = env_int("DC_WINOGRAD", -1);
-  const int stem_mode = env_int("DC_STEM", -1);          // the float16 stem kernel: -1 where measured faster, 0 never, 1 forced
-  const int stream_mode = env_int("DC_STREAM1X1", -1);  // the streaming form of the float16 dense 1x1 layers: -1 where measured faster, 0 never, 1 wherever eligible
+  const int stem_mode = env_int("DC_STEM", -1);          // the stem forms: -1 where measured faster, 0 never, 1 forced
+  const int stream_mode = env_int("DC_STREAM1X1", -1);  // the streaming forms of the dense 1x1 layers: -1 where measured faster, 0 never, 1 wherever eligible
   auto choose_variant = [&](Launch& l, int kgcd) {
     int best = -1;
     double bc = 0;
@@ -520,14 +520,12 @@ void Net::build_plan() {
         if (best < 0 || c < bc) best = v, bc = c;
       }
     if (best < 0) throw DcError(DC_EUNSUP, "launch '" + l.label + "': no tile variant takes K segments of " + std::to_string(kgcd) + " elements");
-    l.variant = best;
-    l.kernel = std::string("conv_gemm<") + conv_variant(best).name + ">";
-    l.grid = conv_grid(l.cg, best);
+    l.set_variant(best);
   };
-  auto use_wino = [&](Launch& l, int wv) {
-    l.variant = wv;
-    l.kernel = wino_kernel_label(wv);
-    l.grid = wino_grid(l.cg);
+  // a form whose image the launch now carries: forced on by its switch (ConvForm::env >= 1), it replaces the tile unless DC_CONV_VARIANT
+  // forces a tile; else the per-shape timing decides
+  auto offer_form = [&](Launch& l, int v) {
+    if (env_int(conv_form(v)->env, -1) >= 1 && (force_variant < 0 || conv_form(force_variant))) l.set_variant(v);
   };
 
   // Channel split of a wide-but-ragged GEMM (the merged heads: N = 406 = 3 x 128 + 22).  On 128-wide tiles a quarter of the
@@ -687,36 +685,36 @@ void Net::build_plan() {
       // stride-1 3x3 layers can also run as Winograd F(2x2,3x3): keep the transformed filters next to the direct ones
       // and let the per-shape timing decide (kernels.hip, wino_f23_kernel)
       if (!rowtap && wino_mode != 0 && op.wls.empty() && wino_eligible(g) && dtype == kElemF32) {
-        l.wino_w = get_vec(dkey + "wino:" + std::to_string(op.wl), [&](std::vector<float>& h) {
+        l.form_w = get_vec(dkey + "wino:" + std::to_string(op.wl), [&](std::vector<float>& h) {
           h.assign(wino_packed_floats(c.num_output, C), 0.f);
           wino_pack_filters(L.params[0]->st->host_ptr(), c.num_output, C, h.data());
         });
-        if (wino_mode >= 1 && (force_variant < 0 || is_wino_variant(force_variant))) use_wino(l, wino_mode == 2 ? kWinoVariant16 : kWinoVariant);
-      } else if (!rowtap && wino_mode != 0 && op.wls.empty() && dtype == kElemF16 && op.in2 < 0 && wino_eligible(g)) {
+        offer_form(l, wino_mode == 2 ? kWinoVariant16 : kWinoVariant);
+      } else if (!rowtap && wino_mode != 0 && op.wls.empty() && dtype == kElemF16 && op.in2 < 0 && wino_half_eligible(g)) {
         // float16 (wino_f16.hip): the image is packed in MFMA fragment order with its own per-channel power-of-two row scale
         // (DevVec::row_scale: G g G^T has other maxima than g); the form's epilogue scale = folded affine x row scale x 4 (the
         // kernel stages the pixels pre-multiplied by 1/4 so that B^T d B cannot overflow float16)
         std::vector<float> rs_made;  // filled only if the image is packed now (else the DevVec found in the cache carries its row scale)
-        l.wino_w = get_vec(dkey + "wino:" + std::to_string(op.wl), [&](std::vector<float>& h) {
+        l.form_w = get_vec(dkey + "wino:" + std::to_string(op.wl), [&](std::vector<float>& h) {
           h.assign(wino_half_packed_elems(c.num_output, C), 0.f);
           rs_made.assign(c.num_output, 1.f);
           wino_half_pack_filters(L.params[0]->st->host_ptr(), c.num_output, C, half_rowscale, h.data(), rs_made.data());
         });
-        if (!rs_made.empty()) l.wino_w->row_scale = std::move(rs_made);
-        l.wino_w->as_half = true;
-        std::shared_ptr<DevVec> ws = l.wino_w;
+        if (!rs_made.empty()) l.form_w->row_scale = std::move(rs_made);
+        l.form_w->as_half = true;
+        std::shared_ptr<DevVec> ws = l.form_w;
         char wkey[40];
         std::snprintf(wkey, sizeof wkey, "%p", (void*)ws.get());
-        l.wino_scale = get_vec(std::string("hwa:") + wkey + ":" + std::to_string(op.lids.front()) + ":" + std::to_string(op.lids.size()), [&](std::vector<float>& h) {
+        l.form_scale = get_vec(std::string("hwa:") + wkey + ":" + std::to_string(op.lids.front()) + ":" + std::to_string(op.lids.size()), [&](std::vector<float>& h) {
           h.resize(OC);
           for (int q = 0; q < OC; ++q) h[q] = (float)((op.a.empty() ? 1.0 : op.a[q]) * 4.0 * (double)(ws->row_scale.empty() ? 1.f : ws->row_scale[q]));
         });
-        if (wino_mode >= 1 && (force_variant < 0 || is_wino_variant(force_variant))) use_wino(l, kWinoHalf);
+        offer_form(l, kWinoHalf);
       } else if (!rowtap && stream_mode != 0 && op.wls.empty() && dtype == kElemF16 && g.klen == C && g.Ktot == C && stream1x1_eligible(g)) {
         // float16 dense 1x1 layers (stream1x1.hip): the same row-scaled filters as the direct image, in MFMA fragment order;
         // scale / shift / shortcut are the launch's own.  The per-shape timing decides (DC_STREAM1X1=1: wherever eligible, 0: never)
         std::shared_ptr<DevVec> direct = l.w;
-        l.wino_w = get_vec(dkey + "ws:" + std::to_string(op.wl), [&](std::vector<float>& h) {
+        l.form_w = get_vec(dkey + "ws:" + std::to_string(op.wl), [&](std::vector<float>& h) {
           const float* src = L.params[0]->st->host_ptr();  // [OC][C][1][1]
           std::vector<float> scaled((size_t)OC * C);
           for (int co = 0; co < OC; ++co) {
@@ -726,22 +724,22 @@ void Net::build_plan() {
           h.assign(stream1x1_packed_elems(OC, C), 0.f);
           stream1x1_pack_filters(scaled.data(), OC, C, h.data());
         });
-        l.wino_w->as_half = true;
-        if (stream_mode >= 1 && (force_variant < 0 || is_wino_variant(force_variant))) use_wino(l, kStreamHalf);
+        l.form_w->as_half = true;
+        offer_form(l, kStreamHalf);
       }
-      if (!rowtap && !l.wino_w && stream_mode != 0 && op.wls.empty() && dtype == kElemF32 && g.klen == C && g.Ktot == C && stream1x1f_eligible(g)) {
+      if (!rowtap && !l.form_w && stream_mode != 0 && op.wls.empty() && dtype == kElemF32 && g.klen == C && g.Ktot == C && stream1x1f_eligible(g)) {
         // float32 dense 1x1 layers with 64 / 128 / 256 / 512 input channels (stream1x1_f32.hip): the filters in the order of its 16x16x4 matrix steps
-        l.wino_w = get_vec(dkey + "wsf:" + std::to_string(op.wl), [&](std::vector<float>& h) {
+        l.form_w = get_vec(dkey + "wsf:" + std::to_string(op.wl), [&](std::vector<float>& h) {
           h.assign(stream1x1f_packed_elems(OC, C), 0.f);
           stream1x1f_pack_filters(L.params[0]->st->host_ptr(), OC, C, h.data());
         });
-        if (stream_mode >= 1 && (force_variant < 0 || is_wino_variant(force_variant))) use_wino(l, kStreamFloat);
+        offer_form(l, kStreamFloat);
       }
       if (rowtap && stem_mode != 0 && op.wls.empty() && dtype == kElemF16 && C <= 4 && stem7x7_eligible(g)) {
         // float16 stem (stem_f16.hip): the same row-scaled filters as the row-tap image, the 28 real elements of every kernel row in MFMA
         // operand order; scale / shift are the launch's own.  The per-shape timing decides (DC_STEM=1: forced, 0: never)
         std::shared_ptr<DevVec> direct = l.w;
-        l.wino_w = get_vec(dkey + "stem:" + std::to_string(op.wl), [&](std::vector<float>& h) {
+        l.form_w = get_vec(dkey + "stem:" + std::to_string(op.wl), [&](std::vector<float>& h) {
           const float* src = L.params[0]->st->host_ptr();  // [64][C][7][7]
           std::vector<float> scaled((size_t)64 * C * 49);
           for (int co = 0; co < 64; ++co) {
@@ -751,14 +749,14 @@ void Net::build_plan() {
           h.assign(stem7x7_packed_elems(), 0.f);
           stem7x7_pack_filters(scaled.data(), C, h.data());
         });
-        l.wino_w->as_half = true;
-        if (stem_mode >= 1 && (force_variant < 0 || is_wino_variant(force_variant))) use_wino(l, kStemHalf);
+        l.form_w->as_half = true;
+        offer_form(l, kStemHalf);
       }
       if (rowtap && stem_mode != 0 && op.wls.empty() && dtype == kElemF32 && C <= 4 && stem_ws_eligible(g)) {
         // float32 stem on the streaming skeleton (stream1x1_f32.hip, "ws7x7f"): the row-tap image's 224 columns + 32 of zeros in the order of
         // its 16x16x4 matrix steps; scale / shift are the launch's own.  The per-shape timing decides (DC_STEM=1: forced, 0: never)
         std::shared_ptr<DevVec> direct = l.w;
-        l.wino_w = get_vec(dkey + "stemws:" + std::to_string(op.wl), [&](std::vector<float>& h) {
+        l.form_w = get_vec(dkey + "stemws:" + std::to_string(op.wl), [&](std::vector<float>& h) {
           const float* w = L.params[0]->st->host_ptr();  // [64][C][7][7]
           std::vector<float> rt((size_t)64 * 224, 0.f);  // the row-tap order: k = ky 32 + kx 4 + ci
           for (int co = 0; co < 64; ++co)
@@ -768,9 +766,9 @@ void Net::build_plan() {
           h.assign(stem_ws_packed_elems(), 0.f);
           stem_ws_pack_filters(rt.data(), h.data());
         });
-        if (stem_mode >= 1 && (force_variant < 0 || is_wino_variant(force_variant))) use_wino(l, kStemFloat);
+        offer_form(l, kStemFloat);
       }
-      if (l.wino_w || rowtap) plan.push_back(std::move(l));
+      if (l.form_w || rowtap) plan.push_back(std::move(l));
       else push_split(std::move(l), kgcd);
     } else if (op.kind == LOp::DECONV) {
       // stride-s transposed convolution = s*s ordinary gather-GEMMs, one per output residue class

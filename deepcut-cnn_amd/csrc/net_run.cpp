@@ -22,7 +22,7 @@ void Net::upload_vecs() {
   std::lock_guard<std::mutex> lk(shared->mu);  // an image may be shared with a clone that uploads at the same moment
   std::vector<DevVec*> todo;
   for (auto& l : plan)
-    for (const std::shared_ptr<DevVec>* vp : {&l.w, &l.scale, &l.shift, &l.wino_w, &l.wino_scale})
+    for (const std::shared_ptr<DevVec>* vp : {&l.w, &l.scale, &l.shift, &l.form_w, &l.form_scale})
       if (*vp && !(*vp)->dev && !(*vp)->host.empty()) todo.push_back(vp->get());
   for (DevVec* vq : todo) {
     DevVec& v = *vq;
@@ -97,13 +97,13 @@ void Net::run_launch(const Launch& l, void* s) {
       g.w = reinterpret_cast<const unsigned char*>(l.w->dev) + (size_t)l.w_off * (size_t)g.esize;
       g.scale = l.scale ? l.scale->dev + l.c_off : nullptr;
       g.shift = l.shift ? l.shift->dev + l.c_off : nullptr;
-      const bool wino = is_wino_variant(l.variant);  // Winograd F(2x2,3x3) form of a stride-1 3x3 layer (8 or 16 waves per workgroup)
-      if (wino) {
-        if (!l.wino_w) throw DcError(DC_EINVAL, "launch '" + l.label + "' has no Winograd filter image");
-        g.w = l.wino_w->dev;
-        if (l.variant == kWinoHalf) {  // float16: the form's own epilogue scale (row scale of ITS image, the 1/4 of the staged pixels)
-          if (!l.wino_scale || l.in2 >= 0) throw DcError(DC_EINVAL, "launch '" + l.label + "' cannot run as the float16 Winograd form");
-          g.scale = l.wino_scale->dev + l.c_off;
+      const ConvForm* form = conv_form(l.variant);
+      if (form) {
+        if (!l.form_w) throw DcError(DC_EINVAL, "launch '" + l.label + "' has no filter image of form " + form->name);
+        g.w = l.form_w->dev;
+        if (form->own_scale) {  // (wino_h23: the row scale of ITS image, the 1/4 of the staged pixels)
+          if (!l.form_scale || l.in2 >= 0) throw DcError(DC_EINVAL, "launch '" + l.label + "' cannot run as form " + form->name);
+          g.scale = l.form_scale->dev + l.c_off;
         }
       }
       static const int dbg_idx = env_int("DC_DEBUG_TIMING", -1);
@@ -114,7 +114,7 @@ void Net::run_launch(const Launch& l, void* s) {
       if (dbg_idx >= 0 && my_idx == dbg_idx) {
         // device-side phase timestamps of ONE launch (diagnostics only): per wave the shader cycle counter at up to 8 phase
         // boundaries (slots 0..7) and the chip-wide 100 MHz clock at start / end (slots 8, 9)
-        const int nwv = wino ? (l.variant == kWinoVariant16 ? 16 : l.variant == kStreamHalf || l.variant == kStemHalf || l.variant == kStreamFloat || l.variant == kStemFloat ? 4 : 8) : conv_variant(l.variant).WR * conv_variant(l.variant).WC * conv_variant(l.variant).WK;
+        const int nwv = form ? form->waves : conv_variant(l.variant).WR * conv_variant(l.variant).WC * conv_variant(l.variant).WK;
         const long n = (l.grid * 2 + 64) * nwv * 12;  // the XCD-aware maps pad the grid (at most 8 x the longest XCD list)
         long long* d = nullptr;
         dev_alloc((void**)&d, n * sizeof(long long));
@@ -125,8 +125,7 @@ void Net::run_launch(const Launch& l, void* s) {
         for (int rep = 0; rep < (insitu ? 1 : 3); ++rep) {
           g.dbg = d;
           if (!insitu) HIPCHECK(hipStreamSynchronize((hipStream_t)s));
-          if (wino) KCHECK(launch_wino_conv(g, s, l.variant));
-          else KCHECK(launch_conv_gemm(g, l.variant, s));
+          KCHECK(launch_conv(g, l.variant, s));
           HIPCHECK(hipStreamSynchronize((hipStream_t)s));
         }
         std::vector<long long> h(n);
@@ -153,32 +152,20 @@ void Net::run_launch(const Launch& l, void* s) {
         // 3 output offsets in LDS, 4 first tile staged (K-loop entry), 5 K-loop exit, 6 split-K exchange done, 7 stores issued
         static const char* kGemm[7] = {"filter-load issue", "row decode + activation-load issue", "output offsets to LDS", "wait+stage+barrier",
                                        "K loop", "split-K exchange", "epilogue math+stores"};
-        static const char* kWino[7] = {"index setup", "first loads issued", "two stages in LDS", "K loop", "partials to LDS + barrier",
-                                       "inverse transform + epilogue constants", "shortcut + stores"};
-        // ws1x1 (stream1x1.hip) slots: 0 start, 1 every prologue request issued, 2 first stage + filters + constants landed, 3 the peeled
-        // first D steps done, 4 the other steps (and the late half's last epilogue) done, 5 requests drained
-        static const char* kStream[7] = {"prologue requests issued", "first stage + filters landed", "the first D steps", "the other steps",
-                                         "drain", "-", "exit"};
         std::string line;
         for (int k = 1; k < 8; ++k) {
           char buf[96];
-          std::snprintf(buf, sizeof buf, "%s%s %.0f", k > 1 ? " | " : "", (l.variant == kStreamHalf || l.variant == kStreamFloat || l.variant == kStemFloat ? kStream : wino ? kWino : kGemm)[k - 1], dsum[k] / std::max(cnt, 1L));
+          std::snprintf(buf, sizeof buf, "%s%s %.0f", k > 1 ? " | " : "", (form ? form->timing_slots : kGemm)[k - 1], dsum[k] / std::max(cnt, 1L));
           line += buf;
         }
         std::fprintf(stderr, "[dc timing] launch %d %s %s\n  mean cycles per wave: %s\n", my_idx, l.kernel.c_str(), l.label.c_str(), line.c_str());
         g.dbg = nullptr;
       }
-      if (wino) {
-        KCHECK(launch_wino_conv(g, s, l.variant));
-        break;
-      }
-      {
-        const int rc = launch_conv_gemm(g, l.variant, s);
-        if (rc == (int)hipErrorInvalidValue)
-          throw DcError(DC_EUNSUP, "launch '" + l.label + "': unsupported geometry (a tensor of 2 GiB or more per launch — "
-                                   "split the batch — or a tap / K layout this variant cannot take)");
-        KCHECK(rc);
-      }
+      const int rc = launch_conv(g, l.variant, s);
+      if (!form && rc == (int)hipErrorInvalidValue)
+        throw DcError(DC_EUNSUP, "launch '" + l.label + "': unsupported geometry (a tensor of 2 GiB or more per launch — "
+                                 "split the batch — or a tap / K layout this variant cannot take)");
+      KCHECK(rc);
       break;
     }
     case Launch::POOL:

@@ -21,8 +21,7 @@ void load_tune_cache_locked(ModelShared& shared) {
     const size_t sp = line.find_last_of(' ');
     if (sp != std::string::npos && sp > 0 && sp + 1 < line.size()) {
       const std::string key = line.substr(0, sp), vname = line.substr(sp + 1);
-      int v = wino_variant_by_name(vname.c_str());
-      if (v < 0) v = conv_variant_by_name(vname.c_str());
+      const int v = variant_by_name(vname.c_str());
       if (v >= 0 && !shared.tune_cache.count(key)) shared.tune_cache[key] = v;
     }
     line.clear();
@@ -46,7 +45,7 @@ void write_tune_cache_locked(ModelShared& shared) {
   FILE* f = std::fopen(tmp.c_str(), "w");
   if (!f) return;
   for (auto& kv : shared.tune_cache)
-    std::fprintf(f, "%s %s\n", kv.first.c_str(), is_wino_variant(kv.second) ? wino_variant_name(kv.second) : conv_variant(kv.second).name);
+    std::fprintf(f, "%s %s\n", kv.first.c_str(), variant_name(kv.second));
   const bool ok = std::fflush(f) == 0;
   std::fclose(f);
   if (!ok || std::rename(tmp.c_str(), cache_path) != 0) std::remove(tmp.c_str());
@@ -88,32 +87,24 @@ void Net::autotune() {
     }
     return ms;
   };
-  // (1) every distinct signature not in the cache: each eligible tile (and the Winograd form) timed alone, back to back
+  // (1) every distinct signature not in the cache: each eligible tile and form timed alone, back to back
   std::map<std::string, std::vector<std::pair<float, int>>> timed;  // signature -> (ms, variant) of this pass
   for (auto& l : plan) {
     if (l.kind != Launch::CONV) continue;
-    const ConvGemmParams& g = l.cg;
     const std::string key = key_of(l);
     if (tune_cache_.count(key)) continue;
     timed_any = true;
     std::vector<std::pair<float, int>>& c = timed[key];
     int ncand = 0;
-    const int* cand = conv_variants_of(g.ekind, &ncand);
-    for (int ci = 0; ci < ncand; ++ci) {
-      const int v = cand[ci];
-      if (!tile_takes_k(v, g.klen, l.row_tap)) continue;
-      if (g.ncls > 1 && !conv_variant_multiclass(v)) continue;
+    const int* cand = conv_variants_of(l.cg.ekind, &ncand);
+    std::vector<int> vs(cand, cand + ncand);  // the tiles of the net's element kind, then the forms
+    for (int v = kFormVariant0; v < kFormVariant0 + kNumForms; ++v) vs.push_back(v);
+    for (int v : vs) {
+      if (!l.takes_tile(v)) continue;
       Launch trial = l;
       trial.variant = v;
       c.push_back({burst_ms(trial), v});
     }
-    if (l.wino_w)  // the Winograd forms of this layer (8 and 16 waves per workgroup) compete with the direct tiles
-      for (int wv : {kWinoVariant, kWinoVariant16, kWinoHalf, kStreamHalf, kStemHalf, kStreamFloat, kStemFloat}) {
-        if (!l.takes_wino(wv)) continue;
-        Launch trial = l;
-        trial.variant = wv;
-        c.push_back({burst_ms(trial), wv});
-      }
     std::sort(c.begin(), c.end());
     tune_cache_[key] = c.empty() ? l.variant : c.front().second;
     shared->tune_timings[key] = c;
@@ -204,11 +195,11 @@ void Net::autotune() {
       }
     }
   }
-  // (2b) the two Winograd forms against each other, by whole passes over the plan.  They differ in how well a workgroup hides
-  // its own latencies (16 waves per workgroup: four per SIMD on launches of at most one workgroup per CU), which shows where a
-  // launch starts behind another kernel's tail on cold caches and hardly at all in a burst of identical launches or between
-  // hipEvents (res4 3x3 at 544x736, batch 1: 15.6 against 15.8 us timed alone, 1.25 us per launch inside the forward): where one
-  // of them was chosen and the other is eligible, both run in whole passes (no events inside) and the faster pass stays.
+  // (2b) a form against its sibling (ConvForm::sibling: the two float32 Winograd forms), by whole passes over the plan.  The two
+  // differ in how well a workgroup hides its own latencies (16 waves per workgroup: four per SIMD on launches of at most one workgroup
+  // per CU), which shows where a launch starts behind another kernel's tail on cold caches and hardly at all in a burst of identical
+  // launches or between hipEvents (res4 3x3 at 544x736, batch 1: 15.6 against 15.8 us timed alone, 1.25 us per launch inside the
+  // forward): where one of them was chosen and the other is eligible, both run in whole passes (no events inside) and the faster pass stays.
   if (timed_any && env_int("DC_TUNE_INSITU", 1) != 0) {
     std::vector<Launch> saved = plan;
     struct Restore {
@@ -219,8 +210,7 @@ void Net::autotune() {
     for (auto& l : plan) {  // the passes run with the tiles chosen so far (what (3) will put into the plan)
       if (l.kind != Launch::CONV) continue;
       auto it = tune_cache_.find(key_of(l));
-      if (it != tune_cache_.end() && !(is_wino_variant(it->second) && !l.takes_wino(it->second)) &&
-          !(l.cg.ncls > 1 && (is_wino_variant(it->second) || !conv_variant_multiclass(it->second))))
+      if (it != tune_cache_.end() && (conv_form(it->second) ? l.takes_form(it->second) : l.cg.ncls <= 1 || conv_variant_multiclass(it->second)))
         l.variant = it->second;
     }
     auto pass_ms = [&]() {
@@ -238,36 +228,30 @@ void Net::autotune() {
     };
     for (auto& kv : timed) {
       auto it = tune_cache_.find(kv.first);
-      if (it == tune_cache_.end() || !is_wino_variant(it->second) || it->second == kWinoHalf || it->second == kStreamHalf || it->second == kStemHalf || it->second == kStreamFloat || it->second == kStemFloat) continue;
+      const ConvForm* chosen = it == tune_cache_.end() ? nullptr : conv_form(it->second);
+      if (!chosen || chosen->sibling < 0) continue;
       bool both = false;
-      for (auto& c : kv.second) both = both || (is_wino_variant(c.second) && c.second != it->second);
+      for (auto& c : kv.second) both = both || c.second == chosen->sibling;
       if (!both) continue;
       float ms[2];
-      const int forms[2] = {kWinoVariant, kWinoVariant16};
+      const int forms[2] = {std::min(it->second, chosen->sibling), std::max(it->second, chosen->sibling)};
       for (int f = 0; f < 2; ++f) {
         for (auto& l : plan)
-          if (l.kind == Launch::CONV && l.wino_w && key_of(l) == kv.first) l.variant = forms[f];
+          if (l.kind == Launch::CONV && l.form_w && key_of(l) == kv.first) l.variant = forms[f];
         ms[f] = pass_ms();
       }
-      it->second = ms[1] < ms[0] ? kWinoVariant16 : kWinoVariant;
+      it->second = ms[1] < ms[0] ? forms[1] : forms[0];
       for (auto& l : plan)  // (later signatures are compared with this one's choice in place)
-        if (l.kind == Launch::CONV && l.wino_w && key_of(l) == kv.first) l.variant = it->second;
+        if (l.kind == Launch::CONV && l.form_w && key_of(l) == kv.first) l.variant = it->second;
     }
   }
   // (3) the choices go into the plan
   for (auto& l : plan) {
     if (l.kind != Launch::CONV) continue;
     auto it = tune_cache_.find(key_of(l));
-    // a cache line naming the Winograd form while it is switched off (or not eligible any more), or a tile of another element kind
+    // a cache line naming a form while it is switched off (or not eligible any more), or a tile of another element kind
     // (a hand-edited file shared by float16 and bfloat16 nets): keep the cost model's tile
-    if (it != tune_cache_.end() && l.takes_tile(it->second)) l.variant = it->second;
-    if (is_wino_variant(l.variant)) {
-      l.kernel = wino_kernel_label(l.variant);
-      l.grid = wino_grid(l.cg);
-    } else {
-      l.kernel = std::string("conv_gemm<") + conv_variant(l.variant).name + ">";
-      l.grid = conv_grid(l.cg, l.variant);
-    }
+    l.set_variant(it != tune_cache_.end() && l.takes_tile(it->second) ? it->second : l.variant);
   }
   if (timed_any) ++stats.autotune_runs;
   if (tune_cache_.size() != cached_before || timed_any) write_tune_cache_locked(*shared);
@@ -275,8 +259,8 @@ void Net::autotune() {
   release_graph();
 }
 
-// GEMM signature of a launch: the key of the tile choice ("h" prefix: float16, "b": bfloat16; "+w": the Winograd form competes for this layer —
-// a different candidate set than with DC_WINOGRAD=0 —; "+mcN:K..": a multi-class launch, N classes with these K and M)
+// GEMM signature of a launch: the key of the tile choice ("h" prefix: float16, "b": bfloat16; "+w": forms compete for this layer —
+// a different candidate set than with their switches at 0 —; "+mcN:K..": a multi-class launch, N classes with these K and M)
 std::string Net::tune_key(const Launch& l) const {
   const ConvGemmParams& g = l.cg;
   char key[200];
@@ -286,7 +270,7 @@ std::string Net::tune_key(const Launch& l) const {
     for (int c = 0; c < g.ncls; ++c) mck += ":" + std::to_string(g.cls[c].Ktot) + "m" + std::to_string(g.cls[c].M);
   }
   std::snprintf(key, sizeof key, "%s%d/%d/%d/%d/%dx%d/%d,%d/%d/%d%s%s", g.ekind == kElemBF16 ? "b" : g.esize == 2 ? "h" : "", g.M, g.Cout, g.Ktot, g.klen, g.nty, g.ntx,
-                g.sy, g.sx, l.in2 >= 0 ? 1 : 0, g.OW, l.wino_w ? "+w" : "", mck.c_str());
+                g.sy, g.sx, l.in2 >= 0 ? 1 : 0, g.OW, l.form_w ? "+w" : "", mck.c_str());
   return key;
 }
 
@@ -304,15 +288,14 @@ std::string Net::tune_report_text() {
     if (it == seen.end()) order.push_back(k), seen[k] = {l.variant, 1};
     else ++it->second.second;
   }
-  auto vname = [](int v) { return std::string(is_wino_variant(v) ? wino_variant_name(v) : conv_variant(v).name); };
   std::string out;
   for (auto& k : order) {
-    out += k + "\t" + vname(seen[k].first) + "\t" + std::to_string(seen[k].second) + "\t";
+    out += k + "\t" + variant_name(seen[k].first) + "\t" + std::to_string(seen[k].second) + "\t";
     auto t = shared->tune_timings.find(k);
     if (t != shared->tune_timings.end())
       for (size_t i = 0; i < t->second.size(); ++i) {
         char buf[96];
-        std::snprintf(buf, sizeof buf, "%s%s:%.2f", i ? " " : "", vname(t->second[i].second).c_str(), t->second[i].first * 1000.f / 5.f);
+        std::snprintf(buf, sizeof buf, "%s%s:%.2f", i ? " " : "", variant_name(t->second[i].second), t->second[i].first * 1000.f / 5.f);
         out += buf;
       }
     out += "\n";
@@ -324,8 +307,7 @@ std::string Net::tune_report_text() {
 // current plan that has the signature, recorded in the shared choice table (clones pick it up at their next lowering; call
 // set_tile on each executor to change their current plans), and the captured graph is dropped.
 void Net::set_tile(const std::string& key, const std::string& tile) {
-  int v = wino_variant_by_name(tile.c_str());
-  if (v < 0) v = conv_variant_by_name(tile.c_str());
+  const int v = variant_by_name(tile.c_str());
   if (v < 0) throw DcError(DC_EINVAL, "no tile variant named '" + tile + "'");
   bool any = false;
   for (auto& l : plan) {
@@ -336,14 +318,7 @@ void Net::set_tile(const std::string& key, const std::string& tile) {
   if (!any) throw DcError(DC_EINVAL, "the current plan has no launch with signature '" + key + "'");
   for (auto& l : plan) {
     if (l.kind != Launch::CONV || tune_key(l) != key) continue;
-    l.variant = v;
-    if (is_wino_variant(v)) {
-      l.kernel = wino_kernel_label(v);
-      l.grid = wino_grid(l.cg);
-    } else {
-      l.kernel = std::string("conv_gemm<") + conv_variant(v).name + ">";
-      l.grid = conv_grid(l.cg, v);
-    }
+    l.set_variant(v);
   }
   {
     std::lock_guard<std::mutex> lk(shared->mu);
