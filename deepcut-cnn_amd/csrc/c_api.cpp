@@ -470,6 +470,16 @@ int dc_net_forward_images(dc_net* net, const unsigned char* images, int n, int h
   });
 }
 
+int dc_net_forward_boxes(dc_net* net, const unsigned char* image, int height, int width, int is_device, const int* boxes, const double* scales,
+                         int n, int canvas_h, int canvas_w, float* prob, float* loc_pred, float* next_pred, double* pose, void* stream) {
+  REQUIRE(net);
+  if (n == 0) return DC_OK;
+  REQUIRE(image);
+  return guard([&] {
+    N(net)->forward_boxes(image, height, width, is_device != 0, boxes, scales, n, canvas_h, canvas_w, prob, loc_pred, next_pred, pose, stream);
+  });
+}
+
 int dc_image_canvas_size(int height, int width, double scale, int* canvas_h, int* canvas_w) {
   REQUIRE(canvas_h);
   REQUIRE(canvas_w);
@@ -648,6 +658,18 @@ int dc_group_forward_images(dc_group* group, const unsigned char* const* images,
     if (n[c] <= 0 || height[c] <= 0 || width[c] <= 0 || !(scale[c] > 0)) return fail(DC_EINVAL, "bad image shape / scale for group member " + std::to_string(c));
   }
   return guard([&] { G(group)->forward_images(images, n, height, width, scale, is_device != 0, prob, loc_pred, next_pred, pose, stream); });
+}
+int dc_group_forward_boxes(dc_group* group, const unsigned char* image, int height, int width, int is_device, const int* boxes,
+                           const double* scales, int n, const double* pyramid_scales, int canvas_h, int canvas_w, float* const* prob,
+                           float* const* loc_pred, float* const* next_pred, double* const* pose, void* stream) {
+  REQUIRE(group);
+  if (n == 0) return DC_OK;
+  REQUIRE(image);
+  REQUIRE(pyramid_scales);
+  return guard([&] {
+    G(group)->forward_boxes(image, height, width, is_device != 0, boxes, scales, n, pyramid_scales, canvas_h, canvas_w, prob, loc_pred,
+                            next_pred, pose, stream);
+  });
 }
 int dc_comm_create(int nexec, const int* devices, int transport, dc_comm** out) {
   REQUIRE(out);

@@ -322,7 +322,41 @@ struct ImagePrepParams {
 };
 int launch_image_prep(const ImagePrepParams& p, void* stream);
 
+// The same pre-processing for n person boxes of ONE image, in one launch: item i is the crop src[y0:y0+h, x0:x0+w] treated as an
+// image of its own (the 64-px replicate padding repeats the CROP's last row / column: reads are clamped at the window's edges),
+// resampled with its own tables and pasted at the top-left of canvas i.  Both resample passes run per output pixel (the
+// horizontal pass of each tap row is recomputed in registers and clipped to 8 bits as Pillow's intermediate image is), so there is
+// no intermediate buffer and no second launch.
+struct BoxPrepItem {
+  int x0, y0, h, w;        // the source window
+  int use_h, use_w;        // top-left part of the resized crop that lands on the canvas; the rest of canvas i is zero
+  const int* x_bounds;     // [new_w][2] (first tap, tap count) in padded-crop columns; nullptr: no horizontal pass
+  const int* x_coeffs;     // [new_w][x_ksize]
+  const int* y_bounds;     // nullptr: no vertical pass
+  const int* y_coeffs;
+  int x_ksize, y_ksize;
+};
+struct BoxPrepParams {
+  const unsigned char* src;  // [img_h][img_w][3] BGR uint8
+  int img_h, img_w;
+  int n;
+  int out_h, out_w;          // the common canvas of every item (= the network input)
+  const BoxPrepItem* items;  // [n], device memory
+  void* dst;                 // [n][out_h][out_w][dst_cp] float, _Float16 or __bf16 (dst_ekind); pad channels zeroed
+  int dst_ekind, dst_cp;
+  float mean[3];
+};
+int launch_box_prep(const BoxPrepParams& p, void* stream);
+
 int launch_pose_decode(const void* prob, int pcp, int pc0, const void* loc, int lcp, int lc0, int ekind, int NB, int H,
                        int W, int J, double scale, double* out, void* stream);
+// launch_pose_decode with a scale, an offset and a valid cell extent per image (device table `items`, one per image): the arg-max
+// runs over cells [0, rows) x [0, cols) only, x and y are divided by the item's scale and then shifted by (dx, dy)
+struct PoseDecodeItem {
+  double scale, dx, dy;
+  int rows, cols;
+};
+int launch_pose_decode_items(const void* prob, int pcp, int pc0, const void* loc, int lcp, int lc0, int ekind, int NB, int H,
+                             int W, int J, const PoseDecodeItem* items, double* out, void* stream);
 
 }  // namespace dc

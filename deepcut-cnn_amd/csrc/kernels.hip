@@ -2302,16 +2302,26 @@ int launch_f32_to_bf16(const float* src, void* dst, long n, void* stream) {
 // the score map in row-major order, refined by the location-regression vector at that cell.  One block
 // per (image, joint); only 5 x J doubles per image leave the GPU instead of the maps.
 // ------------------------------------------------------------------------------------------------
+// `items` (launch_pose_decode_items): image n's own scale, offset and valid cells [0, rows) x [0, cols); the region is walked in
+// row-major order, so the first maximum is the restricted map's first maximum.
 template <typename T>
 __global__ __launch_bounds__(256) void pose_decode_kernel(const T* __restrict__ prob, int pcp, int pc0,
                                                           const T* __restrict__ loc, int lcp, int lc0, int H, int W,
-                                                          int J, double scale, double* __restrict__ out) {
+                                                          int J, double scale, const PoseDecodeItem* __restrict__ items,
+                                                          double* __restrict__ out) {
   __shared__ float sv[256];
   __shared__ int si[256];
   const int j = blockIdx.x, n = blockIdx.y, HW = H * W;
+  int rows = H, cols = W;
+  if (items) {
+    const PoseDecodeItem& it = items[n];
+    rows = min(it.rows, H), cols = min(it.cols, W), scale = it.scale;
+  }
+  const int cnt = rows * cols;
   float best = -3.402823466e+38f;
   int bi = 0x7fffffff;
-  for (int p = threadIdx.x; p < HW; p += 256) {
+  for (int q = threadIdx.x; q < cnt; q += 256) {
+    const int p = cols == W ? q : (q / cols) * W + (q % cols);
     const float v = (float)prob[((long)n * HW + p) * pcp + pc0 + j];
     if (v > best) best = v, bi = p;  // strided scan keeps the smallest index per thread
   }
@@ -2338,6 +2348,7 @@ __global__ __launch_bounds__(256) void pose_decode_kernel(const T* __restrict__ 
     double* o = out + (long)n * 5 * J;
     o[0 * J + j] = ((double)col * 8.0 + 4.0 + ox * kLoc) / scale;
     o[1 * J + j] = ((double)row * 8.0 + 4.0 + oy * kLoc) / scale;
+    if (items) o[0 * J + j] += items[n].dx, o[1 * J + j] += items[n].dy;
     o[2 * J + j] = (double)(float)prob[((long)n * HW + p) * pcp + pc0 + j];
     o[3 * J + j] = oy * kLoc / scale;
     o[4 * J + j] = ox * kLoc / scale;
@@ -2350,7 +2361,19 @@ int launch_pose_decode(const void* prob, int pcp, int pc0, const void* loc, int 
   return dc_by_kind(ekind, [&](auto* tag) {
     using T = std::remove_pointer_t<decltype(tag)>;
     hipLaunchKernelGGL(pose_decode_kernel<T>, dim3(J, NB), dim3(256), 0, (hipStream_t)stream, (const T*)prob, pcp, pc0, (const T*)loc, lcp,
-                       lc0, H, W, J, scale, out);
+                       lc0, H, W, J, scale, (const PoseDecodeItem*)nullptr, out);
+    return (int)hipGetLastError();
+  });
+}
+
+int launch_pose_decode_items(const void* prob, int pcp, int pc0, const void* loc, int lcp, int lc0, int ekind, int NB, int H,
+                             int W, int J, const PoseDecodeItem* items, double* out, void* stream) {
+  if (NB <= 0 || J <= 0) return 0;
+  if (!items) return (int)hipErrorInvalidValue;
+  return dc_by_kind(ekind, [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    hipLaunchKernelGGL(pose_decode_kernel<T>, dim3(J, NB), dim3(256), 0, (hipStream_t)stream, (const T*)prob, pcp, pc0, (const T*)loc, lcp,
+                       lc0, H, W, J, 1.0, items, out);
     return (int)hipGetLastError();
   });
 }
@@ -2578,6 +2601,72 @@ __global__ __launch_bounds__(256) void image_finish_kernel(ImagePrepParams p) {
   }
   T* d = reinterpret_cast<T*>(p.dst) + i * p.dst_cp;
   for (int c = 0; c < p.dst_cp; ++c) d[c] = (T)(c < 3 ? v[c] : 0.f);
+}
+
+// One thread per canvas pixel of every box.  The vertical taps of a pixel read rows of the horizontally resampled crop that
+// are computed here, per tap row, with Pillow's rounding and 8-bit clip: the same integers as the two-pass route.
+template <typename T>
+__global__ __launch_bounds__(256) void box_prep_kernel(BoxPrepParams p) {
+  const long total = (long)p.n * p.out_h * p.out_w;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int x = (int)(i % p.out_w);
+  const long t = i / p.out_w;
+  const int y = (int)(t % p.out_h), n = (int)(t / p.out_h);
+  const BoxPrepItem it = p.items[n];
+  float v[3] = {0.f, 0.f, 0.f};
+  if (y < it.use_h && x < it.use_w) {
+    // row r of the replicate-padded crop after the horizontal pass (rows / columns past the crop repeat its last one)
+    auto hrow = [&](int r, int& b0, int& b1, int& b2) {
+      const unsigned char* row = p.src + ((long)(it.y0 + min(r, it.h - 1)) * p.img_w + it.x0) * 3;
+      if (it.x_bounds) {
+        const int xmin = it.x_bounds[2 * x], cnt = it.x_bounds[2 * x + 1];
+        const int* kk = it.x_coeffs + (long)x * it.x_ksize;
+        int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
+        for (int k = 0; k < cnt; ++k) {
+          const int sx = min(xmin + k, it.w - 1);
+          const int c = kk[k];
+          a0 += row[sx * 3 + 0] * c;
+          a1 += row[sx * 3 + 1] * c;
+          a2 += row[sx * 3 + 2] * c;
+        }
+        b0 = clip8_fixed(a0), b1 = clip8_fixed(a1), b2 = clip8_fixed(a2);
+      } else {
+        const int sx = min(x, it.w - 1);
+        b0 = row[sx * 3 + 0], b1 = row[sx * 3 + 1], b2 = row[sx * 3 + 2];
+      }
+    };
+    int o0, o1, o2;
+    if (it.y_bounds) {
+      const int ymin = it.y_bounds[2 * y], cnt = it.y_bounds[2 * y + 1];
+      const int* kk = it.y_coeffs + (long)y * it.y_ksize;
+      int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
+      for (int k = 0; k < cnt; ++k) {
+        int b0, b1, b2;
+        hrow(ymin + k, b0, b1, b2);
+        const int c = kk[k];
+        a0 += b0 * c, a1 += b1 * c, a2 += b2 * c;
+      }
+      o0 = clip8_fixed(a0), o1 = clip8_fixed(a1), o2 = clip8_fixed(a2);
+    } else {
+      hrow(y, o0, o1, o2);
+    }
+    v[0] = (float)o0 - p.mean[0], v[1] = (float)o1 - p.mean[1], v[2] = (float)o2 - p.mean[2];
+  }
+  T* d = reinterpret_cast<T*>(p.dst) + i * p.dst_cp;
+  for (int c = 0; c < p.dst_cp; ++c) d[c] = (T)(c < 3 ? v[c] : 0.f);
+}
+
+int launch_box_prep(const BoxPrepParams& p, void* stream) {
+  if (p.dst_ekind != kElemF32 && p.dst_ekind != kElemF16 && p.dst_ekind != kElemBF16) return (int)hipErrorInvalidValue;
+  if (p.dst_cp < 3 || !p.items || !p.src) return (int)hipErrorInvalidValue;
+  const long total = (long)p.n * p.out_h * p.out_w;
+  if (total <= 0) return 0;
+  return dc_by_kind(p.dst_ekind, [&](auto* tag) {
+    hipLaunchKernelGGL(box_prep_kernel<std::remove_pointer_t<decltype(tag)>>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, p);
+    return (int)hipGetLastError();
+  });
 }
 
 int launch_image_prep(const ImagePrepParams& p, void* stream) {

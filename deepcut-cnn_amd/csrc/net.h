@@ -11,6 +11,7 @@
 // deconvolution is one launch (4 for a stride-2 deconvolution: one per output parity class) of the
 // gather-GEMM MFMA kernel in kernels.hip.
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <functional>
 #include <map>
@@ -160,6 +161,12 @@ struct ResampleTable {  // Pillow-style 8-bit bilinear resample of one axis: tap
 void resample_coeffs(int in_size, int out_size, int& ksize, std::vector<int>& bounds, std::vector<int>& coeffs);
 // estimate_pose.py:85-88,96: canvas (stride-8) and resized-image sizes for an h x w image at `scale`
 void image_canvas_size(int h, int w, double scale, int& out_h, int& out_w, int& new_h, int& new_w);
+// the box entry's argument checks (Net::forward_boxes), host only: every box (x0, y0, x1, y1) non-empty and inside the h x w image,
+// every scale positive, the canvas a positive multiple of 8 that holds every box's own canvas (image_canvas_size of the crop at its
+// scale).  Throws DC_EINVAL naming the first box at fault.
+void check_boxes(int h, int w, const int* boxes, const double* scales, int n, int canvas_h, int canvas_w);
+// a group member's canvas in the box entry: the base canvas side times the member's pyramid scale, rounded up to the stride 8
+inline int box_member_canvas(int side, double pyramid_scale) { return (int)(std::ceil((double)side * pyramid_scale / 8) * 8); }
 
 // A tile takes K segments of `klen` elements: klen is a multiple of its K tile, and for a row-tap launch exactly one K tile.  (A row
 // tap spans several adjacent pixels of a narrow input; the kernel checks a lane's tap validity at its column of the tap's FIRST K tile,
@@ -308,6 +315,11 @@ struct Net {
   // image entry: pre-processing (estimate_pose.py:83-103) + forward + optional decode, all on the device
   void forward_images(const unsigned char* bgr, int n, int h, int w, double scale, bool is_device, float* prob, float* loc,
                       float* next, double* pose, void* user_stream);
+  // box entry: n person boxes of ONE h x w image (boxes: n x 4 int32 (x0, y0, x1, y1), half-open; scales: n doubles; both host
+  // arrays), box i pre-processed at scales[i] as an image of its own onto a common canvas_h x canvas_w canvas, ONE batch-n forward,
+  // pose i decoded on its own canvas's cells at scales[i] and shifted by (x0, y0) into image coordinates.  n = 0 does nothing.
+  void forward_boxes(const unsigned char* bgr, int h, int w, bool is_device, const int* boxes, const double* scales, int n, int canvas_h,
+                     int canvas_w, float* prob, float* loc, float* next, double* pose, void* user_stream);
   void sync_to_host(Storage& s);       // SyncedMemory::to_cpu
   void sync_to_device(Storage& s);     // SyncedMemory::to_gpu
   void decode_pose(double scale, double* out, bool is_device, void* user_stream);  // after a forward
@@ -319,6 +331,12 @@ struct Net {
   // front half of forward_images: the uint8 pixels -> the network's NHWC input image, enqueued on s (the plan of the canvas
   // shape is active afterwards); returns the canvas height / width
   void prep_images(const unsigned char* bgr, int n, int h, int w, double scale, bool is_device, void* s);
+  // front half of forward_boxes (arguments already checked): the boxes' canvases in ONE launch, and the per-box decode table;
+  // returns the device copy of the image the launch reads (a host image is uploaded once)
+  const unsigned char* prep_boxes(const unsigned char* bgr, int h, int w, bool is_device, const int* boxes, const double* scales, int n,
+                                  int canvas_h, int canvas_w, void* s);
+  // back half: the poses of the boxes of the last prep_boxes, in image coordinates (host or device `out`, n x 5 x J doubles)
+  void decode_boxes(double* out, bool is_device, void* s);
   std::string plan_text();
   std::string profile_text(int iters);
   std::string tune_report_text();  // per GEMM signature of the current plan: tile in use, launches, the isolated timings of autotune
@@ -358,6 +376,10 @@ struct Net {
   size_t img_cap_ = 0;
   unsigned char* tmp_dev_ = nullptr;  // horizontally resampled rows
   size_t tmp_cap_ = 0;
+  unsigned char* box_dev_ = nullptr;  // box entry: BoxPrepItem[n] then PoseDecodeItem[n]
+  size_t box_cap_ = 0;
+  std::vector<unsigned char> box_host_;  // the host side of that table (outlives its upload)
+  int box_n_ = 0;                     // boxes of the last prep_boxes
 };
 
 // ---- pyramid-grouped execution (round 4) ---------------------------------------------------------------------------------
@@ -416,6 +438,11 @@ struct NetGroup {
   // forward, then per member the maps / the decoded pose
   void forward_images(const unsigned char* const* bgr, const int* n, const int* h, const int* w, const double* scale, bool is_device,
                       float* const* prob, float* const* loc, float* const* next, double* const* pose, void* user_stream);
+  // box entry (Net::forward_boxes): member c takes every box at scales[i] * pyramid[c] on a canvas of box_member_canvas(canvas_h / w,
+  // pyramid[c]); the image is uploaded once, each member pre-processes its boxes in one launch, then ONE grouped forward
+  void forward_boxes(const unsigned char* bgr, int h, int w, bool is_device, const int* boxes, const double* scales, int n,
+                     const double* pyramid, int canvas_h, int canvas_w, float* const* prob, float* const* loc, float* const* next,
+                     double* const* pose, void* user_stream);
   // lanes: 0 = automatic (2 members: two lanes; 3: one; 4 and more: two), else that many (at most one per member); every merged plan is dropped
   void set_lanes(int n);
   int lanes() const { return cur_ ? cur_->nlanes : lanes_opt_; }

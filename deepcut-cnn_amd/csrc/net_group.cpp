@@ -724,6 +724,49 @@ void NetGroup::forward_images(const unsigned char* const* bgr, const int* n, con
   if (!(is_device && (user_stream || own_async))) HIPCHECK(hipStreamSynchronize((hipStream_t)s));
 }
 
+void NetGroup::forward_boxes(const unsigned char* bgr, int h, int w, bool is_device, const int* boxes, const double* scales, int n,
+                             const double* pyramid, int canvas_h, int canvas_w, float* const* prob, float* const* loc, float* const* next,
+                             double* const* pose, void* user_stream) {
+  if (!pyramid) throw DcError(DC_EINVAL, "group forward_boxes: null pyramid scales");
+  // every member's boxes and canvas are checked before any device work; the base canvas itself must be a multiple of 8 too
+  if (n < 0) throw DcError(DC_EINVAL, "forward_boxes: n must not be negative");
+  if (n > 0 && (canvas_h < 8 || canvas_w < 8 || canvas_h % 8 || canvas_w % 8))
+    throw DcError(DC_EINVAL, "forward_boxes: canvas " + std::to_string(canvas_h) + "x" + std::to_string(canvas_w) +
+                                 " is not a positive multiple of 8 on both sides");
+  std::vector<std::vector<double>> sc(nets.size(), std::vector<double>((size_t)std::max(n, 0)));
+  std::vector<int> ch(nets.size()), cw(nets.size());
+  for (size_t c = 0; c < nets.size(); ++c) {
+    if (!(pyramid[c] > 0) || !std::isfinite(pyramid[c]))
+      throw DcError(DC_EINVAL, "group forward_boxes: pyramid scale of member " + std::to_string(c) + " is not positive");
+    ch[c] = box_member_canvas(canvas_h, pyramid[c]), cw[c] = box_member_canvas(canvas_w, pyramid[c]);
+    for (int i = 0; i < n && scales; ++i) sc[c][(size_t)i] = scales[i] * pyramid[c];
+    try {
+      check_boxes(h, w, boxes, scales ? sc[c].data() : nullptr, n, ch[c], cw[c]);
+    } catch (const DcError& e) {
+      throw DcError(e.code, std::string(e.what()) + " (group member " + std::to_string(c) + ", pyramid scale " + std::to_string(pyramid[c]) + ")");
+    }
+  }
+  if (n == 0) return;
+  if (!bgr) throw DcError(DC_EINVAL, "group forward_boxes: null image");
+  if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "forward_boxes() in CPU mode: libdeepcut_hip provides the MI355X path only");
+  const bool own_async = user_stream == (void*)-1;
+  if (own_async) user_stream = nullptr;
+  nets[0]->ensure_device();
+  void* s = user_stream ? user_stream : stream();
+  const unsigned char* src = bgr;
+  bool dev = is_device;
+  for (size_t c = 0; c < nets.size(); ++c) {
+    src = nets[c]->prep_boxes(src, h, w, dev, boxes, sc[c].data(), n, ch[c], cw[c], s);  // the image crosses PCIe once
+    dev = true;
+  }
+  enqueue(s);
+  for (size_t c = 0; c < nets.size(); ++c) {
+    nets[c]->emit_maps(prob ? prob[c] : nullptr, loc ? loc[c] : nullptr, next ? next[c] : nullptr, is_device, s);
+    if (pose && pose[c]) nets[c]->decode_boxes(pose[c], is_device, s);
+  }
+  if (!(is_device && (user_stream || own_async))) HIPCHECK(hipStreamSynchronize((hipStream_t)s));
+}
+
 int NetGroup::num_launches() { return cur_ ? (int)cur_->launches.size() : 0; }
 int NetGroup::num_multi_launches() {
   int m = 0;

@@ -62,7 +62,7 @@ std::shared_ptr<ResampleTable> Net::resample_table(int in_size, int out_size) {
   dev_alloc((void**)&t->dev_coeffs, c.size() * sizeof(int));
   dev_upload(t->dev_bounds, b.data(), b.size() * sizeof(int), stream);
   dev_upload(t->dev_coeffs, c.data(), c.size() * sizeof(int), stream);
-  if (resample_.size() > 64) resample_.clear();  // a pyramid uses a handful; bound the cache anyway
+  if (resample_.size() > 256) resample_.clear();  // a pyramid uses a handful, a crowd of boxes two per box size; bound the cache anyway
   resample_[key] = t;
   return t;
 }
@@ -150,6 +150,137 @@ void Net::prep_images(const unsigned char* bgr, int n, int h, int w, double scal
   }
   KCHECK(launch_image_prep(q, s));
   in.head = HEAD_AT_GPU;
+}
+
+// ---- box entry: the person boxes of one image, each pre-processed as the image of its own that the demo would get ---------
+void check_boxes(int h, int w, const int* boxes, const double* scales, int n, int canvas_h, int canvas_w) {
+  if (n < 0) throw DcError(DC_EINVAL, "forward_boxes: n must not be negative");
+  if (n == 0) return;
+  if (!boxes || !scales) throw DcError(DC_EINVAL, "forward_boxes: null boxes / scales");
+  if (h <= 0 || w <= 0) throw DcError(DC_EINVAL, "forward_boxes: image height and width must be positive");
+  if (canvas_h < 8 || canvas_w < 8 || canvas_h % 8 || canvas_w % 8)
+    throw DcError(DC_EINVAL, "forward_boxes: canvas " + std::to_string(canvas_h) + "x" + std::to_string(canvas_w) +
+                                 " is not a positive multiple of 8 on both sides");
+  for (int i = 0; i < n; ++i) {
+    const int x0 = boxes[4 * i], y0 = boxes[4 * i + 1], x1 = boxes[4 * i + 2], y1 = boxes[4 * i + 3];
+    const std::string box = "forward_boxes: box " + std::to_string(i) + " (" + std::to_string(x0) + ", " + std::to_string(y0) + ", " +
+                            std::to_string(x1) + ", " + std::to_string(y1) + ")";
+    if (x1 <= x0 || y1 <= y0) throw DcError(DC_EINVAL, box + " is empty");
+    if (x0 < 0 || y0 < 0 || x1 > w || y1 > h)
+      throw DcError(DC_EINVAL, box + " lies outside the " + std::to_string(h) + "x" + std::to_string(w) + " image");
+    if (!(scales[i] > 0) || !std::isfinite(scales[i])) throw DcError(DC_EINVAL, box + ": scale " + std::to_string(scales[i]) + " is not positive");
+    int oh, ow, nh, nw;
+    image_canvas_size(y1 - y0, x1 - x0, scales[i], oh, ow, nh, nw);
+    if (nh < 1 || nw < 1 || oh < 8 || ow < 8) throw DcError(DC_EINVAL, box + ": scale " + std::to_string(scales[i]) + " leaves no pixels");
+    if (oh > canvas_h || ow > canvas_w)
+      throw DcError(DC_EINVAL, box + " at scale " + std::to_string(scales[i]) + " needs a " + std::to_string(oh) + "x" + std::to_string(ow) +
+                                   " canvas, larger than " + std::to_string(canvas_h) + "x" + std::to_string(canvas_w));
+  }
+}
+
+void Net::forward_boxes(const unsigned char* bgr, int h, int w, bool is_device, const int* boxes, const double* scales, int n, int canvas_h,
+                        int canvas_w, float* prob, float* loc, float* next, double* pose, void* user_stream) {
+  check_boxes(h, w, boxes, scales, n, canvas_h, canvas_w);
+  if (n == 0) return;
+  if (!bgr) throw DcError(DC_EINVAL, "forward_boxes: null image");
+  if (Context::get().mode != DC_MODE_GPU)
+    throw DcError(DC_ENOCPU, "forward_boxes() in CPU mode: libdeepcut_hip provides the MI355X path only");
+  const bool own_async = user_stream == (void*)-1;
+  if (own_async) user_stream = nullptr;
+  prep_boxes(bgr, h, w, is_device, boxes, scales, n, canvas_h, canvas_w, user_stream);
+  void* s = user_stream ? user_stream : stream;
+  enqueue_plan(s);
+  emit_maps(prob, loc, next, is_device, s);
+  if (pose) decode_boxes(pose, is_device, (user_stream || own_async) ? s : nullptr);
+  if (!(is_device && (user_stream || own_async))) HIPCHECK(hipStreamSynchronize((hipStream_t)s));
+}
+
+const unsigned char* Net::prep_boxes(const unsigned char* bgr, int h, int w, bool is_device, const int* boxes, const double* scales, int n,
+                                     int canvas_h, int canvas_w, void* s) {
+  Storage& in = begin_batch(n, canvas_h, canvas_w);
+  if (in.dim(1) != 3) throw DcError(DC_ESHAPE, "forward_boxes needs a 3-channel input blob");
+  if (!s) s = stream;
+  const unsigned char* src = bgr;
+  if (!is_device) {
+    const size_t bytes = (size_t)h * w * 3;
+    if (bytes > img_cap_) {
+      dev_free(img_dev_);
+      img_dev_ = nullptr;
+      dev_alloc((void**)&img_dev_, bytes);
+      img_cap_ = bytes;
+    }
+    HIPCHECK(hipMemcpyAsync(img_dev_, bgr, bytes, hipMemcpyHostToDevice, (hipStream_t)s));
+    src = img_dev_;
+  }
+  // the per-box table: windows, use_h / use_w and the Pillow tables of each axis (one cached table per distinct (extent, size)),
+  // followed by the decode's scale / offset / valid cells
+  const int kPad = 64;
+  const size_t prep_b = ((size_t)n * sizeof(BoxPrepItem) + 15) / 16 * 16, bytes = prep_b + (size_t)n * sizeof(PoseDecodeItem);
+  box_host_.assign(bytes, 0);
+  BoxPrepItem* items = reinterpret_cast<BoxPrepItem*>(box_host_.data());
+  PoseDecodeItem* dec = reinterpret_cast<PoseDecodeItem*>(box_host_.data() + prep_b);
+  std::vector<std::shared_ptr<ResampleTable>> hold;  // the tables outlive a cache flush until the launch is enqueued
+  for (int i = 0; i < n; ++i) {
+    const int x0 = boxes[4 * i], y0 = boxes[4 * i + 1], bw = boxes[4 * i + 2] - x0, bh = boxes[4 * i + 3] - y0;
+    int out_h, out_w, new_h, new_w;
+    image_canvas_size(bh, bw, scales[i], out_h, out_w, new_h, new_w);
+    BoxPrepItem& it = items[i];
+    it.x0 = x0, it.y0 = y0, it.h = bh, it.w = bw;
+    it.use_h = std::min(out_h, new_h), it.use_w = std::min(out_w, new_w);
+    if (new_w != bw + kPad) {
+      hold.push_back(resample_table(bw + kPad, new_w));
+      it.x_bounds = hold.back()->dev_bounds, it.x_coeffs = hold.back()->dev_coeffs, it.x_ksize = hold.back()->ksize;
+    }
+    if (new_h != bh + kPad) {
+      hold.push_back(resample_table(bh + kPad, new_h));
+      it.y_bounds = hold.back()->dev_bounds, it.y_coeffs = hold.back()->dev_coeffs, it.y_ksize = hold.back()->ksize;
+    }
+    dec[i].scale = scales[i], dec[i].dx = x0, dec[i].dy = y0;
+    dec[i].rows = out_h / 8, dec[i].cols = out_w / 8;  // the crop's own canvas in map cells (stride 8)
+  }
+  if (bytes > box_cap_) {
+    dev_free(box_dev_);
+    box_dev_ = nullptr;
+    dev_alloc((void**)&box_dev_, bytes);
+    box_cap_ = bytes;
+  }
+  HIPCHECK(hipMemcpyAsync(box_dev_, box_host_.data(), bytes, hipMemcpyHostToDevice, (hipStream_t)s));
+  box_n_ = n;
+  BoxPrepParams q{};
+  q.src = src;
+  q.img_h = h, q.img_w = w, q.n = n;
+  q.out_h = canvas_h, q.out_w = canvas_w;
+  q.items = reinterpret_cast<const BoxPrepItem*>(box_dev_);
+  q.dst = in.dev, q.dst_ekind = in.ekind, q.dst_cp = in.cp();
+  q.mean[0] = 104.f, q.mean[1] = 117.f, q.mean[2] = 123.f;  // _MEAN, estimate_pose.py:26
+  KCHECK(launch_box_prep(q, s));
+  in.head = HEAD_AT_GPU;
+  return src;
+}
+
+void Net::decode_boxes(double* out, bool is_device, void* user_stream) {
+  const MapRef P = map_ref("prob"), L = map_ref("loc_pred");
+  if (L.C != 2 * P.C || L.H != P.H || L.W != P.W || L.NB != P.NB || L.ek != P.ek)
+    throw DcError(DC_ESHAPE, "forward_boxes: loc_pred must have 2 channels per joint and the score map's size");
+  if (P.NB != box_n_) throw DcError(DC_EINVAL, "forward_boxes: the maps are not those of the last boxes");
+  const size_t prep_b = ((size_t)box_n_ * sizeof(BoxPrepItem) + 15) / 16 * 16;
+  const PoseDecodeItem* items = reinterpret_cast<const PoseDecodeItem*>(box_dev_ + prep_b);
+  void* s = user_stream ? user_stream : stream;
+  if (is_device) {
+    KCHECK(launch_pose_decode_items(P.ptr, P.cp, P.c0, L.ptr, L.cp, L.c0, P.ek, P.NB, P.H, P.W, P.C, items, out, s));
+    if (!user_stream) HIPCHECK(hipStreamSynchronize((hipStream_t)s));
+    return;
+  }
+  const size_t cnt = (size_t)P.NB * 5 * P.C;
+  if (cnt > pose_cap) {
+    dev_free(pose_dev);
+    pose_dev = nullptr;
+    dev_alloc((void**)&pose_dev, cnt * sizeof(double));
+    pose_cap = cnt;
+  }
+  KCHECK(launch_pose_decode_items(P.ptr, P.cp, P.c0, L.ptr, L.cp, L.c0, P.ek, P.NB, P.H, P.W, P.C, items, pose_dev, s));
+  HIPCHECK(hipMemcpyAsync(out, pose_dev, cnt * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)s));
+  HIPCHECK(hipStreamSynchronize((hipStream_t)s));
 }
 
 // _pose_from_mats (python/pose/estimate_pose.py:131-143) on the device: reads the `prob` and `loc_pred`

@@ -100,6 +100,7 @@ def _load():
         "dc_net_emit_maps": (ci, [vp, vp, vp, vp, ci, ci, vp]),
         "dc_net_forward_images": (ci, [vp, vp, ci, ci, ci, C.c_double, ci, vp, vp, vp, vp, vp]),
         "dc_image_canvas_size": (ci, [ci, ci, C.c_double, C.POINTER(ci), C.POINTER(ci)]),
+        "dc_net_forward_boxes": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp]),
         "dc_net_detect_parts": (ci, [vp, C.c_double, C.c_float, ci, ci, vp, vp]),
         "dc_net_decode_pairwise": (ci, [vp, C.c_double, ci, vp, vp, vp, vp]),
         "dc_net_flops": (ci, [vp, C.POINTER(C.c_double)]),
@@ -120,6 +121,8 @@ def _load():
                                         C.POINTER(vp), vp]),
         "dc_group_forward_images": (ci, [vp, C.POINTER(vp), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_double), ci,
                                          C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]),
+        "dc_group_forward_boxes": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, C.POINTER(C.c_double), ci, ci, C.POINTER(vp), C.POINTER(vp),
+                                        C.POINTER(vp), C.POINTER(vp), vp]),
         "dc_group_plan_text": (cp, [vp]),
         "dc_group_profile_text": (cp, [vp, ci]),
         "dc_group_tune_report": (cp, [vp]),
@@ -240,6 +243,55 @@ def canvas_size(height, width, scale):
     h, w = C.c_int(), C.c_int()
     _check(_lib.dc_image_canvas_size(int(height), int(width), float(scale), C.byref(h), C.byref(w)))
     return h.value, w.value
+
+
+def member_canvas(side, pyramid_scale):
+    """A NetGroup member's canvas side in the box entry: `side` * pyramid_scale rounded up to the stride 8."""
+    return int(np.ceil(float(side) * float(pyramid_scale) / 8) * 8)
+
+
+def check_boxes(image_shape, boxes, scales=1.0, canvas=None):
+    """The box entry's arguments, checked on the host before anything reaches the device.  image_shape: (H, W[, 3]); boxes: n x 4
+    integers (x0, y0, x1, y1), half-open, inside the image; scales: one number or one per box.  -> (boxes int32 [n, 4], scales
+    float64 [n], (canvas_h, canvas_w)); canvas None = the smallest canvas that holds every box's own canvas (canvas_size of the
+    crop at its scale).  Raises ValueError naming the box at fault."""
+    h, w = int(image_shape[0]), int(image_shape[1])
+    b = np.asarray(boxes)
+    if b.size == 0:
+        b = b.reshape(0, 4)
+    if b.ndim != 2 or b.shape[1] != 4:
+        raise ValueError("boxes must be an n x 4 array of (x0, y0, x1, y1), got shape %s" % (b.shape,))
+    if not np.issubdtype(b.dtype, np.integer):
+        if not (np.isfinite(b).all() and (b == np.round(b)).all()):
+            raise ValueError("box corners must be whole pixels")
+    b = np.ascontiguousarray(b, dtype=np.int32)
+    n = b.shape[0]
+    sc = np.asarray(scales, np.float64)
+    sc = np.ascontiguousarray(np.full(n, float(sc)) if sc.ndim == 0 else sc.reshape(-1))
+    if sc.shape[0] != n:
+        raise ValueError("%d scales for %d boxes" % (sc.shape[0], n))
+    need_h = need_w = 8
+    for i in range(n):
+        x0, y0, x1, y1 = (int(v) for v in b[i])
+        if x1 <= x0 or y1 <= y0:
+            raise ValueError("box %d (%d, %d, %d, %d) is empty" % (i, x0, y0, x1, y1))
+        if x0 < 0 or y0 < 0 or x1 > w or y1 > h:
+            raise ValueError("box %d (%d, %d, %d, %d) lies outside the %dx%d image" % (i, x0, y0, x1, y1, h, w))
+        if not (np.isfinite(sc[i]) and sc[i] > 0):
+            raise ValueError("box %d (%d, %d, %d, %d): scale %r is not positive" % (i, x0, y0, x1, y1, sc[i]))
+        if int((x1 - x0 + 64) * sc[i]) < 1 or int((y1 - y0 + 64) * sc[i]) < 1:
+            raise ValueError("box %d (%d, %d, %d, %d): scale %r leaves no pixels" % (i, x0, y0, x1, y1, sc[i]))
+        ch, cw = canvas_size(y1 - y0, x1 - x0, sc[i])
+        if canvas is not None and (ch > canvas[0] or cw > canvas[1]):
+            raise ValueError("box %d (%d, %d, %d, %d) at scale %r needs a %dx%d canvas, larger than %dx%d"
+                             % (i, x0, y0, x1, y1, sc[i], ch, cw, canvas[0], canvas[1]))
+        need_h, need_w = max(need_h, ch), max(need_w, cw)
+    if canvas is None:
+        canvas = (need_h, need_w)
+    canvas = (int(canvas[0]), int(canvas[1]))
+    if min(canvas) < 8 or canvas[0] % 8 or canvas[1] % 8:
+        raise ValueError("canvas %dx%d is not a positive multiple of 8 on both sides" % canvas)
+    return b, sc, canvas
 
 
 def lpt_schedule(costs, nexec):
@@ -693,6 +745,50 @@ class Net(object):
                                           ptrs["loc_pred"], ptrs["next_pred"], pp, None))
         return outs
 
+    def forward_boxes(self, image, boxes, scales=1.0, canvas=None, want=("prob", "loc_pred"), pose=True):
+        """Top-down poses of person boxes: image uint8 [H,W,3] BGR host array, boxes n x 4 (x0, y0, x1, y1) half-open pixel
+        corners, scales one number or one per box, canvas (h, w) multiples of 8 or None (the smallest that fits every box:
+        check_boxes).  Box i is pre-processed as forward_images would pre-process image[y0:y1, x0:x1] at scales[i], pasted at the
+        top-left of the common canvas; all boxes in one launch and one batch forward.  -> dict with the requested NCHW maps
+        (n x the whole canvas's map) and "pose" [n,5,J] decoded on each box's own canvas, in image coordinates."""
+        x = np.ascontiguousarray(image, dtype=np.uint8)
+        if x.ndim != 3 or x.shape[2] != 3:
+            raise ValueError("image must be uint8 [H,W,3] (BGR)")
+        b, sc, (ch, cw) = check_boxes(x.shape, boxes, scales, canvas)
+        n, j = b.shape[0], self.blobs["prob"].shape[1]
+        if n == 0:
+            outs = {k: np.empty((0,), np.float32) for k in ("prob", "loc_pred", "next_pred") if k in want}
+            if pose:
+                outs["pose"] = np.empty((0, 5, j), np.float64)
+            return outs
+        self.blobs["data"].reshape(n, 3, ch, cw)
+        self.reshape()
+        outs, ptrs = {}, {}
+        for k in ("prob", "loc_pred", "next_pred"):
+            if k in want:
+                outs[k] = self._out_array(k, self.blobs[k].shape)
+                ptrs[k] = outs[k].ctypes.data_as(C.c_void_p)
+            else:
+                ptrs[k] = None
+        pp = None
+        if pose:
+            outs["pose"] = np.empty((n, 5, j), np.float64)
+            pp = outs["pose"].ctypes.data_as(C.c_void_p)
+        _check(_lib.dc_net_forward_boxes(self._h, x.ctypes.data_as(C.c_void_p), x.shape[0], x.shape[1], 0, b.ctypes.data_as(C.c_void_p),
+                                         sc.ctypes.data_as(C.c_void_p), n, ch, cw, ptrs["prob"], ptrs["loc_pred"], ptrs["next_pred"], pp, None))
+        return outs
+
+    def forward_boxes_device(self, img_ptr, h, w, boxes, scales, canvas, prob_ptr=None, loc_ptr=None, next_ptr=None, pose_ptr=None,
+                             stream=None):
+        """Device-resident form of forward_boxes: the image (uint8 [h,w,3]) and the outputs are raw device pointers, boxes and scales
+        host arrays, canvas (h, w) given; asynchronous on `stream` ("own" = the net's)."""
+        if stream == "own":
+            stream = C.c_void_p(-1).value
+        b, sc, (ch, cw) = check_boxes((h, w), boxes, scales, canvas)
+        _check(_lib.dc_net_forward_boxes(self._h, C.c_void_p(img_ptr), int(h), int(w), 1, b.ctypes.data_as(C.c_void_p),
+                                         sc.ctypes.data_as(C.c_void_p), b.shape[0], ch, cw, C.c_void_p(prob_ptr or 0), C.c_void_p(loc_ptr or 0),
+                                         C.c_void_p(next_ptr or 0), C.c_void_p(pose_ptr or 0), C.c_void_p(stream or 0)))
+
     def forward_images_device(self, img_ptr, n, h, w, scale=1.0, prob_ptr=None, loc_ptr=None, next_ptr=None,
                               pose_ptr=None, stream=None):
         """Device-resident form of forward_images: raw device pointers, asynchronous on `stream` ("own" = the net's)."""
@@ -925,6 +1021,48 @@ class NetGroup(object):
                                             self._ints([x.shape[1] for x in xs]), self._ints([x.shape[2] for x in xs]),
                                             (C.c_double * k)(*[float(s) for s in scales]), 0, col("prob"), col("loc_pred"), col("next_pred"),
                                             col("pose"), None))
+        return outs
+
+    def forward_boxes(self, image, boxes, pyramid, scales=1.0, canvas=None, want=("prob", "loc_pred"), pose=True):
+        """Net.forward_boxes over an image pyramid, as ONE grouped forward: member c takes box i at scales[i] * pyramid[c] on a
+        canvas of member_canvas(canvas, pyramid[c]); canvas None = the smallest base canvas that fits every box at scales[i].
+        -> one dict per member with the requested maps and "pose" [n,5,J] in image coordinates."""
+        k = len(self.nets)
+        x = np.ascontiguousarray(image, dtype=np.uint8)
+        if x.ndim != 3 or x.shape[2] != 3:
+            raise ValueError("image must be uint8 [H,W,3] (BGR)")
+        pyr = [float(p) for p in pyramid]
+        if len(pyr) != k:
+            raise ValueError("one pyramid scale per group member")
+        b, sc, (ch, cw) = check_boxes(x.shape, boxes, scales, canvas)
+        n = b.shape[0]
+        canv = [(member_canvas(ch, p), member_canvas(cw, p)) for p in pyr]
+        for p, cv in zip(pyr, canv):
+            check_boxes(x.shape, b, sc * p, cv)
+        outs = []
+        for m, (mh, mw) in zip(self.nets, canv):
+            j = m.blobs["prob"].shape[1]
+            if n == 0:
+                o = {key: np.empty((0,), np.float32) for key in ("prob", "loc_pred", "next_pred") if key in want}
+                if pose:
+                    o["pose"] = np.empty((0, 5, j), np.float64)
+                outs.append(o)
+                continue
+            m.blobs["data"].reshape(n, 3, mh, mw)
+            m.reshape()
+            o = {key: m._out_array(key, m.blobs[key].shape) for key in ("prob", "loc_pred", "next_pred") if key in want}
+            if pose:
+                o["pose"] = np.empty((n, 5, j), np.float64)
+            outs.append(o)
+        if n == 0:
+            return outs
+
+        def col(key):
+            return self._ptrs([o[key].ctypes.data if key in o else None for o in outs], k)
+
+        _check(_lib.dc_group_forward_boxes(self._h, x.ctypes.data_as(C.c_void_p), x.shape[0], x.shape[1], 0, b.ctypes.data_as(C.c_void_p),
+                                           sc.ctypes.data_as(C.c_void_p), n, (C.c_double * k)(*pyr), ch, cw, col("prob"), col("loc_pred"),
+                                           col("next_pred"), col("pose"), None))
         return outs
 
     def forward_images_device(self, img_ptrs, shapes, scales, prob_ptrs=None, loc_ptrs=None, next_ptrs=None, pose_ptrs=None, stream=None):

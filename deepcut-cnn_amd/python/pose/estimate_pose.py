@@ -151,6 +151,34 @@ def preprocess(image, scale):
     return canvas
 
 
+def crop_canvas_size(h, w, scale):
+    """(out_h, out_w) of `preprocess` for an h x w image at `scale`: the sides rounded up to the stride."""
+    return int(_np.ceil(float(h) * scale / STRIDE) * STRIDE), int(_np.ceil(float(w) * scale / STRIDE) * STRIDE)
+
+
+def box_canvases(image, boxes, scales, canvas):
+    """Host construction of the box entry's batch (`Net.forward_boxes`): canvas i = `preprocess(image[y0:y1, x0:x1], scales[i])`
+    at the top-left of a zero canvas of canvas = (h, w).  -> float32 [n, h, w, 3]."""
+    image = _np.asarray(image)
+    boxes = _np.asarray(boxes).reshape(-1, 4)
+    out = _np.zeros((boxes.shape[0], int(canvas[0]), int(canvas[1]), 3), _np.float32)
+    for i, (x0, y0, x1, y1) in enumerate(boxes):
+        c = preprocess(image[y0:y1, x0:x1], float(scales[i]))
+        out[i, : c.shape[0], : c.shape[1]] = c
+    return out
+
+
+def box_pose_from_maps(prob, loc_pred, box, scale):
+    """The pose the box entry returns for one box from its maps over the whole canvas: `pose_from_maps` on the cells of the crop's
+    own canvas only, then x and y shifted by the box's corner (x0, y0) into image coordinates."""
+    x0, y0, x1, y1 = (int(v) for v in box)
+    oh, ow = crop_canvas_size(y1 - y0, x1 - x0, scale)
+    pose = pose_from_maps(_np.asarray(prob)[:, : oh // STRIDE, : ow // STRIDE], _np.asarray(loc_pred)[:, : oh // STRIDE, : ow // STRIDE], scale)
+    pose[0] += x0
+    pose[1] += y0
+    return pose
+
+
 def pose_from_maps(prob, loc_pred, scale=1.0):
     """prob [14,h,w], loc_pred [28,h,w] (channel 2j / 2j+1 = x / y refinement of joint j in units of
     sqrt(53) px) -> 5x14 float64, exactly the reference's `_pose_from_mats` arithmetic."""
@@ -279,3 +307,30 @@ def estimate_pose(image, model_def, model_bin, scales=None, net=None, tiling=Non
             prob, loc = forward_maps_tiled(net, preprocess(image, s), mode=tiling)
         poses.append(pose_from_maps(prob, loc, s))
     return select_best(poses)
+
+
+def estimate_poses(image, boxes, model_def, model_bin, scales=None, net=None, canvas=None):
+    """Top-down poses of the person boxes of one image: image HxWx3 BGR uint8, boxes n x 4 (x0, y0, x1, y1) half-open pixel corners
+    from the caller's person detector.  Every box runs at every scale of `scales` (default [1.0]; several scales are ONE grouped
+    forward, `NetGroup.forward_boxes`), the crop pre-processed as `estimate_pose` pre-processes an image; the best scale per box is
+    chosen as there (`select_best`).  canvas: the common (h, w) at scale 1, or None for the smallest that fits every box.
+    -> a list of n 5x14 poses in image coordinates (None where no scale reaches a positive confidence).  A caller-supplied `net`
+    keeps its option state; it is used together with clones of it kept with it (as `estimate_pose` does)."""
+    import caffe as _caffe
+
+    if scales is None:
+        scales = [1.0]
+    if net is None:
+        net = _get_model(model_def, model_bin)
+        _read_outputs_only(net)
+    image = _np.ascontiguousarray(image, dtype=_np.uint8)
+    b, _, base = _caffe.check_boxes(image.shape, boxes, 1.0, canvas)
+    if b.shape[0] == 0:
+        return []
+    if len(scales) > 1:
+        outs = _scale_group(net, len(scales)).forward_boxes(image, b, list(scales), canvas=base, want=(), pose=True)
+    else:
+        s = float(scales[0])
+        cv = (_caffe.member_canvas(base[0], s), _caffe.member_canvas(base[1], s))
+        outs = [net.forward_boxes(image, b, s, canvas=cv, want=(), pose=True)]
+    return [select_best([o["pose"][i] for o in outs]) for i in range(b.shape[0])]

@@ -251,6 +251,25 @@ int dc_net_forward_images(dc_net* net, const unsigned char* images, int n, int h
 /* the canvas (= network input) height and width dc_net_forward_images uses for an image at `scale` */
 int dc_image_canvas_size(int height, int width, double scale, int* canvas_h, int* canvas_w);
 
+/* ---- box entry: top-down poses for the person boxes of ONE image ------------------------------------------------------
+ * Box i = boxes[4i..4i+3] = (x0, y0, x1, y1), half-open, inside the height x width image, at scale scales[i], is treated as the
+ * image of its own that a caller would cut on the host: crop = image[y0:y1, x0:x1]; its canvas is dc_net_forward_images' pre-
+ * processing of that crop at scales[i] (the 64-px replicate padding repeats the CROP's last row / column, not the image's),
+ * pasted at the top-left of a zero canvas of canvas_h x canvas_w.  All n canvases are made by ONE launch straight into the `data`
+ * blob's image (float32, float16 or bfloat16 nets alike), then ONE batch-n forward.  pose (n*5*J doubles, or NULL) is
+ * `_pose_from_mats` of box i's maps restricted to the cells of the crop's own canvas (dc_image_canvas_size(y1-y0, x1-x0,
+ * scales[i]) / 8), divided by scales[i], with x and y (rows 0 and 1) shifted by (x0, y0) into image coordinates; the other
+ * rows as dc_net_decode_pose.  The result equals dc_net_forward_images on each host-cut crop placed on the common canvas.
+ * Finding the boxes (a person detector) and choosing their scales are the caller's.
+ * image   : height * width * 3 bytes, BGR, HWC; host (is_device=0) or device memory.  boxes (int32 n x 4) and scales (n doubles)
+ *           are host arrays.
+ * canvas  : canvas_h and canvas_w multiples of 8, at least every box's own canvas (dc_image_canvas_size of the crop).
+ * outputs : as dc_net_forward_images (any may be NULL); maps are n x the whole canvas's map.  stream as dc_net_forward_batch.
+ * Errors  : DC_EINVAL naming the box, before any device work, for an empty box, a box outside the image, a non-positive scale,
+ *           a canvas that is not a multiple of 8 or smaller than a box's own canvas.  n = 0 does nothing.                      */
+int dc_net_forward_boxes(dc_net* net, const unsigned char* image, int height, int width, int is_device, const int* boxes, const double* scales,
+                         int n, int canvas_h, int canvas_w, float* prob, float* loc_pred, float* next_pred, double* pose, void* stream);
+
 /* ---- multi-person consumers of the maps (no reference code: the reference repository stops at the maps) --------
  * What they invert is the label encoding of the reference's training layer (src/caffe/layers/pose_data_layer.cpp:
  * 686-802): a map cell (row, col) stands for the image point pt = (col*8+4, row*8+4)/scale; loc_pred holds
@@ -378,6 +397,14 @@ int dc_group_forward_batch(dc_group* group, const float* const* inputs, const in
 int dc_group_forward_images(dc_group* group, const unsigned char* const* images, const int* n, const int* height, const int* width,
                             const double* scale, int is_device, float* const* prob, float* const* loc_pred, float* const* next_pred,
                             double* const* pose, void* stream);
+/* dc_net_forward_boxes over an image pyramid: member c takes every box i at scales[i] * pyramid_scales[c] on a canvas of
+ * ceil(canvas_h * pyramid_scales[c] / 8) * 8 x ceil(canvas_w * pyramid_scales[c] / 8) * 8; the image is uploaded once, each member
+ * pre-processes all its boxes in one launch, then ONE grouped forward; per member c the maps (n x its canvas's map) and pose[c]
+ * (n*5*J doubles, image coordinates).  Arrays of outputs have one entry per member, as dc_group_forward_images.  The same errors
+ * as dc_net_forward_boxes, checked for every member before any device work; n = 0 does nothing.                             */
+int dc_group_forward_boxes(dc_group* group, const unsigned char* image, int height, int width, int is_device, const int* boxes,
+                           const double* scales, int n, const double* pyramid_scales, int canvas_h, int canvas_w, float* const* prob,
+                           float* const* loc_pred, float* const* next_pred, double* const* pose, void* stream);
 /* the merged plan of the last forward: one line per launch ("conv_gemm_mp<tile> problems=.. grid=.." or "member c: <kernel>");
  * NULL + dc_last_error() before the first forward; pointer valid until the next call on this group                            */
 const char* dc_group_plan_text(dc_group* group);
