@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "lib", "libdeepcut_hip.so")
 SOURCES = ["formats.cpp", "hdf5_reader.cpp", "runtime.cpp", "net_init.cpp", "net_lower.cpp", "net_tune.cpp", "net_run.cpp", "net_image.cpp",
            "net_group.cpp", "streams.cpp", "multi_gpu.cpp", "c_api.cpp", "kernels.hip", "wino_f16.hip", "stream1x1.hip", "stem_f16.hip", "stream1x1_f32.hip"]
-HEADERS = ["formats.h", "net.h", "net_internal.h", "kernels.h", os.path.join("..", "..", "include", "deepcut_hip.h")]
+HEADERS = ["formats.h", "net.h", "net_internal.h", "kernels.h", "kernel_prims.h", os.path.join("..", "..", "include", "deepcut_hip.h")]
 
 
 KERNEL_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-inline-asm"]
@@ -23,9 +23,9 @@ ASM = os.path.join(HERE, "lib", "kernels.gfx950.s")
 
 
 def _asm_key():
-    """What the device assembly of kernels.hip depends on: the two sources, the flags, the compiler."""
+    """What the device assembly of kernels.hip depends on: its sources, the flags, the compiler."""
     h = hashlib.sha256()
-    for f in ("kernels.hip", "kernels.h"):
+    for f in ("kernels.hip", "kernels.h", "kernel_prims.h"):
         h.update(open(os.path.join(CSRC, f), "rb").read())
     h.update(" ".join(KERNEL_FLAGS).encode())
     h.update(_hipcc_version())

@@ -9,6 +9,10 @@ namespace dc {
 
 constexpr int kMaxTaps = 32;  // tap-validity masks are one 32-bit word per staged row
 
+// magic {multiplier, shift word} of n / d for 0 <= n < 2^31 and a divisor known on the host (the device divides with dc_fastdiv,
+// kernel_prims.h): sh = 31 + ceil(log2 d), mul = floor(2^sh / d) + 1, n / d = (n * mul) >> sh; d <= 1 sets bit 31 of the shift word
+void dc_magic(unsigned d, unsigned (&mg)[2]);
+
 // element kind of the device images (the values of DC_OPT_DTYPE): float32, float16, bfloat16.  Host tensors, the per-channel
 // affine vectors and every accumulation are float in all three.
 enum ElemKind { kElemF32 = 0, kElemF16 = 1, kElemBF16 = 2 };
@@ -175,6 +179,12 @@ int launch_conv_multi(const ConvMultiArgs& a, int variant, long grid, void* stre
 // x_rows = H, x_rowlen = W*klen); `w` is the transformed-filter image made by wino_pack_filters().  Launched as the forms
 // wino_f23 and wino_f23_w16 (conv_form below).
 bool wino_eligible(const ConvGemmParams& p);   // geometry / type the kernel takes
+// what both Winograd forms take: a 3x3 "same" convolution, stride 1, dilation d = pad (1..4) along y and x, dense NHWC rows of klen
+// channels (each form adds its element kind, channel multiples, output alignment and 2 GiB limits)
+bool wino_same3x3(const ConvGemmParams& p);
+// `p` as a Winograd form launches it over `grid` workgroups: the per-XCD map (DC_XCD_MAP, grids of 16 or more), the geometry of the
+// bty x btx tile blocks and the magic numbers of the kernel's block-index divisions, the first one by blocks_per_wg blocks at a time
+ConvGemmParams wino_launch_params(const ConvGemmParams& p, long grid, int bty, int btx, int blocks_per_wg);
 long wino_grid(const ConvGemmParams& p);
 size_t wino_packed_floats(int Cout, int Cin);
 // g: [Cout][Cin][3][3] (Caffe order) -> U = G g G^T per (co, ci), laid out so that one wave's B-operand load is 1 KB

@@ -15,94 +15,14 @@
 #include <type_traits>
 #include <vector>
 
+#include "kernel_prims.h"
 #include "kernels.h"
 
 namespace dc {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 // ------------------------------------------------------------------------------------------------
 // gather-GEMM convolution
 // ------------------------------------------------------------------------------------------------
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-// Buffer addressing (V# descriptors): address = base + voffset(VGPR) + soffset(SGPR); an access whose
-// voffset is >= num_records returns 0 / is dropped.  This keeps the K loop almost free of VALU work —
-// which matters because on gfx950 the fp32 MFMA shares the SIMD's fp32 datapath: every VALU
-// instruction issued between MFMAs is paid IN ADDITION to them (tools/probes/mfma_probe.hip:
-// 143 TF/s bare, 91 TF/s with 8 VALU per MFMA, one or two waves per SIMD alike).
-//   * per-thread voffsets are loop invariant, the per-tile displacement (tap, channel block) is uniform
-//     and travels in soffset (SALU);
-//   * zero padding = out-of-range voffset (one v_cndmask per load from a precomputed tap-validity mask).
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t dc_rsrc(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
-}
-__device__ __forceinline__ f32x4 dc_bload4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-constexpr unsigned kOOB = 0x80000000u;  // > any tensor size: hardware returns 0
-// n / d for 0 <= n < 2^31 with host-computed magic {mul, shift}: 2 VALU instead of the ~25 of a runtime division
-__device__ __forceinline__ int dc_fastdiv(int n, const unsigned (&mg)[2]) {
-  return (mg[1] >> 31) ? n : (int)(__umulhi((unsigned)n, mg[0]) >> (mg[1] & 31));  // bit 31 of the shift word: d == 1
-}
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// LDS-DMA (`buffer_load_dwordx4 ... lds`): 64 lanes x 16 bytes travel from global memory straight into LDS, no VGPRs and
-// no ds_write.  The LDS destination is M0 + 16*lane (lane-linear, 1 KiB per wave instruction); the SOURCE address is per
-// lane (V# base + voffset + soffset), so a swizzled LDS image is made by permuting which 16-byte chunk each lane
-// fetches.  An out-of-range voffset stores zeros (the zero padding of the gather keeps working unchanged).
-// Written as inline asm on purpose: through the builtin the compiler knows that LDS is written behind its back and
-// makes every later ds_read wait for vmcnt(0) — the pipeline below keeps 1-2 tiles in flight across its barriers and
-// counts vmcnt itself.  (M0 is written in the same statement that reads it; the compiler does not use M0 on this path.)
-#pragma clang diagnostic ignored "-Winline-asm"
-__device__ __forceinline__ i32x4 dc_rsrc_words(const void* p) {
-  const unsigned long long a = (unsigned long long)p;
-  return i32x4{(int)(unsigned)a, (int)((a >> 32) & 0xffffu), 0x7fffffff, 0x00020000};
-}
-__device__ __forceinline__ void dc_dma16(i32x4 rs, unsigned lds, unsigned voff, unsigned soff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lds), "v"(voff), "s"(rs), "s"(soff)
-               : "memory", "m0");
-}
-// a 4-byte buffer load the compiler does not track (no s_waitcnt of its own): the caller's counted vmcnt covers it
-__device__ __forceinline__ float dc_load_f32_untracked(i32x4 rs, unsigned voff) {
-  float v;
-  // s_nop: the hazard recogniser does not look inside inline asm, and "VALU writes SGPR -> VMEM reads that SGPR" needs 5
-  // wait states (a descriptor restored from an SGPR spill by v_readlane right in front of this statement read stale
-  // registers in the round-3 walking-tile experiment: wild addresses).  tools/check_asm_hazards.py scans for the pattern.
-  asm volatile("s_nop 4\n\tbuffer_load_dword %0, %1, %2, 0 offen" : "=v"(v) : "v"(voff), "s"(rs) : "memory");
-  return v;
-}
-// lanes 32..63 of lo[e] <-> lanes 0..31 of hi[e], e = 0..3 (inline asm: this compiler's builtin returns the first result
-// twice; one s_nop for the four: the VALU instructions that produced the operands need two wait states before a permlane)
-__device__ __forceinline__ void dc_permlane32_swap4(float (&lo)[4], float (&hi)[4]) {
-  asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %4\n\tv_permlane32_swap_b32 %1, %5\n\tv_permlane32_swap_b32 %2, %6\n\tv_permlane32_swap_b32 %3, %7"
-      : "+v"(lo[0]), "+v"(lo[1]), "+v"(lo[2]), "+v"(lo[3]), "+v"(hi[0]), "+v"(hi[1]), "+v"(hi[2]), "+v"(hi[3]));
-}
-// float32 + the low / high half of a packed float16 pair, exactly rounded once (v_fma_mix_f32 h * 1.0 + f): the conversion folded into
-// the add.  Plain (non-volatile) asm: pure functions of their inputs.
-__device__ __forceinline__ float dc_add_half_lo(unsigned h2, float f) {
-  float d;
-  asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(d) : "v"(h2), "v"(f));
-  return d;
-}
-__device__ __forceinline__ float dc_add_half_hi(unsigned h2, float f) {
-  float d;
-  asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(h2), "v"(f));
-  return d;
-}
-template <int N>
-__device__ __forceinline__ void dc_wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-// own LDS traffic retired, then the workgroup barrier (a raw s_barrier: __syncthreads() would drain vmcnt too)
-__device__ __forceinline__ void dc_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // Kernel arguments are fetched lazily, cache line by cache line, wherever the compiler first needs a field: the gather-GEMM
 // touched four lines of its 632-byte block at four different points of its prologue, each first touch a scalar-cache miss
@@ -1133,8 +1053,7 @@ __global__ __launch_bounds__(WR* WC* WK * 64, (DMA && WR * WC * WK == 4) ? 2 : 1
   stamp(7);
 }
 
-// magic {multiplier, shift word} for n / d, 0 <= n < 2^31 (see dc_fastdiv): sh = 31 + ceil(log2 d), mul = floor(2^sh / d) + 1
-static void dc_magic(unsigned d, unsigned (&mg)[2]) {
+void dc_magic(unsigned d, unsigned (&mg)[2]) {
   if (d <= 1) {
     mg[0] = 0;
     mg[1] = 0x80000000u;
@@ -1343,116 +1262,135 @@ long conv_grid(const ConvGemmParams& p, int variant) {
   return tm * tn;
 }
 
+// ---- gather-GEMM launch preparation, shared by the single-problem, multi-class and multi-problem launches
+
+// the switches of the launches (on unless set to 0), each read once, at its first use
+static int env_on(const char* name) { return getenv(name) ? atoi(getenv(name)) : 1; }
+static bool xcd_map_on() {  // DC_XCD_MAP: the per-XCD tile map of single-problem launches and of the Winograd forms
+  static const int on = env_on("DC_XCD_MAP");
+  return on != 0;
+}
+static bool dense_on() {  // DC_DENSE: dense_x / dense_y
+  static const int on = env_on("DC_DENSE");
+  return on != 0;
+}
+static bool wide_epi_on() {  // DC_WIDE_EPI: the float16 epilogue through LDS
+  static const int on = env_on("DC_WIDE_EPI");
+  return on != 0;
+}
+
+// buffer (V#) addressing carries 32-bit byte offsets: every tensor of a launch must stay below 2 GiB
+static constexpr double k2GiB = 2147483647.0;
+static bool images_fit(double es, double nb, long x_img_stride, long y_img_stride) {  // input and output of nb images, es-byte elements
+  return es * nb * (double)x_img_stride < k2GiB && es * nb * (double)y_img_stride < k2GiB;
+}
+// most negative tap displacement: one of the four corners of the arithmetic grid (t: the launch, a class or a problem)
+template <class T>
+static int tap_bias(const T& t, int x_row_stride) {
+  int bias = 0;
+  for (int ty : {0, t.nty - 1})
+    for (int tx : {0, t.ntx - 1}) bias = std::min(bias, (t.dy0 + ty * t.ddy) * x_row_stride + t.x0 + tx * t.ddx);
+  return bias;
+}
+// the output-pixel divisions and the m tiles of the launch, a class or a problem
+template <class T>
+static void set_m_tiles(T& t, int BM) {
+  dc_magic((unsigned)(t.OH * t.OW), t.div_ohw);
+  dc_magic((unsigned)t.OW, t.div_ow);
+  t.tiles_m = (t.M + BM - 1) / BM;
+}
+// the output (and shortcut) of one tensor takes 16-byte vectors: strides in whole vectors of es-byte elements, aligned bases
+template <class T>
+static bool out_vec16(const T& t, long es) {
+  return (t.y_pix_stride * es) % 16 == 0 && (t.y_row_stride * es) % 16 == 0 && (t.y_img_stride * es) % 16 == 0 && ((uintptr_t)t.y & 15) == 0 &&
+         (!t.resid || ((uintptr_t)t.resid & 15) == 0);
+}
+// vec_epi and wide_epi of a launch whose every tensor passes out_vec16 (vec).  wide_epi (float16) asks for Cout and the output strides
+// in multiples of 8 halves: for 2-byte elements exactly what vec_epi asks
+static void set_epi(ConvGemmParams& p, bool vec) {
+  p.vec_epi = vec && (p.Cout * (long)p.esize) % 16 == 0 && p.sigmoid_ch == 0;
+  p.wide_epi = wide_epi_on() && p.esize == 2 && p.vec_epi;
+}
+// dense_x / dense_y (ConvGemmParams) of the launch or a problem; sy, sx and klen are the layer's
+template <class T>
+static bool dense_x_of(const T& t, const ConvGemmParams& p) {
+  return dense_on() && t.nty == 1 && t.ntx == 1 && t.dy0 == 0 && t.x0 == 0 && p.sy == 1 && t.x_rows == t.OH && t.x_row_stride == t.OW * p.sx &&
+         t.x_img_stride == (long)t.OH * t.x_row_stride && t.x_rowlen >= (t.OW - 1) * p.sx + p.klen;
+}
+template <class T>
+static bool dense_y_of(const T& t) {
+  return dense_on() && t.y_row_stride == t.OW * t.y_pix_stride && t.y_img_stride == (long)t.OH * t.y_row_stride;
+}
+// XCD arrangement gx x gy of a multi-class or multi-problem launch (rows[c]: m tiles of class / problem c) minimising what one L2 has to
+// fetch (its share of the filters + its share of the pixels): sets p.mc_lgx, returns the grid (8 x the longest walk of an XCD) or 0
+static long mc_xcd_grid(ConvGemmParams& p, const int* rows, int n, long tn, double wtot, double atot) {
+  long blk = 0, total = 0;
+  double best = 1e300;
+  for (int c = 0; c < n; ++c) total += rows[c] * tn;
+  for (int lgx = 0; lgx <= 3; ++lgx) {
+    const int gx = 1 << lgx, gy = 8 >> lgx;
+    if (gx > tn) continue;
+    long longest = 0;
+    for (int xq = 0; xq < 8; ++xq) {
+      const int qx = xq & (gx - 1), qy = xq >> lgx;
+      const long ncnt = ((tn * (qx + 1)) >> lgx) - ((tn * qx) >> lgx);
+      long cnt = 0;
+      for (int c = 0; c < n; ++c) cnt += ((((long)rows[c] * (qy + 1)) >> (3 - lgx)) - (((long)rows[c] * qy) >> (3 - lgx))) * ncnt;
+      longest = std::max(longest, cnt);
+    }
+    const double cost = (wtot / gx + atot / gy) * (1.0 + 0.02 * (longest * 8 - total) / (double)std::max(total, 1L));
+    if (cost < best) best = cost, p.mc_lgx = lgx, blk = longest * 8;
+  }
+  return blk;
+}
+
 int launch_conv_gemm(const ConvGemmParams& p_in, int variant, void* stream) {
   if (!dc_variant_ok(variant)) return (int)hipErrorInvalidValue;
   const VariantEntry& e = entry_of(variant);
   ConvGemmParams p = p_in;
   if (p.esize != e.esize || (p.ekind == kElemBF16) != is_bf16_variant(variant)) return (int)hipErrorInvalidValue;
-  static const int wide_epi = getenv("DC_WIDE_EPI") ? atoi(getenv("DC_WIDE_EPI")) : 1;
-  p.wide_epi = wide_epi && p.esize == 2 && p.ncls <= 1 && p.Cout % 8 == 0 && p.y_pix_stride % 8 == 0 && p.y_row_stride % 8 == 0 &&
-               p.y_img_stride % 8 == 0 && p.sigmoid_ch == 0 && ((uintptr_t)p.y & 15) == 0 && (!p.resid || ((uintptr_t)p.resid & 15) == 0);
-  {
-    const long es = p.esize;
-    p.vec_epi = p.ncls <= 1 && (p.Cout * es) % 16 == 0 && (p.y_pix_stride * es) % 16 == 0 && (p.y_row_stride * es) % 16 == 0 &&
-                (p.y_img_stride * es) % 16 == 0 && p.sigmoid_ch == 0 && ((uintptr_t)p.y & 15) == 0 && (!p.resid || ((uintptr_t)p.resid & 15) == 0);
-    static const int dense = getenv("DC_DENSE") ? atoi(getenv("DC_DENSE")) : 1;
-    p.dense_x = dense && p.ncls <= 1 && p.nty == 1 && p.ntx == 1 && p.dy0 == 0 && p.x0 == 0 && p.sy == 1 && p.x_rows == p.OH &&
-                p.x_row_stride == p.OW * p.sx && p.x_img_stride == (long)p.OH * p.x_row_stride && p.x_rowlen >= (p.OW - 1) * p.sx + p.klen;
-    p.dense_y = dense && p.ncls <= 1 && p.y_row_stride == p.OW * p.y_pix_stride && p.y_img_stride == (long)p.OH * p.y_row_stride;
-  }
-  // n / d magic: sh = 31 + ceil(log2 d), mul = floor(2^sh / d) + 1, n/d = (n*mul) >> sh for 0 <= n < 2^31
-  auto magic_of = [](unsigned d, unsigned (&mg)[2]) {
-    if (d <= 1) {
-      mg[0] = 0;
-      mg[1] = 0x80000000u;
-      return;
-    }
-    int l = 0;
-    while ((1ull << l) < d) ++l;
-    const int sh = 31 + l;
-    const unsigned long long q = (((unsigned __int128)1) << sh) / d;
-    mg[0] = (unsigned)(q + 1);
-    mg[1] = (unsigned)(sh - 32);
-  };
+  const long tn = (p.Cout + e.v.BN - 1) / e.v.BN;
+  const int nt = e.v.WR * e.v.WC * e.v.WK * 64;
   if (p.ncls > 1) {
     // multi-class launch: the residue classes of a strided deconvolution as consecutive ranges of ONE grid
-    if (p.ncls > kMaxClasses || !e.kernel_mc) return (int)hipErrorInvalidValue;
-    const double lim = 2147483647.0;
-    if ((double)e.esize * p.NB * (double)p.x_img_stride >= lim || (double)e.esize * p.NB * (double)p.y_img_stride >= lim)
-      return (int)hipErrorInvalidValue;
-    const long tn = (p.Cout + e.v.BN - 1) / e.v.BN;
+    if (p.ncls > kMaxClasses || !e.kernel_mc || !images_fit(e.esize, p.NB, p.x_img_stride, p.y_img_stride)) return (int)hipErrorInvalidValue;
     double wtot = 0, atot = 0;
+    int rows[kMaxClasses];
     for (int c = 0; c < p.ncls; ++c) {
       ConvClass& q = p.cls[c];
       const int ntaps = q.nty * q.ntx;
       if (ntaps < 1 || ntaps > kMaxTaps || p.klen % e.BK != 0 || q.Ktot != ntaps * p.klen || q.M <= 0) return (int)hipErrorInvalidValue;
-      int bias = 0;
-      for (int ty : {0, q.nty - 1})
-        for (int tx : {0, q.ntx - 1}) bias = std::min(bias, (q.dy0 + ty * q.ddy) * p.x_row_stride + q.x0 + tx * q.ddx);
-      q.x_bias = bias;
-      magic_of((unsigned)(q.OH * q.OW), q.div_ohw);
-      magic_of((unsigned)q.OW, q.div_ow);
-      q.tiles_m = (q.M + e.v.BM - 1) / e.v.BM;
+      q.x_bias = tap_bias(q, p.x_row_stride);
+      set_m_tiles(q, e.v.BM);
+      rows[c] = q.tiles_m;
       wtot += (double)e.esize * p.Cout * (double)q.Ktot;
       atot += (double)e.esize * q.M * (double)p.klen * q.nty;
     }
-    if (wtot >= lim) return (int)hipErrorInvalidValue;
+    if (wtot >= k2GiB) return (int)hipErrorInvalidValue;
+    p.wide_epi = p.vec_epi = p.dense_x = p.dense_y = 0;
     p.tiles_n = (int)tn;
-    magic_of((unsigned)tn, p.div_tn);
+    dc_magic((unsigned)tn, p.div_tn);
     p.xcd_on = 0;
-    // XCD arrangement gx x gy minimising what one L2 has to fetch (its share of the filters + its share of the pixels)
-    long blk = 0;
-    {
-      double best = 1e300;
-      for (int lgx = 0; lgx <= 3; ++lgx) {
-        const int gx = 1 << lgx, gy = 8 >> lgx;
-        if (gx > tn) continue;
-        long longest = 0;
-        for (int xq = 0; xq < 8; ++xq) {
-          const int qx = xq & (gx - 1), qy = xq >> lgx;
-          const long ncnt = ((tn * (qx + 1)) >> lgx) - ((tn * qx) >> lgx);
-          long cnt = 0;
-          for (int c = 0; c < p.ncls; ++c) cnt += ((((long)p.cls[c].tiles_m * (qy + 1)) >> (3 - lgx)) - (((long)p.cls[c].tiles_m * qy) >> (3 - lgx))) * ncnt;
-          longest = std::max(longest, cnt);
-        }
-        long total = 0;
-        for (int c = 0; c < p.ncls; ++c) total += p.cls[c].tiles_m * tn;
-        const double cost = (wtot / gx + atot / gy) * (1.0 + 0.02 * (longest * 8 - total) / (double)std::max(total, 1L));
-        if (cost < best) best = cost, p.mc_lgx = lgx, blk = longest * 8;
-      }
-    }
+    const long blk = mc_xcd_grid(p, rows, p.ncls, tn, wtot, atot);
     if (blk <= 0 || blk > 0x7fffffffL) return (int)hipErrorInvalidValue;
-    const int nt = e.v.WR * e.v.WC * e.v.WK * 64;
     hipLaunchKernelGGL(e.kernel_mc, dim3((unsigned)blk), dim3(nt), 0, (hipStream_t)stream, p);
     return (int)hipGetLastError();
   }
   const int ntaps = p.nty * p.ntx;
   if (ntaps < 1 || ntaps > kMaxTaps || p.klen % e.BK != 0 || p.Ktot != ntaps * p.klen) return (int)hipErrorInvalidValue;
-  // buffer (V#) addressing carries 32-bit byte offsets: every tensor of a launch must stay below 2 GiB
-  {
-    const double lim = 2147483647.0;
-    const double xb = (double)e.esize * (double)p.NB * (double)p.x_img_stride;
-    const double yb = (double)e.esize * ((double)p.NB * (double)p.y_img_stride);
-    const double wb = (double)e.esize * (double)p.Cout * (double)p.Ktot;
-    if (xb >= lim || yb >= lim || wb >= lim) return (int)hipErrorInvalidValue;
-  }
-  int bias = 0;  // most negative tap displacement: one of the four corners of the arithmetic grid
-  for (int ty : {0, p.nty - 1})
-    for (int tx : {0, p.ntx - 1})
-      bias = std::min(bias, (p.dy0 + ty * p.ddy) * p.x_row_stride + p.x0 + tx * p.ddx);
-  p.x_bias = bias;
+  if (!images_fit(e.esize, p.NB, p.x_img_stride, p.y_img_stride) || (double)e.esize * p.Cout * (double)p.Ktot >= k2GiB) return (int)hipErrorInvalidValue;
+  set_epi(p, out_vec16(p, p.esize));
+  p.dense_x = dense_x_of(p, p);
+  p.dense_y = dense_y_of(p);
+  p.x_bias = tap_bias(p, p.x_row_stride);
   long grid = conv_grid(p, variant);
   if (grid <= 0) return 0;
-  auto& magic = magic_of;
-  const long tn = (p.Cout + e.v.BN - 1) / e.v.BN, tm = (p.M + e.v.BM - 1) / e.v.BM;
   p.tiles_n = (int)tn;
-  magic((unsigned)tn, p.div_tn);
-  magic((unsigned)(p.OH * p.OW), p.div_ohw);
-  magic((unsigned)p.OW, p.div_ow);
-  static const int xcd_map = getenv("DC_XCD_MAP") ? atoi(getenv("DC_XCD_MAP")) : 1;
+  dc_magic((unsigned)tn, p.div_tn);
+  set_m_tiles(p, e.v.BM);
+  const long tm = p.tiles_m;
   p.xcd_on = 0;
-  p.tiles_m = (int)tm;
-  if (xcd_map && grid >= 16) {
+  if (xcd_map_on() && grid >= 16) {
     // Blocks are observed to land on XCD (blockIdx % 8), each with its own 4 MB L2.  Cut the tile grid into 8
     // rectangles (gx along n, 8/gx along m) minimising the bytes an L2 must fetch for its rectangle
     // (filters of its n-range + pixels of its m-range); XCD q walks rectangle q.  A locality hint only.
@@ -1475,13 +1413,12 @@ int launch_conv_gemm(const ConvGemmParams& p_in, int variant, void* stream) {
     if (best_lgx >= 0) {
       p.xcd_lgx = best_lgx;
       const unsigned w0 = (unsigned)(tn >> best_lgx);
-      magic(std::max(w0, 1u), p.div_rw[0]);
-      magic(w0 + 1, p.div_rw[1]);
+      dc_magic(std::max(w0, 1u), p.div_rw[0]);
+      dc_magic(w0 + 1, p.div_rw[1]);
       p.xcd_on = 1;
       grid = best_grid;
     }
   }
-  const int nt = e.v.WR * e.v.WC * e.v.WK * 64;
   hipLaunchKernelGGL(e.kernel, dim3((unsigned)grid), dim3(nt), 0, (hipStream_t)stream, p);
   return (int)hipGetLastError();
 }
@@ -1499,74 +1436,37 @@ long prepare_conv_multi(ConvGemmParams& p, ConvMultiTable& tb, int nprob, int va
   const VariantEntry& e = entry_of(variant);
   if (!e.kernel_mp || p.esize != e.esize || (p.ekind == kElemBF16) != is_bf16_variant(variant) || p.klen % e.BK != 0) return -1;
   const long es = p.esize;
-  const double lim = 2147483647.0;
-  static const int dense = getenv("DC_DENSE") ? atoi(getenv("DC_DENSE")) : 1;
   const long tn = (p.Cout + e.v.BN - 1) / e.v.BN;
-  bool vec = (p.Cout * es) % 16 == 0 && p.sigmoid_ch == 0;
-  double wtot = 0, atot = 0;
+  bool vec = true;
+  double atot = 0;
   long w_lo = 0, w_hi = 0;
+  int rows[kMaxProblems];
   for (int c = 0; c < nprob; ++c) {
     ConvProblem& q = tb.prob[c];
     const int ntaps = q.nty * q.ntx;
     if (ntaps < 1 || ntaps > kMaxTaps || q.Ktot != ntaps * p.klen || q.M <= 0 || q.NB <= 0) return -1;
-    if ((double)es * q.NB * (double)q.x_img_stride >= lim || (double)es * q.NB * (double)q.y_img_stride >= lim) return -1;
+    if (!images_fit(es, q.NB, q.x_img_stride, q.y_img_stride)) return -1;
     if ((q.resid != nullptr) != (tb.prob[0].resid != nullptr)) return -1;
-    int bias = 0;
-    for (int ty : {0, q.nty - 1})
-      for (int tx : {0, q.ntx - 1}) bias = std::min(bias, (q.dy0 + ty * q.ddy) * q.x_row_stride + q.x0 + tx * q.ddx);
-    q.x_bias = bias;
-    dc_magic((unsigned)(q.OH * q.OW), q.div_ohw);
-    dc_magic((unsigned)q.OW, q.div_ow);
-    q.tiles_m = (q.M + e.v.BM - 1) / e.v.BM;
-    q.dense_x = dense && q.nty == 1 && q.ntx == 1 && q.dy0 == 0 && q.x0 == 0 && p.sy == 1 && q.x_rows == q.OH && q.x_row_stride == q.OW * p.sx &&
-                q.x_img_stride == (long)q.OH * q.x_row_stride && q.x_rowlen >= (q.OW - 1) * p.sx + p.klen;
-    q.dense_y = dense && q.y_row_stride == q.OW * q.y_pix_stride && q.y_img_stride == (long)q.OH * q.y_row_stride;
-    vec = vec && (q.y_pix_stride * es) % 16 == 0 && (q.y_row_stride * es) % 16 == 0 && (q.y_img_stride * es) % 16 == 0 && ((uintptr_t)q.y & 15) == 0 &&
-          (!q.resid || ((uintptr_t)q.resid & 15) == 0);
+    q.x_bias = tap_bias(q, q.x_row_stride);
+    set_m_tiles(q, e.v.BM);
+    rows[c] = q.tiles_m;
+    q.dense_x = dense_x_of(q, p);
+    q.dense_y = dense_y_of(q);
+    vec = vec && out_vec16(q, es);
     w_lo = std::min(w_lo, q.w_off);
     w_hi = std::max(w_hi, q.w_off + (long)p.Cout * q.Ktot);
     atot += (double)es * q.M * (double)p.klen * q.nty;
   }
-  wtot = (double)es * (double)(w_hi - w_lo);
-  if (wtot >= lim) return -1;
+  const double wtot = (double)es * (double)(w_hi - w_lo);
+  if (wtot >= k2GiB) return -1;
   p.nprob = nprob;
   p.ncls = 0;
-  p.vec_epi = vec ? 1 : 0;
-  p.wide_epi = 0;  // (the LDS-transposed float16 epilogue addresses one tensor: the element-wise form takes its place here)
-  {
-    static const int wide_epi = getenv("DC_WIDE_EPI") ? atoi(getenv("DC_WIDE_EPI")) : 1;
-    bool w8 = wide_epi && p.esize == 2 && p.Cout % 8 == 0 && p.sigmoid_ch == 0;
-    for (int c = 0; c < nprob; ++c) {
-      const ConvProblem& q = tb.prob[c];
-      w8 = w8 && q.y_pix_stride % 8 == 0 && q.y_row_stride % 8 == 0 && q.y_img_stride % 8 == 0 && ((uintptr_t)q.y & 15) == 0 &&
-           (!q.resid || ((uintptr_t)q.resid & 15) == 0);
-    }
-    p.wide_epi = w8 ? 1 : 0;
-  }
+  set_epi(p, vec);
   p.dense_x = p.dense_y = 0;
   p.xcd_on = 0;
   p.tiles_n = (int)tn;
   dc_magic((unsigned)tn, p.div_tn);
-  // XCD arrangement gx x gy minimising what one L2 has to fetch (its share of the filters + its share of the pixels)
-  long blk = 0;
-  double best = 1e300;
-  long total = 0;
-  for (int c = 0; c < nprob; ++c) total += tb.prob[c].tiles_m * tn;
-  for (int lgx = 0; lgx <= 3; ++lgx) {
-    const int gx = 1 << lgx;
-    if (gx > tn) continue;
-    long longest = 0;
-    for (int xq = 0; xq < 8; ++xq) {
-      const int qx = xq & (gx - 1), qy = xq >> lgx;
-      const long ncnt = ((tn * (qx + 1)) >> lgx) - ((tn * qx) >> lgx);
-      long cnt = 0;
-      for (int c = 0; c < nprob; ++c)
-        cnt += ((((long)tb.prob[c].tiles_m * (qy + 1)) >> (3 - lgx)) - (((long)tb.prob[c].tiles_m * qy) >> (3 - lgx))) * ncnt;
-      longest = std::max(longest, cnt);
-    }
-    const double cost = (wtot / gx + atot / (8 >> lgx)) * (1.0 + 0.02 * (longest * 8 - total) / (double)std::max(total, 1L));
-    if (cost < best) best = cost, p.mc_lgx = lgx, blk = longest * 8;
-  }
+  const long blk = mc_xcd_grid(p, rows, nprob, tn, wtot, atot);
   if (blk <= 0 || blk > 0x7fffffffL) return -1;
   {
     const int lgx = p.mc_lgx, lgy = 3 - lgx;
@@ -1871,14 +1771,35 @@ __global__ __launch_bounds__(WNTH * NG, 4) void wino_f23_kernel(const ConvGemmPa
   stamp(7);
 }
 
-bool wino_eligible(const ConvGemmParams& p) {
+bool wino_same3x3(const ConvGemmParams& p) {
   const int d = p.ddy;  // dilation (1 or more), the same along x and y, with pad = dilation ("same" convolution)
-  if (p.esize != 4 || p.nty != 3 || p.ntx != 3 || p.sy != 1 || d < 1 || d > 4 || p.dy0 != -d) return false;
+  if (p.nty != 3 || p.ntx != 3 || p.sy != 1 || d < 1 || d > 4 || p.dy0 != -d) return false;
   const int C = p.klen;
-  if (C <= 0 || C % WKC != 0 || p.Cout % WBN != 0 || p.sigmoid_ch != 0) return false;
-  if (p.sx != C || p.ddx != d * C || p.x0 != -d * C) return false;           // stride 1, dilation d, pad d along x
-  if (p.x_rowlen % C != 0 || p.x_row_stride != p.x_rowlen) return false;     // dense NHWC rows of C channels
-  if (p.OH != p.x_rows || p.OW != p.x_rowlen / C) return false;              // "same" convolution
+  if (C <= 0) return false;
+  if (p.sx != C || p.ddx != d * C || p.x0 != -d * C) return false;        // stride 1, dilation d, pad d along x
+  if (p.x_rowlen % C != 0 || p.x_row_stride != p.x_rowlen) return false;  // dense NHWC rows of C channels
+  return p.OH == p.x_rows && p.OW == p.x_rowlen / C;                      // "same" convolution
+}
+
+ConvGemmParams wino_launch_params(const ConvGemmParams& p, long grid, int bty, int btx, int blocks_per_wg) {
+  ConvGemmParams q = p;
+  q.xcd_on = xcd_map_on() && grid >= 16;
+  const int d = p.ddy;
+  q.w_TY = ((p.OH + d - 1) / d + 1) / 2, q.w_TX = ((p.OW + d - 1) / d + 1) / 2;
+  q.w_NBY = (q.w_TY + bty - 1) / bty, q.w_NBX = (q.w_TX + btx - 1) / btx;
+  q.w_nblk = p.NB * d * d * q.w_NBY * q.w_NBX;
+  dc_magic((unsigned)((q.w_nblk + blocks_per_wg - 1) / blocks_per_wg), q.w_div_nblk);
+  dc_magic((unsigned)(q.w_NBY * q.w_NBX), q.w_div_nbyx);
+  dc_magic((unsigned)(d * d), q.w_div_dd);
+  dc_magic((unsigned)d, q.w_div_d);
+  dc_magic((unsigned)q.w_NBX, q.w_div_nbx);
+  return q;
+}
+
+bool wino_eligible(const ConvGemmParams& p) {
+  if (p.esize != 4 || !wino_same3x3(p)) return false;
+  const int C = p.klen;
+  if (C % WKC != 0 || p.Cout % WBN != 0 || p.sigmoid_ch != 0) return false;
   // 32-bit byte offsets (buffer addressing): one image of the input and the packed filter image stay below 2 GiB
   if ((long long)p.x_rows * p.x_row_stride * 4 >= 0x7fffffffLL || (long long)wino_packed_floats(p.Cout, C) * 4 >= 0x7fffffffLL) return false;
   return true;
@@ -1917,21 +1838,7 @@ static int launch_wino_f23(const ConvGemmParams& p, void* stream) {
   const long grid = wino_grid(p);
   if (grid <= 0) return 0;
   if (grid > 0x7fffffffL) return (int)hipErrorInvalidValue;
-  ConvGemmParams q = p;
-  static const int xcd_map = getenv("DC_XCD_MAP") ? atoi(getenv("DC_XCD_MAP")) : 1;
-  q.xcd_on = xcd_map && grid >= 16;
-  {
-    const int d = p.ddy;
-    q.w_TY = ((p.OH + d - 1) / d + 1) / 2, q.w_TX = ((p.OW + d - 1) / d + 1) / 2;
-    q.w_NBY = (q.w_TY + WBTY - 1) / WBTY, q.w_NBX = (q.w_TX + WBTX - 1) / WBTX;
-    q.w_nblk = p.NB * d * d * q.w_NBY * q.w_NBX;
-    dc_magic((unsigned)q.w_nblk, q.w_div_nblk);
-    dc_magic((unsigned)(q.w_NBY * q.w_NBX), q.w_div_nbyx);
-    dc_magic((unsigned)(d * d), q.w_div_dd);
-    dc_magic((unsigned)d, q.w_div_d);
-    dc_magic((unsigned)q.w_NBX, q.w_div_nbx);
-  }
-  hipLaunchKernelGGL(wino_f23_kernel<NG>, dim3((unsigned)grid), dim3(NG * WNTH), 0, (hipStream_t)stream, q);
+  hipLaunchKernelGGL(wino_f23_kernel<NG>, dim3((unsigned)grid), dim3(NG * WNTH), 0, (hipStream_t)stream, wino_launch_params(p, grid, WBTY, WBTX, 1));
   return (int)hipGetLastError();
 }
 

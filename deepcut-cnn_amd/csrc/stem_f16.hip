@@ -19,21 +19,11 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "kernel_prims.h"
 #include "kernels.h"
 
 namespace dc {
 namespace {
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
-constexpr unsigned kOOBt = 0x80000000u;
-#pragma clang diagnostic ignored "-Winline-asm"
 
 constexpr int TRH = 8, TCW = 64;                 // conv rows x conv columns of a workgroup's tile
 constexpr int BROWS = 2 * TRH + 5;               // image rows of its band
@@ -55,17 +45,6 @@ struct StemArgs {
   unsigned div_tx[2], div_txy[2];
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t t_rsrc(const void* p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7fffffff, 0x00020000);
-}
-__device__ __forceinline__ int t_fastdiv(int n, const unsigned (&mg)[2]) {
-  return (mg[1] >> 31) ? n : (int)(__umulhi((unsigned)n, mg[0]) >> (mg[1] & 31));
-}
-__device__ __forceinline__ void t_permlane32_swap4(float (&lo)[4], float (&hi)[4]) {
-  asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %4\n\tv_permlane32_swap_b32 %1, %5\n\tv_permlane32_swap_b32 %2, %6\n\tv_permlane32_swap_b32 %3, %7"
-      : "+v"(lo[0]), "+v"(lo[1]), "+v"(lo[2]), "+v"(lo[3]), "+v"(hi[0]), "+v"(hi[1]), "+v"(hi[2]), "+v"(hi[3]));
-}
-
 template <bool RELU>
 __global__ __launch_bounds__(256, 2) void stem7x7_kernel(const StemArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[BANDB + 4 * SOBUF + 2 * 64 * 4];
@@ -75,14 +54,14 @@ __global__ __launch_bounds__(256, 2) void stem7x7_kernel(const StemArgs a) {
   const int p32 = lane & 31, h = lane >> 5;
   // tile: image n, conv rows [r0, r0 + TRH), conv columns [c0, c0 + TCW)
   const int bx = blockIdx.x;
-  const int n = t_fastdiv(bx, a.div_txy), rem = bx - n * a.tiles_x * a.tiles_y;
-  const int ty = t_fastdiv(rem, a.div_tx), tx = rem - ty * a.tiles_x;
+  const int n = dc_fastdiv(bx, a.div_txy), rem = bx - n * a.tiles_x * a.tiles_y;
+  const int ty = dc_fastdiv(rem, a.div_tx), tx = rem - ty * a.tiles_x;
   const int r0 = ty * TRH, c0 = tx * TCW;
 
   // ---- filters: registers (A operand: rows = channels), [fragment][kernel row][K step]
   u32x4 wreg[2][7][2];
   {
-    const __amdgpu_buffer_rsrc_t wr = t_rsrc(a.w);
+    const __amdgpu_buffer_rsrc_t wr = dc_rsrc(a.w);
 #pragma unroll
     for (int f = 0; f < 2; ++f)
 #pragma unroll
@@ -97,7 +76,7 @@ __global__ __launch_bounds__(256, 2) void stem7x7_kernel(const StemArgs a) {
   }
   // ---- the band: image rows 2 r0 - 3 ..., pixels 2 c0 - 3 ...; a pixel (8 bytes) per request, out of the image = 0
   {
-    const __amdgpu_buffer_rsrc_t xr = t_rsrc(reinterpret_cast<const _Float16*>(a.x) + (long)n * a.x_img);
+    const __amdgpu_buffer_rsrc_t xr = dc_rsrc(reinterpret_cast<const _Float16*>(a.x) + (long)n * a.x_img);
     constexpr int NPX = BROWS * BPX, NIT = (NPX + 255) / 256;
     const int iy0 = 2 * r0 - 3, ix0 = 2 * c0 - 3;
     // every request of the thread first, then the LDS writes: one memory round trip for the band instead of one per pixel
@@ -108,7 +87,7 @@ __global__ __launch_bounds__(256, 2) void stem7x7_kernel(const StemArgs a) {
       const int q = t + i * 256;
       const int br = q / BPX, bp = q - br * BPX;
       const int iy = iy0 + br, ix = ix0 + bp;
-      const unsigned off = (q < NPX && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) ? (unsigned)(iy * a.x_row + ix * a.x_pix) * 2u : kOOBt;
+      const unsigned off = (q < NPX && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) ? (unsigned)(iy * a.x_row + ix * a.x_pix) * 2u : kOOB;
       v[i] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(xr, off, 0, 0));
       dst[i] = q < NPX ? br * BROWB + bp * 8 : -1;
     }
@@ -118,7 +97,7 @@ __global__ __launch_bounds__(256, 2) void stem7x7_kernel(const StemArgs a) {
   }
   __syncthreads();
 
-  const __amdgpu_buffer_rsrc_t yr = t_rsrc(reinterpret_cast<_Float16*>(a.y) + (long)n * a.y_img);
+  const __amdgpu_buffer_rsrc_t yr = dc_rsrc(reinterpret_cast<_Float16*>(a.y) + (long)n * a.y_img);
   unsigned char* const obp = smem + BANDB + wave * SOBUF;
   const int oswz = (p32 >> 1) & 7;
   const f16x2 zero2 = {(_Float16)0.f, (_Float16)0.f};
@@ -161,7 +140,7 @@ __global__ __launch_bounds__(256, 2) void stem7x7_kernel(const StemArgs a) {
           lo[e] = acc[f][8 * j + e] * s0[e] + h0[e];
           hi[e] = acc[f][8 * j + 4 + e] * s1[e] + h1[e];
         }
-        t_permlane32_swap4(lo, hi);
+        dc_permlane32_swap4(lo, hi);
         u32x4 o;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -179,22 +158,10 @@ __global__ __launch_bounds__(256, 2) void stem7x7_kernel(const StemArgs a) {
       const int px = i * 8 + lane / 8, sl = lane % 8;
       const u32x4 v = *reinterpret_cast<const u32x4*>(obp + i * 1024 + lane * 16);
       const int oc = ocol0 + px;
-      const unsigned off = oc < a.OW ? (unsigned)(orow * a.y_row + oc * a.y_pix) * 2u + (unsigned)((sl ^ ((px >> 1) & 7)) * 16) : kOOBt;
+      const unsigned off = oc < a.OW ? (unsigned)(orow * a.y_row + oc * a.y_pix) * 2u + (unsigned)((sl ^ ((px >> 1) & 7)) * 16) : kOOB;
       __builtin_amdgcn_raw_buffer_store_b128(v, yr, off, 0, 0);
     }
   }
-}
-
-void t_magic(unsigned dv, unsigned (&mg)[2]) {  // dc_magic of kernels.hip
-  if (dv <= 1) {
-    mg[0] = 0, mg[1] = 0x80000000u;
-    return;
-  }
-  int l = 0;
-  while ((1ull << l) < dv) ++l;
-  const int sh = 31 + l;
-  const unsigned long long qq = (unsigned long long)((((unsigned __int128)1) << sh) / dv);
-  mg[0] = (unsigned)(qq + 1), mg[1] = (unsigned)(sh - 32);
 }
 }  // namespace
 
@@ -243,8 +210,8 @@ int launch_stem7x7(const ConvGemmParams& p, void* stream) {
   a.x_img = p.x_img_stride, a.y_img = p.y_img_stride;
   a.relu = p.relu;
   a.tiles_x = (p.OW + TCW - 1) / TCW, a.tiles_y = (p.OH + TRH - 1) / TRH;
-  t_magic((unsigned)a.tiles_x, a.div_tx);
-  t_magic((unsigned)(a.tiles_x * a.tiles_y), a.div_txy);
+  dc_magic((unsigned)a.tiles_x, a.div_tx);
+  dc_magic((unsigned)(a.tiles_x * a.tiles_y), a.div_txy);
   if (p.relu) hipLaunchKernelGGL(stem7x7_kernel<true>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(stem7x7_kernel<false>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
   return (int)hipGetLastError();

@@ -30,21 +30,11 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "kernel_prims.h"
 #include "kernels.h"
 
 namespace dc {
 namespace {
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
-constexpr unsigned kOOBs = 0x80000000u;
-#pragma clang diagnostic ignored "-Winline-asm"
 
 struct WsProblem {
   const void* x;
@@ -64,52 +54,6 @@ struct WsArgs {
   long long* dbg;
   WsProblem prob[kMaxProblems];
 };
-
-__device__ __forceinline__ i32x4 s_rsrc_words(const void* p) {
-  const unsigned long long a = (unsigned long long)p;
-  return i32x4{(int)(unsigned)a, (int)((a >> 32) & 0xffffu), 0x7fffffff, 0x00020000};
-}
-// (wave-uniform values that the compiler keeps in vector registers — it does behind the wave-uniform branches of the step loop — come back
-//  to scalar ones here: an "s" operand is not converted by the compiler, the assembler rejects the instruction)
-__device__ __forceinline__ unsigned s_uni(unsigned v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ i32x4 s_uni4(i32x4 r) {
-  return i32x4{__builtin_amdgcn_readfirstlane(r[0]), __builtin_amdgcn_readfirstlane(r[1]), __builtin_amdgcn_readfirstlane(r[2]), __builtin_amdgcn_readfirstlane(r[3])};
-}
-// LDS-DMA, as dc_dma16 of kernels.hip (inline asm: the compiler must not make later ds_reads wait for vmcnt(0))
-__device__ __forceinline__ void s_dma16(i32x4 rs_, unsigned lds_, unsigned voff) {
-  const i32x4 rs = s_uni4(rs_);
-  const unsigned lds = s_uni(lds_);
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(lds), "v"(voff), "s"(rs) : "memory", "m0");
-}
-// a 16-byte buffer store the compiler does not track (no s_waitcnt of its own): the counted vmcnt below covers it
-// (the s_nop behind it: a store of more than 8 bytes reads its data registers over several cycles, and the hazard recogniser, which does not
-//  look inside inline asm, let a v_or overwrite the first of them in the next cycle — one wrong dword per vector on some lanes)
-__device__ __forceinline__ void s_store16_untracked(i32x4 rs_, unsigned voff, u32x4 v) {
-  const i32x4 rs = s_uni4(rs_);
-  asm volatile("s_nop 4\n\tbuffer_store_dwordx4 %0, %1, %2, 0 offen\n\ts_nop 1" ::"v"(v), "v"(voff), "s"(rs) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void s_wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void s_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ int s_fastdiv(int n, const unsigned (&mg)[2]) {
-  return (mg[1] >> 31) ? n : (int)(__umulhi((unsigned)n, mg[0]) >> (mg[1] & 31));
-}
-__device__ __forceinline__ void s_permlane32_swap4(float (&lo)[4], float (&hi)[4]) {
-  asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %4\n\tv_permlane32_swap_b32 %1, %5\n\tv_permlane32_swap_b32 %2, %6\n\tv_permlane32_swap_b32 %3, %7"
-      : "+v"(lo[0]), "+v"(lo[1]), "+v"(lo[2]), "+v"(lo[3]), "+v"(hi[0]), "+v"(hi[1]), "+v"(hi[2]), "+v"(hi[3]));
-}
-__device__ __forceinline__ float s_add_half_lo(unsigned h2, float f) {
-  float d;
-  asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(d) : "v"(h2), "v"(f));
-  return d;
-}
-__device__ __forceinline__ float s_add_half_hi(unsigned h2, float f) {
-  float d;
-  asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(h2), "v"(f));
-  return d;
-}
 
 // KC = K / 16 (MFMA steps along the input channels), FN = 32-channel fragments per wave, NW = waves per workgroup (its channel slice is
 // NW * FN * 32 wide), D = ring stages, RES = the layer has a shortcut operand, RELU, MULTI = more than one tensor (problem) in the launch.
@@ -148,11 +92,11 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void ws1x1_kernel(const W
 
   // ---- block -> (channel slice nt, pixel-range chunk jc): XCD x = blockIdx % 8 walks chunks x, x + 8, ..., all tn slices of a chunk in a row
   const int bx = blockIdx.x, xcd = bx & 7, bi = bx >> 3;
-  const int ci = s_fastdiv(bi, a.div_tn);
+  const int ci = dc_fastdiv(bi, a.div_tn);
   const int nt = bi - ci * a.tn;
   const int jc = xcd + 8 * ci;
   if (jc >= a.J) return;
-  const int gs0 = s_fastdiv(a.S * jc, a.div_J), gs1 = s_fastdiv(a.S * (jc + 1), a.div_J);  // S * J < 2^31 (host)
+  const int gs0 = dc_fastdiv(a.S * jc, a.div_J), gs1 = dc_fastdiv(a.S * (jc + 1), a.div_J);  // S * J < 2^31 (host)
   const int n0 = nt * BN;
   const int nw0 = n0 + wave * FN * 32;  // first channel of this wave
 
@@ -163,20 +107,20 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void ws1x1_kernel(const W
   //      requests of the wave, so the wait for the first stage covers them.
   float c_sc = 1.f, c_sh = 0.f;
   {
-    const unsigned co = t < BN ? (unsigned)((n0 + t) * 4) : kOOBs;
-    if (a.scale) asm volatile("s_nop 4\n\tbuffer_load_dword %0, %1, %2, 0 offen" : "=v"(c_sc) : "v"(co), "s"(s_uni4(s_rsrc_words(a.scale))) : "memory");
-    if (a.shift) asm volatile("s_nop 4\n\tbuffer_load_dword %0, %1, %2, 0 offen" : "=v"(c_sh) : "v"(co), "s"(s_uni4(s_rsrc_words(a.shift))) : "memory");
+    const unsigned co = t < BN ? (unsigned)((n0 + t) * 4) : kOOB;
+    if (a.scale) asm volatile("s_nop 4\n\tbuffer_load_dword %0, %1, %2, 0 offen" : "=v"(c_sc) : "v"(co), "s"(dc_uni4(dc_rsrc_words(a.scale))) : "memory");
+    if (a.shift) asm volatile("s_nop 4\n\tbuffer_load_dword %0, %1, %2, 0 offen" : "=v"(c_sh) : "v"(co), "s"(dc_uni4(dc_rsrc_words(a.shift))) : "memory");
   }
   u32x4 wreg[FN][KC];
   {
-    const i32x4 wrs = s_uni4(s_rsrc_words(a.w));
+    const i32x4 wrs = dc_uni4(dc_rsrc_words(a.w));
     const int f0 = nw0 >> 5;
     const unsigned wl = (unsigned)lane * 16u;
 #pragma unroll
     for (int f = 0; f < FN; ++f)
 #pragma unroll
       for (int kk = 0; kk < KC; ++kk) {
-        const unsigned so = s_uni((unsigned)(((f0 + f) * KC + kk) * 1024));
+        const unsigned so = dc_uni((unsigned)(((f0 + f) * KC + kk) * 1024));
         asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(wreg[f][kk]) : "v"(wl), "s"(wrs), "s"(so) : "memory");
       }
   }
@@ -212,7 +156,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void ws1x1_kernel(const W
 #pragma unroll
   for (int i = 0; i < NO; ++i) orow[i] = i * RPO + lane / LPO;
   auto set_cd = [&](int pi) {
-    cd.pi = pi, cd.M = a.prob[pi].M, cd.step0 = a.prob[pi].step0, cd.pitch = a.prob[pi].sxb, cd.rs = s_rsrc_words(a.prob[pi].x);
+    cd.pi = pi, cd.M = a.prob[pi].M, cd.step0 = a.prob[pi].step0, cd.pitch = a.prob[pi].sxb, cd.rs = dc_rsrc_words(a.prob[pi].x);
     cd.next0 = MULTI && pi + 1 < a.nprob ? a.prob[pi + 1].step0 : 0x7fffffff;
 #pragma unroll
     for (int i = 0; i < NA; ++i) {
@@ -221,7 +165,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void ws1x1_kernel(const W
     }
   };
   auto set_co = [&](Cur& c, unsigned (&off)[NO], int pi, const void* base) {
-    c.pi = pi, c.M = a.prob[pi].M, c.step0 = a.prob[pi].step0, c.pitch = a.prob[pi].ypb, c.rs = s_rsrc_words(base);
+    c.pi = pi, c.M = a.prob[pi].M, c.step0 = a.prob[pi].step0, c.pitch = a.prob[pi].ypb, c.rs = dc_rsrc_words(base);
     c.next0 = MULTI && pi + 1 < a.nprob ? a.prob[pi + 1].step0 : 0x7fffffff;
 #pragma unroll
     for (int i = 0; i < NO; ++i) {
@@ -247,7 +191,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void ws1x1_kernel(const W
     const int lim = gs < gs1 ? cd.M - row0 : 0;  // rows of the step that exist
     const unsigned so = (unsigned)row0 * (unsigned)cd.pitch;
 #pragma unroll
-    for (int i = 0; i < NA; ++i) s_dma16(cd.rs, lds0 + (unsigned)(slot * STG + (wave + NW * i) * 1024), arow[i] < lim ? aoff[i] + so : kOOBs);
+    for (int i = 0; i < NA; ++i) dc_dma16_uni(cd.rs, lds0 + (unsigned)(slot * STG + (wave + NW * i) * 1024), arow[i] < lim ? aoff[i] + so : kOOB);
   };
   auto resid_step = [&](int gs, int buf) {  // NR requests: the wave's shortcut tile of step gs -> its buffer `buf`
     if (!RES) return;
@@ -259,7 +203,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void ws1x1_kernel(const W
     const int lim = gs < gs1 ? cr.M - row0 : 0;
     const unsigned so = (unsigned)row0 * (unsigned)cr.pitch;
 #pragma unroll
-    for (int i = 0; i < NO; ++i) s_dma16(cr.rs, lds0 + obuf0 + (unsigned)(buf * OBUF + i * 1024), orow[i] < lim ? roff[i] + so : kOOBs);
+    for (int i = 0; i < NO; ++i) dc_dma16_uni(cr.rs, lds0 + obuf0 + (unsigned)(buf * OBUF + i * 1024), orow[i] < lim ? roff[i] + so : kOOB);
   };
   auto stamp = [&](int sl) {  // DC_DEBUG_TIMING: per-wave phase stamps (format of conv_gemm_kernel)
     if (a.dbg && lane == 0) {
@@ -278,7 +222,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void ws1x1_kernel(const W
   resid_step(gs0 + 1, 1);
   stamp(1);
   // the first stage, and with it everything older (constants, filters), has landed; the registers of the untracked loads are tied to the wait
-  s_wait_vm<(D - 2) * NA + 2 * NR>();
+  dc_wait_vm<(D - 2) * NA + 2 * NR>();
   asm volatile("" : "+v"(c_sc), "+v"(c_sh));
 #pragma unroll
   for (int f = 0; f < FN; ++f)
@@ -290,7 +234,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void ws1x1_kernel(const W
   // its own; channel order of the accumulator registers: 8 (r >> 2) + 4 h + (r & 3))
   f32x4 csc[CREG ? 4 : 1], csh[CREG ? 4 : 1];
   if (CREG) {
-    s_lds_barrier();
+    dc_lds_barrier();
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       csc[CREG ? g : 0] = *reinterpret_cast<const f32x4*>(scl + wave * 32 + 8 * g + 4 * h);
@@ -341,8 +285,8 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void ws1x1_kernel(const W
   auto epi_pre = [&](auto wait_tag) {
     constexpr int WAIT = decltype(wait_tag)::value;
     if (!RES) return;
-    if (WAIT < 0) s_wait_vm<0>();
-    else s_wait_vm<(WAIT < 0 ? 0 : WAIT)>();
+    if (WAIT < 0) dc_wait_vm<0>();
+    else dc_wait_vm<(WAIT < 0 ? 0 : WAIT)>();
     const unsigned char* const obp = smem + obuf0 + ob * OBUF;
 #pragma unroll
     for (int f = 0; f < FN; ++f)
@@ -371,14 +315,14 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void ws1x1_kernel(const W
           lo[e] = acc[f][8 * j + e] * s0[e] + h0[e];
           hi[e] = acc[f][8 * j + 4 + e] * s1[e] + h1[e];
         }
-        s_permlane32_swap4(lo, hi);
+        dc_permlane32_swap4(lo, hi);
         u32x4 o;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           float x0 = i < 2 ? lo[2 * i] : hi[2 * i - 4], x1 = i < 2 ? lo[2 * i + 1] : hi[2 * i - 3];
           if (RES) {
-            x0 = s_add_half_lo(rv[i], x0);
-            x1 = s_add_half_hi(rv[i], x1);
+            x0 = dc_add_half_lo(rv[i], x0);
+            x1 = dc_add_half_hi(rv[i], x1);
           }
           const f32x2 xp = {x0, x1};
           f16x2 hp = __builtin_convertvector(xp, f16x2);
@@ -400,7 +344,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void ws1x1_kernel(const W
 #pragma unroll
       for (int i = 0; i < NO; ++i) ov[i] = *reinterpret_cast<const u32x4*>(obp + i * 1024 + lane * 16);
 #pragma unroll
-      for (int i = 0; i < NO; ++i) s_store16_untracked(cc.rs, orow[i] < lim ? yoff[i] + so : kOOBs, ov[i]);
+      for (int i = 0; i < NO; ++i) dc_store16_untracked_uni(cc.rs, orow[i] < lim ? yoff[i] + so : kOOB, ov[i]);
     }
     // the buffer is free (its reads have returned: the stores above took their data): the shortcut tile of step ge+2 goes into it
     resid_step(ge + 2, ob);
@@ -421,15 +365,15 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void ws1x1_kernel(const W
     constexpr int KS = decltype(k_tag)::value;  // the step's number if < D, else -1
     constexpr int STEADY = (D - 2) * NA + (D - 1) * (NS + NR), E0 = (D - 2) * NA + 2 * NR;
     if (late) {
-      if (KS < 0) s_wait_vm<STEADY>();
-      else if (KS == 0) s_wait_vm<E0>();
-      else if (KS <= D - 2) s_wait_vm<E0 + (KS > 0 ? KS - 1 : 0) * (NS + NR)>();
-      else s_wait_vm<(D - 2) * NA + (D - 2) * (NS + NR)>();
+      if (KS < 0) dc_wait_vm<STEADY>();
+      else if (KS == 0) dc_wait_vm<E0>();
+      else if (KS <= D - 2) dc_wait_vm<E0 + (KS > 0 ? KS - 1 : 0) * (NS + NR)>();
+      else dc_wait_vm<(D - 2) * NA + (D - 2) * (NS + NR)>();
     } else {
-      if (KS < 0 || KS >= D - 1) s_wait_vm<STEADY>();
-      else s_wait_vm<E0 + (KS > 0 ? KS : 0) * (NS + NR)>();
+      if (KS < 0 || KS >= D - 1) dc_wait_vm<STEADY>();
+      else dc_wait_vm<E0 + (KS > 0 ? KS : 0) * (NS + NR)>();
     }
-    s_lds_barrier();  // every wave's pieces are in; every wave is done reading the stage of step gs-1 (and, at the first step, the constants are written)
+    dc_lds_barrier();  // every wave's pieces are in; every wave is done reading the stage of step gs-1 (and, at the first step, the constants are written)
     dma_step(gs + D - 1, slot == 0 ? D - 1 : slot - 1);  // refill that stage with step gs+D-1
     if (late) {
       if (KS != 0) {
@@ -459,7 +403,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void ws1x1_kernel(const W
     epi_part(gs1 - 1);
   }
   stamp(4);
-  s_wait_vm<0>();  // the dummy DMA pieces past the range must not land in the LDS of the next workgroup on this CU
+  dc_wait_vm<0>();  // the dummy DMA pieces past the range must not land in the LDS of the next workgroup on this CU
   stamp(5);
   stamp(6);
   stamp(7);
@@ -497,17 +441,6 @@ const WsForm* form_of(int K) {
     }
   return first;
 }
-void ws_magic(unsigned dv, unsigned (&mg)[2]) {  // dc_magic of kernels.hip
-  if (dv <= 1) {
-    mg[0] = 0, mg[1] = 0x80000000u;
-    return;
-  }
-  int l = 0;
-  while ((1ull << l) < dv) ++l;
-  const int sh = 31 + l;
-  const unsigned long long qq = (unsigned long long)((((unsigned __int128)1) << sh) / dv);
-  mg[0] = (unsigned)(qq + 1), mg[1] = (unsigned)(sh - 32);
-}
 int ws_slots() {  // workgroups the walk is cut into: two per CU
   static const int s = getenv("DC_WS_SLOTS") ? atoi(getenv("DC_WS_SLOTS")) : 512;
   return std::max(8, s);
@@ -526,8 +459,8 @@ long ws_plan(WsArgs& a, int K) {
   long J = std::min<long>(S, std::max(1, ws_slots() / (f->NW == 8 ? 2 : 1) / a.tn));
   if (J >= 8) J -= J % 8;
   a.J = (int)J;
-  ws_magic((unsigned)a.tn, a.div_tn);
-  ws_magic((unsigned)a.J, a.div_J);
+  dc_magic((unsigned)a.tn, a.div_tn);
+  dc_magic((unsigned)a.J, a.div_J);
   return (J + 7) / 8 * 8 * a.tn;
 }
 bool ws_tensor_ok(const void* x, const void* y, const void* resid, long M, long sx, long ypix) {

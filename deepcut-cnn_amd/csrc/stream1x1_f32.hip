@@ -33,17 +33,11 @@
 #include <type_traits>
 #include <vector>
 
+#include "kernel_prims.h"
 #include "kernels.h"
 
 namespace dc {
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-constexpr unsigned kOOBf = 0x80000000u;
-#pragma clang diagnostic ignored "-Winline-asm"
 
 struct WsfArgs {
   const void* x;
@@ -60,27 +54,6 @@ struct WsfArgs {
   int OW, OHW, H, W, xrsb, ximgb;  // output width, output pixels per image, image rows / pixels per row, bytes between image rows / images
   unsigned div_ow[2], div_ohw[2];
 };
-
-__device__ __forceinline__ unsigned f_uni(unsigned v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ i32x4 f_rsrc_words(const void* p) {
-  const unsigned long long a = (unsigned long long)p;
-  return i32x4{__builtin_amdgcn_readfirstlane((int)(unsigned)a), __builtin_amdgcn_readfirstlane((int)((a >> 32) & 0xffffu)), 0x7fffffff, 0x00020000};
-}
-__device__ __forceinline__ void f_dma16(i32x4 rs, unsigned lds_, unsigned voff) {
-  const unsigned lds = f_uni(lds_);
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(lds), "v"(voff), "s"(rs) : "memory", "m0");
-}
-__device__ __forceinline__ void f_store16_untracked(i32x4 rs, unsigned voff, u32x4 v) {
-  asm volatile("s_nop 4\n\tbuffer_store_dwordx4 %0, %1, %2, 0 offen\n\ts_nop 1" ::"v"(v), "v"(voff), "s"(rs) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void f_wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void f_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ int f_fastdiv(int n, const unsigned (&mg)[2]) {
-  return (mg[1] >> 31) ? n : (int)(__umulhi((unsigned)n, mg[0]) >> (mg[1] & 31));
-}
 
 // Counted waits.  The vector-memory requests of a wave, in issue order (vmcnt counts them all, stores included):
 //   prologue: stage 0 .. D-2 (NA each), shortcut tile 0, shortcut tile 1 (NR each); [wait: stage 0 landed] barrier
@@ -130,7 +103,7 @@ __global__ __launch_bounds__(256, 1) void ws1x1f_kernel(const WsfArgs a) {
   const int p16 = lane & 15, q = lane >> 4;
 
   const int bx = blockIdx.x, xcd = bx & 7, bi = bx >> 3;
-  const int ci = f_fastdiv(bi, a.div_tn);
+  const int ci = dc_fastdiv(bi, a.div_tn);
   const int nt = bi - ci * a.tn;
   const int jc = xcd + 8 * ci;
   if (jc >= a.J) return;
@@ -142,22 +115,22 @@ __global__ __launch_bounds__(256, 1) void ws1x1f_kernel(const WsfArgs a) {
   f32x4 csc = {1.f, 1.f, 1.f, 1.f}, csh = {0.f, 0.f, 0.f, 0.f};
   {
     const unsigned co = (unsigned)((nw0 + 4 * q) * 4);
-    if (a.scale) asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(csc) : "v"(co), "s"(f_rsrc_words(a.scale)) : "memory");
-    if (a.shift) asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(csh) : "v"(co), "s"(f_rsrc_words(a.shift)) : "memory");
+    if (a.scale) asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(csc) : "v"(co), "s"(dc_uni4(dc_rsrc_words(a.scale))) : "memory");
+    if (a.shift) asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(csh) : "v"(co), "s"(dc_uni4(dc_rsrc_words(a.shift))) : "memory");
   }
   f32x4 wreg[NJ];
   {
-    const i32x4 wrs = f_rsrc_words(a.w);
+    const i32x4 wrs = dc_uni4(dc_rsrc_words(a.w));
     const unsigned wl = (unsigned)lane * 16u;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-      const unsigned so = f_uni((unsigned)((((nw0 >> 4) * NJ) + j) * 1024));
+      const unsigned so = dc_uni((unsigned)((((nw0 >> 4) * NJ) + j) * 1024));
       asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(wreg[j]) : "v"(wl), "s"(wrs), "s"(so) : "memory");
     }
   }
 
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
-  const i32x4 xr = f_rsrc_words(a.x), rr = f_rsrc_words(RES ? a.resid : a.y), yr = f_rsrc_words(a.y);
+  const i32x4 xr = dc_uni4(dc_rsrc_words(a.x)), rr = dc_uni4(dc_rsrc_words(RES ? a.resid : a.y)), yr = dc_uni4(dc_rsrc_words(a.y));
   const unsigned frag0 = (unsigned)(p16 / RPR * BLKB + p16 % RPR * K * 4 + ((q + p16 % RPR) & 3) * K);  // this lane's run of the pixel's row: + 16 j
   const unsigned obuf0 = (unsigned)(D * STG + wave * 2 * 1024);           // this wave's two 1 KiB tiles
   const unsigned ovec = (unsigned)((4 * p16 + q) * 16);                   // MFMA view: pixel p16, channels 4 q .. + 3
@@ -169,28 +142,28 @@ __global__ __launch_bounds__(256, 1) void ws1x1f_kernel(const WsfArgs a) {
     const int pc = wave + 4 * i;  // request pc of the stage
     if (STEM) {  // output pixel row0 + pc: lane 8 tap + px fetches pixel (2 ox - 3 + px) of image row (2 oy - 3 + tap); tap 7 and the pad are zeros
       const int r = row0 + pc;
-      const int n = f_fastdiv(r, a.div_ohw), rem = r - n * a.OHW;
-      const int oy = f_fastdiv(rem, a.div_ow), ox = rem - oy * a.OW;
+      const int n = dc_fastdiv(r, a.div_ohw), rem = r - n * a.OHW;
+      const int oy = dc_fastdiv(rem, a.div_ow), ox = rem - oy * a.OW;
       const int tap = lane >> 3, iy = 2 * oy - 3 + tap, ix = 2 * ox - 3 + (lane & 7);
       const bool ok = pc < lim && tap < 7 && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-      const unsigned vo = ok ? (unsigned)n * (unsigned)a.ximgb + (unsigned)iy * (unsigned)a.xrsb + (unsigned)ix * 16u : kOOBf;
-      f_dma16(xr, lds0 + (unsigned)(slot * STG + pc * BLKB), vo);
+      const unsigned vo = ok ? (unsigned)n * (unsigned)a.ximgb + (unsigned)iy * (unsigned)a.xrsb + (unsigned)ix * 16u : kOOB;
+      dc_dma16(xr, lds0 + (unsigned)(slot * STG + pc * BLKB), vo);
     } else if (RPR == 1) {        // part `part` of row `row`
       const int row = pc / PPR, part = pc - row * PPR;
-      const unsigned vo = row < lim ? (unsigned)(row0 + row) * (unsigned)a.sxb + (unsigned)(part * 1024 + lane * 16) : kOOBf;
-      f_dma16(xr, lds0 + (unsigned)(slot * STG + row * BLKB + part * 1024), vo);
+      const unsigned vo = row < lim ? (unsigned)(row0 + row) * (unsigned)a.sxb + (unsigned)(part * 1024 + lane * 16) : kOOB;
+      dc_dma16(xr, lds0 + (unsigned)(slot * STG + row * BLKB + part * 1024), vo);
     } else {                      // rows pc RPR .. + RPR - 1, K / 4 lanes each
       constexpr int LPR = 64 / RPR;  // lanes = 16-byte chunks per row
       const int r = lane / LPR, row = pc * RPR + r;
-      const unsigned vo = row < lim ? (unsigned)(row0 + row) * (unsigned)a.sxb + (unsigned)(((lane - r * (LPR / 4)) & (LPR - 1)) * 16) : kOOBf;
-      f_dma16(xr, lds0 + (unsigned)(slot * STG + pc * BLKB), vo);
+      const unsigned vo = row < lim ? (unsigned)(row0 + row) * (unsigned)a.sxb + (unsigned)(((lane - r * (LPR / 4)) & (LPR - 1)) * 16) : kOOB;
+      dc_dma16(xr, lds0 + (unsigned)(slot * STG + pc * BLKB), vo);
     }
   };
   auto resid_step = [&](int gs, int buf) {  // NR requests, always
     if (!RES) return;
     const int row0 = gs * 16;
     const int lim = gs < gs1 ? a.M - row0 : 0;
-    f_dma16(rr, lds0 + obuf0 + (unsigned)(buf * 1024), orow < lim ? (unsigned)(row0 + orow) * (unsigned)a.ypb + ooff : kOOBf);
+    dc_dma16(rr, lds0 + obuf0 + (unsigned)(buf * 1024), orow < lim ? (unsigned)(row0 + orow) * (unsigned)a.ypb + ooff : kOOB);
   };
   auto stamp = [&](int sl) {
     if (a.dbg && lane == 0) {
@@ -208,11 +181,11 @@ __global__ __launch_bounds__(256, 1) void ws1x1f_kernel(const WsfArgs a) {
   resid_step(gs0, 0);
   resid_step(gs0 + 1, 1);
   stamp(1);
-  f_wait_vm<Rq::pro>();
+  dc_wait_vm<Rq::pro>();
   asm volatile("" : "+v"(csc), "+v"(csh));
 #pragma unroll
   for (int j = 0; j < NJ; ++j) asm volatile("" : "+v"(wreg[j]));
-  f_lds_barrier();
+  dc_lds_barrier();
   stamp(2);
 
   // One step = the NJ x 4 matrix products of 16 pixels, and everything else BETWEEN them, so that the matrix pipe runs from the first
@@ -242,7 +215,7 @@ __global__ __launch_bounds__(256, 1) void ws1x1f_kernel(const WsfArgs a) {
   };
   auto epi_store = [&](int gs, const u32x4& ov) {  // memory view: 16 pixels x 64-byte runs
     const int row0 = gs * 16;
-    f_store16_untracked(yr, orow < a.M - row0 ? (unsigned)(row0 + orow) * (unsigned)a.ypb + ooff : kOOBf, ov);
+    dc_store16_untracked(yr, orow < a.M - row0 ? (unsigned)(row0 + orow) * (unsigned)a.ypb + ooff : kOOB, ov);
   };
   auto do_step = [&](int gs, auto k_tag) {
     constexpr int KS = decltype(k_tag)::value;  // the step's number while the request counts still change (Rq), -1 in the steady state
@@ -275,12 +248,12 @@ __global__ __launch_bounds__(256, 1) void ws1x1f_kernel(const WsfArgs a) {
       acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wreg[j][2], xf[j % PD][2], acc0, 0, 0, 0);
       acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wreg[j][3], xf[j % PD][3], acc1, 0, 0, 0);
       if (j == HB) {
-        f_wait_vm<Rq::stage(KQ)>();
+        dc_wait_vm<Rq::stage(KQ)>();
         asm volatile("s_barrier" ::: "memory");
       }
       if (j > HB && j <= HB + NA) dma_req(gs + D - 1, pslot, j - HB - 1);
       if (EPI && j == H1) {
-        if (RES) f_wait_vm<Rq::resid(KQ)>();
+        if (RES) dc_wait_vm<Rq::resid(KQ)>();
         epi_read(obp, rv);
       }
       if (EPI && j == H2) epi_math(obp, sum, rv);
@@ -303,7 +276,7 @@ __global__ __launch_bounds__(256, 1) void ws1x1f_kernel(const WsfArgs a) {
   for (; gs < gs1; ++gs) do_step(gs, std::integral_constant<int, -1>{});
   stamp(4);
   // the last step's epilogue, alone
-  f_wait_vm<0>();
+  dc_wait_vm<0>();
   stamp(5);
   if (gs1 > gs0) {
     unsigned char* const obp = smem + obuf0 + ob * 1024;
@@ -330,17 +303,6 @@ const WsfForm* formf_of(int K) {
     if (f.K == K) return &f;
   return nullptr;
 }
-void f_magic(unsigned dv, unsigned (&mg)[2]) {
-  if (dv <= 1) {
-    mg[0] = 0, mg[1] = 0x80000000u;
-    return;
-  }
-  int l = 0;
-  while ((1ull << l) < dv) ++l;
-  const int sh = 31 + l;
-  const unsigned long long qq = (unsigned long long)((((unsigned __int128)1) << sh) / dv);
-  mg[0] = (unsigned)(qq + 1), mg[1] = (unsigned)(sh - 32);
-}
 long wsf_plan(WsfArgs& a, int klen, bool stem = false) {
   a.tn = a.Cout / 64;
   a.S = (a.M + 15) / 16;
@@ -355,7 +317,7 @@ long wsf_plan(WsfArgs& a, int klen, bool stem = false) {
   a.sbase = a.S / a.J, a.srem = a.S % a.J;
   static const bool remap = !getenv("DC_WSF_REMAP") || atoi(getenv("DC_WSF_REMAP")) != 0;
   if (!remap) a.srem = -1;
-  f_magic((unsigned)a.tn, a.div_tn);
+  dc_magic((unsigned)a.tn, a.div_tn);
   return (J + 7) / 8 * 8 * a.tn;
 }
 }  // namespace
@@ -407,8 +369,8 @@ int launch_stem_ws(const ConvGemmParams& p, void* stream) {
   a.x = p.x, a.w = p.w, a.scale = p.scale, a.shift = p.shift, a.y = p.y, a.resid = nullptr;
   a.M = p.M, a.Cout = p.Cout, a.sxb = 0, a.ypb = p.y_pix_stride * 4, a.dbg = p.dbg;
   a.OW = p.OW, a.OHW = p.OH * p.OW, a.H = p.x_rows, a.W = p.x_rowlen / 4, a.xrsb = p.x_row_stride * 4, a.ximgb = (int)(p.x_img_stride * 4);
-  f_magic((unsigned)a.OW, a.div_ow);
-  f_magic((unsigned)a.OHW, a.div_ohw);
+  dc_magic((unsigned)a.OW, a.div_ow);
+  dc_magic((unsigned)a.OHW, a.div_ohw);
   static const int abl = getenv("DC_WSF_STEM_ABL") ? atoi(getenv("DC_WSF_STEM_ABL")) : 0;  // timing only (wrong results): 1 = every request out of range (no image bytes move)
   if (abl == 1) a.H = 0;
   const long grid = wsf_plan(a, 256, true);

@@ -52,17 +52,12 @@
 #include <type_traits>
 #include <vector>
 
+#include "kernel_prims.h"
 #include "kernels.h"
 
 namespace dc {
 
 namespace {
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
 constexpr int HBTY = 4, HBTX = 8;                      // tiles per block
 constexpr int HRH = 2 * HBTY + 2, HRW = 2 * HBTX + 2;  // staged pixels: 10 x 18
 constexpr int HKC = 32;                                // channels per staged step (two 16-channel MFMA sub-steps)
@@ -75,7 +70,6 @@ constexpr int HPART16 = 8 * 2 * 2 * 4 * 64;            // partial inverse transf
 constexpr int HLDS16 = HPART16;                        // the staging ring (3 x 23.7 KB) lives in the same memory
 static_assert(3 * HSTAGE16 <= HLDS16, "the staging ring lives in the memory the partials reuse");
 static_assert((HLDS16 + 32) * 16 <= 160 * 1024, "LDS of a CU");
-constexpr unsigned kOOBh = 0x80000000u;
 #ifndef DC_WINO_LATE_STORE
 #define DC_WINO_LATE_STORE 0
 #endif
@@ -84,21 +78,8 @@ constexpr unsigned kOOBh = 0x80000000u;
 #endif
 constexpr int HUB = 1;  // filter-fragment register sets: 1 = the next sub-step's fragments into the registers just read, 2 = two sub-steps ahead
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t h_rsrc(const void* p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7fffffff, 0x00020000);
-}
-__device__ __forceinline__ u32x4 h_bload4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-__device__ __forceinline__ int h_fastdiv(int n, const unsigned (&mg)[2]) {
-  return (mg[1] >> 31) ? n : (int)(__umulhi((unsigned)n, mg[0]) >> (mg[1] & 31));
-}
 __device__ __forceinline__ f16x2 h_as_h2(unsigned v) { return __builtin_bit_cast(f16x2, v); }
 __device__ __forceinline__ unsigned h_as_u(f16x2 v) { return __builtin_bit_cast(unsigned, v); }
-// lanes 32..63 of lo <-> lanes 0..31 of hi (one s_nop: the VALU instructions that produced the operands need wait states)
-__device__ __forceinline__ void h_permlane32_swap2(unsigned (&lo)[2], unsigned (&hi)[2]) {
-  asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %2\n\tv_permlane32_swap_b32 %1, %3" : "+v"(lo[0]), "+v"(lo[1]), "+v"(hi[0]), "+v"(hi[1]));
-}
 }  // namespace
 
 __global__ __launch_bounds__(HNTH, 1) void wino_h23_kernel(const ConvGemmParams p) {
@@ -150,15 +131,15 @@ __global__ __launch_bounds__(HNTH, 1) void wino_h23_kernel(const ConvGemmParams 
     const int g8 = gridDim.x >> 3, r8 = gridDim.x & 7, q = blockIdx.x & 7;
     lb = q * g8 + min(q, r8) + (blockIdx.x >> 3);
   }
-  const int nb = h_fastdiv(lb, p.w_div_nblk), pair = lb - nb * npair;  // (w_div_nblk divides by the number of block PAIRS here)
+  const int nb = dc_fastdiv(lb, p.w_div_nblk), pair = lb - nb * npair;  // (w_div_nblk divides by the number of block PAIRS here)
   asm volatile("" ::"s"(ka0), "s"(ka1), "s"(ka2), "s"(ka3), "s"(ka4));  // (the dummy loads have landed: their registers are free)
   // filter fragments: [Cout/32][4 i][C/16][4 j][64 lanes][8 halves]; this wave reads positions (wi, 2 jp + {0, 1}) of the two
   // fragments nb * 2 + {0, 1}: the fragment stride travels in the scalar offset.  Requested first: they need no pixel decode
-  const __amdgpu_buffer_rsrc_t ur = h_rsrc(p.w);
+  const __amdgpu_buffer_rsrc_t ur = dc_rsrc(p.w);
   const unsigned uvo = ((unsigned)((nb * 2 * 4 + wi) * (C / 16)) * 4096u) + (unsigned)(2 * jp) * 1024u + (unsigned)lane * 16u;
   const unsigned ufrag = (unsigned)(4 * (C / 16)) * 4096u;
   u32x4 ub[HUB][2][2];  // [sub-step parity (HUB = 2)][position jj][fragment]
-  auto bload = [&](int s, int jj, int nf, int k16) { ub[s][jj][nf] = h_bload4(ur, uvo + (unsigned)jj * 1024u, (unsigned)k16 * 4096u + (unsigned)nf * ufrag); };
+  auto bload = [&](int s, int jj, int nf, int k16) { ub[s][jj][nf] = dc_bload4<u32x4>(ur, uvo + (unsigned)jj * 1024u, (unsigned)k16 * 4096u + (unsigned)nf * ufrag); };
   const int NS = C / HKC;
 #pragma unroll
   for (int s = 0; s < HUB; ++s)
@@ -173,14 +154,14 @@ __global__ __launch_bounds__(HNTH, 1) void wino_h23_kernel(const ConvGemmParams 
   for (int m = 0; m < 2; ++m) {
     const int blk = 2 * pair + m;
     bok[m] = blk < nblk;
-    const int nph = h_fastdiv(blk, p.w_div_nbyx), brem = blk - nph * (NBY * NBX);
-    bn[m] = h_fastdiv(nph, p.w_div_dd);
+    const int nph = dc_fastdiv(blk, p.w_div_nbyx), brem = blk - nph * (NBY * NBX);
+    bn[m] = dc_fastdiv(nph, p.w_div_dd);
     const int ph = nph - bn[m] * (d * d);
-    bphy[m] = h_fastdiv(ph, p.w_div_d), bphx[m] = ph - bphy[m] * d;
-    bby[m] = h_fastdiv(brem, p.w_div_nbx), bbx[m] = brem - bby[m] * NBX;
+    bphy[m] = dc_fastdiv(ph, p.w_div_d), bphx[m] = ph - bphy[m] * d;
+    bby[m] = dc_fastdiv(brem, p.w_div_nbx), bbx[m] = brem - bby[m] * NBX;
   }
   // ---- staging: thread t moves chunks t, t + 512, t + 1024 of the 2 x 720 (pixel, 8-channel chunk) pairs of a stage
-  const __amdgpu_buffer_rsrc_t xr = h_rsrc(p.x);
+  const __amdgpu_buffer_rsrc_t xr = dc_rsrc(p.x);
   unsigned gofs[3];
   int sofs[3];
 #pragma unroll
@@ -193,13 +174,13 @@ __global__ __launch_bounds__(HNTH, 1) void wino_h23_kernel(const ConvGemmParams 
     const int iy = bphy[m] + d * (oy0 + py), ix = bphx[m] + d * (ox0 + px);
     const bool ok = e0 < 2 * HCHUNKS && bok[m] && oy0 + py >= 0 && ox0 + px >= 0 && iy < H && ix < W;
     // (the whole tensor stays below 2 GiB: wino_half_eligible — the image base travels in the 32-bit offset)
-    gofs[q] = ok ? (unsigned)((long)bn[m] * p.x_img_stride + iy * p.x_row_stride + ix * C + cq * 8) * 2u : kOOBh;
+    gofs[q] = ok ? (unsigned)((long)bn[m] * p.x_img_stride + iy * p.x_row_stride + ix * C + cq * 8) * 2u : kOOB;
     sofs[q] = e0 < 2 * HCHUNKS ? m * HBLK16 + py * HP16 + px * 4 + (cq ^ ((px >> 2) & 3)) : 2 * HBLK16 + (t & 1);
   }
   u32x4 g[3], g1[3];
   auto gload = [&](int K) {
 #pragma unroll
-    for (int q = 0; q < 3; ++q) g[q] = h_bload4(xr, gofs[q], (unsigned)(K * HKC * 2));
+    for (int q = 0; q < 3; ++q) g[q] = dc_bload4<u32x4>(xr, gofs[q], (unsigned)(K * HKC * 2));
   };
   const f16x2 quarter = {(_Float16)0.25f, (_Float16)0.25f};
   auto sstore = [&](int buf, const u32x4 (&gg)[3]) {
@@ -215,7 +196,7 @@ __global__ __launch_bounds__(HNTH, 1) void wino_h23_kernel(const ConvGemmParams 
   gload(0);
   if (NS > 1) {
 #pragma unroll
-    for (int q = 0; q < 3; ++q) g1[q] = h_bload4(xr, gofs[q], (unsigned)(HKC * 2));
+    for (int q = 0; q < 3; ++q) g1[q] = dc_bload4<u32x4>(xr, gofs[q], (unsigned)(HKC * 2));
   }
   if (t < 128) {  // the epilogue's per-channel constants of the workgroup's 64 channels wait in LDS
     const float* src = t < 64 ? p.scale : p.shift;
@@ -337,7 +318,7 @@ __global__ __launch_bounds__(HNTH, 1) void wino_h23_kernel(const ConvGemmParams 
     //      the other position pair and the four rows through LDS, one tile block per round; in a round this wave finalises output
     //      pixel (a, bq) = (I >> 1, I & 1) of every tile for the channel quads 2 JP, 2 JP + 1 of both fragments
     constexpr int A = I >> 1, BQ = I & 1;
-    const __amdgpu_buffer_rsrc_t yr = h_rsrc(p.y);
+    const __amdgpu_buffer_rsrc_t yr = dc_rsrc(p.y);
     __syncthreads();  // every wave is done reading the staging ring, which the partials now overwrite
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
@@ -356,7 +337,7 @@ __global__ __launch_bounds__(HNTH, 1) void wino_h23_kernel(const ConvGemmParams 
           lds[((((JP * 4 + I) * 2 + 1) * 2 + nf) * 4 + rq) * 64 + lane] = __builtin_bit_cast(u32x4, p1);
         }
       const int oy = bphy[m] + d * (2 * (bby[m] * HBTY + ty) + A), ox = bphx[m] + d * (2 * (bbx[m] * HBTX + tx) + BQ);
-      const unsigned ybase = bok[m] && oy < p.OH && ox < p.OW ? (unsigned)((long)bn[m] * p.y_img_stride + oy * p.y_row_stride + ox * p.y_pix_stride) * 2u : kOOBh;
+      const unsigned ybase = bok[m] && oy < p.OH && ox < p.OW ? (unsigned)((long)bn[m] * p.y_img_stride + oy * p.y_row_stride + ox * p.y_pix_stride) * 2u : kOOB;
       __syncthreads();
       if (m == 0) stamp(5), stamp(6);
 #pragma unroll
@@ -385,7 +366,7 @@ __global__ __launch_bounds__(HNTH, 1) void wino_h23_kernel(const ConvGemmParams 
         }
         // lanes 0..31 hold channels 8 rq + 0..3 of their tile, lanes 32..63 channels 8 rq + 4..7: after the swap of the quads
         // (2 JP, 2 JP + 1) lanes 0..31 hold channels 16 JP + 0..7 and lanes 32..63 channels 16 JP + 8..15 — one 16-byte store
-        h_permlane32_swap2(hv[0], hv[1]);
+        dc_permlane32_swap2(hv[0], hv[1]);
         const u32x4 o = {hv[0][0], hv[0][1], hv[1][0], hv[1][1]};
         __builtin_amdgcn_raw_buffer_store_b128(o, yr, ybase + (unsigned)(nb * 64 + nf * 32 + 16 * JP + 8 * kg) * 2u, 0, 0);
       }
@@ -403,13 +384,9 @@ __global__ __launch_bounds__(HNTH, 1) void wino_h23_kernel(const ConvGemmParams 
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
 bool wino_half_eligible(const ConvGemmParams& p) {
-  const int d = p.ddy;  // dilation (1 or more), the same along x and y, with pad = dilation ("same" convolution)
-  if (p.esize != 2 || p.ekind == kElemBF16 || p.nty != 3 || p.ntx != 3 || p.sy != 1 || d < 1 || d > 4 || p.dy0 != -d) return false;
+  if (p.esize != 2 || p.ekind == kElemBF16 || !wino_same3x3(p)) return false;
   const int C = p.klen;
-  if (C <= 0 || C % HKC != 0 || p.Cout % 64 != 0 || p.sigmoid_ch != 0 || p.ncls > 1) return false;
-  if (p.sx != C || p.ddx != d * C || p.x0 != -d * C) return false;        // stride 1, dilation d, pad d along x
-  if (p.x_rowlen % C != 0 || p.x_row_stride != p.x_rowlen) return false;  // dense NHWC rows of C channels
-  if (p.OH != p.x_rows || p.OW != p.x_rowlen / C) return false;           // "same" convolution
+  if (C % HKC != 0 || p.Cout % 64 != 0 || p.sigmoid_ch != 0 || p.ncls > 1) return false;
   if (p.y_pix_stride % 8 != 0 || p.y_row_stride % 8 != 0 || p.y_img_stride % 8 != 0) return false;  // 16-byte output vectors
   // 32-bit byte offsets (buffer addressing): the input, the output and the packed filter image stay below 2 GiB each
   if ((long long)p.NB * p.x_img_stride * 2 >= 0x7fffffffLL || (long long)p.NB * p.y_img_stride * 2 >= 0x7fffffffLL ||
@@ -469,31 +446,7 @@ int launch_wino_half(const ConvGemmParams& p, void* stream) {
   const long grid = wino_half_grid(p);
   if (grid <= 0) return 0;
   if (grid > 0x7fffffffL) return (int)hipErrorInvalidValue;
-  ConvGemmParams q = p;
-  static const int xcd_map = getenv("DC_XCD_MAP") ? atoi(getenv("DC_XCD_MAP")) : 1;
-  q.xcd_on = xcd_map && grid >= 16;
-  auto magic = [](unsigned dv, unsigned (&mg)[2]) {  // dc_magic of kernels.hip: sh = 31 + ceil(log2 dv), mul = floor(2^sh / dv) + 1
-    if (dv <= 1) {
-      mg[0] = 0, mg[1] = 0x80000000u;
-      return;
-    }
-    int l = 0;
-    while ((1ull << l) < dv) ++l;
-    const int sh = 31 + l;
-    const unsigned long long qq = (unsigned long long)((((unsigned __int128)1) << sh) / dv);
-    mg[0] = (unsigned)(qq + 1), mg[1] = (unsigned)(sh - 32);
-  };
-  {
-    const int d = p.ddy;
-    q.w_TY = ((p.OH + d - 1) / d + 1) / 2, q.w_TX = ((p.OW + d - 1) / d + 1) / 2;
-    q.w_NBY = (q.w_TY + HBTY - 1) / HBTY, q.w_NBX = (q.w_TX + HBTX - 1) / HBTX;
-    q.w_nblk = p.NB * d * d * q.w_NBY * q.w_NBX;
-    magic((unsigned)((q.w_nblk + 1) / 2), q.w_div_nblk);  // (the kernel divides by the number of block PAIRS)
-    magic((unsigned)(q.w_NBY * q.w_NBX), q.w_div_nbyx);
-    magic((unsigned)(d * d), q.w_div_dd);
-    magic((unsigned)d, q.w_div_d);
-    magic((unsigned)q.w_NBX, q.w_div_nbx);
-  }
+  const ConvGemmParams q = wino_launch_params(p, grid, HBTY, HBTX, 2);  // a workgroup = two consecutive tile blocks
   const dim3 gd((unsigned)grid), bd(HNTH);
   hipLaunchKernelGGL(wino_h23_kernel, gd, bd, 0, (hipStream_t)stream, q);
   return (int)hipGetLastError();
