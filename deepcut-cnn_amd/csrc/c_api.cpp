@@ -589,6 +589,15 @@ int dc_wino_half_pack(const float* g, int cout, int cin, int rowscale, float* ou
   return guard([&] { dc::wino_half_pack_filters(g, cout, cin, rowscale != 0, out, row_scale); });
 }
 
+int dc_wino_blocks(const char* tile, int tiles_y, int tiles_x) {
+  if (!tile || tiles_y < 1 || tiles_x < 1) return -1;
+  try {
+    return (int)dc::wino_form_blocks(dc::variant_by_name(tile), tiles_y, tiles_x);
+  } catch (...) {
+    return -1;
+  }
+}
+
 int dc_stream1x1_pack(const float* g, int cout, int k, float* out) {
   if (!g || !out) return fail(DC_EINVAL, "dc_stream1x1_pack: null pointer");
   if (cout <= 0 || k <= 0 || cout % 32 || k % 16) return fail(DC_EINVAL, "dc_stream1x1_pack: cout must be a multiple of 32, k of 16");

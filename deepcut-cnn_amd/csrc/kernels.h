@@ -185,7 +185,9 @@ bool wino_same3x3(const ConvGemmParams& p);
 // `p` as a Winograd form launches it over `grid` workgroups: the per-XCD map (DC_XCD_MAP, grids of 16 or more), the geometry of the
 // bty x btx tile blocks and the magic numbers of the kernel's block-index divisions, the first one by blocks_per_wg blocks at a time
 ConvGemmParams wino_launch_params(const ConvGemmParams& p, long grid, int bty, int btx, int blocks_per_wg);
-long wino_grid(const ConvGemmParams& p);
+long wino_grid(const ConvGemmParams& p);                   // of the 4 x 8-tile forms
+long wino_blocks(int TY, int TX, int bty, int btx);        // bty x btx-tile blocks that cover a TY x TX tile grid
+long wino_form_blocks(int variant, int TY, int TX);        // ... blocks of the float32 Winograd form `variant`; -1: not one
 size_t wino_packed_floats(int Cout, int Cin);
 // g: [Cout][Cin][3][3] (Caffe order) -> U = G g G^T per (co, ci), laid out so that one wave's B-operand load is 1 KB
 // contiguous: [Cout/16][4 i][Cin/16][4 j][64 lanes][4]
@@ -238,7 +240,9 @@ constexpr int kStreamHalf = 1003;     // "ws1x1": the float16 streaming form of 
 constexpr int kStemHalf = 1004;       // "stem7x7": the float16 7x7 / stride-2 stem (stem_f16.hip)
 constexpr int kStreamFloat = 1005;    // "ws1x1f": the float32 streaming 1x1 form (stream1x1_f32.hip)
 constexpr int kStemFloat = 1006;      // "ws7x7f": the float32 stem on that kernel's skeleton (stream1x1_f32.hip)
-constexpr int kFormVariant0 = kWinoVariant, kNumForms = 7;
+constexpr int kWinoVariant56 = 1007;     // "wino_f23_5x6": wino_f23 on 5 x 6-tile blocks (two 5 x 3-tile fragments side by side) instead of 4 x 8
+constexpr int kWinoVariant56x16 = 1008;  // "wino_f23_5x6_w16": its 16-wave form
+constexpr int kFormVariant0 = kWinoVariant, kNumForms = 9;
 enum FormGeometry { kForm3x3, kForm1x1, kFormStem };  // the layers a form takes: 3x3, dense 1x1, the 7-row-tap stem
 struct ConvForm {
   int variant;
@@ -255,6 +259,8 @@ struct ConvForm {
   int (*launch_multi)(const ConvMultiArgs& a, void* stream);
   int sibling;         // the form on the same image that autotuning compares it with in whole passes, else -1
   const char* env;     // its switch: unset or -1 where measured faster, 0 never, >= 1 wherever eligible
+  // null: a candidate of the per-shape timing wherever eligible; else only where this says so (set_tile and tune caches take it wherever eligible)
+  bool (*offered)(const ConvGemmParams& p) = nullptr;
 };
 const ConvForm* conv_form(int variant);  // null: not a form (a tile)
 

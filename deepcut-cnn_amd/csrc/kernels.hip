@@ -1510,7 +1510,7 @@ int launch_conv_multi(const ConvMultiArgs& a, int variant, long grid, void* stre
 //  * the transformed filters are the big stream (16/9 of the filter bytes, no reuse inside a workgroup): pre-packed on
 //    the host so that each wave reads its B fragments straight from global memory, 1 KB contiguous per load, one
 //    sub-step ahead; workgroups that share them (same 16 output channels) are adjacent in the grid;
-//  * ~110 VGPRs and 79 KB of LDS: two workgroups per CU, so that forwards in flight can share CUs (with the register-
+//  * 104 VGPRs (96 in the 16-wave form) and 80.7 KB of LDS (75.6 KB on 5 x 6-tile blocks): two workgroups per CU, so that forwards in flight can share CUs (with the register-
 //    hungrier pipelined variant of the probe the kernel was as fast alone but worth nothing with three forwards in flight);
 //  * the inverse transform reduces over j in registers and over i (four waves) through LDS, then applies the folded
 //    BatchNorm/Scale affine, the shortcut and ReLU like the gather-GEMM's epilogue.
@@ -1532,22 +1532,61 @@ int launch_conv_multi(const ConvMultiArgs& a, int variant, long grid, void* stre
 // Measured on the res4 3x3 shape (1x34x46, 256 -> 256; operands rotated through 355 MB): round-1 kernel 18.7 us alone /
 // 13.4 us per image at 8 images per launch; NG = 1 now 17.5 / 11.7; NG = 2 15.95 / 13.5.
 namespace {
-constexpr int WBTY = 4, WBTX = 8, WBN = 16, WKC = 32;
-constexpr int WRH = 2 * WBTY + 2, WRW = 2 * WBTX + 2;   // staged pixels: 10 x 18
+constexpr int WBTY = 4, WBTX = 8, WBN = 16, WKC = 32;   // (WBTY x WBTX tiles: the default block)
 constexpr int WPSTR = WKC + 4;                           // floats per staged pixel
-constexpr int WPITCH = 672;                              // floats per staged pixel row: >= WRW * WPSTR = 648, and 2 * WPITCH % 64 == 0
-constexpr int WSTAGE = WRH * WPITCH + 8;                 // + the dump slot of the staging threads past the block
+constexpr int WPITCH = 672;                              // floats per staged pixel row of the default block: >= 18 * WPSTR = 648, and 2 * WPITCH % 64 == 0
 constexpr int WNTH = 512;
-static_assert(WPITCH >= WRW * WPSTR && (2 * WPITCH) % 64 == 0 && WPSTR == 36, "conflict-free ds_read_b128 layout (see above)");
-static_assert(WPITCH % 4 == 0 && WPSTR % 4 == 0 && WSTAGE % 4 == 0, "16-byte units");
-__device__ __forceinline__ int wino_rowbase(int row) { return row * WPITCH; }
+// The block geometry of wino_f23_kernel: a 16-row MFMA fragment holds FR x FC tiles (lane q = lane & 15 -> tile (q / FC, q % FC); rows
+// past FR * FC carry no tile), a workgroup's block is two fragments, stacked (2 FR x FC tiles) or side by side (FR x 2 FC); PITCH is
+// the LDS row pitch of the staged pixels in floats.  The geometry enters the kernel in four places only: the staging map, the per-lane
+// patch-row offsets, the epilogue's q -> (ty, tx), and the host's grid.  Filter image, K loop, ring and epilogue arithmetic are shared,
+// and a tile's sums do not depend on the slot it sits in: the geometries give the same bits.
+//  * 4 x 8 = {2 x 8, stacked, pitch 672}: 10 x 18 staged pixels.  The form of every shape until the dilated res5 layers, and the default.
+//  * 5 x 6 = {5 x 3, side by side, pitch 524}: 12 x 14 staged pixels, 15 of a fragment's 16 rows in use.  A 9 x 12 tile grid (a
+//    phase image of res5 3x3 dilation 2 at 544x736) is 2 x 2 = 4 such blocks against 3 x 2 = 6 of the 4 x 8 ones: 768 -> 512 workgroups,
+//    two per CU in one round.  Offered to the autotuner where it needs strictly fewer blocks only (wino_fewer_blocks).
+template <int FR_, int FC_, bool SIDE_, int PITCH_>
+struct WinoGeom {
+  static constexpr int FR = FR_, FC = FC_, NT = FR_ * FC_, PITCH = PITCH_;
+  static constexpr bool SIDE = SIDE_;
+  static constexpr int BTY = SIDE_ ? FR_ : 2 * FR_, BTX = SIDE_ ? 2 * FC_ : FC_;  // tiles of a block
+  static constexpr int RH = 2 * BTY + 2, RW = 2 * BTX + 2;                        // staged pixels
+  static constexpr int STAGE = RH * PITCH_ + 8;                                   // + the dump slot of the staging threads past the block
+  // tile (row, column) inside the block of row q of fragment tf: the fragment's first tile + (q / FC, q % FC)
+  static constexpr int frow(int tf) { return SIDE_ ? 0 : FR_ * tf; }
+  static constexpr int fcol(int tf) { return SIDE_ ? FC_ * tf : 0; }
+  static constexpr int trow(int tf, int q) { return frow(tf) + q / FC_; }
+  static constexpr int tcol(int tf, int q) { return fcol(tf) + q % FC_; }
+  // The LDS model of the comment above: a ds_read_b128 is served in groups of 16 lanes, each made of the eight fragment rows {0-3, 12-15}
+  // of one channel quad and the rows {4-11} of the next one; a group takes one LDS cycle iff its lanes' 16-byte slots differ mod 16.
+  // (A row without a tile reads the last tile's address: a broadcast.)  True: every fragment read is conflict-free.
+  static constexpr bool conflict_free() {
+    for (int tf = 0; tf < 2; ++tf)
+      for (int flip = 0; flip < 2; ++flip) {
+        bool seen[16] = {};
+        for (int q = 0; q < NT; ++q) {
+          const int slot = ((2 * trow(tf, q) * PITCH_ + 2 * tcol(tf, q) * WPSTR) / 4 + ((q >= 4 && q < 12) != (flip != 0) ? 1 : 0)) & 15;
+          if (seen[slot]) return false;
+          seen[slot] = true;
+        }
+      }
+    return true;
+  }
+  static_assert(NT <= 16 && PITCH_ >= RW * WPSTR && WPSTR == 36 && conflict_free(), "conflict-free ds_read_b128 layout (see above)");
+  static_assert(PITCH_ % 4 == 0 && WPSTR % 4 == 0 && STAGE % 4 == 0, "16-byte units");
+};
+using WinoG48 = WinoGeom<WBTY / 2, WBTX, false, WPITCH>;  // 2 * 672 = 21 * 64 floats
+using WinoG56 = WinoGeom<5, 3, true, 524>;   // 524 / 2 = 6 (mod 16) slots per tile row, 2 per tile column: the tiles of each half of a group on distinct even slots
+static_assert(WinoG48::BTY == 4 && WinoG48::BTX == 8 && WinoG48::RH == 10 && WinoG48::RW == 18, "the 4 x 8 block");
+static_assert(WinoG56::BTY == 5 && WinoG56::BTX == 6 && WinoG56::RH == 12 && WinoG56::RW == 14, "the 5 x 6 block");
 __device__ __forceinline__ f32x2 wlo(f32x4 v) { return __builtin_shufflevector(v, v, 0, 1); }
 __device__ __forceinline__ f32x2 whi(f32x4 v) { return __builtin_shufflevector(v, v, 2, 3); }
 }  // namespace
 
-template <int NG>
+template <int NG, class G>
 __global__ __launch_bounds__(WNTH * NG, 4) void wino_f23_kernel(const ConvGemmParams p) {
   constexpr int NTH = WNTH * NG;
+  constexpr int BTY = G::BTY, BTX = G::BTX, WRH = G::RH, WRW = G::RW, PITCH = G::PITCH, WSTAGE = G::STAGE;
   constexpr int WNLD = (WRH * WRW * (WKC / 4) + NTH - 1) / NTH;
   const long long t_entry = (long long)__builtin_amdgcn_s_memrealtime();
   DC_KARG_TOUCH(ka0, ka1, ka2, ka3, ka4);
@@ -1589,7 +1628,7 @@ __global__ __launch_bounds__(WNTH * NG, 4) void wino_f23_kernel(const ConvGemmPa
   const int n = dc_fastdiv(nph, p.w_div_dd), ph = nph - n * (d * d);
   const int phy = dc_fastdiv(ph, p.w_div_d), phx = ph - phy * d;
   const int by = dc_fastdiv(brem, p.w_div_nbx), bx = brem - by * NBX;
-  const int oy0 = 2 * WBTY * by - 1, ox0 = 2 * WBTX * bx - 1;  // phase-grid coordinates of staged pixel (0, 0): pad 1
+  const int oy0 = 2 * BTY * by - 1, ox0 = 2 * BTX * bx - 1;  // phase-grid coordinates of staged pixel (0, 0): pad 1
   DC_KARG_HOLD(ka0, ka1, ka2, ka3, ka4);  // the block decode above needed kernel arguments: the dummy loads have landed
   const int kg = lane >> 4;
   const int grp = NG == 1 ? 0 : __builtin_amdgcn_readfirstlane(wave >> 3);  // (an SGPR: it enters the filter loads' soffset)
@@ -1611,11 +1650,13 @@ __global__ __launch_bounds__(WNTH * NG, 4) void wino_f23_kernel(const ConvGemmPa
     const int iy = phy + d * (oy0 + py), ix = phx + d * (ox0 + px);
     const bool ok = pix < WRH * WRW && oy0 + py >= 0 && ox0 + px >= 0 && iy < H && ix < W;
     gofs[q] = ok ? (unsigned)(iy * p.x_row_stride + ix * C + cq * 4) * 4u : kOOB;
-    sofs[q] = (pix < WRH * WRW ? wino_rowbase(py) + px * WPSTR + cq * 4 : WSTAGE - 8 + (t & 1) * 4) >> 2;  // in float4 units (past the block: the dump slot)
+    sofs[q] = (pix < WRH * WRW ? py * PITCH + px * WPSTR + cq * 4 : WSTAGE - 8 + (t & 1) * 4) >> 2;  // in float4 units (past the block: the dump slot)
   }
-  const int r = (lane & 15) >> 3, c = lane & 7;
-  const int ofs_a = wino_rowbase(2 * (2 * tf + r) + ra) + 2 * c * WPSTR + kg * 4;
-  const int ofs_b = wino_rowbase(2 * (2 * tf + r) + rb) + 2 * c * WPSTR + kg * 4;
+  // (a fragment row without a tile reads the last tile's patch: in range, a broadcast, and kept out of the stores below)
+  const int qt = G::NT < 16 ? min(lane & 15, G::NT - 1) : lane & 15;
+  const int r = qt / G::FC, c = G::fcol(tf) + qt % G::FC;
+  const int ofs_a = (2 * (G::frow(tf) + r) + ra) * PITCH + 2 * c * WPSTR + kg * 4;
+  const int ofs_b = (2 * (G::frow(tf) + r) + rb) * PITCH + 2 * c * WPSTR + kg * 4;
   f32x4 acc[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -1758,9 +1799,9 @@ __global__ __launch_bounds__(WNTH * NG, 4) void wino_f23_kernel(const ConvGemmPa
     }
     float v = a == 0 ? p0 + p1 + p2 : p1 - p2 - p3;
     const int q = 4 * (lane >> 4) + r4;  // D layout: row (tile in fragment) = 4*(lane/16) + r, col (channel) = lane%16
-    const int ty = by * WBTY + 2 * tf + (q >> 3), tx = bx * WBTX + (q & 7);
+    const int ty = by * BTY + G::frow(tf) + q / G::FC, tx = bx * BTX + G::fcol(tf) + q % G::FC;
     const int oy = phy + d * (2 * ty + a), ox = phx + d * (2 * tx + bq);
-    if (oy < p.OH && ox < p.OW) {
+    if ((G::NT == 16 || q < G::NT) && oy < p.OH && ox < p.OW) {
       const long off = (long)n * p.y_img_stride + (long)oy * p.y_row_stride + (long)ox * p.y_pix_stride + co;
       v = v * sc + sh;
       if (rbp) v += rbp[off];
@@ -1805,11 +1846,23 @@ bool wino_eligible(const ConvGemmParams& p) {
   return true;
 }
 
-long wino_grid(const ConvGemmParams& p) {
+long wino_blocks(int TY, int TX, int bty, int btx) { return (long)((TY + bty - 1) / bty) * ((TX + btx - 1) / btx); }
+
+template <class G>
+static long wino_grid_of(const ConvGemmParams& p) {
   const int d = p.ddy;
   const int TY = ((p.OH + d - 1) / d + 1) / 2, TX = ((p.OW + d - 1) / d + 1) / 2;
-  return (long)p.NB * d * d * ((TY + WBTY - 1) / WBTY) * ((TX + WBTX - 1) / WBTX) * (p.Cout / WBN);
+  return (long)p.NB * d * d * wino_blocks(TY, TX, G::BTY, G::BTX) * (p.Cout / WBN);
 }
+long wino_grid(const ConvGemmParams& p) { return wino_grid_of<WinoG48>(p); }
+
+// the 5 x 6 forms enter the per-shape timing only where they need strictly fewer workgroups than the 4 x 8 ones (at 544x736: the dilated
+// res5 layers, 9 x 12 tiles per phase image: 4 blocks against 6; res4 takes 16 against 15, res3 56 against 54, res2 224 against 204): the
+// other Winograd layers keep their tuning time.  set_tile takes them wherever the kernel is eligible.  (The tune signature, Net::tune_key, does
+// not carry the dilation: two 3x3 layers of one net that differ in nothing but their dilation share a signature, the first of them in the plan
+// decides whether the 5 x 6 forms are timed for both, and both run the form chosen — correct on either, the kernel is general; no such pair
+// exists in the ResNet nets this library lowers.)
+static bool wino_fewer_blocks(const ConvGemmParams& p) { return wino_grid_of<WinoG56>(p) < wino_grid_of<WinoG48>(p); }
 
 size_t wino_packed_floats(int Cout, int Cin) { return (size_t)16 * Cout * Cin; }
 
@@ -1831,14 +1884,14 @@ void wino_pack_filters(const float* g, int Cout, int Cin, float* out) {
     }
 }
 
-// NG = 1: wino_f23 (8 waves per workgroup), 2: wino_f23_w16 (16)
-template <int NG>
+// NG = 1: wino_f23 (8 waves per workgroup), 2: wino_f23_w16 (16); G: the block geometry (4 x 8, or 5 x 6: wino_f23_5x6, wino_f23_5x6_w16)
+template <int NG, class G>
 static int launch_wino_f23(const ConvGemmParams& p, void* stream) {
   if (p.esize != 4 || !wino_eligible(p)) return (int)hipErrorInvalidValue;
-  const long grid = wino_grid(p);
+  const long grid = wino_grid_of<G>(p);
   if (grid <= 0) return 0;
   if (grid > 0x7fffffffL) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(wino_f23_kernel<NG>, dim3((unsigned)grid), dim3(NG * WNTH), 0, (hipStream_t)stream, wino_launch_params(p, grid, WBTY, WBTX, 1));
+  hipLaunchKernelGGL((wino_f23_kernel<NG, G>), dim3((unsigned)grid), dim3(NG * WNTH), 0, (hipStream_t)stream, wino_launch_params(p, grid, G::BTY, G::BTX, 1));
   return (int)hipGetLastError();
 }
 
@@ -1850,10 +1903,10 @@ static const char* const kWinoSlots[7] = {"index setup", "first loads issued", "
 static const char* const kStreamSlots[7] = {"prologue requests issued", "first stage + filters landed", "the first D steps", "the other steps",
                                             "drain", "-", "exit"};
 static constexpr ConvForm kForms[kNumForms] = {
-    // variant, name, label, ekind, geometry, waves, slots, eligible, grid, launch, own_scale, merges, prepare_multi, launch_multi, sibling, env
-    {kWinoVariant, "wino_f23", "wino_f23<4x8x16>", kElemF32, kForm3x3, 8, kWinoSlots, wino_eligible, wino_grid, launch_wino_f23<1>,
+    // variant, name, label, ekind, geometry, waves, slots, eligible, grid, launch, own_scale, merges, prepare_multi, launch_multi, sibling, env, offered
+    {kWinoVariant, "wino_f23", "wino_f23<4x8x16>", kElemF32, kForm3x3, 8, kWinoSlots, wino_eligible, wino_grid, launch_wino_f23<1, WinoG48>,
      false, false, nullptr, nullptr, kWinoVariant16, "DC_WINOGRAD"},
-    {kWinoVariant16, "wino_f23_w16", "wino_f23<4x8x16_w16>", kElemF32, kForm3x3, 16, kWinoSlots, wino_eligible, wino_grid, launch_wino_f23<2>,
+    {kWinoVariant16, "wino_f23_w16", "wino_f23<4x8x16_w16>", kElemF32, kForm3x3, 16, kWinoSlots, wino_eligible, wino_grid, launch_wino_f23<2, WinoG48>,
      false, false, nullptr, nullptr, kWinoVariant, "DC_WINOGRAD"},
     {kWinoHalf, "wino_h23", "wino_h23<2x4x8x64>", kElemF16, kForm3x3, 8, kWinoSlots, wino_half_eligible, wino_half_grid, launch_wino_half,
      true, true, nullptr, nullptr, -1, "DC_WINOGRAD"},
@@ -1865,6 +1918,10 @@ static constexpr ConvForm kForms[kNumForms] = {
      false, true, nullptr, nullptr, -1, "DC_STREAM1X1"},
     {kStemFloat, "ws7x7f", "ws7x7f<16x64>", kElemF32, kFormStem, 4, kStreamSlots, stem_ws_eligible, stem_ws_grid, launch_stem_ws,
      false, true, nullptr, nullptr, -1, "DC_STEM"},
+    {kWinoVariant56, "wino_f23_5x6", "wino_f23<5x6x16>", kElemF32, kForm3x3, 8, kWinoSlots, wino_eligible, wino_grid_of<WinoG56>, launch_wino_f23<1, WinoG56>,
+     false, false, nullptr, nullptr, kWinoVariant56x16, "DC_WINOGRAD", wino_fewer_blocks},
+    {kWinoVariant56x16, "wino_f23_5x6_w16", "wino_f23<5x6x16_w16>", kElemF32, kForm3x3, 16, kWinoSlots, wino_eligible, wino_grid_of<WinoG56>, launch_wino_f23<2, WinoG56>,
+     false, false, nullptr, nullptr, kWinoVariant56, "DC_WINOGRAD", wino_fewer_blocks},
 };
 
 static constexpr bool forms_in_variant_order() {
@@ -1873,6 +1930,12 @@ static constexpr bool forms_in_variant_order() {
   return true;
 }
 static_assert(forms_in_variant_order(), "row i of kForms is variant kFormVariant0 + i");
+
+long wino_form_blocks(int variant, int TY, int TX) {
+  if (variant == kWinoVariant || variant == kWinoVariant16) return wino_blocks(TY, TX, WinoG48::BTY, WinoG48::BTX);
+  if (variant == kWinoVariant56 || variant == kWinoVariant56x16) return wino_blocks(TY, TX, WinoG56::BTY, WinoG56::BTX);
+  return -1;
+}
 
 const ConvForm* conv_form(int variant) {
   return variant >= kFormVariant0 && variant < kFormVariant0 + kNumForms ? &kForms[variant - kFormVariant0] : nullptr;

@@ -101,6 +101,8 @@ void Net::autotune() {
     for (int v = kFormVariant0; v < kFormVariant0 + kNumForms; ++v) vs.push_back(v);
     for (int v : vs) {
       if (!l.takes_tile(v)) continue;
+      if (const ConvForm* f = conv_form(v))
+        if (f->offered && !f->offered(l.cg)) continue;  // (a form that is a candidate for some shapes only: the 5 x 6-tile Winograd blocks; asked of the signature's first launch)
       Launch trial = l;
       trial.variant = v;
       c.push_back({burst_ms(trial), v});

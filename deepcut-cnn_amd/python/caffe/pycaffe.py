@@ -147,6 +147,7 @@ def _load():
         "dc_conv_bf16_variant_count": (ci, []),
         "dc_conv_bf16_variant_name": (cp, [ci]),
         "dc_wino_half_pack": (ci, [C.c_void_p, ci, ci, ci, C.c_void_p, C.c_void_p]),
+        "dc_wino_blocks": (ci, [cp, ci, ci]),
         "dc_stream1x1_pack": (ci, [C.c_void_p, ci, ci, C.c_void_p]),
         "dc_stem7x7_pack": (ci, [C.c_void_p, ci, C.c_void_p]),
         "dc_stream1x1f_pack": (ci, [C.c_void_p, ci, ci, C.c_void_p]),
@@ -194,6 +195,11 @@ def conv_variants():
 def conv_variants_bf16():
     """[name] of the bfloat16 tile variants (their own table), in DC_CONV_VARIANT_BF16 index order."""
     return [(_lib.dc_conv_bf16_variant_name(i) or b"").decode() for i in range(_lib.dc_conv_bf16_variant_count())]
+
+
+def wino_blocks(tile, tiles_y, tiles_x):
+    """dc_wino_blocks: the tile blocks the float32 Winograd form `tile` needs for a tiles_y x tiles_x tile grid (-1: not such a form)."""
+    return _lib.dc_wino_blocks(tile.encode(), int(tiles_y), int(tiles_x))
 
 
 def stream1x1_pack(g):

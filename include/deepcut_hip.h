@@ -350,6 +350,10 @@ const char* dc_conv_bf16_variant_name(int i);
  * lane = 32 * ((ci % 16) / 8) + co % 32, element = ci % 8.  Diagnostics / tests (the host half of the kernel's parity:
  * tests/test_wino_half_pack.py); the reference has no counterpart (its 3x3 layers are im2col + SGEMM, base_conv_layer.cpp:257-280). */
 int dc_wino_half_pack(const float* g, int cout, int cin, int rowscale, float* out, float* row_scale);
+/* the tile blocks (= workgroups per image phase and 16 output channels) that the float32 Winograd form `tile` (`wino_f23`, `wino_f23_w16`:
+ * 4 x 8 tiles; `wino_f23_5x6`, `wino_f23_5x6_w16`: 5 x 6) needs for a grid of tiles_y x tiles_x 2x2-output tiles; -1 for any other name.
+ * The 5 x 6 forms are candidates of the per-shape timing where they need strictly fewer blocks.  Diagnostics / tests.               */
+int dc_wino_blocks(const char* tile, int tiles_y, int tiles_x);
 
 /* the filter images of the two float16 kernels added in round 6, made on the host exactly as the lowering makes them (diagnostics / tests:
  * tests/test_stream_pack.py emulates the matrix instruction's operand layout on them; the reference has no counterpart — its 1x1 layers

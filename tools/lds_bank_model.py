@@ -32,6 +32,30 @@ def ds_read_b128_cycles(addr):
     return total
 
 
+def ds_write_b128_cycles(addr):
+    """addr: 64 float indices (each the start of 4 consecutive floats) -> LDS-array cycles of one ds_write_b128: eight groups of eight
+    consecutive lanes, 32 write banks (bank = (byte address / 4) mod 32); 8 is conflict-free."""
+    total = 0
+    for g in range(8):
+        banks = {}
+        for lane in range(8 * g, 8 * g + 8):
+            for d in range(4):
+                banks.setdefault((addr[lane] + d) % 32, set()).add(addr[lane] + d)
+        total += max(len(v) for v in banks.values())
+    return total
+
+
+def wino_stage_store(rows, cols, row_pitch, wave, q, nth=512, pixel_pitch=36):
+    """Float index per lane of staging store q of wave `wave` (kernels.hip, sofs): element e = thread + q * nth -> pixel e / 8 (row-major over
+    the rows x cols staged pixels), channel quad e % 8; past the block: the dump slot."""
+    out = []
+    for lane in range(64):
+        e = wave * 64 + lane + q * nth
+        pix, cq = e // 8, e % 8
+        out.append((pix // cols) * row_pitch + (pix % cols) * pixel_pitch + cq * 4 if pix < rows * cols else rows * row_pitch + (lane & 1) * 4)
+    return out
+
+
 def wino_patch_row_read(pixel_pitch, row_pitch, row0, skew=lambda row: 0):
     """Float index per lane of the Winograd kernel's patch-row read (kernels.hip, lread): first tile row of the fragment at staged
     row `row0`, the second one two rows below."""
@@ -48,6 +72,23 @@ def wino_layout_cycles(pixel_pitch, row_pitch, skew=lambda row: 0):
     return max(ds_read_b128_cycles(wino_patch_row_read(pixel_pitch, row_pitch, row0, skew)) for row0 in range(8))
 
 
+def wino_geom_read(fr, fc, side, row_pitch, tf, row0, pixel_pitch=36):
+    """Float index per lane of a patch-row read under a block geometry of kernels.hip (WinoGeom): a fragment of fr x fc tiles, lane
+    q = lane & 15 -> tile (q / fc, q % fc), the two fragments of a block stacked (tile rows fr * tf + ..) or side by side (tile columns
+    fc * tf + ..); a fragment row without a tile reads the last tile's address.  row0: the patch row (0..3) inside the tile."""
+    out = []
+    for lane in range(64):
+        q, kg = min(lane & 15, fr * fc - 1), lane >> 4
+        tr, tc = (0 if side else fr * tf) + q // fc, (fc * tf if side else 0) + q % fc
+        out.append((2 * tr + row0) * row_pitch + 2 * tc * pixel_pitch + 4 * kg)
+    return out
+
+
+def wino_geom_cycles(fr, fc, side, row_pitch, pixel_pitch=36):
+    """Worst case over both fragments and the four patch rows of a tile."""
+    return max(ds_read_b128_cycles(wino_geom_read(fr, fc, side, row_pitch, tf, row0, pixel_pitch)) for tf in (0, 1) for row0 in range(4))
+
+
 if __name__ == "__main__":
     print("library layout (pixel pitch 36, row pitch 672):", wino_layout_cycles(36, 672), "LDS cycles per ds_read_b128")
     print("round-1 layout (pixel pitch 36, row pitch 648 + 4-float skew per row pair):",
@@ -55,3 +96,7 @@ if __name__ == "__main__":
     for pp in (36, 40, 44, 52, 68):
         ok = [rp for rp in range(18 * pp, 18 * pp + 68, 4) if wino_layout_cycles(pp, rp) == 4]
         print("pixel pitch %d: conflict-free row pitches %s" % (pp, ok or "none within +64 floats"))
+    print("4 x 8 blocks as a geometry {2 x 8, stacked, 672}:", wino_geom_cycles(2, 8, False, 672), "LDS cycles")
+    fits = [rp for rp in range(14 * 36, 14 * 36 + 68, 4) if 3 * (12 * rp + 8) * 4 <= 80 * 1024]
+    print("5 x 6 blocks {5 x 3, side by side}: row pitches of a 12 x 14 halo that keep three stages within 80 KB: %d..%d; conflict-free: %s"
+          % (fits[0], fits[-1], [rp for rp in fits if wino_geom_cycles(5, 3, True, rp) == 4]))
