@@ -2,6 +2,7 @@
 // C++ type crosses it.
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -504,6 +505,39 @@ int dc_net_decode_pairwise(dc_net* net, double scale, int ndet, const int* detec
     REQUIRE(out);
   }
   return guard([&] { N(net)->decode_pairwise(scale, ndet, detections, mean, stdev, out); });
+}
+
+int dc_pair_stats_read(const char* path, int max_edges, int* n_edges, int* edges, double* mean, double* stdev) {
+  REQUIRE(path);
+  REQUIRE(n_edges);
+  REQUIRE(edges);
+  REQUIRE(mean);
+  REQUIRE(stdev);
+  *n_edges = 0;
+  if (max_edges < 0) return fail(DC_EINVAL, "max_edges must be >= 0");
+  return guard([&] {
+    const PairStats st = read_pair_stats(path);
+    *n_edges = st.n_edges();
+    if (st.n_edges() > max_edges)
+      throw DcError(DC_EINVAL, std::string("pair statistics ") + path + ": " + std::to_string(st.n_edges()) + " edges, the caller's arrays hold max_edges = " +
+                                   std::to_string(max_edges));
+    std::copy(st.edges.begin(), st.edges.end(), edges);
+    std::copy(st.mean.begin(), st.mean.end(), mean);
+    std::copy(st.stdev.begin(), st.stdev.end(), stdev);
+  });
+}
+
+int dc_net_assemble_people(dc_net* net, const dc_assemble_params* p, int n_edges, const int* edges, const double* mean, const double* stdev,
+                           const int* joint_order, int* n_people, double* people, int* cand, double* cost) {
+  REQUIRE(net);
+  REQUIRE(p);
+  REQUIRE(n_people);
+  REQUIRE(people);
+  if (n_edges > 0) REQUIRE(edges);
+  return guard([&] {
+    Net::AssembleParams q{p->scale, p->threshold, p->radius, p->max_det, p->max_cost, p->seed_threshold, p->max_people, p->min_joints};
+    N(net)->assemble_people(q, n_edges, edges, mean, stdev, joint_order, n_people, people, cand, cost);
+  });
 }
 
 int dc_net_flops(dc_net* net, double* flops) {

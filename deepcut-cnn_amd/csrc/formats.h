@@ -79,4 +79,15 @@ ModelFile read_hdf5_weights(const std::string& path);
 
 std::string read_file(const std::string& path);  // throws DcError(DC_EIO, "Could not open file ...")
 
+// ---- pair statistics (`joint_pairs_stats`, caffe.proto:1184) --------------------------------------
+// Text: repeated blocks of `# <name>`, `<rows> <cols>`, rows x cols numbers, everything whitespace-separated.  The first three
+// matrices are the edges [E][2] (1-based class ids: joint = class - 1), the means [E][2] and the standard deviations [E][2] of the
+// pairwise regression targets (pose_data_layer.cpp:453-455).  Throws DC_EIO / DC_EINVAL naming what is wrong.  (people.cpp)
+struct PairStats {
+  std::vector<int> edges;            // [E][2], 0-based joints
+  std::vector<double> mean, stdev;   // [E][2]
+  int n_edges() const { return (int)(edges.size() / 2); }
+};
+PairStats read_pair_stats(const std::string& path);
+
 }  // namespace dc

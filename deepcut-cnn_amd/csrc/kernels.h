@@ -316,6 +316,23 @@ int launch_pairwise_decode(const void* next, int ncp, int nc0, int ekind, int NB
                            const int* det /* [ndet][3] image, row, col */, const double* mean, const double* stdev, double* out,
                            void* stream);
 
+// Bottom-up assembly of people from those candidates (people.hip; the grouping rule is this project's own: the reference stops at
+// the maps).  Limits of the two kernels: candidates per joint, joints, people per image.
+constexpr int kPeopleMaxDet = 64, kPeopleMaxJoints = 32, kPeopleMaxPeople = 256;
+// pair cost: counts / dets are part_select's outputs (max_det <= kPeopleMaxDet), lut[a*J + c] = the lowest edge index whose (joint,
+//           next joint) is (a, c), or -1; mean / stdev [E][2] (never null: 0 / 1 where the caller has none).  With d_f = |prediction
+//           of (a, i)'s cell on edge a->c - position of (c, k)| and d_r = |prediction of (c, k)'s cell on edge c->a - position of
+//           (a, i)| (image pixels), cost[(((b*J + a)*J + c)*max_det + i)*max_det + k] = scale * mean of those of the two that have an
+//           edge; +inf without an edge, for a == c and for slots beyond a count.  Symmetric: [c][a][k][i] is the same number.
+int launch_pair_cost(const void* next, int ncp, int nc0, int ekind, int NB, int H, int W, int J, int max_det, double scale, const int* counts,
+                     const double* dets, const int* lut, const double* mean, const double* stdev, double* cost, void* stream);
+// greedy assembly (one workgroup per image): order [J] = the joints in processing order; link: NB*max_people*max_det doubles of
+//           scratch; -> n_people [NB], people [NB][max_people][J][3] = x, y, score (0 where a joint is missing), cand
+//           [NB][max_people][J] = candidate index or -1.  The rule: include/deepcut_hip.h, dc_net_assemble_people.
+int launch_assemble(int NB, int J, int max_det, int max_people, int min_joints, double max_cost, double seed_thr, const int* counts,
+                    const double* dets, const double* cost, const int* order, double* link, int* n_people, double* people, int* cand,
+                    void* stream);
+
 // Image pre-processing of the demo (python/pose/estimate_pose.py:83-103) on the device: replicate padding by
 // coordinate clamping, Pillow's two-pass 8-bit bilinear resample (22-bit fixed-point weights from the host),
 // mean subtraction and the zero canvas, written straight into the network's NHWC input image.

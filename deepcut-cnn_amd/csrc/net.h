@@ -328,6 +328,18 @@ struct Net {
   // multi-person consumers of the maps of the last forward (encoding: pose_data_layer.cpp:686-802)
   void detect_parts(double scale, float thr, int radius, int max_det, int* counts, double* dets);
   void decode_pairwise(double scale, int ndet, const int* det, const double* mean, const double* stdev, double* out);
+  // the people of every image of the last forward: candidates (part_select), pair costs and greedy assembly (people.cpp / people.hip)
+  // back to back on the device, only the results travel (dc_net_assemble_people; the grouping rule is this project's own)
+  struct AssembleParams {
+    double scale;
+    float threshold;
+    int radius, max_det;
+    double max_cost;
+    float seed_threshold;
+    int max_people, min_joints;
+  };
+  void assemble_people(const AssembleParams& p, int n_edges, const int* edges, const double* mean, const double* stdev, const int* joint_order,
+                       int* n_people, double* people, int* cand, double* cost);
   // front half of forward_images: the uint8 pixels -> the network's NHWC input image, enqueued on s (the plan of the canvas
   // shape is active afterwards); returns the canvas height / width
   void prep_images(const unsigned char* bgr, int n, int h, int w, double scale, bool is_device, void* s);

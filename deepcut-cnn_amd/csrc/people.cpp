@@ -1,0 +1,202 @@
+// people.cpp — bottom-up assembly of people (dc_net_assemble_people) and the reader of the pair-statistics file it is fed from
+// (dc_pair_stats_read).  The kernels are in people.hip; the grouping rule is stated in include/deepcut_hip.h.
+//
+// PARITY UNPINNED BY THE REFERENCE: eldar/deepcut-cnn has no consumer of `next_pred` (it stops at the maps); only the
+// label encoding of src/caffe/layers/pose_data_layer.cpp:686-802 is restated, as in the two decoders of net_image.cpp.
+#include <cctype>
+
+#include "net_internal.h"
+
+namespace dc {
+
+// ---- the `joint_pairs_stats` file ------------------------------------------------------------------------------------
+namespace {
+struct StatMatrix {
+  std::string name;
+  long rows = 0, cols = 0;
+  std::vector<double> v;
+};
+
+struct StatTokens {
+  const std::string& s;
+  const std::string& path;
+  size_t p = 0;
+  StatTokens(const std::string& text, const std::string& file) : s(text), path(file) {}
+  bool next(std::string& tok) {
+    while (p < s.size() && std::isspace((unsigned char)s[p])) ++p;
+    if (p >= s.size()) return false;
+    const size_t b = p;
+    while (p < s.size() && !std::isspace((unsigned char)s[p])) ++p;
+    tok.assign(s, b, p - b);
+    return true;
+  }
+  [[noreturn]] void bad(const std::string& what) const { throw DcError(DC_EINVAL, "pair statistics " + path + ": " + what); }
+  double number(const std::string& tok, const std::string& where) const {
+    char* end = nullptr;
+    const double v = std::strtod(tok.c_str(), &end);
+    if (end == tok.c_str() || *end) bad("'" + tok + "' is not a number (" + where + ")");
+    return v;
+  }
+  long dimension(const std::string& where) {
+    std::string tok;
+    if (!next(tok)) bad("truncated block: " + where + " has no size line");
+    const double v = number(tok, "size of " + where);
+    if (!(v >= 0 && v <= 1e6 && v == std::floor(v))) bad("size '" + tok + "' of " + where + " is not a whole number of rows / columns");
+    return (long)v;
+  }
+};
+}  // namespace
+
+PairStats read_pair_stats(const std::string& path) {
+  const std::string text = read_file(path);
+  StatTokens tk(text, path);
+  std::vector<StatMatrix> mats;
+  std::string tok;
+  while (mats.size() < 3 && tk.next(tok)) {
+    StatMatrix m;
+    if (tok != "#") tk.bad("expected '# <name>' in front of matrix " + std::to_string(mats.size()) + ", found '" + tok + "'");
+    if (!tk.next(m.name)) tk.bad("truncated block: '#' without a matrix name");
+    const std::string where = "matrix " + std::to_string(mats.size()) + " ('" + m.name + "')";
+    m.rows = tk.dimension(where);
+    m.cols = tk.dimension(where);
+    m.v.reserve((size_t)(m.rows * m.cols));
+    for (long i = 0; i < m.rows * m.cols; ++i) {
+      if (!tk.next(tok))
+        tk.bad("truncated block: " + where + " holds " + std::to_string(i) + " of " + std::to_string(m.rows * m.cols) + " numbers");
+      m.v.push_back(tk.number(tok, where));
+    }
+    mats.push_back(std::move(m));
+  }
+  if (mats.size() < 3)
+    tk.bad("fewer than three matrices (edges, means, standard deviations): found " + std::to_string(mats.size()));
+  for (size_t i = 0; i < 3; ++i)
+    if (mats[i].cols != 2)
+      tk.bad("matrix " + std::to_string(i) + " ('" + mats[i].name + "') is " + std::to_string(mats[i].rows) + " x " +
+             std::to_string(mats[i].cols) + ", not E x 2");
+  for (size_t i = 1; i < 3; ++i)
+    if (mats[i].rows != mats[0].rows)
+      tk.bad("differing row counts: " + std::to_string(mats[0].rows) + " edges, but matrix " + std::to_string(i) + " ('" + mats[i].name +
+             "') has " + std::to_string(mats[i].rows) + " rows");
+  PairStats st;
+  const size_t n = (size_t)mats[0].rows * 2;
+  st.edges.resize(n);
+  for (size_t i = 0; i < n; ++i) {
+    const double c = mats[0].v[i];
+    if (!(c >= 1 && c <= 1e6 && c == std::floor(c)))
+      tk.bad("edge " + std::to_string(i / 2) + ": class id " + std::to_string(c) + " is not a whole number >= 1 (class ids are 1-based)");
+    st.edges[i] = (int)c - 1;
+  }
+  for (size_t i = 0; i < n; ++i) {
+    if (!std::isfinite(mats[1].v[i])) tk.bad("edge " + std::to_string(i / 2) + ": mean is not finite");
+    const double s = mats[2].v[i];
+    if (!(std::isfinite(s) && s > 0))
+      tk.bad("edge " + std::to_string(i / 2) + ": standard deviation " + std::to_string(s) + " is not positive and finite");
+  }
+  st.mean = std::move(mats[1].v);
+  st.stdev = std::move(mats[2].v);
+  return st;
+}
+
+// ---- the device path ---------------------------------------------------------------------------------------------------
+// Stage A = Net::detect_parts' launch with its outputs left in the scratch buffer, stage B = launch_pair_cost, stage C =
+// launch_assemble: three launches on the net's stream with nothing in between, then the downloads of the results.
+void Net::assemble_people(const AssembleParams& q, int n_edges, const int* edges, const double* mean, const double* stdev,
+                          const int* joint_order, int* n_people, double* people, int* cand, double* cost) {
+  auto bad = [](const std::string& m) { throw DcError(DC_EINVAL, "assemble_people: " + m); };
+  if (!(q.scale > 0) || !std::isfinite(q.scale)) bad("scale must be positive");
+  if (!(q.threshold >= 0.f)) bad("threshold must be >= 0");
+  if (q.radius < 0 || q.radius > 64) bad("radius must be in [0, 64]");
+  if (q.max_det < 1 || q.max_det > kPeopleMaxDet) bad("max_det must be in [1, " + std::to_string(kPeopleMaxDet) + "]");
+  if (!(q.max_cost >= 0) || !std::isfinite(q.max_cost)) bad("max_cost must be finite and >= 0");
+  if (!std::isfinite(q.seed_threshold)) bad("seed_threshold must be finite");
+  if (q.max_people < 1 || q.max_people > kPeopleMaxPeople) bad("max_people must be in [1, " + std::to_string(kPeopleMaxPeople) + "]");
+  auto ip = blob_index.find("prob");
+  if (ip == blob_index.end()) throw DcError(DC_EINVAL, "net has no 'prob' blob");
+  const std::vector<int>& pshape = blobs[ip->second]->st->shape;
+  if (pshape.size() != 4) throw DcError(DC_ESHAPE, "'prob' is not a 4-D map");
+  const int J = pshape[1];
+  if (J < 1 || J > kPeopleMaxJoints)
+    throw DcError(DC_ESHAPE, "assemble_people: " + std::to_string(J) + " joints, the assembly holds up to " + std::to_string(kPeopleMaxJoints));
+  if (q.min_joints < 1 || q.min_joints > J) bad("min_joints must be in [1, " + std::to_string(J) + "]");
+  if (n_edges < 0) bad("n_edges must be >= 0");
+  // the lookup table of both directions: lut[a*J + c] = the lowest edge index whose (joint, next joint) is (a, c)
+  std::vector<int> table((size_t)J * J + J, -1);
+  for (int l = 0; l < n_edges; ++l) {
+    const int a = edges[2 * l], c = edges[2 * l + 1];
+    if (a < 0 || a >= J || c < 0 || c >= J)
+      bad("edge " + std::to_string(l) + " (" + std::to_string(a) + ", " + std::to_string(c) + ") names a joint outside [0, " + std::to_string(J) + ")");
+    if (a == c) bad("edge " + std::to_string(l) + " joins joint " + std::to_string(a) + " to itself");
+    if (table[(size_t)a * J + c] < 0) table[(size_t)a * J + c] = l;
+  }
+  int* order = table.data() + (size_t)J * J;
+  {
+    std::vector<char> seen(J, 0);
+    for (int i = 0; i < J; ++i) {
+      const int j = joint_order ? joint_order[i] : i;
+      if (j < 0 || j >= J || seen[j]) bad("joint_order is not a permutation of 0.." + std::to_string(J - 1) + " (entry " + std::to_string(i) + ")");
+      seen[j] = 1;
+      order[i] = j;
+    }
+  }
+  for (int i = 0; i < 2 * n_edges; ++i) {
+    if (mean && !std::isfinite(mean[i])) bad("mean of edge " + std::to_string(i / 2) + " is not finite");
+    if (stdev && !(std::isfinite(stdev[i]) && stdev[i] > 0)) bad("std of edge " + std::to_string(i / 2) + " is not positive and finite");
+  }
+  // (the arguments above are refused with or without a device; from here on the device is needed)
+  if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "assemble_people() in CPU mode");
+  ensure_device();
+  const MapRef P = map_ref("prob"), L = map_ref("loc_pred"), N = map_ref("next_pred");
+  if (L.C != 2 * P.C || L.H != P.H || L.W != P.W || L.NB != P.NB || L.es != P.es)
+    throw DcError(DC_ESHAPE, "assemble_people: loc_pred must have 2 channels per joint and the score map's size");
+  if (N.H != P.H || N.W != P.W || N.NB != P.NB) throw DcError(DC_ESHAPE, "assemble_people: next_pred must have the score map's size");
+  if (N.C % 2 || n_edges != N.C / 2)
+    throw DcError(DC_ESHAPE, "assemble_people: " + std::to_string(n_edges) + " edges for a next_pred of " + std::to_string(N.C) +
+                                 " channels (2 per regression edge)");
+  const int NB = P.NB, MD = q.max_det, PP = q.max_people, E = n_edges, lists = NB * J;
+  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+  const size_t cnt_b = up((size_t)lists * sizeof(int));
+  const size_t spill_b = up((size_t)lists * P.H * P.W * sizeof(unsigned long long));
+  const size_t det_b = up((size_t)lists * MD * 5 * sizeof(double));
+  const size_t tab_b = up(table.size() * sizeof(int));
+  const size_t st_b = up((size_t)std::max(E, 1) * 4 * sizeof(double));
+  const size_t cost_b = up((size_t)NB * J * J * MD * MD * sizeof(double));
+  const size_t link_b = up((size_t)NB * PP * MD * sizeof(double));
+  const size_t np_b = up((size_t)NB * sizeof(int));
+  const size_t ppl_b = up((size_t)NB * PP * J * 3 * sizeof(double));
+  const size_t cand_b = up((size_t)NB * PP * J * sizeof(int));
+  unsigned char* base = (unsigned char*)scratch(cnt_b + spill_b + det_b + tab_b + st_b + cost_b + link_b + np_b + ppl_b + cand_b);
+  unsigned char* at = base;
+  auto take = [&](size_t b) {
+    unsigned char* r = at;
+    at += b;
+    return r;
+  };
+  int* d_cnt = (int*)take(cnt_b);
+  unsigned long long* d_spill = (unsigned long long*)take(spill_b);
+  double* d_det = (double*)take(det_b);
+  int* d_tab = (int*)take(tab_b);
+  double* d_mean = (double*)take(st_b);
+  double* d_std = d_mean + (size_t)2 * E;
+  double* d_cost = (double*)take(cost_b);
+  double* d_link = (double*)take(link_b);
+  int* d_np = (int*)take(np_b);
+  double* d_ppl = (double*)take(ppl_b);
+  int* d_cand = (int*)take(cand_b);
+  std::vector<double> stats((size_t)4 * E);
+  for (int i = 0; i < 2 * E; ++i) stats[i] = mean ? mean[i] : 0.0, stats[(size_t)2 * E + i] = stdev ? stdev[i] : 1.0;
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHECK(hipMemcpyAsync(d_tab, table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice, s));
+  if (E) HIPCHECK(hipMemcpyAsync(d_mean, stats.data(), stats.size() * sizeof(double), hipMemcpyHostToDevice, s));
+  KCHECK(launch_part_select(P.ptr, P.cp, P.c0, L.ptr, L.cp, L.c0, P.ek, NB, P.H, P.W, J, q.threshold, q.radius, q.scale, MD, d_spill, d_cnt,
+                            d_det, stream));
+  KCHECK(launch_pair_cost(N.ptr, N.cp, N.c0, N.ek, NB, N.H, N.W, J, MD, q.scale, d_cnt, d_det, d_tab, d_mean, d_std, d_cost, stream));
+  KCHECK(launch_assemble(NB, J, MD, PP, q.min_joints, q.max_cost, (double)q.seed_threshold, d_cnt, d_det, d_cost, d_tab + (size_t)J * J, d_link,
+                         d_np, d_ppl, d_cand, stream));
+  HIPCHECK(hipMemcpyAsync(n_people, d_np, (size_t)NB * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipMemcpyAsync(people, d_ppl, (size_t)NB * PP * J * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (cand) HIPCHECK(hipMemcpyAsync(cand, d_cand, (size_t)NB * PP * J * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (cost) HIPCHECK(hipMemcpyAsync(cost, d_cost, (size_t)NB * J * J * MD * MD * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+}
+
+}  // namespace dc

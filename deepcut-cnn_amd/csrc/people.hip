@@ -1,0 +1,278 @@
+// people.hip — bottom-up assembly of people from the part candidates and the pairwise maps of one forward (gfx950).
+//
+// PARITY UNPINNED BY THE REFERENCE: eldar/deepcut-cnn has no consumer of `next_pred` (it stops at the maps).  The
+// pair cost inverts the label encoding of its training layer (src/caffe/layers/pose_data_layer.cpp:686-802) exactly as
+// pairwise_decode_kernel does; the greedy grouping rule is this project's own.
+//
+// Two latency-class kernels behind part_select_kernel (kernels.hip), nothing of them on the forward path:
+//   pair_cost_kernel  one workgroup per (image, joint a): cost[b][a][c][i][k] for every partner joint c and candidate pair
+//   assemble_kernel   one workgroup per image: the greedy linking, joint after joint, on that cost tensor
+// All arithmetic is double, like the two decoders.  Double rate does not matter here: a full cost tensor (14 x 14 x 64 x 64) is
+// 1.6 M square roots, and the usual one (16 candidates) a sixteenth of it.
+#include <hip/hip_runtime.h>
+
+#include "kernels.h"
+
+namespace dc {
+
+namespace {
+template <typename F>
+int people_by_kind(int ekind, F&& f) {
+  if (ekind == kElemF16) return f((_Float16*)nullptr);
+  if (ekind == kElemBF16) return f((__bf16*)nullptr);
+  return f((float*)nullptr);
+}
+}  // namespace
+
+// where regression edge l, read at cell (row, col) of image b, puts the next joint (image pixels): pairwise_decode_kernel's arithmetic
+template <typename T>
+__device__ __forceinline__ void pair_predict(const T* __restrict__ next, int ncp, int nc0, int b, int H, int W, int row, int col, int l,
+                                             const double* __restrict__ mean, const double* __restrict__ stdev, double scale, double& x,
+                                             double& y) {
+  const T* p = next + (((long)b * H + row) * W + col) * ncp + nc0 + 2 * l;
+  x = ((double)col * 8.0 + 4.0 + (double)(float)p[0] * stdev[2 * l] + mean[2 * l]) / scale;
+  y = ((double)row * 8.0 + 4.0 + (double)(float)p[1] * stdev[2 * l + 1] + mean[2 * l + 1]) / scale;
+}
+
+// Workgroup (b, a) owns the unordered pairs {a, c} with c > a (and the diagonal block, which is +inf): the number is computed once
+// and stored at [a][c][i][k] and [c][a][k][i], so every element of the tensor is written exactly once and no atomics are needed.
+// LDS (doubles, structure of arrays so that 32 consecutive k are 32 consecutive 8-byte words = every bank once; the i side of a
+// read is one address per MD consecutive lanes, a broadcast):
+//   fx, fy [J][MD]  prediction of candidate (a, i) towards joint c (edge a -> c), loaded ONCE for every partner
+//   ax, ay [MD]     position of candidate (a, i)
+//   rx, ry [MD]     per partner: prediction of candidate (c, k) towards joint a (edge c -> a)
+//   cx, cy [MD]     per partner: position of candidate (c, k)
+// lut[a*J + c] = the lowest edge index l with edges[l] == (a, c), or -1.
+template <typename T>
+__global__ __launch_bounds__(256) void pair_cost_kernel(const T* __restrict__ next, int ncp, int nc0, int H, int W, int J, int MD,
+                                                        double scale, const int* __restrict__ counts, const double* __restrict__ dets,
+                                                        const int* __restrict__ lut, const double* __restrict__ mean,
+                                                        const double* __restrict__ stdev, double* __restrict__ cost) {
+  extern __shared__ double pc_lds[];
+  double* fx = pc_lds;
+  double* fy = fx + J * MD;
+  double* ax = fy + J * MD;
+  double* ay = ax + MD;
+  double* rx = ay + MD;
+  double* ry = rx + MD;
+  double* cx = ry + MD;
+  double* cy = cx + MD;
+  const int ba = blockIdx.x, b = ba / J, a = ba - b * J, t = threadIdx.x;
+  const int ma = min(counts[ba], MD);
+  const double* da = dets + (long)ba * MD * 5;
+  const double inf = __builtin_huge_val();
+  auto cell_ok = [&](int row, int col) { return row >= 0 && row < H && col >= 0 && col < W; };
+  for (int e = t; e < J * MD; e += 256) {
+    const int c = e / MD, i = e - c * MD;
+    const int l = lut[a * J + c];
+    double x = 0.0, y = 0.0;
+    if (i < ma && l >= 0) {
+      const int row = (int)da[i * 5 + 3], col = (int)da[i * 5 + 4];
+      if (cell_ok(row, col)) pair_predict(next, ncp, nc0, b, H, W, row, col, l, mean, stdev, scale, x, y);
+    }
+    fx[e] = x, fy[e] = y;
+  }
+  for (int i = t; i < MD; i += 256) {
+    ax[i] = i < ma ? da[i * 5] : 0.0;
+    ay[i] = i < ma ? da[i * 5 + 1] : 0.0;
+  }
+  const long blk = (long)MD * MD;
+  double* cb = cost + (long)b * J * J * blk;
+  for (int idx = t; idx < MD * MD; idx += 256) cb[((long)a * J + a) * blk + idx] = inf;
+  for (int c = a + 1; c < J; ++c) {
+    const int mc = min(counts[b * J + c], MD), lf = lut[a * J + c], lr = lut[c * J + a];
+    const double* dcand = dets + ((long)b * J + c) * MD * 5;
+    __syncthreads();  // the first time: fx .. ay are complete; later: the previous partner's readers are done with rx .. cy
+    for (int k = t; k < MD; k += 256) {
+      double x = 0.0, y = 0.0, px = 0.0, py = 0.0;
+      if (k < mc) {
+        px = dcand[k * 5], py = dcand[k * 5 + 1];
+        const int row = (int)dcand[k * 5 + 3], col = (int)dcand[k * 5 + 4];
+        if (lr >= 0 && cell_ok(row, col)) pair_predict(next, ncp, nc0, b, H, W, row, col, lr, mean, stdev, scale, x, y);
+      }
+      rx[k] = x, ry[k] = y, cx[k] = px, cy[k] = py;
+    }
+    __syncthreads();
+    double* ac = cb + ((long)a * J + c) * blk;
+    double* ca = cb + ((long)c * J + a) * blk;
+    for (int idx = t; idx < MD * MD; idx += 256) {
+      const int i = idx / MD, k = idx - i * MD;
+      double v = inf;
+      if (i < ma && k < mc && (lf >= 0 || lr >= 0)) {
+        double s = 0.0;
+        int n = 0;
+        if (lf >= 0) {
+          const double dx = fx[c * MD + i] - cx[k], dy = fy[c * MD + i] - cy[k];
+          s += sqrt(dx * dx + dy * dy);
+          ++n;
+        }
+        if (lr >= 0) {
+          const double dx = rx[k] - ax[i], dy = ry[k] - ay[i];
+          s += sqrt(dx * dx + dy * dy);
+          ++n;
+        }
+        v = scale * (s / (double)n);
+      }
+      ac[(long)i * MD + k] = v;
+      ca[(long)k * MD + i] = v;
+    }
+  }
+}
+
+// Greedy assembly of one image by one workgroup.  State in LDS: asg[p][a] = the candidate of joint a that person p holds, or -1.
+// Per joint j (in `order`): every (person, candidate) link cost L goes to this image's rows of `link` (global scratch: 256 people x
+// 64 candidates of doubles do not fit beside the rest; entry e = p*m + i is written and read by the same thread only), then the
+// links are taken one at a time by a workgroup-wide arg-min over (L, e) keys in LDS — e ascending IS (p, i) ascending, the tie rule —
+// and the candidates left over seed new people by a prefix count.  No step depends on thread timing: same inputs, same people.
+__global__ __launch_bounds__(256) void assemble_kernel(int J, int MD, int P, int min_joints, double max_cost, double seed_thr,
+                                                       const int* __restrict__ counts, const double* __restrict__ dets,
+                                                       const double* __restrict__ cost, const int* __restrict__ order,
+                                                       double* __restrict__ link, int* __restrict__ n_people,
+                                                       double* __restrict__ people, int* __restrict__ cand) {
+  extern __shared__ int asg[];  // [P][J]
+  __shared__ double red_l[256];
+  __shared__ int red_e[256];
+  __shared__ int flag[256];
+  __shared__ int slot[256];
+  __shared__ int used[64];
+  __shared__ int np_s;
+  const int b = blockIdx.x, t = threadIdx.x;
+  const double inf = __builtin_huge_val();
+  const int kNone = 0x7fffffff;
+  const long blk = (long)MD * MD;
+  const double* cb = cost + (long)b * J * J * blk;
+  double* L = link + (long)b * P * MD;
+  for (int e = t; e < P * J; e += 256) asg[e] = -1;
+  if (t == 0) np_s = 0;
+  __syncthreads();
+  for (int oj = 0; oj < J; ++oj) {
+    const int j = order[oj];
+    const int m = min(counts[b * J + j], MD);
+    const int np = np_s;
+    const int links = np * m;
+    if (t < 64) used[t] = 0;
+    // 1. link costs: the mean of the finite pair costs between candidate i and the joints the person already holds, a ascending
+    for (int e = t; e < links; e += 256) {
+      const int p = e / m, i = e - p * m;
+      double s = 0.0;
+      int n = 0;
+      for (int a = 0; a < J; ++a) {
+        const int ia = asg[p * J + a];
+        if (a == j || ia < 0) continue;
+        const double v = cb[((long)a * J + j) * blk + (long)ia * MD + i];
+        if (v < inf && v > -inf) s += v, ++n;
+      }
+      L[e] = n ? s / (double)n : inf;
+    }
+    __syncthreads();
+    // 2. linking: the smallest allowed link between a person without joint j and a free candidate, until none is left
+    for (;;) {
+      double bl = inf;
+      int be = kNone;
+      for (int e = t; e < links; e += 256) {
+        const int p = e / m, i = e - p * m;
+        if (used[i] || asg[p * J + j] >= 0) continue;
+        const double v = L[e];
+        if (v <= max_cost && v < bl) bl = v, be = e;  // e ascends within a thread: the first of equal costs stays
+      }
+      red_l[t] = bl, red_e[t] = be;
+      __syncthreads();
+      for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) {
+          const double l2 = red_l[t + s];
+          const int e2 = red_e[t + s];
+          if (e2 != kNone && (red_e[t] == kNone || l2 < red_l[t] || (l2 == red_l[t] && e2 < red_e[t]))) red_l[t] = l2, red_e[t] = e2;
+        }
+        __syncthreads();
+      }
+      const int win = red_e[0];  // the same value in every thread: the exit is uniform
+      if (win == kNone) break;
+      __syncthreads();  // everybody has read the winner before thread 0 of the next round overwrites it
+      if (t == 0) {
+        const int p = win / m, i = win - p * m;
+        asg[p * J + j] = i;
+        used[i] = 1;
+      }
+      __syncthreads();
+    }
+    // 3. seeding: the free candidates at or above the seed threshold, in list order, while there is room
+    __syncthreads();
+    if (t < 64) flag[t] = (t < m && !used[t] && dets[(((long)b * J + j) * MD + t) * 5 + 2] >= seed_thr) ? 1 : 0;
+    __syncthreads();
+    if (t < m && flag[t]) {
+      int rank = 0;
+      for (int i = 0; i < t; ++i) rank += flag[i];
+      if (np + rank < P) asg[(np + rank) * J + j] = t;
+    }
+    if (t == 0) {
+      int total = 0;
+      for (int i = 0; i < m; ++i) total += flag[i];
+      np_s = min(P, np + total);
+    }
+    __syncthreads();
+  }
+  // people with fewer than min_joints joints leave, the others keep their order
+  const int np = np_s;
+  {
+    int nj = 0;
+    if (t < np)
+      for (int a = 0; a < J; ++a) nj += asg[t * J + a] >= 0;
+    flag[t] = (t < np && nj >= min_joints) ? 1 : 0;
+  }
+  __syncthreads();
+  if (flag[t]) {
+    int rank = 0;
+    for (int i = 0; i < t; ++i) rank += flag[i];
+    slot[rank] = t;
+  }
+  if (t == 0) {
+    int total = 0;
+    for (int i = 0; i < np; ++i) total += flag[i];
+    np_s = total;
+    n_people[b] = total;
+  }
+  __syncthreads();
+  const int kept = np_s;
+  for (int e = t; e < P * J; e += 256) {
+    const int q = e / J, a = e - q * J;
+    int ci = -1;
+    double x = 0.0, y = 0.0, s = 0.0;
+    if (q < kept) {
+      ci = asg[slot[q] * J + a];
+      if (ci >= 0) {
+        const double* d = dets + (((long)b * J + a) * MD + ci) * 5;
+        x = d[0], y = d[1], s = d[2];
+      }
+    }
+    double* o = people + ((long)b * P * J + e) * 3;
+    o[0] = x, o[1] = y, o[2] = s;
+    cand[(long)b * P * J + e] = ci;
+  }
+}
+
+size_t pair_cost_lds_bytes(int J, int max_det) { return ((size_t)2 * J * max_det + 6 * (size_t)max_det) * sizeof(double); }
+
+int launch_pair_cost(const void* next, int ncp, int nc0, int ekind, int NB, int H, int W, int J, int max_det, double scale, const int* counts,
+                     const double* dets, const int* lut, const double* mean, const double* stdev, double* cost, void* stream) {
+  if (NB * J <= 0) return 0;
+  if (max_det < 1 || max_det > kPeopleMaxDet || J > kPeopleMaxJoints) return (int)hipErrorInvalidValue;
+  return people_by_kind(ekind, [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    hipLaunchKernelGGL(pair_cost_kernel<T>, dim3(NB * J), dim3(256), pair_cost_lds_bytes(J, max_det), (hipStream_t)stream, (const T*)next, ncp,
+                       nc0, H, W, J, max_det, scale, counts, dets, lut, mean, stdev, cost);
+    return (int)hipGetLastError();
+  });
+}
+
+int launch_assemble(int NB, int J, int max_det, int max_people, int min_joints, double max_cost, double seed_thr, const int* counts,
+                    const double* dets, const double* cost, const int* order, double* link, int* n_people, double* people, int* cand,
+                    void* stream) {
+  if (NB <= 0 || J <= 0) return 0;
+  if (max_det < 1 || max_det > kPeopleMaxDet || J > kPeopleMaxJoints || max_people < 1 || max_people > kPeopleMaxPeople)
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(assemble_kernel, dim3(NB), dim3(256), (size_t)max_people * J * sizeof(int), (hipStream_t)stream, J, max_det, max_people,
+                     min_joints, max_cost, seed_thr, counts, dets, cost, order, link, n_people, people, cand);
+  return (int)hipGetLastError();
+}
+
+}  // namespace dc

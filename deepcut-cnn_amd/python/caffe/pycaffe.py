@@ -35,6 +35,15 @@ def lib_path():
         "there is no Python/CPU fallback for the forward path." % [p for p in _LIB_CANDIDATES if p])
 
 
+class AssembleParams(C.Structure):
+    """dc_assemble_params (include/deepcut_hip.h)."""
+    _fields_ = [("scale", C.c_double), ("threshold", C.c_float), ("radius", C.c_int), ("max_det", C.c_int), ("max_cost", C.c_double),
+                ("seed_threshold", C.c_float), ("max_people", C.c_int), ("min_joints", C.c_int)]
+
+
+MAX_ASSEMBLE_DET, MAX_ASSEMBLE_PEOPLE = 64, 256  # dc_net_assemble_people's limits
+
+
 def _load():
     # PyTorch-ROCm wheels bundle their own HIP runtime under the same SONAME as /opt/rocm's.  Whichever is
     # loaded first serves the whole process; if ours comes first torch later reports "No HIP GPUs".  When
@@ -103,6 +112,8 @@ def _load():
         "dc_net_forward_boxes": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp]),
         "dc_net_detect_parts": (ci, [vp, C.c_double, C.c_float, ci, ci, vp, vp]),
         "dc_net_decode_pairwise": (ci, [vp, C.c_double, ci, vp, vp, vp, vp]),
+        "dc_pair_stats_read": (ci, [cp, ci, C.POINTER(ci), vp, vp, vp]),
+        "dc_net_assemble_people": (ci, [vp, C.POINTER(AssembleParams), ci, vp, vp, vp, vp, vp, vp, vp, vp]),
         "dc_net_flops": (ci, [vp, C.POINTER(C.c_double)]),
         "dc_net_num_launches": (ci, [vp]),
         "dc_net_plan_text": (cp, [vp]),
@@ -298,6 +309,79 @@ def check_boxes(image_shape, boxes, scales=1.0, canvas=None):
     if min(canvas) < 8 or canvas[0] % 8 or canvas[1] % 8:
         raise ValueError("canvas %dx%d is not a positive multiple of 8 on both sides" % canvas)
     return b, sc, canvas
+
+
+def pair_stats_read(path, max_edges=4096):
+    """dc_pair_stats_read: the `joint_pairs_stats` text file of a model -> (edges int32 [E, 2] of 0-based joints, mean float64 [E, 2],
+    std float64 [E, 2]).  Host only."""
+    n = C.c_int()
+    edges = np.zeros((max_edges, 2), np.int32)
+    mean, std = np.zeros((max_edges, 2), np.float64), np.zeros((max_edges, 2), np.float64)
+    _check(_lib.dc_pair_stats_read(os.fsencode(path), int(max_edges), C.byref(n), edges.ctypes.data_as(C.c_void_p),
+                                   mean.ctypes.data_as(C.c_void_p), std.ctypes.data_as(C.c_void_p)))
+    return edges[:n.value].copy(), mean[:n.value].copy(), std[:n.value].copy()
+
+
+def check_assembly(num_joints, n_edges_wanted, edges, mean=None, std=None, joint_order=None, scale=1.0, threshold=0.1, radius=1, max_det=16,
+                   max_cost=32.0, seed_threshold=0.5, max_people=32, min_joints=1):
+    """The arguments of Net.assemble_people, checked on the host before raw pointers cross the boundary (the library reads
+    2 * n_edges numbers through each of them).  n_edges_wanted: next_pred channels / 2, or None when unknown.
+    -> (AssembleParams, edges int32 [E, 2], mean or None, std or None, joint_order int32 [J] or None).  Raises ValueError naming the argument."""
+    j = int(num_joints)
+    e = np.asarray(edges)
+    if e.size == 0:
+        e = e.reshape(0, 2)
+    if e.ndim != 2 or e.shape[1] != 2:
+        raise ValueError("edges must be an E x 2 array of 0-based (joint, next joint), got shape %s" % (e.shape,))
+    if not np.issubdtype(e.dtype, np.integer):
+        if not (np.isfinite(e).all() and (e == np.round(e)).all()):
+            raise ValueError("edges must hold whole joint indices")
+    e = np.ascontiguousarray(e, dtype=np.int32)
+    for l in range(e.shape[0]):
+        a, b = int(e[l, 0]), int(e[l, 1])
+        if not (0 <= a < j and 0 <= b < j):
+            raise ValueError("edges: edge %d (%d, %d) names a joint outside [0, %d)" % (l, a, b, j))
+        if a == b:
+            raise ValueError("edges: edge %d joins joint %d to itself" % (l, a))
+    if n_edges_wanted is not None and e.shape[0] != int(n_edges_wanted):
+        raise ValueError("edges: %d edges for a next_pred of %d channels (2 per regression edge)" % (e.shape[0], 2 * int(n_edges_wanted)))
+
+    def stat(name, v, positive):
+        if v is None:
+            return None
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        if v.size != 2 * e.shape[0]:
+            raise ValueError("%s must be [E, 2] = [%d, 2], got shape %s" % (name, e.shape[0], v.shape))
+        if not np.isfinite(v).all() or (positive and not (v > 0).all()):
+            raise ValueError("%s must be finite%s" % (name, " and positive" if positive else ""))
+        return v.reshape(e.shape[0], 2)
+
+    m, s = stat("mean", mean, False), stat("std", std, True)
+    order = None
+    if joint_order is not None:
+        order = np.asarray(joint_order)
+        if order.ndim != 1 or order.shape[0] != j or sorted(int(v) for v in order) != list(range(j)) or not (order == np.round(order)).all():
+            raise ValueError("joint_order must be a permutation of 0..%d, got %r" % (j - 1, list(np.asarray(joint_order).tolist())))
+        order = np.ascontiguousarray(order, dtype=np.int32)
+    if not (np.isfinite(scale) and scale > 0):
+        raise ValueError("scale must be positive, got %r" % (scale,))
+    if not threshold >= 0:
+        raise ValueError("threshold must be >= 0, got %r" % (threshold,))
+    if not 0 <= int(radius) <= 64:
+        raise ValueError("radius must be in [0, 64], got %r" % (radius,))
+    if not 1 <= int(max_det) <= MAX_ASSEMBLE_DET:
+        raise ValueError("max_det must be in [1, %d], got %r" % (MAX_ASSEMBLE_DET, max_det))
+    if not (np.isfinite(max_cost) and max_cost >= 0):
+        raise ValueError("max_cost must be finite and >= 0, got %r" % (max_cost,))
+    if not np.isfinite(seed_threshold):
+        raise ValueError("seed_threshold must be finite, got %r" % (seed_threshold,))
+    if not 1 <= int(max_people) <= MAX_ASSEMBLE_PEOPLE:
+        raise ValueError("max_people must be in [1, %d], got %r" % (MAX_ASSEMBLE_PEOPLE, max_people))
+    if not 1 <= int(min_joints) <= j:
+        raise ValueError("min_joints must be in [1, %d], got %r" % (j, min_joints))
+    q = AssembleParams(float(scale), float(threshold), int(radius), int(max_det), float(max_cost), float(seed_threshold), int(max_people),
+                       int(min_joints))
+    return q, e, m, s, order
 
 
 def lpt_schedule(costs, nexec):
@@ -833,6 +917,38 @@ class Net(object):
         _check(_lib.dc_net_decode_pairwise(self._h, float(scale), det.shape[0], det.ctypes.data_as(C.c_void_p),
                                            None if m is None else m.ctypes.data_as(C.c_void_p),
                                            None if s is None else s.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def assemble_people(self, scale=1.0, threshold=0.1, radius=1, max_det=16, edges=None, mean=None, std=None, max_cost=32.0,
+                        seed_threshold=0.5, max_people=32, min_joints=1, joint_order=None, return_cost=False):
+        """The people of every image of the last forward (dc_net_assemble_people): part candidates, pair costs from `next_pred` and a
+        greedy assembly, all on the device; only the results come back.  edges: [E, 2] 0-based (joint, next joint) of the regression
+        edges (E = next_pred channels / 2), mean / std: their [E, 2] de-normalisation (deepcut_tools.read_pair_stats), None = 0 / 1.
+        A link is allowed when its cost (network pixels) is <= max_cost; a candidate that joins nobody starts a person when its score
+        is >= seed_threshold.  The defaults of max_cost and seed_threshold are PLACEHOLDERS, not tuned on real images: override them.
+        The grouping rule (include/deepcut_hip.h) is this project's own; the reference stops at the maps.
+        -> one dict per image: {"people": float64 [m, J, 3] = x, y, score ((0, 0, 0) for a missing joint), "cand": int32 [m, J] =
+        index in the joint's candidate list or -1}, plus "cost": float64 [J, J, max_det, max_det] with return_cost."""
+        if edges is None:
+            raise ValueError("assemble_people needs the regression edges (deepcut_tools.read_pair_stats)")
+        n, j = self.blobs["prob"].shape[:2]
+        want_e = self.blobs["next_pred"].shape[1] // 2 if "next_pred" in self.blobs else None
+        q, e, m, s, order = check_assembly(j, want_e, edges, mean, std, joint_order, scale, threshold, radius, max_det, max_cost, seed_threshold,
+                                           max_people, min_joints)
+        p, md = q.max_people, q.max_det
+        count = np.zeros(n, np.int32)
+        people = np.zeros((n, p, j, 3), np.float64)
+        cand = np.zeros((n, p, j), np.int32)
+        cost = np.zeros((n, j, j, md, md), np.float64) if return_cost else None
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        _check(_lib.dc_net_assemble_people(self._h, C.byref(q), e.shape[0], ptr(e), ptr(m), ptr(s), ptr(order), ptr(count), ptr(people),
+                                           ptr(cand), ptr(cost)))
+        out = []
+        for b in range(n):
+            d = {"people": people[b, :count[b]].copy(), "cand": cand[b, :count[b]].copy()}
+            if return_cost:
+                d["cost"] = cost[b]
+            out.append(d)
         return out
 
     def clone(self):

@@ -8,3 +8,4 @@ from .shard import lpt_shards, gather_maps, gather_maps_known  # noqa: F401
 from .pipeline import Pipeline  # noqa: F401
 from .runner import ShardedPoseRunner, plan_work, net_input_shape, rank_batches, group_units  # noqa: F401
 from .tuning import tune_in_flight  # noqa: F401
+from .pair_stats import read_pair_stats, write_pair_stats  # noqa: F401

@@ -1,0 +1,1 @@
+from .people import estimate_people, people_boxes  # noqa: F401

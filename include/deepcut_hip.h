@@ -288,6 +288,55 @@ int dc_net_detect_parts(dc_net* net, double scale, float threshold, int radius, 
 int dc_net_decode_pairwise(dc_net* net, double scale, int ndet, const int* detections, const double* mean,
                            const double* stdev, double* out);
 
+/* ---- people: bottom-up assembly from the part candidates and the pairwise maps, on the device ------------------------
+ * NO REFERENCE COUNTERPART: the reference repository stops at the maps and has no consumer of `next_pred`.  Only the label encoding of
+ * its training layer (src/caffe/layers/pose_data_layer.cpp:686-802) is restated, as above; the grouping rule below is this project's
+ * own and its parity is unpinned by the reference.
+ *
+ * dc_pair_stats_read: the `joint_pairs_stats` file of a model (caffe.proto:1184; the reference reads it with readMatricesFromFile,
+ * src/caffe/util/SimpleMatrix.cpp:9-37).  Text, everything whitespace-separated: repeated blocks of `# <name>`, `<rows> <cols>`, rows x
+ * cols numbers.  The first three matrices are used (pose_data_layer.cpp:453-455): edges [E][2] of 1-based class ids (cls, next_cls),
+ * returned as 0-based joints = class - 1 (:85-88), means [E][2], standard deviations [E][2].  Host only, no GPU.  *n_edges = E.
+ * Errors: DC_EIO for an unreadable file; DC_EINVAL naming what is wrong for fewer than three matrices, a matrix that is not E x 2,
+ *         differing row counts, a truncated block, a class id < 1, a non-positive or non-finite standard deviation, E > max_edges
+ *         (*n_edges then says how many the file holds).
+ *
+ * dc_net_assemble_people: the people of every image of the last forward, in three stages on the device with no host round trip
+ * in between; host output buffers, synchronous on the net's stream like dc_net_detect_parts; float32, float16 and bfloat16 nets alike.
+ *  A. candidates: dc_net_detect_parts(scale, threshold, radius, max_det); candidate (j, i) is entry i of joint j's list.
+ *  B. pair costs: for joints a != c, candidate i of a and k of c, with F = the lowest-index edge l with edges[l] == (a, c) and R = the
+ *     lowest-index edge with edges[l] == (c, a) (edges: n_edges x 2 0-based joints; n_edges = next_pred channels / 2, else DC_ESHAPE):
+ *       pred(cell, l) = pt(cell) + (next_pred[2l..2l+1] at cell * std[l] + mean[l]) / scale        (as dc_net_decode_pairwise)
+ *       d_f = |pred(cell of (a,i), F) - position of (c,k)|,  d_r = |pred(cell of (c,k), R) - position of (a,i)|   (image pixels)
+ *       cost[b][a][c][i][k] = scale * mean of those of d_f, d_r whose edge exists (network pixels); +infinity when neither exists, for
+ *       a == c and for slots beyond a list's count.  cost[b][c][a][k][i] is the same number.  All arithmetic in double.
+ *  C. greedy assembly, deterministic (same inputs, same people): the joints are processed in joint_order ([J], a permutation; NULL =
+ *     0..J-1).  For joint j: (1) for every person p (creation order) and free candidate i of j, the link cost L(p, i) = the arithmetic
+ *     mean of cost[b][a][j][candidate p holds of a][i] over the joints a (ascending) that p holds and whose cost is finite; infinite if
+ *     there is none.  (2) Until no link with L <= max_cost remains: among the links of people without joint j and free candidates
+ *     take the smallest L (ties: the lower p, then the lower i), assign it.  (3) Every candidate of j still free, in list order, with
+ *     score >= seed_threshold starts a new person holding only this joint, until max_people exist.  After the last joint people
+ *     with fewer than min_joints joints are dropped, the others keep their order.
+ * Outputs: n_people[b]; people[((b*P + q)*J + j)*3 + {0,1,2}] = x, y, score of person q's candidate of joint j, (0, 0, 0) where it has
+ *          none and for q >= n_people[b]; cand[(b*P + q)*J + j] = that candidate's index in joint j's list or -1 (may be NULL); cost (may
+ *          be NULL: diagnostics and tests) = the whole tensor [n][J][J][max_det][max_det].  P = max_people.
+ * Errors : DC_EINVAL naming the parameter for scale <= 0, threshold < 0, radius outside [0, 64], max_det outside [1, 64], max_cost
+ *          negative or not finite, max_people outside [1, 256], min_joints outside [1, J]; DC_EINVAL before any device work for a joint
+ *          index outside [0, J), an edge with a == b, a joint_order that is not a permutation; DC_EUNSUP when `next_pred` is left out by
+ *          DC_OPT_OUTPUTS; DC_ESHAPE for a wrong n_edges or more than 32 joints.                                                      */
+typedef struct dc_assemble_params {
+  double scale;          /* as dc_net_detect_parts */
+  float  threshold;      /* candidate score threshold */
+  int    radius, max_det;/* NMS window, candidates kept per joint: 1 <= max_det <= 64 here */
+  double max_cost;       /* a link is allowed when its cost (network pixels) <= max_cost */
+  float  seed_threshold; /* a candidate that joins nobody starts a person when its score >= this */
+  int    max_people;     /* P, 1..256 */
+  int    min_joints;     /* people with fewer assigned joints are dropped from the result */
+} dc_assemble_params;
+int dc_pair_stats_read(const char* path, int max_edges, int* n_edges, int* edges, double* mean, double* stdev);
+int dc_net_assemble_people(dc_net* net, const dc_assemble_params* p, int n_edges, const int* edges, const double* mean, const double* stdev,
+                           const int* joint_order, int* n_people, double* people, int* cand, double* cost);
+
 
 /* ---- introspection used by bench.py / DESIGN.md ----------------------------------------- */
 /* algorithmic FLOPs (2*MAC of conv+deconv) of the current shape               */
