@@ -230,6 +230,15 @@ int launch_stem7x7(const ConvGemmParams& p, void* stream);
 // multi-problem (NetGroup): prepare_conv_multi / launch_conv_multi end here for the ws1x1 form; p.w must be the packed image
 long stream1x1_prepare_multi(const ConvGemmParams& p, const ConvMultiTable& tb, int nprob);  // the grid, or -1
 int launch_stream1x1_multi(const ConvMultiArgs& a, void* stream);                              // a.p.nprob, a.t as filled by the caller
+// ---- the same two kernels for a bfloat16 net ("bs1x1", "bs7x7"): v_mfma_f32_32x32x16_bf16 on the same register images, the epilogue of the
+// bfloat16 gather-GEMM (shortcut widened by a shift / a mask, added and ReLU'd in fp32, one rounding by v_cvt_pk_bf16_f32: bit-identical to a
+// bf16 tile without split-K).  `w` is the image of stream1x1_pack_filters() / stem7x7_pack_filters() uploaded as __bf16 (no row scale)
+bool stream1x1_bf16_eligible(const ConvGemmParams& p);
+int launch_stream1x1_bf16(const ConvGemmParams& p, void* stream);
+long stream1x1_bf16_prepare_multi(const ConvGemmParams& p, const ConvMultiTable& tb, int nprob);
+int launch_stream1x1_bf16_multi(const ConvMultiArgs& a, void* stream);
+bool stem7x7_bf16_eligible(const ConvGemmParams& p);
+int launch_stem7x7_bf16(const ConvGemmParams& p, void* stream);
 
 // ---- FORMS: the convolution kernels outside the tile tables.  A form has a filter image of its own (Launch::form_w) and is timed against
 // the tiles per shape.  Its variant number travels in Launch::variant and tune caches like a tile's, and DC_CONV_VARIANT takes it.
@@ -242,7 +251,9 @@ constexpr int kStreamFloat = 1005;    // "ws1x1f": the float32 streaming 1x1 for
 constexpr int kStemFloat = 1006;      // "ws7x7f": the float32 stem on that kernel's skeleton (stream1x1_f32.hip)
 constexpr int kWinoVariant56 = 1007;     // "wino_f23_5x6": wino_f23 on 5 x 6-tile blocks (two 5 x 3-tile fragments side by side) instead of 4 x 8
 constexpr int kWinoVariant56x16 = 1008;  // "wino_f23_5x6_w16": its 16-wave form
-constexpr int kFormVariant0 = kWinoVariant, kNumForms = 9;
+constexpr int kStreamBf16 = 1009;        // "bs1x1": the streaming form of the dense 1x1 layers of a bfloat16 net (stream1x1.hip, v_mfma_f32_32x32x16_bf16)
+constexpr int kStemBf16 = 1010;          // "bs7x7": the 7x7 / stride-2 stem of a bfloat16 net (stem_f16.hip)
+constexpr int kFormVariant0 = kWinoVariant, kNumForms = 11;
 enum FormGeometry { kForm3x3, kForm1x1, kFormStem };  // the layers a form takes: 3x3, dense 1x1, the 7-row-tap stem
 struct ConvForm {
   int variant;
@@ -258,9 +269,10 @@ struct ConvForm {
   long (*prepare_multi)(const ConvGemmParams& p, const ConvMultiTable& tb, int nprob);
   int (*launch_multi)(const ConvMultiArgs& a, void* stream);
   int sibling;         // the form on the same image that autotuning compares it with in whole passes, else -1
-  const char* env;     // its switch: unset or -1 where measured faster, 0 never, >= 1 wherever eligible
+  const char* env;     // its switch: -1 where measured faster, 0 never, >= 1 wherever eligible; unset = env_default
   // null: a candidate of the per-shape timing wherever eligible; else only where this says so (set_tile and tune caches take it wherever eligible)
   bool (*offered)(const ConvGemmParams& p) = nullptr;
+  int env_default = -1;  // what the switch means while unset (0: the form is opt-in)
 };
 const ConvForm* conv_form(int variant);  // null: not a form (a tile)
 

@@ -1903,7 +1903,7 @@ static const char* const kWinoSlots[7] = {"index setup", "first loads issued", "
 static const char* const kStreamSlots[7] = {"prologue requests issued", "first stage + filters landed", "the first D steps", "the other steps",
                                             "drain", "-", "exit"};
 static constexpr ConvForm kForms[kNumForms] = {
-    // variant, name, label, ekind, geometry, waves, slots, eligible, grid, launch, own_scale, merges, prepare_multi, launch_multi, sibling, env, offered
+    // variant, name, label, ekind, geometry, waves, slots, eligible, grid, launch, own_scale, merges, prepare_multi, launch_multi, sibling, env, offered, env_default
     {kWinoVariant, "wino_f23", "wino_f23<4x8x16>", kElemF32, kForm3x3, 8, kWinoSlots, wino_eligible, wino_grid, launch_wino_f23<1, WinoG48>,
      false, false, nullptr, nullptr, kWinoVariant16, "DC_WINOGRAD"},
     {kWinoVariant16, "wino_f23_w16", "wino_f23<4x8x16_w16>", kElemF32, kForm3x3, 16, kWinoSlots, wino_eligible, wino_grid, launch_wino_f23<2, WinoG48>,
@@ -1922,6 +1922,11 @@ static constexpr ConvForm kForms[kNumForms] = {
      false, false, nullptr, nullptr, kWinoVariant56x16, "DC_WINOGRAD", wino_fewer_blocks},
     {kWinoVariant56x16, "wino_f23_5x6_w16", "wino_f23<5x6x16_w16>", kElemF32, kForm3x3, 16, kWinoSlots, wino_eligible, wino_grid_of<WinoG56>, launch_wino_f23<2, WinoG56>,
      false, false, nullptr, nullptr, kWinoVariant56, "DC_WINOGRAD", wino_fewer_blocks},
+    // the bfloat16 forms are opt-in: switches of their own, 0 while unset
+    {kStreamBf16, "bs1x1", "bs1x1<32xN>", kElemBF16, kForm1x1, 4, kStreamSlots, stream1x1_bf16_eligible, stream1x1_grid, launch_stream1x1_bf16,
+     false, true, stream1x1_bf16_prepare_multi, launch_stream1x1_bf16_multi, -1, "DC_STREAM1X1_BF16", nullptr, 0},
+    {kStemBf16, "bs7x7", "bs7x7<8x64>", kElemBF16, kFormStem, 4, kWinoSlots, stem7x7_bf16_eligible, stem7x7_grid, launch_stem7x7_bf16,
+     false, false, nullptr, nullptr, -1, "DC_STEM_BF16", nullptr, 0},
 };
 
 static constexpr bool forms_in_variant_order() {

@@ -164,7 +164,7 @@ static std::vector<int> group_candidates(const GroupLaunch& gl) {
   const int* cand = conv_variants_of(gl.p.ekind, &n);
   for (int i = 0; i < n; ++i)
     if (conv_variant_multiproblem(cand[i]) && tile_takes_k(cand[i], gl.p.klen, gl.row_tap)) c.push_back(cand[i]);
-  if (gl.form >= 0 && env_int(conv_form(gl.form)->env, -1) != 0) c.push_back(gl.form);
+  if (gl.form >= 0 && form_mode(*conv_form(gl.form)) != 0) c.push_back(gl.form);
   return c;
 }
 
@@ -224,8 +224,8 @@ void NetGroup::merge(GroupPlan& gp) {
       const size_t c = (size_t)mem[cc];
       const Launch& l = nets[c]->plan[i];
       const ConvGemmParams &g = l.cg, &g0 = l0.cg;
-      // (a member on a form merges as the direct layer it also is where ConvForm::merges says so — wino_h23, ws1x1, ws1x1f, ws7x7f —, and
-      //  keeps the launch apart on wino_f23, wino_f23_w16 and stem7x7.  wino_h23 is a one-round kernel that wins alone on a 240-workgroup
+      // (a member on a form merges as the direct layer it also is where ConvForm::merges says so — wino_h23, ws1x1, bs1x1, ws1x1f, ws7x7f —, and
+      //  keeps the launch apart on wino_f23, wino_f23_w16, stem7x7 and bs7x7.  wino_h23 is a one-round kernel that wins alone on a 240-workgroup
       //  grid — round 6: with the 544x736 member's conv4_x 3x3 launches kept out of the merge, the four scales of that layer ran as 17.8 +
       //  31.2 + 17.0 + 14.3 us where the merged direct launch takes 60.5 —; the float32 streaming forms win by a few per cent on a
       //  member's own grid only.)
@@ -325,7 +325,7 @@ void NetGroup::merge(GroupPlan& gp) {
       gl.p.dbg = nullptr;
       gl.p.x = nullptr, gl.p.y = nullptr, gl.p.resid = nullptr;
       gl.p.w = l0.w->dev;
-      // a multi-problem form (ws1x1) is a candidate if every member carries its (shared) image
+      // a multi-problem form (ws1x1, bs1x1) is a candidate if every member carries its (shared) image
       for (int v = kFormVariant0; v < kFormVariant0 + kNumForms; ++v) {
         bool all = conv_form(v)->launch_multi && l0.takes_form(v) && l0.form_w->dev;
         for (int c : mem) all = all && nets[c]->plan[i].form_w == l0.form_w && nets[c]->plan[i].takes_form(v);
@@ -360,7 +360,7 @@ void NetGroup::merge(GroupPlan& gp) {
       if (forced >= 0 && conv_variant_exists(forced) && conv_variant_multiproblem(forced) && tile_takes_k(forced, gl.p.klen, gl.row_tap) &&
           conv_variant_ekind(forced) == gl.p.ekind)
         v = forced;
-      if (forced < 0 && gl.form >= 0 && env_int(conv_form(gl.form)->env, -1) >= 1) v = gl.form;  // (forced on: wherever eligible, as in Net's lowering)
+      if (forced < 0 && gl.form >= 0 && form_mode(*conv_form(gl.form)) >= 1) v = gl.form;  // (forced on: wherever eligible, as in Net's lowering)
       gl.variant = v;
     }
   }
@@ -522,7 +522,9 @@ void NetGroup::autotune(GroupPlan& gp) {
   for (auto& gl : gp.launches) {
     if (!gl.multi) continue;
     auto it = cache.find(gl.key);
-    if (it != cache.end() && it->second != gl.variant) apply_variant(gp, gl, it->second);
+    // (a choice the launch cannot take — a form named by a cache file while its switch is off —: the launch keeps merge()'s fallback)
+    ConvMultiArgs a;
+    if (it != cache.end() && it->second != gl.variant && group_args(gl, it->second, a) > 0) apply_variant(gp, gl, it->second);
   }
   if (timed_any) {
     ++stats.autotune_runs;
@@ -534,7 +536,8 @@ void NetGroup::autotune(GroupPlan& gp) {
       for (auto& gl : other->launches) {
         if (!gl.multi) continue;
         auto it = cache.find(gl.key);
-        if (it != cache.end() && it->second != gl.variant) {
+        ConvMultiArgs a;
+        if (it != cache.end() && it->second != gl.variant && group_args(gl, it->second, a) > 0) {
           apply_variant(*other, gl, it->second);
           touched = true;
         }

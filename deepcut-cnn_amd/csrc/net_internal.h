@@ -84,6 +84,7 @@ inline int env_int(const char* k, int def) {
   const char* v = std::getenv(k);
   return v ? std::atoi(v) : def;
 }
+inline int form_mode(const ConvForm& f) { return env_int(f.env, f.env_default); }  // a form's switch: -1 / 0 / >= 1 (kernels.h ConvForm::env)
 uint64_t content_hash(const float* p, size_t n);               // net_lower.cpp
 void load_tune_cache_locked(ModelShared& shared);        // net_tune.cpp: DC_TUNE_CACHE file -> table (once per model)
 void write_tune_cache_locked(ModelShared& shared);       // net_tune.cpp: table (united with the file) -> file, atomically

@@ -501,6 +501,8 @@ void Net::build_plan() {
   const int wino_mode = env_int("DC_WINOGRAD", -1);
   const int stem_mode = env_int("DC_STEM", -1);          // the stem forms: -1 where measured faster, 0 never, 1 forced
   const int stream_mode = env_int("DC_STREAM1X1", -1);  // the streaming forms of the dense 1x1 layers: -1 where measured faster, 0 never, 1 wherever eligible
+  // the bfloat16 forms have switches of their own, off while unset: the three above do nothing for a bfloat16 net
+  const int stem_bf16_mode = form_mode(*conv_form(kStemBf16)), stream_bf16_mode = form_mode(*conv_form(kStreamBf16));
   auto choose_variant = [&](Launch& l, int kgcd) {
     int best = -1;
     double bc = 0;
@@ -525,7 +527,7 @@ void Net::build_plan() {
   // a form whose image the launch now carries: forced on by its switch (ConvForm::env >= 1), it replaces the tile unless DC_CONV_VARIANT
   // forces a tile; else the per-shape timing decides
   auto offer_form = [&](Launch& l, int v) {
-    if (env_int(conv_form(v)->env, -1) >= 1 && (force_variant < 0 || conv_form(force_variant))) l.set_variant(v);
+    if (form_mode(*conv_form(v)) >= 1 && (force_variant < 0 || conv_form(force_variant))) l.set_variant(v);
   };
 
   // Channel split of a wide-but-ragged GEMM (the merged heads: N = 406 = 3 x 128 + 22).  On 128-wide tiles a quarter of the
@@ -727,6 +729,16 @@ void Net::build_plan() {
         l.form_w->as_half = true;
         offer_form(l, kStreamHalf);
       }
+      if (!rowtap && !l.form_w && stream_bf16_mode != 0 && op.wls.empty() && dtype == kElemBF16 && g.klen == C && g.Ktot == C && stream1x1_bf16_eligible(g)) {
+        // bfloat16 dense 1x1 layers ("bs1x1", stream1x1.hip): the plain filters (bfloat16 has no row scale) in the same fragment order,
+        // rounded to nearest even at the upload like the direct image.  Opt-in (DC_STREAM1X1_BF16: unset = 0)
+        l.form_w = get_vec(dkey + "bs:" + std::to_string(op.wl), [&](std::vector<float>& h) {
+          h.assign(stream1x1_packed_elems(OC, C), 0.f);
+          stream1x1_pack_filters(L.params[0]->st->host_ptr(), OC, C, h.data());
+        });
+        l.form_w->as_bf16 = true;
+        offer_form(l, kStreamBf16);
+      }
       if (!rowtap && !l.form_w && stream_mode != 0 && op.wls.empty() && dtype == kElemF32 && g.klen == C && g.Ktot == C && stream1x1f_eligible(g)) {
         // float32 dense 1x1 layers with 64 / 128 / 256 / 512 input channels (stream1x1_f32.hip): the filters in the order of its 16x16x4 matrix steps
         l.form_w = get_vec(dkey + "wsf:" + std::to_string(op.wl), [&](std::vector<float>& h) {
@@ -751,6 +763,15 @@ void Net::build_plan() {
         });
         l.form_w->as_half = true;
         offer_form(l, kStemHalf);
+      }
+      if (rowtap && stem_bf16_mode != 0 && op.wls.empty() && dtype == kElemBF16 && C <= 4 && stem7x7_bf16_eligible(g)) {
+        // bfloat16 stem ("bs7x7", stem_f16.hip): the plain filters in the float16 stem's operand order.  Opt-in (DC_STEM_BF16: unset = 0)
+        l.form_w = get_vec(dkey + "bstem:" + std::to_string(op.wl), [&](std::vector<float>& h) {
+          h.assign(stem7x7_packed_elems(), 0.f);
+          stem7x7_pack_filters(L.params[0]->st->host_ptr(), C, h.data());
+        });
+        l.form_w->as_bf16 = true;
+        offer_form(l, kStemBf16);
       }
       if (rowtap && stem_mode != 0 && op.wls.empty() && dtype == kElemF32 && C <= 4 && stem_ws_eligible(g)) {
         // float32 stem on the streaming skeleton (stream1x1_f32.hip, "ws7x7f"): the row-tap image's 224 columns + 32 of zeros in the order of

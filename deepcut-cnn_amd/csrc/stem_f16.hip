@@ -12,6 +12,9 @@
 // per 32 x 64 outputs: 35.0 us at batch 8, 9.7 at batch 1 (16.7) — profiles/r06_stem_probe.txt.  The
 // epilogue is the one of stream1x1.hip (affine in fp32, ReLU, 16-byte vectors by v_permlane32_swap, transposed in a wave-private LDS tile
 // to whole 128-byte pixel rows).
+//
+// The same kernel serves a bfloat16 net ("bs7x7", T = __bf16): v_mfma_f32_32x32x16_bf16 on the same register images, ReLU on the floats and
+// one rounding by v_cvt_pk_bf16_f32, as in stream1x1.hip; the band, the filters and the stores move the same bytes.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -45,12 +48,13 @@ struct StemArgs {
   unsigned div_tx[2], div_txy[2];
 };
 
-template <bool RELU>
+template <typename T, bool RELU>
 __global__ __launch_bounds__(256, 2) void stem7x7_kernel(const StemArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[BANDB + 4 * SOBUF + 2 * 64 * 4];
   float* scl = reinterpret_cast<float*>(smem + BANDB + 4 * SOBUF);
   float* shl = scl + 64;
   const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  constexpr bool BF = std::is_same_v<T, __bf16>;
   const int p32 = lane & 31, h = lane >> 5;
   // tile: image n, conv rows [r0, r0 + TRH), conv columns [c0, c0 + TCW)
   const int bx = blockIdx.x;
@@ -125,7 +129,10 @@ __global__ __launch_bounds__(256, 2) void stem7x7_kernel(const StemArgs a) {
       for (int s = 0; s < 2; ++s)
 #pragma unroll
         for (int f = 0; f < 2; ++f)
-          acc[f] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wreg[f][ky][s]), __builtin_bit_cast(f16x8, xf[ky * 2 + s]), acc[f], 0, 0, 0);
+          if constexpr (BF)
+            acc[f] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wreg[f][ky][s]), __builtin_bit_cast(bf16x8, xf[ky * 2 + s]), acc[f], 0, 0, 0);
+          else
+            acc[f] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wreg[f][ky][s]), __builtin_bit_cast(f16x8, xf[ky * 2 + s]), acc[f], 0, 0, 0);
     // epilogue (stream1x1.hip): register r of fragment f is channel f 32 + 8 (r >> 2) + 4 h + (r & 3) of pixel p32
 #pragma unroll
     for (int f = 0; f < 2; ++f)
@@ -144,11 +151,17 @@ __global__ __launch_bounds__(256, 2) void stem7x7_kernel(const StemArgs a) {
         u32x4 o;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          const float x0 = i < 2 ? lo[2 * i] : hi[2 * i - 4], x1 = i < 2 ? lo[2 * i + 1] : hi[2 * i - 3];
-          const f32x2 xp = {x0, x1};
-          f16x2 hp = __builtin_convertvector(xp, f16x2);
-          if (RELU) hp = __builtin_elementwise_max(hp, zero2);
-          o[i] = __builtin_bit_cast(unsigned, hp);
+          float x0 = i < 2 ? lo[2 * i] : hi[2 * i - 4], x1 = i < 2 ? lo[2 * i + 1] : hi[2 * i - 3];
+          if constexpr (BF) {
+            if (RELU) x0 = fmaxf(x0, 0.f), x1 = fmaxf(x1, 0.f);
+            const f32x2 xp = {x0, x1};
+            o[i] = __builtin_bit_cast(unsigned, __builtin_convertvector(xp, bf16x2));
+          } else {
+            const f32x2 xp = {x0, x1};
+            f16x2 hp = __builtin_convertvector(xp, f16x2);
+            if (RELU) hp = __builtin_elementwise_max(hp, zero2);
+            o[i] = __builtin_bit_cast(unsigned, hp);
+          }
         }
         *reinterpret_cast<u32x4*>(obp + p32 * 128 + (((f * 4 + j * 2 + h) ^ oswz) * 16)) = o;
       }
@@ -163,12 +176,11 @@ __global__ __launch_bounds__(256, 2) void stem7x7_kernel(const StemArgs a) {
     }
   }
 }
-}  // namespace
 
 // the launch the lowering makes of the stem: 7 row-taps of one 64-element K segment over an image of CP = 4 or 8 channels per pixel
-// (at most 4 of them real: the caller's business), stride 2, pad 3
-bool stem7x7_eligible(const ConvGemmParams& p) {
-  if (p.esize != 2 || p.ekind == kElemBF16 || p.ncls > 1 || p.nprob > 0 || p.sigmoid_ch != 0 || p.resid) return false;
+// (at most 4 of them real: the caller's business), stride 2, pad 3; ekind: kElemF16 (any 2-byte kind that is not bfloat16) or kElemBF16
+bool stem_eligible(const ConvGemmParams& p, int ekind) {
+  if (p.esize != 2 || (p.ekind == kElemBF16) != (ekind == kElemBF16) || p.ncls > 1 || p.nprob > 0 || p.sigmoid_ch != 0 || p.resid) return false;
   const int CP = p.sx / 2;
   if ((CP != 4 && CP != 8) || p.sx != 2 * CP || p.x0 != -3 * CP) return false;
   if (p.nty != 7 || p.ntx != 1 || p.klen != 64 || p.Ktot != 7 * 64 || p.dy0 != -3 || p.ddy != 1 || p.sy != 2) return false;
@@ -179,6 +191,10 @@ bool stem7x7_eligible(const ConvGemmParams& p) {
   if ((long)p.x_rows * p.x_row_stride * 2 >= 0x7fffffffL || (long)p.OH * p.y_row_stride * 2 >= 0x7fffffffL) return false;  // 32-bit offsets inside an image
   return true;
 }
+}  // namespace
+
+bool stem7x7_eligible(const ConvGemmParams& p) { return stem_eligible(p, kElemF16); }
+bool stem7x7_bf16_eligible(const ConvGemmParams& p) { return stem_eligible(p, kElemBF16); }
 
 long stem7x7_grid(const ConvGemmParams& p) { return (long)p.NB * ((p.OH + TRH - 1) / TRH) * ((p.OW + TCW - 1) / TCW); }
 
@@ -197,8 +213,9 @@ void stem7x7_pack_filters(const float* g, int C, float* out) {
         }
 }
 
-int launch_stem7x7(const ConvGemmParams& p, void* stream) {
-  if (!stem7x7_eligible(p) || ((uintptr_t)p.x & 7) || ((uintptr_t)p.y & 15) || ((uintptr_t)p.w & 15)) return (int)hipErrorInvalidValue;
+namespace {
+int stem_launch(const ConvGemmParams& p, int ekind, void* stream) {
+  if (!stem_eligible(p, ekind) || ((uintptr_t)p.x & 7) || ((uintptr_t)p.y & 15) || ((uintptr_t)p.w & 15)) return (int)hipErrorInvalidValue;
   const long grid = stem7x7_grid(p);
   if (grid <= 0) return 0;
   if (grid > 0x7fffffffL) return (int)hipErrorInvalidValue;
@@ -212,9 +229,14 @@ int launch_stem7x7(const ConvGemmParams& p, void* stream) {
   a.tiles_x = (p.OW + TCW - 1) / TCW, a.tiles_y = (p.OH + TRH - 1) / TRH;
   dc_magic((unsigned)a.tiles_x, a.div_tx);
   dc_magic((unsigned)(a.tiles_x * a.tiles_y), a.div_txy);
-  if (p.relu) hipLaunchKernelGGL(stem7x7_kernel<true>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(stem7x7_kernel<false>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
+  void (*const k)(const StemArgs) = ekind == kElemBF16 ? (p.relu ? stem7x7_kernel<__bf16, true> : stem7x7_kernel<__bf16, false>)
+                                                       : (p.relu ? stem7x7_kernel<_Float16, true> : stem7x7_kernel<_Float16, false>);
+  hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
   return (int)hipGetLastError();
 }
+}  // namespace
+
+int launch_stem7x7(const ConvGemmParams& p, void* stream) { return stem_launch(p, kElemF16, stream); }
+int launch_stem7x7_bf16(const ConvGemmParams& p, void* stream) { return stem_launch(p, kElemBF16, stream); }
 
 }  // namespace dc

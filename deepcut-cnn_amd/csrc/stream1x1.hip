@@ -1,4 +1,5 @@
-// stream1x1.hip — the float16 1x1 / stride-1 layers whose time is memory traffic, not arithmetic, as a STREAM ("ws1x1": weight-stationary).
+// stream1x1.hip — the float16 1x1 / stride-1 layers whose time is memory traffic, not arithmetic, as a STREAM ("ws1x1": weight-stationary),
+// and the same kernel for a bfloat16 net ("bs1x1": the element type T of the template; what differs is at the end of this comment).
 //
 // Which layers: the 1x1 expansions that close a bottleneck block with the shortcut add + ReLU (resNx_branch2c, ResNet-152.prototxt: 64 -> 256,
 // 128 -> 512, 256 -> 1024, 512 -> 2048 channels) and the stride-1 projections (res2a_branch1).  At batch 8 (BASELINE configs[2]) a res4 one
@@ -23,6 +24,11 @@
 //  * blocks of the same pixel range (the tn channel slices) are neighbours on one XCD (blockIdx % 8), so the pixels cross the fabric once;
 //  * the two halves of the workgroup take the step in opposite order (waves w and w + NW/2 share a SIMD).
 // A multi-problem launch (NetGroup: the scales of an image pyramid) is the same walk over the steps of several tensors in turn.
+//
+// T = __bf16 ("bs1x1") moves the same bytes through the same ring with the same request counts; three spots differ: the matrix instruction
+// (v_mfma_f32_32x32x16_bf16, same fragment layout), the shortcut add (the pair widened by a shift / a mask, added in fp32: no v_fma_mix for
+// bfloat16) and the pack (ReLU on the two floats, one rounding by v_cvt_pk_bf16_f32) — the bfloat16 gather-GEMM's epilogue on the same
+// operands in the same K order, so bit-identical to a bf16 tile without split-K.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -46,7 +52,7 @@ struct WsProblem {
   int step0;  // first step of this tensor in the launch-wide numbering
 };
 struct WsArgs {
-  const void* w;  // ws_pack_filters image, _Float16
+  const void* w;  // ws_pack_filters image, _Float16 or __bf16
   const float* scale;
   const float* shift;
   int Cout, relu, tn, J, S, nprob;
@@ -61,9 +67,10 @@ struct WsArgs {
 // instructions per wave and step with two waves per SIMD), so everything that is not a matrix, LDS or memory instruction was taken out of
 // it: no branch except the loop's own (RELU / MULTI are template parameters, the first D-1 steps with their own vmcnt counts are peeled),
 // addresses are a per-lane constant + a scalar per step, masked by one compare (no 64-bit multiply-add, no exec juggling).
-template <int KC, int FN, int NW, int D, bool RES, bool RELU, bool MULTI>
+template <typename T, int KC, int FN, int NW, int D, bool RES, bool RELU, bool MULTI>
 __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void ws1x1_kernel(const WsArgs a) {
   const long long t_entry = (long long)__builtin_amdgcn_s_memrealtime();
+  constexpr bool BF = std::is_same_v<T, __bf16>;
   constexpr int NT = NW * 64;
   constexpr int RB = KC * 32;       // bytes of a pixel's K halves = one row of a stage
   constexpr int STG = 32 * RB;      // a stage: 32 pixels
@@ -272,7 +279,10 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void ws1x1_kernel(const W
       if (kk + PD - 1 < KC) xf[(kk + PD - 1) % PD] = *reinterpret_cast<const u32x4*>(st + (frag0 ^ (unsigned)((kk + PD - 1) * 32)));
 #pragma unroll
       for (int f = 0; f < FN; ++f)
-        acc[f] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wreg[f][kk]), __builtin_bit_cast(f16x8, xf[kk % PD]), acc[f], 0, 0, 0);
+        if constexpr (BF)
+          acc[f] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wreg[f][kk]), __builtin_bit_cast(bf16x8, xf[kk % PD]), acc[f], 0, 0, 0);
+        else
+          acc[f] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, wreg[f][kk]), __builtin_bit_cast(f16x8, xf[kk % PD]), acc[f], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -320,14 +330,24 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void ws1x1_kernel(const W
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           float x0 = i < 2 ? lo[2 * i] : hi[2 * i - 4], x1 = i < 2 ? lo[2 * i + 1] : hi[2 * i - 3];
-          if (RES) {
-            x0 = dc_add_half_lo(rv[i], x0);
-            x1 = dc_add_half_hi(rv[i], x1);
+          if constexpr (BF) {  // (the bfloat16 gather-GEMM's epilogue, kernels.hip: same operations, same order)
+            if (RES) {
+              x0 += __builtin_bit_cast(float, rv[i] << 16);
+              x1 += __builtin_bit_cast(float, rv[i] & 0xffff0000u);
+            }
+            if (RELU) x0 = fmaxf(x0, 0.f), x1 = fmaxf(x1, 0.f);
+            const f32x2 xp = {x0, x1};
+            o[i] = __builtin_bit_cast(unsigned, __builtin_convertvector(xp, bf16x2));
+          } else {
+            if (RES) {
+              x0 = dc_add_half_lo(rv[i], x0);
+              x1 = dc_add_half_hi(rv[i], x1);
+            }
+            const f32x2 xp = {x0, x1};
+            f16x2 hp = __builtin_convertvector(xp, f16x2);
+            if (RELU) hp = __builtin_elementwise_max(hp, zero2);
+            o[i] = __builtin_bit_cast(unsigned, hp);
           }
-          const f32x2 xp = {x0, x1};
-          f16x2 hp = __builtin_convertvector(xp, f16x2);
-          if (RELU) hp = __builtin_elementwise_max(hp, zero2);
-          o[i] = __builtin_bit_cast(unsigned, hp);
         }
         *vp = o;  // the lane's own position: read (shortcut) and written (result) by this lane only
       }
@@ -412,15 +432,16 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void ws1x1_kernel(const W
 typedef void (*WsKernel)(const WsArgs);
 struct WsForm {
   int K, FN, NW, D;
-  WsKernel k[2][2][2];  // [shortcut][relu][multi]
+  WsKernel k[2][2][2];   // [shortcut][relu][multi], float16
+  WsKernel kb[2][2][2];  // ... bfloat16
 };
-#define DC_WS_K(K_, FN_, NW_, D_, R_, L_, M_) ws1x1_kernel<K_ / 16, FN_, NW_, D_, R_, L_, M_>
-#define DC_WS_FORM(K_, FN_, NW_, D_)                                                                                                    \
-  {K_, FN_, NW_, D_,                                                                                                                    \
-   {{{DC_WS_K(K_, FN_, NW_, D_, false, false, false), DC_WS_K(K_, FN_, NW_, D_, false, false, true)},                                     \
-     {DC_WS_K(K_, FN_, NW_, D_, false, true, false), DC_WS_K(K_, FN_, NW_, D_, false, true, true)}},                                      \
-    {{DC_WS_K(K_, FN_, NW_, D_, true, false, false), DC_WS_K(K_, FN_, NW_, D_, true, false, true)},                                       \
-     {DC_WS_K(K_, FN_, NW_, D_, true, true, false), DC_WS_K(K_, FN_, NW_, D_, true, true, true)}}}}
+#define DC_WS_K(T_, K_, FN_, NW_, D_, R_, L_, M_) ws1x1_kernel<T_, K_ / 16, FN_, NW_, D_, R_, L_, M_>
+#define DC_WS_KS(T_, K_, FN_, NW_, D_)                                                                                                  \
+  {{{DC_WS_K(T_, K_, FN_, NW_, D_, false, false, false), DC_WS_K(T_, K_, FN_, NW_, D_, false, false, true)},                              \
+    {DC_WS_K(T_, K_, FN_, NW_, D_, false, true, false), DC_WS_K(T_, K_, FN_, NW_, D_, false, true, true)}},                               \
+   {{DC_WS_K(T_, K_, FN_, NW_, D_, true, false, false), DC_WS_K(T_, K_, FN_, NW_, D_, true, false, true)},                                \
+    {DC_WS_K(T_, K_, FN_, NW_, D_, true, true, false), DC_WS_K(T_, K_, FN_, NW_, D_, true, true, true)}}}
+#define DC_WS_FORM(K_, FN_, NW_, D_) {K_, FN_, NW_, D_, DC_WS_KS(_Float16, K_, FN_, NW_, D_), DC_WS_KS(__bf16, K_, FN_, NW_, D_)}
 const WsForm kForms[] = {
     DC_WS_FORM(64, 2, 4, 4),   // 256-channel slices, 50 KB: res2x_branch2c, res2a_branch1
     DC_WS_FORM(128, 1, 8, 4),  // 256 as eight waves of one fragment, 66 KB: res3x_branch2c in two (20.4 us at batch 8; the tiles 23.6)
@@ -470,8 +491,10 @@ bool ws_tensor_ok(const void* x, const void* y, const void* resid, long M, long 
 }
 }  // namespace
 
-bool stream1x1_eligible(const ConvGemmParams& p) {
-  if (p.esize != 2 || p.ekind == kElemBF16 || p.ncls > 1 || p.nprob > 0 || p.nty != 1 || p.ntx != 1 || p.dy0 != 0 || p.x0 != 0 || p.sy != 1 || p.sigmoid_ch != 0) return false;
+namespace {
+// what both element kinds of the kernel take; ekind: kElemF16 (any 2-byte kind that is not bfloat16) or kElemBF16
+bool ws_eligible(const ConvGemmParams& p, int ekind) {
+  if (p.esize != 2 || (p.ekind == kElemBF16) != (ekind == kElemBF16) || p.ncls > 1 || p.nprob > 0 || p.nty != 1 || p.ntx != 1 || p.dy0 != 0 || p.x0 != 0 || p.sy != 1 || p.sigmoid_ch != 0) return false;
   const WsForm* f = form_of(p.klen);
   if (!f || p.Ktot != p.klen || p.Cout % (f->NW * f->FN * 32) != 0) return false;
   // dense NHWC on both sides: output pixel m reads the klen halves at m * sx and is written at m * y_pix_stride
@@ -482,6 +505,10 @@ bool stream1x1_eligible(const ConvGemmParams& p) {
   if ((long)p.M / 32 * ws_slots() >= 0x7fffffffL) return false;
   return true;
 }
+}  // namespace
+
+bool stream1x1_eligible(const ConvGemmParams& p) { return ws_eligible(p, kElemF16); }
+bool stream1x1_bf16_eligible(const ConvGemmParams& p) { return ws_eligible(p, kElemBF16); }
 
 long stream1x1_grid(const ConvGemmParams& p) {
   WsArgs a{};
@@ -500,8 +527,9 @@ void stream1x1_pack_filters(const float* g, int Cout, int K, float* out) {
       out[((((size_t)(co / 32) * (K / 16) + k / 16) * 64) + ((k % 16) / 8) * 32 + co % 32) * 8 + k % 8] = g[(size_t)co * K + k];
 }
 
-int launch_stream1x1(const ConvGemmParams& p, void* stream) {
-  if (!stream1x1_eligible(p)) return (int)hipErrorInvalidValue;
+namespace {
+int ws_launch(const ConvGemmParams& p, int ekind, void* stream) {
+  if (!ws_eligible(p, ekind)) return (int)hipErrorInvalidValue;
   if (!ws_tensor_ok(p.x, p.y, p.resid, p.M, p.sx, p.y_pix_stride) || ((uintptr_t)p.w & 15)) return (int)hipErrorInvalidValue;
   const WsForm* f = form_of(p.klen);
   WsArgs a{};
@@ -509,9 +537,13 @@ int launch_stream1x1(const ConvGemmParams& p, void* stream) {
   a.prob[0] = WsProblem{p.x, p.y, p.resid, p.M, p.sx * 2, p.y_pix_stride * 2, 0};
   const long grid = ws_plan(a, p.klen);
   if (grid <= 0 || grid > 0x7fffffffL) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(f->k[p.resid ? 1 : 0][p.relu ? 1 : 0][0], dim3((unsigned)grid), dim3(f->NW * 64), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL((ekind == kElemBF16 ? f->kb : f->k)[p.resid ? 1 : 0][p.relu ? 1 : 0][0], dim3((unsigned)grid), dim3(f->NW * 64), 0, (hipStream_t)stream, a);
   return (int)hipGetLastError();
 }
+}  // namespace
+
+int launch_stream1x1(const ConvGemmParams& p, void* stream) { return ws_launch(p, kElemF16, stream); }
+int launch_stream1x1_bf16(const ConvGemmParams& p, void* stream) { return ws_launch(p, kElemBF16, stream); }
 
 // ---- multi-problem launches (NetGroup): the same walk over the steps of several tensors in turn.  `p` carries the layer's common fields
 // (klen, sx, Cout, relu, scale, shift, w = the stream1x1_pack_filters image), tb.prob[0..nprob) the tensors.
@@ -545,14 +577,26 @@ long stream1x1_prepare_multi(const ConvGemmParams& p, const ConvMultiTable& tb, 
   return grid > 0 && grid <= 0x7fffffffL ? grid : -1;
 }
 
-int launch_stream1x1_multi(const ConvMultiArgs& m, void* stream) {
+// (the float16 entry keeps taking whatever 2-byte launch the group hands it; the bfloat16 one asks for its element kind)
+long stream1x1_bf16_prepare_multi(const ConvGemmParams& p, const ConvMultiTable& tb, int nprob) {
+  return p.ekind == kElemBF16 ? stream1x1_prepare_multi(p, tb, nprob) : -1;
+}
+
+namespace {
+int ws_launch_multi(const ConvMultiArgs& m, bool bf, void* stream) {
   WsArgs a;
   if (!ws_fill_multi(a, m.p, m.t, m.p.nprob) || ((uintptr_t)m.p.w & 15)) return (int)hipErrorInvalidValue;
   const WsForm* f = form_of(m.p.klen);
   const long grid = ws_plan(a, m.p.klen);
   if (grid <= 0 || grid > 0x7fffffffL) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(f->k[a.prob[0].resid ? 1 : 0][a.relu ? 1 : 0][a.nprob > 1 ? 1 : 0], dim3((unsigned)grid), dim3(f->NW * 64), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL((bf ? f->kb : f->k)[a.prob[0].resid ? 1 : 0][a.relu ? 1 : 0][a.nprob > 1 ? 1 : 0], dim3((unsigned)grid), dim3(f->NW * 64), 0, (hipStream_t)stream, a);
   return (int)hipGetLastError();
+}
+}  // namespace
+
+int launch_stream1x1_multi(const ConvMultiArgs& m, void* stream) { return ws_launch_multi(m, false, stream); }
+int launch_stream1x1_bf16_multi(const ConvMultiArgs& m, void* stream) {
+  return m.p.ekind == kElemBF16 ? ws_launch_multi(m, true, stream) : (int)hipErrorInvalidValue;
 }
 
 }  // namespace dc

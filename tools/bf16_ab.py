@@ -1,9 +1,11 @@
 """A/B of the bfloat16 mode against float16 on one box: every leg in a fresh process, the legs alternated `--reps` times.
 
-    python tools/bf16_ab.py [--reps 3] [--steps 20] [--out FILE]
+    python tools/bf16_ab.py [--reps 3] [--steps 20] [--out FILE] [--legs f16,bf16,bf16-forms] [--parent DIR]
 
 Legs: f16 (default forms: wino_h23 / ws1x1 / stem7x7 where the tuner takes them), f16-direct (DC_WINOGRAD=0 DC_STREAM1X1=0 DC_STEM=0:
-the gather-GEMM tiles only, what bf16 runs on) and bf16.  Workloads: the batch-8 544x736 forward one at a time (device-resident,
+the gather-GEMM tiles only, what bf16 runs on by default), bf16 (its switches unset: tiles only) and bf16-forms (DC_STREAM1X1_BF16=-1
+DC_STEM_BF16=-1: bs1x1 / bs7x7 where the tuner takes them).  --parent DIR adds the leg bf16-parent: the bf16 leg of another built checkout
+(its own tools/bf16_ab.py), for a comparison across commits.  Workloads: the batch-8 544x736 forward one at a time (device-resident,
 hipGraph) and the 4-scale pyramid (batch 8 x 272x368 .. 680x920) as one NetGroup.  Each leg tunes its tiles in its own process
 (a tune cache per leg, under --cache-dir: the first repetition tunes, the later ones read it).  One JSON line per leg and
 repetition, then the medians; a child that fails ends the run.  Each child runs under its own `timeout -k 10`."""
@@ -15,7 +17,9 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LEGS = {"f16": ("f16", {}), "f16-direct": ("f16", {"DC_WINOGRAD": "0", "DC_STREAM1X1": "0", "DC_STEM": "0"}), "bf16": ("bf16", {})}
+LEGS = {"f16": ("f16", {}), "f16-direct": ("f16", {"DC_WINOGRAD": "0", "DC_STREAM1X1": "0", "DC_STEM": "0"}), "bf16": ("bf16", {}),
+        "bf16-forms": ("bf16", {"DC_STREAM1X1_BF16": "-1", "DC_STEM_BF16": "-1"})}
+PARENT_LEG = "bf16-parent"
 SHAPES = [(272, 368), (408, 552), (544, 736), (680, 920)]
 
 
@@ -78,33 +82,43 @@ def main():
     ap.add_argument("--child", nargs=2, metavar=("LEG", "WORK"))
     ap.add_argument("--timeout", type=int, default=600, help="seconds per child process")
     ap.add_argument("--cache-dir", default="", help="directory of the per-leg tune caches (default: beside --out, else the working directory)")
+    ap.add_argument("--legs", default="", help="comma-separated subset of the legs (default: all)")
+    ap.add_argument("--parent", default="", help="another built checkout of this repository: adds the leg bf16-parent")
     a = ap.parse_args()
     if a.child:
         return child(a.child[0], a.child[1], a.steps)
+    legs = [leg for leg in a.legs.split(",") if leg] or list(LEGS)
+    if any(leg not in LEGS for leg in legs):
+        raise SystemExit("legs: " + ", ".join(LEGS))
+    if a.parent:
+        legs.insert(0, PARENT_LEG)
     rows = []
     for rep in range(a.reps):
         for work in ("b8", "pyramid"):
-            for leg in LEGS:
-                env = dict(os.environ, **LEGS[leg][1])
+            for leg in legs:
+                for k in ("DC_STREAM1X1_BF16", "DC_STEM_BF16"):  # the legs set their own
+                    os.environ.pop(k, None)
+                env = dict(os.environ, **(LEGS[leg][1] if leg in LEGS else {}))
+                script = os.path.join(os.path.abspath(a.parent), "tools", "bf16_ab.py") if leg == PARENT_LEG else os.path.abspath(__file__)
                 cdir = a.cache_dir or (os.path.dirname(os.path.abspath(a.out)) if a.out else ".")
                 env["DC_TUNE_CACHE"] = os.path.join(cdir, "bf16_ab_tune_%s.txt" % leg)
-                cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--child", leg, work, "--steps", str(a.steps)]
+                cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, script, "--child", "bf16" if leg == PARENT_LEG else leg, work, "--steps", str(a.steps)]
                 p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True)
                 if p.returncode != 0:
                     sys.stderr.write(p.stderr[-3000:])
                     raise SystemExit("leg %s / %s failed with status %d: stopping" % (leg, work, p.returncode))
                 r = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
-                r["rep"] = rep
+                r["rep"], r["leg"] = rep, leg
                 rows.append(r)
                 print(json.dumps(r), flush=True)
     summary = {}
     for work in ("b8", "pyramid"):
-        for leg in LEGS:
+        for leg in legs:
             v = sorted(r["images_per_s"] for r in rows if r["leg"] == leg and r["work"] == work)
             summary["%s/%s" % (work, leg)] = {"median_images_per_s": v[len(v) // 2], "min": v[0], "max": v[-1]}
-        base = summary["%s/f16-direct" % work]["median_images_per_s"]
-        summary["%s/bf16_vs_f16_direct" % work] = summary["%s/bf16" % work]["median_images_per_s"] / base - 1.0
-        summary["%s/bf16_vs_f16" % work] = summary["%s/bf16" % work]["median_images_per_s"] / summary["%s/f16" % work]["median_images_per_s"] - 1.0
+        for x, y in (("bf16", "f16-direct"), ("bf16", "f16"), ("bf16-forms", "bf16"), ("bf16-forms", "f16"), ("bf16", PARENT_LEG)):
+            if x in legs and y in legs:
+                summary["%s/%s_vs_%s" % (work, x.replace("-", "_"), y.replace("-", "_"))] = summary["%s/%s" % (work, x)]["median_images_per_s"] / summary["%s/%s" % (work, y)]["median_images_per_s"] - 1.0
     print(json.dumps({"summary": summary}, indent=1))
     if a.out:
         with open(a.out, "w") as f:
