@@ -68,7 +68,7 @@ def pair_costs(prob, loc, next_pred, edges, scale=1.0, threshold=0.1, radius=1, 
     return counts, dets, pair_costs_from_candidates(counts, dets, next_pred, edges, scale, mean, std)
 
 
-def assemble(counts, dets, cost, max_cost, seed_threshold, max_people=32, min_joints=1, joint_order=None, gaps=None):
+def assemble(counts, dets, cost, max_cost, seed_threshold, max_people=32, min_joints=1, joint_order=None, gaps=None, stats=None):
     """Stage C on ONE image -> (people float64 [m, J, 3], cand int32 [m, J]).
 
     gaps (a dict, optional) receives how far the run was from deciding otherwise:
@@ -76,14 +76,20 @@ def assemble(counts, dets, cost, max_cost, seed_threshold, max_people=32, min_jo
                 (another link of the same person or of the same candidate that was still open);
       "max_cost": the smallest |L - max_cost| over every finite link cost that was compared with max_cost.
     A perturbation of the costs smaller than half of both cannot change the result: links that share neither the person nor the
-    candidate with the chosen one stay open whichever of them goes first, so their order does not matter."""
+    candidate with the chosen one stay open whichever of them goes first, so their order does not matter.
+
+    stats (a dict, optional) receives what the run exercised:
+      "tie_steps": the number of linking steps at which two or more open links had the minimal cost (the first in (p, i) order won);
+      "max_links": the largest people x candidates of any joint, the length of the device's link list."""
     J = len(counts)
     order = list(range(J)) if joint_order is None else [int(j) for j in joint_order]
     seed = float(np.float32(seed_threshold))  # the C structure carries it as a float
     people = []
     g_choice, g_max = INF, INF
+    tie_steps, max_links = 0, 0
     for j in order:
         m = int(counts[j])
+        max_links = max(max_links, len(people) * m)
         used = [False] * m
         L = {}
         for p in range(len(people)):
@@ -111,10 +117,14 @@ def assemble(counts, dets, cost, max_cost, seed_threshold, max_people=32, min_jo
             if best is None:
                 break
             _, bp, bi = best
-            for p in range(len(people)):
-                for i in range(m):
-                    if (p, i) != (bp, bi) and (p == bp or i == bi) and not used[i] and people[p][j] < 0:
-                        g_choice = min(g_choice, L[p, i] - best[0])
+            if stats is not None:
+                tie_steps += sum(1 for p in range(len(people)) if people[p][j] < 0
+                                 for i in range(m) if not used[i] and L[p, i] == best[0]) >= 2
+            if gaps is not None:
+                for p in range(len(people)):
+                    for i in range(m):
+                        if (p, i) != (bp, bi) and (p == bp or i == bi) and not used[i] and people[p][j] < 0:
+                            g_choice = min(g_choice, L[p, i] - best[0])
             people[bp][j] = bi
             used[bi] = True
         for i in range(m):
@@ -131,6 +141,8 @@ def assemble(counts, dets, cost, max_cost, seed_threshold, max_people=32, min_jo
                 out[q, a] = dets[a, p[a], :3]
     if gaps is not None:
         gaps["choice"], gaps["max_cost"] = g_choice, g_max
+    if stats is not None:
+        stats["tie_steps"], stats["max_links"] = tie_steps, max_links
     return out, cand
 
 
@@ -191,3 +203,31 @@ def planted_scene(h, w, edges, mean, std, scale=1.0, num_joints=14, sixteen_bit=
         prob[j, r, c] = 0.5625
         strays.append((j, (c * M.STRIDE + 4.0) / scale, (r * M.STRIDE + 4.0) / scale))
     return prob, loc, nxt, joints, strays
+
+
+def crowded_scene(h, w, edges, seed, peaks=40, lattice=False, sixteen_bit=False, num_joints=14):
+    """Maps [J, h, w], [2J, h, w], [2E, h, w] (float32) with `peaks` isolated score peaks per joint, on cells with even row and column
+    (two peaks are at least 2 cells apart: each is alone in its 3x3 neighbourhood, a candidate at radius 1).  Scores lie in
+    [0.6, 0.95]: drawn and rounded to float32, or — sixteen_bit — distinct values that float16 and bfloat16 both hold exactly, so that
+    the candidate order does not hang on a tie.  `loc_pred` is small and random and `next_pred` standard normal (the caller's mean /
+    std spread the predictions over the image), both rounded with round_to_bf16 when sixteen_bit.
+    lattice: `loc_pred` = `next_pred` = 0.  Without mean / std at scale 1 every candidate sits on its cell centre and predicts that
+    centre for every edge, so every pair cost is the distance between two points of a 16-pixel lattice: equal costs are exactly equal
+    in double, on the device and here."""
+    E = np.asarray(edges).reshape(-1, 2).shape[0]
+    rs = np.random.RandomState(seed)
+    spots = [(r, c) for r in range(0, h, 2) for c in range(0, w, 2)]
+    assert len(spots) >= peaks
+    prob = np.zeros((num_joints, h, w), np.float32)
+    grid16 = np.arange(154, 244) / 256.0  # the 8-bit-mantissa values of [0.6, 0.95]: exact in both 16-bit types
+    for j in range(num_joints):
+        where = rs.choice(len(spots), peaks, replace=False)
+        score = rs.choice(grid16, peaks, replace=False) if sixteen_bit else rs.uniform(0.6, 0.95, peaks)
+        for s, v in zip(where, score):
+            prob[j][spots[s]] = np.float32(v)
+    if lattice:
+        return prob, np.zeros((2 * num_joints, h, w), np.float32), np.zeros((2 * E, h, w), np.float32)
+    q16 = round_to_bf16 if sixteen_bit else (lambda v: np.asarray(v, np.float32))
+    loc = q16(rs.uniform(-0.3, 0.3, (2 * num_joints, h, w)))
+    nxt = q16(rs.randn(2 * E, h, w))
+    return prob, loc, nxt

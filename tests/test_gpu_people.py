@@ -202,3 +202,105 @@ def test_estimate_people_on_a_uint8_image(net):
     assert got.shape == by_hand.shape and got.shape[1:] == (14, 3) and np.array_equal(got, by_hand)
     boxes = people_boxes(got, img.shape, 10)
     assert boxes.shape == (len(got), 4) and (boxes[:, 2] > boxes[:, 0]).all() and (boxes[:, 3] > boxes[:, 1]).all()
+
+
+# ---- crowded scenes: every 256-thread loop of the two kernels past its first trip ------------------------------------------------
+CROWD_SEED = 21  # chosen on the CPU: the restatement alone links some candidates and leaves others alone at max_cost 15 and 60
+CROWD = dict(scale=1.0, threshold=0.5, radius=1, max_det=64, seed_threshold=0.7, max_people=256, min_joints=1)
+_scenes = {}
+
+
+def _crowded(kind):
+    """kind: "f32", "16bit" or "lattice" -> the maps and the restatement's candidates and costs of them, computed once per process and
+    never written to afterwards.  40 candidates per joint: MD * MD = 4096 cost entries per joint pair, J * MD = 896 predictions,
+    people x candidates up to 10240 links."""
+    if kind not in _scenes:
+        edges = R.all_pairs_edges()
+        prob, loc, nxt = R.crowded_scene(H // 8, W // 8, edges, CROWD_SEED, lattice=kind == "lattice", sixteen_bit=kind == "16bit")
+        stats = {} if kind == "lattice" else {"mean": MEAN, "std": STD}
+        counts, dets, cost = R.pair_costs(prob, loc, nxt, edges, 1.0, CROWD["threshold"], 1, CROWD["max_det"], stats.get("mean"), stats.get("std"))
+        assert (counts == 40).all()
+        _scenes[kind] = dict(edges=edges, prob=prob, loc=loc, nxt=nxt, counts=counts, dets=dets, cost=cost, stats=stats)
+    return _scenes[kind]
+
+
+@pytest.fixture(scope="module")
+def crowd_net(gpu_caffe, synth152):
+    return _planted_net(gpu_caffe, synth152, "f32")
+
+
+def _check_crowded(n, sc, max_cost, want_ties=0, **over):
+    """The assertions of the crowded scenes, for one max_cost: candidates and costs against the restatement of the maps, the assembly
+    against the restatement run on the device's own candidates and costs (bit for bit), three identical runs.  -> the run's stats."""
+    n.blobs["prob"].data[0], n.blobs["loc_pred"].data[0], n.blobs["next_pred"].data[0] = sc["prob"], sc["loc"], sc["nxt"]
+    q = dict(CROWD, **over)
+    order = q.pop("joint_order", None)
+    # the restatement alone first: what the scene is there for must happen in it
+    st = {}
+    alone, alone_cand = R.assemble(sc["counts"], sc["dets"], sc["cost"], max_cost, q["seed_threshold"], q["max_people"], q["min_joints"], order, stats=st)
+    linked, single = int((alone_cand >= 0).sum() - len(alone_cand)), int(((alone_cand >= 0).sum(1) == 1).sum())
+    print("crowded scene, max_cost %g, %s: the restatement alone has %d people, %d linked joints, %d single-joint people, %d tie steps, "
+          "at most %d links per joint" % (max_cost, over or "defaults", len(alone_cand), linked, single, st["tie_steps"], st["max_links"]))
+    assert st["max_links"] > 256 or q["max_people"] < 256, "people x candidates never left the first trip of the 256-thread loops"
+    assert st["tie_steps"] >= want_ties
+    counts, dets = n.detect_parts(1.0, q["threshold"], q["radius"], q["max_det"])
+    assert np.array_equal(counts[0], sc["counts"]) and np.array_equal(dets[0][:, :, 2:], sc["dets"][:, :, 2:])
+    # score, cell row and cell column exactly; x and y to 1e-9, the bound the decoders are held to everywhere in this file (the device
+    # evaluates cell * 8 + 4 + loc * sqrt(53) in its own order); the assembly below runs on the DEVICE's candidates, so it is not affected
+    assert np.abs(dets[0][:, :, :2] - sc["dets"][:, :, :2]).max() <= 1e-9
+    kw = dict(edges=sc["edges"], max_cost=max_cost, joint_order=order, **dict(q, **sc["stats"]))
+    runs = [n.assemble_people(return_cost=True, **kw)[0] for _ in range(3)]
+    got, fin = runs[0]["cost"], np.isfinite(sc["cost"])
+    assert np.array_equal(np.isposinf(got), np.isposinf(sc["cost"])) and not np.isnan(got).any() and not np.isneginf(got).any()
+    err = float(np.abs(got[fin] - sc["cost"][fin]).max())
+    print("crowded scene: %d finite costs, max |device - restatement| = %.3e" % (fin.sum(), err))
+    assert err <= 1e-9
+    assert np.array_equal(got, got.transpose(1, 0, 3, 2))
+    people, cand = R.assemble(counts[0], dets[0], got, max_cost, q["seed_threshold"], q["max_people"], q["min_joints"], order)
+    assert len(runs[0]["cand"]) == len(cand)  # the people count
+    assert np.array_equal(runs[0]["cand"], cand) and np.array_equal(runs[0]["people"], people)
+    for r in runs[1:]:
+        assert np.array_equal(r["cand"], cand) and np.array_equal(r["people"], people) and np.array_equal(r["cost"], got)
+    return dict(st, people=len(alone_cand), linked=linked, single=single)
+
+
+@pytest.mark.parametrize("max_cost", [15.0, 60.0, 1e9])
+def test_crowded_scene_at_the_entry_limits(crowd_net, max_cost):
+    """40 candidates per joint with max_det = 64 (kPeopleMaxDet) and max_people = 256 (kPeopleMaxPeople): the cost kernel's loops over
+    MD * MD and J * MD and the assembly's loops over people x candidates take up to 40 trips, and the arg-min's per-thread part really
+    compares several links.  At the two finite max_cost values some candidates link and others do not."""
+    st = _check_crowded(crowd_net, _crowded("f32"), max_cost)
+    assert st["max_links"] > 256
+    if max_cost < 1e9:
+        assert st["linked"] > 0 and st["single"] > 0, st
+    else:
+        # nothing is too far to link, so a person is only ever seeded by a candidate that found every person taken: joint 0 seeds its 25
+        # candidates at or above the seed threshold, and later joints, with 40 candidates each, seed the rest up to 40 people
+        assert st["people"] == 40 and st["single"] == 0, st
+
+
+@pytest.mark.parametrize("order", [None, list(range(13, -1, -1))], ids=["default_order", "reversed_order"])
+def test_lattice_scene_ties_go_to_the_first_link(crowd_net, order):
+    """Every cost is a distance between points of a 16-pixel lattice, so the minimal link cost is shared by several open links at many
+    steps (counted by the restatement: at least 10): the winner must be the first in (person, candidate) order, through the per-thread
+    part of the arg-min (e ascending within a thread) and through the LDS reduction (the smaller e of two equal costs)."""
+    st = _check_crowded(crowd_net, _crowded("lattice"), 40.0, want_ties=10, joint_order=order)
+    assert st["tie_steps"] >= 10 and st["max_links"] > 256
+
+
+def test_crowded_scene_under_the_caps(crowd_net):
+    """max_people = 24, below the 25 seeds of the first joint, and min_joints = 14 (only complete people stay)."""
+    few = _check_crowded(crowd_net, _crowded("f32"), 60.0, max_people=24)
+    assert few["people"] == 24
+    whole = _check_crowded(crowd_net, _crowded("f32"), 1e9, min_joints=14)
+    assert 0 < whole["people"] < 40
+
+
+@pytest.mark.parametrize("dtype", ["f16", "bf16"])
+def test_crowded_scene_on_sixteen_bit_nets(gpu_caffe, synth152, dtype):
+    """The crowded scene with every map value rounded to one that float16 and bfloat16 hold exactly (round_to_bf16; the 40 scores of a
+    joint are distinct such values): the same assertions."""
+    n = _planted_net(gpu_caffe, synth152, dtype)
+    assert n.dtype == dtype
+    st = _check_crowded(n, _crowded("16bit"), 60.0)
+    assert st["max_links"] > 256 and st["linked"] > 0
