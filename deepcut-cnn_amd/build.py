@@ -9,62 +9,85 @@ import hashlib
 import os
 import subprocess
 import sys
+from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "lib", "libdeepcut_hip.so")
-SOURCES = ["formats.cpp", "hdf5_reader.cpp", "runtime.cpp", "net_init.cpp", "net_lower.cpp", "net_tune.cpp", "net_run.cpp", "net_image.cpp",
-           "net_group.cpp", "people.cpp", "streams.cpp", "multi_gpu.cpp", "c_api.cpp", "kernels.hip", "wino_f16.hip", "stream1x1.hip", "stem_f16.hip", "stream1x1_f32.hip", "people.hip"]
-HEADERS = ["formats.h", "net.h", "net_internal.h", "kernels.h", "kernel_prims.h", os.path.join("..", "..", "include", "deepcut_hip.h")]
+# (the three gather-GEMM instantiation files take the longest by far: they come first, so that they start first)
+SOURCES = ["conv_gemm_f16.hip", "conv_gemm_bf16.hip", "conv_gemm_f32.hip", "wino_f32.hip", "wino_f16.hip", "stream1x1.hip", "stem_f16.hip",
+           "stream1x1_f32.hip", "people.hip", "layers.hip", "pose.hip", "image_prep.hip", "conv_gemm.cpp", "forms.cpp", "formats.cpp",
+           "hdf5_reader.cpp", "runtime.cpp", "net_init.cpp", "net_lower.cpp", "net_tune.cpp", "net_run.cpp", "net_image.cpp", "net_group.cpp",
+           "people.cpp", "streams.cpp", "multi_gpu.cpp", "c_api.cpp"]
+HEADERS = ["formats.h", "net.h", "net_internal.h", "kernels.h", "kernel_prims.h", "conv_gemm.h", "conv_gemm_variants.h", "by_kind.h",
+           os.path.join("..", "..", "include", "deepcut_hip.h")]
+MAX_JOBS = 16  # compiler processes at a time
 
 
 KERNEL_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-inline-asm"]
-ASM = os.path.join(HERE, "lib", "kernels.gfx950.s")
+# the sources whose kernels issue inline-asm memory requests (dc_dma16, dc_load_f32_untracked: the gather-GEMM), and what they include
+ASM_SOURCES = ["conv_gemm_f16.hip", "conv_gemm_bf16.hip", "conv_gemm_f32.hip"]
+ASM_HEADERS = ["conv_gemm.h", "conv_gemm_variants.h", "kernels.h", "kernel_prims.h"]
 
 
-def _asm_key():
-    """What the device assembly of kernels.hip depends on: its sources, the flags, the compiler."""
+def _asm_path(src):
+    return os.path.join(HERE, "lib", src[:-len(".hip")] + ".gfx950.s")
+
+
+def _asm_key(src):
+    """What the device assembly of a source depends on: the source and its headers, the flags, the compiler."""
     h = hashlib.sha256()
-    for f in ("kernels.hip", "kernels.h", "kernel_prims.h"):
+    for f in [src] + ASM_HEADERS:
         h.update(open(os.path.join(CSRC, f), "rb").read())
     h.update(" ".join(KERNEL_FLAGS).encode())
     h.update(_hipcc_version())
     return h.hexdigest()
 
 
-def _asm_fresh():
+def _asm_fresh(src):
     try:
-        return os.path.getsize(ASM) > 0 and open(ASM + ".key").read().strip() == _asm_key()
+        return os.path.getsize(_asm_path(src)) > 0 and open(_asm_path(src) + ".key").read().strip() == _asm_key(src)
     except OSError:
         return False
 
 
-def _asm_job():
-    """The gfx950 assembly of kernels.hip (device side only, the library's own flags), as a process: what
-    tools/check_asm_hazards.py reads.  Started beside the object compile of build_lib so that the CPU test suite
-    (tests/test_asm_hazards.py) finds it ready instead of compiling the 2 300-line translation unit a second time."""
+def _asm_cmd(src):
+    """The command that writes the gfx950 assembly of a source (device side only, the library's own flags): what
+    tools/check_asm_hazards.py reads.  build_lib runs it beside the object compiles so that the CPU test suite
+    (tests/test_asm_hazards.py) finds the assemblies ready instead of compiling the gather-GEMM instantiations a second time."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    os.makedirs(os.path.dirname(ASM), exist_ok=True)
-    for f in (ASM, ASM + ".key"):
+    asm = _asm_path(src)
+    os.makedirs(os.path.dirname(asm), exist_ok=True)
+    for f in (asm, asm + ".key"):
         if os.path.exists(f):
             os.remove(f)
-    return subprocess.Popen([hipcc] + KERNEL_FLAGS + ["--offload-device-only", "-S", os.path.join(CSRC, "kernels.hip"), "-o", ASM + ".tmp"])
+    return [hipcc] + KERNEL_FLAGS + ["--offload-device-only", "-S", os.path.join(CSRC, src), "-o", asm + ".tmp"]
 
 
-def _asm_finish(proc, key):
-    if proc.wait() != 0:
-        raise RuntimeError("device assembly of kernels.hip failed")
-    os.replace(ASM + ".tmp", ASM)
-    with open(ASM + ".key", "w") as f:
+def _write_key(path, key):
+    with open(path + ".key", "w") as f:
         f.write(key + "\n")
 
 
+def _asm_finish(src, key):
+    os.replace(_asm_path(src) + ".tmp", _asm_path(src))
+    _write_key(_asm_path(src), key)
+
+
+def _run(cmds):
+    """Run the commands, MAX_JOBS at a time; their exit codes, in order."""
+    with ThreadPoolExecutor(MAX_JOBS) as pool:
+        return list(pool.map(subprocess.call, cmds))
+
+
 def device_asm():
-    """Path of the gfx950 assembly of kernels.hip, compiled now unless the cached one matches the sources."""
-    if not _asm_fresh():
-        key = _asm_key()
-        _asm_finish(_asm_job(), key)
-    return ASM
+    """Paths of the gfx950 assemblies of ASM_SOURCES, each compiled now unless the cached one matches its sources."""
+    stale = [(s, _asm_key(s)) for s in ASM_SOURCES if not _asm_fresh(s)]
+    for (src, key), code in zip(stale, _run([_asm_cmd(s) for s, _ in stale])):
+        if code != 0:
+            raise RuntimeError("device assembly of %s failed" % src)
+        _asm_finish(src, key)
+    return [_asm_path(s) for s in ASM_SOURCES]
 
 
 _HIPCC_VERSION = None
@@ -114,15 +137,15 @@ def _stale():
 
 
 def build_lib(force=False, verbose=True):
-    """Per-file incremental, keyed by content hashes (kernels.hip takes a minute, the host translation units seconds each — they
-    compile in parallel): an object is rebuilt when the hash of its source + the headers + the flags + the compiler differs from
-    the one recorded beside it, the library is re-linked when any object's key changed."""
+    """Per-file incremental, keyed by content hashes (a gather-GEMM instantiation file takes a minute, the other translation units
+    seconds each — they compile in parallel, MAX_JOBS at a time): an object is rebuilt when the hash of its source + the headers + the
+    flags + the compiler differs from the one recorded beside it, the library is re-linked when any object's key changed."""
     if not force and not _stale():
         return OUT
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    objs, jobs, keys = [], [], []
-    asm = None
+    objs, keys = [], []
+    jobs = []  # (what, command, what to do once it has succeeded)
     for src in SOURCES:
         obj = os.path.join(HERE, "lib", src + ".o")
         objs.append(obj)
@@ -139,16 +162,15 @@ def build_lib(force=False, verbose=True):
             cmd.insert(2, "hip")
         if verbose:
             print(" ".join(cmd), flush=True)
-        jobs.append((src, obj, key, subprocess.Popen(cmd)))
-        if src == "kernels.hip" and not _asm_fresh():
-            asm = (_asm_job(), _asm_key())
+        jobs.append((src, cmd, lambda obj=obj, key=key: _write_key(obj, key)))
+        if src in ASM_SOURCES and not _asm_fresh(src):
+            jobs.append(("device assembly of " + src, _asm_cmd(src), lambda src=src, key=_asm_key(src): _asm_finish(src, key)))
     failed = []
-    for src, obj, key, p in jobs:
-        if p.wait() != 0:
-            failed.append(src)
+    for (what, _, done), code in zip(jobs, _run([j[1] for j in jobs])):
+        if code != 0:
+            failed.append(what)
         else:
-            with open(obj + ".key", "w") as f:
-                f.write(key + "\n")
+            done()
     if failed:
         raise RuntimeError("compilation failed: %s" % ", ".join(failed))
     if os.path.exists(OUT + ".key"):
@@ -157,10 +179,7 @@ def build_lib(force=False, verbose=True):
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
-    with open(OUT + ".key", "w") as f:
-        f.write(_lib_key(keys) + "\n")
-    if asm:
-        _asm_finish(*asm)
+    _write_key(OUT, _lib_key(keys))
     return OUT
 
 

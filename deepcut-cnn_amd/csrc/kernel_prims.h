@@ -1,4 +1,4 @@
-// kernel_prims.h — the device primitives every kernel source shares (kernels.hip, wino_f16.hip, stream1x1.hip, stream1x1_f32.hip,
+// kernel_prims.h — the device primitives every kernel source shares (conv_gemm.h, wino_f32.hip, wino_f16.hip, stream1x1.hip, stream1x1_f32.hip,
 // stem_f16.hip): vector types, buffer descriptors, the magic-number division, and the inline-asm memory, wait, barrier and lane
 // primitives.  Each exists once here: a fix to one of them (wait states in front of an inline-asm request, say) is one edit.
 #pragma once

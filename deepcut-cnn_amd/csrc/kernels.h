@@ -1,4 +1,4 @@
-// kernels.h — launch interface of the gfx950 kernels (kernels.hip).  Plain structs, no HIP types
+// kernels.h — launch interface of the gfx950 kernels (the .hip sources and conv_gemm.cpp, forms.cpp).  Plain structs, no HIP types
 // in the signatures except the opaque stream, so the graph runtime (net_*.cpp) stays host-only C++.
 #pragma once
 #include <cstddef>
@@ -12,6 +12,8 @@ constexpr int kMaxTaps = 32;  // tap-validity masks are one 32-bit word per stag
 // magic {multiplier, shift word} of n / d for 0 <= n < 2^31 and a divisor known on the host (the device divides with dc_fastdiv,
 // kernel_prims.h): sh = 31 + ceil(log2 d), mul = floor(2^sh / d) + 1, n / d = (n * mul) >> sh; d <= 1 sets bit 31 of the shift word
 void dc_magic(unsigned d, unsigned (&mg)[2]);
+// DC_XCD_MAP (on unless set to 0, read once): the per-XCD tile map of the single-problem gather-GEMM launches and of the Winograd forms
+bool xcd_map_on();
 
 // element kind of the device images (the values of DC_OPT_DTYPE): float32, float16, bfloat16.  Host tensors, the per-channel
 // affine vectors and every accumulation are float in all three.
@@ -186,6 +188,13 @@ bool wino_same3x3(const ConvGemmParams& p);
 // bty x btx tile blocks and the magic numbers of the kernel's block-index divisions, the first one by blocks_per_wg blocks at a time
 ConvGemmParams wino_launch_params(const ConvGemmParams& p, long grid, int bty, int btx, int blocks_per_wg);
 long wino_grid(const ConvGemmParams& p);                   // of the 4 x 8-tile forms
+long wino_grid_5x6(const ConvGemmParams& p);               // of the 5 x 6-tile forms
+bool wino_fewer_blocks(const ConvGemmParams& p);           // the 5 x 6 forms need strictly fewer workgroups: where they are offered to the autotuner
+// the four forms: 8 or 16 (_w16) waves per workgroup, 4 x 8- or 5 x 6-tile blocks
+int launch_wino_f23(const ConvGemmParams& p, void* stream);
+int launch_wino_f23_w16(const ConvGemmParams& p, void* stream);
+int launch_wino_f23_5x6(const ConvGemmParams& p, void* stream);
+int launch_wino_f23_5x6_w16(const ConvGemmParams& p, void* stream);
 long wino_blocks(int TY, int TX, int bty, int btx);        // bty x btx-tile blocks that cover a TY x TX tile grid
 long wino_form_blocks(int variant, int TY, int TX);        // ... blocks of the float32 Winograd form `variant`; -1: not one
 size_t wino_packed_floats(int Cout, int Cin);
@@ -242,7 +251,7 @@ int launch_stem7x7_bf16(const ConvGemmParams& p, void* stream);
 
 // ---- FORMS: the convolution kernels outside the tile tables.  A form has a filter image of its own (Launch::form_w) and is timed against
 // the tiles per shape.  Its variant number travels in Launch::variant and tune caches like a tile's, and DC_CONV_VARIANT takes it.
-constexpr int kWinoVariant = 1000;    // "wino_f23": Winograd F(2x2, 3x3), float32, 8 waves per workgroup (kernels.hip)
+constexpr int kWinoVariant = 1000;    // "wino_f23": Winograd F(2x2, 3x3), float32, 8 waves per workgroup (wino_f32.hip)
 constexpr int kWinoVariant16 = 1001;  // "wino_f23_w16": its 16-wave form (launches of at most one workgroup per CU)
 constexpr int kWinoHalf = 1002;       // "wino_h23": the float16 Winograd kernel (wino_f16.hip): fp16 operands, fp32 accumulate
 constexpr int kStreamHalf = 1003;     // "ws1x1": the float16 streaming form of the dense 1x1 layers (stream1x1.hip)

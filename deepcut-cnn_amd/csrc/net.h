@@ -9,7 +9,7 @@
 // into the producing convolution's epilogue, residual Eltwise adds and the Deconvolution+Crop+Eltwise
 // heads are fused, activations live channels-last (NHWC) in HBM, and every convolution /
 // deconvolution is one launch (4 for a stride-2 deconvolution: one per output parity class) of the
-// gather-GEMM MFMA kernel in kernels.hip.
+// gather-GEMM MFMA kernel in conv_gemm.h.
 #pragma once
 #include <cmath>
 #include <cstdint>

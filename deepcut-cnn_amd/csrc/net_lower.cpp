@@ -685,7 +685,7 @@ void Net::build_plan() {
           half_row_scale(l, op, OC);
       choose_variant(l, kgcd);
       // stride-1 3x3 layers can also run as Winograd F(2x2,3x3): keep the transformed filters next to the direct ones
-      // and let the per-shape timing decide (kernels.hip, wino_f23_kernel)
+      // and let the per-shape timing decide (wino_f32.hip, wino_f23_kernel)
       if (!rowtap && wino_mode != 0 && op.wls.empty() && wino_eligible(g) && dtype == kElemF32) {
         l.form_w = get_vec(dkey + "wino:" + std::to_string(op.wl), [&](std::vector<float>& h) {
           h.assign(wino_packed_floats(c.num_output, C), 0.f);

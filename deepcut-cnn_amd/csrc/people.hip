@@ -4,7 +4,7 @@
 // pair cost inverts the label encoding of its training layer (src/caffe/layers/pose_data_layer.cpp:686-802) exactly as
 // pairwise_decode_kernel does; the greedy grouping rule is this project's own.
 //
-// Two latency-class kernels behind part_select_kernel (kernels.hip), nothing of them on the forward path:
+// Two latency-class kernels behind part_select_kernel (pose.hip), nothing of them on the forward path:
 //   pair_cost_kernel  one workgroup per (image, joint a): cost[b][a][c][i][k] for every partner joint c and candidate pair
 //   assemble_kernel   one workgroup per image: the greedy linking, joint after joint, on that cost tensor
 // All arithmetic is double, like the two decoders.  Double rate does not matter here: a full cost tensor (14 x 14 x 64 x 64) is

@@ -1,0 +1,247 @@
+// pose.hip — what reads the net's maps on the device: pose decode, part candidates, pairwise regression decode.
+#include <hip/hip_runtime.h>
+
+#include <type_traits>
+
+#include "by_kind.h"
+#include "kernels.h"
+
+namespace dc {
+
+// ------------------------------------------------------------------------------------------------
+// pose decode on the device (estimate_pose.py:131-143 `_pose_from_mats`): per joint the FIRST maximum of
+// the score map in row-major order, refined by the location-regression vector at that cell.  One block
+// per (image, joint); only 5 x J doubles per image leave the GPU instead of the maps.
+// ------------------------------------------------------------------------------------------------
+// `items` (launch_pose_decode_items): image n's own scale, offset and valid cells [0, rows) x [0, cols); the region is walked in
+// row-major order, so the first maximum is the restricted map's first maximum.
+template <typename T>
+__global__ __launch_bounds__(256) void pose_decode_kernel(const T* __restrict__ prob, int pcp, int pc0,
+                                                          const T* __restrict__ loc, int lcp, int lc0, int H, int W,
+                                                          int J, double scale, const PoseDecodeItem* __restrict__ items,
+                                                          double* __restrict__ out) {
+  __shared__ float sv[256];
+  __shared__ int si[256];
+  const int j = blockIdx.x, n = blockIdx.y, HW = H * W;
+  int rows = H, cols = W;
+  if (items) {
+    const PoseDecodeItem& it = items[n];
+    rows = min(it.rows, H), cols = min(it.cols, W), scale = it.scale;
+  }
+  const int cnt = rows * cols;
+  float best = -3.402823466e+38f;
+  int bi = 0x7fffffff;
+  for (int q = threadIdx.x; q < cnt; q += 256) {
+    const int p = cols == W ? q : (q / cols) * W + (q % cols);
+    const float v = (float)prob[((long)n * HW + p) * pcp + pc0 + j];
+    if (v > best) best = v, bi = p;  // strided scan keeps the smallest index per thread
+  }
+  sv[threadIdx.x] = best;
+  si[threadIdx.x] = bi;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) {
+      const float v2 = sv[threadIdx.x + s];
+      const int i2 = si[threadIdx.x + s];
+      if (v2 > sv[threadIdx.x] || (v2 == sv[threadIdx.x] && i2 < si[threadIdx.x])) {
+        sv[threadIdx.x] = v2;
+        si[threadIdx.x] = i2;
+      }
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const int p = si[0] == 0x7fffffff ? 0 : si[0];
+    const int row = p / W, col = p - row * W;
+    const double kLoc = 7.280109889280518;  // sqrt(53)  (_LOCREF_SCALE_MUL, estimate_pose.py:27)
+    const double ox = (double)(float)loc[((long)n * HW + p) * lcp + lc0 + 2 * j];
+    const double oy = (double)(float)loc[((long)n * HW + p) * lcp + lc0 + 2 * j + 1];
+    double* o = out + (long)n * 5 * J;
+    o[0 * J + j] = ((double)col * 8.0 + 4.0 + ox * kLoc) / scale;
+    o[1 * J + j] = ((double)row * 8.0 + 4.0 + oy * kLoc) / scale;
+    if (items) o[0 * J + j] += items[n].dx, o[1 * J + j] += items[n].dy;
+    o[2 * J + j] = (double)(float)prob[((long)n * HW + p) * pcp + pc0 + j];
+    o[3 * J + j] = oy * kLoc / scale;
+    o[4 * J + j] = ox * kLoc / scale;
+  }
+}
+
+int launch_pose_decode(const void* prob, int pcp, int pc0, const void* loc, int lcp, int lc0, int ekind, int NB, int H,
+                       int W, int J, double scale, double* out, void* stream) {
+  if (NB <= 0 || J <= 0) return 0;
+  return dc_by_kind(ekind, [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    hipLaunchKernelGGL(pose_decode_kernel<T>, dim3(J, NB), dim3(256), 0, (hipStream_t)stream, (const T*)prob, pcp, pc0, (const T*)loc, lcp,
+                       lc0, H, W, J, scale, (const PoseDecodeItem*)nullptr, out);
+    return (int)hipGetLastError();
+  });
+}
+
+int launch_pose_decode_items(const void* prob, int pcp, int pc0, const void* loc, int lcp, int lc0, int ekind, int NB, int H,
+                             int W, int J, const PoseDecodeItem* items, double* out, void* stream) {
+  if (NB <= 0 || J <= 0) return 0;
+  if (!items) return (int)hipErrorInvalidValue;
+  return dc_by_kind(ekind, [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    hipLaunchKernelGGL(pose_decode_kernel<T>, dim3(J, NB), dim3(256), 0, (hipStream_t)stream, (const T*)prob, pcp, pc0, (const T*)loc, lcp,
+                       lc0, H, W, J, 1.0, items, out);
+    return (int)hipGetLastError();
+  });
+}
+
+// ---- multi-person consumers: part candidates (NMS) and pairwise regression decode ------------------------------------
+// One workgroup per (image, joint) score map.  Every cell is tested for being the maximum of its (2r+1)^2 window (ties: the
+// lower cell index wins) and, if so, becomes the 64-bit key (score bits << 32 | ~cell): keys are unique, and descending key
+// order IS the output order (score descending, cell ascending).  The candidate SET does not depend on thread timing, and
+// the list is then ordered by the whole workgroup: up to kPartLds keys by a bitonic sort in LDS; a map with more local
+// maxima than that (threshold 0, radius 0) spills its keys to global memory and takes the first max_det by repeated
+// workgroup-wide maximum.  Nothing is dropped in arrival order, so the result is deterministic for every input.
+constexpr int kPartLds = 4096;  // keys sorted in LDS (32 KB)
+
+template <typename T>
+__global__ __launch_bounds__(256) void part_select_kernel(const T* __restrict__ prob, int pcp, int pc0, const T* __restrict__ loc, int lcp,
+                                                          int lc0, int H, int W, int J, float thr, int radius, double scale, int max_det,
+                                                          unsigned long long* __restrict__ spill, int* __restrict__ counts,
+                                                          double* __restrict__ out) {
+  __shared__ unsigned long long keys[kPartLds];
+  __shared__ unsigned long long red[256];
+  __shared__ int cnt;
+  const int nj = blockIdx.x, n = nj / J, j = nj - n * J, t = threadIdx.x, HW = H * W;
+  const T* base = prob + ((long)n * HW) * pcp + pc0 + j;
+  unsigned long long* mine = spill + (long)nj * HW;
+  if (t == 0) cnt = 0;
+  __syncthreads();
+  for (int cell = t; cell < HW; cell += 256) {
+    const int row = cell / W, col = cell - row * W;
+    const float v = (float)base[(long)cell * pcp];
+    bool ok = v >= thr;
+    for (int dy = -radius; ok && dy <= radius; ++dy) {
+      const int y = row + dy;
+      if (y < 0 || y >= H) continue;
+      for (int dx = -radius; dx <= radius; ++dx) {
+        const int x = col + dx;
+        if (x < 0 || x >= W || (dy == 0 && dx == 0)) continue;
+        const float u = (float)base[((long)y * W + x) * pcp];
+        if (u > v || (u == v && y * W + x < cell)) {
+          ok = false;
+          break;
+        }
+      }
+    }
+    if (ok) {
+      // the raw bit pattern orders NON-NEGATIVE floats only (a set sign bit would sort above every positive score, in reverse):
+      // v >= thr >= 0 here — Net::detect_parts refuses a negative threshold — and key 0 (the padding) is below every candidate
+      const unsigned long long key = ((unsigned long long)__float_as_uint(v) << 32) | (unsigned)(0xffffffffu - (unsigned)cell);
+      const int slot = atomicAdd(&cnt, 1);  // LDS counter: the slot order varies, the set and (after sorting) the result do not
+      if (slot < kPartLds) keys[slot] = key;
+      mine[slot] = key;
+    }
+  }
+  __syncthreads();
+  const int m = cnt;
+  const int take = min(m, max_det);
+  if (t == 0) counts[nj] = take;
+  double* o = out + (long)nj * max_det * 5;
+  auto emit = [&](int k, unsigned long long key) {
+    const double kLoc = 7.280109889280518;  // sqrt(53)
+    const int cell = (int)(0xffffffffu - (unsigned)key);
+    const int row = cell / W, col = cell - row * W;
+    const T* l = loc + (((long)n * H + row) * W + col) * lcp + lc0 + 2 * j;
+    double* q = o + (long)k * 5;
+    q[0] = ((double)col * 8.0 + 4.0 + (double)(float)l[0] * kLoc) / scale;
+    q[1] = ((double)row * 8.0 + 4.0 + (double)(float)l[1] * kLoc) / scale;
+    q[2] = (double)__uint_as_float((unsigned)(key >> 32));
+    q[3] = (double)row;
+    q[4] = (double)col;
+  };
+  for (int k = take + t; k < max_det; k += 256) {
+    double* q = o + (long)k * 5;
+    q[0] = q[1] = q[2] = 0.0;
+    q[3] = q[4] = -1.0;
+  }
+  if (m <= kPartLds) {
+    int P = 1;
+    while (P < m) P <<= 1;
+    for (int i = m + t; i < P; i += 256) keys[i] = 0ull;  // below every real key (scores >= 0, cell term > 0)
+    __syncthreads();
+    for (int k2 = 2; k2 <= P; k2 <<= 1)
+      for (int j2 = k2 >> 1; j2 > 0; j2 >>= 1) {
+        for (int i = t; i < P; i += 256) {
+          const int ixj = i ^ j2;
+          if (ixj > i) {
+            const unsigned long long a = keys[i], b = keys[ixj];
+            const bool desc = (i & k2) == 0;  // descending overall
+            if (desc ? a < b : a > b) keys[i] = b, keys[ixj] = a;
+          }
+        }
+        __syncthreads();
+      }
+    for (int k = t; k < take; k += 256) emit(k, keys[k]);
+  } else {
+    __threadfence_block();
+    unsigned long long prev = ~0ull;
+    for (int k = 0; k < take; ++k) {  // k-th largest key = the largest key below the previous one
+      unsigned long long best = 0ull;
+      for (int i = t; i < m; i += 256) {
+        const unsigned long long v = mine[i];
+        if (v < prev && v > best) best = v;
+      }
+      red[t] = best;
+      __syncthreads();
+      for (int s2 = 128; s2 > 0; s2 >>= 1) {
+        if (t < s2 && red[t + s2] > red[t]) red[t] = red[t + s2];
+        __syncthreads();
+      }
+      prev = red[0];
+      if (t == 0) emit(k, prev);
+      __syncthreads();
+    }
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void pairwise_decode_kernel(const T* __restrict__ next, int ncp, int nc0, int NB, int H, int W, int E,
+                                                              double scale, int ndet, const int* __restrict__ det,
+                                                              const double* __restrict__ mean, const double* __restrict__ stdev,
+                                                              double* __restrict__ out) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)ndet * E) return;
+  const int d = (int)(i / E), l = (int)(i - (long)d * E);
+  const int n = det[3 * d], row = det[3 * d + 1], col = det[3 * d + 2];
+  double* o = out + i * 2;
+  if (n < 0 || n >= NB || row < 0 || row >= H || col < 0 || col >= W) {
+    o[0] = o[1] = 0.0;
+    return;
+  }
+  const T* p = next + (((long)n * H + row) * W + col) * ncp + nc0 + 2 * l;
+  const double m0 = mean ? mean[2 * l] : 0.0, m1 = mean ? mean[2 * l + 1] : 0.0;
+  const double s0 = stdev ? stdev[2 * l] : 1.0, s1 = stdev ? stdev[2 * l + 1] : 1.0;
+  o[0] = ((double)col * 8.0 + 4.0 + (double)(float)p[0] * s0 + m0) / scale;
+  o[1] = ((double)row * 8.0 + 4.0 + (double)(float)p[1] * s1 + m1) / scale;
+}
+
+int launch_part_select(const void* prob, int pcp, int pc0, const void* loc, int lcp, int lc0, int ekind, int NB, int H, int W, int J, float thr,
+                       int radius, double scale, int max_det, unsigned long long* spill, int* counts, double* out, void* stream) {
+  if (NB * J <= 0) return 0;
+  return dc_by_kind(ekind, [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    hipLaunchKernelGGL(part_select_kernel<T>, dim3(NB * J), dim3(256), 0, (hipStream_t)stream, (const T*)prob, pcp, pc0, (const T*)loc, lcp,
+                       lc0, H, W, J, thr, radius, scale, max_det, spill, counts, out);
+    return (int)hipGetLastError();
+  });
+}
+
+int launch_pairwise_decode(const void* next, int ncp, int nc0, int ekind, int NB, int H, int W, int E, double scale, int ndet,
+                           const int* det, const double* mean, const double* stdev, double* out, void* stream) {
+  const long total = (long)ndet * E;
+  if (total <= 0) return 0;
+  const dim3 grid((unsigned)((total + 255) / 256));
+  return dc_by_kind(ekind, [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    hipLaunchKernelGGL(pairwise_decode_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, (const T*)next, ncp, nc0, NB, H, W, E, scale, ndet,
+                       det, mean, stdev, out);
+    return (int)hipGetLastError();
+  });
+}
+
+}  // namespace dc

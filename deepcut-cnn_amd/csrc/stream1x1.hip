@@ -330,7 +330,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void ws1x1_kernel(const W
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           float x0 = i < 2 ? lo[2 * i] : hi[2 * i - 4], x1 = i < 2 ? lo[2 * i + 1] : hi[2 * i - 3];
-          if constexpr (BF) {  // (the bfloat16 gather-GEMM's epilogue, kernels.hip: same operations, same order)
+          if constexpr (BF) {  // (the bfloat16 gather-GEMM's epilogue, conv_gemm.h: same operations, same order)
             if (RES) {
               x0 += __builtin_bit_cast(float, rv[i] << 16);
               x1 += __builtin_bit_cast(float, rv[i] & 0xffff0000u);

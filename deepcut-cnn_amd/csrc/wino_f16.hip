@@ -1,7 +1,7 @@
 // wino_f16.hip — Winograd F(2x2, 3x3) for the stride-1 3x3 convolutions of a float16 net (gfx950), tile name `wino_h23`.
 //
 // The reference runs these layers as im2col + SGEMM (src/caffe/layers/conv_layer.cpp:25-40, base_conv_layer.cpp:257-280);
-// the product's direct form is the gather-GEMM of kernels.hip.  This kernel computes the same sums as
+// the product's direct form is the gather-GEMM of conv_gemm.h.  This kernel computes the same sums as
 // Y = A^T [ (G g G^T) . (B^T d B) ] A per 4x4 input patch d -> 2x2 outputs: 16 independent GEMMs over the input channels
 // (one per transform position (i, j)), 2.25x fewer MFMA flops than the direct form.  float16 operands, float32 accumulation
 // (v_mfma_f32_32x32x16_f16), float32 epilogue — the arithmetic contract of DC_OPT_DTYPE 1.
@@ -84,7 +84,7 @@ __device__ __forceinline__ unsigned h_as_u(f16x2 v) { return __builtin_bit_cast(
 
 __global__ __launch_bounds__(HNTH, 1) void wino_h23_kernel(const ConvGemmParams p) {
   const long long t_entry = (long long)__builtin_amdgcn_s_memrealtime();
-  // the five 64-byte lines of the argument block this kernel reads are requested together at entry (as DC_KARG_TOUCH of kernels.hip:
+  // the five 64-byte lines of the argument block this kernel reads are requested together at entry (as DC_KARG_TOUCH of conv_gemm.h:
   // fetched lazily, field by field, each first touch of a line is a scalar-cache miss on the critical path)
   unsigned ka0, ka1, ka2, ka3, ka4;
   {

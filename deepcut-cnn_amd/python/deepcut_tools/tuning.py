@@ -13,7 +13,7 @@ is set (dc_net_set_tile rewrites it); the reference has nothing to mirror here (
 """
 
 
-# the two forms of the Winograd kernel (8 / 16 waves per workgroup, csrc/kernels.hip): wherever one is in use the other is eligible, and
+# the two forms of the Winograd kernel (8 / 16 waves per workgroup, csrc/wino_f32.hip): wherever one is in use the other is eligible, and
 # which one is faster is exactly a question of load (16 waves win a launch of at most one workgroup per CU running alone, 8 waves win as
 # soon as workgroups share CUs) — so the sibling is tried even for a signature whose choice came from a cache file, without timings
 _WINO_SIBLING = {"wino_f23": "wino_f23_w16", "wino_f23_w16": "wino_f23", "wino_f23_5x6": "wino_f23_5x6_w16", "wino_f23_5x6_w16": "wino_f23_5x6"}

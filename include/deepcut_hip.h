@@ -382,7 +382,7 @@ const char* dc_net_debug_info(dc_net* net);
  * SGEMM per layer (math_functions.cu:13-27).                                                                            */
 const char* dc_net_tune_report(dc_net* net);
 int dc_net_set_tile(dc_net* net, const char* signature, const char* tile);
-/* the gather-GEMM's tile-variant table (csrc/kernels.hip): number of entries, name and element size (4 float / 2 half) of
+/* the gather-GEMM's tile-variant table (csrc/conv_gemm.cpp): number of entries, name and element size (4 float / 2 half) of
  * entry i — what the environment switch DC_CONV_VARIANT=<i> forces and the names dc_net_plan_text / DC_TUNE_CACHE use.
  * No reference counterpart: the reference has one SGEMM (math_functions.cu:13-27); diagnostics only.                  */
 int dc_conv_variant_count(void);

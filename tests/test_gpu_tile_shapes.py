@@ -122,7 +122,7 @@ XCD_EXCUSED = {}
 
 
 def _xcd_arrangement(M, N, Ktot, nty, klen, BM, BN):
-    """The XCD arrangement launch_conv_gemm (kernels.hip) gives a single-problem launch, restated: None when the map stays off (fewer
+    """The XCD arrangement launch_conv_gemm (conv_gemm.cpp) gives a single-problem launch, restated: None when the map stays off (fewer
     than 16 tiles), else (gx, gy, tiles_m, tiles_n, rectangle widths).  plan_text() does not show the arrangement, so this model of the
     host's choice is what the premise of the XCD nets is asserted on; it has to follow the host code if that changes."""
     tm, tn = -(-M // BM), -(-N // BN)

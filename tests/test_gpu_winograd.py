@@ -1,4 +1,4 @@
-"""-m gpu: the Winograd F(2x2,3x3) form of the stride-1 3x3 convolutions (kernels.hip wino_f23_kernel), forced with
+"""-m gpu: the Winograd F(2x2,3x3) form of the stride-1 3x3 convolutions (wino_f32.hip wino_f23_kernel), forced with
 DC_WINOGRAD=1 (8 waves per workgroup) and DC_WINOGRAD=2 (the 16-wave form, tile name wino_f23_w16); by default either is used
 only where the per-shape timing finds it faster.  Against the CPU oracle.
 Winograd changes the rounding (transforms in fp32), not the mathematics: the bound stays the path's 1e-3, measured ~1e-5."""

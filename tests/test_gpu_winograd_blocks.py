@@ -1,4 +1,4 @@
-"""-m gpu: the 5 x 6-tile block forms of the float32 Winograd kernel (kernels.hip, WinoGeom<5, 3, side by side>; tiles wino_f23_5x6 and
+"""-m gpu: the 5 x 6-tile block forms of the float32 Winograd kernel (wino_f32.hip, WinoGeom<5, 3, side by side>; tiles wino_f23_5x6 and
 wino_f23_5x6_w16), put in place with set_tile on single 3x3 layers and on the res5 layers of the full net.  Against the CPU oracle at the
 suite's bound (<= 1e-3 max-abs), and bit for bit against the 4 x 8 form of the same wave count: a tile's arithmetic (channel order, order
 of the partial sums in the epilogue) does not depend on the block slot it sits in."""

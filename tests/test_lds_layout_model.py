@@ -1,4 +1,4 @@
-"""CPU: the Winograd kernel's LDS layout constants (kernels.hip: WPSTR, WPITCH) against the LDS bank model of MI355X_MICROARCH.md
+"""CPU: the Winograd kernel's LDS layout constants (wino_f32.hip: WPSTR, WPITCH) against the LDS bank model of MI355X_MICROARCH.md
 (tools/lds_bank_model.py): the patch-row reads must stay at 4 LDS cycles per ds_read_b128.  Round 1's layout paid 8 (two-way
 conflicts in every lane group) for four rounds; the PMC side of the same fact is tools/pmc_lds_conflicts.py."""
 import os
@@ -11,7 +11,7 @@ import lds_bank_model as M  # noqa: E402
 
 
 def _constants():
-    src = open(os.path.join(ROOT, "deepcut-cnn_amd", "csrc", "kernels.hip")).read()
+    src = open(os.path.join(ROOT, "deepcut-cnn_amd", "csrc", "wino_f32.hip")).read()
     wkc = int(re.search(r"constexpr int WBTY = \d+, WBTX = \d+, WBN = \d+, WKC = (\d+);", src).group(1))
     pad = int(re.search(r"constexpr int WPSTR = WKC \+ (\d+);", src).group(1))
     pitch = int(re.search(r"constexpr int WPITCH = (\d+);", src).group(1))
@@ -33,7 +33,7 @@ def test_the_model_sees_the_round_1_layout_as_two_way_conflicts():
 
 
 def test_the_lds_dma_swizzles_are_conflict_free_in_the_model_too():
-    """kernels.hip, LDS-DMA stages: 16-byte chunk c of row r sits at position c ^ swz(r), swz(r) = (r >> 1) & 7 for 128-byte rows and
+    """conv_gemm.h, LDS-DMA stages: 16-byte chunk c of row r sits at position c ^ swz(r), swz(r) = (r >> 1) & 7 for 128-byte rows and
     r & 15 for 256-byte rows; the fragment reader (lane -> row lane & 31, chunk 2 q + (lane >> 5)) XORs the same term back.  The PMC
     counters read 0.0 % conflicts for every such tile (profiles/r05_pmc_lds_conflicts*.txt): model and counters agree."""
     for q in range(4):

@@ -1,4 +1,4 @@
-"""CPU: the block geometries of the float32 Winograd kernel (kernels.hip, WinoGeom): how many tile blocks a form needs for a tile grid
+"""CPU: the block geometries of the float32 Winograd kernel (wino_f32.hip, WinoGeom): how many tile blocks a form needs for a tile grid
 (dc_wino_blocks: what decides where the 5 x 6 forms enter the per-shape timing), and the LDS layout of the 5 x 6 block's 12 x 14 staged
 pixels against the bank model of tools/lds_bank_model.py: every patch-row read (ds_read_b128) of both fragments stays at 4 LDS cycles,
 and three stages stay within half of a CU's LDS (two workgroups per CU)."""
@@ -14,8 +14,8 @@ import lds_bank_model as M  # noqa: E402
 
 
 def _geometries():
-    """{name: (fragment rows, fragment columns, side by side, row pitch)} as kernels.hip instantiates them."""
-    src = open(os.path.join(ROOT, "deepcut-cnn_amd", "csrc", "kernels.hip")).read()
+    """{name: (fragment rows, fragment columns, side by side, row pitch)} as wino_f32.hip instantiates them."""
+    src = open(os.path.join(ROOT, "deepcut-cnn_amd", "csrc", "wino_f32.hip")).read()
     found = re.findall(r"using (WinoG\d+) = WinoGeom<(\d+), (\d+), (true|false), (\d+)>;", src)
     g = {n: (int(fr), int(fc), side == "true", int(p)) for n, fr, fc, side, p in found}
     # the default block is spelled with the constants tests/test_lds_layout_model.py reads

@@ -46,7 +46,7 @@ def ds_write_b128_cycles(addr):
 
 
 def wino_stage_store(rows, cols, row_pitch, wave, q, nth=512, pixel_pitch=36):
-    """Float index per lane of staging store q of wave `wave` (kernels.hip, sofs): element e = thread + q * nth -> pixel e / 8 (row-major over
+    """Float index per lane of staging store q of wave `wave` (wino_f32.hip, sofs): element e = thread + q * nth -> pixel e / 8 (row-major over
     the rows x cols staged pixels), channel quad e % 8; past the block: the dump slot."""
     out = []
     for lane in range(64):
@@ -57,7 +57,7 @@ def wino_stage_store(rows, cols, row_pitch, wave, q, nth=512, pixel_pitch=36):
 
 
 def wino_patch_row_read(pixel_pitch, row_pitch, row0, skew=lambda row: 0):
-    """Float index per lane of the Winograd kernel's patch-row read (kernels.hip, lread): first tile row of the fragment at staged
+    """Float index per lane of the Winograd kernel's patch-row read (wino_f32.hip, lread): first tile row of the fragment at staged
     row `row0`, the second one two rows below."""
     out = []
     for lane in range(64):
@@ -73,7 +73,7 @@ def wino_layout_cycles(pixel_pitch, row_pitch, skew=lambda row: 0):
 
 
 def wino_geom_read(fr, fc, side, row_pitch, tf, row0, pixel_pitch=36):
-    """Float index per lane of a patch-row read under a block geometry of kernels.hip (WinoGeom): a fragment of fr x fc tiles, lane
+    """Float index per lane of a patch-row read under a block geometry of wino_f32.hip (WinoGeom): a fragment of fr x fc tiles, lane
     q = lane & 15 -> tile (q / fc, q % fc), the two fragments of a block stacked (tile rows fr * tf + ..) or side by side (tile columns
     fc * tf + ..); a fragment row without a tile reads the last tile's address.  row0: the patch row (0..3) inside the tile."""
     out = []

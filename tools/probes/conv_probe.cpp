@@ -1,7 +1,7 @@
-// conv_probe — stand-alone A/B harness for the gather-GEMM tile variants of kernels.hip (no Python, no torch:
+// conv_probe — stand-alone A/B harness for the gather-GEMM tile variants of conv_gemm.h (no Python, no torch:
 // starts in milliseconds, so one GPU call can time every variant on every layer shape).
 //
-//   hipcc --offload-arch=gfx950 -O2 -std=c++17 tools/probes/conv_probe.cpp deepcut-cnn_amd/lib/kernels.hip.o -o tools/probes/bin/conv_probe
+//   hipcc --offload-arch=gfx950 -O2 -std=c++17 tools/probes/conv_probe.cpp deepcut-cnn_amd/lib/{conv_gemm.cpp,conv_gemm_f32.hip,conv_gemm_f16.hip,conv_gemm_bf16.hip,wino_f32.hip,forms.cpp,layers.hip,pose.hip,image_prep.hip}.o -o tools/probes/bin/conv_probe
 //   tools/probes/bin/conv_probe [--dtype h|f] [--batch 8] [--shapes res4_3x3,res4_c,...] [--variants all|d|name,name] [--reps 30]
 //
 // For every shape: each eligible variant is (a) checked against a float64 CPU evaluation of 4096 sampled outputs, (b) compared

@@ -51,7 +51,7 @@ __device__ __forceinline__ pi32x4 pair_rsrc_words(const void* p, unsigned bytes)
   return pi32x4{(int)(unsigned)a, (int)((a >> 32) & 0xffffu), (int)bytes, 0x00020000};
 }
 // LDS-DMA: 64 lanes x 16 bytes from global memory straight into LDS at M0 + 16*lane.  Inline asm: through the builtin the
-// compiler would make every later ds_read wait for vmcnt(0); the kernel counts vmcnt itself (kernels.hip, dc_dma16).
+// compiler would make every later ds_read wait for vmcnt(0); the kernel counts vmcnt itself (kernel_prims.h, dc_dma16).
 __device__ __forceinline__ void pair_dma16(pi32x4 rs, unsigned lds, unsigned voff, unsigned soff) {
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lds), "v"(voff), "s"(rs), "s"(soff)
                : "memory", "m0");
