@@ -714,6 +714,32 @@ int dc_group_forward_boxes(dc_group* group, const unsigned char* image, int heig
                             next_pred, pose, stream);
   });
 }
+// multi-scale fusion: a null `scales` is the library's to refuse (DC_EINVAL naming it), like every other argument of the rule
+int dc_group_fuse_maps(dc_group* group, const double* scales, int base, int n_edges, const double* mean, const double* stdev, float* prob,
+                       float* loc_pred, float* next_pred, int is_device, void* stream) {
+  REQUIRE(group);
+  return guard([&] { G(group)->fuse_maps(scales, base, n_edges, mean, stdev, prob, loc_pred, next_pred, is_device != 0, stream); });
+}
+int dc_group_detect_parts(dc_group* group, const double* scales, int base, float threshold, int radius, int max_det, int* counts,
+                          double* dets) {
+  REQUIRE(group);
+  REQUIRE(counts);
+  REQUIRE(dets);
+  return guard([&] { G(group)->detect_parts(scales, base, threshold, radius, max_det, counts, dets); });
+}
+int dc_group_assemble_people(dc_group* group, const double* scales, int base, const dc_assemble_params* p, int n_edges, const int* edges,
+                             const double* mean, const double* stdev, const int* joint_order, int* n_people, double* people, int* cand,
+                             double* cost) {
+  REQUIRE(group);
+  REQUIRE(p);
+  REQUIRE(n_people);
+  REQUIRE(people);
+  if (n_edges > 0) REQUIRE(edges);
+  return guard([&] {
+    Net::AssembleParams q{p->scale, p->threshold, p->radius, p->max_det, p->max_cost, p->seed_threshold, p->max_people, p->min_joints};
+    G(group)->assemble_people(scales, base, q, n_edges, edges, mean, stdev, joint_order, n_people, people, cand, cost);
+  });
+}
 int dc_comm_create(int nexec, const int* devices, int transport, dc_comm** out) {
   REQUIRE(out);
   *out = nullptr;

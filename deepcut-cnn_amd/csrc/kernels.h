@@ -354,6 +354,22 @@ int launch_assemble(int NB, int J, int max_det, int max_people, int min_joints, 
                     const double* dets, const double* cost, const int* order, double* link, int* n_people, double* people, int* cand,
                     void* stream);
 
+// Multi-scale fusion of the maps of a pyramid (pose.hip; the rule is this project's own, like the assembly above: include/deepcut_hip.h,
+// dc_group_fuse_maps).  Member m holds the maps of the same NB images at its own scale; map k (0 prob, 1 loc_pred, 2 next_pred) is the
+// NHWC image ptr[k] of H x W cells with channel pitch cp[k], first channel c0[k]; q = scale of m / scale of the base member.
+struct FuseMember {
+  const void* ptr[3];
+  int cp[3], c0[3];
+  int H, W;
+  double q;
+};
+// One launch for every member, map and image: out[((b*Hb + r)*Wb + c)*Ctot + ch] (float32, NHWC, pitch Ctot = C[0] + C[1] + C[2]) =
+// (sum over m ascending of bilinear sample of member m at the cell's point * gain[m*Ctot + ch] + bias[m*Ctot + ch]) * (1 / M).
+// Channels [0, C[0]) are map 0, the next C[1] map 1, the last C[2] map 2; a map with C[k] = 0 takes no part (its ptr is not read).
+// members / gain / bias are device tables ([M], [M][Ctot], [M][Ctot]); ekind is the members' common element type.
+int launch_fuse_maps(const FuseMember* members, const float* gain, const float* bias, int M, int ekind, int NB, int Hb, int Wb, const int C[3],
+                     float* out, void* stream);
+
 // Image pre-processing of the demo (python/pose/estimate_pose.py:83-103) on the device: replicate padding by
 // coordinate clamping, Pillow's two-pass 8-bit bilinear resample (22-bit fixed-point weights from the host),
 // mean subtraction and the zero canvas, written straight into the network's NHWC input image.

@@ -381,6 +381,15 @@ struct Net {
     int cp, c0, es, ek, NB, C, H, W;
   };
   MapRef map_ref(const char* blob_name);  // device image of an output map (channel views of the merged heads included)
+  // assemble_people in three parts, shared with NetGroup::assemble_people (people.cpp): the checks of the parameters, the checks of the
+  // edges / statistics / joint order against J joints (-> the lookup table lut[a*J + c] followed by the joint order), both host only,
+  // and the device half: the three launches on maps given by reference, scratch memory from `scratch(bytes)`, everything on `stream`
+  static void check_assemble_params(const AssembleParams& q);
+  static std::vector<int> check_assemble_graph(const AssembleParams& q, int J, int n_edges, const int* edges, const double* mean,
+                                               const double* stdev, const int* joint_order);
+  static void assemble_maps(const MapRef& P, const MapRef& L, const MapRef& N, const AssembleParams& q, const std::vector<int>& table,
+                            int n_edges, const double* mean, const double* stdev, const std::function<void*(size_t)>& scratch, void* stream,
+                            int* n_people, double* people, int* cand, double* cost);
   unsigned char* scratch_dev_ = nullptr;  // candidates / detections / pairwise scratch
   size_t scratch_cap_ = 0;
   void* scratch(size_t bytes);
@@ -392,6 +401,16 @@ struct Net {
   size_t box_cap_ = 0;
   std::vector<unsigned char> box_host_;  // the host side of that table (outlives its upload)
   int box_n_ = 0;                     // boxes of the last prep_boxes
+};
+
+struct DevBuf {  // a grow-only device buffer
+  unsigned char* dev = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf();
+  void* get(size_t bytes);  // at least `bytes`; the contents do not survive a growth
 };
 
 // ---- pyramid-grouped execution (round 4) ---------------------------------------------------------------------------------
@@ -455,6 +474,21 @@ struct NetGroup {
   void forward_boxes(const unsigned char* bgr, int h, int w, bool is_device, const int* boxes, const double* scales, int n,
                      const double* pyramid, int canvas_h, int canvas_w, float* const* prob, float* const* loc, float* const* next,
                      double* const* pose, void* user_stream);
+  // Multi-scale fusion (dc_group_fuse_maps; the rule: include/deepcut_hip.h): the maps of the members' LAST forwards — member c holds the
+  // same images at scales[c] — resampled onto member `base`'s grid, brought into its units and averaged, in ONE launch (launch_fuse_maps)
+  // into a float32 buffer the group owns.  Everything runs on the group's stream (the first member's own; fuse_maps: or the caller's), so
+  // a grouped forward issued there before is complete; a caller who forwarded the members individually synchronises them first.
+  // The fused buffer, the table and the scratch are the group's only copies: every call first makes its stream wait for the previous
+  // call's work (an event, no host wait), so a call may follow an asynchronous fuse_maps on another stream.  What an asynchronous
+  // fuse_maps wrote to the caller's device buffers is the caller's to wait for, as with forward_images.
+  // fuse_maps: the fused maps as NCHW float32 (any of them null: not fused), host or device, stream as forward_images
+  void fuse_maps(const double* scales, int base, int n_edges, const double* mean, const double* stdev, float* prob, float* loc, float* next,
+                 bool is_device, void* user_stream);
+  // Net::detect_parts on the fused prob / loc_pred at scales[base]
+  void detect_parts(const double* scales, int base, float thr, int radius, int max_det, int* counts, double* dets);
+  // fusion of all three maps, then Net::assemble_people's three launches on them at scales[base] (p.scale is not read)
+  void assemble_people(const double* scales, int base, const Net::AssembleParams& p, int n_edges, const int* edges, const double* mean,
+                       const double* stdev, const int* joint_order, int* n_people, double* people, int* cand, double* cost);
   // lanes: 0 = automatic (2 members: two lanes; 3: one; 4 and more: two), else that many (at most one per member); every merged plan is dropped
   void set_lanes(int n);
   int lanes() const { return cur_ ? cur_->nlanes : lanes_opt_; }
@@ -489,6 +523,20 @@ struct NetGroup {
   void choose_lane_streams(GroupPlan& gp, void* s, bool use_graph);
   void drop_plan(GroupPlan& gp);
   void* stream();
+  // fusion: the host checks (-> channels per map, 0 where use[k] is false, and the batch size), and the launch (-> the fused maps as
+  // channel views of fused_)
+  struct FusedMaps {
+    Net::MapRef map[3];
+  };
+  void check_scales(const char* who, const double* scales, int base) const;  // the scales and the base index alone
+  void check_fuse(const char* who, const double* scales, int base, const bool use[3], int n_edges, const double* mean, const double* stdev,
+                  int C[3], int& NB) const;
+  FusedMaps fuse(const double* scales, int base, const bool use[3], const double* mean, const double* stdev, void* s);
+  DevBuf fused_, fuse_table_, fuse_stage_, people_scratch_;
+  void* fuse_event_ = nullptr;    // recorded behind the last fusion call's work ...
+  void* fuse_stream_ = nullptr;   // ... on this stream
+  void fuse_done(void* s);        // record it
+  std::vector<unsigned char> fuse_table_host_;  // what fuse_table_ holds: the members' descriptors, then gain and bias [M][channels]
 };
 
 // ---- runtime.cpp: pinned host memory (dc_host_alloc / dc_host_free) ---------------------------------------------------------

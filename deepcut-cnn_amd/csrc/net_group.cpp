@@ -53,6 +53,7 @@ NetGroup::~NetGroup() {
   for (auto& gp : plans_) drop_plan(*gp);
   for (void* e : lane_events_) (void)hipEventDestroy((hipEvent_t)e);
   if (fork_event_) (void)hipEventDestroy((hipEvent_t)fork_event_);
+  if (fuse_event_) (void)hipEventDestroy((hipEvent_t)fuse_event_);
   for (auto& kv : lane_choice_) lane_streams_release(kv.second);  // (the streams themselves belong to the process-wide list)
 }
 
@@ -768,6 +769,222 @@ void NetGroup::forward_boxes(const unsigned char* bgr, int h, int w, bool is_dev
     if (pose && pose[c]) nets[c]->decode_boxes(pose[c], is_device, s);
   }
   if (!(is_device && (user_stream || own_async))) HIPCHECK(hipStreamSynchronize((hipStream_t)s));
+}
+
+// ---- multi-scale fusion of the members' maps (the rule: include/deepcut_hip.h, dc_group_fuse_maps; the kernel: pose.hip) -------------
+// PARITY UNPINNED BY THE REFERENCE: eldar/deepcut-cnn stops at the maps and has no multi-scale combination of them; only the
+// label encoding of its training layer (src/caffe/layers/pose_data_layer.cpp:686-802) is restated, in the gain / bias table below.
+DevBuf::~DevBuf() { dev_free(dev); }
+void* DevBuf::get(size_t bytes) {
+  if (bytes > cap) {
+    dev_free(dev);
+    dev = nullptr, cap = 0;
+    dev_alloc((void**)&dev, bytes);
+    cap = bytes;
+  }
+  return dev;
+}
+
+static const char* const kFuseMaps[3] = {"prob", "loc_pred", "next_pred"};
+
+// Host only: what is wrong with the arguments is said before any device work (and with or without a device).
+void NetGroup::check_scales(const char* who, const double* scales, int base) const {
+  const std::string w = std::string(who) + ": ";
+  const int M = (int)nets.size();
+  if (!scales) throw DcError(DC_EINVAL, w + "null scales (one per group member)");
+  for (int m = 0; m < M; ++m)
+    if (!(scales[m] > 0) || !std::isfinite(scales[m]))
+      throw DcError(DC_EINVAL, w + "scale of member " + std::to_string(m) + " is not positive and finite");
+  if (base < 0 || base >= M) throw DcError(DC_EINVAL, w + "base " + std::to_string(base) + " is outside [0, " + std::to_string(M) + ")");
+}
+
+void NetGroup::check_fuse(const char* who, const double* scales, int base, const bool use[3], int n_edges, const double* mean,
+                          const double* stdev, int C[3], int& NB) const {
+  const std::string w = std::string(who) + ": ";
+  const int M = (int)nets.size();
+  check_scales(who, scales, base);
+  if (use[2])
+    for (int i = 0; i < 2 * std::max(n_edges, 0); ++i) {
+      if (mean && !std::isfinite(mean[i])) throw DcError(DC_EINVAL, w + "mean of edge " + std::to_string(i / 2) + " is not finite");
+      if (stdev && !(std::isfinite(stdev[i]) && stdev[i] > 0))
+        throw DcError(DC_EINVAL, w + "std of edge " + std::to_string(i / 2) + " is not positive and finite");
+    }
+  NB = 0;
+  for (int k = 0; k < 3; ++k) {
+    C[k] = 0;
+    if (!use[k]) continue;
+    for (int m = 0; m < M; ++m) {
+      auto it = nets[m]->blob_index.find(kFuseMaps[k]);
+      if (it == nets[m]->blob_index.end()) throw DcError(DC_EINVAL, w + "member " + std::to_string(m) + " has no '" + kFuseMaps[k] + "' blob");
+      const std::vector<int>& sh = nets[m]->blobs[it->second]->st->shape;
+      if (sh.size() != 4) throw DcError(DC_ESHAPE, w + "'" + kFuseMaps[k] + "' of member " + std::to_string(m) + " is not a 4-D map");
+      if (m == 0) C[k] = sh[1];
+      if (NB == 0) NB = sh[0];
+      if (sh[0] != NB || sh[1] != C[k])
+        throw DcError(DC_ESHAPE, w + "'" + kFuseMaps[k] + "' of member " + std::to_string(m) + " is " + std::to_string(sh[0]) + " images of " +
+                                     std::to_string(sh[1]) + " channels, the other members' maps are " + std::to_string(NB) + " images of " +
+                                     std::to_string(C[k]) + " channels (every member holds the same images)");
+    }
+  }
+  if (use[2] && (C[2] % 2 || n_edges != C[2] / 2))
+    throw DcError(DC_ESHAPE, w + std::to_string(n_edges) + " edges for a next_pred of " + std::to_string(C[2]) + " channels (2 per regression edge)");
+}
+
+// The launch.  The table on the device (the members' descriptors, then gain and bias [M][channels]) is uploaded when it differs from the
+// one already there — a new pyramid, a reallocated map —, so the usual call is the one kernel and nothing else.
+NetGroup::FusedMaps NetGroup::fuse(const double* scales, int base, const bool use[3], const double* mean, const double* stdev, void* s) {
+  const int M = (int)nets.size();
+  // the buffers below are shared by every call: work that the previous call left running on ANOTHER stream (an asynchronous
+  // fuse_maps on a caller's stream) finishes before this call's stream touches them
+  if (fuse_event_ && fuse_stream_ != s) HIPCHECK(hipStreamWaitEvent((hipStream_t)s, (hipEvent_t)fuse_event_, 0));
+  std::vector<FuseMember> mem((size_t)M);
+  int C[3] = {0, 0, 0}, NB = 0, ek = nets[0]->dtype;
+  for (int m = 0; m < M; ++m) {
+    FuseMember& f = mem[(size_t)m];
+    std::memset(&f, 0, sizeof f);
+    f.q = m == base ? 1.0 : scales[m] / scales[base];
+    bool first = true;
+    for (int k = 0; k < 3; ++k) {
+      if (!use[k]) continue;
+      const Net::MapRef r = nets[m]->map_ref(kFuseMaps[k]);
+      if (first) f.H = r.H, f.W = r.W;
+      if (m == 0) C[k] = r.C;
+      if (m == 0 && first) NB = r.NB, ek = r.ek;
+      if (r.H != f.H || r.W != f.W || r.NB != NB || r.C != C[k] || r.ek != ek)
+        throw DcError(DC_ESHAPE, std::string("fuse_maps: '") + kFuseMaps[k] + "' of member " + std::to_string(m) +
+                                     " does not have the size of the member's other maps, or the batch size, channels and element type of the other members'");
+      f.ptr[k] = r.ptr, f.cp[k] = r.cp, f.c0[k] = r.c0;
+      first = false;
+    }
+  }
+  const int Ctot = C[0] + C[1] + C[2], Hb = mem[(size_t)base].H, Wb = mem[(size_t)base].W;
+  // gain and bias, in double, stored as float
+  std::vector<float> gb((size_t)2 * M * Ctot);
+  float* gain = gb.data();
+  float* bias = gain + (size_t)M * Ctot;
+  for (int m = 0; m < M; ++m) {
+    const double rho = m == base ? 1.0 : scales[base] / scales[m];
+    float* g = gain + (size_t)m * Ctot;
+    float* bi = bias + (size_t)m * Ctot;
+    for (int ch = 0; ch < C[0]; ++ch) g[ch] = 1.f, bi[ch] = 0.f;
+    for (int ch = C[0]; ch < C[0] + C[1]; ++ch) g[ch] = (float)rho, bi[ch] = 0.f;
+    for (int i = 0; i < C[2]; ++i) {
+      const double mu = mean ? mean[i] : 0.0, sd = stdev ? stdev[i] : 1.0;
+      g[C[0] + C[1] + i] = (float)rho;
+      bi[C[0] + C[1] + i] = (float)((rho - 1.0) * mu / sd);
+    }
+  }
+  const size_t mem_b = (size_t)M * sizeof(FuseMember), gb_b = gb.size() * sizeof(float);
+  std::vector<unsigned char> table(mem_b + gb_b);
+  std::memcpy(table.data(), mem.data(), mem_b);
+  std::memcpy(table.data() + mem_b, gb.data(), gb_b);
+  unsigned char* d_table = (unsigned char*)fuse_table_.get(table.size());
+  if (table != fuse_table_host_) {
+    fuse_table_host_.clear();  // (not what the device holds any more, should the upload throw)
+    dev_upload(d_table, table.data(), table.size(), s);
+    fuse_table_host_ = std::move(table);
+  }
+  float* out = (float*)fused_.get((size_t)NB * Hb * Wb * Ctot * sizeof(float));
+  KCHECK(launch_fuse_maps((const FuseMember*)d_table, (const float*)(d_table + mem_b), (const float*)(d_table + mem_b) + (size_t)M * Ctot, M, ek, NB,
+                          Hb, Wb, C, out, s));
+  FusedMaps fm{};
+  int c0 = 0;
+  for (int k = 0; k < 3; ++k) {
+    fm.map[k] = Net::MapRef{out, Ctot, c0, 4, kElemF32, NB, C[k], Hb, Wb};
+    c0 += C[k];
+  }
+  return fm;
+}
+
+void NetGroup::fuse_done(void* s) {
+  if (!fuse_event_) {
+    hipEvent_t ev;
+    HIPCHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    fuse_event_ = ev;
+  }
+  HIPCHECK(hipEventRecord((hipEvent_t)fuse_event_, (hipStream_t)s));
+  fuse_stream_ = s;
+}
+
+void NetGroup::fuse_maps(const double* scales, int base, int n_edges, const double* mean, const double* stdev, float* prob, float* loc,
+                         float* next, bool is_device, void* user_stream) {
+  float* const dst[3] = {prob, loc, next};
+  const bool use[3] = {prob != nullptr, loc != nullptr, next != nullptr};
+  int C[3], NB;
+  check_fuse("fuse_maps", scales, base, use, n_edges, mean, stdev, C, NB);
+  if (!use[0] && !use[1] && !use[2]) return;
+  if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "fuse_maps() in CPU mode: libdeepcut_hip provides the MI355X path only");
+  const bool own_async = user_stream == (void*)-1;
+  if (own_async) user_stream = nullptr;
+  nets[0]->ensure_device();
+  void* s = user_stream ? user_stream : stream();
+  const FusedMaps fm = fuse(scales, base, use, mean, stdev, s);
+  size_t total = 0;
+  for (int k = 0; k < 3; ++k) total += (size_t)fm.map[k].NB * fm.map[k].C * fm.map[k].H * fm.map[k].W;
+  float* stage = is_device ? nullptr : (float*)fuse_stage_.get(total * sizeof(float));
+  for (int k = 0; k < 3; ++k) {
+    if (!use[k]) continue;
+    const Net::MapRef& r = fm.map[k];
+    const size_t cnt = (size_t)r.NB * r.C * r.H * r.W;
+    float* to = is_device ? dst[k] : stage;
+    KCHECK(launch_nhwc_to_nchw(r.ptr, to, r.ek, r.NB, r.C, r.H, r.W, r.cp, r.c0, s));
+    if (!is_device) {
+      HIPCHECK(hipMemcpyAsync(dst[k], stage, cnt * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)s));
+      stage += cnt;
+    }
+  }
+  fuse_done(s);
+  if (!(is_device && (user_stream || own_async))) HIPCHECK(hipStreamSynchronize((hipStream_t)s));
+}
+
+void NetGroup::detect_parts(const double* scales, int base, float thr, int radius, int max_det, int* counts, double* dets) {
+  const bool use[3] = {true, true, false};
+  int C[3], NB;
+  check_fuse("detect_parts", scales, base, use, 0, nullptr, nullptr, C, NB);
+  if (!(thr >= 0.f) || radius < 0 || radius > 64 || max_det < 1 || max_det > 4096)
+    throw DcError(DC_EINVAL, "detect_parts: scale > 0, threshold >= 0, 0 <= radius <= 64, 1 <= max_det <= 4096");
+  if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "detect_parts() in CPU mode");
+  nets[0]->ensure_device();
+  void* s = stream();
+  const FusedMaps fm = fuse(scales, base, use, nullptr, nullptr, s);
+  const Net::MapRef &P = fm.map[0], &L = fm.map[1];
+  if (L.C != 2 * P.C) throw DcError(DC_ESHAPE, "detect_parts: loc_pred must have 2 channels per joint and the score map's size");
+  const int lists = P.NB * P.C;
+  const size_t cnt_b = ((size_t)lists * sizeof(int) + 255) / 256 * 256;
+  const size_t spill_b = (size_t)lists * P.H * P.W * sizeof(unsigned long long);  // every cell may be a local maximum
+  const size_t out_b = (size_t)lists * max_det * 5 * sizeof(double);
+  unsigned char* at = (unsigned char*)people_scratch_.get(cnt_b + spill_b + out_b);
+  int* cnt = (int*)at;
+  unsigned long long* spill = (unsigned long long*)(at + cnt_b);
+  double* out = (double*)(at + cnt_b + spill_b);
+  KCHECK(launch_part_select(P.ptr, P.cp, P.c0, L.ptr, L.cp, L.c0, P.ek, P.NB, P.H, P.W, P.C, thr, radius, scales[base], max_det, spill, cnt, out, s));
+  HIPCHECK(hipMemcpyAsync(counts, cnt, (size_t)lists * sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)s));
+  HIPCHECK(hipMemcpyAsync(dets, out, out_b, hipMemcpyDeviceToHost, (hipStream_t)s));
+  HIPCHECK(hipStreamSynchronize((hipStream_t)s));
+  fuse_done(s);
+}
+
+void NetGroup::assemble_people(const double* scales, int base, const Net::AssembleParams& p, int n_edges, const int* edges, const double* mean,
+                               const double* stdev, const int* joint_order, int* n_people, double* people, int* cand, double* cost) {
+  const bool use[3] = {true, true, true};
+  int C[3], NB;
+  check_scales("assemble_people", scales, base);  // first: the assembly runs at scales[base]
+  Net::AssembleParams q = p;
+  q.scale = scales[base];
+  Net::check_assemble_params(q);
+  auto ip = nets[(size_t)base]->blob_index.find("prob");
+  if (ip == nets[(size_t)base]->blob_index.end()) throw DcError(DC_EINVAL, "net has no 'prob' blob");
+  const std::vector<int>& pshape = nets[(size_t)base]->blobs[ip->second]->st->shape;
+  if (pshape.size() != 4) throw DcError(DC_ESHAPE, "'prob' is not a 4-D map");
+  const std::vector<int> table = Net::check_assemble_graph(q, pshape[1], n_edges, edges, mean, stdev, joint_order);
+  check_fuse("assemble_people", scales, base, use, n_edges, mean, stdev, C, NB);
+  if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "assemble_people() in CPU mode");
+  nets[0]->ensure_device();
+  void* s = stream();
+  const FusedMaps fm = fuse(scales, base, use, mean, stdev, s);
+  Net::assemble_maps(fm.map[0], fm.map[1], fm.map[2], q, table, n_edges, mean, stdev, [this](size_t bytes) { return people_scratch_.get(bytes); }, s,
+                     n_people, people, cand, cost);
+  fuse_done(s);
 }
 
 int NetGroup::num_launches() { return cur_ ? (int)cur_->launches.size() : 0; }

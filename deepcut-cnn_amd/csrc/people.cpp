@@ -99,9 +99,9 @@ PairStats read_pair_stats(const std::string& path) {
 
 // ---- the device path ---------------------------------------------------------------------------------------------------
 // Stage A = Net::detect_parts' launch with its outputs left in the scratch buffer, stage B = launch_pair_cost, stage C =
-// launch_assemble: three launches on the net's stream with nothing in between, then the downloads of the results.
-void Net::assemble_people(const AssembleParams& q, int n_edges, const int* edges, const double* mean, const double* stdev,
-                          const int* joint_order, int* n_people, double* people, int* cand, double* cost) {
+// launch_assemble: three launches on one stream with nothing in between, then the downloads of the results.  The argument checks
+// and the device half are functions of their own: NetGroup::assemble_people runs them on the fused maps of a pyramid (net_group.cpp).
+void Net::check_assemble_params(const AssembleParams& q) {
   auto bad = [](const std::string& m) { throw DcError(DC_EINVAL, "assemble_people: " + m); };
   if (!(q.scale > 0) || !std::isfinite(q.scale)) bad("scale must be positive");
   if (!(q.threshold >= 0.f)) bad("threshold must be >= 0");
@@ -110,11 +110,11 @@ void Net::assemble_people(const AssembleParams& q, int n_edges, const int* edges
   if (!(q.max_cost >= 0) || !std::isfinite(q.max_cost)) bad("max_cost must be finite and >= 0");
   if (!std::isfinite(q.seed_threshold)) bad("seed_threshold must be finite");
   if (q.max_people < 1 || q.max_people > kPeopleMaxPeople) bad("max_people must be in [1, " + std::to_string(kPeopleMaxPeople) + "]");
-  auto ip = blob_index.find("prob");
-  if (ip == blob_index.end()) throw DcError(DC_EINVAL, "net has no 'prob' blob");
-  const std::vector<int>& pshape = blobs[ip->second]->st->shape;
-  if (pshape.size() != 4) throw DcError(DC_ESHAPE, "'prob' is not a 4-D map");
-  const int J = pshape[1];
+}
+
+std::vector<int> Net::check_assemble_graph(const AssembleParams& q, int J, int n_edges, const int* edges, const double* mean,
+                                           const double* stdev, const int* joint_order) {
+  auto bad = [](const std::string& m) { throw DcError(DC_EINVAL, "assemble_people: " + m); };
   if (J < 1 || J > kPeopleMaxJoints)
     throw DcError(DC_ESHAPE, "assemble_people: " + std::to_string(J) + " joints, the assembly holds up to " + std::to_string(kPeopleMaxJoints));
   if (q.min_joints < 1 || q.min_joints > J) bad("min_joints must be in [1, " + std::to_string(J) + "]");
@@ -142,10 +142,28 @@ void Net::assemble_people(const AssembleParams& q, int n_edges, const int* edges
     if (mean && !std::isfinite(mean[i])) bad("mean of edge " + std::to_string(i / 2) + " is not finite");
     if (stdev && !(std::isfinite(stdev[i]) && stdev[i] > 0)) bad("std of edge " + std::to_string(i / 2) + " is not positive and finite");
   }
+  return table;
+}
+
+void Net::assemble_people(const AssembleParams& q, int n_edges, const int* edges, const double* mean, const double* stdev,
+                          const int* joint_order, int* n_people, double* people, int* cand, double* cost) {
+  check_assemble_params(q);
+  auto ip = blob_index.find("prob");
+  if (ip == blob_index.end()) throw DcError(DC_EINVAL, "net has no 'prob' blob");
+  const std::vector<int>& pshape = blobs[ip->second]->st->shape;
+  if (pshape.size() != 4) throw DcError(DC_ESHAPE, "'prob' is not a 4-D map");
+  const std::vector<int> table = check_assemble_graph(q, pshape[1], n_edges, edges, mean, stdev, joint_order);
   // (the arguments above are refused with or without a device; from here on the device is needed)
   if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "assemble_people() in CPU mode");
   ensure_device();
   const MapRef P = map_ref("prob"), L = map_ref("loc_pred"), N = map_ref("next_pred");
+  assemble_maps(P, L, N, q, table, n_edges, mean, stdev, [this](size_t bytes) { return scratch(bytes); }, stream, n_people, people, cand, cost);
+}
+
+void Net::assemble_maps(const MapRef& P, const MapRef& L, const MapRef& N, const AssembleParams& q, const std::vector<int>& table, int n_edges,
+                        const double* mean, const double* stdev, const std::function<void*(size_t)>& scratch, void* stream, int* n_people,
+                        double* people, int* cand, double* cost) {
+  const int J = P.C;
   if (L.C != 2 * P.C || L.H != P.H || L.W != P.W || L.NB != P.NB || L.es != P.es)
     throw DcError(DC_ESHAPE, "assemble_people: loc_pred must have 2 channels per joint and the score map's size");
   if (N.H != P.H || N.W != P.W || N.NB != P.NB) throw DcError(DC_ESHAPE, "assemble_people: next_pred must have the score map's size");

@@ -1,4 +1,4 @@
-// pose.hip — what reads the net's maps on the device: pose decode, part candidates, pairwise regression decode.
+// pose.hip — what reads the net's maps on the device: pose decode, part candidates, pairwise regression decode, multi-scale fusion.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -218,6 +218,69 @@ __global__ __launch_bounds__(256) void pairwise_decode_kernel(const T* __restric
   const double s0 = stdev ? stdev[2 * l] : 1.0, s1 = stdev ? stdev[2 * l + 1] : 1.0;
   o[0] = ((double)col * 8.0 + 4.0 + (double)(float)p[0] * s0 + m0) / scale;
   o[1] = ((double)row * 8.0 + 4.0 + (double)(float)p[1] * s1 + m1) / scale;
+}
+
+// ---- multi-scale fusion of a pyramid's maps (the rule: include/deepcut_hip.h, dc_group_fuse_maps; this project's own) ---------------
+// One workgroup per base cell (image, row, column), lanes along the channels of the three maps laid end to end: the maps are NHWC, so
+// each corner read of a member and the store are contiguous runs of a wave.  The cell's sample position in every member — four corner
+// cells and two weights — is computed once, by the thread of that member's index, and kept in LDS; the channel loop (406 channels of the
+// full heads: two trips of 256) only reads it.  Members are summed in ascending order by every thread: nothing depends on timing.
+struct FuseCorner {
+  int i00, i01, i10, i11;  // cell indices (y * W + x) of the four corners in the member's map
+  float fx, fy;
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void fuse_maps_kernel(const FuseMember* __restrict__ members, const float* __restrict__ gain,
+                                                        const float* __restrict__ bias, int M, int Hb, int Wb, int C0, int C1, int Ctot,
+                                                        float inv_m, float* __restrict__ out) {
+  extern __shared__ FuseCorner fuse_lds[];  // [M]
+  const int cell = blockIdx.x, t = threadIdx.x;
+  const int b = cell / (Hb * Wb), rc = cell - b * (Hb * Wb), r = rc / Wb, c = rc - r * Wb;
+  for (int m = t; m < M; m += 256) {
+    const FuseMember& mem = members[m];
+    const double q = mem.q;
+    double u = ((double)(8 * c + 4) * q - 4.0) / 8.0, v = ((double)(8 * r + 4) * q - 4.0) / 8.0;
+    u = fmin(fmax(u, 0.0), (double)(mem.W - 1));
+    v = fmin(fmax(v, 0.0), (double)(mem.H - 1));
+    const int x0 = (int)floor(u), y0 = (int)floor(v);
+    const int x1 = min(x0 + 1, mem.W - 1), y1 = min(y0 + 1, mem.H - 1);
+    FuseCorner k;
+    k.i00 = y0 * mem.W + x0, k.i01 = y0 * mem.W + x1, k.i10 = y1 * mem.W + x0, k.i11 = y1 * mem.W + x1;
+    k.fx = (float)(u - (double)x0), k.fy = (float)(v - (double)y0);
+    fuse_lds[m] = k;
+  }
+  __syncthreads();
+  float* o = out + (long)cell * Ctot;
+  for (int ch = t; ch < Ctot; ch += 256) {
+    const int k = ch < C0 ? 0 : ch < C1 ? 1 : 2;
+    const int cc = ch - (k == 0 ? 0 : k == 1 ? C0 : C1);
+    float acc = 0.f;
+    for (int m = 0; m < M; ++m) {
+      const FuseMember& mem = members[m];
+      const FuseCorner kc = fuse_lds[m];
+      const long cp = mem.cp[k];
+      const T* p = (const T*)mem.ptr[k] + (long)b * mem.H * mem.W * cp + mem.c0[k] + cc;
+      const float a00 = (float)p[kc.i00 * cp], a01 = (float)p[kc.i01 * cp], a10 = (float)p[kc.i10 * cp], a11 = (float)p[kc.i11 * cp];
+      const float val = (1.f - kc.fy) * ((1.f - kc.fx) * a00 + kc.fx * a01) + kc.fy * ((1.f - kc.fx) * a10 + kc.fx * a11);
+      acc += val * gain[(long)m * Ctot + ch] + bias[(long)m * Ctot + ch];
+    }
+    o[ch] = acc * inv_m;
+  }
+}
+
+int launch_fuse_maps(const FuseMember* members, const float* gain, const float* bias, int M, int ekind, int NB, int Hb, int Wb, const int C[3],
+                     float* out, void* stream) {
+  const int Ctot = C[0] + C[1] + C[2];
+  const long cells = (long)NB * Hb * Wb;
+  if (cells <= 0 || Ctot <= 0) return 0;
+  if (M < 1 || M > 1024 || cells > 0x7fffffffL || C[0] < 0 || C[1] < 0 || C[2] < 0) return (int)hipErrorInvalidValue;
+  return dc_by_kind(ekind, [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    hipLaunchKernelGGL(fuse_maps_kernel<T>, dim3((unsigned)cells), dim3(256), (size_t)M * sizeof(FuseCorner), (hipStream_t)stream, members, gain,
+                       bias, M, Hb, Wb, C[0], C[0] + C[1], Ctot, 1.f / (float)M, out);
+    return (int)hipGetLastError();
+  });
 }
 
 int launch_part_select(const void* prob, int pcp, int pc0, const void* loc, int lcp, int lc0, int ekind, int NB, int H, int W, int J, float thr,

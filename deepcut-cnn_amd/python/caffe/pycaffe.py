@@ -134,6 +134,9 @@ def _load():
                                          C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]),
         "dc_group_forward_boxes": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, C.POINTER(C.c_double), ci, ci, C.POINTER(vp), C.POINTER(vp),
                                         C.POINTER(vp), C.POINTER(vp), vp]),
+        "dc_group_fuse_maps": (ci, [vp, vp, ci, ci, vp, vp, vp, vp, vp, ci, vp]),
+        "dc_group_detect_parts": (ci, [vp, vp, ci, C.c_float, ci, ci, vp, vp]),
+        "dc_group_assemble_people": (ci, [vp, vp, ci, C.POINTER(AssembleParams), ci, vp, vp, vp, vp, vp, vp, vp, vp]),
         "dc_group_plan_text": (cp, [vp]),
         "dc_group_profile_text": (cp, [vp, ci]),
         "dc_group_tune_report": (cp, [vp]),
@@ -1196,6 +1199,79 @@ class NetGroup(object):
                                             self._ints([s[2] for s in shapes]), (C.c_double * k)(*[float(s) for s in scales]), 1,
                                             self._ptrs(prob_ptrs, k), self._ptrs(loc_ptrs, k), self._ptrs(next_ptrs, k), self._ptrs(pose_ptrs, k),
                                             C.c_void_p(stream or 0)))
+
+    def _scales(self, scales, base):
+        """-> (float64 [M] array, base index): one scale per member; what the values must be is the library's to say."""
+        sc = np.ascontiguousarray(scales, dtype=np.float64).reshape(-1)
+        if sc.shape[0] != len(self.nets):
+            raise ValueError("one scale per group member: %d scales for %d members" % (sc.shape[0], len(self.nets)))
+        return sc, int(base)
+
+    def fuse_maps(self, scales, base=0, mean=None, std=None, want=("prob", "loc_pred", "next_pred")):
+        """The maps of the members' last forwards (member c holds the same images at scales[c]) fused on member `base`'s grid, on the
+        device in one launch (dc_group_fuse_maps; the rule is in include/deepcut_hip.h and is this project's own: the reference stops at
+        the maps).  Every member's map is sampled bilinearly at the base cells' image points, loc_pred and next_pred are converted
+        into the base member's units (mean / std: the [E, 2] statistics of next_pred, None = 0 / 1), and the members are averaged.
+        -> dict of float32 NCHW arrays on the base grid, whatever the members' element type."""
+        sc, base = self._scales(scales, base)
+        want = [k for k in ("prob", "loc_pred", "next_pred") if k in want]
+        ref = self.nets[base if 0 <= base < len(self.nets) else 0]
+        e = ref.blobs["next_pred"].shape[1] // 2 if "next_pred" in want else 0
+        stats = []
+        for name, v in (("mean", mean), ("std", std)):
+            if v is None or "next_pred" not in want:
+                stats.append(None)
+                continue
+            v = np.ascontiguousarray(v, dtype=np.float64)
+            if v.size != 2 * e:
+                raise ValueError("%s must be [E, 2] = [%d, 2], got shape %s" % (name, e, v.shape))
+            stats.append(v)
+        hw = ref.blobs["prob"].shape[2:]
+        out = {k: np.empty(tuple(ref.blobs[k].shape[:2]) + tuple(hw), np.float32) for k in want}
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        _check(_lib.dc_group_fuse_maps(self._h, ptr(sc), base, e, ptr(stats[0]), ptr(stats[1]), ptr(out.get("prob")), ptr(out.get("loc_pred")),
+                                       ptr(out.get("next_pred")), 0, None))
+        return out
+
+    def detect_parts(self, scales, base=0, threshold=0.1, radius=1, max_det=32):
+        """Net.detect_parts on the fused `prob` and `loc_pred` of the members' last forwards, at scales[base] (dc_group_detect_parts).
+        -> (counts int32 [n, J], dets float64 [n, J, max_det, 5] = x, y, score, cell row, cell column on the base member's grid)."""
+        sc, base = self._scales(scales, base)
+        n, j = self.nets[0].blobs["prob"].shape[:2]
+        counts = np.zeros((n, j), np.int32)
+        dets = np.zeros((n, j, max(int(max_det), 0), 5), np.float64)
+        _check(_lib.dc_group_detect_parts(self._h, sc.ctypes.data_as(C.c_void_p), base, float(threshold), int(radius), int(max_det),
+                                          counts.ctypes.data_as(C.c_void_p), dets.ctypes.data_as(C.c_void_p)))
+        return counts, dets
+
+    def assemble_people(self, scales, base=0, threshold=0.1, radius=1, max_det=16, edges=None, mean=None, std=None, max_cost=32.0,
+                        seed_threshold=0.5, max_people=32, min_joints=1, joint_order=None, return_cost=False):
+        """Net.assemble_people on the fused maps of a pyramid (dc_group_assemble_people): the three maps of the members' last forwards
+        are fused on member `base`'s grid (`fuse_maps`), then the candidates, the pair costs and the greedy assembly run on them at
+        scales[base], all on the device with no host round trip in between.  The other arguments and the result are Net.assemble_people's."""
+        if edges is None:
+            raise ValueError("assemble_people needs the regression edges (deepcut_tools.read_pair_stats)")
+        sc, base = self._scales(scales, base)
+        ref = self.nets[0]
+        n, j = ref.blobs["prob"].shape[:2]
+        want_e = ref.blobs["next_pred"].shape[1] // 2 if "next_pred" in ref.blobs else None
+        q, e, m, s, order = check_assembly(j, want_e, edges, mean, std, joint_order, 1.0, threshold, radius, max_det, max_cost, seed_threshold,
+                                           max_people, min_joints)
+        p, md = q.max_people, q.max_det
+        count = np.zeros(n, np.int32)
+        people = np.zeros((n, p, j, 3), np.float64)
+        cand = np.zeros((n, p, j), np.int32)
+        cost = np.zeros((n, j, j, md, md), np.float64) if return_cost else None
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        _check(_lib.dc_group_assemble_people(self._h, ptr(sc), base, C.byref(q), e.shape[0], ptr(e), ptr(m), ptr(s), ptr(order), ptr(count),
+                                             ptr(people), ptr(cand), ptr(cost)))
+        out = []
+        for b in range(n):
+            d = {"people": people[b, :count[b]].copy(), "cand": cand[b, :count[b]].copy()}
+            if return_cost:
+                d["cost"] = cost[b]
+            out.append(d)
+        return out
 
     def synchronize(self):
         self.nets[0].synchronize()

@@ -1,8 +1,10 @@
 """Several people in one image, bottom-up: one forward, then the part candidates, the pair costs from `next_pred` and a greedy
-assembly on the device (`caffe.Net.assemble_people`).
+assembly on the device (`caffe.Net.assemble_people`); over an image pyramid, one grouped forward, then the maps of all scales
+fused on the device and assembled there (`caffe.NetGroup.assemble_people`).
 
 NO REFERENCE COUNTERPART: the reference's python/pose stops at `estimate_pose` (one person) and its repository has no consumer of
-`next_pred`.  The grouping rule is this project's own (include/deepcut_hip.h, dc_net_assemble_people)."""
+`next_pred`.  The grouping rule and the multi-scale fusion rule are this project's own (include/deepcut_hip.h, dc_net_assemble_people and
+dc_group_fuse_maps)."""
 import numpy as _np
 
 _MODEL = {}
@@ -18,14 +20,28 @@ def _get_model(model_def, model_bin):
     return _MODEL[key]
 
 
-def estimate_people(image, model_def, model_bin, stats, scale=1.0, net=None, **assembly):
+def _base_scale(scales):
+    """The member a pyramid is fused on when the caller names none: the scale nearest 1.0, the first of equals."""
+    return min(range(len(scales)), key=lambda i: (abs(float(scales[i]) - 1.0), i))
+
+
+def estimate_people(image, model_def, model_bin, stats, scale=1.0, net=None, scales=None, base=None, **assembly):
     """image: HxWx3 BGR uint8.  stats: the path of the model's pair-statistics file (deepcut_tools.read_pair_stats) or the
     (edges, mean, std) triple itself.  Runs the image entry (`Net.forward_images`: pre-processing on the device) with all three
     outputs computed, then `Net.assemble_people(scale=scale, edges=..., mean=..., std=..., **assembly)`; `assembly` takes its other
     arguments (threshold, radius, max_det, max_cost, seed_threshold, max_people, min_joints, joint_order: the defaults of max_cost
     and seed_threshold are placeholders, not tuned on real images).
     -> float64 [m, J, 3]: x, y, score per person and joint in image coordinates, (0, 0, 0) where a person has no such joint.
-    A caller-supplied `net` keeps its output selection: one that leaves `next_pred` out is refused, not changed."""
+    A caller-supplied `net` keeps its output selection: one that leaves `next_pred` out is refused, not changed.
+    scales: a list of scales runs the image pyramid instead — the net and clones of it kept with it, as `estimate_pose` uses them, in
+    ONE grouped forward (`NetGroup.forward_images`), then `NetGroup.assemble_people`: the maps of all scales are fused on the grid of
+    member `base` (None = the scale nearest 1.0, the first of equals) on the device and assembled there at scales[base].  `scale`
+    must then be left at 1.0.  The clones are the ones `estimate_pose` keeps with the net for its own pyramids; they are set to compute
+    all three outputs here (after the net itself has been accepted: a net that leaves `next_pred` out is refused before anything is
+    touched), and `estimate_pose` on its own cached net narrows its clones again — alternating the two entries on ONE net re-lowers the
+    clones' plans at every switch, so give each entry a net of its own where both are in use."""
+    if scales is not None and float(scale) != 1.0:
+        raise ValueError("estimate_people takes scale (one forward) or scales (a pyramid), not both: scale=%r, scales=%r" % (scale, scales))
     if isinstance(stats, (str, bytes)) or hasattr(stats, "__fspath__"):
         from deepcut_tools import read_pair_stats
 
@@ -39,6 +55,19 @@ def estimate_people(image, model_def, model_bin, stats, scale=1.0, net=None, **a
     image = _np.asarray(image)
     if image.dtype != _np.uint8 or image.ndim != 3 or image.shape[2] != 3:
         raise ValueError("image must be uint8 [H,W,3] (BGR)")
+    if scales is not None:
+        from .estimate_pose import _scale_group
+
+        scales = [float(v) for v in scales]
+        if not scales:
+            raise ValueError("scales must name at least one scale")
+        grp = _scale_group(net, len(scales))
+        for m in grp.nets[1:]:  # the clones kept with the net are this module's to set: all three outputs, like the net itself
+            if sorted(m.wanted_outputs) != sorted(net.wanted_outputs):
+                m.set_outputs(None)
+        grp.forward_images(image, scales, want=(), pose=False)
+        return grp.assemble_people(scales, _base_scale(scales) if base is None else int(base), edges=edges, mean=mean, std=std,
+                                   **assembly)[0]["people"]
     net.forward_images(image, scale, want=(), pose=False)
     return net.assemble_people(scale=scale, edges=edges, mean=mean, std=std, **assembly)[0]["people"]
 

@@ -458,6 +458,51 @@ int dc_group_forward_images(dc_group* group, const unsigned char* const* images,
 int dc_group_forward_boxes(dc_group* group, const unsigned char* image, int height, int width, int is_device, const int* boxes,
                            const double* scales, int n, const double* pyramid_scales, int canvas_h, int canvas_w, float* const* prob,
                            float* const* loc_pred, float* const* next_pred, double* const* pose, void* stream);
+/* ---- multi-scale bottom-up people: the maps of a pyramid fused on the device ------------------------------------------------------
+ * NO REFERENCE COUNTERPART, as for dc_net_assemble_people: the reference repository stops at the maps.  The fusion rule below is this
+ * project's own and its parity is unpinned by the reference; only the label encoding (pose_data_layer.cpp:686-802) is restated.
+ *
+ * The group has M members; member m holds, from its LAST forward, the maps of the same NB images at scale scales[m] (the usual case: one
+ * dc_group_forward_images over a pyramid).  s_b = scales[base].  The fused maps live on the base member's grid H_b x W_b and are
+ * float32 whatever the members' element type.  For member m: q = scales[m] / s_b and rho = s_b / scales[m], one division each in
+ * double (both exactly 1 for the base member).
+ *  Sample position of base cell (r, c) in member m: u = ((8c + 4) q - 4) / 8, v = ((8r + 4) q - 4) / 8 in double (the cell's image
+ *     point, in member m's cells); u clamped to [0, W_m - 1], v to [0, H_m - 1]; x0 = floor(u), x1 = min(x0 + 1, W_m - 1), fx = u - x0,
+ *     the same for y; fx, fy converted to float.
+ *  Sample, in float32, the four corners read in the member's element type and widened to float:
+ *     val = (1 - fy) ((1 - fx) a00 + fx a01) + fy ((1 - fx) a10 + fx a11)
+ *  Conversion into the base member's units: out_m = val * gain + bias, with (gain, bias) = (1, 0) for prob; (rho, 0) for loc_pred, which
+ *     holds (joint - pt) s / sqrt(53); (rho, (rho - 1) mean[l][k] / std[l][k]) for next_pred channel 2l + k, which turns ((next - pt) s_m -
+ *     mean) / std into ((next - pt) s_b - mean) / std.  The table [M][channels] is computed on the host in double and uploaded as float;
+ *     mean / stdev NULL = 0 / 1.
+ *  Fusion: fused = (sum over m ascending of out_m) * (1 / M), in float32.
+ * A group of one member fuses to that member's maps widened to float32; the base member always contributes its own cells unchanged; a
+ * field that is linear in the cell position is interpolated without error wherever nothing is clamped.  Nothing is atomic or
+ * order-dependent: same inputs, same bits.  One launch fuses every map, member and image.
+ *
+ * Everything runs on the group's stream (the first member's own; dc_group_fuse_maps: or `stream`), so a grouped forward issued there
+ * before is complete when the fusion reads its maps.  A caller who forwarded the members individually (dc_net_forward_* with streams
+ * of their own) synchronises them first.  The fused buffer is the group's only one: each of the three calls makes its stream wait
+ * (an event, no host wait) for what the previous of them left running, so they may follow an asynchronous dc_group_fuse_maps on another
+ * stream; the caller's own device destinations of that call are the caller's to wait for.  Calls on one group come from one thread at a time.
+ *
+ * dc_group_fuse_maps: the fused maps as NCHW float32 [NB][C][H_b][W_b], any of prob / loc_pred / next_pred NULL to leave that map out
+ *     (n_edges, mean and stdev are read only when next_pred is asked for).  Host or device destinations and `stream` as in
+ *     dc_group_forward_images.
+ * dc_group_detect_parts: dc_net_detect_parts on the fused prob and loc_pred (only these two are fused) at scale s_b.
+ * dc_group_assemble_people: fuses all three maps, then stages A, B and C of dc_net_assemble_people on the fused maps at scale s_b with no
+ *     host round trip in between; p->scale is not read, everything else is as there (outputs, limits, errors).
+ * Errors, raised before any device work and naming what is wrong: DC_EINVAL for null scales, a scale that is not positive and finite,
+ *     base outside [0, M), a non-finite mean, a std that is not positive and finite; DC_ESHAPE for members whose maps differ in batch size
+ *     or channel counts, and for n_edges different from next_pred channels / 2 when next_pred takes part.  Then DC_ENOCPU in CPU mode.
+ *     DC_EUNSUP when next_pred is asked for or needed but left out by DC_OPT_OUTPUTS on a member.                                      */
+int dc_group_fuse_maps(dc_group* group, const double* scales, int base, int n_edges, const double* mean, const double* stdev, float* prob,
+                       float* loc_pred, float* next_pred, int is_device, void* stream);
+int dc_group_detect_parts(dc_group* group, const double* scales, int base, float threshold, int radius, int max_det, int* counts,
+                          double* dets);
+int dc_group_assemble_people(dc_group* group, const double* scales, int base, const dc_assemble_params* p, int n_edges, const int* edges,
+                             const double* mean, const double* stdev, const int* joint_order, int* n_people, double* people, int* cand,
+                             double* cost);
 /* the merged plan of the last forward: one line per launch ("conv_gemm_mp<tile> problems=.. grid=.." or "member c: <kernel>");
  * NULL + dc_last_error() before the first forward; pointer valid until the next call on this group                            */
 const char* dc_group_plan_text(dc_group* group);
