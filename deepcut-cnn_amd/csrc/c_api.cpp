@@ -740,6 +740,60 @@ int dc_group_assemble_people(dc_group* group, const double* scales, int base, co
     G(group)->assemble_people(scales, base, q, n_edges, edges, mean, stdev, joint_order, n_people, people, cand, cost);
   });
 }
+// mirrored members: the same calls with a dc_fuse_mirror; null, or no member marked, is the unmirrored call (net_group.cpp check_mirror)
+static const NetGroup::FuseMirror* mirror_args(const dc_fuse_mirror* fm, NetGroup::FuseMirror& to) {
+  if (!fm) return nullptr;
+  to = NetGroup::FuseMirror{fm->mirror, fm->image_width, fm->joint_mirror, fm->n_edges, fm->edges};
+  return &to;
+}
+int dc_group_forward_images_mirrored(dc_group* group, const unsigned char* const* images, const int* n, const int* height, const int* width,
+                                     const double* scale, const int* mirror, int is_device, float* const* prob, float* const* loc_pred,
+                                     float* const* next_pred, void* stream) {
+  if (!mirror) return dc_group_forward_images(group, images, n, height, width, scale, is_device, prob, loc_pred, next_pred, nullptr, stream);
+  REQUIRE(group);
+  REQUIRE(images);
+  REQUIRE(n);
+  REQUIRE(height);
+  REQUIRE(width);
+  REQUIRE(scale);
+  for (size_t c = 0; c < G(group)->nets.size(); ++c) {
+    if (!images[c]) return fail(DC_EINVAL, "null images for group member " + std::to_string(c));
+    if (n[c] <= 0 || height[c] <= 0 || width[c] <= 0 || !(scale[c] > 0)) return fail(DC_EINVAL, "bad image shape / scale for group member " + std::to_string(c));
+  }
+  return guard([&] { G(group)->forward_images(images, n, height, width, scale, is_device != 0, prob, loc_pred, next_pred, nullptr, stream, mirror); });
+}
+int dc_group_fuse_maps_mirrored(dc_group* group, const double* scales, int base, const dc_fuse_mirror* fm, int n_edges, const double* mean,
+                                const double* stdev, float* prob, float* loc_pred, float* next_pred, int is_device, void* stream) {
+  REQUIRE(group);
+  return guard([&] {
+    NetGroup::FuseMirror m;
+    G(group)->fuse_maps(scales, base, n_edges, mean, stdev, prob, loc_pred, next_pred, is_device != 0, stream, mirror_args(fm, m));
+  });
+}
+int dc_group_detect_parts_mirrored(dc_group* group, const double* scales, int base, const dc_fuse_mirror* fm, float threshold, int radius,
+                                   int max_det, int* counts, double* dets) {
+  REQUIRE(group);
+  REQUIRE(counts);
+  REQUIRE(dets);
+  return guard([&] {
+    NetGroup::FuseMirror m;
+    G(group)->detect_parts(scales, base, threshold, radius, max_det, counts, dets, mirror_args(fm, m));
+  });
+}
+int dc_group_assemble_people_mirrored(dc_group* group, const double* scales, int base, const dc_fuse_mirror* fm, const dc_assemble_params* p,
+                                      int n_edges, const int* edges, const double* mean, const double* stdev, const int* joint_order,
+                                      int* n_people, double* people, int* cand, double* cost) {
+  REQUIRE(group);
+  REQUIRE(p);
+  REQUIRE(n_people);
+  REQUIRE(people);
+  if (n_edges > 0) REQUIRE(edges);
+  return guard([&] {
+    Net::AssembleParams q{p->scale, p->threshold, p->radius, p->max_det, p->max_cost, p->seed_threshold, p->max_people, p->min_joints};
+    NetGroup::FuseMirror m;
+    G(group)->assemble_people(scales, base, q, n_edges, edges, mean, stdev, joint_order, n_people, people, cand, cost, mirror_args(fm, m));
+  });
+}
 int dc_comm_create(int nexec, const int* devices, int transport, dc_comm** out) {
   REQUIRE(out);
   *out = nullptr;

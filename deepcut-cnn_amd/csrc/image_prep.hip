@@ -28,7 +28,8 @@ __global__ __launch_bounds__(256) void image_resample_x_kernel(ImagePrepParams p
   const int* kk = p.x_coeffs + (long)x * p.x_ksize;
   int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
   for (int k = 0; k < cnt; ++k) {
-    const int sx = min(xmin + k, p.w - 1);  // columns >= w replicate the last column (:93-95)
+    int sx = min(xmin + k, p.w - 1);  // columns >= w replicate the last column (:93-95)
+    if (p.mirror) sx = p.w - 1 - sx;  // ... of the mirrored image: column x of it is source column w - 1 - x
     const int c = kk[k];
     a0 += row[sx * 3 + 0] * c;
     a1 += row[sx * 3 + 1] * c;
@@ -53,7 +54,8 @@ __global__ __launch_bounds__(256) void image_finish_kernel(ImagePrepParams p) {
         const uchar4 q = reinterpret_cast<const uchar4*>(p.tmp)[((long)n * p.rows + (row - p.row0)) * p.use_w + x];
         b0 = q.x, b1 = q.y, b2 = q.z;
       } else {
-        const unsigned char* s = p.src + (((long)n * p.h + min(row, p.h - 1)) * p.w + min(x, p.w - 1)) * 3;
+        const int sx = min(x, p.w - 1);
+        const unsigned char* s = p.src + (((long)n * p.h + min(row, p.h - 1)) * p.w + (p.mirror ? p.w - 1 - sx : sx)) * 3;
         b0 = s[0], b1 = s[1], b2 = s[2];
       }
     };

@@ -370,9 +370,23 @@ struct FuseMember {
 int launch_fuse_maps(const FuseMember* members, const float* gain, const float* bias, int M, int ekind, int NB, int Hb, int Wb, const int C[3],
                      float* out, void* stream);
 
+// The same with mirrored members (dc_group_fuse_maps_mirrored): flip[m].on marks a member that saw the image flipped left to right, ws =
+// (image width - 1) * the member's scale; its sample column is u = ((ws - (8c + 4) q) - 4) / 8.  src[m*Ctot + ch] is the channel WITHIN
+// its map (0 .. C[k] - 1) that output channel ch reads from member m (the identity for an unmirrored member); the sign changes are in
+// gain / bias.  Everything else — corners, weights, the ascending sum, 1 / M — is launch_fuse_maps'.
+struct FuseFlip {
+  double ws;
+  int on, pad_;
+};
+int launch_fuse_maps_mirrored(const FuseMember* members, const FuseFlip* flip, const float* gain, const float* bias, const int* src, int M,
+                              int ekind, int NB, int Hb, int Wb, const int C[3], float* out, void* stream);
+
 // Image pre-processing of the demo (python/pose/estimate_pose.py:83-103) on the device: replicate padding by
 // coordinate clamping, Pillow's two-pass 8-bit bilinear resample (22-bit fixed-point weights from the host),
 // mean subtraction and the zero canvas, written straight into the network's NHWC input image.
+// mirror: the image is read flipped left to right — source column w - 1 - x wherever column x of the unpadded image would be read, so
+// the replicate padding repeats the FLIPPED image's last column (source column 0) — and everything after that is unchanged: the result
+// is, bit for bit, what the unmirrored path makes of the host-flipped image (dc_group_forward_images_mirrored).
 struct ImagePrepParams {
   const unsigned char* src;  // [n][h][w][3] BGR uint8
   int n, h, w;
@@ -389,6 +403,7 @@ struct ImagePrepParams {
   void* dst;                 // [n][out_h][out_w][dst_cp] float, _Float16 or __bf16 (dst_ekind); pad channels zeroed
   int dst_ekind, dst_cp;
   float mean[3];
+  int mirror;                // 0 / 1
 };
 int launch_image_prep(const ImagePrepParams& p, void* stream);
 

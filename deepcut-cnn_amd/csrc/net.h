@@ -342,7 +342,8 @@ struct Net {
                        int* n_people, double* people, int* cand, double* cost);
   // front half of forward_images: the uint8 pixels -> the network's NHWC input image, enqueued on s (the plan of the canvas
   // shape is active afterwards); returns the canvas height / width
-  void prep_images(const unsigned char* bgr, int n, int h, int w, double scale, bool is_device, void* s);
+  // mirror: the images are read flipped left to right (ImagePrepParams::mirror; NetGroup::forward_images hands it down)
+  void prep_images(const unsigned char* bgr, int n, int h, int w, double scale, bool is_device, void* s, bool mirror = false);
   // front half of forward_boxes (arguments already checked): the boxes' canvases in ONE launch, and the per-box decode table;
   // returns the device copy of the image the launch reads (a host image is uploaded once)
   const unsigned char* prep_boxes(const unsigned char* bgr, int h, int w, bool is_device, const int* boxes, const double* scales, int n,
@@ -466,9 +467,11 @@ struct NetGroup {
   void forward_batch(const float* const* inputs, const int* n, const int* h, const int* w, bool is_device, float* const* prob,
                      float* const* loc, float* const* next, void* user_stream);
   // image entry: member c pre-processes n[c] images of h[c] x w[c] at scale[c] (Net::forward_images), then ONE grouped
-  // forward, then per member the maps / the decoded pose
+  // forward, then per member the maps / the decoded pose.  mirror (dc_group_forward_images_mirrored): [M] 0/1, null = none; a mirrored
+  // member pre-processes its images flipped left to right and returns its raw maps, in the flipped image's frame
   void forward_images(const unsigned char* const* bgr, const int* n, const int* h, const int* w, const double* scale, bool is_device,
-                      float* const* prob, float* const* loc, float* const* next, double* const* pose, void* user_stream);
+                      float* const* prob, float* const* loc, float* const* next, double* const* pose, void* user_stream,
+                      const int* mirror = nullptr);
   // box entry (Net::forward_boxes): member c takes every box at scales[i] * pyramid[c] on a canvas of box_member_canvas(canvas_h / w,
   // pyramid[c]); the image is uploaded once, each member pre-processes its boxes in one launch, then ONE grouped forward
   void forward_boxes(const unsigned char* bgr, int h, int w, bool is_device, const int* boxes, const double* scales, int n,
@@ -482,13 +485,24 @@ struct NetGroup {
   // call's work (an event, no host wait), so a call may follow an asynchronous fuse_maps on another stream.  What an asynchronous
   // fuse_maps wrote to the caller's device buffers is the caller's to wait for, as with forward_images.
   // fuse_maps: the fused maps as NCHW float32 (any of them null: not fused), host or device, stream as forward_images
+  // Mirrored members (dc_group_*_mirrored; the rule: include/deepcut_hip.h): `fm` names the members that saw the image flipped left to
+  // right, the image's width, the joint permutation and the regression edges.  Null, or no member marked: the calls below are what they
+  // were, through the unmirrored kernel.  Otherwise the fusion is launch_fuse_maps_mirrored, still one launch.
+  struct FuseMirror {
+    const int* mirror;        // [M] 0/1, null = none
+    int image_width;
+    const int* joint_mirror;  // [J]
+    int n_edges;
+    const int* edges;         // [n_edges][2]
+  };
   void fuse_maps(const double* scales, int base, int n_edges, const double* mean, const double* stdev, float* prob, float* loc, float* next,
-                 bool is_device, void* user_stream);
+                 bool is_device, void* user_stream, const FuseMirror* fm = nullptr);
   // Net::detect_parts on the fused prob / loc_pred at scales[base]
-  void detect_parts(const double* scales, int base, float thr, int radius, int max_det, int* counts, double* dets);
+  void detect_parts(const double* scales, int base, float thr, int radius, int max_det, int* counts, double* dets, const FuseMirror* fm = nullptr);
   // fusion of all three maps, then Net::assemble_people's three launches on them at scales[base] (p.scale is not read)
   void assemble_people(const double* scales, int base, const Net::AssembleParams& p, int n_edges, const int* edges, const double* mean,
-                       const double* stdev, const int* joint_order, int* n_people, double* people, int* cand, double* cost);
+                       const double* stdev, const int* joint_order, int* n_people, double* people, int* cand, double* cost,
+                       const FuseMirror* fm = nullptr);
   // lanes: 0 = automatic (2 members: two lanes; 3: one; 4 and more: two), else that many (at most one per member); every merged plan is dropped
   void set_lanes(int n);
   int lanes() const { return cur_ ? cur_->nlanes : lanes_opt_; }
@@ -531,12 +545,23 @@ struct NetGroup {
   void check_scales(const char* who, const double* scales, int base) const;  // the scales and the base index alone
   void check_fuse(const char* who, const double* scales, int base, const bool use[3], int n_edges, const double* mean, const double* stdev,
                   int C[3], int& NB) const;
-  FusedMaps fuse(const double* scales, int base, const bool use[3], const double* mean, const double* stdev, void* s);
+  // what check_mirror makes of a FuseMirror (host only): empty `on` = no mirrored member, the unmirrored path
+  struct MirrorPlan {
+    std::vector<int> on;      // [M] 0/1
+    std::vector<int> pi;      // [J]
+    std::vector<int> edge;    // [E]: the lowest-index edge equal to (pi[a], pi[c]) of edge (a, c); empty when next_pred takes no part
+    int image_width = 0;
+  };
+  MirrorPlan check_mirror(const char* who, const FuseMirror* fm, int base, const bool use[3], int n_edges, const int C[3]) const;
+  FusedMaps fuse(const double* scales, int base, const bool use[3], const double* mean, const double* stdev, void* s,
+                 const MirrorPlan* mp = nullptr);
+  FusedMaps fuse_mirrored(const double* scales, int base, const std::vector<FuseMember>& mem, const int C[3], int NB, int ek, const double* mean,
+                          const double* stdev, void* s, const MirrorPlan& mp);
   DevBuf fused_, fuse_table_, fuse_stage_, people_scratch_;
   void* fuse_event_ = nullptr;    // recorded behind the last fusion call's work ...
   void* fuse_stream_ = nullptr;   // ... on this stream
   void fuse_done(void* s);        // record it
-  std::vector<unsigned char> fuse_table_host_;  // what fuse_table_ holds: the members' descriptors, then gain and bias [M][channels]
+  std::vector<unsigned char> fuse_table_host_;  // what fuse_table_ holds: the members' descriptors, then gain and bias [M][channels] (mirrored: then the source channels)
 };
 
 // ---- runtime.cpp: pinned host memory (dc_host_alloc / dc_host_free) ---------------------------------------------------------

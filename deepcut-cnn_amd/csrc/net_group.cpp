@@ -711,14 +711,15 @@ void NetGroup::forward_batch(const float* const* inputs, const int* n, const int
 }
 
 void NetGroup::forward_images(const unsigned char* const* bgr, const int* n, const int* h, const int* w, const double* scale, bool is_device,
-                              float* const* prob, float* const* loc, float* const* next, double* const* pose, void* user_stream) {
+                              float* const* prob, float* const* loc, float* const* next, double* const* pose, void* user_stream,
+                              const int* mirror) {
   if (!bgr || !n || !h || !w || !scale) throw DcError(DC_EINVAL, "group forward_images: null argument");
   if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "forward_images() in CPU mode: libdeepcut_hip provides the MI355X path only");
   const bool own_async = user_stream == (void*)-1;
   if (own_async) user_stream = nullptr;
   nets[0]->ensure_device();
   void* s = user_stream ? user_stream : stream();
-  for (size_t c = 0; c < nets.size(); ++c) nets[c]->prep_images(bgr[c], n[c], h[c], w[c], scale[c], is_device, s);
+  for (size_t c = 0; c < nets.size(); ++c) nets[c]->prep_images(bgr[c], n[c], h[c], w[c], scale[c], is_device, s, mirror && mirror[c] != 0);
   enqueue(s);
   for (size_t c = 0; c < nets.size(); ++c) {
     nets[c]->emit_maps(prob ? prob[c] : nullptr, loc ? loc[c] : nullptr, next ? next[c] : nullptr, is_device, s);
@@ -830,9 +831,64 @@ void NetGroup::check_fuse(const char* who, const double* scales, int base, const
     throw DcError(DC_ESHAPE, w + std::to_string(n_edges) + " edges for a next_pred of " + std::to_string(C[2]) + " channels (2 per regression edge)");
 }
 
+// Mirrored members (dc_group_*_mirrored), host only and after check_fuse: what is wrong is said before any device work.  -> the plan of
+// the mirrored launch, or one with an empty `on` (fm null, or no member marked): the unmirrored path, nothing else of fm is read.
+NetGroup::MirrorPlan NetGroup::check_mirror(const char* who, const FuseMirror* fm, int base, const bool use[3], int n_edges, const int C[3]) const {
+  MirrorPlan mp;
+  const std::string w = std::string(who) + ": ";
+  const int M = (int)nets.size();
+  bool any = false;
+  for (int m = 0; fm && fm->mirror && m < M; ++m) any = any || fm->mirror[m] != 0;
+  if (!any) return mp;
+  if (fm->image_width <= 0) throw DcError(DC_EINVAL, w + "image_width " + std::to_string(fm->image_width) + " is not positive (a member is mirrored)");
+  if (fm->mirror[base] != 0)
+    throw DcError(DC_EINVAL, w + "base member " + std::to_string(base) + " is mirrored: the fused maps live in the unmirrored image's frame");
+  if (!fm->joint_mirror) throw DcError(DC_EINVAL, w + "null joint_mirror (a member is mirrored)");
+  int J = use[0] ? C[0] : use[1] ? C[1] / 2 : 0;
+  if (J == 0) {  // next_pred alone: the joints are the base member's `prob` channels
+    auto it = nets[(size_t)base]->blob_index.find("prob");
+    if (it == nets[(size_t)base]->blob_index.end() || nets[(size_t)base]->blobs[it->second]->st->shape.size() != 4)
+      throw DcError(DC_EINVAL, w + "member " + std::to_string(base) + " has no 'prob' map to count the joints of joint_mirror by");
+    J = nets[(size_t)base]->blobs[it->second]->st->shape[1];
+  }
+  if (use[1] && C[1] != 2 * J)
+    throw DcError(DC_ESHAPE, w + "loc_pred has " + std::to_string(C[1]) + " channels for " + std::to_string(J) + " joints (2 per joint)");
+  for (int j = 0; j < J; ++j)
+    if (fm->joint_mirror[j] < 0 || fm->joint_mirror[j] >= J)
+      throw DcError(DC_EINVAL, w + "joint_mirror[" + std::to_string(j) + "] = " + std::to_string(fm->joint_mirror[j]) + " is outside [0, " + std::to_string(J) + ")");
+  for (int j = 0; j < J; ++j)
+    if (fm->joint_mirror[fm->joint_mirror[j]] != j)
+      throw DcError(DC_EINVAL, w + "joint_mirror is not an involution: joint " + std::to_string(j) + " -> " + std::to_string(fm->joint_mirror[j]) + " -> " +
+                                   std::to_string(fm->joint_mirror[fm->joint_mirror[j]]));
+  mp.pi.assign(fm->joint_mirror, fm->joint_mirror + J);
+  if (use[2]) {
+    if (fm->n_edges != n_edges)
+      throw DcError(DC_EINVAL, w + "the mirror table names " + std::to_string(fm->n_edges) + " edges, the call " + std::to_string(n_edges));
+    if (!fm->edges) throw DcError(DC_EINVAL, w + "null edges in the mirror table (next_pred takes part and a member is mirrored)");
+    for (int l = 0; l < 2 * n_edges; ++l)
+      if (fm->edges[l] < 0 || fm->edges[l] >= J)
+        throw DcError(DC_EINVAL, w + "edge " + std::to_string(l / 2) + " of the mirror table names joint " + std::to_string(fm->edges[l]) + ", outside [0, " +
+                                     std::to_string(J) + ")");
+    mp.edge.assign((size_t)n_edges, -1);
+    for (int l = 0; l < n_edges; ++l) {
+      const int a = mp.pi[(size_t)fm->edges[2 * l]], c = mp.pi[(size_t)fm->edges[2 * l + 1]];
+      for (int k = 0; k < n_edges && mp.edge[(size_t)l] < 0; ++k)
+        if (fm->edges[2 * k] == a && fm->edges[2 * k + 1] == c) mp.edge[(size_t)l] = k;
+      if (mp.edge[(size_t)l] < 0)
+        throw DcError(DC_EINVAL, w + "edge " + std::to_string(l) + " (" + std::to_string(fm->edges[2 * l]) + ", " + std::to_string(fm->edges[2 * l + 1]) +
+                                     ") has no mirrored edge (" + std::to_string(a) + ", " + std::to_string(c) + ") among the edges");
+    }
+  }
+  mp.on.resize((size_t)M);
+  for (int m = 0; m < M; ++m) mp.on[(size_t)m] = fm->mirror[m] != 0;
+  mp.image_width = fm->image_width;
+  return mp;
+}
+
 // The launch.  The table on the device (the members' descriptors, then gain and bias [M][channels]) is uploaded when it differs from the
 // one already there — a new pyramid, a reallocated map —, so the usual call is the one kernel and nothing else.
-NetGroup::FusedMaps NetGroup::fuse(const double* scales, int base, const bool use[3], const double* mean, const double* stdev, void* s) {
+NetGroup::FusedMaps NetGroup::fuse(const double* scales, int base, const bool use[3], const double* mean, const double* stdev, void* s,
+                                   const MirrorPlan* mp) {
   const int M = (int)nets.size();
   // the buffers below are shared by every call: work that the previous call left running on ANOTHER stream (an asynchronous
   // fuse_maps on a caller's stream) finishes before this call's stream touches them
@@ -858,6 +914,7 @@ NetGroup::FusedMaps NetGroup::fuse(const double* scales, int base, const bool us
     }
   }
   const int Ctot = C[0] + C[1] + C[2], Hb = mem[(size_t)base].H, Wb = mem[(size_t)base].W;
+  if (mp && !mp->on.empty()) return fuse_mirrored(scales, base, mem, C, NB, ek, mean, stdev, s, *mp);
   // gain and bias, in double, stored as float
   std::vector<float> gb((size_t)2 * M * Ctot);
   float* gain = gb.data();
@@ -896,6 +953,77 @@ NetGroup::FusedMaps NetGroup::fuse(const double* scales, int base, const bool us
   return fm;
 }
 
+// The mirrored launch: the table is the members' descriptors, their FuseFlip records, then gain, bias and source channel [M][channels].
+// An unmirrored member's rows are the ones above with the identity as source; a mirrored member's follow the rule in
+// include/deepcut_hip.h (dc_group_fuse_maps_mirrored).  PARITY UNPINNED BY THE REFERENCE, which mirrors nothing on the pose path.
+NetGroup::FusedMaps NetGroup::fuse_mirrored(const double* scales, int base, const std::vector<FuseMember>& mem, const int C[3], int NB, int ek,
+                                            const double* mean, const double* stdev, void* s, const MirrorPlan& mp) {
+  const int M = (int)nets.size();
+  const int Ctot = C[0] + C[1] + C[2], Hb = mem[(size_t)base].H, Wb = mem[(size_t)base].W, J = (int)mp.pi.size(), E = C[2] / 2;
+  if ((C[0] && C[0] != J) || (C[1] && C[1] != 2 * J) || (C[2] && (int)mp.edge.size() != E))
+    throw DcError(DC_ESHAPE, "fuse_maps: the maps' channels do not match the mirror table's joints and edges");
+  std::vector<FuseFlip> flip((size_t)M);
+  std::vector<float> gb((size_t)2 * M * Ctot);
+  std::vector<int> src((size_t)M * Ctot);
+  float* gain = gb.data();
+  float* bias = gain + (size_t)M * Ctot;
+  auto mu = [&](int l, int k) { return mean ? mean[2 * l + k] : 0.0; };
+  auto sd = [&](int l, int k) { return stdev ? stdev[2 * l + k] : 1.0; };
+  for (int m = 0; m < M; ++m) {
+    const bool on = mp.on[(size_t)m] != 0;
+    const double rho = m == base ? 1.0 : scales[base] / scales[m];
+    flip[(size_t)m] = FuseFlip{on ? (double)(mp.image_width - 1) * scales[m] : 0.0, on ? 1 : 0, 0};
+    float* g = gain + (size_t)m * Ctot;
+    float* bi = bias + (size_t)m * Ctot;
+    int* sc = src.data() + (size_t)m * Ctot;
+    for (int j = 0; j < C[0]; ++j) g[j] = 1.f, bi[j] = 0.f, sc[j] = on ? mp.pi[(size_t)j] : j;
+    for (int i = 0; i < C[1]; ++i) {
+      const int j = i / 2, k = i % 2;
+      g[C[0] + i] = (float)(on && k == 0 ? -rho : rho), bi[C[0] + i] = 0.f, sc[C[0] + i] = on ? 2 * mp.pi[(size_t)j] + k : i;
+    }
+    for (int i = 0; i < C[2]; ++i) {
+      const int l = i / 2, k = i % 2, at = C[0] + C[1] + i;
+      if (!on) {
+        g[at] = (float)rho, bi[at] = (float)((rho - 1.0) * mu(l, k) / sd(l, k)), sc[at] = i;
+        continue;
+      }
+      const int lp = mp.edge[(size_t)l];
+      sc[at] = 2 * lp + k;
+      if (k == 0) {
+        g[at] = (float)(-rho * sd(lp, 0) / sd(l, 0));
+        bi[at] = (float)(-(rho * mu(lp, 0) + mu(l, 0)) / sd(l, 0));
+      } else {
+        g[at] = (float)(rho * sd(lp, 1) / sd(l, 1));
+        bi[at] = (float)((rho * mu(lp, 1) - mu(l, 1)) / sd(l, 1));
+      }
+    }
+  }
+  const size_t mem_b = (size_t)M * sizeof(FuseMember), flip_b = (size_t)M * sizeof(FuseFlip), gb_b = gb.size() * sizeof(float),
+               src_b = src.size() * sizeof(int);
+  std::vector<unsigned char> table(mem_b + flip_b + gb_b + src_b);
+  std::memcpy(table.data(), mem.data(), mem_b);
+  std::memcpy(table.data() + mem_b, flip.data(), flip_b);
+  std::memcpy(table.data() + mem_b + flip_b, gb.data(), gb_b);
+  std::memcpy(table.data() + mem_b + flip_b + gb_b, src.data(), src_b);
+  unsigned char* d_table = (unsigned char*)fuse_table_.get(table.size());
+  if (table != fuse_table_host_) {
+    fuse_table_host_.clear();  // (not what the device holds any more, should the upload throw)
+    dev_upload(d_table, table.data(), table.size(), s);
+    fuse_table_host_ = std::move(table);
+  }
+  float* out = (float*)fused_.get((size_t)NB * Hb * Wb * Ctot * sizeof(float));
+  const float* d_gain = (const float*)(d_table + mem_b + flip_b);
+  KCHECK(launch_fuse_maps_mirrored((const FuseMember*)d_table, (const FuseFlip*)(d_table + mem_b), d_gain, d_gain + (size_t)M * Ctot,
+                                   (const int*)(d_table + mem_b + flip_b + gb_b), M, ek, NB, Hb, Wb, C, out, s));
+  FusedMaps fm{};
+  int c0 = 0;
+  for (int k = 0; k < 3; ++k) {
+    fm.map[k] = Net::MapRef{out, Ctot, c0, 4, kElemF32, NB, C[k], Hb, Wb};
+    c0 += C[k];
+  }
+  return fm;
+}
+
 void NetGroup::fuse_done(void* s) {
   if (!fuse_event_) {
     hipEvent_t ev;
@@ -907,18 +1035,19 @@ void NetGroup::fuse_done(void* s) {
 }
 
 void NetGroup::fuse_maps(const double* scales, int base, int n_edges, const double* mean, const double* stdev, float* prob, float* loc,
-                         float* next, bool is_device, void* user_stream) {
+                         float* next, bool is_device, void* user_stream, const FuseMirror* fm_in) {
   float* const dst[3] = {prob, loc, next};
   const bool use[3] = {prob != nullptr, loc != nullptr, next != nullptr};
   int C[3], NB;
   check_fuse("fuse_maps", scales, base, use, n_edges, mean, stdev, C, NB);
   if (!use[0] && !use[1] && !use[2]) return;
+  const MirrorPlan mp = check_mirror("fuse_maps", fm_in, base, use, n_edges, C);
   if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "fuse_maps() in CPU mode: libdeepcut_hip provides the MI355X path only");
   const bool own_async = user_stream == (void*)-1;
   if (own_async) user_stream = nullptr;
   nets[0]->ensure_device();
   void* s = user_stream ? user_stream : stream();
-  const FusedMaps fm = fuse(scales, base, use, mean, stdev, s);
+  const FusedMaps fm = fuse(scales, base, use, mean, stdev, s, &mp);
   size_t total = 0;
   for (int k = 0; k < 3; ++k) total += (size_t)fm.map[k].NB * fm.map[k].C * fm.map[k].H * fm.map[k].W;
   float* stage = is_device ? nullptr : (float*)fuse_stage_.get(total * sizeof(float));
@@ -937,16 +1066,17 @@ void NetGroup::fuse_maps(const double* scales, int base, int n_edges, const doub
   if (!(is_device && (user_stream || own_async))) HIPCHECK(hipStreamSynchronize((hipStream_t)s));
 }
 
-void NetGroup::detect_parts(const double* scales, int base, float thr, int radius, int max_det, int* counts, double* dets) {
+void NetGroup::detect_parts(const double* scales, int base, float thr, int radius, int max_det, int* counts, double* dets, const FuseMirror* fm_in) {
   const bool use[3] = {true, true, false};
   int C[3], NB;
   check_fuse("detect_parts", scales, base, use, 0, nullptr, nullptr, C, NB);
+  const MirrorPlan mp = check_mirror("detect_parts", fm_in, base, use, 0, C);
   if (!(thr >= 0.f) || radius < 0 || radius > 64 || max_det < 1 || max_det > 4096)
     throw DcError(DC_EINVAL, "detect_parts: scale > 0, threshold >= 0, 0 <= radius <= 64, 1 <= max_det <= 4096");
   if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "detect_parts() in CPU mode");
   nets[0]->ensure_device();
   void* s = stream();
-  const FusedMaps fm = fuse(scales, base, use, nullptr, nullptr, s);
+  const FusedMaps fm = fuse(scales, base, use, nullptr, nullptr, s, &mp);
   const Net::MapRef &P = fm.map[0], &L = fm.map[1];
   if (L.C != 2 * P.C) throw DcError(DC_ESHAPE, "detect_parts: loc_pred must have 2 channels per joint and the score map's size");
   const int lists = P.NB * P.C;
@@ -965,7 +1095,8 @@ void NetGroup::detect_parts(const double* scales, int base, float thr, int radiu
 }
 
 void NetGroup::assemble_people(const double* scales, int base, const Net::AssembleParams& p, int n_edges, const int* edges, const double* mean,
-                               const double* stdev, const int* joint_order, int* n_people, double* people, int* cand, double* cost) {
+                               const double* stdev, const int* joint_order, int* n_people, double* people, int* cand, double* cost,
+                               const FuseMirror* fm_in) {
   const bool use[3] = {true, true, true};
   int C[3], NB;
   check_scales("assemble_people", scales, base);  // first: the assembly runs at scales[base]
@@ -978,10 +1109,11 @@ void NetGroup::assemble_people(const double* scales, int base, const Net::Assemb
   if (pshape.size() != 4) throw DcError(DC_ESHAPE, "'prob' is not a 4-D map");
   const std::vector<int> table = Net::check_assemble_graph(q, pshape[1], n_edges, edges, mean, stdev, joint_order);
   check_fuse("assemble_people", scales, base, use, n_edges, mean, stdev, C, NB);
+  const MirrorPlan mp = check_mirror("assemble_people", fm_in, base, use, n_edges, C);
   if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "assemble_people() in CPU mode");
   nets[0]->ensure_device();
   void* s = stream();
-  const FusedMaps fm = fuse(scales, base, use, mean, stdev, s);
+  const FusedMaps fm = fuse(scales, base, use, mean, stdev, s, &mp);
   Net::assemble_maps(fm.map[0], fm.map[1], fm.map[2], q, table, n_edges, mean, stdev, [this](size_t bytes) { return people_scratch_.get(bytes); }, s,
                      n_people, people, cand, cost);
   fuse_done(s);

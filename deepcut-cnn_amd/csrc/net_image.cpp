@@ -92,7 +92,7 @@ void Net::forward_images(const unsigned char* bgr, int n, int h, int w, double s
   if (!(is_device && (user_stream || own_async))) HIPCHECK(hipStreamSynchronize((hipStream_t)s));
 }
 
-void Net::prep_images(const unsigned char* bgr, int n, int h, int w, double scale, bool is_device, void* s) {
+void Net::prep_images(const unsigned char* bgr, int n, int h, int w, double scale, bool is_device, void* s, bool mirror) {
   if (n <= 0 || h <= 0 || w <= 0 || !(scale > 0)) throw DcError(DC_EINVAL, "forward_images: n, height, width and scale must be positive");
   int out_h, out_w, new_h, new_w;
   image_canvas_size(h, w, scale, out_h, out_w, new_h, new_w);
@@ -124,6 +124,7 @@ void Net::prep_images(const unsigned char* bgr, int n, int h, int w, double scal
   q.out_h = out_h, q.out_w = out_w, q.use_h = use_h, q.use_w = use_w;
   q.dst = in.dev, q.dst_ekind = in.ekind, q.dst_cp = in.cp();
   q.mean[0] = 104.f, q.mean[1] = 117.f, q.mean[2] = 123.f;  // _MEAN, estimate_pose.py:26
+  q.mirror = mirror ? 1 : 0;
   std::shared_ptr<ResampleTable> hold_y, hold_x;  // the tables outlive a cache flush until the launches are enqueued
   if (need_y) {
     hold_y = resample_table(ph, new_h);

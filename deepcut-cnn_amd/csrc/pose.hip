@@ -283,6 +283,75 @@ int launch_fuse_maps(const FuseMember* members, const float* gain, const float* 
   });
 }
 
+// ---- the same with mirrored members (the rule: include/deepcut_hip.h, dc_group_fuse_maps_mirrored; this project's own) -----------------
+// A member that saw the image flipped left to right is sampled at the reflected position, and lane ch reads the member's channel
+// src[m][ch] of the same map (left and right joints swapped, the regression edge replaced by its mirror image), with the sign change of
+// the x components folded into the gain / bias table.  Same shape as fuse_maps_kernel: one workgroup per base cell, the corner record of
+// every member computed once into LDS, lanes along the channels.  A corner read is no longer one ascending run of the wave but a
+// permutation of it INSIDE the same map, i.e. inside the same cache lines (14 / 28 / 364 channels of 2 or 4 bytes: 1 + 1 + 6 to 12 lines
+// of 128 bytes per corner either way), and the store stays a contiguous run.  Kept beside the unmirrored kernel, which a group
+// without a mirrored member still launches.
+__device__ __forceinline__ double fuse_mirrored_u(double ws, int c, double q) {
+#pragma clang fp contract(off)  // the rule's own order: a product, two differences, a quotient
+  const double a = (double)(8 * c + 4) * q;
+  const double d = ws - a;
+  return (d - 4.0) / 8.0;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void fuse_maps_mirror_kernel(const FuseMember* __restrict__ members, const FuseFlip* __restrict__ flip,
+                                                               const float* __restrict__ gain, const float* __restrict__ bias,
+                                                               const int* __restrict__ src, int M, int Hb, int Wb, int C0, int C1, int Ctot,
+                                                               float inv_m, float* __restrict__ out) {
+  extern __shared__ FuseCorner fuse_lds[];  // [M]
+  const int cell = blockIdx.x, t = threadIdx.x;
+  const int b = cell / (Hb * Wb), rc = cell - b * (Hb * Wb), r = rc / Wb, c = rc - r * Wb;
+  for (int m = t; m < M; m += 256) {
+    const FuseMember& mem = members[m];
+    const double q = mem.q;
+    double u = flip[m].on ? fuse_mirrored_u(flip[m].ws, c, q) : ((double)(8 * c + 4) * q - 4.0) / 8.0;
+    double v = ((double)(8 * r + 4) * q - 4.0) / 8.0;
+    u = fmin(fmax(u, 0.0), (double)(mem.W - 1));
+    v = fmin(fmax(v, 0.0), (double)(mem.H - 1));
+    const int x0 = (int)floor(u), y0 = (int)floor(v);
+    const int x1 = min(x0 + 1, mem.W - 1), y1 = min(y0 + 1, mem.H - 1);
+    FuseCorner k;
+    k.i00 = y0 * mem.W + x0, k.i01 = y0 * mem.W + x1, k.i10 = y1 * mem.W + x0, k.i11 = y1 * mem.W + x1;
+    k.fx = (float)(u - (double)x0), k.fy = (float)(v - (double)y0);
+    fuse_lds[m] = k;
+  }
+  __syncthreads();
+  float* o = out + (long)cell * Ctot;
+  for (int ch = t; ch < Ctot; ch += 256) {
+    const int k = ch < C0 ? 0 : ch < C1 ? 1 : 2;
+    float acc = 0.f;
+    for (int m = 0; m < M; ++m) {
+      const FuseMember& mem = members[m];
+      const FuseCorner kc = fuse_lds[m];
+      const long cp = mem.cp[k];
+      const T* p = (const T*)mem.ptr[k] + (long)b * mem.H * mem.W * cp + mem.c0[k] + src[(long)m * Ctot + ch];
+      const float a00 = (float)p[kc.i00 * cp], a01 = (float)p[kc.i01 * cp], a10 = (float)p[kc.i10 * cp], a11 = (float)p[kc.i11 * cp];
+      const float val = (1.f - kc.fy) * ((1.f - kc.fx) * a00 + kc.fx * a01) + kc.fy * ((1.f - kc.fx) * a10 + kc.fx * a11);
+      acc += val * gain[(long)m * Ctot + ch] + bias[(long)m * Ctot + ch];
+    }
+    o[ch] = acc * inv_m;
+  }
+}
+
+int launch_fuse_maps_mirrored(const FuseMember* members, const FuseFlip* flip, const float* gain, const float* bias, const int* src, int M,
+                              int ekind, int NB, int Hb, int Wb, const int C[3], float* out, void* stream) {
+  const int Ctot = C[0] + C[1] + C[2];
+  const long cells = (long)NB * Hb * Wb;
+  if (cells <= 0 || Ctot <= 0) return 0;
+  if (M < 1 || M > 1024 || cells > 0x7fffffffL || C[0] < 0 || C[1] < 0 || C[2] < 0 || !flip || !src) return (int)hipErrorInvalidValue;
+  return dc_by_kind(ekind, [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    hipLaunchKernelGGL(fuse_maps_mirror_kernel<T>, dim3((unsigned)cells), dim3(256), (size_t)M * sizeof(FuseCorner), (hipStream_t)stream, members,
+                       flip, gain, bias, src, M, Hb, Wb, C[0], C[0] + C[1], Ctot, 1.f / (float)M, out);
+    return (int)hipGetLastError();
+  });
+}
+
 int launch_part_select(const void* prob, int pcp, int pc0, const void* loc, int lcp, int lc0, int ekind, int NB, int H, int W, int J, float thr,
                        int radius, double scale, int max_det, unsigned long long* spill, int* counts, double* out, void* stream) {
   if (NB * J <= 0) return 0;

@@ -41,6 +41,11 @@ class AssembleParams(C.Structure):
                 ("seed_threshold", C.c_float), ("max_people", C.c_int), ("min_joints", C.c_int)]
 
 
+class FuseMirror(C.Structure):
+    """dc_fuse_mirror (include/deepcut_hip.h)."""
+    _fields_ = [("mirror", C.c_void_p), ("image_width", C.c_int), ("joint_mirror", C.c_void_p), ("n_edges", C.c_int), ("edges", C.c_void_p)]
+
+
 MAX_ASSEMBLE_DET, MAX_ASSEMBLE_PEOPLE = 64, 256  # dc_net_assemble_people's limits
 
 
@@ -137,6 +142,12 @@ def _load():
         "dc_group_fuse_maps": (ci, [vp, vp, ci, ci, vp, vp, vp, vp, vp, ci, vp]),
         "dc_group_detect_parts": (ci, [vp, vp, ci, C.c_float, ci, ci, vp, vp]),
         "dc_group_assemble_people": (ci, [vp, vp, ci, C.POINTER(AssembleParams), ci, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "dc_group_forward_images_mirrored": (ci, [vp, C.POINTER(vp), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_double), vp, ci,
+                                                  C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]),
+        "dc_group_fuse_maps_mirrored": (ci, [vp, vp, ci, C.POINTER(FuseMirror), ci, vp, vp, vp, vp, vp, ci, vp]),
+        "dc_group_detect_parts_mirrored": (ci, [vp, vp, ci, C.POINTER(FuseMirror), C.c_float, ci, ci, vp, vp]),
+        "dc_group_assemble_people_mirrored": (ci, [vp, vp, ci, C.POINTER(FuseMirror), C.POINTER(AssembleParams), ci, vp, vp, vp, vp, vp, vp, vp,
+                                                   vp]),
         "dc_group_plan_text": (cp, [vp]),
         "dc_group_profile_text": (cp, [vp, ci]),
         "dc_group_tune_report": (cp, [vp]),
@@ -1118,10 +1129,19 @@ class NetGroup(object):
                                            col("loc_pred"), col("next_pred"), None))
         return outs
 
-    def forward_images(self, images, scales, want=("prob", "loc_pred"), pose=True):
+    def forward_images(self, images, scales, want=("prob", "loc_pred"), pose=True, mirror=None):
         """images: ONE uint8 [n,H,W,3] BGR host array (every member sees it, member c at scales[c] — the demo's pyramid), or a
-        list of one array per member.  -> one dict per member with the requested maps and "pose" [n,5,J]."""
+        list of one array per member.  -> one dict per member with the requested maps and "pose" [n,5,J].
+        mirror: one 0/1 per member; a marked member sees its images flipped left to right, flipped by the pre-processing on the device
+        (dc_group_forward_images_mirrored), and returns its RAW maps, in the flipped image's frame (`fuse_maps(mirror=...)` undoes the
+        flip).  No pose is decoded then: a mirrored member's own pose would be in flipped coordinates, so pose=True is refused."""
         k = len(self.nets)
+        if mirror is not None:
+            mirror = [int(bool(v)) for v in mirror]
+            if len(mirror) != k:
+                raise ValueError("one mirror flag per group member: %d flags for %d members" % (len(mirror), k))
+            if pose:
+                raise ValueError("forward_images(mirror=...) decodes no pose (a mirrored member's would be in flipped coordinates): pass pose=False")
         if isinstance(images, np.ndarray):
             images = [images] * k
         xs = [np.ascontiguousarray(x, dtype=np.uint8) for x in images]
@@ -1142,6 +1162,12 @@ class NetGroup(object):
         def col(key):
             return self._ptrs([o[key].ctypes.data if key in o else None for o in outs], k)
 
+        if mirror is not None:
+            _check(_lib.dc_group_forward_images_mirrored(self._h, self._ptrs([x.ctypes.data for x in xs], k), self._ints([x.shape[0] for x in xs]),
+                                                         self._ints([x.shape[1] for x in xs]), self._ints([x.shape[2] for x in xs]),
+                                                         (C.c_double * k)(*[float(s) for s in scales]), self._ints(mirror), 0, col("prob"),
+                                                         col("loc_pred"), col("next_pred"), None))
+            return outs
         _check(_lib.dc_group_forward_images(self._h, self._ptrs([x.ctypes.data for x in xs], k), self._ints([x.shape[0] for x in xs]),
                                             self._ints([x.shape[1] for x in xs]), self._ints([x.shape[2] for x in xs]),
                                             (C.c_double * k)(*[float(s) for s in scales]), 0, col("prob"), col("loc_pred"), col("next_pred"),
@@ -1207,12 +1233,33 @@ class NetGroup(object):
             raise ValueError("one scale per group member: %d scales for %d members" % (sc.shape[0], len(self.nets)))
         return sc, int(base)
 
-    def fuse_maps(self, scales, base=0, mean=None, std=None, want=("prob", "loc_pred", "next_pred")):
+    def _mirror(self, mirror, image_width, joint_mirror, edges):
+        """-> (FuseMirror, the arrays it points into) for the dc_group_*_mirrored entries.  Only the lengths are checked here; what the
+        values must be (a positive width, an involution, an unmirrored base, mirrored edges present) is the library's to say."""
+        flags = np.ascontiguousarray([int(bool(v)) for v in mirror], dtype=np.int32)
+        if flags.shape[0] != len(self.nets):
+            raise ValueError("one mirror flag per group member: %d flags for %d members" % (flags.shape[0], len(self.nets)))
+        pi = None if joint_mirror is None else np.ascontiguousarray(joint_mirror, dtype=np.int32).reshape(-1)
+        j = self.nets[0].blobs["prob"].shape[1]
+        if pi is not None and pi.shape[0] != j:
+            raise ValueError("joint_mirror must name one joint per joint: %d entries for %d joints" % (pi.shape[0], j))
+        e = None if edges is None else np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 2)
+        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        fm = FuseMirror(ptr(flags), int(image_width or 0), ptr(pi), 0 if e is None else e.shape[0], ptr(e))
+        return fm, (flags, pi, e)
+
+    def fuse_maps(self, scales, base=0, mean=None, std=None, want=("prob", "loc_pred", "next_pred"), mirror=None, image_width=None,
+                  joint_mirror=None, edges=None):
         """The maps of the members' last forwards (member c holds the same images at scales[c]) fused on member `base`'s grid, on the
         device in one launch (dc_group_fuse_maps; the rule is in include/deepcut_hip.h and is this project's own: the reference stops at
         the maps).  Every member's map is sampled bilinearly at the base cells' image points, loc_pred and next_pred are converted
         into the base member's units (mean / std: the [E, 2] statistics of next_pred, None = 0 / 1), and the members are averaged.
-        -> dict of float32 NCHW arrays on the base grid, whatever the members' element type."""
+        -> dict of float32 NCHW arrays on the base grid, whatever the members' element type.
+        mirror: one 0/1 per member, marking the members that saw the image flipped left to right (`forward_images(mirror=...)`); then
+        image_width (the pixels of the unscaled image), joint_mirror (the joint every joint becomes in the mirror, e.g.
+        pose.MIRROR_MPII14) and — when next_pred is fused — edges ([E, 2], as assemble_people) are needed: the mirrored members are
+        sampled at the reflected position, their channels permuted and the x components negated, still in the one launch
+        (dc_group_fuse_maps_mirrored).  None: today's call."""
         sc, base = self._scales(scales, base)
         want = [k for k in ("prob", "loc_pred", "next_pred") if k in want]
         ref = self.nets[base if 0 <= base < len(self.nets) else 0]
@@ -1229,26 +1276,39 @@ class NetGroup(object):
         hw = ref.blobs["prob"].shape[2:]
         out = {k: np.empty(tuple(ref.blobs[k].shape[:2]) + tuple(hw), np.float32) for k in want}
         ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        if mirror is not None:
+            fm, _keep = self._mirror(mirror, image_width, joint_mirror, edges if "next_pred" in want else None)
+            _check(_lib.dc_group_fuse_maps_mirrored(self._h, ptr(sc), base, C.byref(fm), e, ptr(stats[0]), ptr(stats[1]), ptr(out.get("prob")),
+                                                    ptr(out.get("loc_pred")), ptr(out.get("next_pred")), 0, None))
+            return out
         _check(_lib.dc_group_fuse_maps(self._h, ptr(sc), base, e, ptr(stats[0]), ptr(stats[1]), ptr(out.get("prob")), ptr(out.get("loc_pred")),
                                        ptr(out.get("next_pred")), 0, None))
         return out
 
-    def detect_parts(self, scales, base=0, threshold=0.1, radius=1, max_det=32):
+    def detect_parts(self, scales, base=0, threshold=0.1, radius=1, max_det=32, mirror=None, image_width=None, joint_mirror=None):
         """Net.detect_parts on the fused `prob` and `loc_pred` of the members' last forwards, at scales[base] (dc_group_detect_parts).
-        -> (counts int32 [n, J], dets float64 [n, J, max_det, 5] = x, y, score, cell row, cell column on the base member's grid)."""
+        -> (counts int32 [n, J], dets float64 [n, J, max_det, 5] = x, y, score, cell row, cell column on the base member's grid).
+        mirror / image_width / joint_mirror: as `fuse_maps` (dc_group_detect_parts_mirrored)."""
         sc, base = self._scales(scales, base)
         n, j = self.nets[0].blobs["prob"].shape[:2]
         counts = np.zeros((n, j), np.int32)
         dets = np.zeros((n, j, max(int(max_det), 0), 5), np.float64)
+        if mirror is not None:
+            fm, _keep = self._mirror(mirror, image_width, joint_mirror, None)
+            _check(_lib.dc_group_detect_parts_mirrored(self._h, sc.ctypes.data_as(C.c_void_p), base, C.byref(fm), float(threshold), int(radius),
+                                                       int(max_det), counts.ctypes.data_as(C.c_void_p), dets.ctypes.data_as(C.c_void_p)))
+            return counts, dets
         _check(_lib.dc_group_detect_parts(self._h, sc.ctypes.data_as(C.c_void_p), base, float(threshold), int(radius), int(max_det),
                                           counts.ctypes.data_as(C.c_void_p), dets.ctypes.data_as(C.c_void_p)))
         return counts, dets
 
     def assemble_people(self, scales, base=0, threshold=0.1, radius=1, max_det=16, edges=None, mean=None, std=None, max_cost=32.0,
-                        seed_threshold=0.5, max_people=32, min_joints=1, joint_order=None, return_cost=False):
+                        seed_threshold=0.5, max_people=32, min_joints=1, joint_order=None, return_cost=False, mirror=None, image_width=None,
+                        joint_mirror=None):
         """Net.assemble_people on the fused maps of a pyramid (dc_group_assemble_people): the three maps of the members' last forwards
         are fused on member `base`'s grid (`fuse_maps`), then the candidates, the pair costs and the greedy assembly run on them at
-        scales[base], all on the device with no host round trip in between.  The other arguments and the result are Net.assemble_people's."""
+        scales[base], all on the device with no host round trip in between.  The other arguments and the result are Net.assemble_people's.
+        mirror / image_width / joint_mirror: as `fuse_maps`, with `edges` as the regression edges (dc_group_assemble_people_mirrored)."""
         if edges is None:
             raise ValueError("assemble_people needs the regression edges (deepcut_tools.read_pair_stats)")
         sc, base = self._scales(scales, base)
@@ -1263,8 +1323,13 @@ class NetGroup(object):
         cand = np.zeros((n, p, j), np.int32)
         cost = np.zeros((n, j, j, md, md), np.float64) if return_cost else None
         ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        _check(_lib.dc_group_assemble_people(self._h, ptr(sc), base, C.byref(q), e.shape[0], ptr(e), ptr(m), ptr(s), ptr(order), ptr(count),
-                                             ptr(people), ptr(cand), ptr(cost)))
+        if mirror is not None:
+            fm, _keep = self._mirror(mirror, image_width, joint_mirror, e)
+            _check(_lib.dc_group_assemble_people_mirrored(self._h, ptr(sc), base, C.byref(fm), C.byref(q), e.shape[0], ptr(e), ptr(m), ptr(s),
+                                                          ptr(order), ptr(count), ptr(people), ptr(cand), ptr(cost)))
+        else:
+            _check(_lib.dc_group_assemble_people(self._h, ptr(sc), base, C.byref(q), e.shape[0], ptr(e), ptr(m), ptr(s), ptr(order), ptr(count),
+                                                 ptr(people), ptr(cand), ptr(cost)))
         out = []
         for b in range(n):
             d = {"people": people[b, :count[b]].copy(), "cand": cand[b, :count[b]].copy()}

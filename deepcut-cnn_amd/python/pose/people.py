@@ -3,11 +3,17 @@ assembly on the device (`caffe.Net.assemble_people`); over an image pyramid, one
 fused on the device and assembled there (`caffe.NetGroup.assemble_people`).
 
 NO REFERENCE COUNTERPART: the reference's python/pose stops at `estimate_pose` (one person) and its repository has no consumer of
-`next_pred`.  The grouping rule and the multi-scale fusion rule are this project's own (include/deepcut_hip.h, dc_net_assemble_people and
-dc_group_fuse_maps)."""
+`next_pred`.  The grouping rule, the multi-scale fusion rule and its mirrored form (flip=True) are this project's own
+(include/deepcut_hip.h, dc_net_assemble_people, dc_group_fuse_maps and dc_group_fuse_maps_mirrored); the reference mirrors nothing on
+the pose path, so their parity is unpinned by the reference."""
 import numpy as _np
 
 _MODEL = {}
+
+# The joint every joint becomes when the image is flipped left to right, in the MPII 14-joint order the DeeperCut models are trained on
+# (right ankle, knee, hip; left hip, knee, ankle; right wrist, elbow, shoulder; left shoulder, elbow, wrist; upper neck; head top).  The
+# reference's Python names no joints, so this table is the caller's to override (`joint_mirror=`) for a model with another joint order.
+MIRROR_MPII14 = (5, 4, 3, 2, 1, 0, 11, 10, 9, 8, 7, 6, 12, 13)
 
 
 def _get_model(model_def, model_bin):
@@ -25,7 +31,21 @@ def _base_scale(scales):
     return min(range(len(scales)), key=lambda i: (abs(float(scales[i]) - 1.0), i))
 
 
-def estimate_people(image, model_def, model_bin, stats, scale=1.0, net=None, scales=None, base=None, **assembly):
+def _check_joint_mirror(joint_mirror):
+    """-> the table as a list of ints; ValueError unless it is an involution of 0..J-1 (needs no net and no device)."""
+    if joint_mirror is None:
+        raise ValueError("flip=True needs joint_mirror (pose.MIRROR_MPII14 for the DeeperCut models)")
+    pi = [int(v) for v in joint_mirror]
+    for j, v in enumerate(pi):
+        if not 0 <= v < len(pi):
+            raise ValueError("joint_mirror[%d] = %d is outside [0, %d)" % (j, v, len(pi)))
+        if pi[v] != j:
+            raise ValueError("joint_mirror is not an involution: joint %d -> %d -> %d" % (j, v, pi[v]))
+    return pi
+
+
+def estimate_people(image, model_def, model_bin, stats, scale=1.0, net=None, scales=None, base=None, flip=False, joint_mirror=MIRROR_MPII14,
+                    **assembly):
     """image: HxWx3 BGR uint8.  stats: the path of the model's pair-statistics file (deepcut_tools.read_pair_stats) or the
     (edges, mean, std) triple itself.  Runs the image entry (`Net.forward_images`: pre-processing on the device) with all three
     outputs computed, then `Net.assemble_people(scale=scale, edges=..., mean=..., std=..., **assembly)`; `assembly` takes its other
@@ -39,9 +59,19 @@ def estimate_people(image, model_def, model_bin, stats, scale=1.0, net=None, sca
     must then be left at 1.0.  The clones are the ones `estimate_pose` keeps with the net for its own pyramids; they are set to compute
     all three outputs here (after the net itself has been accepted: a net that leaves `next_pred` out is refused before anything is
     touched), and `estimate_pose` on its own cached net narrows its clones again — alternating the two entries on ONE net re-lowers the
-    clones' plans at every switch, so give each entry a net of its own where both are in use."""
+    clones' plans at every switch, so give each entry a net of its own where both are in use.
+    flip: mirror test-time augmentation — every scale is run on the image and on its left-right mirror and all the maps are fused: a single
+    `scale` becomes a group of two, a pyramid of k scales a group of 2k (the k plain members, then their mirrors), still ONE grouped
+    forward (the flip is part of the device pre-processing) and ONE `NetGroup.assemble_people`.  joint_mirror: the joint every joint
+    becomes in the mirror (MIRROR_MPII14 by default: the caller's to override for another joint order); `stats` must hold, for every edge
+    (a, c), the edge (joint_mirror[a], joint_mirror[c]).  The base stays a plain member: None = the plain scale nearest 1.0."""
     if scales is not None and float(scale) != 1.0:
         raise ValueError("estimate_people takes scale (one forward) or scales (a pyramid), not both: scale=%r, scales=%r" % (scale, scales))
+    if flip:
+        joint_mirror = _check_joint_mirror(joint_mirror)
+        plain = len(scales) if scales is not None else 1
+        if base is not None and not 0 <= int(base) < plain:
+            raise ValueError("base %r must name one of the %d plain members: the mirrored members come after them and cannot be the base" % (base, plain))
     if isinstance(stats, (str, bytes)) or hasattr(stats, "__fspath__"):
         from deepcut_tools import read_pair_stats
 
@@ -55,19 +85,25 @@ def estimate_people(image, model_def, model_bin, stats, scale=1.0, net=None, sca
     image = _np.asarray(image)
     if image.dtype != _np.uint8 or image.ndim != 3 or image.shape[2] != 3:
         raise ValueError("image must be uint8 [H,W,3] (BGR)")
-    if scales is not None:
+    if scales is not None or flip:
         from .estimate_pose import _scale_group
 
-        scales = [float(v) for v in scales]
+        scales = [float(v) for v in scales] if scales is not None else [float(scale)]
         if not scales:
             raise ValueError("scales must name at least one scale")
+        mirrored = {}
+        if flip:
+            if base is None:
+                base = _base_scale(scales)
+            mirrored = dict(mirror=[0] * len(scales) + [1] * len(scales), image_width=image.shape[1], joint_mirror=joint_mirror)
+            scales = scales + scales
         grp = _scale_group(net, len(scales))
         for m in grp.nets[1:]:  # the clones kept with the net are this module's to set: all three outputs, like the net itself
             if sorted(m.wanted_outputs) != sorted(net.wanted_outputs):
                 m.set_outputs(None)
-        grp.forward_images(image, scales, want=(), pose=False)
+        grp.forward_images(image, scales, want=(), pose=False, mirror=mirrored.get("mirror"))
         return grp.assemble_people(scales, _base_scale(scales) if base is None else int(base), edges=edges, mean=mean, std=std,
-                                   **assembly)[0]["people"]
+                                   **dict(assembly, **mirrored))[0]["people"]
     net.forward_images(image, scale, want=(), pose=False)
     return net.assemble_people(scale=scale, edges=edges, mean=mean, std=std, **assembly)[0]["people"]
 

@@ -503,6 +503,63 @@ int dc_group_detect_parts(dc_group* group, const double* scales, int base, float
 int dc_group_assemble_people(dc_group* group, const double* scales, int base, const dc_assemble_params* p, int n_edges, const int* edges,
                              const double* mean, const double* stdev, const int* joint_order, int* n_people, double* people, int* cand,
                              double* cost);
+/* ---- mirror test-time augmentation for the bottom-up entry: mirrored members fused on the device --------------------------------------
+ * NO REFERENCE COUNTERPART: the reference stops at the maps and mirrors nothing on the pose path.  The rule below extends the
+ * fusion rule above, is this project's own, and its parity is unpinned by the reference.
+ *
+ * dc_group_forward_images_mirrored: dc_group_forward_images with mirror[c] != 0 marking the members that see their images flipped left
+ *     to right.  Such a member's pre-processing reads source column w - 1 - x wherever it would read column x of the unpadded image (the
+ *     replicate padding therefore repeats the flipped image's last column, which is original column 0); the resample, the mean and the
+ *     canvas are unchanged, so its network input is, bit for bit, what dc_group_forward_images makes of the host-flipped image, for
+ *     float32, float16 and bfloat16 nets, with and without a horizontal resample pass.  The maps returned for a mirrored member are that
+ *     member's RAW maps, in the flipped image's frame: columns run right to left, left and right joints are swapped and the x components
+ *     of loc_pred and next_pred have the other sign — dc_group_fuse_maps_mirrored undoes all of it.  There is no `pose` argument: a
+ *     mirrored member's own decoded pose would be in flipped coordinates.  mirror NULL or all zeros enqueues exactly what
+ *     dc_group_forward_images enqueues.
+ *
+ * dc_fuse_mirror: mirror[m] != 0 marks the members that saw the image flipped; image_width = w, the pixels of the unscaled image every
+ *     member saw; joint_mirror = pi, the joint that joint j becomes in the mirror (an involution: pi[pi[j]] == j; the table is the
+ *     model's: the caller supplies it); edges [n_edges][2] = the 0-based (joint, next joint) of every regression edge, as
+ *     dc_net_assemble_people, needed whenever next_pred takes part and a member is mirrored.
+ * For a member with mirror[m] == 0 everything is as in dc_group_fuse_maps.  The base member must be unmirrored.  For a mirrored member
+ * m, with q = scales[m] / s_b and rho = s_b / scales[m] as there:
+ *  Sample position of base cell (r, c): v as there; u = (((w - 1) scales[m] - (8c + 4) q) - 4) / 8 in double, in this order (a cell
+ *     stands for image point (8c + 4) / s, and image column x of the flipped image is column w - 1 - x of the original).  Clamp, floor,
+ *     corners and the float weights as there.
+ *  Source channel and conversion, out_m = val(source channel) * gain + bias:
+ *     prob j          reads channel pi[j],         gain 1
+ *     loc_pred 2j     reads channel 2 pi[j],       gain -rho
+ *     loc_pred 2j + 1 reads channel 2 pi[j] + 1,   gain rho
+ *     next_pred of edge l = (a, c) reads edge l', the lowest-index edge equal to (pi[a], pi[c]):
+ *       channel 2l     reads 2l',     gain -rho std[l'][0] / std[l][0], bias -(rho mean[l'][0] + mean[l][0]) / std[l][0]
+ *       channel 2l + 1 reads 2l' + 1, gain  rho std[l'][1] / std[l][1], bias  (rho mean[l'][1] - mean[l][1]) / std[l][1]
+ *     (with l' = l and no sign change these are dc_group_fuse_maps' (rho, (rho - 1) mean / std)).  Gain and bias are computed on the host in
+ *     double and uploaded as float; a third table of the same size holds the source channel, as int.
+ *  Fusion: unchanged — the ascending sum over the members, times 1 / M, in float32; nothing is atomic, same inputs give the same bits.
+ * One launch fuses every map, member and image, as before.  A group without a mirrored member (fm NULL, fm->mirror NULL or all zeros)
+ * takes dc_group_fuse_maps' own path and kernel: the results are bit-identical to the unmirrored calls and nothing else of fm is read.
+ * dc_group_detect_parts_mirrored / dc_group_assemble_people_mirrored: dc_group_detect_parts / dc_group_assemble_people on maps fused so.
+ * Errors, raised before any device work and naming what is wrong: everything the unmirrored calls refuse, in the same way; then, with a
+ *     mirrored member, DC_EINVAL for image_width <= 0, a mirrored base member, joint_mirror NULL, out of range or not an involution, and
+ *     — only when next_pred takes part — fm->n_edges different from n_edges, NULL edges, or an edge whose mirrored edge is not among
+ *     the edges.                                                                                                                        */
+typedef struct dc_fuse_mirror {
+  const int* mirror;       /* [M] 0/1 per member */
+  int        image_width;  /* pixels of the unscaled image every member saw */
+  const int* joint_mirror; /* [J], an involution: pi[pi[j]] == j */
+  int        n_edges;      /* with edges: needed whenever next_pred takes part and a member is mirrored */
+  const int* edges;        /* [n_edges][2] 0-based (joint, next joint), as dc_net_assemble_people */
+} dc_fuse_mirror;
+int dc_group_forward_images_mirrored(dc_group* group, const unsigned char* const* images, const int* n, const int* height, const int* width,
+                                     const double* scale, const int* mirror /* [M], 0/1; NULL = none */, int is_device, float* const* prob,
+                                     float* const* loc_pred, float* const* next_pred, void* stream);
+int dc_group_fuse_maps_mirrored(dc_group* group, const double* scales, int base, const dc_fuse_mirror* fm, int n_edges, const double* mean,
+                                const double* stdev, float* prob, float* loc_pred, float* next_pred, int is_device, void* stream);
+int dc_group_detect_parts_mirrored(dc_group* group, const double* scales, int base, const dc_fuse_mirror* fm, float threshold, int radius,
+                                   int max_det, int* counts, double* dets);
+int dc_group_assemble_people_mirrored(dc_group* group, const double* scales, int base, const dc_fuse_mirror* fm, const dc_assemble_params* p,
+                                      int n_edges, const int* edges, const double* mean, const double* stdev, const int* joint_order,
+                                      int* n_people, double* people, int* cand, double* cost);
 /* the merged plan of the last forward: one line per launch ("conv_gemm_mp<tile> problems=.. grid=.." or "member c: <kernel>");
  * NULL + dc_last_error() before the first forward; pointer valid until the next call on this group                            */
 const char* dc_group_plan_text(dc_group* group);
