@@ -687,9 +687,10 @@ int dc_group_forward_batch(dc_group* group, const float* const* inputs, const in
   }
   return guard([&] { G(group)->forward_batch(inputs, n, h, w, is_device != 0, prob, loc_pred, next_pred, stream); });
 }
-int dc_group_forward_images(dc_group* group, const unsigned char* const* images, const int* n, const int* height, const int* width,
-                            const double* scale, int is_device, float* const* prob, float* const* loc_pred, float* const* next_pred,
-                            double* const* pose, void* stream) {
+// the argument checks and the call of both image entries of a group (mirror null: nobody is mirrored)
+static int group_forward_images(dc_group* group, const unsigned char* const* images, const int* n, const int* height, const int* width,
+                                const double* scale, const int* mirror, int is_device, float* const* prob, float* const* loc_pred,
+                                float* const* next_pred, double* const* pose, void* stream) {
   REQUIRE(group);
   REQUIRE(images);
   REQUIRE(n);
@@ -700,7 +701,12 @@ int dc_group_forward_images(dc_group* group, const unsigned char* const* images,
     if (!images[c]) return fail(DC_EINVAL, "null images for group member " + std::to_string(c));
     if (n[c] <= 0 || height[c] <= 0 || width[c] <= 0 || !(scale[c] > 0)) return fail(DC_EINVAL, "bad image shape / scale for group member " + std::to_string(c));
   }
-  return guard([&] { G(group)->forward_images(images, n, height, width, scale, is_device != 0, prob, loc_pred, next_pred, pose, stream); });
+  return guard([&] { G(group)->forward_images(images, n, height, width, scale, is_device != 0, prob, loc_pred, next_pred, pose, stream, mirror); });
+}
+int dc_group_forward_images(dc_group* group, const unsigned char* const* images, const int* n, const int* height, const int* width,
+                            const double* scale, int is_device, float* const* prob, float* const* loc_pred, float* const* next_pred,
+                            double* const* pose, void* stream) {
+  return group_forward_images(group, images, n, height, width, scale, nullptr, is_device, prob, loc_pred, next_pred, pose, stream);
 }
 int dc_group_forward_boxes(dc_group* group, const unsigned char* image, int height, int width, int is_device, const int* boxes,
                            const double* scales, int n, const double* pyramid_scales, int canvas_h, int canvas_w, float* const* prob,
@@ -714,33 +720,22 @@ int dc_group_forward_boxes(dc_group* group, const unsigned char* image, int heig
                             next_pred, pose, stream);
   });
 }
-// multi-scale fusion: a null `scales` is the library's to refuse (DC_EINVAL naming it), like every other argument of the rule
+// multi-scale fusion: a null `scales` is the library's to refuse (DC_EINVAL naming it), like every other argument of the rule.  The plain
+// entries are the mirrored ones with no mirror table.
 int dc_group_fuse_maps(dc_group* group, const double* scales, int base, int n_edges, const double* mean, const double* stdev, float* prob,
                        float* loc_pred, float* next_pred, int is_device, void* stream) {
-  REQUIRE(group);
-  return guard([&] { G(group)->fuse_maps(scales, base, n_edges, mean, stdev, prob, loc_pred, next_pred, is_device != 0, stream); });
+  return dc_group_fuse_maps_mirrored(group, scales, base, nullptr, n_edges, mean, stdev, prob, loc_pred, next_pred, is_device, stream);
 }
 int dc_group_detect_parts(dc_group* group, const double* scales, int base, float threshold, int radius, int max_det, int* counts,
                           double* dets) {
-  REQUIRE(group);
-  REQUIRE(counts);
-  REQUIRE(dets);
-  return guard([&] { G(group)->detect_parts(scales, base, threshold, radius, max_det, counts, dets); });
+  return dc_group_detect_parts_mirrored(group, scales, base, nullptr, threshold, radius, max_det, counts, dets);
 }
 int dc_group_assemble_people(dc_group* group, const double* scales, int base, const dc_assemble_params* p, int n_edges, const int* edges,
                              const double* mean, const double* stdev, const int* joint_order, int* n_people, double* people, int* cand,
                              double* cost) {
-  REQUIRE(group);
-  REQUIRE(p);
-  REQUIRE(n_people);
-  REQUIRE(people);
-  if (n_edges > 0) REQUIRE(edges);
-  return guard([&] {
-    Net::AssembleParams q{p->scale, p->threshold, p->radius, p->max_det, p->max_cost, p->seed_threshold, p->max_people, p->min_joints};
-    G(group)->assemble_people(scales, base, q, n_edges, edges, mean, stdev, joint_order, n_people, people, cand, cost);
-  });
+  return dc_group_assemble_people_mirrored(group, scales, base, nullptr, p, n_edges, edges, mean, stdev, joint_order, n_people, people, cand, cost);
 }
-// mirrored members: the same calls with a dc_fuse_mirror; null, or no member marked, is the unmirrored call (net_group.cpp check_mirror)
+// mirrored members: a dc_fuse_mirror; null, or no member marked: nobody is mirrored (net_group.cpp check_mirror)
 static const NetGroup::FuseMirror* mirror_args(const dc_fuse_mirror* fm, NetGroup::FuseMirror& to) {
   if (!fm) return nullptr;
   to = NetGroup::FuseMirror{fm->mirror, fm->image_width, fm->joint_mirror, fm->n_edges, fm->edges};
@@ -749,18 +744,7 @@ static const NetGroup::FuseMirror* mirror_args(const dc_fuse_mirror* fm, NetGrou
 int dc_group_forward_images_mirrored(dc_group* group, const unsigned char* const* images, const int* n, const int* height, const int* width,
                                      const double* scale, const int* mirror, int is_device, float* const* prob, float* const* loc_pred,
                                      float* const* next_pred, void* stream) {
-  if (!mirror) return dc_group_forward_images(group, images, n, height, width, scale, is_device, prob, loc_pred, next_pred, nullptr, stream);
-  REQUIRE(group);
-  REQUIRE(images);
-  REQUIRE(n);
-  REQUIRE(height);
-  REQUIRE(width);
-  REQUIRE(scale);
-  for (size_t c = 0; c < G(group)->nets.size(); ++c) {
-    if (!images[c]) return fail(DC_EINVAL, "null images for group member " + std::to_string(c));
-    if (n[c] <= 0 || height[c] <= 0 || width[c] <= 0 || !(scale[c] > 0)) return fail(DC_EINVAL, "bad image shape / scale for group member " + std::to_string(c));
-  }
-  return guard([&] { G(group)->forward_images(images, n, height, width, scale, is_device != 0, prob, loc_pred, next_pred, nullptr, stream, mirror); });
+  return group_forward_images(group, images, n, height, width, scale, mirror, is_device, prob, loc_pred, next_pred, nullptr, stream);
 }
 int dc_group_fuse_maps_mirrored(dc_group* group, const double* scales, int base, const dc_fuse_mirror* fm, int n_edges, const double* mean,
                                 const double* stdev, float* prob, float* loc_pred, float* next_pred, int is_device, void* stream) {

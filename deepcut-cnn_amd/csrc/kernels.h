@@ -355,31 +355,30 @@ int launch_assemble(int NB, int J, int max_det, int max_people, int min_joints, 
                     void* stream);
 
 // Multi-scale fusion of the maps of a pyramid (pose.hip; the rule is this project's own, like the assembly above: include/deepcut_hip.h,
-// dc_group_fuse_maps).  Member m holds the maps of the same NB images at its own scale; map k (0 prob, 1 loc_pred, 2 next_pred) is the
-// NHWC image ptr[k] of H x W cells with channel pitch cp[k], first channel c0[k]; q = scale of m / scale of the base member.
+// dc_group_fuse_maps and dc_group_fuse_maps_mirrored).  Member m holds the maps of the same NB images at its own scale; map k (0 prob,
+// 1 loc_pred, 2 next_pred) is the NHWC image ptr[k] of H x W cells with channel pitch cp[k], first channel c0[k]; q = scale of m / scale
+// of the base member.
 struct FuseMember {
   const void* ptr[3];
   int cp[3], c0[3];
   int H, W;
   double q;
 };
-// One launch for every member, map and image: out[((b*Hb + r)*Wb + c)*Ctot + ch] (float32, NHWC, pitch Ctot = C[0] + C[1] + C[2]) =
-// (sum over m ascending of bilinear sample of member m at the cell's point * gain[m*Ctot + ch] + bias[m*Ctot + ch]) * (1 / M).
-// Channels [0, C[0]) are map 0, the next C[1] map 1, the last C[2] map 2; a map with C[k] = 0 takes no part (its ptr is not read).
-// members / gain / bias are device tables ([M], [M][Ctot], [M][Ctot]); ekind is the members' common element type.
-int launch_fuse_maps(const FuseMember* members, const float* gain, const float* bias, int M, int ekind, int NB, int Hb, int Wb, const int C[3],
-                     float* out, void* stream);
-
-// The same with mirrored members (dc_group_fuse_maps_mirrored): flip[m].on marks a member that saw the image flipped left to right, ws =
-// (image width - 1) * the member's scale; its sample column is u = ((ws - (8c + 4) q) - 4) / 8.  src[m*Ctot + ch] is the channel WITHIN
-// its map (0 .. C[k] - 1) that output channel ch reads from member m (the identity for an unmirrored member); the sign changes are in
-// gain / bias.  Everything else — corners, weights, the ascending sum, 1 / M — is launch_fuse_maps'.
+// on marks a member that saw the image flipped left to right, ws = (image width - 1) * the member's scale
 struct FuseFlip {
   double ws;
   int on, pad_;
 };
-int launch_fuse_maps_mirrored(const FuseMember* members, const FuseFlip* flip, const float* gain, const float* bias, const int* src, int M,
-                              int ekind, int NB, int Hb, int Wb, const int C[3], float* out, void* stream);
+// One launch for every member, map and image: out[((b*Hb + r)*Wb + c)*Ctot + ch] (float32, NHWC, pitch Ctot = C[0] + C[1] + C[2]) =
+// (sum over m ascending of bilinear sample of member m at the cell's point * gain[m*Ctot + ch] + bias[m*Ctot + ch]) * (1 / M).
+// Channels [0, C[0]) are map 0, the next C[1] map 1, the last C[2] map 2; a map with C[k] = 0 takes no part (its ptr is not read).
+// members / gain / bias are device tables ([M], [M][Ctot], [M][Ctot]); ekind is the members' common element type.
+// flip and src both null: no member is mirrored, and neither table is read.  Both given ([M], [M][Ctot]): the same kernel body with two
+// differences — a member with flip[m].on is sampled at the column u = ((ws - (8c + 4) q) - 4) / 8, and output channel ch reads from
+// member m the channel src[m*Ctot + ch] WITHIN its map (0 .. C[k] - 1; the identity for an unmirrored member); the sign changes are in
+// gain / bias.  Exactly one of the two null: hipErrorInvalidValue.
+int launch_fuse_maps(const FuseMember* members, const FuseFlip* flip, const float* gain, const float* bias, const int* src, int M, int ekind,
+                     int NB, int Hb, int Wb, const int C[3], float* out, void* stream);
 
 // Image pre-processing of the demo (python/pose/estimate_pose.py:83-103) on the device: replicate padding by
 // coordinate clamping, Pillow's two-pass 8-bit bilinear resample (22-bit fixed-point weights from the host),

@@ -486,8 +486,8 @@ struct NetGroup {
   // fuse_maps wrote to the caller's device buffers is the caller's to wait for, as with forward_images.
   // fuse_maps: the fused maps as NCHW float32 (any of them null: not fused), host or device, stream as forward_images
   // Mirrored members (dc_group_*_mirrored; the rule: include/deepcut_hip.h): `fm` names the members that saw the image flipped left to
-  // right, the image's width, the joint permutation and the regression edges.  Null, or no member marked: the calls below are what they
-  // were, through the unmirrored kernel.  Otherwise the fusion is launch_fuse_maps_mirrored, still one launch.
+  // right, the image's width, the joint permutation and the regression edges.  Null, or no member marked: nobody is mirrored, and the
+  // launch reads no mirror table.  Otherwise the same launch_fuse_maps, with the two tables of the mirrored members.
   struct FuseMirror {
     const int* mirror;        // [M] 0/1, null = none
     int image_width;
@@ -545,7 +545,7 @@ struct NetGroup {
   void check_scales(const char* who, const double* scales, int base) const;  // the scales and the base index alone
   void check_fuse(const char* who, const double* scales, int base, const bool use[3], int n_edges, const double* mean, const double* stdev,
                   int C[3], int& NB) const;
-  // what check_mirror makes of a FuseMirror (host only): empty `on` = no mirrored member, the unmirrored path
+  // what check_mirror makes of a FuseMirror (host only): empty `on` = no mirrored member
   struct MirrorPlan {
     std::vector<int> on;      // [M] 0/1
     std::vector<int> pi;      // [J]
@@ -553,15 +553,12 @@ struct NetGroup {
     int image_width = 0;
   };
   MirrorPlan check_mirror(const char* who, const FuseMirror* fm, int base, const bool use[3], int n_edges, const int C[3]) const;
-  FusedMaps fuse(const double* scales, int base, const bool use[3], const double* mean, const double* stdev, void* s,
-                 const MirrorPlan* mp = nullptr);
-  FusedMaps fuse_mirrored(const double* scales, int base, const std::vector<FuseMember>& mem, const int C[3], int NB, int ek, const double* mean,
-                          const double* stdev, void* s, const MirrorPlan& mp);
+  FusedMaps fuse(const double* scales, int base, const bool use[3], const double* mean, const double* stdev, void* s, const MirrorPlan& mp);
   DevBuf fused_, fuse_table_, fuse_stage_, people_scratch_;
   void* fuse_event_ = nullptr;    // recorded behind the last fusion call's work ...
   void* fuse_stream_ = nullptr;   // ... on this stream
   void fuse_done(void* s);        // record it
-  std::vector<unsigned char> fuse_table_host_;  // what fuse_table_ holds: the members' descriptors, then gain and bias [M][channels] (mirrored: then the source channels)
+  std::vector<unsigned char> fuse_table_host_;  // what fuse_table_ holds: the members' descriptors, then gain and bias [M][channels] (a member mirrored: then the FuseFlip records and the source channels)
 };
 
 // ---- runtime.cpp: pinned host memory (dc_host_alloc / dc_host_free) ---------------------------------------------------------

@@ -832,7 +832,7 @@ void NetGroup::check_fuse(const char* who, const double* scales, int base, const
 }
 
 // Mirrored members (dc_group_*_mirrored), host only and after check_fuse: what is wrong is said before any device work.  -> the plan of
-// the mirrored launch, or one with an empty `on` (fm null, or no member marked): the unmirrored path, nothing else of fm is read.
+// the launch, with an empty `on` when nobody is mirrored (fm null, or no member marked): then nothing else of fm is read.
 NetGroup::MirrorPlan NetGroup::check_mirror(const char* who, const FuseMirror* fm, int base, const bool use[3], int n_edges, const int C[3]) const {
   MirrorPlan mp;
   const std::string w = std::string(who) + ": ";
@@ -885,10 +885,13 @@ NetGroup::MirrorPlan NetGroup::check_mirror(const char* who, const FuseMirror* f
   return mp;
 }
 
-// The launch.  The table on the device (the members' descriptors, then gain and bias [M][channels]) is uploaded when it differs from the
-// one already there — a new pyramid, a reallocated map —, so the usual call is the one kernel and nothing else.
+// The launch.  The table on the device — the members' descriptors, then gain and bias [M][channels], and when a member is mirrored
+// their FuseFlip records and the source channels [M][channels] behind them — is uploaded when it differs from the one already there (a
+// new pyramid, a reallocated map), so the usual call is the one kernel and nothing else.  An unmirrored member's rows are the rule of
+// dc_group_fuse_maps with the identity as source; a mirrored member's follow dc_group_fuse_maps_mirrored (include/deepcut_hip.h).
+// PARITY UNPINNED BY THE REFERENCE, which mirrors nothing on the pose path.
 NetGroup::FusedMaps NetGroup::fuse(const double* scales, int base, const bool use[3], const double* mean, const double* stdev, void* s,
-                                   const MirrorPlan* mp) {
+                                   const MirrorPlan& mp) {
   const int M = (int)nets.size();
   // the buffers below are shared by every call: work that the previous call left running on ANOTHER stream (an asynchronous
   // fuse_maps on a caller's stream) finishes before this call's stream touches them
@@ -913,98 +916,52 @@ NetGroup::FusedMaps NetGroup::fuse(const double* scales, int base, const bool us
       first = false;
     }
   }
-  const int Ctot = C[0] + C[1] + C[2], Hb = mem[(size_t)base].H, Wb = mem[(size_t)base].W;
-  if (mp && !mp->on.empty()) return fuse_mirrored(scales, base, mem, C, NB, ek, mean, stdev, s, *mp);
-  // gain and bias, in double, stored as float
-  std::vector<float> gb((size_t)2 * M * Ctot);
-  float* gain = gb.data();
-  float* bias = gain + (size_t)M * Ctot;
-  for (int m = 0; m < M; ++m) {
-    const double rho = m == base ? 1.0 : scales[base] / scales[m];
-    float* g = gain + (size_t)m * Ctot;
-    float* bi = bias + (size_t)m * Ctot;
-    for (int ch = 0; ch < C[0]; ++ch) g[ch] = 1.f, bi[ch] = 0.f;
-    for (int ch = C[0]; ch < C[0] + C[1]; ++ch) g[ch] = (float)rho, bi[ch] = 0.f;
-    for (int i = 0; i < C[2]; ++i) {
-      const double mu = mean ? mean[i] : 0.0, sd = stdev ? stdev[i] : 1.0;
-      g[C[0] + C[1] + i] = (float)rho;
-      bi[C[0] + C[1] + i] = (float)((rho - 1.0) * mu / sd);
-    }
-  }
-  const size_t mem_b = (size_t)M * sizeof(FuseMember), gb_b = gb.size() * sizeof(float);
-  std::vector<unsigned char> table(mem_b + gb_b);
-  std::memcpy(table.data(), mem.data(), mem_b);
-  std::memcpy(table.data() + mem_b, gb.data(), gb_b);
-  unsigned char* d_table = (unsigned char*)fuse_table_.get(table.size());
-  if (table != fuse_table_host_) {
-    fuse_table_host_.clear();  // (not what the device holds any more, should the upload throw)
-    dev_upload(d_table, table.data(), table.size(), s);
-    fuse_table_host_ = std::move(table);
-  }
-  float* out = (float*)fused_.get((size_t)NB * Hb * Wb * Ctot * sizeof(float));
-  KCHECK(launch_fuse_maps((const FuseMember*)d_table, (const float*)(d_table + mem_b), (const float*)(d_table + mem_b) + (size_t)M * Ctot, M, ek, NB,
-                          Hb, Wb, C, out, s));
-  FusedMaps fm{};
-  int c0 = 0;
-  for (int k = 0; k < 3; ++k) {
-    fm.map[k] = Net::MapRef{out, Ctot, c0, 4, kElemF32, NB, C[k], Hb, Wb};
-    c0 += C[k];
-  }
-  return fm;
-}
-
-// The mirrored launch: the table is the members' descriptors, their FuseFlip records, then gain, bias and source channel [M][channels].
-// An unmirrored member's rows are the ones above with the identity as source; a mirrored member's follow the rule in
-// include/deepcut_hip.h (dc_group_fuse_maps_mirrored).  PARITY UNPINNED BY THE REFERENCE, which mirrors nothing on the pose path.
-NetGroup::FusedMaps NetGroup::fuse_mirrored(const double* scales, int base, const std::vector<FuseMember>& mem, const int C[3], int NB, int ek,
-                                            const double* mean, const double* stdev, void* s, const MirrorPlan& mp) {
-  const int M = (int)nets.size();
   const int Ctot = C[0] + C[1] + C[2], Hb = mem[(size_t)base].H, Wb = mem[(size_t)base].W, J = (int)mp.pi.size(), E = C[2] / 2;
-  if ((C[0] && C[0] != J) || (C[1] && C[1] != 2 * J) || (C[2] && (int)mp.edge.size() != E))
+  const bool mirrored = !mp.on.empty();
+  if (mirrored && ((C[0] && C[0] != J) || (C[1] && C[1] != 2 * J) || (C[2] && (int)mp.edge.size() != E)))
     throw DcError(DC_ESHAPE, "fuse_maps: the maps' channels do not match the mirror table's joints and edges");
-  std::vector<FuseFlip> flip((size_t)M);
-  std::vector<float> gb((size_t)2 * M * Ctot);
-  std::vector<int> src((size_t)M * Ctot);
-  float* gain = gb.data();
-  float* bias = gain + (size_t)M * Ctot;
+  // gain and bias, in double, stored as float; flip and src only when a member is mirrored
+  const size_t rows = (size_t)M * Ctot;
+  std::vector<float> gb(2 * rows);
+  std::vector<FuseFlip> flip(mirrored ? (size_t)M : 0);
+  std::vector<int> src(mirrored ? rows : 0);
   auto mu = [&](int l, int k) { return mean ? mean[2 * l + k] : 0.0; };
   auto sd = [&](int l, int k) { return stdev ? stdev[2 * l + k] : 1.0; };
   for (int m = 0; m < M; ++m) {
-    const bool on = mp.on[(size_t)m] != 0;
+    const bool on = mirrored && mp.on[(size_t)m] != 0;
     const double rho = m == base ? 1.0 : scales[base] / scales[m];
-    flip[(size_t)m] = FuseFlip{on ? (double)(mp.image_width - 1) * scales[m] : 0.0, on ? 1 : 0, 0};
-    float* g = gain + (size_t)m * Ctot;
-    float* bi = bias + (size_t)m * Ctot;
-    int* sc = src.data() + (size_t)m * Ctot;
-    for (int j = 0; j < C[0]; ++j) g[j] = 1.f, bi[j] = 0.f, sc[j] = on ? mp.pi[(size_t)j] : j;
+    if (mirrored) flip[(size_t)m] = FuseFlip{on ? (double)(mp.image_width - 1) * scales[m] : 0.0, on ? 1 : 0, 0};
+    auto row = [&](int at, float gain, float bias, int from) {
+      gb[(size_t)m * Ctot + at] = gain, gb[rows + (size_t)m * Ctot + at] = bias;
+      if (mirrored) src[(size_t)m * Ctot + at] = from;
+    };
+    for (int j = 0; j < C[0]; ++j) row(j, 1.f, 0.f, on ? mp.pi[(size_t)j] : j);
     for (int i = 0; i < C[1]; ++i) {
       const int j = i / 2, k = i % 2;
-      g[C[0] + i] = (float)(on && k == 0 ? -rho : rho), bi[C[0] + i] = 0.f, sc[C[0] + i] = on ? 2 * mp.pi[(size_t)j] + k : i;
+      row(C[0] + i, (float)(on && k == 0 ? -rho : rho), 0.f, on ? 2 * mp.pi[(size_t)j] + k : i);
     }
     for (int i = 0; i < C[2]; ++i) {
       const int l = i / 2, k = i % 2, at = C[0] + C[1] + i;
       if (!on) {
-        g[at] = (float)rho, bi[at] = (float)((rho - 1.0) * mu(l, k) / sd(l, k)), sc[at] = i;
+        row(at, (float)rho, (float)((rho - 1.0) * mu(l, k) / sd(l, k)), i);
         continue;
       }
       const int lp = mp.edge[(size_t)l];
-      sc[at] = 2 * lp + k;
-      if (k == 0) {
-        g[at] = (float)(-rho * sd(lp, 0) / sd(l, 0));
-        bi[at] = (float)(-(rho * mu(lp, 0) + mu(l, 0)) / sd(l, 0));
-      } else {
-        g[at] = (float)(rho * sd(lp, 1) / sd(l, 1));
-        bi[at] = (float)((rho * mu(lp, 1) - mu(l, 1)) / sd(l, 1));
-      }
+      if (k == 0)
+        row(at, (float)(-rho * sd(lp, 0) / sd(l, 0)), (float)(-(rho * mu(lp, 0) + mu(l, 0)) / sd(l, 0)), 2 * lp + k);
+      else
+        row(at, (float)(rho * sd(lp, 1) / sd(l, 1)), (float)((rho * mu(lp, 1) - mu(l, 1)) / sd(l, 1)), 2 * lp + k);
     }
   }
-  const size_t mem_b = (size_t)M * sizeof(FuseMember), flip_b = (size_t)M * sizeof(FuseFlip), gb_b = gb.size() * sizeof(float),
+  const size_t mem_b = (size_t)M * sizeof(FuseMember), gb_b = gb.size() * sizeof(float), flip_b = flip.size() * sizeof(FuseFlip),
                src_b = src.size() * sizeof(int);
-  std::vector<unsigned char> table(mem_b + flip_b + gb_b + src_b);
+  std::vector<unsigned char> table(mem_b + gb_b + flip_b + src_b);
   std::memcpy(table.data(), mem.data(), mem_b);
-  std::memcpy(table.data() + mem_b, flip.data(), flip_b);
-  std::memcpy(table.data() + mem_b + flip_b, gb.data(), gb_b);
-  std::memcpy(table.data() + mem_b + flip_b + gb_b, src.data(), src_b);
+  std::memcpy(table.data() + mem_b, gb.data(), gb_b);
+  if (mirrored) {
+    std::memcpy(table.data() + mem_b + gb_b, flip.data(), flip_b);
+    std::memcpy(table.data() + mem_b + gb_b + flip_b, src.data(), src_b);
+  }
   unsigned char* d_table = (unsigned char*)fuse_table_.get(table.size());
   if (table != fuse_table_host_) {
     fuse_table_host_.clear();  // (not what the device holds any more, should the upload throw)
@@ -1012,9 +969,9 @@ NetGroup::FusedMaps NetGroup::fuse_mirrored(const double* scales, int base, cons
     fuse_table_host_ = std::move(table);
   }
   float* out = (float*)fused_.get((size_t)NB * Hb * Wb * Ctot * sizeof(float));
-  const float* d_gain = (const float*)(d_table + mem_b + flip_b);
-  KCHECK(launch_fuse_maps_mirrored((const FuseMember*)d_table, (const FuseFlip*)(d_table + mem_b), d_gain, d_gain + (size_t)M * Ctot,
-                                   (const int*)(d_table + mem_b + flip_b + gb_b), M, ek, NB, Hb, Wb, C, out, s));
+  const float* d_gain = (const float*)(d_table + mem_b);
+  KCHECK(launch_fuse_maps((const FuseMember*)d_table, mirrored ? (const FuseFlip*)(d_table + mem_b + gb_b) : nullptr, d_gain, d_gain + rows,
+                          mirrored ? (const int*)(d_table + mem_b + gb_b + flip_b) : nullptr, M, ek, NB, Hb, Wb, C, out, s));
   FusedMaps fm{};
   int c0 = 0;
   for (int k = 0; k < 3; ++k) {
@@ -1047,7 +1004,7 @@ void NetGroup::fuse_maps(const double* scales, int base, int n_edges, const doub
   if (own_async) user_stream = nullptr;
   nets[0]->ensure_device();
   void* s = user_stream ? user_stream : stream();
-  const FusedMaps fm = fuse(scales, base, use, mean, stdev, s, &mp);
+  const FusedMaps fm = fuse(scales, base, use, mean, stdev, s, mp);
   size_t total = 0;
   for (int k = 0; k < 3; ++k) total += (size_t)fm.map[k].NB * fm.map[k].C * fm.map[k].H * fm.map[k].W;
   float* stage = is_device ? nullptr : (float*)fuse_stage_.get(total * sizeof(float));
@@ -1076,7 +1033,7 @@ void NetGroup::detect_parts(const double* scales, int base, float thr, int radiu
   if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "detect_parts() in CPU mode");
   nets[0]->ensure_device();
   void* s = stream();
-  const FusedMaps fm = fuse(scales, base, use, nullptr, nullptr, s, &mp);
+  const FusedMaps fm = fuse(scales, base, use, nullptr, nullptr, s, mp);
   const Net::MapRef &P = fm.map[0], &L = fm.map[1];
   if (L.C != 2 * P.C) throw DcError(DC_ESHAPE, "detect_parts: loc_pred must have 2 channels per joint and the score map's size");
   const int lists = P.NB * P.C;
@@ -1113,7 +1070,7 @@ void NetGroup::assemble_people(const double* scales, int base, const Net::Assemb
   if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "assemble_people() in CPU mode");
   nets[0]->ensure_device();
   void* s = stream();
-  const FusedMaps fm = fuse(scales, base, use, mean, stdev, s, &mp);
+  const FusedMaps fm = fuse(scales, base, use, mean, stdev, s, mp);
   Net::assemble_maps(fm.map[0], fm.map[1], fm.map[2], q, table, n_edges, mean, stdev, [this](size_t bytes) { return people_scratch_.get(bytes); }, s,
                      n_people, people, cand, cost);
   fuse_done(s);

@@ -220,19 +220,35 @@ __global__ __launch_bounds__(256) void pairwise_decode_kernel(const T* __restric
   o[1] = ((double)row * 8.0 + 4.0 + (double)(float)p[1] * s1 + m1) / scale;
 }
 
-// ---- multi-scale fusion of a pyramid's maps (the rule: include/deepcut_hip.h, dc_group_fuse_maps; this project's own) ---------------
+// ---- multi-scale fusion of a pyramid's maps (the rule: include/deepcut_hip.h, dc_group_fuse_maps and dc_group_fuse_maps_mirrored; this
+// project's own) -----------------------------------------------------------------------------------------------------------------------
 // One workgroup per base cell (image, row, column), lanes along the channels of the three maps laid end to end: the maps are NHWC, so
 // each corner read of a member and the store are contiguous runs of a wave.  The cell's sample position in every member — four corner
 // cells and two weights — is computed once, by the thread of that member's index, and kept in LDS; the channel loop (406 channels of the
 // full heads: two trips of 256) only reads it.  Members are summed in ascending order by every thread: nothing depends on timing.
+// One body, two instantiations.  Mirror = false reads neither `flip` nor `src`.  Mirror = true differs in two expressions: a member that
+// saw the image flipped left to right is sampled at the reflected column, and lane ch reads the member's channel src[m][ch] of the same
+// map (left and right joints swapped, the regression edge replaced by its mirror image), with the sign change of the x components
+// folded into the gain / bias table.  A corner read is then no longer one ascending run of the wave but a permutation of it INSIDE the
+// same map, i.e. inside the same cache lines (14 / 28 / 364 channels of 2 or 4 bytes: 1 + 1 + 6 to 12 lines of 128 bytes per corner
+// either way), and the store stays a contiguous run.  The flag is compile-time so that a group without a mirrored member pays no
+// dependent integer load per member and channel.
 struct FuseCorner {
   int i00, i01, i10, i11;  // cell indices (y * W + x) of the four corners in the member's map
   float fx, fy;
 };
 
-template <typename T>
-__global__ __launch_bounds__(256) void fuse_maps_kernel(const FuseMember* __restrict__ members, const float* __restrict__ gain,
-                                                        const float* __restrict__ bias, int M, int Hb, int Wb, int C0, int C1, int Ctot,
+__device__ __forceinline__ double fuse_mirrored_u(double ws, int c, double q) {
+#pragma clang fp contract(off)  // the rule's own order: a product, two differences, a quotient
+  const double a = (double)(8 * c + 4) * q;
+  const double d = ws - a;
+  return (d - 4.0) / 8.0;
+}
+
+template <typename T, bool Mirror>
+__global__ __launch_bounds__(256) void fuse_maps_kernel(const FuseMember* __restrict__ members, const FuseFlip* __restrict__ flip,
+                                                        const float* __restrict__ gain, const float* __restrict__ bias,
+                                                        const int* __restrict__ src, int M, int Hb, int Wb, int C0, int C1, int Ctot,
                                                         float inv_m, float* __restrict__ out) {
   extern __shared__ FuseCorner fuse_lds[];  // [M]
   const int cell = blockIdx.x, t = threadIdx.x;
@@ -240,7 +256,10 @@ __global__ __launch_bounds__(256) void fuse_maps_kernel(const FuseMember* __rest
   for (int m = t; m < M; m += 256) {
     const FuseMember& mem = members[m];
     const double q = mem.q;
-    double u = ((double)(8 * c + 4) * q - 4.0) / 8.0, v = ((double)(8 * r + 4) * q - 4.0) / 8.0;
+    bool flipped = false;
+    if constexpr (Mirror) flipped = flip[m].on;
+    double u = flipped ? fuse_mirrored_u(flip[m].ws, c, q) : ((double)(8 * c + 4) * q - 4.0) / 8.0;
+    double v = ((double)(8 * r + 4) * q - 4.0) / 8.0;
     u = fmin(fmax(u, 0.0), (double)(mem.W - 1));
     v = fmin(fmax(v, 0.0), (double)(mem.H - 1));
     const int x0 = (int)floor(u), y0 = (int)floor(v);
@@ -260,7 +279,9 @@ __global__ __launch_bounds__(256) void fuse_maps_kernel(const FuseMember* __rest
       const FuseMember& mem = members[m];
       const FuseCorner kc = fuse_lds[m];
       const long cp = mem.cp[k];
-      const T* p = (const T*)mem.ptr[k] + (long)b * mem.H * mem.W * cp + mem.c0[k] + cc;
+      int sc = cc;  // the channel within map k that this lane reads from member m
+      if constexpr (Mirror) sc = src[(long)m * Ctot + ch];
+      const T* p = (const T*)mem.ptr[k] + (long)b * mem.H * mem.W * cp + mem.c0[k] + sc;
       const float a00 = (float)p[kc.i00 * cp], a01 = (float)p[kc.i01 * cp], a10 = (float)p[kc.i10 * cp], a11 = (float)p[kc.i11 * cp];
       const float val = (1.f - kc.fy) * ((1.f - kc.fx) * a00 + kc.fx * a01) + kc.fy * ((1.f - kc.fx) * a10 + kc.fx * a11);
       acc += val * gain[(long)m * Ctot + ch] + bias[(long)m * Ctot + ch];
@@ -269,85 +290,17 @@ __global__ __launch_bounds__(256) void fuse_maps_kernel(const FuseMember* __rest
   }
 }
 
-int launch_fuse_maps(const FuseMember* members, const float* gain, const float* bias, int M, int ekind, int NB, int Hb, int Wb, const int C[3],
-                     float* out, void* stream) {
+int launch_fuse_maps(const FuseMember* members, const FuseFlip* flip, const float* gain, const float* bias, const int* src, int M, int ekind,
+                     int NB, int Hb, int Wb, const int C[3], float* out, void* stream) {
   const int Ctot = C[0] + C[1] + C[2];
   const long cells = (long)NB * Hb * Wb;
   if (cells <= 0 || Ctot <= 0) return 0;
-  if (M < 1 || M > 1024 || cells > 0x7fffffffL || C[0] < 0 || C[1] < 0 || C[2] < 0) return (int)hipErrorInvalidValue;
+  if (M < 1 || M > 1024 || cells > 0x7fffffffL || C[0] < 0 || C[1] < 0 || C[2] < 0 || !flip != !src) return (int)hipErrorInvalidValue;
   return dc_by_kind(ekind, [&](auto* tag) {
     using T = std::remove_pointer_t<decltype(tag)>;
-    hipLaunchKernelGGL(fuse_maps_kernel<T>, dim3((unsigned)cells), dim3(256), (size_t)M * sizeof(FuseCorner), (hipStream_t)stream, members, gain,
-                       bias, M, Hb, Wb, C[0], C[0] + C[1], Ctot, 1.f / (float)M, out);
-    return (int)hipGetLastError();
-  });
-}
-
-// ---- the same with mirrored members (the rule: include/deepcut_hip.h, dc_group_fuse_maps_mirrored; this project's own) -----------------
-// A member that saw the image flipped left to right is sampled at the reflected position, and lane ch reads the member's channel
-// src[m][ch] of the same map (left and right joints swapped, the regression edge replaced by its mirror image), with the sign change of
-// the x components folded into the gain / bias table.  Same shape as fuse_maps_kernel: one workgroup per base cell, the corner record of
-// every member computed once into LDS, lanes along the channels.  A corner read is no longer one ascending run of the wave but a
-// permutation of it INSIDE the same map, i.e. inside the same cache lines (14 / 28 / 364 channels of 2 or 4 bytes: 1 + 1 + 6 to 12 lines
-// of 128 bytes per corner either way), and the store stays a contiguous run.  Kept beside the unmirrored kernel, which a group
-// without a mirrored member still launches.
-__device__ __forceinline__ double fuse_mirrored_u(double ws, int c, double q) {
-#pragma clang fp contract(off)  // the rule's own order: a product, two differences, a quotient
-  const double a = (double)(8 * c + 4) * q;
-  const double d = ws - a;
-  return (d - 4.0) / 8.0;
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void fuse_maps_mirror_kernel(const FuseMember* __restrict__ members, const FuseFlip* __restrict__ flip,
-                                                               const float* __restrict__ gain, const float* __restrict__ bias,
-                                                               const int* __restrict__ src, int M, int Hb, int Wb, int C0, int C1, int Ctot,
-                                                               float inv_m, float* __restrict__ out) {
-  extern __shared__ FuseCorner fuse_lds[];  // [M]
-  const int cell = blockIdx.x, t = threadIdx.x;
-  const int b = cell / (Hb * Wb), rc = cell - b * (Hb * Wb), r = rc / Wb, c = rc - r * Wb;
-  for (int m = t; m < M; m += 256) {
-    const FuseMember& mem = members[m];
-    const double q = mem.q;
-    double u = flip[m].on ? fuse_mirrored_u(flip[m].ws, c, q) : ((double)(8 * c + 4) * q - 4.0) / 8.0;
-    double v = ((double)(8 * r + 4) * q - 4.0) / 8.0;
-    u = fmin(fmax(u, 0.0), (double)(mem.W - 1));
-    v = fmin(fmax(v, 0.0), (double)(mem.H - 1));
-    const int x0 = (int)floor(u), y0 = (int)floor(v);
-    const int x1 = min(x0 + 1, mem.W - 1), y1 = min(y0 + 1, mem.H - 1);
-    FuseCorner k;
-    k.i00 = y0 * mem.W + x0, k.i01 = y0 * mem.W + x1, k.i10 = y1 * mem.W + x0, k.i11 = y1 * mem.W + x1;
-    k.fx = (float)(u - (double)x0), k.fy = (float)(v - (double)y0);
-    fuse_lds[m] = k;
-  }
-  __syncthreads();
-  float* o = out + (long)cell * Ctot;
-  for (int ch = t; ch < Ctot; ch += 256) {
-    const int k = ch < C0 ? 0 : ch < C1 ? 1 : 2;
-    float acc = 0.f;
-    for (int m = 0; m < M; ++m) {
-      const FuseMember& mem = members[m];
-      const FuseCorner kc = fuse_lds[m];
-      const long cp = mem.cp[k];
-      const T* p = (const T*)mem.ptr[k] + (long)b * mem.H * mem.W * cp + mem.c0[k] + src[(long)m * Ctot + ch];
-      const float a00 = (float)p[kc.i00 * cp], a01 = (float)p[kc.i01 * cp], a10 = (float)p[kc.i10 * cp], a11 = (float)p[kc.i11 * cp];
-      const float val = (1.f - kc.fy) * ((1.f - kc.fx) * a00 + kc.fx * a01) + kc.fy * ((1.f - kc.fx) * a10 + kc.fx * a11);
-      acc += val * gain[(long)m * Ctot + ch] + bias[(long)m * Ctot + ch];
-    }
-    o[ch] = acc * inv_m;
-  }
-}
-
-int launch_fuse_maps_mirrored(const FuseMember* members, const FuseFlip* flip, const float* gain, const float* bias, const int* src, int M,
-                              int ekind, int NB, int Hb, int Wb, const int C[3], float* out, void* stream) {
-  const int Ctot = C[0] + C[1] + C[2];
-  const long cells = (long)NB * Hb * Wb;
-  if (cells <= 0 || Ctot <= 0) return 0;
-  if (M < 1 || M > 1024 || cells > 0x7fffffffL || C[0] < 0 || C[1] < 0 || C[2] < 0 || !flip || !src) return (int)hipErrorInvalidValue;
-  return dc_by_kind(ekind, [&](auto* tag) {
-    using T = std::remove_pointer_t<decltype(tag)>;
-    hipLaunchKernelGGL(fuse_maps_mirror_kernel<T>, dim3((unsigned)cells), dim3(256), (size_t)M * sizeof(FuseCorner), (hipStream_t)stream, members,
-                       flip, gain, bias, src, M, Hb, Wb, C[0], C[0] + C[1], Ctot, 1.f / (float)M, out);
+    auto* kernel = flip ? fuse_maps_kernel<T, true> : fuse_maps_kernel<T, false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)cells), dim3(256), (size_t)M * sizeof(FuseCorner), (hipStream_t)stream, members, flip, gain, bias,
+                       src, M, Hb, Wb, C[0], C[0] + C[1], Ctot, 1.f / (float)M, out);
     return (int)hipGetLastError();
   });
 }

@@ -1234,8 +1234,11 @@ class NetGroup(object):
         return sc, int(base)
 
     def _mirror(self, mirror, image_width, joint_mirror, edges):
-        """-> (FuseMirror, the arrays it points into) for the dc_group_*_mirrored entries.  Only the lengths are checked here; what the
-        values must be (a positive width, an involution, an unmirrored base, mirrored edges present) is the library's to say."""
+        """-> (pointer to a FuseMirror, the arrays it points into) for the dc_group_*_mirrored entries; mirror None: a null pointer,
+        nobody is mirrored.  Only the lengths are checked here; what the values must be (a positive width, an involution, an unmirrored
+        base, mirrored edges present) is the library's to say."""
+        if mirror is None:
+            return None, ()
         flags = np.ascontiguousarray([int(bool(v)) for v in mirror], dtype=np.int32)
         if flags.shape[0] != len(self.nets):
             raise ValueError("one mirror flag per group member: %d flags for %d members" % (flags.shape[0], len(self.nets)))
@@ -1246,7 +1249,7 @@ class NetGroup(object):
         e = None if edges is None else np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 2)
         ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
         fm = FuseMirror(ptr(flags), int(image_width or 0), ptr(pi), 0 if e is None else e.shape[0], ptr(e))
-        return fm, (flags, pi, e)
+        return C.pointer(fm), (flags, pi, e)
 
     def fuse_maps(self, scales, base=0, mean=None, std=None, want=("prob", "loc_pred", "next_pred"), mirror=None, image_width=None,
                   joint_mirror=None, edges=None):
@@ -1259,7 +1262,7 @@ class NetGroup(object):
         image_width (the pixels of the unscaled image), joint_mirror (the joint every joint becomes in the mirror, e.g.
         pose.MIRROR_MPII14) and — when next_pred is fused — edges ([E, 2], as assemble_people) are needed: the mirrored members are
         sampled at the reflected position, their channels permuted and the x components negated, still in the one launch
-        (dc_group_fuse_maps_mirrored).  None: today's call."""
+        (dc_group_fuse_maps_mirrored).  None: no member is mirrored, and the other three are not read."""
         sc, base = self._scales(scales, base)
         want = [k for k in ("prob", "loc_pred", "next_pred") if k in want]
         ref = self.nets[base if 0 <= base < len(self.nets) else 0]
@@ -1276,13 +1279,9 @@ class NetGroup(object):
         hw = ref.blobs["prob"].shape[2:]
         out = {k: np.empty(tuple(ref.blobs[k].shape[:2]) + tuple(hw), np.float32) for k in want}
         ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        if mirror is not None:
-            fm, _keep = self._mirror(mirror, image_width, joint_mirror, edges if "next_pred" in want else None)
-            _check(_lib.dc_group_fuse_maps_mirrored(self._h, ptr(sc), base, C.byref(fm), e, ptr(stats[0]), ptr(stats[1]), ptr(out.get("prob")),
-                                                    ptr(out.get("loc_pred")), ptr(out.get("next_pred")), 0, None))
-            return out
-        _check(_lib.dc_group_fuse_maps(self._h, ptr(sc), base, e, ptr(stats[0]), ptr(stats[1]), ptr(out.get("prob")), ptr(out.get("loc_pred")),
-                                       ptr(out.get("next_pred")), 0, None))
+        fm, _keep = self._mirror(mirror, image_width, joint_mirror, edges if "next_pred" in want else None)
+        _check(_lib.dc_group_fuse_maps_mirrored(self._h, ptr(sc), base, fm, e, ptr(stats[0]), ptr(stats[1]), ptr(out.get("prob")),
+                                                ptr(out.get("loc_pred")), ptr(out.get("next_pred")), 0, None))
         return out
 
     def detect_parts(self, scales, base=0, threshold=0.1, radius=1, max_det=32, mirror=None, image_width=None, joint_mirror=None):
@@ -1293,13 +1292,9 @@ class NetGroup(object):
         n, j = self.nets[0].blobs["prob"].shape[:2]
         counts = np.zeros((n, j), np.int32)
         dets = np.zeros((n, j, max(int(max_det), 0), 5), np.float64)
-        if mirror is not None:
-            fm, _keep = self._mirror(mirror, image_width, joint_mirror, None)
-            _check(_lib.dc_group_detect_parts_mirrored(self._h, sc.ctypes.data_as(C.c_void_p), base, C.byref(fm), float(threshold), int(radius),
-                                                       int(max_det), counts.ctypes.data_as(C.c_void_p), dets.ctypes.data_as(C.c_void_p)))
-            return counts, dets
-        _check(_lib.dc_group_detect_parts(self._h, sc.ctypes.data_as(C.c_void_p), base, float(threshold), int(radius), int(max_det),
-                                          counts.ctypes.data_as(C.c_void_p), dets.ctypes.data_as(C.c_void_p)))
+        fm, _keep = self._mirror(mirror, image_width, joint_mirror, None)
+        _check(_lib.dc_group_detect_parts_mirrored(self._h, sc.ctypes.data_as(C.c_void_p), base, fm, float(threshold), int(radius), int(max_det),
+                                                   counts.ctypes.data_as(C.c_void_p), dets.ctypes.data_as(C.c_void_p)))
         return counts, dets
 
     def assemble_people(self, scales, base=0, threshold=0.1, radius=1, max_det=16, edges=None, mean=None, std=None, max_cost=32.0,
@@ -1323,13 +1318,9 @@ class NetGroup(object):
         cand = np.zeros((n, p, j), np.int32)
         cost = np.zeros((n, j, j, md, md), np.float64) if return_cost else None
         ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        if mirror is not None:
-            fm, _keep = self._mirror(mirror, image_width, joint_mirror, e)
-            _check(_lib.dc_group_assemble_people_mirrored(self._h, ptr(sc), base, C.byref(fm), C.byref(q), e.shape[0], ptr(e), ptr(m), ptr(s),
-                                                          ptr(order), ptr(count), ptr(people), ptr(cand), ptr(cost)))
-        else:
-            _check(_lib.dc_group_assemble_people(self._h, ptr(sc), base, C.byref(q), e.shape[0], ptr(e), ptr(m), ptr(s), ptr(order), ptr(count),
-                                                 ptr(people), ptr(cand), ptr(cost)))
+        fm, _keep = self._mirror(mirror, image_width, joint_mirror, e)
+        _check(_lib.dc_group_assemble_people_mirrored(self._h, ptr(sc), base, fm, C.byref(q), e.shape[0], ptr(e), ptr(m), ptr(s), ptr(order),
+                                                      ptr(count), ptr(people), ptr(cand), ptr(cost)))
         out = []
         for b in range(n):
             d = {"people": people[b, :count[b]].copy(), "cand": cand[b, :count[b]].copy()}

@@ -105,6 +105,10 @@ def test_fused_maps_of_a_real_mirrored_forward_match_the_restatement(forwarded):
     part = grp.fuse_maps(SCALES, 1, want=("prob", "loc_pred"), **MKW)
     full = grp.fuse_maps(SCALES, 1, MEAN, STD, edges=EDGES, **MKW)
     assert sorted(part) == ["loc_pred", "prob"] and all(np.array_equal(part[k], full[k]) for k in part)
+    # one map alone: its rows of the table start at channel 0; next_pred alone counts the joints from the base member's prob
+    for name in ALL:
+        one = grp.fuse_maps(SCALES, 1, MEAN, STD, want=(name,), edges=EDGES, **MKW)
+        assert list(one) == [name] and np.array_equal(one[name], full[name]), name
 
 
 def _vp(a):

@@ -57,6 +57,10 @@ def test_fused_maps_of_a_real_forward_match_the_restatement(forwarded):
     part = grp.fuse_maps(PYRAMID, 1, want=("prob", "loc_pred"))
     full = grp.fuse_maps(PYRAMID, 1, MEAN, STD)
     assert sorted(part) == ["loc_pred", "prob"] and all(np.array_equal(part[k], full[k]) for k in part)
+    # one map alone: its rows of the table start at channel 0, whichever maps would have come before it
+    for name in ALL:
+        one = grp.fuse_maps(PYRAMID, 1, MEAN, STD, want=(name,))
+        assert list(one) == [name] and np.array_equal(one[name], full[name]), name
 
 
 @pytest.mark.parametrize("kw", [dict(dtype="f16"), dict(dtype="bf16"), dict(fuse=0)], ids=["f16", "bf16", "fuse0"])
