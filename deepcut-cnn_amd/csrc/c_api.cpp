@@ -632,6 +632,19 @@ int dc_wino_blocks(const char* tile, int tiles_y, int tiles_x) {
   }
 }
 
+int dc_wino_cover(int tiles_y, int tiles_x, int* out) {
+  if (!out || tiles_y < 1 || tiles_x < 1) return -1;
+  const dc::WinoCover c = dc::wino_plan_cover(tiles_y, tiles_x);
+  const int v[12] = {c.vertical, c.cut, c.blocks, c.na, c.nb, c.a_nby, c.a_nbx, c.b_nby, c.b_nbx, c.b_ty0, c.b_tx0, dc::wino_mix_offered(tiles_y, tiles_x) ? 1 : 0};
+  for (int i = 0; i < 12; ++i) out[i] = v[i];
+  return c.blocks;
+}
+
+int dc_wino_mix_offered(int tiles_y, int tiles_x, int images, int cout) {
+  if (tiles_y < 1 || tiles_x < 1 || images < 1 || cout < 1) return -1;
+  return dc::wino_mix_offered_launch(tiles_y, tiles_x, images, cout) ? 1 : 0;
+}
+
 int dc_stream1x1_pack(const float* g, int cout, int k, float* out) {
   if (!g || !out) return fail(DC_EINVAL, "dc_stream1x1_pack: null pointer");
   if (cout <= 0 || k <= 0 || cout % 32 || k % 16) return fail(DC_EINVAL, "dc_stream1x1_pack: cout must be a multiple of 32, k of 16");

@@ -39,6 +39,10 @@ static constexpr ConvForm kForms[kNumForms] = {
      false, true, stream1x1_bf16_prepare_multi, launch_stream1x1_bf16_multi, -1, "DC_STREAM1X1_BF16", nullptr, 0},
     {kStemBf16, "bs7x7", "bs7x7<8x64>", kElemBF16, kFormStem, 4, kWinoSlots, stem7x7_bf16_eligible, stem7x7_grid, launch_stem7x7_bf16,
      false, false, nullptr, nullptr, -1, "DC_STEM_BF16", nullptr, 0},
+    {kWinoVariantMix, "wino_f23_mix", "wino_f23<4x8+5x6x16>", kElemF32, kForm3x3, 8, kWinoSlots, wino_eligible, wino_grid_mix, launch_wino_f23_mix,
+     false, false, nullptr, nullptr, kWinoVariantMix16, "DC_WINOGRAD", wino_mix_fewer_blocks},
+    {kWinoVariantMix16, "wino_f23_mix_w16", "wino_f23<4x8+5x6x16_w16>", kElemF32, kForm3x3, 16, kWinoSlots, wino_eligible, wino_grid_mix, launch_wino_f23_mix_w16,
+     false, false, nullptr, nullptr, kWinoVariantMix, "DC_WINOGRAD", wino_mix_fewer_blocks},
 };
 
 static constexpr bool forms_in_variant_order() {

@@ -127,12 +127,23 @@ struct ConvGemmParams {
   int dense_y;   // (filled) the output pixels are dense: pixel m is written at m * y_pix_stride
   int ncls;
   int mc_lgx;  // multi-class tile map: the 8 XCDs form a (1 << mc_lgx) x (8 >> mc_lgx) grid over (n tiles) x (m tiles of every class)
+  // --- mixed Winograd launches (wino_f23_mix: blocks of two geometries, wino_plan_cover): per phase image, blocks [0, w_mix_na) are region A,
+  //     4 x 8 tiles from the grid's origin on the w_NBY x w_NBX grid above; blocks [w_mix_na, w_mix_nab) are region B, 5 x 6 tiles from tile
+  //     (w_mix_ty0, w_mix_tx0), w_mix_NBX of them per block row.  One 64-byte line of its own (bytes 0x140-0x17f of the block, asserted below;
+  //     w_mix_pad_ fills line 0x100 up): the kernel requests it at entry with the other lines, and every other field keeps its place in its line.
+  int w_mix_pad_;
+  int w_mix_na, w_mix_nab, w_mix_ty0, w_mix_tx0, w_mix_NBX;
+  unsigned w_mix_div_nbx[2];
+  int w_mix_reserved_[8];
   ConvClass cls[kMaxClasses];
   // --- multi-problem launches: nprob > 0 and the ConvMultiTable that follows the block in the kernel arguments
   //     (ConvMultiArgs) replace every per-tensor field above
   int nprob;
   int ekind;  // ElemKind of x / w / y / resid (esize alone does not tell float16 from bfloat16)
 };
+static_assert(offsetof(ConvGemmParams, w_mix_na) % 64 == 0 && offsetof(ConvGemmParams, w_mix_div_nbx) + 8 <= offsetof(ConvGemmParams, w_mix_na) + 64 &&
+                  offsetof(ConvGemmParams, cls) == offsetof(ConvGemmParams, w_mix_na) + 64,
+              "the w_mix_* fields are one 64-byte line of the argument block, the multi-class table starts on the next");
 // kernel arguments of a multi-problem launch: the table travels IN the argument block (3.6 KB of the 4 KB a HIP kernel may
 // take), so a workgroup finds its problem with scalar loads from the same segment as everything else — with the table behind
 // a pointer in device memory every workgroup paid one more dependent round trip (argument block -> table row -> problem)
@@ -190,7 +201,19 @@ ConvGemmParams wino_launch_params(const ConvGemmParams& p, long grid, int bty, i
 long wino_grid(const ConvGemmParams& p);                   // of the 4 x 8-tile forms
 long wino_grid_5x6(const ConvGemmParams& p);               // of the 5 x 6-tile forms
 bool wino_fewer_blocks(const ConvGemmParams& p);           // the 5 x 6 forms need strictly fewer workgroups: where they are offered to the autotuner
-// the four forms: 8 or 16 (_w16) waves per workgroup, 4 x 8- or 5 x 6-tile blocks
+// the cover of a TY x TX tile grid by one straight cut: region A (rows [0, cut) of a horizontal cut, columns [0, cut) of a vertical one) as
+// a_nby x a_nbx blocks of 4 x 8 tiles from the origin, region B (the rest) as b_nby x b_nbx blocks of 5 x 6 tiles from tile (b_ty0, b_tx0)
+struct WinoCover {
+  int vertical, cut, blocks, na, nb, a_nby, a_nbx, b_nby, b_nbx, b_ty0, b_tx0;
+};
+WinoCover wino_plan_cover(int TY, int TX);                 // fewest blocks, then a pure cover before a cut one, then fewest 5 x 6 blocks; either region may be empty
+long wino_grid_mix(const ConvGemmParams& p);               // of the mixed forms
+bool wino_mix_offered(int TY, int TX);                     // the mixed cover needs strictly fewer blocks than both pure ones ...
+bool wino_mix_offered_launch(int TY, int TX, long images, int Cout);  // ... and `images` (phase) images x Cout channels are a launch of half the CUs or more ...
+bool wino_mix_fewer_blocks(const ConvGemmParams& p);       // ... for this layer: where the mixed forms are offered to the autotuner
+int launch_wino_f23_mix(const ConvGemmParams& p, void* stream);
+int launch_wino_f23_mix_w16(const ConvGemmParams& p, void* stream);
+// the four forms of one geometry: 8 or 16 (_w16) waves per workgroup, 4 x 8- or 5 x 6-tile blocks
 int launch_wino_f23(const ConvGemmParams& p, void* stream);
 int launch_wino_f23_w16(const ConvGemmParams& p, void* stream);
 int launch_wino_f23_5x6(const ConvGemmParams& p, void* stream);
@@ -262,7 +285,9 @@ constexpr int kWinoVariant56 = 1007;     // "wino_f23_5x6": wino_f23 on 5 x 6-ti
 constexpr int kWinoVariant56x16 = 1008;  // "wino_f23_5x6_w16": its 16-wave form
 constexpr int kStreamBf16 = 1009;        // "bs1x1": the streaming form of the dense 1x1 layers of a bfloat16 net (stream1x1.hip, v_mfma_f32_32x32x16_bf16)
 constexpr int kStemBf16 = 1010;          // "bs7x7": the 7x7 / stride-2 stem of a bfloat16 net (stem_f16.hip)
-constexpr int kFormVariant0 = kWinoVariant, kNumForms = 11;
+constexpr int kWinoVariantMix = 1011;     // "wino_f23_mix": wino_f23 on a cover of 4 x 8- and 5 x 6-tile blocks in one launch (wino_plan_cover)
+constexpr int kWinoVariantMix16 = 1012;   // "wino_f23_mix_w16": its 16-wave form
+constexpr int kFormVariant0 = kWinoVariant, kNumForms = 13;
 enum FormGeometry { kForm3x3, kForm1x1, kFormStem };  // the layers a form takes: 3x3, dense 1x1, the 7-row-tap stem
 struct ConvForm {
   int variant;

@@ -226,7 +226,7 @@ void NetGroup::merge(GroupPlan& gp) {
       const Launch& l = nets[c]->plan[i];
       const ConvGemmParams &g = l.cg, &g0 = l0.cg;
       // (a member on a form merges as the direct layer it also is where ConvForm::merges says so — wino_h23, ws1x1, bs1x1, ws1x1f, ws7x7f —, and
-      //  keeps the launch apart on wino_f23, wino_f23_w16, stem7x7 and bs7x7.  wino_h23 is a one-round kernel that wins alone on a 240-workgroup
+      //  keeps the launch apart on the wino_f23 forms (4 x 8, 5 x 6 and mixed blocks, 8 and 16 waves), stem7x7 and bs7x7.  wino_h23 is a one-round kernel that wins alone on a 240-workgroup
       //  grid — round 6: with the 544x736 member's conv4_x 3x3 launches kept out of the merge, the four scales of that layer ran as 17.8 +
       //  31.2 + 17.0 + 14.3 us where the merged direct launch takes 60.5 —; the float32 streaming forms win by a few per cent on a
       //  member's own grid only.)

@@ -102,7 +102,7 @@ void Net::autotune() {
     for (int v : vs) {
       if (!l.takes_tile(v)) continue;
       if (const ConvForm* f = conv_form(v))
-        if (f->offered && !f->offered(l.cg)) continue;  // (a form that is a candidate for some shapes only: the 5 x 6-tile Winograd blocks; asked of the signature's first launch)
+        if (f->offered && !f->offered(l.cg)) continue;  // (a form that is a candidate for some shapes only: the 5 x 6-tile and the mixed Winograd blocks; asked of the signature's first launch)
       Launch trial = l;
       trial.variant = v;
       c.push_back({burst_ms(trial), v});

@@ -1,6 +1,8 @@
 // wino_f32.hip — the float32 Winograd F(2x2, 3x3) kernel of the stride-1 3x3 convolutions and its host side: the forms wino_f23,
-// wino_f23_w16, wino_f23_5x6 and wino_f23_5x6_w16 of forms.cpp (its float16 counterpart: wino_f16.hip).
+// wino_f23_w16, wino_f23_5x6, wino_f23_5x6_w16, wino_f23_mix and wino_f23_mix_w16 of forms.cpp (its float16 counterpart: wino_f16.hip).
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
 
 #include "conv_gemm.h"  // DC_KARG_TOUCH, DC_KARG_HOLD
 #include "kernel_prims.h"
@@ -56,6 +58,10 @@ constexpr int WNTH = 512;
 //  * 5 x 6 = {5 x 3, side by side, pitch 524}: 12 x 14 staged pixels, 15 of a fragment's 16 rows in use.  A 9 x 12 tile grid (a
 //    phase image of res5 3x3 dilation 2 at 544x736) is 2 x 2 = 4 such blocks against 3 x 2 = 6 of the 4 x 8 ones: 768 -> 512 workgroups,
 //    two per CU in one round.  Offered to the autotuner where it needs strictly fewer blocks only (wino_fewer_blocks).
+//  * mixed (WinoGMix) = both in ONE launch: the tile grid is cut once, straight, into a region of 4 x 8 blocks (at the grid's origin) and a
+//    region of 5 x 6 blocks (wino_plan_cover); a workgroup takes its geometry, wave-uniformly, from its block index.  The four places above
+//    are computed per geometry in front of the K loop and in the epilogue; ring (on the larger stage's stride), K loop and epilogue
+//    arithmetic are one code path.  A res4 image (17 x 23 tiles) is 9 + 4 = 13 blocks against 15 of 4 x 8 and 16 of 5 x 6.
 template <int FR_, int FC_, bool SIDE_, int PITCH_>
 struct WinoGeom {
   static constexpr int FR = FR_, FC = FC_, NT = FR_ * FC_, PITCH = PITCH_;
@@ -63,6 +69,8 @@ struct WinoGeom {
   static constexpr int BTY = SIDE_ ? FR_ : 2 * FR_, BTX = SIDE_ ? 2 * FC_ : FC_;  // tiles of a block
   static constexpr int RH = 2 * BTY + 2, RW = 2 * BTX + 2;                        // staged pixels
   static constexpr int STAGE = RH * PITCH_ + 8;                                   // + the dump slot of the staging threads past the block
+  static constexpr int PIXELS = RH * RW;
+  static constexpr bool MIX = false;
   // tile (row, column) inside the block of row q of fragment tf: the fragment's first tile + (q / FC, q % FC)
   static constexpr int frow(int tf) { return SIDE_ ? 0 : FR_ * tf; }
   static constexpr int fcol(int tf) { return SIDE_ ? FC_ * tf : 0; }
@@ -90,6 +98,12 @@ using WinoG48 = WinoGeom<WBTY / 2, WBTX, false, WPITCH>;  // 2 * 672 = 21 * 64 f
 using WinoG56 = WinoGeom<5, 3, true, 524>;   // 524 / 2 = 6 (mod 16) slots per tile row, 2 per tile column: the tiles of each half of a group on distinct even slots
 static_assert(WinoG48::BTY == 4 && WinoG48::BTX == 8 && WinoG48::RH == 10 && WinoG48::RW == 18, "the 4 x 8 block");
 static_assert(WinoG56::BTY == 5 && WinoG56::BTX == 6 && WinoG56::RH == 12 && WinoG56::RW == 14, "the 5 x 6 block");
+// a launch of blocks of both geometries: region A = WinoG48, region B = WinoG56 (per block: ConvGemmParams::w_mix_*); the ring's stride and the
+// staging loads per thread are the larger of the two
+struct WinoGMix {
+  static constexpr int STAGE = std::max(WinoG48::STAGE, WinoG56::STAGE), PIXELS = std::max(WinoG48::PIXELS, WinoG56::PIXELS);
+  static constexpr bool MIX = true;
+};
 __device__ __forceinline__ f32x2 wlo(f32x4 v) { return __builtin_shufflevector(v, v, 0, 1); }
 __device__ __forceinline__ f32x2 whi(f32x4 v) { return __builtin_shufflevector(v, v, 2, 3); }
 }  // namespace
@@ -97,10 +111,12 @@ __device__ __forceinline__ f32x2 whi(f32x4 v) { return __builtin_shufflevector(v
 template <int NG, class G>
 __global__ __launch_bounds__(WNTH * NG, 4) void wino_f23_kernel(const ConvGemmParams p) {
   constexpr int NTH = WNTH * NG;
-  constexpr int BTY = G::BTY, BTX = G::BTX, WRH = G::RH, WRW = G::RW, PITCH = G::PITCH, WSTAGE = G::STAGE;
-  constexpr int WNLD = (WRH * WRW * (WKC / 4) + NTH - 1) / NTH;
+  constexpr int WSTAGE = G::STAGE;
+  constexpr int WNLD = (G::PIXELS * (WKC / 4) + NTH - 1) / NTH;
   const long long t_entry = (long long)__builtin_amdgcn_s_memrealtime();
   DC_KARG_TOUCH(ka0, ka1, ka2, ka3, ka4);
+  unsigned ka5 = 0;  // (mixed launches: the sixth line, the w_mix_* fields' (kernels.h asserts that they are one line), with the others)
+  if constexpr (G::MIX) asm volatile("s_load_dword %0, %1, %2" : "=&s"(ka5) : "s"(__builtin_amdgcn_kernarg_segment_ptr()), "n"(offsetof(ConvGemmParams, w_mix_na)));
   __shared__ __attribute__((aligned(16))) float stage[3][WSTAGE];
   // [g][i][b][tf][r][lane] partial inverse transforms: reuses the staging ring once the K loop is over (79 KB per
   // workgroup: two 8-wave workgroups fit the 160 KB of a CU)
@@ -135,12 +151,25 @@ __global__ __launch_bounds__(WNTH * NG, 4) void wino_f23_kernel(const ConvGemmPa
     lb = q * g8 + min(q, r8) + (blockIdx.x >> 3);
   }
   const int nt = dc_fastdiv(lb, p.w_div_nblk), blk = lb - nt * nblk;  // same-filter workgroups are adjacent in the logical grid
-  const int nph = dc_fastdiv(blk, p.w_div_nbyx), brem = blk - nph * (NBY * NBX);
+  const int nph = dc_fastdiv(blk, p.w_div_nbyx), brem = blk - nph * (G::MIX ? p.w_mix_nab : NBY * NBX);
   const int n = dc_fastdiv(nph, p.w_div_dd), ph = nph - n * (d * d);
   const int phy = dc_fastdiv(ph, p.w_div_d), phx = ph - phy * d;
-  const int by = dc_fastdiv(brem, p.w_div_nbx), bx = brem - by * NBX;
-  const int oy0 = 2 * BTY * by - 1, ox0 = 2 * BTX * bx - 1;  // phase-grid coordinates of staged pixel (0, 0): pad 1
+  // block (by, bx) of its region's block grid, whose first tile is (rty0, rtx0).  Mixed launches: blocks [0, nA) of a phase image are region
+  // A (4 x 8, from the grid's origin), the others region B (5 x 6, from its own origin): scalar selects, everything here is uniform
+  bool in_b = false;
+  int by, bx, rty0 = 0, rtx0 = 0, oy0, ox0;  // (oy0, ox0): phase-grid coordinates of staged pixel (0, 0): pad 1
+  if constexpr (G::MIX) {
+    in_b = brem >= p.w_mix_na;
+    const int br = in_b ? brem - p.w_mix_na : brem;
+    by = in_b ? dc_fastdiv(br, p.w_mix_div_nbx) : dc_fastdiv(br, p.w_div_nbx), bx = br - by * (in_b ? p.w_mix_NBX : NBX);
+    rty0 = in_b ? p.w_mix_ty0 : 0, rtx0 = in_b ? p.w_mix_tx0 : 0;
+    oy0 = 2 * (rty0 + (in_b ? WinoG56::BTY : WinoG48::BTY) * by) - 1, ox0 = 2 * (rtx0 + (in_b ? WinoG56::BTX : WinoG48::BTX) * bx) - 1;
+  } else {
+    by = dc_fastdiv(brem, p.w_div_nbx), bx = brem - by * NBX;
+    oy0 = 2 * G::BTY * by - 1, ox0 = 2 * G::BTX * bx - 1;
+  }
   DC_KARG_HOLD(ka0, ka1, ka2, ka3, ka4);  // the block decode above needed kernel arguments: the dummy loads have landed
+  if constexpr (G::MIX) asm volatile("" ::"s"(ka5));
   const int kg = lane >> 4;
   const int grp = NG == 1 ? 0 : __builtin_amdgcn_readfirstlane(wave >> 3);  // (an SGPR: it enters the filter loads' soffset)
   const int i = wave & 3, tf = (wave >> 2) & 1;
@@ -152,22 +181,51 @@ __global__ __launch_bounds__(WNTH * NG, 4) void wino_f23_kernel(const ConvGemmPa
   const __amdgpu_buffer_rsrc_t xr = dc_rsrc(reinterpret_cast<const float*>(p.x) + (long)n * p.x_img_stride, 0x7fffffffu);
   const __amdgpu_buffer_rsrc_t ur = dc_rsrc(p.w, 0x7fffffffu);
   unsigned gofs[WNLD];
-  int sofs[WNLD];
+  int sofs[WNLD], ofs_a, ofs_b;
+  if constexpr (!G::MIX) {
+    // (written out, not through index_setup below: the same statements behind a generic lambda cost the 16-wave 4 x 8 kernel the packed form of
+    // five fp32 instructions of its K loop in the compiler's late scheduling)
 #pragma unroll
-  for (int q = 0; q < WNLD; ++q) {
-    const int e = t + q * NTH;
-    const int pix = e / (WKC / 4), cq = e % (WKC / 4);
-    const int py = pix / WRW, px = pix % WRW;
-    const int iy = phy + d * (oy0 + py), ix = phx + d * (ox0 + px);
-    const bool ok = pix < WRH * WRW && oy0 + py >= 0 && ox0 + px >= 0 && iy < H && ix < W;
-    gofs[q] = ok ? (unsigned)(iy * p.x_row_stride + ix * C + cq * 4) * 4u : kOOB;
-    sofs[q] = (pix < WRH * WRW ? py * PITCH + px * WPSTR + cq * 4 : WSTAGE - 8 + (t & 1) * 4) >> 2;  // in float4 units (past the block: the dump slot)
+    for (int q = 0; q < WNLD; ++q) {
+      const int e = t + q * NTH;
+      const int pix = e / (WKC / 4), cq = e % (WKC / 4);
+      const int py = pix / G::RW, px = pix % G::RW;
+      const int iy = phy + d * (oy0 + py), ix = phx + d * (ox0 + px);
+      const bool ok = pix < G::PIXELS && oy0 + py >= 0 && ox0 + px >= 0 && iy < H && ix < W;
+      gofs[q] = ok ? (unsigned)(iy * p.x_row_stride + ix * C + cq * 4) * 4u : kOOB;
+      sofs[q] = (pix < G::PIXELS ? py * G::PITCH + px * WPSTR + cq * 4 : WSTAGE - 8 + (t & 1) * 4) >> 2;  // in float4 units (past the block: the dump slot)
+    }
+    // (a fragment row without a tile reads the last tile's patch: in range, a broadcast, and kept out of the stores below)
+    const int qt = G::NT < 16 ? min(lane & 15, G::NT - 1) : lane & 15;
+    const int r = qt / G::FC, c = G::fcol(tf) + qt % G::FC;
+    ofs_a = (2 * (G::frow(tf) + r) + ra) * G::PITCH + 2 * c * WPSTR + kg * 4;
+    ofs_b = (2 * (G::frow(tf) + r) + rb) * G::PITCH + 2 * c * WPSTR + kg * 4;
+  } else {
+    // the staging map and the per-lane patch-row offsets of a block of geometry GG
+    auto index_setup = [&](auto geom) {
+      using GG = decltype(geom);
+  #pragma unroll
+      for (int q = 0; q < WNLD; ++q) {
+        const int e = t + q * NTH;
+        const int pix = e / (WKC / 4), cq = e % (WKC / 4);
+        const int py = pix / GG::RW, px = pix % GG::RW;
+        const int iy = phy + d * (oy0 + py), ix = phx + d * (ox0 + px);
+        const bool ok = pix < GG::PIXELS && oy0 + py >= 0 && ox0 + px >= 0 && iy < H && ix < W;
+        gofs[q] = ok ? (unsigned)(iy * p.x_row_stride + ix * C + cq * 4) * 4u : kOOB;
+        sofs[q] = (pix < GG::PIXELS ? py * GG::PITCH + px * WPSTR + cq * 4 : GG::STAGE - 8 + (t & 1) * 4) >> 2;  // in float4 units (past the block: the dump slot)
+      }
+      // (a fragment row without a tile reads the last tile's patch: in range, a broadcast, and kept out of the stores below)
+      const int qt = GG::NT < 16 ? min(lane & 15, GG::NT - 1) : lane & 15;
+      const int r = qt / GG::FC, c = GG::fcol(tf) + qt % GG::FC;
+      ofs_a = (2 * (GG::frow(tf) + r) + ra) * GG::PITCH + 2 * c * WPSTR + kg * 4;
+      ofs_b = (2 * (GG::frow(tf) + r) + rb) * GG::PITCH + 2 * c * WPSTR + kg * 4;
+    };
+    if (in_b)
+      index_setup(WinoG56{});
+    else
+      index_setup(WinoG48{});
+    __builtin_assume((ofs_a & 3) == 0 && (ofs_b & 3) == 0);  // (every term is a multiple of 4 floats; behind the select the compiler no longer sees it, and would split the 16-byte LDS reads)
   }
-  // (a fragment row without a tile reads the last tile's patch: in range, a broadcast, and kept out of the stores below)
-  const int qt = G::NT < 16 ? min(lane & 15, G::NT - 1) : lane & 15;
-  const int r = qt / G::FC, c = G::fcol(tf) + qt % G::FC;
-  const int ofs_a = (2 * (G::frow(tf) + r) + ra) * PITCH + 2 * c * WPSTR + kg * 4;
-  const int ofs_b = (2 * (G::frow(tf) + r) + rb) * PITCH + 2 * c * WPSTR + kg * 4;
   f32x4 acc[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -310,9 +368,23 @@ __global__ __launch_bounds__(WNTH * NG, 4) void wino_f23_kernel(const ConvGemmPa
     }
     float v = a == 0 ? p0 + p1 + p2 : p1 - p2 - p3;
     const int q = 4 * (lane >> 4) + r4;  // D layout: row (tile in fragment) = 4*(lane/16) + r, col (channel) = lane%16
-    const int ty = by * BTY + G::frow(tf) + q / G::FC, tx = bx * BTX + G::fcol(tf) + q % G::FC;
+    int ty, tx;
+    bool has_tile;
+    auto tile_of = [&](auto geom) {
+      using GG = decltype(geom);
+      ty = rty0 + by * GG::BTY + GG::frow(tf) + q / GG::FC, tx = rtx0 + bx * GG::BTX + GG::fcol(tf) + q % GG::FC;
+      has_tile = GG::NT == 16 || q < GG::NT;
+    };
+    if constexpr (G::MIX) {
+      if (in_b)
+        tile_of(WinoG56{});
+      else
+        tile_of(WinoG48{});
+    } else {
+      tile_of(G{});
+    }
     const int oy = phy + d * (2 * ty + a), ox = phx + d * (2 * tx + bq);
-    if ((G::NT == 16 || q < G::NT) && oy < p.OH && ox < p.OW) {
+    if (has_tile && oy < p.OH && ox < p.OW) {
       const long off = (long)n * p.y_img_stride + (long)oy * p.y_row_stride + (long)ox * p.y_pix_stride + co;
       v = v * sc + sh;
       if (rbp) v += rbp[off];
@@ -376,6 +448,60 @@ long wino_grid_5x6(const ConvGemmParams& p) { return wino_grid_of<WinoG56>(p); }
 // exists in the ResNet nets this library lowers.)
 bool wino_fewer_blocks(const ConvGemmParams& p) { return wino_grid_of<WinoG56>(p) < wino_grid_of<WinoG48>(p); }
 
+// The cover of the mixed forms: ONE straight cut of the TY x TX tile grid, region A (rows or columns in front of the cut) on 4 x 8 blocks,
+// region B (from the cut on) on 5 x 6 blocks, either of them possibly empty; fewest blocks; on a tie a pure cover before a cut one (a 9 x 12
+// grid keeps its four 5 x 6 blocks although 2 + 2 blocks would do), then fewest 5 x 6 blocks, then the horizontal cut, then the smaller one.
+// Which side gets which geometry is no choice of its own: the block count of a cut at `a` with the sides swapped
+// is that of the cut at (extent - a).  A cut inside a 4 x 8 block would make region A's last blocks overhang region B; a cut on the next
+// multiple of the block's extent needs no more blocks, so only those (and the grid's far edge: the pure 4 x 8 cover) are candidates.
+WinoCover wino_plan_cover(int TY, int TX) {
+  WinoCover best{};
+  best.blocks = -1;
+  for (int vertical = 0; vertical < 2; ++vertical) {
+    const int ext = vertical ? TX : TY, step = vertical ? WinoG48::BTX : WinoG48::BTY;
+    for (int cut = 0; cut <= ext; cut = cut == ext ? ext + 1 : std::min(cut + step, ext)) {
+      WinoCover c{};
+      c.vertical = vertical, c.cut = cut;
+      const int aty = vertical ? TY : cut, atx = vertical ? cut : TX, bty = vertical ? TY : TY - cut, btx = vertical ? TX - cut : TX;
+      if (aty > 0 && atx > 0) c.a_nby = (aty + WinoG48::BTY - 1) / WinoG48::BTY, c.a_nbx = (atx + WinoG48::BTX - 1) / WinoG48::BTX;
+      if (bty > 0 && btx > 0) c.b_nby = (bty + WinoG56::BTY - 1) / WinoG56::BTY, c.b_nbx = (btx + WinoG56::BTX - 1) / WinoG56::BTX;
+      c.na = c.a_nby * c.a_nbx, c.nb = c.b_nby * c.b_nbx, c.blocks = c.na + c.nb;
+      c.b_ty0 = vertical ? 0 : cut, c.b_tx0 = vertical ? cut : 0;
+      const bool is_cut = c.na > 0 && c.nb > 0, best_cut = best.na > 0 && best.nb > 0;
+      if (best.blocks < 0 || c.blocks < best.blocks || (c.blocks == best.blocks && (is_cut < best_cut || (is_cut == best_cut && c.nb < best.nb)))) best = c;
+    }
+  }
+  return best;
+}
+static long wino_mix_grid_tiles(const ConvGemmParams& p, int& TY, int& TX) {
+  const int d = p.ddy;
+  TY = ((p.OH + d - 1) / d + 1) / 2, TX = ((p.OW + d - 1) / d + 1) / 2;
+  return (long)p.NB * d * d * wino_plan_cover(TY, TX).blocks * (p.Cout / WBN);
+}
+long wino_grid_mix(const ConvGemmParams& p) {
+  int TY, TX;
+  return wino_mix_grid_tiles(p, TY, TX);
+}
+// the mixed forms enter the per-shape timing where their cover needs strictly fewer blocks than both pure ones (at 544x736: res4 13 against
+// 15 / 16, res3 52 against 54 / 56, res2 198, by a vertical cut, against 204 / 224; the dilated res5 phase images keep the pure 5 x 6 cover) ...
+bool wino_mix_offered(int TY, int TX) {
+  return wino_plan_cover(TY, TX).blocks < std::min(wino_blocks(TY, TX, WinoG48::BTY, WinoG48::BTX), wino_blocks(TY, TX, WinoG56::BTY, WinoG56::BTX));
+}
+// ... and the launch is large enough for workgroups to matter: `images` (phase) images of TY x TX tiles and Cout output channels on 4 x 8 blocks
+// are at least kWinoMixMinWorkgroups workgroups, half of the 256 CUs.  A smaller launch leaves most of the chip's workgroup slots free with
+// either cover, its time is one workgroup's, alone and with neighbours in flight: what a shorter grid frees there nobody waits for, and the two
+// extra candidates would only lengthen the tuning of every small shape (a 72 x 104 image's res2 layers: 9 x 13 tiles, 5 blocks against 6, 24
+// workgroups).  The smallest launches of the benchmark shape that are offered: res4, 240 workgroups.  (128 comes from this argument about
+// workgroup slots, not from a measurement: no launch between 24 and 240 workgroups was timed on the mixed forms.)
+constexpr long kWinoMixMinWorkgroups = 128;
+bool wino_mix_offered_launch(int TY, int TX, long images, int Cout) {
+  return wino_mix_offered(TY, TX) && images * wino_blocks(TY, TX, WinoG48::BTY, WinoG48::BTX) * (Cout / WBN) >= kWinoMixMinWorkgroups;
+}
+bool wino_mix_fewer_blocks(const ConvGemmParams& p) {
+  int TY, TX;
+  return wino_mix_grid_tiles(p, TY, TX) > 0 && wino_mix_offered_launch(TY, TX, (long)p.NB * p.ddy * p.ddy, p.Cout);
+}
+
 size_t wino_packed_floats(int Cout, int Cin) { return (size_t)16 * Cout * Cin; }
 
 void wino_pack_filters(const float* g, int Cout, int Cin, float* out) {
@@ -396,7 +522,7 @@ void wino_pack_filters(const float* g, int Cout, int Cin, float* out) {
     }
 }
 
-// NG = 1: wino_f23 (8 waves per workgroup), 2: wino_f23_w16 (16); G: the block geometry (4 x 8, or 5 x 6: wino_f23_5x6, wino_f23_5x6_w16)
+// NG = 1: wino_f23 (8 waves per workgroup), 2: wino_f23_w16 (16); G: the block geometry (4 x 8, or 5 x 6: wino_f23_5x6, wino_f23_5x6_w16; both: below)
 template <int NG, class G>
 static int launch_wino_f23(const ConvGemmParams& p, void* stream) {
   if (p.esize != 4 || !wino_eligible(p)) return (int)hipErrorInvalidValue;
@@ -411,9 +537,33 @@ int launch_wino_f23_w16(const ConvGemmParams& p, void* stream) { return launch_w
 int launch_wino_f23_5x6(const ConvGemmParams& p, void* stream) { return launch_wino_f23<1, WinoG56>(p, stream); }
 int launch_wino_f23_5x6_w16(const ConvGemmParams& p, void* stream) { return launch_wino_f23<2, WinoG56>(p, stream); }
 
+// the mixed forms: region A's block grid in w_NBY / w_NBX / w_div_nbx as the 4 x 8 forms have it, region B's in w_mix_*
+template <int NG>
+static int launch_wino_f23_mix(const ConvGemmParams& p, void* stream) {
+  if (p.esize != 4 || !wino_eligible(p)) return (int)hipErrorInvalidValue;
+  int TY, TX;
+  const long grid = wino_mix_grid_tiles(p, TY, TX);
+  if (grid <= 0) return 0;
+  if (grid > 0x7fffffffL) return (int)hipErrorInvalidValue;
+  const WinoCover c = wino_plan_cover(TY, TX);
+  ConvGemmParams q = wino_launch_params(p, grid, WinoG48::BTY, WinoG48::BTX, 1);
+  q.w_NBY = c.a_nby, q.w_NBX = c.a_nbx;
+  q.w_nblk = p.NB * p.ddy * p.ddy * c.blocks;
+  q.w_mix_na = c.na, q.w_mix_nab = c.blocks, q.w_mix_ty0 = c.b_ty0, q.w_mix_tx0 = c.b_tx0, q.w_mix_NBX = c.b_nbx;
+  dc_magic((unsigned)q.w_nblk, q.w_div_nblk);
+  dc_magic((unsigned)c.blocks, q.w_div_nbyx);
+  dc_magic((unsigned)c.a_nbx, q.w_div_nbx);
+  dc_magic((unsigned)c.b_nbx, q.w_mix_div_nbx);
+  hipLaunchKernelGGL((wino_f23_kernel<NG, WinoGMix>), dim3((unsigned)grid), dim3(NG * WNTH), 0, (hipStream_t)stream, q);
+  return (int)hipGetLastError();
+}
+int launch_wino_f23_mix(const ConvGemmParams& p, void* stream) { return launch_wino_f23_mix<1>(p, stream); }
+int launch_wino_f23_mix_w16(const ConvGemmParams& p, void* stream) { return launch_wino_f23_mix<2>(p, stream); }
+
 long wino_form_blocks(int variant, int TY, int TX) {
   if (variant == kWinoVariant || variant == kWinoVariant16) return wino_blocks(TY, TX, WinoG48::BTY, WinoG48::BTX);
   if (variant == kWinoVariant56 || variant == kWinoVariant56x16) return wino_blocks(TY, TX, WinoG56::BTY, WinoG56::BTX);
+  if (variant == kWinoVariantMix || variant == kWinoVariantMix16) return wino_plan_cover(TY, TX).blocks;
   return -1;
 }
 

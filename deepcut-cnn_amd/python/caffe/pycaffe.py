@@ -173,6 +173,8 @@ def _load():
         "dc_conv_bf16_variant_name": (cp, [ci]),
         "dc_wino_half_pack": (ci, [C.c_void_p, ci, ci, ci, C.c_void_p, C.c_void_p]),
         "dc_wino_blocks": (ci, [cp, ci, ci]),
+        "dc_wino_cover": (ci, [ci, ci, C.c_void_p]),
+        "dc_wino_mix_offered": (ci, [ci, ci, ci, ci]),
         "dc_stream1x1_pack": (ci, [C.c_void_p, ci, ci, C.c_void_p]),
         "dc_stem7x7_pack": (ci, [C.c_void_p, ci, C.c_void_p]),
         "dc_stream1x1f_pack": (ci, [C.c_void_p, ci, ci, C.c_void_p]),
@@ -225,6 +227,22 @@ def conv_variants_bf16():
 def wino_blocks(tile, tiles_y, tiles_x):
     """dc_wino_blocks: the tile blocks the float32 Winograd form `tile` needs for a tiles_y x tiles_x tile grid (-1: not such a form)."""
     return _lib.dc_wino_blocks(tile.encode(), int(tiles_y), int(tiles_x))
+
+
+def wino_cover(tiles_y, tiles_x):
+    """dc_wino_cover: the cover of a tiles_y x tiles_x tile grid by 4 x 8- and 5 x 6-tile blocks that the forms wino_f23_mix / wino_f23_mix_w16
+    run, as a dict: vertical, cut, blocks, na, nb, a_nby, a_nbx, b_nby, b_nbx, b_ty0, b_tx0, offered (None on bad arguments)."""
+    out = (C.c_int * 12)()
+    if _lib.dc_wino_cover(int(tiles_y), int(tiles_x), C.cast(out, C.c_void_p)) < 0:
+        return None
+    keys = ("vertical", "cut", "blocks", "na", "nb", "a_nby", "a_nbx", "b_nby", "b_nbx", "b_ty0", "b_tx0", "offered")
+    return dict(zip(keys, (int(v) for v in out)))
+
+
+def wino_mix_offered(tiles_y, tiles_x, images, cout):
+    """dc_wino_mix_offered: whether the per-shape timing tries wino_f23_mix / wino_f23_mix_w16 for a 3x3 layer of `images` (phase) images of
+    tiles_y x tiles_x tiles and cout output channels (-1 on bad arguments)."""
+    return _lib.dc_wino_mix_offered(int(tiles_y), int(tiles_x), int(images), int(cout))
 
 
 def stream1x1_pack(g):

@@ -16,12 +16,18 @@ is set (dc_net_set_tile rewrites it); the reference has nothing to mirror here (
 # the two forms of the Winograd kernel (8 / 16 waves per workgroup, csrc/wino_f32.hip): wherever one is in use the other is eligible, and
 # which one is faster is exactly a question of load (16 waves win a launch of at most one workgroup per CU running alone, 8 waves win as
 # soon as workgroups share CUs) — so the sibling is tried even for a signature whose choice came from a cache file, without timings
-_WINO_SIBLING = {"wino_f23": "wino_f23_w16", "wino_f23_w16": "wino_f23", "wino_f23_5x6": "wino_f23_5x6_w16", "wino_f23_5x6_w16": "wino_f23_5x6"}
+# (the same holds across block geometries: the forms of one kernel on covers of fewer blocks — 5 x 6, mixed — run one round of workgroups
+# alone like the 4 x 8 ones, within the noise of the isolated timing, so which of them are among the first `max_candidates` is chance; with
+# forwards in flight the freed workgroup slots are another forward's.  Every timed form of this family within `margin` is therefore tried.)
+_WINO_SIBLING = {"wino_f23": "wino_f23_w16", "wino_f23_w16": "wino_f23", "wino_f23_5x6": "wino_f23_5x6_w16", "wino_f23_5x6_w16": "wino_f23_5x6",
+                 "wino_f23_mix": "wino_f23_mix_w16", "wino_f23_mix_w16": "wino_f23_mix"}
 
 
 def tune_in_flight(nets, run, top=6, margin=1.20, min_gain=0.01, reps=3, max_candidates=2, log=None):
     """nets: the executors of ONE model (a net and its clones), all at the shape to tune, each having run a forward.
     run(): enqueue the representative load on the executors, synchronise, return the wall seconds.
+    Per signature the first max_candidates + 1 isolated timings are candidates (within `margin` of the best), and beyond them every timed form of
+    the float32 Winograd kernel within `margin` (see _WINO_SIBLING above): for that family max_candidates is no limit.
     Returns {"before": s, "after": s, "changed": [(signature, old tile, new tile, seconds before, seconds after)], "runs": n,
              "skipped": signatures left alone because no isolated timings exist for them (tiles read from a DC_TUNE_CACHE file)}."""
     runs = [0]
@@ -57,7 +63,8 @@ def tune_in_flight(nets, run, top=6, margin=1.20, min_gain=0.01, reps=3, max_can
         cur = sig["tile"]
         keep = cur
         try:
-            for tile, us in sig["timed"][:max_candidates + 1]:
+            family = [c for c in sig["timed"][max_candidates + 1:] if c[0] in _WINO_SIBLING]
+            for tile, us in sig["timed"][:max_candidates + 1] + family:
                 if tile == cur or us > margin * best_alone:
                     continue
                 put(sig["signature"], tile)

@@ -403,6 +403,19 @@ int dc_wino_half_pack(const float* g, int cout, int cin, int rowscale, float* ou
  * 4 x 8 tiles; `wino_f23_5x6`, `wino_f23_5x6_w16`: 5 x 6) needs for a grid of tiles_y x tiles_x 2x2-output tiles; -1 for any other name.
  * The 5 x 6 forms are candidates of the per-shape timing where they need strictly fewer blocks.  Diagnostics / tests.               */
 int dc_wino_blocks(const char* tile, int tiles_y, int tiles_x);
+/* the cover of a tiles_y x tiles_x tile grid that `wino_f23_mix` / `wino_f23_mix_w16` run (`dc_wino_blocks` answers for these names too): one
+ * straight cut, region A in front of it on 4 x 8-tile blocks from the grid's origin, region B behind it on 5 x 6-tile blocks; fewest blocks,
+ * on a tie a pure cover before a cut one, then fewest 5 x 6 blocks; either region may be empty.  out[12] = {vertical cut (else horizontal), cut (tile row / column), blocks,
+ * blocks of A, of B, A's block rows, block columns, B's block rows, block columns, B's first tile row, first tile column, offered};
+ * offered: the cover needs strictly fewer blocks than both pure ones — one of the two conditions under which the per-shape timing tries the mixed
+ * forms; the other is the size of the launch (`dc_wino_mix_offered`).
+ * Returns the block count, -1 on bad arguments.  A pure function: no device.  Diagnostics / tests.                                   */
+int dc_wino_cover(int tiles_y, int tiles_x, int* out);
+/* 1 where the per-shape timing tries the mixed forms for a 3x3 layer of `images` images (batch x dilation^2 phase images) of tiles_y x tiles_x
+ * tiles and cout output channels: the cover is `offered` (above) and the launch on 4 x 8 blocks has at least 128 workgroups, half the CUs — a
+ * smaller launch leaves most workgroup slots of the chip free with either cover (a bound from that argument, not from a measurement).  0 elsewhere (`set_tile` and tune caches still take the forms
+ * wherever the kernel is eligible), -1 on bad arguments.                                                                              */
+int dc_wino_mix_offered(int tiles_y, int tiles_x, int images, int cout);
 
 /* the filter images of the two float16 kernels added in round 6, made on the host exactly as the lowering makes them (diagnostics / tests:
  * tests/test_stream_pack.py emulates the matrix instruction's operand layout on them; the reference has no counterpart — its 1x1 layers

@@ -52,6 +52,8 @@ def label(name):
         return "wino_h23 (Winograd F(2x2,3x3), float16)"
     if "wino_f23" in name:  # wino_f23_kernel<1, ...WinoGeom<2, 8, false, 672> > / <2, ...> (demangled) or ...wino_f23_kernelILi2E... (mangled): 8 / 16 waves per workgroup
         w16 = "wino_f23_kernel<2" in name or "wino_f23_kernelILi2E" in name
+        if "WinoGMix" in name:  # blocks of both geometries in one launch
+            return "wino_f23_mix_w16 (Winograd F(2x2,3x3), 4x8- and 5x6-tile blocks, 16 waves)" if w16 else "wino_f23_mix (Winograd F(2x2,3x3), 4x8- and 5x6-tile blocks)"
         if "WinoGeom<5, 3" in name or "WinoGeomILi5ELi3E" in name:  # the 5 x 6-tile blocks
             return "wino_f23_5x6_w16 (Winograd F(2x2,3x3), 5x6-tile blocks, 16 waves)" if w16 else "wino_f23_5x6 (Winograd F(2x2,3x3), 5x6-tile blocks)"
         return "wino_f23_w16 (Winograd F(2x2,3x3), 16 waves)" if w16 else "wino_f23 (Winograd F(2x2,3x3))"
