@@ -721,17 +721,24 @@ int dc_group_forward_images(dc_group* group, const unsigned char* const* images,
                             double* const* pose, void* stream) {
   return group_forward_images(group, images, n, height, width, scale, nullptr, is_device, prob, loc_pred, next_pred, pose, stream);
 }
-int dc_group_forward_boxes(dc_group* group, const unsigned char* image, int height, int width, int is_device, const int* boxes,
-                           const double* scales, int n, const double* pyramid_scales, int canvas_h, int canvas_w, float* const* prob,
-                           float* const* loc_pred, float* const* next_pred, double* const* pose, void* stream) {
+// the argument checks and the call of both box entries of a group (mirror null: nobody is mirrored)
+static int group_forward_boxes(dc_group* group, const unsigned char* image, int height, int width, int is_device, const int* boxes,
+                               const double* scales, int n, const double* pyramid_scales, int canvas_h, int canvas_w, const int* mirror,
+                               float* const* prob, float* const* loc_pred, float* const* next_pred, double* const* pose, void* stream) {
   REQUIRE(group);
   if (n == 0) return DC_OK;
   REQUIRE(image);
   REQUIRE(pyramid_scales);
   return guard([&] {
     G(group)->forward_boxes(image, height, width, is_device != 0, boxes, scales, n, pyramid_scales, canvas_h, canvas_w, prob, loc_pred,
-                            next_pred, pose, stream);
+                            next_pred, pose, stream, mirror);
   });
+}
+int dc_group_forward_boxes(dc_group* group, const unsigned char* image, int height, int width, int is_device, const int* boxes,
+                           const double* scales, int n, const double* pyramid_scales, int canvas_h, int canvas_w, float* const* prob,
+                           float* const* loc_pred, float* const* next_pred, double* const* pose, void* stream) {
+  return group_forward_boxes(group, image, height, width, is_device, boxes, scales, n, pyramid_scales, canvas_h, canvas_w, nullptr, prob,
+                             loc_pred, next_pred, pose, stream);
 }
 // multi-scale fusion: a null `scales` is the library's to refuse (DC_EINVAL naming it), like every other argument of the rule.  The plain
 // entries are the mirrored ones with no mirror table.
@@ -789,6 +796,29 @@ int dc_group_assemble_people_mirrored(dc_group* group, const double* scales, int
     Net::AssembleParams q{p->scale, p->threshold, p->radius, p->max_det, p->max_cost, p->seed_threshold, p->max_people, p->min_joints};
     NetGroup::FuseMirror m;
     G(group)->assemble_people(scales, base, q, n_edges, edges, mean, stdev, joint_order, n_people, people, cand, cost, mirror_args(fm, m));
+  });
+}
+// single-person and box poses from the fused maps (net_group.cpp decode_pose / decode_boxes)
+int dc_group_decode_pose(dc_group* group, const double* scales, int base, const dc_fuse_mirror* fm, double* pose, int is_device, void* stream) {
+  REQUIRE(group);
+  REQUIRE(pose);
+  return guard([&] {
+    NetGroup::FuseMirror m;
+    G(group)->decode_pose(scales, base, pose, is_device != 0, stream, mirror_args(fm, m));
+  });
+}
+int dc_group_forward_boxes_mirrored(dc_group* group, const unsigned char* image, int height, int width, int is_device, const int* boxes,
+                                    const double* scales, int n, const double* pyramid_scales, int canvas_h, int canvas_w, const int* mirror,
+                                    float* const* prob, float* const* loc_pred, float* const* next_pred, void* stream) {
+  return group_forward_boxes(group, image, height, width, is_device, boxes, scales, n, pyramid_scales, canvas_h, canvas_w, mirror, prob,
+                             loc_pred, next_pred, nullptr, stream);
+}
+int dc_group_decode_boxes(dc_group* group, const double* pyramid_scales, int base, const dc_fuse_mirror* fm, float* prob, float* loc_pred,
+                          double* pose, int is_device, void* stream) {
+  REQUIRE(group);
+  return guard([&] {
+    NetGroup::FuseMirror m;
+    G(group)->decode_boxes(pyramid_scales, base, prob, loc_pred, pose, is_device != 0, stream, mirror_args(fm, m));
   });
 }
 int dc_comm_create(int nexec, const int* devices, int transport, dc_comm** out) {

@@ -101,7 +101,8 @@ __global__ __launch_bounds__(256) void box_prep_kernel(BoxPrepParams p) {
         const int* kk = it.x_coeffs + (long)x * it.x_ksize;
         int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
         for (int k = 0; k < cnt; ++k) {
-          const int sx = min(xmin + k, it.w - 1);
+          int sx = min(xmin + k, it.w - 1);
+          if (p.mirror) sx = it.w - 1 - sx;  // the mirrored crop: column x of it is crop column w - 1 - x (after the clamp, as image_resample_x_kernel)
           const int c = kk[k];
           a0 += row[sx * 3 + 0] * c;
           a1 += row[sx * 3 + 1] * c;
@@ -109,7 +110,8 @@ __global__ __launch_bounds__(256) void box_prep_kernel(BoxPrepParams p) {
         }
         b0 = clip8_fixed(a0), b1 = clip8_fixed(a1), b2 = clip8_fixed(a2);
       } else {
-        const int sx = min(x, it.w - 1);
+        int sx = min(x, it.w - 1);
+        if (p.mirror) sx = it.w - 1 - sx;
         b0 = row[sx * 3 + 0], b1 = row[sx * 3 + 1], b2 = row[sx * 3 + 2];
       }
     };

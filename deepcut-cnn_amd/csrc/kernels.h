@@ -389,7 +389,9 @@ struct FuseMember {
   int H, W;
   double q;
 };
-// on marks a member that saw the image flipped left to right, ws = (image width - 1) * the member's scale
+// One record per (member, image), [M][NB]: on marks a member that saw the image flipped left to right, ws = (width - 1) * the scale the
+// member ran that image at — the image entries fill every image of a member with (image width - 1) * the member's scale, the box entry
+// (dc_group_decode_boxes) gives every box its own crop width and scale
 struct FuseFlip {
   double ws;
   int on, pad_;
@@ -398,8 +400,9 @@ struct FuseFlip {
 // (sum over m ascending of bilinear sample of member m at the cell's point * gain[m*Ctot + ch] + bias[m*Ctot + ch]) * (1 / M).
 // Channels [0, C[0]) are map 0, the next C[1] map 1, the last C[2] map 2; a map with C[k] = 0 takes no part (its ptr is not read).
 // members / gain / bias are device tables ([M], [M][Ctot], [M][Ctot]); ekind is the members' common element type.
-// flip and src both null: no member is mirrored, and neither table is read.  Both given ([M], [M][Ctot]): the same kernel body with two
-// differences — a member with flip[m].on is sampled at the column u = ((ws - (8c + 4) q) - 4) / 8, and output channel ch reads from
+// flip and src both null: no member is mirrored, and neither table is read.  Both given ([M][NB], [M][Ctot]): the same kernel body with two
+// differences — image b of a member with flip[m*NB + b].on is sampled at the column u = ((ws - (8c + 4) q) - 4) / 8, clamped to the member's
+// whole map like every other sample, and output channel ch reads from
 // member m the channel src[m*Ctot + ch] WITHIN its map (0 .. C[k] - 1; the identity for an unmirrored member); the sign changes are in
 // gain / bias.  Exactly one of the two null: hipErrorInvalidValue.
 int launch_fuse_maps(const FuseMember* members, const FuseFlip* flip, const float* gain, const float* bias, const int* src, int M, int ekind,
@@ -410,7 +413,8 @@ int launch_fuse_maps(const FuseMember* members, const FuseFlip* flip, const floa
 // mean subtraction and the zero canvas, written straight into the network's NHWC input image.
 // mirror: the image is read flipped left to right — source column w - 1 - x wherever column x of the unpadded image would be read, so
 // the replicate padding repeats the FLIPPED image's last column (source column 0) — and everything after that is unchanged: the result
-// is, bit for bit, what the unmirrored path makes of the host-flipped image (dc_group_forward_images_mirrored).
+// is, bit for bit, what the unmirrored path makes of the host-flipped image (dc_group_forward_images_mirrored).  BoxPrepParams::mirror is
+// the same for every crop of a launch: crop column it.w - 1 - sx wherever column sx of the unpadded crop would be read, after the clamp.
 struct ImagePrepParams {
   const unsigned char* src;  // [n][h][w][3] BGR uint8
   int n, h, w;
@@ -454,6 +458,7 @@ struct BoxPrepParams {
   void* dst;                 // [n][out_h][out_w][dst_cp] float, _Float16 or __bf16 (dst_ekind); pad channels zeroed
   int dst_ekind, dst_cp;
   float mean[3];
+  int mirror;                // 0 / 1: every crop of this launch is read flipped left to right (dc_group_forward_boxes_mirrored)
 };
 int launch_box_prep(const BoxPrepParams& p, void* stream);
 

@@ -346,8 +346,10 @@ struct Net {
   void prep_images(const unsigned char* bgr, int n, int h, int w, double scale, bool is_device, void* s, bool mirror = false);
   // front half of forward_boxes (arguments already checked): the boxes' canvases in ONE launch, and the per-box decode table;
   // returns the device copy of the image the launch reads (a host image is uploaded once)
+  // mirror: every crop is read flipped left to right (BoxPrepParams::mirror; NetGroup::forward_boxes hands it down), and the member
+  // remembers that its last box batch was (box_mirror_)
   const unsigned char* prep_boxes(const unsigned char* bgr, int h, int w, bool is_device, const int* boxes, const double* scales, int n,
-                                  int canvas_h, int canvas_w, void* s);
+                                  int canvas_h, int canvas_w, void* s, bool mirror = false);
   // back half: the poses of the boxes of the last prep_boxes, in image coordinates (host or device `out`, n x 5 x J doubles)
   void decode_boxes(double* out, bool is_device, void* s);
   std::string plan_text();
@@ -402,6 +404,7 @@ struct Net {
   size_t box_cap_ = 0;
   std::vector<unsigned char> box_host_;  // the host side of that table (outlives its upload)
   int box_n_ = 0;                     // boxes of the last prep_boxes
+  bool box_mirror_ = false;           // ... and whether it read them flipped left to right
 };
 
 struct DevBuf {  // a grow-only device buffer
@@ -473,10 +476,11 @@ struct NetGroup {
                       float* const* prob, float* const* loc, float* const* next, double* const* pose, void* user_stream,
                       const int* mirror = nullptr);
   // box entry (Net::forward_boxes): member c takes every box at scales[i] * pyramid[c] on a canvas of box_member_canvas(canvas_h / w,
-  // pyramid[c]); the image is uploaded once, each member pre-processes its boxes in one launch, then ONE grouped forward
+  // pyramid[c]); the image is uploaded once, each member pre-processes its boxes in one launch, then ONE grouped forward.
+  // mirror (dc_group_forward_boxes_mirrored): [M] 0/1, null = none; a marked member pre-processes every crop flipped left to right
   void forward_boxes(const unsigned char* bgr, int h, int w, bool is_device, const int* boxes, const double* scales, int n,
                      const double* pyramid, int canvas_h, int canvas_w, float* const* prob, float* const* loc, float* const* next,
-                     double* const* pose, void* user_stream);
+                     double* const* pose, void* user_stream, const int* mirror = nullptr);
   // Multi-scale fusion (dc_group_fuse_maps; the rule: include/deepcut_hip.h): the maps of the members' LAST forwards — member c holds the
   // same images at scales[c] — resampled onto member `base`'s grid, brought into its units and averaged, in ONE launch (launch_fuse_maps)
   // into a float32 buffer the group owns.  Everything runs on the group's stream (the first member's own; fuse_maps: or the caller's), so
@@ -503,6 +507,15 @@ struct NetGroup {
   void assemble_people(const double* scales, int base, const Net::AssembleParams& p, int n_edges, const int* edges, const double* mean,
                        const double* stdev, const int* joint_order, int* n_people, double* people, int* cand, double* cost,
                        const FuseMirror* fm = nullptr);
+  // Single-person pose from the fused maps (dc_group_decode_pose): prob and loc_pred fused as detect_parts fuses them, then
+  // launch_pose_decode on the fused float32 views at scales[base] -> pose [NB][5][J], host or device, stream as fuse_maps
+  void decode_pose(const double* scales, int base, double* pose, bool is_device, void* user_stream, const FuseMirror* fm = nullptr);
+  // The box entry's fused decode (dc_group_decode_boxes) on the boxes of the members' last forward_boxes: prob and loc_pred fused with the
+  // pyramid scales as member scales and, for a mirrored member, one reflected column per box (its crop width and the scale the member ran
+  // it at, from the member's own box table); then launch_pose_decode_items on the fused views with the base member's decode items.
+  // fm->image_width is not read.  Any of prob / loc / pose null: not returned.
+  void decode_boxes(const double* pyramid, int base, float* prob, float* loc, double* pose, bool is_device, void* user_stream,
+                    const FuseMirror* fm = nullptr);
   // lanes: 0 = automatic (2 members: two lanes; 3: one; 4 and more: two), else that many (at most one per member); every merged plan is dropped
   void set_lanes(int n);
   int lanes() const { return cur_ ? cur_->nlanes : lanes_opt_; }
@@ -553,12 +566,16 @@ struct NetGroup {
     int image_width = 0;
   };
   MirrorPlan check_mirror(const char* who, const FuseMirror* fm, int base, const bool use[3], int n_edges, const int C[3]) const;
-  FusedMaps fuse(const double* scales, int base, const bool use[3], const double* mean, const double* stdev, void* s, const MirrorPlan& mp);
+  // ws: null = every image of a mirrored member m reflects at (mp.image_width - 1) * scales[m]; else [M][NB], the box entry's own
+  FusedMaps fuse(const double* scales, int base, const bool use[3], const double* mean, const double* stdev, void* s, const MirrorPlan& mp,
+                 const std::vector<double>* ws = nullptr);
+  // the fused maps k with dst[k] != null as NCHW float32 to host or device destinations, enqueued on s (fuse_maps, decode_boxes)
+  void emit_fused(const FusedMaps& fm, float* const dst[3], bool is_device, void* s);
   DevBuf fused_, fuse_table_, fuse_stage_, people_scratch_;
   void* fuse_event_ = nullptr;    // recorded behind the last fusion call's work ...
   void* fuse_stream_ = nullptr;   // ... on this stream
   void fuse_done(void* s);        // record it
-  std::vector<unsigned char> fuse_table_host_;  // what fuse_table_ holds: the members' descriptors, then gain and bias [M][channels] (a member mirrored: then the FuseFlip records and the source channels)
+  std::vector<unsigned char> fuse_table_host_;  // what fuse_table_ holds: the members' descriptors, then gain and bias [M][channels] (a member mirrored: then the FuseFlip records [M][NB] and the source channels)
 };
 
 // ---- runtime.cpp: pinned host memory (dc_host_alloc / dc_host_free) ---------------------------------------------------------

@@ -731,7 +731,7 @@ void NetGroup::forward_images(const unsigned char* const* bgr, const int* n, con
 
 void NetGroup::forward_boxes(const unsigned char* bgr, int h, int w, bool is_device, const int* boxes, const double* scales, int n,
                              const double* pyramid, int canvas_h, int canvas_w, float* const* prob, float* const* loc, float* const* next,
-                             double* const* pose, void* user_stream) {
+                             double* const* pose, void* user_stream, const int* mirror) {
   if (!pyramid) throw DcError(DC_EINVAL, "group forward_boxes: null pyramid scales");
   // every member's boxes and canvas are checked before any device work; the base canvas itself must be a multiple of 8 too
   if (n < 0) throw DcError(DC_EINVAL, "forward_boxes: n must not be negative");
@@ -761,7 +761,7 @@ void NetGroup::forward_boxes(const unsigned char* bgr, int h, int w, bool is_dev
   const unsigned char* src = bgr;
   bool dev = is_device;
   for (size_t c = 0; c < nets.size(); ++c) {
-    src = nets[c]->prep_boxes(src, h, w, dev, boxes, sc[c].data(), n, ch[c], cw[c], s);  // the image crosses PCIe once
+    src = nets[c]->prep_boxes(src, h, w, dev, boxes, sc[c].data(), n, ch[c], cw[c], s, mirror && mirror[c] != 0);  // the image crosses PCIe once
     dev = true;
   }
   enqueue(s);
@@ -886,12 +886,12 @@ NetGroup::MirrorPlan NetGroup::check_mirror(const char* who, const FuseMirror* f
 }
 
 // The launch.  The table on the device — the members' descriptors, then gain and bias [M][channels], and when a member is mirrored
-// their FuseFlip records and the source channels [M][channels] behind them — is uploaded when it differs from the one already there (a
+// their FuseFlip records [M][NB] and the source channels [M][channels] behind them — is uploaded when it differs from the one already there (a
 // new pyramid, a reallocated map), so the usual call is the one kernel and nothing else.  An unmirrored member's rows are the rule of
 // dc_group_fuse_maps with the identity as source; a mirrored member's follow dc_group_fuse_maps_mirrored (include/deepcut_hip.h).
 // PARITY UNPINNED BY THE REFERENCE, which mirrors nothing on the pose path.
 NetGroup::FusedMaps NetGroup::fuse(const double* scales, int base, const bool use[3], const double* mean, const double* stdev, void* s,
-                                   const MirrorPlan& mp) {
+                                   const MirrorPlan& mp, const std::vector<double>* ws) {
   const int M = (int)nets.size();
   // the buffers below are shared by every call: work that the previous call left running on ANOTHER stream (an asynchronous
   // fuse_maps on a caller's stream) finishes before this call's stream touches them
@@ -923,14 +923,17 @@ NetGroup::FusedMaps NetGroup::fuse(const double* scales, int base, const bool us
   // gain and bias, in double, stored as float; flip and src only when a member is mirrored
   const size_t rows = (size_t)M * Ctot;
   std::vector<float> gb(2 * rows);
-  std::vector<FuseFlip> flip(mirrored ? (size_t)M : 0);
+  if (ws && ws->size() != (size_t)M * NB) throw DcError(DC_EINVAL, "fuse_maps: one reflected column per member and image");
+  std::vector<FuseFlip> flip(mirrored ? (size_t)M * NB : 0);  // [M][NB]
   std::vector<int> src(mirrored ? rows : 0);
   auto mu = [&](int l, int k) { return mean ? mean[2 * l + k] : 0.0; };
   auto sd = [&](int l, int k) { return stdev ? stdev[2 * l + k] : 1.0; };
   for (int m = 0; m < M; ++m) {
     const bool on = mirrored && mp.on[(size_t)m] != 0;
     const double rho = m == base ? 1.0 : scales[base] / scales[m];
-    if (mirrored) flip[(size_t)m] = FuseFlip{on ? (double)(mp.image_width - 1) * scales[m] : 0.0, on ? 1 : 0, 0};
+    // (the image entries: one value for every image of the member; the box entry: the caller's own per box)
+    for (int b = 0; mirrored && b < NB; ++b)
+      flip[(size_t)m * NB + b] = FuseFlip{!on ? 0.0 : ws ? (*ws)[(size_t)m * NB + b] : (double)(mp.image_width - 1) * scales[m], on ? 1 : 0, 0};
     auto row = [&](int at, float gain, float bias, int from) {
       gb[(size_t)m * Ctot + at] = gain, gb[rows + (size_t)m * Ctot + at] = bias;
       if (mirrored) src[(size_t)m * Ctot + at] = from;
@@ -1005,11 +1008,17 @@ void NetGroup::fuse_maps(const double* scales, int base, int n_edges, const doub
   nets[0]->ensure_device();
   void* s = user_stream ? user_stream : stream();
   const FusedMaps fm = fuse(scales, base, use, mean, stdev, s, mp);
+  emit_fused(fm, dst, is_device, s);
+  fuse_done(s);
+  if (!(is_device && (user_stream || own_async))) HIPCHECK(hipStreamSynchronize((hipStream_t)s));
+}
+
+void NetGroup::emit_fused(const FusedMaps& fm, float* const dst[3], bool is_device, void* s) {
   size_t total = 0;
   for (int k = 0; k < 3; ++k) total += (size_t)fm.map[k].NB * fm.map[k].C * fm.map[k].H * fm.map[k].W;
   float* stage = is_device ? nullptr : (float*)fuse_stage_.get(total * sizeof(float));
   for (int k = 0; k < 3; ++k) {
-    if (!use[k]) continue;
+    if (!dst[k]) continue;
     const Net::MapRef& r = fm.map[k];
     const size_t cnt = (size_t)r.NB * r.C * r.H * r.W;
     float* to = is_device ? dst[k] : stage;
@@ -1018,6 +1027,100 @@ void NetGroup::fuse_maps(const double* scales, int base, int n_edges, const doub
       HIPCHECK(hipMemcpyAsync(dst[k], stage, cnt * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)s));
       stage += cnt;
     }
+  }
+}
+
+// ---- single-person and box poses from the fused maps (dc_group_decode_pose, dc_group_decode_boxes; include/deepcut_hip.h) ---------------
+// PARITY UNPINNED BY THE REFERENCE: the reference decodes every scale on its own and keeps one (estimate_pose.py:119-126); decoding the
+// fused maps is this project's own rule.
+// the pose doubles of a decode on `s`: straight into a device destination, or through the group's scratch to the host
+template <typename Launch>
+static void decode_to(DevBuf& scratch, size_t cnt, double* out, bool is_device, void* s, const Launch& launch) {
+  if (is_device) {
+    KCHECK(launch(out));
+    return;
+  }
+  double* dev = (double*)scratch.get(cnt * sizeof(double));
+  KCHECK(launch(dev));
+  HIPCHECK(hipMemcpyAsync(out, dev, cnt * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)s));
+}
+
+void NetGroup::decode_pose(const double* scales, int base, double* pose, bool is_device, void* user_stream, const FuseMirror* fm_in) {
+  const bool use[3] = {true, true, false};
+  int C[3], NB;
+  check_fuse("decode_pose", scales, base, use, 0, nullptr, nullptr, C, NB);
+  const MirrorPlan mp = check_mirror("decode_pose", fm_in, base, use, 0, C);
+  if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "decode_pose() in CPU mode");
+  const bool own_async = user_stream == (void*)-1;
+  if (own_async) user_stream = nullptr;
+  nets[0]->ensure_device();
+  void* s = user_stream ? user_stream : stream();
+  const FusedMaps fm = fuse(scales, base, use, nullptr, nullptr, s, mp);
+  const Net::MapRef &P = fm.map[0], &L = fm.map[1];
+  if (L.C != 2 * P.C) throw DcError(DC_ESHAPE, "decode_pose: loc_pred must have 2 channels per joint and the score map's size");
+  decode_to(people_scratch_, (size_t)P.NB * 5 * P.C, pose, is_device, s, [&](double* to) {
+    return launch_pose_decode(P.ptr, P.cp, P.c0, L.ptr, L.cp, L.c0, P.ek, P.NB, P.H, P.W, P.C, scales[base], to, s);
+  });
+  fuse_done(s);
+  if (!(is_device && (user_stream || own_async))) HIPCHECK(hipStreamSynchronize((hipStream_t)s));
+}
+
+void NetGroup::decode_boxes(const double* pyramid, int base, float* prob, float* loc, double* pose, bool is_device, void* user_stream,
+                            const FuseMirror* fm_in) {
+  const std::string w = "decode_boxes: ";
+  const int M = (int)nets.size();
+  float* const dst[3] = {prob, loc, nullptr};
+  const bool use[3] = {true, true, false};
+  int C[3], NB;
+  const int n = nets[0]->box_n_;
+  for (int m = 1; m < M; ++m)
+    if (nets[(size_t)m]->box_n_ != n)
+      throw DcError(DC_EINVAL, w + "member " + std::to_string(m) + " holds " + std::to_string(nets[(size_t)m]->box_n_) + " boxes from its last forward_boxes, member 0 holds " +
+                                   std::to_string(n) + " (every member holds the same boxes)");
+  check_fuse("decode_boxes", pyramid, base, use, 0, nullptr, nullptr, C, NB);
+  // (the reflected columns come from the members' own box tables: image_width is not read, and check_mirror's test of it is kept quiet)
+  FuseMirror patched{};
+  if (fm_in) patched = *fm_in, patched.image_width = 1;
+  const MirrorPlan mp = check_mirror("decode_boxes", fm_in ? &patched : nullptr, base, use, 0, C);
+  for (int m = 0; m < M; ++m) {
+    const bool said = !mp.on.empty() && mp.on[(size_t)m] != 0, was = nets[(size_t)m]->box_mirror_;
+    if (said != was)
+      throw DcError(DC_EINVAL, w + "member " + std::to_string(m) + " is " + (said ? "" : "not ") + "marked as mirrored, its last box batch was " +
+                                   (was ? "" : "not ") + "mirrored (dc_group_forward_boxes_mirrored)");
+  }
+  if (n <= 0) throw DcError(DC_EINVAL, w + "the members hold no boxes: run forward_boxes first");
+  for (int m = 0; m < M; ++m) {
+    const Net& net = *nets[(size_t)m];
+    const size_t prep_b = ((size_t)n * sizeof(BoxPrepItem) + 15) / 16 * 16;
+    if (NB != n || net.box_host_.size() != prep_b + (size_t)n * sizeof(PoseDecodeItem))
+      throw DcError(DC_EINVAL, w + "the maps of member " + std::to_string(m) + " are not those of its last boxes (" + std::to_string(NB) + " images, " +
+                                   std::to_string(n) + " boxes)");
+  }
+  if (!prob && !loc && !pose) return;
+  if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "decode_boxes() in CPU mode");
+  // per (member, box) the reflected column's ws = (crop width - 1) * the scale the member ran that box at
+  const size_t prep_b = ((size_t)n * sizeof(BoxPrepItem) + 15) / 16 * 16;
+  std::vector<double> ws((size_t)M * n, 0.0);
+  for (int m = 0; m < M && !mp.on.empty(); ++m) {
+    if (!mp.on[(size_t)m]) continue;
+    const BoxPrepItem* items = reinterpret_cast<const BoxPrepItem*>(nets[(size_t)m]->box_host_.data());
+    const PoseDecodeItem* dec = reinterpret_cast<const PoseDecodeItem*>(nets[(size_t)m]->box_host_.data() + prep_b);
+    for (int i = 0; i < n; ++i) ws[(size_t)m * n + i] = (double)(items[i].w - 1) * dec[i].scale;
+  }
+  const bool own_async = user_stream == (void*)-1;
+  if (own_async) user_stream = nullptr;
+  nets[0]->ensure_device();
+  void* s = user_stream ? user_stream : stream();
+  const FusedMaps fm = fuse(pyramid, base, use, nullptr, nullptr, s, mp, &ws);
+  emit_fused(fm, dst, is_device, s);
+  if (pose) {
+    const Net::MapRef &P = fm.map[0], &L = fm.map[1];
+    if (L.C != 2 * P.C) throw DcError(DC_ESHAPE, "decode_boxes: loc_pred must have 2 channels per joint and the score map's size");
+    // the base member's own items: scale scales[i] * pyramid[base], offset (x0, y0), the crop's own canvas on the base grid
+    const PoseDecodeItem* items = reinterpret_cast<const PoseDecodeItem*>(nets[(size_t)base]->box_dev_ + prep_b);
+    decode_to(people_scratch_, (size_t)P.NB * 5 * P.C, pose, is_device, s, [&](double* to) {
+      return launch_pose_decode_items(P.ptr, P.cp, P.c0, L.ptr, L.cp, L.c0, P.ek, P.NB, P.H, P.W, P.C, items, to, s);
+    });
   }
   fuse_done(s);
   if (!(is_device && (user_stream || own_async))) HIPCHECK(hipStreamSynchronize((hipStream_t)s));

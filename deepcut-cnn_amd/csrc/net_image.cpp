@@ -197,7 +197,7 @@ void Net::forward_boxes(const unsigned char* bgr, int h, int w, bool is_device, 
 }
 
 const unsigned char* Net::prep_boxes(const unsigned char* bgr, int h, int w, bool is_device, const int* boxes, const double* scales, int n,
-                                     int canvas_h, int canvas_w, void* s) {
+                                     int canvas_h, int canvas_w, void* s, bool mirror) {
   Storage& in = begin_batch(n, canvas_h, canvas_w);
   if (in.dim(1) != 3) throw DcError(DC_ESHAPE, "forward_boxes needs a 3-channel input blob");
   if (!s) s = stream;
@@ -247,6 +247,7 @@ const unsigned char* Net::prep_boxes(const unsigned char* bgr, int h, int w, boo
   }
   HIPCHECK(hipMemcpyAsync(box_dev_, box_host_.data(), bytes, hipMemcpyHostToDevice, (hipStream_t)s));
   box_n_ = n;
+  box_mirror_ = mirror;
   BoxPrepParams q{};
   q.src = src;
   q.img_h = h, q.img_w = w, q.n = n;
@@ -254,6 +255,7 @@ const unsigned char* Net::prep_boxes(const unsigned char* bgr, int h, int w, boo
   q.items = reinterpret_cast<const BoxPrepItem*>(box_dev_);
   q.dst = in.dev, q.dst_ekind = in.ekind, q.dst_cp = in.cp();
   q.mean[0] = 104.f, q.mean[1] = 117.f, q.mean[2] = 123.f;  // _MEAN, estimate_pose.py:26
+  q.mirror = mirror ? 1 : 0;
   KCHECK(launch_box_prep(q, s));
   in.head = HEAD_AT_GPU;
   return src;

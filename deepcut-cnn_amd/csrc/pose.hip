@@ -232,7 +232,8 @@ __global__ __launch_bounds__(256) void pairwise_decode_kernel(const T* __restric
 // folded into the gain / bias table.  A corner read is then no longer one ascending run of the wave but a permutation of it INSIDE the
 // same map, i.e. inside the same cache lines (14 / 28 / 364 channels of 2 or 4 bytes: 1 + 1 + 6 to 12 lines of 128 bytes per corner
 // either way), and the store stays a contiguous run.  The flag is compile-time so that a group without a mirrored member pays no
-// dependent integer load per member and channel.
+// dependent integer load per member and channel.  The flip record is per (member, image): every box of the box entry has its own width
+// and scale, so its reflected column is its own; the clamp stays at the member's whole map (the common canvas).
 struct FuseCorner {
   int i00, i01, i10, i11;  // cell indices (y * W + x) of the four corners in the member's map
   float fx, fy;
@@ -257,8 +258,12 @@ __global__ __launch_bounds__(256) void fuse_maps_kernel(const FuseMember* __rest
     const FuseMember& mem = members[m];
     const double q = mem.q;
     bool flipped = false;
-    if constexpr (Mirror) flipped = flip[m].on;
-    double u = flipped ? fuse_mirrored_u(flip[m].ws, c, q) : ((double)(8 * c + 4) * q - 4.0) / 8.0;
+    double ws = 0.0;
+    if constexpr (Mirror) {  // the record of (member, image): one workgroup per cell, so the grid is NB * Hb * Wb
+      const FuseFlip& ff = flip[(long)m * (gridDim.x / (unsigned)(Hb * Wb)) + b];
+      flipped = ff.on, ws = ff.ws;
+    }
+    double u = flipped ? fuse_mirrored_u(ws, c, q) : ((double)(8 * c + 4) * q - 4.0) / 8.0;
     double v = ((double)(8 * r + 4) * q - 4.0) / 8.0;
     u = fmin(fmax(u, 0.0), (double)(mem.W - 1));
     v = fmin(fmax(v, 0.0), (double)(mem.H - 1));

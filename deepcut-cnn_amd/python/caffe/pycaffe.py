@@ -148,6 +148,10 @@ def _load():
         "dc_group_detect_parts_mirrored": (ci, [vp, vp, ci, C.POINTER(FuseMirror), C.c_float, ci, ci, vp, vp]),
         "dc_group_assemble_people_mirrored": (ci, [vp, vp, ci, C.POINTER(FuseMirror), C.POINTER(AssembleParams), ci, vp, vp, vp, vp, vp, vp, vp,
                                                    vp]),
+        "dc_group_decode_pose": (ci, [vp, vp, ci, C.POINTER(FuseMirror), vp, ci, vp]),
+        "dc_group_forward_boxes_mirrored": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, C.POINTER(C.c_double), ci, ci, vp, C.POINTER(vp), C.POINTER(vp),
+                                                 C.POINTER(vp), vp]),
+        "dc_group_decode_boxes": (ci, [vp, vp, ci, C.POINTER(FuseMirror), vp, vp, vp, ci, vp]),
         "dc_group_plan_text": (cp, [vp]),
         "dc_group_profile_text": (cp, [vp, ci]),
         "dc_group_tune_report": (cp, [vp]),
@@ -1192,11 +1196,23 @@ class NetGroup(object):
                                             col("pose"), None))
         return outs
 
-    def forward_boxes(self, image, boxes, pyramid, scales=1.0, canvas=None, want=("prob", "loc_pred"), pose=True):
+    def forward_boxes(self, image, boxes, pyramid, scales=1.0, canvas=None, want=("prob", "loc_pred"), pose=True, mirror=None):
         """Net.forward_boxes over an image pyramid, as ONE grouped forward: member c takes box i at scales[i] * pyramid[c] on a
         canvas of member_canvas(canvas, pyramid[c]); canvas None = the smallest base canvas that fits every box at scales[i].
-        -> one dict per member with the requested maps and "pose" [n,5,J] in image coordinates."""
+        -> one dict per member with the requested maps and "pose" [n,5,J] in image coordinates.
+        mirror: one 0/1 per member; a marked member pre-processes every crop flipped left to right on the device
+        (dc_group_forward_boxes_mirrored) and returns its RAW maps, in the flipped crop's frame (`decode_boxes(mirror=...)` undoes the
+        flip).  When it names a member, "pose" is absent from the result: a mirrored member's own pose would be in flipped coordinates.
+        None or all zeros: exactly the unmirrored call."""
         k = len(self.nets)
+        if mirror is not None:
+            mirror = [int(bool(v)) for v in mirror]
+            if len(mirror) != k:
+                raise ValueError("one mirror flag per group member: %d flags for %d members" % (len(mirror), k))
+            if not any(mirror):
+                mirror = None
+            else:
+                pose = False
         x = np.ascontiguousarray(image, dtype=np.uint8)
         if x.ndim != 3 or x.shape[2] != 3:
             raise ValueError("image must be uint8 [H,W,3] (BGR)")
@@ -1229,6 +1245,11 @@ class NetGroup(object):
         def col(key):
             return self._ptrs([o[key].ctypes.data if key in o else None for o in outs], k)
 
+        if mirror is not None:
+            _check(_lib.dc_group_forward_boxes_mirrored(self._h, x.ctypes.data_as(C.c_void_p), x.shape[0], x.shape[1], 0,
+                                                        b.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p), n, (C.c_double * k)(*pyr), ch,
+                                                        cw, self._ints(mirror), col("prob"), col("loc_pred"), col("next_pred"), None))
+            return outs
         _check(_lib.dc_group_forward_boxes(self._h, x.ctypes.data_as(C.c_void_p), x.shape[0], x.shape[1], 0, b.ctypes.data_as(C.c_void_p),
                                            sc.ctypes.data_as(C.c_void_p), n, (C.c_double * k)(*pyr), ch, cw, col("prob"), col("loc_pred"),
                                            col("next_pred"), col("pose"), None))
@@ -1314,6 +1335,35 @@ class NetGroup(object):
         _check(_lib.dc_group_detect_parts_mirrored(self._h, sc.ctypes.data_as(C.c_void_p), base, fm, float(threshold), int(radius), int(max_det),
                                                    counts.ctypes.data_as(C.c_void_p), dets.ctypes.data_as(C.c_void_p)))
         return counts, dets
+
+    def decode_pose(self, scales, base=0, mirror=None, image_width=None, joint_mirror=None):
+        """The single-person pose of every image of the members' last forwards from the FUSED maps (dc_group_decode_pose): `prob` and
+        `loc_pred` are fused on member `base`'s grid as `detect_parts` fuses them, then decoded there at scales[base] as
+        `Net.decode_pose` decodes a net's own maps.  -> float64 [n, 5, J].  Works on members narrowed to `prob` and `loc_pred`.
+        mirror / image_width / joint_mirror: as `fuse_maps`.  The rule is this project's own (the reference keeps the best single scale)."""
+        sc, base = self._scales(scales, base)
+        n, j = self.nets[0].blobs["prob"].shape[:2]
+        pose = np.empty((n, 5, j), np.float64)
+        fm, _keep = self._mirror(mirror, image_width, joint_mirror, None)
+        _check(_lib.dc_group_decode_pose(self._h, sc.ctypes.data_as(C.c_void_p), base, fm, pose.ctypes.data_as(C.c_void_p), 0, None))
+        return pose
+
+    def decode_boxes(self, pyramid, base=0, mirror=None, joint_mirror=None, want=()):
+        """The poses of the boxes of the members' last `forward_boxes` from the FUSED maps (dc_group_decode_boxes): `prob` and `loc_pred`
+        of every member are fused on member `base`'s canvas — `pyramid` as the member scales; a mirrored member (`forward_boxes(mirror=...)`,
+        the same flags here) is sampled at every box's own reflected column — and decoded there as `forward_boxes` decodes a member's own
+        maps: at scales[i] * pyramid[base], restricted to the crop's own cells, shifted by the box corner.
+        -> dict: "pose" [n, 5, J] float64 in image coordinates, and the fused float32 maps named in `want` ("prob", "loc_pred")."""
+        sc, base = self._scales(pyramid, base)
+        ref = self.nets[base if 0 <= base < len(self.nets) else 0]
+        n, j = ref.blobs["prob"].shape[:2]
+        hw = tuple(ref.blobs["prob"].shape[2:])
+        out = {k: np.empty((n, ref.blobs[k].shape[1]) + hw, np.float32) for k in ("prob", "loc_pred") if k in want}
+        out["pose"] = np.empty((n, 5, j), np.float64)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        fm, _keep = self._mirror(mirror, 0, joint_mirror, None)
+        _check(_lib.dc_group_decode_boxes(self._h, ptr(sc), base, fm, ptr(out.get("prob")), ptr(out.get("loc_pred")), ptr(out["pose"]), 0, None))
+        return out
 
     def assemble_people(self, scales, base=0, threshold=0.1, radius=1, max_det=16, edges=None, mean=None, std=None, max_cost=32.0,
                         seed_threshold=0.5, max_people=32, min_joints=1, joint_order=None, return_cost=False, mirror=None, image_width=None,

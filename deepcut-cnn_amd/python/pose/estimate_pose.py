@@ -32,6 +32,8 @@ import logging as _logging
 
 import numpy as _np
 
+from .people import MIRROR_MPII14
+
 _LOGGER = _logging.getLogger(__name__)
 
 MEAN_BGR = _np.array([104.0, 117.0, 123.0])
@@ -271,7 +273,27 @@ def _read_outputs_only(net):
             n.set_outputs(["loc_pred", "prob"])
 
 
-def estimate_pose(image, model_def, model_bin, scales=None, net=None, tiling=None, on_device=True, grouped=None, all_outputs=False):
+def _fused_members(who, scales, fuse, flip, joint_mirror, base):
+    """The members of a fused call, checked without a net or a device: -> (member scales, mirror flags or None, base, joint table or
+    None).  flip doubles the group: the plain members first, then their mirrors; the base is a plain member (None = the plain scale
+    nearest 1.0, the first of equals)."""
+    from .people import _base_scale, _check_joint_mirror
+
+    scales = [float(v) for v in scales]
+    if not scales:
+        raise ValueError("%s: scales must name at least one scale" % who)
+    pi = _check_joint_mirror(joint_mirror) if flip else None
+    if base is not None and not 0 <= int(base) < len(scales):
+        raise ValueError("%s: base %r must name one of the %d plain members%s" %
+                         (who, base, len(scales), ": the mirrored members come after them and cannot be the base" if flip else ""))
+    base = _base_scale(scales) if base is None else int(base)
+    if not flip:
+        return scales, None, base, None
+    return scales + scales, [0] * len(scales) + [1] * len(scales), base, pi
+
+
+def estimate_pose(image, model_def, model_bin, scales=None, net=None, tiling=None, on_device=True, grouped=None, all_outputs=False, fuse=False,
+                  flip=False, joint_mirror=MIRROR_MPII14, base=None):
     """image: HxWx3 BGR uint8.  Returns the 5x14 pose of the best scale (see module docstring).
     tiling: None (one forward per scale), "exact" or "reference" (see `forward_maps_tiled`).
     on_device: without tiling, pre-process and decode on the GPU (`Net.forward_images`: the same canvas bit
@@ -280,13 +302,35 @@ def estimate_pose(image, model_def, model_bin, scales=None, net=None, tiling=Non
     grouped: None = several scales on the device run as ONE grouped forward (`caffe.NetGroup`); False = the
     reference's loop, one forward per scale (bit-identical to the host route's forwards).
     all_outputs: False (default) = the net computes only what is read here, `prob` and `loc_pred` (see `_read_outputs_only`); True
-    leaves the net's output selection alone (a caller that also reads `net.blobs['next_pred']` afterwards)."""
+    leaves the net's output selection alone (a caller that also reads `net.blobs['next_pred']` afterwards).
+    fuse: True returns the pose decoded from the FUSED maps of all scales (`NetGroup.decode_pose`: `prob` and `loc_pred` of every scale
+    resampled onto the grid of member `base`, averaged and decoded there) instead of `select_best` over per-scale poses — ONE grouped
+    forward and one decode, even for a single scale.  PARITY UNPINNED BY THE REFERENCE, which keeps the best single scale: the rule is
+    this project's own (include/deepcut_hip.h, dc_group_decode_pose).  It needs the device route: with `tiling`, on_device=False or
+    grouped=False it raises ValueError before touching the net.
+    flip: mirror test-time augmentation; implies fuse and doubles the group — the plain members, then their mirrors, as
+    `estimate_people` does — with joint_mirror (pose.MIRROR_MPII14 by default) naming the joint every joint becomes in the mirror.
+    base: the plain member whose grid the maps are fused on; None = the plain scale nearest 1.0, the first of equals."""
     if scales is None:
         scales = [1.0]
+    if fuse or flip:
+        if tiling is not None or not on_device or (grouped is not None and not grouped):
+            raise ValueError("estimate_pose(fuse=True / flip=True) fuses the maps on the device in a grouped forward: it takes no tiling, "
+                             "on_device=False or grouped=False")
+        members, flags, base, pi = _fused_members("estimate_pose", scales, fuse, flip, joint_mirror, base)
+        image = _np.asarray(image)
+        if image.dtype != _np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+            raise ValueError("image must be uint8 [H,W,3] (BGR)")
     if net is None:
         net = _get_model(model_def, model_bin)
     if not all_outputs:
         _read_outputs_only(net)
+    if fuse or flip:
+        grp = _scale_group(net, len(members))
+        if not all_outputs:
+            _read_outputs_only(net)  # (clones made just now follow their net)
+        grp.forward_images(image, members, want=(), pose=False, mirror=flags)
+        return grp.decode_pose(members, base, mirror=flags, image_width=image.shape[1], joint_mirror=pi)[0]
     poses = []
     if (grouped is None or grouped) and tiling is None and on_device and len(scales) > 1 and hasattr(net, "clone") \
             and _np.asarray(image).dtype == _np.uint8:
@@ -309,17 +353,24 @@ def estimate_pose(image, model_def, model_bin, scales=None, net=None, tiling=Non
     return select_best(poses)
 
 
-def estimate_poses(image, boxes, model_def, model_bin, scales=None, net=None, canvas=None):
+def estimate_poses(image, boxes, model_def, model_bin, scales=None, net=None, canvas=None, fuse=False, flip=False,
+                   joint_mirror=MIRROR_MPII14, base=None):
     """Top-down poses of the person boxes of one image: image HxWx3 BGR uint8, boxes n x 4 (x0, y0, x1, y1) half-open pixel corners
     from the caller's person detector.  Every box runs at every scale of `scales` (default [1.0]; several scales are ONE grouped
     forward, `NetGroup.forward_boxes`), the crop pre-processed as `estimate_pose` pre-processes an image; the best scale per box is
     chosen as there (`select_best`).  canvas: the common (h, w) at scale 1, or None for the smallest that fits every box.
     -> a list of n 5x14 poses in image coordinates (None where no scale reaches a positive confidence).  A caller-supplied `net`
-    keeps its option state; it is used together with clones of it kept with it (as `estimate_pose` does)."""
+    keeps its option state; it is used together with clones of it kept with it (as `estimate_pose` does).
+    fuse / flip / joint_mirror / base: as `estimate_pose` — every box's pose is decoded from the FUSED maps of all scales
+    (`NetGroup.forward_boxes`, then `NetGroup.decode_boxes`: one grouped forward, one fusion launch, one decode) instead of `select_best`;
+    flip adds a mirrored member per scale, each crop flipped by the device pre-processing and sampled at its own reflected column.
+    PARITY UNPINNED BY THE REFERENCE: the rule is this project's own (include/deepcut_hip.h, dc_group_decode_boxes).  No entry is None then."""
     import caffe as _caffe
 
     if scales is None:
         scales = [1.0]
+    if fuse or flip:
+        members, flags, fuse_base, pi = _fused_members("estimate_poses", scales, fuse, flip, joint_mirror, base)
     if net is None:
         net = _get_model(model_def, model_bin)
         _read_outputs_only(net)
@@ -327,6 +378,10 @@ def estimate_poses(image, boxes, model_def, model_bin, scales=None, net=None, ca
     b, _, base = _caffe.check_boxes(image.shape, boxes, 1.0, canvas)
     if b.shape[0] == 0:
         return []
+    if fuse or flip:
+        grp = _scale_group(net, len(members))
+        grp.forward_boxes(image, b, members, canvas=base, want=(), pose=False, mirror=flags)
+        return list(grp.decode_boxes(members, fuse_base, mirror=flags, joint_mirror=pi)["pose"])
     if len(scales) > 1:
         outs = _scale_group(net, len(scales)).forward_boxes(image, b, list(scales), canvas=base, want=(), pose=True)
     else:

@@ -573,6 +573,50 @@ int dc_group_detect_parts_mirrored(dc_group* group, const double* scales, int ba
 int dc_group_assemble_people_mirrored(dc_group* group, const double* scales, int base, const dc_fuse_mirror* fm, const dc_assemble_params* p,
                                       int n_edges, const int* edges, const double* mean, const double* stdev, const int* joint_order,
                                       int* n_people, double* people, int* cand, double* cost);
+/* ---- fused multi-scale and mirrored poses for the single-person entry and the box entry ----------------------------------------------
+ * NO REFERENCE COUNTERPART, PARITY UNPINNED BY THE REFERENCE: the reference decodes every scale of its pyramid on its own and keeps the
+ * "best" one (estimate_pose.py:119-126), combines no maps and mirrors nothing.  Decoding the FUSED maps is this project's own rule; the
+ * fusion is dc_group_fuse_maps[_mirrored]'s, the decode is `_pose_from_mats` (:131-143) as dc_net_decode_pose / dc_net_forward_boxes run it.
+ *
+ * dc_group_decode_pose: the members hold, from their last forward, the same NB images at scales[m]; fm is NULL or as in
+ *     dc_group_fuse_maps_mirrored.  `prob` and `loc_pred` alone are fused, by that rule, in the same launch and with the same tables as
+ *     dc_group_detect_parts_mirrored — so it also works on members whose outputs are narrowed to these two (DC_OPT_OUTPUTS) —, then every
+ *     joint's first maximum of the fused float32 `prob` in row-major order is refined by the fused `loc_pred` at s_b = scales[base]:
+ *     pose[NB][5][J] doubles, as dc_net_decode_pose.  Host or device destination and `stream` as in dc_group_fuse_maps.  Refuses what
+ *     dc_group_detect_parts_mirrored refuses of its scales, base and fm, in the same order and before any device work.
+ *
+ * dc_group_forward_boxes_mirrored: dc_group_forward_boxes with mirror[c] != 0 marking the members that pre-process every crop flipped
+ *     left to right: crop column w - 1 - sx wherever column sx of the unpadded crop would be read, applied after the clamp that makes the
+ *     replicate padding (which therefore repeats the flipped crop's last column, the crop's original column 0); resample tables, mean and
+ *     canvas are untouched, so a mirrored member's input and maps are, bit for bit, those of dc_group_forward_boxes on the host-flipped
+ *     image with every box reflected as (W - x1, y0, W - x0, y1), for float32, float16 and bfloat16 nets.  The member remembers that its
+ *     last box batch was mirrored.  The maps returned for it are its RAW maps, in the flipped crop's frame, and there is no `pose`
+ *     argument, for the reason dc_group_forward_images_mirrored has none.  mirror NULL or all zeros enqueues exactly what
+ *     dc_group_forward_boxes enqueues.
+ *
+ * dc_group_decode_boxes: on the n boxes of the members' last (dc_net_ / dc_group_)forward_boxes[_mirrored] — every member keeps its own
+ *     table of them, nothing is passed again.  The fusion rule is dc_group_fuse_maps[_mirrored]'s with the pyramid scales as the member
+ *     scales: q = pyramid_scales[m] / pyramid_scales[base], rho = pyramid_scales[base] / pyramid_scales[m], the same for every box, so
+ *     gain, bias and source channels are unchanged.  The one difference is the reflected column of a mirrored member, which every box has
+ *     of its own: for box i of width cw_i = x1 - x0, ws[m][i] = (double)(cw_i - 1) * (scales[i] * pyramid_scales[m]) — the inner product
+ *     being the scale the member ran that box at — and u = ((ws[m][i] - (8c + 4) q) - 4) / 8, in this order; clamp, floor, corners and
+ *     float weights as there.  THE CLAMP STAYS AT THE MEMBER'S WHOLE MAP, the common canvas, not at the crop's own cells: cells past a
+ *     crop's own canvas hold the net's answer to the zero canvas, and the decode never looks at them.
+ *     The decode is dc_net_forward_boxes' on the fused float32 maps with the base member's own items: scale scales[i] *
+ *     pyramid_scales[base], offset (x0, y0), arg-max (first maximum in row-major order) restricted to the crop's own canvas on the base
+ *     grid.  prob / loc_pred: the fused maps as NCHW float32 [n][C][H_b][W_b] on the base member's canvas; pose: [n][5][J] doubles in image
+ *     coordinates; any of the three NULL.  Host or device destinations and `stream` as in dc_group_fuse_maps.
+ *     Errors, before any device work: DC_EINVAL naming the member that holds another number of boxes than member 0; what
+ *     dc_group_detect_parts_mirrored refuses of the scales, base and fm (a mirrored base member included) except that fm->image_width is
+ *     not read; DC_EINVAL naming the member whose fm->mirror flag disagrees with what its last box batch was; DC_EINVAL when no boxes
+ *     are held or the maps are not those of the boxes.  Then DC_ENOCPU in CPU mode.                                                     */
+int dc_group_decode_pose(dc_group* group, const double* scales, int base, const dc_fuse_mirror* fm, double* pose, int is_device, void* stream);
+int dc_group_forward_boxes_mirrored(dc_group* group, const unsigned char* image, int height, int width, int is_device, const int* boxes,
+                                    const double* scales, int n, const double* pyramid_scales, int canvas_h, int canvas_w,
+                                    const int* mirror /* [M], 0/1; NULL = none */, float* const* prob, float* const* loc_pred,
+                                    float* const* next_pred, void* stream);
+int dc_group_decode_boxes(dc_group* group, const double* pyramid_scales, int base, const dc_fuse_mirror* fm, float* prob, float* loc_pred,
+                          double* pose, int is_device, void* stream);
 /* the merged plan of the last forward: one line per launch ("conv_gemm_mp<tile> problems=.. grid=.." or "member c: <kernel>");
  * NULL + dc_last_error() before the first forward; pointer valid until the next call on this group                            */
 const char* dc_group_plan_text(dc_group* group);
