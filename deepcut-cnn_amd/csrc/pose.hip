@@ -91,7 +91,7 @@ int launch_pose_decode_items(const void* prob, int pcp, int pc0, const void* loc
 
 // ---- multi-person consumers: part candidates (NMS) and pairwise regression decode ------------------------------------
 // One workgroup per (image, joint) score map.  Every cell is tested for being the maximum of its (2r+1)^2 window (ties: the
-// lower cell index wins) and, if so, becomes the 64-bit key (score bits << 32 | ~cell): keys are unique, and descending key
+// lower cell index wins) and, if so, becomes the 64-bit key (score bits without the sign << 32 | ~cell): keys are unique, and descending key
 // order IS the output order (score descending, cell ascending).  The candidate SET does not depend on thread timing, and
 // the list is then ordered by the whole workgroup: up to kPartLds keys by a bitonic sort in LDS; a map with more local
 // maxima than that (threshold 0, radius 0) spills its keys to global memory and takes the first max_det by repeated
@@ -129,9 +129,11 @@ __global__ __launch_bounds__(256) void part_select_kernel(const T* __restrict__ 
       }
     }
     if (ok) {
-      // the raw bit pattern orders NON-NEGATIVE floats only (a set sign bit would sort above every positive score, in reverse):
-      // v >= thr >= 0 here — Net::detect_parts refuses a negative threshold — and key 0 (the padding) is below every candidate
-      const unsigned long long key = ((unsigned long long)__float_as_uint(v) << 32) | (unsigned)(0xffffffffu - (unsigned)cell);
+      // the bit pattern orders NON-NEGATIVE floats only (a set sign bit would sort above every positive score).  Here v >= thr >= 0
+      // (detect_parts refuses a negative threshold), which leaves one value with the sign bit set: -0.0 at threshold 0 (a blob written
+      // by a caller may hold it; a sigmoid never does).  The sign bit is cleared, so -0.0 sorts with the zeros, by cell, and is emitted
+      // as +0.0; every positive score keeps its bits.  Key 0 (the padding) stays below every candidate: the cell term is > 0.
+      const unsigned long long key = ((unsigned long long)(__float_as_uint(v) & 0x7fffffffu) << 32) | (unsigned)(0xffffffffu - (unsigned)cell);
       const int slot = atomicAdd(&cnt, 1);  // LDS counter: the slot order varies, the set and (after sorting) the result do not
       if (slot < kPartLds) keys[slot] = key;
       mine[slot] = key;

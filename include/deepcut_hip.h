@@ -232,7 +232,8 @@ int dc_net_emit_maps(dc_net* net, void* prob, void* loc_pred, void* next_pred, i
 
 /* ---- pose decoding on the device (python/pose/estimate_pose.py:131-143 `_pose_from_mats`): after a
  * forward, writes pose[n][5][J] doubles (x, y, confidence, and the refinement vector in the reference's
- * (row, column) order, all divided by `scale`) to a host buffer (is_device=0) or a device buffer.        */
+ * (row, column) order, all divided by `scale`) to a host buffer (is_device=0) or a device buffer.
+ * A NaN in `prob` is outside the rule: numpy's argmax picks the first NaN, the device skips NaN cells.   */
 int dc_net_decode_pose(dc_net* net, double scale, double* pose, int is_device, void* stream);
 
 /* ---- image entry: the demo's pre-processing on the device + forward + optional decode -------------------

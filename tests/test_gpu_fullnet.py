@@ -152,20 +152,28 @@ def test_pose_demo_pipeline_config0(gpu_caffe, synth152):
 def test_device_pose_decode_equals_host_decode(gpu_caffe, synth152, fuse):
     """dc_net_decode_pose (arg-max + refinement on the GPU) == pose_from_maps on the downloaded maps, which
     is pinned to the reference's _pose_from_mats by tests/test_pose.py; channel views (fuse 2) and plain
-    tensors (fuse 0) alike; batch of 2."""
+    tensors (fuse 0) alike; batch of 2.  104x136 is a 13x17 map, fewer cells than the block has threads; 200x264 is a 25x33 map
+    of 825 cells, four trips of the scan: there the cells and the confidence are compared exactly as well (exact ties, which a
+    float32 forward does not produce, are tests/test_gpu_map_readers.py's)."""
     from deepcut_tools import deepercut_prototxt
     from pose import estimate_pose as ep
 
     path, _ = synth152
-    net = gpu_caffe.Net(deepercut_prototxt(152, 104, 136, 2), path, gpu_caffe.TEST, from_text=True, fuse=fuse)
-    net.blobs["data"].data[...] = rand_image(8, 104, 136, n=2)
-    net.forward()
-    for scale in (1.0, 0.75):
-        got = net.decode_pose(scale)
-        assert got.shape == (2, 5, 14)
-        for i in range(2):
-            ref = ep.pose_from_maps(net.blobs["prob"].data[i], net.blobs["loc_pred"].data[i], scale)
-            assert np.allclose(got[i], ref, rtol=0, atol=1e-9)
+    for h, w in ((104, 136), (200, 264)):
+        net = gpu_caffe.Net(deepercut_prototxt(152, h, w, 2), path, gpu_caffe.TEST, from_text=True, fuse=fuse)
+        net.blobs["data"].data[...] = rand_image(8, h, w, n=2)
+        net.forward()
+        for scale in (1.0, 0.75):
+            got = net.decode_pose(scale)
+            assert got.shape == (2, 5, 14)
+            for i in range(2):
+                ref = ep.pose_from_maps(net.blobs["prob"].data[i], net.blobs["loc_pred"].data[i], scale)
+                assert np.allclose(got[i], ref, rtol=0, atol=1e-9)
+                if (h // 8) * (w // 8) > 256:
+                    rows, cols = ep.pose_cells(got[i], scale)
+                    rrows, rcols = ep.pose_cells(ref, scale)
+                    assert np.array_equal(rows, rrows) and np.array_equal(cols, rcols) and np.array_equal(got[i][2], ref[2])
+                    assert (rrows * (w // 8) + rcols >= 256).any()  # some joint's maximum lies past the scan's first trip
 
 
 def test_benchmark_config_fullsize_matches_oracle(gpu_caffe, synth152):
