@@ -1,10 +1,24 @@
 """-m gpu: the float16 path (DC_OPT_DTYPE 1, BASELINE configs[2]: fp16 operands in HBM, v_mfma_f32_32x32x16_f16
-with float32 accumulation and float32 epilogue) against the float32 CPU oracle.
+with float32 accumulation and float32 epilogue) against the CPU oracle.
 
-Tolerances (stated, not 1e-3: activations are rounded to 11 significant bits after each of 152 layers):
+Single layers on float16-representable operands (f16_operands below) are held to ONE rounding of the output: the oracle accumulates
+in double and |got - ref| <= ulp_f16(ref) + 1e-6 x range — the 26 convolution / deconvolution configurations of the net
+(test_fp16_conv_deconv_configs), every h... / d... tile (test_gpu_tile_shapes.py), the streaming and stem forms
+(test_gpu_fp16_forms.py, + 1e-5 x max(1, range) as their bfloat16 twins), the per-row filter scaling
+(test_fp16_row_scaling_keeps_small_filter_rows, range taken per output channel).  The filter upload and the input conversion round to
+nearest even bit for bit; max-pool, crop and eltwise are exact against the oracle rounded to float16.  wino_h23 rounds differently
+by design and is held to a model of its own arithmetic (test_gpu_winograd_f16.py).
+
+The older figure, 2e-3 x max(1, range) per layer (one rounding of inputs, weights and output), still applies where the operands are
+NOT float16 values (test_fp16_single_layers, and the forms' own files), to the two large Winograd cases, and — as the larger figures
+below — to full nets, whose activations are rounded to 11 significant bits after each of 152 layers:
   prob      <= 2.5e-3 max-abs          (measured ~9e-4 at 240x320; the sigmoid compresses the error)
   loc_pred, next_pred <= 4e-3 x max(1, range of the map)   (measured ~1.4e-3 x range)
-Single layers: <= 2e-3 relative to the output range (one rounding of inputs, weights and output)."""
+
+Worst |got - bound's reference| / bound measured on an MI355X, per group (0.5 is the one rounding itself; no row needed more than the
+1e-6 x range accumulation term):
+  the 26 T2 rows 0.499 | every float16 tile on the small nets 0.499 | ws1x1 0.491 | stem7x7 0.490 | row scaling 0.498 (small rows 0.492)
+  wino_h23 (a) 0.494, (b) 0.499, with max|model - ref64| / range = 5.06e-4, 5.35e-4, 2.92e-4, 4.57e-4, 5.87e-4, 5.91e-4 on its six cases"""
 import os
 import zlib
 
@@ -15,6 +29,26 @@ from conftest import rand_image
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
+
+
+def f16_round(a):
+    """float32 -> the nearest float16 (ties to even), as float32."""
+    return np.asarray(a, np.float32).astype(np.float16).astype(np.float32)
+
+
+def f16_ulp(a):
+    """2^(floor(log2(max(|a|, 2^-14))) - 10): the spacing of float16 at a (any real a, float64 inside); below the smallest normal
+    number it stays at the subnormal spacing 2^-24.  (frexp, not log2: log2 of the float just below a power of two rounds up.)"""
+    m = np.maximum(np.abs(np.asarray(a, np.float64)), 2.0 ** -14)
+    return np.ldexp(1.0, np.frexp(m)[1] - 1 - 10)
+
+
+def f16_operands(a):
+    """f16_round, then every value with |v| < 2^-14 set to 0: operands a float16 kernel reads exactly and that are never subnormal.
+    How the matrix unit treats float16 SUBNORMAL inputs (kept or flushed) has not been established here, and the one-ulp bounds
+    of the tight tests must not rest on it: subnormal operands are out of their scope."""
+    r = f16_round(a)
+    return np.where(np.abs(r) < 2.0 ** -14, np.float32(0), r)
 
 
 def _check_maps(out, ref):
@@ -107,6 +141,180 @@ def test_fp16_single_layers(gpu_caffe, cfg):
     ref = (O.conv_forward if kind == "conv" else O.deconv_forward)(x, wt, b, s, p, d)
     assert got.shape == ref.shape
     assert float(np.abs(got - ref).max()) <= 2e-3 * max(1.0, float(np.abs(ref).max()))
+
+
+# ---- single layers on float16 operands: one rounding ------------------------------------------------------------------------------
+from test_gpu_layers import T2, _inp  # noqa: E402  (the 26 convolution / deconvolution configurations of the net)
+
+
+@pytest.mark.parametrize("cfg", T2, ids=lambda c: "%s_k%ds%dp%dd%d_%dto%d" % (c[0], c[1], c[2], c[3], c[4], c[6], c[7]))
+def test_fp16_conv_deconv_configs(gpu_caffe, cfg, monkeypatch):
+    """As test_bf16_conv_deconv_configs: operands that are float16 values, the oracle accumulating in double, one rounding of the
+    output.  The Winograd form is off (it rounds its transformed patches: test_gpu_winograd_f16.py holds it to its own model); the
+    streaming and stem forms stay at their defaults — they claim the tiles' arithmetic."""
+    monkeypatch.setenv("DC_WINOGRAD", "0")
+    kind, k, s, p, d, bias, cin, cout, h, w = cfg
+    rs = np.random.RandomState(zlib.crc32(repr(cfg).encode()) & 0x7fffffff)
+    typ = "Convolution" if kind == "conv" else "Deconvolution"
+    text = _inp("x", (2, cin, h, w)) + (
+        'layer { name: "l" type: "%s" bottom: "x" top: "y" convolution_param { num_output: %d kernel_size: %d '
+        "stride: %d pad: %d dilation: %d bias_term: %s } }" % (typ, cout, k, s, p, d, "true" if bias else "false"))
+    net = gpu_caffe.Net(text, gpu_caffe.TEST, from_text=True, fuse=0, dtype="f16")
+    x = f16_operands(rs.randn(2, cin, h, w))
+    wshape = (cout, cin, k, k) if kind == "conv" else (cin, cout, k, k)
+    wt = f16_operands(rs.randn(*wshape) / np.sqrt(cin * k * k))
+    b = rs.randn(cout).astype(np.float32) if bias else None
+    net.params["l"][0].data[...] = wt
+    if bias:
+        net.params["l"][1].data[...] = b
+    net.blobs["x"].data[...] = x
+    got = net.forward()["y"]
+    O.set_double_acc(True)
+    try:
+        ref = (O.conv_forward if kind == "conv" else O.deconv_forward)(x, wt, b, s, p, d)
+    finally:
+        O.set_double_acc(False)
+    assert got.shape == ref.shape
+    assert np.array_equal(got, f16_round(got)), "outputs are float16 values"
+    rng = float(np.abs(ref).max())
+    bound = f16_ulp(ref) + 1e-6 * rng
+    err = np.abs(got.astype(np.float64) - ref)
+    at = np.unravel_index(int(np.argmax(err / bound)), err.shape)
+    tiles = sorted(set(ln.split("\t")[1] for ln in net.plan_text().splitlines() if not ln.startswith("#") and "\t" in ln))
+    print("f16 %s: worst |got - ref| / bound = %.3f at %s (got %r, ref %r, range %.3g) on %s" % (
+        cfg, float((err / bound).max()), at, float(got[at]), float(ref[at]), rng, tiles))
+    assert float((err - bound).max()) <= 0, "worst excess %g (range %g)" % (float((err - bound).max()), rng)
+
+
+def _one_hot_layer(gpu_caffe, cin, cout, wt, bias=None):
+    """A 1x1 layer over `cin` one-hot pixels: y[co, j] = w[co, j] (+ bias[co]) — every converted weight read back."""
+    text = _inp("x", (1, cin, 1, cin)) + ('layer { name: "l" type: "Convolution" bottom: "x" top: "y" '
+                                          "convolution_param { num_output: %d kernel_size: 1 bias_term: %s } }" % (cout, "true" if bias is not None else "false"))
+    net = gpu_caffe.Net(text, gpu_caffe.TEST, from_text=True, fuse=0, dtype="f16")
+    net.params["l"][0].data[...] = wt
+    if bias is not None:
+        net.params["l"][1].data[...] = bias
+    x = np.zeros((1, cin, 1, cin), np.float32)
+    x[0, np.arange(cin), 0, np.arange(cin)] = 1.0  # pixel j holds e_j
+    net.blobs["x"].data[...] = x
+    return net.forward()["y"][0, :, 0, :].copy()
+
+
+def _ties(a, idx):
+    """The float32 values a[idx] moved onto exact float16 ties: the low 13 mantissa bits become 0x1000."""
+    u = a.view(np.uint32)
+    u[idx] = (u[idx] & np.uint32(0xFFFFE000)) | np.uint32(0x1000)
+
+
+def test_fp16_filter_upload_rounds_to_nearest_even(gpu_caffe):
+    """Weights that are NOT float16 values (N(0,1), eight exact ties, the smallest normal binade, all |w| >= 2^-14): the upload scales
+    every filter row by a power of two (DevVec::row_scale) and converts it on the device; what comes back through the epilogue's
+    inverse scale must be numpy's round-to-nearest-even of the weight, bit for bit — the row scale changes no rounding."""
+    cin, cout = 64, 64
+    rs = np.random.RandomState(5)
+    wt = rs.randn(cout, cin, 1, 1).astype(np.float32)
+    wt[1, :4, 0, 0] = [2.0 ** -14, 2.0 ** -14 * (1 + 2.0 ** -11), 1.3e-4, -7e-5]  # the bottom of the normal range (a tie among them)
+    small = np.abs(wt) < 2.0 ** -14
+    wt[small] = np.float32(0.37)
+    _ties(wt[0, :, 0, 0], slice(0, 8))
+    assert (np.abs(wt) >= 2.0 ** -14).all()
+    assert int((f16_round(wt) != wt).sum()) > 4000 and (wt.view(np.uint32)[0, :8, 0, 0] & 0x1FFF == 0x1000).all()
+    y = _one_hot_layer(gpu_caffe, cin, cout, wt)
+    assert np.array_equal(y, f16_round(wt[:, :, 0, 0]))
+
+
+def test_fp16_input_conversion_rounds_to_nearest_even(gpu_caffe):
+    """The same layer with identity filters: y is the converted input, which must be f16_round(x) for an x that is not float16
+    values — ties, values up to the thousands and down to the smallest normal binade included."""
+    c, npix = 64, 96
+    rs = np.random.RandomState(6)
+    x = (rs.randn(1, c, 1, npix) * np.exp2(rs.randint(-10, 11, (1, c, 1, npix)))).astype(np.float32)
+    x[np.abs(x) < 2.0 ** -14] = np.float32(2.0 ** -14 * 1.5)
+    _ties(x[0, :, 0, 0], slice(0, 8))
+    _ties(x[0, 5, 0, :], slice(8, 16))
+    assert int((f16_round(x) != x).sum()) > 5000
+    text = _inp("x", (1, c, 1, npix)) + ('layer { name: "l" type: "Convolution" bottom: "x" top: "y" '
+                                         "convolution_param { num_output: %d kernel_size: 1 bias_term: false } }" % c)
+    net = gpu_caffe.Net(text, gpu_caffe.TEST, from_text=True, fuse=0, dtype="f16")
+    net.params["l"][0].data[...] = np.eye(c, dtype=np.float32).reshape(c, c, 1, 1)
+    net.blobs["x"].data[...] = x
+    assert np.array_equal(net.forward()["y"], f16_round(x))
+
+
+def _row_scaled_f16(w):
+    """The filter rows as the lowering stores them (net_lower.cpp, half_row_scale): k = 13 - floor(log2(max|row|)) brings the row's
+    largest magnitude into [2^13, 2^14), w' = f16_round(w x 2^k) / 2^k; an all-zero row stays as it is.  -> float64"""
+    w = np.asarray(w, np.float32)
+    mx = np.abs(w).max(axis=1)
+    k = np.where(mx > 0, 13 - (np.frexp(np.where(mx > 0, mx, 1.0))[1] - 1), 0)
+    f = np.ldexp(1.0, k)[:, None]
+    return f16_round(w.astype(np.float64) * f).astype(np.float64) / f
+
+
+def test_fp16_row_scaling_keeps_small_filter_rows(gpu_caffe):
+    """What DevVec::row_scale is for: filter rows of magnitude 1e-5, 1e-6 and 1e-7, of which plain float16 (smallest normal 6.1e-5,
+    subnormal spacing 6e-8) would keep a few bits or none, over activations of magnitude ~100.  The reference is float64 over the
+    weights rounded as the lowering rounds them; the bound is one rounding of the output, ulp_f16(ref) + 1e-6 x range, the range taken
+    PER OUTPUT CHANNEL (the rows differ by seven orders of magnitude: the layer's range would excuse the small rows entirely; float32
+    accumulation over K = 64 and the bias add are relative to the row's own sums).  One row is all zero (its output is exactly the
+    bias), one has a largest weight that is exactly a power of two (the edge of ilogb)."""
+    cin, cout, n, h, w = 64, 64, 2, 5, 7
+    rs = np.random.RandomState(7)
+    wt = (rs.randn(cout, cin) / 8).astype(np.float32)
+    for r, mag in ((3, 1e-5), (4, 1e-6), (5, 1e-7), (40, 1e-5), (41, 1e-7)):
+        wt[r] = (mag * rs.uniform(0.25, 1.0, cin) * rs.choice([-1.0, 1.0], cin)).astype(np.float32)
+    wt[7] = 0.0
+    wt[9] = (rs.uniform(0.01, 0.1, cin) * rs.choice([-1.0, 1.0], cin)).astype(np.float32)
+    wt[9, 11] = 0.125  # the row's largest weight: exactly 2^-3
+    bias = f16_round(rs.randn(cout))
+    bias[[3, 4, 5]] = 0.0  # the small rows' outputs stand alone here; rows 40, 41 add them to an O(1) bias
+    x = f16_operands(rs.randn(n, cin, h, w) * 100.0)
+    text = _inp("x", (n, cin, h, w)) + ('layer { name: "l" type: "Convolution" bottom: "x" top: "y" '
+                                        "convolution_param { num_output: %d kernel_size: 1 bias_term: true } }" % cout)
+    net = gpu_caffe.Net(text, gpu_caffe.TEST, from_text=True, fuse=0, dtype="f16")
+    net.params["l"][0].data[...] = wt.reshape(cout, cin, 1, 1)
+    net.params["l"][1].data[...] = bias
+    net.blobs["x"].data[...] = x
+    got = net.forward()["y"]
+    ref = np.einsum("oc,nchw->nohw", _row_scaled_f16(wt), x.astype(np.float64)) + bias.astype(np.float64)[None, :, None, None]
+    exact = np.einsum("oc,nchw->nohw", wt.astype(np.float64), x.astype(np.float64)) + bias.astype(np.float64)[None, :, None, None]
+    rng = np.abs(ref).max(axis=(0, 2, 3), keepdims=True)
+    ratio = np.abs(got.astype(np.float64) - ref) / (f16_ulp(ref) + 1e-6 * rng)
+    print("row scaling: worst |got - ref| / bound per row group: small rows %.3f, zero row %.3f, power-of-two row %.3f, others %.3f" % (
+        float(ratio[:, [3, 4, 5, 40, 41]].max()), float(ratio[:, 7].max()), float(ratio[:, 9].max()),
+        float(np.delete(ratio, [3, 4, 5, 7, 9, 40, 41], axis=1).max())))
+    assert np.array_equal(got, f16_round(got))
+    assert float(ratio.max()) <= 1.0, float(ratio.max())
+    assert np.array_equal(got[:, 7], np.broadcast_to(bias[7], got[:, 7].shape)), "the all-zero row returns the bias"
+    # the small rows keep their precision against the EXACT weights: every weight is within 2^-11 of itself (relative), then the bound above
+    slack = 2.0 ** -11 * np.einsum("oc,nchw->nohw", np.abs(wt).astype(np.float64), np.abs(x).astype(np.float64))
+    for r in (3, 4, 5):
+        over = np.abs(got[:, r] - exact[:, r]) - (slack[:, r] + f16_ulp(exact[:, r]) + 1e-6 * float(np.abs(exact[:, r]).max()))
+        assert float(over.max()) <= 0, (r, float(over.max()))
+
+
+@pytest.mark.parametrize("hw", [(3, 5), (15, 20), (33, 47)])
+def test_fp16_maxpool_is_exact(gpu_caffe, hw):
+    text = _inp("x", (2, 64) + hw) + 'layer { name: "p" type: "Pooling" bottom: "x" top: "y" pooling_param { pool: MAX kernel_size: 3 stride: 2 } }'
+    net = gpu_caffe.Net(text, gpu_caffe.TEST, from_text=True, fuse=0, dtype="f16")
+    x = f16_round(np.random.RandomState(1).randn(2, 64, *hw) * 1e3)
+    net.blobs["x"].data[...] = x
+    assert np.array_equal(net.forward()["y"], O.maxpool_forward(x, 3, 2))
+
+
+def test_fp16_eltwise_crop_are_exact(gpu_caffe):
+    text = (_inp("a", (2, 14, 9, 11)) + _inp("b", (2, 14, 8, 10)) +
+            'layer { name: "c" type: "Crop" bottom: "a" bottom: "b" top: "ac" }'
+            'layer { name: "e" type: "Eltwise" bottom: "b" bottom: "ac" top: "s" }')
+    net = gpu_caffe.Net(text, gpu_caffe.TEST, from_text=True, fuse=0, dtype="f16")
+    rs = np.random.RandomState(3)
+    a, b = f16_round(rs.randn(2, 14, 9, 11)), f16_round(rs.randn(2, 14, 8, 10))
+    net.blobs["a"].data[...] = a
+    net.blobs["b"].data[...] = b
+    net.forward()
+    ac = O.crop_forward(a, b)
+    assert np.array_equal(net.blobs["ac"].data, ac)
+    assert np.array_equal(net.blobs["s"].data, f16_round(b + ac))  # (a + b in float32 is exact for two float16 values)
 
 
 def _large_activation_weights(layers, gain):

@@ -1,7 +1,9 @@
 """-m gpu: the float16 stem kernel (csrc/stem_f16.hip, tile name "stem7x7": conv1 of ResNet-152.prototxt — 7x7, stride 2, pad 3,
 3 -> 64 channels, + BatchNorm / Scale / ReLU), forced with DC_STEM=1; by default it is used where the per-shape timing finds it faster.
-Against the CPU oracle at the float16 path's single-layer bound (2e-3 x range) and against the row-tap gather-GEMM launch of the same
-layer (same operands, another summation grouping: float16 rounding apart).  Odd and tiny images (the zero padding on every side, tiles
+Against the CPU oracle within 2e-3 x range (the float16 path's figure for operands that are NOT float16 values, as here: inputs, filters
+and output are rounded once each) and against the row-tap gather-GEMM launch of the same layer (same operands, another summation
+grouping: float16 rounding apart); on float16-valued operands the form is held to ONE rounding of the float64 reference in
+tests/test_gpu_fp16_forms.py.  Odd and tiny images (the zero padding on every side, tiles
 that hang over the right / bottom edge, fewer pixels than one tile), batches, with and without the affine / the ReLU."""
 import os
 

@@ -1,6 +1,7 @@
 """-m gpu: the streaming form of the float16 dense 1x1 layers (csrc/stream1x1.hip, tile name "ws1x1"), forced with DC_STREAM1X1=1 —
-by default it is used only where the per-shape timing finds it faster.  Against the CPU oracle at the float16 path's stated bound
-(single layers <= 2e-3 x range) AND bit for bit against a gather-GEMM tile without split-K on the same layer (the epilogue is the same instruction
+by default it is used only where the per-shape timing finds it faster.  Against the CPU oracle within 2e-3 x range (the float16 path's
+figure for operands that are NOT float16 values, as here; on float16-valued operands tests/test_gpu_fp16_forms.py holds the form to ONE
+rounding of the float64 reference) AND bit for bit against a gather-GEMM tile without split-K on the same layer (the epilogue is the same instruction
 sequence on the same operands; the matrix products accumulate the same K order): what the kernel changes is how the bytes travel.
 Covers every K the kernel takes (64, 128, 256, 512), ragged pixel counts (M % 32 != 0, M < 32, a single pixel), batches, the
 shortcut + ReLU and plain epilogues, layers without BatchNorm / Scale (no scale, no shift), multi-tensor launches of a NetGroup, and the
