@@ -481,6 +481,29 @@ int dc_net_forward_boxes(dc_net* net, const unsigned char* image, int height, in
   });
 }
 
+int dc_net_forward_frames(dc_net* net, const dc_frame* frames, int n, int height, int width, double scale, int is_device, float* prob,
+                          float* loc_pred, float* next_pred, double* pose, void* stream) {
+  REQUIRE(net);
+  REQUIRE(frames);
+  if (n <= 0 || height <= 0 || width <= 0) return fail(DC_EINVAL, "n, height and width must be positive");
+  if (!(scale > 0)) return fail(DC_EINVAL, "scale must be positive");
+  return guard([&] {
+    N(net)->forward_images(nullptr, n, height, width, scale, is_device != 0, prob, loc_pred, next_pred, pose, stream, frames);
+  });
+}
+
+int dc_net_forward_boxes_frame(dc_net* net, const dc_frame* frame, int height, int width, int is_device, const int* boxes,
+                               const double* scales, int n, int canvas_h, int canvas_w, float* prob, float* loc_pred, float* next_pred,
+                               double* pose, void* stream) {
+  REQUIRE(net);
+  if (n == 0) return DC_OK;
+  REQUIRE(frame);
+  return guard([&] {
+    N(net)->forward_boxes(nullptr, height, width, is_device != 0, boxes, scales, n, canvas_h, canvas_w, prob, loc_pred, next_pred, pose, stream,
+                          frame);
+  });
+}
+
 int dc_image_canvas_size(int height, int width, double scale, int* canvas_h, int* canvas_w) {
   REQUIRE(canvas_h);
   REQUIRE(canvas_w);
@@ -739,6 +762,36 @@ int dc_group_forward_boxes(dc_group* group, const unsigned char* image, int heig
                            float* const* loc_pred, float* const* next_pred, double* const* pose, void* stream) {
   return group_forward_boxes(group, image, height, width, is_device, boxes, scales, n, pyramid_scales, canvas_h, canvas_w, nullptr, prob,
                              loc_pred, next_pred, pose, stream);
+}
+// the same two on video frames (dc_frame)
+int dc_group_forward_frames(dc_group* group, const dc_frame* const* frames, const int* n, const int* height, const int* width,
+                            const double* scale, const int* mirror, int is_device, float* const* prob, float* const* loc_pred,
+                            float* const* next_pred, double* const* pose, void* stream) {
+  REQUIRE(group);
+  REQUIRE(frames);
+  REQUIRE(n);
+  REQUIRE(height);
+  REQUIRE(width);
+  REQUIRE(scale);
+  for (size_t c = 0; c < G(group)->nets.size(); ++c) {
+    if (!frames[c]) return fail(DC_EINVAL, "null frames for group member " + std::to_string(c));
+    if (n[c] <= 0 || height[c] <= 0 || width[c] <= 0 || !(scale[c] > 0)) return fail(DC_EINVAL, "bad image shape / scale for group member " + std::to_string(c));
+  }
+  return guard([&] {
+    G(group)->forward_images(nullptr, n, height, width, scale, is_device != 0, prob, loc_pred, next_pred, pose, stream, mirror, frames);
+  });
+}
+int dc_group_forward_boxes_frame(dc_group* group, const dc_frame* frame, int height, int width, int is_device, const int* boxes,
+                                 const double* scales, int n, const double* pyramid_scales, int canvas_h, int canvas_w, const int* mirror,
+                                 float* const* prob, float* const* loc_pred, float* const* next_pred, double* const* pose, void* stream) {
+  REQUIRE(group);
+  if (n == 0) return DC_OK;
+  REQUIRE(frame);
+  REQUIRE(pyramid_scales);
+  return guard([&] {
+    G(group)->forward_boxes(nullptr, height, width, is_device != 0, boxes, scales, n, pyramid_scales, canvas_h, canvas_w, prob, loc_pred,
+                            next_pred, pose, stream, mirror, frame);
+  });
 }
 // multi-scale fusion: a null `scales` is the library's to refuse (DC_EINVAL naming it), like every other argument of the rule.  The plain
 // entries are the mirrored ones with no mirror table.

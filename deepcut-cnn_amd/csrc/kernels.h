@@ -415,8 +415,26 @@ int launch_fuse_maps(const FuseMember* members, const FuseFlip* flip, const floa
 // the replicate padding repeats the FLIPPED image's last column (source column 0) — and everything after that is unchanged: the result
 // is, bit for bit, what the unmirrored path makes of the host-flipped image (dc_group_forward_images_mirrored).  BoxPrepParams::mirror is
 // the same for every crop of a launch: crop column it.w - 1 - sx wherever column sx of the unpadded crop would be read, after the clamp.
+//
+// Source-pixel readers (the kernels' compile-time parameter; the rule: include/deepcut_hip.h, dc_frame).  kReadPacked is the packed
+// BGR block `src` the existing entries hand over.  The two frame readers take image n's planes from a device table instead:
+// kReadBgr the same three bytes through a row pitch, kReadNv12 a Y byte at (x, y) and the Cb, Cr pair at (x >> 1, y >> 1), converted
+// to B, G, R where the pixel is fetched — after the clamp and the mirror reflection, with the image's absolute coordinates —, so
+// everything behind the fetch (replicate padding, mirror, both resample passes, the direct branch, tmp, mean, canvas) is one body.
+enum { kReadPacked = 0, kReadBgr = 1, kReadNv12 = 2 };
+struct FramePlanes {
+  const unsigned char* plane0;  // Y rows (NV12) or B,G,R rows (BGR24)
+  const unsigned char* plane1;  // Cb,Cr rows (NV12); unused otherwise
+  int pitch0, pitch1;           // bytes
+};
+struct FrameSource {
+  const FramePlanes* planes;  // [n] device table, one entry per image of the batch (the box entry: one); nullptr with kReadPacked
+  int reader;                 // kRead*
+  int ky, rv, bu, gu, gv, y0;  // NV12: 16.16 fixed-point coefficients of the conversion and the luma offset (net_image.cpp frame_csc)
+};
 struct ImagePrepParams {
-  const unsigned char* src;  // [n][h][w][3] BGR uint8
+  const unsigned char* src;  // [n][h][w][3] BGR uint8 (kReadPacked)
+  FrameSource frame;         // the frame readers' source; zero for kReadPacked
   int n, h, w;
   int out_h, out_w;          // canvas = the network input
   int use_h, use_w;          // top-left part of the resized image that lands on the canvas; the rest is zero
@@ -450,7 +468,8 @@ struct BoxPrepItem {
   int x_ksize, y_ksize;
 };
 struct BoxPrepParams {
-  const unsigned char* src;  // [img_h][img_w][3] BGR uint8
+  const unsigned char* src;  // [img_h][img_w][3] BGR uint8 (kReadPacked)
+  FrameSource frame;         // the frame readers' source (one table entry); zero for kReadPacked
   int img_h, img_w;
   int n;
   int out_h, out_w;          // the common canvas of every item (= the network input)

@@ -23,6 +23,8 @@
 #include "formats.h"
 #include "kernels.h"
 
+struct dc_frame;  // include/deepcut_hip.h: one video frame (planes, pitches, format, matrix, range)
+
 namespace dc {
 
 // ---- Caffe context (common.cpp:13-20: thread-local mode + device) ---------------------------------
@@ -165,6 +167,10 @@ void image_canvas_size(int h, int w, double scale, int& out_h, int& out_w, int& 
 // every scale positive, the canvas a positive multiple of 8 that holds every box's own canvas (image_canvas_size of the crop at its
 // scale).  Throws DC_EINVAL naming the first box at fault.
 void check_boxes(int h, int w, const int* boxes, const double* scales, int n, int canvas_h, int canvas_w);
+// the frame entries' argument checks, host only: n frames of h x w (include/deepcut_hip.h, dc_frame).  Throws DC_EINVAL naming the
+// field and the frame index: a NULL plane the format needs, a pitch below the minimum, an unknown format / matrix / range, a frame that
+// differs from frame 0 in one of those three.
+void check_frames(const char* who, const dc_frame* frames, int n, int h, int w);
 // a group member's canvas in the box entry: the base canvas side times the member's pyramid scale, rounded up to the stride 8
 inline int box_member_canvas(int side, double pyramid_scale) { return (int)(std::ceil((double)side * pyramid_scale / 8) * 8); }
 
@@ -313,13 +319,15 @@ struct Net {
   void forward_requests(int n, const float* const* inputs, int h, int w, float* const* prob, float* const* loc, float* const* next,
                         void* user_stream);
   // image entry: pre-processing (estimate_pose.py:83-103) + forward + optional decode, all on the device
+  // frames (dc_net_forward_frames): n video frames instead of `bgr`, which is then not read; the same call in every other respect
   void forward_images(const unsigned char* bgr, int n, int h, int w, double scale, bool is_device, float* prob, float* loc,
-                      float* next, double* pose, void* user_stream);
+                      float* next, double* pose, void* user_stream, const dc_frame* frames = nullptr);
   // box entry: n person boxes of ONE h x w image (boxes: n x 4 int32 (x0, y0, x1, y1), half-open; scales: n doubles; both host
   // arrays), box i pre-processed at scales[i] as an image of its own onto a common canvas_h x canvas_w canvas, ONE batch-n forward,
   // pose i decoded on its own canvas's cells at scales[i] and shifted by (x0, y0) into image coordinates.  n = 0 does nothing.
+  // frame (dc_net_forward_boxes_frame): ONE video frame instead of `bgr`
   void forward_boxes(const unsigned char* bgr, int h, int w, bool is_device, const int* boxes, const double* scales, int n, int canvas_h,
-                     int canvas_w, float* prob, float* loc, float* next, double* pose, void* user_stream);
+                     int canvas_w, float* prob, float* loc, float* next, double* pose, void* user_stream, const dc_frame* frame = nullptr);
   void sync_to_host(Storage& s);       // SyncedMemory::to_cpu
   void sync_to_device(Storage& s);     // SyncedMemory::to_gpu
   void decode_pose(double scale, double* out, bool is_device, void* user_stream);  // after a forward
@@ -343,13 +351,20 @@ struct Net {
   // front half of forward_images: the uint8 pixels -> the network's NHWC input image, enqueued on s (the plan of the canvas
   // shape is active afterwards); returns the canvas height / width
   // mirror: the images are read flipped left to right (ImagePrepParams::mirror; NetGroup::forward_images hands it down)
-  void prep_images(const unsigned char* bgr, int n, int h, int w, double scale, bool is_device, void* s, bool mirror = false);
+  // frames (already checked): n video frames instead of `bgr`, read by the kernels' frame reader through the per-image plane table;
+  // host frames are staged first (stage_frames), device frames read where they are
+  void prep_images(const unsigned char* bgr, int n, int h, int w, double scale, bool is_device, void* s, bool mirror = false,
+                   const dc_frame* frames = nullptr);
   // front half of forward_boxes (arguments already checked): the boxes' canvases in ONE launch, and the per-box decode table;
   // returns the device copy of the image the launch reads (a host image is uploaded once)
   // mirror: every crop is read flipped left to right (BoxPrepParams::mirror; NetGroup::forward_boxes hands it down), and the member
   // remembers that its last box batch was (box_mirror_)
+  // frame (already checked): ONE video frame instead of `bgr`; a host frame is staged (staged_planes() is its device copy); returns null
   const unsigned char* prep_boxes(const unsigned char* bgr, int h, int w, bool is_device, const int* boxes, const double* scales, int n,
-                                  int canvas_h, int canvas_w, void* s, bool mirror = false);
+                                  int canvas_h, int canvas_w, void* s, bool mirror = false, const dc_frame* frame = nullptr);
+  // the device copies of the host frames of the last prep_images / prep_boxes (planes in the net's image buffer, pitch padding dropped):
+  // what a group hands to the other members that share those frames, so that they travel once
+  const std::vector<FramePlanes>& staged_planes() const { return frame_host_; }
   // back half: the poses of the boxes of the last prep_boxes, in image coordinates (host or device `out`, n x 5 x J doubles)
   void decode_boxes(double* out, bool is_device, void* s);
   std::string plan_text();
@@ -398,6 +413,13 @@ struct Net {
   void* scratch(size_t bytes);
   unsigned char* img_dev_ = nullptr;  // uint8 source images uploaded from the host
   size_t img_cap_ = 0;
+  unsigned char* frame_dev_ = nullptr;   // frame entries: FramePlanes[n], the frame readers' plane table
+  size_t frame_cap_ = 0;
+  std::vector<FramePlanes> frame_host_;  // the host side of that table (device addresses): uploaded only when it differs from what is there
+  void* frame_stream_ = nullptr;         // ... and the stream that upload ran on
+  // n checked frames of h x w -> the frame readers' source: host planes staged into img_dev_ (one 2-D copy per plane on s), the plane
+  // table uploaded when it differs from the one on the device, the conversion's coefficients
+  FrameSource frame_source(const dc_frame* frames, int n, int h, int w, bool is_device, void* s);
   unsigned char* tmp_dev_ = nullptr;  // horizontally resampled rows
   size_t tmp_cap_ = 0;
   unsigned char* box_dev_ = nullptr;  // box entry: BoxPrepItem[n] then PoseDecodeItem[n]
@@ -472,15 +494,18 @@ struct NetGroup {
   // image entry: member c pre-processes n[c] images of h[c] x w[c] at scale[c] (Net::forward_images), then ONE grouped
   // forward, then per member the maps / the decoded pose.  mirror (dc_group_forward_images_mirrored): [M] 0/1, null = none; a mirrored
   // member pre-processes its images flipped left to right and returns its raw maps, in the flipped image's frame
+  // frames (dc_group_forward_frames): frames[c] = member c's n[c] video frames instead of bgr[c]; host frames that several members share
+  // are staged once
   void forward_images(const unsigned char* const* bgr, const int* n, const int* h, const int* w, const double* scale, bool is_device,
                       float* const* prob, float* const* loc, float* const* next, double* const* pose, void* user_stream,
-                      const int* mirror = nullptr);
+                      const int* mirror = nullptr, const dc_frame* const* frames = nullptr);
   // box entry (Net::forward_boxes): member c takes every box at scales[i] * pyramid[c] on a canvas of box_member_canvas(canvas_h / w,
   // pyramid[c]); the image is uploaded once, each member pre-processes its boxes in one launch, then ONE grouped forward.
   // mirror (dc_group_forward_boxes_mirrored): [M] 0/1, null = none; a marked member pre-processes every crop flipped left to right
+  // frame (dc_group_forward_boxes_frame): ONE video frame instead of `bgr`, staged once when it is host memory
   void forward_boxes(const unsigned char* bgr, int h, int w, bool is_device, const int* boxes, const double* scales, int n,
                      const double* pyramid, int canvas_h, int canvas_w, float* const* prob, float* const* loc, float* const* next,
-                     double* const* pose, void* user_stream, const int* mirror = nullptr);
+                     double* const* pose, void* user_stream, const int* mirror = nullptr, const dc_frame* frame = nullptr);
   // Multi-scale fusion (dc_group_fuse_maps; the rule: include/deepcut_hip.h): the maps of the members' LAST forwards — member c holds the
   // same images at scales[c] — resampled onto member `base`'s grid, brought into its units and averaged, in ONE launch (launch_fuse_maps)
   // into a float32 buffer the group owns.  Everything runs on the group's stream (the first member's own; fuse_maps: or the caller's), so

@@ -712,14 +712,45 @@ void NetGroup::forward_batch(const float* const* inputs, const int* n, const int
 
 void NetGroup::forward_images(const unsigned char* const* bgr, const int* n, const int* h, const int* w, const double* scale, bool is_device,
                               float* const* prob, float* const* loc, float* const* next, double* const* pose, void* user_stream,
-                              const int* mirror) {
-  if (!bgr || !n || !h || !w || !scale) throw DcError(DC_EINVAL, "group forward_images: null argument");
+                              const int* mirror, const dc_frame* const* frames) {
+  if (!(frames || bgr) || !n || !h || !w || !scale) throw DcError(DC_EINVAL, "group forward_images: null argument");
+  // every member's frames are checked before any device work
+  for (size_t c = 0; frames && c < nets.size(); ++c) {
+    try {
+      check_frames("forward_frames", frames[c], n[c], h[c], w[c]);
+    } catch (const DcError& e) {
+      throw DcError(e.code, std::string(e.what()) + " (group member " + std::to_string(c) + ")");
+    }
+  }
   if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "forward_images() in CPU mode: libdeepcut_hip provides the MI355X path only");
   const bool own_async = user_stream == (void*)-1;
   if (own_async) user_stream = nullptr;
   nets[0]->ensure_device();
   void* s = user_stream ? user_stream : stream();
-  for (size_t c = 0; c < nets.size(); ++c) nets[c]->prep_images(bgr[c], n[c], h[c], w[c], scale[c], is_device, s, mirror && mirror[c] != 0);
+  for (size_t c = 0; c < nets.size(); ++c) {
+    if (!frames) {
+      nets[c]->prep_images(bgr[c], n[c], h[c], w[c], scale[c], is_device, s, mirror && mirror[c] != 0);
+      continue;
+    }
+    // host frames an earlier member has staged (the usual pyramid: every member sees the same frames) are read from its copy
+    size_t from = c;
+    for (size_t e = 0; !is_device && e < c && from == c; ++e)
+      if (n[e] == n[c] && h[e] == h[c] && w[e] == w[c] &&
+          (frames[e] == frames[c] || std::memcmp(frames[e], frames[c], (size_t)n[c] * sizeof(dc_frame)) == 0))
+        from = e;
+    if (from == c) {
+      nets[c]->prep_images(nullptr, n[c], h[c], w[c], scale[c], is_device, s, mirror && mirror[c] != 0, frames[c]);
+      continue;
+    }
+    // (a member that itself read an earlier one's copy holds that copy's addresses: any match serves)
+    std::vector<dc_frame> staged(frames[c], frames[c] + n[c]);
+    const std::vector<FramePlanes>& pl = nets[from]->staged_planes();
+    for (int i = 0; i < n[c]; ++i) {
+      staged[(size_t)i].plane[0] = pl[(size_t)i].plane0, staged[(size_t)i].plane[1] = pl[(size_t)i].plane1;
+      staged[(size_t)i].pitch[0] = pl[(size_t)i].pitch0, staged[(size_t)i].pitch[1] = pl[(size_t)i].pitch1;
+    }
+    nets[c]->prep_images(nullptr, n[c], h[c], w[c], scale[c], true, s, mirror && mirror[c] != 0, staged.data());
+  }
   enqueue(s);
   for (size_t c = 0; c < nets.size(); ++c) {
     nets[c]->emit_maps(prob ? prob[c] : nullptr, loc ? loc[c] : nullptr, next ? next[c] : nullptr, is_device, s);
@@ -731,7 +762,7 @@ void NetGroup::forward_images(const unsigned char* const* bgr, const int* n, con
 
 void NetGroup::forward_boxes(const unsigned char* bgr, int h, int w, bool is_device, const int* boxes, const double* scales, int n,
                              const double* pyramid, int canvas_h, int canvas_w, float* const* prob, float* const* loc, float* const* next,
-                             double* const* pose, void* user_stream, const int* mirror) {
+                             double* const* pose, void* user_stream, const int* mirror, const dc_frame* frame) {
   if (!pyramid) throw DcError(DC_EINVAL, "group forward_boxes: null pyramid scales");
   // every member's boxes and canvas are checked before any device work; the base canvas itself must be a multiple of 8 too
   if (n < 0) throw DcError(DC_EINVAL, "forward_boxes: n must not be negative");
@@ -752,7 +783,8 @@ void NetGroup::forward_boxes(const unsigned char* bgr, int h, int w, bool is_dev
     }
   }
   if (n == 0) return;
-  if (!bgr) throw DcError(DC_EINVAL, "group forward_boxes: null image");
+  if (frame) check_frames("forward_boxes_frame", frame, 1, h, w);
+  else if (!bgr) throw DcError(DC_EINVAL, "group forward_boxes: null image");
   if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "forward_boxes() in CPU mode: libdeepcut_hip provides the MI355X path only");
   const bool own_async = user_stream == (void*)-1;
   if (own_async) user_stream = nullptr;
@@ -760,8 +792,15 @@ void NetGroup::forward_boxes(const unsigned char* bgr, int h, int w, bool is_dev
   void* s = user_stream ? user_stream : stream();
   const unsigned char* src = bgr;
   bool dev = is_device;
+  dc_frame staged{};  // a host frame: member 0 stages it, the others read that copy
   for (size_t c = 0; c < nets.size(); ++c) {
-    src = nets[c]->prep_boxes(src, h, w, dev, boxes, sc[c].data(), n, ch[c], cw[c], s, mirror && mirror[c] != 0);  // the image crosses PCIe once
+    src = nets[c]->prep_boxes(src, h, w, dev, boxes, sc[c].data(), n, ch[c], cw[c], s, mirror && mirror[c] != 0, frame);  // the image crosses PCIe once
+    if (frame && !dev) {
+      const FramePlanes& pl = nets[c]->staged_planes()[0];
+      staged = *frame;
+      staged.plane[0] = pl.plane0, staged.plane[1] = pl.plane1, staged.pitch[0] = pl.pitch0, staged.pitch[1] = pl.pitch1;
+      frame = &staged;
+    }
     dev = true;
   }
   enqueue(s);

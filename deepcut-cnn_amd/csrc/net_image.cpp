@@ -75,14 +75,101 @@ void image_canvas_size(int h, int w, double scale, int& out_h, int& out_w, int& 
   new_h = (int)((double)(h + kPad) * scale);
 }
 
+// ---- video frames (include/deepcut_hip.h, dc_frame): the checks, the conversion's coefficients, the staging and the plane table -----
+static int frame_row_bytes(int format, int w, int plane) { return plane == 0 ? (format == DC_PIX_NV12 ? w : 3 * w) : 2 * ((w + 1) / 2); }
+
+void check_frames(const char* who, const dc_frame* frames, int n, int h, int w) {
+  const std::string pre = std::string(who) + ": ";
+  if (!frames) throw DcError(DC_EINVAL, pre + "null frames");
+  if (n <= 0 || h <= 0 || w <= 0) throw DcError(DC_EINVAL, pre + "n, height and width must be positive");
+  for (int i = 0; i < n; ++i) {
+    const dc_frame& f = frames[i];
+    const std::string fr = pre + "frame " + std::to_string(i) + ": ";
+    if (f.format != DC_PIX_BGR24 && f.format != DC_PIX_NV12) throw DcError(DC_EINVAL, fr + "unknown format " + std::to_string(f.format));
+    if (f.matrix != DC_CSC_BT601 && f.matrix != DC_CSC_BT709) throw DcError(DC_EINVAL, fr + "unknown matrix " + std::to_string(f.matrix));
+    if (f.range != DC_RANGE_LIMITED && f.range != DC_RANGE_FULL) throw DcError(DC_EINVAL, fr + "unknown range " + std::to_string(f.range));
+    if (f.format != frames[0].format) throw DcError(DC_EINVAL, fr + "format " + std::to_string(f.format) + " differs from frame 0's");
+    if (f.matrix != frames[0].matrix) throw DcError(DC_EINVAL, fr + "matrix " + std::to_string(f.matrix) + " differs from frame 0's");
+    if (f.range != frames[0].range) throw DcError(DC_EINVAL, fr + "range " + std::to_string(f.range) + " differs from frame 0's");
+    for (int k = 0; k < (f.format == DC_PIX_NV12 ? 2 : 1); ++k) {
+      if (!f.plane[k]) throw DcError(DC_EINVAL, fr + "plane[" + std::to_string(k) + "] is NULL");
+      const int need = frame_row_bytes(f.format, w, k);
+      if (f.pitch[k] < need)
+        throw DcError(DC_EINVAL, fr + "pitch[" + std::to_string(k) + "] = " + std::to_string(f.pitch[k]) + " is below the minimum " +
+                                     std::to_string(need) + " of a " + std::to_string(w) + "-pixel row");
+    }
+  }
+}
+
+// the five coefficients of the rule, in double, rounded to nearest (the header's table is this function's output)
+static void frame_csc(int matrix, int range, FrameSource& fs) {
+  const double Kr = matrix == DC_CSC_BT709 ? 0.2126 : 0.299, Kb = matrix == DC_CSC_BT709 ? 0.0722 : 0.114, Kg = 1.0 - Kr - Kb;
+  const double sy = range == DC_RANGE_FULL ? 1.0 : 255.0 / 219.0, sc = range == DC_RANGE_FULL ? 1.0 : 255.0 / 224.0;
+  fs.y0 = range == DC_RANGE_FULL ? 0 : 16;
+  fs.ky = (int)std::rint(65536.0 * sy);
+  fs.rv = (int)std::rint(65536.0 * 2.0 * (1.0 - Kr) * sc);
+  fs.bu = (int)std::rint(65536.0 * 2.0 * (1.0 - Kb) * sc);
+  fs.gu = (int)std::rint(65536.0 * (-2.0 * Kb * (1.0 - Kb) / Kg) * sc);
+  fs.gv = (int)std::rint(65536.0 * (-2.0 * Kr * (1.0 - Kr) / Kg) * sc);
+}
+
+FrameSource Net::frame_source(const dc_frame* frames, int n, int h, int w, bool is_device, void* s) {
+  const int format = frames[0].format, planes = format == DC_PIX_NV12 ? 2 : 1;
+  const int rows[2] = {h, (h + 1) / 2}, rb[2] = {frame_row_bytes(format, w, 0), frame_row_bytes(format, w, 1)};
+  std::vector<FramePlanes> table((size_t)n);
+  if (is_device) {
+    for (int i = 0; i < n; ++i)
+      table[(size_t)i] = FramePlanes{(const unsigned char*)frames[i].plane[0], planes > 1 ? (const unsigned char*)frames[i].plane[1] : nullptr,
+                                     frames[i].pitch[0], planes > 1 ? frames[i].pitch[1] : 0};
+  } else {
+    // the planes as they are, minus the pitch padding: no converted image is made on the host, and 1.5 bytes per pixel travel for NV12
+    const size_t per = (size_t)rb[0] * rows[0] + (planes > 1 ? (size_t)rb[1] * rows[1] : 0), bytes = per * n;
+    if (bytes > img_cap_) {
+      dev_free(img_dev_);
+      img_dev_ = nullptr;
+      dev_alloc((void**)&img_dev_, bytes);
+      img_cap_ = bytes;
+    }
+    for (int i = 0; i < n; ++i) {
+      unsigned char* d[2] = {img_dev_ + per * i, img_dev_ + per * i + (size_t)rb[0] * rows[0]};
+      for (int k = 0; k < planes; ++k)
+        HIPCHECK(hipMemcpy2DAsync(d[k], (size_t)rb[k], frames[i].plane[k], (size_t)frames[i].pitch[k], (size_t)rb[k], (size_t)rows[k],
+                                  hipMemcpyHostToDevice, (hipStream_t)s));
+      table[(size_t)i] = FramePlanes{d[0], planes > 1 ? d[1] : nullptr, rb[0], planes > 1 ? rb[1] : 0};
+    }
+  }
+  // the table, as the box table: a grow-only device buffer filled from a host copy that outlives the upload — and left alone when it
+  // already holds these very entries (a stream of frames decoded into one surface pool, or staged into the same buffer)
+  const size_t tb = (size_t)n * sizeof(FramePlanes);
+  bool same = frame_dev_ && frame_stream_ == s && frame_host_.size() == table.size() && std::memcmp(frame_host_.data(), table.data(), tb) == 0;
+  if (tb > frame_cap_) {
+    dev_free(frame_dev_);
+    frame_dev_ = nullptr;
+    dev_alloc((void**)&frame_dev_, tb);
+    frame_cap_ = tb;
+    same = false;
+  }
+  if (!same) {
+    frame_host_ = table;
+    HIPCHECK(hipMemcpyAsync(frame_dev_, frame_host_.data(), tb, hipMemcpyHostToDevice, (hipStream_t)s));
+    frame_stream_ = s;
+  }
+  FrameSource fs{};
+  fs.planes = reinterpret_cast<const FramePlanes*>(frame_dev_);
+  fs.reader = format == DC_PIX_NV12 ? kReadNv12 : kReadBgr;
+  if (format == DC_PIX_NV12) frame_csc(frames[0].matrix, frames[0].range, fs);
+  return fs;
+}
+
 void Net::forward_images(const unsigned char* bgr, int n, int h, int w, double scale, bool is_device, float* prob, float* loc,
-                         float* next, double* pose, void* user_stream) {
+                         float* next, double* pose, void* user_stream, const dc_frame* frames) {
+  if (frames) check_frames("forward_frames", frames, n, h, w);
   if (Context::get().mode != DC_MODE_GPU)
     throw DcError(DC_ENOCPU, "forward_images() in CPU mode: libdeepcut_hip provides the MI355X path only");
   const bool own_async = user_stream == (void*)-1;
   if (own_async) user_stream = nullptr;
   // (the net's own stream exists only after ensure_device(): prep_images resolves a null `s` to it)
-  prep_images(bgr, n, h, w, scale, is_device, user_stream);
+  prep_images(bgr, n, h, w, scale, is_device, user_stream, false, frames);
   void* s = user_stream ? user_stream : stream;
   enqueue_plan(s);
   emit_maps(prob, loc, next, is_device, s);
@@ -92,7 +179,7 @@ void Net::forward_images(const unsigned char* bgr, int n, int h, int w, double s
   if (!(is_device && (user_stream || own_async))) HIPCHECK(hipStreamSynchronize((hipStream_t)s));
 }
 
-void Net::prep_images(const unsigned char* bgr, int n, int h, int w, double scale, bool is_device, void* s, bool mirror) {
+void Net::prep_images(const unsigned char* bgr, int n, int h, int w, double scale, bool is_device, void* s, bool mirror, const dc_frame* frames) {
   if (n <= 0 || h <= 0 || w <= 0 || !(scale > 0)) throw DcError(DC_EINVAL, "forward_images: n, height, width and scale must be positive");
   int out_h, out_w, new_h, new_w;
   image_canvas_size(h, w, scale, out_h, out_w, new_h, new_w);
@@ -107,7 +194,11 @@ void Net::prep_images(const unsigned char* bgr, int n, int h, int w, double scal
   const int use_h = std::min(out_h, new_h), use_w = std::min(out_w, new_w);  // part of the resized image on the canvas
   const unsigned char* src = bgr;
   const size_t bytes = (size_t)n * h * w * 3;
-  if (!is_device) {
+  ImagePrepParams q{};
+  if (frames) {
+    q.frame = frame_source(frames, n, h, w, is_device, s);
+    src = nullptr;
+  } else if (!is_device) {
     if (bytes > img_cap_) {
       dev_free(img_dev_);
       img_dev_ = nullptr;
@@ -118,7 +209,6 @@ void Net::prep_images(const unsigned char* bgr, int n, int h, int w, double scal
     src = img_dev_;
   }
   const bool need_x = new_w != pw, need_y = new_h != ph;
-  ImagePrepParams q{};
   q.src = src;
   q.n = n, q.h = h, q.w = w;
   q.out_h = out_h, q.out_w = out_w, q.use_h = use_h, q.use_w = use_w;
@@ -180,15 +270,16 @@ void check_boxes(int h, int w, const int* boxes, const double* scales, int n, in
 }
 
 void Net::forward_boxes(const unsigned char* bgr, int h, int w, bool is_device, const int* boxes, const double* scales, int n, int canvas_h,
-                        int canvas_w, float* prob, float* loc, float* next, double* pose, void* user_stream) {
+                        int canvas_w, float* prob, float* loc, float* next, double* pose, void* user_stream, const dc_frame* frame) {
   check_boxes(h, w, boxes, scales, n, canvas_h, canvas_w);
   if (n == 0) return;
-  if (!bgr) throw DcError(DC_EINVAL, "forward_boxes: null image");
+  if (frame) check_frames("forward_boxes_frame", frame, 1, h, w);
+  else if (!bgr) throw DcError(DC_EINVAL, "forward_boxes: null image");
   if (Context::get().mode != DC_MODE_GPU)
     throw DcError(DC_ENOCPU, "forward_boxes() in CPU mode: libdeepcut_hip provides the MI355X path only");
   const bool own_async = user_stream == (void*)-1;
   if (own_async) user_stream = nullptr;
-  prep_boxes(bgr, h, w, is_device, boxes, scales, n, canvas_h, canvas_w, user_stream);
+  prep_boxes(bgr, h, w, is_device, boxes, scales, n, canvas_h, canvas_w, user_stream, false, frame);
   void* s = user_stream ? user_stream : stream;
   enqueue_plan(s);
   emit_maps(prob, loc, next, is_device, s);
@@ -197,12 +288,16 @@ void Net::forward_boxes(const unsigned char* bgr, int h, int w, bool is_device, 
 }
 
 const unsigned char* Net::prep_boxes(const unsigned char* bgr, int h, int w, bool is_device, const int* boxes, const double* scales, int n,
-                                     int canvas_h, int canvas_w, void* s, bool mirror) {
+                                     int canvas_h, int canvas_w, void* s, bool mirror, const dc_frame* frame) {
   Storage& in = begin_batch(n, canvas_h, canvas_w);
   if (in.dim(1) != 3) throw DcError(DC_ESHAPE, "forward_boxes needs a 3-channel input blob");
   if (!s) s = stream;
   const unsigned char* src = bgr;
-  if (!is_device) {
+  BoxPrepParams q{};
+  if (frame) {
+    q.frame = frame_source(frame, 1, h, w, is_device, s);
+    src = nullptr;
+  } else if (!is_device) {
     const size_t bytes = (size_t)h * w * 3;
     if (bytes > img_cap_) {
       dev_free(img_dev_);
@@ -248,7 +343,6 @@ const unsigned char* Net::prep_boxes(const unsigned char* bgr, int h, int w, boo
   HIPCHECK(hipMemcpyAsync(box_dev_, box_host_.data(), bytes, hipMemcpyHostToDevice, (hipStream_t)s));
   box_n_ = n;
   box_mirror_ = mirror;
-  BoxPrepParams q{};
   q.src = src;
   q.img_h = h, q.img_w = w, q.n = n;
   q.out_h = canvas_h, q.out_w = canvas_w;

@@ -103,6 +103,7 @@ Net::~Net() {
   dev_free(scratch_dev_);
   dev_free(img_dev_);
   dev_free(tmp_dev_);
+  dev_free(frame_dev_);
   dev_free(box_dev_);
 }
 

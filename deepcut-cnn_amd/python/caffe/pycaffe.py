@@ -46,7 +46,137 @@ class FuseMirror(C.Structure):
     _fields_ = [("mirror", C.c_void_p), ("image_width", C.c_int), ("joint_mirror", C.c_void_p), ("n_edges", C.c_int), ("edges", C.c_void_p)]
 
 
+class DcFrame(C.Structure):
+    """dc_frame (include/deepcut_hip.h)."""
+    _fields_ = [("plane", C.c_void_p * 2), ("pitch", C.c_int * 2), ("format", C.c_int), ("matrix", C.c_int), ("range", C.c_int)]
+
+
 MAX_ASSEMBLE_DET, MAX_ASSEMBLE_PEOPLE = 64, 256  # dc_net_assemble_people's limits
+PIX_BGR24, PIX_NV12 = 0, 1  # DC_PIX_*
+_CSC_MATRIX = {"bt601": 0, "bt709": 1}  # DC_CSC_*
+_CSC_RANGE = {"limited": 0, "full": 1}  # DC_RANGE_*
+
+
+def csc_coefficients(matrix="bt601", range="limited"):
+    """(ky, rv, bu, gu, gv, y0) of the NV12 conversion rule (include/deepcut_hip.h, dc_frame): computed in double, rounded to nearest."""
+    kr, kb = ((0.299, 0.114), (0.2126, 0.0722))[_CSC_MATRIX[matrix]]
+    kg = 1.0 - kr - kb
+    full = bool(_CSC_RANGE[range])
+    sy, sc = (1.0, 1.0) if full else (255.0 / 219.0, 255.0 / 224.0)
+    r = lambda v: int(np.rint(v))  # noqa: E731
+    return (r(65536.0 * sy), r(65536.0 * 2.0 * (1.0 - kr) * sc), r(65536.0 * 2.0 * (1.0 - kb) * sc),
+            r(65536.0 * (-2.0 * kb * (1.0 - kb) / kg) * sc), r(65536.0 * (-2.0 * kr * (1.0 - kr) / kg) * sc), 0 if full else 16)
+
+
+class Frame(object):
+    """One video frame where a decoder left it (dc_frame): NV12 or BGR planes with a row pitch, host arrays or device addresses.
+    Accepted by Net / NetGroup.forward_images and forward_boxes and by pose.estimate_pose / estimate_poses / estimate_people wherever
+    they take a uint8 image; the conversion runs on the device where the pre-processing fetches a pixel (the rule: deepcut_hip.h)."""
+
+    def __init__(self, fmt, planes, pitches, height, width, matrix="bt601", range="limited", device=False, keep=()):
+        if matrix not in _CSC_MATRIX:
+            raise ValueError("matrix must be one of %s, got %r" % (sorted(_CSC_MATRIX), matrix))
+        if range not in _CSC_RANGE:
+            raise ValueError("range must be one of %s, got %r" % (sorted(_CSC_RANGE), range))
+        self.format, self.matrix, self.range = int(fmt), matrix, range
+        self.height, self.width = int(height), int(width)
+        if self.height <= 0 or self.width <= 0:
+            raise ValueError("a frame's height and width must be positive, got %d x %d" % (self.height, self.width))
+        self.planes = [int(p or 0) for p in planes]
+        self.pitches = [int(p) for p in pitches]
+        self.is_device = bool(device)
+        self._keep = tuple(keep)  # the host arrays the plane addresses point into
+
+    @property
+    def shape(self):
+        return (self.height, self.width, 3)
+
+    @staticmethod
+    def _plane(a, name, shape):
+        """A host plane as it is (no copy: the pitch is the array's own row stride); -> its row pitch in bytes."""
+        if not isinstance(a, np.ndarray) or a.dtype != np.uint8:
+            raise ValueError("%s must be a uint8 numpy array" % name)
+        if tuple(a.shape) != tuple(shape):
+            raise ValueError("%s must have shape %s, got %s" % (name, tuple(shape), tuple(a.shape)))
+        inner = [int(np.prod(shape[k + 1:])) for k in range(1, len(shape))]
+        if [int(v) for v in a.strides[1:]] != inner:
+            raise ValueError("%s: the samples of a row must be contiguous (strides %s, expected %s after the row stride)" %
+                             (name, tuple(a.strides), tuple(inner)))
+        if a.strides[0] < int(np.prod(shape[1:])):
+            raise ValueError("%s: row stride %d is below the %d bytes of a row" % (name, a.strides[0], int(np.prod(shape[1:]))))
+        return int(a.strides[0])
+
+    @classmethod
+    def nv12(cls, y, uv, matrix="bt601", range="limited"):
+        """y: uint8 [H, W]; uv: uint8 [(H+1)//2, (W+1)//2, 2] (Cb, Cr).  Row pitches are the arrays' strides[0]."""
+        if not isinstance(y, np.ndarray) or y.ndim != 2:
+            raise ValueError("y must be a uint8 [H, W] numpy array")
+        h, w = y.shape
+        py = cls._plane(y, "y", (h, w))
+        puv = cls._plane(uv, "uv", ((h + 1) // 2, (w + 1) // 2, 2))
+        return cls(PIX_NV12, [y.ctypes.data, uv.ctypes.data], [py, puv], h, w, matrix, range, False, (y, uv))
+
+    @classmethod
+    def bgr(cls, array):
+        """array: uint8 [H, W, 3] B, G, R with any row stride (a view of a wider surface)."""
+        if not isinstance(array, np.ndarray) or array.ndim != 3:
+            raise ValueError("array must be a uint8 [H, W, 3] numpy array")
+        h, w = array.shape[:2]
+        p = cls._plane(array, "array", (h, w, 3))
+        return cls(PIX_BGR24, [array.ctypes.data, 0], [p, 0], h, w, keep=(array,))
+
+    @classmethod
+    def nv12_device(cls, y_ptr, uv_ptr, height, width, pitch_y, pitch_uv, matrix="bt601", range="limited"):
+        """Device planes by address (e.g. tensor.data_ptr()); the memory stays the caller's to keep alive."""
+        return cls(PIX_NV12, [y_ptr, uv_ptr], [pitch_y, pitch_uv], height, width, matrix, range, True)
+
+    @classmethod
+    def bgr_device(cls, ptr, height, width, pitch):
+        return cls(PIX_BGR24, [ptr, 0], [pitch, 0], height, width, device=True)
+
+    def c_frame(self):
+        f = DcFrame()
+        f.plane[0], f.plane[1] = self.planes[0] or None, self.planes[1] or None
+        f.pitch[0], f.pitch[1] = self.pitches
+        f.format, f.matrix, f.range = self.format, _CSC_MATRIX[self.matrix], _CSC_RANGE[self.range]
+        return f
+
+    def to_bgr(self):
+        """-> uint8 [H, W, 3] B, G, R: the conversion rule in numpy (host frames only), for callers who draw the result."""
+        if self.is_device:
+            raise ValueError("to_bgr() works on host frames only")
+        if self.format == PIX_BGR24:
+            return np.ascontiguousarray(self._keep[0])
+        y, uv = self._keep
+        ky, rv, bu, gu, gv, y0 = csc_coefficients(self.matrix, self.range)
+        rows, cols = np.arange(self.height) >> 1, np.arange(self.width) >> 1
+        c = y.astype(np.int32) - y0
+        d = uv[rows][:, cols, 0].astype(np.int32) - 128
+        e = uv[rows][:, cols, 1].astype(np.int32) - 128
+        lum = ky * c + 32768
+        out = np.stack([(lum + bu * d) >> 16, (lum + gu * d + gv * e) >> 16, (lum + rv * e) >> 16], axis=2)
+        return np.clip(out, 0, 255).astype(np.uint8)
+
+
+def _frame_list(images):
+    """images -> a list of Frames when it is a Frame or a non-empty list / tuple of Frames, else None (the array paths)."""
+    if isinstance(images, Frame):
+        return [images]
+    if isinstance(images, (list, tuple)) and images and all(isinstance(f, Frame) for f in images):
+        return list(images)
+    return None
+
+
+def _frame_array(frames):
+    """-> (dc_frame[n], height, width, is_device) of frames of one size that are all host or all device memory."""
+    f0 = frames[0]
+    for i, f in enumerate(frames):
+        if (f.height, f.width) != (f0.height, f0.width):
+            raise ValueError("frame %d is %d x %d, frame 0 is %d x %d (one batch takes frames of one size)" %
+                             (i, f.height, f.width, f0.height, f0.width))
+        if f.is_device != f0.is_device:
+            raise ValueError("frame %d and frame 0 are not both host or both device frames" % i)
+    return (DcFrame * len(frames))(*[f.c_frame() for f in frames]), f0.height, f0.width, f0.is_device
 
 
 def _load():
@@ -115,6 +245,12 @@ def _load():
         "dc_net_forward_images": (ci, [vp, vp, ci, ci, ci, C.c_double, ci, vp, vp, vp, vp, vp]),
         "dc_image_canvas_size": (ci, [ci, ci, C.c_double, C.POINTER(ci), C.POINTER(ci)]),
         "dc_net_forward_boxes": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp]),
+        "dc_net_forward_frames": (ci, [vp, C.POINTER(DcFrame), ci, ci, ci, C.c_double, ci, vp, vp, vp, vp, vp]),
+        "dc_net_forward_boxes_frame": (ci, [vp, C.POINTER(DcFrame), ci, ci, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp]),
+        "dc_group_forward_frames": (ci, [vp, C.POINTER(vp), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_double), vp, ci,
+                                         C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]),
+        "dc_group_forward_boxes_frame": (ci, [vp, C.POINTER(DcFrame), ci, ci, ci, vp, vp, ci, C.POINTER(C.c_double), ci, ci, vp, C.POINTER(vp),
+                                              C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]),
         "dc_net_detect_parts": (ci, [vp, C.c_double, C.c_float, ci, ci, vp, vp]),
         "dc_net_decode_pairwise": (ci, [vp, C.c_double, ci, vp, vp, vp, vp]),
         "dc_pair_stats_read": (ci, [cp, ci, C.POINTER(ci), vp, vp, vp]),
@@ -846,7 +982,11 @@ class Net(object):
     def forward_images(self, images, scale=1.0, want=("prob", "loc_pred"), pose=True):
         """images: uint8 [n,H,W,3] (or [H,W,3]) BGR host array.  The demo's pre-processing (replicate pad, PIL-exact
         bilinear rescale, mean subtraction, stride-8 canvas; estimate_pose.py:83-103) runs on the device, then the
-        forward and — pose=True — `_pose_from_mats`.  -> dict with the requested NCHW maps and "pose" [n,5,J]."""
+        forward and — pose=True — `_pose_from_mats`.  -> dict with the requested NCHW maps and "pose" [n,5,J].
+        A `Frame` or a list of `Frame`s (video frames of one size: dc_net_forward_frames) is taken in place of the array."""
+        frames = _frame_list(images)
+        if frames is not None:
+            return self._forward_frames(frames, scale, want, pose)
         x = np.ascontiguousarray(images, dtype=np.uint8)
         if x.ndim == 3:
             x = x[None]
@@ -871,16 +1011,51 @@ class Net(object):
                                           ptrs["loc_pred"], ptrs["next_pred"], pp, None))
         return outs
 
+    def _host_maps(self, want):
+        """-> the requested maps of the last forward as NCHW float32 host arrays (dc_net_emit_maps)."""
+        outs = {k: self._out_array(k, self.blobs[k].shape) for k in ("prob", "loc_pred", "next_pred") if k in want}
+        if outs:
+            p = {k: outs[k].ctypes.data_as(C.c_void_p) if k in outs else None for k in ("prob", "loc_pred", "next_pred")}
+            _check(_lib.dc_net_emit_maps(self._h, p["prob"], p["loc_pred"], p["next_pred"], 0, 0, None))
+        return outs
+
+    def _forward_frames(self, frames, scale, want, pose):
+        arr, h, w, dev = _frame_array(frames)
+        n = len(frames)
+        ch, cw = canvas_size(h, w, scale)
+        self.blobs["data"].reshape(n, 3, ch, cw)
+        self.reshape()
+        if dev:  # device frames: the forward with no output (it is complete on return), then the maps and the pose to the host
+            _check(_lib.dc_net_forward_frames(self._h, arr, n, h, w, float(scale), 1, None, None, None, None, None))
+            outs = self._host_maps(want)
+            if pose:
+                outs["pose"] = self.decode_pose(scale)
+            return outs
+        outs = {k: self._out_array(k, self.blobs[k].shape) for k in ("prob", "loc_pred", "next_pred") if k in want}
+        ptrs = {k: outs[k].ctypes.data_as(C.c_void_p) if k in outs else None for k in ("prob", "loc_pred", "next_pred")}
+        pp = None
+        if pose:
+            outs["pose"] = np.empty((n, 5, self.blobs["prob"].shape[1]), np.float64)
+            pp = outs["pose"].ctypes.data_as(C.c_void_p)
+        _check(_lib.dc_net_forward_frames(self._h, arr, n, h, w, float(scale), 0, ptrs["prob"], ptrs["loc_pred"], ptrs["next_pred"], pp, None))
+        return outs
+
     def forward_boxes(self, image, boxes, scales=1.0, canvas=None, want=("prob", "loc_pred"), pose=True):
         """Top-down poses of person boxes: image uint8 [H,W,3] BGR host array, boxes n x 4 (x0, y0, x1, y1) half-open pixel
         corners, scales one number or one per box, canvas (h, w) multiples of 8 or None (the smallest that fits every box:
         check_boxes).  Box i is pre-processed as forward_images would pre-process image[y0:y1, x0:x1] at scales[i], pasted at the
         top-left of the common canvas; all boxes in one launch and one batch forward.  -> dict with the requested NCHW maps
-        (n x the whole canvas's map) and "pose" [n,5,J] decoded on each box's own canvas, in image coordinates."""
-        x = np.ascontiguousarray(image, dtype=np.uint8)
-        if x.ndim != 3 or x.shape[2] != 3:
+        (n x the whole canvas's map) and "pose" [n,5,J] decoded on each box's own canvas, in image coordinates.
+        A `Frame` (dc_net_forward_boxes_frame) is taken in place of the array; a box pairs chroma by its place in the IMAGE.  A device
+        frame's poses are not copied to the host by this method: pass pose=False."""
+        frame = image if isinstance(image, Frame) else None
+        if frame is not None and frame.is_device and pose:
+            raise ValueError("forward_boxes of a device frame returns maps only: pass pose=False")
+        x = None if frame is not None else np.ascontiguousarray(image, dtype=np.uint8)
+        if x is not None and (x.ndim != 3 or x.shape[2] != 3):
             raise ValueError("image must be uint8 [H,W,3] (BGR)")
-        b, sc, (ch, cw) = check_boxes(x.shape, boxes, scales, canvas)
+        shape = frame.shape if frame is not None else x.shape
+        b, sc, (ch, cw) = check_boxes(shape, boxes, scales, canvas)
         n, j = b.shape[0], self.blobs["prob"].shape[1]
         if n == 0:
             outs = {k: np.empty((0,), np.float32) for k in ("prob", "loc_pred", "next_pred") if k in want}
@@ -889,6 +1064,10 @@ class Net(object):
             return outs
         self.blobs["data"].reshape(n, 3, ch, cw)
         self.reshape()
+        if frame is not None and frame.is_device:
+            _check(_lib.dc_net_forward_boxes_frame(self._h, C.byref(frame.c_frame()), shape[0], shape[1], 1, b.ctypes.data_as(C.c_void_p),
+                                                   sc.ctypes.data_as(C.c_void_p), n, ch, cw, None, None, None, None, None))
+            return self._host_maps(want)
         outs, ptrs = {}, {}
         for k in ("prob", "loc_pred", "next_pred"):
             if k in want:
@@ -900,6 +1079,11 @@ class Net(object):
         if pose:
             outs["pose"] = np.empty((n, 5, j), np.float64)
             pp = outs["pose"].ctypes.data_as(C.c_void_p)
+        if frame is not None:
+            _check(_lib.dc_net_forward_boxes_frame(self._h, C.byref(frame.c_frame()), shape[0], shape[1], 0, b.ctypes.data_as(C.c_void_p),
+                                                   sc.ctypes.data_as(C.c_void_p), n, ch, cw, ptrs["prob"], ptrs["loc_pred"], ptrs["next_pred"],
+                                                   pp, None))
+            return outs
         _check(_lib.dc_net_forward_boxes(self._h, x.ctypes.data_as(C.c_void_p), x.shape[0], x.shape[1], 0, b.ctypes.data_as(C.c_void_p),
                                          sc.ctypes.data_as(C.c_void_p), n, ch, cw, ptrs["prob"], ptrs["loc_pred"], ptrs["next_pred"], pp, None))
         return outs
@@ -1156,7 +1340,9 @@ class NetGroup(object):
         list of one array per member.  -> one dict per member with the requested maps and "pose" [n,5,J].
         mirror: one 0/1 per member; a marked member sees its images flipped left to right, flipped by the pre-processing on the device
         (dc_group_forward_images_mirrored), and returns its RAW maps, in the flipped image's frame (`fuse_maps(mirror=...)` undoes the
-        flip).  No pose is decoded then: a mirrored member's own pose would be in flipped coordinates, so pose=True is refused."""
+        flip).  No pose is decoded then: a mirrored member's own pose would be in flipped coordinates, so pose=True is refused.
+        A `Frame` or a list of `Frame`s is ONE batch of video frames that every member sees (dc_group_forward_frames); host frames
+        are uploaded once for the whole group."""
         k = len(self.nets)
         if mirror is not None:
             mirror = [int(bool(v)) for v in mirror]
@@ -1164,6 +1350,9 @@ class NetGroup(object):
                 raise ValueError("one mirror flag per group member: %d flags for %d members" % (len(mirror), k))
             if pose:
                 raise ValueError("forward_images(mirror=...) decodes no pose (a mirrored member's would be in flipped coordinates): pass pose=False")
+        frames = _frame_list(images)
+        if frames is not None:  # one batch of video frames that every member sees (dc_group_forward_frames)
+            return self._forward_frames(frames, scales, want, pose, mirror)
         if isinstance(images, np.ndarray):
             images = [images] * k
         xs = [np.ascontiguousarray(x, dtype=np.uint8) for x in images]
@@ -1196,6 +1385,38 @@ class NetGroup(object):
                                             col("pose"), None))
         return outs
 
+    def _forward_frames(self, frames, scales, want, pose, mirror):
+        k = len(self.nets)
+        if len(scales) != k:
+            raise ValueError("one scale per group member")
+        arr, h, w, dev = _frame_array(frames)
+        n = len(frames)
+        outs = []
+        for m, sc in zip(self.nets, scales):
+            ch, cw = canvas_size(h, w, sc)
+            m.blobs["data"].reshape(n, 3, ch, cw)
+            m.reshape()
+            o = {}
+            if not dev:
+                o = {key: m._out_array(key, m.blobs[key].shape) for key in ("prob", "loc_pred", "next_pred") if key in want}
+                if pose:
+                    o["pose"] = np.empty((n, 5, m.blobs["prob"].shape[1]), np.float64)
+            outs.append(o)
+
+        def col(key):
+            return None if dev else self._ptrs([o[key].ctypes.data if key in o else None for o in outs], k)
+
+        _check(_lib.dc_group_forward_frames(self._h, self._ptrs([C.addressof(arr)] * k, k), self._ints([n] * k), self._ints([h] * k),
+                                            self._ints([w] * k), (C.c_double * k)(*[float(s) for s in scales]),
+                                            None if mirror is None else self._ints(mirror), 1 if dev else 0, col("prob"), col("loc_pred"),
+                                            col("next_pred"), col("pose"), None))
+        if dev:  # the forward is complete: every member's maps and pose to the host
+            for m, sc, o in zip(self.nets, scales, outs):
+                o.update(m._host_maps(want))
+                if pose:
+                    o["pose"] = m.decode_pose(sc)
+        return outs
+
     def forward_boxes(self, image, boxes, pyramid, scales=1.0, canvas=None, want=("prob", "loc_pred"), pose=True, mirror=None):
         """Net.forward_boxes over an image pyramid, as ONE grouped forward: member c takes box i at scales[i] * pyramid[c] on a
         canvas of member_canvas(canvas, pyramid[c]); canvas None = the smallest base canvas that fits every box at scales[i].
@@ -1213,17 +1434,21 @@ class NetGroup(object):
                 mirror = None
             else:
                 pose = False
-        x = np.ascontiguousarray(image, dtype=np.uint8)
-        if x.ndim != 3 or x.shape[2] != 3:
+        frame = image if isinstance(image, Frame) else None  # a video frame (dc_group_forward_boxes_frame) in place of the array
+        if frame is not None and frame.is_device and pose:
+            raise ValueError("forward_boxes of a device frame returns maps only: pass pose=False")
+        x = None if frame is not None else np.ascontiguousarray(image, dtype=np.uint8)
+        if x is not None and (x.ndim != 3 or x.shape[2] != 3):
             raise ValueError("image must be uint8 [H,W,3] (BGR)")
+        shape = frame.shape if frame is not None else x.shape
         pyr = [float(p) for p in pyramid]
         if len(pyr) != k:
             raise ValueError("one pyramid scale per group member")
-        b, sc, (ch, cw) = check_boxes(x.shape, boxes, scales, canvas)
+        b, sc, (ch, cw) = check_boxes(shape, boxes, scales, canvas)
         n = b.shape[0]
         canv = [(member_canvas(ch, p), member_canvas(cw, p)) for p in pyr]
         for p, cv in zip(pyr, canv):
-            check_boxes(x.shape, b, sc * p, cv)
+            check_boxes(shape, b, sc * p, cv)
         outs = []
         for m, (mh, mw) in zip(self.nets, canv):
             j = m.blobs["prob"].shape[1]
@@ -1245,6 +1470,16 @@ class NetGroup(object):
         def col(key):
             return self._ptrs([o[key].ctypes.data if key in o else None for o in outs], k)
 
+        if frame is not None:
+            dev = frame.is_device
+            _check(_lib.dc_group_forward_boxes_frame(self._h, C.byref(frame.c_frame()), shape[0], shape[1], 1 if dev else 0,
+                                                     b.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p), n, (C.c_double * k)(*pyr), ch, cw,
+                                                     None if mirror is None else self._ints(mirror), None if dev else col("prob"),
+                                                     None if dev else col("loc_pred"), None if dev else col("next_pred"),
+                                                     None if dev else col("pose"), None))
+            if dev:  # the forward is complete: the arrays made above are filled from the members' maps
+                outs = [m._host_maps(want) for m in self.nets]
+            return outs
         if mirror is not None:
             _check(_lib.dc_group_forward_boxes_mirrored(self._h, x.ctypes.data_as(C.c_void_p), x.shape[0], x.shape[1], 0,
                                                         b.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p), n, (C.c_double * k)(*pyr), ch,

@@ -292,9 +292,17 @@ def _fused_members(who, scales, fuse, flip, joint_mirror, base):
     return scales + scales, [0] * len(scales) + [1] * len(scales), base, pi
 
 
+def _is_frame(image):
+    """A video frame (`caffe.Frame`: NV12 or pitched BGR planes) in place of the uint8 array?  The device entries take it as it is."""
+    import caffe as _caffe
+
+    return isinstance(image, getattr(_caffe, "Frame", ()))
+
+
 def estimate_pose(image, model_def, model_bin, scales=None, net=None, tiling=None, on_device=True, grouped=None, all_outputs=False, fuse=False,
                   flip=False, joint_mirror=MIRROR_MPII14, base=None):
-    """image: HxWx3 BGR uint8.  Returns the 5x14 pose of the best scale (see module docstring).
+    """image: HxWx3 BGR uint8, or a `caffe.Frame` (converted on the device by the pre-processing; with on_device=False or `tiling`,
+    by `Frame.to_bgr()` on the host first).  Returns the 5x14 pose of the best scale (see module docstring).
     tiling: None (one forward per scale), "exact" or "reference" (see `forward_maps_tiled`).
     on_device: without tiling, pre-process and decode on the GPU (`Net.forward_images`: the same canvas bit
     for bit, the same forward, 70 doubles back instead of the maps); False keeps every step where the
@@ -318,9 +326,13 @@ def estimate_pose(image, model_def, model_bin, scales=None, net=None, tiling=Non
             raise ValueError("estimate_pose(fuse=True / flip=True) fuses the maps on the device in a grouped forward: it takes no tiling, "
                              "on_device=False or grouped=False")
         members, flags, base, pi = _fused_members("estimate_pose", scales, fuse, flip, joint_mirror, base)
-        image = _np.asarray(image)
-        if image.dtype != _np.uint8 or image.ndim != 3 or image.shape[2] != 3:
-            raise ValueError("image must be uint8 [H,W,3] (BGR)")
+        if not _is_frame(image):
+            image = _np.asarray(image)
+            if image.dtype != _np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+                raise ValueError("image must be uint8 [H,W,3] (BGR)")
+    elif _is_frame(image) and (tiling is not None or not on_device):
+        image = image.to_bgr()
+    frame = _is_frame(image)
     if net is None:
         net = _get_model(model_def, model_bin)
     if not all_outputs:
@@ -330,20 +342,20 @@ def estimate_pose(image, model_def, model_bin, scales=None, net=None, tiling=Non
         if not all_outputs:
             _read_outputs_only(net)  # (clones made just now follow their net)
         grp.forward_images(image, members, want=(), pose=False, mirror=flags)
-        return grp.decode_pose(members, base, mirror=flags, image_width=image.shape[1], joint_mirror=pi)[0]
+        return grp.decode_pose(members, base, mirror=flags, image_width=image.width if frame else image.shape[1], joint_mirror=pi)[0]
     poses = []
     if (grouped is None or grouped) and tiling is None and on_device and len(scales) > 1 and hasattr(net, "clone") \
-            and _np.asarray(image).dtype == _np.uint8:
+            and (frame or _np.asarray(image).dtype == _np.uint8):
         # the scale loop of the reference (:81-128) as ONE grouped forward: a member per scale (the net and clones of it, kept
         # with the net), every layer a single launch over all the scales (caffe.NetGroup / dc_group_forward_images)
         import caffe as _caffe
 
         if hasattr(_caffe, "NetGroup"):
-            outs = _scale_group(net, len(scales)).forward_images(_np.asarray(image), list(scales), want=(), pose=True)
+            outs = _scale_group(net, len(scales)).forward_images(image if frame else _np.asarray(image), list(scales), want=(), pose=True)
             return select_best([o["pose"][0] for o in outs])
     for s in scales:
-        if tiling is None and on_device and hasattr(net, "forward_images") and _np.asarray(image).dtype == _np.uint8:
-            poses.append(net.forward_images(_np.asarray(image), s, want=(), pose=True)["pose"][0])
+        if tiling is None and on_device and hasattr(net, "forward_images") and (frame or _np.asarray(image).dtype == _np.uint8):
+            poses.append(net.forward_images(image if frame else _np.asarray(image), s, want=(), pose=True)["pose"][0])
             continue
         if tiling is None:
             prob, loc = forward_maps(net, preprocess(image, s))
@@ -355,7 +367,7 @@ def estimate_pose(image, model_def, model_bin, scales=None, net=None, tiling=Non
 
 def estimate_poses(image, boxes, model_def, model_bin, scales=None, net=None, canvas=None, fuse=False, flip=False,
                    joint_mirror=MIRROR_MPII14, base=None):
-    """Top-down poses of the person boxes of one image: image HxWx3 BGR uint8, boxes n x 4 (x0, y0, x1, y1) half-open pixel corners
+    """Top-down poses of the person boxes of one image: image HxWx3 BGR uint8 or a host `caffe.Frame`, boxes n x 4 (x0, y0, x1, y1) half-open pixel corners
     from the caller's person detector.  Every box runs at every scale of `scales` (default [1.0]; several scales are ONE grouped
     forward, `NetGroup.forward_boxes`), the crop pre-processed as `estimate_pose` pre-processes an image; the best scale per box is
     chosen as there (`select_best`).  canvas: the common (h, w) at scale 1, or None for the smallest that fits every box.
@@ -374,7 +386,8 @@ def estimate_poses(image, boxes, model_def, model_bin, scales=None, net=None, ca
     if net is None:
         net = _get_model(model_def, model_bin)
         _read_outputs_only(net)
-    image = _np.ascontiguousarray(image, dtype=_np.uint8)
+    if not _is_frame(image):
+        image = _np.ascontiguousarray(image, dtype=_np.uint8)
     b, _, base = _caffe.check_boxes(image.shape, boxes, 1.0, canvas)
     if b.shape[0] == 0:
         return []

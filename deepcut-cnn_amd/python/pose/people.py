@@ -46,7 +46,7 @@ def _check_joint_mirror(joint_mirror):
 
 def estimate_people(image, model_def, model_bin, stats, scale=1.0, net=None, scales=None, base=None, flip=False, joint_mirror=MIRROR_MPII14,
                     **assembly):
-    """image: HxWx3 BGR uint8.  stats: the path of the model's pair-statistics file (deepcut_tools.read_pair_stats) or the
+    """image: HxWx3 BGR uint8, or a `caffe.Frame` (NV12 / pitched BGR planes, converted by the device pre-processing).  stats: the path of the model's pair-statistics file (deepcut_tools.read_pair_stats) or the
     (edges, mean, std) triple itself.  Runs the image entry (`Net.forward_images`: pre-processing on the device) with all three
     outputs computed, then `Net.assemble_people(scale=scale, edges=..., mean=..., std=..., **assembly)`; `assembly` takes its other
     arguments (threshold, radius, max_det, max_cost, seed_threshold, max_people, min_joints, joint_order: the defaults of max_cost
@@ -82,9 +82,13 @@ def estimate_people(image, model_def, model_bin, stats, scale=1.0, net=None, sca
     missing = [k for k in ("prob", "loc_pred", "next_pred") if k not in net.wanted_outputs]
     if missing:
         raise ValueError("estimate_people needs all three maps, the net leaves out %r (net.set_outputs(None) brings them back)" % (missing,))
-    image = _np.asarray(image)
-    if image.dtype != _np.uint8 or image.ndim != 3 or image.shape[2] != 3:
-        raise ValueError("image must be uint8 [H,W,3] (BGR)")
+    from .estimate_pose import _is_frame
+
+    frame = _is_frame(image)
+    if not frame:
+        image = _np.asarray(image)
+        if image.dtype != _np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+            raise ValueError("image must be uint8 [H,W,3] (BGR)")
     if scales is not None or flip:
         from .estimate_pose import _scale_group
 
@@ -95,7 +99,7 @@ def estimate_people(image, model_def, model_bin, stats, scale=1.0, net=None, sca
         if flip:
             if base is None:
                 base = _base_scale(scales)
-            mirrored = dict(mirror=[0] * len(scales) + [1] * len(scales), image_width=image.shape[1], joint_mirror=joint_mirror)
+            mirrored = dict(mirror=[0] * len(scales) + [1] * len(scales), image_width=image.width if frame else image.shape[1], joint_mirror=joint_mirror)
             scales = scales + scales
         grp = _scale_group(net, len(scales))
         for m in grp.nets[1:]:  # the clones kept with the net are this module's to set: all three outputs, like the net itself

@@ -271,6 +271,53 @@ int dc_image_canvas_size(int height, int width, double scale, int* canvas_h, int
 int dc_net_forward_boxes(dc_net* net, const unsigned char* image, int height, int width, int is_device, const int* boxes, const double* scales,
                          int n, int canvas_h, int canvas_w, float* prob, float* loc_pred, float* next_pred, double* pose, void* stream);
 
+/* ---- video frames: the image and box entries on NV12 and pitched surfaces ------------------------------------------------
+ * NO REFERENCE COUNTERPART: the reference's demo reads packed BGR from cv2.imread.  A dc_frame describes one image where a decoder
+ * left it: up to two planes with a row pitch in BYTES each, host (is_device=0) or device memory like the other entries' pixels.
+ * Odd widths and heights are allowed; the chroma plane then has the extra half row / column, as the sizes below say.            */
+#define DC_PIX_BGR24 0   /* plane[0]: B,G,R bytes, pitch[0] >= 3*width; plane[1] unused                                  */
+#define DC_PIX_NV12  1   /* plane[0]: Y, height rows, pitch[0] >= width; plane[1]: Cb,Cr byte pairs,
+                            (height+1)/2 rows of (width+1)/2 pairs, pitch[1] >= 2*((width+1)/2)                         */
+#define DC_CSC_BT601 0   /* Kr = 0.299,  Kb = 0.114  */
+#define DC_CSC_BT709 1   /* Kr = 0.2126, Kb = 0.0722 */
+#define DC_RANGE_LIMITED 0   /* Y 16..235, C 16..240 */
+#define DC_RANGE_FULL    1
+typedef struct dc_frame { const void* plane[2]; int pitch[2]; int format, matrix, range; } dc_frame;
+/* THE RULE (this project's statement of the two standards; integer arithmetic, the same on every path).
+ * Chroma siting: the pixel at image position (x, y) uses chroma sample (x >> 1, y >> 1); there is no interpolation.  For the box
+ *   entries x and y are ABSOLUTE image coordinates (x0 + crop column, y0 + crop row), not crop-relative: a box with an odd origin
+ *   pairs chroma differently from a host-cut crop of the planes.
+ * Conversion: c = Y - y0, d = Cb - 128, e = Cr - 128.  Limited range: y0 = 16, sy = 255/219, sc = 255/224; full range: y0 = 0,
+ *   sy = sc = 1.  Kg = 1 - Kr - Kb.  Five coefficients, computed on the host in double and rounded to nearest:
+ *     ky = rint(65536 sy)                     rv = rint(65536 * 2(1-Kr) sc)          bu = rint(65536 * 2(1-Kb) sc)
+ *     gu = rint(65536 * (-2 Kb (1-Kb) / Kg) sc)                 gv = rint(65536 * (-2 Kr (1-Kr) / Kg) sc)
+ *   then on int32 with an arithmetic shift (the magnitude stays below 2^26), clip8 = clamp to 0..255:
+ *     R = clip8((ky c + rv e + 32768) >> 16)    G = clip8((ky c + gu d + gv e + 32768) >> 16)    B = clip8((ky c + bu d + 32768) >> 16)
+ *   (ky, rv, bu, gu, gv): BT.601 limited (76309, 104597, 132201, -25675, -53279), BT.709 limited (76309, 117489, 138438, -13975,
+ *   -34925), BT.601 full (65536, 91881, 116130, -22553, -46802).  Each coefficient is within 2^-17 of the real one and multiplies a
+ *   value of at most 255, so the result is within one level of the real-valued matrix rounded to nearest (tests/test_nv12_rule.py:
+ *   all 2^24 triples, every matrix and range; full-range BT.601 is also within one level of Pillow's YCbCr -> RGB, whose tables
+ *   are no closed form, so equality with Pillow is not claimed).
+ * Where it runs: where a source pixel is fetched by the pre-processing kernels, after the replicate clamp and the mirror
+ *   reflection.  Pillow's resample works on 8-bit channels, so every frame entry gives BIT FOR BIT what the entry it is named after
+ *   gives on the image converted by the rule on the host.  DC_PIX_BGR24 applies no conversion: it only adds the pitch.
+ * The entries: each is the entry it is named after with a dc_frame where that one takes a pixel pointer, and behaves like it in
+ *   every other respect (outputs, pose, stream, is_device, errors, n = 0).  dc_net_forward_frames takes n frames (n separate
+ *   surfaces of one height x width, format, matrix and range); the box entries one.  dc_group_forward_frames takes one array of
+ *   n[c] frames per member (the usual case: the same array for every member); the two group entries take `mirror` ([members] 0/1,
+ *   NULL = none) as the _mirrored entries do, and a mirrored member records that its last batch was mirrored exactly as they do, so
+ *   dc_group_fuse_maps_mirrored, dc_group_decode_pose, dc_group_decode_boxes and dc_group_assemble_people_mirrored work unchanged.
+ * Host frames (is_device = 0) are NOT converted on the host: their planes are staged into the net's image buffer, one 2-D copy per
+ *   plane on the call's stream, without the pitch padding — 1.5 bytes per pixel travel for NV12 —, and a frame that several
+ *   members of a group share travels once.
+ * Errors: DC_EINVAL naming the field and the frame index, before any device work, for a NULL plane the format needs, a pitch below
+ *   the minimum, an unknown format / matrix / range, and frames of one call that differ in format, matrix or range.             */
+int dc_net_forward_frames(dc_net* net, const dc_frame* frames, int n, int height, int width, double scale, int is_device, float* prob,
+                          float* loc_pred, float* next_pred, double* pose, void* stream);
+int dc_net_forward_boxes_frame(dc_net* net, const dc_frame* frame, int height, int width, int is_device, const int* boxes,
+                               const double* scales, int n, int canvas_h, int canvas_w, float* prob, float* loc_pred, float* next_pred,
+                               double* pose, void* stream);
+
 /* ---- multi-person consumers of the maps (no reference code: the reference repository stops at the maps) --------
  * What they invert is the label encoding of the reference's training layer (src/caffe/layers/pose_data_layer.cpp:
  * 686-802): a map cell (row, col) stands for the image point pt = (col*8+4, row*8+4)/scale; loc_pred holds
@@ -618,6 +665,15 @@ int dc_group_forward_boxes_mirrored(dc_group* group, const unsigned char* image,
                                     float* const* next_pred, void* stream);
 int dc_group_decode_boxes(dc_group* group, const double* pyramid_scales, int base, const dc_fuse_mirror* fm, float* prob, float* loc_pred,
                           double* pose, int is_device, void* stream);
+/* dc_group_forward_images[_mirrored] / dc_group_forward_boxes[_mirrored] on video frames (dc_frame, above: the rule, the staging, the
+ * errors).  frames[c] is member c's array of n[c] frames; pose entries of a mirrored member are the caller's to leave NULL.     */
+int dc_group_forward_frames(dc_group* group, const dc_frame* const* frames, const int* n, const int* height, const int* width,
+                            const double* scale, const int* mirror /* [M], 0/1; NULL = none */, int is_device, float* const* prob,
+                            float* const* loc_pred, float* const* next_pred, double* const* pose, void* stream);
+int dc_group_forward_boxes_frame(dc_group* group, const dc_frame* frame, int height, int width, int is_device, const int* boxes,
+                                 const double* scales, int n, const double* pyramid_scales, int canvas_h, int canvas_w,
+                                 const int* mirror /* [M], 0/1; NULL = none */, float* const* prob, float* const* loc_pred,
+                                 float* const* next_pred, double* const* pose, void* stream);
 /* the merged plan of the last forward: one line per launch ("conv_gemm_mp<tile> problems=.. grid=.." or "member c: <kernel>");
  * NULL + dc_last_error() before the first forward; pointer valid until the next call on this group                            */
 const char* dc_group_plan_text(dc_group* group);
