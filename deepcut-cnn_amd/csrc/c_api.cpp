@@ -174,6 +174,8 @@ int dc_net_set_option(dc_net* net, int key, int value) {
       n->set_dtype(value);
     } else if (key == DC_OPT_OUTPUTS) {
       n->set_outputs_mask(value);
+    } else if (key == DC_OPT_SPARSE_PAIRWISE) {
+      n->set_sparse_pairwise(value);
     } else {
       throw DcError(DC_EINVAL, "unknown option " + std::to_string(key));
     }
@@ -187,6 +189,7 @@ int dc_net_get_option(dc_net* net, int key, int* value) {
   else if (key == DC_OPT_HIPGRAPH) *value = n->use_graph;
   else if (key == DC_OPT_DTYPE) *value = n->dtype;
   else if (key == DC_OPT_OUTPUTS) *value = n->outputs_mask;
+  else if (key == DC_OPT_SPARSE_PAIRWISE) *value = n->sparse_pairwise;
   else return fail(DC_EINVAL, "unknown option " + std::to_string(key));
   return DC_OK;
 }
@@ -530,6 +533,15 @@ int dc_net_decode_pairwise(dc_net* net, double scale, int ndet, const int* detec
   return guard([&] { N(net)->decode_pairwise(scale, ndet, detections, mean, stdev, out); });
 }
 
+int dc_net_pairwise_at(dc_net* net, int ndet, const int* detections, float* out) {
+  REQUIRE(net);
+  if (ndet > 0) {
+    REQUIRE(detections);
+    REQUIRE(out);
+  }
+  return guard([&] { N(net)->pairwise_at(ndet, detections, out); });
+}
+
 int dc_pair_stats_read(const char* path, int max_edges, int* n_edges, int* edges, double* mean, double* stdev) {
   REQUIRE(path);
   REQUIRE(n_edges);
@@ -592,7 +604,8 @@ int dc_net_stats(dc_net* net, long long* out, int n) {
   REQUIRE(out);
   const NetStats& st = N(net)->stats;
   const long long v[DC_NUM_STATS] = {st.lowerings,      st.graph_instantiations, st.plan_hits, st.autotune_runs,
-                                     st.buffer_growths, st.repacks,              (long long)N(net)->parked_.size() + (N(net)->plan_valid ? 1 : 0)};
+                                     st.buffer_growths, st.repacks,              (long long)N(net)->parked_.size() + (N(net)->plan_valid ? 1 : 0),
+                                     st.sparse_packs};
   for (int i = 0; i < n && i < DC_NUM_STATS; ++i) out[i] = v[i];
   return DC_OK;
 }
@@ -672,6 +685,18 @@ int dc_stream1x1_pack(const float* g, int cout, int k, float* out) {
   if (!g || !out) return fail(DC_EINVAL, "dc_stream1x1_pack: null pointer");
   if (cout <= 0 || k <= 0 || cout % 32 || k % 16) return fail(DC_EINVAL, "dc_stream1x1_pack: cout must be a multiple of 32, k of 16");
   return guard([&] { dc::stream1x1_pack_filters(g, cout, k, out); });
+}
+
+int dc_sparse_head_pack_size(int cout, int k3, int k5) {
+  if (cout <= 0 || k3 <= 0 || k5 <= 0) return -1;
+  const size_t n = dc::sparse_head_image_floats(cout, k3, k5);
+  return n > 0x7fffffffu ? -1 : (int)n;
+}
+
+int dc_sparse_head_pack(const float* ws, const float* wd, int cout, int k3, int k5, float* out) {
+  if (!ws || !wd || !out) return fail(DC_EINVAL, "dc_sparse_head_pack: null pointer");
+  if (dc_sparse_head_pack_size(cout, k3, k5) < 0) return fail(DC_EINVAL, "dc_sparse_head_pack: cout, k3 and k5 must be positive (and the image below 2^31 floats)");
+  return guard([&] { dc::sparse_head_pack_filters(ws, wd, cout, k3, k5, out); });
 }
 
 int dc_stream1x1f_pack(const float* g, int cout, int k, float* out) {

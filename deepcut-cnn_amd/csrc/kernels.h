@@ -379,6 +379,37 @@ int launch_assemble(int NB, int J, int max_det, int max_people, int min_joints, 
                     const double* dets, const double* cost, const int* order, double* link, int* n_people, double* people, int* cand,
                     void* stream);
 
+// The pairwise head at a list of cells (sparse_head.hip; the rule: include/deepcut_hip.h, dc_net_pairwise_at).  x3 / x5: the NHWC inputs
+// of the head's 1x1 skip convolution ([NB][H][W], pitch cp3, K3 channels) and of its stride-2 3x3 deconvolution ([NB][h5][w5], pitch cp5,
+// K5 channels), first channel already added, in the net's element type; vec3 / vec5: 4 consecutive channels of a cell may be read as one
+// aligned vector (K % 4 == 0, pitch and first channel multiples of 4).  wimg / bias: sparse_head_pack_filters' image and bias_s + bias_d
+// [Cout].  out: float32 [NB][H][W][Cout]; only the listed cells are written.
+struct SparseHeadArgs {
+  const void* x3;
+  const void* x5;
+  const float* wimg;
+  const float* bias;
+  float* out;
+  int cp3, cp5, K3, K5, Cout;
+  int NB, H, W, h5, w5, oh, ow;
+  int vec3, vec5;
+};
+// the image's size in floats, and the image: ws [cout][k3], wd [k5][cout][3][3] -> [segment 0..9][ceil(cout/32)][K block of 8][64][4]
+// (segment t < 9: tap ky*3 + kx = t over k5, at float offset t * ceil(cout/32) * ceil(k5/8) * 256; segment 9: the skip over k3, behind them)
+size_t sparse_head_image_floats(int cout, int k3, int k5);
+void sparse_head_pack_filters(const float* ws, const float* wd, int cout, int k3, int k5, float* out);
+// p[i] = (float)(T)p[i] in place, T the 16-bit type of ekind (nothing for float32): the filters as a 16-bit net's dense head sees them
+int launch_round_through(float* p, long n, int ekind, void* stream);
+// Two launches: the n slots — part_select's candidates (counts [NB*J], dets [NB*J][MD][5], n = NB*J*MD, cells null) or n (image, row,
+// col) triples on the device (cells; counts / dets null) — sorted into the four parity classes in `work` (4 + 4n ints of scratch), then
+// the head at those cells.  Slots that are no cell of the map are skipped.
+int launch_sparse_head(const SparseHeadArgs& a, int ekind, const int* counts, const double* dets, int J, int MD, const int* cells, int n,
+                       int* work, void* stream);
+
+// out[d*C + ch] = (float) map[((n*H + row)*W + col)*cp + c0 + ch] for detection d = (n, row, col) of det [ndet][3] (device; every cell
+// inside the map: the caller checked): the raw values of a map at given cells
+int launch_map_gather(const void* map, int cp, int c0, int ekind, int H, int W, int C, int ndet, const int* det, float* out, void* stream);
+
 // Multi-scale fusion of the maps of a pyramid (pose.hip; the rule is this project's own, like the assembly above: include/deepcut_hip.h,
 // dc_group_fuse_maps and dc_group_fuse_maps_mirrored).  Member m holds the maps of the same NB images at its own scale; map k (0 prob,
 // 1 loc_pred, 2 next_pred) is the NHWC image ptr[k] of H x W cells with channel pitch cp[k], first channel c0[k]; q = scale of m / scale

@@ -243,7 +243,7 @@ struct PlanState {
 };
 
 struct NetStats {  // dc_net_stats
-  long long lowerings = 0, graph_instantiations = 0, plan_hits = 0, autotune_runs = 0, buffer_growths = 0, repacks = 0;
+  long long lowerings = 0, graph_instantiations = 0, plan_hits = 0, autotune_runs = 0, buffer_growths = 0, repacks = 0, sparse_packs = 0;
 };
 
 struct Net {
@@ -259,6 +259,7 @@ struct Net {
   int dtype = 0;  // ElemKind of activations / filters: 0 float; 1 _Float16, 2 __bf16 (fp32 accumulate + epilogue in both)
   int use_graph = 0;
   int outputs_mask = -1;  // DC_OPT_OUTPUTS: bit i = output i (order of `outputs`) is wanted
+  int sparse_pairwise = 0;  // DC_OPT_SPARSE_PAIRWISE: a plan without next_pred has the pairwise head evaluated at the cells its consumers read
   std::shared_ptr<ModelShared> shared;   // joint with every clone
   uint64_t seen_weights_gen = 0;         // generation the cached plans were lowered from
   // the ACTIVE plan (the fields below are swapped with a parked PlanState when the input shape changes)
@@ -296,6 +297,7 @@ struct Net {
   void* own_stream();          // the net's own stream, created on first use
   void set_dtype(int d);  // 0 float32 / 1 float16 / 2 bfloat16 device images (DC_OPT_DTYPE)
   void set_outputs_mask(int mask);  // DC_OPT_OUTPUTS
+  void set_sparse_pairwise(int v);  // DC_OPT_SPARSE_PAIRWISE (sparse_pairwise.cpp): DC_EUNSUP on a net without a recognisable pairwise head
   void copy_from(const std::string& path);
   void save(const std::string& path);
   void reshape();         // propagate input shapes through every layer (Net::Reshape)
@@ -336,6 +338,9 @@ struct Net {
   // multi-person consumers of the maps of the last forward (encoding: pose_data_layer.cpp:686-802)
   void detect_parts(double scale, float thr, int radius, int max_det, int* counts, double* dets);
   void decode_pairwise(double scale, int ndet, const int* det, const double* mean, const double* stdev, double* out);
+  // the raw next_pred values at ndet (image, row, col) cells -> out [ndet][C] float32 (dc_net_pairwise_at): from the dense map when the plan
+  // has it, by the sparse head otherwise
+  void pairwise_at(int ndet, const int* det, float* out);
   // the people of every image of the last forward: candidates (part_select), pair costs and greedy assembly (people.cpp / people.hip)
   // back to back on the device, only the results travel (dc_net_assemble_people; the grouping rule is this project's own)
   struct AssembleParams {
@@ -405,9 +410,31 @@ struct Net {
   static void check_assemble_params(const AssembleParams& q);
   static std::vector<int> check_assemble_graph(const AssembleParams& q, int J, int n_edges, const int* edges, const double* mean,
                                                const double* stdev, const int* joint_order);
+  // between (may be empty): called with stage A's device outputs (counts, dets) after its launch and before stage B's — the sparse
+  // pairwise head fills N's cells there
   static void assemble_maps(const MapRef& P, const MapRef& L, const MapRef& N, const AssembleParams& q, const std::vector<int>& table,
                             int n_edges, const double* mean, const double* stdev, const std::function<void*(size_t)>& scratch, void* stream,
-                            int* n_people, double* people, int* cand, double* cost);
+                            int* n_people, double* people, int* cand, double* cost,
+                            const std::function<void(const int*, const double*)>& between = nullptr);
+  // DC_OPT_SPARSE_PAIRWISE (sparse_pairwise.cpp)
+  struct PairHead {
+    int elt = -1, conv = -1, crop = -1, deconv = -1;  // layer indices: the Eltwise SUM, its 1x1 Convolution, its Crop and the Crop's Deconvolution
+  };
+  PairHead find_pair_head() const;
+  bool next_in_plan() const;  // the current plan computes next_pred (as a tensor of its own or a view of the merged heads)
+  struct SparseNext {
+    MapRef N;          // the float32 scratch map [NB][H][W][C]: defined at the cells the head was run at
+    SparseHeadArgs a;
+    int ekind;         // element type of the head's inputs
+    int* work;         // class lists (launch_sparse_head)
+    int* cells;        // room for the (image, row, col) triples
+  };
+  SparseNext sparse_next(int nslots, int ntriples);   // inputs, packed filters and scratch; nothing launched
+  SparseNext sparse_next_at(int ndet, const int* det);  // ... and the head run at ndet host triples
+  void refresh_pack_cache();  // caller holds shared->mu: the packed-image cache emptied when the parameters changed since it was filled
+  std::shared_ptr<DevVec> sparse_w_, sparse_b_;  // the head's filter image and bias (kept alive here as a plan keeps its launches')
+  unsigned char* sparse_dev_ = nullptr;
+  size_t sparse_cap_ = 0;
   unsigned char* scratch_dev_ = nullptr;  // candidates / detections / pairwise scratch
   size_t scratch_cap_ = 0;
   void* scratch(size_t bytes);

@@ -489,7 +489,8 @@ void Net::decode_pairwise(double scale, int ndet, const int* det, const double* 
   if (!(scale > 0) || ndet < 0) throw DcError(DC_EINVAL, "decode_pairwise: scale > 0, ndet >= 0");
   if (ndet == 0) return;
   ensure_device();
-  const MapRef N = map_ref("next_pred");
+  // DC_OPT_SPARSE_PAIRWISE on a plan without next_pred: the head at the detections' cells first (sparse_pairwise.cpp)
+  const MapRef N = sparse_pairwise && !next_in_plan() ? sparse_next_at(ndet, det).N : map_ref("next_pred");
   if (N.C % 2) throw DcError(DC_ESHAPE, "decode_pairwise: next_pred must have 2 channels per regression edge");
   const int E = N.C / 2;
   const size_t det_b = ((size_t)ndet * 3 * sizeof(int) + 255) / 256 * 256, st_b = (size_t)E * 2 * sizeof(double);

@@ -105,6 +105,7 @@ Net::~Net() {
   dev_free(tmp_dev_);
   dev_free(frame_dev_);
   dev_free(box_dev_);
+  dev_free(sparse_dev_);
 }
 
 Net* Net::create(const std::string& text, int phase, const Net* clone_of) {
@@ -132,6 +133,7 @@ Net* Net::clone() {
   c->fuse = fuse;
   c->use_graph = use_graph;
   c->outputs_mask = outputs_mask;
+  c->sparse_pairwise = sparse_pairwise;
   if (dtype != c->dtype) {
     c->dtype = dtype;
     for (auto& st : c->storages)

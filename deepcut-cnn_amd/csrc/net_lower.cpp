@@ -406,13 +406,7 @@ void Net::build_plan() {
   // the packed-image cache is shared with the clones: the first executor to lower after a parameter change empties it
   // (images still referenced by another executor's plans stay alive until that executor re-lowers too)
   std::lock_guard<std::mutex> pack_lock(shared->mu);
-  if (shared->packed_gen != shared->weights_gen) {
-    shared->vec_by_key.clear();
-    shared->packed_gen = shared->weights_gen;
-    for (auto& L : layers)
-      for (auto& pb : L.params) pb->st->packed_hash = content_hash(pb->st->host_ptr(), pb->st->count());
-    ++stats.repacks;
-  }
+  refresh_pack_cache();
   auto get_vec = [&](const std::string& key, const std::function<void(std::vector<float>&)>& fill) {
     auto it = shared->vec_by_key.find(key);
     if (it != shared->vec_by_key.end()) return it->second;
@@ -983,6 +977,16 @@ void Net::build_plan() {
     for (int d : blobs[bi]->st->shape) plan_input_shape.push_back(d);
   cur_last_use_ = ++use_clock_;
   release_graph();
+}
+
+// Caller holds shared->mu.
+void Net::refresh_pack_cache() {
+  if (shared->packed_gen == shared->weights_gen) return;
+  shared->vec_by_key.clear();
+  shared->packed_gen = shared->weights_gen;
+  for (auto& L : layers)
+    for (auto& pb : L.params) pb->st->packed_hash = content_hash(pb->st->host_ptr(), pb->st->count());
+  ++stats.repacks;
 }
 
 // ---- per-shape plan cache -----------------------------------------------------------------------------

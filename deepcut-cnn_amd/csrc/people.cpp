@@ -99,7 +99,8 @@ PairStats read_pair_stats(const std::string& path) {
 
 // ---- the device path ---------------------------------------------------------------------------------------------------
 // Stage A = Net::detect_parts' launch with its outputs left in the scratch buffer, stage B = launch_pair_cost, stage C =
-// launch_assemble: three launches on one stream with nothing in between, then the downloads of the results.  The argument checks
+// launch_assemble: three launches on one stream with nothing in between (DC_OPT_SPARSE_PAIRWISE on a net without next_pred: the sparse
+// head's two launches between A and B, sparse_pairwise.cpp), then the downloads of the results.  The argument checks
 // and the device half are functions of their own: NetGroup::assemble_people runs them on the fused maps of a pyramid (net_group.cpp).
 void Net::check_assemble_params(const AssembleParams& q) {
   auto bad = [](const std::string& m) { throw DcError(DC_EINVAL, "assemble_people: " + m); };
@@ -156,13 +157,22 @@ void Net::assemble_people(const AssembleParams& q, int n_edges, const int* edges
   // (the arguments above are refused with or without a device; from here on the device is needed)
   if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "assemble_people() in CPU mode");
   ensure_device();
-  const MapRef P = map_ref("prob"), L = map_ref("loc_pred"), N = map_ref("next_pred");
+  const MapRef P = map_ref("prob"), L = map_ref("loc_pred");
+  if (sparse_pairwise && !next_in_plan()) {  // DC_OPT_SPARSE_PAIRWISE: the head at the candidates' cells, between stages A and B
+    const SparseNext sn = sparse_next(P.NB * P.C * q.max_det, 0);
+    assemble_maps(P, L, sn.N, q, table, n_edges, mean, stdev, [this](size_t bytes) { return scratch(bytes); }, stream, n_people, people, cand, cost,
+                  [&](const int* d_cnt, const double* d_det) {
+                    KCHECK(launch_sparse_head(sn.a, sn.ekind, d_cnt, d_det, P.C, q.max_det, nullptr, P.NB * P.C * q.max_det, sn.work, stream));
+                  });
+    return;
+  }
+  const MapRef N = map_ref("next_pred");
   assemble_maps(P, L, N, q, table, n_edges, mean, stdev, [this](size_t bytes) { return scratch(bytes); }, stream, n_people, people, cand, cost);
 }
 
 void Net::assemble_maps(const MapRef& P, const MapRef& L, const MapRef& N, const AssembleParams& q, const std::vector<int>& table, int n_edges,
                         const double* mean, const double* stdev, const std::function<void*(size_t)>& scratch, void* stream, int* n_people,
-                        double* people, int* cand, double* cost) {
+                        double* people, int* cand, double* cost, const std::function<void(const int*, const double*)>& between) {
   const int J = P.C;
   if (L.C != 2 * P.C || L.H != P.H || L.W != P.W || L.NB != P.NB || L.es != P.es)
     throw DcError(DC_ESHAPE, "assemble_people: loc_pred must have 2 channels per joint and the score map's size");
@@ -207,6 +217,7 @@ void Net::assemble_maps(const MapRef& P, const MapRef& L, const MapRef& N, const
   if (E) HIPCHECK(hipMemcpyAsync(d_mean, stats.data(), stats.size() * sizeof(double), hipMemcpyHostToDevice, s));
   KCHECK(launch_part_select(P.ptr, P.cp, P.c0, L.ptr, L.cp, L.c0, P.ek, NB, P.H, P.W, J, q.threshold, q.radius, q.scale, MD, d_spill, d_cnt,
                             d_det, stream));
+  if (between) between(d_cnt, d_det);
   KCHECK(launch_pair_cost(N.ptr, N.cp, N.c0, N.ek, NB, N.H, N.W, J, MD, q.scale, d_cnt, d_det, d_tab, d_mean, d_std, d_cost, stream));
   KCHECK(launch_assemble(NB, J, MD, PP, q.min_joints, q.max_cost, (double)q.seed_threshold, d_cnt, d_det, d_cost, d_tab + (size_t)J * J, d_link,
                          d_np, d_ppl, d_cand, stream));

@@ -318,6 +318,9 @@ def _load():
         "dc_stream1x1_pack": (ci, [C.c_void_p, ci, ci, C.c_void_p]),
         "dc_stem7x7_pack": (ci, [C.c_void_p, ci, C.c_void_p]),
         "dc_stream1x1f_pack": (ci, [C.c_void_p, ci, ci, C.c_void_p]),
+        "dc_net_pairwise_at": (ci, [vp, ci, C.c_void_p, C.c_void_p]),
+        "dc_sparse_head_pack_size": (ci, [ci, ci, ci]),
+        "dc_sparse_head_pack": (ci, [C.c_void_p, C.c_void_p, ci, ci, ci, C.c_void_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -403,6 +406,27 @@ def stream1x1f_pack(g):
     out = np.empty((cout // 16, k // 16, 64, 4), np.float32)
     _check(_lib.dc_stream1x1f_pack(g.ctypes.data_as(C.c_void_p), cout, k, out.ctypes.data_as(C.c_void_p)))
     return out
+
+
+def sparse_head_pack(ws, wd):
+    """dc_sparse_head_pack: the filter image of the sparse pairwise head (csrc/sparse_head.hip) of the skip filters ws [cout, k3] (or
+    [cout, k3, 1, 1]) and the deconvolution filters wd [k5, cout, 3, 3] as the library packs it for float32 nets -> (taps float32
+    [9, ceil(cout/32), ceil(k5/8), 64, 4], skip float32 [ceil(cout/32), ceil(k3/8), 64, 4]): lane l of K block j of chunk q holds
+    W[k = 8j + 4(l // 32) + m][n = 32q + l % 32], zeros beyond k and cout (tests / diagnostics)."""
+    ws = np.ascontiguousarray(ws, np.float32)
+    wd = np.ascontiguousarray(wd, np.float32)
+    cout, k3 = ws.shape[0], int(np.prod(ws.shape[1:]))
+    if wd.ndim != 4 or wd.shape[1:] != (cout, 3, 3):
+        raise ValueError("wd must be [k5, %d, 3, 3], got %s" % (cout, wd.shape))
+    k5 = wd.shape[0]
+    n = _lib.dc_sparse_head_pack_size(cout, k3, k5)
+    if n < 0:
+        raise ValueError("bad sizes cout=%d k3=%d k5=%d" % (cout, k3, k5))
+    out = np.empty(n, np.float32)
+    _check(_lib.dc_sparse_head_pack(ws.ctypes.data_as(C.c_void_p), wd.ctypes.data_as(C.c_void_p), cout, k3, k5, out.ctypes.data_as(C.c_void_p)))
+    nq, n5, n3 = (cout + 31) // 32, (k5 + 7) // 8, (k3 + 7) // 8
+    cut = 9 * nq * n5 * 256
+    return out[:cut].reshape(9, nq, n5, 64, 4), out[cut:].reshape(nq, n3, 64, 4)
 
 
 def stem7x7_pack(g):
@@ -727,6 +751,8 @@ class Net(object):
         self._params = None
         if kw.get("want") is not None:
             self.set_outputs(kw["want"])
+        if kw.get("sparse_pairwise"):
+            self.sparse_pairwise = True
 
     def set_option(self, key, value):
         _check(_lib.dc_net_set_option(self._h, int(key), int(value)))
@@ -757,6 +783,17 @@ class Net(object):
     def wanted_outputs(self):
         mask = self.get_option(4)
         return [n for i, n in enumerate(self.outputs) if mask == -1 or (mask >> i) & 1]
+
+    @property
+    def sparse_pairwise(self):
+        """DC_OPT_SPARSE_PAIRWISE: a net whose outputs leave `next_pred` out evaluates the pairwise head at the cells `assemble_people`,
+        `decode_pairwise` and `pairwise_at` read (include/deepcut_hip.h, dc_net_pairwise_at) instead of refusing.  Off by default; a
+        net that computes `next_pred` reads the dense map either way.  Setting it on a net without such a head raises (DC_EUNSUP)."""
+        return bool(self.get_option(5))
+
+    @sparse_pairwise.setter
+    def sparse_pairwise(self, on):
+        self.set_option(5, 1 if on else 0)
 
     @property
     def dtype(self):
@@ -1139,6 +1176,15 @@ class Net(object):
                                            None if s is None else s.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def pairwise_at(self, detections):
+        """detections: int [D, 3] (image, cell row, cell column) -> float32 [D, C]: the raw `next_pred` values of the last forward at those
+        cells (dc_net_pairwise_at): from the dense map when the plan computes it, else — `sparse_pairwise` set — the pairwise head
+        evaluated at those cells alone.  A cell outside the map raises before any device work."""
+        det = np.ascontiguousarray(detections, np.int32).reshape(-1, 3)
+        out = np.zeros((det.shape[0], self.blobs["next_pred"].shape[1]), np.float32)
+        _check(_lib.dc_net_pairwise_at(self._h, det.shape[0], det.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def assemble_people(self, scale=1.0, threshold=0.1, radius=1, max_det=16, edges=None, mean=None, std=None, max_cost=32.0,
                         seed_threshold=0.5, max_people=32, min_joints=1, joint_order=None, return_cost=False):
         """The people of every image of the last forward (dc_net_assemble_people): part candidates, pair costs from `next_pred` and a
@@ -1188,7 +1234,7 @@ class Net(object):
         return bool(b.value)
 
     STAT_NAMES = ("lowerings", "graph_instantiations", "plan_hits", "autotune_runs", "buffer_growths", "repacks",
-                  "cached_plans")
+                  "cached_plans", "sparse_packs")
 
     def stats(self):
         """Counters of the per-shape plan cache (dc_net_stats): dict name -> int."""

@@ -26,6 +26,19 @@ def _get_model(model_def, model_bin):
     return _MODEL[key]
 
 
+_SPARSE_MODEL = {}
+
+
+def _get_sparse_model(model_def, model_bin):
+    # the sparse entry's own cache: a net narrowed to `prob` and `loc_pred` with the pairwise head evaluated at the candidates' cells
+    import caffe as _caffe
+
+    key = (model_def, model_bin)
+    if key not in _SPARSE_MODEL:
+        _SPARSE_MODEL[key] = _caffe.Net(model_def, model_bin, _caffe.TEST, want=["loc_pred", "prob"], sparse_pairwise=True)
+    return _SPARSE_MODEL[key]
+
+
 def _base_scale(scales):
     """The member a pyramid is fused on when the caller names none: the scale nearest 1.0, the first of equals."""
     return min(range(len(scales)), key=lambda i: (abs(float(scales[i]) - 1.0), i))
@@ -45,7 +58,7 @@ def _check_joint_mirror(joint_mirror):
 
 
 def estimate_people(image, model_def, model_bin, stats, scale=1.0, net=None, scales=None, base=None, flip=False, joint_mirror=MIRROR_MPII14,
-                    **assembly):
+                    sparse=False, **assembly):
     """image: HxWx3 BGR uint8, or a `caffe.Frame` (NV12 / pitched BGR planes, converted by the device pre-processing).  stats: the path of the model's pair-statistics file (deepcut_tools.read_pair_stats) or the
     (edges, mean, std) triple itself.  Runs the image entry (`Net.forward_images`: pre-processing on the device) with all three
     outputs computed, then `Net.assemble_people(scale=scale, edges=..., mean=..., std=..., **assembly)`; `assembly` takes its other
@@ -56,7 +69,12 @@ def estimate_people(image, model_def, model_bin, stats, scale=1.0, net=None, sca
     scales: a list of scales runs the image pyramid instead — the net and clones of it kept with it, as `estimate_pose` uses them, in
     ONE grouped forward (`NetGroup.forward_images`), then `NetGroup.assemble_people`: the maps of all scales are fused on the grid of
     member `base` (None = the scale nearest 1.0, the first of equals) on the device and assembled there at scales[base].  `scale`
-    must then be left at 1.0.  The clones are the ones `estimate_pose` keeps with the net for its own pyramids; they are set to compute
+    must then be left at 1.0.
+    sparse: True runs on a cached net of its own that computes `prob` and `loc_pred` only and evaluates the 364-channel pairwise head at
+    the part candidates' cells (`Net.sparse_pairwise`; the rule: include/deepcut_hip.h, dc_net_pairwise_at) instead of over the whole map.
+    A caller's `net` is used as given and never changed: it must either compute `next_pred` or have `sparse_pairwise` set.  Pyramids and
+    mirrored members are out of scope for the sparse head: sparse=True with scales= or flip=True raises ValueError.
+    The clones are the ones `estimate_pose` keeps with the net for its own pyramids; they are set to compute
     all three outputs here (after the net itself has been accepted: a net that leaves `next_pred` out is refused before anything is
     touched), and `estimate_pose` on its own cached net narrows its clones again — alternating the two entries on ONE net re-lowers the
     clones' plans at every switch, so give each entry a net of its own where both are in use.
@@ -67,6 +85,9 @@ def estimate_people(image, model_def, model_bin, stats, scale=1.0, net=None, sca
     (a, c), the edge (joint_mirror[a], joint_mirror[c]).  The base stays a plain member: None = the plain scale nearest 1.0."""
     if scales is not None and float(scale) != 1.0:
         raise ValueError("estimate_people takes scale (one forward) or scales (a pyramid), not both: scale=%r, scales=%r" % (scale, scales))
+    if sparse and (scales is not None or flip):
+        raise ValueError("estimate_people: sparse=True evaluates the pairwise head of ONE forward at its candidates' cells; the fused path of "
+                         "scales= / flip=True needs every member's dense next_pred")
     if flip:
         joint_mirror = _check_joint_mirror(joint_mirror)
         plain = len(scales) if scales is not None else 1
@@ -78,8 +99,9 @@ def estimate_people(image, model_def, model_bin, stats, scale=1.0, net=None, sca
         stats = read_pair_stats(stats)
     edges, mean, std = stats
     if net is None:
-        net = _get_model(model_def, model_bin)
-    missing = [k for k in ("prob", "loc_pred", "next_pred") if k not in net.wanted_outputs]
+        net = _get_sparse_model(model_def, model_bin) if sparse else _get_model(model_def, model_bin)
+    need = ("prob", "loc_pred") if getattr(net, "sparse_pairwise", False) else ("prob", "loc_pred", "next_pred")
+    missing = [k for k in need if k not in net.wanted_outputs]
     if missing:
         raise ValueError("estimate_people needs all three maps, the net leaves out %r (net.set_outputs(None) brings them back)" % (missing,))
     from .estimate_pose import _is_frame

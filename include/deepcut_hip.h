@@ -64,6 +64,12 @@ extern "C" {
                                maps equal the full forward's up to the summation order of the tile chosen for the narrower head GEMM
                                (bit for bit under the same tile, tests/test_gpu_outputs.py) */
 
+#define DC_OPT_SPARSE_PAIRWISE 5 /* 0 (default): nothing changes anywhere.  1: on a net whose DC_OPT_OUTPUTS leaves `next_pred` out,
+                               dc_net_assemble_people, dc_net_decode_pairwise and dc_net_pairwise_at evaluate the pairwise head at the
+                               cells they read instead of answering DC_EUNSUP (the rule: dc_net_pairwise_at); a net whose plan computes
+                               `next_pred` reads the dense map, same bits as with 0.  Inherited by clones.  Setting 1 on a net without
+                               a recognisable pairwise head is DC_EUNSUP naming the layer.  dc_group_* entries do not look at it. */
+
 typedef struct dc_net dc_net;
 typedef struct dc_blob dc_blob;
 
@@ -371,7 +377,8 @@ int dc_net_decode_pairwise(dc_net* net, double scale, int ndet, const int* detec
  * Errors : DC_EINVAL naming the parameter for scale <= 0, threshold < 0, radius outside [0, 64], max_det outside [1, 64], max_cost
  *          negative or not finite, max_people outside [1, 256], min_joints outside [1, J]; DC_EINVAL before any device work for a joint
  *          index outside [0, J), an edge with a == b, a joint_order that is not a permutation; DC_EUNSUP when `next_pred` is left out by
- *          DC_OPT_OUTPUTS; DC_ESHAPE for a wrong n_edges or more than 32 joints.                                                      */
+ *          DC_OPT_OUTPUTS (unless DC_OPT_SPARSE_PAIRWISE is 1: stage B then reads the head evaluated at stage A's cells, see
+ *          dc_net_pairwise_at); DC_ESHAPE for a wrong n_edges or more than 32 joints.                                                 */
 typedef struct dc_assemble_params {
   double scale;          /* as dc_net_detect_parts */
   float  threshold;      /* candidate score threshold */
@@ -384,6 +391,49 @@ typedef struct dc_assemble_params {
 int dc_pair_stats_read(const char* path, int max_edges, int* n_edges, int* edges, double* mean, double* stdev);
 int dc_net_assemble_people(dc_net* net, const dc_assemble_params* p, int n_edges, const int* edges, const double* mean, const double* stdev,
                            const int* joint_order, int* n_people, double* people, int* cand, double* cost);
+
+/* ---- the pairwise head at candidate cells only (DC_OPT_SPARSE_PAIRWISE) -------------------------------------------------------
+ * Bottom-up people is the only consumer of `next_pred` and reads it at the part candidates' cells only: at most J x max_det cells
+ * per image of the 68 x 92 of a 544x736 forward, while the dense 364-channel head is 23.3 of that forward's 241 GFLOP.  With
+ * DC_OPT_SPARSE_PAIRWISE 1 a net whose output selection leaves `next_pred` out (DC_OPT_OUTPUTS) evaluates the head at those cells:
+ * dc_net_assemble_people between its stages A and B (no host round trip: the candidates stay on the device), dc_net_decode_pairwise
+ * and dc_net_pairwise_at at the cells they are given.  Everything downstream runs unchanged on a float32 scratch map.
+ *
+ * The pairwise head is recognised from the layer list (it does not depend on the lowering): `next_pred` must be the top of an Eltwise
+ * SUM whose bottoms are
+ *   - a Convolution 1x1, stride 1, pad 0, group 1 (filters Ws[n][k], input X3), and
+ *   - the fork's Crop (offsets oh, ow) of a Deconvolution with kernel 3, stride 2, pad 0, dilation 1, group 1 (filters
+ *     Wd[k][n][ky][kx], input X5 of h5 x w5 cells),
+ * each with or without a bias.  Anything else is DC_EUNSUP naming the layer.  For image b, channel n and cell (r, c):
+ *
+ *   next[b,n,r,c] = bias_s[n] + bias_d[n]
+ *                 + sum_k Ws[n,k] * X3[b,k,r,c]
+ *                 + sum over ky, kx in {0,1,2} with (r+oh-ky) even, (c+ow-kx) even, 0 <= (r+oh-ky)/2 < h5, 0 <= (c+ow-kx)/2 < w5 of
+ *                       sum_k Wd[k,n,ky,kx] * X5[b,k,(r+oh-ky)/2,(c+ow-kx)/2]
+ *
+ * A cell uses 1, 2, 2 or 4 of the nine taps, by the parity of (r+oh, c+ow); row 0 and column 0 lose the ky = 2 / kx = 2 taps.
+ * Operands are what the dense head sees: activations in the net's element type, filters rounded to it on float16 / bfloat16 nets, the
+ * bias in float32.  Products are accumulated in float32 on v_mfma_f32_32x32x2_f32 and the result is float32 for every net type: it is
+ * NOT rounded to 16 bits as the dense map of a 16-bit net is.  Deterministic, no float atomics: the value at a cell depends on that cell
+ * only — not on its place in the list, the other cells, or which entry asked; a cell listed twice is computed twice.
+ * X3 and X5 must be materialised in the current plan (they are in every plan that computes `loc_pred`), else DC_EUNSUP; a host-
+ * authoritative one is uploaded first, as an output map is.  The filters are packed once per model and element type, shared with
+ * clones and dropped when the parameters change, like every other filter image (DC_STAT_SPARSE_PACKS counts the packs a net made).
+ * OUT OF SCOPE: dc_group_* (pyramids, mirrored members).  The fused bottom-up path needs every member's head at the four neighbours of
+ * each base cell; dc_group_assemble_people on members without `next_pred` keeps answering DC_EUNSUP whatever this option says.
+ *
+ * dc_net_pairwise_at: the raw `next_pred` values of the last forward at ndet cells, detections = (image, cell row, cell column)
+ * triples, out[d*C + n] float32: read from the dense map when the plan has it (widened from a 16-bit net's map), by the rule above
+ * otherwise.  Host buffers; synchronous.  DC_EINVAL before any device work for a cell outside the map; DC_EUNSUP for a net whose plan
+ * has no `next_pred` while the option is 0.
+ * dc_sparse_head_pack (tests / diagnostics; host only): the head's filter image as the library packs it for float32 nets, from
+ * ws [cout][k3] and wd [k5][cout][3][3]: float32 [segment 0..9][ceil(cout/32)][K block of 8][64 lanes][4], segment t < 9 the tap
+ * ky*3 + kx = t over k5 channels, segment 9 the skip over k3; lane l of K block j of chunk q holds W[k = 8j + 4(l/32) + m][n = 32q + l%32],
+ * m = 0..3, zeros beyond k and cout.  Segments 0..8 take ceil(cout/32) * ceil(k5/8) * 256 floats each, segment 9
+ * ceil(cout/32) * ceil(k3/8) * 256; dc_sparse_head_pack_size is their sum (-1 on bad arguments).                                   */
+int dc_net_pairwise_at(dc_net* net, int ndet, const int* detections /* image,row,col */, float* out /* [ndet][C] */);
+int dc_sparse_head_pack_size(int cout, int k3, int k5);
+int dc_sparse_head_pack(const float* ws, const float* wd, int cout, int k3, int k5, float* out);
 
 
 /* ---- introspection used by bench.py / DESIGN.md ----------------------------------------- */
@@ -401,7 +451,8 @@ int dc_net_num_launches(dc_net* net);
 #define DC_STAT_BUFFER_GROWTHS 4   /* device buffers (re)allocated                                        */
 #define DC_STAT_REPACKS 5          /* times the filter images were re-packed from the parameter blobs     */
 #define DC_STAT_CACHED_PLANS 6     /* shapes currently cached (LRU of DC_PLAN_CACHE, default 16)          */
-#define DC_NUM_STATS 7
+#define DC_STAT_SPARSE_PACKS 7     /* times this net packed the pairwise head's filter image (DC_OPT_SPARSE_PAIRWISE) */
+#define DC_NUM_STATS 8
 int dc_net_stats(dc_net* net, long long* out, int n);
 /* lower, allocate and tune the plan of an [n,3,h,w] input without running it: reserving the LARGEST shape of a
  * pyramid first means no buffer grows (and no captured graph goes stale) while the smaller ones are met        */
