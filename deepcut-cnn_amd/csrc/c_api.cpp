@@ -705,6 +705,12 @@ int dc_stream1x1f_pack(const float* g, int cout, int k, float* out) {
   return guard([&] { dc::stream1x1f_pack_filters(g, cout, k, out); });
 }
 
+int dc_wino43_pack(const float* g, int cout, int cin, float* out) {
+  if (!g || !out) return fail(DC_EINVAL, "dc_wino43_pack: null pointer");
+  if (cout <= 0 || cin <= 0 || cout % 16 || cin % 16) return fail(DC_EINVAL, "dc_wino43_pack: cout and cin must be multiples of 16");
+  return guard([&] { dc::wino43_pack_filters(g, cout, cin, out); });
+}
+
 int dc_stem7x7_pack(const float* g, int c, float* out) {
   if (!g || !out) return fail(DC_EINVAL, "dc_stem7x7_pack: null pointer");
   if (c < 1 || c > 4) return fail(DC_EINVAL, "dc_stem7x7_pack: 1 to 4 input channels");

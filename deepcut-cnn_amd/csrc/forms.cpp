@@ -15,7 +15,7 @@ static const char* const kWinoSlots[7] = {"index setup", "first loads issued", "
 static const char* const kStreamSlots[7] = {"prologue requests issued", "first stage + filters landed", "the first D steps", "the other steps",
                                             "drain", "-", "exit"};
 static constexpr ConvForm kForms[kNumForms] = {
-    // variant, name, label, ekind, geometry, waves, slots, eligible, grid, launch, own_scale, merges, prepare_multi, launch_multi, sibling, env, offered, env_default
+    // variant, name, label, ekind, geometry, waves, slots, eligible, grid, launch, own_scale, merges, prepare_multi, launch_multi, sibling, env, offered, env_default, load_only
     {kWinoVariant, "wino_f23", "wino_f23<4x8x16>", kElemF32, kForm3x3, 8, kWinoSlots, wino_eligible, wino_grid, launch_wino_f23,
      false, false, nullptr, nullptr, kWinoVariant16, "DC_WINOGRAD"},
     {kWinoVariant16, "wino_f23_w16", "wino_f23<4x8x16_w16>", kElemF32, kForm3x3, 16, kWinoSlots, wino_eligible, wino_grid, launch_wino_f23_w16,
@@ -43,6 +43,9 @@ static constexpr ConvForm kForms[kNumForms] = {
      false, false, nullptr, nullptr, kWinoVariantMix16, "DC_WINOGRAD", wino_mix_fewer_blocks},
     {kWinoVariantMix16, "wino_f23_mix_w16", "wino_f23<4x8+5x6x16_w16>", kElemF32, kForm3x3, 16, kWinoSlots, wino_eligible, wino_grid_mix, launch_wino_f23_mix_w16,
      false, false, nullptr, nullptr, kWinoVariantMix, "DC_WINOGRAD", wino_mix_fewer_blocks},
+    // three launches (wino43_f32.hip): the label names the multiply, whose batched instantiation does the matrix work (launch counts read "ws1x1f<")
+    {kWinoF43, "wino_f43", "wino_f43+ws1x1f<16xN>", kElemF32, kForm3x3, 4, kStreamSlots, wino43_eligible, wino43_grid, launch_wino_f43,
+     false, false, nullptr, nullptr, -1, "DC_WINOGRAD43", wino43_offered, -1, true},
 };
 
 static constexpr bool forms_in_variant_order() {

@@ -134,14 +134,17 @@ struct ConvGemmParams {
   int w_mix_pad_;
   int w_mix_na, w_mix_nab, w_mix_ty0, w_mix_tx0, w_mix_NBX;
   unsigned w_mix_div_nbx[2];
-  int w_mix_reserved_[8];
+  int w_mix_reserved0_;
+  void* form_ws;  // the executor's V / M workspace of the wino_f43 form (Net::wino43_dev_: 36 R (Cin + Cout) floats); null for every other form
+  int w_mix_reserved_[6];
   ConvClass cls[kMaxClasses];
   // --- multi-problem launches: nprob > 0 and the ConvMultiTable that follows the block in the kernel arguments
   //     (ConvMultiArgs) replace every per-tensor field above
   int nprob;
   int ekind;  // ElemKind of x / w / y / resid (esize alone does not tell float16 from bfloat16)
 };
-static_assert(offsetof(ConvGemmParams, w_mix_na) % 64 == 0 && offsetof(ConvGemmParams, w_mix_div_nbx) + 8 <= offsetof(ConvGemmParams, w_mix_na) + 64 &&
+static_assert(offsetof(ConvGemmParams, form_ws) == offsetof(ConvGemmParams, w_mix_na) + 32 &&
+                  offsetof(ConvGemmParams, w_mix_na) % 64 == 0 && offsetof(ConvGemmParams, w_mix_div_nbx) + 8 <= offsetof(ConvGemmParams, w_mix_na) + 64 &&
                   offsetof(ConvGemmParams, cls) == offsetof(ConvGemmParams, w_mix_na) + 64,
               "the w_mix_* fields are one 64-byte line of the argument block, the multi-class table starts on the next");
 // kernel arguments of a multi-problem launch: the table travels IN the argument block (3.6 KB of the 4 KB a HIP kernel may
@@ -245,6 +248,26 @@ long stream1x1f_grid(const ConvGemmParams& p);
 size_t stream1x1f_packed_elems(int Cout, int K);
 void stream1x1f_pack_filters(const float* g, int Cout, int K, float* out);
 int launch_stream1x1f(const ConvGemmParams& p, void* stream);
+// ---- Winograd F(4x4, 3x3), float32, unfused ("wino_f43", wino43_f32.hip + the batched instantiation of the kernel above): the input transformed
+// once per layer into V[36][R][Cin] (R = NB d d TY TX tiles of 4 x 4 output pixels on the dilation-phase grid), the 36 points multiplied as
+// plain [R][Cin] x [Cin][Cout] products by ws1x1f_kernel<.., BATCH> into M[36][R][Cout], the inverse transform with the folded affine and
+// ReLU.  V and M live in p.form_ws (wino43_workspace_bytes); `w` is the image made by wino43_pack_filters().  No shortcut operand.
+bool wino43_eligible(const ConvGemmParams& p);
+bool wino43_offered(const ConvGemmParams& p);   // where the per-shape timing tries it: kWino43MinTiles tiles or more
+long wino43_tiles(const ConvGemmParams& p);     // R
+long wino43_grid(const ConvGemmParams& p);      // workgroups of the multiply
+size_t wino43_workspace_bytes(const ConvGemmParams& p);
+size_t wino43_packed_floats(int Cout, int Cin);
+// g: [Cout][Cin][3][3] -> U = G g G^T per (co, ci) in double, rounded once; point p = 6 i + j is the [Cout][Cin] matrix at out + p Cout Cin,
+// in stream1x1f_pack_filters' order
+void wino43_pack_filters(const float* g, int Cout, int Cin, float* out);
+int launch_wino_f43(const ConvGemmParams& p, void* stream);
+// the two transform kernels of wino43_f32.hip (R tiles; V / M as above)
+int launch_wino43_input(const ConvGemmParams& p, float* V, long R, int TY, int TX, void* stream);
+int launch_wino43_output(const ConvGemmParams& p, const float* M, long R, int TY, int TX, void* stream);
+// the 36 products (stream1x1_f32.hip): M[p] = V[p] U[p], p = 0..35
+long stream1x1f_batched_grid(long R, int Cin, int Cout);
+int launch_stream1x1f_batched(const float* V, const float* U, float* M, long R, int Cin, int Cout, void* stream);
 // ---- the float32 stem on the same skeleton ("ws7x7f"): conv1 7x7 / 2 over the NHWC4 image as the lowering's 7-row-tap launch describes it; a
 // 1 KiB request gathers an output pixel's 7 x 8 input pixels (K = 224, the row-tap image's columns); `w` from stem_ws_pack_filters()
 bool stem_ws_eligible(const ConvGemmParams& p);
@@ -287,7 +310,8 @@ constexpr int kStreamBf16 = 1009;        // "bs1x1": the streaming form of the d
 constexpr int kStemBf16 = 1010;          // "bs7x7": the 7x7 / stride-2 stem of a bfloat16 net (stem_f16.hip)
 constexpr int kWinoVariantMix = 1011;     // "wino_f23_mix": wino_f23 on a cover of 4 x 8- and 5 x 6-tile blocks in one launch (wino_plan_cover)
 constexpr int kWinoVariantMix16 = 1012;   // "wino_f23_mix_w16": its 16-wave form
-constexpr int kFormVariant0 = kWinoVariant, kNumForms = 13;
+constexpr int kWinoF43 = 1013;            // "wino_f43": Winograd F(4x4, 3x3), float32, unfused: transform, 36 batched ws1x1f products, inverse (wino43_f32.hip)
+constexpr int kFormVariant0 = kWinoVariant, kNumForms = 14;
 enum FormGeometry { kForm3x3, kForm1x1, kFormStem };  // the layers a form takes: 3x3, dense 1x1, the 7-row-tap stem
 struct ConvForm {
   int variant;
@@ -307,6 +331,10 @@ struct ConvForm {
   // null: a candidate of the per-shape timing wherever eligible; else only where this says so (set_tile and tune caches take it wherever eligible)
   bool (*offered)(const ConvGemmParams& p) = nullptr;
   int env_default = -1;  // what the switch means while unset (0: the form is opt-in)
+  // a throughput form: Net::autotune times it alone like any other (the figure is in the tune report, where deepcut_tools.tune_in_flight finds
+  // it) but does not choose it — the latency plan of one forward keeps its tile; the form enters a plan by tune_in_flight, set_tile, a tune
+  // cache or its switch at >= 1
+  bool load_only = false;
 };
 const ConvForm* conv_form(int variant);  // null: not a form (a tile)
 

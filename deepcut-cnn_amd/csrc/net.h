@@ -195,11 +195,12 @@ struct Launch {
   std::shared_ptr<DevVec> w, scale, shift;  // packed filters / folded affine (kept alive by the plan)
   std::shared_ptr<DevVec> form_w;           // the filter image of the forms this launch can run on (kernels.h ConvForm): Winograd-transformed
                                             // filters of a 3x3 layer, the image of a streaming 1x1 layer or of the stem; else null
+  std::shared_ptr<DevVec> form_w43;         // the filter image of wino_f43 (36 points, wino43_pack_filters), beside form_w on a 3x3 layer that takes both
   std::shared_ptr<DevVec> form_scale;       // the epilogue scale of a form with its own (ConvForm::own_scale: folded affine x the image's row scale x 4)
   // a form this launch can run on: the image exists, and the form serves the net's element type and takes the layer
   bool takes_form(int v) const {
     const ConvForm* f = conv_form(v);
-    return f && form_w && f->ekind == cg.ekind && cg.ncls <= 1 && (f->geometry == kForm1x1) == (cg.nty == 1 && cg.ntx == 1) &&
+    return f && form_w && (v != kWinoF43 || form_w43) && f->ekind == cg.ekind && cg.ncls <= 1 && (f->geometry == kForm1x1) == (cg.nty == 1 && cg.ntx == 1) &&
            (f->geometry == kFormStem) == (cg.nty == 7 && cg.ntx == 1) && f->eligible(cg);
   }
   // a tile (or form) this launch can run on: the net's element kind, the launch's K segments and deconvolution classes
@@ -386,6 +387,7 @@ struct Net {
   void reshape_layer(LayerRec& L);
   void ensure_device();
   void upload_vecs();
+  friend void prepare_wino43(Net& n, bool& grew);
   void run_launch(const Launch& l, void* s);
   void run_plan(int start, int end, void* s);
   const Net* clone_src_ = nullptr;  // during create() of a clone only
@@ -435,6 +437,10 @@ struct Net {
   std::shared_ptr<DevVec> sparse_w_, sparse_b_;  // the head's filter image and bias (kept alive here as a plan keeps its launches')
   unsigned char* sparse_dev_ = nullptr;
   size_t sparse_cap_ = 0;
+  // V and M of the wino_f43 launches (kernels.h wino43_workspace_bytes): sized for the largest such launch of the plan when the buffers of a
+  // plan are prepared, before any forward or capture; grown (buf_gen_ bumped) but never shrunk or freed while the net lives; a clone has its own
+  unsigned char* wino43_dev_ = nullptr;
+  size_t wino43_cap_ = 0;
   unsigned char* scratch_dev_ = nullptr;  // candidates / detections / pairwise scratch
   size_t scratch_cap_ = 0;
   void* scratch(size_t bytes);

@@ -101,6 +101,7 @@ Net::~Net() {
   else if (stream) (void)hipStreamDestroy((hipStream_t)stream);
   dev_free(pose_dev);
   dev_free(scratch_dev_);
+  dev_free(wino43_dev_);
   dev_free(img_dev_);
   dev_free(tmp_dev_);
   dev_free(frame_dev_);

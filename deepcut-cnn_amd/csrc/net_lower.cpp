@@ -686,6 +686,15 @@ void Net::build_plan() {
           wino_pack_filters(L.params[0]->st->host_ptr(), c.num_output, C, h.data());
         });
         offer_form(l, wino_mode == 2 ? kWinoVariant16 : kWinoVariant);
+        // ... and as the unfused F(4x4,3x3) (wino43_f32.hip): a filter image of its own beside that one (DC_WINOGRAD43: 0 never; -1, the default:
+        // timed alone, taken under load by tune_in_flight / set_tile / a tune cache, never by the latency plan; 1 wherever eligible)
+        if (form_mode(*conv_form(kWinoF43)) != 0 && op.in2 < 0 && wino43_eligible(g)) {
+          l.form_w43 = get_vec(dkey + "wino43:" + std::to_string(op.wl), [&](std::vector<float>& h) {
+            h.assign(wino43_packed_floats(c.num_output, C), 0.f);
+            wino43_pack_filters(L.params[0]->st->host_ptr(), c.num_output, C, h.data());
+          });
+          offer_form(l, kWinoF43);
+        }
       } else if (!rowtap && wino_mode != 0 && op.wls.empty() && dtype == kElemF16 && op.in2 < 0 && wino_half_eligible(g)) {
         // float16 (wino_f16.hip): the image is packed in MFMA fragment order with its own per-channel power-of-two row scale
         // (DevVec::row_scale: G g G^T has other maxima than g); the form's epilogue scale = folded affine x row scale x 4 (the

@@ -22,7 +22,7 @@ void Net::upload_vecs() {
   std::lock_guard<std::mutex> lk(shared->mu);  // an image may be shared with a clone that uploads at the same moment
   std::vector<DevVec*> todo;
   for (auto& l : plan)
-    for (const std::shared_ptr<DevVec>* vp : {&l.w, &l.scale, &l.shift, &l.form_w, &l.form_scale})
+    for (const std::shared_ptr<DevVec>* vp : {&l.w, &l.scale, &l.shift, &l.form_w, &l.form_w43, &l.form_scale})
       if (*vp && !(*vp)->dev && !(*vp)->host.empty()) todo.push_back(vp->get());
   for (DevVec* vq : todo) {
     DevVec& v = *vq;
@@ -101,6 +101,11 @@ void Net::run_launch(const Launch& l, void* s) {
       if (form) {
         if (!l.form_w) throw DcError(DC_EINVAL, "launch '" + l.label + "' has no filter image of form " + form->name);
         g.w = l.form_w->dev;
+        if (l.variant == kWinoF43) {  // its own image, and this executor's V / M (prepare_buffers sized it for every launch that carries the image)
+          if (!l.form_w43 || l.in2 >= 0 || wino43_cap_ < wino43_workspace_bytes(g)) throw DcError(DC_EINVAL, "launch '" + l.label + "' cannot run as form " + form->name);
+          g.w = l.form_w43->dev;
+          g.form_ws = wino43_dev_;
+        }
         if (form->own_scale) {  // (wino_h23: the row scale of ITS image, the 1/4 of the staged pixels)
           if (!l.form_scale || l.in2 >= 0) throw DcError(DC_EINVAL, "launch '" + l.label + "' cannot run as form " + form->name);
           g.scale = l.form_scale->dev + l.c_off;
@@ -192,6 +197,22 @@ void Net::run_plan(int start, int end, void* s) {
   }
 }
 
+// the wino_f43 workspace: room for the largest launch of the plan that carries the form's image, whichever tile it runs on now (set_tile and the
+// timing passes switch a launch to the form without another allocation).  Called only between forwards: a captured graph that addressed the old
+// buffer is stale by buf_gen_
+void prepare_wino43(Net& n, bool& grew) {
+  size_t need = 0;
+  for (auto& l : n.plan)
+    if (l.kind == Launch::CONV && l.form_w43) need = std::max(need, wino43_workspace_bytes(l.cg));
+  if (need <= n.wino43_cap_) return;
+  dev_free(n.wino43_dev_);
+  n.wino43_dev_ = nullptr, n.wino43_cap_ = 0;
+  dev_alloc((void**)&n.wino43_dev_, need);
+  n.wino43_cap_ = need;
+  ++n.buf_gen_;
+  grew = true;
+}
+
 static void prepare_buffers(Net& n, bool& grew) {
   grew = false;
   auto prep = [&](int sidx) {
@@ -207,6 +228,7 @@ static void prepare_buffers(Net& n, bool& grew) {
     prep(l.out);
     if (l.in2 >= 0) prep(l.in2);
   }
+  prepare_wino43(n, grew);
 }
 
 // Everything a launch sequence of the CURRENT input shape needs, without running it and without touching the inputs: the plan of

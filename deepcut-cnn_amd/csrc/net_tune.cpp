@@ -108,8 +108,9 @@ void Net::autotune() {
       c.push_back({burst_ms(trial), v});
     }
     std::sort(c.begin(), c.end());
+    shared->tune_timings[key] = c;  // every timing, the throughput forms' too (ConvForm::load_only): the choice below is among the others
+    c.erase(std::remove_if(c.begin(), c.end(), [](const std::pair<float, int>& t) { return conv_form(t.second) && conv_form(t.second)->load_only; }), c.end());
     tune_cache_[key] = c.empty() ? l.variant : c.front().second;
-    shared->tune_timings[key] = c;
   }
   // (2) in situ: a launch timed alone re-reads warm filters and starts on an idle chip; inside a forward it follows another
   // kernel's tail and finds its filters wherever the 263 MB sweep of the forward left them.  The candidates within 12 % of a

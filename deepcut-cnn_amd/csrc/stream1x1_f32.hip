@@ -53,6 +53,12 @@ struct WsfArgs {
   // the stem form ("ws7x7f"): output map and image geometry (a 1 KiB request gathers an output pixel's 7 rows x 8 pixels of 4 channels)
   int OW, OHW, H, W, xrsb, ximgb;  // output width, output pixels per image, image rows / pixels per row, bytes between image rows / images
   unsigned div_ow[2], div_ohw[2];
+  // the batched form (BATCH: the 36 points of wino_f43, one matrix product each): slice s = point * tn + nt, workgroup g = s * J + range; XCD q
+  // runs workgroups [q bper, (q + 1) bper) of the btotal, so every XCD gets the same count (to within one) and the workgroups that share a
+  // point's rows and a slice's filters are neighbours on one XCD; x / w / y of point p start bxs / bws / bys bytes x p behind the bases
+  int bper, btotal;
+  unsigned div_j[2];
+  unsigned bxs, bws, bys;
 };
 
 // Counted waits.  The vector-memory requests of a wave, in issue order (vmcnt counts them all, stores included):
@@ -83,8 +89,9 @@ struct ReqCount {
 // inside a block row r keeps its 16-byte chunks rotated by r runs (chunk c of row r at position (c + r K/16) mod (K/4): the request's lane l
 // simply fetches the chunk that belongs at position l), which puts the 16 lanes of a read — 16 rows, one chunk index — into 16 different
 // bank groups again and leaves the read offsets immediates (a lane's run starts at ((q + r) mod 4) K bytes of its row instead of q K).
-template <int K, int D, bool RES, bool RELU, bool STEM = false>
+template <int K, int D, bool RES, bool RELU, bool STEM = false, bool BATCH = false>
 __global__ __launch_bounds__(256, 1) void ws1x1f_kernel(const WsfArgs a) {
+  static_assert(!BATCH || (!STEM && !RES && !RELU), "the batched form: plain products");
   static_assert(!STEM || (K == 224 && !RES), "the stem form: 7 taps x 32 image floats per output pixel (the request's eighth tap is never read), no shortcut");
   const long long t_entry = (long long)__builtin_amdgcn_s_memrealtime();
   constexpr int RPR = K * 4 >= 1024 ? 1 : 1024 / (K * 4);  // pixel rows per 1 KiB request
@@ -103,10 +110,20 @@ __global__ __launch_bounds__(256, 1) void ws1x1f_kernel(const WsfArgs a) {
   const int p16 = lane & 15, q = lane >> 4;
 
   const int bx = blockIdx.x, xcd = bx & 7, bi = bx >> 3;
-  const int ci = dc_fastdiv(bi, a.div_tn);
-  const int nt = bi - ci * a.tn;
-  const int jc = xcd + 8 * ci;
-  if (jc >= a.J) return;
+  int nt, jc, pt = 0;
+  if (BATCH) {
+    const int g = xcd * a.bper + bi;
+    if (g >= a.btotal) return;
+    const int sl = dc_fastdiv(g, a.div_j);
+    jc = g - sl * a.J;
+    pt = dc_fastdiv(sl, a.div_tn);
+    nt = sl - pt * a.tn;
+  } else {
+    const int ci = dc_fastdiv(bi, a.div_tn);
+    nt = bi - ci * a.tn;
+    jc = xcd + 8 * ci;
+    if (jc >= a.J) return;
+  }
   int gs0 = jc * a.sbase + min(jc, a.srem), gs1 = gs0 + a.sbase + (jc < a.srem ? 1 : 0);
   if (a.srem < 0) gs0 = a.S * jc / a.J, gs1 = a.S * (jc + 1) / a.J;  // (DC_WSF_REMAP=0: the longer ranges spread over the grid, for A/B timing)
   const int nw0 = nt * 64 + wave * 16;  // first channel of this wave
@@ -120,7 +137,7 @@ __global__ __launch_bounds__(256, 1) void ws1x1f_kernel(const WsfArgs a) {
   }
   f32x4 wreg[NJ];
   {
-    const i32x4 wrs = dc_uni4(dc_rsrc_words(a.w));
+    const i32x4 wrs = dc_uni4(dc_rsrc_words(BATCH ? (const unsigned char*)a.w + (unsigned long long)(unsigned)pt * a.bws : a.w));
     const unsigned wl = (unsigned)lane * 16u;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
@@ -130,7 +147,9 @@ __global__ __launch_bounds__(256, 1) void ws1x1f_kernel(const WsfArgs a) {
   }
 
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
-  const i32x4 xr = dc_uni4(dc_rsrc_words(a.x)), rr = dc_uni4(dc_rsrc_words(RES ? a.resid : a.y)), yr = dc_uni4(dc_rsrc_words(a.y));
+  const void* const xb = BATCH ? (const unsigned char*)a.x + (unsigned long long)(unsigned)pt * a.bxs : a.x;
+  void* const yb = BATCH ? (unsigned char*)a.y + (unsigned long long)(unsigned)pt * a.bys : a.y;
+  const i32x4 xr = dc_uni4(dc_rsrc_words(xb)), rr = dc_uni4(dc_rsrc_words(RES ? a.resid : yb)), yr = dc_uni4(dc_rsrc_words(yb));
   const unsigned frag0 = (unsigned)(p16 / RPR * BLKB + p16 % RPR * K * 4 + ((q + p16 % RPR) & 3) * K);  // this lane's run of the pixel's row: + 16 j
   const unsigned obuf0 = (unsigned)(D * STG + wave * 2 * 1024);           // this wave's two 1 KiB tiles
   const unsigned ovec = (unsigned)((4 * p16 + q) * 16);                   // MFMA view: pixel p16, channels 4 q .. + 3
@@ -298,6 +317,8 @@ struct WsfForm {
   {K_, {{ws1x1f_kernel<K_, D_, false, false>, ws1x1f_kernel<K_, D_, false, true>}, {ws1x1f_kernel<K_, D_, true, false>, ws1x1f_kernel<K_, D_, true, true>}}}
 const WsfForm kFormsF[] = {DC_WSF_FORM(64, 4), DC_WSF_FORM(128, 4), DC_WSF_FORM(256, 4), DC_WSF_FORM(512, 3)};
 const WsfKernel kStemWs[2] = {ws1x1f_kernel<224, 4, false, false, true>, ws1x1f_kernel<224, 4, false, true, true>};  // [relu]
+const WsfKernel kBatchedF[4] = {ws1x1f_kernel<64, 4, false, false, false, true>, ws1x1f_kernel<128, 4, false, false, false, true>,
+                                ws1x1f_kernel<256, 4, false, false, false, true>, ws1x1f_kernel<512, 3, false, false, false, true>};  // as kFormsF
 const WsfForm* formf_of(int K) {
   for (const WsfForm& f : kFormsF)
     if (f.K == K) return &f;
@@ -320,7 +341,47 @@ long wsf_plan(WsfArgs& a, int klen, bool stem = false) {
   dc_magic((unsigned)a.tn, a.div_tn);
   return (J + 7) / 8 * 8 * a.tn;
 }
+
+// the batched form: 36 tn slices of J ranges each.  The target is DC_WSF43_SLOTS workgroups (unset: 288): a workgroup fetches its slice's whole
+// filter block (K x 64 floats) whatever its range, so few long ranges cost the fewest CU cycles where other forwards fill the idle CUs
+long wsf_plan_batched(WsfArgs& a, int points) {
+  a.tn = a.Cout / 64;
+  a.S = (a.M + 15) / 16;
+  static const int slots = getenv("DC_WSF43_SLOTS") ? std::max(8, atoi(getenv("DC_WSF43_SLOTS"))) : 288;
+  const long slices = (long)points * a.tn;
+  const long J = std::min<long>(a.S, std::max<long>(1, (slots + slices / 2) / slices));
+  a.J = (int)J;
+  a.sbase = a.S / a.J, a.srem = a.S % a.J;
+  const long total = slices * J;
+  if (total > 0x3fffffffL) return -1;
+  a.btotal = (int)total, a.bper = (int)((total + 7) / 8);
+  dc_magic((unsigned)a.tn, a.div_tn);
+  dc_magic((unsigned)a.J, a.div_j);
+  return (long)a.bper * 8;
+}
 }  // namespace
+
+long stream1x1f_batched_grid(long R, int Cin, int Cout) {
+  WsfArgs a{};
+  a.Cout = Cout, a.M = (int)R;
+  return wsf_plan_batched(a, 36);
+}
+
+int launch_stream1x1f_batched(const float* V, const float* U, float* M, long R, int Cin, int Cout, void* stream) {
+  int fi = -1;
+  for (int i = 0; i < 4; ++i)
+    if (kFormsF[i].K == Cin) fi = i;
+  if (fi < 0 || Cout % 64 != 0 || R <= 0 || R * Cin * 4 >= 0x7fffffffL || R * Cout * 4 >= 0x7fffffffL || (long)Cout * Cin * 4 >= 0x7fffffffL) return (int)hipErrorInvalidValue;
+  if (((uintptr_t)V & 15) || ((uintptr_t)U & 15) || ((uintptr_t)M & 15)) return (int)hipErrorInvalidValue;
+  WsfArgs a{};
+  a.x = V, a.w = U, a.y = M;
+  a.M = (int)R, a.Cout = Cout, a.sxb = Cin * 4, a.ypb = Cout * 4;
+  a.bxs = (unsigned)(R * Cin * 4), a.bws = (unsigned)((long)Cout * Cin * 4), a.bys = (unsigned)(R * Cout * 4);
+  const long grid = wsf_plan_batched(a, 36);
+  if (grid <= 0 || grid > 0x7fffffffL) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(kBatchedF[fi], dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
 
 bool stream1x1f_eligible(const ConvGemmParams& p) {
   if (p.esize != 4 || p.ncls > 1 || p.nprob > 0 || p.nty != 1 || p.ntx != 1 || p.dy0 != 0 || p.x0 != 0 || p.sy != 1 || p.sigmoid_ch != 0) return false;

@@ -318,6 +318,7 @@ def _load():
         "dc_stream1x1_pack": (ci, [C.c_void_p, ci, ci, C.c_void_p]),
         "dc_stem7x7_pack": (ci, [C.c_void_p, ci, C.c_void_p]),
         "dc_stream1x1f_pack": (ci, [C.c_void_p, ci, ci, C.c_void_p]),
+        "dc_wino43_pack": (ci, [C.c_void_p, ci, ci, C.c_void_p]),
         "dc_net_pairwise_at": (ci, [vp, ci, C.c_void_p, C.c_void_p]),
         "dc_sparse_head_pack_size": (ci, [ci, ci, ci]),
         "dc_sparse_head_pack": (ci, [C.c_void_p, C.c_void_p, ci, ci, ci, C.c_void_p]),
@@ -405,6 +406,16 @@ def stream1x1f_pack(g):
     cout, k = g.shape[0], int(np.prod(g.shape[1:]))
     out = np.empty((cout // 16, k // 16, 64, 4), np.float32)
     _check(_lib.dc_stream1x1f_pack(g.ctypes.data_as(C.c_void_p), cout, k, out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def wino43_pack(g):
+    """dc_wino43_pack: the filter image of the unfused Winograd F(4x4,3x3) form (csrc/wino43_f32.hip) of g [cout, cin, 3, 3] as the lowering
+    packs it: [36 points][cout/16][cin/16][64 lanes][4], point 6 i + j = (G g G^T)[i][j] in stream1x1f_pack's order (tests / diagnostics)."""
+    g = np.ascontiguousarray(g, np.float32)
+    cout, cin = g.shape[0], g.shape[1]
+    out = np.empty((36, cout // 16, cin // 16, 64, 4), np.float32)
+    _check(_lib.dc_wino43_pack(g.ctypes.data_as(C.c_void_p), cout, cin, out.ctypes.data_as(C.c_void_p)))
     return out
 
 

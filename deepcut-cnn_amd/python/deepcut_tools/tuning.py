@@ -21,6 +21,11 @@ is set (dc_net_set_tile rewrites it); the reference has nothing to mirror here (
 # forwards in flight the freed workgroup slots are another forward's.  Every timed form of this family within `margin` is therefore tried.)
 _WINO_SIBLING = {"wino_f23": "wino_f23_w16", "wino_f23_w16": "wino_f23", "wino_f23_5x6": "wino_f23_5x6_w16", "wino_f23_5x6_w16": "wino_f23_5x6",
                  "wino_f23_mix": "wino_f23_mix_w16", "wino_f23_mix_w16": "wino_f23_mix"}
+# ... and the unfused F(4x4,3x3) form (csrc/wino43_f32.hip) belongs to the family for the same reason, only more so: alone its three launches and
+# two bandwidth passes make it the slowest of the timed forms, while its matrix work is 0.56 of theirs — under load that is what counts.  It is
+# tried wherever it was timed, whatever its isolated figure (no `margin`), and it has no sibling of its own to stand in for a missing timing.
+_WINO_FAMILY = set(_WINO_SIBLING) | {"wino_f43"}
+_WINO_ALWAYS = {"wino_f43"}
 
 
 def tune_in_flight(nets, run, top=6, margin=1.20, min_gain=0.01, reps=3, max_candidates=2, log=None):
@@ -63,9 +68,9 @@ def tune_in_flight(nets, run, top=6, margin=1.20, min_gain=0.01, reps=3, max_can
         cur = sig["tile"]
         keep = cur
         try:
-            family = [c for c in sig["timed"][max_candidates + 1:] if c[0] in _WINO_SIBLING]
+            family = [c for c in sig["timed"][max_candidates + 1:] if c[0] in _WINO_FAMILY]
             for tile, us in sig["timed"][:max_candidates + 1] + family:
-                if tile == cur or us > margin * best_alone:
+                if tile == cur or (us > margin * best_alone and tile not in _WINO_ALWAYS):
                     continue
                 put(sig["signature"], tile)
                 t = measure()

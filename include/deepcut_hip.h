@@ -531,6 +531,10 @@ int dc_stem7x7_pack(const float* g, int c, float* out);
  *    4 j + e of a 16-pixel step multiplies column (q k/4 + 4 j + e) of the filters with the same element of the pixel rows (one 16-byte LDS
  *    read of a pixel's row feeds four matrix steps).  tests/test_stream_pack.py.                                                        */
 int dc_stream1x1f_pack(const float* g, int cout, int k, float* out);
+/*  dc_wino43_pack: the filter image of the unfused Winograd F(4x4,3x3) form (csrc/wino43_f32.hip, tile `wino_f43`): g = [cout][cin][3][3]
+ *    (cout % 16 == 0, cin % 16 == 0) -> out[36 * cout * cin]: U = G g G^T per (co, ci) in double, rounded once to float; point p = 6 i + j
+ *    (U[i][j]) is the [cout][cin] matrix at out + p * cout * cin, each in dc_stream1x1f_pack's order.  tests/test_wino43_host.py.          */
+int dc_wino43_pack(const float* g, int cout, int cin, float* out);
 
 /* ---- pyramid-grouped execution: several executors of ONE model, each at its own input shape, as ONE launch sequence ----
  * Replaces the scale loop of the demo (python/pose/estimate_pose.py:81-128: one net.forward() per scale, every shape change a

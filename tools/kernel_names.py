@@ -42,6 +42,8 @@ def variant_name(name):
 
 
 def label(name):
+    if "ws1x1f_kernel" in name and (re.search(r"ws1x1f_kernel<\d+, \d+, false, false, false, true>", name) or "Lb0ELb0ELb0ELb1EE" in name):
+        return "ws1x1f batched (wino_f43: the 36 products, float32)"  # the BATCH instantiation (csrc/wino43_f32.hip launches it)
     if "ws1x1f_kernel" in name:  # its float32 form (csrc/stream1x1_f32.hip)
         return "ws1x1f (streaming 1x1, float32)"
     if "ws1x1_kernel" in name:  # the streaming form of the dense float16 1x1 layers (csrc/stream1x1.hip)
