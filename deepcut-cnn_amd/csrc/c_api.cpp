@@ -882,6 +882,69 @@ int dc_group_assemble_people_mirrored(dc_group* group, const double* scales, int
     G(group)->assemble_people(scales, base, q, n_edges, edges, mean, stdev, joint_order, n_people, people, cand, cost, mirror_args(fm, m));
   });
 }
+// tracking people from frame to frame (track.cpp): a dc_tracker* is a dc::Tracker*
+static inline Tracker* TR(dc_tracker* t) { return reinterpret_cast<Tracker*>(t); }
+int dc_tracker_create(const dc_tracker_params* p, dc_tracker** out) {
+  REQUIRE(p);
+  REQUIRE(out);
+  *out = nullptr;
+  return guard([&] {
+    *out = reinterpret_cast<dc_tracker*>(
+        Tracker::create(p->slots, p->max_tracks, p->n_joints, p->sigma, p->max_misses, p->min_common, p->max_dist, p->min_size, p->motion));
+  });
+}
+int dc_tracker_destroy(dc_tracker* tracker) {
+  if (!tracker) return DC_OK;
+  return guard([&] { delete TR(tracker); });
+}
+int dc_tracker_reset(dc_tracker* tracker, int slot) {
+  REQUIRE(tracker);
+  return guard([&] { TR(tracker)->reset(slot); });
+}
+int dc_tracker_update(dc_tracker* tracker, int nb, int P, const int* n_people, const double* people, long long* ids, int* place,
+                      double* dist) {
+  REQUIRE(tracker);
+  REQUIRE(n_people);
+  REQUIRE(people);
+  REQUIRE(ids);
+  return guard([&] { TR(tracker)->update(nb, P, n_people, people, ids, place, dist); });
+}
+int dc_tracker_state(dc_tracker* tracker, int slot, long long* ids, int* misses, int* hits, double* poses) {
+  REQUIRE(tracker);
+  return guard([&] { TR(tracker)->state(slot, ids, misses, hits, poses); });
+}
+int dc_net_track_people(dc_net* net, dc_tracker* tracker, const dc_assemble_params* p, int n_edges, const int* edges, const double* mean,
+                        const double* stdev, const int* joint_order, int* n_people, double* people, int* cand, double* cost,
+                        long long* ids, int* place) {
+  REQUIRE(net);
+  REQUIRE(tracker);
+  REQUIRE(p);
+  REQUIRE(n_people);
+  REQUIRE(people);
+  REQUIRE(ids);
+  if (n_edges > 0) REQUIRE(edges);
+  return guard([&] {
+    Net::AssembleParams q{p->scale, p->threshold, p->radius, p->max_det, p->max_cost, p->seed_threshold, p->max_people, p->min_joints};
+    N(net)->assemble_people(q, n_edges, edges, mean, stdev, joint_order, n_people, people, cand, cost, TR(tracker), ids, place);
+  });
+}
+int dc_group_track_people(dc_group* group, dc_tracker* tracker, const double* scales, int base, const dc_fuse_mirror* fm,
+                          const dc_assemble_params* p, int n_edges, const int* edges, const double* mean, const double* stdev,
+                          const int* joint_order, int* n_people, double* people, int* cand, double* cost, long long* ids, int* place) {
+  REQUIRE(group);
+  REQUIRE(tracker);
+  REQUIRE(p);
+  REQUIRE(n_people);
+  REQUIRE(people);
+  REQUIRE(ids);
+  if (n_edges > 0) REQUIRE(edges);
+  return guard([&] {
+    Net::AssembleParams q{p->scale, p->threshold, p->radius, p->max_det, p->max_cost, p->seed_threshold, p->max_people, p->min_joints};
+    NetGroup::FuseMirror m;
+    G(group)->assemble_people(scales, base, q, n_edges, edges, mean, stdev, joint_order, n_people, people, cand, cost, mirror_args(fm, m),
+                              TR(tracker), ids, place);
+  });
+}
 // single-person and box poses from the fused maps (net_group.cpp decode_pose / decode_boxes)
 int dc_group_decode_pose(dc_group* group, const double* scales, int base, const dc_fuse_mirror* fm, double* pose, int is_device, void* stream) {
   REQUIRE(group);

@@ -407,6 +407,47 @@ int launch_assemble(int NB, int J, int max_det, int max_people, int min_joints, 
                     const double* dets, const double* cost, const int* order, double* link, int* n_people, double* people, int* cand,
                     void* stream);
 
+// Tracking people from frame to frame (track.hip; the rule: include/deepcut_hip.h, dc_tracker_update — this project's own).  A slot's
+// state is one block of track_slot_bytes(T, J) bytes, all zero = no track and next_id 0:
+//   long long next_id (+ 8 bytes of padding) | long long id[T] | double pose[T][J][3] | double vel[T][J][2] | int live[T] | int misses[T]
+//   | int hits[T]
+// Limits: T and P <= kPeopleMaxPeople, J <= kPeopleMaxJoints.
+struct TrackParams {
+  int T, J, max_misses, min_common, motion;
+  double max_dist, min_size;
+};
+struct TrackSlot {  // the arrays of one slot inside its block
+  long long* next_id;
+  long long* id;
+  double* pose;
+  double* vel;
+  int* live;
+  int* misses;
+  int* hits;
+};
+inline size_t track_slot_bytes(int T, int J) { return 16 + (size_t)T * (8 + (size_t)J * 5 * 8 + 3 * 4); }
+#ifdef __HIP__  // the kernel and the host side both take a block apart with this
+#define DC_HOST_DEVICE __host__ __device__
+#else
+#define DC_HOST_DEVICE
+#endif
+DC_HOST_DEVICE inline TrackSlot track_slot(unsigned char* block, int T, int J) {
+  TrackSlot s;
+  s.next_id = (long long*)block;
+  s.id = (long long*)(block + 16);
+  s.pose = (double*)(s.id + T);
+  s.vel = s.pose + (size_t)T * J * 3;
+  s.live = (int*)(s.vel + (size_t)T * J * 2);
+  s.misses = s.live + T;
+  s.hits = s.misses + T;
+  return s;
+}
+// one workgroup per image b, which updates the slot whose block is state + b * slot_stride (a multiple of 16): reads n_people[b]
+// (clamped to [0, P]) and people [NB][P][J][3] from device memory, writes the state back in place, dist[b * T * kPeopleMaxPeople + i * P
+// + q] (scratch the caller keeps: the matching reads it back), ids [NB][P] and place [NB][P].  sig2 [J] = sigma_j^2.
+int launch_track(int NB, int P, const TrackParams& p, const double* sig2, unsigned char* state, size_t slot_stride, double* dist,
+                 const int* n_people, const double* people, long long* ids, int* place, void* stream);
+
 // The pairwise head at a list of cells (sparse_head.hip; the rule: include/deepcut_hip.h, dc_net_pairwise_at).  x3 / x5: the NHWC inputs
 // of the head's 1x1 skip convolution ([NB][H][W], pitch cp3, K3 channels) and of its stride-2 3x3 deconvolution ([NB][h5][w5], pitch cp5,
 // K5 channels), first channel already added, in the net's element type; vec3 / vec5: 4 consecutive channels of a cell may be read as one

@@ -39,6 +39,7 @@ int device_count();  // 0 without a GPU; never throws
 enum Head { UNINITIALIZED = 0, HEAD_AT_CPU = 1, HEAD_AT_GPU = 2, SYNCED = 3 };
 
 struct Net;
+struct Tracker;
 struct ModelShared;
 struct Storage {
   std::vector<int> shape;  // logical Caffe shape (N,C,H,W for activations)
@@ -352,8 +353,11 @@ struct Net {
     float seed_threshold;
     int max_people, min_joints;
   };
+  // tracker (may be null; dc_net_track_people): its launch runs behind the assembly's on the people left on the device -> ids, place
+  // [NB][max_people]; everything else is computed and returned exactly as without it
   void assemble_people(const AssembleParams& p, int n_edges, const int* edges, const double* mean, const double* stdev, const int* joint_order,
-                       int* n_people, double* people, int* cand, double* cost);
+                       int* n_people, double* people, int* cand, double* cost, Tracker* tracker = nullptr, long long* ids = nullptr,
+                       int* place = nullptr);
   // front half of forward_images: the uint8 pixels -> the network's NHWC input image, enqueued on s (the plan of the canvas
   // shape is active afterwards); returns the canvas height / width
   // mirror: the images are read flipped left to right (ImagePrepParams::mirror; NetGroup::forward_images hands it down)
@@ -413,11 +417,13 @@ struct Net {
   static std::vector<int> check_assemble_graph(const AssembleParams& q, int J, int n_edges, const int* edges, const double* mean,
                                                const double* stdev, const int* joint_order);
   // between (may be empty): called with stage A's device outputs (counts, dets) after its launch and before stage B's — the sparse
-  // pairwise head fills N's cells there
+  // pairwise head fills N's cells there.  after (may be empty): called with stage C's device outputs (n_people, people) behind its
+  // launch and before the downloads — the tracker's launch goes there
   static void assemble_maps(const MapRef& P, const MapRef& L, const MapRef& N, const AssembleParams& q, const std::vector<int>& table,
                             int n_edges, const double* mean, const double* stdev, const std::function<void*(size_t)>& scratch, void* stream,
                             int* n_people, double* people, int* cand, double* cost,
-                            const std::function<void(const int*, const double*)>& between = nullptr);
+                            const std::function<void(const int*, const double*)>& between = nullptr,
+                            const std::function<void(const int*, const double*)>& after = nullptr);
   // DC_OPT_SPARSE_PAIRWISE (sparse_pairwise.cpp)
   struct PairHead {
     int elt = -1, conv = -1, crop = -1, deconv = -1;  // layer indices: the Eltwise SUM, its 1x1 Convolution, its Crop and the Crop's Deconvolution
@@ -460,6 +466,36 @@ struct Net {
   std::vector<unsigned char> box_host_;  // the host side of that table (outlives its upload)
   int box_n_ = 0;                     // boxes of the last prep_boxes
   bool box_mirror_ = false;           // ... and whether it read them flipped left to right
+};
+
+// ---- tracking people from frame to frame (track.cpp / track.hip; the rule: include/deepcut_hip.h, dc_tracker_update) ---------------
+// The tracks of `slots` independent sequences in ONE device allocation, made, zeroed and bound to a device at the first update:
+//   slot blocks (kernels.h TrackSlot) | sigma^2 [J] | distances [slots][T][256] | staging of host poses: n_people [slots], people
+//   [slots][256][J][3] | outputs: ids [slots][256], place [slots][256]
+// Every call holds the runtime lock from its launch until the stream it ran on has been waited for, so the updates of a tracker apply
+// in host call order whichever stream they ran on.
+struct Tracker {
+  TrackParams tp{};
+  int slots = 0;
+  std::vector<double> sig2;
+  int device = -1;  // bound at the first update
+  unsigned char* dev = nullptr;
+  size_t slot_stride = 0, off_sig = 0, off_dist = 0, off_np = 0, off_ppl = 0, off_ids = 0, off_place = 0, total = 0;
+  // every argument error is DC_EINVAL naming the parameter; no device is needed
+  static Tracker* create(int slots, int max_tracks, int n_joints, const double* sigma, int max_misses, int min_common, double max_dist,
+                         double min_size, int motion);
+  ~Tracker();
+  Tracker() = default;
+  Tracker(const Tracker&) = delete;
+  Tracker& operator=(const Tracker&) = delete;
+  // host only: nb images of at most P people with J joints fit this tracker (DC_EINVAL / DC_ESHAPE naming what does not)
+  void check_call(const char* who, int nb, int P, int J) const;
+  // the caller holds the runtime lock and keeps it until `stream` has been waited for; `dev` is the current device.  Binds / checks
+  // the device, allocates at the first use, enqueues the launch on d_np / d_ppl and the downloads of ids / place / dist (any null).
+  void enqueue(int on_device, int nb, int P, const int* d_np, const double* d_ppl, long long* ids, int* place, double* dist, void* stream);
+  void update(int nb, int P, const int* n_people, const double* people, long long* ids, int* place, double* dist);
+  void reset(int slot);  // -1: all
+  void state(int slot, long long* ids, int* misses, int* hits, double* poses);
 };
 
 struct DevBuf {  // a grow-only device buffer
@@ -564,7 +600,7 @@ struct NetGroup {
   // fusion of all three maps, then Net::assemble_people's three launches on them at scales[base] (p.scale is not read)
   void assemble_people(const double* scales, int base, const Net::AssembleParams& p, int n_edges, const int* edges, const double* mean,
                        const double* stdev, const int* joint_order, int* n_people, double* people, int* cand, double* cost,
-                       const FuseMirror* fm = nullptr);
+                       const FuseMirror* fm = nullptr, Tracker* tracker = nullptr, long long* ids = nullptr, int* place = nullptr);
   // Single-person pose from the fused maps (dc_group_decode_pose): prob and loc_pred fused as detect_parts fuses them, then
   // launch_pose_decode on the fused float32 views at scales[base] -> pose [NB][5][J], host or device, stream as fuse_maps
   void decode_pose(const double* scales, int base, double* pose, bool is_device, void* user_stream, const FuseMirror* fm = nullptr);

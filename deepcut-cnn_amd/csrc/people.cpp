@@ -147,32 +147,45 @@ std::vector<int> Net::check_assemble_graph(const AssembleParams& q, int J, int n
 }
 
 void Net::assemble_people(const AssembleParams& q, int n_edges, const int* edges, const double* mean, const double* stdev,
-                          const int* joint_order, int* n_people, double* people, int* cand, double* cost) {
+                          const int* joint_order, int* n_people, double* people, int* cand, double* cost, Tracker* tracker, long long* ids,
+                          int* place) {
   check_assemble_params(q);
   auto ip = blob_index.find("prob");
   if (ip == blob_index.end()) throw DcError(DC_EINVAL, "net has no 'prob' blob");
   const std::vector<int>& pshape = blobs[ip->second]->st->shape;
   if (pshape.size() != 4) throw DcError(DC_ESHAPE, "'prob' is not a 4-D map");
   const std::vector<int> table = check_assemble_graph(q, pshape[1], n_edges, edges, mean, stdev, joint_order);
+  if (tracker) tracker->check_call("track_people", pshape[0], q.max_people, pshape[1]);
   // (the arguments above are refused with or without a device; from here on the device is needed)
   if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "assemble_people() in CPU mode");
   ensure_device();
   const MapRef P = map_ref("prob"), L = map_ref("loc_pred");
+  // the tracker's launch behind stage C: the runtime lock is taken there and kept until assemble_maps has waited for the stream
+  std::unique_lock<std::recursive_mutex> order(runtime_mu(), std::defer_lock);
+  std::function<void(const int*, const double*)> after;
+  if (tracker)
+    after = [&](const int* d_np, const double* d_ppl) {
+      order.lock();
+      tracker->enqueue(device, P.NB, q.max_people, d_np, d_ppl, ids, place, nullptr, stream);
+    };
   if (sparse_pairwise && !next_in_plan()) {  // DC_OPT_SPARSE_PAIRWISE: the head at the candidates' cells, between stages A and B
     const SparseNext sn = sparse_next(P.NB * P.C * q.max_det, 0);
     assemble_maps(P, L, sn.N, q, table, n_edges, mean, stdev, [this](size_t bytes) { return scratch(bytes); }, stream, n_people, people, cand, cost,
                   [&](const int* d_cnt, const double* d_det) {
                     KCHECK(launch_sparse_head(sn.a, sn.ekind, d_cnt, d_det, P.C, q.max_det, nullptr, P.NB * P.C * q.max_det, sn.work, stream));
-                  });
+                  },
+                  after);
     return;
   }
   const MapRef N = map_ref("next_pred");
-  assemble_maps(P, L, N, q, table, n_edges, mean, stdev, [this](size_t bytes) { return scratch(bytes); }, stream, n_people, people, cand, cost);
+  assemble_maps(P, L, N, q, table, n_edges, mean, stdev, [this](size_t bytes) { return scratch(bytes); }, stream, n_people, people, cand, cost,
+                nullptr, after);
 }
 
 void Net::assemble_maps(const MapRef& P, const MapRef& L, const MapRef& N, const AssembleParams& q, const std::vector<int>& table, int n_edges,
                         const double* mean, const double* stdev, const std::function<void*(size_t)>& scratch, void* stream, int* n_people,
-                        double* people, int* cand, double* cost, const std::function<void(const int*, const double*)>& between) {
+                        double* people, int* cand, double* cost, const std::function<void(const int*, const double*)>& between,
+                        const std::function<void(const int*, const double*)>& after) {
   const int J = P.C;
   if (L.C != 2 * P.C || L.H != P.H || L.W != P.W || L.NB != P.NB || L.es != P.es)
     throw DcError(DC_ESHAPE, "assemble_people: loc_pred must have 2 channels per joint and the score map's size");
@@ -221,6 +234,7 @@ void Net::assemble_maps(const MapRef& P, const MapRef& L, const MapRef& N, const
   KCHECK(launch_pair_cost(N.ptr, N.cp, N.c0, N.ek, NB, N.H, N.W, J, MD, q.scale, d_cnt, d_det, d_tab, d_mean, d_std, d_cost, stream));
   KCHECK(launch_assemble(NB, J, MD, PP, q.min_joints, q.max_cost, (double)q.seed_threshold, d_cnt, d_det, d_cost, d_tab + (size_t)J * J, d_link,
                          d_np, d_ppl, d_cand, stream));
+  if (after) after(d_np, d_ppl);
   HIPCHECK(hipMemcpyAsync(n_people, d_np, (size_t)NB * sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHECK(hipMemcpyAsync(people, d_ppl, (size_t)NB * PP * J * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
   if (cand) HIPCHECK(hipMemcpyAsync(cand, d_cand, (size_t)NB * PP * J * sizeof(int), hipMemcpyDeviceToHost, s));

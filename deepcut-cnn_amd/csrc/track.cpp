@@ -1,0 +1,149 @@
+// track.cpp — the tracker object behind dc_tracker_*: argument checks, the device buffer of the slots' tracks and the launches of
+// track.hip.  The rule is stated in include/deepcut_hip.h (dc_tracker_update).
+//
+// PARITY UNPINNED BY THE REFERENCE: eldar/deepcut-cnn stops at the maps and has no tracker; the rule is this project's own.
+#include "net_internal.h"
+
+namespace dc {
+
+namespace {
+[[noreturn]] void bad(const std::string& who, const std::string& m) { throw DcError(DC_EINVAL, who + ": " + m); }
+size_t up256(size_t b) { return (b + 255) / 256 * 256; }
+// the calling thread's current device for the length of a call on a tracker bound to another one (state, reset)
+struct DeviceScope {
+  int before = -1;
+  explicit DeviceScope(int d) {
+    HIPCHECK(hipGetDevice(&before));
+    if (before != d) HIPCHECK(hipSetDevice(d));
+    else before = -1;
+  }
+  ~DeviceScope() {
+    if (before >= 0) (void)hipSetDevice(before);
+  }
+};
+}  // namespace
+
+Tracker* Tracker::create(int slots, int max_tracks, int n_joints, const double* sigma, int max_misses, int min_common, double max_dist,
+                         double min_size, int motion) {
+  const std::string who = "tracker_create";
+  if (slots < 1 || slots > 64) bad(who, "slots must be in [1, 64]");
+  if (max_tracks < 1 || max_tracks > kPeopleMaxPeople) bad(who, "max_tracks must be in [1, " + std::to_string(kPeopleMaxPeople) + "]");
+  if (n_joints < 1 || n_joints > kPeopleMaxJoints) bad(who, "n_joints must be in [1, " + std::to_string(kPeopleMaxJoints) + "]");
+  for (int j = 0; sigma && j < n_joints; ++j)
+    if (!(std::isfinite(sigma[j]) && sigma[j] > 0)) bad(who, "sigma of joint " + std::to_string(j) + " must be finite and > 0");
+  if (max_misses < 0) bad(who, "max_misses must be >= 0");
+  if (min_common < 1 || min_common > n_joints) bad(who, "min_common must be in [1, " + std::to_string(n_joints) + "]");
+  if (!(max_dist >= 0) || !std::isfinite(max_dist)) bad(who, "max_dist must be finite and >= 0");
+  if (!(min_size > 0) || !std::isfinite(min_size)) bad(who, "min_size must be finite and > 0");
+  if (motion != 0 && motion != 1) bad(who, "motion must be 0 or 1");
+  std::unique_ptr<Tracker> t(new Tracker());
+  t->tp = TrackParams{max_tracks, n_joints, max_misses, min_common, motion, max_dist, min_size};
+  t->slots = slots;
+  t->sig2.resize((size_t)n_joints);
+  for (int j = 0; j < n_joints; ++j) t->sig2[(size_t)j] = sigma ? sigma[j] * sigma[j] : 1.0;
+  const size_t S = (size_t)slots, T = (size_t)max_tracks, J = (size_t)n_joints, PM = (size_t)kPeopleMaxPeople;
+  t->slot_stride = up256(track_slot_bytes(max_tracks, n_joints));
+  size_t at = S * t->slot_stride;
+  auto take = [&](size_t bytes) {
+    const size_t r = at;
+    at += up256(bytes);
+    return r;
+  };
+  t->off_sig = take(J * sizeof(double));
+  t->off_dist = take(S * T * PM * sizeof(double));
+  t->off_np = take(S * sizeof(int));
+  t->off_ppl = take(S * PM * J * 3 * sizeof(double));
+  t->off_ids = take(S * PM * sizeof(long long));
+  t->off_place = take(S * PM * sizeof(int));
+  t->total = at;
+  return t.release();
+}
+
+Tracker::~Tracker() { dev_free(dev); }
+
+void Tracker::check_call(const char* who, int nb, int P, int J) const {
+  if (nb < 1 || nb > slots) bad(who, std::to_string(nb) + " images for a tracker of " + std::to_string(slots) + " slots (nb must be in [1, slots])");
+  if (P < 1 || P > kPeopleMaxPeople) bad(who, "max_people (P) must be in [1, " + std::to_string(kPeopleMaxPeople) + "]");
+  if (J != tp.J)
+    throw DcError(DC_ESHAPE, std::string(who) + ": the tracker holds " + std::to_string(tp.J) + " joints (n_joints), the poses " + std::to_string(J));
+}
+
+void Tracker::enqueue(int on_device, int nb, int P, const int* d_np, const double* d_ppl, long long* ids, int* place, double* dist, void* stream) {
+  if (device >= 0 && device != on_device)
+    throw DcError(DC_EDEVICE, "tracker: bound to device " + std::to_string(device) + ", used on device " + std::to_string(on_device));
+  hipStream_t s = (hipStream_t)stream;
+  if (!dev) {
+    dev_alloc((void**)&dev, total);
+    device = on_device;
+    dev_zero(dev, total, stream);
+    dev_upload(dev + off_sig, sig2.data(), sig2.size() * sizeof(double), stream);
+  }
+  long long* d_ids = (long long*)(dev + off_ids);
+  int* d_place = (int*)(dev + off_place);
+  double* d_dist = (double*)(dev + off_dist);
+  KCHECK(launch_track(nb, P, tp, (const double*)(dev + off_sig), dev, slot_stride, d_dist, d_np, d_ppl, d_ids, d_place, stream));
+  if (ids) HIPCHECK(hipMemcpyAsync(ids, d_ids, (size_t)nb * P * sizeof(long long), hipMemcpyDeviceToHost, s));
+  if (place) HIPCHECK(hipMemcpyAsync(place, d_place, (size_t)nb * P * sizeof(int), hipMemcpyDeviceToHost, s));
+  for (int b = 0; dist && b < nb; ++b)
+    HIPCHECK(hipMemcpyAsync(dist + (size_t)b * tp.T * P, d_dist + (size_t)b * tp.T * kPeopleMaxPeople, (size_t)tp.T * P * sizeof(double),
+                            hipMemcpyDeviceToHost, s));
+}
+
+void Tracker::update(int nb, int P, const int* n_people, const double* people, long long* ids, int* place, double* dist) {
+  check_call("tracker_update", nb, P, tp.J);
+  for (int b = 0; b < nb; ++b)
+    if (n_people[b] < 0 || n_people[b] > P)
+      bad("tracker_update", "n_people[" + std::to_string(b) + "] = " + std::to_string(n_people[b]) + " is outside [0, P = " + std::to_string(P) + "]");
+  if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "tracker_update() in CPU mode");
+  if (device_count() <= 0) throw DcError(DC_EDEVICE, "no HIP device visible");
+  const int d = Context::get().device;
+  HIPCHECK(hipSetDevice(d));
+  RuntimeLock rl;
+  hipStream_t s = util_stream();
+  if (!dev || device != d) enqueue(d, 0, P, nullptr, nullptr, nullptr, nullptr, nullptr, s);  // no launch: binds, allocates and zeroes, or DC_EDEVICE
+  int* d_np = (int*)(dev + off_np);
+  double* d_ppl = (double*)(dev + off_ppl);
+  const size_t img = (size_t)P * tp.J * 3;
+  HIPCHECK(hipMemcpyAsync(d_np, n_people, (size_t)nb * sizeof(int), hipMemcpyHostToDevice, s));
+  // only the people that exist are read on either side
+  for (int b = 0; b < nb; ++b)
+    if (n_people[b] > 0)
+      HIPCHECK(hipMemcpyAsync(d_ppl + (size_t)b * img, people + (size_t)b * img, (size_t)n_people[b] * tp.J * 3 * sizeof(double),
+                              hipMemcpyHostToDevice, s));
+  enqueue(d, nb, P, d_np, d_ppl, ids, place, dist, s);
+  HIPCHECK(hipStreamSynchronize(s));
+}
+
+void Tracker::reset(int slot) {
+  if (slot < -1 || slot >= slots) bad("tracker_reset", "slot must be in [0, " + std::to_string(slots) + ") or -1 for all");
+  if (!dev) return;  // nothing has been tracked yet
+  RuntimeLock rl;
+  DeviceScope on(device);
+  hipStream_t s = util_stream();
+  if (slot < 0) HIPCHECK(hipMemsetAsync(dev, 0, (size_t)slots * slot_stride, s));
+  else HIPCHECK(hipMemsetAsync(dev + (size_t)slot * slot_stride, 0, slot_stride, s));
+  HIPCHECK(hipStreamSynchronize(s));
+}
+
+void Tracker::state(int slot, long long* ids, int* misses, int* hits, double* poses) {
+  if (slot < 0 || slot >= slots) bad("tracker_state", "slot must be in [0, " + std::to_string(slots) + ")");
+  const int T = tp.T, J = tp.J;
+  std::vector<unsigned char> block(track_slot_bytes(T, J), 0);  // all zero: every place free
+  if (dev) {
+    RuntimeLock rl;
+    DeviceScope on(device);
+    hipStream_t s = util_stream();
+    HIPCHECK(hipMemcpyAsync(block.data(), dev + (size_t)slot * slot_stride, block.size(), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+  }
+  const TrackSlot st = track_slot(block.data(), T, J);
+  for (int i = 0; i < T; ++i) {
+    const bool lv = st.live[i] != 0;
+    if (ids) ids[i] = lv ? st.id[i] : -1;
+    if (misses) misses[i] = lv ? st.misses[i] : 0;
+    if (hits) hits[i] = lv ? st.hits[i] : 0;
+    for (int k = 0; poses && k < J * 3; ++k) poses[(size_t)i * J * 3 + k] = lv ? st.pose[(size_t)i * J * 3 + k] : 0.0;
+  }
+}
+
+}  // namespace dc

@@ -1,0 +1,278 @@
+// track.hip — people from frame to frame: the greedy association of one frame's people with a slot's live tracks (gfx950).
+//
+// PARITY UNPINNED BY THE REFERENCE: eldar/deepcut-cnn stops at the maps and has no tracker.  The rule is this project's own
+// (include/deepcut_hip.h, dc_tracker_update), restated in float64 in tests/track_ref.py.
+//
+// One latency-class kernel behind assemble_kernel (people.hip) or behind an upload of host poses, nothing of it on the forward path.
+// All arithmetic is double and there is no matrix instruction in it: a frame is at most 256 x 256 distances of at most 32 joints.
+#include <hip/hip_runtime.h>
+
+#include "kernels.h"
+
+namespace dc {
+
+namespace {
+constexpr int kTrackMax = kPeopleMaxPeople;  // T and P: one thread per track place and per person
+constexpr int kTrackBlock = 16;              // track places whose predicted joints sit in LDS at a time (distances)
+
+// the smaller of two (value, index) keys, index ascending among equal values; kNone = no key
+constexpr int kNone = 0x7fffffff;
+__device__ __forceinline__ void key_min(double& v, int& e, double v2, int e2) {
+  if (e2 != kNone && (e == kNone || v2 < v || (v2 == v && e2 < e))) v = v2, e = e2;
+}
+// ... over the 64 lanes of a wave: every lane ends with the wave's key
+__device__ __forceinline__ void wave_key_min(double& v, int& e) {
+  for (int s = 32; s > 0; s >>= 1) {
+    const double v2 = __shfl_xor(v, s);
+    const int e2 = __shfl_xor(e, s);
+    key_min(v, e, v2, e2);
+  }
+}
+}  // namespace
+
+// One workgroup of 256 threads (4 waves) updates one slot.  Thread i owns track place i in steps 1, 5 and 6, thread q owns person q in
+// step 7.  D lives in global scratch (256 x 256 doubles do not fit in LDS beside the rest) and is written and read
+// inside this workgroup only, with a barrier in between.
+// Matching: a round takes the smallest D among unmatched pairs.  Scanning all T*P entries every round is 256 rounds of 65 536 reads at
+// T = P = 256, so the minimum of every ROW is kept in LDS — rv[i], rq[i] = the smallest allowed D of track i among unmatched people and
+// the lowest q that has it — and a round is (1) the arg-min over the rows, a (value, place) key whose index order is the tie rule:
+// lower place first, and within the row the lower q was kept; (2) the re-derivation of the rows the match invalidates: those whose
+// minimum sat at the person just taken.  A wave re-derives a row with coalesced reads and a shuffle reduction; rows go to waves round
+// robin.  No step depends on thread timing: same inputs, same ids.
+__global__ __launch_bounds__(256) void track_kernel(int P, TrackParams tp, const double* __restrict__ sig2_g, unsigned char* __restrict__ state,
+                                                    size_t slot_stride, double* __restrict__ dist, const int* __restrict__ n_people,
+                                                    const double* __restrict__ people, long long* __restrict__ ids, int* __restrict__ place) {
+  __shared__ double s2[kTrackMax];   // s_i^2
+  __shared__ double rv[kTrackMax];   // row minima: value ...
+  __shared__ int rq[kTrackMax];      // ... and person, -1 = the row has no allowed entry left
+  __shared__ int live[kTrackMax];    // the place holds a track (as of the start of the update; step 6 clears it)
+  __shared__ int mult[kTrackMax];    // misses + 1 of the track
+  __shared__ int tm[kTrackMax];      // the person matched to track i, or -1
+  __shared__ int pm[kTrackMax];      // the place matched to person q, or -1
+  __shared__ int fplace[kTrackMax];  // the free places in ascending order
+  __shared__ int flag[kTrackMax];
+  __shared__ double sig2[kPeopleMaxJoints];
+  __shared__ double bpx[kTrackBlock][kPeopleMaxJoints], bpy[kTrackBlock][kPeopleMaxJoints];  // predicted joints of a block of tracks
+  __shared__ int bheld[kTrackBlock][kPeopleMaxJoints];                                        // ... and whether the track holds them
+  __shared__ double red_v[4];
+  __shared__ int red_e[4];
+  __shared__ int nfree_s;
+  const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int T = tp.T, J = tp.J;
+  const double inf = __builtin_huge_val();
+  const TrackSlot st = track_slot(state + (size_t)b * slot_stride, T, J);
+  const int n = min(max(n_people[b], 0), P);
+  const double* ppl = people + (size_t)b * P * J * 3;
+  double* D = dist + (size_t)b * T * kTrackMax;
+
+  // 1. track sizes
+  if (t < J) sig2[t] = sig2_g[t];
+  tm[t] = -1, pm[t] = -1, rq[t] = -1, rv[t] = inf;
+  {
+    int lv = 0, ms = 0;
+    double size2 = 0.0;
+    if (t < T) {
+      lv = st.live[t];
+      ms = st.misses[t];
+      if (lv) {
+        double x0 = inf, x1 = -inf, y0 = inf, y1 = -inf;
+        for (int j = 0; j < J; ++j) {
+          const double* p = st.pose + ((size_t)t * J + j) * 3;
+          if (p[2] > 0.0) x0 = fmin(x0, p[0]), x1 = fmax(x1, p[0]), y0 = fmin(y0, p[1]), y1 = fmax(y1, p[1]);
+        }
+        double s = tp.min_size;
+        if (x1 >= x0) s = fmax(s, fmax(x1 - x0, y1 - y0));
+        size2 = s * s;
+      }
+    }
+    live[t] = lv, mult[t] = ms + 1, s2[t] = size2;
+  }
+  __syncthreads();
+
+  // 2., 3. distances, kTrackBlock track places at a time: their predicted joints go to LDS once, then a thread holds one joint of
+  // person q in registers and reads tracks of the block from LDS (one address per wave or per P lanes: broadcasts) — a person's pose
+  // is fetched T / kTrackBlock times, not T times.  With P < 256 the threads form G = 256 / P slices that share the block's tracks
+  // between them.  The sum of a (track, person) pair still runs over the joints ascending, in one thread.
+  const int G = min(256 / P, kTrackBlock);
+  for (int i0 = 0; i0 < T; i0 += kTrackBlock) {
+    __syncthreads();  // the readers of the previous block are done
+    for (int e = t; e < kTrackBlock * J; e += 256) {
+      const int r = e / J, j = e - r * J, i = i0 + r;
+      double px = 0.0, py = 0.0;
+      int held = 0;
+      if (i < T && live[i]) {
+        const double* tr = st.pose + ((size_t)i * J + j) * 3;
+        if (tr[2] > 0.0) {
+          held = 1, px = tr[0], py = tr[1];
+          if (tp.motion == 1) {
+            const double* ve = st.vel + ((size_t)i * J + j) * 2;
+            const double m = (double)mult[i];
+            px = px + ve[0] * m, py = py + ve[1] * m;
+          }
+        }
+      }
+      bpx[r][j] = px, bpy[r][j] = py, bheld[r][j] = held;
+    }
+    __syncthreads();
+    if (t < G * P) {  // thread (slice, q): the block's tracks slice, slice + G, ... against person q
+      const int slice = t / P, q = t - slice * P;
+      double sum[kTrackBlock];
+      int nc[kTrackBlock];
+#pragma unroll
+      for (int k = 0; k < kTrackBlock; ++k) sum[k] = 0.0, nc[k] = 0;
+      if (q < n)
+        for (int j = 0; j < J; ++j) {
+          const double* pe = ppl + ((size_t)q * J + j) * 3;
+          const double qx = pe[0], qy = pe[1];
+          if (!(pe[2] > 0.0)) continue;
+          const double sg = sig2[j];
+#pragma unroll
+          for (int k = 0; k < kTrackBlock; ++k) {
+            const int r = slice + k * G;
+            if (r < kTrackBlock && bheld[r][j]) {
+              const double dx = bpx[r][j] - qx, dy = bpy[r][j] - qy;
+              sum[k] += (dx * dx + dy * dy) / (s2[i0 + r] * sg);
+              ++nc[k];
+            }
+          }
+        }
+#pragma unroll
+      for (int k = 0; k < kTrackBlock; ++k) {
+        const int r = slice + k * G;
+        if (r < kTrackBlock && i0 + r < T)
+          D[(size_t)(i0 + r) * P + q] = (nc[k] >= tp.min_common && nc[k] > 0) ? sum[k] / (double)nc[k] : inf;
+      }
+    }
+  }
+  __syncthreads();  // D is complete (global memory written and read by this workgroup only)
+
+  // 4. greedy matching on row minima
+  auto row_min = [&](int i) {  // by one wave: rv[i], rq[i] over the unmatched people
+    double v = inf;
+    int e = kNone;
+    for (int q = lane; q < n; q += 64) {
+      if (pm[q] >= 0) continue;
+      const double d = D[(size_t)i * P + q];
+      if (d <= tp.max_dist && d < v) v = d, e = q;  // q ascends within a lane: the first of equal distances stays
+    }
+    wave_key_min(v, e);
+    if (lane == 0) rv[i] = v, rq[i] = e == kNone ? -1 : e;
+  };
+  for (int i = wave; i < T; i += 4)
+    if (live[i]) row_min(i);
+  for (;;) {
+    __syncthreads();  // the row minima of this round are in place
+    double v = inf;
+    int e = kNone;
+    if (t < T && live[t] && tm[t] < 0 && rq[t] >= 0) v = rv[t], e = t;
+    wave_key_min(v, e);
+    if (lane == 0) red_v[wave] = v, red_e[wave] = e;
+    __syncthreads();
+    v = red_v[0], e = red_e[0];
+    for (int w = 1; w < 4; ++w) key_min(v, e, red_v[w], red_e[w]);
+    if (e == kNone) break;  // the same value in every thread: the exit is uniform
+    const int wi = e, wq = rq[wi];
+    __syncthreads();  // everybody has read the winner's row before it changes
+    if (t == 0) tm[wi] = wq, pm[wq] = wi;
+    __syncthreads();
+    for (int i = wave; i < T; i += 4)
+      if (live[i] && tm[i] < 0 && rq[i] == wq) row_min(i);
+  }
+  __syncthreads();
+
+  // 5., 6. the tracks
+  {
+    int free_now = 0;
+    if (t < T) {
+      if (live[t] && tm[t] >= 0) {
+        const double m = (double)mult[t];
+        const double* pe = ppl + (size_t)tm[t] * J * 3;
+        for (int j = 0; j < J; ++j) {
+          double* tr = st.pose + ((size_t)t * J + j) * 3;
+          double* ve = st.vel + ((size_t)t * J + j) * 2;
+          const double x = pe[j * 3], y = pe[j * 3 + 1], sc = pe[j * 3 + 2];
+          double vx = 0.0, vy = 0.0;
+          if (tr[2] > 0.0 && sc > 0.0) vx = (x - tr[0]) / m, vy = (y - tr[1]) / m;
+          ve[0] = vx, ve[1] = vy;
+          tr[0] = x, tr[1] = y, tr[2] = sc;
+        }
+        st.misses[t] = 0;
+        st.hits[t] += 1;
+      } else if (live[t]) {
+        const int ms = mult[t];  // misses + 1
+        st.misses[t] = ms;
+        if (ms > tp.max_misses) st.live[t] = 0, free_now = 1;
+      } else {
+        free_now = 1;
+      }
+    }
+    flag[t] = free_now;
+  }
+  __syncthreads();
+  // 7. births: the r-th unmatched person takes the r-th free place
+  if (flag[t]) {
+    int rank = 0;
+    for (int i = 0; i < t; ++i) rank += flag[i];
+    fplace[rank] = t;
+  }
+  if (t == 0) {
+    int total = 0;
+    for (int i = 0; i < T; ++i) total += flag[i];
+    nfree_s = total;
+  }
+  __syncthreads();
+  const int unmatched = (t < n && pm[t] < 0) ? 1 : 0;
+  const int nfree = nfree_s;
+  const long long next_id = *st.next_id;  // read by everybody before thread 0 moves it on, below the next barrier
+  __syncthreads();                        // flag is free again
+  flag[t] = unmatched;
+  __syncthreads();
+  long long my_id = -1;
+  int my_place = -1;
+  if (t < n) {
+    if (!unmatched) {
+      my_place = pm[t];
+      my_id = st.id[my_place];
+    } else {
+      int rank = 0;
+      for (int q = 0; q < t; ++q) rank += flag[q];
+      if (rank < nfree) {
+        my_place = fplace[rank];
+        my_id = next_id + rank;
+        const double* pe = ppl + (size_t)t * J * 3;
+        for (int j = 0; j < J; ++j) {
+          double* tr = st.pose + ((size_t)my_place * J + j) * 3;
+          double* ve = st.vel + ((size_t)my_place * J + j) * 2;
+          tr[0] = pe[j * 3], tr[1] = pe[j * 3 + 1], tr[2] = pe[j * 3 + 2];
+          ve[0] = 0.0, ve[1] = 0.0;
+        }
+        st.id[my_place] = my_id;
+        st.live[my_place] = 1;
+        st.misses[my_place] = 0;
+        st.hits[my_place] = 1;
+      }
+    }
+  }
+  if (t == 0) {
+    int born = 0;
+    for (int q = 0; q < n; ++q) born += flag[q];
+    *st.next_id = next_id + min(born, nfree);
+  }
+  if (t < P) {
+    ids[(size_t)b * P + t] = my_id;
+    place[(size_t)b * P + t] = my_place;
+  }
+}
+
+int launch_track(int NB, int P, const TrackParams& p, const double* sig2, unsigned char* state, size_t slot_stride, double* dist,
+                 const int* n_people, const double* people, long long* ids, int* place, void* stream) {
+  if (NB <= 0) return 0;
+  if (P < 1 || P > kTrackMax || p.T < 1 || p.T > kTrackMax || p.J < 1 || p.J > kPeopleMaxJoints || slot_stride % 16 ||
+      slot_stride < track_slot_bytes(p.T, p.J))
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(track_kernel, dim3(NB), dim3(256), 0, (hipStream_t)stream, P, p, sig2, state, slot_stride, dist, n_people, people, ids,
+                     place);
+  return (int)hipGetLastError();
+}
+
+}  // namespace dc

@@ -46,6 +46,12 @@ class FuseMirror(C.Structure):
     _fields_ = [("mirror", C.c_void_p), ("image_width", C.c_int), ("joint_mirror", C.c_void_p), ("n_edges", C.c_int), ("edges", C.c_void_p)]
 
 
+class TrackerParams(C.Structure):
+    """dc_tracker_params (include/deepcut_hip.h)."""
+    _fields_ = [("slots", C.c_int), ("max_tracks", C.c_int), ("n_joints", C.c_int), ("sigma", C.c_void_p), ("max_misses", C.c_int),
+                ("min_common", C.c_int), ("max_dist", C.c_double), ("min_size", C.c_double), ("motion", C.c_int)]
+
+
 class DcFrame(C.Structure):
     """dc_frame (include/deepcut_hip.h)."""
     _fields_ = [("plane", C.c_void_p * 2), ("pitch", C.c_int * 2), ("format", C.c_int), ("matrix", C.c_int), ("range", C.c_int)]
@@ -255,6 +261,14 @@ def _load():
         "dc_net_decode_pairwise": (ci, [vp, C.c_double, ci, vp, vp, vp, vp]),
         "dc_pair_stats_read": (ci, [cp, ci, C.POINTER(ci), vp, vp, vp]),
         "dc_net_assemble_people": (ci, [vp, C.POINTER(AssembleParams), ci, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "dc_tracker_create": (ci, [C.POINTER(TrackerParams), C.POINTER(vp)]),
+        "dc_tracker_destroy": (ci, [vp]),
+        "dc_tracker_reset": (ci, [vp, ci]),
+        "dc_tracker_update": (ci, [vp, ci, ci, vp, vp, vp, vp, vp]),
+        "dc_tracker_state": (ci, [vp, ci, vp, vp, vp, vp]),
+        "dc_net_track_people": (ci, [vp, vp, C.POINTER(AssembleParams), ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "dc_group_track_people": (ci, [vp, vp, vp, ci, C.POINTER(FuseMirror), C.POINTER(AssembleParams), ci, vp, vp, vp, vp, vp, vp, vp, vp,
+                                       vp, vp]),
         "dc_net_flops": (ci, [vp, C.POINTER(C.c_double)]),
         "dc_net_num_launches": (ci, [vp]),
         "dc_net_plan_text": (cp, [vp]),
@@ -654,6 +668,84 @@ class _OutPool(object):
 
             self.entries.append([buf, n, _w.ref(a)])
         return a.reshape(shape)
+
+
+class Tracker(object):
+    """The same person across the frames of a video (dc_tracker_*): `slots` independent sequences of at most `max_tracks` live tracks
+    each, kept on the device.  An update associates the people of a frame with the slot's tracks greedily by a size-normalised mean
+    squared joint distance and gives every person an id that stays with them; the rule is stated in include/deepcut_hip.h
+    (dc_tracker_update).  PARITY UNPINNED BY THE REFERENCE, which stops at the maps: the rule is this project's own.
+    sigma: [J] per-joint tolerance (None = 1.0); a track and a person are compared over the joints both hold (at least min_common), a
+    match needs a distance <= max_dist, a track without a match for more than max_misses updates in a row is dropped; min_size: lower
+    bound in pixels of the track size the distance is normalised by; motion: 1 compares with the pose moved on by its velocity, 0 with
+    the last pose.  THE DEFAULTS OF max_misses, min_common, max_dist, min_size AND sigma ARE PLACEHOLDERS, NOT TUNED ON REAL VIDEO:
+    override them.  Creation needs no device; updates need GPU mode.  Calls are synchronous and apply in call order."""
+
+    def __init__(self, n_joints=14, slots=1, max_tracks=64, sigma=None, max_misses=5, min_common=3, max_dist=0.25, min_size=32.0, motion=1):
+        self._h = None
+        sig = None
+        if sigma is not None:
+            sig = np.ascontiguousarray(sigma, dtype=np.float64).reshape(-1)
+            if sig.shape[0] != int(n_joints):
+                raise ValueError("sigma must hold one value per joint: %d values for %d joints" % (sig.shape[0], int(n_joints)))
+        q = TrackerParams(int(slots), int(max_tracks), int(n_joints), None if sig is None else sig.ctypes.data, int(max_misses),
+                          int(min_common), float(max_dist), float(min_size), int(motion))
+        h = C.c_void_p()
+        _check(_lib.dc_tracker_create(C.byref(q), C.byref(h)))
+        self._h = h
+        self.n_joints, self.slots, self.max_tracks = int(n_joints), int(slots), int(max_tracks)
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            _lib.dc_tracker_destroy(self._h)
+            self._h = None
+
+    def update(self, people, n_people=None, return_dist=False):
+        """people: [nb, P, J, 3] float64 (x, y, score; a joint counts when its score > 0) with n_people [nb] of them valid per image, or
+        a list of nb arrays [m_b, J, 3] (n_people is then their lengths) — image b updates slot b.  This is how poses that did not come
+        from `track_people` (top-down poses of `forward_boxes`, say) get tracked.
+        -> (ids int64 [nb, P], place int32 [nb, P]): -1 beyond n_people[b] and for a person no track place was free for; with
+        return_dist also the distances float64 [nb, max_tracks, P]."""
+        j = self.n_joints
+        if n_people is None and not (isinstance(people, np.ndarray) and people.ndim == 4):
+            arrs = [np.asarray(a, np.float64).reshape(-1, j, 3) for a in people]
+            n = np.array([a.shape[0] for a in arrs], np.int32)
+            ppl = np.zeros((len(arrs), max(1, int(n.max()) if len(arrs) else 1), j, 3), np.float64)
+            for b, a in enumerate(arrs):
+                ppl[b, :a.shape[0]] = a
+        else:
+            ppl = np.ascontiguousarray(people, dtype=np.float64)
+            if ppl.ndim != 4 or ppl.shape[2:] != (j, 3):
+                raise ValueError("people must be [nb, P, %d, 3] (x, y, score), got shape %s" % (j, ppl.shape))
+            n = np.full(ppl.shape[0], ppl.shape[1], np.int32) if n_people is None else np.ascontiguousarray(n_people, dtype=np.int32).reshape(-1)
+            if n.shape[0] != ppl.shape[0]:
+                raise ValueError("n_people must hold one count per image: %d counts for %d images" % (n.shape[0], ppl.shape[0]))
+        nb, p = ppl.shape[:2]
+        ids = np.full((nb, p), -1, np.int64)
+        place = np.full((nb, p), -1, np.int32)
+        dist = np.zeros((nb, self.max_tracks, p), np.float64) if return_dist else None
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        _check(_lib.dc_tracker_update(self._h, nb, p, ptr(n), ptr(ppl), ptr(ids), ptr(place), ptr(dist)))
+        return (ids, place, dist) if return_dist else (ids, place)
+
+    def reset(self, slot=None):
+        """Forget the tracks of `slot` (None: of every slot); its ids start again at 0."""
+        _check(_lib.dc_tracker_reset(self._h, -1 if slot is None else int(slot)))
+
+    def state(self, slot=0):
+        """The tracks of a slot, e.g. to see where occluded people were last seen -> dict: "ids" int64 [T] (-1 = free place), "misses"
+        int32 [T] (updates since the last match), "hits" int32 [T] (matches so far, the birth included), "poses" float64 [T, J, 3]."""
+        t, j = self.max_tracks, self.n_joints
+        out = {"ids": np.full(t, -1, np.int64), "misses": np.zeros(t, np.int32), "hits": np.zeros(t, np.int32),
+               "poses": np.zeros((t, j, 3), np.float64)}
+        _check(_lib.dc_tracker_state(self._h, int(slot), *[out[k].ctypes.data_as(C.c_void_p) for k in ("ids", "misses", "hits", "poses")]))
+        return out
+
+
+def _tracker_handle(tracker):
+    if not isinstance(tracker, Tracker):
+        raise TypeError("track_people needs a caffe.Tracker, got %r" % (type(tracker).__name__,))
+    return tracker._h
 
 
 class Layer(object):
@@ -1206,6 +1298,21 @@ class Net(object):
         The grouping rule (include/deepcut_hip.h) is this project's own; the reference stops at the maps.
         -> one dict per image: {"people": float64 [m, J, 3] = x, y, score ((0, 0, 0) for a missing joint), "cand": int32 [m, J] =
         index in the joint's candidate list or -1}, plus "cost": float64 [J, J, max_det, max_det] with return_cost."""
+        return self._assemble_people(None, scale, threshold, radius, max_det, edges, mean, std, max_cost, seed_threshold, max_people, min_joints,
+                                     joint_order, return_cost)
+
+    def track_people(self, tracker, scale=1.0, threshold=0.1, radius=1, max_det=16, edges=None, mean=None, std=None, max_cost=32.0,
+                     seed_threshold=0.5, max_people=32, min_joints=1, joint_order=None, return_cost=False):
+        """`assemble_people` with the identities of a `caffe.Tracker` (dc_net_track_people): the tracker's update runs on the device
+        behind the assembly, on the people where the assembly left them — image b updates slot b.  The arguments and the result are
+        `assemble_people`'s, unchanged, with two more entries per image: "ids": int64 [m] (the same person keeps their id from frame
+        to frame; -1 = no track place was free) and "place": int32 [m] (the track place, an index into `tracker.state()`)."""
+        _tracker_handle(tracker)
+        return self._assemble_people(tracker, scale, threshold, radius, max_det, edges, mean, std, max_cost, seed_threshold, max_people,
+                                     min_joints, joint_order, return_cost)
+
+    def _assemble_people(self, tracker, scale, threshold, radius, max_det, edges, mean, std, max_cost, seed_threshold, max_people, min_joints,
+                         joint_order, return_cost):
         if edges is None:
             raise ValueError("assemble_people needs the regression edges (deepcut_tools.read_pair_stats)")
         n, j = self.blobs["prob"].shape[:2]
@@ -1218,13 +1325,20 @@ class Net(object):
         cand = np.zeros((n, p, j), np.int32)
         cost = np.zeros((n, j, j, md, md), np.float64) if return_cost else None
         ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        _check(_lib.dc_net_assemble_people(self._h, C.byref(q), e.shape[0], ptr(e), ptr(m), ptr(s), ptr(order), ptr(count), ptr(people),
-                                           ptr(cand), ptr(cost)))
+        if tracker is None:
+            _check(_lib.dc_net_assemble_people(self._h, C.byref(q), e.shape[0], ptr(e), ptr(m), ptr(s), ptr(order), ptr(count), ptr(people),
+                                               ptr(cand), ptr(cost)))
+        else:
+            ids, place = np.full((n, p), -1, np.int64), np.full((n, p), -1, np.int32)
+            _check(_lib.dc_net_track_people(self._h, _tracker_handle(tracker), C.byref(q), e.shape[0], ptr(e), ptr(m), ptr(s), ptr(order),
+                                            ptr(count), ptr(people), ptr(cand), ptr(cost), ptr(ids), ptr(place)))
         out = []
         for b in range(n):
             d = {"people": people[b, :count[b]].copy(), "cand": cand[b, :count[b]].copy()}
             if return_cost:
                 d["cost"] = cost[b]
+            if tracker is not None:
+                d["ids"], d["place"] = ids[b, :count[b]].copy(), place[b, :count[b]].copy()
             out.append(d)
         return out
 
@@ -1664,6 +1778,21 @@ class NetGroup(object):
         are fused on member `base`'s grid (`fuse_maps`), then the candidates, the pair costs and the greedy assembly run on them at
         scales[base], all on the device with no host round trip in between.  The other arguments and the result are Net.assemble_people's.
         mirror / image_width / joint_mirror: as `fuse_maps`, with `edges` as the regression edges (dc_group_assemble_people_mirrored)."""
+        return self._assemble_people(None, scales, base, threshold, radius, max_det, edges, mean, std, max_cost, seed_threshold, max_people,
+                                     min_joints, joint_order, return_cost, mirror, image_width, joint_mirror)
+
+    def track_people(self, tracker, scales, base=0, threshold=0.1, radius=1, max_det=16, edges=None, mean=None, std=None, max_cost=32.0,
+                     seed_threshold=0.5, max_people=32, min_joints=1, joint_order=None, return_cost=False, mirror=None, image_width=None,
+                     joint_mirror=None):
+        """`assemble_people` with the identities of a `caffe.Tracker` (dc_group_track_people), plain or mirrored: the tracker's update
+        runs on the device behind the assembly of the fused maps.  The arguments and the result are `assemble_people`'s, unchanged,
+        plus "ids" and "place" per image as `Net.track_people` gives them."""
+        _tracker_handle(tracker)
+        return self._assemble_people(tracker, scales, base, threshold, radius, max_det, edges, mean, std, max_cost, seed_threshold, max_people,
+                                     min_joints, joint_order, return_cost, mirror, image_width, joint_mirror)
+
+    def _assemble_people(self, tracker, scales, base, threshold, radius, max_det, edges, mean, std, max_cost, seed_threshold, max_people,
+                         min_joints, joint_order, return_cost, mirror, image_width, joint_mirror):
         if edges is None:
             raise ValueError("assemble_people needs the regression edges (deepcut_tools.read_pair_stats)")
         sc, base = self._scales(scales, base)
@@ -1679,13 +1808,20 @@ class NetGroup(object):
         cost = np.zeros((n, j, j, md, md), np.float64) if return_cost else None
         ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
         fm, _keep = self._mirror(mirror, image_width, joint_mirror, e)
-        _check(_lib.dc_group_assemble_people_mirrored(self._h, ptr(sc), base, fm, C.byref(q), e.shape[0], ptr(e), ptr(m), ptr(s), ptr(order),
-                                                      ptr(count), ptr(people), ptr(cand), ptr(cost)))
+        if tracker is None:
+            _check(_lib.dc_group_assemble_people_mirrored(self._h, ptr(sc), base, fm, C.byref(q), e.shape[0], ptr(e), ptr(m), ptr(s), ptr(order),
+                                                          ptr(count), ptr(people), ptr(cand), ptr(cost)))
+        else:
+            ids, place = np.full((n, p), -1, np.int64), np.full((n, p), -1, np.int32)
+            _check(_lib.dc_group_track_people(self._h, _tracker_handle(tracker), ptr(sc), base, fm, C.byref(q), e.shape[0], ptr(e), ptr(m),
+                                              ptr(s), ptr(order), ptr(count), ptr(people), ptr(cand), ptr(cost), ptr(ids), ptr(place)))
         out = []
         for b in range(n):
             d = {"people": people[b, :count[b]].copy(), "cand": cand[b, :count[b]].copy()}
             if return_cost:
                 d["cost"] = cost[b]
+            if tracker is not None:
+                d["ids"], d["place"] = ids[b, :count[b]].copy(), place[b, :count[b]].copy()
             out.append(d)
         return out
 

@@ -83,6 +83,35 @@ def estimate_people(image, model_def, model_bin, stats, scale=1.0, net=None, sca
     forward (the flip is part of the device pre-processing) and ONE `NetGroup.assemble_people`.  joint_mirror: the joint every joint
     becomes in the mirror (MIRROR_MPII14 by default: the caller's to override for another joint order); `stats` must hold, for every edge
     (a, c), the edge (joint_mirror[a], joint_mirror[c]).  The base stays a plain member: None = the plain scale nearest 1.0."""
+    return _people_of_image(None, image, model_def, model_bin, stats, scale, net, scales, base, flip, joint_mirror, sparse, assembly)["people"]
+
+
+def track_people(frames, model_def, model_bin, stats, tracker=None, **kw):
+    """`estimate_people` over the frames of a video, with identities: a generator over an iterable of images (HxWx3 BGR uint8) or
+    `caffe.Frame`s that yields, per frame, (people float64 [m, J, 3], ids int64 [m]) — the same person keeps their id from frame to
+    frame, -1 marks a person no track place was free for.  kw: what `estimate_people` takes (scale / scales / base / flip / joint_mirror /
+    sparse / net / the assembly arguments); every frame runs as `estimate_people` runs it, except that the last call is
+    `Net.track_people` / `NetGroup.track_people`: the association runs on the device behind the assembly, the people it returns are
+    `estimate_people`'s.  tracker: a `caffe.Tracker` of one slot or more (slot 0 is used); None makes one with the defaults, which are
+    PLACEHOLDERS, not tuned on real video.  PARITY UNPINNED BY THE REFERENCE: the tracking rule is this project's own
+    (include/deepcut_hip.h, dc_tracker_update)."""
+    args = dict(scale=1.0, net=None, scales=None, base=None, flip=False, joint_mirror=MIRROR_MPII14, sparse=False)
+    for k in list(kw):
+        if k in args:
+            args[k] = kw.pop(k)
+    for image in frames:
+        if tracker is None:
+            import caffe as _caffe
+
+            tracker = _caffe.Tracker(n_joints=len(MIRROR_MPII14))
+        d = _people_of_image(tracker, image, model_def, model_bin, stats, args["scale"], args["net"], args["scales"], args["base"], args["flip"],
+                             args["joint_mirror"], args["sparse"], kw)
+        yield d["people"], d["ids"]
+
+
+def _people_of_image(tracker, image, model_def, model_bin, stats, scale, net, scales, base, flip, joint_mirror, sparse, assembly):
+    """The body `estimate_people` and `track_people` share -> the dict of the one image: the forward, then `assemble_people` (tracker
+    None) or `track_people` of the net or of the group."""
     if scales is not None and float(scale) != 1.0:
         raise ValueError("estimate_people takes scale (one forward) or scales (a pyramid), not both: scale=%r, scales=%r" % (scale, scales))
     if sparse and (scales is not None or flip):
@@ -128,10 +157,11 @@ def estimate_people(image, model_def, model_bin, stats, scale=1.0, net=None, sca
             if sorted(m.wanted_outputs) != sorted(net.wanted_outputs):
                 m.set_outputs(None)
         grp.forward_images(image, scales, want=(), pose=False, mirror=mirrored.get("mirror"))
-        return grp.assemble_people(scales, _base_scale(scales) if base is None else int(base), edges=edges, mean=mean, std=std,
-                                   **dict(assembly, **mirrored))[0]["people"]
+        last = grp.assemble_people if tracker is None else (lambda *a, **k: grp.track_people(tracker, *a, **k))
+        return last(scales, _base_scale(scales) if base is None else int(base), edges=edges, mean=mean, std=std, **dict(assembly, **mirrored))[0]
     net.forward_images(image, scale, want=(), pose=False)
-    return net.assemble_people(scale=scale, edges=edges, mean=mean, std=std, **assembly)[0]["people"]
+    last = net.assemble_people if tracker is None else (lambda **k: net.track_people(tracker, **k))
+    return last(scale=scale, edges=edges, mean=mean, std=std, **assembly)[0]
 
 
 def people_boxes(people, image_shape, margin):

@@ -751,6 +751,75 @@ int dc_group_stats(dc_group* group, long long* out, int n);
 /* algorithmic FLOPs of the last grouped forward (the members' dc_net_flops summed)                                          */
 int dc_group_flops(dc_group* group, double* out);
 
+/* ---- tracking: the same person across the frames of a video, identities kept on the device --------------------------------------
+ * PARITY UNPINNED BY THE REFERENCE: the reference repository stops at the maps and has no tracker.  As with the assembly rule of
+ * dc_net_assemble_people, the rule below is this project's own; tests/track_ref.py restates it in float64 NumPy.
+ *
+ * A tracker has S slots.  A slot is one independent sequence: image b of a call updates slot b.  Each slot has T track places and a
+ * counter next_id that starts at 0.  A live track holds: id; pose[J][3] = x, y, score in image pixels (a joint is HELD when its score
+ * > 0); vel[J][2]; misses; hits.  An update of a slot with the people[n][J][3] of a frame (n <= P <= 256) does the following, all
+ * arithmetic in double, sums over joints ascending:
+ *  1. Track size.  s_i = max(min_size, max(x extent, y extent) over the held joints of pose_i); one held joint has extent 0.
+ *  2. Predicted joints.  pred_i[j] = pose_i[j] + (motion == 1 ? vel_i[j] * (misses_i + 1) : 0).
+ *  3. Distance.  Over the n_c joints held by both track i and person q:
+ *         D[i][q] = (sum_j ((pred_x - q_x)^2 + (pred_y - q_y)^2) / (s_i^2 * sigma_j^2)) / n_c,
+ *     +inf when n_c < min_common, when place i is free, or when q >= n.
+ *  4. Greedy matching.  While an unmatched live track and an unmatched person with D <= max_dist remain, the pair with the smallest D
+ *     is matched; ties go to the lower place i, then the lower q.
+ *  5. Matched track.  vel[j] = (person - old pose) / (misses + 1) for the joints held by both the old pose and the person, 0 elsewhere;
+ *     pose = the person's, whole (a joint the person lacks becomes not held); misses = 0; hits += 1.
+ *  6. Unmatched live track.  misses += 1; pose and velocity stay; the track is freed when misses > max_misses.
+ *  7. Births.  The unmatched people, q ascending, take the free places, place index ascending (places freed in step 6 of this update
+ *     count as free): id = next_id++, hits = 1, misses = 0, vel = 0.  A person for whom no place is free gets id -1 and is not
+ *     tracked.  Ids are never reused within a slot.
+ * Deterministic: the same calls give the same ids.  dc_tracker_reset(slot) frees the slot's tracks and sets next_id back to 0.
+ *
+ * dc_tracker_create: slots 1..64; max_tracks (T) 1..256; n_joints (J) 1..32; sigma[J] NULL (all 1.0) or each finite and > 0;
+ *     max_misses >= 0; min_common 1..J; max_dist finite and >= 0; min_size finite and > 0; motion 0 or 1.  Anything else is DC_EINVAL
+ *     naming the parameter.  Creation needs no device: the device buffer is allocated, zeroed and bound to the calling thread's device
+ *     (the net's, in the chained entries) at the first update.  THE DEFAULTS THE PYTHON LAYER CHOOSES FOR max_misses, min_common,
+ *     max_dist, min_size AND sigma ARE PLACEHOLDERS, NOT TUNED ON REAL VIDEO: override them.
+ * dc_tracker_update: host poses — n_people[nb], people[nb][P][J][3] (entries of q >= n_people[b] are not read) — are uploaded and
+ *     image b updates slot b in one launch (one workgroup per image).  This is how top-down poses of dc_net_forward_boxes get tracked.
+ *     Outputs: ids[nb][P] (long long; -1 for q >= n and for an untracked person), place[nb][P] (int, the track place; -1 likewise; may
+ *     be NULL), dist[nb][T][P] (the D of step 3; may be NULL: diagnostics and tests).
+ * dc_net_track_people / dc_group_track_people: dc_net_assemble_people / dc_group_assemble_people[_mirrored] (fm may be NULL) with the
+ *     tracker's launch behind the assembly's on the same stream, reading the people where the assembly left them on the device: one more
+ *     launch, no more transfer than the ids.  They return what the assembly entries return, unchanged, plus ids / place
+ *     [n][max_people].  The sparse pairwise path (DC_OPT_SPARSE_PAIRWISE) is covered.
+ * dc_tracker_state: a slot's tracks, e.g. to see where occluded people were last seen: ids[T], misses[T], hits[T], poses[T][J][3]
+ *     (any may be NULL); free places give -1 / 0 / 0 / zeros.  Before the first update every place is free.
+ * Order: every call on a tracker is synchronous and holds the library's runtime lock from its launch to its completion, so updates
+ *     apply in host call order whichever net, group or stream they ran behind.
+ * Errors, before any device work: DC_EINVAL naming the parameter for nb outside [1, slots], P (max_people) outside [1, 256], a
+ *     n_people[b] outside [0, P], a slot outside [0, slots) (dc_tracker_reset: -1 = all); DC_ESHAPE for a tracker whose n_joints is not
+ *     the net's; whatever the assembly entry refuses.  Then DC_ENOCPU for an update in CPU mode (there is no CPU path), DC_EDEVICE for
+ *     a tracker bound to another device than the calling thread's (the net's).                                                        */
+typedef struct dc_tracker dc_tracker;
+typedef struct dc_tracker_params {
+  int    slots;          /* S, 1..64 */
+  int    max_tracks;     /* T, 1..256 */
+  int    n_joints;       /* J, 1..32 */
+  const double* sigma;   /* [J] per-joint tolerance, NULL = all 1.0 */
+  int    max_misses;     /* a track is freed after more than this many updates in a row without a match */
+  int    min_common;     /* joints a track and a person must both hold to be compared */
+  double max_dist;       /* a match needs D <= max_dist */
+  double min_size;       /* lower bound of the track size s_i, image pixels */
+  int    motion;         /* 0: compare with the last pose; 1: with the pose moved on by its velocity */
+} dc_tracker_params;
+int dc_tracker_create(const dc_tracker_params* p, dc_tracker** out);
+int dc_tracker_destroy(dc_tracker* tracker);
+int dc_tracker_reset(dc_tracker* tracker, int slot /* -1: all */);
+int dc_tracker_update(dc_tracker* tracker, int nb, int P, const int* n_people, const double* people, long long* ids, int* place,
+                      double* dist);
+int dc_tracker_state(dc_tracker* tracker, int slot, long long* ids, int* misses, int* hits, double* poses);
+int dc_net_track_people(dc_net* net, dc_tracker* tracker, const dc_assemble_params* p, int n_edges, const int* edges, const double* mean,
+                        const double* stdev, const int* joint_order, int* n_people, double* people, int* cand, double* cost,
+                        long long* ids, int* place);
+int dc_group_track_people(dc_group* group, dc_tracker* tracker, const double* scales, int base, const dc_fuse_mirror* fm /* may be NULL */,
+                          const dc_assemble_params* p, int n_edges, const int* edges, const double* mean, const double* stdev,
+                          const int* joint_order, int* n_people, double* people, int* cand, double* cost, long long* ids, int* place);
+
 /* ---- in-process multi-GPU forward (SURVEY 8(b)'s dc_forward_batch) -------------------------------------------------------
  * A communicator over `nexec` executors: executor k runs on devices[k] (NULL: k modulo the visible devices) on a host thread of its
  * own (mode and device are per thread, src/caffe/common.cpp:13-20).  transport: how the maps travel to the root executor's device —
