@@ -903,11 +903,15 @@ int dc_tracker_reset(dc_tracker* tracker, int slot) {
 }
 int dc_tracker_update(dc_tracker* tracker, int nb, int P, const int* n_people, const double* people, long long* ids, int* place,
                       double* dist) {
+  return dc_tracker_update_slots(tracker, nb, P, nullptr, n_people, people, ids, place, dist);
+}
+int dc_tracker_update_slots(dc_tracker* tracker, int nb, int P, const int* slot_of, const int* n_people, const double* people,
+                            long long* ids, int* place, double* dist) {
   REQUIRE(tracker);
   REQUIRE(n_people);
   REQUIRE(people);
   REQUIRE(ids);
-  return guard([&] { TR(tracker)->update(nb, P, n_people, people, ids, place, dist); });
+  return guard([&] { TR(tracker)->update(nb, P, slot_of, n_people, people, ids, place, dist); });
 }
 int dc_tracker_state(dc_tracker* tracker, int slot, long long* ids, int* misses, int* hits, double* poses) {
   REQUIRE(tracker);
@@ -916,6 +920,11 @@ int dc_tracker_state(dc_tracker* tracker, int slot, long long* ids, int* misses,
 int dc_net_track_people(dc_net* net, dc_tracker* tracker, const dc_assemble_params* p, int n_edges, const int* edges, const double* mean,
                         const double* stdev, const int* joint_order, int* n_people, double* people, int* cand, double* cost,
                         long long* ids, int* place) {
+  return dc_net_track_people_slots(net, tracker, nullptr, p, n_edges, edges, mean, stdev, joint_order, n_people, people, cand, cost, ids, place);
+}
+int dc_net_track_people_slots(dc_net* net, dc_tracker* tracker, const int* slot_of, const dc_assemble_params* p, int n_edges,
+                              const int* edges, const double* mean, const double* stdev, const int* joint_order, int* n_people,
+                              double* people, int* cand, double* cost, long long* ids, int* place) {
   REQUIRE(net);
   REQUIRE(tracker);
   REQUIRE(p);
@@ -925,12 +934,19 @@ int dc_net_track_people(dc_net* net, dc_tracker* tracker, const dc_assemble_para
   if (n_edges > 0) REQUIRE(edges);
   return guard([&] {
     Net::AssembleParams q{p->scale, p->threshold, p->radius, p->max_det, p->max_cost, p->seed_threshold, p->max_people, p->min_joints};
-    N(net)->assemble_people(q, n_edges, edges, mean, stdev, joint_order, n_people, people, cand, cost, TR(tracker), ids, place);
+    N(net)->assemble_people(q, n_edges, edges, mean, stdev, joint_order, n_people, people, cand, cost, TR(tracker), ids, place, slot_of);
   });
 }
 int dc_group_track_people(dc_group* group, dc_tracker* tracker, const double* scales, int base, const dc_fuse_mirror* fm,
                           const dc_assemble_params* p, int n_edges, const int* edges, const double* mean, const double* stdev,
                           const int* joint_order, int* n_people, double* people, int* cand, double* cost, long long* ids, int* place) {
+  return dc_group_track_people_slots(group, tracker, nullptr, scales, base, fm, p, n_edges, edges, mean, stdev, joint_order, n_people, people,
+                                     cand, cost, ids, place);
+}
+int dc_group_track_people_slots(dc_group* group, dc_tracker* tracker, const int* slot_of, const double* scales, int base,
+                                const dc_fuse_mirror* fm, const dc_assemble_params* p, int n_edges, const int* edges, const double* mean,
+                                const double* stdev, const int* joint_order, int* n_people, double* people, int* cand, double* cost,
+                                long long* ids, int* place) {
   REQUIRE(group);
   REQUIRE(tracker);
   REQUIRE(p);
@@ -942,7 +958,25 @@ int dc_group_track_people(dc_group* group, dc_tracker* tracker, const double* sc
     Net::AssembleParams q{p->scale, p->threshold, p->radius, p->max_det, p->max_cost, p->seed_threshold, p->max_people, p->min_joints};
     NetGroup::FuseMirror m;
     G(group)->assemble_people(scales, base, q, n_edges, edges, mean, stdev, joint_order, n_people, people, cand, cost, mirror_args(fm, m),
-                              TR(tracker), ids, place);
+                              TR(tracker), ids, place, slot_of);
+  });
+}
+int dc_net_track_frames_async(dc_net* net, dc_tracker* tracker, const dc_frame* frames, const unsigned char* images, int n, int height,
+                              int width, double scale, int is_device, const int* slot_of, const dc_assemble_params* p, int n_edges,
+                              const int* edges, const double* mean, const double* stdev, const int* joint_order, int* n_people,
+                              double* people, int* cand, long long* ids, int* place) {
+  REQUIRE(net);
+  if (!frames) REQUIRE(images);
+  if (n <= 0 || height <= 0 || width <= 0) return fail(DC_EINVAL, "n, height and width must be positive");
+  if (!(scale > 0)) return fail(DC_EINVAL, "scale must be positive");
+  REQUIRE(p);
+  REQUIRE(n_people);
+  REQUIRE(people);
+  if (n_edges > 0) REQUIRE(edges);
+  return guard([&] {
+    Net::AssembleParams q{p->scale, p->threshold, p->radius, p->max_det, p->max_cost, p->seed_threshold, p->max_people, p->min_joints};
+    N(net)->track_frames_async(tracker ? TR(tracker) : nullptr, frames, images, n, height, width, scale, is_device != 0, slot_of, q, n_edges,
+                               edges, mean, stdev, joint_order, n_people, people, cand, ids, place);
   });
 }
 // single-person and box poses from the fused maps (net_group.cpp decode_pose / decode_boxes)

@@ -442,11 +442,20 @@ DC_HOST_DEVICE inline TrackSlot track_slot(unsigned char* block, int T, int J) {
   s.hits = s.misses + T;
   return s;
 }
-// one workgroup per image b, which updates the slot whose block is state + b * slot_stride (a multiple of 16): reads n_people[b]
-// (clamped to [0, P]) and people [NB][P][J][3] from device memory, writes the state back in place, dist[b * T * kPeopleMaxPeople + i * P
-// + q] (scratch the caller keeps: the matching reads it back), ids [NB][P] and place [NB][P].  sig2 [J] = sigma_j^2.
-int launch_track(int NB, int P, const TrackParams& p, const double* sig2, unsigned char* state, size_t slot_stride, double* dist,
-                 const int* n_people, const double* people, long long* ids, int* place, void* stream);
+// Which slot every image of a launch updates, passed to the kernel BY VALUE (64 bytes: nothing to upload and nothing that has to outlive
+// the call): byte b of the words = slot of image b, b < 64.
+constexpr int kTrackMaxImages = 64;
+struct TrackSlotMap {
+  unsigned int w[kTrackMaxImages / 4];
+};
+inline void track_slot_map_set(TrackSlotMap& m, int b, int slot) { m.w[b >> 2] |= (unsigned)(slot & 0xff) << ((b & 3) * 8); }
+// one workgroup per slot s (S of them), whose block is state + s * slot_stride (a multiple of 16).  It applies the images b = 0 .. NB - 1
+// with map[b] == s in ascending b, each on the state the one before left; a slot no image names is not touched.  Image b: reads
+// n_people[b] (clamped to [0, P]) and people [NB][P][J][3] from device memory, writes the state back in place, dist[b * T *
+// kPeopleMaxPeople + i * P + q] (scratch the caller keeps: the matching reads it back), ids [NB][P] and place [NB][P].  sig2 [J] =
+// sigma_j^2.  NB <= kTrackMaxImages, every map[b] in [0, S).
+int launch_track(int S, int NB, int P, const TrackParams& p, const double* sig2, unsigned char* state, size_t slot_stride, double* dist,
+                 const int* n_people, const double* people, long long* ids, int* place, const TrackSlotMap& map, void* stream);
 
 // The pairwise head at a list of cells (sparse_head.hip; the rule: include/deepcut_hip.h, dc_net_pairwise_at).  x3 / x5: the NHWC inputs
 // of the head's 1x1 skip convolution ([NB][H][W], pitch cp3, K3 channels) and of its stride-2 3x3 deconvolution ([NB][h5][w5], pitch cp5,

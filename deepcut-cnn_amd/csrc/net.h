@@ -354,10 +354,18 @@ struct Net {
     int max_people, min_joints;
   };
   // tracker (may be null; dc_net_track_people): its launch runs behind the assembly's on the people left on the device -> ids, place
-  // [NB][max_people]; everything else is computed and returned exactly as without it
+  // [NB][max_people]; everything else is computed and returned exactly as without it.  slot_of (may be null: image b updates slot b):
+  // [NB], the slot every image updates (dc_net_track_people_slots)
   void assemble_people(const AssembleParams& p, int n_edges, const int* edges, const double* mean, const double* stdev, const int* joint_order,
                        int* n_people, double* people, int* cand, double* cost, Tracker* tracker = nullptr, long long* ids = nullptr,
-                       int* place = nullptr);
+                       int* place = nullptr, const int* slot_of = nullptr);
+  // The whole video chain on the net's own stream with no host wait (dc_net_track_frames_async): upload of host planes, pre-processing,
+  // the plan, candidates, (sparse head,) pair costs, assembly, the tracker's launch (tracker may be null: people without ids) and the
+  // downloads.  Every argument check runs before any device work, in the order forward_images / assemble_people / Tracker::check_call
+  // make them; everything small is copied before the return; frame planes and output arrays stay the caller's until synchronize().
+  void track_frames_async(Tracker* tracker, const dc_frame* frames, const unsigned char* bgr, int n, int h, int w, double scale, bool is_device,
+                          const int* slot_of, const AssembleParams& p, int n_edges, const int* edges, const double* mean, const double* stdev,
+                          const int* joint_order, int* n_people, double* people, int* cand, long long* ids, int* place);
   // front half of forward_images: the uint8 pixels -> the network's NHWC input image, enqueued on s (the plan of the canvas
   // shape is active afterwards); returns the canvas height / width
   // mirror: the images are read flipped left to right (ImagePrepParams::mirror; NetGroup::forward_images hands it down)
@@ -419,11 +427,26 @@ struct Net {
   // between (may be empty): called with stage A's device outputs (counts, dets) after its launch and before stage B's — the sparse
   // pairwise head fills N's cells there.  after (may be empty): called with stage C's device outputs (n_people, people) behind its
   // launch and before the downloads — the tracker's launch goes there
+  // keep (may be null: the table and the statistics go into the scratch with every call): where they stay on the device from call to call,
+  // uploaded only when their content differs from what is there, from a host copy that outlives the upload.  wait = false: nothing is
+  // waited for — the results are in the host arrays once `stream` has been, and nothing of the caller's small arguments is read after
+  // the return (keep is needed then)
+  struct AssembleTables {
+    unsigned char* dev = nullptr;
+    size_t cap = 0;
+    std::vector<unsigned char> host;  // lookup table and joint order (ints), then mean and standard deviation (doubles)
+    void* stream = nullptr;           // the stream the upload ran on
+  };
   static void assemble_maps(const MapRef& P, const MapRef& L, const MapRef& N, const AssembleParams& q, const std::vector<int>& table,
                             int n_edges, const double* mean, const double* stdev, const std::function<void*(size_t)>& scratch, void* stream,
                             int* n_people, double* people, int* cand, double* cost,
                             const std::function<void(const int*, const double*)>& between = nullptr,
-                            const std::function<void(const int*, const double*)>& after = nullptr);
+                            const std::function<void(const int*, const double*)>& after = nullptr, AssembleTables* keep = nullptr,
+                            bool wait = true);
+  AssembleTables asm_tables_;
+  void assemble_last(const AssembleParams& q, const std::vector<int>& table, int n_edges, const double* mean, const double* stdev,
+                     int* n_people, double* people, int* cand, double* cost, const std::function<void(const int*, const double*)>& after,
+                     bool wait);
   // DC_OPT_SPARSE_PAIRWISE (sparse_pairwise.cpp)
   struct PairHead {
     int elt = -1, conv = -1, crop = -1, deconv = -1;  // layer indices: the Eltwise SUM, its 1x1 Convolution, its Crop and the Crop's Deconvolution
@@ -469,18 +492,27 @@ struct Net {
 };
 
 // ---- tracking people from frame to frame (track.cpp / track.hip; the rule: include/deepcut_hip.h, dc_tracker_update) ---------------
-// The tracks of `slots` independent sequences in ONE device allocation, made, zeroed and bound to a device at the first update:
-//   slot blocks (kernels.h TrackSlot) | sigma^2 [J] | distances [slots][T][256] | staging of host poses: n_people [slots], people
-//   [slots][256][J][3] | outputs: ids [slots][256], place [slots][256]
-// Every call holds the runtime lock from its launch until the stream it ran on has been waited for, so the updates of a tracker apply
-// in host call order whichever stream they ran on.
+// The tracks of `slots` independent sequences in one device allocation, made, zeroed and bound to a device at the first update:
+//   slot blocks (kernels.h TrackSlot) | sigma^2 [J]
+// and the per-image scratch in a second one, sized for the largest image count of a call so far (at least `slots`):
+//   distances [cap][T][256] | staging of host poses: n_people [cap], people [cap][256][J][3] | outputs: ids [cap][256], place [cap][256]
+// It grows on demand; the contents do not survive that and need not: every call fills what it reads.
+// Order: the tracker holds an event.  Every enqueue of an update — under the runtime lock, which is held for the enqueue only — makes its
+// stream wait for the event of the update enqueued before it (hipStreamWaitEvent: no host wait) and records the event again behind its
+// own launch and the copies out of the shared scratch.  Updates therefore apply in the order of the host calls that enqueued them,
+// whichever net, clone or stream carried them, and an asynchronous entry (Net::track_frames_async) need not wait for anything.  The
+// synchronous calls (update, state, reset, the destructor, the synchronous track_people entries) wait for the event on the host first.
 struct Tracker {
   TrackParams tp{};
   int slots = 0;
   std::vector<double> sig2;
   int device = -1;  // bound at the first update
   unsigned char* dev = nullptr;
-  size_t slot_stride = 0, off_sig = 0, off_dist = 0, off_np = 0, off_ppl = 0, off_ids = 0, off_place = 0, total = 0;
+  size_t slot_stride = 0, off_sig = 0, total = 0;
+  void* done = nullptr;              // hipEvent_t: behind the last update enqueued (made with the device buffer)
+  unsigned char* img_dev = nullptr;  // the per-image scratch ...
+  int img_cap = 0;                   // ... and how many images it holds
+  size_t off_dist = 0, off_np = 0, off_ppl = 0, off_ids = 0, off_place = 0;
   // every argument error is DC_EINVAL naming the parameter; no device is needed
   static Tracker* create(int slots, int max_tracks, int n_joints, const double* sigma, int max_misses, int min_common, double max_dist,
                          double min_size, int motion);
@@ -488,12 +520,18 @@ struct Tracker {
   Tracker() = default;
   Tracker(const Tracker&) = delete;
   Tracker& operator=(const Tracker&) = delete;
-  // host only: nb images of at most P people with J joints fit this tracker (DC_EINVAL / DC_ESHAPE naming what does not)
-  void check_call(const char* who, int nb, int P, int J) const;
-  // the caller holds the runtime lock and keeps it until `stream` has been waited for; `dev` is the current device.  Binds / checks
-  // the device, allocates at the first use, enqueues the launch on d_np / d_ppl and the downloads of ids / place / dist (any null).
-  void enqueue(int on_device, int nb, int P, const int* d_np, const double* d_ppl, long long* ids, int* place, double* dist, void* stream);
-  void update(int nb, int P, const int* n_people, const double* people, long long* ids, int* place, double* dist);
+  // host only: nb images of at most P people with J joints fit this tracker (DC_EINVAL / DC_ESHAPE naming what does not).  slot_of
+  // null: image b updates slot b, nb <= slots; else nb <= 64 images, image b updates slot slot_of[b], each in [0, slots)
+  void check_call(const char* who, int nb, int P, int J, const int* slot_of = nullptr) const;
+  // host wait for the last update enqueued (nothing enqueued yet: returns at once); the caller is on the tracker's device
+  void wait_done();
+  // the caller holds the runtime lock; `on_device` is the current device.  Binds / checks the device, allocates at the first use and
+  // makes room for nb images, waiting for the tracker's work in flight before the scratch is replaced
+  void prepare(int on_device, int nb, void* stream);
+  // ... and, after prepare, still under the lock: `stream` waits for the update before, then the launch on d_np / d_ppl (slot_of checked,
+  // or null) and the downloads of ids / place / dist (any null), then the event is recorded.  No host wait.
+  void enqueue(int nb, int P, const int* slot_of, const int* d_np, const double* d_ppl, long long* ids, int* place, double* dist, void* stream);
+  void update(int nb, int P, const int* slot_of, const int* n_people, const double* people, long long* ids, int* place, double* dist);
   void reset(int slot);  // -1: all
   void state(int slot, long long* ids, int* misses, int* hits, double* poses);
 };
@@ -600,7 +638,8 @@ struct NetGroup {
   // fusion of all three maps, then Net::assemble_people's three launches on them at scales[base] (p.scale is not read)
   void assemble_people(const double* scales, int base, const Net::AssembleParams& p, int n_edges, const int* edges, const double* mean,
                        const double* stdev, const int* joint_order, int* n_people, double* people, int* cand, double* cost,
-                       const FuseMirror* fm = nullptr, Tracker* tracker = nullptr, long long* ids = nullptr, int* place = nullptr);
+                       const FuseMirror* fm = nullptr, Tracker* tracker = nullptr, long long* ids = nullptr, int* place = nullptr,
+                       const int* slot_of = nullptr);
   // Single-person pose from the fused maps (dc_group_decode_pose): prob and loc_pred fused as detect_parts fuses them, then
   // launch_pose_decode on the fused float32 views at scales[base] -> pose [NB][5][J], host or device, stream as fuse_maps
   void decode_pose(const double* scales, int base, double* pose, bool is_device, void* user_stream, const FuseMirror* fm = nullptr);

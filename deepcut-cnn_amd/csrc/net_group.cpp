@@ -1195,7 +1195,7 @@ void NetGroup::detect_parts(const double* scales, int base, float thr, int radiu
 
 void NetGroup::assemble_people(const double* scales, int base, const Net::AssembleParams& p, int n_edges, const int* edges, const double* mean,
                                const double* stdev, const int* joint_order, int* n_people, double* people, int* cand, double* cost,
-                               const FuseMirror* fm_in, Tracker* tracker, long long* ids, int* place) {
+                               const FuseMirror* fm_in, Tracker* tracker, long long* ids, int* place, const int* slot_of) {
   const bool use[3] = {true, true, true};
   int C[3], NB;
   check_scales("assemble_people", scales, base);  // first: the assembly runs at scales[base]
@@ -1209,7 +1209,7 @@ void NetGroup::assemble_people(const double* scales, int base, const Net::Assemb
   const std::vector<int> table = Net::check_assemble_graph(q, pshape[1], n_edges, edges, mean, stdev, joint_order);
   check_fuse("assemble_people", scales, base, use, n_edges, mean, stdev, C, NB);
   const MirrorPlan mp = check_mirror("assemble_people", fm_in, base, use, n_edges, C);
-  if (tracker) tracker->check_call("track_people", NB, q.max_people, pshape[1]);
+  if (tracker) tracker->check_call("track_people", NB, q.max_people, pshape[1], slot_of);
   if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "assemble_people() in CPU mode");
   nets[0]->ensure_device();
   void* s = stream();
@@ -1220,7 +1220,9 @@ void NetGroup::assemble_people(const double* scales, int base, const Net::Assemb
   if (tracker)
     after = [&](const int* d_np, const double* d_ppl) {
       order.lock();
-      tracker->enqueue(nets[0]->device, NB, q.max_people, d_np, d_ppl, ids, place, nullptr, s);
+      tracker->prepare(nets[0]->device, NB, s);
+      tracker->wait_done();
+      tracker->enqueue(NB, q.max_people, slot_of, d_np, d_ppl, ids, place, nullptr, s);
     };
   Net::assemble_maps(fm.map[0], fm.map[1], fm.map[2], q, table, n_edges, mean, stdev, [this](size_t bytes) { return people_scratch_.get(bytes); }, s,
                      n_people, people, cand, cost, nullptr, after);

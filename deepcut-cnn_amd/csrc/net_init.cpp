@@ -107,6 +107,7 @@ Net::~Net() {
   dev_free(frame_dev_);
   dev_free(box_dev_);
   dev_free(sparse_dev_);
+  dev_free(asm_tables_.dev);
 }
 
 Net* Net::create(const std::string& text, int phase, const Net* clone_of) {

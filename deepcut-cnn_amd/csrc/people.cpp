@@ -148,44 +148,83 @@ std::vector<int> Net::check_assemble_graph(const AssembleParams& q, int J, int n
 
 void Net::assemble_people(const AssembleParams& q, int n_edges, const int* edges, const double* mean, const double* stdev,
                           const int* joint_order, int* n_people, double* people, int* cand, double* cost, Tracker* tracker, long long* ids,
-                          int* place) {
+                          int* place, const int* slot_of) {
   check_assemble_params(q);
   auto ip = blob_index.find("prob");
   if (ip == blob_index.end()) throw DcError(DC_EINVAL, "net has no 'prob' blob");
   const std::vector<int>& pshape = blobs[ip->second]->st->shape;
   if (pshape.size() != 4) throw DcError(DC_ESHAPE, "'prob' is not a 4-D map");
   const std::vector<int> table = check_assemble_graph(q, pshape[1], n_edges, edges, mean, stdev, joint_order);
-  if (tracker) tracker->check_call("track_people", pshape[0], q.max_people, pshape[1]);
+  if (tracker) tracker->check_call("track_people", pshape[0], q.max_people, pshape[1], slot_of);
   // (the arguments above are refused with or without a device; from here on the device is needed)
   if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "assemble_people() in CPU mode");
   ensure_device();
-  const MapRef P = map_ref("prob"), L = map_ref("loc_pred");
+  const MapRef P = map_ref("prob");
   // the tracker's launch behind stage C: the runtime lock is taken there and kept until assemble_maps has waited for the stream
   std::unique_lock<std::recursive_mutex> order(runtime_mu(), std::defer_lock);
   std::function<void(const int*, const double*)> after;
   if (tracker)
     after = [&](const int* d_np, const double* d_ppl) {
       order.lock();
-      tracker->enqueue(device, P.NB, q.max_people, d_np, d_ppl, ids, place, nullptr, stream);
+      tracker->prepare(device, P.NB, stream);
+      tracker->wait_done();
+      tracker->enqueue(P.NB, q.max_people, slot_of, d_np, d_ppl, ids, place, nullptr, stream);
     };
+  assemble_last(q, table, n_edges, mean, stdev, n_people, people, cand, cost, after, true);
+}
+
+// the device half of assemble_people / track_frames_async on the maps of the net's last (enqueued) forward
+void Net::assemble_last(const AssembleParams& q, const std::vector<int>& table, int n_edges, const double* mean, const double* stdev,
+                        int* n_people, double* people, int* cand, double* cost, const std::function<void(const int*, const double*)>& after,
+                        bool wait) {
+  const MapRef P = map_ref("prob"), L = map_ref("loc_pred");
   if (sparse_pairwise && !next_in_plan()) {  // DC_OPT_SPARSE_PAIRWISE: the head at the candidates' cells, between stages A and B
     const SparseNext sn = sparse_next(P.NB * P.C * q.max_det, 0);
     assemble_maps(P, L, sn.N, q, table, n_edges, mean, stdev, [this](size_t bytes) { return scratch(bytes); }, stream, n_people, people, cand, cost,
                   [&](const int* d_cnt, const double* d_det) {
                     KCHECK(launch_sparse_head(sn.a, sn.ekind, d_cnt, d_det, P.C, q.max_det, nullptr, P.NB * P.C * q.max_det, sn.work, stream));
                   },
-                  after);
+                  after, &asm_tables_, wait);
     return;
   }
   const MapRef N = map_ref("next_pred");
   assemble_maps(P, L, N, q, table, n_edges, mean, stdev, [this](size_t bytes) { return scratch(bytes); }, stream, n_people, people, cand, cost,
-                nullptr, after);
+                nullptr, after, &asm_tables_, wait);
+}
+
+void Net::track_frames_async(Tracker* tracker, const dc_frame* frames, const unsigned char* bgr, int n, int h, int w, double scale,
+                             bool is_device, const int* slot_of, const AssembleParams& p, int n_edges, const int* edges, const double* mean,
+                             const double* stdev, const int* joint_order, int* n_people, double* people, int* cand, long long* ids,
+                             int* place) {
+  // what forward_images refuses ...
+  if (frames) check_frames("track_frames_async", frames, n, h, w);
+  // ... what assemble_people refuses (the batch of the forward to come is n; the joints do not depend on it) ...
+  check_assemble_params(p);
+  auto ip = blob_index.find("prob");
+  if (ip == blob_index.end()) throw DcError(DC_EINVAL, "net has no 'prob' blob");
+  const std::vector<int>& pshape = blobs[ip->second]->st->shape;
+  if (pshape.size() != 4) throw DcError(DC_ESHAPE, "'prob' is not a 4-D map");
+  const std::vector<int> table = check_assemble_graph(p, pshape[1], n_edges, edges, mean, stdev, joint_order);
+  // ... and what the tracker refuses
+  if (tracker) tracker->check_call("track_frames_async", n, p.max_people, pshape[1], slot_of);
+  else if (ids) throw DcError(DC_EINVAL, "track_frames_async: ids without a tracker (ids must be NULL when tracker is NULL)");
+  if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "track_frames_async() in CPU mode");
+  prep_images(bgr, n, h, w, scale, is_device, nullptr, false, frames);
+  enqueue_plan(stream);
+  std::function<void(const int*, const double*)> after;
+  if (tracker)
+    after = [&](const int* d_np, const double* d_ppl) {
+      RuntimeLock rl;  // for the enqueue only: the tracker's event keeps the order from here on
+      tracker->prepare(device, n, stream);
+      tracker->enqueue(n, p.max_people, slot_of, d_np, d_ppl, ids, place, nullptr, stream);
+    };
+  assemble_last(p, table, n_edges, mean, stdev, n_people, people, cand, nullptr, after, false);
 }
 
 void Net::assemble_maps(const MapRef& P, const MapRef& L, const MapRef& N, const AssembleParams& q, const std::vector<int>& table, int n_edges,
                         const double* mean, const double* stdev, const std::function<void*(size_t)>& scratch, void* stream, int* n_people,
                         double* people, int* cand, double* cost, const std::function<void(const int*, const double*)>& between,
-                        const std::function<void(const int*, const double*)>& after) {
+                        const std::function<void(const int*, const double*)>& after, AssembleTables* keep, bool wait) {
   const int J = P.C;
   if (L.C != 2 * P.C || L.H != P.H || L.W != P.W || L.NB != P.NB || L.es != P.es)
     throw DcError(DC_ESHAPE, "assemble_people: loc_pred must have 2 channels per joint and the score map's size");
@@ -198,6 +237,7 @@ void Net::assemble_maps(const MapRef& P, const MapRef& L, const MapRef& N, const
   const size_t cnt_b = up((size_t)lists * sizeof(int));
   const size_t spill_b = up((size_t)lists * P.H * P.W * sizeof(unsigned long long));
   const size_t det_b = up((size_t)lists * MD * 5 * sizeof(double));
+  if (!wait && !keep) throw DcError(DC_EINVAL, "assemble_people: the no-wait form needs its tables kept");
   const size_t tab_b = up(table.size() * sizeof(int));
   const size_t st_b = up((size_t)std::max(E, 1) * 4 * sizeof(double));
   const size_t cost_b = up((size_t)NB * J * J * MD * MD * sizeof(double));
@@ -205,7 +245,7 @@ void Net::assemble_maps(const MapRef& P, const MapRef& L, const MapRef& N, const
   const size_t np_b = up((size_t)NB * sizeof(int));
   const size_t ppl_b = up((size_t)NB * PP * J * 3 * sizeof(double));
   const size_t cand_b = up((size_t)NB * PP * J * sizeof(int));
-  unsigned char* base = (unsigned char*)scratch(cnt_b + spill_b + det_b + tab_b + st_b + cost_b + link_b + np_b + ppl_b + cand_b);
+  unsigned char* base = (unsigned char*)scratch(cnt_b + spill_b + det_b + (keep ? 0 : tab_b + st_b) + cost_b + link_b + np_b + ppl_b + cand_b);
   unsigned char* at = base;
   auto take = [&](size_t b) {
     unsigned char* r = at;
@@ -215,19 +255,47 @@ void Net::assemble_maps(const MapRef& P, const MapRef& L, const MapRef& N, const
   int* d_cnt = (int*)take(cnt_b);
   unsigned long long* d_spill = (unsigned long long*)take(spill_b);
   double* d_det = (double*)take(det_b);
-  int* d_tab = (int*)take(tab_b);
-  double* d_mean = (double*)take(st_b);
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<double> stats((size_t)4 * E);
+  for (int i = 0; i < 2 * E; ++i) stats[i] = mean ? mean[i] : 0.0, stats[(size_t)2 * E + i] = stdev ? stdev[i] : 1.0;
+  int* d_tab;
+  double* d_mean;
+  if (keep) {
+    std::vector<unsigned char> now(tab_b + st_b, 0);
+    std::memcpy(now.data(), table.data(), table.size() * sizeof(int));
+    if (E) std::memcpy(now.data() + tab_b, stats.data(), stats.size() * sizeof(double));
+    bool same = keep->dev && keep->stream == stream && keep->host == now;
+    if (now.size() > keep->cap) {
+      dev_free(keep->dev);
+      keep->dev = nullptr, keep->cap = 0;
+      dev_alloc((void**)&keep->dev, now.size());
+      keep->cap = now.size();
+      same = false;
+    }
+    if (!same) {
+      // rare (another graph, other statistics): what is in flight on this stream may still read the old content, and an upload from the
+      // host copy may not have read it yet — both are waited for before either is replaced
+      HIPCHECK(hipStreamSynchronize(s));
+      keep->host.swap(now);
+      HIPCHECK(hipMemcpyAsync(keep->dev, keep->host.data(), keep->host.size(), hipMemcpyHostToDevice, s));
+      keep->stream = stream;
+    }
+    d_tab = (int*)keep->dev;
+    d_mean = (double*)(keep->dev + tab_b);
+  } else {
+    d_tab = (int*)take(tab_b);
+    d_mean = (double*)take(st_b);
+  }
   double* d_std = d_mean + (size_t)2 * E;
   double* d_cost = (double*)take(cost_b);
   double* d_link = (double*)take(link_b);
   int* d_np = (int*)take(np_b);
   double* d_ppl = (double*)take(ppl_b);
   int* d_cand = (int*)take(cand_b);
-  std::vector<double> stats((size_t)4 * E);
-  for (int i = 0; i < 2 * E; ++i) stats[i] = mean ? mean[i] : 0.0, stats[(size_t)2 * E + i] = stdev ? stdev[i] : 1.0;
-  hipStream_t s = (hipStream_t)stream;
-  HIPCHECK(hipMemcpyAsync(d_tab, table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice, s));
-  if (E) HIPCHECK(hipMemcpyAsync(d_mean, stats.data(), stats.size() * sizeof(double), hipMemcpyHostToDevice, s));
+  if (!keep) {
+    HIPCHECK(hipMemcpyAsync(d_tab, table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    if (E) HIPCHECK(hipMemcpyAsync(d_mean, stats.data(), stats.size() * sizeof(double), hipMemcpyHostToDevice, s));
+  }
   KCHECK(launch_part_select(P.ptr, P.cp, P.c0, L.ptr, L.cp, L.c0, P.ek, NB, P.H, P.W, J, q.threshold, q.radius, q.scale, MD, d_spill, d_cnt,
                             d_det, stream));
   if (between) between(d_cnt, d_det);
@@ -239,7 +307,7 @@ void Net::assemble_maps(const MapRef& P, const MapRef& L, const MapRef& N, const
   HIPCHECK(hipMemcpyAsync(people, d_ppl, (size_t)NB * PP * J * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
   if (cand) HIPCHECK(hipMemcpyAsync(cand, d_cand, (size_t)NB * PP * J * sizeof(int), hipMemcpyDeviceToHost, s));
   if (cost) HIPCHECK(hipMemcpyAsync(cost, d_cost, (size_t)NB * J * J * MD * MD * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHECK(hipStreamSynchronize(s));
+  if (wait) HIPCHECK(hipStreamSynchronize(s));
 }
 
 }  // namespace dc

@@ -41,56 +41,96 @@ Tracker* Tracker::create(int slots, int max_tracks, int n_joints, const double* 
   t->slots = slots;
   t->sig2.resize((size_t)n_joints);
   for (int j = 0; j < n_joints; ++j) t->sig2[(size_t)j] = sigma ? sigma[j] * sigma[j] : 1.0;
-  const size_t S = (size_t)slots, T = (size_t)max_tracks, J = (size_t)n_joints, PM = (size_t)kPeopleMaxPeople;
+  const size_t S = (size_t)slots, J = (size_t)n_joints;
   t->slot_stride = up256(track_slot_bytes(max_tracks, n_joints));
-  size_t at = S * t->slot_stride;
-  auto take = [&](size_t bytes) {
-    const size_t r = at;
-    at += up256(bytes);
-    return r;
-  };
-  t->off_sig = take(J * sizeof(double));
-  t->off_dist = take(S * T * PM * sizeof(double));
-  t->off_np = take(S * sizeof(int));
-  t->off_ppl = take(S * PM * J * 3 * sizeof(double));
-  t->off_ids = take(S * PM * sizeof(long long));
-  t->off_place = take(S * PM * sizeof(int));
-  t->total = at;
+  t->off_sig = S * t->slot_stride;
+  t->total = t->off_sig + up256(J * sizeof(double));
   return t.release();
 }
 
-Tracker::~Tracker() { dev_free(dev); }
+Tracker::~Tracker() {
+  if (done) {  // an update enqueued by an asynchronous entry may still be running on these buffers
+    int before = -1;
+    const bool moved = hipGetDevice(&before) == hipSuccess && before != device && hipSetDevice(device) == hipSuccess;
+    (void)hipEventSynchronize((hipEvent_t)done);
+    (void)hipEventDestroy((hipEvent_t)done);
+    if (moved) (void)hipSetDevice(before);
+  }
+  dev_free(img_dev);
+  dev_free(dev);
+}
 
-void Tracker::check_call(const char* who, int nb, int P, int J) const {
-  if (nb < 1 || nb > slots) bad(who, std::to_string(nb) + " images for a tracker of " + std::to_string(slots) + " slots (nb must be in [1, slots])");
+void Tracker::wait_done() {
+  if (done) HIPCHECK(hipEventSynchronize((hipEvent_t)done));
+}
+
+void Tracker::check_call(const char* who, int nb, int P, int J, const int* slot_of) const {
+  if (slot_of) {
+    if (nb < 1 || nb > kTrackMaxImages)
+      bad(who, std::to_string(nb) + " images with a slot map (nb must be in [1, " + std::to_string(kTrackMaxImages) + "])");
+    for (int b = 0; b < nb; ++b)
+      if (slot_of[b] < 0 || slot_of[b] >= slots)
+        bad(who, "slot_of[" + std::to_string(b) + "] = " + std::to_string(slot_of[b]) + " is outside [0, slots = " + std::to_string(slots) + ")");
+  } else if (nb < 1 || nb > slots) {
+    bad(who, std::to_string(nb) + " images for a tracker of " + std::to_string(slots) + " slots (nb must be in [1, slots])");
+  }
   if (P < 1 || P > kPeopleMaxPeople) bad(who, "max_people (P) must be in [1, " + std::to_string(kPeopleMaxPeople) + "]");
   if (J != tp.J)
     throw DcError(DC_ESHAPE, std::string(who) + ": the tracker holds " + std::to_string(tp.J) + " joints (n_joints), the poses " + std::to_string(J));
 }
 
-void Tracker::enqueue(int on_device, int nb, int P, const int* d_np, const double* d_ppl, long long* ids, int* place, double* dist, void* stream) {
+void Tracker::prepare(int on_device, int nb, void* stream) {
   if (device >= 0 && device != on_device)
     throw DcError(DC_EDEVICE, "tracker: bound to device " + std::to_string(device) + ", used on device " + std::to_string(on_device));
-  hipStream_t s = (hipStream_t)stream;
   if (!dev) {
     dev_alloc((void**)&dev, total);
     device = on_device;
     dev_zero(dev, total, stream);
     dev_upload(dev + off_sig, sig2.data(), sig2.size() * sizeof(double), stream);
+    hipEvent_t ev = nullptr;
+    HIPCHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    done = ev;
+    HIPCHECK(hipEventRecord(ev, (hipStream_t)stream));  // the next update, on whichever stream, runs behind the zeroing
   }
-  long long* d_ids = (long long*)(dev + off_ids);
-  int* d_place = (int*)(dev + off_place);
-  double* d_dist = (double*)(dev + off_dist);
-  KCHECK(launch_track(nb, P, tp, (const double*)(dev + off_sig), dev, slot_stride, d_dist, d_np, d_ppl, d_ids, d_place, stream));
+  if (nb > img_cap) {
+    wait_done();  // nobody reads the old scratch any more
+    const size_t N = (size_t)std::max(nb, slots), T = (size_t)tp.T, J = (size_t)tp.J, PM = (size_t)kPeopleMaxPeople;
+    size_t at = 0;
+    auto take = [&](size_t bytes) {
+      const size_t r = at;
+      at += up256(bytes);
+      return r;
+    };
+    const size_t o_dist = take(N * T * PM * sizeof(double)), o_np = take(N * sizeof(int)), o_ppl = take(N * PM * J * 3 * sizeof(double)),
+                 o_ids = take(N * PM * sizeof(long long)), o_place = take(N * PM * sizeof(int));
+    unsigned char* grown = nullptr;
+    dev_alloc((void**)&grown, at);
+    dev_free(img_dev);
+    img_dev = grown, img_cap = (int)N;
+    off_dist = o_dist, off_np = o_np, off_ppl = o_ppl, off_ids = o_ids, off_place = o_place;
+  }
+}
+
+void Tracker::enqueue(int nb, int P, const int* slot_of, const int* d_np, const double* d_ppl, long long* ids, int* place, double* dist,
+                      void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  long long* d_ids = (long long*)(img_dev + off_ids);
+  int* d_place = (int*)(img_dev + off_place);
+  double* d_dist = (double*)(img_dev + off_dist);
+  TrackSlotMap map{};
+  for (int b = 0; b < nb; ++b) track_slot_map_set(map, b, slot_of ? slot_of[b] : b);
+  HIPCHECK(hipStreamWaitEvent(s, (hipEvent_t)done, 0));
+  KCHECK(launch_track(slots, nb, P, tp, (const double*)(dev + off_sig), dev, slot_stride, d_dist, d_np, d_ppl, d_ids, d_place, map, stream));
   if (ids) HIPCHECK(hipMemcpyAsync(ids, d_ids, (size_t)nb * P * sizeof(long long), hipMemcpyDeviceToHost, s));
   if (place) HIPCHECK(hipMemcpyAsync(place, d_place, (size_t)nb * P * sizeof(int), hipMemcpyDeviceToHost, s));
   for (int b = 0; dist && b < nb; ++b)
     HIPCHECK(hipMemcpyAsync(dist + (size_t)b * tp.T * P, d_dist + (size_t)b * tp.T * kPeopleMaxPeople, (size_t)tp.T * P * sizeof(double),
                             hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipEventRecord((hipEvent_t)done, s));
 }
 
-void Tracker::update(int nb, int P, const int* n_people, const double* people, long long* ids, int* place, double* dist) {
-  check_call("tracker_update", nb, P, tp.J);
+void Tracker::update(int nb, int P, const int* slot_of, const int* n_people, const double* people, long long* ids, int* place, double* dist) {
+  check_call("tracker_update", nb, P, tp.J, slot_of);
   for (int b = 0; b < nb; ++b)
     if (n_people[b] < 0 || n_people[b] > P)
       bad("tracker_update", "n_people[" + std::to_string(b) + "] = " + std::to_string(n_people[b]) + " is outside [0, P = " + std::to_string(P) + "]");
@@ -100,9 +140,10 @@ void Tracker::update(int nb, int P, const int* n_people, const double* people, l
   HIPCHECK(hipSetDevice(d));
   RuntimeLock rl;
   hipStream_t s = util_stream();
-  if (!dev || device != d) enqueue(d, 0, P, nullptr, nullptr, nullptr, nullptr, nullptr, s);  // no launch: binds, allocates and zeroes, or DC_EDEVICE
-  int* d_np = (int*)(dev + off_np);
-  double* d_ppl = (double*)(dev + off_ppl);
+  prepare(d, nb, s);  // binds, allocates and zeroes, or DC_EDEVICE
+  wait_done();        // the staging below is the tracker's own: an update still in flight reads it
+  int* d_np = (int*)(img_dev + off_np);
+  double* d_ppl = (double*)(img_dev + off_ppl);
   const size_t img = (size_t)P * tp.J * 3;
   HIPCHECK(hipMemcpyAsync(d_np, n_people, (size_t)nb * sizeof(int), hipMemcpyHostToDevice, s));
   // only the people that exist are read on either side
@@ -110,7 +151,7 @@ void Tracker::update(int nb, int P, const int* n_people, const double* people, l
     if (n_people[b] > 0)
       HIPCHECK(hipMemcpyAsync(d_ppl + (size_t)b * img, people + (size_t)b * img, (size_t)n_people[b] * tp.J * 3 * sizeof(double),
                               hipMemcpyHostToDevice, s));
-  enqueue(d, nb, P, d_np, d_ppl, ids, place, dist, s);
+  enqueue(nb, P, slot_of, d_np, d_ppl, ids, place, dist, s);
   HIPCHECK(hipStreamSynchronize(s));
 }
 
@@ -119,6 +160,7 @@ void Tracker::reset(int slot) {
   if (!dev) return;  // nothing has been tracked yet
   RuntimeLock rl;
   DeviceScope on(device);
+  wait_done();
   hipStream_t s = util_stream();
   if (slot < 0) HIPCHECK(hipMemsetAsync(dev, 0, (size_t)slots * slot_stride, s));
   else HIPCHECK(hipMemsetAsync(dev + (size_t)slot * slot_stride, 0, slot_stride, s));
@@ -132,6 +174,7 @@ void Tracker::state(int slot, long long* ids, int* misses, int* hits, double* po
   if (dev) {
     RuntimeLock rl;
     DeviceScope on(device);
+    wait_done();
     hipStream_t s = util_stream();
     HIPCHECK(hipMemcpyAsync(block.data(), dev + (size_t)slot * slot_stride, block.size(), hipMemcpyDeviceToHost, s));
     HIPCHECK(hipStreamSynchronize(s));

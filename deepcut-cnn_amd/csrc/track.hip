@@ -4,6 +4,7 @@
 // (include/deepcut_hip.h, dc_tracker_update), restated in float64 in tests/track_ref.py.
 //
 // One latency-class kernel behind assemble_kernel (people.hip) or behind an upload of host poses, nothing of it on the forward path.
+// One workgroup per slot walks the images a slot map gives to its slot, so that several frames of one video are tracked in one launch.
 // All arithmetic is double and there is no matrix instruction in it: a frame is at most 256 x 256 distances of at most 32 joints.
 #include <hip/hip_runtime.h>
 
@@ -30,18 +31,21 @@ __device__ __forceinline__ void wave_key_min(double& v, int& e) {
 }
 }  // namespace
 
-// One workgroup of 256 threads (4 waves) updates one slot.  Thread i owns track place i in steps 1, 5 and 6, thread q owns person q in
-// step 7.  D lives in global scratch (256 x 256 doubles do not fit in LDS beside the rest) and is written and read
-// inside this workgroup only, with a barrier in between.
+// One workgroup of 256 threads (4 waves) applies one image to one slot: the body of an update, steps 1-7.  Thread i owns track place i
+// in steps 1, 5 and 6, thread q owns person q in step 7.  D lives in global scratch (256 x 256 doubles do not fit in LDS beside the rest)
+// and is written and read inside this workgroup only, with a barrier in between.
 // Matching: a round takes the smallest D among unmatched pairs.  Scanning all T*P entries every round is 256 rounds of 65 536 reads at
 // T = P = 256, so the minimum of every ROW is kept in LDS — rv[i], rq[i] = the smallest allowed D of track i among unmatched people and
 // the lowest q that has it — and a round is (1) the arg-min over the rows, a (value, place) key whose index order is the tie rule:
 // lower place first, and within the row the lower q was kept; (2) the re-derivation of the rows the match invalidates: those whose
 // minimum sat at the person just taken.  A wave re-derives a row with coalesced reads and a shuffle reduction; rows go to waves round
 // robin.  No step depends on thread timing: same inputs, same ids.
-__global__ __launch_bounds__(256) void track_kernel(int P, TrackParams tp, const double* __restrict__ sig2_g, unsigned char* __restrict__ state,
-                                                    size_t slot_stride, double* __restrict__ dist, const int* __restrict__ n_people,
-                                                    const double* __restrict__ people, long long* __restrict__ ids, int* __restrict__ place) {
+// The state block is read AND written here, and track_kernel calls this several times on one block with a barrier in between: `state`
+// carries no __restrict__, so that nothing loaded from it is kept across that barrier.
+__device__ __forceinline__ void track_image(int b, unsigned char* state_block, int P, const TrackParams& tp,
+                                            const double* __restrict__ sig2_g, double* __restrict__ dist,
+                                            const int* __restrict__ n_people, const double* __restrict__ people,
+                                            long long* __restrict__ ids, int* __restrict__ place) {
   __shared__ double s2[kTrackMax];   // s_i^2
   __shared__ double rv[kTrackMax];   // row minima: value ...
   __shared__ int rq[kTrackMax];      // ... and person, -1 = the row has no allowed entry left
@@ -57,10 +61,10 @@ __global__ __launch_bounds__(256) void track_kernel(int P, TrackParams tp, const
   __shared__ double red_v[4];
   __shared__ int red_e[4];
   __shared__ int nfree_s;
-  const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int T = tp.T, J = tp.J;
   const double inf = __builtin_huge_val();
-  const TrackSlot st = track_slot(state + (size_t)b * slot_stride, T, J);
+  const TrackSlot st = track_slot(state_block, T, J);
   const int n = min(max(n_people[b], 0), P);
   const double* ppl = people + (size_t)b * P * J * 3;
   double* D = dist + (size_t)b * T * kTrackMax;
@@ -264,14 +268,34 @@ __global__ __launch_bounds__(256) void track_kernel(int P, TrackParams tp, const
   }
 }
 
-int launch_track(int NB, int P, const TrackParams& p, const double* sig2, unsigned char* state, size_t slot_stride, double* dist,
-                 const int* n_people, const double* people, long long* ids, int* place, void* stream) {
+// One workgroup per slot: it walks the images in ascending b and applies those the map gives to its slot, each on the state the one
+// before left.  The map is a kernel argument and blockIdx is uniform, so the branch is.  The barrier behind an image stands between its
+// last stores to the state (steps 5-7) and the next image's loads of it (steps 1-3) by other threads of this workgroup, and between its
+// last readers of the LDS arrays (flag, fplace, pm in step 7) and the next image's initialisation of them.  A workgroup whose slot no
+// image names returns without touching the slot.
+__global__ __launch_bounds__(256) void track_kernel(int NB, int P, TrackParams tp, TrackSlotMap map, const double* __restrict__ sig2_g,
+                                                    unsigned char* state, size_t slot_stride, double* __restrict__ dist,
+                                                    const int* __restrict__ n_people, const double* __restrict__ people,
+                                                    long long* __restrict__ ids, int* __restrict__ place) {
+  const int slot = blockIdx.x;
+  unsigned char* block = state + (size_t)slot * slot_stride;
+  for (int b = 0; b < NB; ++b) {
+    if ((int)((map.w[b >> 2] >> ((b & 3) * 8)) & 0xffu) != slot) continue;  // uniform
+    track_image(b, block, P, tp, sig2_g, dist, n_people, people, ids, place);
+    __syncthreads();
+  }
+}
+
+int launch_track(int S, int NB, int P, const TrackParams& p, const double* sig2, unsigned char* state, size_t slot_stride, double* dist,
+                 const int* n_people, const double* people, long long* ids, int* place, const TrackSlotMap& map, void* stream) {
   if (NB <= 0) return 0;
-  if (P < 1 || P > kTrackMax || p.T < 1 || p.T > kTrackMax || p.J < 1 || p.J > kPeopleMaxJoints || slot_stride % 16 ||
-      slot_stride < track_slot_bytes(p.T, p.J))
+  if (S < 1 || S > 256 || NB > kTrackMaxImages || P < 1 || P > kTrackMax || p.T < 1 || p.T > kTrackMax || p.J < 1 ||
+      p.J > kPeopleMaxJoints || slot_stride % 16 || slot_stride < track_slot_bytes(p.T, p.J))
     return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(track_kernel, dim3(NB), dim3(256), 0, (hipStream_t)stream, P, p, sig2, state, slot_stride, dist, n_people, people, ids,
-                     place);
+  for (int b = 0; b < NB; ++b)
+    if ((int)((map.w[b >> 2] >> ((b & 3) * 8)) & 0xffu) >= S) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(track_kernel, dim3(S), dim3(256), 0, (hipStream_t)stream, NB, P, p, map, sig2, state, slot_stride, dist, n_people,
+                     people, ids, place);
   return (int)hipGetLastError();
 }
 

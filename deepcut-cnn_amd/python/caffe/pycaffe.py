@@ -265,10 +265,16 @@ def _load():
         "dc_tracker_destroy": (ci, [vp]),
         "dc_tracker_reset": (ci, [vp, ci]),
         "dc_tracker_update": (ci, [vp, ci, ci, vp, vp, vp, vp, vp]),
+        "dc_tracker_update_slots": (ci, [vp, ci, ci, vp, vp, vp, vp, vp, vp]),
         "dc_tracker_state": (ci, [vp, ci, vp, vp, vp, vp]),
+        "dc_net_track_people_slots": (ci, [vp, vp, vp, C.POINTER(AssembleParams), ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "dc_net_track_people": (ci, [vp, vp, C.POINTER(AssembleParams), ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "dc_group_track_people": (ci, [vp, vp, vp, ci, C.POINTER(FuseMirror), C.POINTER(AssembleParams), ci, vp, vp, vp, vp, vp, vp, vp, vp,
                                        vp, vp]),
+        "dc_group_track_people_slots": (ci, [vp, vp, vp, vp, ci, C.POINTER(FuseMirror), C.POINTER(AssembleParams), ci, vp, vp, vp, vp, vp, vp,
+                                             vp, vp, vp, vp]),
+        "dc_net_track_frames_async": (ci, [vp, vp, vp, vp, ci, ci, ci, C.c_double, ci, vp, C.POINTER(AssembleParams), ci, vp, vp, vp, vp, vp,
+                                           vp, vp, vp, vp]),
         "dc_net_flops": (ci, [vp, C.POINTER(C.c_double)]),
         "dc_net_num_launches": (ci, [vp]),
         "dc_net_plan_text": (cp, [vp]),
@@ -679,7 +685,8 @@ class Tracker(object):
     match needs a distance <= max_dist, a track without a match for more than max_misses updates in a row is dropped; min_size: lower
     bound in pixels of the track size the distance is normalised by; motion: 1 compares with the pose moved on by its velocity, 0 with
     the last pose.  THE DEFAULTS OF max_misses, min_common, max_dist, min_size AND sigma ARE PLACEHOLDERS, NOT TUNED ON REAL VIDEO:
-    override them.  Creation needs no device; updates need GPU mode.  Calls are synchronous and apply in call order."""
+    override them.  Creation needs no device; updates need GPU mode.  The calls of this class are synchronous; updates apply in call order, those
+    enqueued by `Net.track_frames_async` included (the synchronous calls wait for them first)."""
 
     def __init__(self, n_joints=14, slots=1, max_tracks=64, sigma=None, max_misses=5, min_common=3, max_dist=0.25, min_size=32.0, motion=1):
         self._h = None
@@ -700,10 +707,12 @@ class Tracker(object):
             _lib.dc_tracker_destroy(self._h)
             self._h = None
 
-    def update(self, people, n_people=None, return_dist=False):
+    def update(self, people, n_people=None, return_dist=False, slot_of=None):
         """people: [nb, P, J, 3] float64 (x, y, score; a joint counts when its score > 0) with n_people [nb] of them valid per image, or
         a list of nb arrays [m_b, J, 3] (n_people is then their lengths) — image b updates slot b.  This is how poses that did not come
         from `track_people` (top-down poses of `forward_boxes`, say) get tracked.
+        slot_of: [nb] ints in [0, slots), the slot every image updates (dc_tracker_update_slots): images of one slot apply in ascending b,
+        each on the state the one before left — several frames of one video in one call; nb may then be 1..64 whatever `slots` is.
         -> (ids int64 [nb, P], place int32 [nb, P]): -1 beyond n_people[b] and for a person no track place was free for; with
         return_dist also the distances float64 [nb, max_tracks, P]."""
         j = self.n_joints
@@ -725,7 +734,10 @@ class Tracker(object):
         place = np.full((nb, p), -1, np.int32)
         dist = np.zeros((nb, self.max_tracks, p), np.float64) if return_dist else None
         ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        _check(_lib.dc_tracker_update(self._h, nb, p, ptr(n), ptr(ppl), ptr(ids), ptr(place), ptr(dist)))
+        if slot_of is None:
+            _check(_lib.dc_tracker_update(self._h, nb, p, ptr(n), ptr(ppl), ptr(ids), ptr(place), ptr(dist)))
+        else:
+            _check(_lib.dc_tracker_update_slots(self._h, nb, p, ptr(_slot_map(slot_of, nb)), ptr(n), ptr(ppl), ptr(ids), ptr(place), ptr(dist)))
         return (ids, place, dist) if return_dist else (ids, place)
 
     def reset(self, slot=None):
@@ -740,6 +752,50 @@ class Tracker(object):
                "poses": np.zeros((t, j, 3), np.float64)}
         _check(_lib.dc_tracker_state(self._h, int(slot), *[out[k].ctypes.data_as(C.c_void_p) for k in ("ids", "misses", "hits", "poses")]))
         return out
+
+
+def _slot_map(slot_of, nb):
+    """slot_of of a tracked call -> int32 [nb] (the library checks the values)."""
+    m = np.ascontiguousarray(slot_of, dtype=np.int32).reshape(-1)
+    if m.shape[0] != nb:
+        raise ValueError("slot_of must hold one slot per image: %d slots for %d images" % (m.shape[0], nb))
+    return m
+
+
+class TrackedFrames(object):
+    """What `Net.track_frames_async` returns: the request in flight.  It owns the pinned output arrays and keeps the frames alive;
+    `result()` waits for the net and returns what `Net.track_people` returns."""
+
+    def __init__(self, net, tracked, count, people, cand, ids, place, keep, pool=None):
+        self._net, self._tracked, self._keep, self._pool = net, tracked, keep, pool
+        self._count, self._people, self._cand, self._ids, self._place = count, people, cand, ids, place
+        self._out, self._ready = None, False
+
+    def done(self):
+        """True when the results are there: the net's stream was seen with nothing left to do since this request went out (remembered,
+        so that a later request on the same net does not make this one look unfinished)."""
+        if not self._ready and not self._net.busy():
+            self._ready = True
+        return self._ready
+
+    def result(self):
+        """-> one dict per image: "people", "cand" and, with a tracker, "ids" and "place" (`Net.track_people`).  Waits for the net."""
+        if self._out is None:
+            if not self._ready:
+                self._net.synchronize()
+                self._ready = True
+            out = []
+            for b in range(self._count.shape[0]):
+                m = int(self._count[b])
+                d = {"people": self._people[b, :m].copy(), "cand": self._cand[b, :m].copy()}
+                if self._tracked:
+                    d["ids"], d["place"] = self._ids[b, :m].copy(), self._place[b, :m].copy()
+                out.append(d)
+            self._out, self._keep = out, None
+            if self._pool is not None:  # everything is copied out: the pinned arrays serve the net's next request of this shape
+                self._pool.append((self._count, self._people, self._cand, self._ids, self._place))
+                self._count = self._people = self._cand = self._ids = self._place = self._pool = None
+        return self._out
 
 
 def _tracker_handle(tracker):
@@ -1302,17 +1358,76 @@ class Net(object):
                                      joint_order, return_cost)
 
     def track_people(self, tracker, scale=1.0, threshold=0.1, radius=1, max_det=16, edges=None, mean=None, std=None, max_cost=32.0,
-                     seed_threshold=0.5, max_people=32, min_joints=1, joint_order=None, return_cost=False):
+                     seed_threshold=0.5, max_people=32, min_joints=1, joint_order=None, return_cost=False, slot_of=None):
         """`assemble_people` with the identities of a `caffe.Tracker` (dc_net_track_people): the tracker's update runs on the device
         behind the assembly, on the people where the assembly left them — image b updates slot b.  The arguments and the result are
         `assemble_people`'s, unchanged, with two more entries per image: "ids": int64 [m] (the same person keeps their id from frame
-        to frame; -1 = no track place was free) and "place": int32 [m] (the track place, an index into `tracker.state()`)."""
+        to frame; -1 = no track place was free) and "place": int32 [m] (the track place, an index into `tracker.state()`).
+        slot_of: [batch] ints, the slot every image updates (dc_net_track_people_slots; `Tracker.update`): a batch forward of k
+        consecutive frames of one video is tracked with slot_of = [slot] * k."""
         _tracker_handle(tracker)
         return self._assemble_people(tracker, scale, threshold, radius, max_det, edges, mean, std, max_cost, seed_threshold, max_people,
-                                     min_joints, joint_order, return_cost)
+                                     min_joints, joint_order, return_cost, slot_of)
+
+    def track_frames_async(self, frames_or_images, tracker=None, scale=1.0, slot_of=None, assemble_scale=None, threshold=0.1, radius=1,
+                           max_det=16, edges=None, mean=None, std=None, max_cost=32.0, seed_threshold=0.5, max_people=32, min_joints=1,
+                           joint_order=None):
+        """The whole video chain without a host wait (dc_net_track_frames_async): upload, pre-processing, forward, assembly, the
+        tracker's update and the downloads are enqueued on the net's own stream and the call returns.  frames_or_images: a `Frame`, a
+        list of `Frame`s of one size, or uint8 [n,H,W,3] / [H,W,3] BGR; they must stay untouched until the result is collected.
+        tracker: a `caffe.Tracker`, or None for people without ids; slot_of as `track_people`.  scale: the pre-processing's;
+        assemble_scale: the assembly's (None: the same).  The other arguments are `assemble_people`'s.
+        -> a `TrackedFrames`: `result()` synchronises the net and returns what `forward_images` + `track_people` return, bit for bit.
+        A second call on a busy net queues behind the first; to overlap calls use clones (`deepcut_tools.VideoPipeline`): the tracker
+        keeps the updates in call order."""
+        if edges is None:
+            raise ValueError("track_frames_async needs the regression edges (deepcut_tools.read_pair_stats)")
+        if tracker is not None:
+            _tracker_handle(tracker)
+        frames = _frame_list(frames_or_images)
+        if frames is not None:
+            arr, h, w, dev = _frame_array(frames)
+            n, x, keep = len(frames), None, (arr, frames)
+        else:
+            x = np.ascontiguousarray(frames_or_images, dtype=np.uint8)
+            if x.ndim == 3:
+                x = x[None]
+            if x.ndim != 4 or x.shape[3] != 3:
+                raise ValueError("images must be uint8 [n,H,W,3] (BGR)")
+            n, h, w, _ = x.shape
+            arr, dev, keep = None, False, (x,)
+        ch, cw = canvas_size(h, w, scale)
+        self.blobs["data"].reshape(n, 3, ch, cw)
+        self.reshape()
+        j = self.blobs["prob"].shape[1]
+        want_e = self.blobs["next_pred"].shape[1] // 2 if "next_pred" in self.blobs else None
+        q, e, m, s, order = check_assembly(j, want_e, edges, mean, std, joint_order, scale if assemble_scale is None else assemble_scale,
+                                           threshold, radius, max_det, max_cost, seed_threshold, max_people, min_joints)
+        p = q.max_people
+        # pinned outputs: the DMA engines move them.  In CPU mode there is no device to pin against, and the call below says so
+        # (DC_ENOCPU) after the library's own argument checks
+        # (pinning and unpinning cost more than the call and wait for the device: a collected request hands its arrays back)
+        out = pinned_empty if _lib.dc_get_mode() == 1 else np.empty
+        pools = self.__dict__.setdefault("_async_outputs", {})
+        if len(pools) > 8:
+            pools.clear()
+        pool = pools.setdefault((n, p, j, tracker is not None), [])
+        if pool:
+            count, people, cand, ids, place = pool.pop()
+        else:
+            count, people, cand = out((n,), np.int32), out((n, p, j, 3), np.float64), out((n, p, j), np.int32)
+            ids = place = None
+            if tracker is not None:
+                ids, place = out((n, p), np.int64), out((n, p), np.int32)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        _check(_lib.dc_net_track_frames_async(self._h, None if tracker is None else tracker._h, arr, ptr(x), n, h, w, float(scale),
+                                              1 if dev else 0, None if slot_of is None else ptr(_slot_map(slot_of, n)), C.byref(q),
+                                              e.shape[0], ptr(e), ptr(m), ptr(s), ptr(order), ptr(count), ptr(people), ptr(cand), ptr(ids),
+                                              ptr(place)))
+        return TrackedFrames(self, tracker is not None, count, people, cand, ids, place, keep + (tracker,), pool)
 
     def _assemble_people(self, tracker, scale, threshold, radius, max_det, edges, mean, std, max_cost, seed_threshold, max_people, min_joints,
-                         joint_order, return_cost):
+                         joint_order, return_cost, slot_of=None):
         if edges is None:
             raise ValueError("assemble_people needs the regression edges (deepcut_tools.read_pair_stats)")
         n, j = self.blobs["prob"].shape[:2]
@@ -1330,8 +1445,13 @@ class Net(object):
                                                ptr(cand), ptr(cost)))
         else:
             ids, place = np.full((n, p), -1, np.int64), np.full((n, p), -1, np.int32)
-            _check(_lib.dc_net_track_people(self._h, _tracker_handle(tracker), C.byref(q), e.shape[0], ptr(e), ptr(m), ptr(s), ptr(order),
-                                            ptr(count), ptr(people), ptr(cand), ptr(cost), ptr(ids), ptr(place)))
+            if slot_of is None:
+                _check(_lib.dc_net_track_people(self._h, _tracker_handle(tracker), C.byref(q), e.shape[0], ptr(e), ptr(m), ptr(s), ptr(order),
+                                                ptr(count), ptr(people), ptr(cand), ptr(cost), ptr(ids), ptr(place)))
+            else:
+                _check(_lib.dc_net_track_people_slots(self._h, _tracker_handle(tracker), ptr(_slot_map(slot_of, n)), C.byref(q), e.shape[0],
+                                                      ptr(e), ptr(m), ptr(s), ptr(order), ptr(count), ptr(people), ptr(cand), ptr(cost),
+                                                      ptr(ids), ptr(place)))
         out = []
         for b in range(n):
             d = {"people": people[b, :count[b]].copy(), "cand": cand[b, :count[b]].copy()}
@@ -1783,16 +1903,16 @@ class NetGroup(object):
 
     def track_people(self, tracker, scales, base=0, threshold=0.1, radius=1, max_det=16, edges=None, mean=None, std=None, max_cost=32.0,
                      seed_threshold=0.5, max_people=32, min_joints=1, joint_order=None, return_cost=False, mirror=None, image_width=None,
-                     joint_mirror=None):
+                     joint_mirror=None, slot_of=None):
         """`assemble_people` with the identities of a `caffe.Tracker` (dc_group_track_people), plain or mirrored: the tracker's update
         runs on the device behind the assembly of the fused maps.  The arguments and the result are `assemble_people`'s, unchanged,
-        plus "ids" and "place" per image as `Net.track_people` gives them."""
+        plus "ids" and "place" per image as `Net.track_people` gives them.  slot_of: as `Net.track_people` (dc_group_track_people_slots)."""
         _tracker_handle(tracker)
         return self._assemble_people(tracker, scales, base, threshold, radius, max_det, edges, mean, std, max_cost, seed_threshold, max_people,
-                                     min_joints, joint_order, return_cost, mirror, image_width, joint_mirror)
+                                     min_joints, joint_order, return_cost, mirror, image_width, joint_mirror, slot_of)
 
     def _assemble_people(self, tracker, scales, base, threshold, radius, max_det, edges, mean, std, max_cost, seed_threshold, max_people,
-                         min_joints, joint_order, return_cost, mirror, image_width, joint_mirror):
+                         min_joints, joint_order, return_cost, mirror, image_width, joint_mirror, slot_of=None):
         if edges is None:
             raise ValueError("assemble_people needs the regression edges (deepcut_tools.read_pair_stats)")
         sc, base = self._scales(scales, base)
@@ -1813,8 +1933,13 @@ class NetGroup(object):
                                                           ptr(count), ptr(people), ptr(cand), ptr(cost)))
         else:
             ids, place = np.full((n, p), -1, np.int64), np.full((n, p), -1, np.int32)
-            _check(_lib.dc_group_track_people(self._h, _tracker_handle(tracker), ptr(sc), base, fm, C.byref(q), e.shape[0], ptr(e), ptr(m),
-                                              ptr(s), ptr(order), ptr(count), ptr(people), ptr(cand), ptr(cost), ptr(ids), ptr(place)))
+            if slot_of is None:
+                _check(_lib.dc_group_track_people(self._h, _tracker_handle(tracker), ptr(sc), base, fm, C.byref(q), e.shape[0], ptr(e), ptr(m),
+                                                  ptr(s), ptr(order), ptr(count), ptr(people), ptr(cand), ptr(cost), ptr(ids), ptr(place)))
+            else:
+                _check(_lib.dc_group_track_people_slots(self._h, _tracker_handle(tracker), ptr(_slot_map(slot_of, n)), ptr(sc), base, fm,
+                                                        C.byref(q), e.shape[0], ptr(e), ptr(m), ptr(s), ptr(order), ptr(count), ptr(people),
+                                                        ptr(cand), ptr(cost), ptr(ids), ptr(place)))
         out = []
         for b in range(n):
             d = {"people": people[b, :count[b]].copy(), "cand": cand[b, :count[b]].copy()}

@@ -1,0 +1,136 @@
+"""Video frames in flight: tracked people of a stream of frames with several requests on the GPU at a time.
+
+`Net.track_frames_async` (dc_net_track_frames_async) enqueues the whole chain of a frame — upload, pre-processing, forward, assembly,
+the tracker's update, downloads — on its net's stream and returns.  `VideoPipeline` keeps `depth` executors busy with it (the net and
+`depth - 1` clones: own activations, own stream, own graph, SHARED parameters) and can send `batch` consecutive frames as ONE batch
+forward whose images the tracker applies in order (the slot map of dc_tracker_update_slots).  The tracker keeps the updates of all
+executors in the order of the calls (an event on the device, no host wait), and results come back in submission order.
+PARITY UNPINNED BY THE REFERENCE, which stops at the maps: assembly and tracking rules are this project's own (include/deepcut_hip.h).
+"""
+import collections
+
+
+class VideoPipeline(object):
+    MAX_DEPTH = 4  # a HIP process has four hardware queues: a fifth executor only shares one
+
+    def __init__(self, net, tracker=None, depth=3, batch=1, stats=None, scale=1.0, choose_streams=True, **assembly):
+        """net: a `caffe.Net` with all three maps (or a sparse-pairwise net); tracker: a `caffe.Tracker` or None (people without ids,
+        ids come back as None); depth: executors, 1..4; batch: frames per call, 1..64; stats: (edges, mean, std) as
+        `deepcut_tools.read_pair_stats` returns them, or a path; scale: the pre-processing's and the assembly's; assembly: what
+        `Net.assemble_people` takes (threshold, max_det, max_cost, ...)."""
+        depth, batch = int(depth), int(batch)
+        if not 1 <= depth <= self.MAX_DEPTH:
+            raise ValueError("depth must be in [1, %d], got %d" % (self.MAX_DEPTH, depth))
+        if not 1 <= batch <= 64:
+            raise ValueError("batch must be in [1, 64], got %d" % batch)
+        if stats is None:
+            raise ValueError("VideoPipeline needs the pair statistics (stats=(edges, mean, std) or a path)")
+        if isinstance(stats, (str, bytes)) or hasattr(stats, "__fspath__"):
+            from .pair_stats import read_pair_stats
+
+            stats = read_pair_stats(stats)
+        self.edges, self.mean, self.std = stats
+        self.nets = [net] + [net.clone() for _ in range(depth - 1)]
+        self.tracker, self.batch, self.scale, self.assembly = tracker, batch, float(scale), dict(assembly)
+        self._choose_streams = bool(choose_streams)
+        self.stream_choice = None            # what caffe.choose_streams measured, once it ran
+        self._held = []                      # frames of the batch being gathered: (frame, tag, slot, shape key)
+        self._pending = collections.deque()  # requests in flight, in submission order: (executor, handle, tags)
+        self._done = collections.deque()     # results not yet handed back, in submission order
+        self._next = 0
+        self.calls = 0
+
+    @property
+    def depth(self):
+        return len(self.nets)
+
+    # ---- launching ----------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _shape_key(frame):
+        if hasattr(frame, "is_device") and hasattr(frame, "c_frame"):  # a caffe.Frame
+            return ("frame", frame.format, frame.height, frame.width, frame.is_device, frame.matrix, frame.range)
+        shape = tuple(getattr(frame, "shape", ()))
+        if len(shape) != 3 or shape[2] != 3:
+            raise ValueError("submit takes a caffe.Frame or an HxWx3 uint8 image")
+        return ("bgr",) + shape
+
+    def _free_executor(self):
+        # an executor is busy while a request of it has not been SEEN finished (done() remembers: the net may get the next one at once)
+        busy = set(k for k, handle, _ in self._pending if not handle.done())
+        for i in range(len(self.nets)):
+            k = (self._next + i) % len(self.nets)
+            if k not in busy:
+                return k
+        return None
+
+    def _collect_oldest(self):
+        """Wait for the oldest request (the tracker ran them in submission order, so it finishes first or nearly) and queue its results."""
+        k, handle, tags = self._pending.popleft()
+        for tag, d in zip(tags, handle.result()):
+            self._done.append((tag, d["people"], d.get("ids")))
+
+    def _send(self):
+        held, self._held = self._held, []
+        if not held:
+            return
+        k = self._free_executor()
+        while k is None:  # every executor is busy: the only place a submit blocks
+            self._collect_oldest()
+            k = self._free_executor()
+        self._next = (k + 1) % len(self.nets)
+        frames = [h[0] for h in held]
+        if held[0][3][0] == "bgr":
+            import numpy as np
+
+            frames = np.stack(frames) if len(frames) > 1 else frames[0]
+        if self._choose_streams and len(self.nets) > 1 and not self._pending and self.calls == 0:
+            # first call: every executor lowers / allocates / tunes the shape, then the library picks their streams by timing them
+            # together — untimed set-up, as in Pipeline
+            import caffe
+
+            self._choose_streams = False
+            key = held[0][3]
+            ch, cw = caffe.canvas_size(*(key[2:4] if key[0] == "frame" else key[1:3]), self.scale)
+            for e in self.nets:
+                e.reserve(len(held), ch, cw)
+            self.stream_choice = caffe.choose_streams(self.nets)
+        slot_of = None if self.tracker is None else [h[2] for h in held]
+        handle = self.nets[k].track_frames_async(frames, self.tracker, self.scale, slot_of=slot_of, edges=self.edges, mean=self.mean,
+                                                 std=self.std, **self.assembly)
+        self.calls += 1
+        self._pending.append((k, handle, [h[1] for h in held]))
+
+    def submit(self, frame, tag=None, slot=0):
+        """Enqueue one frame (a `caffe.Frame` or an HxWx3 uint8 BGR image) of the sequence in tracker slot `slot`.  With batch > 1 the
+        frame is held until `batch` frames of one shape are there (or flush() / drain()); a frame of another shape sends what is held
+        first.  The frame must stay untouched until its result comes back.  Blocks only when every executor is busy."""
+        key = self._shape_key(frame)
+        if self._held and self._held[0][3] != key:
+            self._send()
+        self._held.append((frame, tag, int(slot), key))
+        if len(self._held) >= self.batch:
+            self._send()
+
+    def flush(self):
+        """Send the frames held for a batch as they are (a partial batch)."""
+        self._send()
+
+    def wait_one(self):
+        """-> (tag, people float64 [m, J, 3], ids int64 [m] or None) of the oldest frame not yet handed back: results come in
+        submission order."""
+        if not (self._done or self._pending or self._held):
+            raise RuntimeError("wait_one() with nothing submitted")
+        if not self._done:
+            if not self._pending:
+                self._send()
+            self._collect_oldest()
+        return self._done.popleft()
+
+    def drain(self):
+        """Send what is held, wait for everything -> the list of (tag, people, ids) in submission order."""
+        self._send()
+        while self._pending:
+            self._collect_oldest()
+        out = list(self._done)
+        self._done.clear()
+        return out

@@ -86,7 +86,7 @@ def estimate_people(image, model_def, model_bin, stats, scale=1.0, net=None, sca
     return _people_of_image(None, image, model_def, model_bin, stats, scale, net, scales, base, flip, joint_mirror, sparse, assembly)["people"]
 
 
-def track_people(frames, model_def, model_bin, stats, tracker=None, **kw):
+def track_people(frames, model_def, model_bin, stats, tracker=None, depth=1, batch=1, **kw):
     """`estimate_people` over the frames of a video, with identities: a generator over an iterable of images (HxWx3 BGR uint8) or
     `caffe.Frame`s that yields, per frame, (people float64 [m, J, 3], ids int64 [m]) — the same person keeps their id from frame to
     frame, -1 marks a person no track place was free for.  kw: what `estimate_people` takes (scale / scales / base / flip / joint_mirror /
@@ -94,11 +94,22 @@ def track_people(frames, model_def, model_bin, stats, tracker=None, **kw):
     `Net.track_people` / `NetGroup.track_people`: the association runs on the device behind the assembly, the people it returns are
     `estimate_people`'s.  tracker: a `caffe.Tracker` of one slot or more (slot 0 is used); None makes one with the defaults, which are
     PLACEHOLDERS, not tuned on real video.  PARITY UNPINNED BY THE REFERENCE: the tracking rule is this project's own
-    (include/deepcut_hip.h, dc_tracker_update)."""
+    (include/deepcut_hip.h, dc_tracker_update).
+    depth / batch: the defaults (1, 1) run one synchronous call per frame.  depth > 1 keeps that many frames in flight on the net and
+    its clones, batch > 1 sends that many consecutive frames as one batch forward (`deepcut_tools.VideoPipeline`); the results are the
+    same (people, ids) in frame order, up to `depth * batch` frames behind the input.  One forward per frame only: a pyramid
+    (scales= / flip=True) has no asynchronous entry and raises ValueError."""
     args = dict(scale=1.0, net=None, scales=None, base=None, flip=False, joint_mirror=MIRROR_MPII14, sparse=False)
     for k in list(kw):
         if k in args:
             args[k] = kw.pop(k)
+    if int(depth) != 1 or int(batch) != 1:
+        if args["scales"] is not None or args["flip"]:
+            raise ValueError("track_people: depth > 1 / batch > 1 run one forward per frame; a pyramid (scales= / flip=True) has no "
+                             "asynchronous entry: use depth=1, batch=1")
+        for item in _track_in_flight(frames, model_def, model_bin, stats, tracker, int(depth), int(batch), args, kw):
+            yield item
+        return
     for image in frames:
         if tracker is None:
             import caffe as _caffe
@@ -107,6 +118,29 @@ def track_people(frames, model_def, model_bin, stats, tracker=None, **kw):
         d = _people_of_image(tracker, image, model_def, model_bin, stats, args["scale"], args["net"], args["scales"], args["base"], args["flip"],
                              args["joint_mirror"], args["sparse"], kw)
         yield d["people"], d["ids"]
+
+
+def _track_in_flight(frames, model_def, model_bin, stats, tracker, depth, batch, args, assembly):
+    """`track_people` through `deepcut_tools.VideoPipeline` -> (people, ids) per frame, in frame order."""
+    import caffe as _caffe
+    from deepcut_tools import VideoPipeline
+
+    net = args["net"]
+    if net is None:
+        net = _get_sparse_model(model_def, model_bin) if args["sparse"] else _get_model(model_def, model_bin)
+    if tracker is None:
+        tracker = _caffe.Tracker(n_joints=len(MIRROR_MPII14))
+    pipe = VideoPipeline(net, tracker, depth=depth, batch=batch, stats=stats, scale=args["scale"], **assembly)
+    ahead = 0
+    for image in frames:
+        pipe.submit(image if hasattr(image, "c_frame") else _np.ascontiguousarray(image, dtype=_np.uint8))
+        ahead += 1
+        if ahead > depth * batch:
+            _, people, ids = pipe.wait_one()
+            ahead -= 1
+            yield people, ids
+    for _, people, ids in pipe.drain():
+        yield people, ids
 
 
 def _people_of_image(tracker, image, model_def, model_bin, stats, scale, net, scales, base, flip, joint_mirror, sparse, assembly):

@@ -755,8 +755,8 @@ int dc_group_flops(dc_group* group, double* out);
  * PARITY UNPINNED BY THE REFERENCE: the reference repository stops at the maps and has no tracker.  As with the assembly rule of
  * dc_net_assemble_people, the rule below is this project's own; tests/track_ref.py restates it in float64 NumPy.
  *
- * A tracker has S slots.  A slot is one independent sequence: image b of a call updates slot b.  Each slot has T track places and a
- * counter next_id that starts at 0.  A live track holds: id; pose[J][3] = x, y, score in image pixels (a joint is HELD when its score
+ * A tracker has S slots.  A slot is one independent sequence: image b of a call updates slot b, or the slot a slot map names (below).
+ * Each slot has T track places and a counter next_id that starts at 0.  A live track holds: id; pose[J][3] = x, y, score in image pixels (a joint is HELD when its score
  * > 0); vel[J][2]; misses; hits.  An update of a slot with the people[n][J][3] of a frame (n <= P <= 256) does the following, all
  * arithmetic in double, sums over joints ascending:
  *  1. Track size.  s_i = max(min_size, max(x extent, y extent) over the held joints of pose_i); one held joint has extent 0.
@@ -780,18 +780,45 @@ int dc_group_flops(dc_group* group, double* out);
  *     (the net's, in the chained entries) at the first update.  THE DEFAULTS THE PYTHON LAYER CHOOSES FOR max_misses, min_common,
  *     max_dist, min_size AND sigma ARE PLACEHOLDERS, NOT TUNED ON REAL VIDEO: override them.
  * dc_tracker_update: host poses — n_people[nb], people[nb][P][J][3] (entries of q >= n_people[b] are not read) — are uploaded and
- *     image b updates slot b in one launch (one workgroup per image).  This is how top-down poses of dc_net_forward_boxes get tracked.
+ *     image b updates slot b in one launch (one workgroup per slot).  This is how top-down poses of dc_net_forward_boxes get tracked.
  *     Outputs: ids[nb][P] (long long; -1 for q >= n and for an untracked person), place[nb][P] (int, the track place; -1 likewise; may
  *     be NULL), dist[nb][T][P] (the D of step 3; may be NULL: diagnostics and tests).
+ * Slot map (dc_tracker_update_slots, dc_net_track_people_slots, dc_group_track_people_slots): slot_of[nb], each in [0, S), says which slot
+ *     image b updates, so that several consecutive frames of ONE video travel in one call (a batch forward of k frames, slot_of = k times
+ *     the sequence's slot).  Images with the same slot are applied in ascending b, each on the state the one before left; images with
+ *     different slots are independent.  The result — ids, place and dist per image, the slots' state — is by definition that of applying
+ *     the images one at a time.  A slot no image names is not touched.  With a map nb may be 1..64 whatever S is; the tracker's per-image
+ *     scratch grows to the largest nb seen.  slot_of == NULL is the identity map of the entries without it (nb <= S), which are these
+ *     entries called with NULL.  One launch either way: one workgroup per slot walks the images of its slot.
  * dc_net_track_people / dc_group_track_people: dc_net_assemble_people / dc_group_assemble_people[_mirrored] (fm may be NULL) with the
  *     tracker's launch behind the assembly's on the same stream, reading the people where the assembly left them on the device: one more
  *     launch, no more transfer than the ids.  They return what the assembly entries return, unchanged, plus ids / place
  *     [n][max_people].  The sparse pairwise path (DC_OPT_SPARSE_PAIRWISE) is covered.
  * dc_tracker_state: a slot's tracks, e.g. to see where occluded people were last seen: ids[T], misses[T], hits[T], poses[T][J][3]
  *     (any may be NULL); free places give -1 / 0 / 0 / zeros.  Before the first update every place is free.
- * Order: every call on a tracker is synchronous and holds the library's runtime lock from its launch to its completion, so updates
- *     apply in host call order whichever net, group or stream they ran behind.
- * Errors, before any device work: DC_EINVAL naming the parameter for nb outside [1, slots], P (max_people) outside [1, 256], a
+ * dc_net_track_frames_async: the whole video chain on the net's own stream with NO host wait — it enqueues the upload of host planes,
+ *     the pre-processing launch, the forward, candidates, the sparse pairwise head when DC_OPT_SPARSE_PAIRWISE applies, pair costs,
+ *     assembly, the tracker's launch and the downloads — and returns when all of this is enqueued.  The input is n video frames
+ *     (frames, as dc_net_forward_frames) or, with frames == NULL, n packed BGR images (images, as dc_net_forward_images); scale and
+ *     p->scale are the pre-processing's and the assembly's as in the synchronous entries.  tracker may be NULL: people without ids, and
+ *     ids must then be NULL too.  slot_of as above (NULL: image b -> slot b).  Outputs: n_people[n], people[n][max_people][J][3],
+ *     cand[n][max_people][J] (may be NULL), ids / place [n][max_people] (place may be NULL).  dc_net_busy / dc_net_synchronize tell when
+ *     the outputs are there, as for dc_net_forward_host_async.  Lifetimes: frame planes (host or device) and the output arrays must
+ *     stay valid and untouched until then; everything small — params, edges, statistics, joint order, slot map, frame descriptors — is
+ *     copied before the return.  Output arrays and host planes from dc_host_alloc are moved by the DMA engines in place; pageable ones
+ *     work too and are staged by the runtime (the call may then wait for earlier copies).  A second call on a net that is still busy
+ *     queues behind the first in stream order; to overlap calls, issue them on a net and its clones — the tracker keeps their updates in
+ *     the order of the calls.  The results equal those of dc_net_forward_frames / dc_net_forward_images followed by
+ *     dc_net_track_people[_slots] (or dc_net_assemble_people), bit for bit.  There is no asynchronous group (pyramid / mirror) entry.
+ * Order: updates of a tracker apply in the order of the host calls that enqueued them, whichever net, clone, group or stream carried
+ *     them.  The tracker holds an event: every enqueue of an update makes its stream wait for the event of the update before it (on
+ *     the device, no host wait) and records the event again behind its own launch and copies; the library's runtime lock is held for the
+ *     enqueue only.  The synchronous calls — dc_tracker_update[_slots], dc_tracker_state, dc_tracker_reset, dc_tracker_destroy and the
+ *     synchronous dc_*_track_people[_slots] — wait on the host for the last enqueued update first and return with their own work done,
+ *     so dc_tracker_state called with asynchronous requests in flight returns the state after all of them.
+ * Errors, before any device work: DC_EINVAL naming the parameter for nb outside [1, slots] (with a slot map: outside [1, 64]), a
+ *     slot_of[b] outside [0, slots), ids without a tracker (dc_net_track_frames_async, which refuses what dc_net_forward_frames,
+ *     dc_net_assemble_people and dc_tracker_update refuse, in that order), P (max_people) outside [1, 256], a
  *     n_people[b] outside [0, P], a slot outside [0, slots) (dc_tracker_reset: -1 = all); DC_ESHAPE for a tracker whose n_joints is not
  *     the net's; whatever the assembly entry refuses.  Then DC_ENOCPU for an update in CPU mode (there is no CPU path), DC_EDEVICE for
  *     a tracker bound to another device than the calling thread's (the net's).                                                        */
@@ -812,6 +839,8 @@ int dc_tracker_destroy(dc_tracker* tracker);
 int dc_tracker_reset(dc_tracker* tracker, int slot /* -1: all */);
 int dc_tracker_update(dc_tracker* tracker, int nb, int P, const int* n_people, const double* people, long long* ids, int* place,
                       double* dist);
+int dc_tracker_update_slots(dc_tracker* tracker, int nb, int P, const int* slot_of /* [nb], NULL: image b -> slot b */,
+                            const int* n_people, const double* people, long long* ids, int* place, double* dist);
 int dc_tracker_state(dc_tracker* tracker, int slot, long long* ids, int* misses, int* hits, double* poses);
 int dc_net_track_people(dc_net* net, dc_tracker* tracker, const dc_assemble_params* p, int n_edges, const int* edges, const double* mean,
                         const double* stdev, const int* joint_order, int* n_people, double* people, int* cand, double* cost,
@@ -819,6 +848,19 @@ int dc_net_track_people(dc_net* net, dc_tracker* tracker, const dc_assemble_para
 int dc_group_track_people(dc_group* group, dc_tracker* tracker, const double* scales, int base, const dc_fuse_mirror* fm /* may be NULL */,
                           const dc_assemble_params* p, int n_edges, const int* edges, const double* mean, const double* stdev,
                           const int* joint_order, int* n_people, double* people, int* cand, double* cost, long long* ids, int* place);
+int dc_net_track_people_slots(dc_net* net, dc_tracker* tracker, const int* slot_of /* [batch], NULL: image b -> slot b */,
+                              const dc_assemble_params* p, int n_edges, const int* edges, const double* mean, const double* stdev,
+                              const int* joint_order, int* n_people, double* people, int* cand, double* cost, long long* ids, int* place);
+int dc_group_track_people_slots(dc_group* group, dc_tracker* tracker, const int* slot_of /* [batch], NULL: image b -> slot b */,
+                                const double* scales, int base, const dc_fuse_mirror* fm /* may be NULL */, const dc_assemble_params* p,
+                                int n_edges, const int* edges, const double* mean, const double* stdev, const int* joint_order,
+                                int* n_people, double* people, int* cand, double* cost, long long* ids, int* place);
+int dc_net_track_frames_async(dc_net* net, dc_tracker* tracker /* NULL: people without ids */, const dc_frame* frames /* or NULL */,
+                              const unsigned char* images /* packed BGR when frames is NULL */, int n, int height, int width, double scale,
+                              int is_device, const int* slot_of /* NULL: identity */, const dc_assemble_params* p, int n_edges,
+                              const int* edges, const double* mean, const double* stdev, const int* joint_order, int* n_people,
+                              double* people, int* cand /* may be NULL */, long long* ids, int* place /* both may be NULL; ids must be
+                              NULL when tracker is NULL */);
 
 /* ---- in-process multi-GPU forward (SURVEY 8(b)'s dc_forward_batch) -------------------------------------------------------
  * A communicator over `nexec` executors: executor k runs on devices[k] (NULL: k modulo the visible devices) on a host thread of its
