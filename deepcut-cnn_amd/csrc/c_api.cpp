@@ -917,6 +917,15 @@ int dc_tracker_state(dc_tracker* tracker, int slot, long long* ids, int* misses,
   REQUIRE(tracker);
   return guard([&] { TR(tracker)->state(slot, ids, misses, hits, poses); });
 }
+int dc_tracker_set_option(dc_tracker* tracker, int key, int value) {
+  REQUIRE(tracker);
+  return guard([&] { TR(tracker)->set_option(key, value); });
+}
+int dc_tracker_get_option(dc_tracker* tracker, int key, int* value) {
+  REQUIRE(tracker);
+  REQUIRE(value);
+  return guard([&] { *value = TR(tracker)->get_option(key); });
+}
 int dc_net_track_people(dc_net* net, dc_tracker* tracker, const dc_assemble_params* p, int n_edges, const int* edges, const double* mean,
                         const double* stdev, const int* joint_order, int* n_people, double* people, int* cand, double* cost,
                         long long* ids, int* place) {

@@ -415,6 +415,7 @@ int launch_assemble(int NB, int J, int max_det, int max_people, int min_joints, 
 struct TrackParams {
   int T, J, max_misses, min_common, motion;
   double max_dist, min_size;
+  int assign;  // the matching rule of an update: 0 = step 4 (greedy), 1 = step 4' (optimal assignment); selects the kernel instantiation
 };
 struct TrackSlot {  // the arrays of one slot inside its block
   long long* next_id;

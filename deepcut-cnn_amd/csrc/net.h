@@ -533,6 +533,9 @@ struct Tracker {
   void enqueue(int nb, int P, const int* slot_of, const int* d_np, const double* d_ppl, long long* ids, int* place, double* dist, void* stream);
   void update(int nb, int P, const int* slot_of, const int* n_people, const double* people, long long* ids, int* place, double* dist);
   void reset(int slot);  // -1: all
+  // DC_TRACK_OPT_*: host only (no device needed); set waits for the last update enqueued, then stores: later updates use the value
+  void set_option(int key, int value);
+  int get_option(int key) const;
   void state(int slot, long long* ids, int* misses, int* hits, double* poses);
 };
 

@@ -37,7 +37,7 @@ Tracker* Tracker::create(int slots, int max_tracks, int n_joints, const double* 
   if (!(min_size > 0) || !std::isfinite(min_size)) bad(who, "min_size must be finite and > 0");
   if (motion != 0 && motion != 1) bad(who, "motion must be 0 or 1");
   std::unique_ptr<Tracker> t(new Tracker());
-  t->tp = TrackParams{max_tracks, n_joints, max_misses, min_common, motion, max_dist, min_size};
+  t->tp = TrackParams{max_tracks, n_joints, max_misses, min_common, motion, max_dist, min_size, DC_TRACK_ASSIGN_GREEDY};
   t->slots = slots;
   t->sig2.resize((size_t)n_joints);
   for (int j = 0; j < n_joints; ++j) t->sig2[(size_t)j] = sigma ? sigma[j] * sigma[j] : 1.0;
@@ -165,6 +165,23 @@ void Tracker::reset(int slot) {
   if (slot < 0) HIPCHECK(hipMemsetAsync(dev, 0, (size_t)slots * slot_stride, s));
   else HIPCHECK(hipMemsetAsync(dev + (size_t)slot * slot_stride, 0, slot_stride, s));
   HIPCHECK(hipStreamSynchronize(s));
+}
+
+void Tracker::set_option(int key, int value) {
+  if (key != DC_TRACK_OPT_ASSIGN) bad("tracker_set_option", "unknown key " + std::to_string(key));
+  if (value != DC_TRACK_ASSIGN_GREEDY && value != DC_TRACK_ASSIGN_OPTIMAL)
+    bad("tracker_set_option", "DC_TRACK_OPT_ASSIGN takes DC_TRACK_ASSIGN_GREEDY (0) or DC_TRACK_ASSIGN_OPTIMAL (1), not value " + std::to_string(value));
+  RuntimeLock rl;  // no update is being enqueued meanwhile
+  if (dev) {       // nothing has been tracked yet otherwise, and nothing is in flight
+    DeviceScope on(device);
+    wait_done();
+  }
+  tp.assign = value;
+}
+
+int Tracker::get_option(int key) const {
+  if (key != DC_TRACK_OPT_ASSIGN) bad("tracker_get_option", "unknown key " + std::to_string(key));
+  return tp.assign;
 }
 
 void Tracker::state(int slot, long long* ids, int* misses, int* hits, double* poses) {

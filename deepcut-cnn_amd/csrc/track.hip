@@ -1,4 +1,5 @@
-// track.hip — people from frame to frame: the greedy association of one frame's people with a slot's live tracks (gfx950).
+// track.hip — people from frame to frame: the association of one frame's people with a slot's live tracks, greedy (step 4) or by
+// optimal assignment (step 4'), chosen per tracker (gfx950).
 //
 // PARITY UNPINNED BY THE REFERENCE: eldar/deepcut-cnn stops at the maps and has no tracker.  The rule is this project's own
 // (include/deepcut_hip.h, dc_tracker_update), restated in float64 in tests/track_ref.py.
@@ -31,10 +32,119 @@ __device__ __forceinline__ void wave_key_min(double& v, int& e) {
 }
 }  // namespace
 
+// Step 4' (include/deepcut_hip.h): the optimal assignment of the frame's n people to the slot's live tracks by the shortest augmenting
+// path Hungarian method, by the whole workgroup, behind a barrier that follows the last store to D.  -> tm[i] / pm[q] of the matched
+// pairs; the caller's barrier follows.  The rule is the procedure of the header, scan order included, so this is that procedure and no
+// other: per row r an inner loop of at most m + 1 trips, each of which prices the open columns against row i0, takes their arg-min
+// (delta, j1) and moves the duals, then one thread walks the augmenting path back.
+// Columns go to threads with a stride of 256: thread t owns j = t + 1 and j = t + 257.  People are n <= 256, so the first is a real
+// column (person t) when t < n and the second is always a dummy; the row i0 of D is therefore one coalesced read of n doubles, from
+// the scratch step 4 reads.  v[j], minv[j] and used[j] are touched by the owner of column j only — they live in its registers, two of
+// each; what other threads read is in LDS: u (the owner of a used column moves the dual of ITS row, every thread reads u[i0]), p and
+// way (the thread that walks the path reads them all).  (delta, j1) is key_min's (value, index) order: the lowest j among equal
+// minima, which is the strict `<` of the ascending scan.  A trip is two barriers, a row one more.  j0 and every exit test derive from LDS values read
+// behind a barrier — the four keys, p — so they are the same in every thread.  Both loops carry their bound as a hard trip limit: a
+// finite dummy column is always open, so delta is finite and the limits are never reached, but no input may make a workgroup spin.
+// Only subtract, add and compare, in the header's order (C - u[i0]) - v[j]; nothing here for the compiler to contract or reassociate.
+__device__ __forceinline__ void match_optimal(int T, int P, int n, double max_dist, const double* __restrict__ D, const int* live, int* tm,
+                                              int* pm) {
+  __shared__ double u[kTrackMax + 1];   // row duals, rows 1..R
+  __shared__ int p[2 * kTrackMax + 1];  // the row on column j (0 = none); p[0] = the row being inserted
+  __shared__ int way[2 * kTrackMax + 1];
+  __shared__ int rowp[kTrackMax];  // the place of row r, at r - 1
+  __shared__ double red_v[4];
+  __shared__ int red_e[4];
+  __shared__ int nrow_s;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const double inf = __builtin_huge_val();
+  if (t < T && live[t]) {
+    int rank = 0;
+    for (int i = 0; i < t; ++i) rank += live[i];
+    rowp[rank] = t;
+  }
+  if (t == 0) {
+    int total = 0;
+    for (int i = 0; i < T; ++i) total += live[i];
+    nrow_s = total;
+  }
+  u[t] = 0.0, p[t] = 0, p[t + 256] = 0, way[t] = 0, way[t + 256] = 0;
+  if (t == 0) u[256] = 0.0, p[512] = 0, way[512] = 0;
+  __syncthreads();
+  const int R = nrow_s, m = n + R;
+  const int j_a = t + 1, j_b = t + 257;  // this thread's columns
+  const bool in_a = j_a <= m, in_b = j_b <= m, real_a = t < n;
+  double v_a = 0.0, v_b = 0.0;
+  for (int r = 1; r <= R; ++r) {
+    double minv_a = inf, minv_b = inf;
+    bool used_a = false, used_b = false;
+    int j0 = 0;
+    if (t == 0) p[0] = r;
+    for (int trip = 0; trip <= m; ++trip) {
+      __syncthreads();  // the duals of the trip before, p after the walk of the row before, p[0]; red_v / red_e are free again
+      if (j0 == j_a) used_a = true;
+      if (j0 == j_b) used_b = true;
+      const int i0 = p[j0];
+      const double ui0 = u[i0];
+      double dv = inf;
+      int de = kNone;
+      if (in_a && !used_a) {
+        double c = max_dist;
+        if (real_a) {
+          const double d = D[(size_t)rowp[i0 - 1] * P + t];
+          c = d <= max_dist ? d : inf;
+        }
+        const double cur = (c - ui0) - v_a;
+        if (cur < minv_a) minv_a = cur, way[j_a] = j0;
+        if (minv_a < inf) dv = minv_a, de = j_a;
+      }
+      if (in_b && !used_b) {
+        const double cur = (max_dist - ui0) - v_b;
+        if (cur < minv_b) minv_b = cur, way[j_b] = j0;
+        if (minv_b < inf) key_min(dv, de, minv_b, j_b);
+      }
+      wave_key_min(dv, de);
+      if (lane == 0) red_v[wave] = dv, red_e[wave] = de;
+      __syncthreads();
+      double delta = red_v[0];
+      int j1 = red_e[0];
+      for (int w = 1; w < 4; ++w) key_min(delta, j1, red_v[w], red_e[w]);
+      if (j1 == kNone) break;  // no open column with a finite price: cannot happen (a dummy is always open); uniform
+      if (t == 0) u[r] += delta;  // column 0 is always used and holds row r (v[0] is never read)
+      if (in_a) {
+        if (used_a) u[p[j_a]] += delta, v_a -= delta;
+        else minv_a -= delta;
+      }
+      if (in_b) {
+        if (used_b) u[p[j_b]] += delta, v_b -= delta;
+        else minv_b -= delta;
+      }
+      j0 = j1;
+      if (p[j0] == 0) break;  // p does not change inside this loop, j1 came from LDS: uniform
+    }
+    __syncthreads();  // everybody is done with p (the exit test, the rows of the used columns) before the walk rewrites it
+    if (t == 0 && j0 != 0 && p[j0] == 0) {  // way[] of this row is in place: its last stores precede the barriers above
+      for (int k = 0; k <= m && j0 != 0; ++k) {
+        const int j1 = way[j0];
+        p[j0] = p[j1];
+        j0 = j1;
+      }
+    }
+  }
+  __syncthreads();
+  if (t < n) {
+    const int r = p[t + 1];
+    if (r != 0) {
+      const int i = rowp[r - 1];
+      pm[t] = i, tm[i] = t;
+    }
+  }
+}
+
 // One workgroup of 256 threads (4 waves) applies one image to one slot: the body of an update, steps 1-7.  Thread i owns track place i
 // in steps 1, 5 and 6, thread q owns person q in step 7.  D lives in global scratch (256 x 256 doubles do not fit in LDS beside the rest)
 // and is written and read inside this workgroup only, with a barrier in between.
-// Matching: a round takes the smallest D among unmatched pairs.  Scanning all T*P entries every round is 256 rounds of 65 536 reads at
+// Matching, step 4': match_optimal above.  Step 4: a round takes the smallest D among unmatched pairs.  Scanning all T*P entries every
+// round is 256 rounds of 65 536 reads at
 // T = P = 256, so the minimum of every ROW is kept in LDS — rv[i], rq[i] = the smallest allowed D of track i among unmatched people and
 // the lowest q that has it — and a round is (1) the arg-min over the rows, a (value, place) key whose index order is the tie rule:
 // lower place first, and within the row the lower q was kept; (2) the re-derivation of the rows the match invalidates: those whose
@@ -42,6 +152,7 @@ __device__ __forceinline__ void wave_key_min(double& v, int& e) {
 // robin.  No step depends on thread timing: same inputs, same ids.
 // The state block is read AND written here, and track_kernel calls this several times on one block with a barrier in between: `state`
 // carries no __restrict__, so that nothing loaded from it is kept across that barrier.
+template <int Assign>  // the matching rule, TrackParams::assign: the greedy instance is the kernel it was, instruction for instruction
 __device__ __forceinline__ void track_image(int b, unsigned char* state_block, int P, const TrackParams& tp,
                                             const double* __restrict__ sig2_g, double* __restrict__ dist,
                                             const int* __restrict__ n_people, const double* __restrict__ people,
@@ -150,37 +261,42 @@ __device__ __forceinline__ void track_image(int b, unsigned char* state_block, i
   }
   __syncthreads();  // D is complete (global memory written and read by this workgroup only)
 
-  // 4. greedy matching on row minima
-  auto row_min = [&](int i) {  // by one wave: rv[i], rq[i] over the unmatched people
-    double v = inf;
-    int e = kNone;
-    for (int q = lane; q < n; q += 64) {
-      if (pm[q] >= 0) continue;
-      const double d = D[(size_t)i * P + q];
-      if (d <= tp.max_dist && d < v) v = d, e = q;  // q ascends within a lane: the first of equal distances stays
-    }
-    wave_key_min(v, e);
-    if (lane == 0) rv[i] = v, rq[i] = e == kNone ? -1 : e;
-  };
-  for (int i = wave; i < T; i += 4)
-    if (live[i]) row_min(i);
-  for (;;) {
-    __syncthreads();  // the row minima of this round are in place
-    double v = inf;
-    int e = kNone;
-    if (t < T && live[t] && tm[t] < 0 && rq[t] >= 0) v = rv[t], e = t;
-    wave_key_min(v, e);
-    if (lane == 0) red_v[wave] = v, red_e[wave] = e;
-    __syncthreads();
-    v = red_v[0], e = red_e[0];
-    for (int w = 1; w < 4; ++w) key_min(v, e, red_v[w], red_e[w]);
-    if (e == kNone) break;  // the same value in every thread: the exit is uniform
-    const int wi = e, wq = rq[wi];
-    __syncthreads();  // everybody has read the winner's row before it changes
-    if (t == 0) tm[wi] = wq, pm[wq] = wi;
-    __syncthreads();
+  if constexpr (Assign == 1) {
+    // 4'. optimal assignment
+    match_optimal(T, P, n, tp.max_dist, D, live, tm, pm);
+  } else {
+    // 4. greedy matching on row minima
+    auto row_min = [&](int i) {  // by one wave: rv[i], rq[i] over the unmatched people
+      double v = inf;
+      int e = kNone;
+      for (int q = lane; q < n; q += 64) {
+        if (pm[q] >= 0) continue;
+        const double d = D[(size_t)i * P + q];
+        if (d <= tp.max_dist && d < v) v = d, e = q;  // q ascends within a lane: the first of equal distances stays
+      }
+      wave_key_min(v, e);
+      if (lane == 0) rv[i] = v, rq[i] = e == kNone ? -1 : e;
+    };
     for (int i = wave; i < T; i += 4)
-      if (live[i] && tm[i] < 0 && rq[i] == wq) row_min(i);
+      if (live[i]) row_min(i);
+    for (;;) {
+      __syncthreads();  // the row minima of this round are in place
+      double v = inf;
+      int e = kNone;
+      if (t < T && live[t] && tm[t] < 0 && rq[t] >= 0) v = rv[t], e = t;
+      wave_key_min(v, e);
+      if (lane == 0) red_v[wave] = v, red_e[wave] = e;
+      __syncthreads();
+      v = red_v[0], e = red_e[0];
+      for (int w = 1; w < 4; ++w) key_min(v, e, red_v[w], red_e[w]);
+      if (e == kNone) break;  // the same value in every thread: the exit is uniform
+      const int wi = e, wq = rq[wi];
+      __syncthreads();  // everybody has read the winner's row before it changes
+      if (t == 0) tm[wi] = wq, pm[wq] = wi;
+      __syncthreads();
+      for (int i = wave; i < T; i += 4)
+        if (live[i] && tm[i] < 0 && rq[i] == wq) row_min(i);
+    }
   }
   __syncthreads();
 
@@ -273,6 +389,7 @@ __device__ __forceinline__ void track_image(int b, unsigned char* state_block, i
 // last stores to the state (steps 5-7) and the next image's loads of it (steps 1-3) by other threads of this workgroup, and between its
 // last readers of the LDS arrays (flag, fplace, pm in step 7) and the next image's initialisation of them.  A workgroup whose slot no
 // image names returns without touching the slot.
+template <int Assign>
 __global__ __launch_bounds__(256) void track_kernel(int NB, int P, TrackParams tp, TrackSlotMap map, const double* __restrict__ sig2_g,
                                                     unsigned char* state, size_t slot_stride, double* __restrict__ dist,
                                                     const int* __restrict__ n_people, const double* __restrict__ people,
@@ -281,7 +398,7 @@ __global__ __launch_bounds__(256) void track_kernel(int NB, int P, TrackParams t
   unsigned char* block = state + (size_t)slot * slot_stride;
   for (int b = 0; b < NB; ++b) {
     if ((int)((map.w[b >> 2] >> ((b & 3) * 8)) & 0xffu) != slot) continue;  // uniform
-    track_image(b, block, P, tp, sig2_g, dist, n_people, people, ids, place);
+    track_image<Assign>(b, block, P, tp, sig2_g, dist, n_people, people, ids, place);
     __syncthreads();
   }
 }
@@ -290,12 +407,16 @@ int launch_track(int S, int NB, int P, const TrackParams& p, const double* sig2,
                  const int* n_people, const double* people, long long* ids, int* place, const TrackSlotMap& map, void* stream) {
   if (NB <= 0) return 0;
   if (S < 1 || S > 256 || NB > kTrackMaxImages || P < 1 || P > kTrackMax || p.T < 1 || p.T > kTrackMax || p.J < 1 ||
-      p.J > kPeopleMaxJoints || slot_stride % 16 || slot_stride < track_slot_bytes(p.T, p.J))
+      p.J > kPeopleMaxJoints || slot_stride % 16 || slot_stride < track_slot_bytes(p.T, p.J) || p.assign < 0 || p.assign > 1)
     return (int)hipErrorInvalidValue;
   for (int b = 0; b < NB; ++b)
     if ((int)((map.w[b >> 2] >> ((b & 3) * 8)) & 0xffu) >= S) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(track_kernel, dim3(S), dim3(256), 0, (hipStream_t)stream, NB, P, p, map, sig2, state, slot_stride, dist, n_people,
-                     people, ids, place);
+  if (p.assign == 1)  // step 4' : an instantiation of its own, so that the greedy one keeps its registers and its LDS
+    hipLaunchKernelGGL((track_kernel<1>), dim3(S), dim3(256), 0, (hipStream_t)stream, NB, P, p, map, sig2, state, slot_stride, dist,
+                       n_people, people, ids, place);
+  else
+    hipLaunchKernelGGL((track_kernel<0>), dim3(S), dim3(256), 0, (hipStream_t)stream, NB, P, p, map, sig2, state, slot_stride, dist,
+                       n_people, people, ids, place);
   return (int)hipGetLastError();
 }
 

@@ -267,6 +267,8 @@ def _load():
         "dc_tracker_update": (ci, [vp, ci, ci, vp, vp, vp, vp, vp]),
         "dc_tracker_update_slots": (ci, [vp, ci, ci, vp, vp, vp, vp, vp, vp]),
         "dc_tracker_state": (ci, [vp, ci, vp, vp, vp, vp]),
+        "dc_tracker_set_option": (ci, [vp, ci, ci]),
+        "dc_tracker_get_option": (ci, [vp, ci, C.POINTER(ci)]),
         "dc_net_track_people_slots": (ci, [vp, vp, vp, C.POINTER(AssembleParams), ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "dc_net_track_people": (ci, [vp, vp, C.POINTER(AssembleParams), ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "dc_group_track_people": (ci, [vp, vp, vp, ci, C.POINTER(FuseMirror), C.POINTER(AssembleParams), ci, vp, vp, vp, vp, vp, vp, vp, vp,
@@ -685,11 +687,19 @@ class Tracker(object):
     match needs a distance <= max_dist, a track without a match for more than max_misses updates in a row is dropped; min_size: lower
     bound in pixels of the track size the distance is normalised by; motion: 1 compares with the pose moved on by its velocity, 0 with
     the last pose.  THE DEFAULTS OF max_misses, min_common, max_dist, min_size AND sigma ARE PLACEHOLDERS, NOT TUNED ON REAL VIDEO:
-    override them.  Creation needs no device; updates need GPU mode.  The calls of this class are synchronous; updates apply in call order, those
+    override them.  assign: "greedy" (the default: the closest pair first, step 4 of the rule) or "optimal" (step 4': the assignment
+    with the smallest total distance, an unmatched track costing max_dist — two people who pass each other keep their ids where greedy
+    matching swaps them); also a property, which may change between updates: the tracks stay.
+    Creation needs no device; updates need GPU mode.  The calls of this class are synchronous; updates apply in call order, those
     enqueued by `Net.track_frames_async` included (the synchronous calls wait for them first)."""
 
-    def __init__(self, n_joints=14, slots=1, max_tracks=64, sigma=None, max_misses=5, min_common=3, max_dist=0.25, min_size=32.0, motion=1):
+    ASSIGN = {"greedy": 0, "optimal": 1}  # DC_TRACK_ASSIGN_*
+    _OPT_ASSIGN = 1  # DC_TRACK_OPT_ASSIGN
+
+    def __init__(self, n_joints=14, slots=1, max_tracks=64, sigma=None, max_misses=5, min_common=3, max_dist=0.25, min_size=32.0, motion=1,
+                 assign="greedy"):
         self._h = None
+        self._assign_value(assign)
         sig = None
         if sigma is not None:
             sig = np.ascontiguousarray(sigma, dtype=np.float64).reshape(-1)
@@ -701,6 +711,25 @@ class Tracker(object):
         _check(_lib.dc_tracker_create(C.byref(q), C.byref(h)))
         self._h = h
         self.n_joints, self.slots, self.max_tracks = int(n_joints), int(slots), int(max_tracks)
+        if assign != "greedy":
+            self.assign = assign
+
+    @classmethod
+    def _assign_value(cls, assign):
+        if not isinstance(assign, str) or assign not in cls.ASSIGN:
+            raise ValueError("assign must be one of %s, got %r" % (", ".join(repr(k) for k in sorted(cls.ASSIGN)), assign))
+        return cls.ASSIGN[assign]
+
+    @property
+    def assign(self):
+        """The matching rule of the updates to come: "greedy" or "optimal" (DC_TRACK_OPT_ASSIGN)."""
+        v = C.c_int(-1)
+        _check(_lib.dc_tracker_get_option(self._h, self._OPT_ASSIGN, C.byref(v)))
+        return [k for k, x in self.ASSIGN.items() if x == v.value][0]
+
+    @assign.setter
+    def assign(self, assign):
+        _check(_lib.dc_tracker_set_option(self._h, self._OPT_ASSIGN, self._assign_value(assign)))
 
     def __del__(self):
         if getattr(self, "_h", None):

@@ -766,6 +766,35 @@ int dc_group_flops(dc_group* group, double* out);
  *     +inf when n_c < min_common, when place i is free, or when q >= n.
  *  4. Greedy matching.  While an unmatched live track and an unmatched person with D <= max_dist remain, the pair with the smallest D
  *     is matched; ties go to the lower place i, then the lower q.
+ *  4'. Optimal assignment, INSTEAD of step 4 in a tracker whose option DC_TRACK_OPT_ASSIGN is DC_TRACK_ASSIGN_OPTIMAL (below; the
+ *     default is step 4).  Greedy matching swaps identities when two people pass each other: the closest pair is taken first and the
+ *     leftover pair forced together even when the other pairing is far better overall.  Step 4' solves the linear assignment problem.
+ *     Rows are the places live at the start of the update in ascending place order, r = 1..R (place i_r); real columns are the frame's
+ *     people, c = 1..n for person q = c - 1; dummy columns are c = n+1..n+R; m = n + R <= 512.  C[r][c] of a real column is
+ *     D[i_r][q] when `D <= max_dist` is true and +inf otherwise (a NaN distance is forbidden, as in step 4); C[r][c] of a dummy column
+ *     is max_dist for every row: an unmatched track costs max_dist.  The matching is what this procedure returns — the shortest
+ *     augmenting path Hungarian method with row duals u and column duals v, all in double, nothing but subtract, add and compare:
+ *         u[0..R] = 0, v[0..m] = 0, p[0..m] = 0, way[0..m] = 0
+ *         for r = 1..R:
+ *             p[0] = r; j0 = 0; minv[1..m] = +inf; used[0..m] = false
+ *             repeat:
+ *                 used[j0] = true; i0 = p[j0]; delta = +inf
+ *                 for j = 1..m ascending, not used[j]:
+ *                     cur = (C[i0][j] - u[i0]) - v[j]
+ *                     if cur < minv[j]: minv[j] = cur; way[j] = j0
+ *                     if minv[j] < delta: delta = minv[j]; j1 = j        (strict: the lowest j among equal minima)
+ *                 for j = 0..m: if used[j]: u[p[j]] += delta; v[j] -= delta
+ *                               else:       minv[j] -= delta
+ *                 j0 = j1
+ *             until p[j0] == 0
+ *             repeat: j1 = way[j0]; p[j0] = p[j1]; j0 = j1  until j0 == 0
+ *     Person q is matched to place i_{p[q+1]} when p[q+1] != 0; a row that sits on a dummy column is unmatched.  The total — the sum of
+ *     D over the matched pairs + max_dist * (the unmatched live tracks) — is minimal, and no matched pair has D > max_dist.  An allowed
+ *     pair with D == max_dist ties with a dummy column; the scan order above decides that tie and every other one, which is why the rule
+ *     is the procedure itself and not merely "an optimum".  Deterministic.  A dummy column with finite cost is always unused, so delta is
+ *     always finite, the inner loop marks one new column per trip and ends within m + 1 trips; the kernel holds both loops to these
+ *     bounds as hard trip limits, so that no input can make it spin.  PARITY UNPINNED BY THE REFERENCE, like the rest of the tracker:
+ *     there is no reference counterpart; tests/assign_ref.py restates the procedure in float64 loops.  Steps 1-3 and 5-7 are shared.
  *  5. Matched track.  vel[j] = (person - old pose) / (misses + 1) for the joints held by both the old pose and the person, 0 elsewhere;
  *     pose = the person's, whole (a joint the person lacks becomes not held); misses = 0; hits += 1.
  *  6. Unmatched live track.  misses += 1; pose and velocity stay; the track is freed when misses > max_misses.
@@ -779,6 +808,11 @@ int dc_group_flops(dc_group* group, double* out);
  *     naming the parameter.  Creation needs no device: the device buffer is allocated, zeroed and bound to the calling thread's device
  *     (the net's, in the chained entries) at the first update.  THE DEFAULTS THE PYTHON LAYER CHOOSES FOR max_misses, min_common,
  *     max_dist, min_size AND sigma ARE PLACEHOLDERS, NOT TUNED ON REAL VIDEO: override them.
+ * dc_tracker_set_option / dc_tracker_get_option: key DC_TRACK_OPT_ASSIGN, value DC_TRACK_ASSIGN_GREEDY (step 4, the default) or
+ *     DC_TRACK_ASSIGN_OPTIMAL (step 4').  Setting needs no device and works before the first update, like creation.  It orders itself
+ *     like the other synchronous calls: it waits for the last enqueued update, then stores the value, and every update enqueued
+ *     afterwards uses it.  The slots' state is untouched, so a sequence may switch rule between frames.  An unknown key or value is
+ *     DC_EINVAL naming it.  dc_tracker_params carries no option: it has no size field and compiled callers exist.
  * dc_tracker_update: host poses — n_people[nb], people[nb][P][J][3] (entries of q >= n_people[b] are not read) — are uploaded and
  *     image b updates slot b in one launch (one workgroup per slot).  This is how top-down poses of dc_net_forward_boxes get tracked.
  *     Outputs: ids[nb][P] (long long; -1 for q >= n and for an untracked person), place[nb][P] (int, the track place; -1 likewise; may
@@ -842,6 +876,11 @@ int dc_tracker_update(dc_tracker* tracker, int nb, int P, const int* n_people, c
 int dc_tracker_update_slots(dc_tracker* tracker, int nb, int P, const int* slot_of /* [nb], NULL: image b -> slot b */,
                             const int* n_people, const double* people, long long* ids, int* place, double* dist);
 int dc_tracker_state(dc_tracker* tracker, int slot, long long* ids, int* misses, int* hits, double* poses);
+#define DC_TRACK_OPT_ASSIGN     1
+#define DC_TRACK_ASSIGN_GREEDY  0   /* step 4, the default */
+#define DC_TRACK_ASSIGN_OPTIMAL 1   /* step 4' */
+int dc_tracker_set_option(dc_tracker* tracker, int key, int value);
+int dc_tracker_get_option(dc_tracker* tracker, int key, int* value);
 int dc_net_track_people(dc_net* net, dc_tracker* tracker, const dc_assemble_params* p, int n_edges, const int* edges, const double* mean,
                         const double* stdev, const int* joint_order, int* n_people, double* people, int* cand, double* cost,
                         long long* ids, int* place);

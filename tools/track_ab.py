@@ -6,7 +6,12 @@ and at the entry limits T = P = n = 256, there on people who each stay near thei
 any row minimum) and on a planted worst case in which every open track is nearest to the same person in every round (every round
 re-derives the row minima of all tracks that are still open), beside `Net.assemble_people` at max_det 64 and max_people 256.  Every figure is a host clock around a synchronous call, ms per call, the median
 of five windows of at least 0.5 s with the windows listed.
-    python tools/track_ab.py [--out profiles/track_ab.txt]"""
+    python tools/track_ab.py [--out profiles/track_ab.txt]
+--assign both measures the matching rules against each other instead (DC_TRACK_OPT_ASSIGN: step 4, greedy, and step 4', the optimal
+assignment): the same calls, every one on a greedy and on an optimal tracker, the two alternated in the same windows — `Net.track_people`
+and the stand-alone updates above —, with the number of inner trips step 4' takes on each case, counted by its restatement
+(tests/assign_ref.py) on the device's own distances.
+    python tools/track_ab.py --assign both [--out profiles/track_assign_ab.txt]"""
 import argparse
 import os
 import statistics
@@ -38,9 +43,99 @@ def windows(calls, n_windows=5, seconds=0.5):
     return per
 
 
+def near(n):
+    """n people on a 400-pixel grid, then the same people moved by up to 3 pixels a joint, in another order"""
+    r = np.random.RandomState(1)
+    out = np.zeros((1, n, 14, 3), np.float64)
+    side = int(np.ceil(np.sqrt(n)))
+    for q in range(n):
+        out[0, q, :, :2] = (400.0 * (q % side), 400.0 * (q // side)) + r.uniform(-40, 40, (14, 2))
+        out[0, q, :, 2] = 0.5
+    nxt = out.copy()
+    nxt[0, :, :, :2] += r.uniform(-3, 3, (n, 14, 2))
+    return out, nxt[:, r.permutation(n)]
+
+
+def contended(n):
+    """one rigid pose at x = q, then at x = 1000 + 10 q: every track's nearest open person is the SAME one in every round (the
+    leftmost of the second frame, the rightmost of the first on the way back), so every round re-derives the rows of all open tracks"""
+    r = np.random.RandomState(2)
+    body = r.uniform(-40, 40, (14, 2))
+    a, b = np.zeros((1, n, 14, 3), np.float64), np.zeros((1, n, 14, 3), np.float64)
+    for q in range(n):
+        a[0, q, :, :2], b[0, q, :, :2] = body + (q, 0), body + (1000 + 10 * q, 0)
+    a[..., 2] = b[..., 2] = 0.5
+    return a, b
+
+
+CASES = [("T 64, P = n = 32, everybody near their own track", 64, 32, near, 0.25),
+         ("T = P = n = 256, everybody near their own track", 256, 256, near, 0.25),
+         ("T = P = n = 256, motion 0, every open track nearest to the same person in every round", 256, 256, contended, 1e9)]
+
+
+def assign_ab(caffe, net, kw, say, fmt):
+    """Greedy against optimal, alternated in the same windows: Net.track_people on the held forward, then every stand-alone case."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import assign_ref
+
+    spread = lambda v: "%.4f [%.4f - %.4f]" % (statistics.median(v), min(v), max(v))  # noqa: E731
+    rules = ("greedy", "optimal")
+    trackers = {r: caffe.Tracker(n_joints=14, slots=1, max_tracks=64, assign=r) for r in rules}
+    calls = {"track_people " + r: (lambda t=trackers[r]: net.track_people(t, **kw)) for r in rules}
+    calls["assemble_people"] = lambda: net.assemble_people(**kw)
+    for call in calls.values():
+        for _ in range(20):
+            call()
+    found = len(net.assemble_people(**kw)[0]["people"])
+    per = windows(calls)
+    s = statistics.median(per["assemble_people"])
+    say("max_det 16 max_people 32 (%d people found), T 64: Net.assemble_people %s ms per call" % (found, spread(per["assemble_people"])))
+    # what step 4' had to do there: the assembled people fed to a stand-alone optimal tracker as often as the chained one saw them (the
+    # chained entry is Tracker.update bit for bit), the last update's distances handed to the restatement
+    people = net.assemble_people(**kw)[0]["people"]
+    again = caffe.Tracker(n_joints=14, slots=1, max_tracks=64, assign="optimal")
+    for _ in range(40):
+        again.update([people])
+    live = again.state()["ids"] >= 0
+    _, _, dist = again.update([people], return_dist=True)
+    count = {}
+    assign_ref.assign(dist[0], live.tolist(), len(people), 0.25, count)  # 0.25: caffe.Tracker's default max_dist
+    say("  the same frame again and again: %d live tracks against %d people, %d inner trips of step 4' per update" % (int(live.sum()), len(people), count["trips"]))
+    for r in rules:
+        v = per["track_people " + r]
+        say("  Net.track_people, %s: %s ms per call (%+.4f ms on assemble_people); windows %s" % (r, spread(v), statistics.median(v) - s, fmt(v)))
+    for name, T, n, make, max_dist in CASES:
+        first, second = make(n)
+        calls, trips = {}, None
+        for r in rules:
+            trk = caffe.Tracker(n_joints=14, slots=1, max_tracks=T, max_dist=max_dist, max_misses=1000, motion=0 if make is contended else 1, assign=r)
+            ids0, _ = trk.update(first)
+            live = trk.state()["ids"] >= 0
+            ids1, _, dist = trk.update(second, return_dist=True)
+            assert sorted(ids0[0].tolist()) == list(range(n)) and sorted(ids1[0].tolist()) == list(range(n)), (name, r)  # all born, all matched
+            if r == "optimal":
+                count = {}
+                assign_ref.assign(dist[0], live.tolist(), n, max_dist, count)
+                trips = count["trips"]
+            state = {"k": 1}
+
+            def call(trk=trk, frames=(first, second), state=state):
+                state["k"] ^= 1
+                trk.update(frames[state["k"]])
+
+            for _ in range(4):
+                call()
+            calls[r] = call
+        per = windows(calls)
+        g, o = statistics.median(per["greedy"]), statistics.median(per["optimal"])
+        say("Tracker.update %s: greedy %s ms, optimal %s ms per call (%+.4f ms, x %.2f), %d inner trips of step 4'; windows greedy %s optimal %s"
+            % (name, spread(per["greedy"]), spread(per["optimal"]), o - g, o / g, trips, fmt(per["greedy"]), fmt(per["optimal"])))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
+    ap.add_argument("--assign", default="greedy", choices=["greedy", "both"], help="both: greedy against optimal, alternated")
     a = ap.parse_args()
     import caffe
     from deepcut_tools import deepercut_prototxt, synth_weights, write_caffemodel
@@ -65,6 +160,12 @@ def main():
         "windows >= 0.5 s, calls alternated" % (H, W))
     net.forward_images(img, 1.0, want=(), pose=False)
     kw = dict(scale=1.0, threshold=0.5, radius=1, max_det=16, edges=edges, mean=mean, std=std, max_cost=30.0, seed_threshold=0.6, max_people=32)
+    if a.assign == "both":
+        assign_ab(caffe, net, kw, say, fmt)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     tracker = caffe.Tracker(n_joints=14, slots=1, max_tracks=64)
     calls = {"track_people": lambda: net.track_people(tracker, **kw), "assemble_people": lambda: net.assemble_people(**kw)}
     for call in calls.values():
@@ -81,34 +182,8 @@ def main():
         wide()
     found256 = len(wide()[0]["people"])
 
-    def near(n):
-        """n people on a 400-pixel grid, then the same people moved by up to 3 pixels a joint, in another order"""
-        r = np.random.RandomState(1)
-        out = np.zeros((1, n, 14, 3), np.float64)
-        side = int(np.ceil(np.sqrt(n)))
-        for q in range(n):
-            out[0, q, :, :2] = (400.0 * (q % side), 400.0 * (q // side)) + r.uniform(-40, 40, (14, 2))
-            out[0, q, :, 2] = 0.5
-        nxt = out.copy()
-        nxt[0, :, :, :2] += r.uniform(-3, 3, (n, 14, 2))
-        return out, nxt[:, r.permutation(n)]
-
-    def contended(n):
-        """one rigid pose at x = q, then at x = 1000 + 10 q: every track's nearest open person is the SAME one in every round (the
-        leftmost of the second frame, the rightmost of the first on the way back), so every round re-derives the rows of all open tracks"""
-        r = np.random.RandomState(2)
-        body = r.uniform(-40, 40, (14, 2))
-        a, b = np.zeros((1, n, 14, 3), np.float64), np.zeros((1, n, 14, 3), np.float64)
-        for q in range(n):
-            a[0, q, :, :2], b[0, q, :, :2] = body + (q, 0), body + (1000 + 10 * q, 0)
-        a[..., 2] = b[..., 2] = 0.5
-        return a, b
-
-    cases = [("T 64, P = n = 32, everybody near their own track", 64, 32, near, 0.25),
-             ("T = P = n = 256, everybody near their own track", 256, 256, near, 0.25),
-             ("T = P = n = 256, motion 0, every open track nearest to the same person in every round", 256, 256, contended, 1e9)]
     standalone = {"assemble_people max_det 64 max_people 256 (%d found)" % found256: wide}
-    for name, T, n, make, max_dist in cases:
+    for name, T, n, make, max_dist in CASES:
         trk = caffe.Tracker(n_joints=14, slots=1, max_tracks=T, max_dist=max_dist, max_misses=1000, motion=0 if make is contended else 1)
         first, second = make(n)
         ids0, _ = trk.update(first)
