@@ -516,7 +516,7 @@ void Comm::forward(Net* const* nets, const float* const* inputs, const int (*hw)
           for (int b = 0; b < nb; ++b) std::memcpy(st + b * img, srcs[(size_t)b], img * sizeof(float));
           net->forward_batch(st, nb, g.h, g.w, false, nullptr, nullptr, nullptr, nullptr, true);  // upload + forward enqueued on the net's own stream, not waited for
         }
-        net->emit_last_maps(pp, lp, np, 0, true, (void*)-1);                                    // ... and the maps, same stream
+        net->emit_last_maps(pp, lp, np, 0, true, DC_STREAM_OWN);                                    // ... and the maps, same stream
         HIPCHECK(hipEventRecord((hipEvent_t)ev[2 * j], (hipStream_t)net->stream));
         if (to_host) {
           HIPCHECK(hipStreamWaitEvent((hipStream_t)copy_stream[(size_t)k], (hipEvent_t)ev[2 * j], 0));

@@ -248,6 +248,22 @@ struct NetStats {  // dc_net_stats
   long long lowerings = 0, graph_instantiations = 0, plan_hits = 0, autotune_runs = 0, buffer_growths = 0, repacks = 0, sparse_packs = 0;
 };
 
+// The grow-only device buffer of the host code (runtime.cpp): every scratch, staging and table buffer of a Net and a NetGroup is one.
+// Not one, on purpose: Storage (the head state of a SyncedMemory, zero fill, buffer_growths), the Tracker's per-image scratch (sized in
+// images; allocates before it frees, after waiting for its event) and Comm::grow_dev (switches devices, shares Buf with pinned memory).
+struct DevBuf {
+  unsigned char* dev = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf();
+  // at least `bytes`; the contents do not survive a growth.  -> whether it reallocated.  A failed allocation throws and leaves the
+  // buffer empty (dev null, cap 0): the next call allocates again, never works on a null pointer
+  bool reserve(size_t bytes);
+  void* get(size_t bytes) { return reserve(bytes), dev; }
+};
+
 struct Net {
   std::string name;
   int phase = 1;
@@ -283,8 +299,7 @@ struct Net {
   void* stream = nullptr;
   bool stream_borrowed_ = false;  // `stream` belongs to the process-wide executor pool (streams.cpp): never destroyed with the net
   int device = -1;
-  double* pose_dev = nullptr;
-  size_t pose_cap = 0;
+  DevBuf pose_dev;  // the poses of a decode on their way to a host destination (decode_to)
   std::string text_buf;
   std::string proto_text;  // kept for clone()
 
@@ -418,6 +433,11 @@ struct Net {
     int cp, c0, es, ek, NB, C, H, W;
   };
   MapRef map_ref(const char* blob_name);  // device image of an output map (channel views of the merged heads included)
+  const std::vector<int>& prob_shape() const;  // (NB, J, H, W) of `prob`, host only: DC_EINVAL without the blob, DC_ESHAPE unless 4-D
+  // the device half of detect_parts, shared with NetGroup::detect_parts (net_image.cpp): the scratch carved, launch_part_select on the
+  // maps given by reference, the two downloads, and the wait for `stream`
+  static void select_parts(const MapRef& P, const MapRef& L, float thr, int radius, double scale, int max_det,
+                           const std::function<void*(size_t)>& scratch, void* stream, int* counts, double* dets);
   // assemble_people in three parts, shared with NetGroup::assemble_people (people.cpp): the checks of the parameters, the checks of the
   // edges / statistics / joint order against J joints (-> the lookup table lut[a*J + c] followed by the joint order), both host only,
   // and the device half: the three launches on maps given by reference, scratch memory from `scratch(bytes)`, everything on `stream`
@@ -432,8 +452,7 @@ struct Net {
   // waited for — the results are in the host arrays once `stream` has been, and nothing of the caller's small arguments is read after
   // the return (keep is needed then)
   struct AssembleTables {
-    unsigned char* dev = nullptr;
-    size_t cap = 0;
+    DevBuf buf;
     std::vector<unsigned char> host;  // lookup table and joint order (ints), then mean and standard deviation (doubles)
     void* stream = nullptr;           // the stream the upload ran on
   };
@@ -464,28 +483,22 @@ struct Net {
   SparseNext sparse_next_at(int ndet, const int* det);  // ... and the head run at ndet host triples
   void refresh_pack_cache();  // caller holds shared->mu: the packed-image cache emptied when the parameters changed since it was filled
   std::shared_ptr<DevVec> sparse_w_, sparse_b_;  // the head's filter image and bias (kept alive here as a plan keeps its launches')
-  unsigned char* sparse_dev_ = nullptr;
-  size_t sparse_cap_ = 0;
+  DevBuf sparse_dev_;
   // V and M of the wino_f43 launches (kernels.h wino43_workspace_bytes): sized for the largest such launch of the plan when the buffers of a
   // plan are prepared, before any forward or capture; grown (buf_gen_ bumped) but never shrunk or freed while the net lives; a clone has its own
-  unsigned char* wino43_dev_ = nullptr;
-  size_t wino43_cap_ = 0;
-  unsigned char* scratch_dev_ = nullptr;  // candidates / detections / pairwise scratch
-  size_t scratch_cap_ = 0;
-  void* scratch(size_t bytes);
-  unsigned char* img_dev_ = nullptr;  // uint8 source images uploaded from the host
-  size_t img_cap_ = 0;
-  unsigned char* frame_dev_ = nullptr;   // frame entries: FramePlanes[n], the frame readers' plane table
-  size_t frame_cap_ = 0;
+  DevBuf wino43_dev_;
+  DevBuf scratch_dev_;  // candidates / detections / pairwise scratch
+  void* scratch(size_t bytes) { return scratch_dev_.get(bytes); }
+  DevBuf img_dev_;  // uint8 source images uploaded from the host
+  const unsigned char* upload_image(const unsigned char* host, size_t bytes, void* s);  // -> the device copy in img_dev_, enqueued on s
+  DevBuf frame_dev_;   // frame entries: FramePlanes[n], the frame readers' plane table
   std::vector<FramePlanes> frame_host_;  // the host side of that table (device addresses): uploaded only when it differs from what is there
   void* frame_stream_ = nullptr;         // ... and the stream that upload ran on
   // n checked frames of h x w -> the frame readers' source: host planes staged into img_dev_ (one 2-D copy per plane on s), the plane
   // table uploaded when it differs from the one on the device, the conversion's coefficients
   FrameSource frame_source(const dc_frame* frames, int n, int h, int w, bool is_device, void* s);
-  unsigned char* tmp_dev_ = nullptr;  // horizontally resampled rows
-  size_t tmp_cap_ = 0;
-  unsigned char* box_dev_ = nullptr;  // box entry: BoxPrepItem[n] then PoseDecodeItem[n]
-  size_t box_cap_ = 0;
+  DevBuf tmp_dev_;  // horizontally resampled rows
+  DevBuf box_dev_;  // box entry: BoxPrepItem[n] then PoseDecodeItem[n] (net_internal.h box_decode_offset / box_table_bytes)
   std::vector<unsigned char> box_host_;  // the host side of that table (outlives its upload)
   int box_n_ = 0;                     // boxes of the last prep_boxes
   bool box_mirror_ = false;           // ... and whether it read them flipped left to right
@@ -537,16 +550,6 @@ struct Tracker {
   void set_option(int key, int value);
   int get_option(int key) const;
   void state(int slot, long long* ids, int* misses, int* hits, double* poses);
-};
-
-struct DevBuf {  // a grow-only device buffer
-  unsigned char* dev = nullptr;
-  size_t cap = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf();
-  void* get(size_t bytes);  // at least `bytes`; the contents do not survive a growth
 };
 
 // ---- pyramid-grouped execution (round 4) ---------------------------------------------------------------------------------

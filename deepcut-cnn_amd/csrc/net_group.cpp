@@ -687,11 +687,10 @@ void NetGroup::choose_lane_streams(GroupPlan& gp, void* s, bool use_graph) {
 void NetGroup::forward_batch(const float* const* inputs, const int* n, const int* h, const int* w, bool is_device, float* const* prob,
                              float* const* loc, float* const* next, void* user_stream) {
   if (!inputs || !n || !h || !w) throw DcError(DC_EINVAL, "group forward: null argument");
-  const bool own_async = user_stream == (void*)-1;
-  if (own_async) user_stream = nullptr;
+  const CallStream cs(user_stream);
   std::vector<Storage*> ins;
   for (size_t c = 0; c < nets.size(); ++c) ins.push_back(&nets[c]->begin_batch(n[c], h[c], w[c]));
-  void* s = user_stream ? user_stream : stream();
+  void* s = cs.on(stream());
   for (size_t c = 0; c < nets.size(); ++c) {
     Storage& in = *ins[c];
     const int C = in.dim(1);
@@ -707,7 +706,7 @@ void NetGroup::forward_batch(const float* const* inputs, const int* n, const int
   enqueue(s);
   for (size_t c = 0; c < nets.size(); ++c)
     nets[c]->emit_maps(prob ? prob[c] : nullptr, loc ? loc[c] : nullptr, next ? next[c] : nullptr, is_device, s);
-  if (!(is_device && (user_stream || own_async))) HIPCHECK(hipStreamSynchronize((hipStream_t)s));
+  cs.finish(is_device, s);
 }
 
 void NetGroup::forward_images(const unsigned char* const* bgr, const int* n, const int* h, const int* w, const double* scale, bool is_device,
@@ -723,10 +722,9 @@ void NetGroup::forward_images(const unsigned char* const* bgr, const int* n, con
     }
   }
   if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "forward_images() in CPU mode: libdeepcut_hip provides the MI355X path only");
-  const bool own_async = user_stream == (void*)-1;
-  if (own_async) user_stream = nullptr;
+  const CallStream cs(user_stream);
   nets[0]->ensure_device();
-  void* s = user_stream ? user_stream : stream();
+  void* s = cs.on(stream());
   for (size_t c = 0; c < nets.size(); ++c) {
     if (!frames) {
       nets[c]->prep_images(bgr[c], n[c], h[c], w[c], scale[c], is_device, s, mirror && mirror[c] != 0);
@@ -757,7 +755,7 @@ void NetGroup::forward_images(const unsigned char* const* bgr, const int* n, con
     // decode on the group's stream; a host destination synchronises inside (the maps are complete there: same stream)
     if (pose && pose[c]) nets[c]->decode_pose(scale[c], pose[c], is_device, s);
   }
-  if (!(is_device && (user_stream || own_async))) HIPCHECK(hipStreamSynchronize((hipStream_t)s));
+  cs.finish(is_device, s);
 }
 
 void NetGroup::forward_boxes(const unsigned char* bgr, int h, int w, bool is_device, const int* boxes, const double* scales, int n,
@@ -786,10 +784,9 @@ void NetGroup::forward_boxes(const unsigned char* bgr, int h, int w, bool is_dev
   if (frame) check_frames("forward_boxes_frame", frame, 1, h, w);
   else if (!bgr) throw DcError(DC_EINVAL, "group forward_boxes: null image");
   if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "forward_boxes() in CPU mode: libdeepcut_hip provides the MI355X path only");
-  const bool own_async = user_stream == (void*)-1;
-  if (own_async) user_stream = nullptr;
+  const CallStream cs(user_stream);
   nets[0]->ensure_device();
-  void* s = user_stream ? user_stream : stream();
+  void* s = cs.on(stream());
   const unsigned char* src = bgr;
   bool dev = is_device;
   dc_frame staged{};  // a host frame: member 0 stages it, the others read that copy
@@ -808,23 +805,12 @@ void NetGroup::forward_boxes(const unsigned char* bgr, int h, int w, bool is_dev
     nets[c]->emit_maps(prob ? prob[c] : nullptr, loc ? loc[c] : nullptr, next ? next[c] : nullptr, is_device, s);
     if (pose && pose[c]) nets[c]->decode_boxes(pose[c], is_device, s);
   }
-  if (!(is_device && (user_stream || own_async))) HIPCHECK(hipStreamSynchronize((hipStream_t)s));
+  cs.finish(is_device, s);
 }
 
 // ---- multi-scale fusion of the members' maps (the rule: include/deepcut_hip.h, dc_group_fuse_maps; the kernel: pose.hip) -------------
 // PARITY UNPINNED BY THE REFERENCE: eldar/deepcut-cnn stops at the maps and has no multi-scale combination of them; only the
 // label encoding of its training layer (src/caffe/layers/pose_data_layer.cpp:686-802) is restated, in the gain / bias table below.
-DevBuf::~DevBuf() { dev_free(dev); }
-void* DevBuf::get(size_t bytes) {
-  if (bytes > cap) {
-    dev_free(dev);
-    dev = nullptr, cap = 0;
-    dev_alloc((void**)&dev, bytes);
-    cap = bytes;
-  }
-  return dev;
-}
-
 static const char* const kFuseMaps[3] = {"prob", "loc_pred", "next_pred"};
 
 // Host only: what is wrong with the arguments is said before any device work (and with or without a device).
@@ -1042,14 +1028,13 @@ void NetGroup::fuse_maps(const double* scales, int base, int n_edges, const doub
   if (!use[0] && !use[1] && !use[2]) return;
   const MirrorPlan mp = check_mirror("fuse_maps", fm_in, base, use, n_edges, C);
   if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "fuse_maps() in CPU mode: libdeepcut_hip provides the MI355X path only");
-  const bool own_async = user_stream == (void*)-1;
-  if (own_async) user_stream = nullptr;
+  const CallStream cs(user_stream);
   nets[0]->ensure_device();
-  void* s = user_stream ? user_stream : stream();
+  void* s = cs.on(stream());
   const FusedMaps fm = fuse(scales, base, use, mean, stdev, s, mp);
   emit_fused(fm, dst, is_device, s);
   fuse_done(s);
-  if (!(is_device && (user_stream || own_async))) HIPCHECK(hipStreamSynchronize((hipStream_t)s));
+  cs.finish(is_device, s);
 }
 
 void NetGroup::emit_fused(const FusedMaps& fm, float* const dst[3], bool is_device, void* s) {
@@ -1072,28 +1057,16 @@ void NetGroup::emit_fused(const FusedMaps& fm, float* const dst[3], bool is_devi
 // ---- single-person and box poses from the fused maps (dc_group_decode_pose, dc_group_decode_boxes; include/deepcut_hip.h) ---------------
 // PARITY UNPINNED BY THE REFERENCE: the reference decodes every scale on its own and keeps one (estimate_pose.py:119-126); decoding the
 // fused maps is this project's own rule.
-// the pose doubles of a decode on `s`: straight into a device destination, or through the group's scratch to the host
-template <typename Launch>
-static void decode_to(DevBuf& scratch, size_t cnt, double* out, bool is_device, void* s, const Launch& launch) {
-  if (is_device) {
-    KCHECK(launch(out));
-    return;
-  }
-  double* dev = (double*)scratch.get(cnt * sizeof(double));
-  KCHECK(launch(dev));
-  HIPCHECK(hipMemcpyAsync(out, dev, cnt * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)s));
-}
-
+// (decode_to, net_internal.h: straight into a device destination, or through the group's scratch to the host)
 void NetGroup::decode_pose(const double* scales, int base, double* pose, bool is_device, void* user_stream, const FuseMirror* fm_in) {
   const bool use[3] = {true, true, false};
   int C[3], NB;
   check_fuse("decode_pose", scales, base, use, 0, nullptr, nullptr, C, NB);
   const MirrorPlan mp = check_mirror("decode_pose", fm_in, base, use, 0, C);
   if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "decode_pose() in CPU mode");
-  const bool own_async = user_stream == (void*)-1;
-  if (own_async) user_stream = nullptr;
+  const CallStream cs(user_stream);
   nets[0]->ensure_device();
-  void* s = user_stream ? user_stream : stream();
+  void* s = cs.on(stream());
   const FusedMaps fm = fuse(scales, base, use, nullptr, nullptr, s, mp);
   const Net::MapRef &P = fm.map[0], &L = fm.map[1];
   if (L.C != 2 * P.C) throw DcError(DC_ESHAPE, "decode_pose: loc_pred must have 2 channels per joint and the score map's size");
@@ -1101,7 +1074,7 @@ void NetGroup::decode_pose(const double* scales, int base, double* pose, bool is
     return launch_pose_decode(P.ptr, P.cp, P.c0, L.ptr, L.cp, L.c0, P.ek, P.NB, P.H, P.W, P.C, scales[base], to, s);
   });
   fuse_done(s);
-  if (!(is_device && (user_stream || own_async))) HIPCHECK(hipStreamSynchronize((hipStream_t)s));
+  cs.finish(is_device, s);
 }
 
 void NetGroup::decode_boxes(const double* pyramid, int base, float* prob, float* loc, double* pose, bool is_device, void* user_stream,
@@ -1130,15 +1103,14 @@ void NetGroup::decode_boxes(const double* pyramid, int base, float* prob, float*
   if (n <= 0) throw DcError(DC_EINVAL, w + "the members hold no boxes: run forward_boxes first");
   for (int m = 0; m < M; ++m) {
     const Net& net = *nets[(size_t)m];
-    const size_t prep_b = ((size_t)n * sizeof(BoxPrepItem) + 15) / 16 * 16;
-    if (NB != n || net.box_host_.size() != prep_b + (size_t)n * sizeof(PoseDecodeItem))
+    if (NB != n || net.box_host_.size() != box_table_bytes(n))
       throw DcError(DC_EINVAL, w + "the maps of member " + std::to_string(m) + " are not those of its last boxes (" + std::to_string(NB) + " images, " +
                                    std::to_string(n) + " boxes)");
   }
   if (!prob && !loc && !pose) return;
   if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "decode_boxes() in CPU mode");
   // per (member, box) the reflected column's ws = (crop width - 1) * the scale the member ran that box at
-  const size_t prep_b = ((size_t)n * sizeof(BoxPrepItem) + 15) / 16 * 16;
+  const size_t prep_b = box_decode_offset(n);
   std::vector<double> ws((size_t)M * n, 0.0);
   for (int m = 0; m < M && !mp.on.empty(); ++m) {
     if (!mp.on[(size_t)m]) continue;
@@ -1146,23 +1118,22 @@ void NetGroup::decode_boxes(const double* pyramid, int base, float* prob, float*
     const PoseDecodeItem* dec = reinterpret_cast<const PoseDecodeItem*>(nets[(size_t)m]->box_host_.data() + prep_b);
     for (int i = 0; i < n; ++i) ws[(size_t)m * n + i] = (double)(items[i].w - 1) * dec[i].scale;
   }
-  const bool own_async = user_stream == (void*)-1;
-  if (own_async) user_stream = nullptr;
+  const CallStream cs(user_stream);
   nets[0]->ensure_device();
-  void* s = user_stream ? user_stream : stream();
+  void* s = cs.on(stream());
   const FusedMaps fm = fuse(pyramid, base, use, nullptr, nullptr, s, mp, &ws);
   emit_fused(fm, dst, is_device, s);
   if (pose) {
     const Net::MapRef &P = fm.map[0], &L = fm.map[1];
     if (L.C != 2 * P.C) throw DcError(DC_ESHAPE, "decode_boxes: loc_pred must have 2 channels per joint and the score map's size");
     // the base member's own items: scale scales[i] * pyramid[base], offset (x0, y0), the crop's own canvas on the base grid
-    const PoseDecodeItem* items = reinterpret_cast<const PoseDecodeItem*>(nets[(size_t)base]->box_dev_ + prep_b);
+    const PoseDecodeItem* items = reinterpret_cast<const PoseDecodeItem*>(nets[(size_t)base]->box_dev_.dev + prep_b);
     decode_to(people_scratch_, (size_t)P.NB * 5 * P.C, pose, is_device, s, [&](double* to) {
       return launch_pose_decode_items(P.ptr, P.cp, P.c0, L.ptr, L.cp, L.c0, P.ek, P.NB, P.H, P.W, P.C, items, to, s);
     });
   }
   fuse_done(s);
-  if (!(is_device && (user_stream || own_async))) HIPCHECK(hipStreamSynchronize((hipStream_t)s));
+  cs.finish(is_device, s);
 }
 
 void NetGroup::detect_parts(const double* scales, int base, float thr, int radius, int max_det, int* counts, double* dets, const FuseMirror* fm_in) {
@@ -1178,18 +1149,7 @@ void NetGroup::detect_parts(const double* scales, int base, float thr, int radiu
   const FusedMaps fm = fuse(scales, base, use, nullptr, nullptr, s, mp);
   const Net::MapRef &P = fm.map[0], &L = fm.map[1];
   if (L.C != 2 * P.C) throw DcError(DC_ESHAPE, "detect_parts: loc_pred must have 2 channels per joint and the score map's size");
-  const int lists = P.NB * P.C;
-  const size_t cnt_b = ((size_t)lists * sizeof(int) + 255) / 256 * 256;
-  const size_t spill_b = (size_t)lists * P.H * P.W * sizeof(unsigned long long);  // every cell may be a local maximum
-  const size_t out_b = (size_t)lists * max_det * 5 * sizeof(double);
-  unsigned char* at = (unsigned char*)people_scratch_.get(cnt_b + spill_b + out_b);
-  int* cnt = (int*)at;
-  unsigned long long* spill = (unsigned long long*)(at + cnt_b);
-  double* out = (double*)(at + cnt_b + spill_b);
-  KCHECK(launch_part_select(P.ptr, P.cp, P.c0, L.ptr, L.cp, L.c0, P.ek, P.NB, P.H, P.W, P.C, thr, radius, scales[base], max_det, spill, cnt, out, s));
-  HIPCHECK(hipMemcpyAsync(counts, cnt, (size_t)lists * sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)s));
-  HIPCHECK(hipMemcpyAsync(dets, out, out_b, hipMemcpyDeviceToHost, (hipStream_t)s));
-  HIPCHECK(hipStreamSynchronize((hipStream_t)s));
+  Net::select_parts(P, L, thr, radius, scales[base], max_det, [this](size_t bytes) { return people_scratch_.get(bytes); }, s, counts, dets);
   fuse_done(s);
 }
 
@@ -1202,10 +1162,7 @@ void NetGroup::assemble_people(const double* scales, int base, const Net::Assemb
   Net::AssembleParams q = p;
   q.scale = scales[base];
   Net::check_assemble_params(q);
-  auto ip = nets[(size_t)base]->blob_index.find("prob");
-  if (ip == nets[(size_t)base]->blob_index.end()) throw DcError(DC_EINVAL, "net has no 'prob' blob");
-  const std::vector<int>& pshape = nets[(size_t)base]->blobs[ip->second]->st->shape;
-  if (pshape.size() != 4) throw DcError(DC_ESHAPE, "'prob' is not a 4-D map");
+  const std::vector<int>& pshape = nets[(size_t)base]->prob_shape();
   const std::vector<int> table = Net::check_assemble_graph(q, pshape[1], n_edges, edges, mean, stdev, joint_order);
   check_fuse("assemble_people", scales, base, use, n_edges, mean, stdev, C, NB);
   const MirrorPlan mp = check_mirror("assemble_people", fm_in, base, use, n_edges, C);

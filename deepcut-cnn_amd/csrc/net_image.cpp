@@ -124,14 +124,9 @@ FrameSource Net::frame_source(const dc_frame* frames, int n, int h, int w, bool 
   } else {
     // the planes as they are, minus the pitch padding: no converted image is made on the host, and 1.5 bytes per pixel travel for NV12
     const size_t per = (size_t)rb[0] * rows[0] + (planes > 1 ? (size_t)rb[1] * rows[1] : 0), bytes = per * n;
-    if (bytes > img_cap_) {
-      dev_free(img_dev_);
-      img_dev_ = nullptr;
-      dev_alloc((void**)&img_dev_, bytes);
-      img_cap_ = bytes;
-    }
+    unsigned char* img = (unsigned char*)img_dev_.get(bytes);
     for (int i = 0; i < n; ++i) {
-      unsigned char* d[2] = {img_dev_ + per * i, img_dev_ + per * i + (size_t)rb[0] * rows[0]};
+      unsigned char* d[2] = {img + per * i, img + per * i + (size_t)rb[0] * rows[0]};
       for (int k = 0; k < planes; ++k)
         HIPCHECK(hipMemcpy2DAsync(d[k], (size_t)rb[k], frames[i].plane[k], (size_t)frames[i].pitch[k], (size_t)rb[k], (size_t)rows[k],
                                   hipMemcpyHostToDevice, (hipStream_t)s));
@@ -141,21 +136,15 @@ FrameSource Net::frame_source(const dc_frame* frames, int n, int h, int w, bool 
   // the table, as the box table: a grow-only device buffer filled from a host copy that outlives the upload — and left alone when it
   // already holds these very entries (a stream of frames decoded into one surface pool, or staged into the same buffer)
   const size_t tb = (size_t)n * sizeof(FramePlanes);
-  bool same = frame_dev_ && frame_stream_ == s && frame_host_.size() == table.size() && std::memcmp(frame_host_.data(), table.data(), tb) == 0;
-  if (tb > frame_cap_) {
-    dev_free(frame_dev_);
-    frame_dev_ = nullptr;
-    dev_alloc((void**)&frame_dev_, tb);
-    frame_cap_ = tb;
-    same = false;
-  }
+  bool same = frame_dev_.dev && frame_stream_ == s && frame_host_.size() == table.size() && std::memcmp(frame_host_.data(), table.data(), tb) == 0;
+  if (frame_dev_.reserve(tb)) same = false;
   if (!same) {
     frame_host_ = table;
-    HIPCHECK(hipMemcpyAsync(frame_dev_, frame_host_.data(), tb, hipMemcpyHostToDevice, (hipStream_t)s));
+    HIPCHECK(hipMemcpyAsync(frame_dev_.dev, frame_host_.data(), tb, hipMemcpyHostToDevice, (hipStream_t)s));
     frame_stream_ = s;
   }
   FrameSource fs{};
-  fs.planes = reinterpret_cast<const FramePlanes*>(frame_dev_);
+  fs.planes = reinterpret_cast<const FramePlanes*>(frame_dev_.dev);
   fs.reader = format == DC_PIX_NV12 ? kReadNv12 : kReadBgr;
   if (format == DC_PIX_NV12) frame_csc(frames[0].matrix, frames[0].range, fs);
   return fs;
@@ -166,17 +155,20 @@ void Net::forward_images(const unsigned char* bgr, int n, int h, int w, double s
   if (frames) check_frames("forward_frames", frames, n, h, w);
   if (Context::get().mode != DC_MODE_GPU)
     throw DcError(DC_ENOCPU, "forward_images() in CPU mode: libdeepcut_hip provides the MI355X path only");
-  const bool own_async = user_stream == (void*)-1;
-  if (own_async) user_stream = nullptr;
+  const CallStream cs(user_stream);
   // (the net's own stream exists only after ensure_device(): prep_images resolves a null `s` to it)
-  prep_images(bgr, n, h, w, scale, is_device, user_stream, false, frames);
-  void* s = user_stream ? user_stream : stream;
+  prep_images(bgr, n, h, w, scale, is_device, cs.user, false, frames);
+  void* s = cs.on(stream);
   enqueue_plan(s);
   emit_maps(prob, loc, next, is_device, s);
-  if (pose) {
-    decode_pose(scale, pose, is_device, (user_stream || own_async) ? s : nullptr);
-  }
-  if (!(is_device && (user_stream || own_async))) HIPCHECK(hipStreamSynchronize((hipStream_t)s));
+  if (pose) decode_pose(scale, pose, is_device, cs.async() ? s : nullptr);
+  cs.finish(is_device, s);
+}
+
+const unsigned char* Net::upload_image(const unsigned char* host, size_t bytes, void* s) {
+  void* d = img_dev_.get(bytes);
+  HIPCHECK(hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, (hipStream_t)s));
+  return (const unsigned char*)d;
 }
 
 void Net::prep_images(const unsigned char* bgr, int n, int h, int w, double scale, bool is_device, void* s, bool mirror, const dc_frame* frames) {
@@ -193,20 +185,12 @@ void Net::prep_images(const unsigned char* bgr, int n, int h, int w, double scal
   const int ph = h + kPad, pw = w + kPad;              // the replicate-padded image (never materialised)
   const int use_h = std::min(out_h, new_h), use_w = std::min(out_w, new_w);  // part of the resized image on the canvas
   const unsigned char* src = bgr;
-  const size_t bytes = (size_t)n * h * w * 3;
   ImagePrepParams q{};
   if (frames) {
     q.frame = frame_source(frames, n, h, w, is_device, s);
     src = nullptr;
   } else if (!is_device) {
-    if (bytes > img_cap_) {
-      dev_free(img_dev_);
-      img_dev_ = nullptr;
-      dev_alloc((void**)&img_dev_, bytes);
-      img_cap_ = bytes;
-    }
-    HIPCHECK(hipMemcpyAsync(img_dev_, bgr, bytes, hipMemcpyHostToDevice, (hipStream_t)s));
-    src = img_dev_;
+    src = upload_image(bgr, (size_t)n * h * w * 3, s);
   }
   const bool need_x = new_w != pw, need_y = new_h != ph;
   q.src = src;
@@ -230,14 +214,7 @@ void Net::prep_images(const unsigned char* bgr, int n, int h, int w, double scal
     hold_x = resample_table(pw, new_w);
     const ResampleTable& tx = *hold_x;
     q.x_bounds = tx.dev_bounds, q.x_coeffs = tx.dev_coeffs, q.x_ksize = tx.ksize;
-    const size_t tb = (size_t)n * q.rows * use_w * 4;
-    if (tb > tmp_cap_) {
-      dev_free(tmp_dev_);
-      tmp_dev_ = nullptr;
-      dev_alloc((void**)&tmp_dev_, tb);
-      tmp_cap_ = tb;
-    }
-    q.tmp = tmp_dev_;
+    q.tmp = (unsigned char*)tmp_dev_.get((size_t)n * q.rows * use_w * 4);
   }
   KCHECK(launch_image_prep(q, s));
   in.head = HEAD_AT_GPU;
@@ -277,14 +254,13 @@ void Net::forward_boxes(const unsigned char* bgr, int h, int w, bool is_device, 
   else if (!bgr) throw DcError(DC_EINVAL, "forward_boxes: null image");
   if (Context::get().mode != DC_MODE_GPU)
     throw DcError(DC_ENOCPU, "forward_boxes() in CPU mode: libdeepcut_hip provides the MI355X path only");
-  const bool own_async = user_stream == (void*)-1;
-  if (own_async) user_stream = nullptr;
-  prep_boxes(bgr, h, w, is_device, boxes, scales, n, canvas_h, canvas_w, user_stream, false, frame);
-  void* s = user_stream ? user_stream : stream;
+  const CallStream cs(user_stream);
+  prep_boxes(bgr, h, w, is_device, boxes, scales, n, canvas_h, canvas_w, cs.user, false, frame);  // (resolves a null `s`, as prep_images)
+  void* s = cs.on(stream);
   enqueue_plan(s);
   emit_maps(prob, loc, next, is_device, s);
-  if (pose) decode_boxes(pose, is_device, (user_stream || own_async) ? s : nullptr);
-  if (!(is_device && (user_stream || own_async))) HIPCHECK(hipStreamSynchronize((hipStream_t)s));
+  if (pose) decode_boxes(pose, is_device, cs.async() ? s : nullptr);
+  cs.finish(is_device, s);
 }
 
 const unsigned char* Net::prep_boxes(const unsigned char* bgr, int h, int w, bool is_device, const int* boxes, const double* scales, int n,
@@ -298,23 +274,15 @@ const unsigned char* Net::prep_boxes(const unsigned char* bgr, int h, int w, boo
     q.frame = frame_source(frame, 1, h, w, is_device, s);
     src = nullptr;
   } else if (!is_device) {
-    const size_t bytes = (size_t)h * w * 3;
-    if (bytes > img_cap_) {
-      dev_free(img_dev_);
-      img_dev_ = nullptr;
-      dev_alloc((void**)&img_dev_, bytes);
-      img_cap_ = bytes;
-    }
-    HIPCHECK(hipMemcpyAsync(img_dev_, bgr, bytes, hipMemcpyHostToDevice, (hipStream_t)s));
-    src = img_dev_;
+    src = upload_image(bgr, (size_t)h * w * 3, s);
   }
   // the per-box table: windows, use_h / use_w and the Pillow tables of each axis (one cached table per distinct (extent, size)),
   // followed by the decode's scale / offset / valid cells
   const int kPad = 64;
-  const size_t prep_b = ((size_t)n * sizeof(BoxPrepItem) + 15) / 16 * 16, bytes = prep_b + (size_t)n * sizeof(PoseDecodeItem);
+  const size_t bytes = box_table_bytes(n);
   box_host_.assign(bytes, 0);
   BoxPrepItem* items = reinterpret_cast<BoxPrepItem*>(box_host_.data());
-  PoseDecodeItem* dec = reinterpret_cast<PoseDecodeItem*>(box_host_.data() + prep_b);
+  PoseDecodeItem* dec = reinterpret_cast<PoseDecodeItem*>(box_host_.data() + box_decode_offset(n));
   std::vector<std::shared_ptr<ResampleTable>> hold;  // the tables outlive a cache flush until the launch is enqueued
   for (int i = 0; i < n; ++i) {
     const int x0 = boxes[4 * i], y0 = boxes[4 * i + 1], bw = boxes[4 * i + 2] - x0, bh = boxes[4 * i + 3] - y0;
@@ -334,19 +302,13 @@ const unsigned char* Net::prep_boxes(const unsigned char* bgr, int h, int w, boo
     dec[i].scale = scales[i], dec[i].dx = x0, dec[i].dy = y0;
     dec[i].rows = out_h / 8, dec[i].cols = out_w / 8;  // the crop's own canvas in map cells (stride 8)
   }
-  if (bytes > box_cap_) {
-    dev_free(box_dev_);
-    box_dev_ = nullptr;
-    dev_alloc((void**)&box_dev_, bytes);
-    box_cap_ = bytes;
-  }
-  HIPCHECK(hipMemcpyAsync(box_dev_, box_host_.data(), bytes, hipMemcpyHostToDevice, (hipStream_t)s));
+  HIPCHECK(hipMemcpyAsync(box_dev_.get(bytes), box_host_.data(), bytes, hipMemcpyHostToDevice, (hipStream_t)s));
   box_n_ = n;
   box_mirror_ = mirror;
   q.src = src;
   q.img_h = h, q.img_w = w, q.n = n;
   q.out_h = canvas_h, q.out_w = canvas_w;
-  q.items = reinterpret_cast<const BoxPrepItem*>(box_dev_);
+  q.items = reinterpret_cast<const BoxPrepItem*>(box_dev_.dev);
   q.dst = in.dev, q.dst_ekind = in.ekind, q.dst_cp = in.cp();
   q.mean[0] = 104.f, q.mean[1] = 117.f, q.mean[2] = 123.f;  // _MEAN, estimate_pose.py:26
   q.mirror = mirror ? 1 : 0;
@@ -360,24 +322,12 @@ void Net::decode_boxes(double* out, bool is_device, void* user_stream) {
   if (L.C != 2 * P.C || L.H != P.H || L.W != P.W || L.NB != P.NB || L.ek != P.ek)
     throw DcError(DC_ESHAPE, "forward_boxes: loc_pred must have 2 channels per joint and the score map's size");
   if (P.NB != box_n_) throw DcError(DC_EINVAL, "forward_boxes: the maps are not those of the last boxes");
-  const size_t prep_b = ((size_t)box_n_ * sizeof(BoxPrepItem) + 15) / 16 * 16;
-  const PoseDecodeItem* items = reinterpret_cast<const PoseDecodeItem*>(box_dev_ + prep_b);
+  const PoseDecodeItem* items = reinterpret_cast<const PoseDecodeItem*>(box_dev_.dev + box_decode_offset(box_n_));
   void* s = user_stream ? user_stream : stream;
-  if (is_device) {
-    KCHECK(launch_pose_decode_items(P.ptr, P.cp, P.c0, L.ptr, L.cp, L.c0, P.ek, P.NB, P.H, P.W, P.C, items, out, s));
-    if (!user_stream) HIPCHECK(hipStreamSynchronize((hipStream_t)s));
-    return;
-  }
-  const size_t cnt = (size_t)P.NB * 5 * P.C;
-  if (cnt > pose_cap) {
-    dev_free(pose_dev);
-    pose_dev = nullptr;
-    dev_alloc((void**)&pose_dev, cnt * sizeof(double));
-    pose_cap = cnt;
-  }
-  KCHECK(launch_pose_decode_items(P.ptr, P.cp, P.c0, L.ptr, L.cp, L.c0, P.ek, P.NB, P.H, P.W, P.C, items, pose_dev, s));
-  HIPCHECK(hipMemcpyAsync(out, pose_dev, cnt * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)s));
-  HIPCHECK(hipStreamSynchronize((hipStream_t)s));
+  decode_to(pose_dev, (size_t)P.NB * 5 * P.C, out, is_device, s, [&](double* to) {
+    return launch_pose_decode_items(P.ptr, P.cp, P.c0, L.ptr, L.cp, L.c0, P.ek, P.NB, P.H, P.W, P.C, items, to, s);
+  });
+  if (!is_device || !user_stream) HIPCHECK(hipStreamSynchronize((hipStream_t)s));  // a host destination: always
 }
 
 // _pose_from_mats (python/pose/estimate_pose.py:131-143) on the device: reads the `prob` and `loc_pred`
@@ -385,48 +335,15 @@ void Net::decode_boxes(double* out, bool is_device, void* user_stream) {
 // returns 5 x J doubles per image — the 10 MB of maps need not cross PCIe for single-person decoding.
 void Net::decode_pose(double scale, double* out, bool is_device, void* user_stream) {
   if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "decode_pose() in CPU mode");
-  auto ip = blob_index.find("prob"), il = blob_index.find("loc_pred");
-  if (ip == blob_index.end() || il == blob_index.end()) throw DcError(DC_EINVAL, "net has no 'prob' / 'loc_pred' blobs");
-  Storage& P = *blobs[ip->second]->st;
-  Storage& L = *blobs[il->second]->st;
-  if (P.head == UNINITIALIZED || L.head == UNINITIALIZED) throw DcError(DC_EINVAL, "decode_pose: run forward() first");
-  if (L.dim(1) != 2 * P.dim(1) || L.dim(2) != P.dim(2) || L.dim(3) != P.dim(3) || L.dim(0) != P.dim(0))
-    throw DcError(DC_ESHAPE, "decode_pose: loc_pred must have 2 channels per joint and the score map's size");
   ensure_device();
-  auto img = [&](Storage& s, const void*& ptr, int& cp, int& c0) {
-    if (s.view_of >= 0) {
-      ptr = storages[s.view_of]->dev;
-      cp = storages[s.view_of]->cp();
-      c0 = s.view_c0;
-    } else {
-      if (s.head == HEAD_AT_CPU || s.head == UNINITIALIZED) sync_to_device(s);
-      ptr = s.dev;
-      cp = s.cp();
-      c0 = 0;
-    }
-  };
-  const void *pp, *lp;
-  int pcp, pc0, lcp, lc0;
-  const int pek = P.view_of >= 0 ? storages[P.view_of]->ekind : P.ekind;
-  img(P, pp, pcp, pc0);
-  img(L, lp, lcp, lc0);
-  const int NB = P.dim(0), J = P.dim(1), H = P.dim(2), W = P.dim(3);
+  const MapRef P = map_ref("prob"), L = map_ref("loc_pred");
+  if (L.C != 2 * P.C || L.H != P.H || L.W != P.W || L.NB != P.NB || L.ek != P.ek)
+    throw DcError(DC_ESHAPE, "decode_pose: loc_pred must have 2 channels per joint and the score map's size");
   void* s = user_stream ? user_stream : stream;
-  const size_t cnt = (size_t)NB * 5 * J;
-  if (is_device) {
-    KCHECK(launch_pose_decode(pp, pcp, pc0, lp, lcp, lc0, pek, NB, H, W, J, scale, out, s));
-    if (!user_stream) HIPCHECK(hipStreamSynchronize((hipStream_t)s));
-    return;
-  }
-  if (cnt > pose_cap) {
-    dev_free(pose_dev);
-    pose_dev = nullptr;
-    dev_alloc((void**)&pose_dev, cnt * sizeof(double));
-    pose_cap = cnt;
-  }
-  KCHECK(launch_pose_decode(pp, pcp, pc0, lp, lcp, lc0, pek, NB, H, W, J, scale, pose_dev, s));
-  HIPCHECK(hipMemcpyAsync(out, pose_dev, cnt * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)s));
-  HIPCHECK(hipStreamSynchronize((hipStream_t)s));
+  decode_to(pose_dev, (size_t)P.NB * 5 * P.C, out, is_device, s, [&](double* to) {
+    return launch_pose_decode(P.ptr, P.cp, P.c0, L.ptr, L.cp, L.c0, P.ek, P.NB, P.H, P.W, P.C, scale, to, s);
+  });
+  if (!is_device || !user_stream) HIPCHECK(hipStreamSynchronize((hipStream_t)s));  // a host destination: always
 }
 
 Net::MapRef Net::map_ref(const char* blob_name) {
@@ -449,14 +366,12 @@ Net::MapRef Net::map_ref(const char* blob_name) {
   return r;
 }
 
-void* Net::scratch(size_t bytes) {
-  if (bytes > scratch_cap_) {
-    dev_free(scratch_dev_);
-    scratch_dev_ = nullptr;
-    dev_alloc((void**)&scratch_dev_, bytes);
-    scratch_cap_ = bytes;
-  }
-  return scratch_dev_;
+const std::vector<int>& Net::prob_shape() const {
+  auto ip = blob_index.find("prob");
+  if (ip == blob_index.end()) throw DcError(DC_EINVAL, "net has no 'prob' blob");
+  const std::vector<int>& shape = blobs[ip->second]->st->shape;
+  if (shape.size() != 4) throw DcError(DC_ESHAPE, "'prob' is not a 4-D map");
+  return shape;
 }
 
 // Part candidates: non-maximum suppression of every score map + location refinement, on the device.
@@ -468,6 +383,11 @@ void Net::detect_parts(double scale, float thr, int radius, int max_det, int* co
   const MapRef P = map_ref("prob"), L = map_ref("loc_pred");
   if (L.C != 2 * P.C || L.H != P.H || L.W != P.W || L.NB != P.NB || L.es != P.es)
     throw DcError(DC_ESHAPE, "detect_parts: loc_pred must have 2 channels per joint and the score map's size");
+  select_parts(P, L, thr, radius, scale, max_det, [this](size_t bytes) { return scratch(bytes); }, stream, counts, dets);
+}
+
+void Net::select_parts(const MapRef& P, const MapRef& L, float thr, int radius, double scale, int max_det,
+                       const std::function<void*(size_t)>& scratch, void* stream, int* counts, double* dets) {
   const int lists = P.NB * P.C;
   const size_t cnt_b = ((size_t)lists * sizeof(int) + 255) / 256 * 256;
   const size_t spill_b = (size_t)lists * P.H * P.W * sizeof(unsigned long long);  // every cell may be a local maximum

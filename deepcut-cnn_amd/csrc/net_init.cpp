@@ -99,15 +99,7 @@ Net::~Net() {
     if (ps->graph_exec) (void)hipGraphExecDestroy((hipGraphExec_t)ps->graph_exec);
   if (stream && stream_borrowed_) pool_stream_release(stream);
   else if (stream) (void)hipStreamDestroy((hipStream_t)stream);
-  dev_free(pose_dev);
-  dev_free(scratch_dev_);
-  dev_free(wino43_dev_);
-  dev_free(img_dev_);
-  dev_free(tmp_dev_);
-  dev_free(frame_dev_);
-  dev_free(box_dev_);
-  dev_free(sparse_dev_);
-  dev_free(asm_tables_.dev);
+  // (the DevBuf members release their memory after this body: the stream is gone first, as it always was)
 }
 
 Net* Net::create(const std::string& text, int phase, const Net* clone_of) {

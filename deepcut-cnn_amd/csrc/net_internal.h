@@ -1,14 +1,17 @@
 // net_internal.h — what the translation units of the graph runtime share and nobody else sees (net.h is the interface).
 // Round 5: csrc/net.cpp (3 700 lines) was split by concern, no behaviour change:
-//   runtime.cpp   Caffe context, the process-wide runtime lock, device allocation / fills / uploads, Storage (SyncedMemory + Blob)
+//   runtime.cpp   Caffe context, the process-wide runtime lock, device allocation / fills / uploads, DevBuf (the grow-only device
+//                 buffer, net.h), Storage (SyncedMemory + Blob)
 //   net_init.cpp  Net::Init semantics: InsertSplits, layer set-up and shape inference, weight files
 //   net_lower.cpp the lowering to a launch plan and the per-shape plan cache
 //   net_tune.cpp  tile selection by measurement, the tune-cache file, set_tile / reports
 //   net_run.cpp   execution: uploads, SyncedMemory moves, launches, hipGraph capture, the batch / request entries, map output
-//   net_image.cpp image entry (pre-processing on the device), pose decode, multi-person consumers, plan / profile / debug text
+//   net_image.cpp image entry (pre-processing on the device), pose decode, multi-person consumers, plan / profile / debug text;
+//                 the map readers on MapRefs that Net and NetGroup share (select_parts; people.cpp: assemble_maps)
 //   net_group.cpp NetGroup: pyramid-grouped execution
 //   streams.cpp   the process-wide pool of executor streams chosen by measurement (round 5)
 //   multi_gpu.cpp in-process multi-GPU forward of the C ABI (round 5)
+// This header: CallStream (the one stream rule of the entries), decode_to and the box table's layout (shared by the readers).
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -52,6 +55,36 @@ void dev_upload(void* dst, const void* src, size_t bytes, void* s);
 void dev_free(void* p);
 void dev_alloc(void** p, size_t bytes);
 void storage_to_device_impl(Storage& s, void* stream, bool wait);
+
+// ---- the stream rule of the entries that take a `stream` (include/deepcut_hip.h, dc_net_forward_batch) ----------------------------
+// NULL: the executor's own stream, synchronous.  A caller's stream, or DC_STREAM_OWN (the executor's own): asynchronous when the buffers
+// are device memory, nothing is waited for; host destinations are always waited for.
+struct CallStream {
+  void* user;  // the caller's stream, else null
+  bool own;    // DC_STREAM_OWN
+  explicit CallStream(void* user_stream) : user(user_stream == DC_STREAM_OWN ? nullptr : user_stream), own(user_stream == DC_STREAM_OWN) {}
+  void* on(void* own_stream) const { return user ? user : own_stream; }  // the caller's stream, or the executor's own
+  bool async() const { return user || own; }
+  void finish(bool is_device, void* s) const {
+    if (!(is_device && async())) HIPCHECK(hipStreamSynchronize((hipStream_t)s));
+  }
+};
+
+// ---- shared by the map readers of Net and NetGroup (net_image.cpp, net_group.cpp) -------------------------------------------------
+// the pose doubles of a decode on `s`: straight into a device destination, or through `scratch` to the host (enqueued, not waited for)
+template <typename Launch>
+void decode_to(DevBuf& scratch, size_t cnt, double* out, bool is_device, void* s, const Launch& launch) {
+  if (is_device) {
+    KCHECK(launch(out));
+    return;
+  }
+  double* dev = (double*)scratch.get(cnt * sizeof(double));
+  KCHECK(launch(dev));
+  HIPCHECK(hipMemcpyAsync(out, dev, cnt * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)s));
+}
+// the box table of n boxes (Net::box_dev_ / box_host_): BoxPrepItem[n], padded to 16 bytes, then PoseDecodeItem[n]
+inline size_t box_decode_offset(int n) { return ((size_t)n * sizeof(BoxPrepItem) + 15) / 16 * 16; }
+inline size_t box_table_bytes(int n) { return box_decode_offset(n) + (size_t)n * sizeof(PoseDecodeItem); }
 // library's own and only kernel launches are recorded — nothing another thread does can belong to the capture.
 template <class F>
 hipGraphExec_t capture_graph(void* cs, F&& enqueue) {

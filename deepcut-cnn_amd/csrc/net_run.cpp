@@ -102,9 +102,9 @@ void Net::run_launch(const Launch& l, void* s) {
         if (!l.form_w) throw DcError(DC_EINVAL, "launch '" + l.label + "' has no filter image of form " + form->name);
         g.w = l.form_w->dev;
         if (l.variant == kWinoF43) {  // its own image, and this executor's V / M (prepare_buffers sized it for every launch that carries the image)
-          if (!l.form_w43 || l.in2 >= 0 || wino43_cap_ < wino43_workspace_bytes(g)) throw DcError(DC_EINVAL, "launch '" + l.label + "' cannot run as form " + form->name);
+          if (!l.form_w43 || l.in2 >= 0 || wino43_dev_.cap < wino43_workspace_bytes(g)) throw DcError(DC_EINVAL, "launch '" + l.label + "' cannot run as form " + form->name);
           g.w = l.form_w43->dev;
-          g.form_ws = wino43_dev_;
+          g.form_ws = wino43_dev_.dev;
         }
         if (form->own_scale) {  // (wino_h23: the row scale of ITS image, the 1/4 of the staged pixels)
           if (!l.form_scale || l.in2 >= 0) throw DcError(DC_EINVAL, "launch '" + l.label + "' cannot run as form " + form->name);
@@ -204,11 +204,7 @@ void prepare_wino43(Net& n, bool& grew) {
   size_t need = 0;
   for (auto& l : n.plan)
     if (l.kind == Launch::CONV && l.form_w43) need = std::max(need, wino43_workspace_bytes(l.cg));
-  if (need <= n.wino43_cap_) return;
-  dev_free(n.wino43_dev_);
-  n.wino43_dev_ = nullptr, n.wino43_cap_ = 0;
-  dev_alloc((void**)&n.wino43_dev_, need);
-  n.wino43_cap_ = need;
+  if (!n.wino43_dev_.reserve(need)) return;
   ++n.buf_gen_;
   grew = true;
 }
@@ -385,11 +381,10 @@ void Net::emit_last_maps(void* prob, void* loc, void* next, int elem, bool is_de
   if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "emit_maps() in CPU mode");
   if (elem != 0 && elem != 1) throw DcError(DC_EINVAL, "element type must be 0 (float32) or 1 (the net's 16-bit type)");
   ensure_device();
-  const bool own_async = user_stream == (void*)-1;
-  if (own_async) user_stream = nullptr;
-  void* s = user_stream ? user_stream : stream;
+  const CallStream cs(user_stream);
+  void* s = cs.on(stream);
   emit_maps(prob, loc, next, is_device, s, elem == 1 ? 2 : 4);
-  if (!(is_device && (user_stream || own_async))) HIPCHECK(hipStreamSynchronize((hipStream_t)s));
+  cs.finish(is_device, s);
 }
 
 void Net::forward_batch(const float* input, int n, int h, int w, bool is_device, float* prob, float* loc, float* next,
@@ -397,9 +392,8 @@ void Net::forward_batch(const float* input, int n, int h, int w, bool is_device,
   if (host_async && (is_device || user_stream)) throw DcError(DC_EINVAL, "forward_host_async takes host buffers and runs on the net's own stream");
   Storage& in = begin_batch(n, h, w);
   const int C = in.dim(1);
-  const bool own_async = user_stream == (void*)-1;  // DC_STREAM_OWN: the net's stream, no final sync
-  if (own_async) user_stream = nullptr;
-  void* s = user_stream ? user_stream : stream;
+  const CallStream cs(user_stream);
+  void* s = cs.on(stream);
   size_t cnt = in.count();
   if (is_device) {
     KCHECK(launch_nchw_to_nhwc(input, in.dev, in.ekind, n, C, h, w, in.cp(), s));
@@ -411,7 +405,7 @@ void Net::forward_batch(const float* input, int n, int h, int w, bool is_device,
   in.head = HEAD_AT_GPU;
   enqueue_plan(s);
   emit_maps(prob, loc, next, is_device, s);
-  if (!(is_device && (user_stream || own_async)) && !host_async) HIPCHECK(hipStreamSynchronize((hipStream_t)s));
+  if (!host_async) cs.finish(is_device, s);
 }
 
 void Net::forward_host_images(const float* const* inputs, int n, int h, int w) {
@@ -433,9 +427,8 @@ void Net::forward_requests(int n, const float* const* inputs, int h, int w, floa
                            void* user_stream) {
   Storage& in = begin_batch(n, h, w);
   const int C = in.dim(1);
-  const bool own_async = user_stream == (void*)-1;
-  if (own_async) user_stream = nullptr;
-  void* s = user_stream ? user_stream : stream;
+  const CallStream cs(user_stream);
+  void* s = cs.on(stream);
   const long img = (long)h * w * in.cp();
   for (int i = 0; i < n; ++i) KCHECK(launch_nchw_to_nhwc(inputs[i], in.dev_at(i * img), in.ekind, 1, C, h, w, in.cp(), s));
   in.head = HEAD_AT_GPU;
@@ -452,7 +445,7 @@ void Net::forward_requests(int n, const float* const* inputs, int h, int w, floa
       if (o.dst[i])
         KCHECK(launch_nhwc_to_nchw((const unsigned char*)m.ptr + (size_t)i * per * m.es, o.dst[i], m.ek, 1, m.C, m.H, m.W, m.cp, m.c0, s));
   }
-  if (!(user_stream || own_async)) HIPCHECK(hipStreamSynchronize((hipStream_t)s));
+  cs.finish(true, s);  // every buffer of a request is device memory
 }
 
 }  // namespace dc

@@ -150,10 +150,7 @@ void Net::assemble_people(const AssembleParams& q, int n_edges, const int* edges
                           const int* joint_order, int* n_people, double* people, int* cand, double* cost, Tracker* tracker, long long* ids,
                           int* place, const int* slot_of) {
   check_assemble_params(q);
-  auto ip = blob_index.find("prob");
-  if (ip == blob_index.end()) throw DcError(DC_EINVAL, "net has no 'prob' blob");
-  const std::vector<int>& pshape = blobs[ip->second]->st->shape;
-  if (pshape.size() != 4) throw DcError(DC_ESHAPE, "'prob' is not a 4-D map");
+  const std::vector<int>& pshape = prob_shape();
   const std::vector<int> table = check_assemble_graph(q, pshape[1], n_edges, edges, mean, stdev, joint_order);
   if (tracker) tracker->check_call("track_people", pshape[0], q.max_people, pshape[1], slot_of);
   // (the arguments above are refused with or without a device; from here on the device is needed)
@@ -200,10 +197,7 @@ void Net::track_frames_async(Tracker* tracker, const dc_frame* frames, const uns
   if (frames) check_frames("track_frames_async", frames, n, h, w);
   // ... what assemble_people refuses (the batch of the forward to come is n; the joints do not depend on it) ...
   check_assemble_params(p);
-  auto ip = blob_index.find("prob");
-  if (ip == blob_index.end()) throw DcError(DC_EINVAL, "net has no 'prob' blob");
-  const std::vector<int>& pshape = blobs[ip->second]->st->shape;
-  if (pshape.size() != 4) throw DcError(DC_ESHAPE, "'prob' is not a 4-D map");
+  const std::vector<int>& pshape = prob_shape();
   const std::vector<int> table = check_assemble_graph(p, pshape[1], n_edges, edges, mean, stdev, joint_order);
   // ... and what the tracker refuses
   if (tracker) tracker->check_call("track_frames_async", n, p.max_people, pshape[1], slot_of);
@@ -264,24 +258,18 @@ void Net::assemble_maps(const MapRef& P, const MapRef& L, const MapRef& N, const
     std::vector<unsigned char> now(tab_b + st_b, 0);
     std::memcpy(now.data(), table.data(), table.size() * sizeof(int));
     if (E) std::memcpy(now.data() + tab_b, stats.data(), stats.size() * sizeof(double));
-    bool same = keep->dev && keep->stream == stream && keep->host == now;
-    if (now.size() > keep->cap) {
-      dev_free(keep->dev);
-      keep->dev = nullptr, keep->cap = 0;
-      dev_alloc((void**)&keep->dev, now.size());
-      keep->cap = now.size();
-      same = false;
-    }
+    bool same = keep->buf.dev && keep->stream == stream && keep->host == now;
+    if (keep->buf.reserve(now.size())) same = false;
     if (!same) {
       // rare (another graph, other statistics): what is in flight on this stream may still read the old content, and an upload from the
       // host copy may not have read it yet — both are waited for before either is replaced
       HIPCHECK(hipStreamSynchronize(s));
       keep->host.swap(now);
-      HIPCHECK(hipMemcpyAsync(keep->dev, keep->host.data(), keep->host.size(), hipMemcpyHostToDevice, s));
+      HIPCHECK(hipMemcpyAsync(keep->buf.dev, keep->host.data(), keep->host.size(), hipMemcpyHostToDevice, s));
       keep->stream = stream;
     }
-    d_tab = (int*)keep->dev;
-    d_mean = (double*)(keep->dev + tab_b);
+    d_tab = (int*)keep->buf.dev;
+    d_mean = (double*)(keep->buf.dev + tab_b);
   } else {
     d_tab = (int*)take(tab_b);
     d_mean = (double*)take(st_b);

@@ -85,6 +85,15 @@ void dev_alloc(void** p, size_t bytes) {
   RuntimeLock rl;
   HIPCHECK(hipMalloc(p, bytes));
 }
+DevBuf::~DevBuf() { dev_free(dev); }
+bool DevBuf::reserve(size_t bytes) {
+  if (bytes <= cap) return false;
+  dev_free(dev);
+  dev = nullptr, cap = 0;
+  dev_alloc((void**)&dev, bytes);
+  cap = bytes;
+  return true;
+}
 // The launches `enqueue(cs)` puts on stream cs, as an executable graph.  Relaxed mode: cs is a non-blocking stream of the
 // ---- Storage ------------------------------------------------------------------------------------
 Storage::~Storage() {

@@ -155,18 +155,13 @@ Net::SparseNext Net::sparse_next(int nslots, int ntriples) {
   const size_t map_b = up((size_t)a.NB * a.H * a.W * a.Cout * sizeof(float));
   const size_t work_b = up(((size_t)4 + 4 * (size_t)std::max(nslots, 1)) * sizeof(int));
   const size_t cell_b = up((size_t)std::max(ntriples, 1) * 3 * sizeof(int));
-  if (map_b + work_b + cell_b > sparse_cap_) {
-    if (stream) HIPCHECK(hipStreamSynchronize((hipStream_t)stream));
-    dev_free(sparse_dev_);
-    sparse_dev_ = nullptr, sparse_cap_ = 0;
-    dev_alloc((void**)&sparse_dev_, map_b + work_b + cell_b);
-    sparse_cap_ = map_b + work_b + cell_b;
-  }
-  a.out = (float*)sparse_dev_;
-  r.work = (int*)(sparse_dev_ + map_b);
-  r.cells = (int*)(sparse_dev_ + map_b + work_b);
+  if (map_b + work_b + cell_b > sparse_dev_.cap && stream) HIPCHECK(hipStreamSynchronize((hipStream_t)stream));  // before it is replaced
+  unsigned char* base = (unsigned char*)sparse_dev_.get(map_b + work_b + cell_b);
+  a.out = (float*)base;
+  r.work = (int*)(base + map_b);
+  r.cells = (int*)(base + map_b + work_b);
   r.ekind = ek3;
-  r.N = MapRef{sparse_dev_, a.Cout, 0, 4, kElemF32, a.NB, a.Cout, a.H, a.W};
+  r.N = MapRef{base, a.Cout, 0, 4, kElemF32, a.NB, a.Cout, a.H, a.W};
   return r;
 }
 
@@ -206,7 +201,7 @@ void Net::pairwise_at(int ndet, const int* det, float* out) {
     N = sn.N, ddet = sn.cells;
     (void)scratch(((size_t)ndet * 3 * sizeof(int) + 255) / 256 * 256 + (size_t)ndet * N.C * sizeof(float));
   }
-  float* dout = (float*)(scratch_dev_ + ((size_t)ndet * 3 * sizeof(int) + 255) / 256 * 256);
+  float* dout = (float*)(scratch_dev_.dev + ((size_t)ndet * 3 * sizeof(int) + 255) / 256 * 256);
   KCHECK(launch_map_gather(N.ptr, N.cp, N.c0, N.ek, N.H, N.W, N.C, ndet, ddet, dout, stream));
   HIPCHECK(hipMemcpyAsync(out, dout, (size_t)ndet * N.C * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)stream));
   HIPCHECK(hipStreamSynchronize((hipStream_t)stream));
