@@ -1,12 +1,14 @@
 """-m gpu: every layer type of the path stand-alone (Layer::Forward_gpu surface = a one-layer prototxt,
 DC_OPT_FUSE 0, weights injected through net.params) and every one of the 26 distinct convolution /
 deconvolution configurations of the DeeperCut net at reduced spatial size, against the
-CPU oracle.  fp32; bound 1e-4 relative to the output range (the reference's own conv-test bound)."""
+CPU oracle.  fp32; bound 1e-4 relative to the output range (the reference's own conv-test bound); the 26 configurations are also
+held to the error of a plain float32 sum (tests/f32_ref.py: 3 x the maximum and 2 x the RMS error of a sequential float32 sum)."""
 import zlib
 
 import numpy as np
 import pytest
 
+import f32_ref as F
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -58,20 +60,38 @@ T2 = [
 ]
 
 
-@pytest.mark.parametrize("cfg", T2, ids=lambda c: "%s_k%ds%dp%dd%d_%dto%d" % (c[0], c[1], c[2], c[3], c[4], c[6], c[7]))
+def t2_id(c):
+    return "%s_k%ds%dp%dd%d_%dto%d" % (c[0], c[1], c[2], c[3], c[4], c[6], c[7])
+
+
+def t2_data(cfg, batch):
+    """input, filters and bias of a T2 row (tests/test_f32_bound_host.py runs the blocked float32 models on the same data)"""
+    kind, k, s, p, d, bias, cin, cout, h, w = cfg
+    rs = np.random.RandomState(zlib.crc32(repr(cfg).encode()) & 0x7fffffff)  # (hash() of a tuple holding a str moves with PYTHONHASHSEED)
+    x = rs.randn(batch, cin, h, w).astype(np.float32)
+    wshape = (cout, cin, k, k) if kind == "conv" else (cin, cout, k, k)
+    wt = (rs.randn(*wshape) / np.sqrt(cin * k * k)).astype(np.float32)
+    b = rs.randn(cout).astype(np.float32) if bias else None
+    return x, wt, b
+
+
+def t2_case(cfg, batch, form="conv"):
+    """(ref64, model32, pixels) of a T2 row; form: what the layer ran on, "wino23" for a 3x3 row the per-shape timing gave to wino_f23"""
+    kind, k, s, p, d, bias, cin, cout, h, w = cfg
+    x, wt, b = t2_data(cfg, batch)
+    return F.layer_case(kind if form == "conv" else form, x, wt, *F.fold_affine64(cout, b), stride=s, pad=p, dilation=d)
+
+
+@pytest.mark.parametrize("cfg", T2, ids=t2_id)
 @pytest.mark.parametrize("batch", [1, 2])
 def test_conv_deconv_configs(gpu_caffe, cfg, batch):
     kind, k, s, p, d, bias, cin, cout, h, w = cfg
-    rs = np.random.RandomState(zlib.crc32(repr(cfg).encode()) & 0x7fffffff)  # (hash() of a tuple holding a str moves with PYTHONHASHSEED)
     typ = "Convolution" if kind == "conv" else "Deconvolution"
     text = _inp("x", (batch, cin, h, w)) + (
         'layer { name: "l" type: "%s" bottom: "x" top: "y" convolution_param { num_output: %d kernel_size: %d '
         "stride: %d pad: %d dilation: %d bias_term: %s } }" % (typ, cout, k, s, p, d, "true" if bias else "false"))
     net = _net(gpu_caffe, text)
-    x = rs.randn(batch, cin, h, w).astype(np.float32)
-    wshape = (cout, cin, k, k) if kind == "conv" else (cin, cout, k, k)
-    wt = (rs.randn(*wshape) / np.sqrt(cin * k * k)).astype(np.float32)
-    b = rs.randn(cout).astype(np.float32) if bias else None
+    x, wt, b = t2_data(cfg, batch)
     net.params["l"][0].data[...] = wt
     if bias:
         net.params["l"][1].data[...] = b
@@ -79,6 +99,12 @@ def test_conv_deconv_configs(gpu_caffe, cfg, batch):
     got = net.forward()["y"]
     ref = (O.conv_forward if kind == "conv" else O.deconv_forward)(x, wt, b, s, p, d)
     _check(got, ref)
+    # ... and to a plain float32 sum's error.  The per-shape timing may have given a 3x3 row to a Winograd form, whose own roundings are
+    # part of what it is: that run is held to the form's float32 emulation, every other one to the sequential sum
+    plan = net.plan_text()
+    form = "wino43" if "wino_f43" in plan else "wino23" if "wino_f23" in plan else "conv"
+    ref64, model, pixels = t2_case(cfg, batch, form)
+    F.assert_f32_tight(got, ref64, model, "%s: %s batch %d" % ({"conv": "gather-GEMM and streaming tiles (T2)"}.get(form, form + " (T2)"), t2_id(cfg), batch), pixels)
 
 
 def test_deconv_closed_form_on_gpu(gpu_caffe):

@@ -2,7 +2,9 @@
 by default it is used only where the per-shape timing finds it faster.  Against the CPU oracle (the reference's arithmetic for these
 layers: one SGEMM per image, base_conv_layer.cpp:326-341, + BatchNorm / Scale / Eltwise / ReLU) at 2e-5 x range — the float32 path's
 stated bound for whole nets is 1e-3; a single layer of K <= 512 products differs by summation order only — and against a gather-GEMM tile on
-the same layer (not bit for bit: four interleaved K runs and two accumulators are another grouping of the same sums).
+the same layer (not bit for bit: four interleaved K runs and two accumulators are another grouping of the same sums); form and tile
+are also held to the error of a plain float32 sum (tests/f32_ref.py: 3 x the maximum, 2 x the RMS error of a sequential float32 sum
+against a float64 reference; measured, worst over the cases: ws1x1f 0.79 / 0.80, the tile 0.82 / 0.74).
 Covers every K the kernel takes (64, 128, 256, 512), ragged pixel counts (M % 16 != 0, M < 16, a single pixel), walks of 0 / 1 / 2 / 3 / many steps per
 workgroup (the peeled first steps, the steady loop), batches, shortcut + ReLU and plain epilogues, layers without BatchNorm / Scale, the
 shapes the form does not take, and the reference's own expansion layers inside the full net (ResNet-152.prototxt res4*_branch2c, res5*_branch2c)."""
@@ -11,6 +13,7 @@ import os
 import numpy as np
 import pytest
 
+import f32_ref as F
 from conftest import rand_image
 from test_gpu_stream1x1 import _net_text, _weights
 
@@ -67,15 +70,27 @@ def _run(caffe, proto, weights, inputs, out, mode, monkeypatch):
     return net.blobs[out].data.copy(), net.plan_text()
 
 
-@pytest.mark.parametrize("case", CASES)
-def test_single_layers_match_the_oracle_and_the_tiles(gpu_caffe, case, monkeypatch):
+def case_data(case):
     n, cin, cout, h, w, shortcut, relu, affine = case
-    proto, out = _net_text(n, cin, cout, h, w, shortcut, relu, affine)
     rs = np.random.RandomState(cin + cout + h)
     weights = _weights(rs, cin, cout, affine)
     inputs = {"data": rs.randn(n, cin, h, w).astype(np.float32)}
     if shortcut:
         inputs["sc"] = rs.randn(n, cout, h, w).astype(np.float32)
+    return weights, inputs
+
+
+def f32_case(case, weights, inputs):
+    """(ref64, model32, pixels) of tests/f32_ref.py: the 1x1 layer as a sequential float32 sum over its input channels + the epilogue"""
+    a, b = F.fold_layers64(case[2], weights)
+    return F.layer_case("conv", inputs["data"], weights[0][2][0], a, b, inputs.get("sc"), case[6])
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_single_layers_match_the_oracle_and_the_tiles(gpu_caffe, case, monkeypatch):
+    n, cin, cout, h, w, shortcut, relu, affine = case
+    proto, out = _net_text(n, cin, cout, h, w, shortcut, relu, affine)
+    weights, inputs = case_data(case)
     got, plan = _run(gpu_caffe, proto, weights, inputs, out, "1", monkeypatch)
     assert "ws1x1f" in plan, plan
     direct, plan0 = _run(gpu_caffe, proto, weights, inputs, out, "0", monkeypatch)
@@ -85,6 +100,9 @@ def test_single_layers_match_the_oracle_and_the_tiles(gpu_caffe, case, monkeypat
     rng = max(1.0, float(np.abs(ref).max()))
     assert float(np.abs(got - ref).max()) <= 2e-5 * rng
     assert float(np.abs(got - direct).max()) <= 2e-5 * rng
+    ref64, model, pixels = f32_case(case, weights, inputs)
+    F.assert_f32_tight(got, ref64, model, "ws1x1f: %s" % (case,), pixels)
+    F.assert_f32_tight(direct, ref64, model, "the tile beside ws1x1f: %s" % (case,), pixels)
 
 
 def test_layers_the_form_does_not_take_keep_their_tiles(gpu_caffe, monkeypatch):

@@ -1,12 +1,15 @@
 """-m gpu: the Winograd F(2x2,3x3) form of the stride-1 3x3 convolutions (wino_f32.hip wino_f23_kernel), forced with
 DC_WINOGRAD=1 (8 waves per workgroup) and DC_WINOGRAD=2 (the 16-wave form, tile name wino_f23_w16); by default either is used
 only where the per-shape timing finds it faster.  Against the CPU oracle.
-Winograd changes the rounding (transforms in fp32), not the mathematics: the bound stays the path's 1e-3, measured ~1e-5."""
+Winograd changes the rounding (transforms in fp32), not the mathematics.  Single layers: 1e-4 x max(1, range) against the oracle, and
+the error of the form's own float32 emulation with sequential sums (tests/f32_ref.py wino23_f32: at most 3 x its maximum and 2 x its RMS
+error against a float64 reference; measured, worst over the cases and both wave counts: 1.27 and 1.00).  Whole nets: the path's 1e-3."""
 import os
 
 import numpy as np
 import pytest
 
+import f32_ref as F
 from conftest import rand_image
 
 pytestmark = pytest.mark.gpu
@@ -53,22 +56,36 @@ CASES = [  # n, cin, cout, h, w, dilation, relu, residual
 ]
 
 
+def case_data(case):
+    """weights and input of a single-layer case; tests/test_gpu_winograd_mixed.py and test_gpu_winograd_blocks.py draw theirs the same way"""
+    n, cin, cout, h, w, dil, relu, resid = case
+    rs = np.random.RandomState(cin + h)
+    weights = [("c", "Convolution", [(rs.randn(cout, cin, 3, 3) / np.sqrt(9.0 * cin)).astype(np.float32)]),
+               ("bn", "BatchNorm", [rs.randn(cout).astype(np.float32) * 0.1, rs.uniform(0.5, 1.5, cout).astype(np.float32),
+                                    np.array([1.0], np.float32)]),
+               ("sc", "Scale", [rs.uniform(0.5, 1.5, cout).astype(np.float32), rs.randn(cout).astype(np.float32) * 0.1])]
+    return weights, rs.randn(n, cin, h, w).astype(np.float32)
+
+
+def wino_case(case, weights, x, kind="wino23"):
+    """(ref64, model32, pixels) of a 3x3 layer + BatchNorm / Scale (+ shortcut = the input) (+ ReLU): the float64 reference and the form's
+    float32 emulation (f32_ref.layer_case makes them once per data; block geometry and wave count do not change a tile's arithmetic)"""
+    dil, relu, resid = case[5], case[6], len(case) > 7 and case[7]
+    a, b = F.fold_layers64(case[2], weights)
+    return F.layer_case(kind, x, weights[0][2][0], a, b, x if resid else None, relu, 1, dil, dil)
+
+
 @pytest.mark.parametrize("case", CASES)
 def test_single_layers_match_oracle(gpu_caffe, case, _force):
     n, cin, cout, h, w, dil, relu, resid = case
     if resid and cin != cout:
         pytest.skip("residual needs equal channel counts")
     proto, out = _conv_net(n, cin, cout, h, w, dil, relu, resid)
-    rs = np.random.RandomState(cin + h)
-    weights = [("c", "Convolution", [(rs.randn(cout, cin, 3, 3) / np.sqrt(9.0 * cin)).astype(np.float32)]),
-               ("bn", "BatchNorm", [rs.randn(cout).astype(np.float32) * 0.1, rs.uniform(0.5, 1.5, cout).astype(np.float32),
-                                    np.array([1.0], np.float32)]),
-               ("sc", "Scale", [rs.uniform(0.5, 1.5, cout).astype(np.float32), rs.randn(cout).astype(np.float32) * 0.1])]
+    weights, x = case_data(case)
     net = gpu_caffe.Net(proto, gpu_caffe.TEST, from_text=True)
     for name, _t, blobs in weights:
         for p, b in zip(net.params[name], blobs):
             p.data[...] = b
-    x = rs.randn(n, cin, h, w).astype(np.float32)
     net.blobs["data"].data[...] = x
     net.forward()
     assert _force in net.plan_text(), "the layer was not lowered to the Winograd kernel"
@@ -77,6 +94,8 @@ def test_single_layers_match_oracle(gpu_caffe, case, _force):
     assert got.shape == ref.shape
     err = float(np.abs(got - ref).max())
     assert err <= 1e-4 * max(1.0, float(np.abs(ref).max())), err
+    ref64, model, pixels = wino_case(case, weights, x)
+    F.assert_f32_tight(got, ref64, model, "wino_f23: %s %s" % (_force, case), pixels)
 
 
 @pytest.mark.parametrize("hw", [(104, 136), (240, 320)])

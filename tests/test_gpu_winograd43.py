@@ -1,7 +1,9 @@
 """-m gpu: the unfused Winograd F(4x4,3x3) form of the float32 3x3 layers (csrc/wino43_f32.hip, tile `wino_f43`: input transform, 36 batched
 ws1x1f products, inverse transform), put in place with set_tile on single layers and on every 3x3 layer of a small whole net.  Against the CPU
-oracle at the bound tests/test_gpu_winograd.py holds single layers to, 1e-4 x max(1, max|reference|) (the float32 emulation of the form,
-tests/test_wino43_host.py, measures 1.0e-5 x range on a res4 layer: about 9 x inside; measured here 7e-6 .. 3.8e-5 absolute on ranges of 4 .. 7), whole nets at the path's 1e-3.
+oracle at the bound tests/test_gpu_winograd.py holds single layers to, 1e-4 x max(1, max|reference|) (measured here 7e-6 .. 3.8e-5 absolute on
+ranges of 4 .. 7), and at the error of the form's own float32 emulation with sequential sums (tests/f32_ref.py wino43_f32, which measures 1.0e-5 x
+range on a res4 layer): at most 3 x its maximum and 2 x its RMS error against a float64 reference; measured, worst over the cases: 1.24 and 0.87.
+Whole nets at the path's 1e-3.
 
 Shapes: the smallest that reach each path of the three kernels.  A step of the multiply is 16 tiles, a tile 4 x 4 pixels:
   5 x 9, 6 x 7      2 x 3 / 2 x 2 tiles, partial in both directions, one partial step
@@ -15,7 +17,9 @@ import os
 import numpy as np
 import pytest
 
+import f32_ref as F
 from conftest import rand_image
+from test_gpu_winograd import wino_case
 
 pytestmark = pytest.mark.gpu
 LABEL = "wino_f43+ws1x1f<16xN>"
@@ -118,6 +122,8 @@ def test_single_layers_match_the_oracle_twice_with_the_same_bits(gpu_caffe, case
     bound = 1e-4 * max(1.0, float(np.abs(ref).max()))
     print("wino_f43 %s: max|hip - oracle| = %.3e (bound %.3e)" % (case, err, bound))
     assert err <= bound, (err, bound)
+    ref64, model, pixels = wino_case(case, weights, x, "wino43")
+    F.assert_f32_tight(runs[0], ref64, model, "wino_f43: %s" % (case,), pixels)
     assert np.array_equal(runs[0], runs[1]), "two runs differ"
 
 

@@ -1,13 +1,16 @@
 """-m gpu: the 5 x 6-tile block forms of the float32 Winograd kernel (wino_f32.hip, WinoGeom<5, 3, side by side>; tiles wino_f23_5x6 and
 wino_f23_5x6_w16), put in place with set_tile on single 3x3 layers and on the res5 layers of the full net.  Against the CPU oracle at the
-suite's bound (<= 1e-3 max-abs), and bit for bit against the 4 x 8 form of the same wave count: a tile's arithmetic (channel order, order
+suite's bound (<= 1e-3 max-abs) and, single layers, at the error of the form's float32 emulation with sequential sums (tests/f32_ref.py:
+3 x its maximum, 2 x its RMS error against a float64 reference), and bit for bit against the 4 x 8 form of the same wave count: a tile's arithmetic (channel order, order
 of the partial sums in the epilogue) does not depend on the block slot it sits in."""
 import os
 
 import numpy as np
 import pytest
 
+import f32_ref as F
 from conftest import rand_image
+from test_gpu_winograd import wino_case
 
 pytestmark = pytest.mark.gpu
 
@@ -94,6 +97,8 @@ def test_single_layers_match_the_oracle_and_the_4x8_form(gpu_caffe, case, form):
     err = float(np.abs(got[tile] - ref).max())
     print("%s %s: max|hip - oracle| = %.3e, differing elements against %s: %d" % (tile, case, err, tile48, int((got[tile] != got[tile48]).sum())))
     assert err <= 1e-3, err
+    ref64, model, pixels = wino_case(case, weights, x)
+    F.assert_f32_tight(got[tile], ref64, model, "wino_f23_5x6: %s %s" % (tile, case), pixels)
     assert np.array_equal(got[tile], got[tile48]), "not bit-identical to the 4 x 8 form"
 
 

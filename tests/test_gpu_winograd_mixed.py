@@ -3,13 +3,15 @@ launch whose workgroups run 4 x 8-tile blocks in front of a straight cut of the 
 with set_tile on single 3x3 layers and on every 3x3 layer of a small whole net.  Bit for bit against the 4 x 8 form of the same wave count
 (a tile's arithmetic does not depend on the block slot it sits in; the 8- and the 16-wave forms differ from each other by float32 rounding,
 tests/test_gpu_winograd.py, so each is compared with its own), and against the CPU oracle at the bound tests/test_gpu_winograd.py holds
-single layers to: 1e-4 * max(1, max|reference|)."""
+single layers to: 1e-4 * max(1, max|reference|), and the error of the form's float32 emulation with sequential sums (tests/f32_ref.py)."""
 import os
 
 import numpy as np
 import pytest
 
+import f32_ref as F
 from conftest import rand_image
+from test_gpu_winograd import wino_case
 
 pytestmark = pytest.mark.gpu
 
@@ -105,6 +107,8 @@ def test_single_layers_match_the_4x8_form_and_the_oracle(gpu_caffe, case, tiles,
     bound = 1e-4 * max(1.0, float(np.abs(ref).max()))
     print("%s %s: max|hip - oracle| = %.3e (bound %.3e), differing elements against %s: %d" % (tile, case, err, bound, tile48, int((got[tile] != got[tile48]).sum())))
     assert err <= bound, (err, bound)
+    ref64, model, pixels = wino_case(case, weights, x)
+    F.assert_f32_tight(got[tile], ref64, model, "wino_f23_mix: %s %s" % (tile, case), pixels)
     assert np.array_equal(got[tile], got[tile48]), "not bit-identical to the 4 x 8 form"
 
 

@@ -9,10 +9,9 @@ import numpy as np
 import pytest
 
 import caffe
+from f32_ref import wino43_f32  # the form as the kernels lay it out, every stage in float32, sequential products
 
-BT = np.array([[4, 0, -5, 0, 1, 0], [0, -4, -4, 1, 1, 0], [0, 4, -4, -1, 1, 0], [0, -2, -1, 2, 1, 0], [0, 2, -1, -2, 1, 0], [0, 4, 0, -5, 0, 1]], np.float64)
 G = np.array([[1 / 4, 0, 0], [-1 / 6, -1 / 6, -1 / 6], [-1 / 6, 1 / 6, -1 / 6], [1 / 24, 1 / 12, 1 / 6], [1 / 24, -1 / 12, 1 / 6], [0, 0, 1]], np.float64)
-AT = np.array([[1, 1, 1, 1, 1, 0], [0, 1, -1, 2, -2, 0], [0, 1, 1, 4, 4, 0], [0, 1, -1, 8, -8, 1]], np.float64)
 
 
 def _mfma16(a_lanes, b_lanes):
@@ -65,39 +64,6 @@ def _direct64(x, g, d):
     return out
 
 
-def _wino43_f32(x, g, d):
-    """the form as the kernels lay it out: rows r = ((n d d + phase) TY + ty) TX + tx, every stage in float32"""
-    n, cin, h, w = x.shape
-    cout = g.shape[0]
-    TY, TX = (-(-h // d) + 3) // 4, (-(-w // d) + 3) // 4
-    R = n * d * d * TY * TX
-    bt, at = BT.astype(np.float32), AT.astype(np.float32)
-    U = _u64(g).astype(np.float32).reshape(36, cout, cin)
-    V = np.zeros((36, R, cin), np.float32)
-    tiles = []
-    for img in range(n):
-        for py in range(d):
-            for px in range(d):
-                ph = x[img, :, py::d, px::d]
-                pad = np.zeros((cin, 4 * TY + 2, 4 * TX + 2), np.float32)
-                pad[:, 1:1 + ph.shape[1], 1:1 + ph.shape[2]] = ph
-                for ty in range(TY):
-                    for tx in range(TX):
-                        r = len(tiles)
-                        tiles.append((img, py, px, ty, tx))
-                        patch = pad[:, 4 * ty:4 * ty + 6, 4 * tx:4 * tx + 6]
-                        V[:, r, :] = np.einsum("ia,cab,jb->ijc", bt, patch, bt).reshape(36, cin)
-    assert len(tiles) == R
-    M = np.stack([V[p] @ U[p].T for p in range(36)])  # [36, R, cout] float32
-    out = np.zeros((n, cout, h, w), np.float32)
-    for r, (img, py, px, ty, tx) in enumerate(tiles):
-        Y = np.einsum("ia,abo,jb->oij", at, M[:, r, :].reshape(6, 6, cout), at)
-        dst = out[img, :, py::d, px::d]
-        ys, xs = dst[:, 4 * ty:4 * ty + 4, 4 * tx:4 * tx + 4].shape[1:]
-        dst[:, 4 * ty:4 * ty + 4, 4 * tx:4 * tx + 4] = Y[:, :ys, :xs]
-    return out
-
-
 @pytest.mark.parametrize("shape", [(1, 256, 256, 34, 46, 1), (1, 64, 32, 5, 9, 1), (2, 64, 32, 6, 7, 1), (1, 64, 32, 9, 11, 2)],
                          ids=["res4", "5x9", "batch2_6x7", "dilation2_9x11"])
 def test_three_float32_stages_against_a_float64_convolution(shape):
@@ -106,7 +72,7 @@ def test_three_float32_stages_against_a_float64_convolution(shape):
     x = np.maximum(rs.randn(n, cin, h, w), 0).astype(np.float32)          # post-ReLU activations
     g = (rs.randn(cout, cin, 3, 3) * np.sqrt(2.0 / (9 * cin))).astype(np.float32)  # He-scaled
     ref = _direct64(x, g, d)
-    got = _wino43_f32(x, g, d)
+    got = wino43_f32(x, g, d)
     rng = float(np.abs(ref).max())
     err = float(np.abs(got - ref).max())
     print("wino_f43 in float32 %s: max error %.3e on a range of %.3f = %.2e x range" % (shape, err, rng, err / rng))
