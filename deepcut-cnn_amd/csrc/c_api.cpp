@@ -988,6 +988,33 @@ int dc_net_track_frames_async(dc_net* net, dc_tracker* tracker, const dc_frame* 
                                edges, mean, stdev, joint_order, n_people, people, cand, ids, place);
   });
 }
+// stage D of the people assembly: state of the net / the group, checked here with no device (CompleteParams::checked, people.cpp)
+static void completion_out(const CompleteParams& c, dc_complete_params* out) {
+  out->enabled = c.enabled;
+  out->fill_threshold = c.fill_threshold;
+  out->fill_radius = c.fill_radius;
+  out->min_support = c.min_support;
+}
+int dc_net_set_completion(dc_net* net, const dc_complete_params* p) {
+  REQUIRE(net);
+  return guard([&] { N(net)->completion = CompleteParams::checked(p); });
+}
+int dc_net_get_completion(dc_net* net, dc_complete_params* out) {
+  REQUIRE(net);
+  REQUIRE(out);
+  completion_out(N(net)->completion, out);
+  return DC_OK;
+}
+int dc_group_set_completion(dc_group* group, const dc_complete_params* p) {
+  REQUIRE(group);
+  return guard([&] { G(group)->completion = CompleteParams::checked(p); });
+}
+int dc_group_get_completion(dc_group* group, dc_complete_params* out) {
+  REQUIRE(group);
+  REQUIRE(out);
+  completion_out(G(group)->completion, out);
+  return DC_OK;
+}
 // single-person and box poses from the fused maps (net_group.cpp decode_pose / decode_boxes)
 int dc_group_decode_pose(dc_group* group, const double* scales, int base, const dc_fuse_mirror* fm, double* pose, int is_device, void* stream) {
   REQUIRE(group);

@@ -406,6 +406,16 @@ int launch_pair_cost(const void* next, int ncp, int nc0, int ekind, int NB, int 
 int launch_assemble(int NB, int J, int max_det, int max_people, int min_joints, double max_cost, double seed_thr, const int* counts,
                     const double* dets, const double* cost, const int* order, double* link, int* n_people, double* people, int* cand,
                     void* stream);
+// completion (stage D, one workgroup per image and joint; the rule: include/deepcut_hip.h, dc_complete_params): prob / loc in element
+//           type `ekind`, next in `next_ekind` (float32 on the sparse pairwise path whatever the net's type); dets, lut, mean, stdev as
+//           launch_pair_cost; n_people and cand_in are launch_assemble's outputs and are only read; radius = the assembly's NMS radius.
+//           -> people[b][q][j] of every joint filled, cand_out [NB][max_people][J] = cand_in with -2 where a joint was filled (a
+//           buffer of its own: every entry is written).  fill_radius <= kCompleteMaxRadius.
+constexpr int kCompleteMaxRadius = 16;
+int launch_complete(const void* prob, int pcp, int pc0, const void* loc, int lcp, int lc0, int ekind, const void* next, int ncp, int nc0,
+                    int next_ekind, int NB, int H, int W, int J, int max_det, int max_people, double scale, int radius, float fill_thr,
+                    int fill_radius, int min_support, const double* dets, const int* lut, const double* mean, const double* stdev,
+                    const int* n_people, const int* cand_in, double* people, int* cand_out, void* stream);
 
 // Tracking people from frame to frame (track.hip; the rule: include/deepcut_hip.h, dc_tracker_update — this project's own).  A slot's
 // state is one block of track_slot_bytes(T, J) bytes, all zero = no track and next_id 0:

@@ -24,6 +24,7 @@
 #include "kernels.h"
 
 struct dc_frame;  // include/deepcut_hip.h: one video frame (planes, pitches, format, matrix, range)
+struct dc_complete_params;  // include/deepcut_hip.h: stage D of the people assembly
 
 namespace dc {
 
@@ -264,6 +265,15 @@ struct DevBuf {
   void* get(size_t bytes) { return reserve(bytes), dev; }
 };
 
+// Stage D of the people assembly (dc_complete_params, include/deepcut_hip.h): state of a net or a group, not an argument of the entries
+struct CompleteParams {
+  int enabled = 0;
+  float fill_threshold = 0.f;
+  int fill_radius = 0, min_support = 0;
+  // DC_EINVAL naming the field; host only.  A null pointer is "off"
+  static CompleteParams checked(const dc_complete_params* p);
+};
+
 struct Net {
   std::string name;
   int phase = 1;
@@ -278,6 +288,7 @@ struct Net {
   int use_graph = 0;
   int outputs_mask = -1;  // DC_OPT_OUTPUTS: bit i = output i (order of `outputs`) is wanted
   int sparse_pairwise = 0;  // DC_OPT_SPARSE_PAIRWISE: a plan without next_pred has the pairwise head evaluated at the cells its consumers read
+  CompleteParams completion;  // dc_net_set_completion: stage D behind every assembly of this net (off by default; a clone copies it)
   std::shared_ptr<ModelShared> shared;   // joint with every clone
   uint64_t seen_weights_gen = 0;         // generation the cached plans were lowered from
   // the ACTIVE plan (the fields below are swapped with a parked PlanState when the input shape changes)
@@ -367,6 +378,8 @@ struct Net {
     double max_cost;
     float seed_threshold;
     int max_people, min_joints;
+    CompleteParams complete{};  // what assemble_maps runs behind stage C: the net's or the group's setting, put there by assemble_last /
+                                // NetGroup::assemble_people (the entries leave it off)
   };
   // tracker (may be null; dc_net_track_people): its launch runs behind the assembly's on the people left on the device -> ids, place
   // [NB][max_people]; everything else is computed and returned exactly as without it.  slot_of (may be null: image b updates slot b):
@@ -446,7 +459,8 @@ struct Net {
                                                const double* stdev, const int* joint_order);
   // between (may be empty): called with stage A's device outputs (counts, dets) after its launch and before stage B's — the sparse
   // pairwise head fills N's cells there.  after (may be empty): called with stage C's device outputs (n_people, people) behind its
-  // launch and before the downloads — the tracker's launch goes there
+  // launch — and behind stage D's when q.complete is enabled, on the completed people — and before the downloads — the tracker's launch
+  // goes there
   // keep (may be null: the table and the statistics go into the scratch with every call): where they stay on the device from call to call,
   // uploaded only when their content differs from what is there, from a host copy that outlives the upload.  wait = false: nothing is
   // waited for — the results are in the host arrays once `stream` has been, and nothing of the caller's small arguments is read after
@@ -463,7 +477,7 @@ struct Net {
                             const std::function<void(const int*, const double*)>& after = nullptr, AssembleTables* keep = nullptr,
                             bool wait = true);
   AssembleTables asm_tables_;
-  void assemble_last(const AssembleParams& q, const std::vector<int>& table, int n_edges, const double* mean, const double* stdev,
+  void assemble_last(const AssembleParams& q_in, const std::vector<int>& table, int n_edges, const double* mean, const double* stdev,
                      int* n_people, double* people, int* cand, double* cost, const std::function<void(const int*, const double*)>& after,
                      bool wait);
   // DC_OPT_SPARSE_PAIRWISE (sparse_pairwise.cpp)
@@ -597,6 +611,7 @@ struct GroupStats {
 };
 struct NetGroup {
   std::vector<Net*> nets;  // borrowed: executors of one model (a net and its clones), alive as long as the group
+  CompleteParams completion;  // dc_group_set_completion: stage D behind the assembly of the fused maps (the members' settings are not read)
   GroupStats stats;
   std::string text_buf;
   ~NetGroup();

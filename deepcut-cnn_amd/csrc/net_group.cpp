@@ -1161,6 +1161,7 @@ void NetGroup::assemble_people(const double* scales, int base, const Net::Assemb
   check_scales("assemble_people", scales, base);  // first: the assembly runs at scales[base]
   Net::AssembleParams q = p;
   q.scale = scales[base];
+  q.complete = completion;  // stage D on the fused maps, when the group has it enabled
   Net::check_assemble_params(q);
   const std::vector<int>& pshape = nets[(size_t)base]->prob_shape();
   const std::vector<int> table = Net::check_assemble_graph(q, pshape[1], n_edges, edges, mean, stdev, joint_order);

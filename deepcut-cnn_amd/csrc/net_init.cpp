@@ -128,6 +128,7 @@ Net* Net::clone() {
   c->use_graph = use_graph;
   c->outputs_mask = outputs_mask;
   c->sparse_pairwise = sparse_pairwise;
+  c->completion = completion;
   if (dtype != c->dtype) {
     c->dtype = dtype;
     for (auto& st : c->storages)

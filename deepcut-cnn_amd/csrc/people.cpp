@@ -99,7 +99,8 @@ PairStats read_pair_stats(const std::string& path) {
 
 // ---- the device path ---------------------------------------------------------------------------------------------------
 // Stage A = Net::detect_parts' launch with its outputs left in the scratch buffer, stage B = launch_pair_cost, stage C =
-// launch_assemble: three launches on one stream with nothing in between (DC_OPT_SPARSE_PAIRWISE on a net without next_pred: the sparse
+// launch_assemble, stage D = launch_complete (only with completion enabled: dc_net_set_completion): three or four launches on one
+// stream with nothing in between (DC_OPT_SPARSE_PAIRWISE on a net without next_pred: the sparse
 // head's two launches between A and B, sparse_pairwise.cpp), then the downloads of the results.  The argument checks
 // and the device half are functions of their own: NetGroup::assemble_people runs them on the fused maps of a pyramid (net_group.cpp).
 void Net::check_assemble_params(const AssembleParams& q) {
@@ -111,6 +112,21 @@ void Net::check_assemble_params(const AssembleParams& q) {
   if (!(q.max_cost >= 0) || !std::isfinite(q.max_cost)) bad("max_cost must be finite and >= 0");
   if (!std::isfinite(q.seed_threshold)) bad("seed_threshold must be finite");
   if (q.max_people < 1 || q.max_people > kPeopleMaxPeople) bad("max_people must be in [1, " + std::to_string(kPeopleMaxPeople) + "]");
+}
+
+// dc_net_set_completion / dc_group_set_completion: refused here, with no device, so that no assembling entry has to
+CompleteParams CompleteParams::checked(const dc_complete_params* p) {
+  CompleteParams c;
+  if (!p || !p->enabled) return c;  // off: the other fields are not read
+  auto bad = [](const std::string& m) { throw DcError(DC_EINVAL, "set_completion: " + m); };
+  if (!std::isfinite(p->fill_threshold) || !(p->fill_threshold > 0.f)) bad("fill_threshold must be finite and > 0");
+  if (p->fill_radius < 0 || p->fill_radius > kCompleteMaxRadius) bad("fill_radius must be in [0, " + std::to_string(kCompleteMaxRadius) + "]");
+  if (p->min_support < 1) bad("min_support must be >= 1");
+  c.enabled = 1;
+  c.fill_threshold = p->fill_threshold;
+  c.fill_radius = p->fill_radius;
+  c.min_support = p->min_support;
+  return c;
 }
 
 std::vector<int> Net::check_assemble_graph(const AssembleParams& q, int J, int n_edges, const int* edges, const double* mean,
@@ -171,9 +187,11 @@ void Net::assemble_people(const AssembleParams& q, int n_edges, const int* edges
 }
 
 // the device half of assemble_people / track_frames_async on the maps of the net's last (enqueued) forward
-void Net::assemble_last(const AssembleParams& q, const std::vector<int>& table, int n_edges, const double* mean, const double* stdev,
+void Net::assemble_last(const AssembleParams& q_in, const std::vector<int>& table, int n_edges, const double* mean, const double* stdev,
                         int* n_people, double* people, int* cand, double* cost, const std::function<void(const int*, const double*)>& after,
                         bool wait) {
+  AssembleParams q = q_in;
+  q.complete = completion;  // stage D, when the net has it enabled
   const MapRef P = map_ref("prob"), L = map_ref("loc_pred");
   if (sparse_pairwise && !next_in_plan()) {  // DC_OPT_SPARSE_PAIRWISE: the head at the candidates' cells, between stages A and B
     const SparseNext sn = sparse_next(P.NB * P.C * q.max_det, 0);
@@ -239,7 +257,10 @@ void Net::assemble_maps(const MapRef& P, const MapRef& L, const MapRef& N, const
   const size_t np_b = up((size_t)NB * sizeof(int));
   const size_t ppl_b = up((size_t)NB * PP * J * 3 * sizeof(double));
   const size_t cand_b = up((size_t)NB * PP * J * sizeof(int));
-  unsigned char* base = (unsigned char*)scratch(cnt_b + spill_b + det_b + (keep ? 0 : tab_b + st_b) + cost_b + link_b + np_b + ppl_b + cand_b);
+  const bool complete = q.complete.enabled != 0;
+  const size_t fill_b = complete ? cand_b : 0;  // stage D writes `cand` into a buffer of its own: it reads stage C's while it runs
+  unsigned char* base =
+      (unsigned char*)scratch(cnt_b + spill_b + det_b + (keep ? 0 : tab_b + st_b) + cost_b + link_b + np_b + ppl_b + cand_b + fill_b);
   unsigned char* at = base;
   auto take = [&](size_t b) {
     unsigned char* r = at;
@@ -280,6 +301,7 @@ void Net::assemble_maps(const MapRef& P, const MapRef& L, const MapRef& N, const
   int* d_np = (int*)take(np_b);
   double* d_ppl = (double*)take(ppl_b);
   int* d_cand = (int*)take(cand_b);
+  int* d_filled = complete ? (int*)take(fill_b) : nullptr;
   if (!keep) {
     HIPCHECK(hipMemcpyAsync(d_tab, table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice, s));
     if (E) HIPCHECK(hipMemcpyAsync(d_mean, stats.data(), stats.size() * sizeof(double), hipMemcpyHostToDevice, s));
@@ -290,6 +312,12 @@ void Net::assemble_maps(const MapRef& P, const MapRef& L, const MapRef& N, const
   KCHECK(launch_pair_cost(N.ptr, N.cp, N.c0, N.ek, NB, N.H, N.W, J, MD, q.scale, d_cnt, d_det, d_tab, d_mean, d_std, d_cost, stream));
   KCHECK(launch_assemble(NB, J, MD, PP, q.min_joints, q.max_cost, (double)q.seed_threshold, d_cnt, d_det, d_cost, d_tab + (size_t)J * J, d_link,
                          d_np, d_ppl, d_cand, stream));
+  if (complete) {  // stage D: the joints people lack, from the maps stages A and B read; the tracker below receives the completed people
+    KCHECK(launch_complete(P.ptr, P.cp, P.c0, L.ptr, L.cp, L.c0, P.ek, N.ptr, N.cp, N.c0, N.ek, NB, P.H, P.W, J, MD, PP, q.scale, q.radius,
+                           q.complete.fill_threshold, q.complete.fill_radius, q.complete.min_support, d_det, d_tab, d_mean, d_std, d_np, d_cand,
+                           d_ppl, d_filled, stream));
+    d_cand = d_filled;
+  }
   if (after) after(d_np, d_ppl);
   HIPCHECK(hipMemcpyAsync(n_people, d_np, (size_t)NB * sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHECK(hipMemcpyAsync(people, d_ppl, (size_t)NB * PP * J * 3 * sizeof(double), hipMemcpyDeviceToHost, s));

@@ -7,6 +7,9 @@
 // Two latency-class kernels behind part_select_kernel (pose.hip), nothing of them on the forward path:
 //   pair_cost_kernel  one workgroup per (image, joint a): cost[b][a][c][i][k] for every partner joint c and candidate pair
 //   assemble_kernel   one workgroup per image: the greedy linking, joint after joint, on that cost tensor
+// and, only when the caller enabled completion (dc_net_set_completion), a third behind them:
+//   complete_kernel   one workgroup per (image, joint j): the joints j that people lack, looked for in the score map around the mean
+//                     of the positions their held joints predict (stage D; like B and C this project's own rule)
 // All arithmetic is double, like the two decoders.  Double rate does not matter here: a full cost tensor (14 x 14 x 64 x 64) is
 // 1.6 M square roots, and the usual one (16 candidates) a sixteenth of it.
 #include <hip/hip_runtime.h>
@@ -250,6 +253,111 @@ __global__ __launch_bounds__(256) void assemble_kernel(int J, int MD, int P, int
   }
 }
 
+// Stage D, the completion pass (opt-in; the rule: include/deepcut_hip.h, dc_complete_params).  One workgroup per (image, joint j):
+// the cells of the candidates of j that people hold go to LDS first, indexed by the candidate (a candidate is held by at most one
+// person, so slot ci is written by one thread and no counter is needed; a free slot stays far off the map), then the four waves walk
+// the people of the image, one (person, joint) item per wave.  Lane a computes predictor a (J <= 32 lanes busy); the sum runs over a
+// ascending through lane broadcasts, so every lane holds the same e; the lanes then stride over the window — its cells ascend with
+// the lane's trips, so the first of equal scores stays within a lane — and an xor-butterfly arg-max over (score, cell) leaves the
+// winner in every lane; lane 0 writes.  No atomics, and nothing read here is written here: `cand_in` is stage C's, `cand_out` a
+// column of its own per workgroup, and people[b][.][j] is touched by this workgroup alone — the result does not depend on timing.
+template <typename T, typename TN>
+__global__ __launch_bounds__(256) void complete_kernel(const T* __restrict__ prob, int pcp, int pc0, const T* __restrict__ loc, int lcp,
+                                                       int lc0, const TN* __restrict__ next, int ncp, int nc0, int H, int W, int J, int MD,
+                                                       int P, double scale, int radius, float fill_thr, int fill_radius, int min_support,
+                                                       const double* __restrict__ dets, const int* __restrict__ lut,
+                                                       const double* __restrict__ mean, const double* __restrict__ stdev,
+                                                       const int* __restrict__ n_people, const int* __restrict__ cand_in,
+                                                       double* __restrict__ people, int* __restrict__ cand_out) {
+  __shared__ int ex_row[kPeopleMaxDet], ex_col[kPeopleMaxDet];
+  const int bj = blockIdx.x, b = bj / J, j = bj - b * J, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int n = min(max(n_people[b], 0), P);
+  const int kFar = -(1 << 20);  // further than any radius from every cell
+  const int kNone = 0x7fffffff;
+  const int* cin = cand_in + (long)b * P * J;
+  const double* dj = dets + (long)bj * MD * 5;
+  if (t < kPeopleMaxDet) ex_row[t] = kFar, ex_col[t] = kFar;
+  __syncthreads();
+  for (int q = t; q < n; q += 256) {
+    const int ci = cin[q * J + j];
+    if (ci >= 0 && ci < MD) ex_row[ci] = (int)dj[ci * 5 + 3], ex_col[ci] = (int)dj[ci * 5 + 4];
+  }
+  __syncthreads();
+  const T* pj = prob + ((long)b * H * W) * pcp + pc0 + j;
+  for (int q = wave; q < P; q += 4) {  // uniform per wave
+    const int mine = cin[q * J + j];
+    int* co = cand_out + ((long)b * P + q) * J + j;
+    if (q >= n || mine >= 0) {
+      if (lane == 0) *co = mine;
+      continue;
+    }
+    // 1. predictors: lane a holds pred_a when q holds joint a and an edge a -> j exists
+    double px = 0.0, py = 0.0;
+    bool have = false;
+    if (lane < J && lane != j) {
+      const int ia = cin[q * J + lane], l = lut[lane * J + j];
+      if (ia >= 0 && ia < MD && l >= 0) {
+        const double* da = dets + (((long)b * J + lane) * MD + ia) * 5;
+        const int row = (int)da[3], col = (int)da[4];
+        if (row >= 0 && row < H && col >= 0 && col < W) {
+          pair_predict(next, ncp, nc0, b, H, W, row, col, l, mean, stdev, scale, px, py);
+          have = true;
+        }
+      }
+    }
+    const unsigned long long who = __ballot(have);
+    const int support = __popcll(who);
+    // 2. the expected position: the sum over a ascending, the same in every lane
+    double sx = 0.0, sy = 0.0;
+    for (int a = 0; a < J; ++a) {
+      const double ax = __shfl(px, a), ay = __shfl(py, a);
+      if ((who >> a) & 1ull) sx += ax, sy += ay;
+    }
+    float bv = 0.f;
+    int bc = kNone;
+    if (support >= min_support && support > 0) {
+      const double ex = sx / (double)support, ey = sy / (double)support;
+      if (ex - ex == 0.0 && ey - ey == 0.0) {  // finite
+        // 3. the window, clipped in double: e may lie anywhere
+        const double fc = floor(ex * scale / 8.0), fr = floor(ey * scale / 8.0);
+        const double c_lo = fmax(fc - (double)fill_radius, 0.0), c_hi = fmin(fc + (double)fill_radius, (double)(W - 1));
+        const double r_lo = fmax(fr - (double)fill_radius, 0.0), r_hi = fmin(fr + (double)fill_radius, (double)(H - 1));
+        if (c_lo <= c_hi && r_lo <= r_hi) {
+          const int c0 = (int)c_lo, r0 = (int)r_lo, ww = (int)c_hi - c0 + 1, wh = (int)r_hi - r0 + 1;
+          for (int idx = lane; idx < ww * wh; idx += 64) {
+            const int dr = idx / ww, row = r0 + dr, col = c0 + (idx - dr * ww), cell = row * W + col;
+            // 4. somebody's peak: within `radius` of a held candidate of j
+            bool taken = false;
+            for (int k = 0; k < MD; ++k) taken = taken || (abs(row - ex_row[k]) <= radius && abs(col - ex_col[k]) <= radius);
+            const float v = (float)pj[(long)cell * pcp];
+            // 5. v >= fill_thr is false for a NaN; cells ascend within a lane, so `>` keeps the first of equal scores
+            if (!taken && v >= fill_thr && (bc == kNone || v > bv)) bv = v, bc = cell;
+          }
+        }
+      }
+    }
+    for (int s = 32; s > 0; s >>= 1) {
+      const float v2 = __shfl_xor(bv, s);
+      const int c2 = __shfl_xor(bc, s);
+      if (c2 != kNone && (bc == kNone || v2 > bv || (v2 == bv && c2 < bc))) bv = v2, bc = c2;
+    }
+    if (lane == 0) {
+      if (bc != kNone) {
+        const double kLoc = 7.280109889280518;  // sqrt(53), as part_select_kernel
+        const int row = bc / W, col = bc - row * W;
+        const T* l = loc + (((long)b * H + row) * W + col) * lcp + lc0 + 2 * j;
+        double* o = people + (((long)b * P + q) * J + j) * 3;
+        o[0] = ((double)col * 8.0 + 4.0 + (double)(float)l[0] * kLoc) / scale;
+        o[1] = ((double)row * 8.0 + 4.0 + (double)(float)l[1] * kLoc) / scale;
+        o[2] = (double)bv;
+        *co = -2;
+      } else {
+        *co = -1;
+      }
+    }
+  }
+}
+
 size_t pair_cost_lds_bytes(int J, int max_det) { return ((size_t)2 * J * max_det + 6 * (size_t)max_det) * sizeof(double); }
 
 int launch_pair_cost(const void* next, int ncp, int nc0, int ekind, int NB, int H, int W, int J, int max_det, double scale, const int* counts,
@@ -273,6 +381,26 @@ int launch_assemble(int NB, int J, int max_det, int max_people, int min_joints, 
   hipLaunchKernelGGL(assemble_kernel, dim3(NB), dim3(256), (size_t)max_people * J * sizeof(int), (hipStream_t)stream, J, max_det, max_people,
                      min_joints, max_cost, seed_thr, counts, dets, cost, order, link, n_people, people, cand);
   return (int)hipGetLastError();
+}
+
+int launch_complete(const void* prob, int pcp, int pc0, const void* loc, int lcp, int lc0, int ekind, const void* next, int ncp, int nc0,
+                    int next_ekind, int NB, int H, int W, int J, int max_det, int max_people, double scale, int radius, float fill_thr,
+                    int fill_radius, int min_support, const double* dets, const int* lut, const double* mean, const double* stdev,
+                    const int* n_people, const int* cand_in, double* people, int* cand_out, void* stream) {
+  if (NB <= 0 || J <= 0) return 0;
+  if (max_det < 1 || max_det > kPeopleMaxDet || J > kPeopleMaxJoints || max_people < 1 || max_people > kPeopleMaxPeople || H < 1 || W < 1 ||
+      (long)H * W > 0x7ffffffe || radius < 0 || fill_radius < 0 || fill_radius > kCompleteMaxRadius || min_support < 1)
+    return (int)hipErrorInvalidValue;
+  return people_by_kind(ekind, [&](auto* tag) {
+    using T = std::remove_pointer_t<decltype(tag)>;
+    return people_by_kind(next_ekind, [&](auto* ntag) {
+      using TN = std::remove_pointer_t<decltype(ntag)>;
+      hipLaunchKernelGGL((complete_kernel<T, TN>), dim3(NB * J), dim3(256), 0, (hipStream_t)stream, (const T*)prob, pcp, pc0, (const T*)loc, lcp,
+                         lc0, (const TN*)next, ncp, nc0, H, W, J, max_det, max_people, scale, radius, fill_thr, fill_radius, min_support, dets,
+                         lut, mean, stdev, n_people, cand_in, people, cand_out);
+      return (int)hipGetLastError();
+    });
+  });
 }
 
 }  // namespace dc

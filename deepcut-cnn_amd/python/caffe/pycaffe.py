@@ -1,5 +1,6 @@
 """ctypes binding of libdeepcut_hip.so with the reference's pycaffe names and semantics
 (python/caffe/pycaffe.py:22-108, python/caffe/_caffe.cpp:76-96,159-193,219-277)."""
+import contextlib
 import ctypes as C
 import os
 import sys
@@ -41,6 +42,11 @@ class AssembleParams(C.Structure):
                 ("seed_threshold", C.c_float), ("max_people", C.c_int), ("min_joints", C.c_int)]
 
 
+class CompleteParams(C.Structure):
+    """dc_complete_params (include/deepcut_hip.h)."""
+    _fields_ = [("enabled", C.c_int), ("fill_threshold", C.c_float), ("fill_radius", C.c_int), ("min_support", C.c_int)]
+
+
 class FuseMirror(C.Structure):
     """dc_fuse_mirror (include/deepcut_hip.h)."""
     _fields_ = [("mirror", C.c_void_p), ("image_width", C.c_int), ("joint_mirror", C.c_void_p), ("n_edges", C.c_int), ("edges", C.c_void_p)]
@@ -58,6 +64,8 @@ class DcFrame(C.Structure):
 
 
 MAX_ASSEMBLE_DET, MAX_ASSEMBLE_PEOPLE = 64, 256  # dc_net_assemble_people's limits
+# Stage D of the people assembly (`Net.completion`, the `complete=` arguments).  PLACEHOLDERS, not tuned on real images: override them.
+COMPLETE_DEFAULTS = {"fill_threshold": 0.25, "fill_radius": 2, "min_support": 2}
 PIX_BGR24, PIX_NV12 = 0, 1  # DC_PIX_*
 _CSC_MATRIX = {"bt601": 0, "bt709": 1}  # DC_CSC_*
 _CSC_RANGE = {"limited": 0, "full": 1}  # DC_RANGE_*
@@ -344,6 +352,10 @@ def _load():
         "dc_net_pairwise_at": (ci, [vp, ci, C.c_void_p, C.c_void_p]),
         "dc_sparse_head_pack_size": (ci, [ci, ci, ci]),
         "dc_sparse_head_pack": (ci, [C.c_void_p, C.c_void_p, ci, ci, ci, C.c_void_p]),
+        "dc_net_set_completion": (ci, [vp, C.POINTER(CompleteParams)]),
+        "dc_net_get_completion": (ci, [vp, C.POINTER(CompleteParams)]),
+        "dc_group_set_completion": (ci, [vp, C.POINTER(CompleteParams)]),
+        "dc_group_get_completion": (ci, [vp, C.POINTER(CompleteParams)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -791,12 +803,71 @@ def _slot_map(slot_of, nb):
     return m
 
 
+def completion_params(complete):
+    """A `complete=` argument / a `completion` value -> the dict of the three parameters, or None for off.  None and False are off, True
+    is COMPLETE_DEFAULTS, a dict overrides some of them.  The values themselves are checked by the library (dc_net_set_completion)."""
+    if complete is None or complete is False:
+        return None
+    if complete is True:
+        return dict(COMPLETE_DEFAULTS)
+    if not isinstance(complete, dict):
+        raise TypeError("complete must be None, True or a dict of %s, got %r" % (sorted(COMPLETE_DEFAULTS), complete))
+    unknown = sorted(set(complete) - set(COMPLETE_DEFAULTS))
+    if unknown:
+        raise ValueError("complete: unknown keys %r (known: %s)" % (unknown, sorted(COMPLETE_DEFAULTS)))
+    return dict(COMPLETE_DEFAULTS, **complete)
+
+
+class _Completing(object):
+    """`completion` of Net and NetGroup (stage D of the people assembly, include/deepcut_hip.h): state of the object, read by every
+    entry that assembles people.  `_set_completion` / `_get_completion` name the two library entries."""
+
+    @property
+    def completion(self):
+        """None (off, the default) or {"fill_threshold", "fill_radius", "min_support"}: with it every assembling entry fills the joints
+        a person lacks from the score map around the position the person's held joints predict, on the device behind the assembly
+        (a joint filled so has cand == -2, and the result a "filled" array).  Assign None / False, True (COMPLETE_DEFAULTS: PLACEHOLDERS,
+        not tuned on real images) or a dict of some of the three.  A bad value raises DeepcutError naming the field, with or without a
+        device.  `Net.clone()` copies the setting; a NetGroup has one of its own.  The rule is this project's own: the reference stops
+        at the maps."""
+        q = CompleteParams()
+        _check(getattr(_lib, self._get_completion)(self._h, C.byref(q)))
+        if not q.enabled:
+            return None
+        return {"fill_threshold": float(q.fill_threshold), "fill_radius": int(q.fill_radius), "min_support": int(q.min_support)}
+
+    @completion.setter
+    def completion(self, complete):
+        d = completion_params(complete)
+        if d is None:
+            _check(getattr(_lib, self._set_completion)(self._h, None))
+            return
+        try:
+            q = CompleteParams(1, float(d["fill_threshold"]), int(d["fill_radius"]), int(d["min_support"]))
+        except (TypeError, ValueError) as e:
+            raise ValueError("completion: fill_threshold must be a number, fill_radius and min_support whole numbers (%s)" % (e,))
+        _check(getattr(_lib, self._set_completion)(self._h, C.byref(q)))
+
+    @contextlib.contextmanager
+    def _completing(self, complete):
+        """For the calls that take `complete=`: None leaves the object's `completion` as it is; anything else holds for this call only."""
+        if complete is None:
+            yield self.completion is not None
+            return
+        before = self.completion
+        self.completion = complete
+        try:
+            yield self.completion is not None
+        finally:
+            self.completion = before
+
+
 class TrackedFrames(object):
     """What `Net.track_frames_async` returns: the request in flight.  It owns the pinned output arrays and keeps the frames alive;
     `result()` waits for the net and returns what `Net.track_people` returns."""
 
-    def __init__(self, net, tracked, count, people, cand, ids, place, keep, pool=None):
-        self._net, self._tracked, self._keep, self._pool = net, tracked, keep, pool
+    def __init__(self, net, tracked, count, people, cand, ids, place, keep, pool=None, completed=False):
+        self._net, self._tracked, self._keep, self._pool, self._completed = net, tracked, keep, pool, completed
         self._count, self._people, self._cand, self._ids, self._place = count, people, cand, ids, place
         self._out, self._ready = None, False
 
@@ -817,6 +888,8 @@ class TrackedFrames(object):
             for b in range(self._count.shape[0]):
                 m = int(self._count[b])
                 d = {"people": self._people[b, :m].copy(), "cand": self._cand[b, :m].copy()}
+                if self._completed:
+                    d["filled"] = d["cand"] == -2
                 if self._tracked:
                     d["ids"], d["place"] = self._ids[b, :m].copy(), self._place[b, :m].copy()
                 out.append(d)
@@ -905,8 +978,10 @@ class _NetHandle(object):
             self.h = None
 
 
-class Net(object):
+class Net(_Completing):
     """caffe.Net(model_def, model_bin, phase) / caffe.Net(model_def, phase)  (_caffe.cpp:76-96,227-228)."""
+
+    _set_completion, _get_completion = "dc_net_set_completion", "dc_net_get_completion"
 
     def __init__(self, model_def, *args, **kw):
         if "_handle" in kw:  # clone()
@@ -1374,7 +1449,7 @@ class Net(object):
         return out
 
     def assemble_people(self, scale=1.0, threshold=0.1, radius=1, max_det=16, edges=None, mean=None, std=None, max_cost=32.0,
-                        seed_threshold=0.5, max_people=32, min_joints=1, joint_order=None, return_cost=False):
+                        seed_threshold=0.5, max_people=32, min_joints=1, joint_order=None, return_cost=False, complete=None):
         """The people of every image of the last forward (dc_net_assemble_people): part candidates, pair costs from `next_pred` and a
         greedy assembly, all on the device; only the results come back.  edges: [E, 2] 0-based (joint, next joint) of the regression
         edges (E = next_pred channels / 2), mean / std: their [E, 2] de-normalisation (deepcut_tools.read_pair_stats), None = 0 / 1.
@@ -1382,30 +1457,35 @@ class Net(object):
         is >= seed_threshold.  The defaults of max_cost and seed_threshold are PLACEHOLDERS, not tuned on real images: override them.
         The grouping rule (include/deepcut_hip.h) is this project's own; the reference stops at the maps.
         -> one dict per image: {"people": float64 [m, J, 3] = x, y, score ((0, 0, 0) for a missing joint), "cand": int32 [m, J] =
-        index in the joint's candidate list or -1}, plus "cost": float64 [J, J, max_det, max_det] with return_cost."""
+        index in the joint's candidate list or -1}, plus "cost": float64 [J, J, max_det, max_det] with return_cost.
+        complete: None = the net's `completion` as it stands; True, a dict or False = that setting for this call only.  When completion
+        runs, missing joints are filled on the device (stage D, include/deepcut_hip.h): such a joint has cand == -2 and the dict gains
+        "filled": bool [m, J]."""
         return self._assemble_people(None, scale, threshold, radius, max_det, edges, mean, std, max_cost, seed_threshold, max_people, min_joints,
-                                     joint_order, return_cost)
+                                     joint_order, return_cost, complete=complete)
 
     def track_people(self, tracker, scale=1.0, threshold=0.1, radius=1, max_det=16, edges=None, mean=None, std=None, max_cost=32.0,
-                     seed_threshold=0.5, max_people=32, min_joints=1, joint_order=None, return_cost=False, slot_of=None):
+                     seed_threshold=0.5, max_people=32, min_joints=1, joint_order=None, return_cost=False, slot_of=None, complete=None):
         """`assemble_people` with the identities of a `caffe.Tracker` (dc_net_track_people): the tracker's update runs on the device
         behind the assembly, on the people where the assembly left them — image b updates slot b.  The arguments and the result are
         `assemble_people`'s, unchanged, with two more entries per image: "ids": int64 [m] (the same person keeps their id from frame
         to frame; -1 = no track place was free) and "place": int32 [m] (the track place, an index into `tracker.state()`).
         slot_of: [batch] ints, the slot every image updates (dc_net_track_people_slots; `Tracker.update`): a batch forward of k
-        consecutive frames of one video is tracked with slot_of = [slot] * k."""
+        consecutive frames of one video is tracked with slot_of = [slot] * k.
+        complete: as `assemble_people`; the tracker then receives the completed people."""
         _tracker_handle(tracker)
         return self._assemble_people(tracker, scale, threshold, radius, max_det, edges, mean, std, max_cost, seed_threshold, max_people,
-                                     min_joints, joint_order, return_cost, slot_of)
+                                     min_joints, joint_order, return_cost, slot_of, complete)
 
     def track_frames_async(self, frames_or_images, tracker=None, scale=1.0, slot_of=None, assemble_scale=None, threshold=0.1, radius=1,
                            max_det=16, edges=None, mean=None, std=None, max_cost=32.0, seed_threshold=0.5, max_people=32, min_joints=1,
-                           joint_order=None):
+                           joint_order=None, complete=None):
         """The whole video chain without a host wait (dc_net_track_frames_async): upload, pre-processing, forward, assembly, the
         tracker's update and the downloads are enqueued on the net's own stream and the call returns.  frames_or_images: a `Frame`, a
         list of `Frame`s of one size, or uint8 [n,H,W,3] / [H,W,3] BGR; they must stay untouched until the result is collected.
         tracker: a `caffe.Tracker`, or None for people without ids; slot_of as `track_people`.  scale: the pre-processing's;
-        assemble_scale: the assembly's (None: the same).  The other arguments are `assemble_people`'s.
+        assemble_scale: the assembly's (None: the same).  The other arguments are `assemble_people`'s, `complete` included (what holds
+        when the call is made is what the request runs with).
         -> a `TrackedFrames`: `result()` synchronises the net and returns what `forward_images` + `track_people` return, bit for bit.
         A second call on a busy net queues behind the first; to overlap calls use clones (`deepcut_tools.VideoPipeline`): the tracker
         keeps the updates in call order."""
@@ -1449,14 +1529,15 @@ class Net(object):
             if tracker is not None:
                 ids, place = out((n, p), np.int64), out((n, p), np.int32)
         ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        _check(_lib.dc_net_track_frames_async(self._h, None if tracker is None else tracker._h, arr, ptr(x), n, h, w, float(scale),
-                                              1 if dev else 0, None if slot_of is None else ptr(_slot_map(slot_of, n)), C.byref(q),
-                                              e.shape[0], ptr(e), ptr(m), ptr(s), ptr(order), ptr(count), ptr(people), ptr(cand), ptr(ids),
-                                              ptr(place)))
-        return TrackedFrames(self, tracker is not None, count, people, cand, ids, place, keep + (tracker,), pool)
+        with self._completing(complete) as completed:
+            _check(_lib.dc_net_track_frames_async(self._h, None if tracker is None else tracker._h, arr, ptr(x), n, h, w, float(scale),
+                                                  1 if dev else 0, None if slot_of is None else ptr(_slot_map(slot_of, n)), C.byref(q),
+                                                  e.shape[0], ptr(e), ptr(m), ptr(s), ptr(order), ptr(count), ptr(people), ptr(cand),
+                                                  ptr(ids), ptr(place)))
+        return TrackedFrames(self, tracker is not None, count, people, cand, ids, place, keep + (tracker,), pool, completed)
 
     def _assemble_people(self, tracker, scale, threshold, radius, max_det, edges, mean, std, max_cost, seed_threshold, max_people, min_joints,
-                         joint_order, return_cost, slot_of=None):
+                         joint_order, return_cost, slot_of=None, complete=None):
         if edges is None:
             raise ValueError("assemble_people needs the regression edges (deepcut_tools.read_pair_stats)")
         n, j = self.blobs["prob"].shape[:2]
@@ -1469,21 +1550,24 @@ class Net(object):
         cand = np.zeros((n, p, j), np.int32)
         cost = np.zeros((n, j, j, md, md), np.float64) if return_cost else None
         ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        if tracker is None:
-            _check(_lib.dc_net_assemble_people(self._h, C.byref(q), e.shape[0], ptr(e), ptr(m), ptr(s), ptr(order), ptr(count), ptr(people),
-                                               ptr(cand), ptr(cost)))
-        else:
-            ids, place = np.full((n, p), -1, np.int64), np.full((n, p), -1, np.int32)
-            if slot_of is None:
-                _check(_lib.dc_net_track_people(self._h, _tracker_handle(tracker), C.byref(q), e.shape[0], ptr(e), ptr(m), ptr(s), ptr(order),
-                                                ptr(count), ptr(people), ptr(cand), ptr(cost), ptr(ids), ptr(place)))
+        with self._completing(complete) as completed:
+            if tracker is None:
+                _check(_lib.dc_net_assemble_people(self._h, C.byref(q), e.shape[0], ptr(e), ptr(m), ptr(s), ptr(order), ptr(count), ptr(people),
+                                                   ptr(cand), ptr(cost)))
             else:
-                _check(_lib.dc_net_track_people_slots(self._h, _tracker_handle(tracker), ptr(_slot_map(slot_of, n)), C.byref(q), e.shape[0],
-                                                      ptr(e), ptr(m), ptr(s), ptr(order), ptr(count), ptr(people), ptr(cand), ptr(cost),
-                                                      ptr(ids), ptr(place)))
+                ids, place = np.full((n, p), -1, np.int64), np.full((n, p), -1, np.int32)
+                if slot_of is None:
+                    _check(_lib.dc_net_track_people(self._h, _tracker_handle(tracker), C.byref(q), e.shape[0], ptr(e), ptr(m), ptr(s),
+                                                    ptr(order), ptr(count), ptr(people), ptr(cand), ptr(cost), ptr(ids), ptr(place)))
+                else:
+                    _check(_lib.dc_net_track_people_slots(self._h, _tracker_handle(tracker), ptr(_slot_map(slot_of, n)), C.byref(q),
+                                                          e.shape[0], ptr(e), ptr(m), ptr(s), ptr(order), ptr(count), ptr(people), ptr(cand),
+                                                          ptr(cost), ptr(ids), ptr(place)))
         out = []
         for b in range(n):
             d = {"people": people[b, :count[b]].copy(), "cand": cand[b, :count[b]].copy()}
+            if completed:
+                d["filled"] = d["cand"] == -2
             if return_cost:
                 d["cost"] = cost[b]
             if tracker is not None:
@@ -1572,7 +1656,7 @@ class Net(object):
         return t.decode()
 
 
-class NetGroup(object):
+class NetGroup(_Completing):
     """Several executors of ONE model (a net and its clones), each at its own input shape, run as ONE launch sequence
     (dc_group_*): launch i of the group is launch i of every member merged into a multi-problem gather-GEMM.  The scale
     loop of the demo (python/pose/estimate_pose.py:81-128) as one forward: `NetGroup.for_shapes(net, [(8, 272, 368), ...])`.
@@ -1580,6 +1664,7 @@ class NetGroup(object):
     emit_maps_device on a member see them)."""
 
     STAT_NAMES = ("merges", "graph_instantiations", "autotune_runs", "plan_hits", "launches", "multi_launches", "lanes")
+    _set_completion, _get_completion = "dc_group_set_completion", "dc_group_get_completion"
 
     def __init__(self, nets, lanes=None):
         """lanes: None / 0 = automatic (the members are dealt largest-with-smallest to lanes that run concurrently on their own
@@ -1922,26 +2007,27 @@ class NetGroup(object):
 
     def assemble_people(self, scales, base=0, threshold=0.1, radius=1, max_det=16, edges=None, mean=None, std=None, max_cost=32.0,
                         seed_threshold=0.5, max_people=32, min_joints=1, joint_order=None, return_cost=False, mirror=None, image_width=None,
-                        joint_mirror=None):
+                        joint_mirror=None, complete=None):
         """Net.assemble_people on the fused maps of a pyramid (dc_group_assemble_people): the three maps of the members' last forwards
         are fused on member `base`'s grid (`fuse_maps`), then the candidates, the pair costs and the greedy assembly run on them at
         scales[base], all on the device with no host round trip in between.  The other arguments and the result are Net.assemble_people's.
-        mirror / image_width / joint_mirror: as `fuse_maps`, with `edges` as the regression edges (dc_group_assemble_people_mirrored)."""
+        mirror / image_width / joint_mirror: as `fuse_maps`, with `edges` as the regression edges (dc_group_assemble_people_mirrored).
+        complete: as `Net.assemble_people`, on the group's own `completion` (the members' settings are not read)."""
         return self._assemble_people(None, scales, base, threshold, radius, max_det, edges, mean, std, max_cost, seed_threshold, max_people,
-                                     min_joints, joint_order, return_cost, mirror, image_width, joint_mirror)
+                                     min_joints, joint_order, return_cost, mirror, image_width, joint_mirror, complete=complete)
 
     def track_people(self, tracker, scales, base=0, threshold=0.1, radius=1, max_det=16, edges=None, mean=None, std=None, max_cost=32.0,
                      seed_threshold=0.5, max_people=32, min_joints=1, joint_order=None, return_cost=False, mirror=None, image_width=None,
-                     joint_mirror=None, slot_of=None):
+                     joint_mirror=None, slot_of=None, complete=None):
         """`assemble_people` with the identities of a `caffe.Tracker` (dc_group_track_people), plain or mirrored: the tracker's update
         runs on the device behind the assembly of the fused maps.  The arguments and the result are `assemble_people`'s, unchanged,
         plus "ids" and "place" per image as `Net.track_people` gives them.  slot_of: as `Net.track_people` (dc_group_track_people_slots)."""
         _tracker_handle(tracker)
         return self._assemble_people(tracker, scales, base, threshold, radius, max_det, edges, mean, std, max_cost, seed_threshold, max_people,
-                                     min_joints, joint_order, return_cost, mirror, image_width, joint_mirror, slot_of)
+                                     min_joints, joint_order, return_cost, mirror, image_width, joint_mirror, slot_of, complete)
 
     def _assemble_people(self, tracker, scales, base, threshold, radius, max_det, edges, mean, std, max_cost, seed_threshold, max_people,
-                         min_joints, joint_order, return_cost, mirror, image_width, joint_mirror, slot_of=None):
+                         min_joints, joint_order, return_cost, mirror, image_width, joint_mirror, slot_of=None, complete=None):
         if edges is None:
             raise ValueError("assemble_people needs the regression edges (deepcut_tools.read_pair_stats)")
         sc, base = self._scales(scales, base)
@@ -1957,21 +2043,25 @@ class NetGroup(object):
         cost = np.zeros((n, j, j, md, md), np.float64) if return_cost else None
         ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
         fm, _keep = self._mirror(mirror, image_width, joint_mirror, e)
-        if tracker is None:
-            _check(_lib.dc_group_assemble_people_mirrored(self._h, ptr(sc), base, fm, C.byref(q), e.shape[0], ptr(e), ptr(m), ptr(s), ptr(order),
-                                                          ptr(count), ptr(people), ptr(cand), ptr(cost)))
-        else:
-            ids, place = np.full((n, p), -1, np.int64), np.full((n, p), -1, np.int32)
-            if slot_of is None:
-                _check(_lib.dc_group_track_people(self._h, _tracker_handle(tracker), ptr(sc), base, fm, C.byref(q), e.shape[0], ptr(e), ptr(m),
-                                                  ptr(s), ptr(order), ptr(count), ptr(people), ptr(cand), ptr(cost), ptr(ids), ptr(place)))
+        with self._completing(complete) as completed:
+            if tracker is None:
+                _check(_lib.dc_group_assemble_people_mirrored(self._h, ptr(sc), base, fm, C.byref(q), e.shape[0], ptr(e), ptr(m), ptr(s),
+                                                              ptr(order), ptr(count), ptr(people), ptr(cand), ptr(cost)))
             else:
-                _check(_lib.dc_group_track_people_slots(self._h, _tracker_handle(tracker), ptr(_slot_map(slot_of, n)), ptr(sc), base, fm,
-                                                        C.byref(q), e.shape[0], ptr(e), ptr(m), ptr(s), ptr(order), ptr(count), ptr(people),
-                                                        ptr(cand), ptr(cost), ptr(ids), ptr(place)))
+                ids, place = np.full((n, p), -1, np.int64), np.full((n, p), -1, np.int32)
+                if slot_of is None:
+                    _check(_lib.dc_group_track_people(self._h, _tracker_handle(tracker), ptr(sc), base, fm, C.byref(q), e.shape[0], ptr(e),
+                                                      ptr(m), ptr(s), ptr(order), ptr(count), ptr(people), ptr(cand), ptr(cost), ptr(ids),
+                                                      ptr(place)))
+                else:
+                    _check(_lib.dc_group_track_people_slots(self._h, _tracker_handle(tracker), ptr(_slot_map(slot_of, n)), ptr(sc), base, fm,
+                                                            C.byref(q), e.shape[0], ptr(e), ptr(m), ptr(s), ptr(order), ptr(count),
+                                                            ptr(people), ptr(cand), ptr(cost), ptr(ids), ptr(place)))
         out = []
         for b in range(n):
             d = {"people": people[b, :count[b]].copy(), "cand": cand[b, :count[b]].copy()}
+            if completed:
+                d["filled"] = d["cand"] == -2
             if return_cost:
                 d["cost"] = cost[b]
             if tracker is not None:

@@ -371,6 +371,8 @@ int dc_net_decode_pairwise(dc_net* net, double scale, int ndet, const int* detec
  *     take the smallest L (ties: the lower p, then the lower i), assign it.  (3) Every candidate of j still free, in list order, with
  *     score >= seed_threshold starts a new person holding only this joint, until max_people exist.  After the last joint people
  *     with fewer than min_joints joints are dropped, the others keep their order.
+ *  D. (only with dc_net_set_completion enabled; off by default) completion: joints a person lacks are looked for in the score map
+ *     around the position its held joints predict; a joint filled so has cand = -2.  The rule is stated at dc_complete_params below.
  * Outputs: n_people[b]; people[((b*P + q)*J + j)*3 + {0,1,2}] = x, y, score of person q's candidate of joint j, (0, 0, 0) where it has
  *          none and for q >= n_people[b]; cand[(b*P + q)*J + j] = that candidate's index in joint j's list or -1 (may be NULL); cost (may
  *          be NULL: diagnostics and tests) = the whole tensor [n][J][J][max_det][max_det].  P = max_people.
@@ -900,6 +902,53 @@ int dc_net_track_frames_async(dc_net* net, dc_tracker* tracker /* NULL: people w
                               const int* edges, const double* mean, const double* stdev, const int* joint_order, int* n_people,
                               double* people, int* cand /* may be NULL */, long long* ids, int* place /* both may be NULL; ids must be
                               NULL when tracker is NULL */);
+
+/* ---- people, stage D: joints the assembly missed, filled from the pairwise predictions (opt-in) ------------------------------------
+ * NO REFERENCE COUNTERPART, PARITY UNPINNED BY THE REFERENCE: like stages B and C of dc_net_assemble_people this rule is this project's
+ * own (the reference repository stops at the maps); tests/complete_ref.py restates it in float64.
+ *
+ * A person can only hold a joint that survived stage A (score >= threshold, the maximum of its window, among the first max_det).  With
+ * completion enabled every entry that assembles people runs one more launch behind stage C, on the device, and looks for each missing
+ * joint where the person's held joints say it should be.  The setting is state of the net or the group (dc_assemble_params is
+ * unchanged): it covers dc_net_assemble_people, dc_net_track_people[_slots], dc_net_track_frames_async and — set on the group — the
+ * dc_group_assemble_people[_mirrored] and dc_group_track_people[_slots] entries; the sparse pairwise path (DC_OPT_SPARSE_PAIRWISE) is
+ * covered, because the head was evaluated at exactly the cells of the held candidates.  The tracker's launch receives the completed
+ * people.  Not enabled (the default): no launch is added and every result keeps its bits.
+ *
+ * Inputs: stage A's candidate lists; stage C's people and `cand` AFTER the min_joints drop; the three maps the assembly read (prob,
+ * loc_pred, and next_pred or the sparse float32 map); the lookup of the edges, mean, std, scale and the NMS radius of the assembly; the
+ * three parameters below.  All arithmetic in double; map values are read as their element type holds them.  For every image b, every
+ * surviving person q and every joint j that q does not hold — the items are independent of each other: a joint filled here is NOT a
+ * predictor of another fill, so neither order nor thread timing matters:
+ *  1. predictors: the joints a, ascending, that q holds from stage C and for which an edge F = the lowest-index edge (a, j) exists; each
+ *     gives pred_a = pred(cell of q's candidate of a, F), image pixels, as in stage B.  Fewer than min_support predictors: j stays missing.
+ *  2. expected position: e = (the sum of pred_a over a ascending) / their count.  e not finite: j stays missing.
+ *  3. window: col0 = floor(e_x * scale / 8), row0 = floor(e_y * scale / 8); rows row0 - fill_radius .. row0 + fill_radius and the same
+ *     for columns, clipped to the map.  Empty after clipping: j stays missing.
+ *  4. exclusion: a window cell is skipped when it lies within Chebyshev distance `radius` (the assembly's NMS radius) of the cell of a
+ *     candidate of joint j that ANY person of image b holds after stage C: such a cell belongs to somebody's peak.  Cells of fills
+ *     exclude nothing, so two people may fill the same joint from the same cell.
+ *  5. choice: among the remaining cells the one with the largest prob[j], ties to the lower row-major cell index; a NaN score is never
+ *     chosen.  If that score is >= fill_threshold the joint becomes x, y = the cell refined with loc_pred exactly as stage A computes a
+ *     candidate's x, y, score = prob, and cand = -2.  Otherwise j stays (0, 0, 0) with cand -1.
+ * Unchanged by stage D: n_people, the order of people, every joint stage C assigned; min_joints keeps counting stage C's joints only,
+ * so completion never changes who survives.
+ *
+ * dc_net_set_completion / dc_group_set_completion: p == NULL or p->enabled == 0 turns completion off (the other fields are then not
+ * read and read back as 0).  Host only, no device needed.  DC_EINVAL naming the field for fill_threshold not finite or <= 0,
+ * fill_radius outside [0, 16], min_support < 1.  dc_*_get_completion: what was stored.  dc_net_clone copies the net's setting at clone
+ * time; a group has a setting of its own and does not read its members'.  The values are the caller's to choose: nothing here has
+ * been tuned on real images.                                                                                                      */
+typedef struct dc_complete_params {
+  int   enabled;         /* 0: off */
+  float fill_threshold;  /* a fill needs prob >= this; > 0 */
+  int   fill_radius;     /* half width of the search window, map cells: 0..16 */
+  int   min_support;     /* predictors needed, >= 1 */
+} dc_complete_params;
+int dc_net_set_completion(dc_net* net, const dc_complete_params* p /* NULL: off */);
+int dc_net_get_completion(dc_net* net, dc_complete_params* out);
+int dc_group_set_completion(dc_group* group, const dc_complete_params* p /* NULL: off */);
+int dc_group_get_completion(dc_group* group, dc_complete_params* out);
 
 /* ---- in-process multi-GPU forward (SURVEY 8(b)'s dc_forward_batch) -------------------------------------------------------
  * A communicator over `nexec` executors: executor k runs on devices[k] (NULL: k modulo the visible devices) on a host thread of its
