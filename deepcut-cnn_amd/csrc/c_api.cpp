@@ -705,6 +705,51 @@ int dc_stream1x1f_pack(const float* g, int cout, int k, float* out) {
   return guard([&] { dc::stream1x1f_pack_filters(g, cout, k, out); });
 }
 
+int dc_stream1x1f_rows(const float* x, int m, int k, int x_stride, const float* g, int cout, const float* scale, const float* shift, float* y,
+                       int y_rows, int y_stride, int y_c0, const float* resid, int relu) {
+  if (!x || !g || !y) return fail(DC_EINVAL, "dc_stream1x1f_rows: null pointer");
+  if (m <= 0 || y_rows < m || k <= 0 || k % 16 || cout <= 0 || cout % 64 || x_stride < k || x_stride % 4 || y_stride % 4 || y_c0 < 0 || y_c0 % 4 ||
+      y_c0 + cout > y_stride || (long)y_rows * y_stride * 4 >= 0x7fffffffL || (long)m * x_stride * 4 >= 0x7fffffffL)
+    return fail(DC_EINVAL, "dc_stream1x1f_rows: m <= y_rows, k % 16 == 0, cout % 64 == 0, k <= x_stride, y_c0 + cout <= y_stride, strides and y_c0 multiples of 4");
+  return guard([&] {
+    ConvGemmParams p{};
+    p.esize = 4, p.ekind = kElemF32;
+    p.NB = 1, p.OH = 1, p.OW = m, p.M = m, p.Cout = cout;
+    p.x_img_stride = (long)m * x_stride, p.x_row_stride = m * x_stride, p.x_rows = 1, p.x_rowlen = (m - 1) * x_stride + k;
+    p.sy = 1, p.sx = x_stride, p.nty = 1, p.ntx = 1, p.klen = k, p.Ktot = k;
+    p.y_img_stride = (long)m * y_stride, p.y_row_stride = m * y_stride, p.y_pix_stride = y_stride;
+    p.relu = relu ? 1 : 0;
+    if (!stream1x1f_eligible(p)) throw DcError(DC_EINVAL, "dc_stream1x1f_rows: the form does not take this shape");
+    standalone_device();
+    struct Dev {  // the launch's device buffers, freed whatever happens
+      std::vector<void*> p;
+      ~Dev() {
+        for (void* q : p) (void)hipFree(q);
+      }
+      float* up(const float* h, size_t n) {
+        void* d = nullptr;
+        if (hipMalloc(&d, n * 4) != hipSuccess) throw DcError(DC_EDEVICE, "dc_stream1x1f_rows: hipMalloc failed");
+        p.push_back(d);
+        if (hipMemcpy(d, h, n * 4, hipMemcpyHostToDevice) != hipSuccess) throw DcError(DC_EDEVICE, "dc_stream1x1f_rows: copy to the device failed");
+        return (float*)d;
+      }
+    } dev;
+    std::vector<float> packed((size_t)cout * k);
+    stream1x1f_pack_filters(g, cout, k, packed.data());
+    const size_t ny = (size_t)y_rows * y_stride;
+    float* const dy = dev.up(y, ny);
+    p.x = dev.up(x, (size_t)m * x_stride);
+    p.w = dev.up(packed.data(), packed.size());
+    p.scale = scale ? dev.up(scale, cout) : nullptr;
+    p.shift = shift ? dev.up(shift, cout) : nullptr;
+    p.y = dy + y_c0;
+    p.resid = resid ? dev.up(resid, ny) + y_c0 : nullptr;
+    const int e = launch_stream1x1f(p, nullptr);
+    if (e != 0 || hipDeviceSynchronize() != hipSuccess) throw DcError(DC_EDEVICE, "dc_stream1x1f_rows: the launch failed");
+    if (hipMemcpy(y, dy, ny * 4, hipMemcpyDeviceToHost) != hipSuccess) throw DcError(DC_EDEVICE, "dc_stream1x1f_rows: copy from the device failed");
+  });
+}
+
 int dc_wino43_pack(const float* g, int cout, int cin, float* out) {
   if (!g || !out) return fail(DC_EINVAL, "dc_wino43_pack: null pointer");
   if (cout <= 0 || cin <= 0 || cout % 16 || cin % 16) return fail(DC_EINVAL, "dc_wino43_pack: cout and cin must be multiples of 16");

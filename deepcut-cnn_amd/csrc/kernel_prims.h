@@ -50,6 +50,22 @@ __device__ __forceinline__ i32x4 dc_rsrc_words(const void* p) {
   const unsigned long long a = (unsigned long long)p;
   return i32x4{(int)(unsigned)a, (int)((a >> 32) & 0xffffu), 0x7fffffff, 0x00020000};
 }
+// The descriptor of what lies behind byte `off` of a view: the base moved by off (wave uniform, sign extended: SALU), `bytes` records.
+// This is how a uniform, step-dependent displacement comes UNDER the range check with a loop-invariant voffset and no VALU work: for a
+// raw buffer (stride 0, not swizzled) the check compares inst_offset + voffset with num_records; soffset is added to the address but
+// takes no part in the check ("sgpr_offset is not a part of the offset term", buffer addressing / range checking in the CDNA3 ISA
+// guide), so a displacement in soffset would leave the end of the operand unguarded.  bytes = 0: every access is dropped.
+__device__ __forceinline__ i32x4 dc_rsrc_behind(i32x4 base, int off, int bytes) {
+  const unsigned long long a = (((unsigned long long)(unsigned)base[1] << 32) | (unsigned)base[0]) + (unsigned long long)(long long)off;
+  return i32x4{(int)(unsigned)a, (int)(unsigned)(a >> 32), bytes, base[3]};
+}
+// voff on the lanes whose bit is set in a wave-uniform mask, an out-of-range offset on the others: ONE VALU instruction, the mask is
+// SALU work (plain asm: a pure function of its inputs)
+__device__ __forceinline__ unsigned dc_lanes_or_oob(unsigned long long mask, unsigned voff) {
+  unsigned v;
+  asm("v_cndmask_b32_e64 %0, -1, %1, %2" : "=v"(v) : "v"(voff), "s"(mask));
+  return v;
+}
 // (wave-uniform values that the compiler keeps in vector registers — it does behind the wave-uniform branches of a step loop — come back
 //  to scalar ones here: an "s" operand is not converted by the compiler, the assembler rejects the instruction)
 __device__ __forceinline__ unsigned dc_uni(unsigned v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); }

@@ -22,6 +22,11 @@
 //  * two accumulators taken in turn (a matrix step does not wait for the one before it), added at the end;
 //  * shortcut and output tiles (16 pixels x 16 channels = 1 KiB) through a wave-private LDS buffer as whole 64-byte runs, the epilogue's
 //    affine / add / ReLU in fp32 in between.
+//  * nothing but the products, the operand reads and the epilogue's own fp32 arithmetic on the vector ALU inside a step (on gfx950 every VALU
+//    instruction between fp32 MFMAs is paid in addition to them): request and store addresses are a loop-invariant lane offset plus a
+//    per-request descriptor made by SALU (see "Addresses" in the kernel), the sums are read where the products leave them.  Per K = 256 step
+//    with shortcut: 17 VALU instructions (3 LDS bases, 14 epilogue) beside 64 products, 42 before; VALU instructions per forward -11 %, MFMA
+//    busy cycles unchanged, the family's kernels 5-9 % shorter alone, `value` +0.9 % (profiles/ws1x1f_step_isa.txt, _trace.txt, _bench_ab.txt).
 // Not bit-identical to the gather-GEMM tiles (another summation grouping); same 1e-3 bound against the oracle, measured ~3e-6.
 // Forms that were built and dropped (eight waves with four moving the bytes, the two waves of a SIMD sharing the products, the early-start
 // prologue) and the timing ablations: profiles/r06_stream1x1f_forms.txt, EXPERIMENTS.md L; measurements: DESIGN.md 4.1h.
@@ -90,7 +95,10 @@ struct ReqCount {
 // simply fetches the chunk that belongs at position l), which puts the 16 lanes of a read — 16 rows, one chunk index — into 16 different
 // bank groups again and leaves the read offsets immediates (a lane's run starts at ((q + r) mod 4) K bytes of its row instead of q K).
 template <int K, int D, bool RES, bool RELU, bool STEM = false, bool BATCH = false>
-__global__ __launch_bounds__(256, 1) void ws1x1f_kernel(const WsfArgs a) {
+// (the register bound of two workgroups per CU, 256 per lane, wherever the kernel fits it — all but K = 512, whose 128 filter registers do not: within
+//  it the compiler has no accumulation registers to put the products' sums into, and the epilogue reads them where they are: no v_accvgpr_read
+//  beside the products, 8 per step before.  LDS decides how many workgroups a CU really holds, as before.)
+__global__ __launch_bounds__(256, K >= 512 ? 1 : 2) void ws1x1f_kernel(const WsfArgs a) {
   static_assert(!BATCH || (!STEM && !RES && !RELU), "the batched form: plain products");
   static_assert(!STEM || (K == 224 && !RES), "the stem form: 7 taps x 32 image floats per output pixel (the request's eighth tap is never read), no shortcut");
   const long long t_entry = (long long)__builtin_amdgcn_s_memrealtime();
@@ -155,34 +163,47 @@ __global__ __launch_bounds__(256, 1) void ws1x1f_kernel(const WsfArgs a) {
   const unsigned ovec = (unsigned)((4 * p16 + q) * 16);                   // MFMA view: pixel p16, channels 4 q .. + 3
   const int orow = lane >> 2;                                             // memory view: pixel lane / 4, channels 4 (lane % 4) .. + 3
   const unsigned ooff = (unsigned)((nw0 + 4 * (lane & 3)) * 4);
+  // Addresses.  No request and no store of the step loop costs a vector instruction for its address (the stem: one): a lane's offset is
+  // loop invariant — made here, once — and everything that moves with the step is wave uniform and goes, by SALU, into the request's own
+  // DESCRIPTOR (dc_rsrc_behind): the base at the request's first row, num_records up to the last valid byte of the operand, (M - 1) x
+  // stride + row bytes behind the view's base.  Rows >= M are then out of range by the hardware's check, a stage beyond the range gets
+  // num_records 0.  soffset stays 0 on purpose: it takes no part in the range check of a raw buffer (kernel_prims.h), and with it the
+  // tail would need a select per request.
+  constexpr int LPR = 64 / RPR;  // K <= 128: lanes = 16-byte chunks per row
+  unsigned xlane = STEM      ? (unsigned)(lane >> 3) * (unsigned)a.xrsb + (unsigned)(lane & 7) * 16u  // image row `tap`, pixel px behind the patch's corner
+                   : RPR == 1 ? (unsigned)lane * 16u
+                              : (unsigned)(lane / LPR) * (unsigned)a.sxb + (unsigned)(((lane - lane / LPR * (LPR / 4)) & (LPR - 1)) * 16);  // row-in-request, rotated chunk
+  unsigned ylane = (unsigned)orow * (unsigned)a.ypb + ooff;
+  asm volatile("" : "+v"(xlane), "+v"(ylane));  // (kept in registers: not recomputed beside the products)
+  const int xbytes = (a.M - 1) * a.sxb + K * 4, ybytes = (a.M - 1) * a.ypb + a.Cout * 4;  // the views' last valid byte + 1
   auto dma_req = [&](int gs, int slot, int i) {  // request i of the wave's NA for stage gs (issued whatever gs is: beyond the range it moves nothing)
     const int row0 = gs * 16;
     const int lim = gs < gs1 ? a.M - row0 : 0;
     const int pc = wave + 4 * i;  // request pc of the stage
     if (STEM) {  // output pixel row0 + pc: lane 8 tap + px fetches pixel (2 ox - 3 + px) of image row (2 oy - 3 + tap); tap 7 and the pad are zeros
-      const int r = row0 + pc;
+      const bool ok = pc < lim;
+      const int r = ok ? row0 + pc : 0;
       const int n = dc_fastdiv(r, a.div_ohw), rem = r - n * a.OHW;
       const int oy = dc_fastdiv(rem, a.div_ow), ox = rem - oy * a.OW;
-      const int tap = lane >> 3, iy = 2 * oy - 3 + tap, ix = 2 * ox - 3 + (lane & 7);
-      const bool ok = pc < lim && tap < 7 && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-      const unsigned vo = ok ? (unsigned)n * (unsigned)a.ximgb + (unsigned)iy * (unsigned)a.xrsb + (unsigned)ix * 16u : kOOB;
-      dc_dma16(xr, lds0 + (unsigned)(slot * STG + pc * BLKB), vo);
-    } else if (RPR == 1) {        // part `part` of row `row`
-      const int row = pc / PPR, part = pc - row * PPR;
-      const unsigned vo = row < lim ? (unsigned)(row0 + row) * (unsigned)a.sxb + (unsigned)(part * 1024 + lane * 16) : kOOB;
-      dc_dma16(xr, lds0 + (unsigned)(slot * STG + row * BLKB + part * 1024), vo);
-    } else {                      // rows pc RPR .. + RPR - 1, K / 4 lanes each
-      constexpr int LPR = 64 / RPR;  // lanes = 16-byte chunks per row
-      const int r = lane / LPR, row = pc * RPR + r;
-      const unsigned vo = row < lim ? (unsigned)(row0 + row) * (unsigned)a.sxb + (unsigned)(((lane - r * (LPR / 4)) & (LPR - 1)) * 16) : kOOB;
-      dc_dma16(xr, lds0 + (unsigned)(slot * STG + pc * BLKB), vo);
+      // which lanes fetch: taps [t0, t1) have an image row (and tap 7 none), pixels [p0, p1) a column — two runs of bits, made by SALU
+      const int t0 = max(3 - 2 * oy, 0), t1 = min(a.H + 3 - 2 * oy, 7), p0 = max(3 - 2 * ox, 0), p1 = min(a.W + 3 - 2 * ox, 8);
+      const unsigned long long rows = t1 > t0 ? (1ull << (8 * t1)) - (1ull << (8 * t0)) : 0ull;
+      const unsigned cols = p1 > p0 ? ((1u << p1) - (1u << p0)) * 0x01010101u : 0u;
+      const unsigned long long mask = ok ? rows & (((unsigned long long)cols << 32) | cols) : 0ull;
+      const int off = n * a.ximgb + (2 * oy - 3) * a.xrsb + (2 * ox - 3) * 16;  // the patch's corner (in front of the image at its edges: those lanes are masked)
+      dc_dma16(dc_rsrc_behind(xr, off, 0x7fffffff), lds0 + (unsigned)(slot * STG + pc * BLKB), dc_lanes_or_oob(mask, xlane));
+    } else {  // K >= 256: part `part` of row `row`; K <= 128: rows pc RPR .. + RPR - 1, K / 4 lanes each
+      const int row = RPR == 1 ? pc / PPR : pc * RPR, part = RPR == 1 ? pc - row * PPR : 0;
+      const bool ok = row < lim;
+      const int off = ok ? (row0 + row) * a.sxb + part * 1024 : 0;
+      dc_dma16(dc_rsrc_behind(xr, off, ok ? xbytes - off : 0), lds0 + (unsigned)(RPR == 1 ? slot * STG + row * BLKB + part * 1024 : slot * STG + pc * BLKB), xlane);
     }
   };
   auto resid_step = [&](int gs, int buf) {  // NR requests, always
     if (!RES) return;
-    const int row0 = gs * 16;
-    const int lim = gs < gs1 ? a.M - row0 : 0;
-    dc_dma16(rr, lds0 + obuf0 + (unsigned)(buf * 1024), orow < lim ? (unsigned)(row0 + orow) * (unsigned)a.ypb + ooff : kOOB);
+    const bool ok = gs < gs1;  // (then gs 16 < M)
+    const int off = ok ? gs * 16 * a.ypb : 0;
+    dc_dma16(dc_rsrc_behind(rr, off, ok ? ybytes - off : 0), lds0 + obuf0 + (unsigned)(buf * 1024), ylane);
   };
   auto stamp = [&](int sl) {
     if (a.dbg && lane == 0) {
@@ -233,8 +254,8 @@ __global__ __launch_bounds__(256, 1) void ws1x1f_kernel(const WsfArgs a) {
     *reinterpret_cast<f32x4*>(obp + ovec) = o;
   };
   auto epi_store = [&](int gs, const u32x4& ov) {  // memory view: 16 pixels x 64-byte runs
-    const int row0 = gs * 16;
-    dc_store16_untracked(yr, orow < a.M - row0 ? (unsigned)(row0 + orow) * (unsigned)a.ypb + ooff : kOOB, ov);
+    const int off = gs * 16 * a.ypb;  // (gs < gs1: in the view) rows >= M, and only those, lie behind the descriptor's end: y may be a channel view
+    dc_store16_untracked(dc_rsrc_behind(yr, off, ybytes - off), ylane, ov);
   };
   auto do_step = [&](int gs, auto k_tag) {
     constexpr int KS = decltype(k_tag)::value;  // the step's number while the request counts still change (Rq), -1 in the steady state
@@ -389,6 +410,7 @@ bool stream1x1f_eligible(const ConvGemmParams& p) {
   if (p.x_rows != p.OH || p.x_row_stride != p.OW * p.sx || p.x_img_stride != (long)p.OH * p.x_row_stride || p.x_rowlen < (p.OW - 1) * p.sx + p.klen) return false;
   if (p.y_row_stride != p.OW * p.y_pix_stride || p.y_img_stride != (long)p.OH * p.y_row_stride) return false;
   if ((p.sx * 4) % 16 != 0 || (p.y_pix_stride * 4) % 16 != 0) return false;
+  if (p.sx < p.klen || p.y_pix_stride < p.Cout) return false;  // a row's bytes end in front of the next row: the descriptors' ends cut whole rows
   if ((long)p.M * p.sx * 4 >= 0x7fffffffL || (long)p.M * p.y_pix_stride * 4 >= 0x7fffffffL || (long)p.M / 16 * 512 >= 0x7fffffffL) return false;
   return true;
 }
@@ -408,7 +430,7 @@ bool stem_ws_eligible(const ConvGemmParams& p) {
   if (p.Cout != 64 || p.x_rowlen % 4 != 0 || p.x_row_stride < p.x_rowlen || p.x_row_stride % 4 != 0 || p.x_img_stride % 4 != 0) return false;
   const int W = p.x_rowlen / 4, H = p.x_rows;
   if (p.OH != (H + 6 - 7) / 2 + 1 || p.OW != (W + 6 - 7) / 2 + 1 || p.M != (long)p.NB * p.OH * p.OW) return false;
-  if (p.y_row_stride != p.OW * p.y_pix_stride || p.y_img_stride != (long)p.OH * p.y_row_stride || (p.y_pix_stride * 4) % 16 != 0) return false;
+  if (p.y_row_stride != p.OW * p.y_pix_stride || p.y_img_stride != (long)p.OH * p.y_row_stride || (p.y_pix_stride * 4) % 16 != 0 || p.y_pix_stride < p.Cout) return false;
   if ((long)p.NB * p.x_img_stride * 4 >= 0x7fffffffL || (long)p.M * p.y_pix_stride * 4 >= 0x7fffffffL) return false;  // 32-bit byte offsets
   return true;
 }

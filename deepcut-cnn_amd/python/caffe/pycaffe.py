@@ -348,6 +348,7 @@ def _load():
         "dc_stream1x1_pack": (ci, [C.c_void_p, ci, ci, C.c_void_p]),
         "dc_stem7x7_pack": (ci, [C.c_void_p, ci, C.c_void_p]),
         "dc_stream1x1f_pack": (ci, [C.c_void_p, ci, ci, C.c_void_p]),
+        "dc_stream1x1f_rows": (ci, [C.c_void_p, ci, ci, ci, C.c_void_p, ci, C.c_void_p, C.c_void_p, C.c_void_p, ci, ci, ci, C.c_void_p, ci]),
         "dc_wino43_pack": (ci, [C.c_void_p, ci, ci, C.c_void_p]),
         "dc_net_pairwise_at": (ci, [vp, ci, C.c_void_p, C.c_void_p]),
         "dc_sparse_head_pack_size": (ci, [ci, ci, ci]),
@@ -441,6 +442,22 @@ def stream1x1f_pack(g):
     out = np.empty((cout // 16, k // 16, 64, 4), np.float32)
     _check(_lib.dc_stream1x1f_pack(g.ctypes.data_as(C.c_void_p), cout, k, out.ctypes.data_as(C.c_void_p)))
     return out
+
+
+def stream1x1f_rows(x, g, y, y_c0=0, m=None, scale=None, shift=None, resid=None, relu=False):
+    """dc_stream1x1f_rows: one launch of the float32 streaming 1x1 form on x [rows, x_stride] (a pixel's channels: the first k floats of its row),
+    filters g [cout, k]; writes channels [y_c0, y_c0 + cout) of the first m rows (default: all rows of x) of y [y_rows, y_stride] IN PLACE;
+    resid: the shortcut, an array like y (tests / diagnostics)."""
+    x, g = np.ascontiguousarray(x, np.float32), np.ascontiguousarray(g, np.float32)
+    assert y.dtype == np.float32 and y.flags["C_CONTIGUOUS"] and y.ndim == 2 and x.ndim == 2 and g.ndim == 2
+    m = x.shape[0] if m is None else m
+    assert m <= x.shape[0]
+    opt = [None if v is None else np.ascontiguousarray(v, np.float32) for v in (scale, shift, resid)]
+    assert opt[2] is None or opt[2].shape == y.shape
+    ptr = lambda v: None if v is None else v.ctypes.data_as(C.c_void_p)
+    _check(_lib.dc_stream1x1f_rows(ptr(x), m, g.shape[1], x.shape[1], ptr(g), g.shape[0], ptr(opt[0]), ptr(opt[1]), ptr(y), y.shape[0], y.shape[1],
+                                   y_c0, ptr(opt[2]), 1 if relu else 0))
+    return y
 
 
 def wino43_pack(g):

@@ -533,6 +533,14 @@ int dc_stem7x7_pack(const float* g, int c, float* out);
  *    4 j + e of a 16-pixel step multiplies column (q k/4 + 4 j + e) of the filters with the same element of the pixel rows (one 16-byte LDS
  *    read of a pixel's row feeds four matrix steps).  tests/test_stream_pack.py.                                                        */
 int dc_stream1x1f_pack(const float* g, int cout, int k, float* out);
+/*  dc_stream1x1f_rows: ONE launch of that kernel on host arrays, with the strides a lowered net does not produce (tests / diagnostics):
+ *    x = [m][x_stride], the first k floats of a row are the pixel's channels; g = [cout][k] (packed here); scale / shift = [cout] or NULL;
+ *    y = [y_rows][y_stride], in and out: the launch writes channels [y_c0, y_c0 + cout) of rows [0, m) — a channel view of a wider tensor —
+ *    and every other element comes back as it went in; resid = NULL or the shortcut in y's layout, read at the same channels; relu != 0
+ *    applies the ReLU.  m <= y_rows, k in 64 / 128 / 256 / 512, cout % 64 == 0, strides and y_c0 multiples of 4.  Copies to the calling
+ *    thread's device, launches on its default stream, waits, copies y back.  tests/test_gpu_ws1x1f_addressing.py.                       */
+int dc_stream1x1f_rows(const float* x, int m, int k, int x_stride, const float* g, int cout, const float* scale, const float* shift, float* y,
+                       int y_rows, int y_stride, int y_c0, const float* resid, int relu);
 /*  dc_wino43_pack: the filter image of the unfused Winograd F(4x4,3x3) form (csrc/wino43_f32.hip, tile `wino_f43`): g = [cout][cin][3][3]
  *    (cout % 16 == 0, cin % 16 == 0) -> out[36 * cout * cin]: U = G g G^T per (co, ci) in double, rounded once to float; point p = 6 i + j
  *    (U[i][j]) is the [cout][cin] matrix at out + p * cout * cin, each in dc_stream1x1f_pack's order.  tests/test_wino43_host.py.          */

@@ -3,7 +3,7 @@
     python tools/wino43_profiles.py trace  <parent t_kernel_trace.csv> <change t_kernel_trace.csv>
     python tools/wino43_profiles.py pmc    <parent c_counter_collection.csv> <change c_counter_collection.csv>
 trace: per kernel and grid size (the shape), calls and average microseconds, the 3x3 layers' kernels first.
-pmc:   SQ_VALU_MFMA_BUSY_CYCLES and GRBM_GUI_ACTIVE summed over the dispatches of one forward (forwards = max-pool dispatches)."""
+pmc:   every collected counter (SQ_VALU_MFMA_BUSY_CYCLES first) summed over the dispatches of one forward (forwards = max-pool dispatches)."""
 import collections
 import csv
 import os
@@ -70,5 +70,4 @@ if __name__ == "__main__":
     else:
         for tag, p in (("parent", parent), ("change", change)):
             s, n = pmc(p)
-            print("%s: %d forwards; per forward SQ_VALU_MFMA_BUSY_CYCLES %.4g, GRBM_GUI_ACTIVE %.4g" % (
-                tag, n, s["SQ_VALU_MFMA_BUSY_CYCLES"] / n, s["GRBM_GUI_ACTIVE"] / n))
+            print("%s: %d forwards; per forward %s" % (tag, n, ", ".join("%s %.4g" % (c, s[c] / n) for c in sorted(s, key=lambda c: (c != "SQ_VALU_MFMA_BUSY_CYCLES", c)))))
