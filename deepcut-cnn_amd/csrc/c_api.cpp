@@ -1060,6 +1060,45 @@ int dc_group_get_completion(dc_group* group, dc_complete_params* out) {
   completion_out(G(group)->completion, out);
   return DC_OK;
 }
+// stage E of the people assembly: state of the net / the group like stage D's (DedupeParams::checked, people.cpp)
+static void dedupe_out(const DedupeParams& d, dc_dedupe_params* out, double* sigma_out) {
+  out->enabled = d.enabled;
+  out->max_dist = d.max_dist;
+  out->min_common = d.min_common;
+  out->min_size = d.min_size;
+  out->n_sigma = d.n_sigma;
+  out->absorb = d.absorb;
+  for (int j = 0; sigma_out && j < kPeopleMaxJoints; ++j) sigma_out[j] = d.sigma[j];
+}
+int dc_net_set_dedupe(dc_net* net, const dc_dedupe_params* p) {
+  REQUIRE(net);
+  return guard([&] { N(net)->dedupe = DedupeParams::checked(p, "set_dedupe"); });
+}
+int dc_net_get_dedupe(dc_net* net, dc_dedupe_params* out, double* sigma_out) {
+  REQUIRE(net);
+  REQUIRE(out);
+  dedupe_out(N(net)->dedupe, out, sigma_out);
+  return DC_OK;
+}
+int dc_group_set_dedupe(dc_group* group, const dc_dedupe_params* p) {
+  REQUIRE(group);
+  return guard([&] { G(group)->dedupe = DedupeParams::checked(p, "set_dedupe"); });
+}
+int dc_group_get_dedupe(dc_group* group, dc_dedupe_params* out, double* sigma_out) {
+  REQUIRE(group);
+  REQUIRE(out);
+  dedupe_out(G(group)->dedupe, out, sigma_out);
+  return DC_OK;
+}
+int dc_dedupe_people(const dc_dedupe_params* p, int nb, int P, int J, const int* n_people, const double* people, const int* cand, int* n_out,
+                     double* people_out, int* cand_out, int* kept_from, int* suppressed_by) {
+  REQUIRE(p);
+  REQUIRE(n_people);
+  REQUIRE(people);
+  REQUIRE(n_out);
+  REQUIRE(people_out);
+  return guard([&] { dedupe_people(p, nb, P, J, n_people, people, cand, n_out, people_out, cand_out, kept_from, suppressed_by); });
+}
 // single-person and box poses from the fused maps (net_group.cpp decode_pose / decode_boxes)
 int dc_group_decode_pose(dc_group* group, const double* scales, int base, const dc_fuse_mirror* fm, double* pose, int is_device, void* stream) {
   REQUIRE(group);

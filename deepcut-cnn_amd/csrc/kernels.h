@@ -416,6 +416,15 @@ int launch_complete(const void* prob, int pcp, int pc0, const void* loc, int lcp
                     int next_ekind, int NB, int H, int W, int J, int max_det, int max_people, double scale, int radius, float fill_thr,
                     int fill_radius, int min_support, const double* dets, const int* lut, const double* mean, const double* stdev,
                     const int* n_people, const int* cand_in, double* people, int* cand_out, void* stream);
+// duplicate suppression (stage E, one workgroup per image; the rule: include/deepcut_hip.h, dc_dedupe_params): n_in [NB], people_in
+//           [NB][max_people][J][3] and cand_in [NB][max_people][J] are the previous stage's outputs and are only read; sigma is a HOST
+//           array [J] or null (all 1.0) and travels as a kernel argument.  -> n_out, people_out, cand_out of the same shapes (buffers of
+//           their own, every entry written), kept_from / suppressed_by [NB][max_people] (device, either may be null).  Dynamic LDS:
+//           dedupe_lds_bytes(J, max_people), up to 128 KiB.
+size_t dedupe_lds_bytes(int J, int max_people);
+int launch_dedupe(int NB, int J, int max_people, double max_dist, int min_common, double min_size, int absorb, const double* sigma,
+                  const int* n_in, const double* people_in, const int* cand_in, int* n_out, double* people_out, int* cand_out,
+                  int* kept_from, int* suppressed_by, void* stream);
 
 // Tracking people from frame to frame (track.hip; the rule: include/deepcut_hip.h, dc_tracker_update — this project's own).  A slot's
 // state is one block of track_slot_bytes(T, J) bytes, all zero = no track and next_id 0:

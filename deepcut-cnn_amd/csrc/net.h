@@ -25,6 +25,7 @@
 
 struct dc_frame;  // include/deepcut_hip.h: one video frame (planes, pitches, format, matrix, range)
 struct dc_complete_params;  // include/deepcut_hip.h: stage D of the people assembly
+struct dc_dedupe_params;    // include/deepcut_hip.h: stage E of the people assembly
 
 namespace dc {
 
@@ -274,6 +275,23 @@ struct CompleteParams {
   static CompleteParams checked(const dc_complete_params* p);
 };
 
+// Stage E of the people assembly (dc_dedupe_params, include/deepcut_hip.h): state of a net or a group like CompleteParams
+struct DedupeParams {
+  int enabled = 0;
+  double max_dist = 0.0, min_size = 0.0;
+  int min_common = 0, n_sigma = 0, absorb = 0;
+  double sigma[kPeopleMaxJoints] = {};  // the first n_sigma are the caller's; n_sigma == 0: all 1.0
+  // DC_EINVAL naming the field; host only.  A null pointer is "off", and so is enabled == 0 unless `always` (dc_dedupe_people, which
+  // has no use for a switch)
+  static DedupeParams checked(const dc_dedupe_params* p, const char* who, bool always = false);
+  // DC_ESHAPE for an n_sigma that is neither 0 nor J and for min_common > J: what only a call that knows the joints can refuse
+  void check_joints(const char* who, int J) const;
+  const double* sigma_or_null() const { return n_sigma ? sigma : nullptr; }
+};
+// dc_dedupe_people (people.cpp): stage E alone on host arrays, synchronous
+void dedupe_people(const dc_dedupe_params* params, int nb, int P, int J, const int* n_people, const double* people, const int* cand,
+                   int* n_out, double* people_out, int* cand_out, int* kept_from, int* suppressed_by);
+
 struct Net {
   std::string name;
   int phase = 1;
@@ -289,6 +307,7 @@ struct Net {
   int outputs_mask = -1;  // DC_OPT_OUTPUTS: bit i = output i (order of `outputs`) is wanted
   int sparse_pairwise = 0;  // DC_OPT_SPARSE_PAIRWISE: a plan without next_pred has the pairwise head evaluated at the cells its consumers read
   CompleteParams completion;  // dc_net_set_completion: stage D behind every assembly of this net (off by default; a clone copies it)
+  DedupeParams dedupe;        // dc_net_set_dedupe: stage E behind stage D (or C), likewise
   std::shared_ptr<ModelShared> shared;   // joint with every clone
   uint64_t seen_weights_gen = 0;         // generation the cached plans were lowered from
   // the ACTIVE plan (the fields below are swapped with a parked PlanState when the input shape changes)
@@ -380,6 +399,7 @@ struct Net {
     int max_people, min_joints;
     CompleteParams complete{};  // what assemble_maps runs behind stage C: the net's or the group's setting, put there by assemble_last /
                                 // NetGroup::assemble_people (the entries leave it off)
+    DedupeParams dedupe{};      // likewise stage E, behind stage D (or stage C when completion is off)
   };
   // tracker (may be null; dc_net_track_people): its launch runs behind the assembly's on the people left on the device -> ids, place
   // [NB][max_people]; everything else is computed and returned exactly as without it.  slot_of (may be null: image b updates slot b):
@@ -459,8 +479,8 @@ struct Net {
                                                const double* stdev, const int* joint_order);
   // between (may be empty): called with stage A's device outputs (counts, dets) after its launch and before stage B's — the sparse
   // pairwise head fills N's cells there.  after (may be empty): called with stage C's device outputs (n_people, people) behind its
-  // launch — and behind stage D's when q.complete is enabled, on the completed people — and before the downloads — the tracker's launch
-  // goes there
+  // launch — and behind stage D's when q.complete is enabled, on the completed people, and stage E's when q.dedupe is, on the people it
+  // kept — and before the downloads — the tracker's launch goes there
   // keep (may be null: the table and the statistics go into the scratch with every call): where they stay on the device from call to call,
   // uploaded only when their content differs from what is there, from a host copy that outlives the upload.  wait = false: nothing is
   // waited for — the results are in the host arrays once `stream` has been, and nothing of the caller's small arguments is read after
@@ -612,6 +632,7 @@ struct GroupStats {
 struct NetGroup {
   std::vector<Net*> nets;  // borrowed: executors of one model (a net and its clones), alive as long as the group
   CompleteParams completion;  // dc_group_set_completion: stage D behind the assembly of the fused maps (the members' settings are not read)
+  DedupeParams dedupe;        // dc_group_set_dedupe: stage E likewise
   GroupStats stats;
   std::string text_buf;
   ~NetGroup();

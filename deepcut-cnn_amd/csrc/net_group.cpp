@@ -1162,6 +1162,7 @@ void NetGroup::assemble_people(const double* scales, int base, const Net::Assemb
   Net::AssembleParams q = p;
   q.scale = scales[base];
   q.complete = completion;  // stage D on the fused maps, when the group has it enabled
+  q.dedupe = dedupe;        // stage E likewise
   Net::check_assemble_params(q);
   const std::vector<int>& pshape = nets[(size_t)base]->prob_shape();
   const std::vector<int> table = Net::check_assemble_graph(q, pshape[1], n_edges, edges, mean, stdev, joint_order);

@@ -129,6 +129,7 @@ Net* Net::clone() {
   c->outputs_mask = outputs_mask;
   c->sparse_pairwise = sparse_pairwise;
   c->completion = completion;
+  c->dedupe = dedupe;
   if (dtype != c->dtype) {
     c->dtype = dtype;
     for (auto& st : c->storages)

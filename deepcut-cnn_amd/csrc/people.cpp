@@ -99,10 +99,11 @@ PairStats read_pair_stats(const std::string& path) {
 
 // ---- the device path ---------------------------------------------------------------------------------------------------
 // Stage A = Net::detect_parts' launch with its outputs left in the scratch buffer, stage B = launch_pair_cost, stage C =
-// launch_assemble, stage D = launch_complete (only with completion enabled: dc_net_set_completion): three or four launches on one
-// stream with nothing in between (DC_OPT_SPARSE_PAIRWISE on a net without next_pred: the sparse
-// head's two launches between A and B, sparse_pairwise.cpp), then the downloads of the results.  The argument checks
-// and the device half are functions of their own: NetGroup::assemble_people runs them on the fused maps of a pyramid (net_group.cpp).
+// launch_assemble, stage D = launch_complete (only with completion enabled: dc_net_set_completion), stage E = launch_dedupe (only with
+// duplicate suppression enabled: dc_net_set_dedupe): three to five launches on one stream with nothing in between
+// (DC_OPT_SPARSE_PAIRWISE on a net without next_pred: the sparse head's two launches between A and B, sparse_pairwise.cpp), then the
+// downloads of the results.  The argument checks and the device half are functions of their own: NetGroup::assemble_people runs them
+// on the fused maps of a pyramid (net_group.cpp).
 void Net::check_assemble_params(const AssembleParams& q) {
   auto bad = [](const std::string& m) { throw DcError(DC_EINVAL, "assemble_people: " + m); };
   if (!(q.scale > 0) || !std::isfinite(q.scale)) bad("scale must be positive");
@@ -127,6 +128,100 @@ CompleteParams CompleteParams::checked(const dc_complete_params* p) {
   c.fill_radius = p->fill_radius;
   c.min_support = p->min_support;
   return c;
+}
+
+// dc_net_set_dedupe / dc_group_set_dedupe / dc_dedupe_people: likewise
+DedupeParams DedupeParams::checked(const dc_dedupe_params* p, const char* who, bool always) {
+  DedupeParams d;
+  if (!always && (!p || !p->enabled)) return d;  // off: the other fields are not read
+  auto bad = [&](const std::string& m) { throw DcError(DC_EINVAL, std::string(who) + ": " + m); };
+  if (!p) bad("null argument: params");
+  if (!std::isfinite(p->max_dist) || !(p->max_dist >= 0)) bad("max_dist must be finite and >= 0");
+  if (p->min_common < 1) bad("min_common must be >= 1");
+  if (!std::isfinite(p->min_size) || !(p->min_size > 0)) bad("min_size must be finite and > 0");
+  if (p->n_sigma < 0 || p->n_sigma > kPeopleMaxJoints) bad("n_sigma must be in [0, " + std::to_string(kPeopleMaxJoints) + "]");
+  if (p->n_sigma != 0 && !p->sigma) bad("sigma must be [n_sigma] values, or NULL with n_sigma = 0");
+  for (int j = 0; j < p->n_sigma; ++j)
+    if (!(std::isfinite(p->sigma[j]) && p->sigma[j] > 0)) bad("sigma of joint " + std::to_string(j) + " must be finite and > 0");
+  if (p->absorb != 0 && p->absorb != 1) bad("absorb must be 0 or 1");
+  d.enabled = 1;
+  d.max_dist = p->max_dist, d.min_size = p->min_size;
+  d.min_common = p->min_common, d.n_sigma = p->n_sigma, d.absorb = p->absorb;
+  for (int j = 0; j < p->n_sigma; ++j) d.sigma[j] = p->sigma[j];
+  return d;
+}
+
+void DedupeParams::check_joints(const char* who, int J) const {
+  if (n_sigma != 0 && n_sigma != J)
+    throw DcError(DC_ESHAPE, std::string(who) + ": dedupe holds " + std::to_string(n_sigma) + " sigma values (n_sigma), the poses " +
+                                 std::to_string(J) + " joints");
+  if (min_common > J)
+    throw DcError(DC_ESHAPE, std::string(who) + ": dedupe min_common = " + std::to_string(min_common) + " is more than the poses' " +
+                                 std::to_string(J) + " joints");
+}
+
+// dc_dedupe_people: stage E alone on host poses (top-down poses before dc_tracker_update).  One launch on the utility stream, synchronous
+void dedupe_people(const dc_dedupe_params* params, int nb, int P, int J, const int* n_people, const double* people, const int* cand,
+                   int* n_out, double* people_out, int* cand_out, int* kept_from, int* suppressed_by) {
+  const char* who = "dedupe_people";
+  auto bad = [&](const std::string& m) { throw DcError(DC_EINVAL, std::string(who) + ": " + m); };
+  const DedupeParams d = DedupeParams::checked(params, who, true);
+  if (nb < 1) bad("nb must be >= 1");
+  if (P < 1 || P > kPeopleMaxPeople) bad("max_people (P) must be in [1, " + std::to_string(kPeopleMaxPeople) + "]");
+  if (J < 1 || J > kPeopleMaxJoints) bad("n_joints (J) must be in [1, " + std::to_string(kPeopleMaxJoints) + "]");
+  for (int b = 0; b < nb; ++b)
+    if (n_people[b] < 0 || n_people[b] > P)
+      bad("n_people[" + std::to_string(b) + "] = " + std::to_string(n_people[b]) + " is outside [0, P = " + std::to_string(P) + "]");
+  d.check_joints(who, J);
+  if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "dedupe_people() in CPU mode");
+  if (device_count() <= 0) throw DcError(DC_EDEVICE, "no HIP device visible");
+  HIPCHECK(hipSetDevice(Context::get().device));
+  const size_t img = (size_t)P * J, N = (size_t)nb;
+  // without `cand` a joint counts as assigned exactly when it is held: candidate 0 there, -1 elsewhere
+  std::vector<int> made;
+  if (!cand) {
+    made.assign(N * img, -1);
+    for (int b = 0; b < nb; ++b)
+      for (size_t e = 0; e < (size_t)n_people[b] * J; ++e)
+        if (people[((size_t)b * img + e) * 3 + 2] > 0.0) made[(size_t)b * img + e] = 0;
+    cand = made.data();
+  }
+  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+  const size_t np_b = up(N * sizeof(int)), ppl_b = up(N * img * 3 * sizeof(double)), cand_b = up(N * img * sizeof(int)),
+               row_b = up(N * P * sizeof(int));
+  RuntimeLock rl;
+  hipStream_t s = util_stream();
+  DevBuf buf;
+  unsigned char* at = (unsigned char*)buf.get(2 * (np_b + ppl_b + cand_b + row_b));
+  auto take = [&](size_t b) {
+    unsigned char* r = at;
+    at += b;
+    return r;
+  };
+  int* d_np = (int*)take(np_b);
+  double* d_ppl = (double*)take(ppl_b);
+  int* d_cand = (int*)take(cand_b);
+  int* d_np2 = (int*)take(np_b);
+  double* d_ppl2 = (double*)take(ppl_b);
+  int* d_cand2 = (int*)take(cand_b);
+  int* d_from = (int*)take(row_b);
+  int* d_by = (int*)take(row_b);
+  HIPCHECK(hipMemcpyAsync(d_np, n_people, N * sizeof(int), hipMemcpyHostToDevice, s));
+  // only the people that exist are read on either side
+  for (int b = 0; b < nb; ++b)
+    if (n_people[b] > 0) {
+      const size_t m = (size_t)n_people[b] * J;
+      HIPCHECK(hipMemcpyAsync(d_ppl + (size_t)b * img * 3, people + (size_t)b * img * 3, m * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+      HIPCHECK(hipMemcpyAsync(d_cand + (size_t)b * img, cand + (size_t)b * img, m * sizeof(int), hipMemcpyHostToDevice, s));
+    }
+  KCHECK(launch_dedupe(nb, J, P, d.max_dist, d.min_common, d.min_size, d.absorb, d.sigma_or_null(), d_np, d_ppl, d_cand, d_np2, d_ppl2, d_cand2,
+                       d_from, d_by, s));
+  HIPCHECK(hipMemcpyAsync(n_out, d_np2, N * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipMemcpyAsync(people_out, d_ppl2, N * img * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (cand_out) HIPCHECK(hipMemcpyAsync(cand_out, d_cand2, N * img * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (kept_from) HIPCHECK(hipMemcpyAsync(kept_from, d_from, N * P * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (suppressed_by) HIPCHECK(hipMemcpyAsync(suppressed_by, d_by, N * P * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
 }
 
 std::vector<int> Net::check_assemble_graph(const AssembleParams& q, int J, int n_edges, const int* edges, const double* mean,
@@ -192,6 +287,7 @@ void Net::assemble_last(const AssembleParams& q_in, const std::vector<int>& tabl
                         bool wait) {
   AssembleParams q = q_in;
   q.complete = completion;  // stage D, when the net has it enabled
+  q.dedupe = dedupe;        // stage E likewise
   const MapRef P = map_ref("prob"), L = map_ref("loc_pred");
   if (sparse_pairwise && !next_in_plan()) {  // DC_OPT_SPARSE_PAIRWISE: the head at the candidates' cells, between stages A and B
     const SparseNext sn = sparse_next(P.NB * P.C * q.max_det, 0);
@@ -244,6 +340,8 @@ void Net::assemble_maps(const MapRef& P, const MapRef& L, const MapRef& N, const
   if (N.C % 2 || n_edges != N.C / 2)
     throw DcError(DC_ESHAPE, "assemble_people: " + std::to_string(n_edges) + " edges for a next_pred of " + std::to_string(N.C) +
                                  " channels (2 per regression edge)");
+  const bool dedupe = q.dedupe.enabled != 0;
+  if (dedupe) q.dedupe.check_joints("assemble_people", J);
   const int NB = P.NB, MD = q.max_det, PP = q.max_people, E = n_edges, lists = NB * J;
   auto up = [](size_t b) { return (b + 255) / 256 * 256; };
   const size_t cnt_b = up((size_t)lists * sizeof(int));
@@ -259,8 +357,9 @@ void Net::assemble_maps(const MapRef& P, const MapRef& L, const MapRef& N, const
   const size_t cand_b = up((size_t)NB * PP * J * sizeof(int));
   const bool complete = q.complete.enabled != 0;
   const size_t fill_b = complete ? cand_b : 0;  // stage D writes `cand` into a buffer of its own: it reads stage C's while it runs
+  const size_t kept_b = dedupe ? np_b + ppl_b + cand_b : 0;  // stage E writes all three into buffers of its own, for the same reason
   unsigned char* base =
-      (unsigned char*)scratch(cnt_b + spill_b + det_b + (keep ? 0 : tab_b + st_b) + cost_b + link_b + np_b + ppl_b + cand_b + fill_b);
+      (unsigned char*)scratch(cnt_b + spill_b + det_b + (keep ? 0 : tab_b + st_b) + cost_b + link_b + np_b + ppl_b + cand_b + fill_b + kept_b);
   unsigned char* at = base;
   auto take = [&](size_t b) {
     unsigned char* r = at;
@@ -302,6 +401,9 @@ void Net::assemble_maps(const MapRef& P, const MapRef& L, const MapRef& N, const
   double* d_ppl = (double*)take(ppl_b);
   int* d_cand = (int*)take(cand_b);
   int* d_filled = complete ? (int*)take(fill_b) : nullptr;
+  int* d_np_kept = dedupe ? (int*)take(np_b) : nullptr;
+  double* d_ppl_kept = dedupe ? (double*)take(ppl_b) : nullptr;
+  int* d_cand_kept = dedupe ? (int*)take(cand_b) : nullptr;
   if (!keep) {
     HIPCHECK(hipMemcpyAsync(d_tab, table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice, s));
     if (E) HIPCHECK(hipMemcpyAsync(d_mean, stats.data(), stats.size() * sizeof(double), hipMemcpyHostToDevice, s));
@@ -317,6 +419,11 @@ void Net::assemble_maps(const MapRef& P, const MapRef& L, const MapRef& N, const
                            q.complete.fill_threshold, q.complete.fill_radius, q.complete.min_support, d_det, d_tab, d_mean, d_std, d_np, d_cand,
                            d_ppl, d_filled, stream));
     d_cand = d_filled;
+  }
+  if (dedupe) {  // stage E: the people a better one is the same as leave; the tracker and the downloads below take what it kept
+    KCHECK(launch_dedupe(NB, J, PP, q.dedupe.max_dist, q.dedupe.min_common, q.dedupe.min_size, q.dedupe.absorb, q.dedupe.sigma_or_null(), d_np,
+                         d_ppl, d_cand, d_np_kept, d_ppl_kept, d_cand_kept, nullptr, nullptr, stream));
+    d_np = d_np_kept, d_ppl = d_ppl_kept, d_cand = d_cand_kept;
   }
   if (after) after(d_np, d_ppl);
   HIPCHECK(hipMemcpyAsync(n_people, d_np, (size_t)NB * sizeof(int), hipMemcpyDeviceToHost, s));

@@ -10,6 +10,9 @@
 // and, only when the caller enabled completion (dc_net_set_completion), a third behind them:
 //   complete_kernel   one workgroup per (image, joint j): the joints j that people lack, looked for in the score map around the mean
 //                     of the positions their held joints predict (stage D; like B and C this project's own rule)
+// and, only when the caller enabled duplicate suppression (dc_net_set_dedupe), or through dc_dedupe_people, one more:
+//   dedupe_kernel     one workgroup per image: people ranked by score, everybody a better kept person is "the same" as by the
+//                     tracker's distance suppressed, optionally absorbed, the rest compacted (stage E; this project's own rule too)
 // All arithmetic is double, like the two decoders.  Double rate does not matter here: a full cost tensor (14 x 14 x 64 x 64) is
 // 1.6 M square roots, and the usual one (16 candidates) a sixteenth of it.
 #include <hip/hip_runtime.h>
@@ -358,6 +361,173 @@ __global__ __launch_bounds__(256) void complete_kernel(const T* __restrict__ pro
   }
 }
 
+// Stage E, duplicate suppression (opt-in; the rule: include/deepcut_hip.h, dc_dedupe_params).  One workgroup per image, thread q =
+// person q of the input:
+//   1. thread q: S_q, s_q^2 and the held mask, joints ascending;
+//   2. rank_q = the number of people that rank before q, counted over S in LDS (S is never a NaN: only scores > 0 are summed).  A count
+//      needs no 72-bit (S, q) sort key and no order of its own; the poses then go to LDS IN RANK ORDER as a structure of arrays
+//      px, py [j][rank]: the 64 lanes of a wave below read 64 consecutive 8-byte words of one joint — each 32-lane half covers the 64
+//      banks once — and the better-ranked side of a pair is one address per wave, a broadcast;
+//   3. the similarity matrix as bits: a wave takes (rank ra, word w), lane l the pair (ra, rb = 64 w + l) with rb > ra, the sum of a
+//      pair runs over the joints ascending in that one lane, and the ballot of the decisions is word w of row ra — every word has one
+//      writer;
+//   4. wave 0 sweeps the ranks: lane w owns word w of the `removed` set; a kept ra ors its row in and the bits that are new record ra as
+//      their killer.  The loop has n trips, whatever the data;
+//   5. thread q again: kept people are counted by a prefix over q (ballots and four wave totals), so they keep their input order; then
+//      every (output person, joint) item copies its joint, from the first-ranked donor when absorbing.
+// Values are copied, never computed: only the decisions depend on arithmetic.  No atomics; the inputs are read only and the outputs
+// are buffers of their own, so nothing read here is written here.
+struct DedupeSigma {
+  double s2[kPeopleMaxJoints];  // sigma_j^2, 1.0 where the caller gave none
+};
+__global__ __launch_bounds__(256) void dedupe_kernel(int J, int P, double max_dist, int min_common, double min_size, int absorb,
+                                                     DedupeSigma sig, const int* __restrict__ n_in, const double* __restrict__ ppl_in,
+                                                     const int* __restrict__ cand_in, int* __restrict__ n_out,
+                                                     double* __restrict__ ppl_out, int* __restrict__ cand_out,
+                                                     int* __restrict__ kept_from, int* __restrict__ supp_by) {
+  extern __shared__ double dd_lds[];  // px [J][P], py [J][P], rank order
+  __shared__ unsigned long long sim[kPeopleMaxPeople * 4];  // row ra, word w: bit l = rank 64 w + l is similar to ra (and ranks behind it)
+  __shared__ double S_s[kPeopleMaxPeople];                  // by person
+  __shared__ double s2_s[kPeopleMaxPeople];                 // by rank: s^2
+  __shared__ double sig2[kPeopleMaxJoints];
+  __shared__ unsigned hm_s[kPeopleMaxPeople];  // by rank: bit j = joint j is held
+  __shared__ int order_s[kPeopleMaxPeople];    // rank -> person
+  __shared__ int rank_s[kPeopleMaxPeople];     // person -> rank
+  __shared__ int by_s[kPeopleMaxPeople];       // by rank: the rank of the kept person that suppressed it, or -1 = kept
+  __shared__ int from_s[kPeopleMaxPeople];     // output person -> input person
+  __shared__ int wtot[4];
+  const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int n = min(max(n_in[b], 0), P);
+  const double inf = __builtin_huge_val();
+  const double* pin = ppl_in + (long)b * P * J * 3;
+  const int* cin = cand_in + (long)b * P * J;
+  double* px = dd_lds;
+  double* py = px + J * P;
+
+  // 1. score, size, held
+  double S = 0.0, size2 = 0.0;
+  unsigned held = 0u;
+  if (t < n) {
+    double x0 = inf, x1 = -inf, y0 = inf, y1 = -inf;
+    for (int j = 0; j < J; ++j) {
+      const double* p = pin + ((long)t * J + j) * 3;
+      const double sc = p[2];
+      if (sc > 0.0) {  // false for a NaN
+        held |= 1u << j, S += sc;
+        x0 = fmin(x0, p[0]), x1 = fmax(x1, p[0]), y0 = fmin(y0, p[1]), y1 = fmax(y1, p[1]);
+      }
+    }
+    double s = min_size;  // as track_image (track.hip) sizes a track
+    if (x1 >= x0) s = fmax(s, fmax(x1 - x0, y1 - y0));
+    size2 = s * s;
+  }
+  S_s[t] = S, by_s[t] = -1;
+  if (t < J) sig2[t] = sig.s2[t];
+  __syncthreads();
+
+  // 2. rank, and the poses in rank order
+  int r = 0;
+  if (t < n) {
+    for (int o = 0; o < n; ++o) {
+      const double So = S_s[o];
+      r += (So > S || (So == S && o < t)) ? 1 : 0;
+    }
+    order_s[r] = t, rank_s[t] = r, hm_s[r] = held, s2_s[r] = size2;
+    for (int j = 0; j < J; ++j) {
+      const double* p = pin + ((long)t * J + j) * 3;
+      px[j * P + r] = p[0], py[j * P + r] = p[1];
+    }
+  }
+  __syncthreads();
+
+  // 3. similarity
+  const int nw = (n + 63) >> 6;
+  for (int task = wave; task < n * nw; task += 4) {  // uniform per wave
+    const int ra = task / nw, w = task - ra * nw, rb = w * 64 + lane;
+    bool similar = false;
+    if (rb > ra && rb < n) {
+      const unsigned common = hm_s[ra] & hm_s[rb];
+      const double sa2 = s2_s[ra];
+      double sum = 0.0;
+      int nc = 0;
+      for (int j = 0; j < J; ++j)
+        if ((common >> j) & 1u) {
+          const double dx = px[j * P + ra] - px[j * P + rb], dy = py[j * P + ra] - py[j * P + rb];
+          sum += (dx * dx + dy * dy) / (sa2 * sig2[j]);
+          ++nc;
+        }
+      similar = nc >= min_common && nc > 0 && sum / (double)nc <= max_dist;  // false for a NaN
+    }
+    const unsigned long long word = __ballot(similar);
+    if (lane == 0) sim[ra * 4 + w] = word;
+  }
+  __syncthreads();
+
+  // 4. the sweep in rank order
+  if (wave == 0) {
+    unsigned long long removed = 0ull;
+    for (int ra = 0; ra < n; ++ra) {
+      const unsigned long long mine = __shfl(removed, ra >> 6);
+      if ((mine >> (ra & 63)) & 1ull) continue;  // a suppressed person suppresses nobody (uniform)
+      const unsigned long long row = lane < nw ? sim[ra * 4 + lane] : 0ull;
+      const unsigned long long fresh = row & ~removed;
+      removed |= fresh;
+      for (int w = 0; w < nw; ++w) {
+        const unsigned long long f = __shfl(fresh, w);
+        if ((f >> lane) & 1ull) by_s[w * 64 + lane] = ra;
+      }
+    }
+  }
+  __syncthreads();
+
+  // 5. compaction in input order
+  const bool kept = t < n && by_s[r] < 0;
+  const unsigned long long kb = __ballot(kept);
+  if (lane == 0) wtot[wave] = __popcll(kb);
+  __syncthreads();
+  int o = __popcll(kb & ((1ull << lane) - 1ull)), total = 0;
+  for (int w = 0; w < 4; ++w) {
+    if (w < wave) o += wtot[w];
+    total += wtot[w];
+  }
+  if (kept) from_s[o] = t;
+  if (t < P) {
+    if (supp_by) supp_by[(long)b * P + t] = (t < n && !kept) ? order_s[by_s[r]] : -1;
+    if (kept_from && t >= total) kept_from[(long)b * P + t] = -1;
+  }
+  if (kept && kept_from) kept_from[(long)b * P + o] = t;
+  if (t == 0) n_out[b] = total;
+  __syncthreads();
+
+  double* pout = ppl_out + (long)b * P * J * 3;
+  int* cout = cand_out + (long)b * P * J;
+  for (int e = t; e < P * J; e += 256) {
+    const int q = e / J, j = e - q * J;
+    double x = 0.0, y = 0.0, sc = 0.0;
+    int c = -1;
+    if (q < total) {
+      const int A = from_s[q];
+      int src = A;
+      c = cin[A * J + j];
+      if (absorb && c < 0) {  // missing or filled: the first-ranked donor among the people A suppressed
+        const int rA = rank_s[A];
+        for (int rd = rA + 1; rd < n; ++rd) {
+          if (by_s[rd] != rA) continue;
+          const int d = order_s[rd], cd = cin[d * J + j];
+          if (cd >= 0) {
+            src = d, c = cd;
+            break;
+          }
+        }
+      }
+      const double* p = pin + ((long)src * J + j) * 3;
+      x = p[0], y = p[1], sc = p[2];
+    }
+    pout[(long)e * 3] = x, pout[(long)e * 3 + 1] = y, pout[(long)e * 3 + 2] = sc;
+    cout[e] = c;
+  }
+}
+
 size_t pair_cost_lds_bytes(int J, int max_det) { return ((size_t)2 * J * max_det + 6 * (size_t)max_det) * sizeof(double); }
 
 int launch_pair_cost(const void* next, int ncp, int nc0, int ekind, int NB, int H, int W, int J, int max_det, double scale, const int* counts,
@@ -401,6 +571,25 @@ int launch_complete(const void* prob, int pcp, int pc0, const void* loc, int lcp
       return (int)hipGetLastError();
     });
   });
+}
+
+size_t dedupe_lds_bytes(int J, int max_people) { return (size_t)2 * J * max_people * sizeof(double); }
+
+int launch_dedupe(int NB, int J, int max_people, double max_dist, int min_common, double min_size, int absorb, const double* sigma,
+                  const int* n_in, const double* people_in, const int* cand_in, int* n_out, double* people_out, int* cand_out,
+                  int* kept_from, int* suppressed_by, void* stream) {
+  if (NB <= 0) return 0;
+  if (J < 1 || J > kPeopleMaxJoints || max_people < 1 || max_people > kPeopleMaxPeople || min_common < 1) return (int)hipErrorInvalidValue;
+  DedupeSigma sig;
+  for (int j = 0; j < kPeopleMaxJoints; ++j) sig.s2[j] = (sigma && j < J) ? sigma[j] * sigma[j] : 1.0;
+  const size_t lds = dedupe_lds_bytes(J, max_people);
+  if (lds > 32 * 1024) {  // beyond what a launch gets unasked (the kernel's own arrays take 16 KiB more); 128 KiB at J = 32, P = 256
+    const hipError_t e = hipFuncSetAttribute((const void*)dedupe_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+  }
+  hipLaunchKernelGGL(dedupe_kernel, dim3(NB), dim3(256), lds, (hipStream_t)stream, J, max_people, max_dist, min_common, min_size, absorb, sig,
+                     n_in, people_in, cand_in, n_out, people_out, cand_out, kept_from, suppressed_by);
+  return (int)hipGetLastError();
 }
 
 }  // namespace dc

@@ -47,6 +47,12 @@ class CompleteParams(C.Structure):
     _fields_ = [("enabled", C.c_int), ("fill_threshold", C.c_float), ("fill_radius", C.c_int), ("min_support", C.c_int)]
 
 
+class DedupeParams(C.Structure):
+    """dc_dedupe_params (include/deepcut_hip.h)."""
+    _fields_ = [("enabled", C.c_int), ("max_dist", C.c_double), ("min_common", C.c_int), ("min_size", C.c_double), ("sigma", C.c_void_p),
+                ("n_sigma", C.c_int), ("absorb", C.c_int)]
+
+
 class FuseMirror(C.Structure):
     """dc_fuse_mirror (include/deepcut_hip.h)."""
     _fields_ = [("mirror", C.c_void_p), ("image_width", C.c_int), ("joint_mirror", C.c_void_p), ("n_edges", C.c_int), ("edges", C.c_void_p)]
@@ -66,6 +72,9 @@ class DcFrame(C.Structure):
 MAX_ASSEMBLE_DET, MAX_ASSEMBLE_PEOPLE = 64, 256  # dc_net_assemble_people's limits
 # Stage D of the people assembly (`Net.completion`, the `complete=` arguments).  PLACEHOLDERS, not tuned on real images: override them.
 COMPLETE_DEFAULTS = {"fill_threshold": 0.25, "fill_radius": 2, "min_support": 2}
+# Stage E of the people assembly (`Net.dedupe`, the `dedupe=` arguments, `dedupe_people`).  PLACEHOLDERS, not tuned on real images:
+# override them.  sigma None = 1.0 for every joint.
+DEDUPE_DEFAULTS = {"max_dist": 0.05, "min_common": 3, "min_size": 32.0, "sigma": None, "absorb": True}
 PIX_BGR24, PIX_NV12 = 0, 1  # DC_PIX_*
 _CSC_MATRIX = {"bt601": 0, "bt709": 1}  # DC_CSC_*
 _CSC_RANGE = {"limited": 0, "full": 1}  # DC_RANGE_*
@@ -357,6 +366,11 @@ def _load():
         "dc_net_get_completion": (ci, [vp, C.POINTER(CompleteParams)]),
         "dc_group_set_completion": (ci, [vp, C.POINTER(CompleteParams)]),
         "dc_group_get_completion": (ci, [vp, C.POINTER(CompleteParams)]),
+        "dc_net_set_dedupe": (ci, [vp, C.POINTER(DedupeParams)]),
+        "dc_net_get_dedupe": (ci, [vp, C.POINTER(DedupeParams), C.c_void_p]),
+        "dc_group_set_dedupe": (ci, [vp, C.POINTER(DedupeParams)]),
+        "dc_group_get_dedupe": (ci, [vp, C.POINTER(DedupeParams), C.c_void_p]),
+        "dc_dedupe_people": (ci, [C.POINTER(DedupeParams), ci, ci, ci] + [C.c_void_p] * 8),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -835,9 +849,120 @@ def completion_params(complete):
     return dict(COMPLETE_DEFAULTS, **complete)
 
 
+def dedupe_params(dedupe):
+    """A `dedupe=` argument / a `dedupe` value -> the dict of the five parameters, or None for off.  None and False are off, True is
+    DEDUPE_DEFAULTS (PLACEHOLDERS, not tuned on real images), a dict overrides some of them.  The values themselves are checked by the
+    library (dc_net_set_dedupe)."""
+    if dedupe is None or dedupe is False:
+        return None
+    if dedupe is True:
+        return dict(DEDUPE_DEFAULTS)
+    if not isinstance(dedupe, dict):
+        raise TypeError("dedupe must be None, True or a dict of %s, got %r" % (sorted(DEDUPE_DEFAULTS), dedupe))
+    unknown = sorted(set(dedupe) - set(DEDUPE_DEFAULTS))
+    if unknown:
+        raise ValueError("dedupe: unknown keys %r (known: %s)" % (unknown, sorted(DEDUPE_DEFAULTS)))
+    return dict(DEDUPE_DEFAULTS, **dedupe)
+
+
+def _dedupe_struct(d):
+    """The dict of `dedupe_params` -> (DedupeParams, what must stay alive beside it)."""
+    try:
+        sig = None if d["sigma"] is None else np.ascontiguousarray(d["sigma"], dtype=np.float64).reshape(-1)
+        q = DedupeParams(1, float(d["max_dist"]), int(d["min_common"]), float(d["min_size"]), None if sig is None else sig.ctypes.data,
+                         0 if sig is None else int(sig.shape[0]), int(bool(d["absorb"])))
+    except (TypeError, ValueError) as e:
+        raise ValueError("dedupe: max_dist and min_size must be numbers, min_common a whole number, sigma numbers or None (%s)" % (e,))
+    return q, sig
+
+
+def dedupe_people(people, n_people=None, cand=None, dedupe=True, return_maps=False):
+    """Stage E of the people assembly alone, on poses from anywhere (dc_dedupe_people; the rule: include/deepcut_hip.h): the people a
+    better-scored kept person is the same as, by the tracker's distance, are suppressed.  This is how top-down poses of `forward_boxes`
+    (overlapping boxes give the same person twice) are cleaned before `Tracker.update`.
+    people: [nb, P, J, 3] float64 (x, y, score; a joint is held when its score > 0) with n_people [nb] of them valid per image, or a
+    list of nb arrays [m_b, J, 3], as `Tracker.update` takes them.  cand: int32 [nb, P, J] (or a list of [m_b, J]) as `assemble_people`
+    returns it, or None: a joint then counts as assigned exactly when it is held.  dedupe: True (DEDUPE_DEFAULTS: PLACEHOLDERS, not
+    tuned on real images) or a dict of some of max_dist, min_common, min_size, sigma, absorb.
+    -> one dict per image: {"people": [m, J, 3], "cand": int32 [m, J]}, the kept people in input order; with return_maps also
+    "kept_from": int32 [m] (the input index of every kept person) and "suppressed_by": int32 [n_b] (per input person the input index of
+    the kept person that suppressed it, -1 = kept).  Needs GPU mode."""
+    d = dedupe_params(dedupe)
+    if d is None:
+        raise ValueError("dedupe_people needs parameters: dedupe=True or a dict, not %r" % (dedupe,))
+    q, _sig = _dedupe_struct(d)
+    if n_people is None and not (isinstance(people, np.ndarray) and people.ndim == 4):
+        arrs = [np.asarray(a, np.float64) for a in people]
+        if not arrs:
+            return []
+        j = max([a.shape[1] for a in arrs if a.ndim == 3] or [0])
+        if j < 1 or any(a.ndim != 3 or a.shape[1:] != (j, 3) for a in arrs):
+            raise ValueError("people must be arrays [m, J, 3] of one J, got shapes %s" % ([a.shape for a in arrs],))
+        n = np.array([a.shape[0] for a in arrs], np.int32)
+        ppl = np.zeros((len(arrs), max(1, int(n.max())), j, 3), np.float64)
+        cnd = None if cand is None else np.full(ppl.shape[:3], -1, np.int32)
+        for b, a in enumerate(arrs):
+            ppl[b, :a.shape[0]] = a
+            if cnd is not None:
+                cnd[b, :a.shape[0]] = np.asarray(cand[b], np.int32).reshape(a.shape[0], j)
+    else:
+        ppl = np.ascontiguousarray(people, dtype=np.float64)
+        if ppl.ndim != 4 or ppl.shape[3] != 3:
+            raise ValueError("people must be [nb, P, J, 3] (x, y, score), got shape %s" % (ppl.shape,))
+        n = np.full(ppl.shape[0], ppl.shape[1], np.int32) if n_people is None else np.ascontiguousarray(n_people, dtype=np.int32).reshape(-1)
+        if n.shape[0] != ppl.shape[0]:
+            raise ValueError("n_people must hold one count per image: %d counts for %d images" % (n.shape[0], ppl.shape[0]))
+        cnd = None if cand is None else np.ascontiguousarray(cand, dtype=np.int32)
+        if cnd is not None and cnd.shape != ppl.shape[:3]:
+            raise ValueError("cand must be %s like people, got shape %s" % (ppl.shape[:3], cnd.shape))
+    nb, p, j = ppl.shape[:3]
+    n_out = np.zeros(nb, np.int32)
+    ppl_out, cand_out = np.zeros((nb, p, j, 3), np.float64), np.full((nb, p, j), -1, np.int32)
+    kept_from, by = np.full((nb, p), -1, np.int32), np.full((nb, p), -1, np.int32)
+    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    _check(_lib.dc_dedupe_people(C.byref(q), nb, p, j, ptr(n), ptr(ppl), ptr(cnd), ptr(n_out), ptr(ppl_out), ptr(cand_out), ptr(kept_from),
+                                 ptr(by)))
+    out = []
+    for b in range(nb):
+        m = int(n_out[b])
+        e = {"people": ppl_out[b, :m].copy(), "cand": cand_out[b, :m].copy()}
+        if return_maps:
+            e["kept_from"], e["suppressed_by"] = kept_from[b, :m].copy(), by[b, :int(n[b])].copy()
+        out.append(e)
+    return out
+
+
 class _Completing(object):
-    """`completion` of Net and NetGroup (stage D of the people assembly, include/deepcut_hip.h): state of the object, read by every
-    entry that assembles people.  `_set_completion` / `_get_completion` name the two library entries."""
+    """`completion` and `dedupe` of Net and NetGroup (stages D and E of the people assembly, include/deepcut_hip.h): state of the object,
+    read by every entry that assembles people.  `_set_completion` / `_get_completion` / `_set_dedupe` / `_get_dedupe` name the library
+    entries."""
+
+    @property
+    def dedupe(self):
+        """None (off, the default) or {"max_dist", "min_common", "min_size", "sigma", "absorb"}: with it every assembling entry removes
+        the people who are there twice, on the device behind the assembly and the completion and before the tracker (stage E): people
+        are ranked by the sum of their joint scores, and a person that a better kept person is the same as — the tracker's distance,
+        normalised by the better one's size, <= max_dist over at least min_common joints both hold — is suppressed; with absorb the kept
+        person takes the assigned joints it lacks from the people it suppressed, which puts two fragments of one human back together.
+        Assign None / False, True (DEDUPE_DEFAULTS: PLACEHOLDERS, not tuned on real images) or a dict of some of the five.  A bad value
+        raises DeepcutError naming the field, with or without a device; a sigma whose length is not the net's joints, or min_common above
+        them, is refused by the first assembling call.  `Net.clone()` copies the setting; a NetGroup has one of its own.  The rule is
+        this project's own: the reference stops at the maps."""
+        q, sig = DedupeParams(), np.zeros(32, np.float64)
+        _check(getattr(_lib, self._get_dedupe)(self._h, C.byref(q), sig.ctypes.data_as(C.c_void_p)))
+        if not q.enabled:
+            return None
+        return {"max_dist": float(q.max_dist), "min_common": int(q.min_common), "min_size": float(q.min_size),
+                "sigma": sig[:q.n_sigma].copy() if q.n_sigma else None, "absorb": bool(q.absorb)}
+
+    @dedupe.setter
+    def dedupe(self, dedupe):
+        d = dedupe_params(dedupe)
+        if d is None:
+            _check(getattr(_lib, self._set_dedupe)(self._h, None))
+            return
+        q, _sig = _dedupe_struct(d)
+        _check(getattr(_lib, self._set_dedupe)(self._h, C.byref(q)))
 
     @property
     def completion(self):
@@ -866,8 +991,18 @@ class _Completing(object):
         _check(getattr(_lib, self._set_completion)(self._h, C.byref(q)))
 
     @contextlib.contextmanager
-    def _completing(self, complete):
-        """For the calls that take `complete=`: None leaves the object's `completion` as it is; anything else holds for this call only."""
+    def _completing(self, complete, dedupe=None):
+        """For the calls that take `complete=` and `dedupe=`: None leaves the object's `completion` / `dedupe` as it is; anything else
+        holds for this call only."""
+        if dedupe is not None:
+            before = self.dedupe
+            self.dedupe = dedupe
+            try:
+                with self._completing(complete) as completed:
+                    yield completed
+            finally:
+                self.dedupe = before
+            return
         if complete is None:
             yield self.completion is not None
             return
@@ -999,6 +1134,7 @@ class Net(_Completing):
     """caffe.Net(model_def, model_bin, phase) / caffe.Net(model_def, phase)  (_caffe.cpp:76-96,227-228)."""
 
     _set_completion, _get_completion = "dc_net_set_completion", "dc_net_get_completion"
+    _set_dedupe, _get_dedupe = "dc_net_set_dedupe", "dc_net_get_dedupe"
 
     def __init__(self, model_def, *args, **kw):
         if "_handle" in kw:  # clone()
@@ -1466,7 +1602,7 @@ class Net(_Completing):
         return out
 
     def assemble_people(self, scale=1.0, threshold=0.1, radius=1, max_det=16, edges=None, mean=None, std=None, max_cost=32.0,
-                        seed_threshold=0.5, max_people=32, min_joints=1, joint_order=None, return_cost=False, complete=None):
+                        seed_threshold=0.5, max_people=32, min_joints=1, joint_order=None, return_cost=False, complete=None, dedupe=None):
         """The people of every image of the last forward (dc_net_assemble_people): part candidates, pair costs from `next_pred` and a
         greedy assembly, all on the device; only the results come back.  edges: [E, 2] 0-based (joint, next joint) of the regression
         edges (E = next_pred channels / 2), mean / std: their [E, 2] de-normalisation (deepcut_tools.read_pair_stats), None = 0 / 1.
@@ -1477,32 +1613,35 @@ class Net(_Completing):
         index in the joint's candidate list or -1}, plus "cost": float64 [J, J, max_det, max_det] with return_cost.
         complete: None = the net's `completion` as it stands; True, a dict or False = that setting for this call only.  When completion
         runs, missing joints are filled on the device (stage D, include/deepcut_hip.h): such a joint has cand == -2 and the dict gains
-        "filled": bool [m, J]."""
+        "filled": bool [m, J].
+        dedupe: likewise for the net's `dedupe` (stage E): None = as it stands; True, a dict or False = for this call only.  When it runs,
+        people who are there twice are suppressed on the device behind the completion: m shrinks, the kept people keep their order."""
         return self._assemble_people(None, scale, threshold, radius, max_det, edges, mean, std, max_cost, seed_threshold, max_people, min_joints,
-                                     joint_order, return_cost, complete=complete)
+                                     joint_order, return_cost, complete=complete, dedupe=dedupe)
 
     def track_people(self, tracker, scale=1.0, threshold=0.1, radius=1, max_det=16, edges=None, mean=None, std=None, max_cost=32.0,
-                     seed_threshold=0.5, max_people=32, min_joints=1, joint_order=None, return_cost=False, slot_of=None, complete=None):
+                     seed_threshold=0.5, max_people=32, min_joints=1, joint_order=None, return_cost=False, slot_of=None, complete=None,
+                     dedupe=None):
         """`assemble_people` with the identities of a `caffe.Tracker` (dc_net_track_people): the tracker's update runs on the device
         behind the assembly, on the people where the assembly left them — image b updates slot b.  The arguments and the result are
         `assemble_people`'s, unchanged, with two more entries per image: "ids": int64 [m] (the same person keeps their id from frame
         to frame; -1 = no track place was free) and "place": int32 [m] (the track place, an index into `tracker.state()`).
         slot_of: [batch] ints, the slot every image updates (dc_net_track_people_slots; `Tracker.update`): a batch forward of k
         consecutive frames of one video is tracked with slot_of = [slot] * k.
-        complete: as `assemble_people`; the tracker then receives the completed people."""
+        complete, dedupe: as `assemble_people`; the tracker then receives the completed people / only the people that were kept."""
         _tracker_handle(tracker)
         return self._assemble_people(tracker, scale, threshold, radius, max_det, edges, mean, std, max_cost, seed_threshold, max_people,
-                                     min_joints, joint_order, return_cost, slot_of, complete)
+                                     min_joints, joint_order, return_cost, slot_of, complete, dedupe)
 
     def track_frames_async(self, frames_or_images, tracker=None, scale=1.0, slot_of=None, assemble_scale=None, threshold=0.1, radius=1,
                            max_det=16, edges=None, mean=None, std=None, max_cost=32.0, seed_threshold=0.5, max_people=32, min_joints=1,
-                           joint_order=None, complete=None):
+                           joint_order=None, complete=None, dedupe=None):
         """The whole video chain without a host wait (dc_net_track_frames_async): upload, pre-processing, forward, assembly, the
         tracker's update and the downloads are enqueued on the net's own stream and the call returns.  frames_or_images: a `Frame`, a
         list of `Frame`s of one size, or uint8 [n,H,W,3] / [H,W,3] BGR; they must stay untouched until the result is collected.
         tracker: a `caffe.Tracker`, or None for people without ids; slot_of as `track_people`.  scale: the pre-processing's;
-        assemble_scale: the assembly's (None: the same).  The other arguments are `assemble_people`'s, `complete` included (what holds
-        when the call is made is what the request runs with).
+        assemble_scale: the assembly's (None: the same).  The other arguments are `assemble_people`'s, `complete` and `dedupe` included
+        (what holds when the call is made is what the request runs with).
         -> a `TrackedFrames`: `result()` synchronises the net and returns what `forward_images` + `track_people` return, bit for bit.
         A second call on a busy net queues behind the first; to overlap calls use clones (`deepcut_tools.VideoPipeline`): the tracker
         keeps the updates in call order."""
@@ -1546,7 +1685,7 @@ class Net(_Completing):
             if tracker is not None:
                 ids, place = out((n, p), np.int64), out((n, p), np.int32)
         ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        with self._completing(complete) as completed:
+        with self._completing(complete, dedupe) as completed:
             _check(_lib.dc_net_track_frames_async(self._h, None if tracker is None else tracker._h, arr, ptr(x), n, h, w, float(scale),
                                                   1 if dev else 0, None if slot_of is None else ptr(_slot_map(slot_of, n)), C.byref(q),
                                                   e.shape[0], ptr(e), ptr(m), ptr(s), ptr(order), ptr(count), ptr(people), ptr(cand),
@@ -1554,7 +1693,7 @@ class Net(_Completing):
         return TrackedFrames(self, tracker is not None, count, people, cand, ids, place, keep + (tracker,), pool, completed)
 
     def _assemble_people(self, tracker, scale, threshold, radius, max_det, edges, mean, std, max_cost, seed_threshold, max_people, min_joints,
-                         joint_order, return_cost, slot_of=None, complete=None):
+                         joint_order, return_cost, slot_of=None, complete=None, dedupe=None):
         if edges is None:
             raise ValueError("assemble_people needs the regression edges (deepcut_tools.read_pair_stats)")
         n, j = self.blobs["prob"].shape[:2]
@@ -1567,7 +1706,7 @@ class Net(_Completing):
         cand = np.zeros((n, p, j), np.int32)
         cost = np.zeros((n, j, j, md, md), np.float64) if return_cost else None
         ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        with self._completing(complete) as completed:
+        with self._completing(complete, dedupe) as completed:
             if tracker is None:
                 _check(_lib.dc_net_assemble_people(self._h, C.byref(q), e.shape[0], ptr(e), ptr(m), ptr(s), ptr(order), ptr(count), ptr(people),
                                                    ptr(cand), ptr(cost)))
@@ -1682,6 +1821,7 @@ class NetGroup(_Completing):
 
     STAT_NAMES = ("merges", "graph_instantiations", "autotune_runs", "plan_hits", "launches", "multi_launches", "lanes")
     _set_completion, _get_completion = "dc_group_set_completion", "dc_group_get_completion"
+    _set_dedupe, _get_dedupe = "dc_group_set_dedupe", "dc_group_get_dedupe"
 
     def __init__(self, nets, lanes=None):
         """lanes: None / 0 = automatic (the members are dealt largest-with-smallest to lanes that run concurrently on their own
@@ -2024,27 +2164,27 @@ class NetGroup(_Completing):
 
     def assemble_people(self, scales, base=0, threshold=0.1, radius=1, max_det=16, edges=None, mean=None, std=None, max_cost=32.0,
                         seed_threshold=0.5, max_people=32, min_joints=1, joint_order=None, return_cost=False, mirror=None, image_width=None,
-                        joint_mirror=None, complete=None):
+                        joint_mirror=None, complete=None, dedupe=None):
         """Net.assemble_people on the fused maps of a pyramid (dc_group_assemble_people): the three maps of the members' last forwards
         are fused on member `base`'s grid (`fuse_maps`), then the candidates, the pair costs and the greedy assembly run on them at
         scales[base], all on the device with no host round trip in between.  The other arguments and the result are Net.assemble_people's.
         mirror / image_width / joint_mirror: as `fuse_maps`, with `edges` as the regression edges (dc_group_assemble_people_mirrored).
-        complete: as `Net.assemble_people`, on the group's own `completion` (the members' settings are not read)."""
+        complete, dedupe: as `Net.assemble_people`, on the group's own `completion` / `dedupe` (the members' settings are not read)."""
         return self._assemble_people(None, scales, base, threshold, radius, max_det, edges, mean, std, max_cost, seed_threshold, max_people,
-                                     min_joints, joint_order, return_cost, mirror, image_width, joint_mirror, complete=complete)
+                                     min_joints, joint_order, return_cost, mirror, image_width, joint_mirror, complete=complete, dedupe=dedupe)
 
     def track_people(self, tracker, scales, base=0, threshold=0.1, radius=1, max_det=16, edges=None, mean=None, std=None, max_cost=32.0,
                      seed_threshold=0.5, max_people=32, min_joints=1, joint_order=None, return_cost=False, mirror=None, image_width=None,
-                     joint_mirror=None, slot_of=None, complete=None):
+                     joint_mirror=None, slot_of=None, complete=None, dedupe=None):
         """`assemble_people` with the identities of a `caffe.Tracker` (dc_group_track_people), plain or mirrored: the tracker's update
         runs on the device behind the assembly of the fused maps.  The arguments and the result are `assemble_people`'s, unchanged,
         plus "ids" and "place" per image as `Net.track_people` gives them.  slot_of: as `Net.track_people` (dc_group_track_people_slots)."""
         _tracker_handle(tracker)
         return self._assemble_people(tracker, scales, base, threshold, radius, max_det, edges, mean, std, max_cost, seed_threshold, max_people,
-                                     min_joints, joint_order, return_cost, mirror, image_width, joint_mirror, slot_of, complete)
+                                     min_joints, joint_order, return_cost, mirror, image_width, joint_mirror, slot_of, complete, dedupe)
 
     def _assemble_people(self, tracker, scales, base, threshold, radius, max_det, edges, mean, std, max_cost, seed_threshold, max_people,
-                         min_joints, joint_order, return_cost, mirror, image_width, joint_mirror, slot_of=None, complete=None):
+                         min_joints, joint_order, return_cost, mirror, image_width, joint_mirror, slot_of=None, complete=None, dedupe=None):
         if edges is None:
             raise ValueError("assemble_people needs the regression edges (deepcut_tools.read_pair_stats)")
         sc, base = self._scales(scales, base)
@@ -2060,7 +2200,7 @@ class NetGroup(_Completing):
         cost = np.zeros((n, j, j, md, md), np.float64) if return_cost else None
         ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
         fm, _keep = self._mirror(mirror, image_width, joint_mirror, e)
-        with self._completing(complete) as completed:
+        with self._completing(complete, dedupe) as completed:
             if tracker is None:
                 _check(_lib.dc_group_assemble_people_mirrored(self._h, ptr(sc), base, fm, C.byref(q), e.shape[0], ptr(e), ptr(m), ptr(s),
                                                               ptr(order), ptr(count), ptr(people), ptr(cand), ptr(cost)))

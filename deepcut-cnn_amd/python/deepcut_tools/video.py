@@ -13,12 +13,13 @@ import collections
 class VideoPipeline(object):
     MAX_DEPTH = 4  # a HIP process has four hardware queues: a fifth executor only shares one
 
-    def __init__(self, net, tracker=None, depth=3, batch=1, stats=None, scale=1.0, choose_streams=True, complete=None, **assembly):
+    def __init__(self, net, tracker=None, depth=3, batch=1, stats=None, scale=1.0, choose_streams=True, complete=None, dedupe=None, **assembly):
         """net: a `caffe.Net` with all three maps (or a sparse-pairwise net); tracker: a `caffe.Tracker` or None (people without ids,
         ids come back as None); depth: executors, 1..4; batch: frames per call, 1..64; stats: (edges, mean, std) as
         `deepcut_tools.read_pair_stats` returns them, or a path; scale: the pre-processing's and the assembly's; assembly: what
         `Net.assemble_people` takes (threshold, max_det, max_cost, ...).  complete: as `Net.assemble_people` takes it — None leaves
-        every executor with the net's `completion` (the clones made here copy it), True or a dict is passed with every request."""
+        every executor with the net's `completion` (the clones made here copy it), True or a dict is passed with every request.  dedupe: likewise for the net's `dedupe`
+        (stage E: people who are there twice are suppressed before the tracker sees them)."""
         depth, batch = int(depth), int(batch)
         if not 1 <= depth <= self.MAX_DEPTH:
             raise ValueError("depth must be in [1, %d], got %d" % (self.MAX_DEPTH, depth))
@@ -35,6 +36,8 @@ class VideoPipeline(object):
         self.tracker, self.batch, self.scale, self.assembly = tracker, batch, float(scale), dict(assembly)
         if complete is not None:
             self.assembly["complete"] = complete
+        if dedupe is not None:
+            self.assembly["dedupe"] = dedupe
         self._choose_streams = bool(choose_streams)
         self.stream_choice = None            # what caffe.choose_streams measured, once it ran
         self._held = []                      # frames of the batch being gathered: (frame, tag, slot, shape key)

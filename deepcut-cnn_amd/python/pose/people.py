@@ -64,7 +64,8 @@ def estimate_people(image, model_def, model_bin, stats, scale=1.0, net=None, sca
     outputs computed, then `Net.assemble_people(scale=scale, edges=..., mean=..., std=..., **assembly)`; `assembly` takes its other
     arguments (threshold, radius, max_det, max_cost, seed_threshold, max_people, min_joints, joint_order: the defaults of max_cost
     and seed_threshold are placeholders, not tuned on real images) and `complete` (None, True or a dict: joints the assembly missed are
-    filled on the device from the pairwise predictions, `Net.completion`; its defaults are placeholders too).
+    filled on the device from the pairwise predictions, `Net.completion`; its defaults are placeholders too) and `dedupe` (None, True or
+    a dict: people who are there twice are suppressed on the device behind the completion, `Net.dedupe`; placeholders likewise).
     -> float64 [m, J, 3]: x, y, score per person and joint in image coordinates, (0, 0, 0) where a person has no such joint.
     A caller-supplied `net` keeps its output selection: one that leaves `next_pred` out is refused, not changed.
     scales: a list of scales runs the image pyramid instead — the net and clones of it kept with it, as `estimate_pose` uses them, in
@@ -91,7 +92,7 @@ def track_people(frames, model_def, model_bin, stats, tracker=None, depth=1, bat
     """`estimate_people` over the frames of a video, with identities: a generator over an iterable of images (HxWx3 BGR uint8) or
     `caffe.Frame`s that yields, per frame, (people float64 [m, J, 3], ids int64 [m]) — the same person keeps their id from frame to
     frame, -1 marks a person no track place was free for.  kw: what `estimate_people` takes (scale / scales / base / flip / joint_mirror /
-    sparse / net / the assembly arguments, `complete` among them: the tracker then receives the completed people); every frame runs as `estimate_people` runs it, except that the last call is
+    sparse / net / the assembly arguments, `complete` and `dedupe` among them: the tracker then receives the completed people, and only those that were kept); every frame runs as `estimate_people` runs it, except that the last call is
     `Net.track_people` / `NetGroup.track_people`: the association runs on the device behind the assembly, the people it returns are
     `estimate_people`'s.  tracker: a `caffe.Tracker` of one slot or more (slot 0 is used); None makes one with the defaults, which are
     PLACEHOLDERS, not tuned on real video, and with the matching rule `assign` ("greedy" or "optimal", as `caffe.Tracker` takes it; a

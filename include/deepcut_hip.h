@@ -373,6 +373,8 @@ int dc_net_decode_pairwise(dc_net* net, double scale, int ndet, const int* detec
  *     with fewer than min_joints joints are dropped, the others keep their order.
  *  D. (only with dc_net_set_completion enabled; off by default) completion: joints a person lacks are looked for in the score map
  *     around the position its held joints predict; a joint filled so has cand = -2.  The rule is stated at dc_complete_params below.
+ *  E. (only with dc_net_set_dedupe enabled; off by default) dedupe: a person that a better-scored kept person is "the same" as, by the
+ *     tracker's distance, is suppressed, and n_people shrinks.  The rule is stated at dc_dedupe_params below.
  * Outputs: n_people[b]; people[((b*P + q)*J + j)*3 + {0,1,2}] = x, y, score of person q's candidate of joint j, (0, 0, 0) where it has
  *          none and for q >= n_people[b]; cand[(b*P + q)*J + j] = that candidate's index in joint j's list or -1 (may be NULL); cost (may
  *          be NULL: diagnostics and tests) = the whole tensor [n][J][J][max_det][max_det].  P = max_people.
@@ -957,6 +959,77 @@ int dc_net_set_completion(dc_net* net, const dc_complete_params* p /* NULL: off 
 int dc_net_get_completion(dc_net* net, dc_complete_params* out);
 int dc_group_set_completion(dc_group* group, const dc_complete_params* p /* NULL: off */);
 int dc_group_get_completion(dc_group* group, dc_complete_params* out);
+
+/* ---- people, stage E: a person who is there twice is suppressed on the device (opt-in) -----------------------------------------------
+ * NO REFERENCE COUNTERPART, PARITY UNPINNED BY THE REFERENCE: like stages B to D and the tracker this rule is this project's own (the
+ * reference repository stops at the maps); tests/dedupe_ref.py restates it in float64 loops.
+ *
+ * The assembly produces the same human twice in three ways: a link that costs more than max_cost lets the rest of a body seed a second
+ * person (A holds joints 0..6, B holds 7..13); stage D then fills what each fragment lacks — "two people may fill the same joint from
+ * the same cell" — so both come back as full skeletons on top of each other; and a small NMS radius or a fused pyramid gives two
+ * candidates a cell apart, each of which becomes a person.  Every duplicate is a track of its own in a tracker and a box of its own for
+ * a top-down forward.  With dedupe enabled every entry that assembles people runs one more launch behind stage D (behind stage C when
+ * completion is off), before the tracker's launch and before the downloads: the tracker and the caller receive the people it kept.
+ * The setting is state of the net or the group exactly as completion is, and covers the same entries.  Not enabled (the default): no
+ * launch is added and every result keeps its bits.
+ *
+ * Inputs, per image b: n = n_people[b]; people[q][j] = (x, y, score) and cand[q][j] as the previous stage left them; the parameters
+ * below.  All arithmetic in double; sums run over the joints ascending.
+ *  1. Held, score, size.  Joint j of q is HELD when its score > 0 (the tracker's definition: a NaN or negative score is not held; a
+ *     joint stage D filled, cand == -2, is).  S_q = the sum of the scores of q's held joints.  s_q = max(min_size, max(x extent, y
+ *     extent) over q's held joints): step 1 of the tracker rule with this stage's own min_size, computed as the tracker computes it —
+ *     the extents are max - min with fmin / fmax, which pass over a NaN, and count only when the x extent is >= 0, i.e. when some held
+ *     joint has an x that is not a NaN.
+ *  2. Rank.  q ranks before q' when S_q > S_q', or when the two are equal and q < q'.  (S is never a NaN; an infinite score ranks first.)
+ *  3. Distance.  For A ranked before B, over the n_c joints both hold:
+ *         D(A, B) = (sum_j ((A_x - B_x)^2 + (A_y - B_y)^2) / (s_A^2 * sigma_j^2)) / n_c
+ *     — the tracker's step 3 with pred = pose.  A and B are SIMILAR when n_c >= min_common and `D <= max_dist` is true: a NaN distance is
+ *     never similar, D == max_dist is.
+ *  4. Sweep, in rank order.  A person is SUPPRESSED by the first kept person ranked before it that it is similar to; otherwise it is
+ *     KEPT.  A suppressed person suppresses nobody.
+ *  5. Absorb (only with absorb = 1).  For a kept A and a joint j with cand_A[j] < 0 (missing or filled), the donors are the people
+ *     suppressed by A whose cand[j] >= 0, i.e. assigned by stage C.  If there are any, A's joint j becomes the first-ranked donor's
+ *     (x, y, score) and cand.  Steps 1 to 4 read the input only: absorbed joints influence no decision.  Every candidate still belongs
+ *     to at most one person, because a donor does not survive.  This turns the two fragments above back into one person made of
+ *     stage C's joints only.
+ *  6. Compaction.  The kept people stay in ascending input order (stage C's "the others keep their order"); n_people[b] is their count;
+ *     entries beyond it are (0, 0, 0) with cand = -1.  The stage writes to buffers of its own and reads its input while it runs.
+ * Stage E leaves min_joints and stage D's results for the survivors as they are.  Deterministic: no step depends on thread timing.
+ *
+ * dc_net_set_dedupe / dc_group_set_dedupe: p == NULL or p->enabled == 0 turns the stage off (the other fields are then not read and
+ * read back as 0, sigma as n_sigma = 0).  Host only, no device needed.  DC_EINVAL naming the field for max_dist not finite or < 0,
+ * min_common < 1, min_size not finite or <= 0, n_sigma outside [0, 32], sigma NULL with n_sigma != 0, a sigma value not
+ * finite or <= 0, absorb other than 0 or 1.  sigma is copied (at most 32 entries); it need not outlive the call.  What only a call
+ * that knows the joints can refuse is DC_ESHAPE at the first assembling call: an n_sigma that is neither 0 nor the net's J, and
+ * min_common > J.  dc_*_get_dedupe: what was stored; out->sigma is not written — pass sigma_out [32] (may be NULL) for the values.
+ * dc_net_clone copies the net's setting at clone time; a group has a setting of its own and does not read its members'.
+ * THE DEFAULTS THE PYTHON LAYER CHOOSES ARE PLACEHOLDERS, NOT TUNED ON REAL IMAGES: override them.
+ *
+ * dc_dedupe_people: the stage alone, on host arrays, synchronous — this is how top-down poses of dc_net_forward_boxes (overlapping
+ * detector boxes give the same person twice) are cleaned before dc_tracker_update.  people[nb][P][J][3] and cand[nb][P][J] (entries of
+ * q >= n_people[b] are not read).  cand == NULL: a joint counts as assigned exactly when it is held (candidate 0 where held, -1
+ * elsewhere, which is also what cand_out then holds), so only missing joints are absorbed.  Outputs: n_out[nb], people_out[nb][P][J][3],
+ * cand_out[nb][P][J] (may be NULL), kept_from[nb][P] = the input index of output person o, -1 for o >= n_out[b] (may be NULL),
+ * suppressed_by[nb][P] = the input index of the kept person that suppressed q, -1 for a kept q and for q >= n_people[b] (may be NULL).
+ * p->enabled is not read.  Errors, before any device work: DC_EINVAL for a NULL p, n_people, people, n_out or people_out, whatever
+ * the setters refuse, nb < 1, P outside [1, 256], J outside [1, 32], an n_people[b] outside [0, P]; DC_ESHAPE for n_sigma neither 0
+ * nor J and for min_common > J.  Then DC_ENOCPU in CPU mode (there is no CPU path).                                                 */
+typedef struct dc_dedupe_params {
+  int    enabled;        /* 0: off */
+  double max_dist;       /* A and B are the same person when D(A, B) <= max_dist; finite, >= 0 */
+  int    min_common;     /* joints both must hold to be compared, >= 1 */
+  double min_size;       /* lower bound of the size s_A, image pixels; finite, > 0 */
+  const double* sigma;   /* [n_sigma] per-joint tolerance, each finite and > 0; NULL with n_sigma = 0 = all 1.0 */
+  int    n_sigma;        /* 0 or the number of joints */
+  int    absorb;         /* 1: a kept person takes the assigned joints it lacks from the people it suppressed */
+} dc_dedupe_params;
+int dc_net_set_dedupe(dc_net* net, const dc_dedupe_params* p /* NULL: off */);
+int dc_net_get_dedupe(dc_net* net, dc_dedupe_params* out, double* sigma_out /* [32], may be NULL */);
+int dc_group_set_dedupe(dc_group* group, const dc_dedupe_params* p /* NULL: off */);
+int dc_group_get_dedupe(dc_group* group, dc_dedupe_params* out, double* sigma_out /* [32], may be NULL */);
+int dc_dedupe_people(const dc_dedupe_params* p, int nb, int P, int J, const int* n_people, const double* people,
+                     const int* cand /* may be NULL: assigned == held */, int* n_out, double* people_out, int* cand_out /* may be NULL */,
+                     int* kept_from /* [nb][P], may be NULL */, int* suppressed_by /* [nb][P] input index or -1, may be NULL */);
 
 /* ---- in-process multi-GPU forward (SURVEY 8(b)'s dc_forward_batch) -------------------------------------------------------
  * A communicator over `nexec` executors: executor k runs on devices[k] (NULL: k modulo the visible devices) on a host thread of its
