@@ -971,6 +971,30 @@ int dc_tracker_get_option(dc_tracker* tracker, int key, int* value) {
   REQUIRE(value);
   return guard([&] { *value = TR(tracker)->get_option(key); });
 }
+int dc_tracker_set_smoothing(dc_tracker* tracker, const dc_track_smooth_params* p) {
+  REQUIRE(tracker);
+  return guard([&] { TR(tracker)->set_smoothing(p); });
+}
+int dc_tracker_get_smoothing(dc_tracker* tracker, dc_track_smooth_params* out) {
+  REQUIRE(tracker);
+  REQUIRE(out);
+  return guard([&] {
+    const Tracker::SmoothParams& q = TR(tracker)->smooth;
+    *out = dc_track_smooth_params{q.enabled, q.min_cutoff, q.beta, q.d_cutoff, q.max_hold};
+  });
+}
+int dc_tracker_update_smoothed(dc_tracker* tracker, int nb, int P, const int* slot_of, const int* n_people, const double* people,
+                               long long* ids, int* place, double* dist, double* smooth, int* src) {
+  REQUIRE(tracker);
+  REQUIRE(n_people);
+  REQUIRE(people);
+  REQUIRE(ids);
+  return guard([&] { TR(tracker)->update(nb, P, slot_of, n_people, people, ids, place, dist, smooth, src, true); });
+}
+int dc_tracker_smooth_state(dc_tracker* tracker, int slot, double* poses, int* gap) {
+  REQUIRE(tracker);
+  return guard([&] { TR(tracker)->smooth_state(slot, poses, gap); });
+}
 int dc_net_track_people(dc_net* net, dc_tracker* tracker, const dc_assemble_params* p, int n_edges, const int* edges, const double* mean,
                         const double* stdev, const int* joint_order, int* n_people, double* people, int* cand, double* cost,
                         long long* ids, int* place) {

@@ -474,8 +474,25 @@ inline void track_slot_map_set(TrackSlotMap& m, int b, int slot) { m.w[b >> 2] |
 // n_people[b] (clamped to [0, P]) and people [NB][P][J][3] from device memory, writes the state back in place, dist[b * T *
 // kPeopleMaxPeople + i * P + q] (scratch the caller keeps: the matching reads it back), ids [NB][P] and place [NB][P].  sig2 [J] =
 // sigma_j^2.  NB <= kTrackMaxImages, every map[b] in [0, S).
+// sm (null: off, the instances and the work of a tracker without smoothing): step 8 of the rule behind step 7 of every image, on the
+// filters filt [S][T][J] (all zero = every filter empty) -> smooth [NB][P][J][3], src [NB][P][J] (0 nothing, 1 observed, 2 bridged) and,
+// where cand_in [NB][P][J] is given, cand_out = cand_in with -3 at the bridged joints (every entry written; cand_in is only read).
+struct TrackFilter {  // of one track place and joint, 48 bytes
+  double fx, fy, dx, dy, fs;
+  int gap, n;  // n: 0 holds nothing, 1 one observation, 2 running
+};
+struct TrackSmooth {
+  double min_cutoff, beta, d_cutoff;
+  int max_hold;
+  TrackFilter* filt;
+  double* smooth;
+  int* src;
+  const int* cand_in;
+  int* cand_out;
+};
 int launch_track(int S, int NB, int P, const TrackParams& p, const double* sig2, unsigned char* state, size_t slot_stride, double* dist,
-                 const int* n_people, const double* people, long long* ids, int* place, const TrackSlotMap& map, void* stream);
+                 const int* n_people, const double* people, long long* ids, int* place, const TrackSlotMap& map, void* stream,
+                 const TrackSmooth* sm = nullptr);
 
 // The pairwise head at a list of cells (sparse_head.hip; the rule: include/deepcut_hip.h, dc_net_pairwise_at).  x3 / x5: the NHWC inputs
 // of the head's 1x1 skip convolution ([NB][H][W], pitch cp3, K3 channels) and of its stride-2 3x3 deconvolution ([NB][h5][w5], pitch cp5,

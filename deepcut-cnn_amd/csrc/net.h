@@ -26,6 +26,7 @@
 struct dc_frame;  // include/deepcut_hip.h: one video frame (planes, pitches, format, matrix, range)
 struct dc_complete_params;  // include/deepcut_hip.h: stage D of the people assembly
 struct dc_dedupe_params;    // include/deepcut_hip.h: stage E of the people assembly
+struct dc_track_smooth_params;  // include/deepcut_hip.h: step 8 of the tracker's rule
 
 namespace dc {
 
@@ -292,6 +293,10 @@ struct DedupeParams {
 void dedupe_people(const dc_dedupe_params* params, int nb, int P, int J, const int* n_people, const double* people, const int* cand,
                    int* n_out, double* people_out, int* cand_out, int* kept_from, int* suppressed_by);
 
+// What the assembly calls behind its last stage with the device arrays it left (n_people, people, cand): the tracker's launch.  True:
+// the hook has delivered `people` and `cand` to the host arrays itself (a tracker with smoothing on), and the assembly downloads neither.
+using AfterPeople = std::function<bool(const int* d_np, const double* d_ppl, const int* d_cand)>;
+
 struct Net {
   std::string name;
   int phase = 1;
@@ -494,11 +499,11 @@ struct Net {
                             int n_edges, const double* mean, const double* stdev, const std::function<void*(size_t)>& scratch, void* stream,
                             int* n_people, double* people, int* cand, double* cost,
                             const std::function<void(const int*, const double*)>& between = nullptr,
-                            const std::function<void(const int*, const double*)>& after = nullptr, AssembleTables* keep = nullptr,
+                            const AfterPeople& after = nullptr, AssembleTables* keep = nullptr,
                             bool wait = true);
   AssembleTables asm_tables_;
   void assemble_last(const AssembleParams& q_in, const std::vector<int>& table, int n_edges, const double* mean, const double* stdev,
-                     int* n_people, double* people, int* cand, double* cost, const std::function<void(const int*, const double*)>& after,
+                     int* n_people, double* people, int* cand, double* cost, const AfterPeople& after,
                      bool wait);
   // DC_OPT_SPARSE_PAIRWISE (sparse_pairwise.cpp)
   struct PairHead {
@@ -543,7 +548,9 @@ struct Net {
 //   slot blocks (kernels.h TrackSlot) | sigma^2 [J]
 // and the per-image scratch in a second one, sized for the largest image count of a call so far (at least `slots`):
 //   distances [cap][T][256] | staging of host poses: n_people [cap], people [cap][256][J][3] | outputs: ids [cap][256], place [cap][256]
-// It grows on demand; the contents do not survive that and need not: every call fills what it reads.
+//   and, once smoothing has been on: step 8's outputs smooth [cap][256][J][3], src [cap][256][J], cand [cap][256][J]
+// It grows on demand; the contents do not survive that and need not: every call fills what it reads.  The filters of step 8 are a third
+// allocation, [slots][T][J] TrackFilter, made at the first update with smoothing on.
 // Order: the tracker holds an event.  Every enqueue of an update — under the runtime lock, which is held for the enqueue only — makes its
 // stream wait for the event of the update enqueued before it (hipStreamWaitEvent: no host wait) and records the event again behind its
 // own launch and the copies out of the shared scratch.  Updates therefore apply in the order of the host calls that enqueued them,
@@ -560,6 +567,24 @@ struct Tracker {
   unsigned char* img_dev = nullptr;  // the per-image scratch ...
   int img_cap = 0;                   // ... and how many images it holds
   size_t off_dist = 0, off_np = 0, off_ppl = 0, off_ids = 0, off_place = 0;
+  // step 8 (dc_tracker_set_smoothing).  The filters [slots][T][J] (kernels.h TrackFilter) are an allocation of their own, made at the
+  // first update with smoothing on and zeroed there and at the first update after smoothing went from off to on (filt_clear).  The
+  // scratch then also holds the outputs smooth [cap][256][J][3], src and cand [cap][256][J] (img_smooth), which the enqueue downloads
+  // BEFORE it records the event: the next update's launch waits for that event, so it cannot overwrite what has not been copied out.
+  struct SmoothParams {
+    int enabled = 0;
+    double min_cutoff = 0.0, beta = 0.0, d_cutoff = 0.0;
+    int max_hold = 0;
+  } smooth;
+  unsigned char* filt_dev = nullptr;
+  bool filt_clear = false, img_smooth = false;
+  size_t off_smooth = 0, off_src = 0, off_cand = 0;
+  struct SmoothOut {  // where an enqueue delivers step 8 (host arrays, any may be null); d_cand: the assembly's, on the device, or null
+    double* people = nullptr;
+    int* src = nullptr;
+    const int* d_cand = nullptr;
+    int* cand = nullptr;
+  };
   // every argument error is DC_EINVAL naming the parameter; no device is needed
   static Tracker* create(int slots, int max_tracks, int n_joints, const double* sigma, int max_misses, int min_common, double max_dist,
                          double min_size, int motion);
@@ -577,8 +602,18 @@ struct Tracker {
   void prepare(int on_device, int nb, void* stream);
   // ... and, after prepare, still under the lock: `stream` waits for the update before, then the launch on d_np / d_ppl (slot_of checked,
   // or null) and the downloads of ids / place / dist (any null), then the event is recorded.  No host wait.
-  void enqueue(int nb, int P, const int* slot_of, const int* d_np, const double* d_ppl, long long* ids, int* place, double* dist, void* stream);
-  void update(int nb, int P, const int* slot_of, const int* n_people, const double* people, long long* ids, int* place, double* dist);
+  // With smoothing on step 8 runs in the same launch, and `so` (may be null) says where its results go.
+  void enqueue(int nb, int P, const int* slot_of, const int* d_np, const double* d_ppl, long long* ids, int* place, double* dist, void* stream,
+               const SmoothOut* so = nullptr);
+  void update(int nb, int P, const int* slot_of, const int* n_people, const double* people, long long* ids, int* place, double* dist,
+              double* smooth_out = nullptr, int* src = nullptr, bool smoothed = false);
+  // host only, ordered like set_option; null: off.  Off -> on starts with empty filters, a change while on keeps them
+  void set_smoothing(const dc_track_smooth_params* p);
+  void smooth_state(int slot, double* poses, int* gap);
+  // for the chained entries' `after` hook: enqueue, and with smoothing on deliver people / cand from step 8 -> true (the caller then
+  // downloads neither itself)
+  bool enqueue_chained(int nb, int P, const int* slot_of, const int* d_np, const double* d_ppl, const int* d_cand, long long* ids, int* place,
+                       double* people, int* cand, void* stream);
   void reset(int slot);  // -1: all
   // DC_TRACK_OPT_*: host only (no device needed); set waits for the last update enqueued, then stores: later updates use the value
   void set_option(int key, int value);

@@ -1175,13 +1175,13 @@ void NetGroup::assemble_people(const double* scales, int base, const Net::Assemb
   const FusedMaps fm = fuse(scales, base, use, mean, stdev, s, mp);
   // the tracker's launch behind the assembly's, as in Net::assemble_people: the runtime lock from there until the stream has been waited for
   std::unique_lock<std::recursive_mutex> order(runtime_mu(), std::defer_lock);
-  std::function<void(const int*, const double*)> after;
+  AfterPeople after;
   if (tracker)
-    after = [&](const int* d_np, const double* d_ppl) {
+    after = [&](const int* d_np, const double* d_ppl, const int* d_cand) {
       order.lock();
       tracker->prepare(nets[0]->device, NB, s);
       tracker->wait_done();
-      tracker->enqueue(NB, q.max_people, slot_of, d_np, d_ppl, ids, place, nullptr, s);
+      return tracker->enqueue_chained(NB, q.max_people, slot_of, d_np, d_ppl, d_cand, ids, place, people, cand, s);
     };
   Net::assemble_maps(fm.map[0], fm.map[1], fm.map[2], q, table, n_edges, mean, stdev, [this](size_t bytes) { return people_scratch_.get(bytes); }, s,
                      n_people, people, cand, cost, nullptr, after);

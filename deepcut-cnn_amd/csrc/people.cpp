@@ -270,20 +270,20 @@ void Net::assemble_people(const AssembleParams& q, int n_edges, const int* edges
   const MapRef P = map_ref("prob");
   // the tracker's launch behind stage C: the runtime lock is taken there and kept until assemble_maps has waited for the stream
   std::unique_lock<std::recursive_mutex> order(runtime_mu(), std::defer_lock);
-  std::function<void(const int*, const double*)> after;
+  AfterPeople after;
   if (tracker)
-    after = [&](const int* d_np, const double* d_ppl) {
+    after = [&](const int* d_np, const double* d_ppl, const int* d_cand) {
       order.lock();
       tracker->prepare(device, P.NB, stream);
       tracker->wait_done();
-      tracker->enqueue(P.NB, q.max_people, slot_of, d_np, d_ppl, ids, place, nullptr, stream);
+      return tracker->enqueue_chained(P.NB, q.max_people, slot_of, d_np, d_ppl, d_cand, ids, place, people, cand, stream);
     };
   assemble_last(q, table, n_edges, mean, stdev, n_people, people, cand, cost, after, true);
 }
 
 // the device half of assemble_people / track_frames_async on the maps of the net's last (enqueued) forward
 void Net::assemble_last(const AssembleParams& q_in, const std::vector<int>& table, int n_edges, const double* mean, const double* stdev,
-                        int* n_people, double* people, int* cand, double* cost, const std::function<void(const int*, const double*)>& after,
+                        int* n_people, double* people, int* cand, double* cost, const AfterPeople& after,
                         bool wait) {
   AssembleParams q = q_in;
   q.complete = completion;  // stage D, when the net has it enabled
@@ -319,12 +319,12 @@ void Net::track_frames_async(Tracker* tracker, const dc_frame* frames, const uns
   if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "track_frames_async() in CPU mode");
   prep_images(bgr, n, h, w, scale, is_device, nullptr, false, frames);
   enqueue_plan(stream);
-  std::function<void(const int*, const double*)> after;
+  AfterPeople after;
   if (tracker)
-    after = [&](const int* d_np, const double* d_ppl) {
+    after = [&](const int* d_np, const double* d_ppl, const int* d_cand) {
       RuntimeLock rl;  // for the enqueue only: the tracker's event keeps the order from here on
       tracker->prepare(device, n, stream);
-      tracker->enqueue(n, p.max_people, slot_of, d_np, d_ppl, ids, place, nullptr, stream);
+      return tracker->enqueue_chained(n, p.max_people, slot_of, d_np, d_ppl, d_cand, ids, place, people, cand, stream);
     };
   assemble_last(p, table, n_edges, mean, stdev, n_people, people, cand, nullptr, after, false);
 }
@@ -332,7 +332,7 @@ void Net::track_frames_async(Tracker* tracker, const dc_frame* frames, const uns
 void Net::assemble_maps(const MapRef& P, const MapRef& L, const MapRef& N, const AssembleParams& q, const std::vector<int>& table, int n_edges,
                         const double* mean, const double* stdev, const std::function<void*(size_t)>& scratch, void* stream, int* n_people,
                         double* people, int* cand, double* cost, const std::function<void(const int*, const double*)>& between,
-                        const std::function<void(const int*, const double*)>& after, AssembleTables* keep, bool wait) {
+                        const AfterPeople& after, AssembleTables* keep, bool wait) {
   const int J = P.C;
   if (L.C != 2 * P.C || L.H != P.H || L.W != P.W || L.NB != P.NB || L.es != P.es)
     throw DcError(DC_ESHAPE, "assemble_people: loc_pred must have 2 channels per joint and the score map's size");
@@ -425,10 +425,11 @@ void Net::assemble_maps(const MapRef& P, const MapRef& L, const MapRef& N, const
                          d_ppl, d_cand, d_np_kept, d_ppl_kept, d_cand_kept, nullptr, nullptr, stream));
     d_np = d_np_kept, d_ppl = d_ppl_kept, d_cand = d_cand_kept;
   }
-  if (after) after(d_np, d_ppl);
+  // a tracker with smoothing on delivers people and cand itself, from step 8's outputs (the device copies here stay raw)
+  const bool delivered = after ? after(d_np, d_ppl, d_cand) : false;
   HIPCHECK(hipMemcpyAsync(n_people, d_np, (size_t)NB * sizeof(int), hipMemcpyDeviceToHost, s));
-  HIPCHECK(hipMemcpyAsync(people, d_ppl, (size_t)NB * PP * J * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (cand) HIPCHECK(hipMemcpyAsync(cand, d_cand, (size_t)NB * PP * J * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (!delivered) HIPCHECK(hipMemcpyAsync(people, d_ppl, (size_t)NB * PP * J * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (cand && !delivered) HIPCHECK(hipMemcpyAsync(cand, d_cand, (size_t)NB * PP * J * sizeof(int), hipMemcpyDeviceToHost, s));
   if (cost) HIPCHECK(hipMemcpyAsync(cost, d_cost, (size_t)NB * J * J * MD * MD * sizeof(double), hipMemcpyDeviceToHost, s));
   if (wait) HIPCHECK(hipStreamSynchronize(s));
 }

@@ -57,6 +57,7 @@ Tracker::~Tracker() {
     if (moved) (void)hipSetDevice(before);
   }
   dev_free(img_dev);
+  dev_free(filt_dev);
   dev_free(dev);
 }
 
@@ -92,9 +93,16 @@ void Tracker::prepare(int on_device, int nb, void* stream) {
     done = ev;
     HIPCHECK(hipEventRecord(ev, (hipStream_t)stream));  // the next update, on whichever stream, runs behind the zeroing
   }
-  if (nb > img_cap) {
+  const bool on = smooth.enabled != 0;
+  if (on && (!filt_dev || filt_clear)) {  // the first update with smoothing on, or the first since it went from off to on: empty filters
+    const size_t bytes = (size_t)slots * tp.T * tp.J * sizeof(TrackFilter);
+    if (!filt_dev) dev_alloc((void**)&filt_dev, bytes);
+    dev_zero(filt_dev, bytes, stream);  // set_smoothing waited for the updates before; the launch follows on this stream
+    filt_clear = false;
+  }
+  if (nb > img_cap || (on && !img_smooth)) {
     wait_done();  // nobody reads the old scratch any more
-    const size_t N = (size_t)std::max(nb, slots), T = (size_t)tp.T, J = (size_t)tp.J, PM = (size_t)kPeopleMaxPeople;
+    const size_t N = (size_t)std::max(std::max(nb, img_cap), slots), T = (size_t)tp.T, J = (size_t)tp.J, PM = (size_t)kPeopleMaxPeople;
     size_t at = 0;
     auto take = [&](size_t bytes) {
       const size_t r = at;
@@ -103,16 +111,20 @@ void Tracker::prepare(int on_device, int nb, void* stream) {
     };
     const size_t o_dist = take(N * T * PM * sizeof(double)), o_np = take(N * sizeof(int)), o_ppl = take(N * PM * J * 3 * sizeof(double)),
                  o_ids = take(N * PM * sizeof(long long)), o_place = take(N * PM * sizeof(int));
+    const bool with = on || img_smooth;
+    const size_t o_smooth = with ? take(N * PM * J * 3 * sizeof(double)) : 0, o_src = with ? take(N * PM * J * sizeof(int)) : 0,
+                 o_cand = with ? take(N * PM * J * sizeof(int)) : 0;
     unsigned char* grown = nullptr;
     dev_alloc((void**)&grown, at);
     dev_free(img_dev);
     img_dev = grown, img_cap = (int)N;
     off_dist = o_dist, off_np = o_np, off_ppl = o_ppl, off_ids = o_ids, off_place = o_place;
+    off_smooth = o_smooth, off_src = o_src, off_cand = o_cand, img_smooth = with;
   }
 }
 
 void Tracker::enqueue(int nb, int P, const int* slot_of, const int* d_np, const double* d_ppl, long long* ids, int* place, double* dist,
-                      void* stream) {
+                      void* stream, const SmoothOut* so) {
   hipStream_t s = (hipStream_t)stream;
   long long* d_ids = (long long*)(img_dev + off_ids);
   int* d_place = (int*)(img_dev + off_place);
@@ -120,7 +132,22 @@ void Tracker::enqueue(int nb, int P, const int* slot_of, const int* d_np, const 
   TrackSlotMap map{};
   for (int b = 0; b < nb; ++b) track_slot_map_set(map, b, slot_of ? slot_of[b] : b);
   HIPCHECK(hipStreamWaitEvent(s, (hipEvent_t)done, 0));
-  KCHECK(launch_track(slots, nb, P, tp, (const double*)(dev + off_sig), dev, slot_stride, d_dist, d_np, d_ppl, d_ids, d_place, map, stream));
+  TrackSmooth sm{};
+  const bool on = smooth.enabled != 0;
+  if (on) {
+    sm.min_cutoff = smooth.min_cutoff, sm.beta = smooth.beta, sm.d_cutoff = smooth.d_cutoff, sm.max_hold = smooth.max_hold;
+    sm.filt = (TrackFilter*)filt_dev;
+    sm.smooth = (double*)(img_dev + off_smooth), sm.src = (int*)(img_dev + off_src);
+    if (so && so->d_cand) sm.cand_in = so->d_cand, sm.cand_out = (int*)(img_dev + off_cand);
+  }
+  KCHECK(launch_track(slots, nb, P, tp, (const double*)(dev + off_sig), dev, slot_stride, d_dist, d_np, d_ppl, d_ids, d_place, map, stream,
+                      on ? &sm : nullptr));
+  if (on && so) {  // out of the shared scratch, in front of the event: the next update's launch waits for it
+    const size_t e = (size_t)nb * P * tp.J;
+    if (so->people) HIPCHECK(hipMemcpyAsync(so->people, sm.smooth, e * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (so->src) HIPCHECK(hipMemcpyAsync(so->src, sm.src, e * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (so->cand && sm.cand_out) HIPCHECK(hipMemcpyAsync(so->cand, sm.cand_out, e * sizeof(int), hipMemcpyDeviceToHost, s));
+  }
   if (ids) HIPCHECK(hipMemcpyAsync(ids, d_ids, (size_t)nb * P * sizeof(long long), hipMemcpyDeviceToHost, s));
   if (place) HIPCHECK(hipMemcpyAsync(place, d_place, (size_t)nb * P * sizeof(int), hipMemcpyDeviceToHost, s));
   for (int b = 0; dist && b < nb; ++b)
@@ -129,8 +156,23 @@ void Tracker::enqueue(int nb, int P, const int* slot_of, const int* d_np, const 
   HIPCHECK(hipEventRecord((hipEvent_t)done, s));
 }
 
-void Tracker::update(int nb, int P, const int* slot_of, const int* n_people, const double* people, long long* ids, int* place, double* dist) {
+bool Tracker::enqueue_chained(int nb, int P, const int* slot_of, const int* d_np, const double* d_ppl, const int* d_cand, long long* ids,
+                              int* place, double* people, int* cand, void* stream) {
+  if (!smooth.enabled) {
+    enqueue(nb, P, slot_of, d_np, d_ppl, ids, place, nullptr, stream);
+    return false;
+  }
+  SmoothOut so;
+  so.people = people, so.d_cand = cand ? d_cand : nullptr, so.cand = cand;
+  enqueue(nb, P, slot_of, d_np, d_ppl, ids, place, nullptr, stream, &so);
+  return true;
+}
+
+void Tracker::update(int nb, int P, const int* slot_of, const int* n_people, const double* people, long long* ids, int* place, double* dist,
+                     double* smooth_out, int* src, bool smoothed) {
   check_call("tracker_update", nb, P, tp.J, slot_of);
+  if (smoothed && !smooth.enabled)
+    bad("tracker_update_smoothed", "smoothing is off (dc_tracker_set_smoothing): there are no smoothed poses to return");
   for (int b = 0; b < nb; ++b)
     if (n_people[b] < 0 || n_people[b] > P)
       bad("tracker_update", "n_people[" + std::to_string(b) + "] = " + std::to_string(n_people[b]) + " is outside [0, P = " + std::to_string(P) + "]");
@@ -151,7 +193,9 @@ void Tracker::update(int nb, int P, const int* slot_of, const int* n_people, con
     if (n_people[b] > 0)
       HIPCHECK(hipMemcpyAsync(d_ppl + (size_t)b * img, people + (size_t)b * img, (size_t)n_people[b] * tp.J * 3 * sizeof(double),
                               hipMemcpyHostToDevice, s));
-  enqueue(nb, P, slot_of, d_np, d_ppl, ids, place, dist, s);
+  SmoothOut so;
+  so.people = smooth_out, so.src = src;
+  enqueue(nb, P, slot_of, d_np, d_ppl, ids, place, dist, s, &so);
   HIPCHECK(hipStreamSynchronize(s));
 }
 
@@ -164,7 +208,56 @@ void Tracker::reset(int slot) {
   hipStream_t s = util_stream();
   if (slot < 0) HIPCHECK(hipMemsetAsync(dev, 0, (size_t)slots * slot_stride, s));
   else HIPCHECK(hipMemsetAsync(dev + (size_t)slot * slot_stride, 0, slot_stride, s));
+  if (filt_dev) {  // the slot's filters go with its tracks
+    const size_t per = (size_t)tp.T * tp.J * sizeof(TrackFilter);
+    if (slot < 0) HIPCHECK(hipMemsetAsync(filt_dev, 0, (size_t)slots * per, s));
+    else HIPCHECK(hipMemsetAsync(filt_dev + (size_t)slot * per, 0, per, s));
+  }
   HIPCHECK(hipStreamSynchronize(s));
+}
+
+void Tracker::set_smoothing(const dc_track_smooth_params* p) {
+  const std::string who = "tracker_set_smoothing";
+  SmoothParams q;
+  if (p && p->enabled) {
+    if (p->enabled != 1) bad(who, "enabled must be 0 or 1");
+    if (!(std::isfinite(p->min_cutoff) && p->min_cutoff > 0)) bad(who, "min_cutoff must be finite and > 0");
+    if (!(std::isfinite(p->beta) && p->beta >= 0)) bad(who, "beta must be finite and >= 0");
+    if (!(std::isfinite(p->d_cutoff) && p->d_cutoff > 0)) bad(who, "d_cutoff must be finite and > 0");
+    if (p->max_hold < 0 || p->max_hold > 1000) bad(who, "max_hold must be in [0, 1000]");
+    q.enabled = 1, q.min_cutoff = p->min_cutoff, q.beta = p->beta, q.d_cutoff = p->d_cutoff, q.max_hold = p->max_hold;
+  }
+  RuntimeLock rl;  // no update is being enqueued meanwhile
+  if (dev) {
+    DeviceScope on(device);
+    wait_done();
+  }
+  if (q.enabled && !smooth.enabled) filt_clear = true;  // off -> on: the next update starts with empty filters
+  smooth = q;
+}
+
+void Tracker::smooth_state(int slot, double* poses, int* gap) {
+  if (slot < 0 || slot >= slots) bad("tracker_smooth_state", "slot must be in [0, " + std::to_string(slots) + ")");
+  const size_t n = (size_t)tp.T * tp.J;
+  std::vector<TrackFilter> f(n);  // value-initialised: every filter empty
+  if (filt_dev && smooth.enabled && !filt_clear) {
+    RuntimeLock rl;
+    DeviceScope on(device);
+    wait_done();
+    hipStream_t s = util_stream();
+    HIPCHECK(hipMemcpyAsync(f.data(), filt_dev + (size_t)slot * n * sizeof(TrackFilter), n * sizeof(TrackFilter), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+  }
+  for (size_t e = 0; e < n; ++e) {
+    const TrackFilter& g = f[e];
+    const bool has = g.n > 0;
+    if (poses) {
+      poses[e * 3] = has ? g.fx + g.dx * (double)g.gap : 0.0;
+      poses[e * 3 + 1] = has ? g.fy + g.dy * (double)g.gap : 0.0;
+      poses[e * 3 + 2] = has ? g.fs : 0.0;
+    }
+    if (gap) gap[e] = has ? g.gap : -1;
+  }
 }
 
 void Tracker::set_option(int key, int value) {

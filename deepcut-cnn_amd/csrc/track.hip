@@ -140,6 +140,109 @@ __device__ __forceinline__ void match_optimal(int T, int P, int n, double max_di
   }
 }
 
+// Step 8 (include/deepcut_hip.h): the smoothed poses of image b and the slot's filters, behind step 7 by the whole workgroup.  The caller
+// hands over what steps 4-7 left: live / tm / mult (LDS, as of the start of the update: mult = misses + 1), and per thread q < n the
+// place of person q (my_place, -1 = none) and whether the person was born into it.  Items are (person, joint) pairs for 8a / 8c and
+// (place, joint) pairs for 8b, strided over the 256 threads; a (place, joint) filter is touched by exactly one item of one of the two
+// loops — by the person's item when the place was matched or born, by the place's item otherwise — so no barrier stands between them.
+// The filters are read AND written across the images of a launch with the caller's barrier in between: no __restrict__ on them.
+__device__ __forceinline__ void smooth_image(int b, int P, int n, const TrackParams& tp, const TrackSmooth& sm, TrackFilter* filt,
+                                             const double* __restrict__ ppl, const int* live, const int* tm, const int* mult, int my_place,
+                                             bool born) {
+  __shared__ int pplace[kTrackMax];   // per person: its place, + kTrackMax when born into it, -1 = untracked
+  __shared__ double psize[kTrackMax]; // per person: the step-1 size of its pose
+  __shared__ int pkind[kTrackMax];    // per place: 0 = a person's item updates it (8a), 1 = live and unmatched (8b), 2 = free
+  const int t = threadIdx.x, T = tp.T, J = tp.J;
+  const double inf = __builtin_huge_val();
+  constexpr double kTwoPi = 6.283185307179586;
+  if (t < n) {
+    pplace[t] = my_place < 0 ? -1 : my_place + (born ? kTrackMax : 0);
+    double x0 = inf, x1 = -inf, y0 = inf, y1 = -inf;
+    for (int j = 0; j < J; ++j) {
+      const double* p = ppl + ((size_t)t * J + j) * 3;
+      if (p[2] > 0.0) x0 = fmin(x0, p[0]), x1 = fmax(x1, p[0]), y0 = fmin(y0, p[1]), y1 = fmax(y1, p[1]);
+    }
+    double s = tp.min_size;
+    if (x1 >= x0) s = fmax(s, fmax(x1 - x0, y1 - y0));
+    psize[t] = s;
+  }
+  // a place a person was born into is free here (2) and is not touched by the second loop before the person's item has cleared it:
+  // the barrier below is followed by the override
+  if (t < T) pkind[t] = live[t] ? (tm[t] >= 0 ? 0 : (mult[t] > tp.max_misses ? 2 : 1)) : 2;
+  __syncthreads();
+  if (t < n && my_place >= 0 && born) pkind[my_place] = 0;
+  __syncthreads();
+
+  double* out = sm.smooth + (size_t)b * P * J * 3;
+  int* src = sm.src + (size_t)b * P * J;
+  const int* cin = sm.cand_in ? sm.cand_in + (size_t)b * P * J : nullptr;
+  int* cout = sm.cand_in ? sm.cand_out + (size_t)b * P * J : nullptr;
+  for (int e = t; e < P * J; e += 256) {
+    const int q = e / J, j = e - q * J;
+    double ox = 0.0, oy = 0.0, os = 0.0;
+    int sr = 0;
+    if (q < n) {
+      const double px = ppl[(size_t)e * 3], py = ppl[(size_t)e * 3 + 1], ps = ppl[(size_t)e * 3 + 2];
+      const bool held = ps > 0.0;
+      const int pl = pplace[q];
+      if (pl < 0) {  // 8c
+        ox = px, oy = py, os = ps, sr = held ? 1 : 0;
+      } else {  // 8a
+        TrackFilter* f = filt + (size_t)(pl & (kTrackMax - 1)) * J + j;
+        TrackFilter g = *f;
+        if (pl >= kTrackMax) g.n = 0;  // born: cleared first
+        if (held) {
+          if (g.n == 0) {
+            g.fx = px, g.fy = py, g.dx = 0.0, g.dy = 0.0, g.n = 1;
+            ox = px, oy = py;
+          } else if (g.n == 1) {
+            const double dt = (double)(g.gap + 1);
+            g.dx = (px - g.fx) / dt, g.dy = (py - g.fy) / dt;
+            g.fx = px, g.fy = py, g.n = 2;
+            ox = px, oy = py;
+          } else {
+            const double dt = (double)(g.gap + 1);
+            const double qx = g.fx + g.dx * dt, qy = g.fy + g.dy * dt;
+            const double ex = px - qx, ey = py - qy;
+            const double fc = sm.min_cutoff + sm.beta * ((fabs(ex) + fabs(ey)) / psize[q]);
+            const double ra = (kTwoPi * fc) * dt, rb = (kTwoPi * sm.d_cutoff) * dt;
+            const double a = ra / (ra + 1.0), bb = rb / (rb + 1.0);
+            g.fx = qx + a * ex, g.fy = qy + a * ey;
+            g.dx = g.dx + bb * (ex / dt), g.dy = g.dy + bb * (ey / dt);
+            ox = g.fx, oy = g.fy;
+          }
+          g.fs = ps, g.gap = 0;
+          os = ps, sr = 1;
+        } else if (g.n > 0) {
+          g.gap += 1;
+          if (g.gap > sm.max_hold) {
+            g.n = 0;
+          } else {
+            const double gp = (double)g.gap;
+            ox = g.fx + g.dx * gp, oy = g.fy + g.dy * gp, os = g.fs, sr = 2;
+          }
+        }
+        *f = g;
+      }
+    }
+    out[(size_t)e * 3] = ox, out[(size_t)e * 3 + 1] = oy, out[(size_t)e * 3 + 2] = os;
+    src[e] = sr;
+    if (cin) cout[e] = sr == 2 ? -3 : cin[e];
+  }
+  for (int e = t; e < T * J; e += 256) {
+    const int k = pkind[e / J];
+    if (k == 0) continue;
+    TrackFilter* f = filt + e;
+    if (k == 2) {
+      f->n = 0;
+    } else if (f->n > 0) {  // 8b
+      const int gap = f->gap + 1;
+      f->gap = gap;
+      if (gap > sm.max_hold) f->n = 0;
+    }
+  }
+}
+
 // One workgroup of 256 threads (4 waves) applies one image to one slot: the body of an update, steps 1-7.  Thread i owns track place i
 // in steps 1, 5 and 6, thread q owns person q in step 7.  D lives in global scratch (256 x 256 doubles do not fit in LDS beside the rest)
 // and is written and read inside this workgroup only, with a barrier in between.
@@ -152,11 +255,12 @@ __device__ __forceinline__ void match_optimal(int T, int P, int n, double max_di
 // robin.  No step depends on thread timing: same inputs, same ids.
 // The state block is read AND written here, and track_kernel calls this several times on one block with a barrier in between: `state`
 // carries no __restrict__, so that nothing loaded from it is kept across that barrier.
-template <int Assign>  // the matching rule, TrackParams::assign: the greedy instance is the kernel it was, instruction for instruction
+// Smooth (step 8, TrackSmooth): a second parameter for the same reason — the instances without it are the kernels they were.
+template <int Assign, int Smooth>  // the matching rule, TrackParams::assign: the greedy instance is the kernel it was, instruction for instruction
 __device__ __forceinline__ void track_image(int b, unsigned char* state_block, int P, const TrackParams& tp,
                                             const double* __restrict__ sig2_g, double* __restrict__ dist,
                                             const int* __restrict__ n_people, const double* __restrict__ people,
-                                            long long* __restrict__ ids, int* __restrict__ place) {
+                                            long long* __restrict__ ids, int* __restrict__ place, const TrackSmooth& sm, TrackFilter* filt) {
   __shared__ double s2[kTrackMax];   // s_i^2
   __shared__ double rv[kTrackMax];   // row minima: value ...
   __shared__ int rq[kTrackMax];      // ... and person, -1 = the row has no allowed entry left
@@ -382,6 +486,7 @@ __device__ __forceinline__ void track_image(int b, unsigned char* state_block, i
     ids[(size_t)b * P + t] = my_id;
     place[(size_t)b * P + t] = my_place;
   }
+  if constexpr (Smooth == 1) smooth_image(b, P, n, tp, sm, filt, ppl, live, tm, mult, my_place, unmatched != 0);
 }
 
 // One workgroup per slot: it walks the images in ascending b and applies those the map gives to its slot, each on the state the one
@@ -389,34 +494,40 @@ __device__ __forceinline__ void track_image(int b, unsigned char* state_block, i
 // last stores to the state (steps 5-7) and the next image's loads of it (steps 1-3) by other threads of this workgroup, and between its
 // last readers of the LDS arrays (flag, fplace, pm in step 7) and the next image's initialisation of them.  A workgroup whose slot no
 // image names returns without touching the slot.
-template <int Assign>
+// With Smooth the same barrier stands between an image's stores to the slot's filters (step 8) and the next image's loads of them.
+template <int Assign, int Smooth>
 __global__ __launch_bounds__(256) void track_kernel(int NB, int P, TrackParams tp, TrackSlotMap map, const double* __restrict__ sig2_g,
                                                     unsigned char* state, size_t slot_stride, double* __restrict__ dist,
                                                     const int* __restrict__ n_people, const double* __restrict__ people,
-                                                    long long* __restrict__ ids, int* __restrict__ place) {
+                                                    long long* __restrict__ ids, int* __restrict__ place, TrackSmooth sm) {
   const int slot = blockIdx.x;
   unsigned char* block = state + (size_t)slot * slot_stride;
+  TrackFilter* filt = Smooth == 1 ? sm.filt + (size_t)slot * tp.T * tp.J : nullptr;
   for (int b = 0; b < NB; ++b) {
     if ((int)((map.w[b >> 2] >> ((b & 3) * 8)) & 0xffu) != slot) continue;  // uniform
-    track_image<Assign>(b, block, P, tp, sig2_g, dist, n_people, people, ids, place);
+    track_image<Assign, Smooth>(b, block, P, tp, sig2_g, dist, n_people, people, ids, place, sm, filt);
     __syncthreads();
   }
 }
 
 int launch_track(int S, int NB, int P, const TrackParams& p, const double* sig2, unsigned char* state, size_t slot_stride, double* dist,
-                 const int* n_people, const double* people, long long* ids, int* place, const TrackSlotMap& map, void* stream) {
+                 const int* n_people, const double* people, long long* ids, int* place, const TrackSlotMap& map, void* stream,
+                 const TrackSmooth* sm) {
   if (NB <= 0) return 0;
   if (S < 1 || S > 256 || NB > kTrackMaxImages || P < 1 || P > kTrackMax || p.T < 1 || p.T > kTrackMax || p.J < 1 ||
       p.J > kPeopleMaxJoints || slot_stride % 16 || slot_stride < track_slot_bytes(p.T, p.J) || p.assign < 0 || p.assign > 1)
     return (int)hipErrorInvalidValue;
   for (int b = 0; b < NB; ++b)
     if ((int)((map.w[b >> 2] >> ((b & 3) * 8)) & 0xffu) >= S) return (int)hipErrorInvalidValue;
-  if (p.assign == 1)  // step 4' : an instantiation of its own, so that the greedy one keeps its registers and its LDS
-    hipLaunchKernelGGL((track_kernel<1>), dim3(S), dim3(256), 0, (hipStream_t)stream, NB, P, p, map, sig2, state, slot_stride, dist,
-                       n_people, people, ids, place);
-  else
-    hipLaunchKernelGGL((track_kernel<0>), dim3(S), dim3(256), 0, (hipStream_t)stream, NB, P, p, map, sig2, state, slot_stride, dist,
-                       n_people, people, ids, place);
+  if (sm && (!sm->filt || !sm->smooth || !sm->src || (sm->cand_in && !sm->cand_out) || sm->max_hold < 0)) return (int)hipErrorInvalidValue;
+  const TrackSmooth off{};
+  auto go = [&](auto kernel, const TrackSmooth& s8) {
+    hipLaunchKernelGGL(kernel, dim3(S), dim3(256), 0, (hipStream_t)stream, NB, P, p, map, sig2, state, slot_stride, dist, n_people, people,
+                       ids, place, s8);
+  };
+  // step 4' and step 8: instantiations of their own, so that the greedy one without smoothing keeps its registers and its LDS
+  if (sm) p.assign == 1 ? go(track_kernel<1, 1>, *sm) : go(track_kernel<0, 1>, *sm);
+  else p.assign == 1 ? go(track_kernel<1, 0>, off) : go(track_kernel<0, 0>, off);
   return (int)hipGetLastError();
 }
 

@@ -9,5 +9,6 @@ libdeepcut_hip.so (include/deepcut_hip.h); there is no compute in Python and no 
 from .pycaffe import Net, NetGroup, Tracker, TrackedFrames, Comm, Blob, Frame, csc_coefficients, Layer, choose_streams, pinned_empty, lpt_schedule, set_mode_cpu, set_mode_gpu, set_device, device_count, canvas_size, check_boxes, member_canvas, check_assembly, pair_stats_read, conv_variants, conv_variants_bf16, wino_half_pack, wino_blocks, wino_cover, wino_mix_offered, stream1x1_pack, stream1x1f_pack, stream1x1f_rows, wino43_pack, stem7x7_pack, sparse_head_pack, lib_path  # noqa: F401
 from .pycaffe import TRAIN, TEST, DeepcutError  # noqa: F401
 from .pycaffe import dedupe_people, dedupe_params, DEDUPE_DEFAULTS  # noqa: F401
+from .pycaffe import smooth_params, SMOOTH_DEFAULTS  # noqa: F401
 
 __version__ = "1.0.0-rc3+deepcut_hip"

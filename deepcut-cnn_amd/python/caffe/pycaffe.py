@@ -64,6 +64,16 @@ class TrackerParams(C.Structure):
                 ("min_common", C.c_int), ("max_dist", C.c_double), ("min_size", C.c_double), ("motion", C.c_int)]
 
 
+class TrackSmoothParams(C.Structure):
+    """dc_track_smooth_params (include/deepcut_hip.h)."""
+    _fields_ = [("enabled", C.c_int), ("min_cutoff", C.c_double), ("beta", C.c_double), ("d_cutoff", C.c_double), ("max_hold", C.c_int)]
+
+
+# Step 8 of the tracker's rule (`Tracker.smoothing`).  PLACEHOLDERS, NOT TUNED ON REAL VIDEO: override them.  Time counts in updates: a
+# 1 Hz cutoff on 30 fps video is min_cutoff = 1 / 30.
+SMOOTH_DEFAULTS = {"min_cutoff": 0.1, "beta": 4.0, "d_cutoff": 0.03, "max_hold": 3}
+
+
 class DcFrame(C.Structure):
     """dc_frame (include/deepcut_hip.h)."""
     _fields_ = [("plane", C.c_void_p * 2), ("pitch", C.c_int * 2), ("format", C.c_int), ("matrix", C.c_int), ("range", C.c_int)]
@@ -286,6 +296,10 @@ def _load():
         "dc_tracker_state": (ci, [vp, ci, vp, vp, vp, vp]),
         "dc_tracker_set_option": (ci, [vp, ci, ci]),
         "dc_tracker_get_option": (ci, [vp, ci, C.POINTER(ci)]),
+        "dc_tracker_set_smoothing": (ci, [vp, C.POINTER(TrackSmoothParams)]),
+        "dc_tracker_get_smoothing": (ci, [vp, C.POINTER(TrackSmoothParams)]),
+        "dc_tracker_update_smoothed": (ci, [vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "dc_tracker_smooth_state": (ci, [vp, ci, vp, vp]),
         "dc_net_track_people_slots": (ci, [vp, vp, vp, C.POINTER(AssembleParams), ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "dc_net_track_people": (ci, [vp, vp, C.POINTER(AssembleParams), ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "dc_group_track_people": (ci, [vp, vp, vp, ci, C.POINTER(FuseMirror), C.POINTER(AssembleParams), ci, vp, vp, vp, vp, vp, vp, vp, vp,
@@ -733,6 +747,9 @@ class Tracker(object):
     override them.  assign: "greedy" (the default: the closest pair first, step 4 of the rule) or "optimal" (step 4': the assignment
     with the smallest total distance, an unmatched track costing max_dist — two people who pass each other keep their ids where greedy
     matching swaps them); also a property, which may change between updates: the tracks stay.
+    smooth: None / False (off, the default), True (SMOOTH_DEFAULTS: PLACEHOLDERS, NOT TUNED ON REAL VIDEO) or a dict of some of
+    min_cutoff, beta, d_cutoff, max_hold — step 8 of the rule: a filter per track and joint on the device smooths the poses and
+    bridges joints that vanish for at most max_hold updates; no id, place or distance changes by a bit.  Also the property `smoothing`.
     Creation needs no device; updates need GPU mode.  The calls of this class are synchronous; updates apply in call order, those
     enqueued by `Net.track_frames_async` included (the synchronous calls wait for them first)."""
 
@@ -740,9 +757,10 @@ class Tracker(object):
     _OPT_ASSIGN = 1  # DC_TRACK_OPT_ASSIGN
 
     def __init__(self, n_joints=14, slots=1, max_tracks=64, sigma=None, max_misses=5, min_common=3, max_dist=0.25, min_size=32.0, motion=1,
-                 assign="greedy"):
+                 assign="greedy", smooth=None):
         self._h = None
         self._assign_value(assign)
+        smooth = smooth_params(smooth)
         sig = None
         if sigma is not None:
             sig = np.ascontiguousarray(sigma, dtype=np.float64).reshape(-1)
@@ -756,6 +774,8 @@ class Tracker(object):
         self.n_joints, self.slots, self.max_tracks = int(n_joints), int(slots), int(max_tracks)
         if assign != "greedy":
             self.assign = assign
+        if smooth is not None:
+            self.smoothing = smooth
 
     @classmethod
     def _assign_value(cls, assign):
@@ -774,19 +794,45 @@ class Tracker(object):
     def assign(self, assign):
         _check(_lib.dc_tracker_set_option(self._h, self._OPT_ASSIGN, self._assign_value(assign)))
 
+    @property
+    def smoothing(self):
+        """None (off, the default) or {"min_cutoff", "beta", "d_cutoff", "max_hold"}: step 8 of the rule (dc_tracker_set_smoothing).
+        Assign None / False, True (SMOOTH_DEFAULTS: PLACEHOLDERS, NOT TUNED ON REAL VIDEO) or a dict of some of the four; cutoffs are in
+        cycles per update.  May change between updates: off -> on starts with empty filters, a change while on keeps them.  A bad value
+        raises DeepcutError naming the field, with or without a device."""
+        q = TrackSmoothParams()
+        _check(_lib.dc_tracker_get_smoothing(self._h, C.byref(q)))
+        if not q.enabled:
+            return None
+        return {"min_cutoff": float(q.min_cutoff), "beta": float(q.beta), "d_cutoff": float(q.d_cutoff), "max_hold": int(q.max_hold)}
+
+    @smoothing.setter
+    def smoothing(self, smooth):
+        d = smooth_params(smooth)
+        if d is None:
+            _check(_lib.dc_tracker_set_smoothing(self._h, None))
+            return
+        try:
+            q = TrackSmoothParams(1, float(d["min_cutoff"]), float(d["beta"]), float(d["d_cutoff"]), int(d["max_hold"]))
+        except (TypeError, ValueError) as e:
+            raise ValueError("smooth: min_cutoff, beta and d_cutoff must be numbers, max_hold a whole number (%s)" % (e,))
+        _check(_lib.dc_tracker_set_smoothing(self._h, C.byref(q)))
+
     def __del__(self):
         if getattr(self, "_h", None):
             _lib.dc_tracker_destroy(self._h)
             self._h = None
 
-    def update(self, people, n_people=None, return_dist=False, slot_of=None):
+    def update(self, people, n_people=None, return_dist=False, slot_of=None, return_smooth=False):
         """people: [nb, P, J, 3] float64 (x, y, score; a joint counts when its score > 0) with n_people [nb] of them valid per image, or
         a list of nb arrays [m_b, J, 3] (n_people is then their lengths) — image b updates slot b.  This is how poses that did not come
         from `track_people` (top-down poses of `forward_boxes`, say) get tracked.
         slot_of: [nb] ints in [0, slots), the slot every image updates (dc_tracker_update_slots): images of one slot apply in ascending b,
         each on the state the one before left — several frames of one video in one call; nb may then be 1..64 whatever `slots` is.
         -> (ids int64 [nb, P], place int32 [nb, P]): -1 beyond n_people[b] and for a person no track place was free for; with
-        return_dist also the distances float64 [nb, max_tracks, P]."""
+        return_dist also the distances float64 [nb, max_tracks, P].  return_smooth (needs `smoothing` on, dc_tracker_update_smoothed):
+        -> (ids, place[, dist], smooth, src) with smooth float64 [nb, P, J, 3], the smoothed poses, and src int32 [nb, P, J]: 0 nothing,
+        1 observed, 2 bridged."""
         j = self.n_joints
         if n_people is None and not (isinstance(people, np.ndarray) and people.ndim == 4):
             arrs = [np.asarray(a, np.float64).reshape(-1, j, 3) for a in people]
@@ -806,6 +852,11 @@ class Tracker(object):
         place = np.full((nb, p), -1, np.int32)
         dist = np.zeros((nb, self.max_tracks, p), np.float64) if return_dist else None
         ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        if return_smooth:
+            smooth, src = np.zeros((nb, p, j, 3), np.float64), np.zeros((nb, p, j), np.int32)
+            _check(_lib.dc_tracker_update_smoothed(self._h, nb, p, None if slot_of is None else ptr(_slot_map(slot_of, nb)), ptr(n), ptr(ppl),
+                                                   ptr(ids), ptr(place), ptr(dist), ptr(smooth), ptr(src)))
+            return (ids, place, dist, smooth, src) if return_dist else (ids, place, smooth, src)
         if slot_of is None:
             _check(_lib.dc_tracker_update(self._h, nb, p, ptr(n), ptr(ppl), ptr(ids), ptr(place), ptr(dist)))
         else:
@@ -824,6 +875,31 @@ class Tracker(object):
                "poses": np.zeros((t, j, 3), np.float64)}
         _check(_lib.dc_tracker_state(self._h, int(slot), *[out[k].ctypes.data_as(C.c_void_p) for k in ("ids", "misses", "hits", "poses")]))
         return out
+
+    def smooth_state(self, slot=0):
+        """Where the filters of a slot expect every joint now (dc_tracker_smooth_state) -> dict: "poses" float64 [T, J, 3], the filter's
+        position moved on by its rate over the updates since the joint was last observed, with the last observed score, and "gap" int32
+        [T, J], those updates; zeros and -1 where the filter holds nothing (always, with smoothing off)."""
+        t, j = self.max_tracks, self.n_joints
+        out = {"poses": np.zeros((t, j, 3), np.float64), "gap": np.full((t, j), -1, np.int32)}
+        _check(_lib.dc_tracker_smooth_state(self._h, int(slot), out["poses"].ctypes.data_as(C.c_void_p), out["gap"].ctypes.data_as(C.c_void_p)))
+        return out
+
+
+def smooth_params(smooth):
+    """A `smooth=` argument / a `smoothing` value -> the dict of the four parameters, or None for off.  None and False are off, True is
+    SMOOTH_DEFAULTS (PLACEHOLDERS, not tuned on real video), a dict overrides some of them.  The values themselves are checked by the
+    library (dc_tracker_set_smoothing)."""
+    if smooth is None or smooth is False:
+        return None
+    if smooth is True:
+        return dict(SMOOTH_DEFAULTS)
+    if not isinstance(smooth, dict):
+        raise TypeError("smooth must be None, True or a dict of %s, got %r" % (sorted(SMOOTH_DEFAULTS), smooth))
+    unknown = sorted(set(smooth) - set(SMOOTH_DEFAULTS))
+    if unknown:
+        raise ValueError("smooth: unknown keys %r (known: %s)" % (unknown, sorted(SMOOTH_DEFAULTS)))
+    return dict(SMOOTH_DEFAULTS, **smooth)
 
 
 def _slot_map(slot_of, nb):
@@ -1018,8 +1094,9 @@ class TrackedFrames(object):
     """What `Net.track_frames_async` returns: the request in flight.  It owns the pinned output arrays and keeps the frames alive;
     `result()` waits for the net and returns what `Net.track_people` returns."""
 
-    def __init__(self, net, tracked, count, people, cand, ids, place, keep, pool=None, completed=False):
+    def __init__(self, net, tracked, count, people, cand, ids, place, keep, pool=None, completed=False, bridging=False):
         self._net, self._tracked, self._keep, self._pool, self._completed = net, tracked, keep, pool, completed
+        self._bridging = bridging
         self._count, self._people, self._cand, self._ids, self._place = count, people, cand, ids, place
         self._out, self._ready = None, False
 
@@ -1042,6 +1119,8 @@ class TrackedFrames(object):
                 d = {"people": self._people[b, :m].copy(), "cand": self._cand[b, :m].copy()}
                 if self._completed:
                     d["filled"] = d["cand"] == -2
+                if self._bridging:
+                    d["bridged"] = d["cand"] == -3
                 if self._tracked:
                     d["ids"], d["place"] = self._ids[b, :m].copy(), self._place[b, :m].copy()
                 out.append(d)
@@ -1050,6 +1129,12 @@ class TrackedFrames(object):
                 self._pool.append((self._count, self._people, self._cand, self._ids, self._place))
                 self._count = self._people = self._cand = self._ids = self._place = self._pool = None
         return self._out
+
+
+def _tracker_smoothing(tracker):
+    """Whether the results of a chained entry carry "bridged": the tracker has smoothing on (`Tracker.smoothing`)."""
+    _tracker_handle(tracker)
+    return tracker.smoothing is not None
 
 
 def _tracker_handle(tracker):
@@ -1685,12 +1770,13 @@ class Net(_Completing):
             if tracker is not None:
                 ids, place = out((n, p), np.int64), out((n, p), np.int32)
         ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        bridging = tracker is not None and _tracker_smoothing(tracker)
         with self._completing(complete, dedupe) as completed:
             _check(_lib.dc_net_track_frames_async(self._h, None if tracker is None else tracker._h, arr, ptr(x), n, h, w, float(scale),
                                                   1 if dev else 0, None if slot_of is None else ptr(_slot_map(slot_of, n)), C.byref(q),
                                                   e.shape[0], ptr(e), ptr(m), ptr(s), ptr(order), ptr(count), ptr(people), ptr(cand),
                                                   ptr(ids), ptr(place)))
-        return TrackedFrames(self, tracker is not None, count, people, cand, ids, place, keep + (tracker,), pool, completed)
+        return TrackedFrames(self, tracker is not None, count, people, cand, ids, place, keep + (tracker,), pool, completed, bridging)
 
     def _assemble_people(self, tracker, scale, threshold, radius, max_det, edges, mean, std, max_cost, seed_threshold, max_people, min_joints,
                          joint_order, return_cost, slot_of=None, complete=None, dedupe=None):
@@ -1706,6 +1792,7 @@ class Net(_Completing):
         cand = np.zeros((n, p, j), np.int32)
         cost = np.zeros((n, j, j, md, md), np.float64) if return_cost else None
         ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        bridging = tracker is not None and _tracker_smoothing(tracker)
         with self._completing(complete, dedupe) as completed:
             if tracker is None:
                 _check(_lib.dc_net_assemble_people(self._h, C.byref(q), e.shape[0], ptr(e), ptr(m), ptr(s), ptr(order), ptr(count), ptr(people),
@@ -1724,6 +1811,8 @@ class Net(_Completing):
             d = {"people": people[b, :count[b]].copy(), "cand": cand[b, :count[b]].copy()}
             if completed:
                 d["filled"] = d["cand"] == -2
+            if bridging:
+                d["bridged"] = d["cand"] == -3
             if return_cost:
                 d["cost"] = cost[b]
             if tracker is not None:
@@ -2200,6 +2289,7 @@ class NetGroup(_Completing):
         cost = np.zeros((n, j, j, md, md), np.float64) if return_cost else None
         ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
         fm, _keep = self._mirror(mirror, image_width, joint_mirror, e)
+        bridging = tracker is not None and _tracker_smoothing(tracker)
         with self._completing(complete, dedupe) as completed:
             if tracker is None:
                 _check(_lib.dc_group_assemble_people_mirrored(self._h, ptr(sc), base, fm, C.byref(q), e.shape[0], ptr(e), ptr(m), ptr(s),
@@ -2219,6 +2309,8 @@ class NetGroup(_Completing):
             d = {"people": people[b, :count[b]].copy(), "cand": cand[b, :count[b]].copy()}
             if completed:
                 d["filled"] = d["cand"] == -2
+            if bridging:
+                d["bridged"] = d["cand"] == -3
             if return_cost:
                 d["cost"] = cost[b]
             if tracker is not None:

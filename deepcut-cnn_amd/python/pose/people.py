@@ -88,7 +88,7 @@ def estimate_people(image, model_def, model_bin, stats, scale=1.0, net=None, sca
     return _people_of_image(None, image, model_def, model_bin, stats, scale, net, scales, base, flip, joint_mirror, sparse, assembly)["people"]
 
 
-def track_people(frames, model_def, model_bin, stats, tracker=None, depth=1, batch=1, assign="greedy", **kw):
+def track_people(frames, model_def, model_bin, stats, tracker=None, depth=1, batch=1, assign="greedy", smooth=None, **kw):
     """`estimate_people` over the frames of a video, with identities: a generator over an iterable of images (HxWx3 BGR uint8) or
     `caffe.Frame`s that yields, per frame, (people float64 [m, J, 3], ids int64 [m]) — the same person keeps their id from frame to
     frame, -1 marks a person no track place was free for.  kw: what `estimate_people` takes (scale / scales / base / flip / joint_mirror /
@@ -96,7 +96,9 @@ def track_people(frames, model_def, model_bin, stats, tracker=None, depth=1, bat
     `Net.track_people` / `NetGroup.track_people`: the association runs on the device behind the assembly, the people it returns are
     `estimate_people`'s.  tracker: a `caffe.Tracker` of one slot or more (slot 0 is used); None makes one with the defaults, which are
     PLACEHOLDERS, not tuned on real video, and with the matching rule `assign` ("greedy" or "optimal", as `caffe.Tracker` takes it; a
-    tracker of the caller's keeps its own setting).  PARITY UNPINNED BY THE REFERENCE: the tracking rule is this project's own
+    tracker of the caller's keeps its own setting) and with `smooth` (None, True or a dict, as `caffe.Tracker` takes it: the people
+    yielded are then the smoothed poses of step 8 of the rule, short gaps bridged; its defaults are PLACEHOLDERS, not tuned on real
+    video, and a tracker of the caller's keeps its own setting here too).  PARITY UNPINNED BY THE REFERENCE: the tracking rule is this project's own
     (include/deepcut_hip.h, dc_tracker_update).
     depth / batch: the defaults (1, 1) run one synchronous call per frame.  depth > 1 keeps that many frames in flight on the net and
     its clones, batch > 1 sends that many consecutive frames as one batch forward (`deepcut_tools.VideoPipeline`); the results are the
@@ -110,20 +112,20 @@ def track_people(frames, model_def, model_bin, stats, tracker=None, depth=1, bat
         if args["scales"] is not None or args["flip"]:
             raise ValueError("track_people: depth > 1 / batch > 1 run one forward per frame; a pyramid (scales= / flip=True) has no "
                              "asynchronous entry: use depth=1, batch=1")
-        for item in _track_in_flight(frames, model_def, model_bin, stats, tracker, int(depth), int(batch), args, kw, assign):
+        for item in _track_in_flight(frames, model_def, model_bin, stats, tracker, int(depth), int(batch), args, kw, assign, smooth):
             yield item
         return
     for image in frames:
         if tracker is None:
             import caffe as _caffe
 
-            tracker = _caffe.Tracker(n_joints=len(MIRROR_MPII14), assign=assign)
+            tracker = _caffe.Tracker(n_joints=len(MIRROR_MPII14), assign=assign, smooth=smooth)
         d = _people_of_image(tracker, image, model_def, model_bin, stats, args["scale"], args["net"], args["scales"], args["base"], args["flip"],
                              args["joint_mirror"], args["sparse"], kw)
         yield d["people"], d["ids"]
 
 
-def _track_in_flight(frames, model_def, model_bin, stats, tracker, depth, batch, args, assembly, assign="greedy"):
+def _track_in_flight(frames, model_def, model_bin, stats, tracker, depth, batch, args, assembly, assign="greedy", smooth=None):
     """`track_people` through `deepcut_tools.VideoPipeline` -> (people, ids) per frame, in frame order."""
     import caffe as _caffe
     from deepcut_tools import VideoPipeline
@@ -132,7 +134,7 @@ def _track_in_flight(frames, model_def, model_bin, stats, tracker, depth, batch,
     if net is None:
         net = _get_sparse_model(model_def, model_bin) if args["sparse"] else _get_model(model_def, model_bin)
     if tracker is None:
-        tracker = _caffe.Tracker(n_joints=len(MIRROR_MPII14), assign=assign)
+        tracker = _caffe.Tracker(n_joints=len(MIRROR_MPII14), assign=assign, smooth=smooth)
     pipe = VideoPipeline(net, tracker, depth=depth, batch=batch, stats=stats, scale=args["scale"], **assembly)
     ahead = 0
     for image in frames:

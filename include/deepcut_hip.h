@@ -813,7 +813,41 @@ int dc_group_flops(dc_group* group, double* out);
  *  7. Births.  The unmatched people, q ascending, take the free places, place index ascending (places freed in step 6 of this update
  *     count as free): id = next_id++, hits = 1, misses = 0, vel = 0.  A person for whom no place is free gets id -1 and is not
  *     tracked.  Ids are never reused within a slot.
- * Deterministic: the same calls give the same ids.  dc_tracker_reset(slot) frees the slot's tracks and sets next_id back to 0.
+ *  8. Smoothed poses, OPT-IN (dc_tracker_set_smoothing; off by default, and nothing above changes by a bit when it is off or on).
+ *     PARITY UNPINNED BY THE REFERENCE, like the rest of the tracker: the reference stops at the maps; tests/smooth_ref.py restates this
+ *     step in float64 loops.  The raw assembly result jitters from frame to frame, and a joint that falls below the threshold for one
+ *     frame comes back as (0, 0, 0); step 5 forgets it too.  Step 8 keeps a filter per track place and joint and returns, beside ids and
+ *     place, a smoothed pose per person in which short gaps are bridged.  All arithmetic is in double, in the order written.  Smoothing
+ *     influences no decision: ids, place, dist and everything dc_tracker_state returns are bit for bit what they are without it.
+ *     Parameters (dc_track_smooth_params): min_cutoff (finite, > 0; cycles per update), beta (finite, >= 0: how much a surprise opens
+ *     the filter), d_cutoff (finite, > 0; cycles per update, for the rate estimate), max_hold (0..1000: updates a joint may be
+ *     bridged).  Time is counted in updates — one image of a slot is one update —, so a 1 Hz cutoff on 30 fps video is
+ *     min_cutoff = 1/30.  THE DEFAULTS THE PYTHON LAYER CHOOSES (0.1, 4.0, 0.03, 3) ARE PLACEHOLDERS, NOT TUNED ON REAL VIDEO.
+ *     Helper: A(fc, dt) = r / (r + 1) with r = (TWO_PI * fc) * dt and TWO_PI = 6.283185307179586.
+ *     Filter state per track place i and joint j: fx, fy (position), dx, dy (rate per update), fs (last observed score), gap (updates
+ *     since the last observation), n (0: holds nothing, 1: one observation, 2: running).  After steps 5-7 of an image:
+ *     8a. A place matched in step 5 to person q, or born in step 7 from q.  On birth the place's filter is cleared first (n = 0 for
+ *         every joint).  s is the step-1 size of the person's pose, which is the track's new pose.  For every joint, with (px, py, ps)
+ *         the person's values:
+ *           held (ps > 0), n == 0:  fx = px; fy = py; dx = dy = 0; fs = ps; gap = 0; n = 1.  Out (px, py, ps), src 1.
+ *           held, n == 1:  dt = gap + 1; dx = (px - fx) / dt; dy = (py - fy) / dt; fx = px; fy = py; fs = ps; gap = 0; n = 2.
+ *                          Out (px, py, ps), src 1.  (The rate starts from the first difference: started from zero it takes tens of
+ *                          frames to catch up with a walking person.)
+ *           held, n == 2:  dt = gap + 1; qx = fx + dx * dt; qy = fy + dy * dt; ex = px - qx; ey = py - qy;
+ *                          a = A(min_cutoff + beta * ((|ex| + |ey|) / s), dt); b = A(d_cutoff, dt);
+ *                          fx = qx + a * ex; fy = qy + a * ey; dx = dx + b * (ex / dt); dy = dy + b * (ey / dt); fs = ps; gap = 0.
+ *                          Out (fx, fy, ps), src 1.  (Predict, then correct: unlike a plain low-pass this has no lag behind a constant
+ *                          velocity; the surprise, normalised by the person's size, opens the filter, so a real change of direction
+ *                          is followed quickly.)
+ *           not held, n > 0:  gap += 1.  If gap > max_hold: n = 0, out (0, 0, 0), src 0.  Otherwise out (fx + dx * gap, fy + dy * gap,
+ *                          fs), src 2: a BRIDGED joint.
+ *           not held, n == 0:  out (0, 0, 0), src 0.
+ *     8b. A live track that step 6 left unmatched and did not free.  For every joint with n > 0: gap += 1, and n = 0 when
+ *         gap > max_hold.  A freed place has n = 0 everywhere.
+ *     8c. A person with id -1 (no free place): out is the person as given, src 1 for held joints.  Entries q >= n_people: zeros.
+ *     Scores are not smoothed, real timestamps (variable frame intervals) are not taken, and bridged joints take no part in the matching.
+ * Deterministic: the same calls give the same ids.  dc_tracker_reset(slot) frees the slot's tracks and sets next_id back to 0; it
+ *     clears the slot's filters of step 8 as well.
  *
  * dc_tracker_create: slots 1..64; max_tracks (T) 1..256; n_joints (J) 1..32; sigma[J] NULL (all 1.0) or each finite and > 0;
  *     max_misses >= 0; min_common 1..J; max_dist finite and >= 0; min_size finite and > 0; motion 0 or 1.  Anything else is DC_EINVAL
@@ -825,6 +859,22 @@ int dc_group_flops(dc_group* group, double* out);
  *     like the other synchronous calls: it waits for the last enqueued update, then stores the value, and every update enqueued
  *     afterwards uses it.  The slots' state is untouched, so a sequence may switch rule between frames.  An unknown key or value is
  *     DC_EINVAL naming it.  dc_tracker_params carries no option: it has no size field and compiled callers exist.
+ * dc_tracker_set_smoothing / dc_tracker_get_smoothing: step 8's switch and parameters; NULL (or enabled == 0) is off, the default.  They
+ *     need no device and order themselves like dc_tracker_set_option: set waits for the last enqueued update, after which every update
+ *     enqueued later uses the new value.  Going from off to on starts with empty filters; changing parameters while on keeps the
+ *     filters.  A bad value is DC_EINVAL naming the field.  The filters are a device allocation of their own, 48 bytes per place and
+ *     joint, made at the first update with smoothing on; a tracker that leaves smoothing off runs the kernels it ran without step 8.
+ * dc_tracker_update_smoothed: dc_tracker_update_slots plus smooth[nb][P][J][3] and src[nb][P][J] (int: 0 nothing, 1 observed,
+ *     2 bridged; either may be NULL).  DC_EINVAL when smoothing is off.  The other update entries advance the filters too when
+ *     smoothing is on; they merely do not return step 8's outputs.
+ * dc_tracker_smooth_state: where the filters of a slot expect every joint now: poses[T][J][3] = (fx + dx * gap, fy + dy * gap, fs) and
+ *     gap[T][J] where n > 0, zeros and -1 elsewhere (either may be NULL).  Synchronous like dc_tracker_state.
+ * Chained entries with smoothing on (dc_net_track_people[_slots], dc_group_track_people[_slots], dc_net_track_frames_async; no
+ *     signature changes): `people` is downloaded from the smoothed poses and `cand` carries -3 at bridged joints, next to -2 for filled
+ *     ones; n_people, cost, ids and place are what they were, and the net's own device copies of the people stay raw.  The sparse
+ *     pairwise head, fused pyramids, mirrored groups, completion and dedupe are covered: the tracker receives what those stages leave.
+ *     Step 8's outputs leave the tracker's scratch in front of the tracker's event, so a later update cannot overwrite what an earlier
+ *     asynchronous call has not downloaded yet.
  * dc_tracker_update: host poses — n_people[nb], people[nb][P][J][3] (entries of q >= n_people[b] are not read) — are uploaded and
  *     image b updates slot b in one launch (one workgroup per slot).  This is how top-down poses of dc_net_forward_boxes get tracked.
  *     Outputs: ids[nb][P] (long long; -1 for q >= n and for an untracked person), place[nb][P] (int, the track place; -1 likewise; may
@@ -893,6 +943,19 @@ int dc_tracker_state(dc_tracker* tracker, int slot, long long* ids, int* misses,
 #define DC_TRACK_ASSIGN_OPTIMAL 1   /* step 4' */
 int dc_tracker_set_option(dc_tracker* tracker, int key, int value);
 int dc_tracker_get_option(dc_tracker* tracker, int key, int* value);
+typedef struct dc_track_smooth_params {
+  int    enabled;     /* 0 / 1: the switch */
+  double min_cutoff;  /* finite, > 0; cycles per update */
+  double beta;        /* finite, >= 0; how much a surprise opens the filter */
+  double d_cutoff;    /* finite, > 0; cycles per update, for the rate estimate */
+  int    max_hold;    /* 0..1000: updates a joint may be bridged */
+} dc_track_smooth_params;
+int dc_tracker_set_smoothing(dc_tracker* tracker, const dc_track_smooth_params* p /* NULL: off */);
+int dc_tracker_get_smoothing(dc_tracker* tracker, dc_track_smooth_params* out);
+int dc_tracker_update_smoothed(dc_tracker* tracker, int nb, int P, const int* slot_of /* [nb], NULL: image b -> slot b */,
+                               const int* n_people, const double* people, long long* ids, int* place, double* dist,
+                               double* smooth /* [nb][P][J][3] */, int* src /* [nb][P][J] */);
+int dc_tracker_smooth_state(dc_tracker* tracker, int slot, double* poses /* [T][J][3] */, int* gap /* [T][J] */);
 int dc_net_track_people(dc_net* net, dc_tracker* tracker, const dc_assemble_params* p, int n_edges, const int* edges, const double* mean,
                         const double* stdev, const int* joint_order, int* n_people, double* people, int* cand, double* cost,
                         long long* ids, int* place);

@@ -11,7 +11,11 @@ of five windows of at least 0.5 s with the windows listed.
 assignment): the same calls, every one on a greedy and on an optimal tracker, the two alternated in the same windows — `Net.track_people`
 and the stand-alone updates above —, with the number of inner trips step 4' takes on each case, counted by its restatement
 (tests/assign_ref.py) on the device's own distances.
-    python tools/track_ab.py --assign both [--out profiles/track_assign_ab.txt]"""
+    python tools/track_ab.py --assign both [--out profiles/track_assign_ab.txt]
+--smooth measures step 8 (smoothed poses, `Tracker.smoothing`) the same way: every call on a tracker without smoothing and on one with
+it (the placeholder parameters), the two alternated in the same windows — `Net.track_people` on the held forward, the stand-alone update
+at 32 people and at T = P = n = 256.  The smoothing-off figures are the ones to hold against this tool's default run on the commit before.
+    python tools/track_ab.py --smooth [--out profiles/track_smooth_ab.txt]"""
 import argparse
 import os
 import statistics
@@ -132,9 +136,50 @@ def assign_ab(caffe, net, kw, say, fmt):
             % (name, spread(per["greedy"]), spread(per["optimal"]), o - g, o / g, trips, fmt(per["greedy"]), fmt(per["optimal"])))
 
 
+def smooth_ab(caffe, net, kw, say, fmt):
+    """Smoothing off against on, alternated in the same windows: Net.track_people on the held forward, then the stand-alone updates."""
+    spread = lambda v: "%.4f [%.4f - %.4f]" % (statistics.median(v), min(v), max(v))  # noqa: E731
+    modes = {"off": None, "on": True}
+    trackers = {m: caffe.Tracker(n_joints=14, slots=1, max_tracks=64, smooth=v) for m, v in modes.items()}
+    calls = {"track_people " + m: (lambda t=trackers[m]: net.track_people(t, **kw)) for m in modes}
+    calls["assemble_people"] = lambda: net.assemble_people(**kw)
+    for call in calls.values():
+        for _ in range(20):
+            call()
+    found = len(net.assemble_people(**kw)[0]["people"])
+    per = windows(calls)
+    s = statistics.median(per["assemble_people"])
+    say("max_det 16 max_people 32 (%d people found), T 64: Net.assemble_people %s ms per call" % (found, spread(per["assemble_people"])))
+    for m in modes:
+        v = per["track_people " + m]
+        say("  Net.track_people, smoothing %s: %s ms per call (%+.4f ms on assemble_people); windows %s" % (m, spread(v), statistics.median(v) - s, fmt(v)))
+    for name, T, n, make, max_dist in CASES[:2]:
+        first, second = make(n)
+        calls = {}
+        for m, v in modes.items():
+            trk = caffe.Tracker(n_joints=14, slots=1, max_tracks=T, max_dist=max_dist, max_misses=1000, smooth=v)
+            ids0, _ = trk.update(first)
+            ids1, _ = trk.update(second)
+            assert sorted(ids0[0].tolist()) == list(range(n)) and sorted(ids1[0].tolist()) == list(range(n)), (name, m)  # all born, all matched
+            state = {"k": 1}
+
+            def call(trk=trk, frames=(first, second), state=state, smoothed=v is not None):
+                state["k"] ^= 1
+                trk.update(frames[state["k"]], return_smooth=smoothed)  # on: the smoothed poses and src come back as well
+
+            for _ in range(10):
+                call()
+            calls[m] = call
+        per = windows(calls)
+        off, on = statistics.median(per["off"]), statistics.median(per["on"])
+        say("Tracker.update %s: smoothing off %s ms, on %s ms per call (%+.4f ms, x %.2f); windows off %s on %s"
+            % (name, spread(per["off"]), spread(per["on"]), on - off, on / off, fmt(per["off"]), fmt(per["on"])))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
+    ap.add_argument("--smooth", action="store_true", help="smoothing off against on (step 8), alternated")
     ap.add_argument("--assign", default="greedy", choices=["greedy", "both"], help="both: greedy against optimal, alternated")
     a = ap.parse_args()
     import caffe
@@ -160,8 +205,8 @@ def main():
         "windows >= 0.5 s, calls alternated" % (H, W))
     net.forward_images(img, 1.0, want=(), pose=False)
     kw = dict(scale=1.0, threshold=0.5, radius=1, max_det=16, edges=edges, mean=mean, std=std, max_cost=30.0, seed_threshold=0.6, max_people=32)
-    if a.assign == "both":
-        assign_ab(caffe, net, kw, say, fmt)
+    if a.smooth or a.assign == "both":
+        (smooth_ab if a.smooth else assign_ab)(caffe, net, kw, say, fmt)
         if a.out:
             with open(a.out, "w") as f:
                 f.write("\n".join(lines) + "\n")
