@@ -1123,6 +1123,19 @@ int dc_dedupe_people(const dc_dedupe_params* p, int nb, int P, int J, const int*
   REQUIRE(people_out);
   return guard([&] { dedupe_people(p, nb, P, J, n_people, people, cand, n_out, people_out, cand_out, kept_from, suppressed_by); });
 }
+// the skeleton overlay (draw.cpp)
+int dc_draw_people(const dc_frame* frames, int nb, int height, int width, int is_device, int P, int J, const int* n_people,
+                   const double* people, const int* cand, const long long* ids, const dc_draw_style* style, void* stream) {
+  REQUIRE(frames);
+  REQUIRE(n_people);
+  REQUIRE(people);
+  REQUIRE(style);
+  return guard([&] { draw_people(frames, nb, height, width, is_device != 0, P, J, n_people, people, cand, ids, style, stream); });
+}
+int dc_draw_limits(int* tile_w, int* tile_h, int* chunk) {
+  draw_limits(tile_w, tile_h, chunk);
+  return DC_OK;
+}
 // single-person and box poses from the fused maps (net_group.cpp decode_pose / decode_boxes)
 int dc_group_decode_pose(dc_group* group, const double* scales, int base, const dc_fuse_mirror* fm, double* pose, int is_device, void* stream) {
   REQUIRE(group);

@@ -426,6 +426,31 @@ int launch_dedupe(int NB, int J, int max_people, double max_dist, int min_common
                   const int* n_in, const double* people_in, const int* cand_in, int* n_out, double* people_out, int* cand_out,
                   int* kept_from, int* suppressed_by, void* stream);
 
+// Skeleton overlay (draw.hip; the rule: include/deepcut_hip.h, dc_draw_people — this project's own).  The host (draw.cpp) snaps the
+// joints to 1/16-pixel fixed point, converts the colours and bins the primitives, in drawing order, into kDrawTileW x kDrawTileH pixel
+// tiles; one workgroup draws one non-empty tile, one thread one 2 x 2 pixel block (so the thread that owns a chroma sample owns its
+// luma pixels), every thread walking the tile's primitives in order, kDrawChunk at a time through LDS.
+constexpr int kDrawTileW = 32, kDrawTileH = 32, kDrawChunk = 64;
+struct DrawPrim {       // 32 bytes
+  int ax, ay, bx, by;   // the ends in 1/16 pixel, |v| <= 2^19; a disc has b == a
+  int r16;              // radius in 1/16 pixel, 1..1024
+  int capsule;          // 0: the disc at a; 1: the capsule from a to b
+  int alpha;            // 0..256
+  unsigned colour;      // byte 0, 1, 2 = B, G, R (BGR24) or Y, Cb, Cr (NV12)
+};
+struct DrawTile {
+  int frame, tx, ty;  // the frame and the tile's column and row
+  int first, count;   // its primitives: index[first .. first + count), ascending = drawing order
+};
+struct DrawPlanes {
+  unsigned char* plane0;  // as FramePlanes, written
+  unsigned char* plane1;
+  int pitch0, pitch1;
+};
+// format: DC_PIX_BGR24 or DC_PIX_NV12.  Grid = n_tiles (> 0).  Every pointer is device memory.
+int launch_draw(int format, const DrawPlanes* frames, int height, int width, const DrawTile* tiles, int n_tiles, const int* index,
+                const DrawPrim* prims, void* stream);
+
 // Tracking people from frame to frame (track.hip; the rule: include/deepcut_hip.h, dc_tracker_update — this project's own).  A slot's
 // state is one block of track_slot_bytes(T, J) bytes, all zero = no track and next_id 0:
 //   long long next_id (+ 8 bytes of padding) | long long id[T] | double pose[T][J][3] | double vel[T][J][2] | int live[T] | int misses[T]

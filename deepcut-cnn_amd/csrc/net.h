@@ -26,6 +26,7 @@
 struct dc_frame;  // include/deepcut_hip.h: one video frame (planes, pitches, format, matrix, range)
 struct dc_complete_params;  // include/deepcut_hip.h: stage D of the people assembly
 struct dc_dedupe_params;    // include/deepcut_hip.h: stage E of the people assembly
+struct dc_draw_style;       // include/deepcut_hip.h: the skeleton overlay
 struct dc_track_smooth_params;  // include/deepcut_hip.h: step 8 of the tracker's rule
 
 namespace dc {
@@ -292,6 +293,10 @@ struct DedupeParams {
 // dc_dedupe_people (people.cpp): stage E alone on host arrays, synchronous
 void dedupe_people(const dc_dedupe_params* params, int nb, int P, int J, const int* n_people, const double* people, const int* cand,
                    int* n_out, double* people_out, int* cand_out, int* kept_from, int* suppressed_by);
+// dc_draw_people / dc_draw_limits (draw.cpp): skeletons blended into frames in place on the device, synchronous
+void draw_people(const dc_frame* frames, int nb, int h, int w, bool is_device, int P, int J, const int* n_people, const double* people,
+                 const int* cand, const long long* ids, const dc_draw_style* style, void* stream);
+void draw_limits(int* tile_w, int* tile_h, int* chunk);
 
 // What the assembly calls behind its last stage with the device arrays it left (n_people, people, cand): the tracker's launch.  True:
 // the hook has delivered `people` and `cand` to the host arrays itself (a tracker with smoothing on), and the assembly downloads neither.

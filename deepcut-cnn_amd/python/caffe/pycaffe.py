@@ -79,6 +79,13 @@ class DcFrame(C.Structure):
     _fields_ = [("plane", C.c_void_p * 2), ("pitch", C.c_int * 2), ("format", C.c_int), ("matrix", C.c_int), ("range", C.c_int)]
 
 
+class DrawStyle(C.Structure):
+    """dc_draw_style (include/deepcut_hip.h)."""
+    _fields_ = [("n_edges", C.c_int), ("edges", C.c_void_p), ("joint_radius", C.c_double), ("limb_radius", C.c_double), ("alpha", C.c_int),
+                ("alpha_filled", C.c_int), ("min_score", C.c_double), ("color_mode", C.c_int), ("palette", C.c_void_p), ("n_palette", C.c_int),
+                ("untracked", C.c_ubyte * 3)]
+
+
 MAX_ASSEMBLE_DET, MAX_ASSEMBLE_PEOPLE = 64, 256  # dc_net_assemble_people's limits
 # Stage D of the people assembly (`Net.completion`, the `complete=` arguments).  PLACEHOLDERS, not tuned on real images: override them.
 COMPLETE_DEFAULTS = {"fill_threshold": 0.25, "fill_radius": 2, "min_support": 2}
@@ -385,6 +392,8 @@ def _load():
         "dc_group_set_dedupe": (ci, [vp, C.POINTER(DedupeParams)]),
         "dc_group_get_dedupe": (ci, [vp, C.POINTER(DedupeParams), C.c_void_p]),
         "dc_dedupe_people": (ci, [C.POINTER(DedupeParams), ci, ci, ci] + [C.c_void_p] * 8),
+        "dc_draw_people": (ci, [C.POINTER(DcFrame), ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, C.POINTER(DrawStyle), vp]),
+        "dc_draw_limits": (ci, [C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -1006,6 +1015,128 @@ def dedupe_people(people, n_people=None, cand=None, dedupe=True, return_maps=Fal
             e["kept_from"], e["suppressed_by"] = kept_from[b, :m].copy(), by[b, :int(n[b])].copy()
         out.append(e)
     return out
+
+
+# ---- drawing people into frames (dc_draw_people; the rule: include/deepcut_hip.h — this project's own, the reference has none) -------
+# By-joint colours: the reference demo's 14-colour table (R, G, B), one per MPII joint.
+DRAW_JOINT_COLORS = tuple([(255, 0, 0), (0, 255, 0), (0, 0, 255), (0, 245, 255), (255, 131, 250), (255, 255, 0)] * 2 + [(0, 0, 0), (255, 255, 255)])
+# By-person colours (R, G, B), indexed by id.  A PLACEHOLDER: twelve hues chosen by eye to stay apart from their neighbours, not tested
+# for legibility on real video; pass palette= for another.
+DRAW_ID_COLORS = ((230, 25, 75), (60, 180, 75), (255, 225, 25), (0, 130, 200), (245, 130, 48), (145, 30, 180), (70, 240, 240), (240, 50, 230),
+                  (210, 245, 60), (250, 190, 190), (0, 128, 128), (170, 110, 40))
+_DRAW_MODES = {"id": 0, "joint": 1}  # DC_DRAW_BY_PERSON, DC_DRAW_BY_JOINT
+
+
+def draw_limits():
+    """-> (tile_w, tile_h, chunk): the tile a workgroup of the drawing kernel covers, and the primitives it stages at a time."""
+    v = [C.c_int() for _ in range(3)]
+    _check(_lib.dc_draw_limits(*[C.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def draw_coefficients(matrix="bt601", range="limited"):
+    """((yr, yg, yb), (cb_r, cb_g, cb_b), (cr_r, cr_g, cr_b), y0) of the forward colour rule the NV12 overlay converts its colours by
+    (include/deepcut_hip.h, dc_draw_people): the counterpart of `csc_coefficients`, computed in double, rounded to nearest."""
+    kr, kb = ((0.299, 0.114), (0.2126, 0.0722))[_CSC_MATRIX[matrix]]
+    kg = 1.0 - kr - kb
+    full = bool(_CSC_RANGE[range])
+    sy, sc = (1.0, 1.0) if full else (255.0 / 219.0, 255.0 / 224.0)
+    r = lambda v: int(np.rint(v))  # noqa: E731
+    return (tuple(r(65536.0 * k / sy) for k in (kr, kg, kb)),
+            tuple(r(65536.0 * k / (2.0 * (1.0 - kb)) / sc) for k in (-kr, -kg, 1.0 - kb)),
+            tuple(r(65536.0 * k / (2.0 * (1.0 - kr)) / sc) for k in (1.0 - kr, -kg, -kb)), 0 if full else 16)
+
+
+def draw_people(frames, people, n_people=None, ids=None, cand=None, edges=None, joint_radius=4.0, limb_radius=2.0, alpha=256, alpha_filled=128,
+                min_score=0.0, color="id", palette=None, untracked=(128, 128, 128), stream=None):
+    """Skeletons blended into frames IN PLACE on the device (dc_draw_people; the rule — integer only, this project's own: the reference
+    draws with matplotlib and states none — is in include/deepcut_hip.h): joints as discs of joint_radius pixels, the limbs `edges`
+    ([E, 2] joints, None = joints only) as capsules of limb_radius, people in index order, of a person the limbs and then the joints.
+    frames: a `Frame` (NV12 or BGR24, host or device), a list of them (one size, format, matrix and range), or a uint8 [H, W, 3] BGR
+    array, wrapped like `Frame.bgr`.  Host arrays are drawn in place and must be writable (ValueError otherwise).
+    people: float64 [m, J, 3] (one frame) or [nb, P, J, 3] with n_people [nb], or a list of nb arrays [m_b, J, 3], as `dedupe_people`
+    takes them; cand: int32 of the same leading shape or None — joints it marks filled (-2) or bridged (-3), and limbs that end in one,
+    are blended with alpha_filled instead of alpha (both 0..256, 256 = opaque); ids: int64 [nb, P] / [m] or None.
+    color: "id" — palette[id % len] (the person's index without ids; `untracked` for id < 0), palette None = DRAW_ID_COLORS (a
+    PLACEHOLDER) — or "joint" — palette[j % len] for joint j and for a limb ending in j, None = DRAW_JOINT_COLORS.  Colours are R, G, B.
+    stream: a HIP stream for device frames (None: the library's own).  The call returns when the drawing is complete.  Needs GPU mode."""
+    fl = _frame_list(frames)
+    if fl is None:
+        if isinstance(frames, np.ndarray) and frames.ndim == 3:
+            fl = [Frame.bgr(frames)]
+        else:
+            raise ValueError("frames must be a caffe.Frame, a non-empty list of them, or a uint8 [H, W, 3] BGR array")
+    for i, f in enumerate(fl):
+        for a in f._keep:
+            if isinstance(a, np.ndarray) and not a.flags.writeable:
+                raise ValueError("frame %d: a host array that is drawn into must be writable" % i)
+    arr, h, w, is_device = _frame_array(fl)
+    nb = len(fl)
+
+    def per_image(v, dtype, tail):
+        """v -> [nb, P] + tail, from the [nb, P, ...] array, the single image's [m, ...] array or a list of nb arrays [m_b, ...]."""
+        if not isinstance(v, np.ndarray):
+            try:  # a list of numbers or of equal arrays is the array itself; a ragged one stays a list of per-image arrays
+                a = np.asarray(v, dtype)
+                v = a if a.ndim in (1 + len(tail), 2 + len(tail)) else v
+            except ValueError:
+                pass
+        if isinstance(v, np.ndarray) and v.ndim == 2 + len(tail):
+            return np.ascontiguousarray(v, dtype=dtype)
+        if isinstance(v, np.ndarray) and v.ndim == 1 + len(tail):
+            v = [v]
+        rows = [np.asarray(a, dtype).reshape((-1,) + tail) for a in v]
+        out = np.zeros((len(rows), max([1] + [a.shape[0] for a in rows])) + tail, dtype)
+        for b, a in enumerate(rows):
+            out[b, :a.shape[0]] = a
+        return out
+
+    if isinstance(people, np.ndarray) and people.ndim in (3, 4):
+        if people.shape[-1] != 3:
+            raise ValueError("people must be [m, J, 3] or [nb, P, J, 3] (x, y, score), got shape %s" % (people.shape,))
+        j = int(people.shape[-2])
+        if n_people is None:
+            n_people = [people.shape[0]] if people.ndim == 3 else [people.shape[1]] * people.shape[0]
+    else:
+        rows = [np.asarray(a, np.float64) for a in people]
+        if not rows or any(a.ndim != 3 or a.shape[1:] != rows[0].shape[1:] or a.shape[2] != 3 for a in rows):
+            raise ValueError("people must be arrays [m, J, 3] of one J, got shapes %s" % ([a.shape for a in rows],))
+        j = int(rows[0].shape[1])
+        if n_people is None:
+            n_people = [a.shape[0] for a in rows]
+        people = rows
+    ppl = per_image(people, np.float64, (j, 3))
+    n = np.ascontiguousarray(n_people, dtype=np.int32).reshape(-1)
+    if ppl.shape[0] != nb or n.shape[0] != nb:
+        raise ValueError("people and n_people must hold one entry per frame: %d and %d for %d frames" % (ppl.shape[0], n.shape[0], nb))
+    p = int(ppl.shape[1])
+    if p < 1:
+        ppl, p = np.zeros((nb, 1, j, 3), np.float64), 1
+    cnd = None if cand is None else per_image(cand, np.int32, (j,))
+    if cnd is not None and cnd.shape != ppl.shape[:3]:
+        raise ValueError("cand must be %s like people, got shape %s" % (ppl.shape[:3], cnd.shape))
+    idv = None if ids is None else per_image(ids, np.int64, ())
+    if idv is not None and idv.shape != ppl.shape[:2]:
+        raise ValueError("ids must be %s like people, got shape %s" % (ppl.shape[:2], idv.shape))
+    if color not in _DRAW_MODES:
+        raise ValueError("color must be one of %s, got %r" % (sorted(_DRAW_MODES), color))
+    if palette is None:
+        palette = DRAW_ID_COLORS if color == "id" else DRAW_JOINT_COLORS
+    pal = np.ascontiguousarray(palette, dtype=np.uint8)
+    if pal.ndim != 2 or pal.shape[1] != 3:
+        raise ValueError("palette must be [n, 3] R, G, B, got shape %s" % (pal.shape,))
+    e = np.zeros((0, 2), np.int32) if edges is None else np.ascontiguousarray(edges, dtype=np.int32)
+    if e.ndim != 2 or e.shape[1] != 2:
+        raise ValueError("edges must be [E, 2] joints, got shape %s" % (e.shape,))
+    st = DrawStyle()
+    st.n_edges, st.edges = int(e.shape[0]), e.ctypes.data if e.shape[0] else None
+    st.joint_radius, st.limb_radius = float(joint_radius), float(limb_radius)
+    st.alpha, st.alpha_filled, st.min_score = int(alpha), int(alpha_filled), float(min_score)
+    st.color_mode, st.palette, st.n_palette = _DRAW_MODES[color], pal.ctypes.data if pal.shape[0] else None, int(pal.shape[0])
+    st.untracked[:] = [int(v) for v in untracked]
+    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    _check(_lib.dc_draw_people(arr, nb, h, w, int(is_device), p, j, ptr(n), ptr(ppl), ptr(cnd), ptr(idv), C.byref(st),
+                               None if stream is None else C.c_void_p(int(stream))))
 
 
 class _Completing(object):

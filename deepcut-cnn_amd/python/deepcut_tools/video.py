@@ -13,13 +13,17 @@ import collections
 class VideoPipeline(object):
     MAX_DEPTH = 4  # a HIP process has four hardware queues: a fifth executor only shares one
 
-    def __init__(self, net, tracker=None, depth=3, batch=1, stats=None, scale=1.0, choose_streams=True, complete=None, dedupe=None, **assembly):
+    def __init__(self, net, tracker=None, depth=3, batch=1, stats=None, scale=1.0, choose_streams=True, complete=None, dedupe=None, draw=None,
+                 **assembly):
         """net: a `caffe.Net` with all three maps (or a sparse-pairwise net); tracker: a `caffe.Tracker` or None (people without ids,
         ids come back as None); depth: executors, 1..4; batch: frames per call, 1..64; stats: (edges, mean, std) as
         `deepcut_tools.read_pair_stats` returns them, or a path; scale: the pre-processing's and the assembly's; assembly: what
         `Net.assemble_people` takes (threshold, max_det, max_cost, ...).  complete: as `Net.assemble_people` takes it — None leaves
         every executor with the net's `completion` (the clones made here copy it), True or a dict is passed with every request.  dedupe: likewise for the net's `dedupe`
-        (stage E: people who are there twice are suppressed before the tracker sees them)."""
+        (stage E: people who are there twice are suppressed before the tracker sees them).  draw: None (off: nothing is added), True or a
+        dict of what `pose.draw_people` takes — every frame is kept with its request and drawn into IN PLACE on the device with the people
+        and ids being handed back (filled and bridged joints at alpha_filled), before they are handed back; the frames must then be
+        writable arrays or `caffe.Frame`s."""
         depth, batch = int(depth), int(batch)
         if not 1 <= depth <= self.MAX_DEPTH:
             raise ValueError("depth must be in [1, %d], got %d" % (self.MAX_DEPTH, depth))
@@ -38,6 +42,11 @@ class VideoPipeline(object):
             self.assembly["complete"] = complete
         if dedupe is not None:
             self.assembly["dedupe"] = dedupe
+        self._draw = None  # the style dict when frames are drawn into
+        if draw is not None and draw is not False:
+            from pose.people import _draw_style
+
+            self._draw = _draw_style(draw)
         self._choose_streams = bool(choose_streams)
         self.stream_choice = None            # what caffe.choose_streams measured, once it ran
         self._held = []                      # frames of the batch being gathered: (frame, tag, slot, shape key)
@@ -62,7 +71,7 @@ class VideoPipeline(object):
 
     def _free_executor(self):
         # an executor is busy while a request of it has not been SEEN finished (done() remembers: the net may get the next one at once)
-        busy = set(k for k, handle, _ in self._pending if not handle.done())
+        busy = set(k for k, handle, _, _ in self._pending if not handle.done())
         for i in range(len(self.nets)):
             k = (self._next + i) % len(self.nets)
             if k not in busy:
@@ -71,8 +80,12 @@ class VideoPipeline(object):
 
     def _collect_oldest(self):
         """Wait for the oldest request (the tracker ran them in submission order, so it finishes first or nearly) and queue its results."""
-        k, handle, tags = self._pending.popleft()
-        for tag, d in zip(tags, handle.result()):
+        k, handle, tags, frames = self._pending.popleft()
+        for i, (tag, d) in enumerate(zip(tags, handle.result())):
+            if frames is not None:
+                from pose.people import draw_people
+
+                draw_people(frames[i], d["people"], d.get("ids"), **dict(self._draw, cand=d.get("cand")))
             self._done.append((tag, d["people"], d.get("ids")))
 
     def _send(self):
@@ -85,6 +98,7 @@ class VideoPipeline(object):
             k = self._free_executor()
         self._next = (k + 1) % len(self.nets)
         frames = [h[0] for h in held]
+        kept = frames if self._draw is not None else None  # the frames themselves, to be drawn into when their results are there
         if held[0][3][0] == "bgr":
             import numpy as np
 
@@ -104,7 +118,7 @@ class VideoPipeline(object):
         handle = self.nets[k].track_frames_async(frames, self.tracker, self.scale, slot_of=slot_of, edges=self.edges, mean=self.mean,
                                                  std=self.std, **self.assembly)
         self.calls += 1
-        self._pending.append((k, handle, [h[1] for h in held]))
+        self._pending.append((k, handle, [h[1] for h in held], kept))
 
     def submit(self, frame, tag=None, slot=0):
         """Enqueue one frame (a `caffe.Frame` or an HxWx3 uint8 BGR image) of the sequence in tracker slot `slot`.  With batch > 1 the

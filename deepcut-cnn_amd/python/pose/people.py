@@ -14,6 +14,9 @@ _MODEL = {}
 # (right ankle, knee, hip; left hip, knee, ankle; right wrist, elbow, shoulder; left shoulder, elbow, wrist; upper neck; head top).  The
 # reference's Python names no joints, so this table is the caller's to override (`joint_mirror=`) for a model with another joint order.
 MIRROR_MPII14 = (5, 4, 3, 2, 1, 0, 11, 10, 9, 8, 7, 6, 12, 13)
+# The limbs `draw_people` draws between the joints of that order: the legs through the hips, the arms through the shoulders to the upper
+# neck, neck to head top, and the trunk's two sides.  Like the mirror table it is the caller's to override (`edges=`).
+SKELETON_MPII14 = ((0, 1), (1, 2), (2, 3), (3, 4), (4, 5), (6, 7), (7, 8), (8, 12), (12, 9), (9, 10), (10, 11), (12, 13), (2, 8), (3, 9))
 
 
 def _get_model(model_def, model_bin):
@@ -88,7 +91,30 @@ def estimate_people(image, model_def, model_bin, stats, scale=1.0, net=None, sca
     return _people_of_image(None, image, model_def, model_bin, stats, scale, net, scales, base, flip, joint_mirror, sparse, assembly)["people"]
 
 
-def track_people(frames, model_def, model_bin, stats, tracker=None, depth=1, batch=1, assign="greedy", smooth=None, **kw):
+def draw_people(frame, people, ids=None, **style):
+    """Draw people into a frame IN PLACE on the device: `caffe.draw_people` with the MPII skeleton (`SKELETON_MPII14`) for `edges` unless
+    the caller names another.  frame: a writable uint8 [H, W, 3] BGR array or a `caffe.Frame` (NV12 / BGR24, host or device); people:
+    [m, J, 3] as `estimate_people` / `track_people` return them; ids: int64 [m] or None; style: what `caffe.draw_people` takes (cand,
+    edges, joint_radius, limb_radius, alpha, alpha_filled, min_score, color, palette, untracked, stream).  PARITY UNPINNED BY THE
+    REFERENCE: the drawing rule is this project's own (include/deepcut_hip.h, dc_draw_people)."""
+    import caffe as _caffe
+
+    style.setdefault("edges", SKELETON_MPII14)
+    _caffe.draw_people(frame, _np.asarray(people, _np.float64), ids=ids, **style)
+
+
+def _draw_style(draw):
+    """draw= of `track_people` / `VideoPipeline` -> None (off) or the style dict."""
+    if draw is None or draw is False:
+        return None
+    if draw is True:
+        return {}
+    if not isinstance(draw, dict):
+        raise ValueError("draw must be None, True or a dict of what draw_people takes, got %r" % (draw,))
+    return dict(draw)
+
+
+def track_people(frames, model_def, model_bin, stats, tracker=None, depth=1, batch=1, assign="greedy", smooth=None, draw=None, **kw):
     """`estimate_people` over the frames of a video, with identities: a generator over an iterable of images (HxWx3 BGR uint8) or
     `caffe.Frame`s that yields, per frame, (people float64 [m, J, 3], ids int64 [m]) — the same person keeps their id from frame to
     frame, -1 marks a person no track place was free for.  kw: what `estimate_people` takes (scale / scales / base / flip / joint_mirror /
@@ -103,7 +129,11 @@ def track_people(frames, model_def, model_bin, stats, tracker=None, depth=1, bat
     depth / batch: the defaults (1, 1) run one synchronous call per frame.  depth > 1 keeps that many frames in flight on the net and
     its clones, batch > 1 sends that many consecutive frames as one batch forward (`deepcut_tools.VideoPipeline`); the results are the
     same (people, ids) in frame order, up to `depth * batch` frames behind the input.  One forward per frame only: a pyramid
-    (scales= / flip=True) has no asynchronous entry and raises ValueError."""
+    (scales= / flip=True) has no asynchronous entry and raises ValueError.
+    draw: None (off: nothing is added to the run), True or a dict of what `draw_people` takes — every frame is drawn into IN PLACE on the
+    device, with the people and ids being yielded (the smoothed, de-duplicated ones; filled and bridged joints at alpha_filled), before
+    they are yielded.  The frames must then be writable arrays or `caffe.Frame`s; (people, ids) are what they are without `draw`."""
+    style = _draw_style(draw)
     args = dict(scale=1.0, net=None, scales=None, base=None, flip=False, joint_mirror=MIRROR_MPII14, sparse=False)
     for k in list(kw):
         if k in args:
@@ -112,7 +142,7 @@ def track_people(frames, model_def, model_bin, stats, tracker=None, depth=1, bat
         if args["scales"] is not None or args["flip"]:
             raise ValueError("track_people: depth > 1 / batch > 1 run one forward per frame; a pyramid (scales= / flip=True) has no "
                              "asynchronous entry: use depth=1, batch=1")
-        for item in _track_in_flight(frames, model_def, model_bin, stats, tracker, int(depth), int(batch), args, kw, assign, smooth):
+        for item in _track_in_flight(frames, model_def, model_bin, stats, tracker, int(depth), int(batch), args, kw, assign, smooth, style):
             yield item
         return
     for image in frames:
@@ -122,10 +152,12 @@ def track_people(frames, model_def, model_bin, stats, tracker=None, depth=1, bat
             tracker = _caffe.Tracker(n_joints=len(MIRROR_MPII14), assign=assign, smooth=smooth)
         d = _people_of_image(tracker, image, model_def, model_bin, stats, args["scale"], args["net"], args["scales"], args["base"], args["flip"],
                              args["joint_mirror"], args["sparse"], kw)
+        if style is not None:
+            draw_people(image, d["people"], d["ids"], **dict(style, cand=d["cand"]))
         yield d["people"], d["ids"]
 
 
-def _track_in_flight(frames, model_def, model_bin, stats, tracker, depth, batch, args, assembly, assign="greedy", smooth=None):
+def _track_in_flight(frames, model_def, model_bin, stats, tracker, depth, batch, args, assembly, assign="greedy", smooth=None, style=None):
     """`track_people` through `deepcut_tools.VideoPipeline` -> (people, ids) per frame, in frame order."""
     import caffe as _caffe
     from deepcut_tools import VideoPipeline
@@ -135,6 +167,8 @@ def _track_in_flight(frames, model_def, model_bin, stats, tracker, depth, batch,
         net = _get_sparse_model(model_def, model_bin) if args["sparse"] else _get_model(model_def, model_bin)
     if tracker is None:
         tracker = _caffe.Tracker(n_joints=len(MIRROR_MPII14), assign=assign, smooth=smooth)
+    if style is not None:
+        assembly = dict(assembly, draw=style)
     pipe = VideoPipeline(net, tracker, depth=depth, batch=batch, stats=stats, scale=args["scale"], **assembly)
     ahead = 0
     for image in frames:

@@ -35,12 +35,14 @@ def draw_disc(image, cx, cy, radius, color):
 @click.option("--gpu", type=click.INT, default=0)
 @click.option("--tiling", type=click.Choice(["none", "exact", "reference"]), default="none",
               help="none: one forward per scale (default); exact / reference: see pose.estimate_pose")
+@click.option("--skeleton", type=click.BOOL, is_flag=True, default=False,
+              help="draw the overlay on the device: joints and the MPII limbs, coloured by joint (pose.draw_people); default: discs only")
 @click.option("--model_def", default=None,
               help="model definition (.prototxt).  Default: the definition deepcut_tools.deepercut_prototxt(152) generates, which is "
                    "layer-for-layer the reference's models/deepercut/ResNet-152.prototxt (that directory is not part of this repository)")
 @click.option("--model_bin", default=None, required=True,
               help="trained weights (.caffemodel / .h5): the reference fetches them with models/deepercut/download_models.sh; not shipped here")
-def predict_pose_from(image_name, out_name, scales, visualize, folder_image_suffix, use_cpu, gpu, tiling, model_def, model_bin):
+def predict_pose_from(image_name, out_name, scales, visualize, folder_image_suffix, use_cpu, gpu, tiling, skeleton, model_def, model_bin):
     import caffe
     from PIL import Image
 
@@ -76,7 +78,14 @@ def predict_pose_from(image_name, out_name, scales, visualize, folder_image_suff
         img = img[:, :, :3][:, :, ::-1]  # RGB -> BGR
         pose = estimate_pose(img, model_def, model_bin, scales, tiling=None if tiling == "none" else tiling)
         np.savez_compressed(target, pose=pose)
-        if visualize and pose is not None:
+        if visualize and pose is not None and skeleton:
+            from pose.people import SKELETON_MPII14, draw_people
+
+            bgr = np.ascontiguousarray(img)
+            draw_people(bgr, np.ascontiguousarray(pose[:3].T)[None], edges=SKELETON_MPII14, color="joint", joint_radius=8.0, limb_radius=3.0)
+            vis = bgr[:, :, ::-1]
+            Image.fromarray(np.ascontiguousarray(vis)).save(target + "_vis.png")
+        elif visualize and pose is not None:
             vis = img[:, :, ::-1].copy()
             for j in range(14):
                 draw_disc(vis, pose[0, j], pose[1, j], 8, COLORS[j])

@@ -1094,6 +1094,72 @@ int dc_dedupe_people(const dc_dedupe_params* p, int nb, int P, int J, const int*
                      const int* cand /* may be NULL: assigned == held */, int* n_out, double* people_out, int* cand_out /* may be NULL */,
                      int* kept_from /* [nb][P], may be NULL */, int* suppressed_by /* [nb][P] input index or -1, may be NULL */);
 
+/* ---- drawing people into video frames: skeletons blended into BGR24 or NV12 frames in place, on the device ---------------
+ * PARITY UNPINNED BY THE REFERENCE: the reference's demo draws with matplotlib / scipy.misc on the host and states no rule.  THE RULE
+ * below is this project's own, like the assembly and tracking rules.  It is integer only, so every path gives the same bytes
+ * (tests/draw_ref.py restates it in numpy; the device is held to that byte for byte).  No anti-aliasing: it would end byte equality.
+ *
+ * Input per image b: n_people[b] people of J joints (x, y, score) in image pixels, people[nb][P][J][3], as every people entry returns
+ *   them; cand[nb][P][J] (may be NULL): -2 = filled (stage D), -3 = bridged (the tracker's step 8); ids[nb][P] (may be NULL).
+ * Which joints are drawn: x, y and score all finite and score > min_score (min_score >= 0, so (0, 0, 0) is never drawn).  A limb — edge
+ *   e = (a, c) of the style's skeleton table — is drawn when both its joints are.
+ * Snapping: a coordinate is clamped to [-32768, 32768] pixels, then q = (int)rint(16 v): 1/16-pixel fixed point, ties to even.
+ *   Radii: r16 = rint(16 radius), radius in [0, 64] pixels; r16 = 0 means that kind of primitive is not drawn.  The centre of pixel
+ *   (px, py) is (16 px + 8, 16 py + 8).
+ * Coverage, in int64, of the pixel centre p.  w = p - a, v = p - b, d = b - a, L = d.d:
+ *   disc at a:            w.w <= r16^2
+ *   capsule from a to b:  w.w <= r16^2, or v.v <= r16^2, or (0 < w.d < L and |cross| < 2^31 and cross^2 <= r16^2 L), cross = w.x d.y - w.y d.x
+ *   The guard is exact: coordinates are at most 2^19 units, so |d| components are at most 2^20, L <= 2^41 and r16^2 L <= 2^61;
+ *   |cross| >= 2^31 implies cross^2 >= 2^62 > r16^2 L — outside —, so the square is never formed and every product that is fits int64.
+ * Order: people in index order; of a person the limbs in edge order, then the joints in joint order.  Later primitives go over earlier
+ *   ones: with alpha < 256 the order is visible, and it is kept exactly.
+ * Blend, per covered pixel and 8-bit channel: out = (c A + dst (256 - A) + 128) >> 8, A = alpha, or alpha_filled for a joint with
+ *   cand <= -2 and for a limb with such an end (cand NULL: alpha everywhere).
+ * Colour: DC_DRAW_BY_PERSON: palette[key % n_palette] with key = p without ids, key = ids[b][p] when that is >= 0, and the style's
+ *   `untracked` colour when it is < 0.  DC_DRAW_BY_JOINT: joint j gets palette[j % n_palette], limb e palette[edges[e][1] % n_palette].
+ *   palette is [n_palette][3] R, G, B.
+ * BGR24: the pixel's three channels are blended.
+ * NV12: luma is blended per pixel with the colour's Y.  A chroma sample (x >> 1, y >> 1) — the siting of dc_frame's rule — is blended
+ *   once per primitive, in the same order: with k of the block's n in-frame pixels covered (n = 4, or 2 or 1 at an odd right / bottom
+ *   edge) and k > 0, Ac = (A k + n / 2) / n, and Cb and Cr are blended with Ac.  The colour goes R, G, B -> Y, Cb, Cr once per
+ *   primitive by the forward counterpart of dc_frame's rule (Kr, Kb, Kg, y0, sy, sc as there; coefficients in double, rounded to
+ *   nearest; int32 with an arithmetic shift):
+ *     Y  = clip8(y0  + ((yr R + yg G + yb B + 32768) >> 16)),  (yr, yg, yb) = rint(65536 (Kr, Kg, Kb) / sy)
+ *     Cb = clip8(128 + ((...) >> 16)),  coefficients rint(65536 (-Kr, -Kg, 1 - Kb) / (2 (1 - Kb)) / sc)
+ *     Cr = clip8(128 + ((...) >> 16)),  coefficients rint(65536 (1 - Kr, -Kg, -Kb) / (2 (1 - Kr)) / sc)
+ *   BT.601 limited: Y (16829, 33039, 6416), Cb (-9714, -19071, 28784), Cr (28784, -24103, -4681); BT.601 full: (19595, 38470, 7471),
+ *   (-11058, -21710, 32768), (32768, -27439, -5329); BT.709 limited: (11966, 40254, 4064), (-6596, -22189, 28784), (28784, -26145,
+ *   -2639); BT.709 full: (13933, 46871, 4732), (-7509, -25259, 32768), (32768, -29763, -3005).  Forward and then dc_frame's inverse
+ *   comes back within 2 levels (limited) / 1 level (full) on all 2^24 triples (tests/test_draw_host.py).
+ * Untouched bytes: bytes of a frame that no primitive covers are not written — pitch padding and, for NV12, chroma samples whose
+ *   block no primitive covers included.
+ *
+ * dc_draw_people: nb frames (1..64) of one height x width (1..16384 each), format, matrix and range, written through their plane
+ *   pointers; P in [1, 256], J in [1, 32].  Stand-alone like dc_dedupe_people: no net, people as host arrays.  The call returns when the
+ *   drawing is complete: device frames (is_device = 1) are drawn on `stream`, or on the library's utility stream when it is NULL, and the
+ *   stream is waited for; host frames are staged up without their padding, drawn, and copied back with 2-D copies (the padding is never
+ *   written; a frame nothing is drawn into does not travel).  Only tiles that hold a primitive are launched (one workgroup each); a call
+ *   with nothing to draw launches nothing and writes nothing.
+ * Errors, before any device work: DC_EINVAL naming the field and the index for what the frame entries refuse (a NULL plane, a pitch
+ *   below the minimum, an unknown format / matrix / range, frames that differ in these), nb, height, width, P or J out of range, a NULL
+ *   style or palette, n_edges outside [0, 128], an edge joint outside [0, J), a radius outside [0, 64], alpha or alpha_filled outside
+ *   [0, 256], min_score not finite or < 0, an unknown color_mode, n_palette outside [1, 256], an n_people[b] outside [0, P].  Then
+ *   DC_ENOCPU in CPU mode (there is no CPU path).
+ * dc_draw_limits: the tile size and the primitives staged at a time that the kernel was built with (any pointer may be NULL).    */
+#define DC_DRAW_BY_PERSON 0
+#define DC_DRAW_BY_JOINT  1
+typedef struct dc_draw_style {
+  int n_edges; const int* edges;            /* [n_edges][2] 0-based joints, 0..128; 0 = joints only */
+  double joint_radius, limb_radius;         /* pixels, 0..64 */
+  int alpha, alpha_filled;                  /* 0..256 */
+  double min_score;                         /* finite, >= 0 */
+  int color_mode; const unsigned char* palette; int n_palette; unsigned char untracked[3];
+} dc_draw_style;
+int dc_draw_people(const dc_frame* frames, int nb, int height, int width, int is_device, int P, int J, const int* n_people,
+                   const double* people, const int* cand /* may be NULL */, const long long* ids /* may be NULL */,
+                   const dc_draw_style* style, void* stream);
+int dc_draw_limits(int* tile_w, int* tile_h, int* chunk);
+
 /* ---- in-process multi-GPU forward (SURVEY 8(b)'s dc_forward_batch) -------------------------------------------------------
  * A communicator over `nexec` executors: executor k runs on devices[k] (NULL: k modulo the visible devices) on a host thread of its
  * own (mode and device are per thread, src/caffe/common.cpp:13-20).  transport: how the maps travel to the root executor's device —
