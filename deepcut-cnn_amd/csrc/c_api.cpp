@@ -1136,6 +1136,31 @@ int dc_draw_limits(int* tile_w, int* tile_h, int* chunk) {
   draw_limits(tile_w, tile_h, chunk);
   return DC_OK;
 }
+// the score-map overlay (heat.cpp); null geometry / style / map are refused there, after the frames' own checks, naming the field
+int dc_draw_heatmap(const dc_frame* frames, int nb, int height, int width, int is_device, const float* map, int map_is_device, int C, int Hm,
+                    int Wm, const dc_heat_geometry* geometry, const dc_heat_style* style, void* stream) {
+  REQUIRE(frames);
+  return guard([&] { draw_heatmap(frames, nb, height, width, is_device != 0, map, map_is_device != 0, C, Hm, Wm, geometry, style, stream); });
+}
+int dc_net_draw_heatmap(dc_net* net, const dc_frame* frames, int nb, int height, int width, int is_device, const dc_heat_geometry* geometry,
+                        const dc_heat_style* style) {
+  REQUIRE(net);
+  REQUIRE(frames);
+  return guard([&] { N(net)->draw_heatmap(frames, nb, height, width, is_device != 0, geometry, style); });
+}
+int dc_group_draw_heatmap(dc_group* group, const dc_frame* frames, int nb, int height, int width, int is_device, const double* scales, int base,
+                          double origin_x, double origin_y, const dc_heat_style* style) {
+  return dc_group_draw_heatmap_mirrored(group, frames, nb, height, width, is_device, scales, base, nullptr, origin_x, origin_y, style);
+}
+int dc_group_draw_heatmap_mirrored(dc_group* group, const dc_frame* frames, int nb, int height, int width, int is_device, const double* scales,
+                                   int base, const dc_fuse_mirror* fm, double origin_x, double origin_y, const dc_heat_style* style) {
+  REQUIRE(group);
+  REQUIRE(frames);
+  return guard([&] {
+    NetGroup::FuseMirror m;
+    G(group)->draw_heatmap(frames, nb, height, width, is_device != 0, scales, base, origin_x, origin_y, style, mirror_args(fm, m));
+  });
+}
 // single-person and box poses from the fused maps (net_group.cpp decode_pose / decode_boxes)
 int dc_group_decode_pose(dc_group* group, const double* scales, int base, const dc_fuse_mirror* fm, double* pose, int is_device, void* stream) {
   REQUIRE(group);

@@ -12,33 +12,10 @@ namespace dc {
 namespace {
 constexpr int kDrawMaxEdges = 128, kDrawMaxFrames = 64, kDrawMaxSide = 16384;
 
-int clip8(long v) { return v < 0 ? 0 : (v > 255 ? 255 : (int)v); }
-
-// the forward colour rule: the counterpart of frame_csc's inverse (net_image.cpp), coefficients in double, rounded to nearest
-struct ForwardCsc {
-  int y0, y[3], cb[3], cr[3];
-  ForwardCsc(int matrix, int range) {
-    const double Kr = matrix == DC_CSC_BT709 ? 0.2126 : 0.299, Kb = matrix == DC_CSC_BT709 ? 0.0722 : 0.114, Kg = 1.0 - Kr - Kb;
-    const double sy = range == DC_RANGE_FULL ? 1.0 : 255.0 / 219.0, sc = range == DC_RANGE_FULL ? 1.0 : 255.0 / 224.0;
-    y0 = range == DC_RANGE_FULL ? 0 : 16;
-    const double ky[3] = {Kr, Kg, Kb}, kb[3] = {-Kr, -Kg, 1.0 - Kb}, kr[3] = {1.0 - Kr, -Kg, -Kb};
-    for (int i = 0; i < 3; ++i) {
-      y[i] = (int)std::rint(65536.0 * ky[i] / sy);
-      cb[i] = (int)std::rint(65536.0 * kb[i] / (2.0 * (1.0 - Kb)) / sc);
-      cr[i] = (int)std::rint(65536.0 * kr[i] / (2.0 * (1.0 - Kr)) / sc);
-    }
-  }
-  // R, G, B -> Y | Cb << 8 | Cr << 16; the shift is arithmetic
-  unsigned operator()(int r, int g, int b) const {
-    const int Y = clip8(y0 + ((y[0] * r + y[1] * g + y[2] * b + 32768) >> 16));
-    const int Cb = clip8(128 + ((cb[0] * r + cb[1] * g + cb[2] * b + 32768) >> 16));
-    const int Cr = clip8(128 + ((cr[0] * r + cr[1] * g + cr[2] * b + 32768) >> 16));
-    return (unsigned)Y | (unsigned)Cb << 8 | (unsigned)Cr << 16;
-  }
-};
-
 // pixels -> 1/16 pixel, ties to even
 int snap16(double v) { return (int)std::rint(16.0 * std::min(32768.0, std::max(-32768.0, v))); }
+
+}  // namespace
 
 // the calls' device buffer, per device: grow-only and never freed, like the utility stream; the caller holds the runtime lock, and
 // every call waits for its work, so the next call finds it free
@@ -48,7 +25,6 @@ DevBuf& draw_buffer(int device) {
   if (!b) b = new DevBuf();
   return *b;
 }
-}  // namespace
 
 void draw_people(const dc_frame* frames, int nb, int h, int w, bool is_device, int P, int J, const int* n_people, const double* people,
                  const int* cand, const long long* ids, const dc_draw_style* st, void* stream) {

@@ -451,6 +451,27 @@ struct DrawPlanes {
 int launch_draw(int format, const DrawPlanes* frames, int height, int width, const DrawTile* tiles, int n_tiles, const int* index,
                 const DrawPrim* prims, void* stream);
 
+// Score-map overlay (heat.hip; the rule: include/deepcut_hip.h, dc_draw_heatmap — this project's own).  The host (heat.cpp) computes
+// the per-axis sample tables t = rint(256 u), clamped, and converts the colours; one workgroup blends one kDrawTileW x kDrawTileH pixel
+// tile of one frame, one thread one 2 x 2 pixel block (draw_kernel's ownership), after staging the patch of map cells the tile's tables
+// reach into LDS as 16-bit q = rint(4096 clamp01(s)), the drawn channels only, channel-major.
+constexpr int kHeatMaxJoints = 32;
+constexpr int kHeatMaxPatch = kDrawTileW * 8 / 8 + 2;  // cells per side at the largest scale, 8: 32 pixels = 32 cells, + 1 for the second tap, + 1 of rounding
+struct HeatParams {
+  const DrawPlanes* frames;       // [nb], written
+  const void* map;                // NHWC view: cell (b, y, x) channel c at ((b Hm + y) Wm + x) cp + c0 + c in the launch's element type;
+                                  // NCHW: float32 [nb][C][Hm][Wm]
+  const int *tx, *ty, *cx, *cy;   // t of every luma column [W] and row [H]; of every chroma block column and row (NV12; else null)
+  const unsigned* colour;         // DC_HEAT_MAX: [256] by v >> 4; DC_HEAT_BY_JOINT: [n_joints] by place in the list; bytes as DrawPrim::colour
+  int H, W, Hm, Wm, C, cp, c0;
+  int n_joints, by_joint, alpha, alpha_score, vmin;
+  int vgate;      // a tile whose staged q are all below it blends nothing: max(vmin, the least v with A(v) > 0)
+  int max_cells;  // the largest patch (cells) of any tile: the launch's LDS is n_joints * max_cells * 2 bytes
+  unsigned char joints[kHeatMaxJoints];
+};
+// format: DC_PIX_BGR24 or DC_PIX_NV12; ekind: the map's element type; nchw != 0: the float32 NCHW map.  Grid = tiles x frames.
+int launch_heat(int format, int ekind, int nchw, const HeatParams& p, int nb, void* stream);
+
 // Tracking people from frame to frame (track.hip; the rule: include/deepcut_hip.h, dc_tracker_update — this project's own).  A slot's
 // state is one block of track_slot_bytes(T, J) bytes, all zero = no track and next_id 0:
 //   long long next_id (+ 8 bytes of padding) | long long id[T] | double pose[T][J][3] | double vel[T][J][2] | int live[T] | int misses[T]

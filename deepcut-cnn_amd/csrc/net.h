@@ -27,6 +27,8 @@ struct dc_frame;  // include/deepcut_hip.h: one video frame (planes, pitches, fo
 struct dc_complete_params;  // include/deepcut_hip.h: stage D of the people assembly
 struct dc_dedupe_params;    // include/deepcut_hip.h: stage E of the people assembly
 struct dc_draw_style;       // include/deepcut_hip.h: the skeleton overlay
+struct dc_heat_geometry;    // include/deepcut_hip.h: the score-map overlay
+struct dc_heat_style;
 struct dc_track_smooth_params;  // include/deepcut_hip.h: step 8 of the tracker's rule
 
 namespace dc {
@@ -297,6 +299,9 @@ void dedupe_people(const dc_dedupe_params* params, int nb, int P, int J, const i
 void draw_people(const dc_frame* frames, int nb, int h, int w, bool is_device, int P, int J, const int* n_people, const double* people,
                  const int* cand, const long long* ids, const dc_draw_style* style, void* stream);
 void draw_limits(int* tile_w, int* tile_h, int* chunk);
+// dc_draw_heatmap (heat.cpp): a float32 NCHW score map, host or device, blended into frames in place on the device, synchronous
+void draw_heatmap(const dc_frame* frames, int nb, int h, int w, bool is_device, const float* map, bool map_is_device, int C, int Hm, int Wm,
+                  const dc_heat_geometry* geometry, const dc_heat_style* style, void* stream);
 
 // What the assembly calls behind its last stage with the device arrays it left (n_people, people, cand): the tracker's launch.  True:
 // the hook has delivered `people` and `cand` to the host arrays itself (a tracker with smoothing on), and the assembly downloads neither.
@@ -394,6 +399,8 @@ struct Net {
   void emit_last_maps(void* prob, void* loc, void* next, int elem, bool is_device, void* user_stream);
   // multi-person consumers of the maps of the last forward (encoding: pose_data_layer.cpp:686-802)
   void detect_parts(double scale, float thr, int radius, int max_det, int* counts, double* dets);
+  // `prob` of the last forward blended into nb frames in place (dc_net_draw_heatmap; heat.cpp), on the net's stream, waited for
+  void draw_heatmap(const dc_frame* frames, int nb, int h, int w, bool is_device, const dc_heat_geometry* geometry, const dc_heat_style* style);
   void decode_pairwise(double scale, int ndet, const int* det, const double* mean, const double* stdev, double* out);
   // the raw next_pred values at ndet (image, row, col) cells -> out [ndet][C] float32 (dc_net_pairwise_at): from the dense map when the plan
   // has it, by the sparse head otherwise
@@ -717,6 +724,9 @@ struct NetGroup {
                  bool is_device, void* user_stream, const FuseMirror* fm = nullptr);
   // Net::detect_parts on the fused prob / loc_pred at scales[base]
   void detect_parts(const double* scales, int base, float thr, int radius, int max_det, int* counts, double* dets, const FuseMirror* fm = nullptr);
+  // Net::draw_heatmap on the fused prob (fused alone, as detect_parts fuses it) at scales[base] (dc_group_draw_heatmap; heat.cpp)
+  void draw_heatmap(const dc_frame* frames, int nb, int h, int w, bool is_device, const double* scales, int base, double origin_x,
+                    double origin_y, const dc_heat_style* style, const FuseMirror* fm = nullptr);
   // fusion of all three maps, then Net::assemble_people's three launches on them at scales[base] (p.scale is not read)
   void assemble_people(const double* scales, int base, const Net::AssembleParams& p, int n_edges, const int* edges, const double* mean,
                        const double* stdev, const int* joint_order, int* n_people, double* people, int* cand, double* cost,

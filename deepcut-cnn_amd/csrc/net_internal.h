@@ -106,6 +106,33 @@ hipGraphExec_t capture_graph(void* cs, F&& enqueue) {
   return ge;
 }
 
+// ---- shared by the overlays (draw.cpp, heat.cpp) ----------------------------------------------------------------------------------
+inline int clip8(long v) { return v < 0 ? 0 : (v > 255 ? 255 : (int)v); }
+// the forward colour rule: the counterpart of frame_csc's inverse (net_image.cpp), coefficients in double, rounded to nearest
+struct ForwardCsc {
+  int y0, y[3], cb[3], cr[3];
+  ForwardCsc(int matrix, int range) {
+    const double Kr = matrix == DC_CSC_BT709 ? 0.2126 : 0.299, Kb = matrix == DC_CSC_BT709 ? 0.0722 : 0.114, Kg = 1.0 - Kr - Kb;
+    const double sy = range == DC_RANGE_FULL ? 1.0 : 255.0 / 219.0, sc = range == DC_RANGE_FULL ? 1.0 : 255.0 / 224.0;
+    y0 = range == DC_RANGE_FULL ? 0 : 16;
+    const double ky[3] = {Kr, Kg, Kb}, kb[3] = {-Kr, -Kg, 1.0 - Kb}, kr[3] = {1.0 - Kr, -Kg, -Kb};
+    for (int i = 0; i < 3; ++i) {
+      y[i] = (int)std::rint(65536.0 * ky[i] / sy);
+      cb[i] = (int)std::rint(65536.0 * kb[i] / (2.0 * (1.0 - Kb)) / sc);
+      cr[i] = (int)std::rint(65536.0 * kr[i] / (2.0 * (1.0 - Kr)) / sc);
+    }
+  }
+  // R, G, B -> Y | Cb << 8 | Cr << 16; the shift is arithmetic
+  unsigned operator()(int r, int g, int b) const {
+    const int Y = clip8(y0 + ((y[0] * r + y[1] * g + y[2] * b + 32768) >> 16));
+    const int Cb = clip8(128 + ((cb[0] * r + cb[1] * g + cb[2] * b + 32768) >> 16));
+    const int Cr = clip8(128 + ((cr[0] * r + cr[1] * g + cr[2] * b + 32768) >> 16));
+    return (unsigned)Y | (unsigned)Cb << 8 | (unsigned)Cr << 16;
+  }
+};
+// the overlay calls' device buffer, per device (draw.cpp): the caller holds the runtime lock, and every call waits for its work
+DevBuf& draw_buffer(int device);
+
 // ---- streams.cpp ------------------------------------------------------------------------------------
 std::vector<void*> executor_stream_pool(int device, size_t want);  // a COPY of the first `want` process-wide candidates
 void pool_stream_acquire(void* s);

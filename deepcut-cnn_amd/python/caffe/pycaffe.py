@@ -86,6 +86,17 @@ class DrawStyle(C.Structure):
                 ("untracked", C.c_ubyte * 3)]
 
 
+class HeatGeometry(C.Structure):
+    """dc_heat_geometry (include/deepcut_hip.h)."""
+    _fields_ = [("scale", C.c_double), ("origin_x", C.c_double), ("origin_y", C.c_double)]
+
+
+class HeatStyle(C.Structure):
+    """dc_heat_style (include/deepcut_hip.h)."""
+    _fields_ = [("n_joints", C.c_int), ("joints", C.c_void_p), ("mode", C.c_int), ("alpha", C.c_int), ("alpha_mode", C.c_int),
+                ("min_score", C.c_double), ("lut", C.c_void_p), ("palette", C.c_void_p), ("n_palette", C.c_int)]
+
+
 MAX_ASSEMBLE_DET, MAX_ASSEMBLE_PEOPLE = 64, 256  # dc_net_assemble_people's limits
 # Stage D of the people assembly (`Net.completion`, the `complete=` arguments).  PLACEHOLDERS, not tuned on real images: override them.
 COMPLETE_DEFAULTS = {"fill_threshold": 0.25, "fill_radius": 2, "min_support": 2}
@@ -394,6 +405,11 @@ def _load():
         "dc_dedupe_people": (ci, [C.POINTER(DedupeParams), ci, ci, ci] + [C.c_void_p] * 8),
         "dc_draw_people": (ci, [C.POINTER(DcFrame), ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, C.POINTER(DrawStyle), vp]),
         "dc_draw_limits": (ci, [C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]),
+        "dc_draw_heatmap": (ci, [C.POINTER(DcFrame), ci, ci, ci, ci, vp, ci, ci, ci, ci, C.POINTER(HeatGeometry), C.POINTER(HeatStyle), vp]),
+        "dc_net_draw_heatmap": (ci, [vp, C.POINTER(DcFrame), ci, ci, ci, ci, C.POINTER(HeatGeometry), C.POINTER(HeatStyle)]),
+        "dc_group_draw_heatmap": (ci, [vp, C.POINTER(DcFrame), ci, ci, ci, ci, vp, ci, C.c_double, C.c_double, C.POINTER(HeatStyle)]),
+        "dc_group_draw_heatmap_mirrored": (ci, [vp, C.POINTER(DcFrame), ci, ci, ci, ci, vp, ci, C.POINTER(FuseMirror), C.c_double, C.c_double,
+                                                C.POINTER(HeatStyle)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -1139,6 +1155,85 @@ def draw_people(frames, people, n_people=None, ids=None, cand=None, edges=None, 
                                None if stream is None else C.c_void_p(int(stream))))
 
 
+# ---- blending score maps into frames (dc_draw_heatmap; the rule: include/deepcut_hip.h — this project's own, the reference has none) ----
+# The colour ramp of mode "max" (R, G, B by v >> 4).  A PLACEHOLDER: a plain black - blue - cyan - green - yellow - red - white ramp in
+# six linear pieces, not tested for legibility on real video or for colour-blind readers; pass lut= for another.
+def _heat_ramp():
+    stops = ((0, 0, 0), (0, 0, 255), (0, 255, 255), (0, 255, 0), (255, 255, 0), (255, 0, 0), (255, 255, 255))
+    out = []
+    for i in range(256):
+        k, f = divmod(i * (len(stops) - 1), 255)
+        a, b = stops[min(k, len(stops) - 1)], stops[min(k + 1, len(stops) - 1)]
+        out.append(tuple((a[c] * (255 - f) + b[c] * f + 127) // 255 for c in range(3)))
+    return tuple(out)
+
+
+HEAT_LUT = _heat_ramp()
+_HEAT_MODES = {"max": 0, "joints": 1}  # DC_HEAT_MAX, DC_HEAT_BY_JOINT
+_HEAT_ALPHA_MODES = {"const": 0, "score": 1}  # DC_HEAT_ALPHA_CONST, DC_HEAT_ALPHA_SCORE
+
+
+def _heat_frames(frames):
+    """frames of `draw_heatmap` -> (dc_frame[nb], nb, h, w, is_device, what to keep alive)."""
+    fl = _frame_list(frames)
+    if fl is None:
+        if isinstance(frames, np.ndarray) and frames.ndim == 3:
+            fl = [Frame.bgr(frames)]
+        else:
+            raise ValueError("frames must be a caffe.Frame, a non-empty list of them, or a uint8 [H, W, 3] BGR array")
+    for i, f in enumerate(fl):
+        for a in f._keep:
+            if isinstance(a, np.ndarray) and not a.flags.writeable:
+                raise ValueError("frame %d: a host array that is drawn into must be writable" % i)
+    arr, h, w, is_device = _frame_array(fl)
+    return arr, len(fl), h, w, is_device, fl
+
+
+def _heat_style(channels, joints, mode, alpha, alpha_mode, min_score, lut, palette):
+    """-> (HeatStyle, the arrays it points into).  Only names and shapes are checked here; the values are the library's to refuse."""
+    if mode not in _HEAT_MODES:
+        raise ValueError("mode must be one of %s, got %r" % (sorted(_HEAT_MODES), mode))
+    if alpha_mode not in _HEAT_ALPHA_MODES:
+        raise ValueError("alpha_mode must be one of %s, got %r" % (sorted(_HEAT_ALPHA_MODES), alpha_mode))
+    j = np.ascontiguousarray(np.arange(channels) if joints is None else joints, dtype=np.int32).reshape(-1)
+    lt = np.ascontiguousarray(HEAT_LUT if lut is None else lut, dtype=np.uint8)
+    if lt.shape != (256, 3):
+        raise ValueError("lut must be [256, 3] R, G, B, got shape %s" % (lt.shape,))
+    pal = np.ascontiguousarray(DRAW_JOINT_COLORS if palette is None else palette, dtype=np.uint8)
+    if pal.ndim != 2 or pal.shape[1] != 3:
+        raise ValueError("palette must be [n, 3] R, G, B, got shape %s" % (pal.shape,))
+    st = HeatStyle()
+    st.n_joints, st.joints = int(j.shape[0]), j.ctypes.data if j.shape[0] else None
+    st.mode, st.alpha, st.alpha_mode, st.min_score = _HEAT_MODES[mode], int(alpha), _HEAT_ALPHA_MODES[alpha_mode], float(min_score)
+    st.lut, st.palette, st.n_palette = lt.ctypes.data, pal.ctypes.data if pal.shape[0] else None, int(pal.shape[0])
+    return st, (j, lt, pal)
+
+
+def draw_heatmap(frames, scores, scale, origin=(0.0, 0.0), joints=None, mode="max", alpha=128, alpha_mode="score", min_score=0.0, lut=None,
+                 palette=None, stream=None):
+    """A score map blended into frames IN PLACE on the device (dc_draw_heatmap; the rule — integer from the first quantisation on, this
+    project's own: the reference's demo never shows a map — is in include/deepcut_hip.h).  The stride-8 map is brought onto the pixel grid
+    bilinearly in 1/256 steps of 1/4096 scores.
+    frames: as `draw_people` takes them.  scores: float32 [C, Hm, Wm] (one frame) or [nb, C, Hm, Wm], a host array — `net.blobs["prob"].data`,
+    `NetGroup.fuse_maps(...)["prob"]` —, C <= 32.  scale: frame pixels x scale = network pixels (what the forward ran at), 1/64 .. 8;
+    origin: (x, y) in frame pixels of the map's pixel 0 (a crop's corner).
+    joints: the channels drawn, in order (None: all).  mode "max": the maximum over them, coloured by lut[v >> 4] ([256, 3] R, G, B; None =
+    HEAT_LUT, a PLACEHOLDER ramp); "joints": every channel in list order over the ones before it, the k-th with palette[k % len] (None =
+    DRAW_JOINT_COLORS).  alpha 0 .. 256 (256 = opaque), alpha_mode "const" or "score" (alpha times the score); only scores >= min_score
+    (0 .. 1) are blended.  stream: a HIP stream for device frames (None: the library's own).  The call returns when the blending is
+    complete.  Needs GPU mode."""
+    arr, nb, h, w, is_device, _keep = _heat_frames(frames)
+    s = np.ascontiguousarray(scores, dtype=np.float32)
+    if s.ndim == 3:
+        s = s[None]
+    if s.ndim != 4 or s.shape[0] != nb:
+        raise ValueError("scores must be [C, Hm, Wm] or [nb, C, Hm, Wm] with one map per frame: shape %s for %d frame(s)" % (s.shape, nb))
+    st, _arrays = _heat_style(s.shape[1], joints, mode, alpha, alpha_mode, min_score, lut, palette)
+    g = HeatGeometry(float(scale), float(origin[0]), float(origin[1]))
+    _check(_lib.dc_draw_heatmap(arr, nb, h, w, int(is_device), s.ctypes.data_as(C.c_void_p), 0, s.shape[1], s.shape[2], s.shape[3], C.byref(g),
+                                C.byref(st), None if stream is None else C.c_void_p(int(stream))))
+
+
 class _Completing(object):
     """`completion` and `dedupe` of Net and NetGroup (stages D and E of the people assembly, include/deepcut_hip.h): state of the object,
     read by every entry that assembles people.  `_set_completion` / `_get_completion` / `_set_dedupe` / `_get_dedupe` name the library
@@ -1795,6 +1890,16 @@ class Net(_Completing):
                                         counts.ctypes.data_as(C.c_void_p), dets.ctypes.data_as(C.c_void_p)))
         return counts, dets
 
+    def draw_heatmap(self, frames, scale=1.0, origin=(0.0, 0.0), joints=None, mode="max", alpha=128, alpha_mode="score", min_score=0.0,
+                     lut=None, palette=None):
+        """`prob` of the last forward blended into frames IN PLACE (dc_net_draw_heatmap): `caffe.draw_heatmap` on the map where it is on
+        the device, in the net's element type — no download, no layout pass.  One frame per image of the forward; scale: what the forward
+        ran at.  The other arguments as `caffe.draw_heatmap`.  Runs on the net's stream behind the forward and returns when complete."""
+        arr, nb, h, w, is_device, _keep = _heat_frames(frames)
+        st, _arrays = _heat_style(self.blobs["prob"].shape[1], joints, mode, alpha, alpha_mode, min_score, lut, palette)
+        g = HeatGeometry(float(scale), float(origin[0]), float(origin[1]))
+        _check(_lib.dc_net_draw_heatmap(self._h, arr, nb, h, w, int(is_device), C.byref(g), C.byref(st)))
+
     def decode_pairwise(self, detections, scale=1.0, mean=None, std=None):
         """detections: int [D, 3] (image, cell row, cell column) -> float64 [D, E, 2]: where every regression edge of
         next_pred puts the next joint, seen from each detection's cell (mean / std: [E, 2] de-normalisation)."""
@@ -2352,6 +2457,18 @@ class NetGroup(_Completing):
         _check(_lib.dc_group_detect_parts_mirrored(self._h, sc.ctypes.data_as(C.c_void_p), base, fm, float(threshold), int(radius), int(max_det),
                                                    counts.ctypes.data_as(C.c_void_p), dets.ctypes.data_as(C.c_void_p)))
         return counts, dets
+
+    def draw_heatmap(self, frames, scales, base=None, origin=(0.0, 0.0), joints=None, mode="max", alpha=128, alpha_mode="score",
+                     min_score=0.0, lut=None, palette=None, mirror=None, image_width=None, joint_mirror=None):
+        """`Net.draw_heatmap` on the FUSED `prob` of the members' last forwards (dc_group_draw_heatmap): `prob` alone is fused on member
+        `base`'s grid as `detect_parts` fuses it (base None: member 0) and blended at scales[base].  mirror / image_width / joint_mirror:
+        as `fuse_maps` (dc_group_draw_heatmap_mirrored; the fused map is already un-mirrored).  The other arguments as `caffe.draw_heatmap`."""
+        sc, base = self._scales(scales, 0 if base is None else base)
+        arr, nb, h, w, is_device, _keep = _heat_frames(frames)
+        st, _arrays = _heat_style(self.nets[0].blobs["prob"].shape[1], joints, mode, alpha, alpha_mode, min_score, lut, palette)
+        fm, _keep2 = self._mirror(mirror, image_width, joint_mirror, None)
+        _check(_lib.dc_group_draw_heatmap_mirrored(self._h, arr, nb, h, w, int(is_device), sc.ctypes.data_as(C.c_void_p), base, fm,
+                                                   float(origin[0]), float(origin[1]), C.byref(st)))
 
     def decode_pose(self, scales, base=0, mirror=None, image_width=None, joint_mirror=None):
         """The single-person pose of every image of the members' last forwards from the FUSED maps (dc_group_decode_pose): `prob` and

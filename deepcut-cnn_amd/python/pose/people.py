@@ -103,6 +103,18 @@ def draw_people(frame, people, ids=None, **style):
     _caffe.draw_people(frame, _np.asarray(people, _np.float64), ids=ids, **style)
 
 
+def draw_heatmap(frame, scores, scale, **style):
+    """Blend a score map into a frame IN PLACE on the device: `caffe.draw_heatmap` with the demo's joint colours
+    (`caffe.DRAW_JOINT_COLORS`) for `palette` unless the caller names another.  frame: a writable uint8 [H, W, 3] BGR array or a
+    `caffe.Frame`; scores: float32 [J, Hm, Wm] (`net.blobs["prob"].data[0]`); scale: what the forward ran at; style: what
+    `caffe.draw_heatmap` takes (origin, joints, mode, alpha, alpha_mode, min_score, lut, palette, stream).  PARITY UNPINNED BY THE
+    REFERENCE: the blending rule is this project's own (include/deepcut_hip.h, dc_draw_heatmap)."""
+    import caffe as _caffe
+
+    style.setdefault("palette", _caffe.DRAW_JOINT_COLORS)
+    _caffe.draw_heatmap(frame, _np.asarray(scores, _np.float32), scale, **style)
+
+
 def _draw_style(draw):
     """draw= of `track_people` / `VideoPipeline` -> None (off) or the style dict."""
     if draw is None or draw is False:

@@ -37,12 +37,15 @@ def draw_disc(image, cx, cy, radius, color):
               help="none: one forward per scale (default); exact / reference: see pose.estimate_pose")
 @click.option("--skeleton", type=click.BOOL, is_flag=True, default=False,
               help="draw the overlay on the device: joints and the MPII limbs, coloured by joint (pose.draw_people); default: discs only")
+@click.option("--heatmap", type=click.Choice(["max", "joints"]), default=None,
+              help="also write <out>_heat.png: the score maps of one forward at the first scale blended over the image on the device "
+                   "(Net.draw_heatmap) — max: the maximum over the joints through caffe.HEAT_LUT; joints: every joint in its colour; default: off")
 @click.option("--model_def", default=None,
               help="model definition (.prototxt).  Default: the definition deepcut_tools.deepercut_prototxt(152) generates, which is "
                    "layer-for-layer the reference's models/deepercut/ResNet-152.prototxt (that directory is not part of this repository)")
 @click.option("--model_bin", default=None, required=True,
               help="trained weights (.caffemodel / .h5): the reference fetches them with models/deepercut/download_models.sh; not shipped here")
-def predict_pose_from(image_name, out_name, scales, visualize, folder_image_suffix, use_cpu, gpu, tiling, skeleton, model_def, model_bin):
+def predict_pose_from(image_name, out_name, scales, visualize, folder_image_suffix, use_cpu, gpu, tiling, skeleton, heatmap, model_def, model_bin):
     import caffe
     from PIL import Image
 
@@ -90,6 +93,14 @@ def predict_pose_from(image_name, out_name, scales, visualize, folder_image_suff
             for j in range(14):
                 draw_disc(vis, pose[0, j], pose[1, j], 8, COLORS[j])
             Image.fromarray(vis).save(target + "_vis.png")
+        if heatmap is not None:
+            from pose.estimate_pose import _get_model
+
+            net = _get_model(model_def, model_bin)
+            bgr = np.ascontiguousarray(img)
+            net.forward_images(bgr, scales[0], want=(), pose=False)
+            net.draw_heatmap(bgr, scales[0], mode=heatmap, alpha=192 if heatmap == "max" else 256, min_score=0.1)
+            Image.fromarray(np.ascontiguousarray(bgr[:, :, ::-1])).save(target + "_heat.png")
 
 
 if __name__ == "__main__":

@@ -1160,6 +1160,79 @@ int dc_draw_people(const dc_frame* frames, int nb, int height, int width, int is
                    const dc_draw_style* style, void* stream);
 int dc_draw_limits(int* tile_w, int* tile_h, int* chunk);
 
+/* ---- blending score maps into video frames: a stride-8 map brought onto the pixel grid of BGR24 or NV12 frames, on the device ------
+ * PARITY UNPINNED BY THE REFERENCE: the reference's demo (python/pose/pose_demo.py) draws 14 numpy circles and never shows a map.  THE
+ * RULE below is this project's own, like the drawing rule above.  It is integer from the first quantisation on, so every path gives the
+ * same bytes (tests/heat_ref.py restates it in numpy; the device is held to that byte for byte, pitch padding included).
+ *
+ * Input: nb frames as dc_draw_people takes them, a score map S[nb][C][Hm][Wm] (C in [1, 32]; cell (row, col) stands at network pixel
+ *   (8 col + 4, 8 row + 4): the stride is 8, as everywhere on the pose path), a geometry — scale: frame pixels x scale = network pixels,
+ *   finite, in [1/64, 8]; origin_x, origin_y: the frame pixel coordinates the map's pixel 0 lies at, finite, |.| <= 32768 — and a style.
+ * Quantisation, the only floating-point step: a cell's value is widened to float32 (exact for float16 and bfloat16), then
+ *   q = (int)rintf(fminf(fmaxf(s, 0), 1) * 4096.0f), NaN counting as 0: q in [0, 4096].  Every operation is exact or correctly rounded.
+ * Sample positions, on the host, in double, operation by operation with no fused multiply-add.  Luma column x:
+ *   u = ((x + 0.5 - origin_x) * scale - 4.0) / 8.0   (the inverse of x = (8 col + 4) / scale, the pixel's centre at x + 0.5 — the
+ *   drawing rule's 16 px + 8), t = (long)rint(256.0 * u) clamped to [0, 256 (Wm - 1)], i0 = t >> 8, f = t & 255, i1 = min(i0 + 1, Wm - 1).
+ *   Rows likewise with origin_y and Hm.  NV12: the chroma sample of block (bx, by) has tables of its own, evaluated at the block's centre
+ *   — x + 0.5 replaced by 2 bx + 1, y + 0.5 by 2 by + 1 —, at an odd right or bottom edge too.
+ * Interpolation, int32, per drawn channel: top = q00 (256 - fx) + q01 fx, bot = q10 (256 - fx) + q11 fx,
+ *   v = (top (256 - fy) + bot fy + 32768) >> 16: v in [0, 4096], the largest intermediate is 2^28.
+ * What is blended: vmin = (int)rint(4096 min_score); A(v) = alpha (DC_HEAT_ALPHA_CONST) or (alpha v + 2048) >> 12 (DC_HEAT_ALPHA_SCORE);
+ *   the blend is the drawing rule's, out = (c A + dst (256 - A) + 128) >> 8.
+ *   DC_HEAT_MAX: v = the maximum over the drawn channels of their v (interpolate first, then the maximum); if v >= vmin and A(v) > 0, ONE
+ *     blend with colour lut[min(255, v >> 4)].  lut is [256][3] R, G, B and the caller's: the library has none of its own (the Python
+ *     binding's caffe.HEAT_LUT is a PLACEHOLDER ramp, not tested for legibility).
+ *   DC_HEAT_BY_JOINT: the drawn channels in list order; each one with v_k >= vmin and A(v_k) > 0 is blended with palette[k % n_palette],
+ *     k its place in the list (not its channel).  Later channels go over earlier ones: the order is visible, and it is kept.
+ * BGR24: the pixel's three channels are blended.  NV12: luma is blended per pixel with the colour's Y; the chroma sample is blended by
+ *   the same procedure run once at the block centre, with the colour's Cb and Cr.  Colours go R, G, B -> Y, Cb, Cr once, on the host,
+ *   by the forward colour rule stated under dc_draw_people.
+ * Untouched bytes: a byte is written only if a blend was executed for it; pitch padding is never written; a call whose style cannot
+ *   blend anything (alpha = 0) launches nothing and writes nothing.
+ *
+ * dc_draw_heatmap: stand-alone like dc_dedupe_people — `map` is float32 NCHW [nb][C][Hm][Wm] in host (map_is_device = 0) or device
+ *   memory.  The call returns when the blending is complete: on `stream`, or on the library's utility stream when it is NULL; host
+ *   frames are staged up without their padding and copied back with 2-D copies.
+ * dc_net_draw_heatmap: `prob` of the net's last forward, read where it is in the net's element type (float32, float16, bfloat16; the
+ *   channel views of merged heads included), on the net's stream behind the forward.  DC_EINVAL when the forward's batch is not nb;
+ *   what reading `prob` itself refuses (no forward yet: DC_EINVAL; `prob` left out of the plan: DC_EUNSUP) is passed on.
+ * dc_group_draw_heatmap(_mirrored): `prob` alone fused exactly as dc_group_detect_parts(_mirrored) fuses it, drawn at scales[base]
+ *   (which must lie in the geometry's range); geometry->scale is not read.  The mirrored form costs no kernel of its own: the fused map
+ *   is already un-mirrored.
+ * Errors, before any device work: DC_EINVAL naming the field for what dc_draw_people refuses of nb, height, width and the frames; C
+ *   outside [1, 32], Hm or Wm outside [1, 65536]; a NULL map, geometry or style; scale, origin_x, origin_y outside the ranges above or
+ *   not finite; n_joints outside [1, 32], NULL joints, joints[k] outside [0, C); an unknown mode or alpha_mode; alpha outside [0, 256];
+ *   min_score not finite or outside [0, 1]; DC_HEAT_MAX with a NULL lut; DC_HEAT_BY_JOINT with a NULL palette or n_palette outside
+ *   [1, 256].  Then DC_ENOCPU in CPU mode (there is no CPU path).
+ * Not built, on purpose: the box entry's per-box geometry (one geometry per call); an entry on VideoPipeline / dc_net_track_frames_async
+ *   (the net's maps belong to a later frame by the time a result is handed back); the loc_pred / next_pred vector fields; anti-aliasing
+ *   or float blending (either would end byte equality).                                                                          */
+#define DC_HEAT_MAX         0
+#define DC_HEAT_BY_JOINT    1
+#define DC_HEAT_ALPHA_CONST 0
+#define DC_HEAT_ALPHA_SCORE 1
+typedef struct dc_heat_geometry {
+  double scale;                 /* frame pixels x scale = network pixels; [1/64, 8] */
+  double origin_x, origin_y;    /* frame pixels, |.| <= 32768; 0 = the map's image is the frame */
+} dc_heat_geometry;
+typedef struct dc_heat_style {
+  int n_joints; const int* joints;          /* the channels drawn, in order; 1..32 entries in [0, C), repeats allowed */
+  int mode;                                 /* DC_HEAT_MAX, DC_HEAT_BY_JOINT */
+  int alpha, alpha_mode;                    /* 0..256; DC_HEAT_ALPHA_CONST, DC_HEAT_ALPHA_SCORE */
+  double min_score;                         /* finite, 0..1 */
+  const unsigned char* lut;                 /* [256][3] R, G, B: DC_HEAT_MAX */
+  const unsigned char* palette; int n_palette;  /* [n_palette][3] R, G, B, 1..256: DC_HEAT_BY_JOINT */
+} dc_heat_style;
+int dc_draw_heatmap(const dc_frame* frames, int nb, int height, int width, int is_device, const float* map, int map_is_device, int C,
+                    int Hm, int Wm, const dc_heat_geometry* geometry, const dc_heat_style* style, void* stream);
+int dc_net_draw_heatmap(dc_net* net, const dc_frame* frames, int nb, int height, int width, int is_device,
+                        const dc_heat_geometry* geometry, const dc_heat_style* style);
+int dc_group_draw_heatmap(dc_group* group, const dc_frame* frames, int nb, int height, int width, int is_device, const double* scales,
+                          int base, double origin_x, double origin_y, const dc_heat_style* style);
+int dc_group_draw_heatmap_mirrored(dc_group* group, const dc_frame* frames, int nb, int height, int width, int is_device,
+                                   const double* scales, int base, const dc_fuse_mirror* fm, double origin_x, double origin_y,
+                                   const dc_heat_style* style);
+
 /* ---- in-process multi-GPU forward (SURVEY 8(b)'s dc_forward_batch) -------------------------------------------------------
  * A communicator over `nexec` executors: executor k runs on devices[k] (NULL: k modulo the visible devices) on a host thread of its
  * own (mode and device are per thread, src/caffe/common.cpp:13-20).  transport: how the maps travel to the root executor's device —
