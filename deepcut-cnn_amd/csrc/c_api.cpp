@@ -1136,6 +1136,14 @@ int dc_draw_limits(int* tile_w, int* tile_h, int* chunk) {
   draw_limits(tile_w, tile_h, chunk);
   return DC_OK;
 }
+// the redaction (redact.cpp); a null style is refused there, after the frames' own checks, naming the field
+int dc_redact_people(const dc_frame* frames, int nb, int height, int width, int is_device, int P, int J, const int* n_people,
+                     const double* people, const unsigned char* select, const dc_redact_style* style, int* redacted, void* stream) {
+  REQUIRE(frames);
+  REQUIRE(n_people);
+  REQUIRE(people);
+  return guard([&] { redact_people(frames, nb, height, width, is_device != 0, P, J, n_people, people, select, style, redacted, stream); });
+}
 // the score-map overlay (heat.cpp); null geometry / style / map are refused there, after the frames' own checks, naming the field
 int dc_draw_heatmap(const dc_frame* frames, int nb, int height, int width, int is_device, const float* map, int map_is_device, int C, int Hm,
                     int Wm, const dc_heat_geometry* geometry, const dc_heat_style* style, void* stream) {

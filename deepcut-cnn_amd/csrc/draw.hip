@@ -9,6 +9,7 @@
 // into LDS and every lane reads the same address (a broadcast, no bank conflict).  Bytes no primitive covers are never stored.
 #include <hip/hip_runtime.h>
 
+#include "draw_cover.h"
 #include "kernels.h"
 
 namespace dc {
@@ -18,22 +19,6 @@ constexpr int kFmtBgr = 0, kFmtNv12 = 1;  // DC_PIX_BGR24, DC_PIX_NV12
 constexpr int kBlocksX = kDrawTileW / 2, kBlocksY = kDrawTileH / 2;
 static_assert(kBlocksX * kBlocksY == 256, "one thread per 2 x 2 block of the tile");
 static_assert(kDrawChunk <= 256, "a chunk is staged by one pass of the workgroup");
-
-// The coverage rule, in int64.  Coordinates are at most 2^19 units and a pixel centre at most 2^18, so w, v are below 2^20 and d below
-// 2^20 + 1 per component: w.w, w.d and L = d.d stay below 2^42, |cross| below 2^42, and r16^2 L <= 2^20 * 2^41 = 2^61.  |cross| >= 2^31
-// means cross^2 >= 2^62 > r16^2 L — outside —, so the square is formed only below 2^62: every product fits int64.
-__device__ __forceinline__ bool draw_covers(const DrawPrim& p, int px, int py) {
-  const long long wx = px - p.ax, wy = py - p.ay, r2 = (long long)p.r16 * p.r16;
-  if (wx * wx + wy * wy <= r2) return true;
-  if (!p.capsule) return false;
-  const long long vx = px - p.bx, vy = py - p.by;
-  if (vx * vx + vy * vy <= r2) return true;
-  const long long dx = p.bx - p.ax, dy = p.by - p.ay, L = dx * dx + dy * dy, dot = wx * dx + wy * dy;
-  if (!(dot > 0 && dot < L)) return false;
-  const long long cross = wx * dy - wy * dx;
-  if (cross <= -(1LL << 31) || cross >= (1LL << 31)) return false;
-  return cross * cross <= r2 * L;
-}
 
 __device__ __forceinline__ int draw_blend(int c, int dst, int a) { return (c * a + dst * (256 - a) + 128) >> 8; }
 
@@ -69,10 +54,7 @@ __global__ __launch_bounds__(256) void draw_kernel(const DrawPlanes* __restrict_
     if (!n_in) continue;
     for (int i = 0; i < m; ++i) {
       const DrawPrim p = sp[i];
-      // outside the box of the ends grown by the radius: outside the primitive (every covered point is within r16 of the segment)
-      if (cx + 16 < min(p.ax, p.bx) - p.r16 || cx > max(p.ax, p.bx) + p.r16 || cy + 16 < min(p.ay, p.by) - p.r16 ||
-          cy > max(p.ay, p.by) + p.r16)
-        continue;
+      if (draw_block_outside(p, cx, cy)) continue;
       const int c0 = p.colour & 255, c1 = (p.colour >> 8) & 255, c2 = (p.colour >> 16) & 255;
       int k = 0;
       for (int q = 0; q < 4; ++q) {

@@ -451,6 +451,16 @@ struct DrawPlanes {
 int launch_draw(int format, const DrawPlanes* frames, int height, int width, const DrawTile* tiles, int n_tiles, const int* index,
                 const DrawPrim* prims, void* stream);
 
+// Redaction (redact.hip; the rule: include/deepcut_hip.h, dc_redact_people — this project's own).  The host (redact.cpp) turns people
+// into DrawPrims (alpha and colour unused; a head disc's r16 may reach 16384) and bins them into the drawing kernel's tiles; one
+// workgroup redacts one non-empty tile, one thread one 2 x 2 pixel block (draw_kernel's ownership), in three phases between barriers:
+// which B x B blocks hold a covered pixel centre, the blocks' sums in LDS (MOSAIC), the stores.
+constexpr int kRedactMosaic = 0, kRedactFill = 1;  // DC_REDACT_MOSAIC, DC_REDACT_FILL
+// format: DC_PIX_BGR24 or DC_PIX_NV12; effect: kRedactMosaic or kRedactFill; block: 2, 4, 8, 16 or 32; fill: bytes as DrawPrim::colour.
+// Grid = n_tiles (> 0).  Every pointer is device memory.
+int launch_redact(int format, int effect, int block, unsigned fill, const DrawPlanes* frames, int height, int width, const DrawTile* tiles,
+                  int n_tiles, const int* index, const DrawPrim* prims, void* stream);
+
 // Score-map overlay (heat.hip; the rule: include/deepcut_hip.h, dc_draw_heatmap — this project's own).  The host (heat.cpp) computes
 // the per-axis sample tables t = rint(256 u), clamped, and converts the colours; one workgroup blends one kDrawTileW x kDrawTileH pixel
 // tile of one frame, one thread one 2 x 2 pixel block (draw_kernel's ownership), after staging the patch of map cells the tile's tables

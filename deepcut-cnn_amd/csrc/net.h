@@ -27,6 +27,7 @@ struct dc_frame;  // include/deepcut_hip.h: one video frame (planes, pitches, fo
 struct dc_complete_params;  // include/deepcut_hip.h: stage D of the people assembly
 struct dc_dedupe_params;    // include/deepcut_hip.h: stage E of the people assembly
 struct dc_draw_style;       // include/deepcut_hip.h: the skeleton overlay
+struct dc_redact_style;     // include/deepcut_hip.h: the redaction
 struct dc_heat_geometry;    // include/deepcut_hip.h: the score-map overlay
 struct dc_heat_style;
 struct dc_track_smooth_params;  // include/deepcut_hip.h: step 8 of the tracker's rule
@@ -299,6 +300,9 @@ void dedupe_people(const dc_dedupe_params* params, int nb, int P, int J, const i
 void draw_people(const dc_frame* frames, int nb, int h, int w, bool is_device, int P, int J, const int* n_people, const double* people,
                  const int* cand, const long long* ids, const dc_draw_style* style, void* stream);
 void draw_limits(int* tile_w, int* tile_h, int* chunk);
+// dc_redact_people (redact.cpp): regions derived from people's joints replaced by a mosaic or a colour, in place on the device, synchronous
+void redact_people(const dc_frame* frames, int nb, int h, int w, bool is_device, int P, int J, const int* n_people, const double* people,
+                   const unsigned char* select, const dc_redact_style* style, int* redacted, void* stream);
 // dc_draw_heatmap (heat.cpp): a float32 NCHW score map, host or device, blended into frames in place on the device, synchronous
 void draw_heatmap(const dc_frame* frames, int nb, int h, int w, bool is_device, const float* map, bool map_is_device, int C, int Hm, int Wm,
                   const dc_heat_geometry* geometry, const dc_heat_style* style, void* stream);

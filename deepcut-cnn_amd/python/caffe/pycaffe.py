@@ -86,6 +86,13 @@ class DrawStyle(C.Structure):
                 ("untracked", C.c_ubyte * 3)]
 
 
+class RedactStyle(C.Structure):
+    """dc_redact_style (include/deepcut_hip.h)."""
+    _fields_ = [("region", C.c_int), ("head_a", C.c_int), ("head_b", C.c_int), ("head_scale", C.c_double), ("body_scale", C.c_double),
+                ("min_radius", C.c_double), ("max_radius", C.c_double), ("min_score", C.c_double), ("n_edges", C.c_int), ("edges", C.c_void_p),
+                ("effect", C.c_int), ("block", C.c_int), ("fill", C.c_ubyte * 3)]
+
+
 class HeatGeometry(C.Structure):
     """dc_heat_geometry (include/deepcut_hip.h)."""
     _fields_ = [("scale", C.c_double), ("origin_x", C.c_double), ("origin_y", C.c_double)]
@@ -405,6 +412,7 @@ def _load():
         "dc_dedupe_people": (ci, [C.POINTER(DedupeParams), ci, ci, ci] + [C.c_void_p] * 8),
         "dc_draw_people": (ci, [C.POINTER(DcFrame), ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, C.POINTER(DrawStyle), vp]),
         "dc_draw_limits": (ci, [C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]),
+        "dc_redact_people": (ci, [C.POINTER(DcFrame), ci, ci, ci, ci, ci, ci, vp, vp, vp, C.POINTER(RedactStyle), vp, vp]),
         "dc_draw_heatmap": (ci, [C.POINTER(DcFrame), ci, ci, ci, ci, vp, ci, ci, ci, ci, C.POINTER(HeatGeometry), C.POINTER(HeatStyle), vp]),
         "dc_net_draw_heatmap": (ci, [vp, C.POINTER(DcFrame), ci, ci, ci, ci, C.POINTER(HeatGeometry), C.POINTER(HeatStyle)]),
         "dc_group_draw_heatmap": (ci, [vp, C.POINTER(DcFrame), ci, ci, ci, ci, vp, ci, C.c_double, C.c_double, C.POINTER(HeatStyle)]),
@@ -1063,50 +1071,29 @@ def draw_coefficients(matrix="bt601", range="limited"):
             tuple(r(65536.0 * k / (2.0 * (1.0 - kr)) / sc) for k in (1.0 - kr, -kg, -kb)), 0 if full else 16)
 
 
-def draw_people(frames, people, n_people=None, ids=None, cand=None, edges=None, joint_radius=4.0, limb_radius=2.0, alpha=256, alpha_filled=128,
-                min_score=0.0, color="id", palette=None, untracked=(128, 128, 128), stream=None):
-    """Skeletons blended into frames IN PLACE on the device (dc_draw_people; the rule — integer only, this project's own: the reference
-    draws with matplotlib and states none — is in include/deepcut_hip.h): joints as discs of joint_radius pixels, the limbs `edges`
-    ([E, 2] joints, None = joints only) as capsules of limb_radius, people in index order, of a person the limbs and then the joints.
-    frames: a `Frame` (NV12 or BGR24, host or device), a list of them (one size, format, matrix and range), or a uint8 [H, W, 3] BGR
-    array, wrapped like `Frame.bgr`.  Host arrays are drawn in place and must be writable (ValueError otherwise).
-    people: float64 [m, J, 3] (one frame) or [nb, P, J, 3] with n_people [nb], or a list of nb arrays [m_b, J, 3], as `dedupe_people`
-    takes them; cand: int32 of the same leading shape or None — joints it marks filled (-2) or bridged (-3), and limbs that end in one,
-    are blended with alpha_filled instead of alpha (both 0..256, 256 = opaque); ids: int64 [nb, P] / [m] or None.
-    color: "id" — palette[id % len] (the person's index without ids; `untracked` for id < 0), palette None = DRAW_ID_COLORS (a
-    PLACEHOLDER) — or "joint" — palette[j % len] for joint j and for a limb ending in j, None = DRAW_JOINT_COLORS.  Colours are R, G, B.
-    stream: a HIP stream for device frames (None: the library's own).  The call returns when the drawing is complete.  Needs GPU mode."""
-    fl = _frame_list(frames)
-    if fl is None:
-        if isinstance(frames, np.ndarray) and frames.ndim == 3:
-            fl = [Frame.bgr(frames)]
-        else:
-            raise ValueError("frames must be a caffe.Frame, a non-empty list of them, or a uint8 [H, W, 3] BGR array")
-    for i, f in enumerate(fl):
-        for a in f._keep:
-            if isinstance(a, np.ndarray) and not a.flags.writeable:
-                raise ValueError("frame %d: a host array that is drawn into must be writable" % i)
-    arr, h, w, is_device = _frame_array(fl)
-    nb = len(fl)
+def _per_image(v, dtype, tail):
+    """v -> [nb, P] + tail, from the [nb, P, ...] array, the single image's [m, ...] array or a list of nb arrays [m_b, ...]."""
+    if not isinstance(v, np.ndarray):
+        try:  # a list of numbers or of equal arrays is the array itself; a ragged one stays a list of per-image arrays
+            a = np.asarray(v, dtype)
+            v = a if a.ndim in (1 + len(tail), 2 + len(tail)) else v
+        except ValueError:
+            pass
+    if isinstance(v, np.ndarray) and v.ndim == 2 + len(tail):
+        return np.ascontiguousarray(v, dtype=dtype)
+    if isinstance(v, np.ndarray) and v.ndim == 1 + len(tail):
+        v = [v]
+    rows = [np.asarray(a, dtype).reshape((-1,) + tail) for a in v]
+    out = np.zeros((len(rows), max([1] + [a.shape[0] for a in rows])) + tail, dtype)
+    for b, a in enumerate(rows):
+        out[b, :a.shape[0]] = a
+    return out
 
-    def per_image(v, dtype, tail):
-        """v -> [nb, P] + tail, from the [nb, P, ...] array, the single image's [m, ...] array or a list of nb arrays [m_b, ...]."""
-        if not isinstance(v, np.ndarray):
-            try:  # a list of numbers or of equal arrays is the array itself; a ragged one stays a list of per-image arrays
-                a = np.asarray(v, dtype)
-                v = a if a.ndim in (1 + len(tail), 2 + len(tail)) else v
-            except ValueError:
-                pass
-        if isinstance(v, np.ndarray) and v.ndim == 2 + len(tail):
-            return np.ascontiguousarray(v, dtype=dtype)
-        if isinstance(v, np.ndarray) and v.ndim == 1 + len(tail):
-            v = [v]
-        rows = [np.asarray(a, dtype).reshape((-1,) + tail) for a in v]
-        out = np.zeros((len(rows), max([1] + [a.shape[0] for a in rows])) + tail, dtype)
-        for b, a in enumerate(rows):
-            out[b, :a.shape[0]] = a
-        return out
 
+def _frames_and_people(frames, people, n_people):
+    """What `draw_people` and `redact_people` take as frames and people -> (dc_frame[nb], nb, h, w, is_device, what to keep alive,
+    people float64 [nb, P, J, 3], n_people int32 [nb], P, J)."""
+    arr, nb, h, w, is_device, keep = _heat_frames(frames)
     if isinstance(people, np.ndarray) and people.ndim in (3, 4):
         if people.shape[-1] != 3:
             raise ValueError("people must be [m, J, 3] or [nb, P, J, 3] (x, y, score), got shape %s" % (people.shape,))
@@ -1121,17 +1108,34 @@ def draw_people(frames, people, n_people=None, ids=None, cand=None, edges=None, 
         if n_people is None:
             n_people = [a.shape[0] for a in rows]
         people = rows
-    ppl = per_image(people, np.float64, (j, 3))
+    ppl = _per_image(people, np.float64, (j, 3))
     n = np.ascontiguousarray(n_people, dtype=np.int32).reshape(-1)
     if ppl.shape[0] != nb or n.shape[0] != nb:
         raise ValueError("people and n_people must hold one entry per frame: %d and %d for %d frames" % (ppl.shape[0], n.shape[0], nb))
     p = int(ppl.shape[1])
     if p < 1:
         ppl, p = np.zeros((nb, 1, j, 3), np.float64), 1
-    cnd = None if cand is None else per_image(cand, np.int32, (j,))
+    return arr, nb, h, w, is_device, keep, ppl, n, p, j
+
+
+def draw_people(frames, people, n_people=None, ids=None, cand=None, edges=None, joint_radius=4.0, limb_radius=2.0, alpha=256, alpha_filled=128,
+                min_score=0.0, color="id", palette=None, untracked=(128, 128, 128), stream=None):
+    """Skeletons blended into frames IN PLACE on the device (dc_draw_people; the rule — integer only, this project's own: the reference
+    draws with matplotlib and states none — is in include/deepcut_hip.h): joints as discs of joint_radius pixels, the limbs `edges`
+    ([E, 2] joints, None = joints only) as capsules of limb_radius, people in index order, of a person the limbs and then the joints.
+    frames: a `Frame` (NV12 or BGR24, host or device), a list of them (one size, format, matrix and range), or a uint8 [H, W, 3] BGR
+    array, wrapped like `Frame.bgr`.  Host arrays are drawn in place and must be writable (ValueError otherwise).
+    people: float64 [m, J, 3] (one frame) or [nb, P, J, 3] with n_people [nb], or a list of nb arrays [m_b, J, 3], as `dedupe_people`
+    takes them; cand: int32 of the same leading shape or None — joints it marks filled (-2) or bridged (-3), and limbs that end in one,
+    are blended with alpha_filled instead of alpha (both 0..256, 256 = opaque); ids: int64 [nb, P] / [m] or None.
+    color: "id" — palette[id % len] (the person's index without ids; `untracked` for id < 0), palette None = DRAW_ID_COLORS (a
+    PLACEHOLDER) — or "joint" — palette[j % len] for joint j and for a limb ending in j, None = DRAW_JOINT_COLORS.  Colours are R, G, B.
+    stream: a HIP stream for device frames (None: the library's own).  The call returns when the drawing is complete.  Needs GPU mode."""
+    arr, nb, h, w, is_device, _keep, ppl, n, p, j = _frames_and_people(frames, people, n_people)
+    cnd = None if cand is None else _per_image(cand, np.int32, (j,))
     if cnd is not None and cnd.shape != ppl.shape[:3]:
         raise ValueError("cand must be %s like people, got shape %s" % (ppl.shape[:3], cnd.shape))
-    idv = None if ids is None else per_image(ids, np.int64, ())
+    idv = None if ids is None else _per_image(ids, np.int64, ())
     if idv is not None and idv.shape != ppl.shape[:2]:
         raise ValueError("ids must be %s like people, got shape %s" % (ppl.shape[:2], idv.shape))
     if color not in _DRAW_MODES:
@@ -1153,6 +1157,83 @@ def draw_people(frames, people, n_people=None, ids=None, cand=None, edges=None, 
     ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
     _check(_lib.dc_draw_people(arr, nb, h, w, int(is_device), p, j, ptr(n), ptr(ppl), ptr(cnd), ptr(idv), C.byref(st),
                                None if stream is None else C.c_void_p(int(stream))))
+
+
+# ---- redacting people in frames (dc_redact_people; the rule: include/deepcut_hip.h — this project's own, the reference has none) -------
+# PLACEHOLDERS, NOT TUNED ON REAL VIDEO: override them.  The head disc's radius is head_scale times the distance neck - head top, a body
+# primitive's body_scale times the larger side of the person's bounding box; both are kept within [min_radius, max_radius] pixels (the
+# body's within 64 pixels as well).
+REDACT_DEFAULTS = {"head_scale": 0.75, "body_scale": 0.06, "min_radius": 4.0, "max_radius": 256.0}
+_REDACT_REGIONS = {"head": 0, "body": 1, "head_or_body": 2}  # DC_REDACT_HEAD, DC_REDACT_BODY, DC_REDACT_HEAD_OR_BODY
+_REDACT_EFFECTS = {"mosaic": 0, "fill": 1}  # DC_REDACT_MOSAIC, DC_REDACT_FILL
+
+
+def redact_select(ids, only_ids=None, keep_ids=None, select=None):
+    """-> uint8 array shaped like `ids` (or None: everyone): who `redact_people` redacts.  only_ids: only the people with one of these
+    ids; keep_ids: everybody but the people with one of these ids (they stay visible); select: a mask of the caller's, combined with
+    the two by AND.  only_ids / keep_ids need `ids`."""
+    if only_ids is None and keep_ids is None:
+        return None if select is None else (np.asarray(select) != 0).astype(np.uint8)
+    if ids is None:
+        raise ValueError("only_ids / keep_ids choose people by id: ids is needed")
+    ids = np.asarray(ids, np.int64)
+    sel = np.ones(ids.shape, bool) if select is None else np.asarray(select) != 0
+    if sel.shape != ids.shape:
+        raise ValueError("select must be %s like ids, got shape %s" % (ids.shape, sel.shape))
+    if only_ids is not None:
+        sel = sel & np.isin(ids, np.asarray(list(only_ids), np.int64))
+    if keep_ids is not None:
+        sel = sel & ~np.isin(ids, np.asarray(list(keep_ids), np.int64))
+    return sel.astype(np.uint8)
+
+
+def redact_people(frames, people, n_people=None, select=None, ids=None, only_ids=None, keep_ids=None, region="head", head=None, edges=None,
+                  head_scale=REDACT_DEFAULTS["head_scale"], body_scale=REDACT_DEFAULTS["body_scale"], min_radius=REDACT_DEFAULTS["min_radius"],
+                  max_radius=REDACT_DEFAULTS["max_radius"], min_score=0.0, effect="mosaic", block=8, fill=(0, 0, 0), stream=None):
+    """Regions derived from people's joints replaced by a mosaic or a solid colour, IN PLACE on the device (dc_redact_people; the rule —
+    integer only, this project's own: the reference has nothing of the kind — is in include/deepcut_hip.h).  frames and people /
+    n_people: as `draw_people` takes them.
+    region: "head" — a disc around the middle of the joint pair head = (neck, head top), of radius head_scale times their distance;
+    "body" — that disc, the limbs `edges` ([E, 2] joints, None = none) as capsules and every joint as a disc, of radius body_scale times
+    the larger side of the person's bounding box (64 pixels at the most); "head_or_body" — the head disc where the pair is there, else
+    the body.  Radii are kept within [min_radius, max_radius] pixels.  The scale and radius defaults (REDACT_DEFAULTS) are PLACEHOLDERS,
+    not tuned on real video.  Only joints with score > min_score count.
+    effect: "mosaic" — every block x block pixel block (2, 4, 8, 16 or 32; the grid starts at pixel (0, 0)) that holds a covered pixel
+    becomes its mean — or "fill" — it becomes `fill` (R, G, B).  A mosaic with small blocks is NOT a privacy guarantee.
+    Who: everyone, or the people `select` (like ids, non-zero = redact) marks; only_ids / keep_ids (with ids: int64 [nb, P] / [m]) choose
+    by id — only these, or everybody but these (`redact_select`).
+    -> `redacted`, int32 shaped like ids ([m] for one frame's [m, J, 3], else [nb, P]): 1 where a region was made for the person.  A
+    person whose head pair is not there is NOT redacted by region "head": look at what comes back.
+    stream: a HIP stream for device frames (None: the library's own).  The call returns when the redaction is complete.  Needs GPU mode."""
+    single = isinstance(people, np.ndarray) and people.ndim == 3
+    arr, nb, h, w, is_device, _keep, ppl, n, p, j = _frames_and_people(frames, people, n_people)
+    idv = None if ids is None else _per_image(ids, np.int64, ())
+    if idv is not None and idv.shape != ppl.shape[:2]:
+        raise ValueError("ids must be %s like people, got shape %s" % (ppl.shape[:2], idv.shape))
+    sel = None if select is None else _per_image(select, np.uint8, ())
+    if sel is not None and sel.shape != ppl.shape[:2]:
+        raise ValueError("select must be %s like people, got shape %s" % (ppl.shape[:2], sel.shape))
+    sel = redact_select(idv, only_ids, keep_ids, sel)
+    if region not in _REDACT_REGIONS:
+        raise ValueError("region must be one of %s, got %r" % (sorted(_REDACT_REGIONS), region))
+    if effect not in _REDACT_EFFECTS:
+        raise ValueError("effect must be one of %s, got %r" % (sorted(_REDACT_EFFECTS), effect))
+    if head is None or len(head) != 2:
+        raise ValueError("head must name the joint pair (neck, head top), got %r (pose.redact_people has the MPII one)" % (head,))
+    e = np.zeros((0, 2), np.int32) if edges is None else np.ascontiguousarray(edges, dtype=np.int32)
+    if e.ndim != 2 or e.shape[1] != 2:
+        raise ValueError("edges must be [E, 2] joints, got shape %s" % (e.shape,))
+    st = RedactStyle()
+    st.region, st.head_a, st.head_b = _REDACT_REGIONS[region], int(head[0]), int(head[1])
+    st.head_scale, st.body_scale, st.min_radius, st.max_radius = float(head_scale), float(body_scale), float(min_radius), float(max_radius)
+    st.min_score, st.n_edges, st.edges = float(min_score), int(e.shape[0]), e.ctypes.data if e.shape[0] else None
+    st.effect, st.block = _REDACT_EFFECTS[effect], int(block)
+    st.fill[:] = [int(v) for v in fill]
+    out = np.zeros((nb, p), np.int32)
+    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    _check(_lib.dc_redact_people(arr, nb, h, w, int(is_device), p, j, ptr(n), ptr(ppl), ptr(sel), C.byref(st), ptr(out),
+                                 None if stream is None else C.c_void_p(int(stream))))
+    return out[0, :people.shape[0]] if single else out
 
 
 # ---- blending score maps into frames (dc_draw_heatmap; the rule: include/deepcut_hip.h — this project's own, the reference has none) ----

@@ -14,7 +14,7 @@ class VideoPipeline(object):
     MAX_DEPTH = 4  # a HIP process has four hardware queues: a fifth executor only shares one
 
     def __init__(self, net, tracker=None, depth=3, batch=1, stats=None, scale=1.0, choose_streams=True, complete=None, dedupe=None, draw=None,
-                 **assembly):
+                 redact=None, **assembly):
         """net: a `caffe.Net` with all three maps (or a sparse-pairwise net); tracker: a `caffe.Tracker` or None (people without ids,
         ids come back as None); depth: executors, 1..4; batch: frames per call, 1..64; stats: (edges, mean, std) as
         `deepcut_tools.read_pair_stats` returns them, or a path; scale: the pre-processing's and the assembly's; assembly: what
@@ -23,7 +23,9 @@ class VideoPipeline(object):
         (stage E: people who are there twice are suppressed before the tracker sees them).  draw: None (off: nothing is added), True or a
         dict of what `pose.draw_people` takes — every frame is kept with its request and drawn into IN PLACE on the device with the people
         and ids being handed back (filled and bridged joints at alpha_filled), before they are handed back; the frames must then be
-        writable arrays or `caffe.Frame`s."""
+        writable arrays or `caffe.Frame`s.  redact: None (off: nothing is added), True or a dict of what `pose.redact_people` takes —
+        every frame is kept likewise and redacted IN PLACE on the device with the people and ids being handed back, before the drawing
+        (the skeletons go over the mosaic); (people, ids) are what they are without it."""
         depth, batch = int(depth), int(batch)
         if not 1 <= depth <= self.MAX_DEPTH:
             raise ValueError("depth must be in [1, %d], got %d" % (self.MAX_DEPTH, depth))
@@ -47,6 +49,11 @@ class VideoPipeline(object):
             from pose.people import _draw_style
 
             self._draw = _draw_style(draw)
+        self._redact = None  # the style dict when frames are redacted
+        if redact is not None and redact is not False:
+            from pose.people import _redact_style
+
+            self._redact = _redact_style(redact)
         self._choose_streams = bool(choose_streams)
         self.stream_choice = None            # what caffe.choose_streams measured, once it ran
         self._held = []                      # frames of the batch being gathered: (frame, tag, slot, shape key)
@@ -82,7 +89,11 @@ class VideoPipeline(object):
         """Wait for the oldest request (the tracker ran them in submission order, so it finishes first or nearly) and queue its results."""
         k, handle, tags, frames = self._pending.popleft()
         for i, (tag, d) in enumerate(zip(tags, handle.result())):
-            if frames is not None:
+            if frames is not None and self._redact is not None:
+                from pose.people import redact_people
+
+                redact_people(frames[i], d["people"], d.get("ids"), **self._redact)
+            if frames is not None and self._draw is not None:
                 from pose.people import draw_people
 
                 draw_people(frames[i], d["people"], d.get("ids"), **dict(self._draw, cand=d.get("cand")))
@@ -98,7 +109,7 @@ class VideoPipeline(object):
             k = self._free_executor()
         self._next = (k + 1) % len(self.nets)
         frames = [h[0] for h in held]
-        kept = frames if self._draw is not None else None  # the frames themselves, to be drawn into when their results are there
+        kept = frames if self._draw is not None or self._redact is not None else None  # the frames themselves, to be redacted / drawn into when their results are there
         if held[0][3][0] == "bgr":
             import numpy as np
 

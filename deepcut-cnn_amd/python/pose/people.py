@@ -17,6 +17,8 @@ MIRROR_MPII14 = (5, 4, 3, 2, 1, 0, 11, 10, 9, 8, 7, 6, 12, 13)
 # The limbs `draw_people` draws between the joints of that order: the legs through the hips, the arms through the shoulders to the upper
 # neck, neck to head top, and the trunk's two sides.  Like the mirror table it is the caller's to override (`edges=`).
 SKELETON_MPII14 = ((0, 1), (1, 2), (2, 3), (3, 4), (4, 5), (6, 7), (7, 8), (8, 12), (12, 9), (9, 10), (10, 11), (12, 13), (2, 8), (3, 9))
+# The joint pair `redact_people` places the head disc on: (upper neck, head top).  The caller's to override (`head=`) likewise.
+HEAD_MPII14 = (12, 13)
 
 
 def _get_model(model_def, model_bin):
@@ -115,6 +117,31 @@ def draw_heatmap(frame, scores, scale, **style):
     _caffe.draw_heatmap(frame, _np.asarray(scores, _np.float32), scale, **style)
 
 
+def redact_people(frame, people, ids=None, **style):
+    """Redact people in a frame IN PLACE on the device: `caffe.redact_people` with the MPII head pair (`HEAD_MPII14`: upper neck, head
+    top) for `head` and the MPII skeleton (`SKELETON_MPII14`) for `edges` unless the caller names others.  frame, people, ids: as
+    `draw_people` takes them; style: what `caffe.redact_people` takes (select, only_ids, keep_ids, region, head_scale, body_scale,
+    min_radius, max_radius, min_score, effect, block, fill, stream; the scale and radius defaults are PLACEHOLDERS, not tuned on real
+    video).  -> int32 [m]: 1 where a region was made for the person — with region "head" a person whose neck or head top is missing is
+    NOT redacted.  PARITY UNPINNED BY THE REFERENCE: the rule is this project's own (include/deepcut_hip.h, dc_redact_people)."""
+    import caffe as _caffe
+
+    style.setdefault("head", HEAD_MPII14)
+    style.setdefault("edges", SKELETON_MPII14)
+    return _caffe.redact_people(frame, _np.asarray(people, _np.float64), ids=ids, **style)
+
+
+def _redact_style(redact):
+    """redact= of `track_people` / `VideoPipeline` -> None (off) or the style dict."""
+    if redact is None or redact is False:
+        return None
+    if redact is True:
+        return {}
+    if not isinstance(redact, dict):
+        raise ValueError("redact must be None, True or a dict of what redact_people takes, got %r" % (redact,))
+    return dict(redact)
+
+
 def _draw_style(draw):
     """draw= of `track_people` / `VideoPipeline` -> None (off) or the style dict."""
     if draw is None or draw is False:
@@ -126,7 +153,7 @@ def _draw_style(draw):
     return dict(draw)
 
 
-def track_people(frames, model_def, model_bin, stats, tracker=None, depth=1, batch=1, assign="greedy", smooth=None, draw=None, **kw):
+def track_people(frames, model_def, model_bin, stats, tracker=None, depth=1, batch=1, assign="greedy", smooth=None, draw=None, redact=None, **kw):
     """`estimate_people` over the frames of a video, with identities: a generator over an iterable of images (HxWx3 BGR uint8) or
     `caffe.Frame`s that yields, per frame, (people float64 [m, J, 3], ids int64 [m]) — the same person keeps their id from frame to
     frame, -1 marks a person no track place was free for.  kw: what `estimate_people` takes (scale / scales / base / flip / joint_mirror /
@@ -144,8 +171,13 @@ def track_people(frames, model_def, model_bin, stats, tracker=None, depth=1, bat
     (scales= / flip=True) has no asynchronous entry and raises ValueError.
     draw: None (off: nothing is added to the run), True or a dict of what `draw_people` takes — every frame is drawn into IN PLACE on the
     device, with the people and ids being yielded (the smoothed, de-duplicated ones; filled and bridged joints at alpha_filled), before
-    they are yielded.  The frames must then be writable arrays or `caffe.Frame`s; (people, ids) are what they are without `draw`."""
+    they are yielded.  The frames must then be writable arrays or `caffe.Frame`s; (people, ids) are what they are without `draw`.
+    redact: None (off: nothing is added to the run), True or a dict of what `redact_people` takes — every frame is redacted IN PLACE on the
+    device with the people and ids being yielded, BEFORE the drawing (the skeletons go over the mosaic) and before they are yielded;
+    (people, ids) are what they are without `redact`.  Who was not redacted (region "head": no neck or head top) is not reported here:
+    call `redact_people` on the yielded people where that matters."""
     style = _draw_style(draw)
+    rstyle = None if redact is None or redact is False else _redact_style(redact)
     args = dict(scale=1.0, net=None, scales=None, base=None, flip=False, joint_mirror=MIRROR_MPII14, sparse=False)
     for k in list(kw):
         if k in args:
@@ -154,7 +186,7 @@ def track_people(frames, model_def, model_bin, stats, tracker=None, depth=1, bat
         if args["scales"] is not None or args["flip"]:
             raise ValueError("track_people: depth > 1 / batch > 1 run one forward per frame; a pyramid (scales= / flip=True) has no "
                              "asynchronous entry: use depth=1, batch=1")
-        for item in _track_in_flight(frames, model_def, model_bin, stats, tracker, int(depth), int(batch), args, kw, assign, smooth, style):
+        for item in _track_in_flight(frames, model_def, model_bin, stats, tracker, int(depth), int(batch), args, kw, assign, smooth, style, rstyle):
             yield item
         return
     for image in frames:
@@ -164,12 +196,14 @@ def track_people(frames, model_def, model_bin, stats, tracker=None, depth=1, bat
             tracker = _caffe.Tracker(n_joints=len(MIRROR_MPII14), assign=assign, smooth=smooth)
         d = _people_of_image(tracker, image, model_def, model_bin, stats, args["scale"], args["net"], args["scales"], args["base"], args["flip"],
                              args["joint_mirror"], args["sparse"], kw)
+        if rstyle is not None:
+            redact_people(image, d["people"], d["ids"], **rstyle)
         if style is not None:
             draw_people(image, d["people"], d["ids"], **dict(style, cand=d["cand"]))
         yield d["people"], d["ids"]
 
 
-def _track_in_flight(frames, model_def, model_bin, stats, tracker, depth, batch, args, assembly, assign="greedy", smooth=None, style=None):
+def _track_in_flight(frames, model_def, model_bin, stats, tracker, depth, batch, args, assembly, assign="greedy", smooth=None, style=None, rstyle=None):
     """`track_people` through `deepcut_tools.VideoPipeline` -> (people, ids) per frame, in frame order."""
     import caffe as _caffe
     from deepcut_tools import VideoPipeline
@@ -181,6 +215,8 @@ def _track_in_flight(frames, model_def, model_bin, stats, tracker, depth, batch,
         tracker = _caffe.Tracker(n_joints=len(MIRROR_MPII14), assign=assign, smooth=smooth)
     if style is not None:
         assembly = dict(assembly, draw=style)
+    if rstyle is not None:
+        assembly = dict(assembly, redact=rstyle)
     pipe = VideoPipeline(net, tracker, depth=depth, batch=batch, stats=stats, scale=args["scale"], **assembly)
     ahead = 0
     for image in frames:

@@ -40,12 +40,15 @@ def draw_disc(image, cx, cy, radius, color):
 @click.option("--heatmap", type=click.Choice(["max", "joints"]), default=None,
               help="also write <out>_heat.png: the score maps of one forward at the first scale blended over the image on the device "
                    "(Net.draw_heatmap) — max: the maximum over the joints through caffe.HEAT_LUT; joints: every joint in its colour; default: off")
+@click.option("--redact", type=click.Choice(["head", "body"]), default=None,
+              help="pixelate the person's head or whole body in the visualisation on the device, under the overlay (pose.redact_people; "
+                   "its radii are placeholders, and a mosaic is not a privacy guarantee); default: off")
 @click.option("--model_def", default=None,
               help="model definition (.prototxt).  Default: the definition deepcut_tools.deepercut_prototxt(152) generates, which is "
                    "layer-for-layer the reference's models/deepercut/ResNet-152.prototxt (that directory is not part of this repository)")
 @click.option("--model_bin", default=None, required=True,
               help="trained weights (.caffemodel / .h5): the reference fetches them with models/deepercut/download_models.sh; not shipped here")
-def predict_pose_from(image_name, out_name, scales, visualize, folder_image_suffix, use_cpu, gpu, tiling, skeleton, heatmap, model_def, model_bin):
+def predict_pose_from(image_name, out_name, scales, visualize, folder_image_suffix, use_cpu, gpu, tiling, skeleton, heatmap, redact, model_def, model_bin):
     import caffe
     from PIL import Image
 
@@ -81,6 +84,11 @@ def predict_pose_from(image_name, out_name, scales, visualize, folder_image_suff
         img = img[:, :, :3][:, :, ::-1]  # RGB -> BGR
         pose = estimate_pose(img, model_def, model_bin, scales, tiling=None if tiling == "none" else tiling)
         np.savez_compressed(target, pose=pose)
+        if visualize and pose is not None and redact is not None:
+            from pose.people import redact_people
+
+            img = np.ascontiguousarray(img)
+            redact_people(img, np.ascontiguousarray(pose[:3].T)[None], region=redact)
         if visualize and pose is not None and skeleton:
             from pose.people import SKELETON_MPII14, draw_people
 

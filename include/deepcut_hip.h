@@ -1233,6 +1233,73 @@ int dc_group_draw_heatmap_mirrored(dc_group* group, const dc_frame* frames, int 
                                    const double* scales, int base, const dc_fuse_mirror* fm, double origin_x, double origin_y,
                                    const dc_heat_style* style);
 
+/* ---- redacting people in video frames: a mosaic or a solid colour over heads or bodies of BGR24 or NV12 frames, on the device ------
+ * PARITY UNPINNED BY THE REFERENCE, which has nothing of the kind.  THE RULE below is this project's own, like the drawing rule above.
+ * It is integer only, so every path gives the same bytes (tests/redact_ref.py restates it in numpy; the device is held to that byte for
+ * byte, pitch padding included).
+ *
+ * Input: frames, people[nb][P][J][3] and n_people[nb] as dc_draw_people takes them; select[nb][P] (may be NULL: everyone): person p of
+ *   frame b takes part when p < n_people[b] and select[b][p] is non-zero; a style.  Output: redacted[nb][P] (may be NULL), all of it
+ *   written: 1 where at least one region primitive was made for the person, 0 otherwise (not selected, beyond n_people[b], or no
+ *   primitive: a person whose neck is below the threshold gets no head region, and the caller must be able to see that).  A primitive
+ *   is made from the joints alone, whether or not it reaches into the frame; one whose radius comes out 0 is not made.
+ * Which joints are held: as in drawing — x, y and score all finite and score > min_score.  Held coordinates are snapped exactly as
+ *   dc_draw_people snaps them: clamped to [-32768, 32768] pixels, then q = (int)rint(16 v).  clamp(v, lo, hi) below is min(max(v, lo), hi),
+ *   taken in double before the conversion to int.
+ * Regions, by style->region.  The head pair (head_a, head_b) names two joints (the neck, the head top) and is checked for every region.
+ *   The head disc, when both joints of the pair are held: with d = b - a in snapped units and L = d.d in int64 (at most 2^41, exact in
+ *     double), the disc centred at ((ax + bx) >> 1, (ay + by) >> 1) (arithmetic shift) of radius
+ *     r16 = clamp(rint(head_scale * sqrt((double)L)), rint(16 min_radius), rint(16 max_radius)), 0 <= min_radius <= max_radius <= 1024
+ *     pixels: one correctly rounded square root, one double multiply and one rint, ties to even.  The disc test w.w <= r16^2 of the
+ *     drawing rule stays below 2^43 in int64 for such radii (|w| components below 2^21, r16 <= 2^14, so r16^2 <= 2^28).
+ *   The body primitives: every limb of style->edges whose two joints are held, as a capsule; every held joint, as a disc; coverage by
+ *     the drawing rule's capsule and disc tests.  Their radius is rb16 = clamp(rint(body_scale * s16), rint(16 min_radius), 1024), s16
+ *     (an int) the larger side of the bounding box of the person's held joints in snapped units (0 for a single joint: the radius is
+ *     then min_radius).  The cap of 1024 units = 64 pixels — the drawing rule's largest radius, and it wins over min_radius — keeps the
+ *     capsule test's int64 proof as it stands there (r16^2 L <= 2^61).
+ *   DC_REDACT_HEAD: the head disc.  DC_REDACT_BODY: the head disc and the body primitives.  DC_REDACT_HEAD_OR_BODY: the head disc when
+ *     the pair is held, else the body primitives.
+ * Blocks: block B in {2, 4, 8, 16, 32} — even, so an NV12 chroma sample lies in exactly one block; a divisor of the kernel's 32 x 32
+ *   tile, so a block lies in exactly one tile.  The grid is anchored at pixel (0, 0) of the frame; blocks at the right and bottom edge
+ *   may be partial.  A block is selected when the centre (16 px + 8, 16 py + 8) of any of its in-frame pixels is covered by any
+ *   primitive of that frame.  Selection is a set: the result does not depend on the order of people or primitives.
+ * Effect on a selected block, n the number of its in-frame pixels, sums over the bytes the call found:
+ *   DC_REDACT_MOSAIC, BGR24: each channel of every in-frame pixel becomes (sum + n / 2) / n of that channel over the block (integer
+ *     division).  NV12: the same on luma; every chroma sample (cx, cy) with pixel (2 cx, 2 cy) in the block becomes the block's mean Cb
+ *     and Cr, (sum + m / 2) / m over those m samples.  The largest sum is 1024 * 255.
+ *   DC_REDACT_FILL: every in-frame pixel, and every such chroma sample, becomes `fill` (R, G, B), converted once by the forward colour
+ *     rule stated under dc_draw_people.
+ * Untouched bytes: bytes outside selected blocks, pitch padding included, are never stored.  A call that makes no primitive that
+ *   reaches the frame launches nothing and writes nothing; a host frame nothing is redacted in does not travel.  A MOSAIC call
+ *   repeated on its own output changes no byte (a block of equal bytes v has the mean (n v + n / 2) / n = v).
+ *
+ * dc_redact_people: stand-alone like dc_draw_people — no net, people as host arrays, frames in host (is_device = 0) or device memory,
+ *   the work on the device either way; the limits of nb, height, width, P, J and n_edges are dc_draw_people's.  The call returns when
+ *   the redaction is complete: on `stream`, or on the library's utility stream when it is NULL; host frames are staged up without their
+ *   padding and copied back with 2-D copies.  One launch: only tiles some primitive's bounding box touches (one workgroup each).
+ * Errors, before any device work: DC_EINVAL naming the field for everything dc_draw_people refuses of frames, nb, height, width, P, J,
+ *   n_people and edges; a NULL style; an unknown region or effect; block not in the list; head_a or head_b outside [0, J), or equal;
+ *   head_scale or body_scale not finite or < 0; min_radius or max_radius not finite, min_radius < 0, max_radius > 1024 or
+ *   min_radius > max_radius; min_score not finite or < 0.  Then DC_ENOCPU in CPU mode (there is no CPU path).
+ * Not built, on purpose: blur; an asynchronous entry; redaction inside dc_net_track_frames_async; per-box geometry.  A mosaic with
+ *   small blocks is NOT a privacy guarantee (the means still carry the face), and DC_REDACT_HEAD does not redact a person without a
+ *   held head pair: that is what `redacted` is for.                                                                              */
+#define DC_REDACT_HEAD         0
+#define DC_REDACT_BODY         1
+#define DC_REDACT_HEAD_OR_BODY 2
+#define DC_REDACT_MOSAIC       0
+#define DC_REDACT_FILL         1
+typedef struct dc_redact_style {
+  int region, head_a, head_b;               /* DC_REDACT_HEAD, _BODY, _HEAD_OR_BODY; the head pair: two different joints in [0, J) */
+  double head_scale, body_scale, min_radius, max_radius, min_score; /* scales finite, >= 0; radii in pixels, 0 <= min <= max <= 1024 */
+  int n_edges; const int* edges;            /* [n_edges][2] 0-based joints, 0..128: the limbs of the body region */
+  int effect, block;                        /* DC_REDACT_MOSAIC, DC_REDACT_FILL; 2, 4, 8, 16 or 32 */
+  unsigned char fill[3];                    /* R, G, B: DC_REDACT_FILL */
+} dc_redact_style;
+int dc_redact_people(const dc_frame* frames, int nb, int height, int width, int is_device, int P, int J, const int* n_people,
+                     const double* people, const unsigned char* select /* [nb][P], may be NULL: everyone */,
+                     const dc_redact_style* style, int* redacted /* [nb][P], may be NULL */, void* stream);
+
 /* ---- in-process multi-GPU forward (SURVEY 8(b)'s dc_forward_batch) -------------------------------------------------------
  * A communicator over `nexec` executors: executor k runs on devices[k] (NULL: k modulo the visible devices) on a host thread of its
  * own (mode and device are per thread, src/caffe/common.cpp:13-20).  transport: how the maps travel to the root executor's device —
