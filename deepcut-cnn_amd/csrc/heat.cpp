@@ -1,6 +1,6 @@
 // heat.cpp — dc_draw_heatmap / dc_net_draw_heatmap / dc_group_draw_heatmap: the host half of the score-map overlay.  Every check, the
-// per-axis sample tables in double, the colours converted once, one upload into the overlays' buffer (draw.cpp's draw_buffer), one launch
-// (heat.hip).  The rule is stated in include/deepcut_hip.h.
+// per-axis sample tables in double, the colours converted once, one upload through the frame passes' stager (FrameStage, net_internal.h),
+// one launch (heat.hip).  The rule is stated in include/deepcut_hip.h.
 //
 // PARITY UNPINNED BY THE REFERENCE: its demo draws 14 circles with numpy and never shows a map; the rule is this project's own.
 #include "net_internal.h"
@@ -12,7 +12,7 @@
 namespace dc {
 
 namespace {
-constexpr int kHeatMaxFrames = 64, kHeatMaxSide = 16384, kHeatMaxMapSide = 65536;
+constexpr int kHeatMaxMapSide = 65536;
 
 // the map as the kernel reads it
 struct HeatMap {
@@ -25,8 +25,7 @@ void heat_check(const char* who, const dc_frame* frames, int nb, int h, int w, i
                 const dc_heat_style* st) {
   auto bad = [&](const std::string& m) { throw DcError(DC_EINVAL, std::string(who) + ": " + m); };
   auto in_range = [](double v, double lo, double hi) { return std::isfinite(v) && v >= lo && v <= hi; };
-  if (nb < 1 || nb > kHeatMaxFrames) bad("nb must be in [1, " + std::to_string(kHeatMaxFrames) + "]");
-  if (h < 1 || h > kHeatMaxSide || w < 1 || w > kHeatMaxSide) bad("height and width must be in [1, " + std::to_string(kHeatMaxSide) + "]");
+  check_frame_dims(who, nb, h, w);
   if (!frames) bad("null argument: frames");
   check_frames(who, frames, nb, h, w);
   if (C < 1 || C > kHeatMaxJoints) bad("the map's channels (C) must be in [1, " + std::to_string(kHeatMaxJoints) + "]");
@@ -70,12 +69,12 @@ void heat_blend_frames(const dc_frame* frames, int nb, int h, int w, bool is_dev
   const int format = frames[0].format;
   const bool nv12 = format == DC_PIX_NV12;
   const int cw = (w + 1) / 2, ch = (h + 1) / 2;
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
   const int n_col = st->mode == DC_HEAT_MAX ? 256 : st->n_joints;
-  const size_t fr_b = up((size_t)nb * sizeof(DrawPlanes)), tab_n = (size_t)w + h + (nv12 ? cw + ch : 0), tab_b = up(tab_n * sizeof(int)),
-               col_b = up((size_t)n_col * sizeof(unsigned)), head_b = fr_b + tab_b + col_b;
-  std::vector<unsigned char> head(head_b, 0);
-  int* tx = reinterpret_cast<int*>(head.data() + fr_b);
+  const size_t tab_n = (size_t)w + h + (nv12 ? cw + ch : 0), tab_b = frame_up(tab_n * sizeof(int)), col_b = frame_up((size_t)n_col * sizeof(unsigned));
+  // the tables | the colours, made here and copied into the stager's head below: the refusal of a too large patch needs the tables and
+  // comes before the stager's refusal without a device, so they cannot be written straight into stage.head
+  std::vector<unsigned char> head(tab_b + col_b, 0);
+  int* tx = reinterpret_cast<int*>(head.data());
   int *ty = tx + w, *cx = ty + h, *cy = cx + cw;
   heat_table(tx, w, 0.5, 1.0, ox, scale, Wm);
   heat_table(ty, h, 0.5, 1.0, oy, scale, Hm);
@@ -95,47 +94,20 @@ void heat_blend_frames(const dc_frame* frames, int nb, int h, int w, bool is_dev
   const int max_pw = span(tx, cx, w, Wm), max_ph = span(ty, cy, h, Hm);
   if (max_pw > kHeatMaxPatch + 1 || max_ph > kHeatMaxPatch + 1) throw DcError(DC_EINVAL, "draw_heatmap: a tile reaches more map cells than the kernel stages");
   // colours: R, G, B -> the frame's bytes, once
-  const ForwardCsc csc(frames[0].matrix, frames[0].range);
-  auto colour = [&](const unsigned char* rgb) {
-    return nv12 ? csc(rgb[0], rgb[1], rgb[2]) : (unsigned)rgb[2] | (unsigned)rgb[1] << 8 | (unsigned)rgb[0] << 16;
-  };
-  unsigned* col = reinterpret_cast<unsigned*>(head.data() + fr_b + tab_b);
+  const FrameColour colour(frames[0]);
+  unsigned* col = reinterpret_cast<unsigned*>(head.data() + tab_b);
   for (int i = 0; i < n_col; ++i) col[i] = colour(st->mode == DC_HEAT_MAX ? st->lut + 3 * (size_t)i : st->palette + 3 * (size_t)(i % st->n_palette));
 
-  if (device_count() <= 0) throw DcError(DC_EDEVICE, "no HIP device visible");
-  HIPCHECK(hipSetDevice(device));
-  const int planes = nv12 ? 2 : 1;
-  const int rows[2] = {h, ch}, rb[2] = {nv12 ? w : 3 * w, 2 * cw};
-  const size_t per = up((size_t)rb[0] * rows[0]) + (nv12 ? up((size_t)rb[1] * rows[1]) : 0);
-  const size_t map_b = map.host ? up((size_t)nb * C * Hm * Wm * sizeof(float)) : 0;
-  RuntimeLock rl_;
-  hipStream_t s = stream ? (hipStream_t)stream : util_stream();
-  unsigned char* dev = (unsigned char*)draw_buffer(device).get(head_b + map_b + (is_device ? 0 : per * nb));
-  DrawPlanes* table = reinterpret_cast<DrawPlanes*>(head.data());
-  for (int b = 0; b < nb; ++b) {
-    if (is_device) {
-      table[b] = DrawPlanes{(unsigned char*)frames[b].plane[0], nv12 ? (unsigned char*)frames[b].plane[1] : nullptr, frames[b].pitch[0],
-                            nv12 ? frames[b].pitch[1] : 0};
-    } else {  // host frames: the planes without their padding, staged behind the head and the map
-      unsigned char* d0 = dev + head_b + map_b + per * b;
-      table[b] = DrawPlanes{d0, nv12 ? d0 + up((size_t)rb[0] * rows[0]) : nullptr, rb[0], nv12 ? rb[1] : 0};
-    }
-  }
-  HIPCHECK(hipMemcpyAsync(dev, head.data(), head_b, hipMemcpyHostToDevice, s));
-  if (map.host) HIPCHECK(hipMemcpyAsync(dev + head_b, map.host, (size_t)nb * C * Hm * Wm * sizeof(float), hipMemcpyHostToDevice, s));
-  if (!is_device)
-    for (int b = 0; b < nb; ++b) {
-      unsigned char* d[2] = {table[b].plane0, table[b].plane1};
-      for (int k = 0; k < planes; ++k)
-        HIPCHECK(hipMemcpy2DAsync(d[k], (size_t)rb[k], frames[b].plane[k], (size_t)frames[b].pitch[k], (size_t)rb[k], (size_t)rows[k],
-                                  hipMemcpyHostToDevice, s));
-    }
+  // every frame travels; a host map goes between the head and the planes
+  FrameStage stage(frames, nb, h, w, is_device, device, stream, head.size(), map.host ? (size_t)nb * C * Hm * Wm * sizeof(float) : 0);
+  std::memcpy(stage.head, head.data(), head.size());
+  stage.copy_in(nullptr, map.host);
   HeatParams p{};
-  p.frames = reinterpret_cast<const DrawPlanes*>(dev);
-  p.map = map.host ? (const void*)(dev + head_b) : map.ptr;
-  const int* dtab = reinterpret_cast<const int*>(dev + fr_b);
+  p.frames = stage.dev_frames;
+  p.map = map.host ? (const void*)stage.dev_extra : map.ptr;
+  const int* dtab = reinterpret_cast<const int*>(stage.dev_head);
   p.tx = dtab, p.ty = dtab + w, p.cx = nv12 ? dtab + w + h : nullptr, p.cy = nv12 ? dtab + w + h + cw : nullptr;
-  p.colour = reinterpret_cast<const unsigned*>(dev + fr_b + tab_b);
+  p.colour = reinterpret_cast<const unsigned*>(stage.dev_head + tab_b);
   p.H = h, p.W = w, p.Hm = Hm, p.Wm = Wm, p.C = C, p.cp = map.cp, p.c0 = map.c0;
   p.n_joints = st->n_joints, p.by_joint = st->mode == DC_HEAT_BY_JOINT, p.alpha = st->alpha, p.alpha_score = st->alpha_mode == DC_HEAT_ALPHA_SCORE;
   p.vmin = (int)std::rint(4096.0 * st->min_score);
@@ -143,15 +115,8 @@ void heat_blend_frames(const dc_frame* frames, int nb, int h, int w, bool is_dev
   p.vgate = p.alpha_score ? std::max(p.vmin, (2048 + st->alpha - 1) / st->alpha) : p.vmin;
   p.max_cells = max_pw * max_ph;
   for (int k = 0; k < st->n_joints; ++k) p.joints[k] = (unsigned char)st->joints[k];
-  KCHECK(launch_heat(format, map.ek, map.nchw, p, nb, s));
-  if (!is_device)
-    for (int b = 0; b < nb; ++b) {
-      unsigned char* d[2] = {table[b].plane0, table[b].plane1};
-      for (int k = 0; k < planes; ++k)  // rows of rb[k] bytes into the caller's pitch: the padding is never written
-        HIPCHECK(hipMemcpy2DAsync(const_cast<void*>(frames[b].plane[k]), (size_t)frames[b].pitch[k], d[k], (size_t)rb[k], (size_t)rb[k],
-                                  (size_t)rows[k], hipMemcpyDeviceToHost, s));
-    }
-  HIPCHECK(hipStreamSynchronize(s));
+  KCHECK(launch_heat(format, map.ek, map.nchw, p, nb, stage.s));
+  stage.copy_out();
 }
 }  // namespace
 

@@ -3,8 +3,8 @@
 //
 // PARITY UNPINNED BY THE REFERENCE: its demo draws 14 circles with numpy and never shows a map; the rule is this project's own.
 //
-// One workgroup per 32 x 32 pixel tile of one frame, one thread per 2 x 2 pixel block — draw_kernel's ownership: the thread that owns a
-// chroma sample owns its four luma pixels, so there are no atomics and no two threads write one byte.  The per-axis tables say which
+// One workgroup per 32 x 32 pixel tile of one frame, one thread per 2 x 2 pixel block (frame_tile.h: the ownership — the thread that owns
+// a chroma sample owns its four luma pixels, so there are no atomics and no two threads write one byte).  The per-axis tables say which
 // map cells a tile reaches: a patch of at most kHeatMaxPatch cells per side.  The workgroup stages it into LDS once, the drawn channels
 // only, quantised to 16 bits (the rule's only floating-point step), and every interpolation tap then comes from LDS.
 //
@@ -17,17 +17,12 @@
 #include <hip/hip_runtime.h>
 
 #include "by_kind.h"
+#include "frame_tile.h"
 #include "kernels.h"
 
 namespace dc {
 
 namespace {
-constexpr int kFmtBgr = 0, kFmtNv12 = 1;  // DC_PIX_BGR24, DC_PIX_NV12
-constexpr int kBlocksX = kDrawTileW / 2, kBlocksY = kDrawTileH / 2;
-static_assert(kBlocksX * kBlocksY == 256, "one thread per 2 x 2 block of the tile");
-
-__device__ __forceinline__ int heat_blend(int c, int dst, int a) { return (c * a + dst * (256 - a) + 128) >> 8; }
-
 // one sample point: the four taps' places in a channel's patch, and the two fractions (0..255)
 struct HeatTap {
   int o00, o01, o10, o11, fx, fy;
@@ -45,7 +40,6 @@ __device__ __forceinline__ int heat_interp(const unsigned short* q, const HeatTa
 
 template <int FMT, typename T, bool NCHW>
 __global__ __launch_bounds__(256) void heat_kernel(const HeatParams p) {
-  constexpr int NC = FMT == kFmtBgr ? 3 : 1;  // bytes held per pixel
   constexpr int NS = FMT == kFmtBgr ? 4 : 5;  // sample points of a thread: its pixels q = 2 * row + column, then the chroma sample
   extern __shared__ unsigned short heat_lds[];  // [n_joints][cells]
   const int X0 = (int)blockIdx.x * kDrawTileW, Y0 = (int)blockIdx.y * kDrawTileH, b = (int)blockIdx.z;
@@ -73,46 +67,25 @@ __global__ __launch_bounds__(256) void heat_kernel(const HeatParams p) {
   if (!__syncthreads_or(qmax >= p.vgate)) return;
 
   const DrawPlanes f = p.frames[b];
-  const int x0 = X0 + 2 * ((int)threadIdx.x % kBlocksX), y0 = Y0 + 2 * ((int)threadIdx.x / kBlocksX);
-  bool in[4];
-  int n_in = 0;
-  for (int q = 0; q < 4; ++q) in[q] = x0 + (q & 1) < p.W && y0 + (q >> 1) < p.H, n_in += in[q];
-  if (!n_in) return;  // no barrier follows
+  BlockPixels<FMT> px(X0, Y0, p.H, p.W);
+  if (!px.n_in) return;  // no barrier follows
+  const int x0 = px.x0, y0 = px.y0;
   HeatTap tap[NS];
   {
     const int txa = p.tx[x0], txb = p.tx[min(x0 + 1, p.W - 1)], tya = p.ty[y0], tyb = p.ty[min(y0 + 1, p.H - 1)];
     for (int q = 0; q < 4; ++q) tap[q] = heat_tap(q & 1 ? txb : txa, q >> 1 ? tyb : tya, lo_x, lo_y, p.Wm, p.Hm, pw);
     if (FMT == kFmtNv12) tap[NS - 1] = heat_tap(p.cx[x0 >> 1], p.cy[y0 >> 1], lo_x, lo_y, p.Wm, p.Hm, pw);
   }
-  int v[4][NC], cb = 0, cr = 0;
-  unsigned touched = 0;  // bit q: pixel q, bit 4: the chroma sample
-  for (int q = 0; q < 4; ++q) {
-    const unsigned char* s = f.plane0 + (long)(y0 + (q >> 1)) * f.pitch0 + (long)(x0 + (q & 1)) * NC;
-    for (int c = 0; c < NC; ++c) v[q][c] = in[q] ? (int)s[c] : 0;
-  }
-  unsigned char* chroma = nullptr;
-  if (FMT == kFmtNv12) {
-    chroma = f.plane1 + (long)(y0 >> 1) * f.pitch1 + (long)(x0 >> 1) * 2;
-    cb = chroma[0], cr = chroma[1];
-  }
+  px.load(f);
   auto alpha_of = [&](int s) { return p.alpha_score ? (p.alpha * s + 2048) >> 12 : p.alpha; };
-  auto blend = [&](int pt, unsigned colour, int a) {
-    const int c0 = colour & 255, c1 = (colour >> 8) & 255, c2 = (colour >> 16) & 255;
-    if (pt < 4) {
-      v[pt][0] = heat_blend(c0, v[pt][0], a);
-      if (FMT == kFmtBgr) v[pt][1] = heat_blend(c1, v[pt][1], a), v[pt][NC - 1] = heat_blend(c2, v[pt][NC - 1], a);
-    } else {
-      cb = heat_blend(c1, cb, a), cr = heat_blend(c2, cr, a);
-    }
-    touched |= 1u << pt;
-  };
+  auto blend = [&](int pt, unsigned colour, int a) { pt < 4 ? px.blend_pixel(pt, colour, a) : px.blend_chroma(colour, a); };
   if (p.by_joint) {  // the list in order, later channels over earlier ones
     for (int k = 0; k < nj; ++k) {
       const unsigned short* qk = heat_lds + k * cells;
       const unsigned colour = p.colour[k];
 #pragma unroll
       for (int pt = 0; pt < NS; ++pt) {
-        if (pt < 4 && !in[pt]) continue;
+        if (pt < 4 && !px.in[pt]) continue;
         const int s = heat_interp(qk, tap[pt]), a = alpha_of(s);
         if (s >= p.vmin && a > 0) blend(pt, colour, a);
       }
@@ -128,17 +101,12 @@ __global__ __launch_bounds__(256) void heat_kernel(const HeatParams p) {
     }
 #pragma unroll
     for (int pt = 0; pt < NS; ++pt) {
-      if (pt < 4 && !in[pt]) continue;
+      if (pt < 4 && !px.in[pt]) continue;
       const int s = vm[pt], a = alpha_of(s);
       if (s >= p.vmin && a > 0) blend(pt, p.colour[min(255, s >> 4)], a);
     }
   }
-  for (int q = 0; q < 4; ++q)
-    if (touched >> q & 1) {
-      unsigned char* d = f.plane0 + (long)(y0 + (q >> 1)) * f.pitch0 + (long)(x0 + (q & 1)) * NC;
-      for (int c = 0; c < NC; ++c) d[c] = (unsigned char)v[q][c];
-    }
-  if (FMT == kFmtNv12 && (touched & 16u)) chroma[0] = (unsigned char)cb, chroma[1] = (unsigned char)cr;
+  px.store(f);
 }
 
 template <int FMT, typename T, bool NCHW>

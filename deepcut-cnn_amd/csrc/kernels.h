@@ -426,10 +426,14 @@ int launch_dedupe(int NB, int J, int max_people, double max_dist, int min_common
                   const int* n_in, const double* people_in, const int* cand_in, int* n_out, double* people_out, int* cand_out,
                   int* kept_from, int* suppressed_by, void* stream);
 
+// The three passes that write into video frames (draw.hip, redact.hip, heat.hip) share one shape.  On the device (frame_tile.h): one
+// workgroup per kDrawTileW x kDrawTileH pixel tile, one thread per 2 x 2 pixel block, so the thread that owns a chroma sample owns its
+// luma pixels and no two threads write one byte — "the ownership" below.  On the host: the tile binner of the two passes that walk
+// primitives (tile_bins.h) and the stager that moves tables and host frames (FrameStage, net_internal.h).
+//
 // Skeleton overlay (draw.hip; the rule: include/deepcut_hip.h, dc_draw_people — this project's own).  The host (draw.cpp) snaps the
-// joints to 1/16-pixel fixed point, converts the colours and bins the primitives, in drawing order, into kDrawTileW x kDrawTileH pixel
-// tiles; one workgroup draws one non-empty tile, one thread one 2 x 2 pixel block (so the thread that owns a chroma sample owns its
-// luma pixels), every thread walking the tile's primitives in order, kDrawChunk at a time through LDS.
+// joints to 1/16-pixel fixed point, converts the colours and bins the primitives, in drawing order, into the tiles; one workgroup draws
+// one non-empty tile, every thread walking the tile's primitives in order, kDrawChunk at a time through LDS.
 constexpr int kDrawTileW = 32, kDrawTileH = 32, kDrawChunk = 64;
 struct DrawPrim {       // 32 bytes
   int ax, ay, bx, by;   // the ends in 1/16 pixel, |v| <= 2^19; a disc has b == a
@@ -447,13 +451,15 @@ struct DrawPlanes {
   unsigned char* plane1;
   int pitch0, pitch1;
 };
+// every part of what a pass uploads (frame table, tiles, index, primitives, tables, colours, staged planes) starts at a multiple of 256 bytes
+inline size_t frame_up(size_t bytes) { return (bytes + 255) / 256 * 256; }
 // format: DC_PIX_BGR24 or DC_PIX_NV12.  Grid = n_tiles (> 0).  Every pointer is device memory.
 int launch_draw(int format, const DrawPlanes* frames, int height, int width, const DrawTile* tiles, int n_tiles, const int* index,
                 const DrawPrim* prims, void* stream);
 
 // Redaction (redact.hip; the rule: include/deepcut_hip.h, dc_redact_people — this project's own).  The host (redact.cpp) turns people
 // into DrawPrims (alpha and colour unused; a head disc's r16 may reach 16384) and bins them into the drawing kernel's tiles; one
-// workgroup redacts one non-empty tile, one thread one 2 x 2 pixel block (draw_kernel's ownership), in three phases between barriers:
+// workgroup redacts one non-empty tile, one thread one 2 x 2 pixel block (the ownership), in three phases between barriers:
 // which B x B blocks hold a covered pixel centre, the blocks' sums in LDS (MOSAIC), the stores.
 constexpr int kRedactMosaic = 0, kRedactFill = 1;  // DC_REDACT_MOSAIC, DC_REDACT_FILL
 // format: DC_PIX_BGR24 or DC_PIX_NV12; effect: kRedactMosaic or kRedactFill; block: 2, 4, 8, 16 or 32; fill: bytes as DrawPrim::colour.
@@ -463,7 +469,7 @@ int launch_redact(int format, int effect, int block, unsigned fill, const DrawPl
 
 // Score-map overlay (heat.hip; the rule: include/deepcut_hip.h, dc_draw_heatmap — this project's own).  The host (heat.cpp) computes
 // the per-axis sample tables t = rint(256 u), clamped, and converts the colours; one workgroup blends one kDrawTileW x kDrawTileH pixel
-// tile of one frame, one thread one 2 x 2 pixel block (draw_kernel's ownership), after staging the patch of map cells the tile's tables
+// tile of one frame, one thread one 2 x 2 pixel block (the ownership), after staging the patch of map cells the tile's tables
 // reach into LDS as 16-bit q = rint(4096 clamp01(s)), the drawn channels only, channel-major.
 constexpr int kHeatMaxJoints = 32;
 constexpr int kHeatMaxPatch = kDrawTileW * 8 / 8 + 2;  // cells per side at the largest scale, 8: 32 pixels = 32 cells, + 1 for the second tap, + 1 of rounding

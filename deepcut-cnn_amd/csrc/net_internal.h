@@ -11,7 +11,8 @@
 //   net_group.cpp NetGroup: pyramid-grouped execution
 //   streams.cpp   the process-wide pool of executor streams chosen by measurement (round 5)
 //   multi_gpu.cpp in-process multi-GPU forward of the C ABI (round 5)
-// This header: CallStream (the one stream rule of the entries), decode_to and the box table's layout (shared by the readers).
+// This header: CallStream (the one stream rule of the entries), decode_to and the box table's layout (shared by the readers), and what
+// the passes over video frames share: their limits and refusals, snap16 / held_joints / FrameColour, FrameStage.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -106,7 +107,24 @@ hipGraphExec_t capture_graph(void* cs, F&& enqueue) {
   return ge;
 }
 
-// ---- shared by the overlays (draw.cpp, heat.cpp) ----------------------------------------------------------------------------------
+// ---- shared by the passes over video frames (draw.cpp, heat.cpp, redact.cpp; defined in draw.cpp) --------------------------------------
+#define DC_INTERNAL __attribute__((visibility("hidden")))  // shared by the translation units, no part of what the library exports
+constexpr int kFrameMaxFrames = 64, kFrameMaxSide = 16384, kFrameMaxEdges = 128;
+// the refusals the passes word alike (DC_EINVAL, "<who>: ..."), each called where the entry's order of checks has it
+DC_INTERNAL void check_frame_dims(const char* who, int nb, int h, int w);
+DC_INTERNAL void check_people_dims(const char* who, int P, int J);
+DC_INTERNAL void check_edges(const char* who, int n_edges, const int* edges, int J);
+DC_INTERNAL void check_n_people(const char* who, const int* n_people, int nb, int P);
+// pixels -> 1/16 pixel, ties to even
+DC_INTERNAL inline int snap16(double v) { return (int)std::rint(16.0 * std::min(32768.0, std::max(-32768.0, v))); }
+// a pose [J][3] (x, y, score) -> held[j]: the joint is finite and its score above min_score; then (qx, qy)[j] is its snapped place
+DC_INTERNAL inline void held_joints(const double* pose, int J, double min_score, int* qx, int* qy, bool* held) {
+  for (int j = 0; j < J; ++j) {
+    const double x = pose[3 * j], y = pose[3 * j + 1], s = pose[3 * j + 2];
+    held[j] = std::isfinite(x) && std::isfinite(y) && std::isfinite(s) && s > min_score;
+    if (held[j]) qx[j] = snap16(x), qy[j] = snap16(y);
+  }
+}
 inline int clip8(long v) { return v < 0 ? 0 : (v > 255 ? 255 : (int)v); }
 // the forward colour rule: the counterpart of frame_csc's inverse (net_image.cpp), coefficients in double, rounded to nearest
 struct ForwardCsc {
@@ -130,8 +148,41 @@ struct ForwardCsc {
     return (unsigned)Y | (unsigned)Cb << 8 | (unsigned)Cr << 16;
   }
 };
-// the overlay calls' device buffer, per device (draw.cpp): the caller holds the runtime lock, and every call waits for its work
+// R, G, B -> a frame's bytes as DrawPrim::colour: Y | Cb << 8 | Cr << 16 by the forward rule, or B | G << 8 | R << 16; the
+// coefficients are made once
+struct DC_INTERNAL FrameColour {
+  bool nv12;
+  ForwardCsc csc;
+  explicit FrameColour(const dc_frame& f) : nv12(f.format == DC_PIX_NV12), csc(f.matrix, f.range) {}
+  unsigned operator()(const unsigned char* rgb) const {
+    return nv12 ? csc(rgb[0], rgb[1], rgb[2]) : (unsigned)rgb[2] | (unsigned)rgb[1] << 8 | (unsigned)rgb[0] << 16;
+  }
+};
+// the passes' device buffer, per device (draw.cpp): the caller holds the runtime lock, and every call waits for its work
 DevBuf& draw_buffer(int device);
+// One call's device memory in that buffer and the way of host frames through it.  The layout, every part rounded up to 256 bytes:
+//   DrawPlanes[nb] | the caller's head | extra (heat's host map) | host frames only: every frame's planes without their padding
+// The constructor refuses without a device, makes `device` current, takes the runtime lock (held until destruction), chooses the stream
+// (the caller's, else the utility stream) and fills the table: the caller's planes for device frames, the staged ones for host frames.
+// The caller then fills `head`, calls copy_in, launches on `s`, and calls copy_out.  mask: [nb], the frames that travel; null = all.
+struct DC_INTERNAL FrameStage {
+  FrameStage(const dc_frame* frames, int nb, int h, int w, bool is_device, int device, void* stream, size_t head_bytes, size_t extra_bytes = 0);
+  void copy_in(const char* mask = nullptr, const void* extra = nullptr);  // the table and the head, `extra`, the planes of host frames
+  void copy_out(const char* mask = nullptr);                              // the planes of host frames back (never their padding); the wait
+  hipStream_t s;
+  unsigned char* head;           // host: head_bytes zeros
+  const DrawPlanes* dev_frames;  // device: the table, the head, the extra block
+  unsigned char *dev_head, *dev_extra;
+
+ private:
+  void move_planes(const char* mask, bool to_host);
+  std::unique_lock<std::recursive_mutex> lock_;
+  const dc_frame* frames_;
+  int nb_, planes_, rows_[2], rb_[2];  // per plane: rows, and the bytes of a row
+  bool is_device_;
+  size_t extra_bytes_;
+  std::vector<unsigned char> host_;  // the table | the head
+};
 
 // ---- streams.cpp ------------------------------------------------------------------------------------
 std::vector<void*> executor_stream_pool(int device, size_t want);  // a COPY of the first `want` process-wide candidates

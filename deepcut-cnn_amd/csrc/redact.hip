@@ -4,25 +4,22 @@
 //
 // PARITY UNPINNED BY THE REFERENCE, which has nothing of the kind; the rule is this project's own.
 //
-// One workgroup per non-empty tile, one thread per 2 x 2 pixel block — draw_kernel's ownership, so the owner of a chroma sample owns
+// One workgroup per non-empty tile, one thread per 2 x 2 pixel block (frame_tile.h: the ownership), so the owner of a chroma sample owns
 // its luma pixels.  B is even and divides the tile: a thread's four pixels lie in ONE block, a block in ONE tile.  Three phases between
-// barriers: (1) coverage — the tile's primitives go through LDS as in draw.hip, a thread that finds one of its pixel centres covered
+// barriers: (1) coverage — the tile's primitives go through LDS a chunk at a time, a thread that finds one of its pixel centres covered
 // raises its block's flag; (2) sums — the threads of flagged blocks add their in-frame bytes into the block's LDS accumulators (integer
 // adds: any order gives the same sum); (3) stores — the same threads write the rounded means (or the fill colour) to their own pixels
 // and chroma sample.  Nobody else stores anything, and every byte is read before the barrier that precedes its store.
 #include <hip/hip_runtime.h>
 
-#include "draw_cover.h"
+#include "frame_tile.h"
 #include "kernels.h"
 
 namespace dc {
 
 namespace {
-constexpr int kFmtBgr = 0, kFmtNv12 = 1;  // DC_PIX_BGR24, DC_PIX_NV12
-constexpr int kBlocksX = kDrawTileW / 2, kBlocksY = kDrawTileH / 2;
 constexpr int kMaxRedactBlocks = kBlocksX * kBlocksY;  // B = 2: every thread a block of its own
-static_assert(kMaxRedactBlocks == 256, "one thread per 2 x 2 block of the tile; the flags and sums are cleared by one pass of the workgroup");
-static_assert(kDrawChunk <= 256, "a chunk is staged by one pass of the workgroup");
+static_assert(kMaxRedactBlocks == 256, "the flags and sums are cleared by one pass of the workgroup");
 static_assert(kDrawTileW == 32 && kDrawTileH == 32, "the block sizes 2 .. 32 divide the tile");
 
 // bshift = log2(B), 1 .. 5; fill: bytes as DrawPrim::colour (EFFECT == kRedactFill)
@@ -36,13 +33,12 @@ __global__ __launch_bounds__(256) void redact_kernel(const DrawPlanes* __restric
   __shared__ int acc[3][kMaxRedactBlocks];  // BGR24: B, G, R; NV12: Y, Cb, Cr
   const DrawTile t = tiles[blockIdx.x];
   const DrawPlanes f = frames[t.frame];
-  const int lx = 2 * ((int)threadIdx.x % kBlocksX), ly = 2 * ((int)threadIdx.x / kBlocksX);  // the thread's pixels within the tile
-  const int x0 = t.tx * kDrawTileW + lx, y0 = t.ty * kDrawTileH + ly;
-  const int blk = (ly >> bshift) * (kDrawTileW >> bshift) + (lx >> bshift);  // the thread's block within the tile
-  // the thread's pixels q = 2 * row + column; a thread whose pixels lie outside the frame only helps staging
+  // the thread's pixels; a thread whose pixels lie outside the frame only helps staging
+  int x0, y0;
   bool in[4];
-  int n_in = 0;
-  for (int q = 0; q < 4; ++q) in[q] = x0 + (q & 1) < W && y0 + (q >> 1) < H, n_in += in[q];
+  const int n_in = tile_block(t.tx * kDrawTileW, t.ty * kDrawTileH, H, W, x0, y0, in);
+  // the thread's B x B block within the tile
+  const int blk = ((y0 & (kDrawTileH - 1)) >> bshift) * (kDrawTileW >> bshift) + ((x0 & (kDrawTileW - 1)) >> bshift);
   flag[threadIdx.x] = 0;
   for (int c = 0; c < 3; ++c) acc[c][threadIdx.x] = 0;
 
@@ -50,10 +46,7 @@ __global__ __launch_bounds__(256) void redact_kernel(const DrawPlanes* __restric
   const int cx = 16 * x0 + 8, cy = 16 * y0 + 8;  // the centre of pixel 0
   bool hit = false;
   for (int base = 0; base < t.count; base += kDrawChunk) {
-    const int m = min(kDrawChunk, t.count - base);
-    __syncthreads();  // everybody is through with the chunk before (the first trip: the flags and sums are cleared)
-    if ((int)threadIdx.x < m) sp[threadIdx.x] = prims[index[t.first + base + (int)threadIdx.x]];
-    __syncthreads();
+    const int m = stage_chunk(sp, t, base, index, prims);  // its barriers: on the first trip the flags and sums are cleared
     if (!n_in || hit) continue;  // nothing left to find out, but the staging still needs this thread
     for (int i = 0; i < m && !hit; ++i) {
       const DrawPrim p = sp[i];

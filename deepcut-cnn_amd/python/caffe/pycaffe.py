@@ -1093,7 +1093,7 @@ def _per_image(v, dtype, tail):
 def _frames_and_people(frames, people, n_people):
     """What `draw_people` and `redact_people` take as frames and people -> (dc_frame[nb], nb, h, w, is_device, what to keep alive,
     people float64 [nb, P, J, 3], n_people int32 [nb], P, J)."""
-    arr, nb, h, w, is_device, keep = _heat_frames(frames)
+    arr, nb, h, w, is_device, keep = _writable_frames(frames)
     if isinstance(people, np.ndarray) and people.ndim in (3, 4):
         if people.shape[-1] != 3:
             raise ValueError("people must be [m, J, 3] or [nb, P, J, 3] (x, y, score), got shape %s" % (people.shape,))
@@ -1116,6 +1116,27 @@ def _frames_and_people(frames, people, n_people):
     if p < 1:
         ppl, p = np.zeros((nb, 1, j, 3), np.float64), 1
     return arr, nb, h, w, is_device, keep, ppl, n, p, j
+
+
+def _edges_array(edges):
+    """edges of `draw_people` and `redact_people` -> int32 [E, 2] (None: no limbs)."""
+    e = np.zeros((0, 2), np.int32) if edges is None else np.ascontiguousarray(edges, dtype=np.int32)
+    if e.ndim != 2 or e.shape[1] != 2:
+        raise ValueError("edges must be [E, 2] joints, got shape %s" % (e.shape,))
+    return e
+
+
+def _palette_array(palette):
+    """A palette of `draw_people` and `draw_heatmap` -> uint8 [n, 3]."""
+    pal = np.ascontiguousarray(palette, dtype=np.uint8)
+    if pal.ndim != 2 or pal.shape[1] != 3:
+        raise ValueError("palette must be [n, 3] R, G, B, got shape %s" % (pal.shape,))
+    return pal
+
+
+def _stream_arg(stream):
+    """The `stream` of the calls that write into frames, as the library takes it."""
+    return None if stream is None else C.c_void_p(int(stream))
 
 
 def draw_people(frames, people, n_people=None, ids=None, cand=None, edges=None, joint_radius=4.0, limb_radius=2.0, alpha=256, alpha_filled=128,
@@ -1142,12 +1163,8 @@ def draw_people(frames, people, n_people=None, ids=None, cand=None, edges=None, 
         raise ValueError("color must be one of %s, got %r" % (sorted(_DRAW_MODES), color))
     if palette is None:
         palette = DRAW_ID_COLORS if color == "id" else DRAW_JOINT_COLORS
-    pal = np.ascontiguousarray(palette, dtype=np.uint8)
-    if pal.ndim != 2 or pal.shape[1] != 3:
-        raise ValueError("palette must be [n, 3] R, G, B, got shape %s" % (pal.shape,))
-    e = np.zeros((0, 2), np.int32) if edges is None else np.ascontiguousarray(edges, dtype=np.int32)
-    if e.ndim != 2 or e.shape[1] != 2:
-        raise ValueError("edges must be [E, 2] joints, got shape %s" % (e.shape,))
+    pal = _palette_array(palette)
+    e = _edges_array(edges)
     st = DrawStyle()
     st.n_edges, st.edges = int(e.shape[0]), e.ctypes.data if e.shape[0] else None
     st.joint_radius, st.limb_radius = float(joint_radius), float(limb_radius)
@@ -1155,8 +1172,7 @@ def draw_people(frames, people, n_people=None, ids=None, cand=None, edges=None, 
     st.color_mode, st.palette, st.n_palette = _DRAW_MODES[color], pal.ctypes.data if pal.shape[0] else None, int(pal.shape[0])
     st.untracked[:] = [int(v) for v in untracked]
     ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-    _check(_lib.dc_draw_people(arr, nb, h, w, int(is_device), p, j, ptr(n), ptr(ppl), ptr(cnd), ptr(idv), C.byref(st),
-                               None if stream is None else C.c_void_p(int(stream))))
+    _check(_lib.dc_draw_people(arr, nb, h, w, int(is_device), p, j, ptr(n), ptr(ppl), ptr(cnd), ptr(idv), C.byref(st), _stream_arg(stream)))
 
 
 # ---- redacting people in frames (dc_redact_people; the rule: include/deepcut_hip.h — this project's own, the reference has none) -------
@@ -1220,9 +1236,7 @@ def redact_people(frames, people, n_people=None, select=None, ids=None, only_ids
         raise ValueError("effect must be one of %s, got %r" % (sorted(_REDACT_EFFECTS), effect))
     if head is None or len(head) != 2:
         raise ValueError("head must name the joint pair (neck, head top), got %r (pose.redact_people has the MPII one)" % (head,))
-    e = np.zeros((0, 2), np.int32) if edges is None else np.ascontiguousarray(edges, dtype=np.int32)
-    if e.ndim != 2 or e.shape[1] != 2:
-        raise ValueError("edges must be [E, 2] joints, got shape %s" % (e.shape,))
+    e = _edges_array(edges)
     st = RedactStyle()
     st.region, st.head_a, st.head_b = _REDACT_REGIONS[region], int(head[0]), int(head[1])
     st.head_scale, st.body_scale, st.min_radius, st.max_radius = float(head_scale), float(body_scale), float(min_radius), float(max_radius)
@@ -1231,8 +1245,7 @@ def redact_people(frames, people, n_people=None, select=None, ids=None, only_ids
     st.fill[:] = [int(v) for v in fill]
     out = np.zeros((nb, p), np.int32)
     ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-    _check(_lib.dc_redact_people(arr, nb, h, w, int(is_device), p, j, ptr(n), ptr(ppl), ptr(sel), C.byref(st), ptr(out),
-                                 None if stream is None else C.c_void_p(int(stream))))
+    _check(_lib.dc_redact_people(arr, nb, h, w, int(is_device), p, j, ptr(n), ptr(ppl), ptr(sel), C.byref(st), ptr(out), _stream_arg(stream)))
     return out[0, :people.shape[0]] if single else out
 
 
@@ -1254,8 +1267,9 @@ _HEAT_MODES = {"max": 0, "joints": 1}  # DC_HEAT_MAX, DC_HEAT_BY_JOINT
 _HEAT_ALPHA_MODES = {"const": 0, "score": 1}  # DC_HEAT_ALPHA_CONST, DC_HEAT_ALPHA_SCORE
 
 
-def _heat_frames(frames):
-    """frames of `draw_heatmap` -> (dc_frame[nb], nb, h, w, is_device, what to keep alive)."""
+def _writable_frames(frames):
+    """frames of the calls that write into them (`draw_people`, `redact_people`, `draw_heatmap`) -> (dc_frame[nb], nb, h, w, is_device,
+    what to keep alive)."""
     fl = _frame_list(frames)
     if fl is None:
         if isinstance(frames, np.ndarray) and frames.ndim == 3:
@@ -1280,9 +1294,7 @@ def _heat_style(channels, joints, mode, alpha, alpha_mode, min_score, lut, palet
     lt = np.ascontiguousarray(HEAT_LUT if lut is None else lut, dtype=np.uint8)
     if lt.shape != (256, 3):
         raise ValueError("lut must be [256, 3] R, G, B, got shape %s" % (lt.shape,))
-    pal = np.ascontiguousarray(DRAW_JOINT_COLORS if palette is None else palette, dtype=np.uint8)
-    if pal.ndim != 2 or pal.shape[1] != 3:
-        raise ValueError("palette must be [n, 3] R, G, B, got shape %s" % (pal.shape,))
+    pal = _palette_array(DRAW_JOINT_COLORS if palette is None else palette)
     st = HeatStyle()
     st.n_joints, st.joints = int(j.shape[0]), j.ctypes.data if j.shape[0] else None
     st.mode, st.alpha, st.alpha_mode, st.min_score = _HEAT_MODES[mode], int(alpha), _HEAT_ALPHA_MODES[alpha_mode], float(min_score)
@@ -1303,7 +1315,7 @@ def draw_heatmap(frames, scores, scale, origin=(0.0, 0.0), joints=None, mode="ma
     DRAW_JOINT_COLORS).  alpha 0 .. 256 (256 = opaque), alpha_mode "const" or "score" (alpha times the score); only scores >= min_score
     (0 .. 1) are blended.  stream: a HIP stream for device frames (None: the library's own).  The call returns when the blending is
     complete.  Needs GPU mode."""
-    arr, nb, h, w, is_device, _keep = _heat_frames(frames)
+    arr, nb, h, w, is_device, _keep = _writable_frames(frames)
     s = np.ascontiguousarray(scores, dtype=np.float32)
     if s.ndim == 3:
         s = s[None]
@@ -1312,7 +1324,7 @@ def draw_heatmap(frames, scores, scale, origin=(0.0, 0.0), joints=None, mode="ma
     st, _arrays = _heat_style(s.shape[1], joints, mode, alpha, alpha_mode, min_score, lut, palette)
     g = HeatGeometry(float(scale), float(origin[0]), float(origin[1]))
     _check(_lib.dc_draw_heatmap(arr, nb, h, w, int(is_device), s.ctypes.data_as(C.c_void_p), 0, s.shape[1], s.shape[2], s.shape[3], C.byref(g),
-                                C.byref(st), None if stream is None else C.c_void_p(int(stream))))
+                                C.byref(st), _stream_arg(stream)))
 
 
 class _Completing(object):
@@ -1976,7 +1988,7 @@ class Net(_Completing):
         """`prob` of the last forward blended into frames IN PLACE (dc_net_draw_heatmap): `caffe.draw_heatmap` on the map where it is on
         the device, in the net's element type — no download, no layout pass.  One frame per image of the forward; scale: what the forward
         ran at.  The other arguments as `caffe.draw_heatmap`.  Runs on the net's stream behind the forward and returns when complete."""
-        arr, nb, h, w, is_device, _keep = _heat_frames(frames)
+        arr, nb, h, w, is_device, _keep = _writable_frames(frames)
         st, _arrays = _heat_style(self.blobs["prob"].shape[1], joints, mode, alpha, alpha_mode, min_score, lut, palette)
         g = HeatGeometry(float(scale), float(origin[0]), float(origin[1]))
         _check(_lib.dc_net_draw_heatmap(self._h, arr, nb, h, w, int(is_device), C.byref(g), C.byref(st)))
@@ -2545,7 +2557,7 @@ class NetGroup(_Completing):
         `base`'s grid as `detect_parts` fuses it (base None: member 0) and blended at scales[base].  mirror / image_width / joint_mirror:
         as `fuse_maps` (dc_group_draw_heatmap_mirrored; the fused map is already un-mirrored).  The other arguments as `caffe.draw_heatmap`."""
         sc, base = self._scales(scales, 0 if base is None else base)
-        arr, nb, h, w, is_device, _keep = _heat_frames(frames)
+        arr, nb, h, w, is_device, _keep = _writable_frames(frames)
         st, _arrays = _heat_style(self.nets[0].blobs["prob"].shape[1], joints, mode, alpha, alpha_mode, min_score, lut, palette)
         fm, _keep2 = self._mirror(mirror, image_width, joint_mirror, None)
         _check(_lib.dc_group_draw_heatmap_mirrored(self._h, arr, nb, h, w, int(is_device), sc.ctypes.data_as(C.c_void_p), base, fm,
