@@ -1144,6 +1144,46 @@ int dc_redact_people(const dc_frame* frames, int nb, int height, int width, int 
   REQUIRE(people);
   return guard([&] { redact_people(frames, nb, height, width, is_device != 0, P, J, n_people, people, select, style, redacted, stream); });
 }
+// the overlays from people in device memory (overlay.cpp, people.cpp); a call without a style is refused there, naming the field
+static OverlayArgs overlay_args(const dc_draw_style* draw, const dc_redact_style* redact, const long long* only_ids, int n_only,
+                                const long long* keep_ids, int n_keep, int* redacted) {
+  OverlayArgs a;
+  a.draw = draw, a.redact = redact, a.only_ids = only_ids, a.n_only = n_only, a.keep_ids = keep_ids, a.n_keep = n_keep, a.redacted = redacted;
+  return a;
+}
+int dc_overlay_people_device(const dc_frame* frames, int nb, int height, int width, int is_device, int P, int J, const int* n_people,
+                             const double* people, const int* cand, const long long* ids, const dc_draw_style* draw,
+                             const dc_redact_style* redact, const long long* only_ids, int n_only, const long long* keep_ids, int n_keep,
+                             int* redacted, void* stream) {
+  REQUIRE(frames);
+  REQUIRE(n_people);
+  REQUIRE(people);
+  return guard([&] {
+    overlay_people_device(frames, nb, height, width, is_device != 0, P, J, n_people, people, cand, ids,
+                          overlay_args(draw, redact, only_ids, n_only, keep_ids, n_keep, redacted), stream);
+  });
+}
+int dc_net_track_frames_async_overlay(dc_net* net, dc_tracker* tracker, const dc_frame* frames, const unsigned char* images, int n, int height,
+                                      int width, double scale, int is_device, const int* slot_of, const dc_assemble_params* p, int n_edges,
+                                      const int* edges, const double* mean, const double* stdev, const int* joint_order, int* n_people,
+                                      double* people, int* cand, long long* ids, int* place, const dc_draw_style* draw,
+                                      const dc_redact_style* redact, const long long* only_ids, int n_only, const long long* keep_ids,
+                                      int n_keep, int* redacted) {
+  REQUIRE(net);
+  if (!frames) REQUIRE(images);
+  if (n <= 0 || height <= 0 || width <= 0) return fail(DC_EINVAL, "n, height and width must be positive");
+  if (!(scale > 0)) return fail(DC_EINVAL, "scale must be positive");
+  REQUIRE(p);
+  REQUIRE(n_people);
+  REQUIRE(people);
+  if (n_edges > 0) REQUIRE(edges);
+  return guard([&] {
+    Net::AssembleParams q{p->scale, p->threshold, p->radius, p->max_det, p->max_cost, p->seed_threshold, p->max_people, p->min_joints};
+    const OverlayArgs a = overlay_args(draw, redact, only_ids, n_only, keep_ids, n_keep, redacted);
+    N(net)->track_frames_async(tracker ? TR(tracker) : nullptr, frames, images, n, height, width, scale, is_device != 0, slot_of, q, n_edges,
+                               edges, mean, stdev, joint_order, n_people, people, cand, ids, place, &a);
+  });
+}
 // the score-map overlay (heat.cpp); null geometry / style / map are refused there, after the frames' own checks, naming the field
 int dc_draw_heatmap(const dc_frame* frames, int nb, int height, int width, int is_device, const float* map, int map_is_device, int C, int Hm,
                     int Wm, const dc_heat_geometry* geometry, const dc_heat_style* style, void* stream) {

@@ -11,14 +11,9 @@
 
 namespace dc {
 
-void draw_people(const dc_frame* frames, int nb, int h, int w, bool is_device, int P, int J, const int* n_people, const double* people,
-                 const int* cand, const long long* ids, const dc_draw_style* st, void* stream) {
-  const char* who = "draw_people";
+void check_draw_style(const char* who, const dc_draw_style* st, int J) {
   auto bad = [&](const std::string& m) { throw DcError(DC_EINVAL, std::string(who) + ": " + m); };
   auto in_range = [](double v, double lo, double hi) { return std::isfinite(v) && v >= lo && v <= hi; };
-  check_frame_dims(who, nb, h, w);
-  check_frames(who, frames, nb, h, w);
-  check_people_dims(who, P, J);
   if (!st) bad("null argument: style");
   check_edges(who, st->n_edges, st->edges, J);
   if (!in_range(st->joint_radius, 0.0, 64.0)) bad("joint_radius must be in [0, 64]");
@@ -29,6 +24,16 @@ void draw_people(const dc_frame* frames, int nb, int h, int w, bool is_device, i
   if (st->color_mode != DC_DRAW_BY_PERSON && st->color_mode != DC_DRAW_BY_JOINT) bad("color_mode must be DC_DRAW_BY_PERSON or DC_DRAW_BY_JOINT");
   if (!st->palette) bad("null argument: palette");
   if (st->n_palette < 1 || st->n_palette > 256) bad("n_palette must be in [1, 256]");
+}
+
+void draw_people(const dc_frame* frames, int nb, int h, int w, bool is_device, int P, int J, const int* n_people, const double* people,
+                 const int* cand, const long long* ids, const dc_draw_style* st, void* stream) {
+  const char* who = "draw_people";
+  auto bad = [&](const std::string& m) { throw DcError(DC_EINVAL, std::string(who) + ": " + m); };
+  check_frame_dims(who, nb, h, w);
+  check_frames(who, frames, nb, h, w);
+  check_people_dims(who, P, J);
+  check_draw_style(who, st, J);
   check_n_people(who, n_people, nb, P);
   if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "draw_people() in CPU mode");
 

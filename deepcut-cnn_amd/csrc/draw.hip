@@ -27,18 +27,7 @@ __global__ __launch_bounds__(256) void draw_kernel(const DrawPlanes* __restrict_
   for (int base = 0; base < t.count; base += kDrawChunk) {
     const int m = stage_chunk(sp, t, base, index, prims);
     if (!px.n_in) continue;
-    for (int i = 0; i < m; ++i) {
-      const DrawPrim p = sp[i];
-      if (draw_block_outside(p, cx, cy)) continue;
-      int k = 0;
-      for (int q = 0; q < 4; ++q) {
-        if (!px.in[q] || !draw_covers(p, cx + 16 * (q & 1), cy + 16 * (q >> 1))) continue;
-        ++k;
-        px.blend_pixel(q, p.colour, p.alpha);
-      }
-      // the chroma sample once per primitive, by the share of the block's in-frame pixels it covers
-      if (FMT == kFmtNv12 && k) px.blend_chroma(p.colour, (p.alpha * k + px.n_in / 2) / px.n_in);
-    }
+    draw_chunk(px, sp, m, cx, cy);
   }
   px.store(f);
 }

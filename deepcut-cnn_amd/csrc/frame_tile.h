@@ -103,4 +103,90 @@ __device__ __forceinline__ bool draw_block_outside(const DrawPrim& p, int cx, in
          cy > max(p.ay, p.by) + p.r16;
 }
 
+// ---- what a tile does with a chunk of primitives in LDS, shared by the kernels that are handed bins (draw.hip, redact.hip) and the
+// ones that bin for themselves (overlay.hip) ---------------------------------------------------------------------------------------------
+
+// The drawing rule on sp[0 .. m), in order, for the thread's block; (cx, cy) is the centre of pixel 0
+template <int FMT>
+__device__ __forceinline__ void draw_chunk(BlockPixels<FMT>& px, const DrawPrim* sp, int m, int cx, int cy) {
+  for (int i = 0; i < m; ++i) {
+    const DrawPrim p = sp[i];
+    if (draw_block_outside(p, cx, cy)) continue;
+    int k = 0;
+    for (int q = 0; q < 4; ++q) {
+      if (!px.in[q] || !draw_covers(p, cx + 16 * (q & 1), cy + 16 * (q >> 1))) continue;
+      ++k;
+      px.blend_pixel(q, p.colour, p.alpha);
+    }
+    // the chroma sample once per primitive, by the share of the block's in-frame pixels it covers
+    if (FMT == kFmtNv12 && k) px.blend_chroma(p.colour, (p.alpha * k + px.n_in / 2) / px.n_in);
+  }
+}
+
+// The redaction's phase 1 on sp[0 .. m): is the centre of one of the thread's in-frame pixels covered?  A set: `hit` only ever rises
+__device__ __forceinline__ void redact_cover_chunk(bool& hit, const bool (&in)[4], const DrawPrim* sp, int m, int cx, int cy) {
+  for (int i = 0; i < m && !hit; ++i) {
+    const DrawPrim p = sp[i];
+    if (draw_block_outside(p, cx, cy)) continue;
+    for (int q = 0; q < 4; ++q) hit = hit || (in[q] && draw_covers(p, cx + 16 * (q & 1), cy + 16 * (q >> 1)));
+  }
+}
+
+constexpr int kMaxRedactBlocks = kBlocksX * kBlocksY;  // B = 2: every thread a block of its own
+static_assert(kMaxRedactBlocks == 256, "the flags and sums are cleared by one pass of the workgroup");
+static_assert(kDrawTileW == 32 && kDrawTileH == 32, "the block sizes 2 .. 32 divide the tile");
+
+// the thread's B x B block within the tile, B = 1 << bshift
+__device__ __forceinline__ int redact_block_of(int x0, int y0, int bshift) {
+  return ((y0 & (kDrawTileH - 1)) >> bshift) * (kDrawTileW >> bshift) + ((x0 & (kDrawTileW - 1)) >> bshift);
+}
+
+// The redaction's phases 2 and 3 behind phase 1: flag[kMaxRedactBlocks] and acc[3][kMaxRedactBlocks] (LDS) were cleared before a barrier
+// that every thread has passed; EVERY thread of the workgroup calls this (it holds barriers).  (2) sums — the threads of flagged blocks
+// add their in-frame bytes into the block's accumulators (integer adds: any order gives the same sum); (3) stores — the same threads
+// write the rounded means (or the fill colour) to their own pixels and chroma sample.  fill: bytes as DrawPrim::colour
+template <int FMT, int EFFECT>
+__device__ __forceinline__ void redact_finish(const DrawPlanes& f, int H, int W, int x0, int y0, const bool (&in)[4], int n_in, int blk, bool hit,
+                                              int bshift, unsigned fill, int* flag, int (*acc)[kMaxRedactBlocks]) {
+  constexpr int NC = FMT == kFmtBgr ? 3 : 1;  // bytes per pixel of plane 0
+  if (hit) flag[blk] = 1;  // every writer writes the same value
+  __syncthreads();
+  const bool mine = n_in && flag[blk];  // the thread has pixels in a selected block
+
+  unsigned char* const d0 = f.plane0 + (long)y0 * f.pitch0 + (long)x0 * NC;  // pixel 0; dereferenced for in-frame pixels only
+  unsigned char* const chroma = FMT == kFmtNv12 ? f.plane1 + (long)(y0 >> 1) * f.pitch1 + (long)(x0 >> 1) * 2 : nullptr;
+  int out[3] = {(int)(fill & 255), (int)(fill >> 8 & 255), (int)(fill >> 16 & 255)};
+  if (EFFECT == kRedactMosaic) {
+    // ---- 2. sums: the thread's in-frame bytes, and its chroma sample, into the block's accumulators ----------------------------------
+    if (mine) {
+      int s[3] = {0, 0, 0};
+      for (int q = 0; q < 4; ++q) {
+        if (!in[q]) continue;
+        const unsigned char* src = d0 + (long)(q >> 1) * f.pitch0 + (q & 1) * NC;
+        for (int c = 0; c < NC; ++c) s[c] += (int)src[c];
+      }
+      if (FMT == kFmtNv12) s[1] = chroma[0], s[2] = chroma[1];
+      for (int c = 0; c < 3; ++c) atomicAdd(&acc[c][blk], s[c]);
+    }
+    __syncthreads();
+    if (mine) {
+      // the block's in-frame pixels n and chroma samples m: it starts at an even pixel, so a partial row or column of samples counts
+      const int B = 1 << bshift, bw = min(B, W - ((x0 >> bshift) << bshift)), bh = min(B, H - ((y0 >> bshift) << bshift));
+      const int n = bw * bh, mc = ((bw + 1) >> 1) * ((bh + 1) >> 1);
+      for (int c = 0; c < 3; ++c) {
+        const int k = (FMT == kFmtNv12 && c > 0) ? mc : n;
+        out[c] = (int)((unsigned)(acc[c][blk] + k / 2) / (unsigned)k);
+      }
+    }
+  }
+  // ---- 3. stores: the thread's own in-frame pixels and its own chroma sample ---------------------------------------------------------
+  if (!mine) return;
+  for (int q = 0; q < 4; ++q) {
+    if (!in[q]) continue;
+    unsigned char* d = d0 + (long)(q >> 1) * f.pitch0 + (q & 1) * NC;
+    for (int c = 0; c < NC; ++c) d[c] = (unsigned char)out[c];
+  }
+  if (FMT == kFmtNv12) chroma[0] = (unsigned char)out[1], chroma[1] = (unsigned char)out[2];
+}
+
 }  // namespace dc

@@ -467,6 +467,42 @@ constexpr int kRedactMosaic = 0, kRedactFill = 1;  // DC_REDACT_MOSAIC, DC_REDAC
 int launch_redact(int format, int effect, int block, unsigned fill, const DrawPlanes* frames, int height, int width, const DrawTile* tiles,
                   int n_tiles, const int* index, const DrawPrim* prims, void* stream);
 
+// Overlays from people in device memory (overlay.hip; the rules are dc_draw_people's and dc_redact_people's, the bytes theirs).  A builder
+// kernel — one workgroup per frame, one thread per person — makes the DrawPrims draw.cpp / redact.cpp make on the host, in their order,
+// dropping what TileBins::add drops; self-binning forms of the two tile kernels then run over EVERY tile of every frame, each workgroup
+// walking its frame's primitives in passes of 256, compacting in order those whose grown box holds a pixel centre of the tile
+// (TileBins::add's rule) and handing them to the tile code of frame_tile.h.  A tile nothing reaches loads and stores no pixel.
+constexpr int kOverlayMaxIds = 256;  // only_ids / keep_ids, each
+constexpr int kOverlayMaxFrames = 64;  // the frame entries' limit on nb
+// a host list of n ids (<= kOverlayMaxIds) / a host table of nb frames (<= kOverlayMaxFrames) into device memory AS KERNEL ARGUMENTS of a
+// one-workgroup launch: no host buffer has to outlive an upload, and the host waits for nothing
+int launch_overlay_put_ids(const long long* host, int n, long long* to, void* stream);
+int launch_overlay_put_frames(const DrawPlanes* host, int nb, DrawPlanes* to, void* stream);
+struct OverlayBuild {                // a builder launch's arguments, by value (below the 4 KiB of kernel arguments)
+  int redact;                        // 0: the drawing's primitives; 1: the redaction's
+  int P, J, H, W, n_edges;
+  unsigned char edges[2 * 128];      // [n_edges][2]
+  double min_score;
+  // the drawing: r16 of joints and limbs, the alphas, the colours as DrawPrim::colour (converted on the host)
+  int rj, rl, alpha, alpha_filled, by_person, n_palette;
+  unsigned untracked, palette[256];
+  // the redaction: dc_redact_style's fields, the radius bounds as rint(16 radius); n_only / n_keep < 0: no such list
+  int region, head_a, head_b, n_only, n_keep;
+  double head_scale, body_scale, r_lo, r_hi;
+};
+// primitives a person can make at the most, and so a frame's stretch of `prims`: P * overlay_prims_per_person
+constexpr int overlay_prims_per_person(int J, int n_edges) { return 1 + n_edges + J; }
+// n_people [nb], people [nb][P][J][3], cand [nb][P][J] or null, ids [nb][P] or null, only_ids / keep_ids (read when n_only / n_keep >= 0)
+// -> prims [nb][P * per_person] (frame b's first n_prims[b] entries), n_prims [nb], redacted [nb][P] or null (the redaction's).  Every
+// pointer is device memory.  Grid = nb.
+int launch_overlay_build(const OverlayBuild& q, int nb, const int* n_people, const double* people, const int* cand, const long long* ids,
+                         const long long* only_ids, const long long* keep_ids, DrawPrim* prims, int* n_prims, int* redacted, void* stream);
+// the tile kernels over all tiles of nb frames: prims / n_prims as the builder left them, stride = P * per_person
+int launch_draw_all(int format, const DrawPlanes* frames, int nb, int height, int width, const DrawPrim* prims, const int* n_prims,
+                    int stride, void* stream);
+int launch_redact_all(int format, int effect, int block, unsigned fill, const DrawPlanes* frames, int nb, int height, int width,
+                      const DrawPrim* prims, const int* n_prims, int stride, void* stream);
+
 // Score-map overlay (heat.hip; the rule: include/deepcut_hip.h, dc_draw_heatmap — this project's own).  The host (heat.cpp) computes
 // the per-axis sample tables t = rint(256 u), clamped, and converts the colours; one workgroup blends one kDrawTileW x kDrawTileH pixel
 // tile of one frame, one thread one 2 x 2 pixel block (the ownership), after staging the patch of map cells the tile's tables

@@ -300,6 +300,24 @@ void dedupe_people(const dc_dedupe_params* params, int nb, int P, int J, const i
 void draw_people(const dc_frame* frames, int nb, int h, int w, bool is_device, int P, int J, const int* n_people, const double* people,
                  const int* cand, const long long* ids, const dc_draw_style* style, void* stream);
 void draw_limits(int* tile_w, int* tile_h, int* chunk);
+// The overlays of dc_overlay_people_device / dc_net_track_frames_async_overlay: either style or both (redaction first), the id lists
+// of the redaction (n < 0: no such list) and where `redacted` [nb][P] goes (may be null) — device memory for the stand-alone entry,
+// the caller's host array for the chain
+struct OverlayArgs {
+  const dc_draw_style* draw = nullptr;
+  const dc_redact_style* redact = nullptr;
+  const long long* only_ids = nullptr;
+  int n_only = -1;
+  const long long* keep_ids = nullptr;
+  int n_keep = -1;
+  int* redacted = nullptr;
+  bool any() const { return draw || redact; }
+};
+// dc_overlay_people_device (overlay.cpp): the bytes of redact_people then draw_people from people, cand and ids in DEVICE memory, the
+// primitives and the tile selection made on the device.  Asynchronous on a caller's stream with device frames, else it waits
+void overlay_people_device(const dc_frame* frames, int nb, int h, int w, bool is_device, int P, int J, const int* d_n_people,
+                           const double* d_people, const int* d_cand, const long long* d_ids, const OverlayArgs& overlay, void* stream);
+
 // dc_redact_people (redact.cpp): regions derived from people's joints replaced by a mosaic or a colour, in place on the device, synchronous
 void redact_people(const dc_frame* frames, int nb, int h, int w, bool is_device, int P, int J, const int* n_people, const double* people,
                    const unsigned char* select, const dc_redact_style* style, int* redacted, void* stream);
@@ -434,7 +452,11 @@ struct Net {
   // make them; everything small is copied before the return; frame planes and output arrays stay the caller's until synchronize().
   void track_frames_async(Tracker* tracker, const dc_frame* frames, const unsigned char* bgr, int n, int h, int w, double scale, bool is_device,
                           const int* slot_of, const AssembleParams& p, int n_edges, const int* edges, const double* mean, const double* stdev,
-                          const int* joint_order, int* n_people, double* people, int* cand, long long* ids, int* place);
+                          const int* joint_order, int* n_people, double* people, int* cand, long long* ids, int* place,
+                          const OverlayArgs* overlay = nullptr);
+  // ... with `overlay` (dc_net_track_frames_async_overlay) the frames are redacted and drawn into behind the tracker, from the people,
+  // cand and ids where the chain left them on the device: the builders in front of the tracker's event (they read its scratch), the tile
+  // kernels behind it, on the planes frame_source staged for host frames, which then travel back; overlay->redacted is a host array
   // front half of forward_images: the uint8 pixels -> the network's NHWC input image, enqueued on s (the plan of the canvas
   // shape is active afterwards); returns the canvas height / width
   // mirror: the images are read flipped left to right (ImagePrepParams::mirror; NetGroup::forward_images hands it down)
@@ -545,6 +567,7 @@ struct Net {
   DevBuf scratch_dev_;  // candidates / detections / pairwise scratch
   void* scratch(size_t bytes) { return scratch_dev_.get(bytes); }
   DevBuf img_dev_;  // uint8 source images uploaded from the host
+  DevBuf overlay_dev_;  // the overlays of track_frames_async: OverlayPlan's block (net_internal.h)
   const unsigned char* upload_image(const unsigned char* host, size_t bytes, void* s);  // -> the device copy in img_dev_, enqueued on s
   DevBuf frame_dev_;   // frame entries: FramePlanes[n], the frame readers' plane table
   std::vector<FramePlanes> frame_host_;  // the host side of that table (device addresses): uploaded only when it differs from what is there
@@ -619,8 +642,12 @@ struct Tracker {
   // ... and, after prepare, still under the lock: `stream` waits for the update before, then the launch on d_np / d_ppl (slot_of checked,
   // or null) and the downloads of ids / place / dist (any null), then the event is recorded.  No host wait.
   // With smoothing on step 8 runs in the same launch, and `so` (may be null) says where its results go.
+  // before_done (may be null): called behind the launch and IN FRONT OF the event's record with what the update left in the shared
+  // scratch — the people (step 8's with smoothing on, else d_ppl), cand (step 8's cand_out with smoothing on, null when it made none;
+  // else `d_cand`) and the ids.  Whatever it enqueues on `stream` reads the scratch before the next update may overwrite it.
+  using BeforeDone = std::function<void(const double* d_people, const int* d_cand, const long long* d_ids)>;
   void enqueue(int nb, int P, const int* slot_of, const int* d_np, const double* d_ppl, long long* ids, int* place, double* dist, void* stream,
-               const SmoothOut* so = nullptr);
+               const SmoothOut* so = nullptr, const BeforeDone* before_done = nullptr, const int* d_cand = nullptr);
   void update(int nb, int P, const int* slot_of, const int* n_people, const double* people, long long* ids, int* place, double* dist,
               double* smooth_out = nullptr, int* src = nullptr, bool smoothed = false);
   // host only, ordered like set_option; null: off.  Off -> on starts with empty filters, a change while on keeps them
@@ -629,7 +656,7 @@ struct Tracker {
   // for the chained entries' `after` hook: enqueue, and with smoothing on deliver people / cand from step 8 -> true (the caller then
   // downloads neither itself)
   bool enqueue_chained(int nb, int P, const int* slot_of, const int* d_np, const double* d_ppl, const int* d_cand, long long* ids, int* place,
-                       double* people, int* cand, void* stream);
+                       double* people, int* cand, void* stream, const BeforeDone* before_done = nullptr);
   void reset(int slot);  // -1: all
   // DC_TRACK_OPT_*: host only (no device needed); set waits for the last update enqueued, then stores: later updates use the value
   void set_option(int key, int value);

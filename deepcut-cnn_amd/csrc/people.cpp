@@ -306,26 +306,84 @@ void Net::assemble_last(const AssembleParams& q_in, const std::vector<int>& tabl
 void Net::track_frames_async(Tracker* tracker, const dc_frame* frames, const unsigned char* bgr, int n, int h, int w, double scale,
                              bool is_device, const int* slot_of, const AssembleParams& p, int n_edges, const int* edges, const double* mean,
                              const double* stdev, const int* joint_order, int* n_people, double* people, int* cand, long long* ids,
-                             int* place) {
+                             int* place, const OverlayArgs* overlay) {
+  const char* who = "track_frames_async";
   // what forward_images refuses ...
-  if (frames) check_frames("track_frames_async", frames, n, h, w);
+  if (frames) check_frames(who, frames, n, h, w);
   // ... what assemble_people refuses (the batch of the forward to come is n; the joints do not depend on it) ...
   check_assemble_params(p);
   const std::vector<int>& pshape = prob_shape();
   const std::vector<int> table = check_assemble_graph(p, pshape[1], n_edges, edges, mean, stdev, joint_order);
   // ... and what the tracker refuses
-  if (tracker) tracker->check_call("track_frames_async", n, p.max_people, pshape[1], slot_of);
+  if (tracker) tracker->check_call(who, n, p.max_people, pshape[1], slot_of);
   else if (ids) throw DcError(DC_EINVAL, "track_frames_async: ids without a tracker (ids must be NULL when tracker is NULL)");
+  // ... and what the overlays refuse, in the words of dc_draw_people and dc_redact_people
+  std::unique_ptr<OverlayPlan> plan;
+  if (overlay && overlay->any()) {
+    check_frame_dims(who, n, h, w);
+    check_people_dims(who, p.max_people, pshape[1]);
+    dc_frame packed{};
+    packed.format = DC_PIX_BGR24;
+    plan.reset(new OverlayPlan(who, frames ? frames[0] : packed, n, h, w, p.max_people, pshape[1], *overlay, tracker != nullptr));
+  }
   if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "track_frames_async() in CPU mode");
   prep_images(bgr, n, h, w, scale, is_device, nullptr, false, frames);
   enqueue_plan(stream);
   AfterPeople after;
-  if (tracker)
+  if (!plan) {
+    if (tracker)
+      after = [&](const int* d_np, const double* d_ppl, const int* d_cand) {
+        RuntimeLock rl;  // for the enqueue only: the tracker's event keeps the order from here on
+        tracker->prepare(device, n, stream);
+        return tracker->enqueue_chained(n, p.max_people, slot_of, d_np, d_ppl, d_cand, ids, place, people, cand, stream);
+      };
+  } else {
     after = [&](const int* d_np, const double* d_ppl, const int* d_cand) {
-      RuntimeLock rl;  // for the enqueue only: the tracker's event keeps the order from here on
-      tracker->prepare(device, n, stream);
-      return tracker->enqueue_chained(n, p.max_people, slot_of, d_np, d_ppl, d_cand, ids, place, people, cand, stream);
+      unsigned char* block = (unsigned char*)overlay_dev_.get(plan->bytes);
+      int* d_redacted = reinterpret_cast<int*>(block + plan->at_redacted);
+      bool delivered = false;
+      if (tracker) {
+        // the builders read the people, cand and ids the update leaves in the tracker's shared scratch: in front of its event
+        const Tracker::BeforeDone build = [&](const double* t_ppl, const int* t_cand, const long long* t_ids) {
+          plan->build(block, n, d_np, t_ppl, t_cand, t_ids, d_redacted, stream);
+        };
+        RuntimeLock rl;  // for the enqueue only: the tracker's event keeps the order from here on
+        tracker->prepare(device, n, stream);
+        delivered = tracker->enqueue_chained(n, p.max_people, slot_of, d_np, d_ppl, d_cand, ids, place, people, cand, stream, &build);
+      } else {
+        plan->build(block, n, d_np, d_ppl, cand ? d_cand : nullptr, nullptr, d_redacted, stream);
+      }
+      // the tile kernels read the net's own block: behind the event.  Host pixels were staged by the pre-processing and are written there
+      hipStream_t s = (hipStream_t)stream;
+      std::vector<DrawPlanes> planes((size_t)n);
+      const size_t image = (size_t)h * w * 3;
+      for (int b = 0; b < n; ++b) {
+        if (frames) {
+          const FramePlanes& f = frame_host_[(size_t)b];
+          planes[(size_t)b] = DrawPlanes{const_cast<unsigned char*>(f.plane0), const_cast<unsigned char*>(f.plane1), f.pitch0, f.pitch1};
+        } else {
+          unsigned char* base = is_device ? const_cast<unsigned char*>(bgr) : img_dev_.dev;
+          planes[(size_t)b] = DrawPlanes{base + image * b, nullptr, 3 * w, 0};
+        }
+      }
+      plan->tiles(block, planes.data(), n, stream);
+      if (!is_device) {  // every host frame travels back (which of them is touched is known on the device only), never its padding
+        if (!frames) HIPCHECK(hipMemcpyAsync(const_cast<unsigned char*>(bgr), img_dev_.dev, image * n, hipMemcpyDeviceToHost, s));
+        for (int b = 0; frames && b < n; ++b) {
+          const DrawPlanes& d = planes[(size_t)b];
+          const bool nv12 = frames[b].format == DC_PIX_NV12;
+          HIPCHECK(hipMemcpy2DAsync(const_cast<void*>(frames[b].plane[0]), (size_t)frames[b].pitch[0], d.plane0, (size_t)d.pitch0,
+                                    (size_t)d.pitch0, (size_t)h, hipMemcpyDeviceToHost, s));
+          if (nv12)
+            HIPCHECK(hipMemcpy2DAsync(const_cast<void*>(frames[b].plane[1]), (size_t)frames[b].pitch[1], d.plane1, (size_t)d.pitch1,
+                                      (size_t)d.pitch1, (size_t)((h + 1) / 2), hipMemcpyDeviceToHost, s));
+        }
+      }
+      if (plan->redact && overlay->redacted)
+        HIPCHECK(hipMemcpyAsync(overlay->redacted, d_redacted, (size_t)n * p.max_people * sizeof(int), hipMemcpyDeviceToHost, s));
+      return delivered;
     };
+  }
   assemble_last(p, table, n_edges, mean, stdev, n_people, people, cand, nullptr, after, false);
 }
 

@@ -18,14 +18,9 @@ int clamp_int(double v, double lo, double hi) { return (int)std::min(std::max(v,
 
 }  // namespace
 
-void redact_people(const dc_frame* frames, int nb, int h, int w, bool is_device, int P, int J, const int* n_people, const double* people,
-                   const unsigned char* select, const dc_redact_style* st, int* redacted, void* stream) {
-  const char* who = "redact_people";
+void check_redact_style(const char* who, const dc_redact_style* st, int J) {
   auto bad = [&](const std::string& m) { throw DcError(DC_EINVAL, std::string(who) + ": " + m); };
   auto scale_ok = [](double v) { return std::isfinite(v) && v >= 0.0; };
-  check_frame_dims(who, nb, h, w);
-  check_frames(who, frames, nb, h, w);
-  check_people_dims(who, P, J);
   if (!st) bad("null argument: style");
   if (st->region != DC_REDACT_HEAD && st->region != DC_REDACT_BODY && st->region != DC_REDACT_HEAD_OR_BODY)
     bad("region must be DC_REDACT_HEAD, DC_REDACT_BODY or DC_REDACT_HEAD_OR_BODY");
@@ -41,6 +36,16 @@ void redact_people(const dc_frame* frames, int nb, int h, int w, bool is_device,
   if (st->min_radius > st->max_radius) bad("min_radius must not be above max_radius");
   if (!scale_ok(st->min_score)) bad("min_score must be finite and >= 0");
   check_edges(who, st->n_edges, st->edges, J);
+}
+
+void redact_people(const dc_frame* frames, int nb, int h, int w, bool is_device, int P, int J, const int* n_people, const double* people,
+                   const unsigned char* select, const dc_redact_style* st, int* redacted, void* stream) {
+  const char* who = "redact_people";
+  auto bad = [&](const std::string& m) { throw DcError(DC_EINVAL, std::string(who) + ": " + m); };
+  check_frame_dims(who, nb, h, w);
+  check_frames(who, frames, nb, h, w);
+  check_people_dims(who, P, J);
+  check_redact_style(who, st, J);
   check_n_people(who, n_people, nb, P);
   if (Context::get().mode != DC_MODE_GPU) throw DcError(DC_ENOCPU, "redact_people() in CPU mode");
 

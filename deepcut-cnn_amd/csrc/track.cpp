@@ -124,7 +124,7 @@ void Tracker::prepare(int on_device, int nb, void* stream) {
 }
 
 void Tracker::enqueue(int nb, int P, const int* slot_of, const int* d_np, const double* d_ppl, long long* ids, int* place, double* dist,
-                      void* stream, const SmoothOut* so) {
+                      void* stream, const SmoothOut* so, const BeforeDone* before_done, const int* d_cand) {
   hipStream_t s = (hipStream_t)stream;
   long long* d_ids = (long long*)(img_dev + off_ids);
   int* d_place = (int*)(img_dev + off_place);
@@ -148,6 +148,7 @@ void Tracker::enqueue(int nb, int P, const int* slot_of, const int* d_np, const 
     if (so->src) HIPCHECK(hipMemcpyAsync(so->src, sm.src, e * sizeof(int), hipMemcpyDeviceToHost, s));
     if (so->cand && sm.cand_out) HIPCHECK(hipMemcpyAsync(so->cand, sm.cand_out, e * sizeof(int), hipMemcpyDeviceToHost, s));
   }
+  if (before_done && *before_done) (*before_done)(on ? sm.smooth : d_ppl, on ? sm.cand_out : d_cand, d_ids);  // likewise
   if (ids) HIPCHECK(hipMemcpyAsync(ids, d_ids, (size_t)nb * P * sizeof(long long), hipMemcpyDeviceToHost, s));
   if (place) HIPCHECK(hipMemcpyAsync(place, d_place, (size_t)nb * P * sizeof(int), hipMemcpyDeviceToHost, s));
   for (int b = 0; dist && b < nb; ++b)
@@ -157,14 +158,14 @@ void Tracker::enqueue(int nb, int P, const int* slot_of, const int* d_np, const 
 }
 
 bool Tracker::enqueue_chained(int nb, int P, const int* slot_of, const int* d_np, const double* d_ppl, const int* d_cand, long long* ids,
-                              int* place, double* people, int* cand, void* stream) {
+                              int* place, double* people, int* cand, void* stream, const BeforeDone* before_done) {
   if (!smooth.enabled) {
-    enqueue(nb, P, slot_of, d_np, d_ppl, ids, place, nullptr, stream);
+    enqueue(nb, P, slot_of, d_np, d_ppl, ids, place, nullptr, stream, nullptr, before_done, cand ? d_cand : nullptr);
     return false;
   }
   SmoothOut so;
   so.people = people, so.d_cand = cand ? d_cand : nullptr, so.cand = cand;
-  enqueue(nb, P, slot_of, d_np, d_ppl, ids, place, nullptr, stream, &so);
+  enqueue(nb, P, slot_of, d_np, d_ppl, ids, place, nullptr, stream, &so, before_done);
   return true;
 }
 

@@ -413,6 +413,10 @@ def _load():
         "dc_draw_people": (ci, [C.POINTER(DcFrame), ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, C.POINTER(DrawStyle), vp]),
         "dc_draw_limits": (ci, [C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]),
         "dc_redact_people": (ci, [C.POINTER(DcFrame), ci, ci, ci, ci, ci, ci, vp, vp, vp, C.POINTER(RedactStyle), vp, vp]),
+        "dc_overlay_people_device": (ci, [C.POINTER(DcFrame), ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, C.POINTER(DrawStyle), C.POINTER(RedactStyle),
+                                          vp, ci, vp, ci, vp, vp]),
+        "dc_net_track_frames_async_overlay": (ci, [vp, vp, vp, vp, ci, ci, ci, C.c_double, ci, vp, C.POINTER(AssembleParams), ci, vp, vp, vp, vp,
+                                                   vp, vp, vp, vp, vp, C.POINTER(DrawStyle), C.POINTER(RedactStyle), vp, ci, vp, ci, vp]),
         "dc_draw_heatmap": (ci, [C.POINTER(DcFrame), ci, ci, ci, ci, vp, ci, ci, ci, ci, C.POINTER(HeatGeometry), C.POINTER(HeatStyle), vp]),
         "dc_net_draw_heatmap": (ci, [vp, C.POINTER(DcFrame), ci, ci, ci, ci, C.POINTER(HeatGeometry), C.POINTER(HeatStyle)]),
         "dc_group_draw_heatmap": (ci, [vp, C.POINTER(DcFrame), ci, ci, ci, ci, vp, ci, C.c_double, C.c_double, C.POINTER(HeatStyle)]),
@@ -1139,6 +1143,25 @@ def _stream_arg(stream):
     return None if stream is None else C.c_void_p(int(stream))
 
 
+def _draw_style_struct(edges=None, joint_radius=4.0, limb_radius=2.0, alpha=256, alpha_filled=128, min_score=0.0, color="id", palette=None,
+                       untracked=(128, 128, 128)):
+    """The style arguments of `draw_people` -> (DrawStyle, the arrays it points into).  Names and shapes are checked here; the values are
+    the library's to refuse."""
+    if color not in _DRAW_MODES:
+        raise ValueError("color must be one of %s, got %r" % (sorted(_DRAW_MODES), color))
+    if palette is None:
+        palette = DRAW_ID_COLORS if color == "id" else DRAW_JOINT_COLORS
+    pal = _palette_array(palette)
+    e = _edges_array(edges)
+    st = DrawStyle()
+    st.n_edges, st.edges = int(e.shape[0]), e.ctypes.data if e.shape[0] else None
+    st.joint_radius, st.limb_radius = float(joint_radius), float(limb_radius)
+    st.alpha, st.alpha_filled, st.min_score = int(alpha), int(alpha_filled), float(min_score)
+    st.color_mode, st.palette, st.n_palette = _DRAW_MODES[color], pal.ctypes.data if pal.shape[0] else None, int(pal.shape[0])
+    st.untracked[:] = [int(v) for v in untracked]
+    return st, (pal, e)
+
+
 def draw_people(frames, people, n_people=None, ids=None, cand=None, edges=None, joint_radius=4.0, limb_radius=2.0, alpha=256, alpha_filled=128,
                 min_score=0.0, color="id", palette=None, untracked=(128, 128, 128), stream=None):
     """Skeletons blended into frames IN PLACE on the device (dc_draw_people; the rule — integer only, this project's own: the reference
@@ -1159,18 +1182,7 @@ def draw_people(frames, people, n_people=None, ids=None, cand=None, edges=None, 
     idv = None if ids is None else _per_image(ids, np.int64, ())
     if idv is not None and idv.shape != ppl.shape[:2]:
         raise ValueError("ids must be %s like people, got shape %s" % (ppl.shape[:2], idv.shape))
-    if color not in _DRAW_MODES:
-        raise ValueError("color must be one of %s, got %r" % (sorted(_DRAW_MODES), color))
-    if palette is None:
-        palette = DRAW_ID_COLORS if color == "id" else DRAW_JOINT_COLORS
-    pal = _palette_array(palette)
-    e = _edges_array(edges)
-    st = DrawStyle()
-    st.n_edges, st.edges = int(e.shape[0]), e.ctypes.data if e.shape[0] else None
-    st.joint_radius, st.limb_radius = float(joint_radius), float(limb_radius)
-    st.alpha, st.alpha_filled, st.min_score = int(alpha), int(alpha_filled), float(min_score)
-    st.color_mode, st.palette, st.n_palette = _DRAW_MODES[color], pal.ctypes.data if pal.shape[0] else None, int(pal.shape[0])
-    st.untracked[:] = [int(v) for v in untracked]
+    st, _alive = _draw_style_struct(edges, joint_radius, limb_radius, alpha, alpha_filled, min_score, color, palette, untracked)
     ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
     _check(_lib.dc_draw_people(arr, nb, h, w, int(is_device), p, j, ptr(n), ptr(ppl), ptr(cnd), ptr(idv), C.byref(st), _stream_arg(stream)))
 
@@ -1203,6 +1215,27 @@ def redact_select(ids, only_ids=None, keep_ids=None, select=None):
     return sel.astype(np.uint8)
 
 
+def _redact_style_struct(region="head", head=None, edges=None, head_scale=REDACT_DEFAULTS["head_scale"], body_scale=REDACT_DEFAULTS["body_scale"],
+                         min_radius=REDACT_DEFAULTS["min_radius"], max_radius=REDACT_DEFAULTS["max_radius"], min_score=0.0, effect="mosaic",
+                         block=8, fill=(0, 0, 0)):
+    """The style arguments of `redact_people` -> (RedactStyle, the arrays it points into).  Names and shapes are checked here; the values
+    are the library's to refuse."""
+    if region not in _REDACT_REGIONS:
+        raise ValueError("region must be one of %s, got %r" % (sorted(_REDACT_REGIONS), region))
+    if effect not in _REDACT_EFFECTS:
+        raise ValueError("effect must be one of %s, got %r" % (sorted(_REDACT_EFFECTS), effect))
+    if head is None or len(head) != 2:
+        raise ValueError("head must name the joint pair (neck, head top), got %r (pose.redact_people has the MPII one)" % (head,))
+    e = _edges_array(edges)
+    st = RedactStyle()
+    st.region, st.head_a, st.head_b = _REDACT_REGIONS[region], int(head[0]), int(head[1])
+    st.head_scale, st.body_scale, st.min_radius, st.max_radius = float(head_scale), float(body_scale), float(min_radius), float(max_radius)
+    st.min_score, st.n_edges, st.edges = float(min_score), int(e.shape[0]), e.ctypes.data if e.shape[0] else None
+    st.effect, st.block = _REDACT_EFFECTS[effect], int(block)
+    st.fill[:] = [int(v) for v in fill]
+    return st, (e,)
+
+
 def redact_people(frames, people, n_people=None, select=None, ids=None, only_ids=None, keep_ids=None, region="head", head=None, edges=None,
                   head_scale=REDACT_DEFAULTS["head_scale"], body_scale=REDACT_DEFAULTS["body_scale"], min_radius=REDACT_DEFAULTS["min_radius"],
                   max_radius=REDACT_DEFAULTS["max_radius"], min_score=0.0, effect="mosaic", block=8, fill=(0, 0, 0), stream=None):
@@ -1230,23 +1263,74 @@ def redact_people(frames, people, n_people=None, select=None, ids=None, only_ids
     if sel is not None and sel.shape != ppl.shape[:2]:
         raise ValueError("select must be %s like people, got shape %s" % (ppl.shape[:2], sel.shape))
     sel = redact_select(idv, only_ids, keep_ids, sel)
-    if region not in _REDACT_REGIONS:
-        raise ValueError("region must be one of %s, got %r" % (sorted(_REDACT_REGIONS), region))
-    if effect not in _REDACT_EFFECTS:
-        raise ValueError("effect must be one of %s, got %r" % (sorted(_REDACT_EFFECTS), effect))
-    if head is None or len(head) != 2:
-        raise ValueError("head must name the joint pair (neck, head top), got %r (pose.redact_people has the MPII one)" % (head,))
-    e = _edges_array(edges)
-    st = RedactStyle()
-    st.region, st.head_a, st.head_b = _REDACT_REGIONS[region], int(head[0]), int(head[1])
-    st.head_scale, st.body_scale, st.min_radius, st.max_radius = float(head_scale), float(body_scale), float(min_radius), float(max_radius)
-    st.min_score, st.n_edges, st.edges = float(min_score), int(e.shape[0]), e.ctypes.data if e.shape[0] else None
-    st.effect, st.block = _REDACT_EFFECTS[effect], int(block)
-    st.fill[:] = [int(v) for v in fill]
+    st, _alive = _redact_style_struct(region, head, edges, head_scale, body_scale, min_radius, max_radius, min_score, effect, block, fill)
     out = np.zeros((nb, p), np.int32)
     ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
     _check(_lib.dc_redact_people(arr, nb, h, w, int(is_device), p, j, ptr(n), ptr(ppl), ptr(sel), C.byref(st), ptr(out), _stream_arg(stream)))
     return out[0, :people.shape[0]] if single else out
+
+
+# ---- overlays from people in device memory (dc_overlay_people_device, dc_net_track_frames_async_overlay) --------------------------------
+def _overlay_args(draw, redact, have_ids):
+    """draw / redact: None or dicts of the STYLE arguments of `draw_people` / `redact_people` (a redact dict may carry only_ids /
+    keep_ids) -> (DrawStyle or None, RedactStyle or None, only_ids int64 array or None, keep_ids likewise, what to keep alive)."""
+    if draw is None and redact is None:
+        raise ValueError("an overlay needs draw=, redact= or both")
+    dst = rst = only = keep = None
+    alive = []
+    if redact is not None:
+        r = dict(redact)
+        if r.pop("select", None) is not None:
+            raise ValueError("select is a mask over people, who do not exist before the call: choose them by only_ids / keep_ids")
+        only, keep = r.pop("only_ids", None), r.pop("keep_ids", None)
+        if (only is not None or keep is not None) and not have_ids:
+            raise ValueError("only_ids / keep_ids choose people by id: ids is needed")
+        only = None if only is None else np.ascontiguousarray(list(only), dtype=np.int64).reshape(-1)
+        keep = None if keep is None else np.ascontiguousarray(list(keep), dtype=np.int64).reshape(-1)
+        rst, a = _redact_style_struct(**r)
+        alive.append(a)
+    if draw is not None:
+        dst, a = _draw_style_struct(**dict(draw))
+        alive.append(a)
+    return dst, rst, only, keep, alive
+
+
+def _overlay_c_args(dst, rst, only, keep):
+    """... as the two entries take them: draw, redact, only_ids, n_only, keep_ids, n_keep."""
+    ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    return (None if dst is None else C.byref(dst), None if rst is None else C.byref(rst), ptr(only), -1 if only is None else int(only.size),
+            ptr(keep), -1 if keep is None else int(keep.size))
+
+
+def _device_pointer(a, name, dtype, shape):
+    """A device array of the caller's (anything with data_ptr(), dtype and shape, a torch tensor for one; or None) -> its address."""
+    if a is None:
+        return None
+    if not hasattr(a, "data_ptr"):
+        raise ValueError("%s must be a device tensor (data_ptr(), shape), got %r" % (name, type(a).__name__))
+    if tuple(a.shape) != tuple(shape) or dtype not in str(a.dtype) or (hasattr(a, "is_contiguous") and not a.is_contiguous()):
+        raise ValueError("%s must be a contiguous %s device tensor of shape %s, got %s %s" % (name, dtype, tuple(shape), a.dtype, tuple(a.shape)))
+    return C.c_void_p(int(a.data_ptr()))
+
+
+def overlay_people_device(frames, people, n_people, cand=None, ids=None, draw=None, redact=None, redacted=None, stream=None):
+    """The bytes of `redact_people` then `draw_people` from people that are in DEVICE memory (dc_overlay_people_device): the primitives
+    and the per-tile selection are made on the device, nothing of the poses travels.  frames: as `draw_people` takes them (host frames
+    travel up and ALL travel back).  people: a float64 device tensor [nb, P, J, 3] (a torch tensor: anything with data_ptr(), dtype and
+    shape); n_people: int32 [nb]; cand: int32 [nb, P, J] or None; ids: int64 [nb, P] or None; redacted: int32 [nb, P] or None, written by
+    the redaction.  draw / redact: dicts of the style arguments of `draw_people` / `redact_people` (either may be None); a redact dict
+    may carry only_ids / keep_ids (at most 256 each; they need ids) and no `select`.  stream: a HIP stream — with device frames the call
+    then returns once everything is enqueued on it, and the tensors must stay alive until that stream has run; otherwise it waits."""
+    arr, nb, h, w, is_device, _keep = _writable_frames(frames)
+    shape = tuple(getattr(people, "shape", ()))
+    if len(shape) != 4 or shape[0] != nb or shape[3] != 3:
+        raise ValueError("people must be a device tensor [nb = %d, P, J, 3], got shape %s" % (nb, shape))
+    p, j = int(shape[1]), int(shape[2])
+    dst, rst, only, keep, _alive = _overlay_args(draw, redact, ids is not None)
+    _check(_lib.dc_overlay_people_device(arr, nb, h, w, int(is_device), p, j, _device_pointer(n_people, "n_people", "int32", (nb,)),
+                                         _device_pointer(people, "people", "float64", shape), _device_pointer(cand, "cand", "int32", (nb, p, j)),
+                                         _device_pointer(ids, "ids", "int64", (nb, p)), *_overlay_c_args(dst, rst, only, keep),
+                                         _device_pointer(redacted, "redacted", "int32", (nb, p)), _stream_arg(stream)))
 
 
 # ---- blending score maps into frames (dc_draw_heatmap; the rule: include/deepcut_hip.h — this project's own, the reference has none) ----
@@ -1413,9 +1497,9 @@ class TrackedFrames(object):
     """What `Net.track_frames_async` returns: the request in flight.  It owns the pinned output arrays and keeps the frames alive;
     `result()` waits for the net and returns what `Net.track_people` returns."""
 
-    def __init__(self, net, tracked, count, people, cand, ids, place, keep, pool=None, completed=False, bridging=False):
+    def __init__(self, net, tracked, count, people, cand, ids, place, keep, pool=None, completed=False, bridging=False, redacted=None):
         self._net, self._tracked, self._keep, self._pool, self._completed = net, tracked, keep, pool, completed
-        self._bridging = bridging
+        self._bridging, self._redacted = bridging, redacted
         self._count, self._people, self._cand, self._ids, self._place = count, people, cand, ids, place
         self._out, self._ready = None, False
 
@@ -1427,7 +1511,8 @@ class TrackedFrames(object):
         return self._ready
 
     def result(self):
-        """-> one dict per image: "people", "cand" and, with a tracker, "ids" and "place" (`Net.track_people`).  Waits for the net."""
+        """-> one dict per image: "people", "cand" and, with a tracker, "ids" and "place" (`Net.track_people`); with redact= also
+        "redacted" (int32 [m], as `redact_people` returns it).  Waits for the net."""
         if self._out is None:
             if not self._ready:
                 self._net.synchronize()
@@ -1442,11 +1527,16 @@ class TrackedFrames(object):
                     d["bridged"] = d["cand"] == -3
                 if self._tracked:
                     d["ids"], d["place"] = self._ids[b, :m].copy(), self._place[b, :m].copy()
+                if self._redacted is not None:
+                    d["redacted"] = self._redacted[b, :m].copy()
                 out.append(d)
             self._out, self._keep = out, None
             if self._pool is not None:  # everything is copied out: the pinned arrays serve the net's next request of this shape
                 self._pool.append((self._count, self._people, self._cand, self._ids, self._place))
                 self._count = self._people = self._cand = self._ids = self._place = self._pool = None
+                if self._redacted is not None:
+                    self._net.__dict__.setdefault("_async_redacted", {}).setdefault(self._redacted.shape, []).append(self._redacted)
+            self._redacted = None
         return self._out
 
 
@@ -2049,7 +2139,7 @@ class Net(_Completing):
 
     def track_frames_async(self, frames_or_images, tracker=None, scale=1.0, slot_of=None, assemble_scale=None, threshold=0.1, radius=1,
                            max_det=16, edges=None, mean=None, std=None, max_cost=32.0, seed_threshold=0.5, max_people=32, min_joints=1,
-                           joint_order=None, complete=None, dedupe=None):
+                           joint_order=None, complete=None, dedupe=None, draw=None, redact=None):
         """The whole video chain without a host wait (dc_net_track_frames_async): upload, pre-processing, forward, assembly, the
         tracker's update and the downloads are enqueued on the net's own stream and the call returns.  frames_or_images: a `Frame`, a
         list of `Frame`s of one size, or uint8 [n,H,W,3] / [H,W,3] BGR; they must stay untouched until the result is collected.
@@ -2058,15 +2148,28 @@ class Net(_Completing):
         (what holds when the call is made is what the request runs with).
         -> a `TrackedFrames`: `result()` synchronises the net and returns what `forward_images` + `track_people` return, bit for bit.
         A second call on a busy net queues behind the first; to overlap calls use clones (`deepcut_tools.VideoPipeline`): the tracker
-        keeps the updates in call order."""
+        keeps the updates in call order.
+        draw / redact (dc_net_track_frames_async_overlay): None, or dicts of the style arguments of `draw_people` / `redact_people` — the
+        frames are then redacted and drawn into IN PLACE inside the chain, behind the tracker, from the people, cand and ids being handed
+        back (the bytes of `redact_people` then `draw_people` on them), with no host wait: they must be writable, host frames ALL travel
+        back, and they are the caller's again after `result()`.  A redact dict may carry only_ids / keep_ids (they need a tracker) and
+        no `select`; `result()` then adds "redacted"."""
         if edges is None:
             raise ValueError("track_frames_async needs the regression edges (deepcut_tools.read_pair_stats)")
         if tracker is not None:
             _tracker_handle(tracker)
+        overlay = None
+        if draw is not None or redact is not None:
+            overlay = _overlay_args(draw, redact, tracker is not None)
+            if isinstance(frames_or_images, np.ndarray) and not (frames_or_images.dtype == np.uint8 and frames_or_images.flags.c_contiguous and
+                                                                 frames_or_images.flags.writeable):
+                raise ValueError("images that are drawn into must be a writable contiguous uint8 array")
         frames = _frame_list(frames_or_images)
         if frames is not None:
             arr, h, w, dev = _frame_array(frames)
             n, x, keep = len(frames), None, (arr, frames)
+            if overlay is not None:
+                _writable_frames(frames)  # ValueError for a host array that cannot be written
         else:
             x = np.ascontiguousarray(frames_or_images, dtype=np.uint8)
             if x.ndim == 3:
@@ -2100,12 +2203,20 @@ class Net(_Completing):
                 ids, place = out((n, p), np.int64), out((n, p), np.int32)
         ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
         bridging = tracker is not None and _tracker_smoothing(tracker)
+        args = (self._h, None if tracker is None else tracker._h, arr, ptr(x), n, h, w, float(scale), 1 if dev else 0,
+                None if slot_of is None else ptr(_slot_map(slot_of, n)), C.byref(q), e.shape[0], ptr(e), ptr(m), ptr(s), ptr(order), ptr(count),
+                ptr(people), ptr(cand), ptr(ids), ptr(place))
+        redacted = None
         with self._completing(complete, dedupe) as completed:
-            _check(_lib.dc_net_track_frames_async(self._h, None if tracker is None else tracker._h, arr, ptr(x), n, h, w, float(scale),
-                                                  1 if dev else 0, None if slot_of is None else ptr(_slot_map(slot_of, n)), C.byref(q),
-                                                  e.shape[0], ptr(e), ptr(m), ptr(s), ptr(order), ptr(count), ptr(people), ptr(cand),
-                                                  ptr(ids), ptr(place)))
-        return TrackedFrames(self, tracker is not None, count, people, cand, ids, place, keep + (tracker,), pool, completed, bridging)
+            if overlay is None:
+                _check(_lib.dc_net_track_frames_async(*args))
+            else:
+                dst, rst, only, keep_ids, alive = overlay
+                spare = self.__dict__.setdefault("_async_redacted", {}).setdefault((n, p), [])  # pinned once, like the other outputs
+                redacted = None if rst is None else (spare.pop() if spare else out((n, p), np.int32))
+                keep = keep + (alive, redacted)
+                _check(_lib.dc_net_track_frames_async_overlay(*(args + _overlay_c_args(dst, rst, only, keep_ids) + (ptr(redacted),))))
+        return TrackedFrames(self, tracker is not None, count, people, cand, ids, place, keep + (tracker,), pool, completed, bridging, redacted)
 
     def _assemble_people(self, tracker, scale, threshold, radius, max_det, edges, mean, std, max_cost, seed_threshold, max_people, min_joints,
                          joint_order, return_cost, slot_of=None, complete=None, dedupe=None):

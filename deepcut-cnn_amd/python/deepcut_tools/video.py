@@ -14,7 +14,7 @@ class VideoPipeline(object):
     MAX_DEPTH = 4  # a HIP process has four hardware queues: a fifth executor only shares one
 
     def __init__(self, net, tracker=None, depth=3, batch=1, stats=None, scale=1.0, choose_streams=True, complete=None, dedupe=None, draw=None,
-                 redact=None, **assembly):
+                 redact=None, in_chain=False, **assembly):
         """net: a `caffe.Net` with all three maps (or a sparse-pairwise net); tracker: a `caffe.Tracker` or None (people without ids,
         ids come back as None); depth: executors, 1..4; batch: frames per call, 1..64; stats: (edges, mean, std) as
         `deepcut_tools.read_pair_stats` returns them, or a path; scale: the pre-processing's and the assembly's; assembly: what
@@ -25,7 +25,12 @@ class VideoPipeline(object):
         and ids being handed back (filled and bridged joints at alpha_filled), before they are handed back; the frames must then be
         writable arrays or `caffe.Frame`s.  redact: None (off: nothing is added), True or a dict of what `pose.redact_people` takes —
         every frame is kept likewise and redacted IN PLACE on the device with the people and ids being handed back, before the drawing
-        (the skeletons go over the mosaic); (people, ids) are what they are without it."""
+        (the skeletons go over the mosaic); (people, ids) are what they are without it.  in_chain: False (the default) applies draw /
+        redact when a request is collected, with the synchronous `pose.redact_people` / `pose.draw_people` on the people copied to the
+        host; True sends the styles WITH the request (`Net.track_frames_async(draw=, redact=)`): the frames are written inside the chain
+        on the device, from the people where the tracker left them, and collecting a request calls nothing — the same bytes, the same
+        (people, ids).  A redact dict with `select` is refused then (ValueError: a mask cannot exist before the people do; use
+        only_ids / keep_ids, which need a tracker), as is `stream` in either dict."""
         depth, batch = int(depth), int(batch)
         if not 1 <= depth <= self.MAX_DEPTH:
             raise ValueError("depth must be in [1, %d], got %d" % (self.MAX_DEPTH, depth))
@@ -54,6 +59,23 @@ class VideoPipeline(object):
             from pose.people import _redact_style
 
             self._redact = _redact_style(redact)
+        self._in_chain = bool(in_chain) and (self._draw is not None or self._redact is not None)
+        if self._in_chain:
+            from pose.people import HEAD_MPII14, SKELETON_MPII14
+
+            for style in (self._draw, self._redact):
+                if style is not None and "stream" in style:
+                    raise ValueError("in_chain=True runs on the executor's own stream: the style must not name one")
+            if self._draw is not None:
+                self._draw.setdefault("edges", SKELETON_MPII14)  # what pose.draw_people / pose.redact_people fill in on the host route
+            if self._redact is not None:
+                if self._redact.get("select") is not None:
+                    raise ValueError("in_chain=True: select is a mask over people, who do not exist before the request: choose them by "
+                                     "only_ids / keep_ids")
+                if (self._redact.get("only_ids") is not None or self._redact.get("keep_ids") is not None) and tracker is None:
+                    raise ValueError("only_ids / keep_ids choose people by id: ids is needed")
+                self._redact.setdefault("head", HEAD_MPII14)
+                self._redact.setdefault("edges", SKELETON_MPII14)
         self._choose_streams = bool(choose_streams)
         self.stream_choice = None            # what caffe.choose_streams measured, once it ran
         self._held = []                      # frames of the batch being gathered: (frame, tag, slot, shape key)
@@ -88,12 +110,17 @@ class VideoPipeline(object):
     def _collect_oldest(self):
         """Wait for the oldest request (the tracker ran them in submission order, so it finishes first or nearly) and queue its results."""
         k, handle, tags, frames = self._pending.popleft()
-        for i, (tag, d) in enumerate(zip(tags, handle.result())):
-            if frames is not None and self._redact is not None:
+        results = handle.result()
+        if self._in_chain and frames is not None and isinstance(frames, tuple):  # images sent as one stacked batch: back into the caller's
+            for image, written in zip(*frames):
+                image[...] = written
+        host_route = frames is not None and not self._in_chain  # in_chain: the chain has written the frames
+        for i, (tag, d) in enumerate(zip(tags, results)):
+            if host_route and self._redact is not None:
                 from pose.people import redact_people
 
                 redact_people(frames[i], d["people"], d.get("ids"), **self._redact)
-            if frames is not None and self._draw is not None:
+            if host_route and self._draw is not None:
                 from pose.people import draw_people
 
                 draw_people(frames[i], d["people"], d.get("ids"), **dict(self._draw, cand=d.get("cand")))
@@ -113,7 +140,11 @@ class VideoPipeline(object):
         if held[0][3][0] == "bgr":
             import numpy as np
 
-            frames = np.stack(frames) if len(frames) > 1 else frames[0]
+            if self._in_chain and len(frames) > 1:  # the chain writes into the stacked copy
+                stacked = np.stack(frames)
+                kept, frames = (frames, stacked), stacked
+            else:
+                frames = np.stack(frames) if len(frames) > 1 else frames[0]
         if self._choose_streams and len(self.nets) > 1 and not self._pending and self.calls == 0:
             # first call: every executor lowers / allocates / tunes the shape, then the library picks their streams by timing them
             # together — untimed set-up, as in Pipeline
@@ -126,8 +157,9 @@ class VideoPipeline(object):
                 e.reserve(len(held), ch, cw)
             self.stream_choice = caffe.choose_streams(self.nets)
         slot_of = None if self.tracker is None else [h[2] for h in held]
+        styles = dict(draw=self._draw, redact=self._redact) if self._in_chain else {}
         handle = self.nets[k].track_frames_async(frames, self.tracker, self.scale, slot_of=slot_of, edges=self.edges, mean=self.mean,
-                                                 std=self.std, **self.assembly)
+                                                 std=self.std, **dict(self.assembly, **styles))
         self.calls += 1
         self._pending.append((k, handle, [h[1] for h in held], kept))
 

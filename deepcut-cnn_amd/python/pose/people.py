@@ -153,7 +153,8 @@ def _draw_style(draw):
     return dict(draw)
 
 
-def track_people(frames, model_def, model_bin, stats, tracker=None, depth=1, batch=1, assign="greedy", smooth=None, draw=None, redact=None, **kw):
+def track_people(frames, model_def, model_bin, stats, tracker=None, depth=1, batch=1, assign="greedy", smooth=None, draw=None, redact=None,
+                 in_chain=False, **kw):
     """`estimate_people` over the frames of a video, with identities: a generator over an iterable of images (HxWx3 BGR uint8) or
     `caffe.Frame`s that yields, per frame, (people float64 [m, J, 3], ids int64 [m]) — the same person keeps their id from frame to
     frame, -1 marks a person no track place was free for.  kw: what `estimate_people` takes (scale / scales / base / flip / joint_mirror /
@@ -175,17 +176,23 @@ def track_people(frames, model_def, model_bin, stats, tracker=None, depth=1, bat
     redact: None (off: nothing is added to the run), True or a dict of what `redact_people` takes — every frame is redacted IN PLACE on the
     device with the people and ids being yielded, BEFORE the drawing (the skeletons go over the mosaic) and before they are yielded;
     (people, ids) are what they are without `redact`.  Who was not redacted (region "head": no neck or head top) is not reported here:
-    call `redact_people` on the yielded people where that matters."""
+    call `redact_people` on the yielded people where that matters.
+    in_chain: False (the default) redacts and draws with the synchronous entries on the people that came back; True sends the styles with
+    the request (`deepcut_tools.VideoPipeline(in_chain=True)`, whatever depth and batch are): the frames are written inside the
+    asynchronous chain on the device — the same bytes, the same (people, ids).  A redact dict with `select` raises ValueError then."""
     style = _draw_style(draw)
     rstyle = None if redact is None or redact is False else _redact_style(redact)
     args = dict(scale=1.0, net=None, scales=None, base=None, flip=False, joint_mirror=MIRROR_MPII14, sparse=False)
     for k in list(kw):
         if k in args:
             args[k] = kw.pop(k)
-    if int(depth) != 1 or int(batch) != 1:
+    in_chain = bool(in_chain) and (style is not None or rstyle is not None)
+    if int(depth) != 1 or int(batch) != 1 or in_chain:
         if args["scales"] is not None or args["flip"]:
-            raise ValueError("track_people: depth > 1 / batch > 1 run one forward per frame; a pyramid (scales= / flip=True) has no "
+            raise ValueError("track_people: depth > 1 / batch > 1 / in_chain run one forward per frame; a pyramid (scales= / flip=True) has no "
                              "asynchronous entry: use depth=1, batch=1")
+        if in_chain:
+            kw = dict(kw, in_chain=True)
         for item in _track_in_flight(frames, model_def, model_bin, stats, tracker, int(depth), int(batch), args, kw, assign, smooth, style, rstyle):
             yield item
         return

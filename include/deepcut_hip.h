@@ -1281,7 +1281,7 @@ int dc_group_draw_heatmap_mirrored(dc_group* group, const dc_frame* frames, int 
  *   n_people and edges; a NULL style; an unknown region or effect; block not in the list; head_a or head_b outside [0, J), or equal;
  *   head_scale or body_scale not finite or < 0; min_radius or max_radius not finite, min_radius < 0, max_radius > 1024 or
  *   min_radius > max_radius; min_score not finite or < 0.  Then DC_ENOCPU in CPU mode (there is no CPU path).
- * Not built, on purpose: blur; an asynchronous entry; redaction inside dc_net_track_frames_async; per-box geometry.  A mosaic with
+ * Not built, on purpose: blur; per-box geometry (the asynchronous entry is dc_net_track_frames_async_overlay, below).  A mosaic with
  *   small blocks is NOT a privacy guarantee (the means still carry the face), and DC_REDACT_HEAD does not redact a person without a
  *   held head pair: that is what `redacted` is for.                                                                              */
 #define DC_REDACT_HEAD         0
@@ -1299,6 +1299,54 @@ typedef struct dc_redact_style {
 int dc_redact_people(const dc_frame* frames, int nb, int height, int width, int is_device, int P, int J, const int* n_people,
                      const double* people, const unsigned char* select /* [nb][P], may be NULL: everyone */,
                      const dc_redact_style* style, int* redacted /* [nb][P], may be NULL */, void* stream);
+
+/* ---- overlays from people in device memory: redaction and skeletons without a round trip through the host ------------------
+ * PARITY UNPINNED BY THE REFERENCE.  There is NO rule of its own here.  THE RULE'S PLACE: both entries below write the bytes of
+ * dc_redact_people then dc_draw_people on the people this call returns (dc_net_track_frames_async_overlay) or is given
+ * (dc_overlay_people_device) — redaction first, the skeletons over the mosaic —, byte for byte, with `redacted` as dc_redact_people
+ * reports it.  What differs is where the work is done: the primitives (snapping, order, radii, colour keys) and the per-tile selection
+ * are made on the device from n_people, people, cand and ids in device memory, so the host reads no pose, takes no second upload of the
+ * pixels and waits for nothing.  Every tile of every frame is a workgroup; one that no primitive reaches loads and stores no pixel.
+ *
+ * Styles: `draw` and `redact` may each be NULL (not both).  The redaction chooses people by id instead of by mask — a mask cannot exist
+ *   before the people do —: only_ids[n_only] (n_only < 0: no list; 0: nobody) keeps only the people with one of these ids, keep_ids
+ *   [n_keep] (n_keep < 0: no list) leaves the people with one of these ids visible; both are combined by AND, as the Python binding's
+ *   redact_select combines them; at most 256 ids each; they need ids (and a redact style).  The drawing takes cand and ids as
+ *   dc_draw_people does.
+ *
+ * dc_overlay_people_device: the device half alone.  frames as dc_draw_people takes them (device frames are written in place; host frames
+ *   are staged up without their padding, written, and ALL copied back with 2-D copies, padding never written: which frames are touched
+ *   is known on the device only).  n_people [nb], people [nb][P][J][3], cand [nb][P][J] (may be NULL), ids [nb][P] (may be NULL) and
+ *   redacted [nb][P] (may be NULL; written by the redaction only) are DEVICE pointers; an n_people[b] outside [0, P] is read as clamped.
+ *   With device frames and a `stream` the call is asynchronous on that stream: it returns once everything is enqueued, and the next call
+ *   on the same stream may follow at once.  Otherwise (host frames, or stream NULL: the library's utility stream) it waits.
+ * dc_net_track_frames_async_overlay: dc_net_track_frames_async with the overlays enqueued on the net's stream behind the tracker's
+ *   launch, from the people it hands back — the kept people after completion and dedupe, or with smoothing on the tracker's smoothed
+ *   poses and their cand (bridged joints at alpha_filled; cand NULL: alpha everywhere) — and the tracker's ids (no tracker: the person's
+ *   index chooses the colour, and id lists are refused).  Device frames and device `images` are written in place.  Host frames and host
+ *   `images` are written in the device copy the pre-processing staged — no second upload — and then EVERY one of them is copied back
+ *   into the caller's planes (2-D copies into the caller's pitch, padding never written): nobody knows at enqueue time which frames are
+ *   touched.  They must be writable, and stay the caller's only after the net was synchronised; pinned host planes keep the call free
+ *   of host waits.  redacted [n][max_people] (host, may be NULL) comes back with the other results.  With both styles NULL the call
+ *   enqueues exactly what dc_net_track_frames_async enqueues.
+ * Errors, before any device work and worded like the synchronous entries': everything dc_draw_people / dc_redact_people refuse of nb,
+ *   height, width, the frames, P, J and the styles; both styles NULL; an id list of more than 256 ids, one without ids or without a
+ *   redact style; for the chain what dc_net_track_frames_async refuses.  Then DC_ENOCPU in CPU mode.
+ * Not built, on purpose: heat-map overlays in the chain (the net's maps belong to a later frame by the time a result is handed back);
+ *   a `select` mask.                                                                                                              */
+int dc_overlay_people_device(const dc_frame* frames, int nb, int height, int width, int is_device, int P, int J,
+                             const int* n_people /* device */, const double* people /* device */, const int* cand /* device, may be NULL */,
+                             const long long* ids /* device, may be NULL */, const dc_draw_style* draw /* may be NULL */,
+                             const dc_redact_style* redact /* may be NULL */, const long long* only_ids, int n_only /* < 0: no list */,
+                             const long long* keep_ids, int n_keep /* < 0: no list */, int* redacted /* device [nb][P], may be NULL */,
+                             void* stream);
+int dc_net_track_frames_async_overlay(dc_net* net, dc_tracker* tracker /* NULL: people without ids */, const dc_frame* frames /* or NULL */,
+                                      const unsigned char* images /* or NULL */, int n, int height, int width, double scale, int is_device,
+                                      const int* slot_of, const dc_assemble_params* p, int n_edges, const int* edges, const double* mean,
+                                      const double* stdev, const int* joint_order, int* n_people, double* people, int* cand, long long* ids,
+                                      int* place, const dc_draw_style* draw /* may be NULL */, const dc_redact_style* redact /* may be NULL */,
+                                      const long long* only_ids, int n_only /* < 0: no list */, const long long* keep_ids,
+                                      int n_keep /* < 0: no list */, int* redacted /* host [n][max_people], may be NULL */);
 
 /* ---- in-process multi-GPU forward (SURVEY 8(b)'s dc_forward_batch) -------------------------------------------------------
  * A communicator over `nexec` executors: executor k runs on devices[k] (NULL: k modulo the visible devices) on a host thread of its

@@ -7,7 +7,11 @@ on synthetic ResNet-152 weights at 544x736, host NV12 frames in pinned memory, m
  (d) `Tracker.update` of 8 frames of P = n = 32 into ONE slot as one call (slot map) against 8 calls.
 Every figure of (a)-(c) is frames per second by the host clock over a window in which frames are submitted without pause and then
 drained; (d) is ms per 8 frames.  The variants are alternated; the median of five windows of at least 0.5 s, with the windows listed.
-    python tools/video_ab.py [--out profiles/video_ab.txt]"""
+    python tools/video_ab.py [--out profiles/video_ab.txt]
+With --overlay: `VideoPipeline` with draw + redact at depth 1, 2, 3, float32 and float16, on host NV12 frames in pinned
+memory and on device NV12 frames — the host route (in_chain=False: the synchronous redact_people / draw_people when a request is
+collected), in_chain=True (the overlays enqueued with the request) and no overlay at all (the ceiling) alternated in the same windows.
+    python tools/video_ab.py --overlay [--out profiles/video_overlay_ab.txt]"""
 import argparse
 import os
 import statistics
@@ -33,9 +37,58 @@ def windows(runs, n_windows=5, seconds=0.5):
     return per
 
 
+def overlay(caffe, VideoPipeline, nets, host_frames, stats, akw, say, fmt):
+    """The overlay routes of VideoPipeline: frames/s with no overlay, with draw + redact on the host route, and with them in the chain."""
+    import torch
+
+    tensors = [(torch.from_numpy(np.array(f._keep[0])).cuda(), torch.from_numpy(np.array(f._keep[1])).cuda()) for f in host_frames]
+    torch.cuda.synchronize()
+    device_frames = [caffe.Frame.nv12_device(y.data_ptr(), uv.data_ptr(), H, W, W, W) for y, uv in tensors]
+    sources = {"host NV12 (pinned)": host_frames, "device NV12": device_frames}
+    styles = dict(draw=dict(alpha=160), redact=dict(region="head_or_body", block=8))
+    routes = {"no overlay": dict(), "host route": dict(styles), "in_chain": dict(styles, in_chain=True)}
+    people = {}
+
+    def pipeline(dtype, depth, frames, route):
+        pipe = VideoPipeline(nets[dtype], caffe.Tracker(n_joints=14, slots=1, max_tracks=64), depth=depth, batch=1, stats=stats, scale=1.0,
+                             **dict(akw, **routes[route]))
+
+        def run(seconds):
+            n, got, t0 = 0, 0, time.perf_counter()
+            while time.perf_counter() - t0 < seconds:
+                pipe.submit(frames[n % len(frames)])
+                n += 1
+                while pipe._done:
+                    people[route] = len(pipe.wait_one()[1])
+                    got += 1
+            got += len(pipe.drain())
+            assert got == n
+            return n, time.perf_counter() - t0
+
+        return run
+
+    say("# overlays in the video path: draw (MPII skeleton, alpha 160) + redact (head_or_body, mosaic, block 8) on every frame; frames are "
+        "overwritten again and again (a mosaic of a mosaic costs what a mosaic costs)")
+    for dtype in ("f32", "f16"):
+        for where, frames in sources.items():
+            for depth in (1, 2, 3):
+                runs = {route: pipeline(dtype, depth, frames, route) for route in routes}
+                for run in runs.values():
+                    run(0.2)
+                per = windows(runs)
+                med = {k: statistics.median(v) for k, v in per.items()}
+                say("%s, %s, depth %d: " % (dtype, where, depth) + "; ".join(
+                    "%s %.1f frames/s [%.1f - %.1f]" % (k, med[k], min(per[k]), max(per[k])) for k in routes) +
+                    "; in_chain / host route %.3f, in_chain / no overlay %.3f" % (med["in_chain"] / med["host route"], med["in_chain"] / med["no overlay"]))
+                for k in routes:
+                    say("    windows %s: %s" % (k, fmt(per[k])))
+    say("# people in the last frame collected: %r" % (people,))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
+    ap.add_argument("--overlay", action="store_true", help="the overlay routes of VideoPipeline instead of (a)-(d)")
     a = ap.parse_args()
     import caffe
     from deepcut_tools import VideoPipeline, deepercut_prototxt, synth_weights, write_caffemodel
@@ -65,6 +118,13 @@ def main():
     fmt = lambda v: " ".join("%.1f" % x for x in v)  # noqa: E731
     say("# video path, synthetic ResNet-152 %dx%d, host NV12 frames in pinned memory, max_det 16 max_people 32, tracker T 64; tracked "
         "people per frame, frames/s by the host clock, median of 5 windows >= 0.5 s, variants alternated" % (H, W))
+
+    if a.overlay:
+        overlay(caffe, VideoPipeline, nets, frames, (edges, mean, std), akw, say, fmt)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
 
     base_tracker = caffe.Tracker(n_joints=14, slots=1, max_tracks=64)
     found = {}
