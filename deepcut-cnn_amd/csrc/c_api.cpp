@@ -3,6 +3,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -1145,23 +1146,64 @@ int dc_redact_people(const dc_frame* frames, int nb, int height, int width, int 
   return guard([&] { redact_people(frames, nb, height, width, is_device != 0, P, J, n_people, people, select, style, redacted, stream); });
 }
 // the overlays from people in device memory (overlay.cpp, people.cpp); a call without a style is refused there, naming the field
-static OverlayArgs overlay_args(const dc_draw_style* draw, const dc_redact_style* redact, const long long* only_ids, int n_only,
-                                const long long* keep_ids, int n_keep, int* redacted) {
+// dc_overlay_styles as the caller compiled it -> OverlayArgs: fields beyond the caller's `size` read as NULL / no list
+static OverlayArgs overlay_args(const char* who, const dc_overlay_styles* st, int* redacted, bool styles_entry = true) {
   OverlayArgs a;
-  a.draw = draw, a.redact = redact, a.only_ids = only_ids, a.n_only = n_only, a.keep_ids = keep_ids, a.n_keep = n_keep, a.redacted = redacted;
+  a.redacted = redacted, a.styles_entry = styles_entry;
+  if (!st) return a;  // no style at all: refused, or the plain chain, where the entry decides
+  if (st->size < offsetof(dc_overlay_styles, redact) + sizeof(st->redact) || st->size > sizeof(dc_overlay_styles))
+    throw DcError(DC_EINVAL, std::string(who) + ": styles.size = " + std::to_string(st->size) + " must be sizeof(dc_overlay_styles) of the caller, in [" +
+                                 std::to_string(offsetof(dc_overlay_styles, redact) + sizeof(st->redact)) + ", " +
+                                 std::to_string(sizeof(dc_overlay_styles)) + "]");
+  auto has = [&](size_t end) { return st->size >= end; };
+  a.draw = st->draw, a.redact = st->redact;
+  if (has(offsetof(dc_overlay_styles, labels) + sizeof(st->labels))) a.labels = st->labels;
+  if (has(offsetof(dc_overlay_styles, n_only) + sizeof(st->n_only))) a.only_ids = st->only_ids, a.n_only = st->n_only;
+  if (has(offsetof(dc_overlay_styles, n_keep) + sizeof(st->n_keep))) a.keep_ids = st->keep_ids, a.n_keep = st->n_keep;
   return a;
 }
-int dc_overlay_people_device(const dc_frame* frames, int nb, int height, int width, int is_device, int P, int J, const int* n_people,
-                             const double* people, const int* cand, const long long* ids, const dc_draw_style* draw,
-                             const dc_redact_style* redact, const long long* only_ids, int n_only, const long long* keep_ids, int n_keep,
-                             int* redacted, void* stream) {
+// the older entries' arguments as a styles block, and their refusals' words
+static dc_overlay_styles overlay_styles(const dc_draw_style* draw, const dc_redact_style* redact, const long long* only_ids, int n_only,
+                                        const long long* keep_ids, int n_keep) {
+  dc_overlay_styles st{};
+  st.size = sizeof st, st.draw = draw, st.redact = redact, st.labels = nullptr;
+  st.only_ids = only_ids, st.n_only = n_only, st.keep_ids = keep_ids, st.n_keep = n_keep;
+  return st;
+}
+// both device entries; styles_entry: the refusal of a call without any style names the label style too
+static int overlay_device_entry(const dc_frame* frames, int nb, int height, int width, int is_device, int P, int J, const int* n_people,
+                                const double* people, const int* cand, const long long* ids, const dc_overlay_styles* styles, int* redacted,
+                                void* stream, bool styles_entry) {
   REQUIRE(frames);
   REQUIRE(n_people);
   REQUIRE(people);
   return guard([&] {
     overlay_people_device(frames, nb, height, width, is_device != 0, P, J, n_people, people, cand, ids,
-                          overlay_args(draw, redact, only_ids, n_only, keep_ids, n_keep, redacted), stream);
+                          overlay_args("overlay_people_device", styles, redacted, styles_entry), stream);
   });
+}
+int dc_overlay_people_device_styles(const dc_frame* frames, int nb, int height, int width, int is_device, int P, int J, const int* n_people,
+                                    const double* people, const int* cand, const long long* ids, const dc_overlay_styles* styles,
+                                    int* redacted, void* stream) {
+  return overlay_device_entry(frames, nb, height, width, is_device, P, J, n_people, people, cand, ids, styles, redacted, stream, true);
+}
+int dc_overlay_people_device(const dc_frame* frames, int nb, int height, int width, int is_device, int P, int J, const int* n_people,
+                             const double* people, const int* cand, const long long* ids, const dc_draw_style* draw,
+                             const dc_redact_style* redact, const long long* only_ids, int n_only, const long long* keep_ids, int n_keep,
+                             int* redacted, void* stream) {
+  const dc_overlay_styles st = overlay_styles(draw, redact, only_ids, n_only, keep_ids, n_keep);
+  return overlay_device_entry(frames, nb, height, width, is_device, P, J, n_people, people, cand, ids, &st, redacted, stream, false);
+}
+// the label overlay (label.cpp); a null style is refused there, after the frames' own checks, naming the field
+int dc_label_people(const dc_frame* frames, int nb, int height, int width, int is_device, int P, int J, const int* n_people,
+                    const double* people, const long long* ids, const char* texts, const dc_label_style* style, void* stream) {
+  REQUIRE(frames);
+  REQUIRE(n_people);
+  REQUIRE(people);
+  return guard([&] { label_people(frames, nb, height, width, is_device != 0, P, J, n_people, people, ids, texts, style, stream); });
+}
+int dc_label_font(int ch, unsigned char rows[7]) {
+  return guard([&] { label_font(ch, rows); });
 }
 int dc_net_track_frames_async_overlay(dc_net* net, dc_tracker* tracker, const dc_frame* frames, const unsigned char* images, int n, int height,
                                       int width, double scale, int is_device, const int* slot_of, const dc_assemble_params* p, int n_edges,
@@ -1169,6 +1211,14 @@ int dc_net_track_frames_async_overlay(dc_net* net, dc_tracker* tracker, const dc
                                       double* people, int* cand, long long* ids, int* place, const dc_draw_style* draw,
                                       const dc_redact_style* redact, const long long* only_ids, int n_only, const long long* keep_ids,
                                       int n_keep, int* redacted) {
+  const dc_overlay_styles st = overlay_styles(draw, redact, only_ids, n_only, keep_ids, n_keep);
+  return dc_net_track_frames_async_styles(net, tracker, frames, images, n, height, width, scale, is_device, slot_of, p, n_edges, edges, mean, stdev,
+                                          joint_order, n_people, people, cand, ids, place, &st, redacted);
+}
+int dc_net_track_frames_async_styles(dc_net* net, dc_tracker* tracker, const dc_frame* frames, const unsigned char* images, int n, int height,
+                                     int width, double scale, int is_device, const int* slot_of, const dc_assemble_params* p, int n_edges,
+                                     const int* edges, const double* mean, const double* stdev, const int* joint_order, int* n_people,
+                                     double* people, int* cand, long long* ids, int* place, const dc_overlay_styles* styles, int* redacted) {
   REQUIRE(net);
   if (!frames) REQUIRE(images);
   if (n <= 0 || height <= 0 || width <= 0) return fail(DC_EINVAL, "n, height and width must be positive");
@@ -1179,7 +1229,7 @@ int dc_net_track_frames_async_overlay(dc_net* net, dc_tracker* tracker, const dc
   if (n_edges > 0) REQUIRE(edges);
   return guard([&] {
     Net::AssembleParams q{p->scale, p->threshold, p->radius, p->max_det, p->max_cost, p->seed_threshold, p->max_people, p->min_joints};
-    const OverlayArgs a = overlay_args(draw, redact, only_ids, n_only, keep_ids, n_keep, redacted);
+    const OverlayArgs a = overlay_args("track_frames_async", styles, redacted);
     N(net)->track_frames_async(tracker ? TR(tracker) : nullptr, frames, images, n, height, width, scale, is_device != 0, slot_of, q, n_edges,
                                edges, mean, stdev, joint_order, n_people, people, cand, ids, place, &a);
   });

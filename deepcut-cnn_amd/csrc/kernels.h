@@ -503,6 +503,40 @@ int launch_draw_all(int format, const DrawPlanes* frames, int nb, int height, in
 int launch_redact_all(int format, int effect, int block, unsigned fill, const DrawPlanes* frames, int nb, int height, int width,
                       const DrawPrim* prims, const int* n_prims, int stride, void* stream);
 
+// Label overlay (label.hip; the rule: include/deepcut_hip.h, dc_label_people — this project's own).  A primitive is one label with both
+// its layers; its pixel box is the plate rectangle [x, x + s (6 n + 1)) x [y, y + 9 s), also when the plate is not made.  The host
+// (label.cpp) makes the texts, places and clamps the labels, converts the colours and bins the boxes into the tiles (tile_bins.h); one
+// workgroup writes one non-empty tile, every thread walking the tile's labels in order, kLabelChunk at a time through LDS.  The device
+// form (overlay.hip): a builder launch of the overlay_build_kernel pattern, then label_all_kernel over every tile, kLabelPass labels
+// tested at a time.  A frame holds at most 256 labels (one per person), so 256 labels stacked on one tile take four trips through the
+// binned walk and two through the self-binning one.
+constexpr int kLabelMaxChars = 24;  // DC_LABEL_MAX_CHARS: a text holds at most 23 characters
+constexpr int kLabelChunk = 64, kLabelPass = 128;
+struct LabelPrim {                       // 56 bytes
+  int x, y;                              // the plate's upper left pixel, clamped into the frame
+  int n, s;                              // characters (1..23) and scale (1..8)
+  unsigned text_colour, plate_colour;    // bytes as DrawPrim::colour
+  int alpha_text, alpha_plate;           // 0..256; 0: that layer is not made
+  unsigned char text[kLabelMaxChars];    // text[0 .. n): places in the font table (label_font.h)
+};
+// format: DC_PIX_BGR24 or DC_PIX_NV12.  Grid = n_tiles (> 0); index names places in `prims`.  Every pointer is device memory.
+int launch_label(int format, const DrawPlanes* frames, int height, int width, const DrawTile* tiles, int n_tiles, const int* index,
+                 const LabelPrim* prims, void* stream);
+struct LabelBuild {  // the label builder's arguments, by value
+  int P, J, H, W;
+  int scale, gap, anchor, alpha_text, alpha_plate, plate_by_person, n_palette, n_prefix;
+  double min_score;
+  unsigned text_colour, plate_colour, palette[256];  // converted on the host
+  unsigned char prefix[4];                           // places in the font table
+};
+// n_people [nb], people [nb][P][J][3], ids [nb][P] or null -> prims [nb][P] (frame b's first n_labels[b] entries, in person order),
+// n_labels [nb].  Every pointer is device memory.  Grid = nb.
+int launch_label_build(const LabelBuild& q, int nb, const int* n_people, const double* people, const long long* ids, LabelPrim* prims,
+                       int* n_labels, void* stream);
+// label_all_kernel over all tiles of nb frames: prims / n_labels as the builder left them, stride = P
+int launch_label_all(int format, const DrawPlanes* frames, int nb, int height, int width, const LabelPrim* prims, const int* n_labels,
+                     int stride, void* stream);
+
 // Score-map overlay (heat.hip; the rule: include/deepcut_hip.h, dc_draw_heatmap — this project's own).  The host (heat.cpp) computes
 // the per-axis sample tables t = rint(256 u), clamped, and converts the colours; one workgroup blends one kDrawTileW x kDrawTileH pixel
 // tile of one frame, one thread one 2 x 2 pixel block (the ownership), after staging the patch of map cells the tile's tables

@@ -27,6 +27,7 @@ struct dc_frame;  // include/deepcut_hip.h: one video frame (planes, pitches, fo
 struct dc_complete_params;  // include/deepcut_hip.h: stage D of the people assembly
 struct dc_dedupe_params;    // include/deepcut_hip.h: stage E of the people assembly
 struct dc_draw_style;       // include/deepcut_hip.h: the skeleton overlay
+struct dc_label_style;      // include/deepcut_hip.h: the label overlay
 struct dc_redact_style;     // include/deepcut_hip.h: the redaction
 struct dc_heat_geometry;    // include/deepcut_hip.h: the score-map overlay
 struct dc_heat_style;
@@ -300,6 +301,10 @@ void dedupe_people(const dc_dedupe_params* params, int nb, int P, int J, const i
 void draw_people(const dc_frame* frames, int nb, int h, int w, bool is_device, int P, int J, const int* n_people, const double* people,
                  const int* cand, const long long* ids, const dc_draw_style* style, void* stream);
 void draw_limits(int* tile_w, int* tile_h, int* chunk);
+// dc_label_people / dc_label_font (label.cpp): people's ids as text on a plate, in place on the device, synchronous
+void label_people(const dc_frame* frames, int nb, int h, int w, bool is_device, int P, int J, const int* n_people, const double* people,
+                  const long long* ids, const char* texts, const dc_label_style* style, void* stream);
+void label_font(int ch, unsigned char* rows);
 // The overlays of dc_overlay_people_device / dc_net_track_frames_async_overlay: either style or both (redaction first), the id lists
 // of the redaction (n < 0: no such list) and where `redacted` [nb][P] goes (may be null) — device memory for the stand-alone entry,
 // the caller's host array for the chain
@@ -311,7 +316,9 @@ struct OverlayArgs {
   const long long* keep_ids = nullptr;
   int n_keep = -1;
   int* redacted = nullptr;
-  bool any() const { return draw || redact; }
+  const dc_label_style* labels = nullptr;  // the labels, written last (dc_overlay_styles)
+  bool styles_entry = false;               // the call came through a `_styles` entry, which takes a label style too: the refusal says so
+  bool any() const { return draw || redact || labels; }
 };
 // dc_overlay_people_device (overlay.cpp): the bytes of redact_people then draw_people from people, cand and ids in DEVICE memory, the
 // primitives and the tile selection made on the device.  Asynchronous on a caller's stream with device frames, else it waits

@@ -118,6 +118,9 @@ DC_INTERNAL void check_n_people(const char* who, const int* n_people, int nb, in
 // the styles as dc_draw_people / dc_redact_people refuse them, a null one included (draw.cpp, redact.cpp)
 DC_INTERNAL void check_draw_style(const char* who, const dc_draw_style* st, int J);
 DC_INTERNAL void check_redact_style(const char* who, const dc_redact_style* st, int J);
+// the label style as dc_label_people refuses it (label.cpp), and the builder's arguments made from a checked one
+DC_INTERNAL void check_label_style(const char* who, const dc_label_style* st, int J);
+DC_INTERNAL LabelBuild label_build_args(const dc_label_style* st, const dc_frame& like, int P, int J, int h, int w);
 // pixels -> 1/16 pixel, ties to even
 DC_INTERNAL inline int snap16(double v) { return (int)std::rint(16.0 * std::min(32768.0, std::max(-32768.0, v))); }
 // a pose [J][3] (x, y, score) -> held[j]: the joint is finite and its score above min_score; then (qx, qy)[j] is its snapped place
@@ -189,8 +192,8 @@ struct DC_INTERNAL FrameStage {
 
 // The overlays from people in device memory (overlay.cpp), checked with the synchronous entries' words (DC_EINVAL, before a device is
 // needed) and converted once: the builders' arguments, the id lists, and the layout of the device block the launches work in —
-//   DrawPlanes[nb] | only_ids, keep_ids | n_prims of the redaction, of the drawing | redacted [nb][P] | the redaction's primitives | the
-//   drawing's — every part rounded up to 256 bytes.  like: a frame of the call (format, matrix, range).
+//   DrawPlanes[nb] | only_ids, keep_ids | n_prims of the redaction, of the drawing, of the labels | redacted [nb][P] | the redaction's
+//   primitives | the drawing's | the labels' (LabelPrim [nb][P]) — every part rounded up to 256 bytes.  like: a frame of the call (format, matrix, range).
 // build: the builders, which read the people — for the chain IN FRONT OF the tracker's event, since they read its scratch.  tiles: the
 // frame table (host copy `table`, travelling as a kernel argument) and the tile kernels, redaction first; they read the block only.
 struct DC_INTERNAL OverlayPlan {
@@ -198,12 +201,13 @@ struct DC_INTERNAL OverlayPlan {
   void build(unsigned char* dev, int nb, const int* d_np, const double* d_ppl, const int* d_cand, const long long* d_ids, int* d_redacted,
              void* s) const;  // d_redacted null: the block's own
   void tiles(unsigned char* dev, const DrawPlanes* table, int nb, void* s) const;
-  bool draw = false, redact = false;
+  bool draw = false, redact = false, labels = false;
   int format, effect = 0, block = 0, P, J, h, w, stride_draw = 0, stride_redact = 0;
   unsigned fill = 0;
   OverlayBuild db{}, rb{};
+  LabelBuild lb{};
   long long only[kOverlayMaxIds] = {}, keep[kOverlayMaxIds] = {};
-  size_t at_table = 0, at_lists = 0, at_count = 0, at_redacted = 0, at_prims_r = 0, at_prims_d = 0, bytes = 0;
+  size_t at_table = 0, at_lists = 0, at_count = 0, at_redacted = 0, at_prims_r = 0, at_prims_d = 0, at_prims_l = 0, bytes = 0;
 };
 
 // ---- streams.cpp ------------------------------------------------------------------------------------

@@ -16,9 +16,12 @@ static_assert(sizeof(DrawPlanes) == sizeof(FramePlanes), "a staged frame table i
 OverlayPlan::OverlayPlan(const char* who, const dc_frame& like, int nb, int h_, int w_, int P_, int J_, const OverlayArgs& a, bool have_ids)
     : format(like.format), P(P_), J(J_), h(h_), w(w_) {
   auto bad = [&](const std::string& m) { throw DcError(DC_EINVAL, std::string(who) + ": " + m); };
-  if (!a.draw && !a.redact) bad("null argument: style (a draw style, a redact style or both)");
+  if (!a.draw && !a.redact && !a.labels)  // the older entries keep their words
+    bad(a.styles_entry ? "null argument: style (styles must hold a draw style, a redact style, a label style or several of them)"
+                       : "null argument: style (a draw style, a redact style or both)");
   if (a.redact) check_redact_style(who, a.redact, J);
   if (a.draw) check_draw_style(who, a.draw, J);
+  if (a.labels) check_label_style(who, a.labels, J);
   auto check_list = [&](const char* name, const long long* v, int n) {
     if (n < 0) return;
     if (!a.redact) bad(std::string(name) + " chooses who is redacted: a redact style is needed");
@@ -60,6 +63,7 @@ OverlayPlan::OverlayPlan(const char* who, const dc_frame& like, int nb, int h_, 
     for (int k = 0; k < st->n_palette; ++k) db.palette[k] = colour(st->palette + 3 * (size_t)k);
     stride_draw = P * overlay_prims_per_person(J, st->n_edges);
   }
+  if (a.labels) labels = true, lb = label_build_args(a.labels, like, P, J, h, w);
   size_t at = 0;
   auto take = [&](size_t b) {
     const size_t r = at;
@@ -68,10 +72,11 @@ OverlayPlan::OverlayPlan(const char* who, const dc_frame& like, int nb, int h_, 
   };
   at_table = take((size_t)nb * sizeof(DrawPlanes));
   at_lists = take(2 * (size_t)kOverlayMaxIds * sizeof(long long));
-  at_count = take(2 * (size_t)nb * sizeof(int));
+  at_count = take(3 * (size_t)nb * sizeof(int));
   at_redacted = take((size_t)nb * P * sizeof(int));
   at_prims_r = take((size_t)nb * stride_redact * sizeof(DrawPrim));
   at_prims_d = take((size_t)nb * stride_draw * sizeof(DrawPrim));
+  at_prims_l = take(labels ? (size_t)nb * P * sizeof(LabelPrim) : 0);
   bytes = at;
 }
 
@@ -88,6 +93,7 @@ void OverlayPlan::build(unsigned char* dev, int nb, const int* d_np, const doubl
   if (draw)
     KCHECK(launch_overlay_build(db, nb, d_np, d_ppl, d_cand, d_ids, nullptr, nullptr, reinterpret_cast<DrawPrim*>(dev + at_prims_d), count + nb,
                                 nullptr, s));
+  if (labels) KCHECK(launch_label_build(lb, nb, d_np, d_ppl, d_ids, reinterpret_cast<LabelPrim*>(dev + at_prims_l), count + 2 * nb, s));
 }
 
 void OverlayPlan::tiles(unsigned char* dev, const DrawPlanes* table, int nb, void* s) const {
@@ -98,6 +104,8 @@ void OverlayPlan::tiles(unsigned char* dev, const DrawPlanes* table, int nb, voi
     KCHECK(launch_redact_all(format, effect, block, fill, d_table, nb, h, w, reinterpret_cast<const DrawPrim*>(dev + at_prims_r), count,
                              stride_redact, s));
   if (draw) KCHECK(launch_draw_all(format, d_table, nb, h, w, reinterpret_cast<const DrawPrim*>(dev + at_prims_d), count + nb, stride_draw, s));
+  if (labels)  // last: the labels go over everything else
+    KCHECK(launch_label_all(format, d_table, nb, h, w, reinterpret_cast<const LabelPrim*>(dev + at_prims_l), count + 2 * nb, P, s));
 }
 
 namespace {

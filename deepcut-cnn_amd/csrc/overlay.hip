@@ -13,6 +13,7 @@
 
 #include "frame_tile.h"
 #include "kernels.h"
+#include "label_tile.h"
 
 namespace dc {
 
@@ -237,6 +238,100 @@ __global__ __launch_bounds__(256) void redact_all_kernel(const DrawPlanes* __res
   redact_finish<FMT, EFFECT>(f, H, W, x0, y0, in, n_in, blk, hit, bshift, fill, flag, acc);
 }
 
+// ---- the labels (the rule: dc_label_people) ----------------------------------------------------------------------------------------------
+// The builder of the labels, in the pattern of overlay_build_kernel: one workgroup per frame, one thread per person, who makes at most
+// one label exactly as label.cpp makes it — held joints by snap16, the key's digits by int64 division behind the prefix, the anchor and
+// the clamp by label_place —; the workgroup scan puts the labels in person order.  Device labels take no `texts`.
+__global__ __launch_bounds__(256) void label_build_kernel(const LabelBuild q, const int* __restrict__ n_people, const double* __restrict__ people,
+                                                          const long long* __restrict__ ids, LabelPrim* __restrict__ prims,
+                                                          int* __restrict__ n_labels) {
+  __shared__ int wave_tot[4];
+  const int b = blockIdx.x, p = threadIdx.x, lane = p & 63, wave = p >> 6;
+  const int n = min(max(n_people[b], 0), q.P);  // whatever the count says, nothing beyond P is read
+  const size_t at = (size_t)b * q.P + p;
+  LabelPrim lp{};
+  bool made = false;
+  if (p < n && (q.alpha_text > 0 || q.alpha_plate > 0)) {
+    const long long key = ids ? ids[at] : (long long)p;
+    if (key >= 0) {
+      const double* pose = people + at * q.J * 3;
+      int qx[32], qy[32];
+      unsigned held = 0;
+      for (int j = 0; j < q.J; ++j) {
+        const double x = pose[3 * j], y = pose[3 * j + 1], s = pose[3 * j + 2];
+        const bool h = isfinite(x) && isfinite(y) && isfinite(s) && s > q.min_score;
+        qx[j] = h ? snap16_dev(x) : 0, qy[j] = h ? snap16_dev(y) : 0;
+        held |= (unsigned)h << j;
+      }
+      for (int k = 0; k < q.n_prefix; ++k) lp.text[k] = q.prefix[k];
+      lp.n = label_put_key(key, lp.text, q.n_prefix), lp.s = q.scale;
+      made = label_place(qx, qy, held, q.J, q.anchor, lp.n, lp.s, q.gap, q.H, q.W, lp.x, lp.y);
+      const unsigned person = q.palette[(int)(key % q.n_palette)];
+      lp.text_colour = q.plate_by_person ? q.text_colour : person, lp.plate_colour = q.plate_by_person ? person : q.plate_colour;
+      lp.alpha_text = q.alpha_text, lp.alpha_plate = q.alpha_plate;
+    }
+  }
+  const int count = made ? 1 : 0;
+  int upto = count;
+  for (int d = 1; d < 64; d <<= 1) {
+    const int v = __shfl_up(upto, d);
+    if (lane >= d) upto += v;
+  }
+  if (lane == 63) wave_tot[wave] = upto;
+  __syncthreads();
+  int first = upto - count, total = 0;
+  for (int k = 0; k < 4; ++k) {
+    if (k < wave) first += wave_tot[k];
+    total += wave_tot[k];
+  }
+  if (made) prims[(size_t)b * q.P + first] = lp;  // first < the number of people who made a label <= P, the frame's stride
+  if (p == 0) n_labels[b] = total;
+}
+
+// Over every tile of every frame, behind draw_all_kernel: the frame's labels are walked in passes of kLabelPass, the first kLabelPass
+// threads testing one each against the tile; the hits are compacted in order into LDS and go through label_chunk.  A tile that
+// nothing reaches loads no pixel
+template <int FMT>
+__global__ __launch_bounds__(256) void label_all_kernel(const DrawPlanes* __restrict__ frames, int H, int W, const LabelPrim* __restrict__ prims,
+                                                        const int* __restrict__ n_labels, int stride) {
+  __shared__ LabelPrim sp[kLabelPass];
+  __shared__ unsigned char font[kLabelFontBytes];
+  __shared__ int wave_tot[4];
+  const int b = blockIdx.z, n = min(n_labels[b], stride);
+  if (n <= 0) return;
+  const LabelPrim* mine = prims + (size_t)b * stride;
+  label_stage_font(font);  // the first pass's barriers follow
+  BlockPixels<FMT> px(blockIdx.x * kDrawTileW, blockIdx.y * kDrawTileH, H, W);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  DrawPlanes f{};
+  bool loaded = false;
+  for (int base = 0; base < n; base += kLabelPass) {
+    const int i = base + (int)threadIdx.x;
+    LabelPrim p{};
+    bool hit = false;
+    if ((int)threadIdx.x < kLabelPass && i < n) {
+      p = mine[i];
+      hit = label_reaches(p, blockIdx.x, blockIdx.y, H, W);
+    }
+    const unsigned long long hits = __ballot(hit);
+    const int before = __popcll(hits & ((1ull << lane) - 1ull));
+    __syncthreads();  // everybody is through with the pass before, and with its totals
+    if (lane == 0) wave_tot[wave] = __popcll(hits);
+    __syncthreads();
+    int first = before, m = 0;
+    for (int k = 0; k < 4; ++k) {
+      if (k < wave) first += wave_tot[k];
+      m += wave_tot[k];
+    }
+    if (hit) sp[first] = p;  // first < m <= kLabelPass
+    __syncthreads();
+    if (!m) continue;  // the same in every thread
+    if (!loaded) f = frames[b], px.load(f), loaded = true;
+    if (px.n_in) label_chunk(px, sp, m, font);
+  }
+  if (loaded) px.store(f);
+}
+
 // small tables that travel as kernel arguments: no host buffer has to outlive an upload, and nothing waits
 struct IdList {
   long long v[kOverlayMaxIds];
@@ -290,6 +385,29 @@ int launch_draw_all(int format, const DrawPlanes* frames, int nb, int height, in
     hipLaunchKernelGGL(draw_all_kernel<kFmtBgr>, grid, dim3(256), 0, (hipStream_t)stream, frames, height, width, prims, n_prims, stride);
   else
     hipLaunchKernelGGL(draw_all_kernel<kFmtNv12>, grid, dim3(256), 0, (hipStream_t)stream, frames, height, width, prims, n_prims, stride);
+  return (int)hipGetLastError();
+}
+
+int launch_label_build(const LabelBuild& q, int nb, const int* n_people, const double* people, const long long* ids, LabelPrim* prims,
+                       int* n_labels, void* stream) {
+  if (nb < 1 || q.P < 1 || q.P > 256 || q.J < 1 || q.J > 32 || q.scale < 1 || q.scale > 8 || q.n_palette < 1 || q.n_palette > 256 ||
+      q.n_prefix < 0 || q.n_prefix > 4)
+    return (int)hipErrorInvalidValue;
+  for (int k = 0; k < q.n_prefix; ++k)
+    if (q.prefix[k] >= kLabelGlyphs) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(label_build_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, q, n_people, people, ids, prims, n_labels);
+  return (int)hipGetLastError();
+}
+
+int launch_label_all(int format, const DrawPlanes* frames, int nb, int height, int width, const LabelPrim* prims, const int* n_labels, int stride,
+                     void* stream) {
+  if ((format != kFmtBgr && format != kFmtNv12) || nb < 1 || nb > kOverlayMaxFrames || height < 1 || width < 1 || stride < 1)
+    return (int)hipErrorInvalidValue;
+  const dim3 grid = tile_grid(nb, height, width);
+  if (format == kFmtBgr)
+    hipLaunchKernelGGL(label_all_kernel<kFmtBgr>, grid, dim3(256), 0, (hipStream_t)stream, frames, height, width, prims, n_labels, stride);
+  else
+    hipLaunchKernelGGL(label_all_kernel<kFmtNv12>, grid, dim3(256), 0, (hipStream_t)stream, frames, height, width, prims, n_labels, stride);
   return (int)hipGetLastError();
 }
 

@@ -30,17 +30,24 @@ struct __attribute__((visibility("hidden"))) TileBins {  // the library exports 
     const int y0 = std::max(0, lo_px(std::min(p.ay, p.by) - p.r16)), y1 = std::min(h_ - 1, hi_px(std::max(p.ay, p.by) + p.r16));
     if (x0 > x1 || y0 > y1) return false;
     prims.push_back(p);
-    const Box bx{x0 / kDrawTileW, y0 / kDrawTileH, x1 / kDrawTileW, y1 / kDrawTileH};
-    boxes_.push_back(bx);
-    for (int ty = bx.ty0; ty <= bx.ty1; ++ty)
-      for (int tx = bx.tx0; tx <= bx.tx1; ++tx) ++count_[(size_t)ty * tiles_x_ + tx];
+    bin(x0, y0, x1, y1);
+    return true;
+  }
+
+  // A primitive of the frame at hand that is not a DrawPrim (a label: label.cpp), by the pixels [x0, x1] x [y0, y1] it may write, both
+  // ends inclusive.  Nothing goes into `prims`: the caller keeps its own list, and `index` names places in it, counted over the boxes
+  // added.  One binner takes either add or add_box, never both.  -> whether a pixel of the box lies in the frame
+  bool add_box(int x0, int y0, int x1, int y1) {
+    x0 = std::max(0, x0), y0 = std::max(0, y0), x1 = std::min(w_ - 1, x1), y1 = std::min(h_ - 1, y1);
+    if (x0 > x1 || y0 > y1) return false;
+    bin(x0, y0, x1, y1);
     return true;
   }
 
   // Frame b is complete: its non-empty tiles, row by row, each with its stretch of `index`; then the primitives in order fill the
   // stretches.  -> false once there are more than 2^30 primitive-tile pairs (the caller refuses; the binner is not used further)
   bool close_frame(int b) {
-    const size_t first_prim = prims.size() - boxes_.size();
+    const size_t first_prim = added_ - boxes_.size();
     if (boxes_.empty()) return true;
     touched[(size_t)b] = 1;
     slot_.assign(count_.size(), -1);
@@ -77,6 +84,14 @@ struct __attribute__((visibility("hidden"))) TileBins {  // the library exports 
   struct Box {
     int tx0, ty0, tx1, ty1;  // the tiles a primitive is binned into, inclusive
   };
+  void bin(int x0, int y0, int x1, int y1) {  // in-frame pixels, inclusive
+    const Box bx{x0 / kDrawTileW, y0 / kDrawTileH, x1 / kDrawTileW, y1 / kDrawTileH};
+    boxes_.push_back(bx);
+    ++added_;
+    for (int ty = bx.ty0; ty <= bx.ty1; ++ty)
+      for (int tx = bx.tx0; tx <= bx.tx1; ++tx) ++count_[(size_t)ty * tiles_x_ + tx];
+  }
+  size_t added_ = 0;               // primitives binned so far, over all frames
   int h_, w_, tiles_x_;
   std::vector<int> count_, slot_;  // per tile of the frame at hand: its primitives, then its place in `tiles`
   std::vector<Box> boxes_;         // of the frame at hand's primitives

@@ -14,5 +14,6 @@ from .pycaffe import draw_people, draw_limits, draw_coefficients, DRAW_JOINT_COL
 from .pycaffe import draw_heatmap, HEAT_LUT  # noqa: F401
 from .pycaffe import redact_people, redact_select, REDACT_DEFAULTS  # noqa: F401
 from .pycaffe import overlay_people_device  # noqa: F401
+from .pycaffe import label_people, LABEL_FONT, LABEL_CHARS, LABEL_DEFAULTS, LABEL_MAX_CHARS  # noqa: F401
 
 __version__ = "1.0.0-rc3+deepcut_hip"

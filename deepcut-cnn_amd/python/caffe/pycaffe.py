@@ -93,6 +93,19 @@ class RedactStyle(C.Structure):
                 ("effect", C.c_int), ("block", C.c_int), ("fill", C.c_ubyte * 3)]
 
 
+class LabelStyle(C.Structure):
+    """dc_label_style (include/deepcut_hip.h)."""
+    _fields_ = [("scale", C.c_int), ("gap", C.c_int), ("anchor_joint", C.c_int), ("alpha_text", C.c_int), ("alpha_plate", C.c_int),
+                ("min_score", C.c_double), ("color_mode", C.c_int), ("palette", C.c_void_p), ("n_palette", C.c_int),
+                ("text_color", C.c_ubyte * 3), ("plate_color", C.c_ubyte * 3), ("prefix", C.c_char * 8)]
+
+
+class OverlayStyles(C.Structure):
+    """dc_overlay_styles (include/deepcut_hip.h)."""
+    _fields_ = [("size", C.c_size_t), ("draw", C.POINTER(DrawStyle)), ("redact", C.POINTER(RedactStyle)), ("labels", C.POINTER(LabelStyle)),
+                ("only_ids", C.c_void_p), ("n_only", C.c_int), ("keep_ids", C.c_void_p), ("n_keep", C.c_int)]
+
+
 class HeatGeometry(C.Structure):
     """dc_heat_geometry (include/deepcut_hip.h)."""
     _fields_ = [("scale", C.c_double), ("origin_x", C.c_double), ("origin_y", C.c_double)]
@@ -417,6 +430,11 @@ def _load():
                                           vp, ci, vp, ci, vp, vp]),
         "dc_net_track_frames_async_overlay": (ci, [vp, vp, vp, vp, ci, ci, ci, C.c_double, ci, vp, C.POINTER(AssembleParams), ci, vp, vp, vp, vp,
                                                    vp, vp, vp, vp, vp, C.POINTER(DrawStyle), C.POINTER(RedactStyle), vp, ci, vp, ci, vp]),
+        "dc_label_people": (ci, [C.POINTER(DcFrame), ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, C.POINTER(LabelStyle), vp]),
+        "dc_label_font": (ci, [ci, C.POINTER(C.c_ubyte * 7)]),
+        "dc_overlay_people_device_styles": (ci, [C.POINTER(DcFrame), ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, C.POINTER(OverlayStyles), vp, vp]),
+        "dc_net_track_frames_async_styles": (ci, [vp, vp, vp, vp, ci, ci, ci, C.c_double, ci, vp, C.POINTER(AssembleParams), ci, vp, vp, vp, vp,
+                                                  vp, vp, vp, vp, vp, C.POINTER(OverlayStyles), vp]),
         "dc_draw_heatmap": (ci, [C.POINTER(DcFrame), ci, ci, ci, ci, vp, ci, ci, ci, ci, C.POINTER(HeatGeometry), C.POINTER(HeatStyle), vp]),
         "dc_net_draw_heatmap": (ci, [vp, C.POINTER(DcFrame), ci, ci, ci, ci, C.POINTER(HeatGeometry), C.POINTER(HeatStyle)]),
         "dc_group_draw_heatmap": (ci, [vp, C.POINTER(DcFrame), ci, ci, ci, ci, vp, ci, C.c_double, C.c_double, C.POINTER(HeatStyle)]),
@@ -1270,12 +1288,138 @@ def redact_people(frames, people, n_people=None, select=None, ids=None, only_ids
     return out[0, :people.shape[0]] if single else out
 
 
+# ---- labelling people in frames (dc_label_people; the rule: include/deepcut_hip.h — this project's own, the reference has none) --------
+LABEL_CHARS = "0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZ #-.:/%+_?"  # the font's set, in the table's order; lower case folds to upper case
+LABEL_MAX_CHARS = 24  # DC_LABEL_MAX_CHARS: a text holds at most 23 characters
+
+
+def _label_font():
+    font = {}
+    for ch in LABEL_CHARS:
+        rows = (C.c_ubyte * 7)()
+        _check(_lib.dc_label_font(ord(ch), C.byref(rows)))
+        font[ch] = tuple(int(v) for v in rows)
+    return font
+
+
+# The built-in 5 x 7 font as the kernels read it (dc_label_font): {character: 7 rows, bit 4 the leftmost column}.  A PLACEHOLDER.
+LABEL_FONT = _label_font()
+# PLACEHOLDERS, not tested for legibility on real video: override them.  palette None = DRAW_ID_COLORS.
+LABEL_DEFAULTS = {"scale": 2, "gap": 2, "anchor": None, "prefix": "", "alpha_text": 256, "alpha_plate": 160, "min_score": 0.0, "color": "plate",
+                  "palette": None, "text_color": (255, 255, 255), "plate_color": (0, 0, 0)}
+_LABEL_MODES = {"plate": 0, "text": 1}  # DC_LABEL_PLATE_BY_PERSON, DC_LABEL_TEXT_BY_PERSON
+
+
+def _label_text(text, what, limit):
+    """A text of `label_people` -> its bytes, upper-cased; ValueError naming a character outside the set or a text that is too long."""
+    if not isinstance(text, str):
+        raise ValueError("%s must be a str, got %r" % (what, text))
+    up = text.upper()
+    for i, ch in enumerate(up):
+        if ch not in LABEL_CHARS:
+            raise ValueError("%s: character %r at %d is outside the label set %r" % (what, text[i], i, LABEL_CHARS))
+    if len(up) > limit:
+        raise ValueError("%s: %r holds %d characters, at most %d are taken" % (what, text, len(up), limit))
+    return up.encode("ascii")
+
+
+def _label_style_struct(scale=LABEL_DEFAULTS["scale"], gap=LABEL_DEFAULTS["gap"], anchor=LABEL_DEFAULTS["anchor"], prefix=LABEL_DEFAULTS["prefix"],
+                        alpha_text=LABEL_DEFAULTS["alpha_text"], alpha_plate=LABEL_DEFAULTS["alpha_plate"], min_score=LABEL_DEFAULTS["min_score"],
+                        color=LABEL_DEFAULTS["color"], palette=LABEL_DEFAULTS["palette"], text_color=LABEL_DEFAULTS["text_color"],
+                        plate_color=LABEL_DEFAULTS["plate_color"]):
+    """The style arguments of `label_people` -> (LabelStyle, the arrays it points into).  Names, shapes and the prefix's characters are
+    checked here; the values are the library's to refuse."""
+    if color not in _LABEL_MODES:
+        raise ValueError("color must be one of %s, got %r" % (sorted(_LABEL_MODES), color))
+    pal = _palette_array(DRAW_ID_COLORS if palette is None else palette)
+    st = LabelStyle()
+    st.scale, st.gap, st.anchor_joint = int(scale), int(gap), -1 if anchor is None else int(anchor)
+    st.alpha_text, st.alpha_plate, st.min_score = int(alpha_text), int(alpha_plate), float(min_score)
+    st.color_mode, st.palette, st.n_palette = _LABEL_MODES[color], pal.ctypes.data if pal.shape[0] else None, int(pal.shape[0])
+    st.text_color[:] = [int(v) for v in text_color]
+    st.plate_color[:] = [int(v) for v in plate_color]
+    st.prefix = _label_text(prefix, "prefix", 4)
+    return st, (pal,)
+
+
+def _label_texts(texts, nb, p):
+    """texts of `label_people` — a list of str (one frame) or a list of nb such lists; None or "" = the made text — -> bytes [nb, P, 24]."""
+    if texts is None:
+        return None
+    rows = list(texts)
+    if nb == 1 and (not rows or isinstance(rows[0], str) or rows[0] is None):
+        rows = [rows]
+    if len(rows) != nb:
+        raise ValueError("texts must hold one list per frame: %d for %d frames" % (len(rows), nb))
+    out = np.zeros((nb, p, LABEL_MAX_CHARS), np.uint8)
+    for b, row in enumerate(rows):
+        row = list(row)
+        if len(row) > p:
+            raise ValueError("texts[%d] holds %d texts for %d people" % (b, len(row), p))
+        for k, t in enumerate(row):
+            v = _label_text("" if t is None else t, "texts[%d][%d]" % (b, k), LABEL_MAX_CHARS - 1)
+            out[b, k, :len(v)] = np.frombuffer(v, np.uint8)
+    return out
+
+
+def label_people(frames, people, n_people=None, ids=None, texts=None, scale=LABEL_DEFAULTS["scale"], gap=LABEL_DEFAULTS["gap"],
+                 anchor=LABEL_DEFAULTS["anchor"], prefix=LABEL_DEFAULTS["prefix"], alpha_text=LABEL_DEFAULTS["alpha_text"],
+                 alpha_plate=LABEL_DEFAULTS["alpha_plate"], min_score=LABEL_DEFAULTS["min_score"], color=LABEL_DEFAULTS["color"],
+                 palette=LABEL_DEFAULTS["palette"], text_color=LABEL_DEFAULTS["text_color"], plate_color=LABEL_DEFAULTS["plate_color"],
+                 stream=None):
+    """People's ids written into frames IN PLACE on the device (dc_label_people; the rule — integer only, this project's own: the
+    reference labels nothing — is in include/deepcut_hip.h): per person `prefix` (at most 4 characters) and the id in decimal, in the
+    built-in 5 x 7 font (LABEL_FONT) at `scale` (1..8), on a plate, `gap` pixels above the joint `anchor` (centred on it) or, with
+    anchor None or that joint not held, above the upper left corner of the person's bounding box; pulled into the frame where it fits.
+    frames, people, n_people, ids: as `draw_people` takes them (without ids the person's index is written; an id < 0 gets no label).
+    texts: a list of str per frame (a plain list for one frame), upper-cased here; a non-empty one replaces the person's made text.
+    A character outside LABEL_CHARS, or a text of more than 23 characters, is a ValueError here, before any call into the library.
+    color: "plate" — the plate is palette[id % len] and the text text_color — or "text" — the text takes the palette colour and the
+    plate plate_color; palette None = DRAW_ID_COLORS.  alpha_text / alpha_plate: 0..256 (0: that layer is not made).  The defaults
+    (LABEL_DEFAULTS) are PLACEHOLDERS.  stream: as `draw_people`.  The call returns when the frames are written.  Needs GPU mode."""
+    arr, nb, h, w, is_device, _keep, ppl, n, p, j = _frames_and_people(frames, people, n_people)
+    idv = None if ids is None else _per_image(ids, np.int64, ())
+    if idv is not None and idv.shape != ppl.shape[:2]:
+        raise ValueError("ids must be %s like people, got shape %s" % (ppl.shape[:2], idv.shape))
+    txt = _label_texts(texts, nb, p)
+    st, _alive = _label_style_struct(scale, gap, anchor, prefix, alpha_text, alpha_plate, min_score, color, palette, text_color, plate_color)
+    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    _check(_lib.dc_label_people(arr, nb, h, w, int(is_device), p, j, ptr(n), ptr(ppl), ptr(idv), ptr(txt), C.byref(st), _stream_arg(stream)))
+
+
+def _label_overlay_struct(labels):
+    """labels= of the device routes: True or a dict of the STYLE arguments of `label_people` -> (LabelStyle, what to keep alive).  `texts`
+    and `stream` are refused: a text for a person cannot exist before the person does, and the route has its own stream."""
+    style = {} if labels is True else dict(labels)
+    for k in ("texts", "stream"):
+        if style.pop(k, None) is not None:
+            raise ValueError("%s cannot go with labels on this route: the labels are made on the device from the people it finds" % k)
+    return _label_style_struct(**style)
+
+
+def _overlay_styles_struct(dst, rst, lst, only, keep):
+    """The styles of the two `_styles` entries -> (OverlayStyles, nothing more to keep alive than its parts)."""
+    ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data  # noqa: E731
+    st = OverlayStyles()
+    st.size = C.sizeof(OverlayStyles)
+    if dst is not None:
+        st.draw = C.pointer(dst)
+    if rst is not None:
+        st.redact = C.pointer(rst)
+    if lst is not None:
+        st.labels = C.pointer(lst)
+    st.only_ids, st.n_only = ptr(only), -1 if only is None else int(only.size)
+    st.keep_ids, st.n_keep = ptr(keep), -1 if keep is None else int(keep.size)
+    return st
+
+
 # ---- overlays from people in device memory (dc_overlay_people_device, dc_net_track_frames_async_overlay) --------------------------------
-def _overlay_args(draw, redact, have_ids):
+def _overlay_args(draw, redact, have_ids, labels=None):
     """draw / redact: None or dicts of the STYLE arguments of `draw_people` / `redact_people` (a redact dict may carry only_ids /
-    keep_ids) -> (DrawStyle or None, RedactStyle or None, only_ids int64 array or None, keep_ids likewise, what to keep alive)."""
-    if draw is None and redact is None:
-        raise ValueError("an overlay needs draw=, redact= or both")
+    keep_ids) -> (DrawStyle or None, RedactStyle or None, only_ids int64 array or None, keep_ids likewise, what to keep alive).
+    labels (checked by the caller, `_label_overlay_struct`) only makes a call without the two a good one."""
+    if draw is None and redact is None and labels is None:
+        raise ValueError("an overlay needs draw=, redact= or both — or labels=, alone or beside them")
     dst = rst = only = keep = None
     alive = []
     if redact is not None:
@@ -1313,20 +1457,30 @@ def _device_pointer(a, name, dtype, shape):
     return C.c_void_p(int(a.data_ptr()))
 
 
-def overlay_people_device(frames, people, n_people, cand=None, ids=None, draw=None, redact=None, redacted=None, stream=None):
+def overlay_people_device(frames, people, n_people, cand=None, ids=None, draw=None, redact=None, redacted=None, stream=None, labels=None):
     """The bytes of `redact_people` then `draw_people` from people that are in DEVICE memory (dc_overlay_people_device): the primitives
     and the per-tile selection are made on the device, nothing of the poses travels.  frames: as `draw_people` takes them (host frames
     travel up and ALL travel back).  people: a float64 device tensor [nb, P, J, 3] (a torch tensor: anything with data_ptr(), dtype and
     shape); n_people: int32 [nb]; cand: int32 [nb, P, J] or None; ids: int64 [nb, P] or None; redacted: int32 [nb, P] or None, written by
     the redaction.  draw / redact: dicts of the style arguments of `draw_people` / `redact_people` (either may be None); a redact dict
     may carry only_ids / keep_ids (at most 256 each; they need ids) and no `select`.  stream: a HIP stream — with device frames the call
-    then returns once everything is enqueued on it, and the tensors must stay alive until that stream has run; otherwise it waits."""
+    then returns once everything is enqueued on it, and the tensors must stay alive until that stream has run; otherwise it waits.
+    labels: None, True (LABEL_DEFAULTS) or a dict of the style arguments of `label_people` without `texts` and `stream`
+    (dc_overlay_people_device_styles): the bytes of `label_people` behind the other two, the ids (or the people's indices) as text."""
     arr, nb, h, w, is_device, _keep = _writable_frames(frames)
     shape = tuple(getattr(people, "shape", ()))
     if len(shape) != 4 or shape[0] != nb or shape[3] != 3:
         raise ValueError("people must be a device tensor [nb = %d, P, J, 3], got shape %s" % (nb, shape))
     p, j = int(shape[1]), int(shape[2])
-    dst, rst, only, keep, _alive = _overlay_args(draw, redact, ids is not None)
+    lst, _lalive = (None, None) if labels is None else _label_overlay_struct(labels)
+    dst, rst, only, keep, _alive = _overlay_args(draw, redact, ids is not None, lst)
+    if lst is not None:
+        styles = _overlay_styles_struct(dst, rst, lst, only, keep)
+        _check(_lib.dc_overlay_people_device_styles(arr, nb, h, w, int(is_device), p, j, _device_pointer(n_people, "n_people", "int32", (nb,)),
+                                                    _device_pointer(people, "people", "float64", shape),
+                                                    _device_pointer(cand, "cand", "int32", (nb, p, j)), _device_pointer(ids, "ids", "int64", (nb, p)),
+                                                    C.byref(styles), _device_pointer(redacted, "redacted", "int32", (nb, p)), _stream_arg(stream)))
+        return
     _check(_lib.dc_overlay_people_device(arr, nb, h, w, int(is_device), p, j, _device_pointer(n_people, "n_people", "int32", (nb,)),
                                          _device_pointer(people, "people", "float64", shape), _device_pointer(cand, "cand", "int32", (nb, p, j)),
                                          _device_pointer(ids, "ids", "int64", (nb, p)), *_overlay_c_args(dst, rst, only, keep),
@@ -2139,7 +2293,7 @@ class Net(_Completing):
 
     def track_frames_async(self, frames_or_images, tracker=None, scale=1.0, slot_of=None, assemble_scale=None, threshold=0.1, radius=1,
                            max_det=16, edges=None, mean=None, std=None, max_cost=32.0, seed_threshold=0.5, max_people=32, min_joints=1,
-                           joint_order=None, complete=None, dedupe=None, draw=None, redact=None):
+                           joint_order=None, complete=None, dedupe=None, draw=None, redact=None, labels=None):
         """The whole video chain without a host wait (dc_net_track_frames_async): upload, pre-processing, forward, assembly, the
         tracker's update and the downloads are enqueued on the net's own stream and the call returns.  frames_or_images: a `Frame`, a
         list of `Frame`s of one size, or uint8 [n,H,W,3] / [H,W,3] BGR; they must stay untouched until the result is collected.
@@ -2153,14 +2307,19 @@ class Net(_Completing):
         frames are then redacted and drawn into IN PLACE inside the chain, behind the tracker, from the people, cand and ids being handed
         back (the bytes of `redact_people` then `draw_people` on them), with no host wait: they must be writable, host frames ALL travel
         back, and they are the caller's again after `result()`.  A redact dict may carry only_ids / keep_ids (they need a tracker) and
-        no `select`; `result()` then adds "redacted"."""
+        no `select`; `result()` then adds "redacted".
+        labels (dc_net_track_frames_async_styles): None, True (LABEL_DEFAULTS) or a dict of the style arguments of `label_people`
+        without `texts` and `stream` — the tracker's ids (without a tracker the people's indices) are written over the other two, the
+        bytes of `label_people` on the people and ids handed back."""
         if edges is None:
             raise ValueError("track_frames_async needs the regression edges (deepcut_tools.read_pair_stats)")
         if tracker is not None:
             _tracker_handle(tracker)
-        overlay = None
-        if draw is not None or redact is not None:
-            overlay = _overlay_args(draw, redact, tracker is not None)
+        overlay = lst = None
+        if draw is not None or redact is not None or labels is not None:
+            lst, lalive = (None, None) if labels is None else _label_overlay_struct(labels)
+            overlay = _overlay_args(draw, redact, tracker is not None, lst)
+            overlay[4].append(lalive)
             if isinstance(frames_or_images, np.ndarray) and not (frames_or_images.dtype == np.uint8 and frames_or_images.flags.c_contiguous and
                                                                  frames_or_images.flags.writeable):
                 raise ValueError("images that are drawn into must be a writable contiguous uint8 array")
@@ -2215,7 +2374,12 @@ class Net(_Completing):
                 spare = self.__dict__.setdefault("_async_redacted", {}).setdefault((n, p), [])  # pinned once, like the other outputs
                 redacted = None if rst is None else (spare.pop() if spare else out((n, p), np.int32))
                 keep = keep + (alive, redacted)
-                _check(_lib.dc_net_track_frames_async_overlay(*(args + _overlay_c_args(dst, rst, only, keep_ids) + (ptr(redacted),))))
+                if lst is None:
+                    _check(_lib.dc_net_track_frames_async_overlay(*(args + _overlay_c_args(dst, rst, only, keep_ids) + (ptr(redacted),))))
+                else:
+                    styles = _overlay_styles_struct(dst, rst, lst, only, keep_ids)
+                    keep = keep + (lst, styles)
+                    _check(_lib.dc_net_track_frames_async_styles(*(args + (C.byref(styles), ptr(redacted)))))
         return TrackedFrames(self, tracker is not None, count, people, cand, ids, place, keep + (tracker,), pool, completed, bridging, redacted)
 
     def _assemble_people(self, tracker, scale, threshold, radius, max_det, edges, mean, std, max_cost, seed_threshold, max_people, min_joints,

@@ -14,7 +14,7 @@ class VideoPipeline(object):
     MAX_DEPTH = 4  # a HIP process has four hardware queues: a fifth executor only shares one
 
     def __init__(self, net, tracker=None, depth=3, batch=1, stats=None, scale=1.0, choose_streams=True, complete=None, dedupe=None, draw=None,
-                 redact=None, in_chain=False, **assembly):
+                 redact=None, in_chain=False, labels=None, **assembly):
         """net: a `caffe.Net` with all three maps (or a sparse-pairwise net); tracker: a `caffe.Tracker` or None (people without ids,
         ids come back as None); depth: executors, 1..4; batch: frames per call, 1..64; stats: (edges, mean, std) as
         `deepcut_tools.read_pair_stats` returns them, or a path; scale: the pre-processing's and the assembly's; assembly: what
@@ -30,7 +30,10 @@ class VideoPipeline(object):
         host; True sends the styles WITH the request (`Net.track_frames_async(draw=, redact=)`): the frames are written inside the chain
         on the device, from the people where the tracker left them, and collecting a request calls nothing — the same bytes, the same
         (people, ids).  A redact dict with `select` is refused then (ValueError: a mask cannot exist before the people do; use
-        only_ids / keep_ids, which need a tracker), as is `stream` in either dict."""
+        only_ids / keep_ids, which need a tracker), as is `stream` in either dict.  labels: None (off: nothing is added), True or a
+        dict of what `pose.label_people` takes — every frame gets the ids (without a tracker the people's indices) written over the
+        redaction and the skeletons, on either route with the same bytes; with in_chain=True `texts` and `stream` in it are refused
+        (ValueError: a text for a person cannot exist before the person does)."""
         depth, batch = int(depth), int(batch)
         if not 1 <= depth <= self.MAX_DEPTH:
             raise ValueError("depth must be in [1, %d], got %d" % (self.MAX_DEPTH, depth))
@@ -59,13 +62,20 @@ class VideoPipeline(object):
             from pose.people import _redact_style
 
             self._redact = _redact_style(redact)
-        self._in_chain = bool(in_chain) and (self._draw is not None or self._redact is not None)
+        self._labels = None  # the style dict when frames are labelled
+        if labels is not None and labels is not False:
+            from pose.people import _label_style
+
+            self._labels = _label_style(labels)
+        self._in_chain = bool(in_chain) and (self._draw is not None or self._redact is not None or self._labels is not None)
         if self._in_chain:
             from pose.people import HEAD_MPII14, SKELETON_MPII14
 
-            for style in (self._draw, self._redact):
+            for style in (self._draw, self._redact, self._labels):
                 if style is not None and "stream" in style:
                     raise ValueError("in_chain=True runs on the executor's own stream: the style must not name one")
+            if self._labels is not None and self._labels.get("texts") is not None:
+                raise ValueError("in_chain=True: texts are per person, and the people do not exist before the request")
             if self._draw is not None:
                 self._draw.setdefault("edges", SKELETON_MPII14)  # what pose.draw_people / pose.redact_people fill in on the host route
             if self._redact is not None:
@@ -124,6 +134,10 @@ class VideoPipeline(object):
                 from pose.people import draw_people
 
                 draw_people(frames[i], d["people"], d.get("ids"), **dict(self._draw, cand=d.get("cand")))
+            if host_route and self._labels is not None:
+                from pose.people import label_people
+
+                label_people(frames[i], d["people"], d.get("ids"), **self._labels)
             self._done.append((tag, d["people"], d.get("ids")))
 
     def _send(self):
@@ -136,7 +150,7 @@ class VideoPipeline(object):
             k = self._free_executor()
         self._next = (k + 1) % len(self.nets)
         frames = [h[0] for h in held]
-        kept = frames if self._draw is not None or self._redact is not None else None  # the frames themselves, to be redacted / drawn into when their results are there
+        kept = frames if self._draw is not None or self._redact is not None or self._labels is not None else None  # the frames themselves, to be redacted / drawn into when their results are there
         if held[0][3][0] == "bgr":
             import numpy as np
 
@@ -158,6 +172,8 @@ class VideoPipeline(object):
             self.stream_choice = caffe.choose_streams(self.nets)
         slot_of = None if self.tracker is None else [h[2] for h in held]
         styles = dict(draw=self._draw, redact=self._redact) if self._in_chain else {}
+        if self._in_chain and self._labels is not None:
+            styles["labels"] = self._labels
         handle = self.nets[k].track_frames_async(frames, self.tracker, self.scale, slot_of=slot_of, edges=self.edges, mean=self.mean,
                                                  std=self.std, **dict(self.assembly, **styles))
         self.calls += 1

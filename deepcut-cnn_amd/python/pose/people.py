@@ -131,6 +131,28 @@ def redact_people(frame, people, ids=None, **style):
     return _caffe.redact_people(frame, _np.asarray(people, _np.float64), ids=ids, **style)
 
 
+def label_people(frame, people, ids=None, **style):
+    """Write people's ids into a frame IN PLACE on the device: `caffe.label_people`.  frame, people: as `draw_people` takes them; ids:
+    int64 [m] as `track_people` returns them, or None (the people's indices are written); an id < 0 gets no label.  style: what
+    `caffe.label_people` takes (texts, scale, gap, anchor, prefix, alpha_text, alpha_plate, min_score, color, palette, text_color,
+    plate_color, stream; the defaults, `caffe.LABEL_DEFAULTS`, are PLACEHOLDERS).  PARITY UNPINNED BY THE REFERENCE: the rule is this
+    project's own (include/deepcut_hip.h, dc_label_people)."""
+    import caffe as _caffe
+
+    _caffe.label_people(frame, _np.asarray(people, _np.float64), ids=ids, **style)
+
+
+def _label_style(labels):
+    """labels= of `track_people` / `VideoPipeline` -> None (off) or the style dict."""
+    if labels is None or labels is False:
+        return None
+    if labels is True:
+        return {}
+    if not isinstance(labels, dict):
+        raise ValueError("labels must be None, True or a dict of what label_people takes, got %r" % (labels,))
+    return dict(labels)
+
+
 def _redact_style(redact):
     """redact= of `track_people` / `VideoPipeline` -> None (off) or the style dict."""
     if redact is None or redact is False:
@@ -154,7 +176,7 @@ def _draw_style(draw):
 
 
 def track_people(frames, model_def, model_bin, stats, tracker=None, depth=1, batch=1, assign="greedy", smooth=None, draw=None, redact=None,
-                 in_chain=False, **kw):
+                 in_chain=False, labels=None, **kw):
     """`estimate_people` over the frames of a video, with identities: a generator over an iterable of images (HxWx3 BGR uint8) or
     `caffe.Frame`s that yields, per frame, (people float64 [m, J, 3], ids int64 [m]) — the same person keeps their id from frame to
     frame, -1 marks a person no track place was free for.  kw: what `estimate_people` takes (scale / scales / base / flip / joint_mirror /
@@ -179,20 +201,25 @@ def track_people(frames, model_def, model_bin, stats, tracker=None, depth=1, bat
     call `redact_people` on the yielded people where that matters.
     in_chain: False (the default) redacts and draws with the synchronous entries on the people that came back; True sends the styles with
     the request (`deepcut_tools.VideoPipeline(in_chain=True)`, whatever depth and batch are): the frames are written inside the
-    asynchronous chain on the device — the same bytes, the same (people, ids).  A redact dict with `select` raises ValueError then."""
+    asynchronous chain on the device — the same bytes, the same (people, ids).  A redact dict with `select` raises ValueError then.
+    labels: None (off: nothing is added to the run), True or a dict of what `label_people` takes — every frame gets the ids being yielded
+    written over the redaction and the skeletons; with in_chain=True a dict with `texts` or `stream` raises ValueError."""
     style = _draw_style(draw)
     rstyle = None if redact is None or redact is False else _redact_style(redact)
+    lstyle = _label_style(labels)
     args = dict(scale=1.0, net=None, scales=None, base=None, flip=False, joint_mirror=MIRROR_MPII14, sparse=False)
     for k in list(kw):
         if k in args:
             args[k] = kw.pop(k)
-    in_chain = bool(in_chain) and (style is not None or rstyle is not None)
+    in_chain = bool(in_chain) and (style is not None or rstyle is not None or lstyle is not None)
     if int(depth) != 1 or int(batch) != 1 or in_chain:
         if args["scales"] is not None or args["flip"]:
             raise ValueError("track_people: depth > 1 / batch > 1 / in_chain run one forward per frame; a pyramid (scales= / flip=True) has no "
                              "asynchronous entry: use depth=1, batch=1")
         if in_chain:
             kw = dict(kw, in_chain=True)
+        if lstyle is not None:
+            kw = dict(kw, labels=lstyle)
         for item in _track_in_flight(frames, model_def, model_bin, stats, tracker, int(depth), int(batch), args, kw, assign, smooth, style, rstyle):
             yield item
         return
@@ -207,6 +234,8 @@ def track_people(frames, model_def, model_bin, stats, tracker=None, depth=1, bat
             redact_people(image, d["people"], d["ids"], **rstyle)
         if style is not None:
             draw_people(image, d["people"], d["ids"], **dict(style, cand=d["cand"]))
+        if lstyle is not None:
+            label_people(image, d["people"], d["ids"], **lstyle)
         yield d["people"], d["ids"]
 
 

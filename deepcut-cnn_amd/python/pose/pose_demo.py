@@ -43,12 +43,15 @@ def draw_disc(image, cx, cy, radius, color):
 @click.option("--redact", type=click.Choice(["head", "body"]), default=None,
               help="pixelate the person's head or whole body in the visualisation on the device, under the overlay (pose.redact_people; "
                    "its radii are placeholders, and a mosaic is not a privacy guarantee); default: off")
+@click.option("--labels", type=click.BOOL, is_flag=True, default=False,
+              help="write the person's number over the visualisation on the device (pose.label_people): this demo has no tracker, so it "
+                   "is the person's index — pose.track_people(labels=True) writes a tracker's ids; default: off")
 @click.option("--model_def", default=None,
               help="model definition (.prototxt).  Default: the definition deepcut_tools.deepercut_prototxt(152) generates, which is "
                    "layer-for-layer the reference's models/deepercut/ResNet-152.prototxt (that directory is not part of this repository)")
 @click.option("--model_bin", default=None, required=True,
               help="trained weights (.caffemodel / .h5): the reference fetches them with models/deepercut/download_models.sh; not shipped here")
-def predict_pose_from(image_name, out_name, scales, visualize, folder_image_suffix, use_cpu, gpu, tiling, skeleton, heatmap, redact, model_def, model_bin):
+def predict_pose_from(image_name, out_name, scales, visualize, folder_image_suffix, use_cpu, gpu, tiling, skeleton, heatmap, redact, labels, model_def, model_bin):
     import caffe
     from PIL import Image
 
@@ -94,12 +97,22 @@ def predict_pose_from(image_name, out_name, scales, visualize, folder_image_suff
 
             bgr = np.ascontiguousarray(img)
             draw_people(bgr, np.ascontiguousarray(pose[:3].T)[None], edges=SKELETON_MPII14, color="joint", joint_radius=8.0, limb_radius=3.0)
+            if labels:
+                from pose.people import label_people
+
+                label_people(bgr, np.ascontiguousarray(pose[:3].T)[None])
             vis = bgr[:, :, ::-1]
             Image.fromarray(np.ascontiguousarray(vis)).save(target + "_vis.png")
         elif visualize and pose is not None:
             vis = img[:, :, ::-1].copy()
             for j in range(14):
                 draw_disc(vis, pose[0, j], pose[1, j], 8, COLORS[j])
+            if labels:
+                from pose.people import label_people
+
+                bgr = np.ascontiguousarray(vis[:, :, ::-1])
+                label_people(bgr, np.ascontiguousarray(pose[:3].T)[None])
+                vis = np.ascontiguousarray(bgr[:, :, ::-1])
             Image.fromarray(vis).save(target + "_vis.png")
         if heatmap is not None:
             from pose.estimate_pose import _get_model

@@ -1348,6 +1348,101 @@ int dc_net_track_frames_async_overlay(dc_net* net, dc_tracker* tracker /* NULL: 
                                       const long long* only_ids, int n_only /* < 0: no list */, const long long* keep_ids,
                                       int n_keep /* < 0: no list */, int* redacted /* host [n][max_people], may be NULL */);
 
+/* ---- labelling people in video frames: a person's id as text on a plate, in BGR24 or NV12 frames in place, on the device ----
+ * PARITY UNPINNED BY THE REFERENCE: its demo draws with matplotlib and labels nothing.  THE RULE below is this project's own and
+ * integer only, so every path gives the same bytes (tests/label_ref.py restates it in numpy; the device is held to that byte for byte).
+ * No anti-aliasing: it would end byte equality.  All values below are C ints unless said otherwise; / and % act on non-negative
+ * values; >> is arithmetic.
+ *
+ * Font: built in, the project's own data (csrc/label_font.h), a PLACEHOLDER like the palettes.  A glyph is 5 columns x 7 rows, one
+ *   byte per row, bit 4 the leftmost column; the advance is 6 columns.  The set is 0-9, A-Z, space and # - . : / % + _ ? — 46 glyphs.
+ *   Lower-case letters fold to upper-case; every other byte is refused, never substituted.  dc_label_font hands out a glyph's rows.
+ * Text: the key of person p of frame b is ids[b][p], or p when ids is NULL (the drawing rule's key).  The made text is `prefix` (0 to 4
+ *   characters of the set) followed by the key in decimal: at most 4 + 19 = 23 characters (DC_LABEL_MAX_CHARS is 24, the NUL
+ *   included).  A key < 0 — an untracked person — makes no text.  texts[nb][P][24] (synchronous entry only, may be NULL): a row is
+ *   NUL-padded; a non-empty row (first byte not NUL) replaces the made text of that person, whatever the key; an empty row falls back
+ *   to the made text.  A person without a text gets no label.  Rows of people p >= n_people[b] are not read.
+ * Held joints, as in drawing: x, y and score all finite and score > min_score; snapped by the drawing rule's clamp and q = rint(16 v).
+ *   A person with no held joint gets no label.
+ * Geometry, with n the number of characters (1..23) and s = scale (1..8):
+ *   tw = s (6 n - 1), th = 7 s; the plate: pw = tw + 2 s, ph = th + 2 s.
+ *   anchor_joint in [0, J) and that joint held:  X = (qx >> 4) - (pw >> 1), Yb = qy >> 4.
+ *   otherwise (anchor_joint = -1, or the joint not held): the upper left of the bounding box of the held joints,
+ *     X = lo_x >> 4, Yb = lo_y >> 4 (lo_x, lo_y: the least snapped qx, qy over the held joints).
+ *   Y = Yb - gap - ph, gap in [0, 64] pixels.
+ *   X = min(max(X, 0), max(0, W - pw)), Y = min(max(Y, 0), max(0, H - ph)): a label is pulled into the frame where it fits, and cut
+ *   at the right / bottom edge where it does not (then X = 0 / Y = 0).
+ * Layers, per label, in this order:
+ *   plate: the pixels X <= px < X + pw, Y <= py < Y + ph, blended with alpha_plate.  Not made when alpha_plate = 0.
+ *   text:  u = px - X - s, v = py - Y - s; a pixel can be covered when 0 <= u < tw and 0 <= v < th; with k = u / s, i = k / 6, c = k % 6,
+ *     r = v / s it IS covered when c < 5 and bit (4 - c) of row r of the glyph of text[i] is set.  Blended with alpha_text.  Not made
+ *     when alpha_text = 0.
+ *   With both alphas 0 no label is made at all.  Only pixels inside the frame are covered.
+ * Order: frames in order; people in index order; later labels go over earlier ones.  Labels go over everything else: where entries
+ *   combine overlays the order is redaction, then skeletons, then labels.
+ * Blend: the drawing rule's out = (c A + dst (256 - A) + 128) >> 8 per covered pixel and channel.  BGR24: three channels.  NV12: luma
+ *   per pixel; a chroma sample is blended ONCE PER LAYER with Ac = (A k + n / 2) / n for k > 0 of the block's n in-frame pixels
+ *   covered by that layer — what the drawing rule does per primitive, a layer standing for a primitive.
+ * Colour: DC_LABEL_PLATE_BY_PERSON: the plate is palette[key % n_palette], the text text_color.  DC_LABEL_TEXT_BY_PERSON: the text is
+ *   palette[key % n_palette], the plate plate_color.  key is the person's key also when a `texts` row replaces the made text; for a
+ *   key < 0 (possible only with such a row) the palette entry is palette[0].  Colours go R, G, B -> frame bytes once per label by the
+ *   drawing rule's forward conversion.
+ * Untouched bytes: bytes no made layer covers are never stored, pitch padding included.  A call that makes no label launches nothing
+ *   and writes nothing; a host frame nothing is labelled in does not travel.
+ *
+ * dc_label_people: stand-alone like dc_draw_people — no net, people as host arrays, frames in host or device memory with the same
+ *   limits on nb, height, width, P and J; one launch over the non-empty tiles; the call returns when the frames are written.
+ * Errors, before any device work: DC_EINVAL naming the field and the index for everything dc_draw_people refuses of the frames, nb,
+ *   height, width, P, J and n_people; a NULL style or palette; scale outside [1, 8], gap outside [0, 64], anchor_joint outside
+ *   [-1, J), alpha_text or alpha_plate outside [0, 256], min_score not finite or < 0, an unknown color_mode, n_palette outside
+ *   [1, 256]; a prefix without a NUL in its first 5 bytes; a byte outside the set in prefix or in a texts row, naming b, p and the byte;
+ *   a texts row without a NUL in its 24 bytes.  Then DC_ENOCPU in CPU mode.
+ * dc_label_font: rows[0 .. 7) of the glyph of byte ch (lower case folded), or DC_EINVAL for a byte outside the set.
+ *
+ * On the device routes (dc_overlay_styles.labels, below) the labels are made from the people, and the ids, in device memory, exactly
+ *   as above, and written behind the skeletons.
+ * Not built, on purpose: `texts` on the device routes (a text for a person cannot exist before the person does); anti-aliasing; fonts
+ *   of other sizes; per-box geometry.                                                                                               */
+#define DC_LABEL_MAX_CHARS 24
+#define DC_LABEL_PLATE_BY_PERSON 0
+#define DC_LABEL_TEXT_BY_PERSON  1
+typedef struct dc_label_style {
+  int scale, gap, anchor_joint;             /* 1..8; 0..64 px; -1 or [0, J) */
+  int alpha_text, alpha_plate;              /* 0..256 */
+  double min_score;                         /* finite, >= 0 */
+  int color_mode; const unsigned char* palette; int n_palette;   /* [n_palette][3] R, G, B; 1..256 */
+  unsigned char text_color[3], plate_color[3];
+  char prefix[8];                           /* NUL-terminated, at most 4 characters of the set */
+} dc_label_style;
+int dc_label_people(const dc_frame* frames, int nb, int height, int width, int is_device, int P, int J, const int* n_people,
+                    const double* people, const long long* ids /* may be NULL */, const char* texts /* [nb][P][24], may be NULL */,
+                    const dc_label_style* style, void* stream);
+int dc_label_font(int ch, unsigned char rows[7]);   /* 0, or DC_EINVAL for a byte outside the set */
+
+/* ---- one styles block for the two device entries, so that a further overlay needs no further pair of entries -----------------
+ * dc_overlay_people_device_styles / dc_net_track_frames_async_styles are dc_overlay_people_device / dc_net_track_frames_async_overlay
+ * with the styles and the id lists in one struct; the older two are wrappers over them and keep every behaviour and refusal.  `size`
+ * is sizeof(dc_overlay_styles) as the CALLER compiled it: fields beyond it read as NULL / no list, so an older caller keeps working
+ * with a newer library.  A size below that of the first field group (size, draw, redact) or above the library's struct is DC_EINVAL.
+ * labels: the label overlay (dc_label_people's rule, without `texts`), written behind the redaction and the skeletons; the key is
+ * the tracker's id (the person's index without ids).  dc_overlay_people_device_styles refuses a call with all three styles NULL (a
+ * NULL `styles` included); the chain entry then enqueues what dc_net_track_frames_async enqueues.  With `labels` NULL the two
+ * entries enqueue exactly what the older ones enqueue.                                                                              */
+typedef struct dc_overlay_styles {
+  size_t size;                              /* sizeof(dc_overlay_styles) of the caller: fields beyond it read as NULL / no list */
+  const dc_draw_style* draw; const dc_redact_style* redact; const dc_label_style* labels;   /* each may be NULL */
+  const long long* only_ids; int n_only; const long long* keep_ids; int n_keep;             /* < 0: no list */
+} dc_overlay_styles;
+int dc_overlay_people_device_styles(const dc_frame* frames, int nb, int height, int width, int is_device, int P, int J,
+                                    const int* n_people /* device */, const double* people /* device */,
+                                    const int* cand /* device, may be NULL */, const long long* ids /* device, may be NULL */,
+                                    const dc_overlay_styles* styles, int* redacted /* device [nb][P], may be NULL */, void* stream);
+int dc_net_track_frames_async_styles(dc_net* net, dc_tracker* tracker /* NULL: people without ids */, const dc_frame* frames /* or NULL */,
+                                     const unsigned char* images /* or NULL */, int n, int height, int width, double scale, int is_device,
+                                     const int* slot_of, const dc_assemble_params* p, int n_edges, const int* edges, const double* mean,
+                                     const double* stdev, const int* joint_order, int* n_people, double* people, int* cand, long long* ids,
+                                     int* place, const dc_overlay_styles* styles, int* redacted /* host [n][max_people], may be NULL */);
+
 /* ---- in-process multi-GPU forward (SURVEY 8(b)'s dc_forward_batch) -------------------------------------------------------
  * A communicator over `nexec` executors: executor k runs on devices[k] (NULL: k modulo the visible devices) on a host thread of its
  * own (mode and device are per thread, src/caffe/common.cpp:13-20).  transport: how the maps travel to the root executor's device —

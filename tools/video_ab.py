@@ -11,7 +11,9 @@ drained; (d) is ms per 8 frames.  The variants are alternated; the median of fiv
 With --overlay: `VideoPipeline` with draw + redact at depth 1, 2, 3, float32 and float16, on host NV12 frames in pinned
 memory and on device NV12 frames — the host route (in_chain=False: the synchronous redact_people / draw_people when a request is
 collected), in_chain=True (the overlays enqueued with the request) and no overlay at all (the ceiling) alternated in the same windows.
-    python tools/video_ab.py --overlay [--out profiles/video_overlay_ab.txt]"""
+    python tools/video_ab.py --overlay [--out profiles/video_overlay_ab.txt]
+With --overlay --labels: the same, with the label overlay (ids as text, LABEL_DEFAULTS) added to the skeleton and the mosaic.
+    python tools/video_ab.py --overlay --labels [--out profiles/video_overlay_labels_ab.txt]"""
 import argparse
 import os
 import statistics
@@ -37,7 +39,7 @@ def windows(runs, n_windows=5, seconds=0.5):
     return per
 
 
-def overlay(caffe, VideoPipeline, nets, host_frames, stats, akw, say, fmt):
+def overlay(caffe, VideoPipeline, nets, host_frames, stats, akw, say, fmt, labels=False):
     """The overlay routes of VideoPipeline: frames/s with no overlay, with draw + redact on the host route, and with them in the chain."""
     import torch
 
@@ -46,6 +48,8 @@ def overlay(caffe, VideoPipeline, nets, host_frames, stats, akw, say, fmt):
     device_frames = [caffe.Frame.nv12_device(y.data_ptr(), uv.data_ptr(), H, W, W, W) for y, uv in tensors]
     sources = {"host NV12 (pinned)": host_frames, "device NV12": device_frames}
     styles = dict(draw=dict(alpha=160), redact=dict(region="head_or_body", block=8))
+    if labels:
+        styles["labels"] = True
     routes = {"no overlay": dict(), "host route": dict(styles), "in_chain": dict(styles, in_chain=True)}
     people = {}
 
@@ -67,7 +71,8 @@ def overlay(caffe, VideoPipeline, nets, host_frames, stats, akw, say, fmt):
 
         return run
 
-    say("# overlays in the video path: draw (MPII skeleton, alpha 160) + redact (head_or_body, mosaic, block 8) on every frame; frames are "
+    say("# overlays in the video path: draw (MPII skeleton, alpha 160) + redact (head_or_body, mosaic, block 8)" +
+        (" + labels (ids, LABEL_DEFAULTS: scale 2)" if labels else "") + " on every frame; frames are "
         "overwritten again and again (a mosaic of a mosaic costs what a mosaic costs)")
     for dtype in ("f32", "f16"):
         for where, frames in sources.items():
@@ -89,6 +94,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
     ap.add_argument("--overlay", action="store_true", help="the overlay routes of VideoPipeline instead of (a)-(d)")
+    ap.add_argument("--labels", action="store_true", help="with --overlay: the label overlay added to the skeleton and the mosaic")
     a = ap.parse_args()
     import caffe
     from deepcut_tools import VideoPipeline, deepercut_prototxt, synth_weights, write_caffemodel
@@ -120,7 +126,7 @@ def main():
         "people per frame, frames/s by the host clock, median of 5 windows >= 0.5 s, variants alternated" % (H, W))
 
     if a.overlay:
-        overlay(caffe, VideoPipeline, nets, frames, (edges, mean, std), akw, say, fmt)
+        overlay(caffe, VideoPipeline, nets, frames, (edges, mean, std), akw, say, fmt, labels=a.labels)
         if a.out:
             with open(a.out, "w") as f:
                 f.write("\n".join(lines) + "\n")
