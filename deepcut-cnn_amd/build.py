@@ -16,9 +16,9 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "lib", "libdeepcut_hip.so")
 # (the three gather-GEMM instantiation files take the longest by far: they come first, so that they start first)
 SOURCES = ["conv_gemm_f16.hip", "conv_gemm_bf16.hip", "conv_gemm_f32.hip", "wino_f32.hip", "wino43_f32.hip", "wino_f16.hip", "stream1x1.hip", "stem_f16.hip",
-           "stream1x1_f32.hip", "people.hip", "track.hip", "sparse_head.hip", "layers.hip", "pose.hip", "image_prep.hip", "draw.hip", "heat.hip", "redact.hip", "overlay.hip", "label.hip", "conv_gemm.cpp", "forms.cpp", "formats.cpp",
+           "stream1x1_f32.hip", "people.hip", "track.hip", "sparse_head.hip", "layers.hip", "pose.hip", "image_prep.hip", "draw.hip", "heat.hip", "redact.hip", "appearance.hip", "overlay.hip", "label.hip", "conv_gemm.cpp", "forms.cpp", "formats.cpp",
            "hdf5_reader.cpp", "runtime.cpp", "net_init.cpp", "net_lower.cpp", "net_tune.cpp", "net_run.cpp", "net_image.cpp", "net_group.cpp",
-           "people.cpp", "track.cpp", "draw.cpp", "heat.cpp", "redact.cpp", "overlay.cpp", "label.cpp", "sparse_pairwise.cpp", "streams.cpp", "multi_gpu.cpp", "c_api.cpp"]
+           "people.cpp", "track.cpp", "draw.cpp", "heat.cpp", "redact.cpp", "appearance.cpp", "overlay.cpp", "label.cpp", "sparse_pairwise.cpp", "streams.cpp", "multi_gpu.cpp", "c_api.cpp"]
 HEADERS = ["formats.h", "net.h", "net_internal.h", "kernels.h", "kernel_prims.h", "conv_gemm.h", "conv_gemm_variants.h", "by_kind.h", "frame_tile.h", "tile_bins.h", "label_font.h", "label_tile.h",
            os.path.join("..", "..", "include", "deepcut_hip.h")]
 MAX_JOBS = 16  # compiler processes at a time

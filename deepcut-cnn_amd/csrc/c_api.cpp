@@ -996,6 +996,32 @@ int dc_tracker_smooth_state(dc_tracker* tracker, int slot, double* poses, int* g
   REQUIRE(tracker);
   return guard([&] { TR(tracker)->smooth_state(slot, poses, gap); });
 }
+// the tracker's appearance steps (track.cpp)
+int dc_tracker_set_appearance(dc_tracker* tracker, const dc_track_appearance_params* p) {
+  REQUIRE(tracker);
+  return guard([&] { TR(tracker)->set_appearance(p); });
+}
+int dc_tracker_get_appearance(dc_tracker* tracker, dc_track_appearance_params* out) {
+  REQUIRE(tracker);
+  REQUIRE(out);
+  return guard([&] {
+    const Tracker::AppearParams& q = TR(tracker)->appear;
+    *out = dc_track_appearance_params{q.enabled, q.min_pixels, q.alpha256, q.reid_max, q.max_age, q.min_hits};
+  });
+}
+int dc_tracker_update_appearance(dc_tracker* tracker, int nb, int P, const int* slot_of, const int* n_people, const double* people,
+                                 const int* desc, long long* ids, int* place, double* dist, int* reid, double* smooth, int* src) {
+  REQUIRE(tracker);
+  REQUIRE(n_people);
+  REQUIRE(people);
+  REQUIRE(ids);
+  return guard([&] { TR(tracker)->update(nb, P, slot_of, n_people, people, ids, place, dist, smooth, src, false, true, desc, reid); });
+}
+int dc_tracker_appearance_state(dc_tracker* tracker, int slot, int* track_model, int* track_valid, long long* gallery_ids, int* gallery_age,
+                                int* gallery_model) {
+  REQUIRE(tracker);
+  return guard([&] { TR(tracker)->appearance_state(slot, track_model, track_valid, gallery_ids, gallery_age, gallery_model); });
+}
 int dc_net_track_people(dc_net* net, dc_tracker* tracker, const dc_assemble_params* p, int n_edges, const int* edges, const double* mean,
                         const double* stdev, const int* joint_order, int* n_people, double* people, int* cand, double* cost,
                         long long* ids, int* place) {
@@ -1144,6 +1170,15 @@ int dc_redact_people(const dc_frame* frames, int nb, int height, int width, int 
   REQUIRE(n_people);
   REQUIRE(people);
   return guard([&] { redact_people(frames, nb, height, width, is_device != 0, P, J, n_people, people, select, style, redacted, stream); });
+}
+// the appearance descriptor (appearance.cpp); a null style is refused there, after the frames' own checks, naming the field
+int dc_describe_people(const dc_frame* frames, int nb, int height, int width, int is_device, int P, int J, const int* n_people,
+                       const double* people, const dc_appearance_style* style, int* desc, void* stream) {
+  REQUIRE(frames);
+  REQUIRE(n_people);
+  REQUIRE(people);
+  REQUIRE(desc);
+  return guard([&] { describe_people(frames, nb, height, width, is_device != 0, P, J, n_people, people, style, desc, stream); });
 }
 // the overlays from people in device memory (overlay.cpp, people.cpp); a call without a style is refused there, naming the field
 // dc_overlay_styles as the caller compiled it -> OverlayArgs: fields beyond the caller's `size` read as NULL / no list

@@ -467,6 +467,16 @@ constexpr int kRedactMosaic = 0, kRedactFill = 1;  // DC_REDACT_MOSAIC, DC_REDAC
 int launch_redact(int format, int effect, int block, unsigned fill, const DrawPlanes* frames, int height, int width, const DrawTile* tiles,
                   int n_tiles, const int* index, const DrawPrim* prims, void* stream);
 
+// Appearance descriptors (appearance.hip; the rule: include/deepcut_hip.h, dc_describe_people — this project's own).  The host
+// (appearance.cpp) makes the capsules of every person's sampled limbs with the redaction's body radius, the person's index in
+// DrawPrim::colour, and bins them in person order into the drawing kernel's tiles; one workgroup reads one non-empty tile, one thread one
+// 2 x 2 pixel block, and counts per person the bytes of the covered pixels into desc [nb][P][3][16] (c, v >> 4): an LDS histogram per
+// person, then one integer atomicAdd per non-zero bin.  desc is zeroed by the caller on the same stream; no frame byte is stored.
+constexpr int kAppearBins = 16, kAppearDesc = 3 * kAppearBins;  // DC_APPEARANCE_BINS; ints per person
+// format: DC_PIX_BGR24 or DC_PIX_NV12.  Grid = n_tiles (> 0).  Every pointer is device memory.
+int launch_describe(int format, const DrawPlanes* frames, int height, int width, const DrawTile* tiles, int n_tiles, const int* index,
+                    const DrawPrim* prims, int P, int* desc, void* stream);
+
 // Overlays from people in device memory (overlay.hip; the rules are dc_draw_people's and dc_redact_people's, the bytes theirs).  A builder
 // kernel — one workgroup per frame, one thread per person — makes the DrawPrims draw.cpp / redact.cpp make on the host, in their order,
 // dropping what TileBins::add drops; self-binning forms of the two tile kernels then run over EVERY tile of every frame, each workgroup
@@ -622,9 +632,43 @@ struct TrackSmooth {
   const int* cand_in;
   int* cand_out;
 };
+// ap (null: off, the instances and the work of a tracker without appearance): steps 0', 5', 6' and 7' of the rule (include/deepcut_hip.h,
+// dc_tracker_update_appearance), all integer.  A slot's appearance state is one block of track_appear_bytes(T) bytes at
+// state + s * slot_stride, all zero = no valid model and an empty gallery:
+//   long long gid[64] | int gage[64] | int gocc[64] | int gmodel[64][48] | int valid[T] | int model[T][48]
+// desc [NB][P][3][16] (device; null: nobody has a valid descriptor) is only read; qdesc [NB][P][48] is scratch for the quantised
+// descriptors; reid [NB][P] is written whole (1: the person took an id from the gallery).
+constexpr int kTrackGallery = 64, kTrackModel = 48;  // DC_TRACK_GALLERY; 3 x DC_APPEARANCE_BINS
+struct TrackAppearSlot {  // the arrays of one slot inside its block
+  long long* gid;
+  int* gage;
+  int* gocc;
+  int* gmodel;
+  int* valid;
+  int* model;
+};
+inline size_t track_appear_bytes(int T) { return (size_t)kTrackGallery * (8 + 4 + 4 + kTrackModel * 4) + (size_t)T * (4 + kTrackModel * 4); }
+DC_HOST_DEVICE inline TrackAppearSlot track_appear_slot(unsigned char* block, int T) {
+  TrackAppearSlot s;
+  s.gid = (long long*)block;
+  s.gage = (int*)(s.gid + kTrackGallery);
+  s.gocc = s.gage + kTrackGallery;
+  s.gmodel = s.gocc + kTrackGallery;
+  s.valid = s.gmodel + kTrackGallery * kTrackModel;
+  s.model = s.valid + T;
+  return s;
+}
+struct TrackAppear {
+  int min_pixels, alpha256, reid_max, max_age, min_hits;
+  unsigned char* state;
+  size_t slot_stride;  // a multiple of 8
+  const int* desc;
+  int* qdesc;
+  int* reid;
+};
 int launch_track(int S, int NB, int P, const TrackParams& p, const double* sig2, unsigned char* state, size_t slot_stride, double* dist,
                  const int* n_people, const double* people, long long* ids, int* place, const TrackSlotMap& map, void* stream,
-                 const TrackSmooth* sm = nullptr);
+                 const TrackSmooth* sm = nullptr, const TrackAppear* ap = nullptr);
 
 // The pairwise head at a list of cells (sparse_head.hip; the rule: include/deepcut_hip.h, dc_net_pairwise_at).  x3 / x5: the NHWC inputs
 // of the head's 1x1 skip convolution ([NB][H][W], pitch cp3, K3 channels) and of its stride-2 3x3 deconvolution ([NB][h5][w5], pitch cp5,

@@ -29,6 +29,8 @@ struct dc_dedupe_params;    // include/deepcut_hip.h: stage E of the people asse
 struct dc_draw_style;       // include/deepcut_hip.h: the skeleton overlay
 struct dc_label_style;      // include/deepcut_hip.h: the label overlay
 struct dc_redact_style;     // include/deepcut_hip.h: the redaction
+struct dc_appearance_style; // include/deepcut_hip.h: the appearance descriptor
+struct dc_track_appearance_params;  // include/deepcut_hip.h: the tracker's appearance steps
 struct dc_heat_geometry;    // include/deepcut_hip.h: the score-map overlay
 struct dc_heat_style;
 struct dc_track_smooth_params;  // include/deepcut_hip.h: step 8 of the tracker's rule
@@ -328,6 +330,10 @@ void overlay_people_device(const dc_frame* frames, int nb, int h, int w, bool is
 // dc_redact_people (redact.cpp): regions derived from people's joints replaced by a mosaic or a colour, in place on the device, synchronous
 void redact_people(const dc_frame* frames, int nb, int h, int w, bool is_device, int P, int J, const int* n_people, const double* people,
                    const unsigned char* select, const dc_redact_style* style, int* redacted, void* stream);
+// dc_describe_people (appearance.cpp): per person, 3 x 16-bin histograms of the frame bytes under the capsules of `style->edges`, counted
+// on the device; frames are only read.  desc: host [nb][P][3][16], all of it written.  Synchronous
+void describe_people(const dc_frame* frames, int nb, int h, int w, bool is_device, int P, int J, const int* n_people, const double* people,
+                     const dc_appearance_style* style, int* desc, void* stream);
 // dc_draw_heatmap (heat.cpp): a float32 NCHW score map, host or device, blended into frames in place on the device, synchronous
 void draw_heatmap(const dc_frame* frames, int nb, int h, int w, bool is_device, const float* map, bool map_is_device, int C, int Hm, int Wm,
                   const dc_heat_geometry* geometry, const dc_heat_style* style, void* stream);
@@ -631,6 +637,17 @@ struct Tracker {
     const int* d_cand = nullptr;
     int* cand = nullptr;
   };
+  // the appearance steps (dc_tracker_set_appearance).  The models and galleries [slots] (kernels.h TrackAppearSlot) are an allocation of
+  // their own, made at the first update with appearance on and zeroed there and at the first update after it went from off to on
+  // (app_clear).  The scratch then also holds desc and qdesc [cap][256][48] and reid [cap][256] (img_appear); reid is downloaded in front
+  // of the event like step 8's outputs.
+  struct AppearParams {
+    int enabled = 0, min_pixels = 0, alpha256 = 0, reid_max = 0, max_age = 0, min_hits = 0;
+  } appear;
+  unsigned char* app_dev = nullptr;
+  size_t app_stride = 0;
+  bool app_clear = false, img_appear = false;
+  size_t off_desc = 0, off_qdesc = 0, off_reid = 0;
   // every argument error is DC_EINVAL naming the parameter; no device is needed
   static Tracker* create(int slots, int max_tracks, int n_joints, const double* sigma, int max_misses, int min_common, double max_dist,
                          double min_size, int motion);
@@ -653,10 +670,18 @@ struct Tracker {
   // scratch — the people (step 8's with smoothing on, else d_ppl), cand (step 8's cand_out with smoothing on, null when it made none;
   // else `d_cand`) and the ids.  Whatever it enqueues on `stream` reads the scratch before the next update may overwrite it.
   using BeforeDone = std::function<void(const double* d_people, const int* d_cand, const long long* d_ids)>;
+  // With appearance on its steps run in the same launch: d_desc (device [nb][P][48], null: nobody has a valid descriptor) and where
+  // reid goes (host, may be null).
   void enqueue(int nb, int P, const int* slot_of, const int* d_np, const double* d_ppl, long long* ids, int* place, double* dist, void* stream,
-               const SmoothOut* so = nullptr, const BeforeDone* before_done = nullptr, const int* d_cand = nullptr);
+               const SmoothOut* so = nullptr, const BeforeDone* before_done = nullptr, const int* d_cand = nullptr, const int* d_desc = nullptr,
+               int* reid = nullptr);
+  // with_appearance: dc_tracker_update_appearance (DC_EINVAL when appearance is off); desc: host [nb][P][48] or null
   void update(int nb, int P, const int* slot_of, const int* n_people, const double* people, long long* ids, int* place, double* dist,
-              double* smooth_out = nullptr, int* src = nullptr, bool smoothed = false);
+              double* smooth_out = nullptr, int* src = nullptr, bool smoothed = false, bool with_appearance = false, const int* desc = nullptr,
+              int* reid = nullptr);
+  // host only, ordered like set_smoothing; null: off.  Off -> on starts with empty models and gallery, a change while on keeps them
+  void set_appearance(const dc_track_appearance_params* p);
+  void appearance_state(int slot, int* track_model, int* track_valid, long long* gallery_ids, int* gallery_age, int* gallery_model);
   // host only, ordered like set_option; null: off.  Off -> on starts with empty filters, a change while on keeps them
   void set_smoothing(const dc_track_smooth_params* p);
   void smooth_state(int slot, double* poses, int* gap);

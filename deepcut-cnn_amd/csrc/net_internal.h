@@ -131,6 +131,37 @@ DC_INTERNAL inline void held_joints(const double* pose, int J, double min_score,
     if (held[j]) qx[j] = snap16(x), qy[j] = snap16(y);
   }
 }
+// ---- the body primitives of the redaction rule, shared by dc_redact_people (redact.cpp) and dc_describe_people (appearance.cpp) ---------
+constexpr int kBodyRadiusCap = 1024;  // 1/16 pixel: the drawing rule's largest capsule radius
+// min(max(v, lo), hi) in double, then the conversion: hi wins where lo > hi
+DC_INTERNAL inline int clamp_int(double v, double lo, double hi) { return (int)std::min(std::max(v, lo), hi); }
+// s16: the larger side of the bounding box of the held joints in snapped units (0 for one joint or none)
+DC_INTERNAL inline int held_extent(int J, const int* qx, const int* qy, const bool* held) {
+  int lo_x = 0, hi_x = 0, lo_y = 0, hi_y = 0, n_held = 0;
+  for (int j = 0; j < J; ++j) {
+    if (!held[j]) continue;
+    lo_x = n_held ? std::min(lo_x, qx[j]) : qx[j], hi_x = n_held ? std::max(hi_x, qx[j]) : qx[j];
+    lo_y = n_held ? std::min(lo_y, qy[j]) : qy[j], hi_y = n_held ? std::max(hi_y, qy[j]) : qy[j];
+    ++n_held;
+  }
+  return std::max(hi_x - lo_x, hi_y - lo_y);
+}
+// the body radius clamp(rint(scale * s16), r_lo, 1024), r_lo = rint(16 min_radius): one double multiply, one rint
+DC_INTERNAL inline int body_radius16(double scale, int s16, double r_lo) {
+  const double scaled = scale * (double)s16;
+  return clamp_int(std::rint(scaled), r_lo, (double)kBodyRadiusCap);
+}
+// every limb of `edges` whose two joints are held, as a capsule of radius r16 carrying `colour`, handed to add(DrawPrim) -> whether the
+// primitive was made; -> whether any was
+template <class Add>
+inline bool body_capsules(int n_edges, const int* edges, const int* qx, const int* qy, const bool* held, int r16, unsigned colour, Add&& add) {
+  bool made = false;
+  for (int e = 0; e < n_edges; ++e) {
+    const int ea = edges[2 * e], ec = edges[2 * e + 1];
+    if (held[ea] && held[ec]) made |= add(DrawPrim{qx[ea], qy[ea], qx[ec], qy[ec], r16, 1, 0, colour});
+  }
+  return made;
+}
 inline int clip8(long v) { return v < 0 ? 0 : (v > 255 ? 255 : (int)v); }
 // the forward colour rule: the counterpart of frame_csc's inverse (net_image.cpp), coefficients in double, rounded to nearest
 struct ForwardCsc {

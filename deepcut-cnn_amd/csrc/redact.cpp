@@ -11,11 +11,6 @@ namespace dc {
 
 namespace {
 constexpr double kRedactMaxRadius = 1024.0;  // pixels: the head disc
-constexpr int kRedactBodyCap = 1024;         // 1/16 pixel: the drawing rule's largest capsule radius
-
-// min(max(v, lo), hi) in double, then the conversion: hi wins where lo > hi
-int clamp_int(double v, double lo, double hi) { return (int)std::min(std::max(v, lo), hi); }
-
 }  // namespace
 
 void check_redact_style(const char* who, const dc_redact_style* st, int J) {
@@ -65,14 +60,7 @@ void redact_people(const dc_frame* frames, int nb, int h, int w, bool is_device,
       const double* pose = people + ((size_t)b * P + p) * J * 3;
       int qx[kPeopleMaxJoints], qy[kPeopleMaxJoints];
       bool held[kPeopleMaxJoints];
-      int lo_x = 0, hi_x = 0, lo_y = 0, hi_y = 0, n_held = 0;
       held_joints(pose, J, st->min_score, qx, qy, held);
-      for (int j = 0; j < J; ++j) {
-        if (!held[j]) continue;
-        lo_x = n_held ? std::min(lo_x, qx[j]) : qx[j], hi_x = n_held ? std::max(hi_x, qx[j]) : qx[j];
-        lo_y = n_held ? std::min(lo_y, qy[j]) : qy[j], hi_y = n_held ? std::max(hi_y, qy[j]) : qy[j];
-        ++n_held;
-      }
       bool made = false;
       const int a = st->head_a, c = st->head_b;
       const bool head = held[a] && held[c];
@@ -85,13 +73,8 @@ void redact_people(const dc_frame* frames, int nb, int h, int w, bool is_device,
         made |= add(DrawPrim{mx, my, mx, my, r16, 0, 0, 0u});
       }
       if (st->region == DC_REDACT_BODY || (st->region == DC_REDACT_HEAD_OR_BODY && !head)) {
-        const int s16 = std::max(hi_x - lo_x, hi_y - lo_y);
-        const double scaled = st->body_scale * (double)s16;
-        const int rb16 = clamp_int(std::rint(scaled), r_lo, (double)kRedactBodyCap);
-        for (int e = 0; e < st->n_edges; ++e) {
-          const int ea = st->edges[2 * e], ec = st->edges[2 * e + 1];
-          if (held[ea] && held[ec]) made |= add(DrawPrim{qx[ea], qy[ea], qx[ec], qy[ec], rb16, 1, 0, 0u});
-        }
+        const int rb16 = body_radius16(st->body_scale, held_extent(J, qx, qy, held), r_lo);
+        made |= body_capsules(st->n_edges, st->edges, qx, qy, held, rb16, 0u, add);
         for (int j = 0; j < J; ++j)
           if (held[j]) made |= add(DrawPrim{qx[j], qy[j], qx[j], qy[j], rb16, 0, 0, 0u});
       }

@@ -58,6 +58,7 @@ Tracker::~Tracker() {
   }
   dev_free(img_dev);
   dev_free(filt_dev);
+  dev_free(app_dev);
   dev_free(dev);
 }
 
@@ -100,7 +101,15 @@ void Tracker::prepare(int on_device, int nb, void* stream) {
     dev_zero(filt_dev, bytes, stream);  // set_smoothing waited for the updates before; the launch follows on this stream
     filt_clear = false;
   }
-  if (nb > img_cap || (on && !img_smooth)) {
+  const bool app = appear.enabled != 0;
+  if (app && (!app_dev || app_clear)) {  // likewise: empty models and galleries
+    app_stride = up256(track_appear_bytes(tp.T));
+    const size_t bytes = (size_t)slots * app_stride;
+    if (!app_dev) dev_alloc((void**)&app_dev, bytes);
+    dev_zero(app_dev, bytes, stream);
+    app_clear = false;
+  }
+  if (nb > img_cap || (on && !img_smooth) || (app && !img_appear)) {
     wait_done();  // nobody reads the old scratch any more
     const size_t N = (size_t)std::max(std::max(nb, img_cap), slots), T = (size_t)tp.T, J = (size_t)tp.J, PM = (size_t)kPeopleMaxPeople;
     size_t at = 0;
@@ -114,17 +123,21 @@ void Tracker::prepare(int on_device, int nb, void* stream) {
     const bool with = on || img_smooth;
     const size_t o_smooth = with ? take(N * PM * J * 3 * sizeof(double)) : 0, o_src = with ? take(N * PM * J * sizeof(int)) : 0,
                  o_cand = with ? take(N * PM * J * sizeof(int)) : 0;
+    const bool with_app = app || img_appear;
+    const size_t o_desc = with_app ? take(N * PM * kTrackModel * sizeof(int)) : 0, o_qdesc = with_app ? take(N * PM * kTrackModel * sizeof(int)) : 0,
+                 o_reid = with_app ? take(N * PM * sizeof(int)) : 0;
     unsigned char* grown = nullptr;
     dev_alloc((void**)&grown, at);
     dev_free(img_dev);
     img_dev = grown, img_cap = (int)N;
     off_dist = o_dist, off_np = o_np, off_ppl = o_ppl, off_ids = o_ids, off_place = o_place;
     off_smooth = o_smooth, off_src = o_src, off_cand = o_cand, img_smooth = with;
+    off_desc = o_desc, off_qdesc = o_qdesc, off_reid = o_reid, img_appear = with_app;
   }
 }
 
 void Tracker::enqueue(int nb, int P, const int* slot_of, const int* d_np, const double* d_ppl, long long* ids, int* place, double* dist,
-                      void* stream, const SmoothOut* so, const BeforeDone* before_done, const int* d_cand) {
+                      void* stream, const SmoothOut* so, const BeforeDone* before_done, const int* d_cand, const int* d_desc, int* reid) {
   hipStream_t s = (hipStream_t)stream;
   long long* d_ids = (long long*)(img_dev + off_ids);
   int* d_place = (int*)(img_dev + off_place);
@@ -140,8 +153,16 @@ void Tracker::enqueue(int nb, int P, const int* slot_of, const int* d_np, const 
     sm.smooth = (double*)(img_dev + off_smooth), sm.src = (int*)(img_dev + off_src);
     if (so && so->d_cand) sm.cand_in = so->d_cand, sm.cand_out = (int*)(img_dev + off_cand);
   }
+  TrackAppear ap{};
+  const bool app = appear.enabled != 0;
+  if (app) {
+    ap.min_pixels = appear.min_pixels, ap.alpha256 = appear.alpha256, ap.reid_max = appear.reid_max, ap.max_age = appear.max_age;
+    ap.min_hits = appear.min_hits, ap.state = app_dev, ap.slot_stride = app_stride;
+    ap.desc = d_desc, ap.qdesc = (int*)(img_dev + off_qdesc), ap.reid = (int*)(img_dev + off_reid);
+  }
   KCHECK(launch_track(slots, nb, P, tp, (const double*)(dev + off_sig), dev, slot_stride, d_dist, d_np, d_ppl, d_ids, d_place, map, stream,
-                      on ? &sm : nullptr));
+                      on ? &sm : nullptr, app ? &ap : nullptr));
+  if (app && reid) HIPCHECK(hipMemcpyAsync(reid, ap.reid, (size_t)nb * P * sizeof(int), hipMemcpyDeviceToHost, s));
   if (on && so) {  // out of the shared scratch, in front of the event: the next update's launch waits for it
     const size_t e = (size_t)nb * P * tp.J;
     if (so->people) HIPCHECK(hipMemcpyAsync(so->people, sm.smooth, e * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -170,8 +191,12 @@ bool Tracker::enqueue_chained(int nb, int P, const int* slot_of, const int* d_np
 }
 
 void Tracker::update(int nb, int P, const int* slot_of, const int* n_people, const double* people, long long* ids, int* place, double* dist,
-                     double* smooth_out, int* src, bool smoothed) {
+                     double* smooth_out, int* src, bool smoothed, bool with_appearance, const int* desc, int* reid) {
   check_call("tracker_update", nb, P, tp.J, slot_of);
+  if (with_appearance && !appear.enabled)
+    bad("tracker_update_appearance", "appearance is off (dc_tracker_set_appearance): there is nothing to re-identify with");
+  if (with_appearance && (smooth_out || src) && !smooth.enabled)
+    bad("tracker_update_appearance", "smoothing is off (dc_tracker_set_smoothing): smooth and src must be NULL");
   if (smoothed && !smooth.enabled)
     bad("tracker_update_smoothed", "smoothing is off (dc_tracker_set_smoothing): there are no smoothed poses to return");
   for (int b = 0; b < nb; ++b)
@@ -194,9 +219,14 @@ void Tracker::update(int nb, int P, const int* slot_of, const int* n_people, con
     if (n_people[b] > 0)
       HIPCHECK(hipMemcpyAsync(d_ppl + (size_t)b * img, people + (size_t)b * img, (size_t)n_people[b] * tp.J * 3 * sizeof(double),
                               hipMemcpyHostToDevice, s));
+  int* d_desc = nullptr;
+  if (appear.enabled && desc) {  // whole: the kernel reads the people that exist only
+    d_desc = (int*)(img_dev + off_desc);
+    HIPCHECK(hipMemcpyAsync(d_desc, desc, (size_t)nb * P * kTrackModel * sizeof(int), hipMemcpyHostToDevice, s));
+  }
   SmoothOut so;
   so.people = smooth_out, so.src = src;
-  enqueue(nb, P, slot_of, d_np, d_ppl, ids, place, dist, s, &so);
+  enqueue(nb, P, slot_of, d_np, d_ppl, ids, place, dist, s, &so, nullptr, nullptr, d_desc, reid);
   HIPCHECK(hipStreamSynchronize(s));
 }
 
@@ -214,7 +244,61 @@ void Tracker::reset(int slot) {
     if (slot < 0) HIPCHECK(hipMemsetAsync(filt_dev, 0, (size_t)slots * per, s));
     else HIPCHECK(hipMemsetAsync(filt_dev + (size_t)slot * per, 0, per, s));
   }
+  if (app_dev) {  // ... and its models and gallery
+    if (slot < 0) HIPCHECK(hipMemsetAsync(app_dev, 0, (size_t)slots * app_stride, s));
+    else HIPCHECK(hipMemsetAsync(app_dev + (size_t)slot * app_stride, 0, app_stride, s));
+  }
   HIPCHECK(hipStreamSynchronize(s));
+}
+
+void Tracker::set_appearance(const dc_track_appearance_params* p) {
+  const std::string who = "tracker_set_appearance";
+  AppearParams q;
+  if (p && p->enabled) {
+    if (p->enabled != 1) bad(who, "enabled must be 0 or 1");
+    if (p->min_pixels < 1) bad(who, "min_pixels must be >= 1");
+    if (p->alpha256 < 0 || p->alpha256 > 256) bad(who, "alpha256 must be in [0, 256]");
+    if (p->reid_max < 0 || p->reid_max > 3 * 4096) bad(who, "reid_max must be in [0, 12288]");
+    if (p->max_age < 0 || p->max_age > 100000) bad(who, "max_age must be in [0, 100000]");
+    if (p->min_hits < 1) bad(who, "min_hits must be >= 1");
+    q.enabled = 1, q.min_pixels = p->min_pixels, q.alpha256 = p->alpha256, q.reid_max = p->reid_max, q.max_age = p->max_age;
+    q.min_hits = p->min_hits;
+  }
+  RuntimeLock rl;  // no update is being enqueued meanwhile
+  if (dev) {
+    DeviceScope on(device);
+    wait_done();
+  }
+  if (q.enabled && !appear.enabled) app_clear = true;  // off -> on: the next update starts with empty models and galleries
+  appear = q;
+}
+
+void Tracker::appearance_state(int slot, int* track_model, int* track_valid, long long* gallery_ids, int* gallery_age, int* gallery_model) {
+  if (slot < 0 || slot >= slots) bad("tracker_appearance_state", "slot must be in [0, " + std::to_string(slots) + ")");
+  const int T = tp.T;
+  std::vector<unsigned char> block(track_appear_bytes(T), 0), tracks(track_slot_bytes(T, tp.J), 0);  // all zero: nothing valid, empty gallery
+  if (dev && app_dev && appear.enabled && !app_clear) {
+    RuntimeLock rl;
+    DeviceScope on(device);
+    wait_done();
+    hipStream_t s = util_stream();
+    HIPCHECK(hipMemcpyAsync(block.data(), app_dev + (size_t)slot * app_stride, block.size(), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipMemcpyAsync(tracks.data(), dev + (size_t)slot * slot_stride, tracks.size(), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+  }
+  const TrackAppearSlot as = track_appear_slot(block.data(), T);
+  const TrackSlot st = track_slot(tracks.data(), T, tp.J);
+  for (int i = 0; i < T; ++i) {  // a free place keeps stale values on the device: it reports none
+    const bool has = st.live[i] != 0 && as.valid[i] != 0;
+    if (track_valid) track_valid[i] = has ? 1 : 0;
+    for (int k = 0; track_model && k < kTrackModel; ++k) track_model[(size_t)i * kTrackModel + k] = has ? as.model[(size_t)i * kTrackModel + k] : 0;
+  }
+  for (int g = 0; g < kTrackGallery; ++g) {
+    const bool occ = as.gocc[g] != 0;
+    if (gallery_ids) gallery_ids[g] = occ ? as.gid[g] : -1;
+    if (gallery_age) gallery_age[g] = occ ? as.gage[g] : -1;
+    for (int k = 0; gallery_model && k < kTrackModel; ++k) gallery_model[(size_t)g * kTrackModel + k] = occ ? as.gmodel[(size_t)g * kTrackModel + k] : 0;
+  }
 }
 
 void Tracker::set_smoothing(const dc_track_smooth_params* p) {

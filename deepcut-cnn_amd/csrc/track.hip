@@ -243,6 +243,187 @@ __device__ __forceinline__ void smooth_image(int b, int P, int n, const TrackPar
   }
 }
 
+// ---- the appearance steps 0', 5', 6', 7' (include/deepcut_hip.h, dc_tracker_update_appearance): all integer, so nothing here depends on
+// an order of evaluation.  Their LDS lives in one struct behind a function, so that only the instances with Appear hold it.
+static_assert(kTrackModel == kAppearDesc, "a model is a quantised descriptor");
+struct AppearLds {
+  int pvalid[kTrackMax];  // per person: the descriptor is valid (its quantised form is in qdesc)
+  int flag[kTrackMax];
+  int cand[kTrackMax];    // step 6': the places that enter the gallery, ascending
+  int gocc[kTrackGallery];  // the gallery's occupancy as the steps leave it
+  int gsrc[kTrackGallery];  // step 6': the place whose model entry g takes, -1 = none
+  unsigned key;
+  int ncand;
+};
+__device__ __forceinline__ AppearLds& appear_lds() {
+  __shared__ AppearLds lds;
+  return lds;
+}
+// A(m, q) = 12288 - sum min(m, q)
+__device__ __forceinline__ int appear_dissim(const int* m, const int* q) {
+  int s = 0;
+  for (int e = 0; e < kTrackModel; ++e) s += min(m[e], q[e]);
+  return 3 * 4096 - s;
+}
+// m + (((q - m) * alpha256 + 128) >> 8), the shift arithmetic; |q - m| <= 4104, so the product stays below 2^21
+__device__ __forceinline__ int appear_blend(int m, int q, int alpha256) { return m + (((q - m) * alpha256 + 128) >> 8); }
+
+// Step 0' and the quantised descriptors of image b, by the whole workgroup in front of step 1 (whose barrier follows): thread e < 64 ages
+// gallery entry e and frees it beyond max_age; thread q < n quantises person q's descriptor into qdesc when it is valid.
+__device__ __forceinline__ void appear_begin(int b, int P, int n, const TrackAppear& ap, const TrackAppearSlot& as) {
+  AppearLds& L = appear_lds();
+  const int t = threadIdx.x;
+  if (t < kTrackGallery && as.gocc[t]) {
+    const int age = as.gage[t] + 1;
+    as.gage[t] = age;
+    if (age > ap.max_age) as.gocc[t] = 0;
+  }
+  int ok = 0;
+  if (t < n && ap.desc) {
+    const int* h = ap.desc + ((size_t)b * P + t) * kTrackModel;
+    int* q = ap.qdesc + ((size_t)b * P + t) * kTrackModel;
+    long long cnt = 0;
+    for (int k = 0; k < kAppearBins; ++k) cnt += h[k];
+    if (cnt >= ap.min_pixels && cnt > 0) {
+      ok = 1;
+      for (int e = 0; e < kTrackModel; ++e) q[e] = (int)((4096LL * h[e] + cnt / 2) / cnt);
+    }
+  }
+  L.pvalid[t] = ok;
+}
+
+// Steps 5' and 6' behind steps 5 and 6 (and a barrier), in front of step 7, by the whole workgroup; live / tm / mult as of the start of the
+// update.  5': thread i of a matched track whose person has a valid descriptor updates the track's model.  6': the places freed in this
+// update with hits >= min_hits and a valid model are listed in ascending order; wave 0 — lane e holds gallery entry e — takes them one by
+// one: the lowest free entry (a ballot), else the entry of largest age, the lower index among equals (a wave maximum of age << 6 |
+// 63 - e); then the models of the entries that changed hands are copied.  A freed track's id, hits and model are still in place: step 7
+// has not run.  The barrier at the end stands between the copies and step 7' 's stores to the models of reborn places.
+__device__ __forceinline__ void appear_tracks(int b, int P, const TrackParams& tp, const TrackAppear& ap, const TrackAppearSlot& as,
+                                              const TrackSlot& st, const int* live, const int* tm, const int* mult) {
+  AppearLds& L = appear_lds();
+  const int t = threadIdx.x, T = tp.T;
+  int enters = 0;
+  if (t < T && live[t]) {
+    if (tm[t] >= 0) {
+      if (L.pvalid[tm[t]]) {
+        const int* q = ap.qdesc + ((size_t)b * P + tm[t]) * kTrackModel;
+        int* m = as.model + (size_t)t * kTrackModel;
+        const int had = as.valid[t];
+        for (int e = 0; e < kTrackModel; ++e) m[e] = had ? appear_blend(m[e], q[e], ap.alpha256) : q[e];
+        as.valid[t] = 1;
+      }
+    } else if (mult[t] > tp.max_misses) {
+      enters = (st.hits[t] >= ap.min_hits && as.valid[t]) ? 1 : 0;
+    }
+  }
+  L.flag[t] = enters;
+  if (t < kTrackGallery) L.gocc[t] = as.gocc[t], L.gsrc[t] = -1;  // as.gocc[t]: this thread's own store of step 0'
+  __syncthreads();
+  if (enters) {
+    int rank = 0;
+    for (int i = 0; i < t; ++i) rank += L.flag[i];
+    L.cand[rank] = t;
+  }
+  if (t == 0) {
+    int total = 0;
+    for (int i = 0; i < T; ++i) total += L.flag[i];
+    L.ncand = total;
+  }
+  __syncthreads();
+  if (t < kTrackGallery) {  // wave 0, all of it
+    int occ = L.gocc[t], age = occ ? as.gage[t] : 0, src = -1;
+    const int k = L.ncand;
+    for (int c = 0; c < k; ++c) {  // k is the same in every lane
+      const unsigned long long free_mask = __ballot(!occ);
+      int target;
+      if (free_mask) {
+        target = __ffsll((long long)free_mask) - 1;
+      } else {
+        int key = (age << 6) | (kTrackGallery - 1 - t);  // age <= 100000 < 2^17
+        for (int sft = 32; sft > 0; sft >>= 1) key = max(key, __shfl_xor(key, sft));
+        target = kTrackGallery - 1 - (key & (kTrackGallery - 1));
+      }
+      if (t == target) occ = 1, age = 0, src = L.cand[c];
+    }
+    L.gocc[t] = occ, L.gsrc[t] = src;
+    if (src >= 0) as.gocc[t] = 1, as.gage[t] = 0, as.gid[t] = st.id[src];
+  }
+  __syncthreads();
+  for (int e = t; e < kTrackGallery * kTrackModel; e += 256) {
+    const int g = e / kTrackModel, src = L.gsrc[g];
+    if (src >= 0) as.gmodel[e] = as.model[(size_t)src * kTrackModel + (e - g * kTrackModel)];
+  }
+  __syncthreads();
+}
+
+// Step 7' in the place of step 7's ids, by the whole workgroup: thread q of a person born into my_place (born) -> the person's id; `got`
+// >= 0: re-identified with that gallery entry.  A born person with a valid descriptor keeps its best open entry (smallest A <= reid_max,
+// the lower entry among equals); a round takes the smallest key A | entry | person over the workgroup — an LDS atomic minimum, and a
+// minimum does not depend on arrival order —, gives the person the entry, frees it, and the people whose best it was look again.  At most
+// 64 rounds: every round frees an entry.  The exit test reads LDS behind a barrier: uniform.  Then the ids: the entry's, or next_id + the
+// rank among the born people not re-identified; the models of the born places; next_id; the gallery's occupancy back to the state.
+__device__ __forceinline__ long long appear_births(int b, int P, int n, const TrackAppear& ap, const TrackAppearSlot& as, const TrackSlot& st,
+                                                   bool born, int my_place, long long next_id, int& got) {
+  AppearLds& L = appear_lds();
+  const int t = threadIdx.x;
+  const int* q = ap.qdesc + ((size_t)b * P + t) * kTrackModel;
+  const bool want = born && L.pvalid[t];
+  int best_a = 0, best_e = -1;
+  got = -1;
+  auto look = [&]() {
+    best_e = -1;
+    for (int e = 0; e < kTrackGallery; ++e) {
+      if (!L.gocc[e]) continue;
+      const int a = appear_dissim(as.gmodel + (size_t)e * kTrackModel, q);
+      if (a <= ap.reid_max && (best_e < 0 || a < best_a)) best_a = a, best_e = e;
+    }
+  };
+  if (want) look();
+  for (int round = 0; round < kTrackGallery; ++round) {
+    if (t == 0) L.key = 0xffffffffu;
+    __syncthreads();
+    if (want && got < 0 && best_e >= 0) atomicMin(&L.key, ((unsigned)(best_a + 64) << 14) | ((unsigned)best_e << 8) | (unsigned)t);  // A >= -24
+    __syncthreads();
+    const unsigned key = L.key;
+    if (key == 0xffffffffu) break;  // nobody has an entry left: the same value in every thread
+    const int we = (int)(key >> 8) & (kTrackGallery - 1), wq = (int)(key & 255u);
+    __syncthreads();  // everybody has read the key before it is reset, and gocc before it changes
+    if (t == wq) got = we;
+    if (t == 0) L.gocc[we] = 0;
+    __syncthreads();
+    if (want && got < 0 && best_e == we) look();
+  }
+  __syncthreads();
+  L.flag[t] = (born && got < 0) ? 1 : 0;
+  __syncthreads();
+  long long my_id = -1;
+  if (born) {
+    int* m = as.model + (size_t)my_place * kTrackModel;
+    if (got >= 0) {
+      my_id = as.gid[got];
+      const int* gm = as.gmodel + (size_t)got * kTrackModel;
+      for (int e = 0; e < kTrackModel; ++e) m[e] = appear_blend(gm[e], q[e], ap.alpha256);
+      as.valid[my_place] = 1;
+    } else {
+      int rank = 0;
+      for (int i = 0; i < t; ++i) rank += L.flag[i];
+      my_id = next_id + rank;
+      const int ok = L.pvalid[t];
+      if (ok)
+        for (int e = 0; e < kTrackModel; ++e) m[e] = q[e];
+      as.valid[my_place] = ok;
+    }
+    st.id[my_place] = my_id;
+  }
+  if (t == 0) {
+    int fresh = 0;
+    for (int i = 0; i < n; ++i) fresh += L.flag[i];
+    *st.next_id = next_id + fresh;
+  }
+  if (t < kTrackGallery) as.gocc[t] = L.gocc[t];
+  return my_id;
+}
+
 // One workgroup of 256 threads (4 waves) applies one image to one slot: the body of an update, steps 1-7.  Thread i owns track place i
 // in steps 1, 5 and 6, thread q owns person q in step 7.  D lives in global scratch (256 x 256 doubles do not fit in LDS beside the rest)
 // and is written and read inside this workgroup only, with a barrier in between.
@@ -256,11 +437,13 @@ __device__ __forceinline__ void smooth_image(int b, int P, int n, const TrackPar
 // The state block is read AND written here, and track_kernel calls this several times on one block with a barrier in between: `state`
 // carries no __restrict__, so that nothing loaded from it is kept across that barrier.
 // Smooth (step 8, TrackSmooth): a second parameter for the same reason — the instances without it are the kernels they were.
-template <int Assign, int Smooth>  // the matching rule, TrackParams::assign: the greedy instance is the kernel it was, instruction for instruction
+// Appear (steps 0', 5', 6', 7', TrackAppear): a third one, likewise: everything of it stands behind `if constexpr (Appear == 1)`.
+template <int Assign, int Smooth, int Appear>  // the matching rule, TrackParams::assign: the greedy instance is the kernel it was, instruction for instruction
 __device__ __forceinline__ void track_image(int b, unsigned char* state_block, int P, const TrackParams& tp,
                                             const double* __restrict__ sig2_g, double* __restrict__ dist,
                                             const int* __restrict__ n_people, const double* __restrict__ people,
-                                            long long* __restrict__ ids, int* __restrict__ place, const TrackSmooth& sm, TrackFilter* filt) {
+                                            long long* __restrict__ ids, int* __restrict__ place, const TrackSmooth& sm, TrackFilter* filt,
+                                            const TrackAppear& ap, unsigned char* appear_block) {
   __shared__ double s2[kTrackMax];   // s_i^2
   __shared__ double rv[kTrackMax];   // row minima: value ...
   __shared__ int rq[kTrackMax];      // ... and person, -1 = the row has no allowed entry left
@@ -283,6 +466,11 @@ __device__ __forceinline__ void track_image(int b, unsigned char* state_block, i
   const int n = min(max(n_people[b], 0), P);
   const double* ppl = people + (size_t)b * P * J * 3;
   double* D = dist + (size_t)b * T * kTrackMax;
+  TrackAppearSlot as{};
+  if constexpr (Appear == 1) {
+    as = track_appear_slot(appear_block, T);
+    appear_begin(b, P, n, ap, as);  // 0'
+  }
 
   // 1. track sizes
   if (t < J) sig2[t] = sig2_g[t];
@@ -433,6 +621,7 @@ __device__ __forceinline__ void track_image(int b, unsigned char* state_block, i
     flag[t] = free_now;
   }
   __syncthreads();
+  if constexpr (Appear == 1) appear_tracks(b, P, tp, ap, as, st, live, tm, mult);  // 5', 6'
   // 7. births: the r-th unmatched person takes the r-th free place
   if (flag[t]) {
     int rank = 0;
@@ -462,7 +651,7 @@ __device__ __forceinline__ void track_image(int b, unsigned char* state_block, i
       for (int q = 0; q < t; ++q) rank += flag[q];
       if (rank < nfree) {
         my_place = fplace[rank];
-        my_id = next_id + rank;
+        if constexpr (Appear == 0) my_id = next_id + rank;  // with Appear: step 7', below
         const double* pe = ppl + (size_t)t * J * 3;
         for (int j = 0; j < J; ++j) {
           double* tr = st.pose + ((size_t)my_place * J + j) * 3;
@@ -470,17 +659,25 @@ __device__ __forceinline__ void track_image(int b, unsigned char* state_block, i
           tr[0] = pe[j * 3], tr[1] = pe[j * 3 + 1], tr[2] = pe[j * 3 + 2];
           ve[0] = 0.0, ve[1] = 0.0;
         }
-        st.id[my_place] = my_id;
+        if constexpr (Appear == 0) st.id[my_place] = my_id;
         st.live[my_place] = 1;
         st.misses[my_place] = 0;
         st.hits[my_place] = 1;
       }
     }
   }
-  if (t == 0) {
-    int born = 0;
-    for (int q = 0; q < n; ++q) born += flag[q];
-    *st.next_id = next_id + min(born, nfree);
+  if constexpr (Appear == 0) {
+    if (t == 0) {
+      int born = 0;
+      for (int q = 0; q < n; ++q) born += flag[q];
+      *st.next_id = next_id + min(born, nfree);
+    }
+  } else {  // 7': the ids of the born people, from the gallery or from next_id
+    const bool born = unmatched && my_place >= 0;
+    int got;
+    const long long born_id = appear_births(b, P, n, ap, as, st, born, my_place, next_id, got);
+    if (born) my_id = born_id;
+    if (t < P) ap.reid[(size_t)b * P + t] = got >= 0 ? 1 : 0;
   }
   if (t < P) {
     ids[(size_t)b * P + t] = my_id;
@@ -494,25 +691,27 @@ __device__ __forceinline__ void track_image(int b, unsigned char* state_block, i
 // last stores to the state (steps 5-7) and the next image's loads of it (steps 1-3) by other threads of this workgroup, and between its
 // last readers of the LDS arrays (flag, fplace, pm in step 7) and the next image's initialisation of them.  A workgroup whose slot no
 // image names returns without touching the slot.
-// With Smooth the same barrier stands between an image's stores to the slot's filters (step 8) and the next image's loads of them.
-template <int Assign, int Smooth>
+// With Smooth the same barrier stands between an image's stores to the slot's filters (step 8) and the next image's loads of them, with
+// Appear between its stores to the slot's models and gallery and the next image's loads of those.
+template <int Assign, int Smooth, int Appear>
 __global__ __launch_bounds__(256) void track_kernel(int NB, int P, TrackParams tp, TrackSlotMap map, const double* __restrict__ sig2_g,
                                                     unsigned char* state, size_t slot_stride, double* __restrict__ dist,
                                                     const int* __restrict__ n_people, const double* __restrict__ people,
-                                                    long long* __restrict__ ids, int* __restrict__ place, TrackSmooth sm) {
+                                                    long long* __restrict__ ids, int* __restrict__ place, TrackSmooth sm, TrackAppear ap) {
   const int slot = blockIdx.x;
   unsigned char* block = state + (size_t)slot * slot_stride;
   TrackFilter* filt = Smooth == 1 ? sm.filt + (size_t)slot * tp.T * tp.J : nullptr;
+  unsigned char* appear_block = Appear == 1 ? ap.state + (size_t)slot * ap.slot_stride : nullptr;
   for (int b = 0; b < NB; ++b) {
     if ((int)((map.w[b >> 2] >> ((b & 3) * 8)) & 0xffu) != slot) continue;  // uniform
-    track_image<Assign, Smooth>(b, block, P, tp, sig2_g, dist, n_people, people, ids, place, sm, filt);
+    track_image<Assign, Smooth, Appear>(b, block, P, tp, sig2_g, dist, n_people, people, ids, place, sm, filt, ap, appear_block);
     __syncthreads();
   }
 }
 
 int launch_track(int S, int NB, int P, const TrackParams& p, const double* sig2, unsigned char* state, size_t slot_stride, double* dist,
                  const int* n_people, const double* people, long long* ids, int* place, const TrackSlotMap& map, void* stream,
-                 const TrackSmooth* sm) {
+                 const TrackSmooth* sm, const TrackAppear* ap) {
   if (NB <= 0) return 0;
   if (S < 1 || S > 256 || NB > kTrackMaxImages || P < 1 || P > kTrackMax || p.T < 1 || p.T > kTrackMax || p.J < 1 ||
       p.J > kPeopleMaxJoints || slot_stride % 16 || slot_stride < track_slot_bytes(p.T, p.J) || p.assign < 0 || p.assign > 1)
@@ -520,14 +719,25 @@ int launch_track(int S, int NB, int P, const TrackParams& p, const double* sig2,
   for (int b = 0; b < NB; ++b)
     if ((int)((map.w[b >> 2] >> ((b & 3) * 8)) & 0xffu) >= S) return (int)hipErrorInvalidValue;
   if (sm && (!sm->filt || !sm->smooth || !sm->src || (sm->cand_in && !sm->cand_out) || sm->max_hold < 0)) return (int)hipErrorInvalidValue;
+  if (ap && (!ap->state || !ap->qdesc || !ap->reid || ap->slot_stride % 8 || ap->slot_stride < track_appear_bytes(p.T) || ap->min_pixels < 1 ||
+             ap->alpha256 < 0 || ap->alpha256 > 256 || ap->reid_max < 0 || ap->reid_max > 3 * 4096 || ap->max_age < 0 || ap->max_age > 100000 ||
+             ap->min_hits < 1))
+    return (int)hipErrorInvalidValue;
   const TrackSmooth off{};
-  auto go = [&](auto kernel, const TrackSmooth& s8) {
+  const TrackAppear plain{};
+  auto go = [&](auto kernel, const TrackSmooth& s8, const TrackAppear& a) {
     hipLaunchKernelGGL(kernel, dim3(S), dim3(256), 0, (hipStream_t)stream, NB, P, p, map, sig2, state, slot_stride, dist, n_people, people,
-                       ids, place, s8);
+                       ids, place, s8, a);
   };
-  // step 4' and step 8: instantiations of their own, so that the greedy one without smoothing keeps its registers and its LDS
-  if (sm) p.assign == 1 ? go(track_kernel<1, 1>, *sm) : go(track_kernel<0, 1>, *sm);
-  else p.assign == 1 ? go(track_kernel<1, 0>, off) : go(track_kernel<0, 0>, off);
+  // step 4', step 8 and the appearance steps: instantiations of their own, so that the greedy one without either keeps its registers and
+  // its LDS
+  if (ap) {
+    if (sm) p.assign == 1 ? go(track_kernel<1, 1, 1>, *sm, *ap) : go(track_kernel<0, 1, 1>, *sm, *ap);
+    else p.assign == 1 ? go(track_kernel<1, 0, 1>, off, *ap) : go(track_kernel<0, 0, 1>, off, *ap);
+  } else {
+    if (sm) p.assign == 1 ? go(track_kernel<1, 1, 0>, *sm, plain) : go(track_kernel<0, 1, 0>, *sm, plain);
+    else p.assign == 1 ? go(track_kernel<1, 0, 0>, off, plain) : go(track_kernel<0, 0, 0>, off, plain);
+  }
   return (int)hipGetLastError();
 }
 

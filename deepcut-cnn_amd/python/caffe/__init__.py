@@ -14,6 +14,7 @@ from .pycaffe import draw_people, draw_limits, draw_coefficients, DRAW_JOINT_COL
 from .pycaffe import draw_heatmap, HEAT_LUT  # noqa: F401
 from .pycaffe import redact_people, redact_select, REDACT_DEFAULTS  # noqa: F401
 from .pycaffe import overlay_people_device  # noqa: F401
+from .pycaffe import describe_people, appearance_params, APPEARANCE_DEFAULTS, APPEARANCE_BINS, TRACK_GALLERY  # noqa: F401
 from .pycaffe import label_people, LABEL_FONT, LABEL_CHARS, LABEL_DEFAULTS, LABEL_MAX_CHARS  # noqa: F401
 
 __version__ = "1.0.0-rc3+deepcut_hip"

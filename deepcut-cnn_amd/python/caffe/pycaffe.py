@@ -69,6 +69,12 @@ class TrackSmoothParams(C.Structure):
     _fields_ = [("enabled", C.c_int), ("min_cutoff", C.c_double), ("beta", C.c_double), ("d_cutoff", C.c_double), ("max_hold", C.c_int)]
 
 
+class TrackAppearanceParams(C.Structure):
+    """dc_track_appearance_params (include/deepcut_hip.h)."""
+    _fields_ = [("enabled", C.c_int), ("min_pixels", C.c_int), ("alpha256", C.c_int), ("reid_max", C.c_int), ("max_age", C.c_int),
+                ("min_hits", C.c_int)]
+
+
 # Step 8 of the tracker's rule (`Tracker.smoothing`).  PLACEHOLDERS, NOT TUNED ON REAL VIDEO: override them.  Time counts in updates: a
 # 1 Hz cutoff on 30 fps video is min_cutoff = 1 / 30.
 SMOOTH_DEFAULTS = {"min_cutoff": 0.1, "beta": 4.0, "d_cutoff": 0.03, "max_hold": 3}
@@ -91,6 +97,12 @@ class RedactStyle(C.Structure):
     _fields_ = [("region", C.c_int), ("head_a", C.c_int), ("head_b", C.c_int), ("head_scale", C.c_double), ("body_scale", C.c_double),
                 ("min_radius", C.c_double), ("max_radius", C.c_double), ("min_score", C.c_double), ("n_edges", C.c_int), ("edges", C.c_void_p),
                 ("effect", C.c_int), ("block", C.c_int), ("fill", C.c_ubyte * 3)]
+
+
+class AppearanceStyle(C.Structure):
+    """dc_appearance_style (include/deepcut_hip.h)."""
+    _fields_ = [("size", C.c_size_t), ("n_edges", C.c_int), ("edges", C.c_void_p), ("scale", C.c_double), ("min_radius", C.c_double),
+                ("min_score", C.c_double)]
 
 
 class LabelStyle(C.Structure):
@@ -426,6 +438,11 @@ def _load():
         "dc_draw_people": (ci, [C.POINTER(DcFrame), ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, C.POINTER(DrawStyle), vp]),
         "dc_draw_limits": (ci, [C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]),
         "dc_redact_people": (ci, [C.POINTER(DcFrame), ci, ci, ci, ci, ci, ci, vp, vp, vp, C.POINTER(RedactStyle), vp, vp]),
+        "dc_tracker_set_appearance": (ci, [vp, C.POINTER(TrackAppearanceParams)]),
+        "dc_tracker_get_appearance": (ci, [vp, C.POINTER(TrackAppearanceParams)]),
+        "dc_tracker_update_appearance": (ci, [vp, ci, ci] + [vp] * 10),
+        "dc_tracker_appearance_state": (ci, [vp, ci, vp, vp, vp, vp, vp]),
+        "dc_describe_people": (ci, [C.POINTER(DcFrame), ci, ci, ci, ci, ci, ci, vp, vp, C.POINTER(AppearanceStyle), vp, vp]),
         "dc_overlay_people_device": (ci, [C.POINTER(DcFrame), ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, C.POINTER(DrawStyle), C.POINTER(RedactStyle),
                                           vp, ci, vp, ci, vp, vp]),
         "dc_net_track_frames_async_overlay": (ci, [vp, vp, vp, vp, ci, ci, ci, C.c_double, ci, vp, C.POINTER(AssembleParams), ci, vp, vp, vp, vp,
@@ -805,6 +822,10 @@ class Tracker(object):
     smooth: None / False (off, the default), True (SMOOTH_DEFAULTS: PLACEHOLDERS, NOT TUNED ON REAL VIDEO) or a dict of some of
     min_cutoff, beta, d_cutoff, max_hold — step 8 of the rule: a filter per track and joint on the device smooths the poses and
     bridges joints that vanish for at most max_hold updates; no id, place or distance changes by a bit.  Also the property `smoothing`.
+    appearance: None / False (off, the default), True (APPEARANCE_DEFAULTS: PLACEHOLDERS, NOT TUNED ON REAL VIDEO) or a dict of some of
+    min_pixels, alpha256, reid_max, max_age, min_hits — the appearance steps of the rule (dc_tracker_update_appearance): a freed track's
+    appearance model waits in a gallery, and a person born with a descriptor (`describe_people`, handed to `update(desc=...)`) close
+    enough to it takes the old id back.  Also the property `appearance`.
     Creation needs no device; updates need GPU mode.  The calls of this class are synchronous; updates apply in call order, those
     enqueued by `Net.track_frames_async` included (the synchronous calls wait for them first)."""
 
@@ -812,10 +833,11 @@ class Tracker(object):
     _OPT_ASSIGN = 1  # DC_TRACK_OPT_ASSIGN
 
     def __init__(self, n_joints=14, slots=1, max_tracks=64, sigma=None, max_misses=5, min_common=3, max_dist=0.25, min_size=32.0, motion=1,
-                 assign="greedy", smooth=None):
+                 assign="greedy", smooth=None, appearance=None):
         self._h = None
         self._assign_value(assign)
         smooth = smooth_params(smooth)
+        appearance = appearance_params(appearance)
         sig = None
         if sigma is not None:
             sig = np.ascontiguousarray(sigma, dtype=np.float64).reshape(-1)
@@ -831,6 +853,8 @@ class Tracker(object):
             self.assign = assign
         if smooth is not None:
             self.smoothing = smooth
+        if appearance is not None:
+            self.appearance = appearance
 
     @classmethod
     def _assign_value(cls, assign):
@@ -873,12 +897,36 @@ class Tracker(object):
             raise ValueError("smooth: min_cutoff, beta and d_cutoff must be numbers, max_hold a whole number (%s)" % (e,))
         _check(_lib.dc_tracker_set_smoothing(self._h, C.byref(q)))
 
+    @property
+    def appearance(self):
+        """None (off, the default) or {"min_pixels", "alpha256", "reid_max", "max_age", "min_hits"}: the appearance steps of the rule
+        (dc_tracker_set_appearance).  Assign None / False, True (APPEARANCE_DEFAULTS: PLACEHOLDERS, NOT TUNED ON REAL VIDEO) or a dict of
+        some of the five.  May change between updates: off -> on starts with no model and an empty gallery, a change while on keeps them.
+        A bad value raises DeepcutError naming the field, with or without a device."""
+        q = TrackAppearanceParams()
+        _check(_lib.dc_tracker_get_appearance(self._h, C.byref(q)))
+        if not q.enabled:
+            return None
+        return {k: int(getattr(q, k)) for k in _APPEARANCE_TRACK_KEYS}
+
+    @appearance.setter
+    def appearance(self, appearance):
+        d = appearance_params(appearance)
+        if d is None:
+            _check(_lib.dc_tracker_set_appearance(self._h, None))
+            return
+        try:
+            q = TrackAppearanceParams(1, *[int(d[k]) for k in _APPEARANCE_TRACK_KEYS])
+        except (TypeError, ValueError) as e:
+            raise ValueError("appearance: min_pixels, alpha256, reid_max, max_age and min_hits must be whole numbers (%s)" % (e,))
+        _check(_lib.dc_tracker_set_appearance(self._h, C.byref(q)))
+
     def __del__(self):
         if getattr(self, "_h", None):
             _lib.dc_tracker_destroy(self._h)
             self._h = None
 
-    def update(self, people, n_people=None, return_dist=False, slot_of=None, return_smooth=False):
+    def update(self, people, n_people=None, return_dist=False, slot_of=None, return_smooth=False, desc=None, return_reid=False):
         """people: [nb, P, J, 3] float64 (x, y, score; a joint counts when its score > 0) with n_people [nb] of them valid per image, or
         a list of nb arrays [m_b, J, 3] (n_people is then their lengths) — image b updates slot b.  This is how poses that did not come
         from `track_people` (top-down poses of `forward_boxes`, say) get tracked.
@@ -887,7 +935,10 @@ class Tracker(object):
         -> (ids int64 [nb, P], place int32 [nb, P]): -1 beyond n_people[b] and for a person no track place was free for; with
         return_dist also the distances float64 [nb, max_tracks, P].  return_smooth (needs `smoothing` on, dc_tracker_update_smoothed):
         -> (ids, place[, dist], smooth, src) with smooth float64 [nb, P, J, 3], the smoothed poses, and src int32 [nb, P, J]: 0 nothing,
-        1 observed, 2 bridged."""
+        1 observed, 2 bridged.
+        desc (needs `appearance` on, dc_tracker_update_appearance): int32 [nb, P, 3, 16] as `describe_people` returns it for these people
+        — a person born with a valid descriptor may take an id back from the gallery; return_reid: reid int32 [nb, P] comes last in the
+        tuple, 1 where that happened.  Without desc an update of a tracker with appearance on re-identifies nobody."""
         j = self.n_joints
         if n_people is None and not (isinstance(people, np.ndarray) and people.ndim == 4):
             arrs = [np.asarray(a, np.float64).reshape(-1, j, 3) for a in people]
@@ -907,6 +958,16 @@ class Tracker(object):
         place = np.full((nb, p), -1, np.int32)
         dist = np.zeros((nb, self.max_tracks, p), np.float64) if return_dist else None
         ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        if desc is not None or return_reid:
+            dsc = None if desc is None else np.ascontiguousarray(desc, dtype=np.int32)
+            if dsc is not None and dsc.shape != (nb, p, 3, APPEARANCE_BINS):
+                raise ValueError("desc must be [%d, %d, 3, %d] like people, got shape %s" % (nb, p, APPEARANCE_BINS, dsc.shape))
+            reid = np.zeros((nb, p), np.int32)
+            smooth, src = (np.zeros((nb, p, j, 3), np.float64), np.zeros((nb, p, j), np.int32)) if return_smooth else (None, None)
+            _check(_lib.dc_tracker_update_appearance(self._h, nb, p, None if slot_of is None else ptr(_slot_map(slot_of, nb)), ptr(n), ptr(ppl),
+                                                     ptr(dsc), ptr(ids), ptr(place), ptr(dist), ptr(reid), ptr(smooth), ptr(src)))
+            out = (ids, place) + ((dist,) if return_dist else ()) + ((smooth, src) if return_smooth else ())
+            return out + ((reid,) if return_reid else ())
         if return_smooth:
             smooth, src = np.zeros((nb, p, j, 3), np.float64), np.zeros((nb, p, j), np.int32)
             _check(_lib.dc_tracker_update_smoothed(self._h, nb, p, None if slot_of is None else ptr(_slot_map(slot_of, nb)), ptr(n), ptr(ppl),
@@ -929,6 +990,18 @@ class Tracker(object):
         out = {"ids": np.full(t, -1, np.int64), "misses": np.zeros(t, np.int32), "hits": np.zeros(t, np.int32),
                "poses": np.zeros((t, j, 3), np.float64)}
         _check(_lib.dc_tracker_state(self._h, int(slot), *[out[k].ctypes.data_as(C.c_void_p) for k in ("ids", "misses", "hits", "poses")]))
+        return out
+
+    def appearance_state(self, slot=0):
+        """The appearance models of a slot (dc_tracker_appearance_state) -> dict: "track_model" int32 [T, 3, 16] and "track_valid" int32
+        [T] (zeros for a place that is free or has no valid model); "gallery_ids" int64 [64] and "gallery_age" int32 [64] (-1 = free
+        entry), "gallery_model" int32 [64, 3, 16].  All empty with appearance off."""
+        t = self.max_tracks
+        out = {"track_model": np.zeros((t, 3, APPEARANCE_BINS), np.int32), "track_valid": np.zeros(t, np.int32),
+               "gallery_ids": np.full(TRACK_GALLERY, -1, np.int64), "gallery_age": np.full(TRACK_GALLERY, -1, np.int32),
+               "gallery_model": np.zeros((TRACK_GALLERY, 3, APPEARANCE_BINS), np.int32)}
+        _check(_lib.dc_tracker_appearance_state(self._h, int(slot), *[out[k].ctypes.data_as(C.c_void_p) for k in
+                                                                      ("track_model", "track_valid", "gallery_ids", "gallery_age", "gallery_model")]))
         return out
 
     def smooth_state(self, slot=0):
@@ -1112,10 +1185,10 @@ def _per_image(v, dtype, tail):
     return out
 
 
-def _frames_and_people(frames, people, n_people):
+def _frames_and_people(frames, people, n_people, writable=True):
     """What `draw_people` and `redact_people` take as frames and people -> (dc_frame[nb], nb, h, w, is_device, what to keep alive,
-    people float64 [nb, P, J, 3], n_people int32 [nb], P, J)."""
-    arr, nb, h, w, is_device, keep = _writable_frames(frames)
+    people float64 [nb, P, J, 3], n_people int32 [nb], P, J).  writable=False (`describe_people`): the frames are only read."""
+    arr, nb, h, w, is_device, keep = _writable_frames(frames, writable)
     if isinstance(people, np.ndarray) and people.ndim in (3, 4):
         if people.shape[-1] != 3:
             raise ValueError("people must be [m, J, 3] or [nb, P, J, 3] (x, y, score), got shape %s" % (people.shape,))
@@ -1285,6 +1358,59 @@ def redact_people(frames, people, n_people=None, select=None, ids=None, only_ids
     out = np.zeros((nb, p), np.int32)
     ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
     _check(_lib.dc_redact_people(arr, nb, h, w, int(is_device), p, j, ptr(n), ptr(ppl), ptr(sel), C.byref(st), ptr(out), _stream_arg(stream)))
+    return out[0, :people.shape[0]] if single else out
+
+
+# ---- appearance descriptors of people (dc_describe_people; the rule: include/deepcut_hip.h — this project's own, the reference has none) --
+# PLACEHOLDERS, NOT TUNED ON REAL VIDEO: override them.  A capsule's radius is `scale` times the larger side of the person's bounding
+# box, at least min_radius pixels (and 64 pixels at the most).
+# Of the tracker's appearance steps (`Tracker.appearance`): a descriptor needs min_pixels region pixels, a new observation weighs
+# alpha256 / 256 in a track's model, a dissimilarity of at most reid_max (of 12288) re-identifies, a freed track with at least min_hits hits
+# waits max_age updates in the gallery.  PLACEHOLDERS, NOT TUNED ON REAL VIDEO, like the rest.
+APPEARANCE_DEFAULTS = {"scale": 0.04, "min_radius": 2.0, "min_score": 0.0, "min_pixels": 64, "alpha256": 64, "reid_max": 4096, "max_age": 300,
+                       "min_hits": 5}
+APPEARANCE_BINS = 16  # DC_APPEARANCE_BINS
+TRACK_GALLERY = 64  # DC_TRACK_GALLERY
+_APPEARANCE_TRACK_KEYS = ("min_pixels", "alpha256", "reid_max", "max_age", "min_hits")  # dc_track_appearance_params, in its order
+
+
+def appearance_params(appearance, keys=_APPEARANCE_TRACK_KEYS):
+    """An `appearance=` argument / an `appearance` value -> the dict of the parameters `keys` (the tracker's five by default), or None
+    for off.  None and False are off, True is APPEARANCE_DEFAULTS (PLACEHOLDERS, not tuned on real video), a dict overrides some of them.
+    The values themselves are checked by the library (dc_tracker_set_appearance, dc_describe_people)."""
+    if appearance is None or appearance is False:
+        return None
+    if appearance is True:
+        appearance = {}
+    if not isinstance(appearance, dict):
+        raise TypeError("appearance must be None, True or a dict of %s, got %r" % (sorted(keys), appearance))
+    unknown = sorted(set(appearance) - set(keys))
+    if unknown:
+        raise ValueError("appearance: unknown keys %r (known: %s)" % (unknown, sorted(keys)))
+    return dict({k: APPEARANCE_DEFAULTS[k] for k in keys if k in APPEARANCE_DEFAULTS}, **appearance)
+
+
+def describe_people(frames, people, n_people=None, edges=None, scale=APPEARANCE_DEFAULTS["scale"], min_radius=APPEARANCE_DEFAULTS["min_radius"],
+                    min_score=APPEARANCE_DEFAULTS["min_score"], stream=None):
+    """What people look like, counted from frames on the device (dc_describe_people; the rule — integer only, this project's own: the
+    reference stops at the maps — is in include/deepcut_hip.h): per person, the pixels under the capsules of the limbs `edges` ([E, 2]
+    joints: the torso's — `pose.describe_people` has the MPII ones; None = none, so all zeros), of radius `scale` times the larger side
+    of the person's bounding box and at least min_radius pixels, and per channel (BGR24: B, G, R; NV12: Y, Cb, Cr) a histogram of their
+    bytes in 16 bins of 16 values.  The defaults (APPEARANCE_DEFAULTS) are PLACEHOLDERS, not tuned on real video.  Only joints with
+    score > min_score count.
+    frames and people / n_people: as `redact_people` takes them, but the frames are ONLY READ and need not be writable.
+    -> int32 [m, 3, 16] for one frame's [m, J, 3], else [nb, P, 3, 16]: each channel's counts sum to the pixels of the person's region,
+    0 for a person without a held limb or wholly outside the frame.
+    stream: a HIP stream for device frames (None: the library's own).  The call returns when the counts are complete.  Needs GPU mode."""
+    single = isinstance(people, np.ndarray) and people.ndim == 3
+    arr, nb, h, w, is_device, _keep, ppl, n, p, j = _frames_and_people(frames, people, n_people, writable=False)
+    e = _edges_array(edges)
+    st = AppearanceStyle()
+    st.size, st.n_edges, st.edges = C.sizeof(AppearanceStyle), int(e.shape[0]), e.ctypes.data if e.shape[0] else None
+    st.scale, st.min_radius, st.min_score = float(scale), float(min_radius), float(min_score)
+    out = np.zeros((nb, p, 3, APPEARANCE_BINS), np.int32)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    _check(_lib.dc_describe_people(arr, nb, h, w, int(is_device), p, j, ptr(n), ptr(ppl), C.byref(st), ptr(out), _stream_arg(stream)))
     return out[0, :people.shape[0]] if single else out
 
 
@@ -1505,9 +1631,9 @@ _HEAT_MODES = {"max": 0, "joints": 1}  # DC_HEAT_MAX, DC_HEAT_BY_JOINT
 _HEAT_ALPHA_MODES = {"const": 0, "score": 1}  # DC_HEAT_ALPHA_CONST, DC_HEAT_ALPHA_SCORE
 
 
-def _writable_frames(frames):
+def _writable_frames(frames, writable=True):
     """frames of the calls that write into them (`draw_people`, `redact_people`, `draw_heatmap`) -> (dc_frame[nb], nb, h, w, is_device,
-    what to keep alive)."""
+    what to keep alive).  writable=False: of a call that only reads them (`describe_people`), so a read-only host array will do."""
     fl = _frame_list(frames)
     if fl is None:
         if isinstance(frames, np.ndarray) and frames.ndim == 3:
@@ -1516,7 +1642,7 @@ def _writable_frames(frames):
             raise ValueError("frames must be a caffe.Frame, a non-empty list of them, or a uint8 [H, W, 3] BGR array")
     for i, f in enumerate(fl):
         for a in f._keep:
-            if isinstance(a, np.ndarray) and not a.flags.writeable:
+            if writable and isinstance(a, np.ndarray) and not a.flags.writeable:
                 raise ValueError("frame %d: a host array that is drawn into must be writable" % i)
     arr, h, w, is_device = _frame_array(fl)
     return arr, len(fl), h, w, is_device, fl

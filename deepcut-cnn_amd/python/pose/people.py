@@ -19,6 +19,9 @@ MIRROR_MPII14 = (5, 4, 3, 2, 1, 0, 11, 10, 9, 8, 7, 6, 12, 13)
 SKELETON_MPII14 = ((0, 1), (1, 2), (2, 3), (3, 4), (4, 5), (6, 7), (7, 8), (8, 12), (12, 9), (9, 10), (10, 11), (12, 13), (2, 8), (3, 9))
 # The joint pair `redact_people` places the head disc on: (upper neck, head top).  The caller's to override (`head=`) likewise.
 HEAD_MPII14 = (12, 13)
+# The limbs `describe_people` samples a person's appearance under: shoulder to hip on either side, the shoulder line and the hip line.
+# The caller's to override (`edges=`) likewise.
+TORSO_MPII14 = ((8, 2), (9, 3), (8, 9), (2, 3))
 
 
 def _get_model(model_def, model_bin):
@@ -131,6 +134,18 @@ def redact_people(frame, people, ids=None, **style):
     return _caffe.redact_people(frame, _np.asarray(people, _np.float64), ids=ids, **style)
 
 
+def describe_people(frame, people, **style):
+    """What people look like, counted from a frame on the device: `caffe.describe_people` with the MPII torso (`TORSO_MPII14`) for
+    `edges` unless the caller names another.  frame: a uint8 [H, W, 3] BGR array or a `caffe.Frame` (NV12 / BGR24, host or device), only
+    read; people: [m, J, 3] as `estimate_people` / `track_people` return them; style: what `caffe.describe_people` takes (edges, scale,
+    min_radius, min_score, stream; the defaults, `caffe.APPEARANCE_DEFAULTS`, are PLACEHOLDERS, not tuned on real video).
+    -> int32 [m, 3, 16].  PARITY UNPINNED BY THE REFERENCE: the rule is this project's own (include/deepcut_hip.h, dc_describe_people)."""
+    import caffe as _caffe
+
+    style.setdefault("edges", TORSO_MPII14)
+    return _caffe.describe_people(frame, _np.asarray(people, _np.float64), **style)
+
+
 def label_people(frame, people, ids=None, **style):
     """Write people's ids into a frame IN PLACE on the device: `caffe.label_people`.  frame, people: as `draw_people` takes them; ids:
     int64 [m] as `track_people` returns them, or None (the people's indices are written); an id < 0 gets no label.  style: what
@@ -176,7 +191,7 @@ def _draw_style(draw):
 
 
 def track_people(frames, model_def, model_bin, stats, tracker=None, depth=1, batch=1, assign="greedy", smooth=None, draw=None, redact=None,
-                 in_chain=False, labels=None, **kw):
+                 in_chain=False, labels=None, appearance=None, **kw):
     """`estimate_people` over the frames of a video, with identities: a generator over an iterable of images (HxWx3 BGR uint8) or
     `caffe.Frame`s that yields, per frame, (people float64 [m, J, 3], ids int64 [m]) — the same person keeps their id from frame to
     frame, -1 marks a person no track place was free for.  kw: what `estimate_people` takes (scale / scales / base / flip / joint_mirror /
@@ -203,8 +218,16 @@ def track_people(frames, model_def, model_bin, stats, tracker=None, depth=1, bat
     the request (`deepcut_tools.VideoPipeline(in_chain=True)`, whatever depth and batch are): the frames are written inside the
     asynchronous chain on the device — the same bytes, the same (people, ids).  A redact dict with `select` raises ValueError then.
     labels: None (off: nothing is added to the run), True or a dict of what `label_people` takes — every frame gets the ids being yielded
-    written over the redaction and the skeletons; with in_chain=True a dict with `texts` or `stream` raises ValueError."""
+    written over the redaction and the skeletons; with in_chain=True a dict with `texts` or `stream` raises ValueError.
+    appearance: None (off: exactly the calls of today), True or a dict of some of edges, scale, min_radius, min_score (what
+    `describe_people` takes; edges None = `TORSO_MPII14`) and min_pixels, alpha256, reid_max, max_age, min_hits (what `caffe.Tracker`'s
+    `appearance` takes) — a person who left for longer than max_misses frames and comes back looking the same takes their old id back.
+    THE DEFAULTS (`caffe.APPEARANCE_DEFAULTS`) ARE PLACEHOLDERS, NOT TUNED ON REAL VIDEO.  Per frame: the forward, `assemble_people`
+    (completion and dedupe as today), `describe_people` on the frame as it came (before any overlay), then `Tracker.update(people,
+    desc=...)`; with smoothing on the smoothed poses are yielded.  A tracker of the caller's has its `appearance` set from the dict's
+    tracker keys.  The synchronous route only: with depth > 1, batch > 1 or in_chain=True it raises ValueError."""
     style = _draw_style(draw)
+    app = _appearance_args(appearance)
     rstyle = None if redact is None or redact is False else _redact_style(redact)
     lstyle = _label_style(labels)
     args = dict(scale=1.0, net=None, scales=None, base=None, flip=False, joint_mirror=MIRROR_MPII14, sparse=False)
@@ -212,6 +235,9 @@ def track_people(frames, model_def, model_bin, stats, tracker=None, depth=1, bat
         if k in args:
             args[k] = kw.pop(k)
     in_chain = bool(in_chain) and (style is not None or rstyle is not None or lstyle is not None)
+    if app is not None and (int(depth) != 1 or int(batch) != 1 or in_chain):
+        raise ValueError("track_people: appearance= runs on the synchronous route only (depth=1, batch=1, not in_chain): got depth=%r, batch=%r, "
+                         "in_chain=%r" % (depth, batch, in_chain))
     if int(depth) != 1 or int(batch) != 1 or in_chain:
         if args["scales"] is not None or args["flip"]:
             raise ValueError("track_people: depth > 1 / batch > 1 / in_chain run one forward per frame; a pyramid (scales= / flip=True) has no "
@@ -228,8 +254,11 @@ def track_people(frames, model_def, model_bin, stats, tracker=None, depth=1, bat
             import caffe as _caffe
 
             tracker = _caffe.Tracker(n_joints=len(MIRROR_MPII14), assign=assign, smooth=smooth)
-        d = _people_of_image(tracker, image, model_def, model_bin, stats, args["scale"], args["net"], args["scales"], args["base"], args["flip"],
-                             args["joint_mirror"], args["sparse"], kw)
+        if app is not None:
+            d = _people_by_appearance(tracker, app, image, model_def, model_bin, stats, args, kw)
+        else:
+            d = _people_of_image(tracker, image, model_def, model_bin, stats, args["scale"], args["net"], args["scales"], args["base"], args["flip"],
+                                 args["joint_mirror"], args["sparse"], kw)
         if rstyle is not None:
             redact_people(image, d["people"], d["ids"], **rstyle)
         if style is not None:
@@ -237,6 +266,47 @@ def track_people(frames, model_def, model_bin, stats, tracker=None, depth=1, bat
         if lstyle is not None:
             label_people(image, d["people"], d["ids"], **lstyle)
         yield d["people"], d["ids"]
+
+
+_APPEARANCE_STYLE_KEYS = ("edges", "scale", "min_radius", "min_score")
+
+
+def _appearance_args(appearance):
+    """appearance= of `track_people` -> None (off) or (the style dict of `describe_people`, the dict `caffe.Tracker.appearance` takes)."""
+    if appearance is None or appearance is False:
+        return None
+    import caffe as _caffe
+
+    track_keys = ("min_pixels", "alpha256", "reid_max", "max_age", "min_hits")
+    both = _caffe.appearance_params(appearance, _APPEARANCE_STYLE_KEYS + track_keys)  # the refusal of an unknown key
+    style = {k: both[k] for k in _APPEARANCE_STYLE_KEYS if k in both}
+    if style.get("edges") is None:
+        style["edges"] = TORSO_MPII14
+    return style, {k: both[k] for k in track_keys}
+
+
+def _people_by_appearance(tracker, app, image, model_def, model_bin, stats, args, assembly):
+    """One frame of `track_people(appearance=...)` -> the dict `Net.track_people` would give: the people without a tracker, their
+    descriptors from the frame, then the tracker's update with them."""
+    import caffe as _caffe
+
+    style, params = app
+    if tracker.appearance != params:
+        tracker.appearance = params
+    d = _people_of_image(None, image, model_def, model_bin, stats, args["scale"], args["net"], args["scales"], args["base"], args["flip"],
+                         args["joint_mirror"], args["sparse"], assembly)
+    people, cand = _np.ascontiguousarray(d["people"], dtype=_np.float64), _np.array(d["cand"], _np.int32)
+    m = people.shape[0]
+    ppl, desc = _np.zeros((1, max(m, 1)) + people.shape[1:], _np.float64), _np.zeros((1, max(m, 1), 3, _caffe.APPEARANCE_BINS), _np.int32)
+    if m:  # a frame without people still updates the tracker: its tracks miss, the gallery ages
+        ppl[0], desc[0] = people, _caffe.describe_people(image, people, **style)
+    smoothed = tracker.smoothing is not None
+    out = tracker.update(ppl, n_people=[m], desc=desc, return_smooth=smoothed)
+    ids, place = out[0][0, :m], out[1][0, :m]
+    if smoothed:
+        people, src = out[2][0, :m], out[3][0, :m]
+        cand[src == 2] = -3
+    return dict(d, people=people, cand=cand, ids=ids, place=place)
 
 
 def _track_in_flight(frames, model_def, model_bin, stats, tracker, depth, batch, args, assembly, assign="greedy", smooth=None, style=None, rstyle=None):

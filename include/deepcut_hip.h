@@ -812,7 +812,7 @@ int dc_group_flops(dc_group* group, double* out);
  *  6. Unmatched live track.  misses += 1; pose and velocity stay; the track is freed when misses > max_misses.
  *  7. Births.  The unmatched people, q ascending, take the free places, place index ascending (places freed in step 6 of this update
  *     count as free): id = next_id++, hits = 1, misses = 0, vel = 0.  A person for whom no place is free gets id -1 and is not
- *     tracked.  Ids are never reused within a slot.
+ *     tracked.  Ids are never reused within a slot (the opt-in appearance steps below give a RETURNING person their old id back: step 7').
  *  8. Smoothed poses, OPT-IN (dc_tracker_set_smoothing; off by default, and nothing above changes by a bit when it is off or on).
  *     PARITY UNPINNED BY THE REFERENCE, like the rest of the tracker: the reference stops at the maps; tests/smooth_ref.py restates this
  *     step in float64 loops.  The raw assembly result jitters from frame to frame, and a joint that falls below the threshold for one
@@ -959,6 +959,65 @@ int dc_tracker_smooth_state(dc_tracker* tracker, int slot, double* poses /* [T][
 int dc_net_track_people(dc_net* net, dc_tracker* tracker, const dc_assemble_params* p, int n_edges, const int* edges, const double* mean,
                         const double* stdev, const int* joint_order, int* n_people, double* people, int* cand, double* cost,
                         long long* ids, int* place);
+/* ---- the tracker's appearance steps: a returning person takes their old id, OPT-IN (off by default) ----------------------------------
+ * PARITY UNPINNED BY THE REFERENCE, like the rest of the tracker; the rule is this project's own, and tests/appear_ref.py restates it.
+ * Steps 6 and 7 above free a track after max_misses updates and never reuse an id, so a person who walks behind a pillar for two
+ * seconds comes back as a new person.  With appearance on, a freed track's appearance model waits in a gallery for a while, and a
+ * person who is born with a descriptor (dc_describe_people, below) close enough to an entry takes that entry's id.  The rule is ALL
+ * INTEGER.  Steps 1-7 and 8 are untouched: place, dist, the tracks' poses and everything step 8 returns are bit for bit what they are
+ * without it; only ids and next_id differ, and only from the first re-identification on.  With appearance off nothing changes by a bit,
+ * and the kernels are the ones a tracker without it ran.
+ *   Quantised descriptor.  A descriptor h[3][16] with n = sum_k h[0][k] >= min_pixels is VALID; then q[c][k] = (4096 * h[c][k] + n / 2) / n
+ *     in int64, integer division.  Rounding lets a channel of q sum to 4096 +- 8.
+ *   Dissimilarity.  A(m, q) = 12288 - sum_c sum_k min(m[c][k], q[c][k]), an int; it may be as low as -24, and nothing depends on its sign.
+ *   Model update.  m += ((q - m) * alpha256 + 128) >> 8 per element, the shift arithmetic; the first valid observation sets m = q.
+ *   State per slot, beside the tracks: model[T][48] and valid[T]; a gallery of DC_TRACK_GALLERY = 64 entries, each (id, age, model[48]).
+ *   0'. At the start of an image's update every occupied gallery entry gets age += 1 and is freed when age > max_age.
+ *   5'. A track matched in step 5 whose person has a valid descriptor updates its model.
+ *   6'. The tracks freed by step 6 in this update, place ascending, that have hits >= min_hits and a valid model enter the gallery with
+ *       age 0, one after the other: each into the lowest free entry; with none free it replaces the entry of largest age, the lower
+ *       index among equals.
+ *   7'. INSTEAD of step 7's ids.  The places are step 7's.  Among the unmatched people who receive a place and have a valid descriptor:
+ *       while such a person and an occupied entry with A(entry.model, q) <= reid_max remain, the pair with the smallest A is taken — ties
+ *       go to the lower entry index, then to the lower person, step 4's idiom.  The person's new track takes the entry's id, its model is
+ *       the entry's updated with q, the entry is freed, reid = 1.  Every other born person takes next_id + (their rank among the born
+ *       people not re-identified, q ascending), and next_id advances by that count; their model is q when valid, else not valid.
+ *       hits = 1, misses = 0, vel = 0 as in step 7, and step 8's filters are cleared as on any birth.  Entries pushed by step 6' of the
+ *       same update take part.
+ *   Invariants: an id is live at most once, and is never in the gallery while live.
+ *   An update without descriptors — the older update entries, the chained entries, or desc == NULL — counts everyone's descriptor as not
+ *   valid: steps 0' and 6' still run, nobody is re-identified, and the ids are the plain rule's.
+ * dc_tracker_set_appearance / dc_tracker_get_appearance: the switch and parameters; NULL (or enabled == 0) is off.  They need no device
+ *     and order themselves like dc_tracker_set_smoothing.  Off -> on starts with no model and an empty gallery; a parameter change
+ *     while on keeps them; dc_tracker_reset clears the slot's.  A bad value is DC_EINVAL naming the field.  The state is a device
+ *     allocation of its own, made at the first update with appearance on, as the filters of step 8 are.  THE DEFAULTS THE PYTHON LAYER
+ *     CHOOSES ARE PLACEHOLDERS, NOT TUNED ON REAL VIDEO.
+ * dc_tracker_update_appearance: dc_tracker_update_slots plus desc[nb][P][3][16] (host, as dc_describe_people returns it; may be NULL)
+ *     and reid[nb][P] (1: the person took an id from the gallery; may be NULL); smooth and src as dc_tracker_update_smoothed, NULL when
+ *     smoothing is off.  DC_EINVAL when appearance is off, or when smooth / src are given with smoothing off.
+ * dc_tracker_appearance_state: track_model[T][48] and track_valid[T] (zeros for a place that is free or has no valid model),
+ *     gallery_ids[64], gallery_age[64] (-1 for a free entry) and gallery_model[64][48] (zeros likewise); any may be NULL.  Synchronous
+ *     like dc_tracker_state.
+ * Not built, on purpose: descriptors inside the chained and asynchronous entries, an appearance term inside the distance of step 3,
+ *     learned embeddings.                                                                                                          */
+typedef struct dc_track_appearance_params {
+  int enabled;      /* 0 / 1: the switch */
+  int min_pixels;   /* >= 1: a descriptor with fewer region pixels is not valid */
+  int alpha256;     /* 0..256: weight of a new observation in the model */
+  int reid_max;     /* 0..12288: largest dissimilarity that re-identifies */
+  int max_age;      /* 0..100000: updates a freed track stays in the gallery */
+  int min_hits;     /* >= 1: hits a freed track needs to enter the gallery */
+} dc_track_appearance_params;
+#define DC_TRACK_GALLERY 64
+int dc_tracker_set_appearance(dc_tracker* tracker, const dc_track_appearance_params* p /* NULL: off */);
+int dc_tracker_get_appearance(dc_tracker* tracker, dc_track_appearance_params* out);
+int dc_tracker_update_appearance(dc_tracker* tracker, int nb, int P, const int* slot_of /* [nb], NULL: image b -> slot b */,
+                                 const int* n_people, const double* people,
+                                 const int* desc /* host [nb][P][3][16], may be NULL: nobody has a valid descriptor */, long long* ids,
+                                 int* place, double* dist, int* reid /* [nb][P], may be NULL */, double* smooth /* [nb][P][J][3] */,
+                                 int* src /* [nb][P][J] */);
+int dc_tracker_appearance_state(dc_tracker* tracker, int slot, int* track_model /* [T][48] */, int* track_valid /* [T] */,
+                                long long* gallery_ids /* [64] */, int* gallery_age /* [64] */, int* gallery_model /* [64][48] */);
 int dc_group_track_people(dc_group* group, dc_tracker* tracker, const double* scales, int base, const dc_fuse_mirror* fm /* may be NULL */,
                           const dc_assemble_params* p, int n_edges, const int* edges, const double* mean, const double* stdev,
                           const int* joint_order, int* n_people, double* people, int* cand, double* cost, long long* ids, int* place);
@@ -1442,6 +1501,47 @@ int dc_net_track_frames_async_styles(dc_net* net, dc_tracker* tracker /* NULL: p
                                      const int* slot_of, const dc_assemble_params* p, int n_edges, const int* edges, const double* mean,
                                      const double* stdev, const int* joint_order, int* n_people, double* people, int* cand, long long* ids,
                                      int* place, const dc_overlay_styles* styles, int* redacted /* host [n][max_people], may be NULL */);
+
+/* ---- appearance descriptors: what a person looks like, counted from a BGR24 or NV12 frame on the device ------------------------------
+ * PARITY UNPINNED BY THE REFERENCE, which stops at the maps.  THE RULE below is this project's own, like the redaction rule it borrows
+ * from.  It is integer only, so every path gives the same counts (tests/appear_ref.py restates it in numpy; the device is held to that
+ * exactly, and to leaving every frame byte, pitch padding included, as it was).
+ *
+ * Input: frames, people[nb][P][J][3] and n_people[nb] as dc_redact_people takes them; a style.  Output: desc[nb][P][3][16] (host ints),
+ *   ALL of it written: zeros for p >= n_people[b], for a person with no primitive, and for a region that lies outside the frame.
+ * Which joints are held, and how they are snapped: exactly as in dc_redact_people — x, y and score finite and score > min_score; clamped
+ *   to [-32768, 32768] pixels, then q = (int)rint(16 v).
+ * The region of person p: a capsule for every limb of style->edges whose two joints are held (the torso's sides, say); there are no
+ *   joint discs.  The radius is the redaction's body radius, r16 = clamp(rint(scale * s16), rint(16 min_radius), 1024), s16 (an int) the
+ *   larger side of the bounding box of the person's held joints in snapped units; a radius of 0 makes no primitive.  0 <= min_radius <= 64
+ *   pixels, so the cap of 1024 units never meets a larger lower bound.
+ * Region pixels: an in-frame pixel (x, y) belongs to the region when its centre (16 x + 8, 16 y + 8) is covered, by the drawing rule's
+ *   capsule test in int64, by ANY of that person's capsules.  A pixel counts once per person however many of the person's capsules cover
+ *   it, and once for each of several people whose regions overlap.
+ * Per region pixel, three bytes c0, c1, c2 — BGR24: B, G, R; NV12: Y(x, y), and Cb, Cr of the sample (x >> 1, y >> 1) — and
+ *   desc[b][p][c][v >> 4] += 1 for each.  So each channel's 16 counts sum to the region's pixel count n (at most 2^28: the frame's).
+ *   The result is a sum of integers: it does not depend on the order of people, primitives or tiles.
+ * Frames are read-only here: no frame byte is stored, host frames are staged up (only those a primitive reaches) and nothing is copied
+ *   back but desc.  A call whose regions reach no frame launches nothing.
+ *
+ * dc_describe_people: stand-alone like dc_redact_people — no net, people as host arrays, frames in host (is_device = 0) or device
+ *   memory, the counting on the device either way; the limits of nb, height, width, P, J and n_edges are dc_draw_people's.  The call
+ *   returns when desc is complete: on `stream`, or on the library's utility stream when it is NULL.  One launch: only tiles some
+ *   capsule's bounding box touches (one workgroup each), desc zeroed on the same stream in front of it.  style->size is
+ *   sizeof(dc_appearance_style) as the CALLER compiled it, as dc_overlay_styles.size.
+ * Errors, before any device work: DC_EINVAL naming the field for everything dc_redact_people refuses of frames, nb, height, width, P, J,
+ *   n_people and edges; a NULL style, or a size smaller than the struct's first version (through min_score); scale not finite or < 0;
+ *   min_radius outside [0, 64]; min_score not finite or < 0.  Then DC_ENOCPU in CPU mode (there is no CPU path).
+ * Not built, on purpose: descriptors inside the asynchronous video chain, learned embeddings, per-box geometry.  The tracker's use of
+ *   the descriptor is dc_tracker_update_appearance, above.  The descriptor is a coarse colour histogram: it tells a red coat from a blue one, not two people in grey.            */
+#define DC_APPEARANCE_BINS 16
+typedef struct dc_appearance_style {
+  size_t size;                              /* sizeof(dc_appearance_style) of the caller */
+  int n_edges; const int* edges;            /* [n_edges][2] 0-based joints, 0..128: the limbs sampled (the torso) */
+  double scale, min_radius, min_score;      /* scale finite, >= 0; min_radius in pixels, 0..64; min_score finite, >= 0 */
+} dc_appearance_style;
+int dc_describe_people(const dc_frame* frames, int nb, int height, int width, int is_device, int P, int J, const int* n_people,
+                       const double* people, const dc_appearance_style* style, int* desc /* host [nb][P][3][16] */, void* stream);
 
 /* ---- in-process multi-GPU forward (SURVEY 8(b)'s dc_forward_batch) -------------------------------------------------------
  * A communicator over `nexec` executors: executor k runs on devices[k] (NULL: k modulo the visible devices) on a host thread of its
